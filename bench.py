@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the wavefront integrator, one JSON line per run (contract in the task description).
 
-    python bench.py [--config cornell|mesh82k|atrium|mesh328k|mixed|spheres] [--gpus N] [--steps K] [--warmup W] [--spp S]
+    python bench.py [--config cornell|mesh82k|atrium|mesh328k|mixed|spheres] [--gpus N] [--steps K] [--warmup W] [--spp S] [--full] [--dump-outputs DIR]
 
 Default: BASELINE.json configs[1], the configuration the metric is quoted on — the Cornell-class scene at 1920x1080, 256 spp,
 depth 8; one "step" = one complete render of the frame with the scene already resident in HBM.  The other names are the other
@@ -17,12 +17,18 @@ data-path collective while rendering) and each step ends with one RCCL gather of
 `value` = rays that ENTER a traversal kernel per second (whole job).  The reference's call-site count (integrator.rs:179,56,100,103;
 SURVEY 8d: what the CPU baseline counts) is `config.cast_Mray_per_s`; the difference is camera rays answered by the projection of the
 world's root box and BSDF-sampled NEE rays answered by the lights' root-box test in the shading pass (`config.rays_by_class`).
+
+A plain run sets up, warms up, times the steps and prints the line.  `--full` adds what takes work of its own after the timed steps: the
+per-kernel times (`kernel_ms`, two extra untimed renders), the CPU baseline (`cpu_baseline`) and the rooflines (`roofline`, `roofline_shade`).
+`--dump-outputs DIR` writes the frame the last timed step left on the device as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import json
 import os
 import sys
 import time
+
+import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -82,6 +88,39 @@ def _profile(config):
         return None, None
 
 
+DUMP_LIMIT_BYTES = 64_000_000   # all of --dump-outputs together
+DUMP_FULL_FRAME_BYTES = 40_000_000   # the accumulation is written whole up to this size (1920x1080: 33 MB), else at the sampled pixels
+DUMP_SAMPLE_PIXELS = 1 << 19
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(out_dir, accumulation, position=None, ident=None):
+    """The frame a caller of the timed path receives, as <out_dir>/<name>.npy:
+        accumulation    float32 (H, W, 4): per pixel the sum of rgb and the sample count; (S, 4) at `sampled_pixels` when the whole frame
+                        is larger than DUMP_FULL_FRAME_BYTES
+        sampled_pixels  float64 (S,): flat row-major pixel indices, every pixel up to DUMP_SAMPLE_PIXELS, else a fixed seeded sample of them
+        position        float32 (S, 4) at `sampled_pixels`: the last sample's first-hit position (one-rank runs)
+        ident           float64 (S,) at `sampled_pixels`: the id history, u32 values (one-rank runs)
+    The sample depends on the frame size only, so two builds of the project dump the same pixels for the same arguments."""
+    h, w = accumulation.shape[:2]
+    n = h * w
+    if n <= DUMP_SAMPLE_PIXELS:
+        idx = np.arange(n)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, DUMP_SAMPLE_PIXELS, replace=False))
+    acc = np.ascontiguousarray(accumulation, np.float32)
+    out = {"accumulation": acc if acc.nbytes <= DUMP_FULL_FRAME_BYTES else acc.reshape(n, 4)[idx], "sampled_pixels": idx.astype(np.float64)}
+    if position is not None:
+        out["position"] = np.ascontiguousarray(position, np.float32).reshape(n, 4)[idx]
+    if ident is not None:
+        out["ident"] = np.ascontiguousarray(ident).reshape(n)[idx].astype(np.float64)
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_LIMIT_BYTES, total
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", choices=sorted(CONFIGS), default="cornell")
@@ -91,9 +130,11 @@ def main():
     ap.add_argument("--spp", type=int, default=None)
     ap.add_argument("--batch-spp", type=int, default=0)
     ap.add_argument("--pipelines", type=int, default=0, help="wavefront pipelines (0: the library's choice; 1: one batch after another, what the profile passes use so that kernel durations do not overlap)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-ms", action="store_true", help="skip the extra untimed step that times every kernel category (profiling runs: counters then cover the timed steps only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
+    ap.add_argument("--no-kernel-ms", action="store_true", help="with --full: skip the extra untimed step that times every kernel category (profiling runs: counters then cover the timed steps only)")
     ap.add_argument("--time-all-kernels", action="store_true", help="HIP events around every launch INSIDE the timed region (diagnostic, slower)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also kernel_ms (two extra untimed renders), the CPU baseline and the rooflines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the frame of the last timed step as DIR/<name>.npy (float32 / float64, at most 64 MB)")
     args = ap.parse_args()
     cfg = CONFIGS[args.config]
     width, height, spp_own, spp_default, depth, what = cfg[2], cfg[3], cfg[4], cfg[5], cfg[6], cfg[7]
@@ -101,6 +142,8 @@ def main():
     big = width * height * spp > 1920 * 1080 * 2048       # many seconds per step: one timed step, no warm-up, unless asked otherwise
     steps = args.steps if args.steps is not None else (1 if big else 2)
     warmup = args.warmup if args.warmup is not None else (0 if big else 1)
+    if steps < 1 or warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     n_sobol = 512 if spp <= 512 else 1 << (2 * spp - 1).bit_length()   # SobolSampler<N> table (main.rs:48): any N works, >= 2 x spp as in the parity tests
 
     import torch
@@ -132,6 +175,7 @@ def main():
     n_rows = len(r.local_rows())
 
     def step():
+        """one render of the frame; with N > 1 ranks, rank 0 gets the gathered framebuffer"""
         r.reset_accumulation()
         r.render_device(0, spp)
         if world > 1:
@@ -140,7 +184,8 @@ def main():
             if rehearsal:
                 torch.cuda.synchronize(dev)
                 fb = fb.cpu()
-            ptdist.gather_framebuffer(fb, height, width, rank, world, strip, dst=0)
+            return ptdist.gather_framebuffer(fb, height, width, rank, world, strip, dst=0)
+        return None
 
     if warmup == 0 and big:
         # the wavefront buffers are sized and allocated by the first render (hipMalloc of ~240 GiB takes seconds): do that outside the timed
@@ -156,12 +201,18 @@ def main():
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
     for _ in range(steps):
-        step()
+        gathered = step()
     torch.cuda.synchronize(dev)
     if world > 1:
         dist.barrier()
     dt = time.perf_counter() - t0
     st = r.stats()
+    if args.dump_outputs and rank == 0:
+        # before anything else renders into the frame: one rank reads its whole frame state, rank 0 of N has the gathered framebuffer only
+        if world == 1:
+            dump_outputs(args.dump_outputs, *r.read_frame())
+        else:
+            dump_outputs(args.dump_outputs, gathered.cpu().numpy())
     traced_closest_local = st.rays_closest - st.rays_primary_culled       # camera rays answered by the projection never reach the kernel
     traversed_local = traced_closest_local + st.rays_any + st.rays_light_closest_traced
     vals = torch.tensor([dt, float(st.rays), float(st.paths), float(traversed_local)], dtype=torch.float64, device=red_dev)
@@ -176,7 +227,7 @@ def main():
 
     kernel_ms = None
     s1 = None
-    if rank == 0 and world == 1 and not args.no_kernel_ms:
+    if rank == 0 and world == 1 and args.full and not args.no_kernel_ms:
         spp_k = spp if not big else max(1, spp // 16)
         # (a) the dominant kernel's launch durations: one extra, untimed render of the SAME launch structure as the timed steps (the fused
         # world + NEE launch on LDS scenes) with its batches one after another on ONE pipeline — with two pipelines an event pair on one
@@ -203,22 +254,6 @@ def main():
                                + ("" if spp_k == spp else f", measured on {spp_k} spp and scaled to {spp}")}
 
     if rank == 0:
-        launches = max(1, st.launches_trace_closest)
-        avg_ms_timed = st.ms_trace_closest / launches
-        # Launch duration of the dominant kernel: HIP events on its launch stream in the timed region.  When the timed steps run their batches on
-        # TWO pipelines (requests that do not fit at once; BVHs in global memory), an event pair also spans the other pipeline's kernels, so the
-        # one-pipeline render behind kernel_ms (events around every launch, nothing else on the device) is the clean measurement and is used
-        # when it exists; on one pipeline (the headline) the two agree.
-        if s1 is not None and s1.launches_trace_closest:
-            avg_ms = s1.ms_trace_closest / s1.launches_trace_closest
-            rays_per_launch_meas = (s1.rays_closest - s1.rays_primary_culled) / s1.launches_trace_closest
-            launches_meas = int(s1.launches_trace_closest)
-            launch_src = "HIP events on the launch stream around the world closest-hit launches of one extra render on ONE pipeline (same launch structure as the timed steps)"
-        else:
-            avg_ms = avg_ms_timed
-            rays_per_launch_meas = None
-            launches_meas = int(launches)
-            launch_src = "HIP events on the launch stream in the timed region"
         lds_scene = bool(st.lds_scene)
         out = {
             "metric": f"Mray/s at {width}x{height}, {spp} spp; achieved HBM GB/s in traversal kernel",
@@ -242,60 +277,77 @@ def main():
                        "bvh_in_lds": lds_scene, "scene_bytes": int(st.scene_bytes), "state_GiB": st.state_bytes / 2 ** 30},
             "kernel_ms": kernel_ms,
         }
-        cb = None
-        if world == 1 and not args.no_cpu_baseline:
-            cb = cpu_baseline(cfg, depth, n_sobol)
-            out["cpu_baseline"] = cb
-        # ---- roofline of the dominant kernel (world closest hit), SURVEY 8(d): algorithmic bytes per launch / launch duration
-        pname, prof = _profile(args.config)
-        kc = (prof or {}).get("k_closest_world") or {}
-        if lds_scene:
-            alg_per_ray, alg_src = float(BYTES_PER_CLOSEST_RAY), "48 B per closest-hit ray (32 in + 16 out; the BVH never leaves the chip)"
-        elif cb is not None:
-            # the oracle's averages are per CAST; the casts answered by the root-box projection visit no node, so per ray that enters the kernel:
-            per_cast = 32.0 * cb["nodes_visited_per_closest_ray"] + 48.0 * cb["triangles_tested_per_closest_ray"]
-            alg_per_ray = BYTES_PER_CLOSEST_RAY + per_cast * st.rays_closest / max(traced_closest_local, 1)
-            alg_src = ("48 + (32 per node visited + 48 per triangle tested) per ray that enters the kernel; nodes / triangles per cast from the oracle's counters 6, 7 on this "
-                       "run's cpu_baseline sample, x casts / traversed rays")
-        elif kc.get("algorithmic_bytes_per_ray"):
-            alg_per_ray, alg_src = float(kc["algorithmic_bytes_per_ray"]), f"profiles/{pname} (oracle counters 6, 7 at profiling time)"
-        else:
-            alg_per_ray, alg_src = float(BYTES_PER_CLOSEST_RAY), "48 B per ray only: no oracle counters in this run (--no-cpu-baseline) and no committed profile"
-        rays_per_launch = rays_per_launch_meas if rays_per_launch_meas is not None else traced_closest_local / launches
-        achieved = alg_per_ray * rays_per_launch / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
-        waves = kc.get("waves_per_simd")
-        va, lanes = kc.get("valu_active_frac"), kc.get("lanes_per_valu_instr")
-        valu_busy = va * waves if (va is not None and waves) else None
-        binding = "valu-issue" if lds_scene else "valu-issue at low lane agreement, then L2 latency"
-        roof = {"bound": binding, "axis": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": None,
-                "kernel": ("k_closest<LDS, PRIMARY> (bounce 0) + k_trace_fused<LDS> (later bounces: the world closest-hit rays, then the few BSDF-sampled NEE rays of the bounce before)"
-                           if lds_scene else "k_closest<global BVH, PRIMARY> (bounce 0) + k_closest<global BVH, WORLD> (later bounces)"),
-                "avg_launch_ms": avg_ms, "launches": launches_meas, "launch_time_source": launch_src,
-                "avg_launch_ms_timed_region": avg_ms_timed, "launches_timed_region": int(launches),
-                "algorithmic_bytes_per_ray": alg_per_ray, "algorithmic_bytes_source": alg_src, "rays_per_launch": rays_per_launch,
-                "closest_Mray_per_s_in_kernel": rays_per_launch / max(avg_ms, 1e-9) / 1e3,
-                # what actually binds the kernel (profiles/r03_*_summary.md): VALU issue.  valu_busy = share of the SIMD's issue cycles that carry a VALU
-                # instruction (VALU-active share of a wave's lifetime x resident waves per SIMD); effective_valu_frac = valu_busy x lanes / 64
-                "binding_resource": binding,
-                "valu_active_frac": va, "waves_per_simd": waves, "lanes_per_valu_instr": lanes, "valu_busy": valu_busy,
-                "effective_valu_frac": (valu_busy * lanes / 64.0) if (valu_busy is not None and lanes) else None,
-                "note": "`bound` names what binds the kernel (counters: profiles/); `achieved`/`peak`/`frac` are SURVEY 8(d)'s ALGORITHMIC bytes per launch "
-                        "(`algorithmic_bytes_per_ray` x `rays_per_launch`) over `avg_launch_ms` on the HBM axis (`axis`), not bandwidth in use; `launches` x `rays_per_launch` "
-                        "are the extra render's own; counter traffic is `traffic` per launch, `counter_GBps` per second, `counter_over_algorithmic` their ratio"}
-        if kc.get("hbm_bytes_per_ray") is not None:
-            roof["traffic"] = kc["hbm_bytes_per_ray"] * rays_per_launch
-            roof["counter_GBps"] = roof["traffic"] / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else None
-            roof["counter_over_algorithmic"] = kc["hbm_bytes_per_ray"] / alg_per_ray
-            roof["counters_source"] = (f"profiles/{pname} (rocprofv3 --pmc passes of `bench.py --config {args.config} --steps 1 --spp {kc.get('spp')}`, committed with this round): "
-                                       f"{kc['hbm_bytes_per_ray']:.1f} B/ray over {kc.get('rays', 0) / 1e6:.0f} M rays, scaled by this run's rays per launch")
-        out["roofline"] = roof
-        # ---- the memory-bound kernel: counter bytes of the shading pass over its measured time
-        ksh = (prof or {}).get("k_shade_surface")
-        if ksh and kernel_ms and kernel_ms["shade"] > 0 and ksh.get("hbm_bytes_per_spp"):
-            gb = ksh["hbm_bytes_per_spp"] * spp / 1e9
-            out["roofline_shade"] = {"kernel": "k_shade_surface (all launches of a step" + ("; the Lambertian launches of this LDS-resident scene include their inline shadow walk, which moves no bytes: the pass is VALU-bound, this is its byte rate, not its limit)" if lds_scene else ")"), "counter_GB_per_step": gb, "ms_per_step": kernel_ms["shade"],
-                                     "counter_GBps": gb / (kernel_ms["shade"] * 1e-3), "frac_of_8000": gb / (kernel_ms["shade"] * 1e-3) / HBM_PEAK_GBS,
-                                     "source": f"profiles/{pname}: FETCH_SIZE (doubled, gfx950) + WRITE_SIZE of the shading launches per spp, x this run's spp, over this run's kernel_ms.shade"}
+        if args.full:
+            launches = max(1, st.launches_trace_closest)
+            avg_ms_timed = st.ms_trace_closest / launches
+            # Launch duration of the dominant kernel: HIP events on its launch stream in the timed region.  When the timed steps run their batches on
+            # TWO pipelines (requests that do not fit at once; BVHs in global memory), an event pair also spans the other pipeline's kernels, so the
+            # one-pipeline render behind kernel_ms (events around every launch, nothing else on the device) is the clean measurement and is used
+            # when it exists; on one pipeline (the headline) the two agree.
+            if s1 is not None and s1.launches_trace_closest:
+                avg_ms = s1.ms_trace_closest / s1.launches_trace_closest
+                rays_per_launch_meas = (s1.rays_closest - s1.rays_primary_culled) / s1.launches_trace_closest
+                launches_meas = int(s1.launches_trace_closest)
+                launch_src = "HIP events on the launch stream around the world closest-hit launches of one extra render on ONE pipeline (same launch structure as the timed steps)"
+            else:
+                avg_ms = avg_ms_timed
+                rays_per_launch_meas = None
+                launches_meas = int(launches)
+                launch_src = "HIP events on the launch stream in the timed region"
+            cb = None
+            if world == 1 and not args.no_cpu_baseline:
+                cb = cpu_baseline(cfg, depth, n_sobol)
+                out["cpu_baseline"] = cb
+            # ---- roofline of the dominant kernel (world closest hit), SURVEY 8(d): algorithmic bytes per launch / launch duration
+            pname, prof = _profile(args.config)
+            kc = (prof or {}).get("k_closest_world") or {}
+            if lds_scene:
+                alg_per_ray, alg_src = float(BYTES_PER_CLOSEST_RAY), "48 B per closest-hit ray (32 in + 16 out; the BVH never leaves the chip)"
+            elif cb is not None:
+                # the oracle's averages are per CAST; the casts answered by the root-box projection visit no node, so per ray that enters the kernel:
+                per_cast = 32.0 * cb["nodes_visited_per_closest_ray"] + 48.0 * cb["triangles_tested_per_closest_ray"]
+                alg_per_ray = BYTES_PER_CLOSEST_RAY + per_cast * st.rays_closest / max(traced_closest_local, 1)
+                alg_src = ("48 + (32 per node visited + 48 per triangle tested) per ray that enters the kernel; nodes / triangles per cast from the oracle's counters 6, 7 on this "
+                           "run's cpu_baseline sample, x casts / traversed rays")
+            elif kc.get("algorithmic_bytes_per_ray"):
+                alg_per_ray, alg_src = float(kc["algorithmic_bytes_per_ray"]), f"profiles/{pname} (oracle counters 6, 7 at profiling time)"
+            else:
+                alg_per_ray, alg_src = float(BYTES_PER_CLOSEST_RAY), "48 B per ray only: no oracle counters in this run (--no-cpu-baseline) and no committed profile"
+            rays_per_launch = rays_per_launch_meas if rays_per_launch_meas is not None else traced_closest_local / launches
+            achieved = alg_per_ray * rays_per_launch / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
+            waves = kc.get("waves_per_simd")
+            va, lanes = kc.get("valu_active_frac"), kc.get("lanes_per_valu_instr")
+            valu_busy = va * waves if (va is not None and waves) else None
+            binding = "valu-issue" if lds_scene else "valu-issue at low lane agreement, then L2 latency"
+            roof = {"bound": binding, "axis": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": None,
+                    "kernel": ("k_closest<LDS, PRIMARY> (bounce 0) + k_trace_fused<LDS> (later bounces: the world closest-hit rays, then the few BSDF-sampled NEE rays of the bounce before)"
+                               if lds_scene else "k_closest<global BVH, PRIMARY> (bounce 0) + k_closest<global BVH, WORLD> (later bounces)"),
+                    "avg_launch_ms": avg_ms, "launches": launches_meas, "launch_time_source": launch_src,
+                    "avg_launch_ms_timed_region": avg_ms_timed, "launches_timed_region": int(launches),
+                    "algorithmic_bytes_per_ray": alg_per_ray, "algorithmic_bytes_source": alg_src, "rays_per_launch": rays_per_launch,
+                    "closest_Mray_per_s_in_kernel": rays_per_launch / max(avg_ms, 1e-9) / 1e3,
+                    # what actually binds the kernel (profiles/r03_*_summary.md): VALU issue.  valu_busy = share of the SIMD's issue cycles that carry a VALU
+                    # instruction (VALU-active share of a wave's lifetime x resident waves per SIMD); effective_valu_frac = valu_busy x lanes / 64
+                    "binding_resource": binding,
+                    "valu_active_frac": va, "waves_per_simd": waves, "lanes_per_valu_instr": lanes, "valu_busy": valu_busy,
+                    "effective_valu_frac": (valu_busy * lanes / 64.0) if (valu_busy is not None and lanes) else None,
+                    "note": "`bound` names what binds the kernel (counters: profiles/); `achieved`/`peak`/`frac` are SURVEY 8(d)'s ALGORITHMIC bytes per launch "
+                            "(`algorithmic_bytes_per_ray` x `rays_per_launch`) over `avg_launch_ms` on the HBM axis (`axis`), not bandwidth in use; `launches` x `rays_per_launch` "
+                            "are the extra render's own; counter traffic is `traffic` per launch, `counter_GBps` per second, `counter_over_algorithmic` their ratio"}
+            if kc.get("hbm_bytes_per_ray") is not None:
+                roof["traffic"] = kc["hbm_bytes_per_ray"] * rays_per_launch
+                roof["counter_GBps"] = roof["traffic"] / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else None
+                roof["counter_over_algorithmic"] = kc["hbm_bytes_per_ray"] / alg_per_ray
+                roof["counters_source"] = (f"profiles/{pname} (rocprofv3 --pmc passes of `bench.py --full --config {args.config} --steps 1 --spp {kc.get('spp')}`, committed with this round): "
+                                           f"{kc['hbm_bytes_per_ray']:.1f} B/ray over {kc.get('rays', 0) / 1e6:.0f} M rays, scaled by this run's rays per launch")
+            out["roofline"] = roof
+            # ---- the memory-bound kernel: counter bytes of the shading pass over its measured time
+            ksh = (prof or {}).get("k_shade_surface")
+            if ksh and kernel_ms and kernel_ms["shade"] > 0 and ksh.get("hbm_bytes_per_spp"):
+                gb = ksh["hbm_bytes_per_spp"] * spp / 1e9
+                out["roofline_shade"] = {"kernel": "k_shade_surface (all launches of a step" + ("; the Lambertian launches of this LDS-resident scene include their inline shadow walk, which moves no bytes: the pass is VALU-bound, this is its byte rate, not its limit)" if lds_scene else ")"), "counter_GB_per_step": gb, "ms_per_step": kernel_ms["shade"],
+                                         "counter_GBps": gb / (kernel_ms["shade"] * 1e-3), "frac_of_8000": gb / (kernel_ms["shade"] * 1e-3) / HBM_PEAK_GBS,
+                                         "source": f"profiles/{pname}: FETCH_SIZE (doubled, gfx950) + WRITE_SIZE of the shading launches per spp, x this run's spp, over this run's kernel_ms.shade"}
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()

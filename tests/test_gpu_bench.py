@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -26,7 +27,7 @@ def _bench(args, env_extra=None, launcher=None, timeout=900):
 
 
 def test_bench_line_contract_single_gpu():
-    d = _bench(["--steps", "1", "--warmup", "1", "--spp", "4"])
+    d = _bench(["--full", "--steps", "1", "--warmup", "1", "--spp", "4"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config",
               "roofline", "cpu_baseline"):
         assert k in d, k
@@ -40,6 +41,24 @@ def test_bench_line_contract_single_gpu():
     assert abs(r["achieved"] - r["algorithmic_bytes_per_ray"] * r["rays_per_launch"] / (r["avg_launch_ms"] * 1e-3) / 1e9) < 1e-6 * r["achieved"]
     c = d["cpu_baseline"]
     assert c["kind"] == "port" and c["unit"] == "Mray/s" and c["cores"] >= 1 and "samples 0..63 of 256 (fixed)" in c["sample"]
+
+
+def test_bench_plain_line_and_dumped_frame(tmp_path):
+    """A plain run: the headline fields, exactly --steps timed steps, none of --full's extra work; --dump-outputs writes the frame of the
+    last timed step (every pixel holds the run's spp in its sample count), at most 64 MB of float32 / float64."""
+    d = _bench(["--steps", "3", "--warmup", "0", "--spp", "4", "--dump-outputs", str(tmp_path)])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["warmup"] == 0 and d["ms_per_step"] > 0 and d["value"] > 0 and d["unit"] == "Mray/s" and d["higher_is_better"] is True
+    assert d["config"]["job_per_step"]["paths"] == 1920 * 1080 * 4
+    assert d["kernel_ms"] is None and not {"cpu_baseline", "roofline", "roofline_shade"} & set(d)
+    paths = sorted(tmp_path.glob("*.npy"))
+    assert sum(p.stat().st_size for p in paths) <= 64_000_000
+    f = {p.stem: np.load(p) for p in paths}
+    assert set(f) == {"accumulation", "sampled_pixels", "position", "ident"} and all(a.dtype in (np.float32, np.float64) for a in f.values())
+    acc = f["accumulation"]
+    assert acc.shape == (1080, 1920, 4) and (acc[..., 3] == 4).all() and np.isfinite(acc).all() and (acc[..., :3] >= 0).all()
+    assert f["position"].shape == (len(f["sampled_pixels"]), 4)
 
 
 def test_bench_two_ranks_rehearsal_matches_one_rank():

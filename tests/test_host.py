@@ -408,6 +408,46 @@ def test_bench_configurations_name_real_scenes():
     assert 240_000 <= atrium.n_triangles() <= 260_000 and len(atrium.models) > 256 and sum(len(m.matrices) for m in atrium.models) > 500
 
 
+def test_bench_dump_outputs_within_budget_on_a_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: float32 / float64 .npy files, at most 64 MB in all; a 1080p accumulation whole, position and id history at a
+    fixed seeded pixel sample; a frame too large to write whole is written at that sample, the same pixels on every call."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rng = np.random.default_rng(3)
+
+    def load(d):
+        paths = sorted(d.glob("*.npy"))
+        assert sum(p.stat().st_size for p in paths) <= 64_000_000
+        files = {p.stem: np.load(p) for p in paths}
+        assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+        return files
+
+    acc = rng.random((1080, 1920, 4), dtype=np.float32)
+    pos = rng.random((1080, 1920, 4), dtype=np.float32)
+    idb = rng.integers(0, 1 << 32, (1080, 1920), dtype=np.uint32)
+    bench.dump_outputs(str(tmp_path / "hd"), acc, pos, idb)
+    f = load(tmp_path / "hd")
+    assert set(f) == {"accumulation", "sampled_pixels", "position", "ident"}
+    assert np.array_equal(f["accumulation"], acc)
+    idx = f["sampled_pixels"].astype(np.int64)
+    assert len(idx) == 1 << 19 and (np.diff(idx) > 0).all() and idx[-1] < 1080 * 1920
+    assert np.array_equal(f["position"], pos.reshape(-1, 4)[idx]) and np.array_equal(f["ident"], idb.reshape(-1)[idx].astype(np.float64))
+
+    big = rng.random((2048, 2048, 4), dtype=np.float32)
+    for d in ("big1", "big2"):
+        bench.dump_outputs(str(tmp_path / d), big)
+    f1, f2 = load(tmp_path / "big1"), load(tmp_path / "big2")
+    assert set(f1) == {"accumulation", "sampled_pixels"} and np.array_equal(f1["sampled_pixels"], f2["sampled_pixels"])
+    idx = f1["sampled_pixels"].astype(np.int64)
+    assert np.array_equal(f1["accumulation"], big.reshape(-1, 4)[idx])
+
+    small = rng.random((64, 48, 4), dtype=np.float32)
+    bench.dump_outputs(str(tmp_path / "small"), small)
+    assert np.array_equal(load(tmp_path / "small")["sampled_pixels"], np.arange(64 * 48))
+
+
 def _world_triangles_f64(sc):
     """every instance's triangles through its matrix in binary64: (vertices [n, 3, 3], (instance, primitive) tags)"""
     tris, tag, inst = [], [], 0

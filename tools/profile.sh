@@ -13,7 +13,7 @@ O=$R/gpurun_out/prof_$TAG
 rm -rf "$O" && mkdir -p "$O"
 cd /tmp && export TMPDIR=/tmp
 echo "$ARGS" > "$O/args.txt"
-timeout -k 5 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/kt" -o r1 -- python "$R/bench.py" $ARGS --pipelines 1 --steps 1 --warmup 1 --no-cpu-baseline --no-kernel-ms > "$O/kt.log" 2>&1
+timeout -k 5 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/kt" -o r1 -- python "$R/bench.py" --full $ARGS --pipelines 1 --steps 1 --warmup 1 --no-cpu-baseline --no-kernel-ms > "$O/kt.log" 2>&1
 echo "kernel trace done"
 i=1
 for grp in "SQ_WAVES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES" \
@@ -22,7 +22,7 @@ for grp in "SQ_WAVES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU SQ_
            "WRITE_SIZE" \
            "SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE" \
            "TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum"; do
-    timeout -k 5 400 rocprofv3 --pmc $grp --output-format csv -d "$O/pmc$i" -o r1 -- python "$R/bench.py" $PMC_ARGS --pipelines 1 --steps 1 --warmup 0 --no-cpu-baseline --no-kernel-ms > "$O/pmc$i.log" 2>&1 || echo "pmc pass $i ($grp) failed"
+    timeout -k 5 400 rocprofv3 --pmc $grp --output-format csv -d "$O/pmc$i" -o r1 -- python "$R/bench.py" --full $PMC_ARGS --pipelines 1 --steps 1 --warmup 0 --no-cpu-baseline --no-kernel-ms > "$O/pmc$i.log" 2>&1 || echo "pmc pass $i ($grp) failed"
     echo "pmc pass $i done"
     i=$((i + 1))
 done
