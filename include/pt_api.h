@@ -97,7 +97,10 @@ int pt_set_config(pt_ctx* ctx, const pt_config* cfg); /* change image size / bou
 int pt_add_material(pt_ctx* ctx, const pt_material_desc* desc);
 /* Model::new(path, material, matrices)  model.rs:36, with the OBJ file replaced by its triangle soup
  * (positions / normals: n_tris * 3 vertices * xyz, the Vec<Vertex> load_obj returns, blas.rs:44-131);
- * affine3x4_rowmajor: n_instances rigid transforms.  Returns the model (= BLAS) index or a negative pt_status. */
+ * affine3x4_rowmajor: n_instances rigid transforms.  Returns the model (= BLAS) index or a negative pt_status.
+ * Participating media are keyed per model, as the reference keys them by the address of each BLAS's own copy of its material:
+ * two models built with equal (or the same) volume-bearing material are two volumes, every instance of one model is one volume.
+ * A path may be inside up to 8 volumes at once; a render in which a path enters a ninth fails with PT_ERR_LIMIT. */
 int pt_add_model(pt_ctx* ctx, const float* positions_xyz, const float* normals_xyz, uint32_t n_tris, int material,
                  const float* affine3x4_rowmajor, uint32_t n_instances);
 /* Model::new(path, ...) with the reference's own OBJ reader, load_obj blas.rs:44-131 (v / vn / f with v/vt/vn references,
@@ -205,6 +208,12 @@ int pt_math_batch(pt_ctx* ctx, int fn, uint32_t n, const float* a, const float* 
  * drawing from stream (pixel[i], sample[i]) at draws_consumed; out[i*9..] = wo xyz, bsdf rgb, pdf, weakening, draws */
 int pt_material_eval(pt_ctx* ctx, int material, uint32_t n, const float* incoming_xyz, const float* normal_xyz, const uint8_t* front,
                      const uint32_t* pixel, const uint32_t* sample, uint32_t draws_consumed, float* out9);
+/* VolumeScatter::scatter (volume.rs:83-97) and VolumeAbsorption::get_transmission (volume.rs:113) of the material's volume on the
+ * device for n rays (incoming direction, t_max), drawing from stream (pixel[i], sample[i]) at draws_consumed;
+ * out[i*9..] = scattered (0/1), t, direction xyz (0 when not scattered), transmission over dist[i] rgb, draws.
+ * A material without scattering draws nothing; without absorption the transmission is 1. */
+int pt_volume_eval(pt_ctx* ctx, int material, uint32_t n, const float* incoming_xyz, const float* t_max, const float* dist,
+                   const uint32_t* pixel, const uint32_t* sample, uint32_t draws_consumed, float* out9);
 
 /* ---- host-builder introspection (CPU only; compared against the oracle's builders) ----------------------------- */
 int pt_blas_count(pt_ctx* ctx);
@@ -215,6 +224,9 @@ int pt_tlas_dump(pt_ctx* ctx, int which, uint32_t* n_nodes, uint32_t* root, floa
 /* the leaves' `matrix` / `inv_matrix` (tlas_bvh.rs:36-41; inv_matrix = matrix.inverse(), :99) in leaf allocation order — the index a
  * leaf's `a` holds in pt_tlas_dump —, each as 12 floats, rows of the 3x4 */
 int pt_tlas_instances(pt_ctx* ctx, int which, uint32_t* n, float* matrix12, float* inv_matrix12, uint32_t cap);
+/* the material index each leaf's instance is shaded with (leaf allocation order) and the model (BLAS) it instantiates: a further
+ * model of a volume-bearing material reads an appended copy of it (one volume per model, see pt_add_model) */
+int pt_instance_materials(pt_ctx* ctx, int which, uint32_t* n, uint32_t* material, uint32_t* blas, uint32_t cap);
 int pt_light_cdf(pt_ctx* ctx, uint32_t* n, float* pdf, float* cdf, uint32_t* blas, uint32_t* prim, float* max_weight, uint32_t cap);
 int pt_triangle_dump(pt_ctx* ctx, int blas, uint32_t prim, float out36[36]);
 

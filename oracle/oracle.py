@@ -13,7 +13,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.path.join(_HERE, "libpt_oracle.so")
-N_COUNTERS = 8
+N_COUNTERS = 9
 
 
 def build(force: bool = False) -> str:
@@ -92,6 +92,8 @@ def lib():
         L.pto_math_batch.argtypes = [C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.pto_material_eval.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_uint32, C.c_uint32,
                                         C.c_uint32, C.c_void_p]
+        L.pto_volume_eval.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_float, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32,
+                                      C.c_void_p]
         _lib = L
     return _lib
 
@@ -290,6 +292,14 @@ class Oracle:
         out = np.zeros(36, np.float32)
         r = self.L.pto_triangle_dump(self.ctx, which, blas, prim, _p(out))
         assert r == 0
+        return out
+
+    def volume_eval(self, material, incoming, t_max, dist, pixel, sample, draws_consumed=0, seed=DEFAULT_SEED):
+        """pto_volume_eval for one ray: scattered, t, direction xyz, transmission over dist rgb, draws"""
+        i = np.ascontiguousarray(incoming, np.float32)
+        out = np.zeros(9, np.float32)
+        r = self.L.pto_volume_eval(self.ctx, material, _p(i), float(t_max), float(dist), seed, pixel, sample, draws_consumed, _p(out))
+        assert r == 0, r
         return out
 
     def material_eval(self, material, incoming, normal, front, pixel, sample, draws_consumed=0, seed=DEFAULT_SEED):

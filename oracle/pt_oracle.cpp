@@ -36,7 +36,7 @@ const float FRAC_1_PI = 0.318309886183790671537767526745028724f;
 
 struct Counters
 {
-    uint64_t c[PTO_N_COUNTERS] = {0, 0, 0, 0, 0, 0, 0, 0};
+    uint64_t c[PTO_N_COUNTERS] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     int mode = -1; // which counter class the current traversal feeds (0 world closest, 1 any, 2 lights closest)
     void node() { c[3]++; if (mode == 0) c[6]++; }
     void tri() { c[4]++; if (mode == 0) c[7]++; }
@@ -1184,7 +1184,8 @@ Sample integrate(Tracer& tr, Ray r, Rng& rng, uint32_t max_bounces, bool enable_
     V4 position{p0.x, p0.y, p0.z, 1e5f};
     uint8_t first_id = 255;
     bool last_delta = false;
-    std::vector<int> volume_stack; // material indices, insertion ordered (deviation B-13)
+    std::vector<uint32_t> volume_stack; // BLAS (= model) ids, insertion ordered (deviation B-13): the reference keys a volume by the
+                                        // address of the BLAS's own copy of its material (volume.rs:146-162, blas.rs:167,197)
 
     for (uint32_t b = 0;; ++b)
     {
@@ -1212,9 +1213,9 @@ Sample integrate(Tracer& tr, Ray r, Rng& rng, uint32_t max_bounces, bool enable_
             bool scattered = false;
             float best_t = 0;
             V3 best_dir{0, 0, 0};
-            for (int vm : volume_stack)
+            for (uint32_t vb : volume_stack)
             {
-                const Volume& v = scene.materials[vm].volume;
+                const Volume& v = scene.materials[scene.world.blas[vb].material].volume;
                 if (!v.has_scatter) continue;
                 float t;
                 V3 dir;
@@ -1227,9 +1228,9 @@ Sample integrate(Tracer& tr, Ray r, Rng& rng, uint32_t max_bounces, bool enable_
             {
                 float dist = scattered ? best_t : hi.t;
                 V3 w{1, 1, 1};
-                for (int vm : volume_stack)
+                for (uint32_t vb : volume_stack)
                 {
-                    const Volume& v = scene.materials[vm].volume;
+                    const Volume& v = scene.materials[scene.world.blas[vb].material].volume;
                     if (v.has_absorption) w = w * v.get_transmission(dist);
                 }
                 path_weight = path_weight * w;
@@ -1250,9 +1251,10 @@ Sample integrate(Tracer& tr, Ray r, Rng& rng, uint32_t max_bounces, bool enable_
             if (const Volume* v = material.get_volume())                           // integrator.rs:217-227
             {
                 (void)v;
-                auto it = std::find(volume_stack.begin(), volume_stack.end(), mat_index);
-                if (hi.front_facing) { if (it == volume_stack.end()) volume_stack.push_back(mat_index); }
+                auto it = std::find(volume_stack.begin(), volume_stack.end(), blas_id);
+                if (hi.front_facing) { if (it == volume_stack.end()) volume_stack.push_back(blas_id); }
                 else if (it != volume_stack.end()) volume_stack.erase(it);
+                if (volume_stack.size() > tr.ctr.c[8]) tr.ctr.c[8] = volume_stack.size();
             }
             bool is_delta = material.is_delta();
             if (enable_nee && !is_delta)                                           // integrator.rs:231-234
@@ -1583,7 +1585,7 @@ static int render_impl(pto_ctx* c, const pto_render_cfg* cfg, float* accum, floa
         for (int k = 0; k < PTO_N_COUNTERS; ++k)
         {
             counters[k] = 0;
-            for (auto& ct : ctrs) counters[k] += ct.c[k];
+            for (auto& ct : ctrs) counters[k] = k == 8 ? std::max(counters[k], ct.c[k]) : counters[k] + ct.c[k]; // 8 is a maximum
         }
     return 0;
 }
@@ -1998,6 +2000,29 @@ int pto_material_eval(pto_ctx* c, int material, const float incoming[3], const f
     out[3] = bp.bsdf.x; out[4] = bp.bsdf.y; out[5] = bp.bsdf.z;
     out[6] = bp.pdf;
     out[7] = m.get_weakening(wo, n);
+    out[8] = (float)(rng.k - draws_consumed);
+    return 0;
+}
+
+int pto_volume_eval(pto_ctx* c, int material, const float incoming[3], float t_max, float dist, uint64_t seed, uint32_t pixel, uint32_t sample,
+                    uint32_t draws_consumed, float out[9])
+{
+    if (material < 0 || material >= (int)c->materials.size()) return -1;
+    const Volume& v = c->materials[material].volume;
+    Rng rng{stream_state0(seed, pixel, sample), draws_consumed};
+    for (int k = 0; k < 5; ++k) out[k] = 0.0f;
+    if (v.has_scatter)                                                           // integrator.rs:189-199
+    {
+        float t;
+        V3 dir;
+        if (v.scatter(rng, V3{incoming[0], incoming[1], incoming[2]}, t_max, &t, &dir))
+        {
+            out[0] = 1.0f; out[1] = t; out[2] = dir.x; out[3] = dir.y; out[4] = dir.z;
+        }
+    }
+    V3 w{1, 1, 1};
+    if (v.has_absorption) w = v.get_transmission(dist);                          // integrator.rs:200-205
+    out[5] = w.x; out[6] = w.y; out[7] = w.z;
     out[8] = (float)(rng.k - draws_consumed);
     return 0;
 }

@@ -37,8 +37,8 @@ typedef struct pto_render_cfg
 
 /* counters[]: 0 closest-hit casts (world), 1 any-hit casts, 2 closest-hit casts (lights TLAS),
  * 3 nodes visited, 4 triangle tests, 5 paths, 6 nodes visited by world closest only,
- * 7 triangle tests by world closest only */
-enum { PTO_N_COUNTERS = 8 };
+ * 7 triangle tests by world closest only, 8 the deepest volume stack any path reached (a maximum, not a sum) */
+enum { PTO_N_COUNTERS = 9 };
 
 pto_ctx* pto_create(void);
 void pto_destroy(pto_ctx*);
@@ -106,6 +106,9 @@ void pto_math_batch(int fn, uint32_t n, const float* a, const float* b, float* o
  * get_bsdf_pdf(wi=-incoming, wo=scattered) ; out = wo[3], bsdf[3], pdf, weakening, draws used */
 int pto_material_eval(pto_ctx*, int material, const float incoming[3], const float normal[3], int front_facing, uint64_t seed,
                       uint32_t pixel, uint32_t sample, uint32_t draws_consumed, float out[9]);
+/* VolumeScatter::scatter + VolumeAbsorption::get_transmission of the material's volume; out = scattered, t, dir xyz, transmission rgb, draws */
+int pto_volume_eval(pto_ctx*, int material, const float incoming[3], float t_max, float dist, uint64_t seed, uint32_t pixel, uint32_t sample,
+                    uint32_t draws_consumed, float out[9]);
 
 #ifdef __cplusplus
 }

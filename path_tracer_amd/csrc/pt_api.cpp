@@ -483,7 +483,7 @@ int ensure_wavefront(pt_ctx* c, int pipe, size_t n_paths, uint32_t rows)
     TAKE(w.st.rec, n_paths * sizeof(DPathRec));
     TAKE(w.st.radiance, n_paths * 16);
     TAKE(w.st.occl, n_paths);
-    if (c->sv.has_volumes) { TAKE(w.st.vstack, n_paths * 4); }
+    if (c->sv.has_volumes) { TAKE(w.st.vstack, n_paths * sizeof(uint64_t)); }
     else w.st.vstack = nullptr;
     // first-hit position / id: only the batch's last sample / last two samples are ever read (RenderParams::keep_*_from)
     TAKE(w.st.first_pos, (size_t)std::max<uint32_t>(c->local_pixels, 64) * 16);
@@ -597,6 +597,14 @@ int harvest_batch(pt_ctx* c, int pipe)
         {
             pp.ev_used = 0; // the abandoned batch's event pairs must not be added to the next render's timers
             return fail(c, PT_ERR_LIMIT, "a wavefront queue was full (pt_config.queue_slack too small for this scene); the batch was abandoned, no memory was overwritten");
+        }
+    for (uint32_t r = 0; r < rows; ++r)
+        // a path entered a ninth volume: the device's volume stack holds eight, so that path would have skipped the ninth one's media
+        if (pp.h_counters[r].vstack_full)
+        {
+            pp.ev_used = 0;
+            return fail(c, PT_ERR_LIMIT, "a path was inside more than 8 volumes at once (the volume stack holds 8 nested or overlapping "
+                                         "volume-bearing models); the batch was abandoned");
         }
     // exact tallies live beside the claim cursors, one per cursor line (64 addresses per queue instead of one: a launch of a few
     // thousand waves that each add to ONE word spends ~50 us on that alone)
@@ -905,11 +913,11 @@ int render_common(pt_ctx* c, uint32_t first_sample, uint32_t n_samples, float* s
             for (const pt_ctx::Pipe& pp : c->pipe)
                 for (const DevBuf& b : pp.pool) held += b.bytes;
             // bytes of wavefront state per path (ensure_wavefront): 323 in records, ray queues and terminal queues + 54 per surface class present
-            // in the scene (its 48-byte shade queue with an eighth of slack) + 4 with volumes.  (Rounds 1-3 assumed 410 whatever the scene:
+            // in the scene (its 48-byte shade queue with an eighth of slack) + 8 with volumes.  (Rounds 1-3 assumed 410 whatever the scene:
             // right for one class, but the four-class atrium then asked for 268 GiB of a 268.2 GiB device.)
             uint32_t n_classes = 0;
             for (uint32_t q = 1; q < Q_COUNT; ++q) n_classes += c->class_present[q] ? 1u : 0u;
-            const double per_path = 330.0 + 56.0 * std::max(n_classes, 1u) + (c->sv.has_volumes ? 4.0 : 0.0) + 24.0;
+            const double per_path = 330.0 + 56.0 * std::max(n_classes, 1u) + (c->sv.has_volumes ? 8.0 : 0.0) + 24.0;
             max_paths = (size_t)((double)(free_b + held) * 0.85 / per_path);
         }
         max_paths = std::min<size_t>(std::max<size_t>(max_paths, 1u << 20), (1ull << 29) - 1);
@@ -1724,8 +1732,10 @@ int pt_math_batch(pt_ctx* c, int fn, uint32_t n, const float* a, const float* b,
         return r;
     HIPCHK(c, hipMemcpy(da.p, a, (size_t)n * 4, hipMemcpyHostToDevice));
     if (b) HIPCHK(c, hipMemcpy(db.p, b, (size_t)n * 4, hipMemcpyHostToDevice));
-    else HIPCHK(c, hipMemset(db.p, 0, (size_t)n * 4));
-    HIPCHK(c, hipMemset(d1.p, 0, (size_t)n * 4));
+    // on the probe's own stream: c->stream is non-blocking, so a hipMemset (null stream, asynchronous to the host for device memory)
+    // is not ordered before the kernel and could clear what the kernel wrote
+    else HIPCHK(c, hipMemsetAsync(db.p, 0, (size_t)n * 4, c->stream));
+    HIPCHK(c, hipMemsetAsync(d1.p, 0, (size_t)n * 4, c->stream));
     launch_math_probe(c->stream, fn, n, (const float*)da.p, (const float*)db.p, (float*)d0.p, (float*)d1.p, c->cfg.seed);
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(o0, d0.p, (size_t)n * 4, hipMemcpyDeviceToHost));
@@ -1756,6 +1766,35 @@ int pt_material_eval(pt_ctx* c, int material, uint32_t n, const float* incoming,
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(out9, dout.p, (size_t)n * 36, hipMemcpyDeviceToHost));
     dev_free(di); dev_free(dn); dev_free(df); dev_free(dp); dev_free(ds); dev_free(dout);
+    return PT_OK;
+}
+
+int pt_volume_eval(pt_ctx* c, int material, uint32_t n, const float* incoming, const float* t_max, const float* dist, const uint32_t* pixel,
+                   const uint32_t* sample, uint32_t draws, float* out9)
+{
+    if (!c || !incoming || !t_max || !dist || !pixel || !sample || !out9) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (material < 0 || material >= (int)c->scene.materials.size()) return fail(c, PT_ERR_ARG, "material index");
+    if (n == 0) return PT_OK;
+    int r;
+    if ((r = upload_scene(c))) return r;
+    DevBuf di, dt, dd, dp, ds, dout;
+    if ((r = dev_alloc(c, di, (size_t)n * 12)) || (r = dev_alloc(c, dt, (size_t)n * 4)) || (r = dev_alloc(c, dd, (size_t)n * 4)) ||
+        (r = dev_alloc(c, dp, (size_t)n * 4)) || (r = dev_alloc(c, ds, (size_t)n * 4)) || (r = dev_alloc(c, dout, (size_t)n * 36)))
+    {
+        dev_free(di); dev_free(dt); dev_free(dd); dev_free(dp); dev_free(ds); dev_free(dout);
+        return r;
+    }
+    HIPCHK(c, hipMemcpy(di.p, incoming, (size_t)n * 12, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(dt.p, t_max, (size_t)n * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(dd.p, dist, (size_t)n * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(dp.p, pixel, (size_t)n * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(ds.p, sample, (size_t)n * 4, hipMemcpyHostToDevice));
+    launch_volume_probe(c->stream, c->sv, material, n, (const float*)di.p, (const float*)dt.p, (const float*)dd.p, (const uint32_t*)dp.p,
+                        (const uint32_t*)ds.p, draws, c->cfg.seed, (float*)dout.p);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(out9, dout.p, (size_t)n * 36, hipMemcpyDeviceToHost));
+    dev_free(di); dev_free(dt); dev_free(dd); dev_free(dp); dev_free(ds); dev_free(dout);
     return PT_OK;
 }
 
@@ -1812,6 +1851,17 @@ int pt_tlas_instances(pt_ctx* c, int which, uint32_t* n, float* matrix12, float*
         std::memcpy(o, r, sizeof(r));
     };
     for (size_t i = 0; i < t.instances.size(); ++i) { rows(t.instances[i].fwd, matrix12 + 12 * i); rows(t.instances[i].inv, inv_matrix12 + 12 * i); }
+    return PT_OK;
+}
+
+int pt_instance_materials(pt_ctx* c, int which, uint32_t* n, uint32_t* material, uint32_t* blas, uint32_t cap)
+{
+    if (!c || !c->scene.built || !n) return PT_ERR_STATE;
+    const FlatScene& f = c->scene.flat;
+    const uint32_t b = f.inst_base[which ? 1 : 0], e = which ? (uint32_t)f.instances.size() : f.inst_base[1];
+    *n = e - b;
+    if (e - b > cap || !material || !blas) return PT_ERR_ARG;
+    for (uint32_t i = b; i < e; ++i) { material[i - b] = f.instances[i].material; blas[i - b] = f.instances[i].blas; }
     return PT_OK;
 }
 

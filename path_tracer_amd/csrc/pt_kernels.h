@@ -95,5 +95,7 @@ void launch_sobol_probe(hipStream_t s, uint32_t n_points, uint32_t n, const uint
 void launch_math_probe(hipStream_t s, int fn, uint32_t n, const float* a, const float* b, float* o0, float* o1, uint64_t seed);
 void launch_material_probe(hipStream_t s, const SceneView& sv, int material, uint32_t n, const float* incoming, const float* normal,
                            const uint8_t* front, const uint32_t* pixel, const uint32_t* sample, uint32_t draws, uint64_t seed, float* out9);
+void launch_volume_probe(hipStream_t s, const SceneView& sv, int material, uint32_t n, const float* incoming, const float* t_max, const float* dist,
+                         const uint32_t* pixel, const uint32_t* sample, uint32_t draws, uint64_t seed, float* out9);
 
 } // namespace pt

@@ -1938,17 +1938,17 @@ __global__ void __launch_bounds__(PT_SHADE_THREADS, INLINE ? PT_SHADE_WAVES_INLI
             bool scattered = false;
             float s_t = 0.0f;
             f3 s_dir{0.0f, 0.0f, 0.0f};
-            uint32_t vst = 0xffffffffu, vst_in = 0xffffffffu;
+            uint64_t vst = kVStackEmpty, vst_in = kVStackEmpty;
             if (VOLUMES)
             {
                 if (bounce != 0u) vst = io.st.vstack[pid];
                 vst_in = vst;
-                if (vst != 0xffffffffu)
+                if (vst != kVStackEmpty)
                 {
-                    for (uint32_t slot = 0; slot < 4u; ++slot)
+                    for (uint32_t slot = 0; slot < kVStackSlots; ++slot)       // the stack is packed: the first empty slot ends it
                     {
-                        const uint32_t vm = (vst >> (8u * slot)) & 0xffu;
-                        if (vm == 0xffu) continue;
+                        const uint32_t vm = (uint32_t)(vst >> (8u * slot)) & 0xffu;
+                        if (vm == 0xffu) break;
                         const DMaterial& dm = sv.materials[vm];
                         if (dm.vol_flags & 2u)                                         // VolumeScatter::scatter  volume.rs:83-97
                         {
@@ -1963,10 +1963,10 @@ __global__ void __launch_bounds__(PT_SHADE_THREADS, INLINE ? PT_SHADE_WAVES_INLI
                     }
                     const float dist = scattered ? s_t : hit.x;
                     f3 wgt{1.0f, 1.0f, 1.0f};
-                    for (uint32_t slot = 0; slot < 4u; ++slot)
+                    for (uint32_t slot = 0; slot < kVStackSlots; ++slot)
                     {
-                        const uint32_t vm = (vst >> (8u * slot)) & 0xffu;
-                        if (vm == 0xffu) continue;
+                        const uint32_t vm = (uint32_t)(vst >> (8u * slot)) & 0xffu;
+                        if (vm == 0xffu) break;
                         const DMaterial& dm = sv.materials[vm];
                         if (dm.vol_flags & 1u) wgt = wgt * beer_lambert(f3{dm.vol_abs[0], dm.vol_abs[1], dm.vol_abs[2]}, dist);
                     }
@@ -1992,28 +1992,32 @@ __global__ void __launch_bounds__(PT_SHADE_THREADS, INLINE ? PT_SHADE_WAVES_INLI
             {
             if (VOLUMES && sv.materials[in.material].has_volume != 0u)     // integrator.rs:217-227
             {
+                // keyed by the instance's material index, which is one volume per model: the host gives every further model of a
+                // volume-bearing material its own copy (HostScene::flatten)
                 const uint32_t me = in.material & 0xffu;
-                int found = -1, empty = -1;
-                for (int slot = 0; slot < 4; ++slot)
+                uint32_t depth = 0u;
+                int found = -1;
+                for (uint32_t slot = 0; slot < kVStackSlots; ++slot)
                 {
-                    const uint32_t vm = (vst >> (8 * slot)) & 0xffu;
-                    if (vm == me && found < 0) found = slot;
-                    if (vm == 0xffu && empty < 0) empty = slot;
+                    const uint32_t vm = (uint32_t)(vst >> (8u * slot)) & 0xffu;
+                    if (vm == 0xffu) break;
+                    if (vm == me && found < 0) found = (int)slot;
+                    ++depth;
                 }
-                if (front) { if (found < 0 && empty >= 0) vst = (vst & ~(0xffu << (8 * empty))) | (me << (8 * empty)); }
+                if (front)
+                {
+                    if (found < 0)
+                    {
+                        if (depth < kVStackSlots) vst = (vst & ~(0xffull << (8u * depth))) | ((uint64_t)me << (8u * depth));
+                        // a volume the stack cannot hold: the path would skip its media, so the batch is void (the host reports PT_ERR_LIMIT)
+                        else __hip_atomic_store(&io.ctr->vstack_full, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    }
+                }
                 else if (found >= 0)
                 {
-                    // remove and close the gap so that insertion order is kept
-                    uint32_t out_v = 0xffffffffu;
-                    int k = 0;
-                    for (int slot = 0; slot < 4; ++slot)
-                    {
-                        const uint32_t vm = (vst >> (8 * slot)) & 0xffu;
-                        if (slot == found || vm == 0xffu) continue;
-                        out_v = (out_v & ~(0xffu << (8 * k))) | (vm << (8 * k));
-                        ++k;
-                    }
-                    vst = out_v;
+                    // remove and close the gap so that insertion order is kept: the slots above `found` move down one, the top one empties
+                    const uint64_t below = (1ull << (8u * (uint32_t)found)) - 1ull;
+                    vst = (vst & below) | (((vst >> 8u) | (0xffull << 56u)) & ~below);
                 }
             }
             if (rp.enable_nee && !is_delta)                                            // integrator.rs:231
@@ -2405,6 +2409,33 @@ __global__ void k_material_probe(const SceneView sv, int material, uint32_t n, c
     o[8] = (float)(rng.k - draws);
 }
 
+// VolumeScatter::scatter (volume.rs:83-97) and VolumeAbsorption::get_transmission (volume.rs:113) of one material's volume, as the
+// shading pass evaluates them: out9[i*9..] = scattered (0/1), t, direction xyz, transmission over dist[i] rgb, draws consumed
+__global__ void k_volume_probe(const SceneView sv, int material, uint32_t n, const float* incoming, const float* t_max, const float* dist,
+                               const uint32_t* pixel, const uint32_t* sample, uint32_t draws, uint64_t seed, float* out9)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const DMaterial& dm = sv.materials[material];
+    Stream rng{stream_key(seed, pixel[i], sample[i]), draws};
+    const f3 rd{incoming[3 * i], incoming[3 * i + 1], incoming[3 * i + 2]};
+    float* o = out9 + 9 * i;
+    o[0] = 0.0f; o[1] = 0.0f; o[2] = 0.0f; o[3] = 0.0f; o[4] = 0.0f;
+    if (dm.vol_flags & 2u)                                                  // as k_shade_surface's media loop
+    {
+        const float t = -ln_det(rng.f32()) / dm.vol_c;
+        if (!(t > t_max[i]))
+        {
+            const f3 d = hg_direction(dm.vol_g, rng, rd);
+            o[0] = 1.0f; o[1] = t; o[2] = d.x; o[3] = d.y; o[4] = d.z;
+        }
+    }
+    f3 w{1.0f, 1.0f, 1.0f};
+    if (dm.vol_flags & 1u) w = beer_lambert(f3{dm.vol_abs[0], dm.vol_abs[1], dm.vol_abs[2]}, dist[i]);
+    o[5] = w.x; o[6] = w.y; o[7] = w.z;
+    o[8] = (float)(rng.k - draws);
+}
+
 } // namespace
 
 // ================================================================================================ launchers
@@ -2684,6 +2715,12 @@ void launch_material_probe(hipStream_t s, const SceneView& sv, int material, uin
 {
     hipLaunchKernelGGL(k_material_probe, dim3((n + 255u) / 256u), dim3(256), 0, s, sv, material, n, incoming, normal, front, pixel, sample, draws, seed,
                        out9);
+}
+
+void launch_volume_probe(hipStream_t s, const SceneView& sv, int material, uint32_t n, const float* incoming, const float* t_max, const float* dist,
+                         const uint32_t* pixel, const uint32_t* sample, uint32_t draws, uint64_t seed, float* out9)
+{
+    hipLaunchKernelGGL(k_volume_probe, dim3((n + 255u) / 256u), dim3(256), 0, s, sv, material, n, incoming, t_max, dist, pixel, sample, draws, seed, out9);
 }
 
 } // namespace pt

@@ -626,6 +626,31 @@ int HostScene::flatten(std::string* err)
     FlatScene f;
     f.materials = materials;
     for (const DMaterial& m : materials) f.has_volumes = f.has_volumes || m.has_volume != 0;
+    // One volume per model.  The reference keys its volume stack by the address of the material (volume.rs:146-162), and every BLAS
+    // owns a copy of its model's material (blas.rs:167,197): two models of equal materials are two volumes, all instances of one model
+    // are one.  The device keys the stack by material index, so the first model of a volume-bearing material keeps the index and
+    // every further one gets an appended copy.  Indices the caller handed out do not move, and every build starts again from
+    // `materials`, so rebuilds do not pile up copies.
+    std::vector<uint32_t> blas_material(blas.size());
+    {
+        std::vector<uint8_t> taken(materials.size(), 0);
+        for (size_t i = 0; i < blas.size(); ++i)
+        {
+            const uint32_t m = (uint32_t)blas[i].material;
+            blas_material[i] = m;
+            if (materials[m].has_volume && taken[m])
+            {
+                blas_material[i] = (uint32_t)f.materials.size();
+                f.materials.push_back(materials[m]);
+            }
+            taken[m] = 1;
+        }
+    }
+    if (f.materials.size() > 255)
+    {
+        if (err) *err = "at most 255 materials (volume stacks hold 8-bit material indices), counting one copy for every further model of a volume-bearing material";
+        return -5;
+    }
     // absolute node layout: world TLAS | lights TLAS | BLAS 0 | BLAS 1 | ...
     const uint32_t world_base = 0;
     const uint32_t lights_base = (uint32_t)world.nodes.size();
@@ -768,8 +793,8 @@ int HostScene::flatten(std::string* err)
             d.root = blas_root_at[hi.model];
             d.root_node = f.nodes[d.root];
             d.blas = hi.blas;
-            d.material = (uint32_t)blas[hi.model].material;
-            switch (materials[d.material].kind)
+            d.material = blas_material[hi.model];
+            switch (f.materials[d.material].kind)
             {
             case MAT_LAMBERTIAN: d.qclass = Q_LAMBERT; break;
             case MAT_SPECULAR: d.qclass = Q_SPECULAR; break;
@@ -780,7 +805,7 @@ int HostScene::flatten(std::string* err)
             }
             // with participating media an emissive hit is preceded by the volume interaction (integrator.rs:189-205), which may
             // scatter the path onwards: such hits are shaded by a surface kernel instead of the terminal pass
-            if (f.has_volumes && materials[d.material].kind == MAT_EMISSIVE) d.qclass = Q_LAMBERT;
+            if (f.has_volumes && f.materials[d.material].kind == MAT_EMISSIVE) d.qclass = Q_LAMBERT;
             {
                 // bit pattern of Affine3A::IDENTITY.inverse(): unit matrix with +0 zeros, translation -0
                 static const uint32_t ident[12] = {0x3f800000u, 0, 0, 0x80000000u, 0, 0x3f800000u, 0, 0x80000000u, 0, 0, 0x3f800000u, 0x80000000u};

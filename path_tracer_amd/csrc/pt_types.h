@@ -103,7 +103,8 @@ struct Counters
     uint32_t overflow;       // non-zero: some producer found a queue full (its entries went to the queue's dump area, nothing was
                              // written out of bounds); the batch is void and the host reports PT_ERR_LIMIT
     uint32_t n_shadow;       // explicit-light shadow rays produced by this bounce's shading
-    uint32_t spare0;
+    uint32_t vstack_full;    // non-zero: a path entered a volume while inside kVStackSlots others (it was not pushed); the batch is
+                             // void and the host reports PT_ERR_LIMIT
     uint32_t n_lchain;       // BSDF-sampled NEE rays (lights TLAS closest hit, then world any hit)
     uint32_t spare1;
     uint32_t spare2, spare3;
@@ -211,11 +212,14 @@ struct PathState
     // every path of the batch.  Dense bytes.  (The explicit shadow ray's result needs no word: a
     // blocked ray zeroes DPathRec::nee_e.)
     uint8_t* occl;
-    uint32_t* vstack;   // volume stack (integrator.rs:161): four material indices, one per byte, 0xff = empty, insertion order; null without volumes
+    uint64_t* vstack;   // volume stack (integrator.rs:161): up to kVStackSlots material indices (one volume per model: HostScene::flatten),
+                        // one per byte from the low end, packed in insertion order, 0xff = empty; null without volumes
     f4* radiance;       // finished paths: accumulated.xyz (what integrate() returns before the finite check), dense by path id
     f4* first_pos;      // first-hit xyz | t        (main.rs:205) of the batch's LAST sample (RenderParams::keep_s_pos): index = the pixel's index in the active rectangle
     uint32_t* first_id; // of the batch's last TWO samples (id history, main.rs:206): index = (sample - keep_s_id) * act_pixels + pixel index
 };
+enum : uint32_t { kVStackSlots = 8u }; // volumes a path can be inside at once (PathState::vstack)
+constexpr uint64_t kVStackEmpty = ~0ull;
 enum : uint32_t { FLAG_BOUNCE_MASK = 0xffffu, FLAG_LAST_DELTA = 1u << 16, FLAG_NEE_PENDING = 1u << 17, FLAG_BSDF_CAST = 1u << 18 };
 
 // dense ray queue: A = origin.xyz | t_max, B = direction.xyz | path id (bits)

@@ -318,6 +318,114 @@ def random_scene(seed, width=48, height=32, with_media=True, general=True) -> Sc
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# Participating-media scenes for the volume stack's edges (tests/test_gpu_media.py, tools/fuzz_parity.py --media).  The room of
+# cornell_models (light, main, right, left) lights them; the reference camera looks through the room centre.
+
+def media_room(width=48, height=32, extra=(), name="media") -> SceneDesc:
+    return SceneDesc.new(cornell_models()[:4] + list(extra), reference_camera(width / height), name)
+
+
+def _shell_volume(k):
+    """k-th volume of media_shells: absorption only, scattering only (alternating g), and both, in turn; no two equal"""
+    a = (0.2 + 0.05 * k, 0.5, 0.8 - 0.05 * k)
+    kind = k % 3
+    if kind == 0:
+        return Volume.new(a, 0.004, 0.0, 0.0)
+    if kind == 1:
+        return Volume.new((0.0, 0.0, 0.0), 0.0, 1.0 / (900.0 + 50.0 * k), 0.5 if k % 2 else -0.4)
+    return Volume.new(a, 0.002, 1.0 / (1200.0 + 50.0 * k), 0.3)
+
+
+def media_shells(n, width=48, height=32, ior=1.02, level=2) -> SceneDesc:
+    """n concentric smooth-dielectric spheres about the room centre, each with a volume of its own and an IOR near 1 (most rays go
+    straight through): a camera ray through the centre is inside all n volumes at the innermost one."""
+    models = []
+    for k in range(n):
+        t, nr = sphere_mesh(level, ROOM_CENTRE, 40.0 + 25.0 * (n - 1 - k))
+        models.append(_model(t, nr, Dielectric.new((0.98, 0.98, 0.98), ior + 0.001 * k, _shell_volume(k)), f"shell{k}"))
+    return media_room(width, height, models, f"media_shells_{n}")
+
+
+def media_chain(width=48, height=32, level=2) -> SceneDesc:
+    """three overlapping, non-nested scattering spheres.  The central camera ray enters A, B and C, then leaves B while inside A and
+    C (a removal from the middle of the stack), then A, then C."""
+    specs = [((-60.0, 50.0, 100.0), 150.0, Volume.new((0.3, 0.5, 0.7), 0.002, 1.0 / 700.0, 0.4)),
+             ((60.0, 50.0, 125.0), 75.0, Volume.new((0.0, 0.0, 0.0), 0.0, 1.0 / 300.0, -0.5)),
+             ((-30.0, 50.0, 0.0), 110.0, Volume.new((0.6, 0.3, 0.1), 0.003, 1.0 / 500.0, 0.0))]
+    models = []
+    for k, (c, r, v) in enumerate(specs):
+        t, nr = sphere_mesh(level, c, r)
+        models.append(_model(t, nr, Dielectric.new((0.97, 0.98, 0.99), 1.03, v), "ABC"[k]))
+    return media_room(width, height, models, "media_chain")
+
+
+def media_pair(variant, width=48, height=32, volume=None, level=2) -> SceneDesc:
+    """two overlapping glass spheres on the view axis with EQUAL volume-bearing materials.  variant "a": two models (two volumes in the
+    reference); "b": one model with two instances (one volume); "c": one model that holds both spheres' triangles (one volume).
+    The central camera ray enters the near sphere, enters the far one, then leaves the near one."""
+    vol = volume if volume is not None else Volume.new((0.9, 0.5, 0.2), 0.01, 0.0, 0.0)
+    glass = Dielectric.new((1.0, 1.0, 1.0), 1.5, vol)
+    near, far = (0.0, 50.0, 40.0), (0.0, 50.0, -40.0)
+    tn, nn = sphere_mesh(level, near, 100.0)
+    tf, nf = sphere_mesh(level, far, 100.0)
+    if variant == "a":
+        models = [_model(tn, nn, glass, "near"), _model(tf, nf, glass, "far")]
+    elif variant == "b":
+        t0, n0 = sphere_mesh(level, (0.0, 0.0, 0.0), 100.0)
+        mats = np.stack([IDENTITY_3x4, IDENTITY_3x4]).astype(np.float32)
+        mats[0, :, 3] = near
+        mats[1, :, 3] = far
+        models = [Model.new(t0.astype(np.float32), n0.astype(np.float32), glass, mats, "pair")]
+    elif variant == "c":
+        models = [_model(np.concatenate([tn, tf]), np.concatenate([nn, nf]), glass, "pair")]
+    else:
+        raise ValueError(variant)
+    return media_room(width, height, models, f"media_pair_{variant}")
+
+
+def media_scene(seed, width=48, height=32) -> SceneDesc:
+    """Seeded media fuzz scene: 2-9 overlapping or nested volume-bearing models (spheres, some instanced), some of them sharing one
+    material, with every volume kind and g from the whole clamped range."""
+    rng = np.random.default_rng(seed)
+
+    def volume():
+        kind = int(rng.integers(0, 3))
+        a = tuple(float(x) for x in rng.integers(0, 11, 3) / 10.0)
+        k = float(rng.choice([0.001, 0.005, 0.02])) if kind != 1 else 0.0
+        c = 1.0 / float(rng.integers(40, 2000)) if kind != 0 else 0.0
+        g = float(rng.choice([0.0, -0.9, -0.3, 0.3, 0.7, 0.999, -1.0, 2.0]))
+        return Volume.new(a, k, c, g)
+
+    mats = []
+    for _ in range(int(rng.integers(2, 6))):
+        pick = int(rng.integers(0, 3))
+        col = tuple(float(x) for x in 0.7 + rng.integers(0, 31, 3) / 100.0)
+        if pick == 0:
+            mats.append(Dielectric.new(col, float(rng.choice([1.0, 1.02, 1.33, 1.5])), volume()))
+        elif pick == 1:
+            mats.append(GGX.new_dielectric(col, float(rng.choice([0.05, 0.3])), float(rng.choice([1.05, 1.5])), volume()))
+        else:
+            mats.append(Dielectric.new(col, 1.01, volume()))
+    models = []
+    for k in range(int(rng.integers(2, 10))):
+        mat = mats[int(rng.integers(0, len(mats)))]
+        centre = np.array([rng.integers(-120, 121), rng.integers(-80, 141), rng.integers(-120, 121)], np.float64)
+        if rng.random() < 0.4 and models:
+            centre = np.asarray(models[-1][0], np.float64) + rng.integers(-30, 31, 3)       # nested in / overlapping the previous one
+        radius = float(rng.integers(30, 140))
+        mats_inst = None
+        if rng.random() < 0.3:
+            mats_inst = np.stack([IDENTITY_3x4, IDENTITY_3x4]).astype(np.float32)
+            mats_inst[1, :, 3] = rng.integers(-90, 91, 3).astype(np.float32)
+        models.append((centre, radius, mat, mats_inst, int(rng.integers(1, 3))))
+    out = []
+    for k, (c, r, mat, mi, level) in enumerate(models):
+        t, nr = sphere_mesh(level, tuple(c), r)
+        out.append(Model.new(t.astype(np.float32), nr.astype(np.float32), mat, mi, f"vol{k}"))
+    return media_room(width, height, out, f"media_{seed}")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # BASELINE.json configs[3] as SURVEY.md 8(d) fixes it: a procedurally generated ~250 k-triangle ATRIUM (columns / arches grid) —
 # what makes a Sponza-class scene different from one big mesh is many objects, heavy instancing, occlusion and a deep TLAS.
 

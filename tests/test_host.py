@@ -584,3 +584,39 @@ def test_rigid_assert_agrees_between_python_library_and_oracle(api, oracle_mod):
             got_or = False
         assert got_lib == want and got_or == want, (q, want, got_lib, got_or)
     assert seen[True] >= 20 and seen[False] >= 20
+
+
+def test_volumes_are_keyed_per_model_by_material_copies(api):
+    """pt_build gives every further model of a volume-bearing material an appended copy of it (the reference's BLAS owns its own
+    material: blas.rs:167,197): two models of one glass read two indices, two instances of one model read one, non-volume
+    materials stay shared, the caller's indices do not move, and a rebuild does not pile up copies."""
+    from path_tracer_amd import scenes
+    from path_tracer_amd.scene_desc import Model
+    for variant, distinct in (("a", 2), ("b", 1), ("c", 1)):
+        sc = scenes.media_pair(variant)
+        r = api.Renderer(sc, 48, 32)
+        n_mats = len(sc.materials())
+        glass = sc.materials().index(sc.models[-1].material)
+        for _ in range(2):
+            im = r.instance_materials(0)
+            room = im["blas"] < 4
+            assert len(set(im["material"][room].tolist())) == 4                           # light, gray, red, green
+            pair = im["material"][~room]
+            assert len(set(pair.tolist())) == distinct, (variant, im)
+            assert pair[im["blas"][~room] == im["blas"][~room].min()][0] == glass        # the first model keeps the caller's index
+            if distinct == 2:
+                assert sorted(set(pair.tolist())) == [glass, n_mats]                     # the copy is appended
+            r.rebuild()
+    # a non-volume material shared by models stays one index
+    base = scenes.cornell_box(48, 32)
+    r = api.Renderer(base, 48, 32)
+    im = r.instance_materials(0)
+    assert im["material"][im["blas"] == 4][0] == im["material"][im["blas"] == 5][0] == im["material"][im["blas"] == 1][0]
+    # the 255-material limit counts the copies
+    t, n = scenes.sphere_mesh(0, (0.0, 50.0, 0.0), 10.0)
+    glass = scenes.media_pair("a").models[-1].material
+    many = [Model.new(t.astype(np.float32), n.astype(np.float32), glass) for _ in range(252)]
+    with pytest.raises(api.PtError) as e:
+        api.Renderer(scenes.media_room(48, 32, many), 48, 32)
+    assert e.value.code == -5 and "255" in str(e.value)
+    api.Renderer(scenes.media_room(48, 32, many[:250]), 48, 32)                            # 5 materials + 249 copies = 254 indices

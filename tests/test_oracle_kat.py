@@ -176,3 +176,131 @@ def test_accumulation_is_sequential_and_resumable(oracle_mod, cornell64):
     assert_bit_equal(pos_f, pos_p, "position of last sample")
     assert np.array_equal(id_f, idp2)
     assert (full[..., 3] == 4).all()
+
+
+def _narrow(sc):
+    """the scene seen through a 1-degree lens along the room's view axis: every camera ray crosses the middle of the scene"""
+    from path_tracer_amd.scene_desc import Camera
+    sc.camera = Camera.new((0.0, 50.0, 1000.0), (0.0, 50.0, 0.0), 1.0, 1.0)
+    return sc
+
+
+@pytest.mark.parametrize("variant,depth", [("a", 2), ("b", 1), ("c", 1)])
+def test_oracle_keys_volumes_per_model(oracle_mod, variant, depth):
+    """volume.rs:146-162 keys a volume by the address of the material each BLAS owns (blas.rs:167,197): two models of one material
+    are two volumes, two instances of one model or one model holding both spheres are one.  A ray through the overlap reaches a
+    stack of 2, 1, 1 (counter 8, the deepest stack of the render)."""
+    from path_tracer_amd import scenes
+    o = oracle_mod.Oracle(_narrow(scenes.media_pair(variant)))
+    ctr = o.render(4, 4, 8, max_bounces=3)[3]
+    assert ctr.shape == (oracle_mod.N_COUNTERS,) and int(ctr[8]) == depth
+
+
+def test_oracle_volume_stack_is_unbounded(oracle_mod):
+    from path_tracer_amd import scenes
+    for n in (1, 5, 9):
+        assert int(oracle_mod.Oracle(scenes.media_shells(n)).render(48, 32, 2, max_bounces=12)[3][8]) == n
+
+
+def _stream_f32(L, seed, px, sm, k):
+    s0 = L.pto_stream_state0(seed, int(px), int(sm))
+    return np.float32(np.float32(L.pto_wyrand(s0, k) & 0xFFFFFFFF) / np.float32(4294967296.0))
+
+
+def volume_reference_f64(g, c, absorption_k, incoming, t_max, dist, u_t, u0, u1):
+    """volume.rs:32-60 (HG direction on the ONB of -incoming, onb.rs generate_onb), :83-97 (free flight) and :113 (Beer-Lambert) in
+    binary64, fed the binary32 material constants and uniforms the stream produced.  Returns scattered, t, z (along -incoming),
+    direction, transmission."""
+    g, c = np.float64(g), np.float64(c)
+    n = -np.asarray(incoming, np.float64)
+    t = -np.log(u_t) / c
+    if g == 0.0:
+        z = 1.0 - 2.0 * u1
+    else:
+        x = (1.0 - g * g) / (1.0 + g * (1.0 - 2.0 * u1))
+        z = (1.0 + g * g - x * x) / (2.0 * g)
+    r = np.sqrt(np.maximum(0.0, 1.0 - z * z))
+    phi = 2.0 * np.pi * u0
+    sign = np.where(np.signbit(n[:, 2]), -1.0, 1.0)
+    a = -1.0 / (sign + n[:, 2])
+    b = n[:, 0] * n[:, 1] * a
+    c0 = np.stack([1.0 + sign * n[:, 0] * n[:, 0] * a, sign * b, -sign * n[:, 0]], 1)
+    c1 = np.stack([b, sign + n[:, 1] * n[:, 1] * a, -n[:, 1]], 1)
+    d = c0 * (r * np.cos(phi))[:, None] + c1 * (r * np.sin(phi))[:, None] + n * z[:, None]
+    tr = np.exp(-np.asarray(absorption_k, np.float64)[None, :] * np.asarray(dist, np.float64)[:, None])
+    return ~(t > t_max), t, z, d, tr
+
+
+def check_volume_eval(out, vol, incoming, t_max, dist, u_t, u0, u1):
+    """out (pt_volume_eval / pto_volume_eval rows) against volume_reference_f64.  Tolerances: t and the transmission a few ulp; z
+    1e-6 plus the f32 formula's own conditioning (1 - g*g cancels near |g| = 1, and its rounding reaches z through x*x / 2g); the
+    whole direction where it is well conditioned (r = sin(theta) > 0.5), z alone elsewhere; a NaN direction only where |z| rounds
+    past 1."""
+    f32 = np.float32
+    g = float(np.clip(f32(vol.g), f32(-0.999), f32(0.999)))
+    ak = np.array([f32(a) * f32(vol.k) for a in vol.absorption], np.float64)
+    sc, t, z, d, tr = volume_reference_f64(g, f32(vol.c), ak, incoming, t_max.astype(np.float64), dist, u_t, u0, u1)
+    # the scatter decision: equal wherever t is not within rounding of t_max
+    clear = np.abs(t - t_max) > 1e-6 * np.abs(t) + 1e-30
+    assert np.array_equal(out[clear, 0] == 1.0, sc[clear])
+    s = out[:, 0] == 1.0
+    assert np.all(np.abs(out[s, 1] - t[s]) <= 4e-7 * t[s]), "free-flight distance"
+    assert np.all(out[:, 8] == np.where(vol.c != 0.0, np.where(s, 3.0, 1.0), 0.0)), "draws"
+    if g == 0.0:
+        tol_z = np.full(int(s.sum()), 1e-6)
+    else:
+        x = (1.0 - g * g) / (1.0 + g * (1.0 - 2.0 * u1[s]))
+        tol_z = 1e-6 + 2.0 * 2.0 ** -24 * (x * x * (2.0 / (1.0 - g * g) + 3.0) + 4.0) / (2.0 * abs(g))
+    dz = out[s, 2:5].astype(np.float64)
+    zz = (dz * -incoming[s].astype(np.float64)).sum(1)
+    finite = np.isfinite(dz).all(1)
+    assert np.all(np.abs(1.0 - np.abs(z[s][~finite])) < 4 * tol_z[~finite]), "a NaN direction away from |z| = 1"
+    assert np.all(np.abs(zz[finite] - z[s][finite]) <= tol_z[finite]), ("z along -incoming", np.max(np.abs(zz[finite] - z[s][finite])))
+    good = finite & (np.sqrt(np.maximum(0.0, 1.0 - z[s] ** 2)) > 0.5)
+    assert np.all(np.abs(dz[good] - d[s][good]) <= 2 * tol_z[good, None] + 1e-6), "direction"
+    # exp(-a * d): the product's rounding is amplified by |a * d| (exp's condition number)
+    e = ak[None, :] * dist.astype(np.float64)[:, None]
+    with np.errstate(under="ignore"):
+        ok = np.abs(out[:, 5:8] - tr) <= 6e-8 * (4.0 + 2.0 * e) * tr + 1e-44
+    assert ok.all(), "transmission"
+
+
+VOLUME_CASES = [(0.0, 1.0 / 50.0, 0.05), (0.3, 1.0 / 80.0, 0.0), (-0.6, 0.5, 1.0), (0.95, 1e-3, 0.01), (0.999, 1.0 / 50.0, 0.05),
+                (-0.999, 1.0 / 50.0, 0.05), (-5.0, 2.0, 30.0), (1e-30, 1.0 / 50.0, 0.05), (-0.0, 1.0 / 50.0, 0.05)]
+
+
+def volume_eval_inputs(n, seed):
+    rng = np.random.default_rng(seed)
+    inc = rng.normal(size=(n, 3))
+    inc = (inc / np.linalg.norm(inc, axis=1, keepdims=True)).astype(np.float32)
+    inc[:6] = np.array([[0, 0, -1], [0, 0, 1], [1, 0, 0], [0, -1, 0], [0, 0, -1], [0, 0, 1]], np.float32)
+    t_max = rng.uniform(0, 400, n).astype(np.float32)
+    t_max[::5] = np.inf
+    t_max[1::17] = 0.0
+    t_max[2::17] = np.float32(1e-42)
+    t_max[3::17] = np.float32(3e38)
+    dist = rng.uniform(0, 300, n).astype(np.float32)
+    dist[::13] = 0.0
+    dist[1::13] = np.float32(1e-40)
+    return inc, t_max, dist, rng.integers(0, 1 << 22, n).astype(np.uint32), rng.integers(0, 4096, n).astype(np.uint32)
+
+
+def volume_probe_scene(vol):
+    from path_tracer_amd import scenes
+    from path_tracer_amd.scene_desc import Dielectric, Model
+    t, nr = scenes.sphere_mesh(0, (0.0, 0.0, 0.0), 10.0)
+    return scenes.media_room(8, 8, [Model.new(t.astype(np.float32), nr.astype(np.float32), Dielectric.new((1.0, 1.0, 1.0), 1.5, vol))])
+
+
+@pytest.mark.parametrize("g,c,k", VOLUME_CASES)
+def test_oracle_volume_eval_matches_binary64(oracle_mod, g, c, k):
+    from path_tracer_amd.scene_desc import Volume
+    vol = Volume.new((0.4, 0.0, 0.9), k, c, g)
+    sc = volume_probe_scene(vol)
+    o = oracle_mod.Oracle(sc)
+    mi = len(sc.materials()) - 1
+    inc, t_max, dist, px, sm = volume_eval_inputs(2000, 7)
+    out = np.stack([o.volume_eval(mi, inc[i], t_max[i], dist[i], int(px[i]), int(sm[i]), 2) for i in range(len(px))])
+    L = oracle_mod.lib()
+    u = np.array([[_stream_f32(L, oracle_mod.DEFAULT_SEED, px[i], sm[i], 2 + j) for j in range(3)] for i in range(len(px))], np.float64)
+    check_volume_eval(out, vol, inc, t_max, dist, u[:, 0], u[:, 1], u[:, 2])

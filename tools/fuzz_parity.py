@@ -1,6 +1,8 @@
 """Extended randomized parity run (not part of the test suite): random scenes, per-sample radiance + frame + ray tallies, GPU vs oracle.
-Usage: python tools/fuzz_parity.py [first_seed] [n_seeds] [width height]   (default: tiny frames, 40x24 / 64x20; a few hundred pixels a side
-exercise the striped tails, tapered chunks and dynamic claims that tiny queues never reach)"""
+Usage: python tools/fuzz_parity.py [--media] [first_seed] [n_seeds] [width height]   (default: tiny frames, 40x24 / 64x20; a few hundred
+pixels a side exercise the striped tails, tapered chunks and dynamic claims that tiny queues never reach).
+--media: scenes.media_scene (2-9 overlapping / nested volume-bearing models, shared materials, instances).  A scene in which the oracle
+sees a path inside more than 8 volumes must fail with PT_ERR_LIMIT instead (counted apart, not a mismatch)."""
 import sys
 import time
 
@@ -10,6 +12,9 @@ sys.path.insert(0, __file__.rsplit("/tools/", 1)[0])
 from oracle import oracle as O
 from path_tracer_amd import api, scenes
 
+media = "--media" in sys.argv
+if media:
+    sys.argv.remove("--media")
 first = int(sys.argv[1]) if len(sys.argv) > 1 else 100
 count = int(sys.argv[2]) if len(sys.argv) > 2 else 40
 size = (int(sys.argv[3]), int(sys.argv[4])) if len(sys.argv) > 4 else None
@@ -25,12 +30,14 @@ def bits(a):
 
 
 bad = 0
+too_deep = 0
+depths = {}
 n_general = 0   # instance matrices that are rotations about a general axis (nine non-zero entries), summed over the scenes
 with_general = 0
 t0 = time.time()
 for seed in range(first, first + count):
     w, h = size if size else ((40, 24) if seed % 3 else (64, 20))
-    sc = scenes.random_scene(seed, w, h, with_media=(seed % 2 == 0))
+    sc = scenes.media_scene(seed, w, h) if media else scenes.random_scene(seed, w, h, with_media=(seed % 2 == 0))
     g = sum(int(np.count_nonzero(m[:, :3]) > 3) for mo in sc.models for m in mo.matrices)
     n_general += g
     with_general += 1 if g else 0
@@ -38,6 +45,21 @@ for seed in range(first, first + count):
     # every fourth scene keeps its BVH in global memory (the kernels the mesh configurations run)
     r = api.Renderer(sc, w, h, max_bounces=6 + seed % 9, flags=api.FLAG_NO_LDS_SCENE if seed % 4 == 3 else 0)
     mb = 6 + seed % 9
+    if media:
+        octr = o.render(w, h, 3, max_bounces=mb)[3]
+        depths[int(octr[8])] = depths.get(int(octr[8]), 0) + 1
+        if octr[8] > 8:
+            try:
+                r.render(0, 3)
+                ok = False
+            except api.PtError as e:
+                ok = e.code == -5
+            too_deep += 1
+            if not ok:
+                bad += 1
+                print("MISMATCH (no PT_ERR_LIMIT beyond 8 volumes) seed", seed, flush=True)
+            r.close()
+            continue
     ok = np.array_equal(bits(r.render_samples(0, 3)), bits(o.render_samples(w, h, 3, max_bounces=mb)))
     r.reset_stats(); r.reset_accumulation()
     acc, pos, idb = r.render(3, 2)
@@ -51,5 +73,7 @@ for seed in range(first, first + count):
     r.close()
     if (seed - first + 1) % every == 0:
         print(f"{seed - first + 1} scenes so far, {bad} mismatches, {time.time() - t0:.1f} s", flush=True)
+if media:
+    print(f"deepest volume stack per scene: {dict(sorted(depths.items()))}; {too_deep} beyond 8 (PT_ERR_LIMIT checked)")
 print(f"{count} scenes ({with_general} with at least one general rigid instance, {n_general} such instances in all), {bad} mismatches, {time.time() - t0:.1f} s")
 sys.exit(1 if bad else 0)
