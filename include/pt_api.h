@@ -83,7 +83,8 @@ enum
     PT_FLAG_TIMING = 1u,       /* bracket every world closest-hit launch with HIP events on the launch stream (ms_trace_closest) */
     PT_FLAG_NO_LDS_SCENE = 2u, /* force BVH reads from global memory even when the scene fits LDS */
     PT_FLAG_TIMING_ALL = 4u,   /* bracket every kernel launch (adds ~10 us of idle per launch; diagnostic) */
-    PT_FLAG_NO_PRIMARY_CULL = 8u /* generate and trace the camera rays of EVERY pixel, also where they provably miss the scene's bounds */
+    PT_FLAG_NO_PRIMARY_CULL = 8u, /* generate and trace the camera rays of EVERY pixel, also where they provably miss the scene's bounds */
+    PT_FLAG_GENERAL_WALK = 16u    /* traverse with the general two-level walk also where every instance of the TLAS is an identity */
 };
 
 /* ---- lifetime ------------------------------------------------------------------------------------------------ */
@@ -275,6 +276,9 @@ typedef struct pt_stats
                                         the shading pass answers them with that one slab test, tlas.rs:68-74) */
     uint64_t rays_primary_culled;    /* of rays_closest, camera rays of pixels whose every ray misses the world's root box: answered by
                                         the host's projection of that box onto the image plane, never generated */
+    uint32_t ident_tlas;             /* TLASes walked with one ray per lane (every instance an identity, no PT_FLAG_GENERAL_WALK):
+                                        bit 0 the world, bit 1 the lights */
+    uint32_t reserved_stats;
 } pt_stats;
 int pt_get_stats(pt_ctx* ctx, pt_stats* out);
 int pt_multi_get_stats(pt_multi* m, pt_stats* sum);   /* counters summed over the devices; ms_total = the slowest device's */

@@ -123,6 +123,7 @@ struct pt_ctx
     bool env_uploaded = false;
     SceneView sv{};
     bool lds_scene = false;
+    uint32_t ident_tlas = 0;       // FlatScene::ident_tlas of the resident scene
     uint32_t block_threads = 256, trace_blocks = 1024;
     bool class_present[Q_COUNT] = {true, false, false, false, false};
 
@@ -278,6 +279,7 @@ int upload_scene(pt_ctx* c)
     sv.blob_bytes = (uint32_t)blob.size();
     sv.stack_entries = f.stack_entries;
     sv.has_volumes = f.has_volumes ? 1u : 0u;
+    c->ident_tlas = f.ident_tlas;
 
     // launch geometry of the traversal kernels: BVH in LDS when it is small, per-lane stacks always in LDS
     c->lds_scene = blob.size() <= 48 * 1024 && !(c->cfg.flags & PT_FLAG_NO_LDS_SCENE);
@@ -322,6 +324,7 @@ TraceLaunch trace_launch(pt_ctx* c, int pipe = 0, bool side_stream = false)
     if (tl.scene.stack_spill) tl.scene.stack_spill += (size_t)(2 * pipe + (side_stream ? 1 : 0)) * c->spill_region_words;
     tl.blob = c->d_blob.p;
     tl.lds_scene = c->lds_scene;
+    tl.ident_tlas = (c->cfg.flags & PT_FLAG_GENERAL_WALK) ? 0u : c->ident_tlas;
     tl.grid_blocks = c->trace_blocks;
     tl.n_cus = (uint32_t)c->n_cus;
     tl.block_threads = c->block_threads;
@@ -2145,6 +2148,7 @@ int pt_multi_get_stats(pt_multi* m, pt_stats* sum)
         sum->ms_total = std::max(sum->ms_total, s.ms_total);
         sum->state_bytes += s.state_bytes;
         sum->scene_bytes = s.scene_bytes; sum->lds_scene = s.lds_scene; sum->stack_entries = s.stack_entries;
+        sum->ident_tlas = c->scene_uploaded && !(c->cfg.flags & PT_FLAG_GENERAL_WALK) ? c->ident_tlas : 0u;
     }
     return PT_OK;
 }
@@ -2153,6 +2157,7 @@ int pt_get_stats(pt_ctx* c, pt_stats* out)
 {
     if (!c || !out) return PT_ERR_ARG;
     *out = c->stats;
+    out->ident_tlas = c->scene_uploaded && !(c->cfg.flags & PT_FLAG_GENERAL_WALK) ? c->ident_tlas : 0u;
     return PT_OK;
 }
 

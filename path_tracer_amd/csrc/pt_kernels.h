@@ -12,6 +12,7 @@ struct TraceLaunch
     SceneView scene;
     const void* blob;        // contiguous nodes | tri_isect | instances (device), copied to LDS when lds_scene
     bool lds_scene;
+    uint32_t ident_tlas;     // IDENT_TLAS_*: TLASes the IDENT kernels may walk (one ray per lane)
     uint32_t grid_blocks;    // upper bound of the persistent grid (the launchers shrink it to what is resident at once)
     uint32_t n_cus;
     uint32_t block_threads;  // 64..256

@@ -142,6 +142,9 @@ constexpr int shade_waves(uint32_t qclass, bool volumes)
 #ifndef PT_INLINE_SHADOW
 #define PT_INLINE_SHADOW 1
 #endif
+#ifndef PT_IDENT_SHADE
+#define PT_IDENT_SHADE 1 // the Lambertian shading pass's inline shadow walk also takes the one-ray walk on identity-only scenes (ident_ray)
+#endif
 #ifndef PT_SHADE_WAVES_INLINE
 #define PT_SHADE_WAVES_INLINE 5
 #endif
@@ -656,6 +659,52 @@ __device__ __forceinline__ LaneRay to_object(const Blob& bl, uint32_t inst, cons
     return r;
 }
 
+// Identity-only TLAS (IDENT kernels, SceneView::ident_tlas): every instance the walk can meet is an identity instance, so the object ray
+// is the same function of the world ray everywhere, and the walk keeps ONE ray per lane for TLAS boxes, BLAS boxes and triangles:
+// o and d are to_object's identity image (bit-exact, triangles see what they see today), inv is the WORLD ray's reciprocal.  An
+// instance visit is then "note the instance, continue at its BLAS root"; no matrix, no in_blas / blas_base, no per-level select.
+//   TLAS boxes: slab(box, o', inv) == slab(box, o, inv).  o' differs from o only in the sign of a zero component; (m - o) then
+//     differs only in the sign of a zero, times inv only in the sign of a zero (or is NaN in both: 0 * inf).  A zero t can never be
+//     t_enter (max with EPS > 0), and a zero far bound fails `ts <= tb` whatever its sign: the hit bit and t_enter agree.
+//   BLAS boxes: the reference uses 1/d' (to_object: +-inf signed like d' where d is +-0), here 1/d (signed like d).  They differ
+//     only on an axis c with d_c = +-0, and only when o_c lies outside the box's slab on c: one sign gives the empty interval
+//     (-inf, -inf) (a miss), the other (+inf, +inf), a hit only with t_enter = +inf.  Every box under that one lies outside on c too
+//     (a BVH node's box encloses its children's), so every triangle under it is tested at t_estimate = +inf, where
+//     ray.at(t_estimate) has the coordinate d_c * inf + o_c = NaN and tri_planes / tri_eval reject it.  A subtree entered at +inf
+//     therefore accepts nothing, and the triangles that can be accepted are met in the same order with the same t_estimate: same
+//     answer.  (The BLAS root itself, entered at t = 0 with no box test by the closest-hit walk, sees the exact o', d'.)  The
+//     other choice, 1/d' also on TLAS boxes, would not be exact: it can enter an instance the reference skips, and that instance's
+//     root leaf is tested at t = 0.
+//   Non-finite rays (a component of o or d inf or NaN): to_object's full arithmetic multiplies it by a zero of the inverse
+//     matrix, so o' or d' carries a NaN in some component, and so does ray.at(t) for every t: no triangle of an identity
+//     instance is ever accepted.  IDENT walks retire such a ray at set-up with the answer "nothing hit" (closest: MISS_ID,
+//     t = inf; any: not occluded).
+__device__ __forceinline__ LaneRay ident_ray(const LaneRay& w)
+{
+    const uint32_t so = asu(w.o.x) & asu(w.o.y) & asu(w.o.z) & 0x80000000u;
+    const uint32_t sd = asu(w.d.x) & asu(w.d.y) & asu(w.d.z) & 0x80000000u;
+    LaneRay r;
+    r.o.x = w.o.x != 0.0f ? w.o.x : asf(so);
+    r.o.y = w.o.y != 0.0f ? w.o.y : asf(so);
+    r.o.z = w.o.z != 0.0f ? w.o.z : asf(so);
+    r.d.x = w.d.x != 0.0f ? w.d.x : asf(sd);
+    r.d.y = w.d.y != 0.0f ? w.d.y : asf(sd);
+    r.d.z = w.d.z != 0.0f ? w.d.z : asf(sd);
+    r.inv = w.inv;
+    return r;
+}
+// the world ray's six sign bits (o.xyz in bits 0-2, d.xyz in bits 3-5): with them ident_ray's o and d give back the world ray exactly
+__device__ __forceinline__ uint32_t ray_signs(const LaneRay& w)
+{
+    return (asu(w.o.x) >> 31) | ((asu(w.o.y) >> 31) << 1) | ((asu(w.o.z) >> 31) << 2) |
+           ((asu(w.d.x) >> 31) << 3) | ((asu(w.d.y) >> 31) << 4) | ((asu(w.d.z) >> 31) << 5);
+}
+__device__ __forceinline__ f3 with_signs(const f3 v, uint32_t bits)
+{
+    return f3{asf((asu(v.x) & 0x7fffffffu) | ((bits & 1u) << 31)), asf((asu(v.y) & 0x7fffffffu) | (((bits >> 1) & 1u) << 31)),
+              asf((asu(v.z) & 0x7fffffffu) | (((bits >> 2) & 1u) << 31))};
+}
+
 template <bool LDS_SCENE>
 __device__ __forceinline__ Blob stage_scene(const SceneView& sv, const uint4* __restrict__ gblob, uint4* smem, uint32_t& words)
 {
@@ -786,7 +835,7 @@ __device__ __forceinline__ ClosestOutPtr launder_args(ClosestOutPtr p)
     return p;
 }
 // (the kernel's body as a function of the staged scene: k_closest is one launch of it, k_trace_fused runs it before another)
-template <int BVH, int MODE, bool SPILL>
+template <int BVH, int MODE, bool SPILL, bool IDENT>
 __device__ __forceinline__ void closest_body(const SceneView& sv, const Blob& bl, const uint32_t blob_words, uint4* smem, const uint32_t root, const f4* __restrict__ ra,
                                              const f4* __restrict__ rb, const uint32_t* __restrict__ n_ptr, const uint32_t cap_in,
                                              uint32_t* __restrict__ heads, const ClosestOutPtr outp)
@@ -800,7 +849,8 @@ __device__ __forceinline__ void closest_body(const SceneView& sv, const Blob& bl
 
     bool active = false, pending = false, ray_finite = false;
     uint32_t ray_idx = 0, pid = 0;
-    LaneRay w{}, ob{};
+    LaneRay w{}, ob{};    // IDENT: ob is the lane's only ray (ident_ray); w is rebuilt from it and w_signs when the ray retires
+    uint32_t w_signs = 0u;
     float t_max = 0.0f, bt = 0.0f;
     float hud = 0.0f, hvd = 0.0f, hdet = 1.0f; // best hit's (u, v) numerators and determinant: divided once, when the ray retires (primitive.rs:158-160)
     uint32_t bid = MISS_ID, sp = stk.empty(), blas_base = 0, inst = 0;
@@ -849,6 +899,7 @@ __device__ __forceinline__ void closest_body(const SceneView& sv, const Blob& bl
             {
                 if (MODE == CLOSEST_WORLD || MODE == CLOSEST_PRIMARY)
                 {
+                    if (IDENT && pending) { w.o = with_signs(ob.o, w_signs); w.d = with_signs(ob.d, w_signs >> 3); } // the world ray, bit-exact
                     uint64_t qm = pm;
                     if (MODE == CLOSEST_PRIMARY)
                     {
@@ -994,6 +1045,7 @@ __device__ __forceinline__ void closest_body(const SceneView& sv, const Blob& bl
                 w.d = xyz(b);
                 w.inv = rcp3(w.d);
                 ray_finite = finite3(w.o) && finite3(w.d);
+                if (IDENT) { ob = ident_ray(w); w_signs = ray_signs(w); }
                 bid = MISS_ID;
                 any_phase = false;
                 chain_code = 2u;
@@ -1006,7 +1058,8 @@ __device__ __forceinline__ void closest_body(const SceneView& sv, const Blob& bl
                 // TLAS::intersect: root box test, then (root, 0.0)   tlas.rs:68-74
                 float te;
                 const uint4 root0 = bl.nodes[2u * root];
-                const bool ok = (t_max == t_max) && slab(root0, bl.nodes[2u * root + 1u], w.o, w.inv, t_max, te);
+                // (IDENT: a non-finite ray can hit nothing, see ident_ray)
+                const bool ok = (t_max == t_max) && (!IDENT || ray_finite) && slab(root0, bl.nodes[2u * root + 1u], IDENT ? ob.o : w.o, w.inv, t_max, te);
                 if (ok)
                 {
                     stk.put(sp, make_uint2(root0.w, 0u));    // entries are (link, t_enter); the root goes in with t_enter 0
@@ -1035,7 +1088,7 @@ __device__ __forceinline__ void closest_body(const SceneView& sv, const Blob& bl
             }
 #endif
             if (!active) continue;
-            if (in_blas && sp == blas_base) in_blas = false; // BLAS::intersect returned  blas.rs:255
+            if (!IDENT && in_blas && sp == blas_base) in_blas = false; // BLAS::intersect returned  blas.rs:255
             if (MODE == CLOSEST_LIGHTS && any_phase)
             {
                 // TLAS::any_intersect on the world with t_max = light_t * (1 - EPS)   tlas.rs:111-144, blas.rs:257-294; entries are
@@ -1048,9 +1101,17 @@ __device__ __forceinline__ void closest_body(const SceneView& sv, const Blob& bl
                 if ((link >> NODE_KIND_SHIFT) == NODE_INSTANCE)
                 {
                     uint4 r0, r1;
-                    ob = to_object<!LDS_SCENE, true>(bl, link & NODE_PAYLOAD_MASK, w, ray_finite, r0, r1);
-                    in_blas = true;
-                    blas_base = sp;
+                    if (IDENT)
+                    {
+                        const uint4* ip = bl.inst + INST_WORDS * (link & NODE_PAYLOAD_MASK) + INST_ROOT_WORD;
+                        r0 = ip[0]; r1 = ip[1];
+                    }
+                    else
+                    {
+                        ob = to_object<!LDS_SCENE, true>(bl, link & NODE_PAYLOAD_MASK, w, ray_finite, r0, r1);
+                        in_blas = true;
+                        blas_base = sp;
+                    }
                     if (!slab(r0, r1, ob.o, ob.inv, t_max, t_enter)) continue;
                     link = r0.w;
                 }
@@ -1059,7 +1120,7 @@ __device__ __forceinline__ void closest_body(const SceneView& sv, const Blob& bl
                 {
                     const uint4* cp = bl.nodes + 2u * kpay;
                     const uint4 l0 = cp[0], l1 = cp[1], r0 = cp[2], r1 = cp[3];
-                    const f3 so = in_blas ? ob.o : w.o, sinv = in_blas ? ob.inv : w.inv;
+                    const f3 so = (IDENT || in_blas) ? ob.o : w.o, sinv = (IDENT || in_blas) ? ob.inv : w.inv;
                     float tl, tr;
                     const bool hl = slab(l0, l1, so, sinv, t_max, tl);
                     const bool hr = slab(r0, r1, so, sinv, t_max, tr);
@@ -1097,7 +1158,7 @@ __device__ __forceinline__ void closest_body(const SceneView& sv, const Blob& bl
                     float te = 0.0f;
                     const uint4 wr0 = bl.nodes[2u * lights_world_root];
                     // NaN t_max: every box test fails -> visible; so does a ray that misses the world's root box (tlas.rs:118-121)
-                    if (t_max == t_max && slab(wr0, bl.nodes[2u * lights_world_root + 1u], w.o, w.inv, t_max, te)) { stk.put(sp, make_uint2(wr0.w, asu(te))); sp = stk.up(sp); }
+                    if (t_max == t_max && slab(wr0, bl.nodes[2u * lights_world_root + 1u], IDENT ? ob.o : w.o, IDENT ? ob.inv : w.inv, t_max, te)) { stk.put(sp, make_uint2(wr0.w, asu(te))); sp = stk.up(sp); }
                     else { active = false; pending = true; chain_code = 0u; }
                     continue;
                 }
@@ -1119,9 +1180,13 @@ __device__ __forceinline__ void closest_body(const SceneView& sv, const Blob& bl
                 // with t_enter = 0 and no box test (blas.rs:217) and pops it at once: that pop happens here, in the same step.
                 uint4 root0, root1;
                 inst = link & NODE_PAYLOAD_MASK;
-                ob = to_object<!LDS_SCENE, false>(bl, inst, w, ray_finite, root0, root1);
-                in_blas = true;
-                blas_base = sp;
+                if (IDENT) root0.w = reinterpret_cast<const uint32_t*>(bl.inst + INST_WORDS * inst + INST_ROOT_WORD)[3];
+                else
+                {
+                    ob = to_object<!LDS_SCENE, false>(bl, inst, w, ray_finite, root0, root1);
+                    in_blas = true;
+                    blas_base = sp;
+                }
                 if (0.0f > t_max) continue;                  // the root's pop test  blas.rs:222-225
                 link = root0.w;
                 t_est = 0.0f;
@@ -1139,7 +1204,7 @@ __device__ __forceinline__ void closest_body(const SceneView& sv, const Blob& bl
             {
                 const uint4* cp = bl.nodes + 2u * payload; // the children are one contiguous 64-byte record pair
                 const uint4 l0 = cp[0], l1 = cp[1], r0 = cp[2], r1 = cp[3];
-                const f3 o = in_blas ? ob.o : w.o, inv = in_blas ? ob.inv : w.inv;
+                const f3 o = (IDENT || in_blas) ? ob.o : w.o, inv = (IDENT || in_blas) ? ob.inv : w.inv;
                 float tl, tr;
                 const bool hl = slab(l0, l1, o, inv, t_max, tl);
                 const bool hr = slab(r0, r1, o, inv, t_max, tr);
@@ -1235,7 +1300,7 @@ __device__ __forceinline__ void closest_body(const SceneView& sv, const Blob& bl
     // any-hit casts of integrator.rs:103
     if (MODE == CLOSEST_LIGHTS) add_tally(heads, light_hits, HEAD_TALLY1);
 }
-template <int BVH, int MODE, bool SPILL>
+template <int BVH, int MODE, bool SPILL, bool IDENT = false>
 __global__ void __launch_bounds__(256, BVH != 0 ? PT_WAVES_LDS_BVH : PT_WAVES_GLOBAL_BVH) k_closest(const ClosestKArgs a)
 {
     constexpr bool LDS_SCENE = BVH != 0;
@@ -1245,7 +1310,7 @@ __global__ void __launch_bounds__(256, BVH != 0 ? PT_WAVES_LDS_BVH : PT_WAVES_GL
     uint32_t blob_words;
     const Blob bl = stage_scene<LDS_SCENE>(a.sv, a.gblob, smem, blob_words);
     const ClosestOutPtr outp = &((ClosestKArgsPtr)__builtin_amdgcn_kernarg_segment_ptr())->out;
-    closest_body<BVH, MODE, SPILL>(a.sv, bl, blob_words, smem, a.root, a.ra, a.rb, a.n_ptr, a.cap_in, a.heads, outp);
+    closest_body<BVH, MODE, SPILL, IDENT>(a.sv, bl, blob_words, smem, a.root, a.ra, a.rb, a.n_ptr, a.cap_in, a.heads, outp);
 }
 
 // ------------------------------------------------------------------------------------------------ any hit
@@ -1256,7 +1321,7 @@ enum { ANY_SHADOW = 0, ANY_HOOK = 2 };
 // box's own entry distance, so neither the visiting order nor the moment a box is tested can change it.  Here a node's box is
 // tested when its parent is expanded (the instance's BLAS root right after the ray transform) and only nodes that were hit go
 // on the stack, with their entry distance: a missed child costs a slab test instead of a full traversal step.
-template <int BVH, int MODE, bool SPILL>
+template <int BVH, int MODE, bool SPILL, bool IDENT>
 __device__ __forceinline__ void any_body(const SceneView& sv, const Blob& bl, const uint32_t blob_words, uint4* smem, const uint32_t root, const f4* __restrict__ ra,
                                          const f4* __restrict__ rb, const uint32_t* __restrict__ n_ptr, const uint32_t cap_in,
                                          uint32_t* __restrict__ heads, uint32_t* __restrict__ occluded,
@@ -1334,13 +1399,15 @@ __device__ __forceinline__ void any_body(const SceneView& sv, const Blob& bl, co
                 w.d = xyz(b);
                 w.inv = rcp3(w.d);
                 ray_finite = finite3(w.o) && finite3(w.d);
+                if (IDENT) ob = ident_ray(w);
                 t_max = a.w;
                 in_blas = false;
                 sp = stk.empty();
-                // the TLAS root's own box (tlas.rs:118-121); a NaN t_max fails every reference box test -> not occluded
+                // the TLAS root's own box (tlas.rs:118-121); a NaN t_max fails every reference box test -> not occluded (and so, with
+                // IDENT, does a non-finite ray: ident_ray)
                 float te;
                 const uint4 root0 = bl.nodes[2u * root];
-                const bool ok = (t_max == t_max) && slab(root0, bl.nodes[2u * root + 1u], w.o, w.inv, t_max, te);
+                const bool ok = (t_max == t_max) && (!IDENT || ray_finite) && slab(root0, bl.nodes[2u * root + 1u], IDENT ? ob.o : w.o, w.inv, t_max, te);
                 if (ok)
                 {
                     stk.put(sp, make_uint2(root0.w, asu(te)));
@@ -1365,7 +1432,7 @@ __device__ __forceinline__ void any_body(const SceneView& sv, const Blob& bl, co
             }
 #endif
             if (!active) continue;
-            if (in_blas && sp == blas_base) in_blas = false;
+            if (!IDENT && in_blas && sp == blas_base) in_blas = false;
             if (sp == stk.empty())
             {
                 active = false;
@@ -1383,9 +1450,17 @@ __device__ __forceinline__ void any_body(const SceneView& sv, const Blob& bl, co
             {
                 // TLAS leaf: transform the ray; the BLAS root's box is the first thing BLAS::any_intersect tests  blas.rs:262-264
                 uint4 r0, r1;
-                ob = to_object<!LDS_SCENE, true>(bl, link & NODE_PAYLOAD_MASK, w, ray_finite, r0, r1);
-                in_blas = true;
-                blas_base = sp;
+                if (IDENT)
+                {
+                    const uint4* ip = bl.inst + INST_WORDS * (link & NODE_PAYLOAD_MASK) + INST_ROOT_WORD;
+                    r0 = ip[0]; r1 = ip[1];
+                }
+                else
+                {
+                    ob = to_object<!LDS_SCENE, true>(bl, link & NODE_PAYLOAD_MASK, w, ray_finite, r0, r1);
+                    in_blas = true;
+                    blas_base = sp;
+                }
                 if (!slab(r0, r1, ob.o, ob.inv, t_max, t_enter)) continue;
                 link = r0.w;
             }
@@ -1400,7 +1475,7 @@ __device__ __forceinline__ void any_body(const SceneView& sv, const Blob& bl, co
             {
                 const uint4* cp = bl.nodes + 2u * payload;
                 const uint4 l0 = cp[0], l1 = cp[1], r0 = cp[2], r1 = cp[3];
-                const f3 o = in_blas ? ob.o : w.o, inv = in_blas ? ob.inv : w.inv;
+                const f3 o = (IDENT || in_blas) ? ob.o : w.o, inv = (IDENT || in_blas) ? ob.inv : w.inv;
                 float tl, tr;
                 const bool hl = slab(l0, l1, o, inv, t_max, tl);
                 const bool hr = slab(r0, r1, o, inv, t_max, tr);
@@ -1467,7 +1542,7 @@ __device__ __forceinline__ void any_body(const SceneView& sv, const Blob& bl, co
     }
 #endif
 }
-template <int BVH, int MODE, bool SPILL>
+template <int BVH, int MODE, bool SPILL, bool IDENT = false>
 __global__ void __launch_bounds__(256, BVH != 0 ? PT_WAVES_LDS_BVH_ANY : PT_WAVES_GLOBAL_BVH_ANY) k_any(const SceneView sv, const uint4* __restrict__ gblob, const uint32_t root, const f4* __restrict__ ra,
                                               const f4* __restrict__ rb, const uint32_t* __restrict__ n_ptr, const uint32_t cap_in,
                                               uint32_t* __restrict__ heads, uint32_t* __restrict__ occluded,
@@ -1478,7 +1553,7 @@ __global__ void __launch_bounds__(256, BVH != 0 ? PT_WAVES_LDS_BVH_ANY : PT_WAVE
     if (blockIdx.x >= fetch_plan(min(*n_ptr, cap_in), LDS_SCENE ? (uint32_t)PT_CHUNK_DIV : (uint32_t)PT_CHUNK_DIV_GLOBAL_BVH, (uint32_t)PT_TAPER_ANY).blocks) return;
     uint32_t blob_words;
     const Blob bl = stage_scene<LDS_SCENE>(sv, gblob, smem, blob_words);
-    any_body<BVH, MODE, SPILL>(sv, bl, blob_words, smem, root, ra, rb, n_ptr, cap_in, heads, occluded, radiance);
+    any_body<BVH, MODE, SPILL, IDENT>(sv, bl, blob_words, smem, root, ra, rb, n_ptr, cap_in, heads, occluded, radiance);
 }
 
 // One launch for two of the three traversals between two shading passes: the world closest-hit rays of bounce b, then the (few)
@@ -1505,7 +1580,7 @@ struct FusedKArgs
     FusedArgs fa;
     ClosestOut wout, lout;
 };
-template <int BVH, bool SPILL>
+template <int BVH, bool SPILL, bool IDENT = false>
 __global__ void __launch_bounds__(256, BVH != 0 ? PT_WAVES_LDS_BVH : PT_WAVES_GLOBAL_BVH) k_trace_fused(const FusedKArgs a)
 {
     constexpr bool LDS_SCENE = BVH != 0;
@@ -1517,8 +1592,8 @@ __global__ void __launch_bounds__(256, BVH != 0 ? PT_WAVES_LDS_BVH : PT_WAVES_GL
     const Blob bl = stage_scene<LDS_SCENE>(a.sv, a.gblob, smem, blob_words);
     typedef const __attribute__((address_space(4))) FusedKArgs* FusedKArgsPtr;
     const FusedKArgsPtr k = (FusedKArgsPtr)__builtin_amdgcn_kernarg_segment_ptr();
-    closest_body<BVH, CLOSEST_WORLD, SPILL>(a.sv, bl, blob_words, smem, a.fa.world_root, a.fa.wa, a.fa.wb, a.fa.wn, a.fa.cap_in, a.fa.wheads, &k->wout);
-    closest_body<BVH, CLOSEST_LIGHTS, SPILL>(a.sv, bl, blob_words, smem, a.fa.lights_root, a.fa.la, a.fa.lb, a.fa.ln, a.fa.cap_in, a.fa.lheads, &k->lout);
+    closest_body<BVH, CLOSEST_WORLD, SPILL, IDENT>(a.sv, bl, blob_words, smem, a.fa.world_root, a.fa.wa, a.fa.wb, a.fa.wn, a.fa.cap_in, a.fa.wheads, &k->wout);
+    closest_body<BVH, CLOSEST_LIGHTS, SPILL, IDENT>(a.sv, bl, blob_words, smem, a.fa.lights_root, a.fa.la, a.fa.lb, a.fa.ln, a.fa.cap_in, a.fa.lheads, &k->lout);
 }
 
 // ------------------------------------------------------------------------------------------------ path bookkeeping
@@ -1740,6 +1815,7 @@ __global__ void __launch_bounds__(256) k_shade_terminal(const SceneView sv, cons
 // TLAS::any_intersect for ONE ray per lane, run by the whole wave until its last ray is done (no refill): the shading pass of an LDS-resident scene
 // answers its own explicit-light shadow ray with it (k_shade_surface<.., INLINE>).  Steps as in any_body: a node's box is tested when its parent is
 // expanded, only nodes that were met go on the stack; the answer is a disjunction, so the order cannot change it.
+template <bool IDENT>
 __device__ __forceinline__ bool inline_any(const Blob& bl, const Stack8<false>& stk, const uint32_t root, const f4 ra, const f4 rb, const bool want)
 {
     bool active = false, blocked = false, in_blas = false, ray_finite = false;
@@ -1752,9 +1828,10 @@ __device__ __forceinline__ bool inline_any(const Blob& bl, const Stack8<false>& 
         w.d = xyz(rb);
         w.inv = rcp3(w.d);
         ray_finite = finite3(w.o) && finite3(w.d);
+        if (IDENT) ob = ident_ray(w);
         float te;
         const uint4 root0 = bl.nodes[2u * root];
-        if ((t_max == t_max) && slab(root0, bl.nodes[2u * root + 1u], w.o, w.inv, t_max, te))
+        if ((t_max == t_max) && (!IDENT || ray_finite) && slab(root0, bl.nodes[2u * root + 1u], IDENT ? ob.o : w.o, w.inv, t_max, te))
         {
             stk.put(sp, make_uint2(root0.w, asu(te)));
             sp = stk.up(sp);
@@ -1764,7 +1841,7 @@ __device__ __forceinline__ bool inline_any(const Blob& bl, const Stack8<false>& 
     while (__ballot(active) != 0ull)
     {
         if (!active) continue;
-        if (in_blas && sp == blas_base) in_blas = false;
+        if (!IDENT && in_blas && sp == blas_base) in_blas = false;
         if (sp == stk.empty()) { active = false; continue; }
         sp = stk.down(sp);
         const uint2 e = stk.get(sp);
@@ -1773,9 +1850,17 @@ __device__ __forceinline__ bool inline_any(const Blob& bl, const Stack8<false>& 
         if ((link >> NODE_KIND_SHIFT) == NODE_INSTANCE)
         {
             uint4 r0, r1;
-            ob = to_object<false, true>(bl, link & NODE_PAYLOAD_MASK, w, ray_finite, r0, r1);
-            in_blas = true;
-            blas_base = sp;
+            if (IDENT)
+            {
+                const uint4* ip = bl.inst + INST_WORDS * (link & NODE_PAYLOAD_MASK) + INST_ROOT_WORD;
+                r0 = ip[0]; r1 = ip[1];
+            }
+            else
+            {
+                ob = to_object<false, true>(bl, link & NODE_PAYLOAD_MASK, w, ray_finite, r0, r1);
+                in_blas = true;
+                blas_base = sp;
+            }
             if (!slab(r0, r1, ob.o, ob.inv, t_max, t_enter)) continue;
             link = r0.w;
         }
@@ -1785,7 +1870,7 @@ __device__ __forceinline__ bool inline_any(const Blob& bl, const Stack8<false>& 
         {
             const uint4* cp = bl.nodes + 2u * payload;
             const uint4 l0 = cp[0], l1 = cp[1], r0 = cp[2], r1 = cp[3];
-            const f3 o = in_blas ? ob.o : w.o, inv = in_blas ? ob.inv : w.inv;
+            const f3 o = (IDENT || in_blas) ? ob.o : w.o, inv = (IDENT || in_blas) ? ob.inv : w.inv;
             float tl, tr;
             const bool hl = slab(l0, l1, o, inv, t_max, tl);
             const bool hr = slab(r0, r1, o, inv, t_max, tr);
@@ -1840,7 +1925,7 @@ __device__ __forceinline__ const ShadeKArgs& shade_args()
     [[maybe_unused]] const SceneView& sv = ka_.sv;                                                                                 \
     [[maybe_unused]] const RenderParams& rp = ka_.rp;                                                                              \
     [[maybe_unused]] const ShadeIO& io = ka_.io;
-template <uint32_t QCLASS, bool VOLUMES, bool INLINE = false>
+template <uint32_t QCLASS, bool VOLUMES, bool INLINE = false, bool IDENT = false>
 __global__ void __launch_bounds__(PT_SHADE_THREADS, INLINE ? PT_SHADE_WAVES_INLINE : shade_waves(QCLASS, VOLUMES)) k_shade_surface(const ShadeKArgs kargs)
 {
     extern __shared__ uint4 smem_dyn[];
@@ -2190,7 +2275,7 @@ __global__ void __launch_bounds__(PT_SHADE_THREADS, INLINE ? PT_SHADE_WAVES_INLI
             const Stack8<false> stk{reinterpret_cast<char*>(smem_dyn), blob_words * 16u + tid * 8u, blockDim.x * 8u};
             traced += (uint32_t)__popcll(__ballot(want_shadow)); // (both counted here, where the whole wave is: wave-uniform values in scalar registers)
             culled += (uint32_t)__popcll(__ballot(cull_now));
-            const bool blocked = inline_any(bl, stk, ka2.world_root, sh_a, sh_b, want_shadow);
+            const bool blocked = inline_any<IDENT>(bl, stk, ka2.world_root, sh_a, sh_b, want_shadow);
             if (want_shadow)
             {
                 DPathRec* rec = shade_args().io.st.rec + pid;
@@ -2473,17 +2558,34 @@ static uint32_t resident_grid(K kernel, const TraceLaunch& tl, size_t lds)
 #endif
 }
 
+// the TLASes a launch from `root` walks: its own, and for CLOSEST_LIGHTS the world's as well (the any-hit phase)
+static uint32_t tlas_bits(const TraceLaunch& tl, uint32_t root, bool with_world)
+{
+    const uint32_t own = root == tl.scene.world_root ? (uint32_t)IDENT_TLAS_WORLD : root == tl.scene.lights_root ? (uint32_t)IDENT_TLAS_LIGHTS : ~0u;
+    return own | (with_world ? (uint32_t)IDENT_TLAS_WORLD : 0u);
+}
+// the IDENT kernels (one ray per lane, ident_ray) walk a launch whose every TLAS holds identity instances only
+static bool ident_walk(const TraceLaunch& tl, uint32_t bits) { return (tl.ident_tlas & bits) == bits; }
+
 template <int MODE>
 static void launch_closest_impl(hipStream_t s, const TraceLaunch& tl, uint32_t root, const RayQueue& rq, const uint32_t* n_ptr, uint32_t cap_in,
                                 uint32_t* heads, const ClosestOut& out)
 {
+    const bool ident = ident_walk(tl, tlas_bits(tl, root, MODE == CLOSEST_LIGHTS));
     const bool spill = tl.scene.stack_entries > tl.scene.stack_lds;
     const dim3 block(tl.block_threads);
     const uint4* blob = (const uint4*)tl.blob;
     const size_t lds = trace_lds_bytes(tl);
     const ClosestKArgs ka{tl.scene, blob, rq.a, rq.b, n_ptr, heads, root, cap_in, out};
 #define PT_LAUNCH1(K) hipLaunchKernelGGL(K, dim3(resident_grid(K, tl, lds)), block, lds, s, ka)
-    if (tl.lds_scene && !spill) PT_LAUNCH1((k_closest<1, MODE, false>));
+    if (ident)
+    {
+        if (tl.lds_scene && !spill) PT_LAUNCH1((k_closest<1, MODE, false, true>));
+        else if (tl.lds_scene) PT_LAUNCH1((k_closest<1, MODE, true, true>));
+        else if (!spill) PT_LAUNCH1((k_closest<0, MODE, false, true>));
+        else PT_LAUNCH1((k_closest<0, MODE, true, true>));
+    }
+    else if (tl.lds_scene && !spill) PT_LAUNCH1((k_closest<1, MODE, false>));
     else if (tl.lds_scene) PT_LAUNCH1((k_closest<1, MODE, true>));
     else if (!spill) PT_LAUNCH1((k_closest<0, MODE, false>));
     else PT_LAUNCH1((k_closest<0, MODE, true>));
@@ -2493,12 +2595,20 @@ template <int MODE>
 static void launch_any_impl(hipStream_t s, const TraceLaunch& tl, uint32_t root, const RayQueue& rq, const uint32_t* n_ptr, uint32_t cap_in,
                             uint32_t* heads, uint32_t* occluded, f4* radiance = nullptr)
 {
+    const bool ident = ident_walk(tl, tlas_bits(tl, root, false));
     const size_t lds = trace_lds_bytes(tl);
     const bool spill = tl.scene.stack_entries > tl.scene.stack_lds;
     const dim3 block(tl.block_threads);
     const uint4* blob = (const uint4*)tl.blob;
 #define PT_LAUNCH(K) hipLaunchKernelGGL(K, dim3(resident_grid(K, tl, lds)), block, lds, s, tl.scene, blob, root, rq.a, rq.b, n_ptr, cap_in, heads, occluded, radiance)
-    if (tl.lds_scene && !spill) PT_LAUNCH((k_any<1, MODE, false>));
+    if (ident)
+    {
+        if (tl.lds_scene && !spill) PT_LAUNCH((k_any<1, MODE, false, true>));
+        else if (tl.lds_scene) PT_LAUNCH((k_any<1, MODE, true, true>));
+        else if (!spill) PT_LAUNCH((k_any<0, MODE, false, true>));
+        else PT_LAUNCH((k_any<0, MODE, true, true>));
+    }
+    else if (tl.lds_scene && !spill) PT_LAUNCH((k_any<1, MODE, false>));
     else if (tl.lds_scene) PT_LAUNCH((k_any<1, MODE, true>));
     else if (!spill) PT_LAUNCH((k_any<0, MODE, false>));
     else PT_LAUNCH((k_any<0, MODE, true>));
@@ -2585,7 +2695,14 @@ void launch_trace_fused(hipStream_t s, const TraceLaunch& tl, const WavefrontBuf
     const uint4* blob = (const uint4*)tl.blob;
     const FusedKArgs ka{tl.scene, blob, fa, wout, lout};
 #define PT_LAUNCH(K) hipLaunchKernelGGL(K, dim3(resident_grid(K, tl, lds)), block, lds, s, ka)
-    if (tl.lds_scene && !spill) PT_LAUNCH((k_trace_fused<1, false>));
+    if (ident_walk(tl, IDENT_TLAS_WORLD | IDENT_TLAS_LIGHTS))
+    {
+        if (tl.lds_scene && !spill) PT_LAUNCH((k_trace_fused<1, false, true>));
+        else if (tl.lds_scene) PT_LAUNCH((k_trace_fused<1, true, true>));
+        else if (!spill) PT_LAUNCH((k_trace_fused<0, false, true>));
+        else PT_LAUNCH((k_trace_fused<0, true, true>));
+    }
+    else if (tl.lds_scene && !spill) PT_LAUNCH((k_trace_fused<1, false>));
     else if (tl.lds_scene) PT_LAUNCH((k_trace_fused<1, true>));
     else if (!spill) PT_LAUNCH((k_trace_fused<0, false>));
     else PT_LAUNCH((k_trace_fused<0, true>));
@@ -2659,7 +2776,8 @@ void launch_shade(hipStream_t s, uint32_t qclass, const SceneView& sv, const Ren
     {
     case Q_TERMINAL: hipLaunchKernelGGL(k_shade_terminal, dim3(grid_blocks), dim3(256), 0, s, sv, rp, io, b); break;
     case Q_LAMBERT:
-        if (inl) hipLaunchKernelGGL((k_shade_surface<Q_LAMBERT, false, true>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), lds, s, ka);
+        if (inl && PT_IDENT_SHADE && ident_walk(*tl, IDENT_TLAS_WORLD)) hipLaunchKernelGGL((k_shade_surface<Q_LAMBERT, false, true, true>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), lds, s, ka);
+        else if (inl) hipLaunchKernelGGL((k_shade_surface<Q_LAMBERT, false, true>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), lds, s, ka);
         else if (sv.has_volumes) hipLaunchKernelGGL((k_shade_surface<Q_LAMBERT, true>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), 0, s, ka);
         else hipLaunchKernelGGL((k_shade_surface<Q_LAMBERT, false>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), 0, s, ka);
         break;

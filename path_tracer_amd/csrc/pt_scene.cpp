@@ -777,7 +777,8 @@ int HostScene::flatten(std::string* err)
             }
         });
     }
-    auto put_instances = [&](const HostTlas& t) {
+    auto put_instances = [&](const HostTlas& t, uint32_t ident_bit) {
+        bool all_identity = true;
         for (const HostInstance& hi : t.instances)
         {
             DInstance d;
@@ -810,12 +811,15 @@ int HostScene::flatten(std::string* err)
                 // bit pattern of Affine3A::IDENTITY.inverse(): unit matrix with +0 zeros, translation -0
                 static const uint32_t ident[12] = {0x3f800000u, 0, 0, 0x80000000u, 0, 0x3f800000u, 0, 0x80000000u, 0, 0, 0x3f800000u, 0x80000000u};
                 if (std::memcmp(d.inv, ident, sizeof(ident)) == 0) d.qclass |= INSTANCE_IDENTITY;
+                else all_identity = false;
             }
             f.instances.push_back(d);
         }
+        if (all_identity) f.ident_tlas |= ident_bit;
     };
-    put_instances(world);
-    put_instances(lights);
+    f.ident_tlas = 0u;
+    put_instances(world, IDENT_TLAS_WORLD);
+    put_instances(lights, IDENT_TLAS_LIGHTS);
 
     // leaf-order position of every load-order primitive, per model
     std::vector<std::vector<uint32_t>> where(blas.size());

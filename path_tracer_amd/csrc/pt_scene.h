@@ -83,6 +83,7 @@ struct FlatScene
     uint32_t world_root = MISS_ID, lights_root = MISS_ID;
     uint32_t prim_bits = 0;
     uint32_t stack_entries = 0;
+    uint32_t ident_tlas = 0;            // IDENT_TLAS_WORLD / IDENT_TLAS_LIGHTS: every instance of that TLAS carries INSTANCE_IDENTITY
     float light_weight_sum = 0;
     bool has_volumes = false;
 };
