@@ -84,7 +84,8 @@ enum
     PT_FLAG_NO_LDS_SCENE = 2u, /* force BVH reads from global memory even when the scene fits LDS */
     PT_FLAG_TIMING_ALL = 4u,   /* bracket every kernel launch (adds ~10 us of idle per launch; diagnostic) */
     PT_FLAG_NO_PRIMARY_CULL = 8u, /* generate and trace the camera rays of EVERY pixel, also where they provably miss the scene's bounds */
-    PT_FLAG_GENERAL_WALK = 16u    /* traverse with the general two-level walk also where every instance of the TLAS is an identity */
+    PT_FLAG_GENERAL_WALK = 16u,   /* traverse with the general two-level walk also where every instance of the TLAS is an identity */
+    PT_FLAG_ADAPTIVE = 32u        /* keep per-pixel luminance moments beside the accumulation: pt_render_adaptive and friends (below) */
 };
 
 /* ---- lifetime ------------------------------------------------------------------------------------------------ */
@@ -167,6 +168,37 @@ int pt_write_accumulation(pt_ctx* ctx, const float* data_rgba, const float* posi
 /* per-sample radiance (rgb,1) of the last pt_render* call's final batch is not kept; this renders n_samples and
  * writes them un-accumulated: out[(s * local_pixels + pixel) * 4] (test hook for bit-exact comparison per sample) */
 int pt_render_samples(pt_ctx* ctx, uint32_t first_sample, uint32_t n_samples, float* samples_rgba);
+/* ---- adaptive sampling: spend samples only where pixels are still noisy (PT_FLAG_ADAPTIVE) ------------------------- */
+/* With PT_FLAG_ADAPTIVE the context keeps one more f32 per local pixel, Q = sum over the pixel's samples of L * L, where
+ * L = (0.2126f * r + 0.7152f * g) + 0.0722f * b of the finalised sample (finite check, length clamp 100; a miss's 0.006 counts like any
+ * other), every product and sum rounded in f32.  pt_render, pt_render_device and pt_render_adaptive add to Q in sample order wherever they
+ * add to the accumulation.  A pixel is ACTIVE when, in f32 with every operation correctly rounded and in this order,
+ *     n = acc.w;  S = (0.2126f * acc.r + 0.7152f * acc.g) + 0.0722f * acc.b;  m = S / n;  v = Q / n - m * m;  if (!(v > 0)) v = 0;
+ *     e2 = v / n;  t = rel_error * (m > abs_floor ? m : abs_floor);
+ *     active = n < min_samples || ((max_samples == 0 || n < max_samples) && e2 > t * t)
+ * (n is an integer, so the comparisons with min_samples / max_samples are exact).  Errors: PT_ERR_STATE without the flag or when Q does
+ * not describe the accumulation (after pt_write_accumulation without a matching pt_write_moments, after pt_frame, after the flag was set
+ * on a context that had accumulated; pt_reset_accumulation makes Q zero and valid again); PT_ERR_ARG for an invalid pt_adaptive;
+ * PT_ERR_LIMIT when some pixel's acc.w is not an integer in [0, 2^24] (f32 counts stop being exact there).
+ * A rank context (world_size > 1) selects among and renders its own rows; pt_multi_* has no adaptive mode. */
+typedef struct pt_adaptive
+{
+    float rel_error;      /* >= 0, finite: relative standard error of the mean luminance a pixel is rendered down to */
+    float abs_floor;      /* >= 0, finite: luminance below which the error is measured absolutely */
+    uint32_t min_samples; /* >= 2 */
+    uint32_t max_samples; /* 0 = no cap, else >= min_samples */
+} pt_adaptive;
+/* Selects the active pixels, then renders n_samples more samples for each of them: pixel p gets samples [n_p, n_p + n_samples) with
+ * n_p = (uint32_t)acc.w of p when the call starts.  After any sequence of calls a pixel's accumulation, id history and last-sample
+ * first-hit position are exactly what pt_render(0, n_p) gives it; inactive pixels are not touched.  *n_active (may be NULL): the number
+ * of active pixels.  Blocking; the results stay on the device (pt_read_frame, pt_read_moments). */
+int pt_render_adaptive(pt_ctx* ctx, const pt_adaptive* crit, uint32_t n_samples, uint32_t* n_active);
+/* the selection alone: mask[local pixel] = 1 (active) or 0, local_rows * width bytes (may be NULL) */
+int pt_adaptive_mask(pt_ctx* ctx, const pt_adaptive* crit, uint8_t* mask, uint32_t* n_active);
+/* Q per local pixel (local_rows * width floats): read, and restore for a checkpoint (pt_write_accumulation, then pt_write_moments) */
+int pt_read_moments(pt_ctx* ctx, float* sumsq);
+int pt_write_moments(pt_ctx* ctx, const float* sumsq);
+
 /* rows owned by this rank: local row ly <-> global row rows[ly] */
 int pt_local_rows(pt_ctx* ctx, uint32_t* n_rows, uint32_t* rows, uint32_t cap);
 /* HIP stream the library launches on (a hipStream_t); pass NULL to return to the library's own stream */

@@ -156,11 +156,11 @@ class Renderer
 {
 public:
     Renderer(const Scene& scene, const Camera& cam, uint32_t width, uint32_t height, uint32_t max_bounces, uint32_t n_sobol = 512, bool enable_nee = true,
-             uint64_t seed = 0x5EED5EEDull, int device = -1)
+             uint64_t seed = 0x5EED5EEDull, int device = -1, uint32_t flags = 0)
     {
         pt_config cfg{};
         cfg.width = width; cfg.height = height; cfg.max_bounces = max_bounces; cfg.n_sobol = n_sobol; cfg.enable_nee = enable_nee ? 1u : 0u;
-        cfg.seed = seed; cfg.rank = 0; cfg.world_size = 1; cfg.strip_rows = 4; cfg.batch_spp = 0; cfg.device = device; cfg.flags = 0;
+        cfg.seed = seed; cfg.rank = 0; cfg.world_size = 1; cfg.strip_rows = 4; cfg.batch_spp = 0; cfg.device = device; cfg.flags = flags;
         ctx_ = pt_create(&cfg);
         if (!ctx_) throw Error(PT_ERR_ARG, "pt_create failed (bad configuration)");
         width_ = width; height_ = height;
@@ -209,6 +209,28 @@ public:
         if (f.data.size() != px * 4 || (!f.position.empty() && f.position.size() != px * 4) || (!f.id.empty() && f.id.size() != px))
             throw Error(PT_ERR_ARG, "write_accumulation: the frame was not saved at this renderer's " + std::to_string(width_) + "x" + std::to_string(height_));
         check(pt_write_accumulation(ctx_, f.data.data(), f.position.empty() ? nullptr : f.position.data(), f.id.empty() ? nullptr : f.id.data()));
+    }
+    // adaptive sampling (flags with PT_FLAG_ADAPTIVE): n_samples more samples for every pixel the criterion selects, each continuing from
+    // its own count; returns how many pixels were selected.  Blocking; the frame stays on the device (read_frame).
+    uint32_t render_adaptive(const pt_adaptive& crit, uint32_t n_samples)
+    {
+        uint32_t n = 0;
+        check(pt_render_adaptive(ctx_, &crit, n_samples, &n));
+        return n;
+    }
+    // the selection alone: 1 per pixel that render_adaptive would render
+    std::vector<uint8_t> adaptive_mask(const pt_adaptive& crit) const
+    {
+        std::vector<uint8_t> m((size_t)width_ * height_);
+        check(pt_adaptive_mask(ctx_, &crit, m.data(), nullptr));
+        return m;
+    }
+    // Q per pixel (sum of squared sample luminance): saved and restored beside read_frame / write_accumulation for a checkpoint
+    std::vector<float> read_moments() const { std::vector<float> q((size_t)width_ * height_); check(pt_read_moments(ctx_, q.data())); return q; }
+    void write_moments(const std::vector<float>& q)
+    {
+        if (q.size() != (size_t)width_ * height_) throw Error(PT_ERR_ARG, "write_moments: not one value per pixel of this renderer's frame");
+        check(pt_write_moments(ctx_, q.data()));
     }
     std::vector<float> present() const { std::vector<float> v((size_t)width_ * height_ * 4); check(pt_present(ctx_, v.data())); return v; }
     std::vector<uint8_t> present_rgb8() const { std::vector<uint8_t> v((size_t)width_ * height_ * 3); check(pt_present_rgb8(ctx_, v.data())); return v; }

@@ -25,13 +25,14 @@ FLAG_NO_LDS_SCENE = 2
 FLAG_TIMING_ALL = 4
 FLAG_NO_PRIMARY_CULL = 8
 FLAG_GENERAL_WALK = 16
+FLAG_ADAPTIVE = 32
 DEFAULT_SEED = 0x5EED5EED
 
 # every symbol include/pt_api.h declares
 EXPORTS = [
     "pt_create", "pt_destroy", "pt_last_error", "pt_set_config", "pt_add_material", "pt_add_model", "pt_add_model_obj", "pt_model_vertices", "pt_build", "pt_set_camera",
     "pt_camera_matrices", "pt_set_environment", "pt_create_ray", "pt_render", "pt_render_device", "pt_reset_accumulation", "pt_accum_device_ptr",
-    "pt_read_accumulation", "pt_read_frame", "pt_write_accumulation", "pt_render_samples", "pt_active_pixels", "pt_local_rows", "pt_set_stream", "pt_synchronize", "pt_camera_input", "pt_camera_angles", "pt_frame", "pt_inv_projection", "pt_present", "pt_post_velocity", "pt_post_reproject", "pt_post_tonemap", "pt_post_rgb8", "pt_present_rgb8", "pt_write_image", "pt_trace_closest", "pt_trace_any",
+    "pt_read_accumulation", "pt_read_frame", "pt_write_accumulation", "pt_render_samples", "pt_render_adaptive", "pt_adaptive_mask", "pt_read_moments", "pt_write_moments", "pt_active_pixels", "pt_local_rows", "pt_set_stream", "pt_synchronize", "pt_camera_input", "pt_camera_angles", "pt_frame", "pt_inv_projection", "pt_present", "pt_post_velocity", "pt_post_reproject", "pt_post_tonemap", "pt_post_rgb8", "pt_present_rgb8", "pt_write_image", "pt_trace_closest", "pt_trace_any",
     "pt_ss_sobol", "pt_math_batch", "pt_material_eval", "pt_volume_eval", "pt_blas_count", "pt_blas_dump", "pt_tlas_dump", "pt_tlas_instances", "pt_instance_materials", "pt_light_cdf",
     "pt_triangle_dump", "pt_get_stats", "pt_reset_stats", "pt_last_batch_counters", "pt_last_batch_shade_pids", "pt_last_batch_step_stats",
     "pt_multi_create", "pt_multi_destroy", "pt_multi_last_error", "pt_multi_ctx", "pt_multi_render", "pt_multi_framebuffer_device_ptr",
@@ -68,6 +69,11 @@ class Stats(C.Structure):
     @property
     def rays(self):
         return self.rays_closest + self.rays_any + self.rays_light_closest
+
+
+class Adaptive(C.Structure):
+    """pt_adaptive: the selection criterion of an adaptive render (include/pt_api.h)"""
+    _fields_ = [("rel_error", C.c_float), ("abs_floor", C.c_float), ("min_samples", C.c_uint32), ("max_samples", C.c_uint32)]
 
 
 class PtError(RuntimeError):
@@ -122,6 +128,10 @@ def lib():
         L.pt_write_accumulation.argtypes = [vp, vp, vp, vp]
         L.pt_read_frame.argtypes = [vp, vp, vp, vp]
         L.pt_render_samples.argtypes = [vp, u32, u32, vp]
+        L.pt_render_adaptive.argtypes = [vp, C.POINTER(Adaptive), u32, C.POINTER(u32)]
+        L.pt_adaptive_mask.argtypes = [vp, C.POINTER(Adaptive), vp, C.POINTER(u32)]
+        L.pt_read_moments.argtypes = [vp, vp]
+        L.pt_write_moments.argtypes = [vp, vp]
         L.pt_local_rows.argtypes = [vp, C.POINTER(u32), vp, u32]
         L.pt_set_stream.argtypes = [vp, vp]
         L.pt_synchronize.argtypes = [vp]
@@ -336,6 +346,41 @@ class Renderer:
 
     def reset_accumulation(self):
         self._chk(self.L.pt_reset_accumulation(self.ctx))
+
+    # ---- adaptive sampling (FLAG_ADAPTIVE)
+    @staticmethod
+    def _adaptive(rel_error, abs_floor, min_samples, max_samples):
+        return Adaptive(rel_error, abs_floor, min_samples, max_samples)
+
+    def render_adaptive(self, n_samples: int, rel_error: float, abs_floor: float = 0.0, min_samples: int = 2, max_samples: int = 0) -> int:
+        """Select the pixels whose mean luminance is not yet known to rel_error (pt_adaptive), then render n_samples more samples for each
+        of them, continuing from each pixel's own count.  Returns the number of selected pixels; the frame stays on the device (read_frame)."""
+        n = C.c_uint32(0)
+        crit = self._adaptive(rel_error, abs_floor, min_samples, max_samples)
+        self._chk(self.L.pt_render_adaptive(self.ctx, C.byref(crit), n_samples, C.byref(n)))
+        return n.value
+
+    def adaptive_mask(self, rel_error: float, abs_floor: float = 0.0, min_samples: int = 2, max_samples: int = 0) -> np.ndarray:
+        """The selection alone: bool per local pixel (local rows x width), True = would be rendered"""
+        mask = np.zeros((len(self.local_rows()), self.cfg.width), np.uint8)
+        n = C.c_uint32(0)
+        crit = self._adaptive(rel_error, abs_floor, min_samples, max_samples)
+        self._chk(self.L.pt_adaptive_mask(self.ctx, C.byref(crit), _p(mask), C.byref(n)))
+        assert int(mask.sum()) == n.value
+        return mask.astype(bool)
+
+    def read_moments(self) -> np.ndarray:
+        """Q, the sum of the squared luminance of every accumulated sample, per local pixel (local rows x width, f32)"""
+        q = np.zeros((len(self.local_rows()), self.cfg.width), np.float32)
+        self._chk(self.L.pt_read_moments(self.ctx, _p(q)))
+        return q
+
+    def write_moments(self, sumsq):
+        """Restore Q beside write_accumulation (checkpoint / resume of an adaptive render)"""
+        q = np.ascontiguousarray(sumsq, np.float32)
+        if q.size != len(self.local_rows()) * self.cfg.width:
+            raise PtError(-1, f"write_moments: not one value per local pixel of a {self.cfg.width}-wide frame")
+        self._chk(self.L.pt_write_moments(self.ctx, _p(q)))
 
     def read_accumulation(self):
         rows = len(self.local_rows())

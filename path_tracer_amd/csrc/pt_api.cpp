@@ -135,6 +135,13 @@ struct pt_ctx
     DevBuf d_accum, d_position, d_id;
     DevBuf d_input, d_velocity, d_output; // State::update textures (pt_frame)
 
+    // adaptive sampling (PT_FLAG_ADAPTIVE): Q (sum of squared sample luminance) per local pixel, the selection's list {local pixel, n_p}
+    // and its scratch (header {count, bad count} | per-block counts).  moments_valid: Q describes the accumulation.
+    DevBuf d_moments, d_list, d_select;
+    bool moments_valid = true;
+    const uint2* cur_list = nullptr; // the list of the pt_render_adaptive in progress (its paths' pixels), else null: the active rectangle
+    uint32_t cur_list_n = 0;
+
     // stats
     pt_stats stats{};
     int last_pipe = 0; // pipeline whose counters pt_last_batch_counters reports
@@ -427,6 +434,13 @@ int ensure_frame(pt_ctx* c)
         HIPCHK(c, hipMemsetAsync(c->d_accum.p, 0, c->d_accum.bytes, c->stream));
         HIPCHK(c, hipMemsetAsync(c->d_position.p, 0, c->d_position.bytes, c->stream));
         HIPCHK(c, hipMemsetAsync(c->d_id.p, 0, c->d_id.bytes, c->stream));
+        c->moments_valid = true; // (a zero accumulation: zero moments describe it)
+    }
+    if (c->cfg.flags & PT_FLAG_ADAPTIVE)
+    {
+        const bool mfresh = c->d_moments.bytes < px * 4;
+        if ((r = dev_alloc(c, c->d_moments, px * 4))) return r;
+        if (mfresh) HIPCHK(c, hipMemsetAsync(c->d_moments.p, 0, c->d_moments.bytes, c->stream));
     }
     return PT_OK;
 }
@@ -680,7 +694,8 @@ int batch_begin(BatchRun& br, pt_ctx* c, int pipe, uint32_t first_sample, uint32
     rp.strip_rows = g.strip_rows;
     rp.first_sample = first_sample;
     rp.batch_samples = count;
-    const ActiveRect ar = active_rect(c);
+    // an adaptive list takes the rectangle's place: path ids index its entries (one row of cur_list_n; the primary cull does not apply)
+    const ActiveRect ar = c->cur_list ? ActiveRect{0u, c->cur_list_n, 0u, 1u} : active_rect(c);
     rp.act_x0 = ar.x0; rp.act_w = ar.w; rp.act_ly0 = ar.ly0; rp.act_rows = ar.rows;
     rp.act_pixels = ar.w * ar.rows;
     rp.n_paths = rp.act_pixels * count;
@@ -727,7 +742,7 @@ int batch_begin(BatchRun& br, pt_ctx* c, int pipe, uint32_t first_sample, uint32
     HIPCHK(c, hipMemsetAsync(wb.wave_times, 0, (size_t)br.rows * kWaveTimeSlots * 16, br.s));
     HIPCHK(c, hipMemsetAsync(wb.wave_times_any, 0, (size_t)br.rows * kWaveTimeSlots * 16, br.s));
 #endif
-    if (rp.n_paths) { Timer t(c, pp, br.s, T_GEN); launch_generate(br.s, rp, br.cam, wb); }
+    if (rp.n_paths) { Timer t(c, pp, br.s, T_GEN); launch_generate(br.s, rp, br.cam, wb, c->cur_list); }
     br.shade_blocks = (uint32_t)std::max<size_t>(1, std::min<size_t>(((size_t)rp.n_paths + 255) / 256, (size_t)c->n_cus * PT_SHADE_BLOCKS_PER_CU));
     br.nee = g.enable_nee != 0;
     // PT_FUSED_TRACE: the BSDF-sampled NEE rays of a bounce ride in the next bounce's world closest-hit launch (k_trace_fused) instead of
@@ -805,7 +820,7 @@ int batch_bounce(BatchRun& br, uint32_t b)
         batch_join_side(br);
     }
     for (uint32_t q = 0; q < Q_COUNT; ++q)
-        if (c->class_present[q]) { Timer t(c, pp, s, T_SHADE); launch_shade(s, q, c->sv, br.rp, wb, b, br.shade_blocks, br.cam, br.env, &br.tl); }
+        if (c->class_present[q]) { Timer t(c, pp, s, T_SHADE); launch_shade(s, q, c->sv, br.rp, wb, b, br.shade_blocks, br.cam, br.env, &br.tl, c->cur_list); }
     // long bounce budgets (reference default MAX_BOUNCES = 1024): stop once no path is left
     if (g.max_bounces > 16 && b >= 8 && (b % 4) == 0 && b < g.max_bounces)
     {
@@ -844,7 +859,10 @@ int batch_end(BatchRun& br)
     else
     {
         Timer t(c, pp, s, T_ACCUM);
-        launch_accumulate(s, rp, br.cam, wb, (f4*)c->d_accum.p, (f4*)c->d_position.p, (uint32_t*)c->d_id.p, br.write_position ? 1u : 0u, 1u);
+        if (c->cfg.flags & PT_FLAG_ADAPTIVE)
+            launch_accumulate_moments(s, rp, br.cam, wb, (f4*)c->d_accum.p, (f4*)c->d_position.p, (uint32_t*)c->d_id.p, br.write_position ? 1u : 0u, 1u,
+                                      (float*)c->d_moments.p, c->cur_list);
+        else launch_accumulate(s, rp, br.cam, wb, (f4*)c->d_accum.p, (f4*)c->d_position.p, (uint32_t*)c->d_id.p, br.write_position ? 1u : 0u, 1u);
     }
     HIPCHK(c, hipEventRecord(pp.ev_done, s));
     // only the rows the batch used come back (all of them were cleared: last_row + 1 <= cleared_rows)
@@ -853,8 +871,8 @@ int batch_end(BatchRun& br)
     HIPCHK(c, hipMemcpyAsync(pp.h_heads, wb.heads, (size_t)used_rows * HEADS_PER_ROW * kHeadWordsPerQueue * 4, hipMemcpyDeviceToHost, s));
     pp.busy = true;
     pp.busy_rows = used_rows;
-    pp.busy_paths = (uint64_t)rp.local_pixels * br.count;
-    pp.busy_culled = (uint64_t)(rp.local_pixels - rp.act_pixels) * br.count;
+    pp.busy_paths = (uint64_t)(c->cur_list ? rp.act_pixels : rp.local_pixels) * br.count;
+    pp.busy_culled = c->cur_list ? 0u : (uint64_t)(rp.local_pixels - rp.act_pixels) * br.count;
     return PT_OK;
 }
 
@@ -925,7 +943,7 @@ int render_common(pt_ctx* c, uint32_t first_sample, uint32_t n_samples, float* s
         }
         max_paths = std::min<size_t>(std::max<size_t>(max_paths, 1u << 20), (1ull << 29) - 1);
     }
-    const ActiveRect ar = active_rect(c);
+    const ActiveRect ar = c->cur_list ? ActiveRect{0u, c->cur_list_n, 0u, 1u} : active_rect(c);
     const size_t act_pixels = std::max<size_t>((size_t)ar.w * ar.rows, 1);
     uint32_t batch = c->cfg.batch_spp ? c->cfg.batch_spp : (uint32_t)std::max<size_t>(1, max_paths / act_pixels);
     batch = std::min(batch, n_samples);
@@ -1069,12 +1087,51 @@ int render_common(pt_ctx* c, uint32_t first_sample, uint32_t n_samples, float* s
         (void)hipGetLastError();
         if (c->d_accum.p) (void)hipMemsetAsync(c->d_accum.p, 0, c->d_accum.bytes, c->stream);
         if (c->d_id.p) (void)hipMemsetAsync(c->d_id.p, 0, c->d_id.bytes, c->stream);
+        if (c->d_moments.p) (void)hipMemsetAsync(c->d_moments.p, 0, c->d_moments.bytes, c->stream);
+        c->moments_valid = true;
         (void)hipStreamSynchronize(c->stream);
         dev_free(d_samples);
         return err;
     }
     dev_free(d_samples);
     c->stats.ms_total += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return PT_OK;
+}
+
+// ---- adaptive sampling (PT_FLAG_ADAPTIVE)
+// everything that can be refused without touching the device
+int adaptive_check(pt_ctx* c, const pt_adaptive* a)
+{
+    if (!(c->cfg.flags & PT_FLAG_ADAPTIVE)) return fail(c, PT_ERR_STATE, "adaptive sampling needs PT_FLAG_ADAPTIVE in pt_config.flags");
+    if (!a) return fail(c, PT_ERR_ARG, "null pt_adaptive");
+    if (!(a->rel_error >= 0.0f) || !std::isfinite(a->rel_error)) return fail(c, PT_ERR_ARG, "pt_adaptive.rel_error must be finite and >= 0");
+    if (!(a->abs_floor >= 0.0f) || !std::isfinite(a->abs_floor)) return fail(c, PT_ERR_ARG, "pt_adaptive.abs_floor must be finite and >= 0");
+    if (a->min_samples < 2u) return fail(c, PT_ERR_ARG, "pt_adaptive.min_samples must be >= 2");
+    if (a->max_samples != 0u && a->max_samples < a->min_samples) return fail(c, PT_ERR_ARG, "pt_adaptive.max_samples must be 0 or >= min_samples");
+    if (!c->moments_valid)
+        return fail(c, PT_ERR_STATE, "the moments do not describe the accumulation (pt_write_accumulation without pt_write_moments, pt_frame, or "
+                                     "PT_FLAG_ADAPTIVE set after samples were accumulated): pt_write_moments or pt_reset_accumulation first");
+    return PT_OK;
+}
+
+// k_adaptive_count + k_adaptive_write on the context's stream, then ONE small read-back: the list's length and the bad-count flag
+int adaptive_select(pt_ctx* c, const pt_adaptive* a, uint32_t* n_active)
+{
+    int r;
+    const uint32_t px = c->local_pixels;
+    const uint32_t blocks = adaptive_select_blocks(px);
+    if ((r = dev_alloc(c, c->d_list, (size_t)std::max<uint32_t>(px, 1) * 8))) return r;
+    if ((r = dev_alloc(c, c->d_select, ((size_t)blocks + 4) * 4))) return r;
+    uint32_t* header = (uint32_t*)c->d_select.p;
+    const AdaptiveCrit cr{a->rel_error, a->abs_floor, a->min_samples, a->max_samples};
+    HIPCHK(c, hipMemsetAsync(header, 0, 16, c->stream));
+    launch_adaptive_select(c->stream, (const f4*)c->d_accum.p, (const float*)c->d_moments.p, px, cr, header + 4, (uint2*)c->d_list.p, header);
+    HIPCHK(c, hipGetLastError());
+    uint32_t h[2] = {0u, 0u};
+    HIPCHK(c, hipMemcpyAsync(h, header, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (h[1]) return fail(c, PT_ERR_LIMIT, "a pixel's sample count (acc.w) is not an integer in [0, 2^24]: f32 counts are not exact beyond");
+    *n_active = h[0];
     return PT_OK;
 }
 
@@ -1114,7 +1171,8 @@ void pt_destroy(pt_ctx* c)
             if (pp.ev_join) (void)hipEventDestroy(pp.ev_join);
             if (pp.ev_done) (void)hipEventDestroy(pp.ev_done);
         }
-        DevBuf* bufs[] = {&c->d_input, &c->d_velocity, &c->d_output, &c->d_blob, &c->d_tri_shade, &c->d_tri_pos, &c->d_tri_orig, &c->d_materials, &c->d_lights, &c->d_env, &c->d_spill, &c->d_accum, &c->d_position, &c->d_id};
+        DevBuf* bufs[] = {&c->d_input, &c->d_velocity, &c->d_output, &c->d_blob, &c->d_tri_shade, &c->d_tri_pos, &c->d_tri_orig, &c->d_materials, &c->d_lights, &c->d_env, &c->d_spill, &c->d_accum, &c->d_position, &c->d_id,
+                         &c->d_moments, &c->d_list, &c->d_select};
         for (DevBuf* b : bufs) dev_free(*b);
         if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
         if (c->ev_start) (void)hipEventDestroy(c->ev_start);
@@ -1135,11 +1193,15 @@ int pt_set_config(pt_ctx* c, const pt_config* cfg)
     if (r) return r;
     if (c->cfg.stack_lds_levels != old.stack_lds_levels || ((c->cfg.flags ^ old.flags) & PT_FLAG_NO_LDS_SCENE)) c->scene_uploaded = false;
     if (c->dev_ready && cfg->device != old_dev && cfg->device >= 0) return fail(c, PT_ERR_STATE, "device cannot change after first use");
+    // moments that were not kept while the flag was off do not describe an accumulation that may hold samples
+    if ((c->cfg.flags & ~old.flags & PT_FLAG_ADAPTIVE) && c->d_accum.p) c->moments_valid = false;
     if (c->local_pixels != old_px)
     {
         dev_free(c->d_accum);
         dev_free(c->d_position);
         dev_free(c->d_id);
+        dev_free(c->d_moments);
+        dev_free(c->d_list);
     }
     return PT_OK;
 }
@@ -1340,6 +1402,8 @@ int pt_reset_accumulation(pt_ctx* c)
     if ((r = ensure_frame(c))) return r;
     HIPCHK(c, hipMemsetAsync(c->d_accum.p, 0, c->d_accum.bytes, c->stream));
     HIPCHK(c, hipMemsetAsync(c->d_id.p, 0, c->d_id.bytes, c->stream));
+    if (c->d_moments.p) HIPCHK(c, hipMemsetAsync(c->d_moments.p, 0, c->d_moments.bytes, c->stream));
+    c->moments_valid = true;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return PT_OK;
 }
@@ -1395,10 +1459,84 @@ int pt_write_accumulation(pt_ctx* c, const float* data, const float* position, c
     if ((r = ensure_device(c))) return r;
     if ((r = ensure_frame(c))) return r;
     HIPCHK(c, hipStreamSynchronize(c->stream)); // the frame buffers may still be written by a render in flight
+    c->moments_valid = false;                    // until pt_write_moments restores the matching Q (PT_FLAG_ADAPTIVE)
     HIPCHK(c, hipMemcpyAsync(c->d_accum.p, data, (size_t)c->local_pixels * 16, hipMemcpyHostToDevice, c->stream));
     if (position) HIPCHK(c, hipMemcpyAsync(c->d_position.p, position, (size_t)c->local_pixels * 16, hipMemcpyHostToDevice, c->stream));
     if (id) HIPCHK(c, hipMemcpyAsync(c->d_id.p, id, (size_t)c->local_pixels * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PT_OK;
+}
+
+// ---- adaptive sampling (PT_FLAG_ADAPTIVE)
+int pt_render_adaptive(pt_ctx* c, const pt_adaptive* crit, uint32_t n_samples, uint32_t* n_active)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    int r;
+    if ((r = adaptive_check(c, crit))) return r;
+    // a pixel's sample indices run to n_p + n_samples - 1 with n_p <= 2^24: 32 bits
+    if (n_samples > 0xffffffffu - (1u << 24)) return fail(c, PT_ERR_ARG, "n_samples too large");
+    if ((r = precheck(c))) return r;
+    if ((r = upload_scene(c))) return r;
+    if ((r = ensure_frame(c))) return r;
+    uint32_t n = 0;
+    if ((r = adaptive_select(c, crit, &n))) return r;
+    if (n_active) *n_active = n;
+    if (n == 0 || n_samples == 0) return PT_OK;
+    c->cur_list = (const uint2*)c->d_list.p;
+    c->cur_list_n = n;
+    r = render_common(c, 0, n_samples, nullptr);
+    c->cur_list = nullptr;
+    c->cur_list_n = 0;
+    return r;
+}
+
+int pt_adaptive_mask(pt_ctx* c, const pt_adaptive* crit, uint8_t* mask, uint32_t* n_active)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    int r;
+    if ((r = adaptive_check(c, crit))) return r;
+    if ((r = ensure_device(c))) return r;
+    if ((r = ensure_frame(c))) return r;
+    uint32_t n = 0;
+    if ((r = adaptive_select(c, crit, &n))) return r;
+    if (n_active) *n_active = n;
+    if (mask)
+    {
+        std::vector<uint2> list(n);
+        if (n) HIPCHK(c, hipMemcpy(list.data(), c->d_list.p, (size_t)n * 8, hipMemcpyDeviceToHost));
+        std::memset(mask, 0, c->local_pixels);
+        for (const uint2& e : list) mask[e.x] = 1u;
+    }
+    return PT_OK;
+}
+
+int pt_read_moments(pt_ctx* c, float* sumsq)
+{
+    if (!c || !sumsq) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!(c->cfg.flags & PT_FLAG_ADAPTIVE)) return fail(c, PT_ERR_STATE, "moments are kept with PT_FLAG_ADAPTIVE only");
+    int r;
+    if ((r = ensure_device(c))) return r;
+    if ((r = ensure_frame(c))) return r;
+    HIPCHK(c, hipMemcpyAsync(sumsq, c->d_moments.p, (size_t)c->local_pixels * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PT_OK;
+}
+
+int pt_write_moments(pt_ctx* c, const float* sumsq)
+{
+    if (!c || !sumsq) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!(c->cfg.flags & PT_FLAG_ADAPTIVE)) return fail(c, PT_ERR_STATE, "moments are kept with PT_FLAG_ADAPTIVE only");
+    int r;
+    if ((r = ensure_device(c))) return r;
+    if ((r = ensure_frame(c))) return r;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->d_moments.p, sumsq, (size_t)c->local_pixels * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->moments_valid = true;
     return PT_OK;
 }
 
@@ -1453,6 +1591,7 @@ int pt_frame(pt_ctx* c, uint32_t frame_index, const float* last_inv_projection, 
     if (id) HIPCHK(c, hipMemcpyAsync(c->d_id.p, id, px * 4, hipMemcpyHostToDevice, c->stream));
     if ((r = ensure_wavefront(c, 0, px, c->cfg.max_bounces + 2))) return r;
     if ((r = run_batch(c, frame_index, 1, true, (f4*)c->d_input.p, true))) return r;   // main.rs:181-207, one sample per pixel
+    c->moments_valid = false; // State::update adds (or reprojects) the sample without Q: the moments no longer describe the accumulation
     hipStream_t s = c->stream;
     const int w = (int)c->cfg.width, h = (int)c->cfg.height;
     bool moved = false;                                                                                                    // state.rs:549 `inv_projection == last_inv_projection`

@@ -59,7 +59,9 @@ inline ShadeQueue shade_queue(const WavefrontBuffers& wb, uint32_t q)
     return ShadeQueue{a, a + wb.q_stride, a + 2u * (size_t)wb.q_stride};
 }
 
-void launch_generate(hipStream_t s, const RenderParams& rp, const CameraView& cam, const WavefrontBuffers& wb);
+// list: an adaptive list (launch_adaptive_select's {local pixel, n_p} entries, rp.act_pixels of them) whose pixels the batch's paths belong
+// to instead of the active rectangle's (pt_render_adaptive), or null
+void launch_generate(hipStream_t s, const RenderParams& rp, const CameraView& cam, const WavefrontBuffers& wb, const uint2* list = nullptr);
 // closest hit against the world TLAS for bounce `b`: reads rq[b&1], writes hits + shade queues of row b
 void launch_trace_world(hipStream_t s, const TraceLaunch& tl, const WavefrontBuffers& wb, uint32_t b, const RenderParams& rp, const CameraView& cam,
                         const EnvView& env);
@@ -72,13 +74,21 @@ void launch_trace_lchain(hipStream_t s, const TraceLaunch& tl, const WavefrontBu
 // shading of bounce b for one queue class
 // (tl: the scene's traversal launch description; with it the Lambert / GGX passes of an LDS-resident scene may trace their own shadow rays)
 void launch_shade(hipStream_t s, uint32_t qclass, const SceneView& sv, const RenderParams& rp, const WavefrontBuffers& wb, uint32_t b,
-                  uint32_t grid_blocks, const CameraView& cam, const EnvView& env, const TraceLaunch* tl = nullptr);
+                  uint32_t grid_blocks, const CameraView& cam, const EnvView& env, const TraceLaunch* tl = nullptr, const uint2* list = nullptr);
 // true: the shading pass answers the explicit-light shadow rays itself and nothing is queued for launch_trace_shadow
 bool shade_traces_shadow(const TraceLaunch& tl);
 // accum[pixel] += sum over batch samples in order of (finalised rgb, 1); position/id of the last samples
 void launch_accumulate(hipStream_t s, const RenderParams& rp, const CameraView& cam, const WavefrontBuffers& wb, f4* accum, f4* position, uint32_t* id,
                        uint32_t write_position, uint32_t add_to_accum);
+// ... and moments[pixel] += L * L of each finalised sample beside it (PT_FLAG_ADAPTIVE); with a list only the listed pixels, in list order
+void launch_accumulate_moments(hipStream_t s, const RenderParams& rp, const CameraView& cam, const WavefrontBuffers& wb, f4* accum, f4* position, uint32_t* id,
+                               uint32_t write_position, uint32_t add_to_accum, float* moments, const uint2* list);
 void launch_store_samples(hipStream_t s, const RenderParams& rp, const WavefrontBuffers& wb, f4* out);
+// adaptive selection of n_pixels local pixels: list <- {pixel, n_p} of every active pixel in ascending order, header[0] <- their number,
+// header[1] |= 1 if some count is not an integer in [0, 2^24] (the caller zeroes header[1]); counts: adaptive_select_blocks words
+uint32_t adaptive_select_blocks(uint32_t n_pixels);
+void launch_adaptive_select(hipStream_t s, const f4* accum, const float* moments, uint32_t n_pixels, const AdaptiveCrit& cr, uint32_t* counts, uint2* list,
+                            uint32_t* header);
 
 // after the path (pt_post.hip)
 void launch_post_accumulate(hipStream_t s, uint32_t n, const f4* input, f4* accum);

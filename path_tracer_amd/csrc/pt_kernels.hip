@@ -1629,6 +1629,21 @@ __device__ __forceinline__ PixelId path_pixel(const RenderParams& rp, uint32_t p
     return PixelId{gy * rp.width + x, rp.first_sample + pp.s, ly * rp.width + x, x, gy};
 }
 
+// Adaptive list (pt_render_adaptive): the batch's path ids index the entries {local pixel, n_p} of the list k_adaptive_write made
+// (RenderParams::act_pixels = its length) instead of the active rectangle.  Entry k's batch-local sample s is the pixel's sample
+// n_p + first_sample + s: a pixel's samples continue from its own count, whatever the other pixels hold.
+__device__ __forceinline__ PixelId path_pixel_list(const RenderParams& rp, const uint2* __restrict__ list, uint32_t pid, uint32_t* s_local = nullptr,
+                                                   uint32_t* k_out = nullptr)
+{
+    const PidParts pp = pid_split(rp, pid);
+    if (s_local) *s_local = pp.s;
+    if (k_out) *k_out = pp.k;
+    const uint2 e = list[pp.k];
+    const uint32_t ly = fastdiv(e.x, rp.div_width), x = e.x - ly * rp.width;
+    const uint32_t gy = global_row(rp, ly);
+    return PixelId{gy * rp.width + x, e.y + rp.first_sample + pp.s, e.x, x, gy};
+}
+
 // direction of the camera ray of (pixel gx, gy; sample): main.rs:193-199 + Camera::create_ray camera.rs:94-105
 __device__ __forceinline__ f3 camera_ray_dir(const RenderParams& rp, const CameraView& cam, uint32_t gx, uint32_t gy, uint32_t sample)
 {
@@ -1669,6 +1684,17 @@ __global__ void __launch_bounds__(256) k_generate(const RenderParams rp, const C
     // no state is initialised: bounce 0 knows path_weight = 1, accumulated = 0, one draw consumed (integrator.rs:153-161)
 }
 
+// k_generate over an adaptive list (path_pixel_list)
+__global__ void __launch_bounds__(256) k_generate_list(const RenderParams rp, const CameraView cam, const RayQueue rq, Counters* ctr, const uint2* __restrict__ list)
+{
+    const uint32_t pid = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pid == 0u) ctr[0].n_closest = rp.n_paths;
+    if (pid >= rp.n_paths) return;
+    const PixelId px = path_pixel_list(rp, list, pid);
+    const f3 dir = camera_ray_dir(rp, cam, px.gx, px.gy, px.sample);
+    rq.b[pid] = f4{dir.x, dir.y, dir.z, asf(pid)};
+}
+
 struct ShadeIO
 {
     PathState st;
@@ -1677,7 +1703,11 @@ struct ShadeIO
     const f4* lchain_nb_prev; // last bounce's
     const f4* lchain_hit;     // last bounce's light hits, by rq_lchain_prev slot
     const f4* hits;           // terminal pass only: hits of the rays that went to the terminal queue, by ray index
-    const uint2* entries;     // terminal pass: {ray index | ENTRY_DEAD, path id}
+    union
+    {
+        const uint2* entries; // terminal pass: {ray index | ENTRY_DEAD, path id}
+        const uint2* list;    // surface passes of an adaptive render (k_shade_surface<..., LIST>): the list's {local pixel, n_p} entries
+    };
     ShadeQueue q_in;          // surface pass: this class's hit records in queue order
     const uint32_t* tails_in; // ... and the queue's striped tails
     uint2* q_term_next;
@@ -1925,7 +1955,8 @@ __device__ __forceinline__ const ShadeKArgs& shade_args()
     [[maybe_unused]] const SceneView& sv = ka_.sv;                                                                                 \
     [[maybe_unused]] const RenderParams& rp = ka_.rp;                                                                              \
     [[maybe_unused]] const ShadeIO& io = ka_.io;
-template <uint32_t QCLASS, bool VOLUMES, bool INLINE = false, bool IDENT = false>
+// LIST (pt_render_adaptive): path ids index the adaptive list (ShadeIO::list, path_pixel_list) instead of the active rectangle
+template <uint32_t QCLASS, bool VOLUMES, bool INLINE = false, bool IDENT = false, bool LIST = false>
 __global__ void __launch_bounds__(PT_SHADE_THREADS, INLINE ? PT_SHADE_WAVES_INLINE : shade_waves(QCLASS, VOLUMES)) k_shade_surface(const ShadeKArgs kargs)
 {
     extern __shared__ uint4 smem_dyn[];
@@ -2009,7 +2040,7 @@ __global__ void __launch_bounds__(PT_SHADE_THREADS, INLINE ? PT_SHADE_WAVES_INLI
             const f3 normal = hit_normal(sv, inst, tri, hit.y, hit.z, rd, front);
             const f3 p = fma3(rd, bc3(hit.x), ro);                                     // r.at(hit_info.t)
             uint32_t s_local, k_pix;
-            const PixelId px = path_pixel(rp, pid, &s_local, &k_pix);
+            const PixelId px = LIST ? path_pixel_list(rp, io.list, pid, &s_local, &k_pix) : path_pixel(rp, pid, &s_local, &k_pix);
             if (bounce == 0u)                                                          // integrator.rs:181-185
             {
                 if (s_local == rp.keep_s_pos) io.st.first_pos[k_pix] = f4{p.x, p.y, p.z, hit.x};
@@ -2314,6 +2345,9 @@ __device__ __forceinline__ f3 finalise(f3 acc)
     return clamp_len_max(acc, 100.0f);
 }
 
+// luminance of a finalised sample (PT_FLAG_ADAPTIVE's moments and selection): every product and sum rounded in f32 (no contraction)
+__device__ __forceinline__ float luminance(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
+
 // accumulate.wgsl:20-23 applied once per sample, in sample order; id history shift main.rs:206.  A pixel outside the active rectangle
 // (RenderParams::act_*) never had a path: each of its samples is the miss result of integrator.rs:263-266 — radiance 0.006, id 255,
 // position r.at(1e5) of that sample's camera ray (:156-157) — added sample by sample like any other.
@@ -2322,22 +2356,36 @@ __device__ __forceinline__ f3 finalise(f3 acc)
 // sharded frame: the active pixels fill ~250 workgroups, one wave per SIMD, and the kernel waits on memory latency): FOUR lanes per
 // pixel; lane q loads and finalises samples q, q + 4, ... and all four lanes then add the quad's values in sample order (DPP quad
 // broadcasts; the sums are redundant, the loads are not): four times the loads in flight.
-template <bool FEW_PIXELS>
+//
+// MOMENTS (PT_FLAG_ADAPTIVE): moments[pixel] += L * L once per sample beside the colour, in the same order, L = luminance of the finalised
+// sample.  LIST (pt_render_adaptive): one thread (quad) per entry of the adaptive list instead of per local pixel; unlisted pixels are
+// not touched, and entry k's sample s is the pixel's sample n_p + first_sample + s (path_pixel_list).
+template <bool FEW_PIXELS, bool MOMENTS = false, bool LIST = false>
 __global__ void __launch_bounds__(256) k_accumulate(const RenderParams rp, const CameraView cam, const PathState st, f4* accum, f4* position, uint32_t* id,
-                                                     const uint32_t write_position, const uint32_t add_to_accum)
+                                                     const uint32_t write_position, const uint32_t add_to_accum, float* moments, const uint2* list)
 {
     const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t lp = FEW_PIXELS ? tid >> 2 : tid, q = FEW_PIXELS ? (tid & 3u) : 0u;
-    if (lp >= rp.local_pixels) return;
+    const uint32_t t = FEW_PIXELS ? tid >> 2 : tid, q = FEW_PIXELS ? (tid & 3u) : 0u;
+    if (t >= (LIST ? rp.act_pixels : rp.local_pixels)) return;
+    uint2 entry{t, 0u};
+    if (LIST) entry = list[t];
+    const uint32_t lp = entry.x;
     f4 a = accum[lp];
+    float qv = 0.0f;
+    if (MOMENTS) qv = moments[lp];
     uint32_t idv = id[lp];
     const uint32_t ly = fastdiv(lp, rp.div_width), x = lp - ly * rp.width;
-    if (x - rp.act_x0 >= rp.act_w || ly - rp.act_ly0 >= rp.act_rows)
+    if (!LIST && (x - rp.act_x0 >= rp.act_w || ly - rp.act_ly0 >= rp.act_rows))
     {
-        for (uint32_t s = 0; s < rp.batch_samples; ++s) a = f4{a.x + 0.006f, a.y + 0.006f, a.z + 0.006f, a.w + 1.0f};
+        for (uint32_t s = 0; s < rp.batch_samples; ++s)
+        {
+            a = f4{a.x + 0.006f, a.y + 0.006f, a.z + 0.006f, a.w + 1.0f};
+            if (MOMENTS) { const float l = luminance(0.006f, 0.006f, 0.006f); qv = qv + l * l; }
+        }
         for (uint32_t s = rp.batch_samples >= 2u ? rp.batch_samples - 2u : 0u; s < rp.batch_samples; ++s) idv = (idv << 16) | 255u;
         if (q != 0u) return;
         if (add_to_accum) accum[lp] = a;
+        if (MOMENTS && add_to_accum) moments[lp] = qv;
         id[lp] = idv;
         if (write_position)
         {
@@ -2347,7 +2395,7 @@ __global__ void __launch_bounds__(256) k_accumulate(const RenderParams rp, const
         }
         return;
     }
-    const uint32_t k = (ly - rp.act_ly0) * rp.act_w + (x - rp.act_x0);
+    const uint32_t k = LIST ? t : (ly - rp.act_ly0) * rp.act_w + (x - rp.act_x0);
     if (FEW_PIXELS)
     {
         constexpr uint32_t G = 4; // samples per lane and round: 16 per pixel
@@ -2377,6 +2425,7 @@ __global__ void __launch_bounds__(256) k_accumulate(const RenderParams rp, const
                     const float cy = asf(__builtin_amdgcn_mov_dpp(asu(c[j].y), SEL, 0xF, 0xF, true));                                 \
                     const float cz = asf(__builtin_amdgcn_mov_dpp(asu(c[j].z), SEL, 0xF, 0xF, true));                                 \
                     a = f4{a.x + cx, a.y + cy, a.z + cz, a.w + 1.0f};                                                                  \
+                    if (MOMENTS) { const float l = luminance(cx, cy, cz); qv = qv + l * l; }                                           \
                 }
                 PT_QUAD_ADD(0x00, 0u) PT_QUAD_ADD(0x55, 1u) PT_QUAD_ADD(0xAA, 2u) PT_QUAD_ADD(0xFF, 3u)
 #undef PT_QUAD_ADD
@@ -2408,19 +2457,21 @@ __global__ void __launch_bounds__(256) k_accumulate(const RenderParams rp, const
                 if ((s0 + j) >= rp.batch_samples) break;
                 const f3 c = finalise(xyz(rad[j]));
                 a = f4{a.x + c.x, a.y + c.y, a.z + c.z, a.w + 1.0f};
+                if (MOMENTS) { const float l = luminance(c.x, c.y, c.z); qv = qv + l * l; }
                 // (id << 16) | new once per sample: only the last two samples survive in 32 bits; a PRIMARY_MISS is id 255 (integrator.rs:157)
                 if (s0 + j >= rp.keep_s_id) idv = (idv << 16) | (oc[j] == PRIMARY_MISS ? 255u : st.first_id[(s0 + j - rp.keep_s_id) * rp.act_pixels + k]);
             }
         }
     }
     if (add_to_accum) accum[lp] = a;
+    if (MOMENTS && add_to_accum) moments[lp] = qv;
     id[lp] = idv;
     if (write_position)
     {
         // the batch's last sample.  A camera ray that left the scene at once has no record: r.at(1e5) of that sample's ray (integrator.rs:156)
         if (st.occl[pid_join(rp, rp.keep_s_pos, k)] == PRIMARY_MISS)
         {
-            const f3 d = camera_ray_dir(rp, cam, x, global_row(rp, ly), rp.first_sample + rp.keep_s_pos);
+            const f3 d = camera_ray_dir(rp, cam, x, global_row(rp, ly), entry.y + rp.first_sample + rp.keep_s_pos);
             const f3 far = fma3(d, bc3(1e5f), f3{cam.eye[0], cam.eye[1], cam.eye[2]});
             position[lp] = f4{far.x, far.y, far.z, 1e5f};
         }
@@ -2442,6 +2493,88 @@ __global__ void __launch_bounds__(256) k_store_samples(const RenderParams rp, co
         c = finalise(st.occl[pid] == PRIMARY_MISS ? f3{0.006f, 0.006f, 0.006f} : xyz(st.radiance[pid]));
     }
     out[i] = f4{c.x, c.y, c.z, 1.0f};
+}
+
+// ------------------------------------------------------------------------------------------------ adaptive selection (PT_FLAG_ADAPTIVE)
+// The criterion of pt_api.h's pt_adaptive, in f32 with every operation correctly rounded and in this order (the tests restate it in
+// numpy bit for bit).  The count is an exact integer in [0, 2^24] or the pixel is bad (the call fails with PT_ERR_LIMIT).
+__device__ __forceinline__ bool adaptive_active(const f4 a, const float qsum, const AdaptiveCrit& cr, uint32_t& n_p, bool& bad)
+{
+    const float n = a.w;
+    bad = !(n >= 0.0f && n <= 16777216.0f && n == truncf(n));
+    n_p = bad ? 0u : (uint32_t)n;
+    const float m = luminance(a.x, a.y, a.z) / n;
+    float v = qsum / n - m * m;
+    if (!(v > 0.0f)) v = 0.0f;
+    const float e2 = v / n;
+    const float t = cr.rel_error * (m > cr.abs_floor ? m : cr.abs_floor);
+    return !bad && (n_p < cr.min_samples || ((cr.max_samples == 0u || n_p < cr.max_samples) && e2 > t * t));
+}
+
+// Two passes, no atomic append: the list comes out in ascending pixel order whatever the scheduling.  Block b owns local pixels
+// [b * kSelectPerBlock, (b + 1) * kSelectPerBlock), thread i of it pixels b * kSelectPerBlock + j * 256 + i (j = 0..3).
+// k_adaptive_count: active pixels per block -> counts[b]; a bad count anywhere sets header[1].
+__global__ void __launch_bounds__(256) k_adaptive_count(const f4* __restrict__ accum, const float* __restrict__ moments, const uint32_t n_pixels,
+                                                        const AdaptiveCrit cr, uint32_t* counts, uint32_t* header)
+{
+    __shared__ uint32_t sh_cnt[4];
+    const uint32_t base = blockIdx.x * kSelectPerBlock;
+    uint32_t mine = 0u;
+    bool any_bad = false;
+#pragma unroll
+    for (uint32_t j = 0; j < kSelectPerBlock / 256u; ++j)
+    {
+        const uint32_t p = base + j * 256u + threadIdx.x;
+        if (p >= n_pixels) break;
+        uint32_t n_p;
+        bool bad;
+        mine += adaptive_active(accum[p], moments[p], cr, n_p, bad) ? 1u : 0u;
+        any_bad |= bad;
+    }
+    if (any_bad) atomicOr(header + 1, 1u);
+    uint32_t w = mine;
+    for (int off = 32; off > 0; off >>= 1) w += (uint32_t)__shfl_xor((int)w, off);
+    if (lane_id() == 0u) sh_cnt[threadIdx.x >> 6] = w;
+    __syncthreads();
+    if (threadIdx.x == 0u) counts[blockIdx.x] = sh_cnt[0] + sh_cnt[1] + sh_cnt[2] + sh_cnt[3];
+}
+// k_adaptive_write: the block's offset is the sum of the counts of the blocks before it; each group of 256 pixels is compacted with
+// one ballot per wave, mbcnt for a lane's rank in its wave and the waves' counts in LDS.  The last block writes the total to header[0].
+__global__ void __launch_bounds__(256) k_adaptive_write(const f4* __restrict__ accum, const float* __restrict__ moments, const uint32_t n_pixels,
+                                                        const AdaptiveCrit cr, const uint32_t* __restrict__ counts, uint2* list, uint32_t* header)
+{
+    __shared__ uint32_t sh_sum[4];
+    __shared__ uint32_t sh_wave[kSelectPerBlock / 256u][4];
+    const uint32_t wid = threadIdx.x >> 6;
+    uint32_t before = 0u;
+    for (uint32_t b = threadIdx.x; b < blockIdx.x; b += 256u) before += counts[b];
+    for (int off = 32; off > 0; off >>= 1) before += (uint32_t)__shfl_xor((int)before, off);
+    if (lane_id() == 0u) sh_sum[wid] = before;
+    const uint32_t base = blockIdx.x * kSelectPerBlock;
+    bool act[kSelectPerBlock / 256u];
+    uint32_t np[kSelectPerBlock / 256u];
+    uint64_t m[kSelectPerBlock / 256u];
+#pragma unroll
+    for (uint32_t j = 0; j < kSelectPerBlock / 256u; ++j)
+    {
+        const uint32_t p = base + j * 256u + threadIdx.x;
+        bool bad;
+        np[j] = 0u;
+        act[j] = p < n_pixels && adaptive_active(accum[p], moments[p], cr, np[j], bad);
+        m[j] = __ballot(act[j]);
+        if (lane_id() == 0u) sh_wave[j][wid] = (uint32_t)__popcll(m[j]);
+    }
+    __syncthreads();
+    uint32_t off = sh_sum[0] + sh_sum[1] + sh_sum[2] + sh_sum[3];
+#pragma unroll
+    for (uint32_t j = 0; j < kSelectPerBlock / 256u; ++j)
+    {
+        uint32_t pos = off;
+        for (uint32_t w2 = 0; w2 < wid; ++w2) pos += sh_wave[j][w2];
+        if (act[j]) list[pos + mbcnt64(m[j])] = uint2{base + j * 256u + threadIdx.x, np[j]};
+        off += sh_wave[j][0] + sh_wave[j][1] + sh_wave[j][2] + sh_wave[j][3];
+    }
+    if (blockIdx.x + 1u == gridDim.x && threadIdx.x == 0u) header[0] = off;
 }
 
 // ------------------------------------------------------------------------------------------------ probes
@@ -2524,10 +2657,11 @@ __global__ void k_volume_probe(const SceneView sv, int material, uint32_t n, con
 } // namespace
 
 // ================================================================================================ launchers
-void launch_generate(hipStream_t s, const RenderParams& rp, const CameraView& cam, const WavefrontBuffers& wb)
+void launch_generate(hipStream_t s, const RenderParams& rp, const CameraView& cam, const WavefrontBuffers& wb, const uint2* list)
 {
     const uint32_t blocks = (rp.n_paths + 255u) / 256u;
-    hipLaunchKernelGGL(k_generate, dim3(blocks), dim3(256), 0, s, rp, cam, wb.rq[0], wb.counters);
+    if (list) hipLaunchKernelGGL(k_generate_list, dim3(blocks), dim3(256), 0, s, rp, cam, wb.rq[0], wb.counters, list);
+    else hipLaunchKernelGGL(k_generate, dim3(blocks), dim3(256), 0, s, rp, cam, wb.rq[0], wb.counters);
 }
 
 // A persistent grid must be RESIDENT: workgroups that the device cannot hold at once start only when others have left, and by then
@@ -2739,7 +2873,7 @@ bool shade_traces_shadow(const TraceLaunch& tl)
            trace_lds_bytes(tl) + 1024 <= 32 * 1024;
 }
 void launch_shade(hipStream_t s, uint32_t qclass, const SceneView& sv, const RenderParams& rp, const WavefrontBuffers& wb, uint32_t b,
-                  uint32_t grid_blocks, const CameraView& cam, const EnvView& env, const TraceLaunch* tl)
+                  uint32_t grid_blocks, const CameraView& cam, const EnvView& env, const TraceLaunch* tl, const uint2* list)
 {
     ShadeIO io{};
     io.env = env;
@@ -2770,39 +2904,72 @@ void launch_shade(hipStream_t s, uint32_t qclass, const SceneView& sv, const Ren
     io.ctr_next = wb.counters + b + 1u;
     const uint32_t surface_blocks = (grid_blocks * 256u + PT_SHADE_THREADS - 1u) / PT_SHADE_THREADS; // grid_blocks is in units of 256 threads
     const bool inl = tl && shade_traces_shadow(*tl);
+    if (list && qclass != Q_TERMINAL) io.list = list; // (the surface passes read no terminal entries)
     const ShadeKArgs ka{sv, rp, io, b, inl ? (const uint4*)tl->blob : nullptr, inl ? tl->scene.world_root : 0u};
     const size_t lds = inl ? trace_lds_bytes(*tl) : 0;
+    // (LIST: the same classes over an adaptive list's paths, k_shade_surface_list)
+#define PT_SURF(Q, V, ...)                                                                                                              \
+    do {                                                                                                                                 \
+        if (list) hipLaunchKernelGGL((k_shade_surface<Q, V, __VA_ARGS__, true>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), lds, s, ka); \
+        else hipLaunchKernelGGL((k_shade_surface<Q, V, __VA_ARGS__>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), lds, s, ka);           \
+    } while (0)
     switch (qclass)
     {
     case Q_TERMINAL: hipLaunchKernelGGL(k_shade_terminal, dim3(grid_blocks), dim3(256), 0, s, sv, rp, io, b); break;
     case Q_LAMBERT:
-        if (inl && PT_IDENT_SHADE && ident_walk(*tl, IDENT_TLAS_WORLD)) hipLaunchKernelGGL((k_shade_surface<Q_LAMBERT, false, true, true>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), lds, s, ka);
-        else if (inl) hipLaunchKernelGGL((k_shade_surface<Q_LAMBERT, false, true>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), lds, s, ka);
-        else if (sv.has_volumes) hipLaunchKernelGGL((k_shade_surface<Q_LAMBERT, true>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), 0, s, ka);
-        else hipLaunchKernelGGL((k_shade_surface<Q_LAMBERT, false>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), 0, s, ka);
+        if (inl && PT_IDENT_SHADE && ident_walk(*tl, IDENT_TLAS_WORLD)) PT_SURF(Q_LAMBERT, false, true, true);
+        else if (inl) PT_SURF(Q_LAMBERT, false, true, false);
+        else if (sv.has_volumes) PT_SURF(Q_LAMBERT, true, false, false);
+        else PT_SURF(Q_LAMBERT, false, false, false);
         break;
     case Q_SPECULAR:
-        if (sv.has_volumes) hipLaunchKernelGGL((k_shade_surface<Q_SPECULAR, true>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), 0, s, ka);
-        else hipLaunchKernelGGL((k_shade_surface<Q_SPECULAR, false>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), 0, s, ka);
+        if (sv.has_volumes) PT_SURF(Q_SPECULAR, true, false, false);
+        else PT_SURF(Q_SPECULAR, false, false, false);
         break;
     case Q_DIELECTRIC:
-        if (sv.has_volumes) hipLaunchKernelGGL((k_shade_surface<Q_DIELECTRIC, true>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), 0, s, ka);
-        else hipLaunchKernelGGL((k_shade_surface<Q_DIELECTRIC, false>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), 0, s, ka);
+        if (sv.has_volumes) PT_SURF(Q_DIELECTRIC, true, false, false);
+        else PT_SURF(Q_DIELECTRIC, false, false, false);
         break;
     case Q_GGX:
-        if (sv.has_volumes) hipLaunchKernelGGL((k_shade_surface<Q_GGX, true>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), 0, s, ka);
-        else hipLaunchKernelGGL((k_shade_surface<Q_GGX, false>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), 0, s, ka);
+        if (sv.has_volumes) PT_SURF(Q_GGX, true, false, false);
+        else PT_SURF(Q_GGX, false, false, false);
         break;
     default: break;
     }
+#undef PT_SURF
 }
 
 void launch_accumulate(hipStream_t s, const RenderParams& rp, const CameraView& cam, const WavefrontBuffers& wb, f4* accum, f4* position, uint32_t* id,
                        uint32_t write_position, uint32_t add_to_accum)
 {
     const uint32_t blocks = (rp.local_pixels + 255u) / 256u;
-    if (rp.local_pixels < (uint32_t)PT_ACC_QUAD_BELOW) hipLaunchKernelGGL(k_accumulate<true>, dim3((rp.local_pixels * 4u + 255u) / 256u), dim3(256), 0, s, rp, cam, wb.st, accum, position, id, write_position, add_to_accum);
-    else hipLaunchKernelGGL(k_accumulate<false>, dim3(blocks), dim3(256), 0, s, rp, cam, wb.st, accum, position, id, write_position, add_to_accum);
+    if (rp.local_pixels < (uint32_t)PT_ACC_QUAD_BELOW) hipLaunchKernelGGL(k_accumulate<true>, dim3((rp.local_pixels * 4u + 255u) / 256u), dim3(256), 0, s, rp, cam, wb.st, accum, position, id, write_position, add_to_accum,
+                                                                  nullptr, nullptr);
+    else hipLaunchKernelGGL(k_accumulate<false>, dim3(blocks), dim3(256), 0, s, rp, cam, wb.st, accum, position, id, write_position, add_to_accum, nullptr, nullptr);
+}
+void launch_accumulate_moments(hipStream_t s, const RenderParams& rp, const CameraView& cam, const WavefrontBuffers& wb, f4* accum, f4* position, uint32_t* id,
+                               uint32_t write_position, uint32_t add_to_accum, float* moments, const uint2* list)
+{
+    const uint32_t n = list ? rp.act_pixels : rp.local_pixels;
+    if (n == 0u) return;
+    const bool quad = n < (uint32_t)PT_ACC_QUAD_BELOW;
+    const dim3 grid(quad ? (n * 4u + 255u) / 256u : (n + 255u) / 256u);
+    if (list)
+    {
+        if (quad) hipLaunchKernelGGL((k_accumulate<true, true, true>), grid, dim3(256), 0, s, rp, cam, wb.st, accum, position, id, write_position, add_to_accum, moments, list);
+        else hipLaunchKernelGGL((k_accumulate<false, true, true>), grid, dim3(256), 0, s, rp, cam, wb.st, accum, position, id, write_position, add_to_accum, moments, list);
+    }
+    else if (quad) hipLaunchKernelGGL((k_accumulate<true, true, false>), grid, dim3(256), 0, s, rp, cam, wb.st, accum, position, id, write_position, add_to_accum, moments, list);
+    else hipLaunchKernelGGL((k_accumulate<false, true, false>), grid, dim3(256), 0, s, rp, cam, wb.st, accum, position, id, write_position, add_to_accum, moments, list);
+}
+uint32_t adaptive_select_blocks(uint32_t n_pixels) { return (n_pixels + kSelectPerBlock - 1u) / kSelectPerBlock; }
+void launch_adaptive_select(hipStream_t s, const f4* accum, const float* moments, uint32_t n_pixels, const AdaptiveCrit& cr, uint32_t* counts, uint2* list,
+                            uint32_t* header)
+{
+    const uint32_t blocks = adaptive_select_blocks(n_pixels);
+    if (blocks == 0u) return;
+    hipLaunchKernelGGL(k_adaptive_count, dim3(blocks), dim3(256), 0, s, accum, moments, n_pixels, cr, counts, header);
+    hipLaunchKernelGGL(k_adaptive_write, dim3(blocks), dim3(256), 0, s, accum, moments, n_pixels, cr, (const uint32_t*)counts, list, header);
 }
 void launch_store_samples(hipStream_t s, const RenderParams& rp, const WavefrontBuffers& wb, f4* out)
 {

@@ -193,6 +193,14 @@ struct RenderParams
     FastDiv div_blk_paths, div_blk_last, div_act_w, div_width, div_strip_rows; // div_blk_paths: by act_pixels << blk_log
 };
 
+// selection criterion of an adaptive render (pt_adaptive, include/pt_api.h), validated by the host
+struct AdaptiveCrit
+{
+    float rel_error, abs_floor;
+    uint32_t min_samples, max_samples; // max_samples 0: no cap
+};
+enum : uint32_t { kSelectPerBlock = 1024u }; // local pixels per workgroup of the selection kernels (k_adaptive_count / k_adaptive_write)
+
 // wavefront state, one slot per path (pid = s_local * local_pixels + local_pixel).  What a shading pass reads and writes together is
 // ONE 64-byte record: in later bounces only a sparse subset of paths is alive, and a record costs one memory sector per live path
 // where a structure of arrays costs one sector per field.
