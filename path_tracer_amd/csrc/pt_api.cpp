@@ -859,10 +859,9 @@ int batch_end(BatchRun& br)
     else
     {
         Timer t(c, pp, s, T_ACCUM);
-        if (c->cfg.flags & PT_FLAG_ADAPTIVE)
-            launch_accumulate_moments(s, rp, br.cam, wb, (f4*)c->d_accum.p, (f4*)c->d_position.p, (uint32_t*)c->d_id.p, br.write_position ? 1u : 0u, 1u,
-                                      (float*)c->d_moments.p, c->cur_list);
-        else launch_accumulate(s, rp, br.cam, wb, (f4*)c->d_accum.p, (f4*)c->d_position.p, (uint32_t*)c->d_id.p, br.write_position ? 1u : 0u, 1u);
+        const bool adaptive = (c->cfg.flags & PT_FLAG_ADAPTIVE) != 0;
+        launch_accumulate(s, rp, br.cam, wb, (f4*)c->d_accum.p, (f4*)c->d_position.p, (uint32_t*)c->d_id.p, br.write_position ? 1u : 0u, 1u,
+                          adaptive ? (float*)c->d_moments.p : nullptr, adaptive ? c->cur_list : nullptr);
     }
     HIPCHK(c, hipEventRecord(pp.ev_done, s));
     // only the rows the batch used come back (all of them were cleared: last_row + 1 <= cleared_rows)

@@ -77,12 +77,11 @@ void launch_shade(hipStream_t s, uint32_t qclass, const SceneView& sv, const Ren
                   uint32_t grid_blocks, const CameraView& cam, const EnvView& env, const TraceLaunch* tl = nullptr, const uint2* list = nullptr);
 // true: the shading pass answers the explicit-light shadow rays itself and nothing is queued for launch_trace_shadow
 bool shade_traces_shadow(const TraceLaunch& tl);
-// accum[pixel] += sum over batch samples in order of (finalised rgb, 1); position/id of the last samples
+// accum[pixel] += sum over batch samples in order of (finalised rgb, 1); position/id of the last samples.  With moments also
+// moments[pixel] += L * L of each finalised sample beside it (PT_FLAG_ADAPTIVE); with a list (which needs moments) only the listed
+// pixels, in list order
 void launch_accumulate(hipStream_t s, const RenderParams& rp, const CameraView& cam, const WavefrontBuffers& wb, f4* accum, f4* position, uint32_t* id,
-                       uint32_t write_position, uint32_t add_to_accum);
-// ... and moments[pixel] += L * L of each finalised sample beside it (PT_FLAG_ADAPTIVE); with a list only the listed pixels, in list order
-void launch_accumulate_moments(hipStream_t s, const RenderParams& rp, const CameraView& cam, const WavefrontBuffers& wb, f4* accum, f4* position, uint32_t* id,
-                               uint32_t write_position, uint32_t add_to_accum, float* moments, const uint2* list);
+                       uint32_t write_position, uint32_t add_to_accum, float* moments = nullptr, const uint2* list = nullptr);
 void launch_store_samples(hipStream_t s, const RenderParams& rp, const WavefrontBuffers& wb, f4* out);
 // adaptive selection of n_pixels local pixels: list <- {pixel, n_p} of every active pixel in ascending order, header[0] <- their number,
 // header[1] |= 1 if some count is not an integer in [0, 2^24] (the caller zeroes header[1]); counts: adaptive_select_blocks words

@@ -18,6 +18,7 @@
 
 #include <algorithm>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 namespace pt {
@@ -705,10 +706,19 @@ __device__ __forceinline__ f3 with_signs(const f3 v, uint32_t bits)
               asf((asu(v.z) & 0x7fffffffu) | (((bits >> 2) & 1u) << 31))};
 }
 
+// the scene's tables in a blob that starts at `base` (global memory, or its copy in LDS)
+__device__ __forceinline__ Blob blob_at(const SceneView& sv, const uint4* base)
+{
+    Blob b;
+    b.nodes = base;
+    b.tris = base + 2u * sv.n_nodes;
+    b.inst = base + 2u * sv.n_nodes + 3u * sv.n_tris;
+    b.leaves = reinterpret_cast<const uint2*>(base + 2u * sv.n_nodes + 3u * sv.n_tris + INST_WORDS * sv.n_instances);
+    return b;
+}
 template <bool LDS_SCENE>
 __device__ __forceinline__ Blob stage_scene(const SceneView& sv, const uint4* __restrict__ gblob, uint4* smem, uint32_t& words)
 {
-    Blob b;
     const uint4* base = gblob;
     words = 0;
     if (LDS_SCENE)
@@ -718,11 +728,7 @@ __device__ __forceinline__ Blob stage_scene(const SceneView& sv, const uint4* __
         __syncthreads();
         base = smem;
     }
-    b.nodes = base;
-    b.tris = base + 2u * sv.n_nodes;
-    b.inst = base + 2u * sv.n_nodes + 3u * sv.n_tris;
-    b.leaves = reinterpret_cast<const uint2*>(base + 2u * sv.n_nodes + 3u * sv.n_tris + INST_WORDS * sv.n_instances);
-    return b;
+    return blob_at(sv, base);
 }
 
 // CLOSEST_PRIMARY = CLOSEST_WORLD for bounce 0: every ray starts at the eye (only directions are stored, ray index == path id)
@@ -810,9 +816,107 @@ struct Stack8<true>
     }
 };
 
+// ---- diagnostics of variant builds: the members are empty when the macro is 0
+// PT_STEP_STATS: per traversal step, how many lanes take each section.  Words 8..15 of the launch's cursor lines (tools/step_stats.py,
+// pt_last_batch_step_stats): wave-steps executed, lanes active in them, lanes taking the instance / branch / leaf section, and (words
+// 13..15) wave-steps in which at least one lane took that section.
+struct StepStats
+{
+    enum { INST = 0, BRANCH = 1, LEAF = 2 };
+#if PT_STEP_STATS
+    uint32_t iter = 0, lanes = 0, lane[3] = {0u, 0u, 0u}, wave[3] = {0u, 0u, 0u};
+#endif
+    // the wave starts a step (every lane calls this)
+    __device__ __forceinline__ void step(bool active)
+    {
+#if PT_STEP_STATS
+        const uint64_t am = __ballot(active);
+        if (am != 0ull) { iter += 1u; lanes += (uint32_t)__popcll(am); }
+#endif
+    }
+    // the lanes that reach section s of the step: x = this lane takes it
+    __device__ __forceinline__ void section(int s, bool x)
+    {
+#if PT_STEP_STATS
+        const uint64_t m = __ballot(x);
+        lane[s] += x ? 1u : 0u;
+        if (m != 0ull && lane_id() == (uint32_t)__builtin_ctzll(m)) wave[s] += 1u;
+#endif
+    }
+    __device__ __forceinline__ void flush(uint32_t* heads) const
+    {
+#if PT_STEP_STATS
+        const uint32_t w = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+        uint32_t* line = heads + ((w * 7u) & (kQueueHeads - 1u)) * kHeadStrideWords;
+        if (lane_id() == 0u) { atomicAdd(line + 8, iter); atomicAdd(line + 9, lanes); }
+        uint32_t a = lane[0], b = lane[1], c = lane[2];
+        for (int off = 32; off > 0; off >>= 1) { a += __shfl_xor(a, off); b += __shfl_xor(b, off); c += __shfl_xor(c, off); }
+        if (lane_id() == 0u) { atomicAdd(line + 10, a); atomicAdd(line + 11, b); atomicAdd(line + 12, c); }
+        a = wave[0]; b = wave[1]; c = wave[2];
+        for (int off = 32; off > 0; off >>= 1) { a += __shfl_xor(a, off); b += __shfl_xor(b, off); c += __shfl_xor(c, off); }
+        if (lane_id() == 0u) { atomicAdd(line + 13, a); atomicAdd(line + 14, b); atomicAdd(line + 15, c); }
+#endif
+    }
+};
+// PT_WAVE_TIMES: one record per wave (100 MHz ticks, low 32 bits): start, first rays, queue found empty, end; the host reduces them
+// (pt_last_batch_step_stats, tools/wave_times.py)
+struct WaveTimes
+{
+#if PT_WAVE_TIMES
+    uint32_t start = (uint32_t)wall_clock64(), first = 0u, drained = 0u;
+#endif
+    __device__ __forceinline__ void check_drained(bool no_more)
+    {
+#if PT_WAVE_TIMES
+        if (no_more && drained == 0u) drained = (uint32_t)wall_clock64() | 1u;
+#endif
+    }
+    __device__ __forceinline__ void check_first(uint32_t take)
+    {
+#if PT_WAVE_TIMES
+        if (first == 0u && take != 0u) first = (uint32_t)wall_clock64() | 1u;
+#endif
+    }
+    __device__ __forceinline__ void write(uint4* times)
+    {
+#if PT_WAVE_TIMES
+        if (lane_id() == 0u && times)
+        {
+            const uint32_t end = (uint32_t)wall_clock64();
+            if (drained == 0u) drained = end;
+            if (first == 0u) first = start;
+            const uint32_t w = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+            if (w < kWaveTimeSlots) times[w] = make_uint4(start, first, drained, end | 1u);
+        }
+#endif
+    }
+};
 #if PT_WAVE_TIMES
 __device__ uint4* g_any_times = nullptr; // where the shadow-ray launch in flight puts its per-wave time records (set in-stream by launch_trace_shadow)
+#else
+constexpr uint4* g_any_times = nullptr;
 #endif
+
+// A shadow ray's answer applied to its path: blocked, it erases the path's explicit-light candidate (integrator.rs:55-56,73), so the next
+// shading pass needs no visibility word; visible, it leaves it alone.  A path that died in the shading pass with nothing else owed (`ends`)
+// has its radiance completed instead: accumulated += path_weight * (explicit + 0), integrator.rs:231-234.  radiance(): where that goes
+// (asked for only then).
+template <typename Radiance>
+__device__ __forceinline__ void apply_shadow(DPathRec* rec, bool ends, bool blocked, Radiance&& radiance)
+{
+    if (ends)
+    {
+        const f3 e = blocked ? f3{0.0f, 0.0f, 0.0f} : xyz(rec->nee_e);
+        const f3 acc = xyz(rec->acc) + xyz(rec->nee_pw) * (e + f3{0.0f, 0.0f, 0.0f});
+        radiance() = f4{acc.x, acc.y, acc.z, 0.0f};
+    }
+    else if (blocked)
+    {
+        float* e = reinterpret_cast<float*>(&rec->nee_e);
+        e[0] = 0.0f; e[1] = 0.0f; e[2] = 0.0f;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ closest hit
 // a traversal kernel's single argument (one struct, so that it starts at offset 0 of the kernel-argument segment)
 struct ClosestKArgs
@@ -861,13 +965,8 @@ __device__ __forceinline__ void closest_body(const SceneView& sv, const Blob& bl
     // material binning (CLOSEST_WORLD / PRIMARY): a retiring ray's hit record goes straight to its class's shade queue, into a region
     // of that queue this wave has reserved (wave_reserve: one atomic per region, none per entry)
     uint32_t light_hits = 0, valid_rays = 0;
-#if PT_STEP_STATS
-    uint32_t st_iter = 0, st_lane_active = 0, st_lane_inst = 0, st_lane_branch = 0, st_lane_leaf = 0, st_wave_inst = 0, st_wave_branch = 0, st_wave_leaf = 0;
-#endif
-#if PT_WAVE_TIMES
-    const uint32_t tw_start = (uint32_t)wall_clock64();
-    uint32_t tw_first = 0u, tw_drained = 0u;
-#endif
+    StepStats ss;
+    WaveTimes wt;
     Region bin_region[Q_COUNT];
 #pragma unroll
     for (uint32_t c = 0; c < Q_COUNT; ++c) bin_region[c] = Region{0u, 0u};
@@ -886,9 +985,7 @@ __device__ __forceinline__ void closest_body(const SceneView& sv, const Blob& bl
     {
         uint64_t act = __ballot(active);
         const bool no_more = wr.drained && wr.cur >= wr.end;
-#if PT_WAVE_TIMES
-        if (no_more && tw_drained == 0u) tw_drained = (uint32_t)wall_clock64() | 1u;
-#endif
+        wt.check_drained(no_more);
         const bool service = no_more ? (act == 0ull) : (__popcll(act) <= Refill<LDS_SCENE>::kBelow);
         if (service)
         {
@@ -1069,9 +1166,7 @@ __device__ __forceinline__ void closest_body(const SceneView& sv, const Blob& bl
                 else { pending = true; }
                 } // not a hole
             }
-#if PT_WAVE_TIMES
-            if (tw_first == 0u && take != 0u) tw_first = (uint32_t)wall_clock64() | 1u;
-#endif
+            wt.check_first(take);
             act = __ballot(active);
             if (act == 0ull) continue; // retires the lanes that missed the root box, then refills again or exits
             // the wave's chunk ended inside this refill: go round again at once for the next chunk instead of stepping with idle lanes
@@ -1081,12 +1176,7 @@ __device__ __forceinline__ void closest_body(const SceneView& sv, const Blob& bl
 #pragma unroll 1
         for (int it = 0; it < Refill<LDS_SCENE>::kSteps; ++it)
         {
-#if PT_STEP_STATS
-            {
-                const uint64_t am = __ballot(active);
-                if (am != 0ull) { st_iter += 1u; st_lane_active += (uint32_t)__popcll(am); }
-            }
-#endif
+            ss.step(active);
             if (!active) continue;
             if (!IDENT && in_blas && sp == blas_base) in_blas = false; // BLAS::intersect returned  blas.rs:255
             if (MODE == CLOSEST_LIGHTS && any_phase)
@@ -1171,9 +1261,7 @@ __device__ __forceinline__ void closest_body(const SceneView& sv, const Blob& bl
             if (asf(e.y) > t_max) continue;                  // tlas.rs:80-83 / blas.rs:222-225
             uint32_t link = e.x;
             float t_est = asf(e.y);
-#if PT_STEP_STATS
-            { const bool x = (link >> NODE_KIND_SHIFT) == NODE_INSTANCE; const uint64_t m = __ballot(x); st_lane_inst += x ? 1u : 0u; if (m != 0ull && lane_id() == (uint32_t)__builtin_ctzll(m)) st_wave_inst += 1u; }
-#endif
+            ss.section(StepStats::INST, (link >> NODE_KIND_SHIFT) == NODE_INSTANCE);
             if ((link >> NODE_KIND_SHIFT) == NODE_INSTANCE)
             {
                 // TLAS leaf: transform the ray, run the BLAS with the current t_max  tlas.rs:88-99.  BLAS::intersect pushes its root
@@ -1192,9 +1280,7 @@ __device__ __forceinline__ void closest_body(const SceneView& sv, const Blob& bl
                 t_est = 0.0f;
             }
             uint32_t kind = link >> NODE_KIND_SHIFT, payload = link & NODE_PAYLOAD_MASK;
-#if PT_STEP_STATS
-            { const bool x = kind == NODE_BRANCH; const uint64_t m = __ballot(x); st_lane_branch += x ? 1u : 0u; if (m != 0ull && lane_id() == (uint32_t)__builtin_ctzll(m)) st_wave_branch += 1u; }
-#endif
+            ss.section(StepStats::BRANCH, kind == NODE_BRANCH);
             // push_to_stack  blas.rs:133-162.  A near child that is itself a branch is expanded in the SAME step (up to PT_BRANCH_LEVELS
             // levels) instead of going through the stack: the kernel pays per wave-step far more than per section of a step
             // (profiles/r02_step_stats_cornell.md), and the reference would pop exactly that child next (its pop test t_enter > t_max
@@ -1228,9 +1314,7 @@ __device__ __forceinline__ void closest_body(const SceneView& sv, const Blob& bl
                     else { stk.put(sp, near); sp = stk.up(sp); }
                 }
             }
-#if PT_STEP_STATS
-            { const bool x = (kind & 1u) != 0u; const uint64_t m = __ballot(x); st_lane_leaf += x ? 1u : 0u; if (m != 0ull && lane_id() == (uint32_t)__builtin_ctzll(m)) st_wave_leaf += 1u; }
-#endif
+            ss.section(StepStats::LEAF, (kind & 1u) != 0u);
             if (kind & 1u)
             {
                 uint32_t first, count;
@@ -1269,33 +1353,8 @@ __device__ __forceinline__ void closest_body(const SceneView& sv, const Blob& bl
             for (uint32_t i = bin_region[c].cur + lane_id(); i < bin_region[c].end; i += 64u) qa[i] = hole;
         }
     }
-#if PT_WAVE_TIMES
-    // one record per wave (100 MHz ticks, low 32 bits): start, first rays, queue found empty, end; the host reduces them
-    // (pt_last_batch_step_stats in a PT_WAVE_TIMES build, tools/wave_times.py)
-    if (lane_id() == 0u && outp->wave_times)
-    {
-        const uint32_t tw_end = (uint32_t)wall_clock64();
-        if (tw_drained == 0u) tw_drained = tw_end;
-        if (tw_first == 0u) tw_first = tw_start;
-        const uint32_t wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-        if (wave < kWaveTimeSlots) outp->wave_times[wave] = make_uint4(tw_start, tw_first, tw_drained, tw_end | 1u);
-    }
-#endif
-#if PT_STEP_STATS
-    // words 8..15 of the cursor lines: wave-steps executed, lanes active in them, lanes taking the instance / branch / leaf section, and
-    // (words 13..15) wave-steps in which at least one lane took that section; tools/step_stats.py reads these.
-    {
-        const uint32_t wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-        uint32_t* line = heads + ((wave * 7u) & (kQueueHeads - 1u)) * kHeadStrideWords;
-        if (lane_id() == 0u) { atomicAdd(line + 8, st_iter); atomicAdd(line + 9, st_lane_active); }
-        uint32_t a = st_lane_inst, b = st_lane_branch, c2 = st_lane_leaf;
-        for (int off = 32; off > 0; off >>= 1) { a += __shfl_xor(a, off); b += __shfl_xor(b, off); c2 += __shfl_xor(c2, off); }
-        if (lane_id() == 0u) { atomicAdd(line + 10, a); atomicAdd(line + 11, b); atomicAdd(line + 12, c2); }
-        a = st_wave_inst; b = st_wave_branch; c2 = st_wave_leaf;
-        for (int off = 32; off > 0; off >>= 1) { a += __shfl_xor(a, off); b += __shfl_xor(b, off); c2 += __shfl_xor(c2, off); }
-        if (lane_id() == 0u) { atomicAdd(line + 13, a); atomicAdd(line + 14, b); atomicAdd(line + 15, c2); }
-    }
-#endif
+    wt.write(outp->wave_times);
+    ss.flush(heads);
     if (MODE != CLOSEST_HOOK) add_tally(heads, valid_rays, HEAD_TALLY0);
     // any-hit casts of integrator.rs:103
     if (MODE == CLOSEST_LIGHTS) add_tally(heads, light_hits, HEAD_TALLY1);
@@ -1337,47 +1396,24 @@ __device__ __forceinline__ void any_body(const SceneView& sv, const Blob& bl, co
     LaneRay w{}, ob{};
     float t_max = 0.0f;
     uint32_t sp = stk.empty(), blas_base = 0;
-    // ANY_SHADOW: `occluded` is PathState::rec: a blocked shadow ray erases the path's explicit-light candidate (integrator.rs:55-56,73)
-    // and a visible one leaves it alone, so the next shading pass needs no separate visibility word; ANY_HOOK: one word per ray
-    // A shadow ray whose path id carries PATH_ENDS belongs to a path that died in the shading pass with nothing else owed: its
-    // radiance is completed here (accumulated += path_weight * (explicit + 0), integrator.rs:231-234) instead of in a terminal pass.
+    // ANY_SHADOW: `occluded` is PathState::rec, and a shadow ray whose path id carries PATH_ENDS completes its path (apply_shadow);
+    // ANY_HOOK: one word per ray
     bool path_ends = false;
     auto put_result_at = [&](uint32_t idx, bool ends, uint32_t v) {
-        if (MODE == ANY_SHADOW)
-        {
-            DPathRec* rec = reinterpret_cast<DPathRec*>(occluded) + idx;
-            if (ends)
-            {
-                const f3 e = v != 0u ? f3{0.0f, 0.0f, 0.0f} : xyz(rec->nee_e);
-                const f3 acc = xyz(rec->acc) + xyz(rec->nee_pw) * (e + f3{0.0f, 0.0f, 0.0f});
-                radiance[idx] = f4{acc.x, acc.y, acc.z, 0.0f};
-            }
-            else if (v != 0u)
-            {
-                float* e = reinterpret_cast<float*>(&rec->nee_e);
-                e[0] = 0.0f; e[1] = 0.0f; e[2] = 0.0f;
-            }
-        }
+        if (MODE == ANY_SHADOW) apply_shadow(reinterpret_cast<DPathRec*>(occluded) + idx, ends, v != 0u, [&]() -> f4& { return radiance[idx]; });
         else occluded[idx] = v;
     };
     auto put_result = [&](uint32_t v) { put_result_at(out_idx, path_ends, v); };
     bool in_blas = false;
-#if PT_WAVE_TIMES
-    const uint32_t tw_start = (uint32_t)wall_clock64();
-    uint32_t tw_drained = 0u;
-#endif
-#if PT_STEP_STATS
-    uint32_t st_iter = 0, st_lane_active = 0, st_lane_inst = 0, st_lane_branch = 0, st_lane_leaf = 0, st_wave_inst = 0, st_wave_branch = 0, st_wave_leaf = 0;
-#endif
+    WaveTimes wt;
+    StepStats ss;
     WaveRange wr = first_range(plan, heads);
 
     for (;;)
     {
         uint64_t act = __ballot(active);
         const bool no_more = wr.drained && wr.cur >= wr.end;
-#if PT_WAVE_TIMES
-        if (no_more && tw_drained == 0u) tw_drained = (uint32_t)wall_clock64() | 1u;
-#endif
+        wt.check_drained(no_more);
         const bool service = no_more ? (act == 0ull) : (__popcll(act) <= Refill<LDS_SCENE>::kBelowAny);
         if (service)
         {
@@ -1425,12 +1461,7 @@ __device__ __forceinline__ void any_body(const SceneView& sv, const Blob& bl, co
 #pragma unroll 1
         for (int it = 0; it < Refill<LDS_SCENE>::kStepsAny; ++it)
         {
-#if PT_STEP_STATS
-            {
-                const uint64_t am = __ballot(active);
-                if (am != 0ull) { st_iter += 1u; st_lane_active += (uint32_t)__popcll(am); }
-            }
-#endif
+            ss.step(active);
             if (!active) continue;
             if (!IDENT && in_blas && sp == blas_base) in_blas = false;
             if (sp == stk.empty())
@@ -1443,9 +1474,7 @@ __device__ __forceinline__ void any_body(const SceneView& sv, const Blob& bl, co
             const uint2 e = stk.get(sp);                     // (link, entry distance) of a node whose box the ray meets
             uint32_t link = e.x;
             float t_enter = asf(e.y);
-#if PT_STEP_STATS
-            { const bool x = (link >> NODE_KIND_SHIFT) == NODE_INSTANCE; const uint64_t m = __ballot(x); st_lane_inst += x ? 1u : 0u; if (m != 0ull && lane_id() == (uint32_t)__builtin_ctzll(m)) st_wave_inst += 1u; }
-#endif
+            ss.section(StepStats::INST, (link >> NODE_KIND_SHIFT) == NODE_INSTANCE);
             if ((link >> NODE_KIND_SHIFT) == NODE_INSTANCE)
             {
                 // TLAS leaf: transform the ray; the BLAS root's box is the first thing BLAS::any_intersect tests  blas.rs:262-264
@@ -1465,9 +1494,7 @@ __device__ __forceinline__ void any_body(const SceneView& sv, const Blob& bl, co
                 link = r0.w;
             }
             uint32_t kind = link >> NODE_KIND_SHIFT, payload = link & NODE_PAYLOAD_MASK;
-#if PT_STEP_STATS
-            { const bool x = kind == NODE_BRANCH; const uint64_t m = __ballot(x); st_lane_branch += x ? 1u : 0u; if (m != 0ull && lane_id() == (uint32_t)__builtin_ctzll(m)) st_wave_branch += 1u; }
-#endif
+            ss.section(StepStats::BRANCH, kind == NODE_BRANCH);
             // up to PT_BRANCH_LEVELS_ANY levels per step: the child that would be popped next (right if met, else left) is expanded or
             // tested at once instead of going through the stack (the kernel pays per wave-step, profiles/r02_step_stats_cornell.md)
 #pragma unroll 1
@@ -1494,9 +1521,7 @@ __device__ __forceinline__ void any_body(const SceneView& sv, const Blob& bl, co
                     else { stk.put(sp, next); sp = stk.up(sp); }
                 }
             }
-#if PT_STEP_STATS
-            { const bool x = (kind & 1u) != 0u; const uint64_t m = __ballot(x); st_lane_leaf += x ? 1u : 0u; if (m != 0ull && lane_id() == (uint32_t)__builtin_ctzll(m)) st_wave_leaf += 1u; }
-#endif
+            ss.section(StepStats::LEAF, (kind & 1u) != 0u);
             if (kind & 1u)
             {
                 uint32_t first, count;
@@ -1515,32 +1540,12 @@ __device__ __forceinline__ void any_body(const SceneView& sv, const Blob& bl, co
             }
         }
     }
-#if PT_STEP_STATS
-    // words 8..15 of the shadow queue's cursor lines, as k_closest's (tools/step_stats.py any): wave-steps, lanes active, lanes taking the
-    // instance / branch / leaf section, wave-steps in which some lane took it
     if (MODE == ANY_SHADOW)
     {
-        const uint32_t wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-        uint32_t* line = heads + ((wave * 7u) & (kQueueHeads - 1u)) * kHeadStrideWords;
-        if (lane_id() == 0u) { atomicAdd(line + 8, st_iter); atomicAdd(line + 9, st_lane_active); }
-        uint32_t x = st_lane_inst, y = st_lane_branch, z = st_lane_leaf;
-        for (int off = 32; off > 0; off >>= 1) { x += __shfl_xor(x, off); y += __shfl_xor(y, off); z += __shfl_xor(z, off); }
-        if (lane_id() == 0u) { atomicAdd(line + 10, x); atomicAdd(line + 11, y); atomicAdd(line + 12, z); }
-        x = st_wave_inst; y = st_wave_branch; z = st_wave_leaf;
-        for (int off = 32; off > 0; off >>= 1) { x += __shfl_xor(x, off); y += __shfl_xor(y, off); z += __shfl_xor(z, off); }
-        if (lane_id() == 0u) { atomicAdd(line + 13, x); atomicAdd(line + 14, y); atomicAdd(line + 15, z); }
+        ss.flush(heads); // (the shadow queue's cursor lines, as k_closest's: tools/step_stats.py any)
+        add_tally(heads, valid_rays, HEAD_TALLY0);
+        wt.write(g_any_times);
     }
-#endif
-    if (MODE == ANY_SHADOW) add_tally(heads, valid_rays, HEAD_TALLY0);
-#if PT_WAVE_TIMES
-    if (MODE == ANY_SHADOW && lane_id() == 0u && g_any_times)
-    {
-        const uint32_t tw_end = (uint32_t)wall_clock64();
-        if (tw_drained == 0u) tw_drained = tw_end;
-        const uint32_t wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-        if (wave < kWaveTimeSlots) g_any_times[wave] = make_uint4(tw_start, tw_start, tw_drained, tw_end | 1u);
-    }
-#endif
 }
 template <int BVH, int MODE, bool SPILL, bool IDENT = false>
 __global__ void __launch_bounds__(256, BVH != 0 ? PT_WAVES_LDS_BVH_ANY : PT_WAVES_GLOBAL_BVH_ANY) k_any(const SceneView sv, const uint4* __restrict__ gblob, const uint32_t root, const f4* __restrict__ ra,
@@ -2291,37 +2296,19 @@ __global__ void __launch_bounds__(PT_SHADE_THREADS, INLINE ? PT_SHADE_WAVES_INLI
         }
         if (INLINE)
         {
-            // the explicit-light shadow ray is answered here, after the record is on its way: what k_any<SHADOW> does to the record (put_result_at), same arithmetic
+            // the explicit-light shadow ray is answered here, after the record is on its way, and applied to it as k_any<SHADOW> does (apply_shadow)
             // (the stack's base is recomputed here, behind an opaque move, rather than kept in a register across the iteration)
             // ... and so is the description of the staged scene (re-read from the kernel-argument segment like every other section's)
             uint32_t tid = threadIdx.x;
             asm volatile("" : "+v"(tid));
             const ShadeKArgs& ka2 = shade_args();
             const uint32_t blob_words = ka2.sv.blob_bytes >> 4;
-            Blob bl;
-            bl.nodes = smem_dyn;
-            bl.tris = smem_dyn + 2u * ka2.sv.n_nodes;
-            bl.inst = smem_dyn + 2u * ka2.sv.n_nodes + 3u * ka2.sv.n_tris;
-            bl.leaves = reinterpret_cast<const uint2*>(smem_dyn + 2u * ka2.sv.n_nodes + 3u * ka2.sv.n_tris + INST_WORDS * ka2.sv.n_instances);
+            const Blob bl = blob_at(ka2.sv, smem_dyn);
             const Stack8<false> stk{reinterpret_cast<char*>(smem_dyn), blob_words * 16u + tid * 8u, blockDim.x * 8u};
             traced += (uint32_t)__popcll(__ballot(want_shadow)); // (both counted here, where the whole wave is: wave-uniform values in scalar registers)
             culled += (uint32_t)__popcll(__ballot(cull_now));
             const bool blocked = inline_any<IDENT>(bl, stk, ka2.world_root, sh_a, sh_b, want_shadow);
-            if (want_shadow)
-            {
-                DPathRec* rec = shade_args().io.st.rec + pid;
-                if (ends_with_shadow)
-                {
-                    const f3 e = blocked ? f3{0.0f, 0.0f, 0.0f} : xyz(rec->nee_e);
-                    const f3 a2 = xyz(rec->acc) + xyz(rec->nee_pw) * (e + f3{0.0f, 0.0f, 0.0f});
-                    shade_args().io.st.radiance[pid] = f4{a2.x, a2.y, a2.z, 0.0f};
-                }
-                else if (blocked)
-                {
-                    float* e = reinterpret_cast<float*>(&rec->nee_e);
-                    e[0] = 0.0f; e[1] = 0.0f; e[2] = 0.0f;
-                }
-            }
+            if (want_shadow) apply_shadow(shade_args().io.st.rec + pid, ends_with_shadow, blocked, [&]() -> f4& { return shade_args().io.st.radiance[pid]; });
             a_next = (idx + stride) < n ? nt_load(shade_args().io.q_in.a + idx + stride) : hole_a;
         }
     }
@@ -2701,52 +2688,48 @@ static uint32_t tlas_bits(const TraceLaunch& tl, uint32_t root, bool with_world)
 // the IDENT kernels (one ray per lane, ident_ray) walk a launch whose every TLAS holds identity instances only
 static bool ident_walk(const TraceLaunch& tl, uint32_t bits) { return (tl.ident_tlas & bits) == bits; }
 
+// The traversal kernels' variant for a launch, picked once: f(BVH, SPILL, IDENT) with each as a std::integral_constant.  BVH 1: the
+// scene's BVH is staged in LDS; SPILL: the stack's deepest levels live in global memory (Stack8<true>); IDENT: ident_walk.
+template <typename F>
+static void with_trace_variant(const TraceLaunch& tl, bool ident, F&& f)
+{
+    const bool spill = tl.scene.stack_entries > tl.scene.stack_lds;
+    auto bvh = [&](auto sp, auto id) {
+        if (tl.lds_scene) f(std::integral_constant<int, 1>{}, sp, id);
+        else f(std::integral_constant<int, 0>{}, sp, id);
+    };
+    auto stack = [&](auto id) {
+        if (spill) bvh(std::true_type{}, id);
+        else bvh(std::false_type{}, id);
+    };
+    if (ident) stack(std::true_type{});
+    else stack(std::false_type{});
+}
+// a persistent traversal grid (resident_grid, per kernel) with the launch's dynamic LDS
+template <typename K, typename... A>
+static void launch_resident(K kernel, const TraceLaunch& tl, hipStream_t s, const A&... args)
+{
+    const size_t lds = trace_lds_bytes(tl);
+    hipLaunchKernelGGL(kernel, dim3(resident_grid(kernel, tl, lds)), dim3(tl.block_threads), lds, s, args...);
+}
+
 template <int MODE>
 static void launch_closest_impl(hipStream_t s, const TraceLaunch& tl, uint32_t root, const RayQueue& rq, const uint32_t* n_ptr, uint32_t cap_in,
                                 uint32_t* heads, const ClosestOut& out)
 {
-    const bool ident = ident_walk(tl, tlas_bits(tl, root, MODE == CLOSEST_LIGHTS));
-    const bool spill = tl.scene.stack_entries > tl.scene.stack_lds;
-    const dim3 block(tl.block_threads);
-    const uint4* blob = (const uint4*)tl.blob;
-    const size_t lds = trace_lds_bytes(tl);
-    const ClosestKArgs ka{tl.scene, blob, rq.a, rq.b, n_ptr, heads, root, cap_in, out};
-#define PT_LAUNCH1(K) hipLaunchKernelGGL(K, dim3(resident_grid(K, tl, lds)), block, lds, s, ka)
-    if (ident)
-    {
-        if (tl.lds_scene && !spill) PT_LAUNCH1((k_closest<1, MODE, false, true>));
-        else if (tl.lds_scene) PT_LAUNCH1((k_closest<1, MODE, true, true>));
-        else if (!spill) PT_LAUNCH1((k_closest<0, MODE, false, true>));
-        else PT_LAUNCH1((k_closest<0, MODE, true, true>));
-    }
-    else if (tl.lds_scene && !spill) PT_LAUNCH1((k_closest<1, MODE, false>));
-    else if (tl.lds_scene) PT_LAUNCH1((k_closest<1, MODE, true>));
-    else if (!spill) PT_LAUNCH1((k_closest<0, MODE, false>));
-    else PT_LAUNCH1((k_closest<0, MODE, true>));
-#undef PT_LAUNCH1
+    const ClosestKArgs ka{tl.scene, (const uint4*)tl.blob, rq.a, rq.b, n_ptr, heads, root, cap_in, out};
+    with_trace_variant(tl, ident_walk(tl, tlas_bits(tl, root, MODE == CLOSEST_LIGHTS)), [&](auto bvh, auto spill, auto ident) {
+        launch_resident(k_closest<bvh, MODE, spill, ident>, tl, s, ka);
+    });
 }
 template <int MODE>
 static void launch_any_impl(hipStream_t s, const TraceLaunch& tl, uint32_t root, const RayQueue& rq, const uint32_t* n_ptr, uint32_t cap_in,
                             uint32_t* heads, uint32_t* occluded, f4* radiance = nullptr)
 {
-    const bool ident = ident_walk(tl, tlas_bits(tl, root, false));
-    const size_t lds = trace_lds_bytes(tl);
-    const bool spill = tl.scene.stack_entries > tl.scene.stack_lds;
-    const dim3 block(tl.block_threads);
     const uint4* blob = (const uint4*)tl.blob;
-#define PT_LAUNCH(K) hipLaunchKernelGGL(K, dim3(resident_grid(K, tl, lds)), block, lds, s, tl.scene, blob, root, rq.a, rq.b, n_ptr, cap_in, heads, occluded, radiance)
-    if (ident)
-    {
-        if (tl.lds_scene && !spill) PT_LAUNCH((k_any<1, MODE, false, true>));
-        else if (tl.lds_scene) PT_LAUNCH((k_any<1, MODE, true, true>));
-        else if (!spill) PT_LAUNCH((k_any<0, MODE, false, true>));
-        else PT_LAUNCH((k_any<0, MODE, true, true>));
-    }
-    else if (tl.lds_scene && !spill) PT_LAUNCH((k_any<1, MODE, false>));
-    else if (tl.lds_scene) PT_LAUNCH((k_any<1, MODE, true>));
-    else if (!spill) PT_LAUNCH((k_any<0, MODE, false>));
-    else PT_LAUNCH((k_any<0, MODE, true>));
-#undef PT_LAUNCH
+    with_trace_variant(tl, ident_walk(tl, tlas_bits(tl, root, false)), [&](auto bvh, auto spill, auto ident) {
+        launch_resident(k_any<bvh, MODE, spill, ident>, tl, s, tl.scene, blob, root, rq.a, rq.b, n_ptr, cap_in, heads, occluded, radiance);
+    });
 }
 
 static uint32_t* row_heads(const WavefrontBuffers& wb, uint32_t row, uint32_t which)
@@ -2754,8 +2737,9 @@ static uint32_t* row_heads(const WavefrontBuffers& wb, uint32_t row, uint32_t wh
     return wb.heads + ((size_t)row * HEADS_PER_ROW + which) * kHeadWordsPerQueue;
 }
 
-void launch_trace_world(hipStream_t s, const TraceLaunch& tl, const WavefrontBuffers& wb, uint32_t b, const RenderParams& rp, const CameraView& cam,
-                        const EnvView& env)
+// what the world closest-hit launch of bounce b writes (shade queues, terminal queue, counters row b); for b >= 1 (CLOSEST_WORLD) also
+// the paths it finishes
+static ClosestOut world_out(const WavefrontBuffers& wb, uint32_t b, const RenderParams& rp, const EnvView& env)
 {
     Counters* row = wb.counters + b;
     ClosestOut out{};
@@ -2766,11 +2750,26 @@ void launch_trace_world(hipStream_t s, const TraceLaunch& tl, const WavefrontBuf
     out.q_term = wb.q_term[b & 1u];
     out.n_shade = row->n_shade;
     out.tails = wb.tails + (size_t)b * Q_COUNT * kTailWordsPerQueue;
-    out.wave_times = wb.wave_times ? wb.wave_times + (size_t)b * kWaveTimeSlots : nullptr;
     out.cap_shade = wb.cap_slots_shade;
     out.cap_term = wb.cap_slots_term;
     out.class_mask = wb.class_mask | (1u << Q_TERMINAL);
     out.overflow = &row->overflow;
+    out.finalize_miss = env.w == 0u ? 1u : 0u;
+    if (b != 0u)
+    {
+        out.rec = wb.st.rec;
+        out.radiance = wb.st.radiance;
+        out.enable_nee = rp.enable_nee;
+    }
+    return out;
+}
+
+void launch_trace_world(hipStream_t s, const TraceLaunch& tl, const WavefrontBuffers& wb, uint32_t b, const RenderParams& rp, const CameraView& cam,
+                        const EnvView& env)
+{
+    Counters* row = wb.counters + b;
+    ClosestOut out = world_out(wb, b, rp, env);
+    out.wave_times = wb.wave_times ? wb.wave_times + (size_t)b * kWaveTimeSlots : nullptr;
     if (b == 0u)
     {
         out.eye = f3{cam.eye[0], cam.eye[1], cam.eye[2]};
@@ -2781,40 +2780,16 @@ void launch_trace_world(hipStream_t s, const TraceLaunch& tl, const WavefrontBuf
         out.keep_s_id = rp.keep_s_id; out.keep_s_pos = rp.keep_s_pos;
         out.blk_log = rp.blk_log; out.n_blk = rp.n_blk; out.blk_last = rp.blk_last; out.act_pixels = rp.act_pixels;
         out.div_blk_paths = rp.div_blk_paths; out.div_blk_last = rp.div_blk_last;
-        out.finalize_miss = env.w == 0u ? 1u : 0u;
         launch_closest_impl<CLOSEST_PRIMARY>(s, tl, tl.scene.world_root, wb.rq[0], &row->n_closest, wb.cap_slots, row_heads(wb, b, HEADS_CLOSEST), out);
     }
-    else
-    {
-        out.rec = wb.st.rec;
-        out.radiance = wb.st.radiance;
-        out.enable_nee = rp.enable_nee;
-        out.finalize_miss = env.w == 0u ? 1u : 0u;
-        launch_closest_impl<CLOSEST_WORLD>(s, tl, tl.scene.world_root, wb.rq[b & 1u], &row->n_closest, wb.cap_slots, row_heads(wb, b, HEADS_CLOSEST), out);
-    }
+    else launch_closest_impl<CLOSEST_WORLD>(s, tl, tl.scene.world_root, wb.rq[b & 1u], &row->n_closest, wb.cap_slots, row_heads(wb, b, HEADS_CLOSEST), out);
 }
 // world closest hit of bounce b (b >= 1) + the BSDF-sampled NEE rays of bounce b - 1 in one launch (k_trace_fused)
 void launch_trace_fused(hipStream_t s, const TraceLaunch& tl, const WavefrontBuffers& wb, uint32_t b, const RenderParams& rp, const EnvView& env)
 {
     Counters* row = wb.counters + b;
     Counters* prev = wb.counters + (b - 1u);
-    ClosestOut wout{};
-    wout.hits = wb.hits;
-    wout.q_base = wb.q_shade_base;
-    wout.q_stride = wb.q_stride;
-    wout.q_class_slot = wb.q_class_slot;
-    wout.q_term = wb.q_term[b & 1u];
-    wout.n_shade = row->n_shade;
-    wout.tails = wb.tails + (size_t)b * Q_COUNT * kTailWordsPerQueue;
-    wout.wave_times = nullptr;
-    wout.cap_shade = wb.cap_slots_shade;
-    wout.cap_term = wb.cap_slots_term;
-    wout.class_mask = wb.class_mask | (1u << Q_TERMINAL);
-    wout.overflow = &row->overflow;
-    wout.rec = wb.st.rec;
-    wout.radiance = wb.st.radiance;
-    wout.enable_nee = rp.enable_nee;
-    wout.finalize_miss = env.w == 0u ? 1u : 0u;
+    const ClosestOut wout = world_out(wb, b, rp, env);
     ClosestOut lout{};
     lout.hits = wb.lchain_hit;
     lout.world_root = tl.scene.world_root;
@@ -2823,24 +2798,10 @@ void launch_trace_fused(hipStream_t s, const TraceLaunch& tl, const WavefrontBuf
     fa.wa = wb.rq[b & 1u].a; fa.wb = wb.rq[b & 1u].b; fa.wn = &row->n_closest; fa.wheads = row_heads(wb, b, HEADS_CLOSEST);
     fa.la = wb.rq_lchain[(b - 1u) & 1u].a; fa.lb = wb.rq_lchain[(b - 1u) & 1u].b; fa.ln = &prev->n_lchain; fa.lheads = row_heads(wb, b - 1u, HEADS_LCHAIN);
     fa.world_root = tl.scene.world_root; fa.lights_root = tl.scene.lights_root; fa.cap_in = wb.cap_slots;
-    const size_t lds = trace_lds_bytes(tl);
-    const bool spill = tl.scene.stack_entries > tl.scene.stack_lds;
-    const dim3 block(tl.block_threads);
-    const uint4* blob = (const uint4*)tl.blob;
-    const FusedKArgs ka{tl.scene, blob, fa, wout, lout};
-#define PT_LAUNCH(K) hipLaunchKernelGGL(K, dim3(resident_grid(K, tl, lds)), block, lds, s, ka)
-    if (ident_walk(tl, IDENT_TLAS_WORLD | IDENT_TLAS_LIGHTS))
-    {
-        if (tl.lds_scene && !spill) PT_LAUNCH((k_trace_fused<1, false, true>));
-        else if (tl.lds_scene) PT_LAUNCH((k_trace_fused<1, true, true>));
-        else if (!spill) PT_LAUNCH((k_trace_fused<0, false, true>));
-        else PT_LAUNCH((k_trace_fused<0, true, true>));
-    }
-    else if (tl.lds_scene && !spill) PT_LAUNCH((k_trace_fused<1, false>));
-    else if (tl.lds_scene) PT_LAUNCH((k_trace_fused<1, true>));
-    else if (!spill) PT_LAUNCH((k_trace_fused<0, false>));
-    else PT_LAUNCH((k_trace_fused<0, true>));
-#undef PT_LAUNCH
+    const FusedKArgs ka{tl.scene, (const uint4*)tl.blob, fa, wout, lout};
+    with_trace_variant(tl, ident_walk(tl, IDENT_TLAS_WORLD | IDENT_TLAS_LIGHTS), [&](auto bvh, auto spill, auto ident) {
+        launch_resident(k_trace_fused<bvh, spill, ident>, tl, s, ka);
+    });
 }
 void launch_trace_shadow(hipStream_t s, const TraceLaunch& tl, const WavefrontBuffers& wb, uint32_t b)
 {
@@ -2940,27 +2901,17 @@ void launch_shade(hipStream_t s, uint32_t qclass, const SceneView& sv, const Ren
 }
 
 void launch_accumulate(hipStream_t s, const RenderParams& rp, const CameraView& cam, const WavefrontBuffers& wb, f4* accum, f4* position, uint32_t* id,
-                       uint32_t write_position, uint32_t add_to_accum)
-{
-    const uint32_t blocks = (rp.local_pixels + 255u) / 256u;
-    if (rp.local_pixels < (uint32_t)PT_ACC_QUAD_BELOW) hipLaunchKernelGGL(k_accumulate<true>, dim3((rp.local_pixels * 4u + 255u) / 256u), dim3(256), 0, s, rp, cam, wb.st, accum, position, id, write_position, add_to_accum,
-                                                                  nullptr, nullptr);
-    else hipLaunchKernelGGL(k_accumulate<false>, dim3(blocks), dim3(256), 0, s, rp, cam, wb.st, accum, position, id, write_position, add_to_accum, nullptr, nullptr);
-}
-void launch_accumulate_moments(hipStream_t s, const RenderParams& rp, const CameraView& cam, const WavefrontBuffers& wb, f4* accum, f4* position, uint32_t* id,
-                               uint32_t write_position, uint32_t add_to_accum, float* moments, const uint2* list)
+                       uint32_t write_position, uint32_t add_to_accum, float* moments, const uint2* list)
 {
     const uint32_t n = list ? rp.act_pixels : rp.local_pixels;
     if (n == 0u) return;
     const bool quad = n < (uint32_t)PT_ACC_QUAD_BELOW;
     const dim3 grid(quad ? (n * 4u + 255u) / 256u : (n + 255u) / 256u);
-    if (list)
-    {
-        if (quad) hipLaunchKernelGGL((k_accumulate<true, true, true>), grid, dim3(256), 0, s, rp, cam, wb.st, accum, position, id, write_position, add_to_accum, moments, list);
-        else hipLaunchKernelGGL((k_accumulate<false, true, true>), grid, dim3(256), 0, s, rp, cam, wb.st, accum, position, id, write_position, add_to_accum, moments, list);
-    }
-    else if (quad) hipLaunchKernelGGL((k_accumulate<true, true, false>), grid, dim3(256), 0, s, rp, cam, wb.st, accum, position, id, write_position, add_to_accum, moments, list);
-    else hipLaunchKernelGGL((k_accumulate<false, true, false>), grid, dim3(256), 0, s, rp, cam, wb.st, accum, position, id, write_position, add_to_accum, moments, list);
+    auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, rp, cam, wb.st, accum, position, id, write_position, add_to_accum, moments, list); };
+    // (a list comes with moments: pt_render_adaptive)
+    if (list) quad ? go(k_accumulate<true, true, true>) : go(k_accumulate<false, true, true>);
+    else if (moments) quad ? go(k_accumulate<true, true>) : go(k_accumulate<false, true>);
+    else quad ? go(k_accumulate<true>) : go(k_accumulate<false>);
 }
 uint32_t adaptive_select_blocks(uint32_t n_pixels) { return (n_pixels + kSelectPerBlock - 1u) / kSelectPerBlock; }
 void launch_adaptive_select(hipStream_t s, const f4* accum, const float* moments, uint32_t n_pixels, const AdaptiveCrit& cr, uint32_t* counts, uint2* list,
