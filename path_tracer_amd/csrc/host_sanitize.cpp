@@ -7,6 +7,9 @@
 //   host_sanitize png <w> <h> <file>   encode a test image
 //   host_sanitize soup <n> <seed>      Scene::new over n random triangles (PTMI_BUILD_THREADS forks the SAH sweep: also built with
 //                                      -fsanitize=thread by `make host-tsan`); prints a checksum of the BLAS arena
+//   host_sanitize plan <row>...        pt_batch_plan.h: each row "b:free,held,classes,volumes" (max_paths_for) or
+//                                      "p:n_samples,act_pixels,samples_out,pipelines,batch_spp,lds_scene,max_paths,cap0,cap1,cap2,cap3"
+//                                      (plan_batches); prints a JSON list: max_paths, or [batch, n_batches, n_pipes] ([0, 0, 0]: refused)
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -15,6 +18,7 @@
 #include <string>
 #include <vector>
 
+#include "pt_batch_plan.h"
 #include "pt_png.h"
 #include "pt_scene.h"
 
@@ -115,6 +119,27 @@ int main(int argc, char** argv)
         }
         for (uint32_t v : b.prim_ids) mix(v);
         std::printf("{\"nodes\": %zu, \"depth\": %u, \"arena\": \"%016llx\"}\n", b.nodes.size(), b.depth, (unsigned long long)h);
+        return 0;
+    }
+    if (cmd == "plan")
+    {
+        std::printf("[");
+        for (int i = 2; i < argc; ++i)
+        {
+            unsigned long long v[11] = {};
+            const char* sep = i > 2 ? ", " : "";
+            if (std::sscanf(argv[i], "b:%llu,%llu,%llu,%llu", v, v + 1, v + 2, v + 3) == 4)
+                std::printf("%s%zu", sep, max_paths_for(v[0], v[1], (uint32_t)v[2], v[3] != 0));
+            else if (std::sscanf(argv[i], "p:%llu,%llu,%llu,%llu,%llu,%llu,%llu,%llu,%llu,%llu,%llu", v, v + 1, v + 2, v + 3, v + 4, v + 5, v + 6, v + 7, v + 8, v + 9,
+                                 v + 10) == 11)
+            {
+                const PlanRequest q{(uint32_t)v[0], v[1], v[2] != 0, (uint32_t)v[3], (uint32_t)v[4], v[5] != 0, v[6], {v[7], v[8], v[9], v[10]}};
+                const BatchPlan p = plan_batches(q);
+                std::printf("%s[%u, %u, %u]", sep, p.batch, p.n_batches, p.n_pipes);
+            }
+            else return 2;
+        }
+        std::printf("]\n");
         return 0;
     }
     if (cmd == "png" && argc >= 5)

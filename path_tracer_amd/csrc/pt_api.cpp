@@ -13,8 +13,10 @@
 #include <cstring>
 #include <mutex>
 #include <string>
+#include <utility>
 #include <vector>
 
+#include "pt_batch_plan.h"
 #include "pt_kernels.h"
 #include "pt_png.h"
 #include "pt_scene.h"
@@ -28,7 +30,7 @@ using namespace pt;
 #define PT_JOIN_LATE 0 // same-box A/B: joining the side stream only before the shading pass costs +2 ms per frame (the two traversal kernels fight for wave slots), 0.1 ms less for a 1/8 share
 #endif
 #ifndef PT_INTERLEAVE_FIRST
-#define PT_INTERLEAVE_FIRST 1 // the first batches of the pipelines are enqueued bounce by bounce across the pipelines (render_common)
+#define PT_INTERLEAVE_FIRST 1 // the first batches of the pipelines are enqueued bounce by bounce across the pipelines (render_batches)
 #endif
 #ifndef PT_WAVE_TIMES
 #define PT_WAVE_TIMES 0
@@ -38,15 +40,6 @@ using namespace pt;
 #endif
 #ifndef PT_SIDE_PRIORITY
 #define PT_SIDE_PRIORITY 0
-#endif
-#ifndef PT_SPLIT_MIN_PATHS
-#define PT_SPLIT_MIN_PATHS (24u << 20) // BVHs in global memory: a request that fits is cut in two for two pipelines from this many paths on (see render_common)
-#endif
-#ifndef PT_SPLIT_MIN_PATHS_LDS
-#define PT_SPLIT_MIN_PATHS_LDS (24u << 20)
-#endif
-#ifndef PT_PIPES4_MIN_PATHS
-#define PT_PIPES4_MIN_PATHS (~0ull) // four pipelines by default: never (see render_common); pt_config.pipelines = 4 asks for them
 #endif
 // samples per block of path ids (power of two; 1 = sample-major path ids as in rounds 1-3): RenderParams::blk_log.  Same-box A/B of 1 / 4 / 8 / 16 / 64, ms per
 // frame: Cornell 256 spp 67.6 / 67.4 / 66.7 / 67.3 / 67.6, atrium 64 spp 288.4 / 283.8 / 283.1 / 281.4 / 281.4, three spheres 49.95 / 49.2 / 49.0 / 48.7 / 48.7, mixed
@@ -65,10 +58,30 @@ namespace {
 
 enum TimeCat { T_GEN = 0, T_WORLD, T_ANY, T_LIGHT, T_SHADE, T_ACCUM, T_COUNT };
 
-struct DevBuf
+// Owning handles of HIP resources: move-only, released by the destructor or by reset().  out() is the out-parameter of the call
+// that creates the resource (what the handle held before is released first).
+template <class T, auto Release>
+struct Owned
 {
-    void* p = nullptr;
+    T p{};
+    Owned() = default;
+    Owned(Owned&& o) noexcept : p(std::exchange(o.p, T{})) {}
+    ~Owned() { reset(); }
+    void reset() { if (p) (void)Release(p); p = T{}; }
+    T* out() { reset(); return &p; }
+    operator T() const { return p; }
+};
+using StreamHandle = Owned<hipStream_t, hipStreamDestroy>;
+using EventHandle = Owned<hipEvent_t, hipEventDestroy>;
+template <class T> using Pinned = Owned<T*, hipHostFree>; // hipHostMalloc
+
+// device memory: grows through dev_alloc, never shrinks
+struct DevBuf : Owned<void*, hipFree>
+{
     size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : Owned(std::move(o)), bytes(std::exchange(o.bytes, 0)) {}
+    void reset() { Owned::reset(); bytes = 0; }
 };
 
 } // namespace
@@ -83,23 +96,24 @@ struct pt_ctx
     bool dev_ready = false;
     int device = 0;
     int n_cus = 256;
-    hipStream_t own_stream = nullptr, stream = nullptr; // `stream` is what pipeline 0 launches on (the caller's, after pt_set_stream)
-    hipEvent_t ev_start = nullptr;                      // render start on `stream`: what the other pipelines wait for
+    StreamHandle own_stream;
+    hipStream_t stream = nullptr; // what pipeline 0 launches on: own_stream, or the caller's after pt_set_stream
+    EventHandle ev_start;         // render start on `stream`: what the other pipelines wait for
 
     // One wavefront pipeline: the state of ONE batch in flight and the streams it is launched on.  Batches are independent until they
     // add their samples to the frame, so consecutive batches alternate between pipelines: the tail of one batch's launches (a few
     // waves finishing the longest rays) overlaps the body of the other's instead of leaving the device idle.
     struct Pipe
     {
-        hipStream_t own_stream = nullptr, side_stream = nullptr; // side: the (tiny) BSDF-sampled NEE launch runs beside the shadow-ray launch
-        hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_done = nullptr; // ev_done: this pipeline's last batch has been accumulated
+        StreamHandle own_stream, side_stream; // side: the (tiny) BSDF-sampled NEE launch runs beside the shadow-ray launch
+        EventHandle ev_fork, ev_join, ev_done; // ev_done: this pipeline's last batch has been accumulated
         size_t cap_paths = 0, cap_slots = 0, cap_slots_term = 0;
         uint32_t cap_rows = 0;
         std::vector<DevBuf> pool;
         WavefrontBuffers wb{};
-        Counters* h_counters = nullptr; // pinned
-        uint32_t* h_heads = nullptr;    // pinned mirror of the claim-cursor lines (they carry the exact ray tallies)
-        struct Ev { hipEvent_t a, b; int cat; };
+        Pinned<Counters> h_counters;
+        Pinned<uint32_t> h_heads; // mirror of the claim-cursor lines (they carry the exact ray tallies)
+        struct Ev { EventHandle a, b; int cat; };
         std::vector<Ev> ev_pool;
         size_t ev_used = 0;
         uint32_t slack_cfg = 0;         // pt_config.queue_slack the pool was sized with
@@ -109,7 +123,7 @@ struct pt_ctx
         uint32_t busy_rows = 0;
         uint64_t busy_paths = 0, busy_culled = 0;
     };
-    static constexpr int kMaxPipes = 4;
+    static constexpr int kMaxPipes = (int)kMaxPipelines;
     Pipe pipe[kMaxPipes];
     hipStream_t pipe_stream(int i) const { return i == 0 ? stream : pipe[i].own_stream; }
 
@@ -161,20 +175,42 @@ int fail(pt_ctx* c, int code, const std::string& msg)
         if (e__ != hipSuccess) return fail((c), PT_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); \
     } while (0)
 
-void dev_free(DevBuf& b)
-{
-    if (b.p) (void)hipFree(b.p);
-    b = DevBuf();
-}
 int dev_alloc(pt_ctx* c, DevBuf& b, size_t bytes)
 {
     if (b.bytes >= bytes && b.p) return PT_OK;
-    dev_free(b);
+    b.reset();
     bytes = std::max<size_t>(bytes, 16);
     HIPCHK(c, hipMalloc(&b.p, bytes));
     b.bytes = bytes;
     return PT_OK;
 }
+
+// Device buffers of one call, freed when it returns.  in() uploads an input (src null: allocates only) and the copy has finished when it
+// returns, before any launch that reads it; out() allocates an output; download() synchronises the context's stream, then copies back.
+// After a failure in() and out() return null and `err` holds the code.
+struct Staging
+{
+    pt_ctx* c;
+    int err = PT_OK;
+    std::vector<DevBuf> bufs;
+    explicit Staging(pt_ctx* c_) : c(c_) {}
+    void* in(const void* src, size_t bytes)
+    {
+        DevBuf b;
+        if (err || (err = dev_alloc(c, b, bytes))) return nullptr;
+        const hipError_t e = src ? hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice) : hipSuccess;
+        if (e != hipSuccess) { err = fail(c, PT_ERR_HIP, hipGetErrorString(e)); return nullptr; }
+        bufs.push_back(std::move(b));
+        return bufs.back().p;
+    }
+    void* out(size_t bytes) { return in(nullptr, bytes); }
+    int download(void* dst, const void* src, size_t bytes)
+    {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
+        return PT_OK;
+    }
+};
 
 void compute_rows(pt_ctx* c)
 {
@@ -220,16 +256,16 @@ int ensure_device(pt_ctx* c)
     hipDeviceProp_t prop;
     HIPCHK(c, hipGetDeviceProperties(&prop, c->device));
     c->n_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    HIPCHK(c, hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
-    HIPCHK(c, hipEventCreateWithFlags(&c->ev_start, hipEventDisableTiming));
+    HIPCHK(c, hipStreamCreateWithFlags(c->own_stream.out(), hipStreamNonBlocking));
+    HIPCHK(c, hipEventCreateWithFlags(c->ev_start.out(), hipEventDisableTiming));
     for (int i = 0; i < pt_ctx::kMaxPipes; ++i)
     {
         pt_ctx::Pipe& pp = c->pipe[i];
-        if (i > 0) HIPCHK(c, hipStreamCreateWithFlags(&pp.own_stream, hipStreamNonBlocking));
-        HIPCHK(c, hipStreamCreateWithFlags(&pp.side_stream, hipStreamNonBlocking));
-        HIPCHK(c, hipEventCreateWithFlags(&pp.ev_fork, hipEventDisableTiming));
-        HIPCHK(c, hipEventCreateWithFlags(&pp.ev_join, hipEventDisableTiming));
-        HIPCHK(c, hipEventCreateWithFlags(&pp.ev_done, hipEventDisableTiming));
+        if (i > 0) HIPCHK(c, hipStreamCreateWithFlags(pp.own_stream.out(), hipStreamNonBlocking));
+        HIPCHK(c, hipStreamCreateWithFlags(pp.side_stream.out(), hipStreamNonBlocking));
+        HIPCHK(c, hipEventCreateWithFlags(pp.ev_fork.out(), hipEventDisableTiming));
+        HIPCHK(c, hipEventCreateWithFlags(pp.ev_join.out(), hipEventDisableTiming));
+        HIPCHK(c, hipEventCreateWithFlags(pp.ev_done.out(), hipEventDisableTiming));
     }
     if (!c->stream) c->stream = c->own_stream;
     c->dev_ready = true;
@@ -447,10 +483,9 @@ int ensure_frame(pt_ctx* c)
 
 void free_pipe_pool(pt_ctx::Pipe& pp)
 {
-    for (DevBuf& b : pp.pool) dev_free(b);
     pp.pool.clear();
-    if (pp.h_counters) { (void)hipHostFree(pp.h_counters); pp.h_counters = nullptr; }
-    if (pp.h_heads) { (void)hipHostFree(pp.h_heads); pp.h_heads = nullptr; }
+    pp.h_counters.reset();
+    pp.h_heads.reset();
     pp.cap_paths = 0;
     pp.cap_rows = 0;
     pp.wb = WavefrontBuffers{};
@@ -487,9 +522,9 @@ int ensure_wavefront(pt_ctx* c, int pipe, size_t n_paths, uint32_t rows)
         DevBuf b;
         int r = dev_alloc(c, b, bytes);
         if (r) return r;
-        pp.pool.push_back(b);
         *out = b.p;
         total += b.bytes;
+        pp.pool.push_back(std::move(b));
         return PT_OK;
     };
     int r;
@@ -541,8 +576,8 @@ int ensure_wavefront(pt_ctx* c, int pipe, size_t n_paths, uint32_t rows)
     w.cap_slots = (uint32_t)n_slots;
     w.cap_slots_shade = (uint32_t)n_slots_shade;
     w.cap_slots_term = (uint32_t)n_slots_term;
-    HIPCHK(c, hipHostMalloc((void**)&pp.h_counters, (size_t)rows * sizeof(Counters), hipHostMallocDefault));
-    HIPCHK(c, hipHostMalloc((void**)&pp.h_heads, (size_t)rows * HEADS_PER_ROW * kHeadWordsPerQueue * 4, hipHostMallocDefault));
+    HIPCHK(c, hipHostMalloc((void**)pp.h_counters.out(), (size_t)rows * sizeof(Counters), hipHostMallocDefault));
+    HIPCHK(c, hipHostMalloc((void**)pp.h_heads.out(), (size_t)rows * HEADS_PER_ROW * kHeadWordsPerQueue * 4, hipHostMallocDefault));
     pp.cap_paths = n_paths;
     pp.cap_rows = rows;
     pp.state_bytes = total;
@@ -566,9 +601,9 @@ struct Timer
         if (pp.ev_used == pp.ev_pool.size())
         {
             pt_ctx::Pipe::Ev e;
-            (void)hipEventCreate(&e.a);
-            (void)hipEventCreate(&e.b);
-            pp.ev_pool.push_back(e);
+            (void)hipEventCreate(e.a.out());
+            (void)hipEventCreate(e.b.out());
+            pp.ev_pool.push_back(std::move(e));
         }
         slot = pp.ev_used++;
         pp.ev_pool[slot].cat = cat;
@@ -598,6 +633,27 @@ void harvest_events(pt_ctx* c, pt_ctx::Pipe& pp)
     c->stats.ms_accumulate += ms[T_ACCUM];
 }
 
+// The exact ray tallies of one bookkeeping row, summed over its cursor lines: they live beside the claim cursors, one per cursor line
+// (64 addresses per queue instead of one: a launch of a few thousand waves that each add to ONE word spends ~50 us on that alone).
+struct RowTally { uint64_t closest = 0, shadow = 0, lchain0 = 0, lchain1 = 0, lchain2 = 0; };
+RowTally row_tally(const uint32_t* h_heads, uint32_t row)
+{
+    RowTally t;
+    const uint32_t* hrow = h_heads + (size_t)row * HEADS_PER_ROW * kHeadWordsPerQueue;
+    for (uint32_t g = 0; g < kQueueHeads; ++g)
+    {
+        const uint32_t* cl = hrow + HEADS_CLOSEST * kHeadWordsPerQueue + g * kHeadStrideWords;
+        const uint32_t* sh = hrow + HEADS_SHADOW * kHeadWordsPerQueue + g * kHeadStrideWords;
+        const uint32_t* lc = hrow + HEADS_LCHAIN * kHeadWordsPerQueue + g * kHeadStrideWords;
+        t.closest += cl[HEAD_TALLY0];
+        t.shadow += sh[HEAD_TALLY0];
+        t.lchain0 += lc[HEAD_TALLY0];
+        t.lchain1 += lc[HEAD_TALLY1];
+        t.lchain2 += lc[HEAD_TALLY2];
+    }
+    return t;
+}
+
 // what a launched batch leaves behind: overflow flags and exact ray tallies.  Blocks until the pipeline's stream is idle.
 int harvest_batch(pt_ctx* c, int pipe)
 {
@@ -623,21 +679,13 @@ int harvest_batch(pt_ctx* c, int pipe)
             return fail(c, PT_ERR_LIMIT, "a path was inside more than 8 volumes at once (the volume stack holds 8 nested or overlapping "
                                          "volume-bearing models); the batch was abandoned");
         }
-    // exact tallies live beside the claim cursors, one per cursor line (64 addresses per queue instead of one: a launch of a few
-    // thousand waves that each add to ONE word spends ~50 us on that alone)
     for (uint32_t r = 0; r < rows; ++r)
     {
-        const uint32_t* hrow = pp.h_heads + (size_t)r * HEADS_PER_ROW * kHeadWordsPerQueue;
-        for (uint32_t g = 0; g < kQueueHeads; ++g)
-        {
-            const uint32_t* cl = hrow + HEADS_CLOSEST * kHeadWordsPerQueue + g * kHeadStrideWords;
-            const uint32_t* sh = hrow + HEADS_SHADOW * kHeadWordsPerQueue + g * kHeadStrideWords;
-            const uint32_t* lc = hrow + HEADS_LCHAIN * kHeadWordsPerQueue + g * kHeadStrideWords;
-            c->stats.rays_closest += cl[HEAD_TALLY0];
-            c->stats.rays_any += (uint64_t)sh[HEAD_TALLY0] + lc[HEAD_TALLY1];
-            c->stats.rays_light_closest_traced += lc[HEAD_TALLY0];
-            c->stats.rays_light_closest += (uint64_t)lc[HEAD_TALLY0] + lc[HEAD_TALLY2]; // casts of integrator.rs:100, whoever answered them
-        }
+        const RowTally t = row_tally(pp.h_heads, r);
+        c->stats.rays_closest += t.closest;
+        c->stats.rays_any += t.shadow + t.lchain1;
+        c->stats.rays_light_closest_traced += t.lchain0;
+        c->stats.rays_light_closest += t.lchain0 + t.lchain2; // casts of integrator.rs:100, whoever answered them
     }
     c->stats.paths += pp.busy_paths;
     // camera rays of pixels outside the active rectangle: cast (integrator.rs:179) and answered by the projection of the world's root box
@@ -648,42 +696,45 @@ int harvest_batch(pt_ctx* c, int pipe)
     return PT_OK;
 }
 
-// one wavefront batch: samples [first, first+count) of every local pixel, launched on pipeline `pipe` (nothing here waits for the
-// device except the emptiness probes of very long bounce budgets).  `after`: event the batch's accumulation must wait for (the
-// previous batch's accumulation: samples are added to the frame in sample order), or null.
-// One batch's launches, cut at the bounces so that the batches of several pipelines can be enqueued side by side (render_common):
-// batch_begin, batch_bounce(0..max_bounces), batch_end.  Everything is asynchronous on the pipeline's streams except the
-// every-fourth-bounce look at the counters that long bounce budgets use to stop early.
+// One wavefront batch: samples [first_sample, first_sample + count) of every active pixel, launched on pipeline `pipe` (nothing here
+// waits for the device except the emptiness probes of very long bounce budgets).  Its launches are cut at the bounces so that the
+// batches of several pipelines can be enqueued side by side (run_group): batch_begin, batch_bounce(0..max_bounces), batch_end.
+// Everything is asynchronous on the pipeline's streams except the every-fourth-bounce look at the counters that long bounce budgets
+// use to stop early.
 enum : uint32_t { kEagerRows = 18u }; // bookkeeping rows cleared when a batch begins (bounces 0..16); deeper ones are cleared as the bounces are enqueued
+struct BatchSpec
+{
+    int pipe = 0;
+    uint32_t first_sample = 0, count = 0;
+    ActiveRect ar{};               // the render's active rectangle (render_rect)
+    bool write_position = false;   // the last batch of the request: its first-hit positions are kept
+    f4* samples_out = nullptr;     // the batch's samples go here instead of into the accumulation
+    bool aux_with_samples = false; // pt_frame: position / id history are updated beside samples_out
+};
 struct BatchRun
 {
     pt_ctx* c = nullptr;
-    int pipe = 0;
+    BatchSpec spec;
     RenderParams rp{};
     CameraView cam{};
     EnvView env{};
     TraceLaunch tl{}, tl_side{};
     hipStream_t s = nullptr;
-    uint32_t rows = 0, shade_blocks = 1, last_row = 0, count = 0, cleared_rows = 0;
-    bool nee = false, side_busy = false, stopped = false, write_position = false, aux_with_samples = false, fused = false;
+    uint32_t rows = 0, shade_blocks = 1, last_row = 0, cleared_rows = 0;
+    bool nee = false, side_busy = false, stopped = false, fused = false;
     bool no_shadow_queue = false; // every shadow ray of the scene is answered inside the shading pass (shade_traces_shadow): launch_trace_shadow has nothing to do
     int nee_err = PT_OK;
-    f4* samples_out = nullptr;
-    hipEvent_t after = nullptr;
 };
 
-int batch_begin(BatchRun& br, pt_ctx* c, int pipe, uint32_t first_sample, uint32_t count, bool write_position, f4* samples_out, bool aux_with_samples, hipEvent_t after)
+int batch_begin(BatchRun& br, pt_ctx* c, const BatchSpec& spec)
 {
+    const int pipe = spec.pipe;
+    const uint32_t count = spec.count;
     pt_ctx::Pipe& pp = c->pipe[pipe];
     const pt_config& g = c->cfg;
     br = BatchRun{};
     br.c = c;
-    br.pipe = pipe;
-    br.count = count;
-    br.write_position = write_position;
-    br.samples_out = samples_out;
-    br.aux_with_samples = aux_with_samples;
-    br.after = after;
+    br.spec = spec;
     RenderParams& rp = br.rp;
     rp.width = g.width;
     rp.height = g.height;
@@ -692,10 +743,9 @@ int batch_begin(BatchRun& br, pt_ctx* c, int pipe, uint32_t first_sample, uint32
     rp.rank = g.rank;
     rp.world_size = g.world_size;
     rp.strip_rows = g.strip_rows;
-    rp.first_sample = first_sample;
+    rp.first_sample = spec.first_sample;
     rp.batch_samples = count;
-    // an adaptive list takes the rectangle's place: path ids index its entries (one row of cur_list_n; the primary cull does not apply)
-    const ActiveRect ar = c->cur_list ? ActiveRect{0u, c->cur_list_n, 0u, 1u} : active_rect(c);
+    const ActiveRect& ar = spec.ar;
     rp.act_x0 = ar.x0; rp.act_w = ar.w; rp.act_ly0 = ar.ly0; rp.act_rows = ar.rows;
     rp.act_pixels = ar.w * ar.rows;
     rp.n_paths = rp.act_pixels * count;
@@ -762,7 +812,7 @@ int batch_begin(BatchRun& br, pt_ctx* c, int pipe, uint32_t first_sample, uint32
 void batch_nee_launches(BatchRun& br, uint32_t row)
 {
     pt_ctx* c = br.c;
-    pt_ctx::Pipe& pp = c->pipe[br.pipe];
+    pt_ctx::Pipe& pp = c->pipe[br.spec.pipe];
     const WavefrontBuffers& wb = pp.wb;
     const bool timing_all = (c->cfg.flags & PT_FLAG_TIMING_ALL) != 0; // per-launch events want one stream
     // a small batch (an interactive 1-spp frame) gains nothing from the second stream and pays ~20 us per bounce for the two
@@ -783,7 +833,7 @@ void batch_nee_launches(BatchRun& br, uint32_t row)
 void batch_join_side(BatchRun& br)
 {
     if (!br.side_busy) return;
-    if (hipStreamWaitEvent(br.s, br.c->pipe[br.pipe].ev_join, 0) != hipSuccess) br.nee_err = PT_ERR_HIP;
+    if (hipStreamWaitEvent(br.s, br.c->pipe[br.spec.pipe].ev_join, 0) != hipSuccess) br.nee_err = PT_ERR_HIP;
     br.side_busy = false;
 }
 
@@ -791,7 +841,7 @@ int batch_bounce(BatchRun& br, uint32_t b)
 {
     if (br.stopped) return PT_OK;
     pt_ctx* c = br.c;
-    pt_ctx::Pipe& pp = c->pipe[br.pipe];
+    pt_ctx::Pipe& pp = c->pipe[br.spec.pipe];
     const pt_config& g = c->cfg;
     const WavefrontBuffers& wb = pp.wb;
     hipStream_t s = br.s;
@@ -832,10 +882,12 @@ int batch_bounce(BatchRun& br, uint32_t b)
     return PT_OK;
 }
 
-int batch_end(BatchRun& br)
+// `after`: event the batch's accumulation must wait for (the previous batch's accumulation: samples are added to the frame in sample
+// order), or null
+int batch_end(BatchRun& br, hipEvent_t after)
 {
     pt_ctx* c = br.c;
-    pt_ctx::Pipe& pp = c->pipe[br.pipe];
+    pt_ctx::Pipe& pp = c->pipe[br.spec.pipe];
     const pt_config& g = c->cfg;
     const WavefrontBuffers& wb = pp.wb;
     hipStream_t s = br.s;
@@ -849,18 +901,18 @@ int batch_end(BatchRun& br)
         { Timer t(c, pp, s, T_SHADE); launch_shade(s, Q_TERMINAL, c->sv, rp, wb, br.last_row, br.shade_blocks, br.cam, br.env); }
     }
     if (br.nee_err) return fail(c, PT_ERR_HIP, "stream fork/join failed");
-    if (br.after && hipStreamWaitEvent(s, br.after, 0) != hipSuccess) return fail(c, PT_ERR_HIP, "hipStreamWaitEvent");
-    if (br.samples_out)
+    if (after && hipStreamWaitEvent(s, after, 0) != hipSuccess) return fail(c, PT_ERR_HIP, "hipStreamWaitEvent");
+    if (br.spec.samples_out)
     {
-        launch_store_samples(s, rp, wb, br.samples_out);
+        launch_store_samples(s, rp, wb, br.spec.samples_out);
         // pt_frame: the frame's own colour goes to the input texture, position / id history are still updated
-        if (br.aux_with_samples) launch_accumulate(s, rp, br.cam, wb, (f4*)c->d_accum.p, (f4*)c->d_position.p, (uint32_t*)c->d_id.p, 1u, 0u);
+        if (br.spec.aux_with_samples) launch_accumulate(s, rp, br.cam, wb, (f4*)c->d_accum.p, (f4*)c->d_position.p, (uint32_t*)c->d_id.p, 1u, 0u);
     }
     else
     {
         Timer t(c, pp, s, T_ACCUM);
         const bool adaptive = (c->cfg.flags & PT_FLAG_ADAPTIVE) != 0;
-        launch_accumulate(s, rp, br.cam, wb, (f4*)c->d_accum.p, (f4*)c->d_position.p, (uint32_t*)c->d_id.p, br.write_position ? 1u : 0u, 1u,
+        launch_accumulate(s, rp, br.cam, wb, (f4*)c->d_accum.p, (f4*)c->d_position.p, (uint32_t*)c->d_id.p, br.spec.write_position ? 1u : 0u, 1u,
                           adaptive ? (float*)c->d_moments.p : nullptr, adaptive ? c->cur_list : nullptr);
     }
     HIPCHK(c, hipEventRecord(pp.ev_done, s));
@@ -870,19 +922,25 @@ int batch_end(BatchRun& br)
     HIPCHK(c, hipMemcpyAsync(pp.h_heads, wb.heads, (size_t)used_rows * HEADS_PER_ROW * kHeadWordsPerQueue * 4, hipMemcpyDeviceToHost, s));
     pp.busy = true;
     pp.busy_rows = used_rows;
-    pp.busy_paths = (uint64_t)(c->cur_list ? rp.act_pixels : rp.local_pixels) * br.count;
-    pp.busy_culled = c->cur_list ? 0u : (uint64_t)(rp.local_pixels - rp.act_pixels) * br.count;
+    pp.busy_paths = (uint64_t)(c->cur_list ? rp.act_pixels : rp.local_pixels) * br.spec.count;
+    pp.busy_culled = c->cur_list ? 0u : (uint64_t)(rp.local_pixels - rp.act_pixels) * br.spec.count;
     return PT_OK;
 }
 
-int launch_batch(pt_ctx* c, int pipe, uint32_t first_sample, uint32_t count, bool write_position, f4* samples_out, bool aux_with_samples, hipEvent_t after)
+// Batches begun together, one per pipeline: their bounces are enqueued side by side, then their accumulations in sample order (each
+// waits for `prev_done`, the accumulation before it, and becomes the next one's `prev_done`).
+int run_group(pt_ctx* c, BatchRun* run, uint32_t n, hipEvent_t& prev_done)
 {
-    BatchRun br;
     int r;
-    if ((r = batch_begin(br, c, pipe, first_sample, count, write_position, samples_out, aux_with_samples, after))) return r;
     for (uint32_t b = 0; b <= c->cfg.max_bounces; ++b)
-        if ((r = batch_bounce(br, b))) return r;
-    return batch_end(br);
+        for (uint32_t i = 0; i < n; ++i)
+            if ((r = batch_bounce(run[i], b))) return r;
+    for (uint32_t i = 0; i < n; ++i)
+    {
+        if ((r = batch_end(run[i], prev_done))) return r;
+        prev_done = c->pipe[run[i].spec.pipe].ev_done;
+    }
+    return PT_OK;
 }
 
 int ensure_environment(pt_ctx* c)
@@ -895,15 +953,6 @@ int ensure_environment(pt_ctx* c)
     return PT_OK;
 }
 
-// one batch on pipeline 0, start to finish
-int run_batch(pt_ctx* c, uint32_t first_sample, uint32_t count, bool write_position, f4* samples_out, bool aux_with_samples = false)
-{
-    int r;
-    if ((r = ensure_environment(c))) return r;
-    if ((r = launch_batch(c, 0, first_sample, count, write_position, samples_out, aux_with_samples, nullptr))) return r;
-    return harvest_batch(c, 0);
-}
-
 int precheck(pt_ctx* c)
 {
     if (!c->scene.built) return fail(c, PT_ERR_STATE, "pt_build has not been called");
@@ -912,110 +961,90 @@ int precheck(pt_ctx* c)
     return PT_OK;
 }
 
-int render_common(pt_ctx* c, uint32_t first_sample, uint32_t n_samples, float* samples_out)
+// the preambles of the entry points: the device and the frame buffers; the scene too for those that trace
+int device_frame(pt_ctx* c)
+{
+    int r = ensure_device(c);
+    return r ? r : ensure_frame(c);
+}
+int scene_frame(pt_ctx* c)
+{
+    int r;
+    if ((r = precheck(c)) || (r = upload_scene(c))) return r;
+    return ensure_frame(c);
+}
+
+// the pixels whose camera rays a render generates: an adaptive list takes the active rectangle's place (path ids index its entries,
+// one row of cur_list_n; the primary cull does not apply)
+ActiveRect render_rect(pt_ctx* c) { return c->cur_list ? ActiveRect{0u, c->cur_list_n, 0u, 1u} : active_rect(c); }
+
+// zero sums, id history and moments on the context's stream (zero moments describe a zero accumulation)
+hipError_t clear_accumulation(pt_ctx* c)
+{
+    hipError_t e = hipSuccess;
+    for (DevBuf* b : {&c->d_accum, &c->d_id, &c->d_moments})
+        if (b->p && e == hipSuccess) e = hipMemsetAsync(b->p, 0, b->bytes, c->stream);
+    c->moments_valid = true;
+    return e;
+}
+
+// the frame's state as it lies on the device, to the host (any pointer may be null)
+int download_frame(pt_ctx* c, float* data, float* position, uint32_t* id)
+{
+    const size_t px = c->local_pixels;
+    if (data && px) HIPCHK(c, hipMemcpyAsync(data, c->d_accum.p, px * 16, hipMemcpyDeviceToHost, c->stream));
+    if (position && px) HIPCHK(c, hipMemcpyAsync(position, c->d_position.p, px * 16, hipMemcpyDeviceToHost, c->stream));
+    if (id && px) HIPCHK(c, hipMemcpyAsync(id, c->d_id.p, px * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PT_OK;
+}
+
+int render_batches(pt_ctx* c, uint32_t first_sample, uint32_t n_samples, float* samples_out)
 {
     int r;
     if ((r = precheck(c))) return r;
     if (n_samples == 0 || c->local_pixels == 0) return PT_OK;
-    if ((r = upload_scene(c))) return r;
-    if ((r = ensure_frame(c))) return r;
-    if ((r = ensure_environment(c))) return r;
-    // Batches: by default the whole request stays resident when HBM allows; otherwise (or with pt_config.batch_spp) it is cut into
-    // equal batches that alternate between `pipelines` wavefront pipelines on their own HIP streams, so that one batch's launch
-    // tails overlap the other's launches.  ~PT_BYTES_PER_PATH of wavefront state per path; path ids are 29-bit.
-    uint32_t want_pipes = samples_out ? 1u : std::min<uint32_t>(c->cfg.pipelines ? c->cfg.pipelines : 2u, (uint32_t)pt_ctx::kMaxPipes);
-    size_t max_paths = (size_t)96 << 20;
+    if ((r = upload_scene(c)) || (r = ensure_frame(c)) || (r = ensure_environment(c))) return r;
+    PlanRequest q;
+    q.n_samples = n_samples;
+    q.samples_out = samples_out != nullptr;
+    q.pipelines = c->cfg.pipelines;
+    q.batch_spp = c->cfg.batch_spp;
+    q.lds_scene = c->lds_scene;
+    q.max_paths = (size_t)96 << 20;
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
     {
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
-        {
-            size_t held = 0;
-            for (const pt_ctx::Pipe& pp : c->pipe)
-                for (const DevBuf& b : pp.pool) held += b.bytes;
-            // bytes of wavefront state per path (ensure_wavefront): 323 in records, ray queues and terminal queues + 54 per surface class present
-            // in the scene (its 48-byte shade queue with an eighth of slack) + 8 with volumes.  (Rounds 1-3 assumed 410 whatever the scene:
-            // right for one class, but the four-class atrium then asked for 268 GiB of a 268.2 GiB device.)
-            uint32_t n_classes = 0;
-            for (uint32_t q = 1; q < Q_COUNT; ++q) n_classes += c->class_present[q] ? 1u : 0u;
-            const double per_path = 330.0 + 56.0 * std::max(n_classes, 1u) + (c->sv.has_volumes ? 8.0 : 0.0) + 24.0;
-            max_paths = (size_t)((double)(free_b + held) * 0.85 / per_path);
-        }
-        max_paths = std::min<size_t>(std::max<size_t>(max_paths, 1u << 20), (1ull << 29) - 1);
+        size_t held = 0;
+        for (const pt_ctx::Pipe& pp : c->pipe)
+            for (const DevBuf& b : pp.pool) held += b.bytes;
+        uint32_t n_classes = 0;
+        for (uint32_t k = 1; k < Q_COUNT; ++k) n_classes += c->class_present[k] ? 1u : 0u;
+        q.max_paths = max_paths_for(free_b, held, n_classes, c->sv.has_volumes != 0);
     }
-    const ActiveRect ar = c->cur_list ? ActiveRect{0u, c->cur_list_n, 0u, 1u} : active_rect(c);
-    const size_t act_pixels = std::max<size_t>((size_t)ar.w * ar.rows, 1);
-    uint32_t batch = c->cfg.batch_spp ? c->cfg.batch_spp : (uint32_t)std::max<size_t>(1, max_paths / act_pixels);
-    batch = std::min(batch, n_samples);
-    uint32_t n_batches = (n_samples + batch - 1) / batch;
-    // (A request that fits at once runs as ONE batch on one pipeline.  Cutting a small one — a rank's share of a sharded frame — in two
-    // for two pipelines used to hide its launch tails (-8 %); since the tails were shortened at the source (striped tails, tapered
-    // chunks) it costs 5 % instead: twice the launches, and two persistent kernels fighting for the same wave slots.)
-    // ... with one exception: BVHs in global memory.  Their rays are long, the launches end in long tails, and smaller batches on several
-    // pipelines overlap them (same box, 82 k-triangle mesh at 1080p unless noted):
-    //   32 spp   one batch 43.9 ms   2 x 16 on two pipelines 40.8   4 x 8 on four 44.9
-    //   128 spp                      2 x 64: 149.1                  4 x 32: 149.3
-    //   512 spp  one batch 629.5     2 x 256: 580 (4 x 128 on TWO pipelines: 583-588)   3 x 171 on three: 572   4 x 128 on four: 561
-    //   328 k mesh, 1024 spp         2 x 512: 1903                  3 x 342: 1889       4 x 256: 1846
-    //   8 spp (4 M paths) 14.21 -> 14.26: nothing; three spheres, 8 spp (7.8 M paths): 10.46 -> 9.95 (four pipelines: 11.3)
-    // so (rounds 2-3, FOUR waves per SIMD): two pipelines from 6 M paths on.  Round 4, FIVE waves per SIMD — the kernels hide more of their own latency, a second
-    // persistent grid has less to fill — same box, one pipeline against the split: 82 k mesh 64 spp 67.2 -> 64.9 ms, 512 spp 497 -> 475; 328 k mesh 64 spp 115.1 -> 113.5,
-    // 1024 spp (bench.py) 1663 -> 1637; atrium 256 spp 1127-1141 -> 1112-1114, but 64 spp 280.7 -> 288.2 and 8 spp 38.7 -> 39.5; spheres +-0: the split went off ...
-    // ... and came back once the surface shading kernels ran at five waves too (one pipeline's shading beside the other's traversal), same box, one batch against
-    // two halves: atrium 16 / 64 spp 74.1 -> 71.8 / 281.6 -> 272.7 ms, 82 k mesh 16 / 64 spp 20.4 -> 20.3 / 64.7 -> 62.7, 328 k mesh 64 spp 113.5 -> 108.6, three spheres
-    // 16 / 64 spp 15.1 -> 15.2 / 49.4 -> 47.7: from PT_SPLIT_MIN_PATHS = 24 M paths on, as for LDS scenes.  (Requests that do not fit always alternated between two
-    // pipelines.)  Four (from PT_PIPES4_MIN_PATHS on) did not hold up under bench.py: 82 k mesh at 512 spp
-    // 573 -> 588 ms, 328 k mesh at 1024 spp 1979 -> 1959 ms, three spheres at 4096^2 x 1024 spp 12.15 -> 12.43 s; off.
-    const uint64_t total_paths = (uint64_t)n_samples * act_pixels;
-    if (!samples_out && !c->cfg.pipelines && !c->lds_scene && total_paths >= (uint64_t)PT_PIPES4_MIN_PATHS) want_pipes = (uint32_t)pt_ctx::kMaxPipes;
-    // (Round 4: with five waves per SIMD in the traversal AND the surface shading kernels one pipeline's shading pass runs beside the other's traversal, and the split pays
-    // from a quarter of the headline frame on: whole frame 62.4 -> 59.0 ms, rank 0's half 32.4 -> 30.5, its quarter 17.1 -> 16.4, its eighth (16.6 M paths) 9.44 -> 9.38:
-    // from PT_SPLIT_MIN_PATHS_LDS = 24 M paths on.)  Round 3:
-    // LDS-resident BVHs gain only on very large requests (with round 3's launch structure): the 133 M-path headline frame 68.3 -> 67.2 ms
-    // (bench.py, three interleaved repeats), mixed materials at 66 M paths 42.9 -> 42.3 ms, but rank 0's half of the sharded frame (66 M
-    // paths) 35.0 -> 35.7 ms and its quarter +-0: from PT_SPLIT_MIN_PATHS_LDS paths on.
-    if (!c->cfg.batch_spp && n_batches < want_pipes && want_pipes >= 2 && total_paths >= (c->lds_scene ? (uint64_t)PT_SPLIT_MIN_PATHS_LDS : (uint64_t)PT_SPLIT_MIN_PATHS))
-    {
-        n_batches = std::min<uint32_t>(want_pipes, n_samples);
-        batch = (n_samples + n_batches - 1) / n_batches;
-    }
-    uint32_t n_pipes = std::min(want_pipes, n_batches);
-    if (!c->cfg.batch_spp && n_batches > 1 && (uint64_t)batch * act_pixels * n_pipes > max_paths)
-    {
-        // the request does not fit at once: the pipelines share the memory
-        batch = (uint32_t)std::max<size_t>(1, max_paths / n_pipes / act_pixels);
-        n_batches = (n_samples + batch - 1) / batch;
-    }
-    if (!c->cfg.batch_spp && n_batches > 1)
-    {
-        // pools that an earlier request left (a 64-spp warm-up before a 4096-spp render, say) are kept when they are nearly large enough:
-        // rounding n_samples / n_batches up differently must not cost a reallocation of hundreds of GB (seconds) inside a render
-        size_t cap_min = ~(size_t)0;
-        for (uint32_t i = 0; i < n_pipes; ++i) cap_min = std::min(cap_min, c->pipe[i].cap_paths);
-        const size_t want = (size_t)batch * act_pixels;
-        if (cap_min >= act_pixels && cap_min < want && cap_min * 4 >= want * 3)
-        {
-            batch = (uint32_t)(cap_min / act_pixels);
-            n_batches = (n_samples + batch - 1) / batch;
-        }
-    }
-    batch = (n_samples + n_batches - 1) / n_batches;
-    if ((uint64_t)batch * act_pixels >= (1ull << 29)) return fail(c, PT_ERR_ARG, "batch too large (path ids are 29-bit)");
+    const ActiveRect ar = render_rect(c);
+    q.act_pixels = std::max<size_t>((size_t)ar.w * ar.rows, 1);
+    for (int i = 0; i < pt_ctx::kMaxPipes; ++i) q.cap_paths[i] = c->pipe[i].cap_paths;
+    const BatchPlan plan = plan_batches(q);
+    if (!plan.batch) return fail(c, PT_ERR_ARG, "batch too large (path ids are 29-bit)");
+    const uint32_t batch = plan.batch, n_pipes = plan.n_pipes;
     // pipelines this call does not use give their memory back
     for (int i = (int)n_pipes; i < pt_ctx::kMaxPipes; ++i)
         if (!c->pipe[i].busy && c->pipe[i].cap_paths) free_pipe_pool(c->pipe[i]);
     if (std::getenv("PTMI_DEBUG_BATCH"))
-        std::fprintf(stderr, "[ptmi] render %u spp: max_paths %zu act_pixels %zu batch %u x %u on %u pipelines; pools before: %zu %zu paths\n", n_samples, max_paths, act_pixels, batch,
-                     n_batches, n_pipes, c->pipe[0].cap_paths, c->pipe[1].cap_paths);
+        std::fprintf(stderr, "[ptmi] render %u spp: max_paths %zu act_pixels %zu batch %u x %u on %u pipelines; pools before: %zu %zu paths\n", n_samples, q.max_paths, q.act_pixels, batch,
+                     plan.n_batches, n_pipes, c->pipe[0].cap_paths, c->pipe[1].cap_paths);
     // ... and a pipeline that kept a larger pool from an earlier request (a whole frame resident on pipeline 0, say) gives it back when
     // the pipelines have to share the budget: its old pool plus the others' new ones could exceed what max_paths was computed from
-    const size_t need_paths = (size_t)batch * act_pixels;
+    const size_t need_paths = (size_t)batch * q.act_pixels;
     if (n_pipes > 1)
         for (uint32_t i = 0; i < n_pipes; ++i)
             if (!c->pipe[i].busy && c->pipe[i].cap_paths > need_paths + need_paths / 4) free_pipe_pool(c->pipe[i]);
     for (uint32_t i = 0; i < n_pipes; ++i)
         if ((r = ensure_wavefront(c, (int)i, need_paths, c->cfg.max_bounces + 2))) return r;
-    DevBuf d_samples;
-    if (samples_out && (r = dev_alloc(c, d_samples, (size_t)batch * c->local_pixels * 16))) return r;
+    Staging st(c);
+    f4* d_samples = samples_out ? (f4*)st.out((size_t)batch * c->local_pixels * 16) : nullptr;
+    if (st.err) return st.err;
     const auto t0 = std::chrono::steady_clock::now();
     // the other pipelines start after whatever the caller queued on pipeline 0's stream (accumulation resets, uploads)
     if (n_pipes > 1)
@@ -1025,43 +1054,27 @@ int render_common(pt_ctx* c, uint32_t first_sample, uint32_t n_samples, float* s
     }
     hipEvent_t prev_done = nullptr;
     int err = PT_OK;
-    // The first n_pipes batches find every pipeline idle; their launches are enqueued bounce by bounce ACROSS the pipelines:
-    // enqueueing a whole batch takes the host about a millisecond, which the second pipeline of a short request (one rank's share
-    // of a sharded frame is two batches) would otherwise spend idle, and the first would run its tail alone at the end.  Later
-    // batches go out whole, each as soon as its pipeline's previous batch is done, which keeps the pipelines out of step.
-    uint32_t done = 0, k = 0;
-    if (n_pipes > 1 && PT_INTERLEAVE_FIRST)
+    // Batch k runs on pipeline k % n_pipes.  The first n_pipes batches find every pipeline idle; their launches are enqueued bounce by
+    // bounce ACROSS the pipelines (one group): enqueueing a whole batch takes the host about a millisecond, which the second pipeline of
+    // a short request (one rank's share of a sharded frame is two batches) would otherwise spend idle, and the first would run its tail
+    // alone at the end.  Later batches go out whole, each as soon as its pipeline's previous batch is done (a group of one), which keeps
+    // the pipelines out of step.
+    for (uint32_t done = 0, k = 0; done < n_samples && !err;)
     {
+        const uint32_t group = (k == 0 && PT_INTERLEAVE_FIRST) ? n_pipes : 1u;
         BatchRun run[pt_ctx::kMaxPipes];
-        for (uint32_t i = 0; i < n_pipes && done < n_samples && !err; ++i, ++k)
+        uint32_t n = 0;
+        for (; n < group && done < n_samples && !err; ++n, ++k)
         {
+            const int pi = (int)(k % n_pipes);
             const uint32_t cnt = std::min(batch, n_samples - done);
-            if ((err = harvest_batch(c, (int)i))) break;
-            err = batch_begin(run[i], c, (int)i, first_sample + done, cnt, done + cnt == n_samples, nullptr, false, nullptr);
+            // the pipeline's previous batch must be done before its buffers are reused
+            if (!(err = harvest_batch(c, pi))) err = batch_begin(run[n], c, BatchSpec{pi, first_sample + done, cnt, ar, done + cnt == n_samples, d_samples});
             done += cnt;
         }
-        for (uint32_t b = 0; b <= c->cfg.max_bounces && !err; ++b)
-            for (uint32_t i = 0; i < k && !err; ++i) err = batch_bounce(run[i], b);
-        for (uint32_t i = 0; i < k && !err; ++i)
-        {
-            run[i].after = prev_done; // accumulation stays in sample order
-            if ((err = batch_end(run[i]))) break;
-            prev_done = c->pipe[i].ev_done;
-        }
-    }
-    for (; done < n_samples && !err; done += batch, ++k)
-    {
-        const int pi = (int)(k % n_pipes);
-        const uint32_t cnt = std::min(batch, n_samples - done);
-        if ((err = harvest_batch(c, pi))) break; // the pipeline's previous batch must be done before its buffers are reused
-        if ((err = launch_batch(c, pi, first_sample + done, cnt, done + cnt == n_samples, samples_out ? (f4*)d_samples.p : nullptr, false, prev_done))) break;
-        prev_done = c->pipe[pi].ev_done;
-        if (samples_out)
-        {
-            if ((err = harvest_batch(c, pi))) break;
-            hipError_t e = hipMemcpy(samples_out + (size_t)done * c->local_pixels * 4, d_samples.p, (size_t)cnt * c->local_pixels * 16, hipMemcpyDeviceToHost);
-            if (e != hipSuccess) err = fail(c, PT_ERR_HIP, hipGetErrorString(e));
-        }
+        if (!err) err = run_group(c, run, n, prev_done);
+        if (!err && samples_out && !(err = harvest_batch(c, run[0].spec.pipe)))
+            err = st.download(samples_out + (size_t)(run[0].spec.first_sample - first_sample) * c->local_pixels * 4, d_samples, (size_t)run[0].spec.count * c->local_pixels * 16);
     }
     for (uint32_t i = 0; i < n_pipes; ++i)
     {
@@ -1084,15 +1097,10 @@ int render_common(pt_ctx* c, uint32_t first_sample, uint32_t n_samples, float* s
             c->pipe[i].ev_used = 0; // (batches that were never harvested: their timers are void as well)
         }
         (void)hipGetLastError();
-        if (c->d_accum.p) (void)hipMemsetAsync(c->d_accum.p, 0, c->d_accum.bytes, c->stream);
-        if (c->d_id.p) (void)hipMemsetAsync(c->d_id.p, 0, c->d_id.bytes, c->stream);
-        if (c->d_moments.p) (void)hipMemsetAsync(c->d_moments.p, 0, c->d_moments.bytes, c->stream);
-        c->moments_valid = true;
+        (void)clear_accumulation(c);
         (void)hipStreamSynchronize(c->stream);
-        dev_free(d_samples);
         return err;
     }
-    dev_free(d_samples);
     c->stats.ms_total += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return PT_OK;
 }
@@ -1156,27 +1164,8 @@ void pt_destroy(pt_ctx* c)
 {
     if (!c) return;
     if (c->dev_ready)
-    {
-        (void)hipStreamSynchronize(c->stream);
-        for (int i = 0; i < pt_ctx::kMaxPipes; ++i)
-        {
-            pt_ctx::Pipe& pp = c->pipe[i];
-            (void)hipStreamSynchronize(c->pipe_stream(i));
-            free_pipe_pool(pp);
-            for (auto& e : pp.ev_pool) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
-            if (pp.own_stream) (void)hipStreamDestroy(pp.own_stream);
-            if (pp.side_stream) (void)hipStreamDestroy(pp.side_stream);
-            if (pp.ev_fork) (void)hipEventDestroy(pp.ev_fork);
-            if (pp.ev_join) (void)hipEventDestroy(pp.ev_join);
-            if (pp.ev_done) (void)hipEventDestroy(pp.ev_done);
-        }
-        DevBuf* bufs[] = {&c->d_input, &c->d_velocity, &c->d_output, &c->d_blob, &c->d_tri_shade, &c->d_tri_pos, &c->d_tri_orig, &c->d_materials, &c->d_lights, &c->d_env, &c->d_spill, &c->d_accum, &c->d_position, &c->d_id,
-                         &c->d_moments, &c->d_list, &c->d_select};
-        for (DevBuf* b : bufs) dev_free(*b);
-        if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-        if (c->ev_start) (void)hipEventDestroy(c->ev_start);
-    }
-    delete c;
+        for (int i = 0; i < pt_ctx::kMaxPipes; ++i) (void)hipStreamSynchronize(c->pipe_stream(i));
+    delete c; // the handles release the device memory, pinned buffers, events and streams
 }
 
 const char* pt_last_error(pt_ctx* c) { return c ? c->err.c_str() : "null context"; }
@@ -1196,11 +1185,11 @@ int pt_set_config(pt_ctx* c, const pt_config* cfg)
     if ((c->cfg.flags & ~old.flags & PT_FLAG_ADAPTIVE) && c->d_accum.p) c->moments_valid = false;
     if (c->local_pixels != old_px)
     {
-        dev_free(c->d_accum);
-        dev_free(c->d_position);
-        dev_free(c->d_id);
-        dev_free(c->d_moments);
-        dev_free(c->d_list);
+        c->d_accum.reset();
+        c->d_position.reset();
+        c->d_id.reset();
+        c->d_moments.reset();
+        c->d_list.reset();
     }
     return PT_OK;
 }
@@ -1364,7 +1353,7 @@ int pt_render_device(pt_ctx* c, uint32_t first_sample, uint32_t n_samples)
 {
     if (!c) return PT_ERR_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
-    return render_common(c, first_sample, n_samples, nullptr);
+    return render_batches(c, first_sample, n_samples, nullptr);
 }
 
 int pt_render(pt_ctx* c, uint32_t first_sample, uint32_t n_samples, float* data, float* position, uint32_t* id)
@@ -1372,24 +1361,17 @@ int pt_render(pt_ctx* c, uint32_t first_sample, uint32_t n_samples, float* data,
     if (!c) return PT_ERR_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
     int r;
-    if ((r = precheck(c))) return r;
-    if ((r = upload_scene(c))) return r;
-    if ((r = ensure_frame(c))) return r;
-    const size_t px = c->local_pixels;
-    if (id && px) HIPCHK(c, hipMemcpyAsync(c->d_id.p, id, px * 4, hipMemcpyHostToDevice, c->stream));
-    if ((r = render_common(c, first_sample, n_samples, nullptr))) return r;
-    if (data && px) HIPCHK(c, hipMemcpyAsync(data, c->d_accum.p, px * 16, hipMemcpyDeviceToHost, c->stream));
-    if (position && px) HIPCHK(c, hipMemcpyAsync(position, c->d_position.p, px * 16, hipMemcpyDeviceToHost, c->stream));
-    if (id && px) HIPCHK(c, hipMemcpyAsync(id, c->d_id.p, px * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return PT_OK;
+    if ((r = scene_frame(c))) return r;
+    if (id && c->local_pixels) HIPCHK(c, hipMemcpyAsync(c->d_id.p, id, (size_t)c->local_pixels * 4, hipMemcpyHostToDevice, c->stream));
+    if ((r = render_batches(c, first_sample, n_samples, nullptr))) return r;
+    return download_frame(c, data, position, id);
 }
 
 int pt_render_samples(pt_ctx* c, uint32_t first_sample, uint32_t n_samples, float* samples)
 {
     if (!c || !samples) return PT_ERR_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
-    return render_common(c, first_sample, n_samples, samples);
+    return render_batches(c, first_sample, n_samples, samples);
 }
 
 int pt_reset_accumulation(pt_ctx* c)
@@ -1397,12 +1379,8 @@ int pt_reset_accumulation(pt_ctx* c)
     if (!c) return PT_ERR_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
     int r;
-    if ((r = ensure_device(c))) return r;
-    if ((r = ensure_frame(c))) return r;
-    HIPCHK(c, hipMemsetAsync(c->d_accum.p, 0, c->d_accum.bytes, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->d_id.p, 0, c->d_id.bytes, c->stream));
-    if (c->d_moments.p) HIPCHK(c, hipMemsetAsync(c->d_moments.p, 0, c->d_moments.bytes, c->stream));
-    c->moments_valid = true;
+    if ((r = device_frame(c))) return r;
+    HIPCHK(c, clear_accumulation(c));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return PT_OK;
 }
@@ -1412,8 +1390,7 @@ int pt_accum_device_ptr(pt_ctx* c, void** p, uint64_t* n)
     if (!c || !p) return PT_ERR_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
     int r;
-    if ((r = ensure_device(c))) return r;
-    if ((r = ensure_frame(c))) return r;
+    if ((r = device_frame(c))) return r;
     *p = c->d_accum.p;
     if (n) *n = c->local_pixels;
     return PT_OK;
@@ -1423,12 +1400,8 @@ int pt_read_accumulation(pt_ctx* c, float* data)
 {
     if (!c || !data) return PT_ERR_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
-    int r;
-    if ((r = ensure_device(c))) return r;
-    if ((r = ensure_frame(c))) return r;
-    HIPCHK(c, hipMemcpyAsync(data, c->d_accum.p, (size_t)c->local_pixels * 16, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return PT_OK;
+    int r = device_frame(c);
+    return r ? r : download_frame(c, data, nullptr, nullptr);
 }
 
 // the frame's whole state as it lies on the device (any pointer may be null): what pt_write_accumulation takes back
@@ -1436,15 +1409,8 @@ int pt_read_frame(pt_ctx* c, float* data, float* position, uint32_t* id)
 {
     if (!c) return PT_ERR_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
-    int r;
-    if ((r = ensure_device(c))) return r;
-    if ((r = ensure_frame(c))) return r;
-    const size_t px = c->local_pixels;
-    if (data && px) HIPCHK(c, hipMemcpyAsync(data, c->d_accum.p, px * 16, hipMemcpyDeviceToHost, c->stream));
-    if (position && px) HIPCHK(c, hipMemcpyAsync(position, c->d_position.p, px * 16, hipMemcpyDeviceToHost, c->stream));
-    if (id && px) HIPCHK(c, hipMemcpyAsync(id, c->d_id.p, px * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return PT_OK;
+    int r = device_frame(c);
+    return r ? r : download_frame(c, data, position, id);
 }
 
 // Restore what pt_render / pt_read_frame returned into this context, so that a render stopped in one process continues in
@@ -1455,8 +1421,7 @@ int pt_write_accumulation(pt_ctx* c, const float* data, const float* position, c
     if (!c || !data) return PT_ERR_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
     int r;
-    if ((r = ensure_device(c))) return r;
-    if ((r = ensure_frame(c))) return r;
+    if ((r = device_frame(c))) return r;
     HIPCHK(c, hipStreamSynchronize(c->stream)); // the frame buffers may still be written by a render in flight
     c->moments_valid = false;                    // until pt_write_moments restores the matching Q (PT_FLAG_ADAPTIVE)
     HIPCHK(c, hipMemcpyAsync(c->d_accum.p, data, (size_t)c->local_pixels * 16, hipMemcpyHostToDevice, c->stream));
@@ -1475,16 +1440,14 @@ int pt_render_adaptive(pt_ctx* c, const pt_adaptive* crit, uint32_t n_samples, u
     if ((r = adaptive_check(c, crit))) return r;
     // a pixel's sample indices run to n_p + n_samples - 1 with n_p <= 2^24: 32 bits
     if (n_samples > 0xffffffffu - (1u << 24)) return fail(c, PT_ERR_ARG, "n_samples too large");
-    if ((r = precheck(c))) return r;
-    if ((r = upload_scene(c))) return r;
-    if ((r = ensure_frame(c))) return r;
+    if ((r = scene_frame(c))) return r;
     uint32_t n = 0;
     if ((r = adaptive_select(c, crit, &n))) return r;
     if (n_active) *n_active = n;
     if (n == 0 || n_samples == 0) return PT_OK;
     c->cur_list = (const uint2*)c->d_list.p;
     c->cur_list_n = n;
-    r = render_common(c, 0, n_samples, nullptr);
+    r = render_batches(c, 0, n_samples, nullptr);
     c->cur_list = nullptr;
     c->cur_list_n = 0;
     return r;
@@ -1496,8 +1459,7 @@ int pt_adaptive_mask(pt_ctx* c, const pt_adaptive* crit, uint8_t* mask, uint32_t
     std::lock_guard<std::mutex> lk(c->mu);
     int r;
     if ((r = adaptive_check(c, crit))) return r;
-    if ((r = ensure_device(c))) return r;
-    if ((r = ensure_frame(c))) return r;
+    if ((r = device_frame(c))) return r;
     uint32_t n = 0;
     if ((r = adaptive_select(c, crit, &n))) return r;
     if (n_active) *n_active = n;
@@ -1517,8 +1479,7 @@ int pt_read_moments(pt_ctx* c, float* sumsq)
     std::lock_guard<std::mutex> lk(c->mu);
     if (!(c->cfg.flags & PT_FLAG_ADAPTIVE)) return fail(c, PT_ERR_STATE, "moments are kept with PT_FLAG_ADAPTIVE only");
     int r;
-    if ((r = ensure_device(c))) return r;
-    if ((r = ensure_frame(c))) return r;
+    if ((r = device_frame(c))) return r;
     HIPCHK(c, hipMemcpyAsync(sumsq, c->d_moments.p, (size_t)c->local_pixels * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return PT_OK;
@@ -1530,8 +1491,7 @@ int pt_write_moments(pt_ctx* c, const float* sumsq)
     std::lock_guard<std::mutex> lk(c->mu);
     if (!(c->cfg.flags & PT_FLAG_ADAPTIVE)) return fail(c, PT_ERR_STATE, "moments are kept with PT_FLAG_ADAPTIVE only");
     int r;
-    if ((r = ensure_device(c))) return r;
-    if ((r = ensure_frame(c))) return r;
+    if ((r = device_frame(c))) return r;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpyAsync(c->d_moments.p, sumsq, (size_t)c->local_pixels * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1583,13 +1543,17 @@ int pt_frame(pt_ctx* c, uint32_t frame_index, const float* last_inv_projection, 
     int r;
     if ((r = precheck(c))) return r;
     if (c->cfg.world_size != 1) return fail(c, PT_ERR_STATE, "pt_frame needs the whole frame on one rank (3x3 neighbourhoods cross row strips)");
-    if ((r = upload_scene(c))) return r;
-    if ((r = ensure_frame(c))) return r;
+    if ((r = upload_scene(c)) || (r = ensure_frame(c))) return r;
     const size_t px = c->local_pixels;
     if ((r = dev_alloc(c, c->d_input, px * 16)) || (r = dev_alloc(c, c->d_velocity, px * 8)) || (r = dev_alloc(c, c->d_output, px * 16))) return r;
     if (id) HIPCHK(c, hipMemcpyAsync(c->d_id.p, id, px * 4, hipMemcpyHostToDevice, c->stream));
-    if ((r = ensure_wavefront(c, 0, px, c->cfg.max_bounces + 2))) return r;
-    if ((r = run_batch(c, frame_index, 1, true, (f4*)c->d_input.p, true))) return r;   // main.rs:181-207, one sample per pixel
+    if ((r = ensure_wavefront(c, 0, px, c->cfg.max_bounces + 2)) || (r = ensure_environment(c))) return r;
+    // main.rs:181-207, one sample per pixel on pipeline 0 into the input texture
+    BatchRun br;
+    hipEvent_t after = nullptr;
+    if ((r = batch_begin(br, c, BatchSpec{0, frame_index, 1u, render_rect(c), true, (f4*)c->d_input.p, true})) || (r = run_group(c, &br, 1, after)) ||
+        (r = harvest_batch(c, 0)))
+        return r;
     c->moments_valid = false; // State::update adds (or reprojects) the sample without Q: the moments no longer describe the accumulation
     hipStream_t s = c->stream;
     const int w = (int)c->cfg.width, h = (int)c->cfg.height;
@@ -1621,8 +1585,7 @@ int pt_present(pt_ctx* c, float* rgba)
     if (!c || !rgba) return PT_ERR_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
     int r;
-    if ((r = ensure_device(c))) return r;
-    if ((r = ensure_frame(c))) return r;
+    if ((r = device_frame(c))) return r;
     const size_t px = c->local_pixels;
     if ((r = dev_alloc(c, c->d_output, px * 16))) return r;
     launch_post_tonemap(c->stream, (uint32_t)px, (const f4*)c->d_accum.p, (f4*)c->d_output.p);
@@ -1634,8 +1597,7 @@ int pt_present(pt_ctx* c, float* rgba)
 static int present_rgb8_locked(pt_ctx* c, std::vector<uint8_t>& host)
 {
     int r;
-    if ((r = ensure_device(c))) return r;
-    if ((r = ensure_frame(c))) return r;
+    if ((r = device_frame(c))) return r;
     const size_t px = c->local_pixels;
     if ((r = dev_alloc(c, c->d_output, px * 16))) return r;
     launch_post_rgb8(c->stream, (uint32_t)px, (const f4*)c->d_accum.p, (uint8_t*)c->d_output.p);
@@ -1669,38 +1631,19 @@ int pt_write_image(pt_ctx* c, const char* path)
     return PT_OK;
 }
 
-namespace {
-struct TmpBufs
-{
-    std::vector<DevBuf> b;
-    ~TmpBufs() { for (DevBuf& x : b) dev_free(x); }
-    int up(pt_ctx* c, const void* src, size_t bytes, void** out)
-    {
-        DevBuf d;
-        int r = dev_alloc(c, d, bytes);
-        if (r) return r;
-        b.push_back(d);
-        if (src) { hipError_t e = hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice); if (e != hipSuccess) return fail(c, PT_ERR_HIP, hipGetErrorString(e)); }
-        *out = d.p;
-        return PT_OK;
-    }
-};
-} // namespace
-
 int pt_post_velocity(pt_ctx* c, uint32_t w, uint32_t h, const float* position, const float* last_inv_projection, float* velocity)
 {
     if (!c || !position || !last_inv_projection || !velocity || !w || !h) return PT_ERR_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
     int r;
     if ((r = ensure_device(c))) return r;
-    TmpBufs t;
-    void *dp, *dv;
+    Staging t(c);
     const size_t px = (size_t)w * h;
-    if ((r = t.up(c, position, px * 16, &dp)) || (r = t.up(c, nullptr, px * 8, &dv))) return r;
-    launch_post_velocity(c->stream, (int)w, (int)h, (const f4*)dp, last_inv_projection, (float*)dv);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(velocity, dv, px * 8, hipMemcpyDeviceToHost));
-    return PT_OK;
+    const f4* dp = (const f4*)t.in(position, px * 16);
+    float* dv = (float*)t.out(px * 8);
+    if (t.err) return t.err;
+    launch_post_velocity(c->stream, (int)w, (int)h, dp, last_inv_projection, dv);
+    return t.download(velocity, dv, px * 8);
 }
 
 int pt_post_reproject(pt_ctx* c, uint32_t w, uint32_t h, const float* input, const float* accum, const float* velocity, const uint32_t* id, float* output)
@@ -1709,16 +1652,16 @@ int pt_post_reproject(pt_ctx* c, uint32_t w, uint32_t h, const float* input, con
     std::lock_guard<std::mutex> lk(c->mu);
     int r;
     if ((r = ensure_device(c))) return r;
-    TmpBufs t;
-    void *di, *da, *dv, *did, *dout;
+    Staging t(c);
     const size_t px = (size_t)w * h;
-    if ((r = t.up(c, input, px * 16, &di)) || (r = t.up(c, accum, px * 16, &da)) || (r = t.up(c, velocity, px * 8, &dv)) ||
-        (r = t.up(c, id, px * 4, &did)) || (r = t.up(c, nullptr, px * 16, &dout)))
-        return r;
-    launch_post_reproject(c->stream, (int)w, (int)h, (const f4*)di, (const f4*)da, (const float*)dv, (const uint32_t*)did, (f4*)dout);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(output, dout, px * 16, hipMemcpyDeviceToHost));
-    return PT_OK;
+    const f4* di = (const f4*)t.in(input, px * 16);
+    const f4* da = (const f4*)t.in(accum, px * 16);
+    const float* dv = (const float*)t.in(velocity, px * 8);
+    const uint32_t* did = (const uint32_t*)t.in(id, px * 4);
+    f4* dout = (f4*)t.out(px * 16);
+    if (t.err) return t.err;
+    launch_post_reproject(c->stream, (int)w, (int)h, di, da, dv, did, dout);
+    return t.download(output, dout, px * 16);
 }
 
 int pt_post_tonemap(pt_ctx* c, uint32_t w, uint32_t h, const float* accum, float* out)
@@ -1727,14 +1670,13 @@ int pt_post_tonemap(pt_ctx* c, uint32_t w, uint32_t h, const float* accum, float
     std::lock_guard<std::mutex> lk(c->mu);
     int r;
     if ((r = ensure_device(c))) return r;
-    TmpBufs t;
-    void *da, *dout;
+    Staging t(c);
     const size_t px = (size_t)w * h;
-    if ((r = t.up(c, accum, px * 16, &da)) || (r = t.up(c, nullptr, px * 16, &dout))) return r;
-    launch_post_tonemap(c->stream, (uint32_t)px, (const f4*)da, (f4*)dout);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(out, dout, px * 16, hipMemcpyDeviceToHost));
-    return PT_OK;
+    const f4* da = (const f4*)t.in(accum, px * 16);
+    f4* dout = (f4*)t.out(px * 16);
+    if (t.err) return t.err;
+    launch_post_tonemap(c->stream, (uint32_t)px, da, dout);
+    return t.download(out, dout, px * 16);
 }
 
 int pt_post_rgb8(pt_ctx* c, uint32_t w, uint32_t h, const float* accum, uint8_t* rgb)
@@ -1743,18 +1685,19 @@ int pt_post_rgb8(pt_ctx* c, uint32_t w, uint32_t h, const float* accum, uint8_t*
     std::lock_guard<std::mutex> lk(c->mu);
     int r;
     if ((r = ensure_device(c))) return r;
-    TmpBufs t;
-    void *da, *dout;
+    Staging t(c);
     const size_t px = (size_t)w * h;
-    if ((r = t.up(c, accum, px * 16, &da)) || (r = t.up(c, nullptr, px * 3, &dout))) return r;
-    launch_post_rgb8(c->stream, (uint32_t)px, (const f4*)da, (uint8_t*)dout);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(rgb, dout, px * 3, hipMemcpyDeviceToHost));
-    return PT_OK;
+    const f4* da = (const f4*)t.in(accum, px * 16);
+    uint8_t* dout = (uint8_t*)t.out(px * 3);
+    if (t.err) return t.err;
+    launch_post_rgb8(c->stream, (uint32_t)px, da, dout);
+    return t.download(rgb, dout, px * 3);
 }
 
 // ---- unit hooks
-static int upload_rays(pt_ctx* c, uint32_t n, const float* o, const float* d, const float* tmax, DevBuf& da, DevBuf& db, DevBuf& dhead)
+// n rays as the two halves of a ray queue ({origin, tmax}, {direction, ray index}); returns the queue's head: word 0 = n, then its
+// zeroed claim cursors
+static uint32_t* upload_rays(Staging& t, uint32_t n, const float* o, const float* d, const float* tmax, RayQueue& q)
 {
     std::vector<f4> a(n), b(n);
     for (uint32_t i = 0; i < n; ++i)
@@ -1762,15 +1705,10 @@ static int upload_rays(pt_ctx* c, uint32_t n, const float* o, const float* d, co
         a[i] = f4{o[3 * i], o[3 * i + 1], o[3 * i + 2], tmax ? tmax[i] : __builtin_inff()};
         b[i] = f4{d[3 * i], d[3 * i + 1], d[3 * i + 2], from_bits(i)};
     }
-    int r;
-    const size_t head_bytes = (size_t)(32 + kHeadWordsPerQueue) * 4; // word 0 = n, then the queue's zeroed claim cursors
-    if ((r = dev_alloc(c, da, (size_t)n * 16)) || (r = dev_alloc(c, db, (size_t)n * 16)) || (r = dev_alloc(c, dhead, head_bytes))) return r;
-    HIPCHK(c, hipMemcpyAsync(da.p, a.data(), (size_t)n * 16, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(db.p, b.data(), (size_t)n * 16, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(dhead.p, 0, head_bytes, c->stream));
-    HIPCHK(c, hipMemcpyAsync(dhead.p, &n, 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return PT_OK;
+    std::vector<uint32_t> head(32 + kHeadWordsPerQueue, 0u);
+    head[0] = n;
+    q = RayQueue{(f4*)t.in(a.data(), (size_t)n * 16), (f4*)t.in(b.data(), (size_t)n * 16)};
+    return (uint32_t*)t.in(head.data(), head.size() * 4);
 }
 
 int pt_trace_closest(pt_ctx* c, int which, uint32_t n, const float* o, const float* d, const float* tmax, float* t, float* u, float* v,
@@ -1787,35 +1725,28 @@ int pt_trace_closest(pt_ctx* c, int which, uint32_t n, const float* o, const flo
         for (uint32_t i = 0; i < n; ++i) { t[i] = __builtin_inff(); u[i] = v[i] = 0; inst[i] = prim[i] = MISS_ID; }
         return PT_OK;
     }
-    DevBuf da, db, dh, dhit;
-    r = upload_rays(c, n, o, d, tmax, da, db, dh);
-    if (!r) r = dev_alloc(c, dhit, (size_t)n * 16);
-    if (!r)
+    Staging st(c);
+    RayQueue q;
+    uint32_t* dh = upload_rays(st, n, o, d, tmax, q);
+    f4* dhit = (f4*)st.out((size_t)n * 16);
+    if (st.err) return st.err;
+    launch_trace_rays_closest(c->stream, trace_launch(c), root, q, n, dh, dhit);
+    std::vector<f4> h(n);
+    if ((r = st.download(h.data(), dhit, (size_t)n * 16))) return r;
+    const FlatScene& f = c->scene.flat;
+    const uint32_t mask = (1u << f.prim_bits) - 1u;
+    for (uint32_t i = 0; i < n; ++i)
     {
-        launch_trace_rays_closest(c->stream, trace_launch(c), root, RayQueue{(f4*)da.p, (f4*)db.p}, n, (uint32_t*)dh.p, (f4*)dhit.p);
-        std::vector<f4> h(n);
-        hipError_t e = hipMemcpyAsync(h.data(), dhit.p, (size_t)n * 16, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) r = fail(c, PT_ERR_HIP, hipGetErrorString(e));
+        const uint32_t id = bits(h[i].w);
+        t[i] = h[i].x; u[i] = h[i].y; v[i] = h[i].z;
+        if (id == MISS_ID) { inst[i] = prim[i] = MISS_ID; t[i] = __builtin_inff(); u[i] = v[i] = 0; }
         else
         {
-            const FlatScene& f = c->scene.flat;
-            const uint32_t mask = (1u << f.prim_bits) - 1u;
-            for (uint32_t i = 0; i < n; ++i)
-            {
-                const uint32_t id = bits(h[i].w);
-                t[i] = h[i].x; u[i] = h[i].y; v[i] = h[i].z;
-                if (id == MISS_ID) { inst[i] = prim[i] = MISS_ID; t[i] = __builtin_inff(); u[i] = v[i] = 0; }
-                else
-                {
-                    inst[i] = (id >> f.prim_bits) - f.inst_base[which ? 1 : 0];
-                    prim[i] = f.tri_orig[id & mask];
-                }
-            }
+            inst[i] = (id >> f.prim_bits) - f.inst_base[which ? 1 : 0];
+            prim[i] = f.tri_orig[id & mask];
         }
     }
-    dev_free(da); dev_free(db); dev_free(dh); dev_free(dhit);
-    return r;
+    return PT_OK;
 }
 
 int pt_trace_any(pt_ctx* c, int which, uint32_t n, const float* o, const float* d, const float* tmax, uint8_t* hit)
@@ -1827,21 +1758,16 @@ int pt_trace_any(pt_ctx* c, int which, uint32_t n, const float* o, const float* 
     if (n == 0) return PT_OK;
     const uint32_t root = which ? c->sv.lights_root : c->sv.world_root;
     if (root == MISS_ID) { std::memset(hit, 0, n); return PT_OK; }
-    DevBuf da, db, dh, docc;
-    r = upload_rays(c, n, o, d, tmax, da, db, dh);
-    if (!r) r = dev_alloc(c, docc, (size_t)n * 4);
-    if (!r)
-    {
-        launch_trace_rays_any(c->stream, trace_launch(c), root, RayQueue{(f4*)da.p, (f4*)db.p}, n, (uint32_t*)dh.p, (uint32_t*)docc.p);
-        std::vector<uint32_t> h(n);
-        hipError_t e = hipMemcpyAsync(h.data(), docc.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) r = fail(c, PT_ERR_HIP, hipGetErrorString(e));
-        else
-            for (uint32_t i = 0; i < n; ++i) hit[i] = h[i] ? 1 : 0;
-    }
-    dev_free(da); dev_free(db); dev_free(dh); dev_free(docc);
-    return r;
+    Staging st(c);
+    RayQueue q;
+    uint32_t* dh = upload_rays(st, n, o, d, tmax, q);
+    uint32_t* docc = (uint32_t*)st.out((size_t)n * 4);
+    if (st.err) return st.err;
+    launch_trace_rays_any(c->stream, trace_launch(c), root, q, n, dh, docc);
+    std::vector<uint32_t> h(n);
+    if ((r = st.download(h.data(), docc, (size_t)n * 4))) return r;
+    for (uint32_t i = 0; i < n; ++i) hit[i] = h[i] ? 1 : 0;
+    return PT_OK;
 }
 
 int pt_ss_sobol(pt_ctx* c, uint32_t n_points, uint32_t n, const uint32_t* index, const uint32_t* seed, float* out)
@@ -1850,15 +1776,13 @@ int pt_ss_sobol(pt_ctx* c, uint32_t n_points, uint32_t n, const uint32_t* index,
     std::lock_guard<std::mutex> lk(c->mu);
     int r;
     if ((r = ensure_device(c))) return r;
-    DevBuf di, ds, dout;
-    if ((r = dev_alloc(c, di, (size_t)n * 4)) || (r = dev_alloc(c, ds, (size_t)n * 4)) || (r = dev_alloc(c, dout, (size_t)n * 8))) return r;
-    HIPCHK(c, hipMemcpy(di.p, index, (size_t)n * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(ds.p, seed, (size_t)n * 4, hipMemcpyHostToDevice));
-    launch_sobol_probe(c->stream, n_points, n, (const uint32_t*)di.p, (const uint32_t*)ds.p, (float*)dout.p);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(out, dout.p, (size_t)n * 8, hipMemcpyDeviceToHost));
-    dev_free(di); dev_free(ds); dev_free(dout);
-    return PT_OK;
+    Staging t(c);
+    const uint32_t* di = (const uint32_t*)t.in(index, (size_t)n * 4);
+    const uint32_t* ds = (const uint32_t*)t.in(seed, (size_t)n * 4);
+    float* dout = (float*)t.out((size_t)n * 8);
+    if (t.err) return t.err;
+    launch_sobol_probe(c->stream, n_points, n, di, ds, dout);
+    return t.download(out, dout, (size_t)n * 8);
 }
 
 int pt_math_batch(pt_ctx* c, int fn, uint32_t n, const float* a, const float* b, float* o0, float* o1)
@@ -1867,22 +1791,19 @@ int pt_math_batch(pt_ctx* c, int fn, uint32_t n, const float* a, const float* b,
     std::lock_guard<std::mutex> lk(c->mu);
     int r;
     if ((r = ensure_device(c))) return r;
-    DevBuf da, db, d0, d1;
-    if ((r = dev_alloc(c, da, (size_t)n * 4)) || (r = dev_alloc(c, db, (size_t)n * 4)) || (r = dev_alloc(c, d0, (size_t)n * 4)) ||
-        (r = dev_alloc(c, d1, (size_t)n * 4)))
-        return r;
-    HIPCHK(c, hipMemcpy(da.p, a, (size_t)n * 4, hipMemcpyHostToDevice));
-    if (b) HIPCHK(c, hipMemcpy(db.p, b, (size_t)n * 4, hipMemcpyHostToDevice));
+    Staging t(c);
+    const float* da = (const float*)t.in(a, (size_t)n * 4);
+    float* db = (float*)t.in(b, (size_t)n * 4);
+    float* d0 = (float*)t.out((size_t)n * 4);
+    float* d1 = (float*)t.out((size_t)n * 4);
+    if (t.err) return t.err;
     // on the probe's own stream: c->stream is non-blocking, so a hipMemset (null stream, asynchronous to the host for device memory)
     // is not ordered before the kernel and could clear what the kernel wrote
-    else HIPCHK(c, hipMemsetAsync(db.p, 0, (size_t)n * 4, c->stream));
-    HIPCHK(c, hipMemsetAsync(d1.p, 0, (size_t)n * 4, c->stream));
-    launch_math_probe(c->stream, fn, n, (const float*)da.p, (const float*)db.p, (float*)d0.p, (float*)d1.p, c->cfg.seed);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(o0, d0.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    if (o1) HIPCHK(c, hipMemcpy(o1, d1.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    dev_free(da); dev_free(db); dev_free(d0); dev_free(d1);
-    return PT_OK;
+    if (!b) HIPCHK(c, hipMemsetAsync(db, 0, (size_t)n * 4, c->stream));
+    HIPCHK(c, hipMemsetAsync(d1, 0, (size_t)n * 4, c->stream));
+    launch_math_probe(c->stream, fn, n, da, db, d0, d1, c->cfg.seed);
+    if ((r = t.download(o0, d0, (size_t)n * 4))) return r;
+    return o1 ? t.download(o1, d1, (size_t)n * 4) : PT_OK;
 }
 
 int pt_material_eval(pt_ctx* c, int material, uint32_t n, const float* incoming, const float* normal, const uint8_t* front, const uint32_t* pixel,
@@ -1893,21 +1814,16 @@ int pt_material_eval(pt_ctx* c, int material, uint32_t n, const float* incoming,
     if (material < 0 || material >= (int)c->scene.materials.size()) return fail(c, PT_ERR_ARG, "material index");
     int r;
     if ((r = upload_scene(c))) return r;
-    DevBuf di, dn, df, dp, ds, dout;
-    if ((r = dev_alloc(c, di, (size_t)n * 12)) || (r = dev_alloc(c, dn, (size_t)n * 12)) || (r = dev_alloc(c, df, n)) ||
-        (r = dev_alloc(c, dp, (size_t)n * 4)) || (r = dev_alloc(c, ds, (size_t)n * 4)) || (r = dev_alloc(c, dout, (size_t)n * 36)))
-        return r;
-    HIPCHK(c, hipMemcpy(di.p, incoming, (size_t)n * 12, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(dn.p, normal, (size_t)n * 12, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(df.p, front, n, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(dp.p, pixel, (size_t)n * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(ds.p, sample, (size_t)n * 4, hipMemcpyHostToDevice));
-    launch_material_probe(c->stream, c->sv, material, n, (const float*)di.p, (const float*)dn.p, (const uint8_t*)df.p, (const uint32_t*)dp.p,
-                          (const uint32_t*)ds.p, draws, c->cfg.seed, (float*)dout.p);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(out9, dout.p, (size_t)n * 36, hipMemcpyDeviceToHost));
-    dev_free(di); dev_free(dn); dev_free(df); dev_free(dp); dev_free(ds); dev_free(dout);
-    return PT_OK;
+    Staging t(c);
+    const float* di = (const float*)t.in(incoming, (size_t)n * 12);
+    const float* dn = (const float*)t.in(normal, (size_t)n * 12);
+    const uint8_t* df = (const uint8_t*)t.in(front, n);
+    const uint32_t* dp = (const uint32_t*)t.in(pixel, (size_t)n * 4);
+    const uint32_t* ds = (const uint32_t*)t.in(sample, (size_t)n * 4);
+    float* dout = (float*)t.out((size_t)n * 36);
+    if (t.err) return t.err;
+    launch_material_probe(c->stream, c->sv, material, n, di, dn, df, dp, ds, draws, c->cfg.seed, dout);
+    return t.download(out9, dout, (size_t)n * 36);
 }
 
 int pt_volume_eval(pt_ctx* c, int material, uint32_t n, const float* incoming, const float* t_max, const float* dist, const uint32_t* pixel,
@@ -1919,24 +1835,16 @@ int pt_volume_eval(pt_ctx* c, int material, uint32_t n, const float* incoming, c
     if (n == 0) return PT_OK;
     int r;
     if ((r = upload_scene(c))) return r;
-    DevBuf di, dt, dd, dp, ds, dout;
-    if ((r = dev_alloc(c, di, (size_t)n * 12)) || (r = dev_alloc(c, dt, (size_t)n * 4)) || (r = dev_alloc(c, dd, (size_t)n * 4)) ||
-        (r = dev_alloc(c, dp, (size_t)n * 4)) || (r = dev_alloc(c, ds, (size_t)n * 4)) || (r = dev_alloc(c, dout, (size_t)n * 36)))
-    {
-        dev_free(di); dev_free(dt); dev_free(dd); dev_free(dp); dev_free(ds); dev_free(dout);
-        return r;
-    }
-    HIPCHK(c, hipMemcpy(di.p, incoming, (size_t)n * 12, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(dt.p, t_max, (size_t)n * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(dd.p, dist, (size_t)n * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(dp.p, pixel, (size_t)n * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(ds.p, sample, (size_t)n * 4, hipMemcpyHostToDevice));
-    launch_volume_probe(c->stream, c->sv, material, n, (const float*)di.p, (const float*)dt.p, (const float*)dd.p, (const uint32_t*)dp.p,
-                        (const uint32_t*)ds.p, draws, c->cfg.seed, (float*)dout.p);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(out9, dout.p, (size_t)n * 36, hipMemcpyDeviceToHost));
-    dev_free(di); dev_free(dt); dev_free(dd); dev_free(dp); dev_free(ds); dev_free(dout);
-    return PT_OK;
+    Staging t(c);
+    const float* di = (const float*)t.in(incoming, (size_t)n * 12);
+    const float* dt = (const float*)t.in(t_max, (size_t)n * 4);
+    const float* dd = (const float*)t.in(dist, (size_t)n * 4);
+    const uint32_t* dp = (const uint32_t*)t.in(pixel, (size_t)n * 4);
+    const uint32_t* ds = (const uint32_t*)t.in(sample, (size_t)n * 4);
+    float* dout = (float*)t.out((size_t)n * 36);
+    if (t.err) return t.err;
+    launch_volume_probe(c->stream, c->sv, material, n, di, dt, dd, dp, ds, draws, c->cfg.seed, dout);
+    return t.download(out9, dout, (size_t)n * 36);
 }
 
 // ---- host-builder introspection
@@ -2149,8 +2057,8 @@ void pt_multi_destroy(pt_multi* m)
     if (!m->ctx.empty() && m->ctx[0]->dev_ready)
     {
         (void)hipSetDevice(m->ctx[0]->device);
-        dev_free(m->d_parts);
-        dev_free(m->d_full);
+        m->d_parts.reset();
+        m->d_full.reset();
     }
     for (pt_ctx* c : m->ctx) pt_destroy(c);
     delete m;
@@ -2195,7 +2103,7 @@ int pt_multi_render(pt_multi* m, uint32_t first_sample, uint32_t n_samples, floa
     for (pt_ctx* c : m->ctx)
     {
         std::lock_guard<std::mutex> lk(c->mu);
-        if ((r = ensure_device(c)) || (r = ensure_frame(c))) return mfail(m, r, pt_last_error(c));
+        if ((r = device_frame(c))) return mfail(m, r, pt_last_error(c));
     }
     MHIPCHK(m, hipSetDevice(c0->device));
     if ((r = dev_alloc(c0, m->d_parts, std::max<size_t>(part_px * n, 1) * 16)) || (r = dev_alloc(c0, m->d_full, std::max<size_t>(full_px, 1) * 16))) return mfail(m, r, pt_last_error(c0));
@@ -2249,15 +2157,12 @@ int pt_multi_write_image(pt_multi* m, const char* path)
     pt_ctx* c0 = m->ctx[0];
     const size_t px = (size_t)c0->cfg.width * c0->cfg.height;
     MHIPCHK(m, hipSetDevice(c0->device));
-    DevBuf d_rgb;
-    int r = dev_alloc(c0, d_rgb, px * 3);
-    if (r) return mfail(m, r, pt_last_error(c0));
-    launch_post_rgb8(c0->stream, (uint32_t)px, (const f4*)m->d_full.p, (uint8_t*)d_rgb.p);   // ImageHelper::write_image  image_helper.rs:37-58
+    Staging t(c0);
+    uint8_t* d_rgb = (uint8_t*)t.out(px * 3);
+    if (t.err) return mfail(m, t.err, pt_last_error(c0));
+    launch_post_rgb8(c0->stream, (uint32_t)px, (const f4*)m->d_full.p, d_rgb);   // ImageHelper::write_image  image_helper.rs:37-58
     std::vector<uint8_t> host(px * 3);
-    hipError_t e = hipMemcpyAsync(host.data(), d_rgb.p, px * 3, hipMemcpyDeviceToHost, c0->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c0->stream);
-    dev_free(d_rgb);
-    if (e != hipSuccess) return mfail(m, PT_ERR_HIP, hipGetErrorString(e));
+    if (int r = t.download(host.data(), d_rgb, px * 3)) return mfail(m, r, pt_last_error(c0));
     std::string err;
     if (!write_png_rgb8(path, host.data(), c0->cfg.width, c0->cfg.height, &err)) return mfail(m, PT_ERR_IO, err);
     return PT_OK;
@@ -2312,15 +2217,8 @@ int pt_last_batch_counters(pt_ctx* c, uint32_t* rows16, uint32_t cap_rows, uint3
     {
         uint32_t* o = rows16 + 16 * r;
         o[1] = o[3] = o[5] = 0;
-        o[6] = o[7] = o[13] = o[14] = o[15] = 0;
-        const uint32_t* hrow = pp.h_heads + (size_t)r * HEADS_PER_ROW * kHeadWordsPerQueue;
-        for (uint32_t g = 0; g < kQueueHeads; ++g)
-        {
-            const uint32_t* cl = hrow + HEADS_CLOSEST * kHeadWordsPerQueue + g * kHeadStrideWords;
-            const uint32_t* sh = hrow + HEADS_SHADOW * kHeadWordsPerQueue + g * kHeadStrideWords;
-            const uint32_t* lc = hrow + HEADS_LCHAIN * kHeadWordsPerQueue + g * kHeadStrideWords;
-            o[6] += lc[HEAD_TALLY0]; o[7] += lc[HEAD_TALLY1]; o[13] += cl[HEAD_TALLY0]; o[14] += sh[HEAD_TALLY0]; o[15] += lc[HEAD_TALLY2];
-        }
+        const RowTally t = row_tally(pp.h_heads, r);
+        o[6] = (uint32_t)t.lchain0; o[7] = (uint32_t)t.lchain1; o[13] = (uint32_t)t.closest; o[14] = (uint32_t)t.shadow; o[15] = (uint32_t)t.lchain2;
     }
     *n_rows = rows;
     return PT_OK;

@@ -83,3 +83,34 @@ def test_forked_sweep_builder_under_asan_and_tsan(exe):
             assert r.returncode == 0 and "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, (binary, threads, r.returncode, r.stderr[-3000:])
             arenas.add(json.loads(r.stdout.strip().split("\n")[-1])["arena"])
     assert len(arenas) == 1, arenas
+
+
+def test_batch_plan_table(exe):
+    """pt_batch_plan.h: how a render is cut into batches on the wavefront pipelines, and how many paths of state fit.
+    Row: n_samples, active pixels, samples returned, pipelines, batch_spp, LDS scene, max_paths, the four pools' cap_paths."""
+    import json
+    full, px = (1 << 29) - 1, 2073600                              # 1080p, every pixel active
+    plan = [
+        ((256, px, 0, 0, 0, 1, full, 0, 0, 0, 0), [128, 2, 2]),    # the headline: fits, >= 24 M paths: two halves on two pipelines
+        ((256, px, 0, 0, 0, 0, full, 0, 0, 0, 0), [128, 2, 2]),    # the same with the BVH in global memory
+        ((8, px, 0, 0, 0, 1, full, 0, 0, 0, 0), [8, 1, 1]),        # fits, under 24 M paths: one batch on one pipeline
+        ((256, px, 1, 0, 0, 1, full, 0, 0, 0, 0), [256, 1, 1]),    # samples returned: one pipeline
+        ((256, px, 1, 0, 0, 1, 96 << 20, 0, 0, 0, 0), [43, 6, 1]),  # ... cut by what fits
+        ((256, px, 0, 0, 16, 1, full, 0, 0, 0, 0), [16, 16, 2]),   # batch_spp
+        ((256, px, 0, 2, 1, 1, full, 0, 0, 0, 0), [1, 256, 2]),    # batch_spp = 1, pipelines = 2
+        ((256, px, 0, 1, 0, 1, full, 0, 0, 0, 0), [256, 1, 1]),    # pipelines = 1: no split
+        ((256, px, 0, 4, 0, 1, full, 0, 0, 0, 0), [64, 4, 4]),     # pipelines = 4
+        ((256, px, 0, 0, 0, 1, 96 << 20, 0, 0, 0, 0), [24, 11, 2]),  # does not fit: the two pipelines share max_paths
+        ((256, px, 0, 0, 0, 1, 96 << 20, 20 * px, 20 * px, 0, 0), [20, 13, 2]),  # pools of >= 3/4 of a batch are kept
+        ((256, px, 0, 0, 0, 1, 96 << 20, 17 * px, 17 * px, 0, 0), [24, 11, 2]),  # ... smaller ones are not
+        ((300, px, 0, 0, 300, 1, full, 0, 0, 0, 0), [0, 0, 0]),    # refused: path ids are 29-bit
+        ((1, 1 << 30, 0, 0, 0, 1, full, 0, 0, 0, 0), [0, 0, 0]),   # refused: one sample of 2^30 pixels
+    ]
+    budget = [
+        ((256 << 30, 0, 1, 0), (1 << 29) - 1),                     # clamped to 29-bit path ids
+        ((1 << 30, 0, 1, 0), 2226050),                             # 410 bytes per path for one surface class
+        ((16 << 30, 8 << 30, 4, 1), 37379408),                     # 586 with four classes and volumes; held pools count as free
+        ((100 << 20, 0, 0, 0), 1 << 20),                           # at least 1 M paths
+    ]
+    rows = ["p:" + ",".join(map(str, r)) for r, _ in plan] + ["b:" + ",".join(map(str, r)) for r, _ in budget]
+    assert json.loads(_run([exe, "plan"] + rows)) == [e for _, e in plan] + [e for _, e in budget]
