@@ -7,6 +7,7 @@
 //   examples/headless --render FIRST COUNT [--load-state in.bin] [--save-state out.bin] ...   samples [FIRST, FIRST + COUNT) accumulated
 //       without the temporal pass; the frame's state (accumulation, first-hit position, id history) can be saved and picked up by another
 //       process: a long render stopped and continued (pt_read_frame / pt_write_accumulation)
+//   examples/headless ... --denoise den.png   also writes the final frame through the edge-aware denoiser (guides of the last frame's sample)
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -24,7 +25,7 @@ int main(int argc, char** argv)
     bool move = false;
     uint32_t gpus = 0, spp = 64;
     std::vector<int32_t> devices;
-    std::string models_dir = "models/cornell", out = "", load_state = "", save_state = "";
+    std::string models_dir = "models/cornell", out = "", load_state = "", save_state = "", denoise_out = "";
     bool render_mode = false;
     uint32_t render_first = 0, render_count = 0;
     for (int i = 1; i < argc; ++i)
@@ -40,6 +41,7 @@ int main(int argc, char** argv)
         else if (a == "--bounces") bounces = (uint32_t)std::atoi(next("--bounces"));
         else if (a == "--models") models_dir = next("--models");
         else if (a == "--out") out = next("--out");
+        else if (a == "--denoise") denoise_out = next("--denoise");
         else if (a == "--move") move = true;
         else if (a == "--gpus") gpus = (uint32_t)std::atoi(next("--gpus"));
         else if (a == "--spp") spp = (uint32_t)std::atoi(next("--spp"));
@@ -53,7 +55,7 @@ int main(int argc, char** argv)
         }
         else if (a == "--help" || a == "-h")
         {
-            std::printf("usage: %s [--width W] [--height H] [--frames N] [--bounces B] [--move] [--models DIR] [--out file.png]\n", argv[0]);
+            std::printf("usage: %s [--width W] [--height H] [--frames N] [--bounces B] [--move] [--models DIR] [--out file.png] [--denoise file.png]\n", argv[0]);
             return 0;
         }
         else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
@@ -151,6 +153,13 @@ int main(int argc, char** argv)
         std::printf("{\"frames\": %u, \"width\": %u, \"height\": %u, \"ms_per_frame\": %.3f, \"Mray_per_s\": %.1f}\n", frames, width, height,
                     1e3 * seconds / (frames ? frames : 1), rays / seconds / 1e6);
         if (!out.empty()) renderer.write_image(out);         // ImageHelper::write_image
+        if (!denoise_out.empty() && frames)
+        {
+            // the interactive recipe: guides of the last frame's sample, then the filter (pt_api.h)
+            renderer.render_guides(frames - 1);
+            renderer.denoise();
+            renderer.write_denoised_image(denoise_out);
+        }
     }
     catch (const Error& e)
     {

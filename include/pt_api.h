@@ -227,6 +227,62 @@ int pt_post_reproject(pt_ctx* ctx, uint32_t w, uint32_t h, const float* input, c
 int pt_post_tonemap(pt_ctx* ctx, uint32_t w, uint32_t h, const float* accum, float* out);
 int pt_post_rgb8(pt_ctx* ctx, uint32_t w, uint32_t h, const float* accum, uint8_t* rgb);
 
+/* ---- denoising: first-hit guides + an edge-aware a-trous filter (SVGF's spatial part) ------------------------------ */
+/* The reference ships only the temporal half of a real-time denoiser (compute.wgsl); this is the spatial half.  A context that never calls
+ * these entry points allocates and launches nothing for them.
+ *
+ * pt_render_guides traces, for every local pixel (on any rank, ignoring the primary-cull rectangle), the camera ray pt_render's sample
+ * `sample` starts with (main.rs:193-199: the stream's draw 0 and the Sobol jitter) against the world TLAS and keeps three guides on the device:
+ *   position : r.at(t) | t exactly as pt_render writes position; a miss gives r.at(1e5) | 1e5
+ *   normal   : the face-forwarded world-space shading normal of the hit (HitInfo's normal, primitive.rs:161-165 + tlas.rs:105); a miss (0,0,0)
+ *   model    : the model (BLAS) index of the hit instance, 0xffffffff for a miss; its low byte is the id byte pt_render writes for that sample
+ * They never touch the accumulation, position, id history or moments.  pt_set_camera, pt_camera_input, pt_build, pt_set_config and
+ * pt_set_environment make them stale.  After pt_frame(k), pt_render_guides(k) gives exactly pt_frame's position and the low byte of its id.
+ * pt_read_guides copies them to the host (any pointer may be NULL): local_rows * width entries of xyzt, xyz and u32; PT_ERR_STATE without guides. */
+int pt_render_guides(pt_ctx* ctx, uint32_t sample);
+int pt_read_guides(pt_ctx* ctx, float* position_xyzt, float* normal_xyz, uint32_t* model);
+/* The filter, in f32 with every operation correctly rounded (no contraction) and in the order written.  exp is pt_math.h's exp_det.
+ *   Pixel p is VALID when acc.w != 0; an invalid pixel is never a neighbour and its output is (0,0,0,0).  Every valid output is (c, 1).
+ *   c_p = (acc.r / acc.w, acc.g / acc.w, acc.b / acc.w);  l(c) = (0.2126f * c.r + 0.7152f * c.g) + 0.0722f * c.b (of the current colour).
+ *   A NEIGHBOUR q of p is a valid pixel inside the image with model_q == model_p and q != p (other models' pixels are skipped everywhere,
+ *   so changing one model's inputs leaves every other model's outputs bit-identical).  p is a HIT when model_p != 0xffffffff.
+ *   Geometry terms of two hits (n, x: normal and position guides, sn = sigma_normal, sx = sigma_plane):
+ *     nd = (n_p.x * n_q.x + n_p.y * n_q.y) + n_p.z * n_q.z;  wn = nd > 0 ? nd : 0, then wn = wn * wn log2(sn) times;
+ *     d = x_q - x_p (per component);  d2 = (d.x * d.x + d.y * d.y) + d.z * d.z;
+ *     a_x = d2 > 0 ? |(n_p.x * d.x + n_p.y * d.y) + n_p.z * d.z| / (sx * sqrt(d2)) : 0
+ *   VARIANCE before level 0 (no option: the library uses what it can observe):
+ *     PT_FLAG_ADAPTIVE with valid moments Q (pt_denoise), or sumsq != NULL (pt_post_denoise): var_p = e2 of the adaptive criterion above
+ *       (n = acc.w; m = l(acc.rgb) / n; v = Q / n - m * m; if (!(v > 0)) v = 0; var = v / n);
+ *     otherwise (e.g. after pt_frame) the spatial variance: over the 7 x 7 taps (dy, dx in -3..3, row-major: dy outer) that are p or a
+ *       neighbour, w = 1 for p and for two misses, wn * exp(-a_x) for two hits; sw += w; sl += w * l_q; sll += w * (l_q * l_q);
+ *       mu = sl / sw; var = sll / sw - mu * mu; if (!(var > 0)) var = 0.
+ *   Level i = 0 .. iterations-1, step s = 2^i, from (c, var) to (c', var'):
+ *     g = sg / sk over the 3 x 3 taps at step 1 (row-major) that are p or a neighbour: k = kb[dx] * kb[dy], kb = (0.25, 0.5, 0.25);
+ *       sg += k * var_q; sk += k;   inv = 1 / (sigma_luminance * sqrt(g) + 1e-6f);
+ *     over the 5 x 5 taps p + s * (dx, dy), dy outer, dx inner, each in -2..2, that are p or a neighbour:
+ *       e = 1 for p; else a_l = |l_p - l_q| * inv, e = exp(-a_l) for two misses, wn * exp(-(a_x + a_l)) for two hits;
+ *       w = (h[dx] * h[dy]) * e, h = (1, 4, 6, 4, 1) / 16;  sw += w; sc += w * c_q (per channel); sv += (w * w) * var_q;
+ *     c' = sc / sw (per channel); var' = sv / (sw * sw).
+ *   The result is (c', 1) of the last level.  Albedo is constant per model, so there is no demodulation.
+ * pt_denoise filters the context's accumulation with its guides (and its moments where valid) and never changes the accumulation, id history,
+ * position or moments; rgba (NULL: the result stays on the device) receives local_rows * width rgba f32.  PT_ERR_ARG: p NULL, iterations > 8,
+ * a sigma that is negative, NaN or infinite, a sigma_normal that is not a power of two from 1 to 256 (checked before any device call).
+ * PT_ERR_STATE: nothing accumulated yet, the guides missing or stale, world_size > 1 (the neighbourhoods cross row strips, as in pt_frame).
+ * The interactive recipe: pt_frame(k), pt_render_guides(k), pt_denoise, then present the denoised frame (pt_write_denoised_image). */
+typedef struct pt_denoise_params
+{
+    uint32_t iterations;   /* a-trous levels, step 2^i; 0 => 5, at most 8 */
+    float sigma_luminance; /* 0 => 4 */
+    uint32_t sigma_normal; /* 0 => 128; a power of two from 1 to 256 (weight = max(0, n_p . n_q)^sigma by repeated squaring) */
+    float sigma_plane;     /* 0 => 1 */
+} pt_denoise_params;
+int pt_denoise(pt_ctx* ctx, const pt_denoise_params* p, float* rgba);
+int pt_write_denoised_image(pt_ctx* ctx, const char* path); /* pt_write_image of the last pt_denoise result (PT_ERR_STATE without one) */
+/* the same kernels on caller images (host pointers, row-major w*h: rgba f32, position xyzt, normal xyz, model u32; sumsq NULL selects the
+ * spatial variance) */
+int pt_post_denoise(pt_ctx* ctx, uint32_t w, uint32_t h, const pt_denoise_params* p, const float* accum_rgba, const float* position_xyzt,
+                    const float* normal_xyz, const uint32_t* model, const float* sumsq, float* out_rgba);
+
 /* ---- unit hooks: TLAS::intersect / any_intersect  src/tlas.rs:66, 111 ------------------------------------------ */
 /* which: 0 world TLAS, 1 lights TLAS.  Host SoA in, host SoA out.  miss => inst = prim = 0xffffffff, t = +inf.
  * inst = TLAS leaf index in allocation order, prim = triangle index inside its BLAS (load order). */

@@ -235,6 +235,11 @@ public:
     std::vector<float> present() const { std::vector<float> v((size_t)width_ * height_ * 4); check(pt_present(ctx_, v.data())); return v; }
     std::vector<uint8_t> present_rgb8() const { std::vector<uint8_t> v((size_t)width_ * height_ * 3); check(pt_present_rgb8(ctx_, v.data())); return v; }
     void write_image(const std::string& path) const { check(pt_write_image(ctx_, path.c_str())); }
+    // denoising: first-hit guides of one sample, then the edge-aware a-trous filter of the accumulation (pt_denoise); the result stays on
+    // the device for write_denoised_image
+    void render_guides(uint32_t sample) { check(pt_render_guides(ctx_, sample)); }
+    void denoise(const pt_denoise_params& p = pt_denoise_params{}) { check(pt_denoise(ctx_, &p, nullptr)); }
+    void write_denoised_image(const std::string& path) const { check(pt_write_denoised_image(ctx_, path.c_str())); }
     pt_stats stats() const { pt_stats s{}; check(pt_get_stats(ctx_, &s)); return s; }
     pt_ctx* handle() const { return ctx_; }
 

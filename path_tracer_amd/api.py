@@ -37,6 +37,7 @@ EXPORTS = [
     "pt_triangle_dump", "pt_get_stats", "pt_reset_stats", "pt_last_batch_counters", "pt_last_batch_shade_pids", "pt_last_batch_step_stats",
     "pt_multi_create", "pt_multi_destroy", "pt_multi_last_error", "pt_multi_ctx", "pt_multi_render", "pt_multi_framebuffer_device_ptr",
     "pt_multi_reset_accumulation", "pt_multi_get_stats", "pt_multi_used_rccl", "pt_multi_write_image",
+    "pt_render_guides", "pt_read_guides", "pt_denoise", "pt_write_denoised_image", "pt_post_denoise",
 ]
 
 
@@ -74,6 +75,11 @@ class Stats(C.Structure):
 class Adaptive(C.Structure):
     """pt_adaptive: the selection criterion of an adaptive render (include/pt_api.h)"""
     _fields_ = [("rel_error", C.c_float), ("abs_floor", C.c_float), ("min_samples", C.c_uint32), ("max_samples", C.c_uint32)]
+
+
+class DenoiseParams(C.Structure):
+    """pt_denoise_params: the a-trous filter's levels and edge-stopping widths (include/pt_api.h); 0 selects each default"""
+    _fields_ = [("iterations", C.c_uint32), ("sigma_luminance", C.c_float), ("sigma_normal", C.c_uint32), ("sigma_plane", C.c_float)]
 
 
 class PtError(RuntimeError):
@@ -176,6 +182,11 @@ def lib():
         L.pt_reset_stats.argtypes = [vp]
         L.pt_last_batch_counters.argtypes = [vp, vp, u32, C.POINTER(u32)]
         L.pt_last_batch_shade_pids.argtypes = [vp, u32, u32, u32, vp]
+        L.pt_render_guides.argtypes = [vp, u32]
+        L.pt_read_guides.argtypes = [vp, vp, vp, vp]
+        L.pt_denoise.argtypes = [vp, C.POINTER(DenoiseParams), vp]
+        L.pt_write_denoised_image.argtypes = [vp, C.c_char_p]
+        L.pt_post_denoise.argtypes = [vp, u32, u32, C.POINTER(DenoiseParams), vp, vp, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -470,6 +481,43 @@ class Renderer:
         h, w = accum.shape[:2]
         out = np.zeros((h, w, 4), np.float32)
         self._chk(self.L.pt_post_tonemap(self.ctx, w, h, _p(accum), _p(out)))
+        return out
+
+    # ---- denoising: first-hit guides + edge-aware a-trous filter
+    def render_guides(self, sample: int):
+        """trace the camera ray of `sample` of every local pixel: first-hit position, normal and model guides stay on the device"""
+        self._chk(self.L.pt_render_guides(self.ctx, sample))
+
+    def read_guides(self):
+        """(position xyzt, normal xyz, model u32; MISS = 0xffffffff) of the last render_guides, local rows x width"""
+        rows, w = len(self.local_rows()), self.cfg.width
+        pos = np.zeros((rows, w, 4), np.float32); nrm = np.zeros((rows, w, 3), np.float32); model = np.zeros((rows, w), np.uint32)
+        self._chk(self.L.pt_read_guides(self.ctx, _p(pos), _p(nrm), _p(model)))
+        return pos, nrm, model
+
+    def denoise(self, iterations=0, sigma_luminance=0.0, sigma_normal=0, sigma_plane=0.0, download=True):
+        """filter the accumulation with the guides (and the moments where the context keeps valid ones); returns rgba (c, 1) per local pixel,
+        or None with download=False (the result stays on the device for write_denoised_image)"""
+        prm = DenoiseParams(iterations, sigma_luminance, sigma_normal, sigma_plane)
+        out = np.zeros((len(self.local_rows()), self.cfg.width, 4), np.float32) if download else None
+        self._chk(self.L.pt_denoise(self.ctx, C.byref(prm), _p(out)))
+        return out
+
+    def write_denoised_image(self, path):
+        self._chk(self.L.pt_write_denoised_image(self.ctx, str(path).encode()))
+
+    def post_denoise(self, accum, position, normal, model, sumsq=None, iterations=0, sigma_luminance=0.0, sigma_normal=0, sigma_plane=0.0):
+        """the filter's kernels on caller images (h x w x 4 accumulation and position, h x w x 3 normal, h x w model; sumsq None = spatial variance)"""
+        accum = np.ascontiguousarray(accum, np.float32)
+        h, w = accum.shape[:2]
+        position = np.ascontiguousarray(position, np.float32); normal = np.ascontiguousarray(normal, np.float32)
+        model = np.ascontiguousarray(model, np.uint32)
+        q = None if sumsq is None else np.ascontiguousarray(sumsq, np.float32)
+        if position.size != h * w * 4 or normal.size != h * w * 3 or model.size != h * w or (q is not None and q.size != h * w):
+            raise PtError(-1, f"post_denoise: guides are not those of a {w}x{h} image")
+        out = np.zeros((h, w, 4), np.float32)
+        prm = DenoiseParams(iterations, sigma_luminance, sigma_normal, sigma_plane)
+        self._chk(self.L.pt_post_denoise(self.ctx, w, h, C.byref(prm), _p(accum), _p(position), _p(normal), _p(model), _p(q), _p(out)))
         return out
 
     # ---- unit hooks

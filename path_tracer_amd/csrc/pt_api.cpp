@@ -156,6 +156,16 @@ struct pt_ctx
     const uint2* cur_list = nullptr; // the list of the pt_render_adaptive in progress (its paths' pixels), else null: the active rectangle
     uint32_t cur_list_n = 0;
 
+    // denoiser (pt_render_guides / pt_denoise): first-hit guides of one sample of every local pixel and what they belong to, the hook queue
+    // they are traced through, the filter's scratch images and its last result.  Nothing is allocated until the first call.
+    DevBuf d_gpos, d_gnrm, d_gmodel, d_gray_a, d_gray_b, d_ghits, d_ghead;
+    bool guides_valid = false;
+    uint64_t guides_scene_version = 0, guides_config_version = 0;
+    uint32_t guides_sample = 0;
+    uint64_t config_version = 0; // bumped by pt_set_config
+    DevBuf d_dn_a, d_dn_b, d_dn_nv, d_dn_out;
+    bool denoised_valid = false;
+
     // stats
     pt_stats stats{};
     int last_pipe = 0; // pipeline whose counters pt_last_batch_counters reports
@@ -1142,6 +1152,34 @@ int adaptive_select(pt_ctx* c, const pt_adaptive* a, uint32_t* n_active)
     return PT_OK;
 }
 
+// ---- denoiser (pt_denoise, pt_post_denoise)
+// the parameters with their defaults filled in; everything that can be refused without touching the device
+int denoise_params(pt_ctx* c, const pt_denoise_params* p, DenoiseK& k)
+{
+    if (!p) return fail(c, PT_ERR_ARG, "null pt_denoise_params");
+    const uint32_t it = p->iterations ? p->iterations : 5u;
+    if (it > 8u) return fail(c, PT_ERR_ARG, "pt_denoise_params.iterations must be at most 8");
+    if (!(p->sigma_luminance >= 0.0f) || !std::isfinite(p->sigma_luminance)) return fail(c, PT_ERR_ARG, "pt_denoise_params.sigma_luminance must be finite and >= 0");
+    if (!(p->sigma_plane >= 0.0f) || !std::isfinite(p->sigma_plane)) return fail(c, PT_ERR_ARG, "pt_denoise_params.sigma_plane must be finite and >= 0");
+    const uint32_t sn = p->sigma_normal ? p->sigma_normal : 128u;
+    if (sn > 256u || (sn & (sn - 1u))) return fail(c, PT_ERR_ARG, "pt_denoise_params.sigma_normal must be a power of two from 1 to 256");
+    k.iterations = it;
+    k.sigma_l = p->sigma_luminance != 0.0f ? p->sigma_luminance : 4.0f;
+    k.sigma_x = p->sigma_plane != 0.0f ? p->sigma_plane : 1.0f;
+    k.log2_sigma_n = 0;
+    while ((1u << k.log2_sigma_n) < sn) ++k.log2_sigma_n;
+    return PT_OK;
+}
+
+// the filter's scratch images for px pixels
+int denoise_scratch(pt_ctx* c, size_t px)
+{
+    int r;
+    for (DevBuf* b : {&c->d_dn_a, &c->d_dn_b, &c->d_dn_nv})
+        if ((r = dev_alloc(c, *b, px * 16))) return r;
+    return PT_OK;
+}
+
 } // namespace
 
 // ====================================================================================================== C-ABI
@@ -1183,8 +1221,10 @@ int pt_set_config(pt_ctx* c, const pt_config* cfg)
     if (c->dev_ready && cfg->device != old_dev && cfg->device >= 0) return fail(c, PT_ERR_STATE, "device cannot change after first use");
     // moments that were not kept while the flag was off do not describe an accumulation that may hold samples
     if ((c->cfg.flags & ~old.flags & PT_FLAG_ADAPTIVE) && c->d_accum.p) c->moments_valid = false;
+    c->config_version++; // the guides belong to the old configuration
     if (c->local_pixels != old_px)
     {
+        c->denoised_valid = false;
         c->d_accum.reset();
         c->d_position.reset();
         c->d_id.reset();
@@ -1594,13 +1634,14 @@ int pt_present(pt_ctx* c, float* rgba)
     return PT_OK;
 }
 
-static int present_rgb8_locked(pt_ctx* c, std::vector<uint8_t>& host)
+// src: the image to present, null = the accumulation
+static int present_rgb8_locked(pt_ctx* c, std::vector<uint8_t>& host, const f4* src = nullptr)
 {
     int r;
     if ((r = device_frame(c))) return r;
     const size_t px = c->local_pixels;
     if ((r = dev_alloc(c, c->d_output, px * 16))) return r;
-    launch_post_rgb8(c->stream, (uint32_t)px, (const f4*)c->d_accum.p, (uint8_t*)c->d_output.p);
+    launch_post_rgb8(c->stream, (uint32_t)px, src ? src : (const f4*)c->d_accum.p, (uint8_t*)c->d_output.p);
     host.resize(px * 3);
     HIPCHK(c, hipMemcpyAsync(host.data(), c->d_output.p, px * 3, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1692,6 +1733,143 @@ int pt_post_rgb8(pt_ctx* c, uint32_t w, uint32_t h, const float* accum, uint8_t*
     if (t.err) return t.err;
     launch_post_rgb8(c->stream, (uint32_t)px, da, dout);
     return t.download(rgb, dout, px * 3);
+}
+
+// ---- denoiser: first-hit guides + edge-aware a-trous filter
+int pt_render_guides(pt_ctx* c, uint32_t sample)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->scene.built) return fail(c, PT_ERR_STATE, "pt_build has not been called");
+    if (!c->scene.camera.set) return fail(c, PT_ERR_STATE, "pt_set_camera has not been called");
+    int r;
+    if ((r = upload_scene(c))) return r;
+    const uint32_t px = c->local_pixels;
+    const size_t n = std::max<uint32_t>(px, 1);
+    for (DevBuf* b : {&c->d_gpos, &c->d_gnrm, &c->d_gray_a, &c->d_gray_b, &c->d_ghits})
+        if ((r = dev_alloc(c, *b, n * 16))) return r;
+    if ((r = dev_alloc(c, c->d_gmodel, n * 4)) || (r = dev_alloc(c, c->d_ghead, ((size_t)32 + kHeadWordsPerQueue) * 4))) return r;
+    c->guides_valid = false;
+    if (px)
+    {
+        const pt_config& g = c->cfg;
+        RenderParams rp{};
+        rp.width = g.width;
+        rp.height = g.height;
+        rp.local_rows = (uint32_t)c->rows.size();
+        rp.local_pixels = px;
+        rp.rank = g.rank;
+        rp.world_size = g.world_size;
+        rp.strip_rows = g.strip_rows;
+        rp.first_sample = sample;
+        rp.n_sobol = g.n_sobol;
+        rp.seed = g.seed;
+        rp.div_width = fastdiv_make(rp.width);
+        rp.div_strip_rows = fastdiv_make(rp.strip_rows);
+        CameraView cam{};
+        std::memcpy(cam.ray_matrix, c->scene.camera.ray_matrix, 64);
+        cam.eye[0] = c->scene.camera.matrix.t.x;
+        cam.eye[1] = c->scene.camera.matrix.t.y;
+        cam.eye[2] = c->scene.camera.matrix.t.z;
+        const RayQueue q{(f4*)c->d_gray_a.p, (f4*)c->d_gray_b.p};
+        uint32_t* head = (uint32_t*)c->d_ghead.p;
+        HIPCHK(c, hipMemsetAsync(head, 0, c->d_ghead.bytes, c->stream));
+        launch_guide_rays(c->stream, rp, cam, q, head);
+        // (an empty world: every ray misses)
+        if (c->sv.world_root == MISS_ID) HIPCHK(c, hipMemsetAsync(c->d_ghits.p, 0xff, (size_t)px * 16, c->stream));
+        else launch_trace_rays_closest(c->stream, trace_launch(c), c->sv.world_root, q, px, head, (f4*)c->d_ghits.p);
+        launch_guide_resolve(c->stream, c->sv, px, cam, q, (const f4*)c->d_ghits.p, (f4*)c->d_gpos.p, (f4*)c->d_gnrm.p, (uint32_t*)c->d_gmodel.p);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    c->guides_valid = true;
+    c->guides_scene_version = c->scene_version;
+    c->guides_config_version = c->config_version;
+    c->guides_sample = sample;
+    return PT_OK;
+}
+
+int pt_read_guides(pt_ctx* c, float* position, float* normal, uint32_t* model)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->guides_valid) return fail(c, PT_ERR_STATE, "no guides: pt_render_guides first");
+    const size_t px = c->local_pixels;
+    if (!px) return PT_OK;
+    if (position) HIPCHK(c, hipMemcpyAsync(position, c->d_gpos.p, px * 16, hipMemcpyDeviceToHost, c->stream));
+    if (model) HIPCHK(c, hipMemcpyAsync(model, c->d_gmodel.p, px * 4, hipMemcpyDeviceToHost, c->stream));
+    std::vector<f4> nr(normal ? px : 0);
+    if (normal) HIPCHK(c, hipMemcpyAsync(nr.data(), c->d_gnrm.p, px * 16, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i < nr.size(); ++i) { normal[3 * i] = nr[i].x; normal[3 * i + 1] = nr[i].y; normal[3 * i + 2] = nr[i].z; }
+    return PT_OK;
+}
+
+int pt_denoise(pt_ctx* c, const pt_denoise_params* p, float* rgba)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    DenoiseK k{};
+    int r;
+    if ((r = denoise_params(c, p, k))) return r;
+    if (c->cfg.world_size != 1) return fail(c, PT_ERR_STATE, "pt_denoise needs the whole frame on one rank (the neighbourhoods cross row strips)");
+    if (!c->guides_valid) return fail(c, PT_ERR_STATE, "no guides: pt_render_guides first");
+    if (c->guides_scene_version != c->scene_version || c->guides_config_version != c->config_version)
+        return fail(c, PT_ERR_STATE, "the guides are stale (camera, scene, environment or configuration changed since pt_render_guides)");
+    if (!c->d_accum.p) return fail(c, PT_ERR_STATE, "nothing has been accumulated");
+    if ((r = ensure_device(c))) return r;
+    const size_t px = c->local_pixels;
+    if ((r = denoise_scratch(c, px)) || (r = dev_alloc(c, c->d_dn_out, px * 16))) return r;
+    const bool moments = (c->cfg.flags & PT_FLAG_ADAPTIVE) && c->moments_valid && c->d_moments.p;
+    launch_denoise(c->stream, (int)c->cfg.width, (int)c->cfg.height, k, (const f4*)c->d_accum.p, moments ? (const float*)c->d_moments.p : nullptr,
+                   (const f4*)c->d_gpos.p, (const f4*)c->d_gnrm.p, (const uint32_t*)c->d_gmodel.p, (f4*)c->d_dn_a.p, (f4*)c->d_dn_b.p,
+                   (f4*)c->d_dn_nv.p, (f4*)c->d_dn_out.p);
+    HIPCHK(c, hipGetLastError());
+    if (rgba) HIPCHK(c, hipMemcpyAsync(rgba, c->d_dn_out.p, px * 16, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->denoised_valid = true;
+    return PT_OK;
+}
+
+int pt_write_denoised_image(pt_ctx* c, const char* path)
+{
+    if (!c || !path) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->denoised_valid) return fail(c, PT_ERR_STATE, "no denoised frame: pt_denoise first");
+    std::vector<uint8_t> host;
+    int r = present_rgb8_locked(c, host, (const f4*)c->d_dn_out.p);
+    if (r) return r;
+    std::string err;
+    if (!write_png_rgb8(path, host.data(), c->cfg.width, c->cfg.height, &err)) return fail(c, PT_ERR_IO, err.c_str());
+    return PT_OK;
+}
+
+int pt_post_denoise(pt_ctx* c, uint32_t w, uint32_t h, const pt_denoise_params* p, const float* accum, const float* position, const float* normal,
+                    const uint32_t* model, const float* sumsq, float* out)
+{
+    if (!c) return PT_ERR_ARG;
+    if (!accum || !position || !normal || !model || !out || !w || !h) return fail(c, PT_ERR_ARG, "pt_post_denoise: null image or empty size");
+    if ((uint64_t)w * h > 0x7fffffffull) return fail(c, PT_ERR_ARG, "pt_post_denoise: image too large");
+    std::lock_guard<std::mutex> lk(c->mu);
+    DenoiseK k{};
+    int r;
+    if ((r = denoise_params(c, p, k))) return r;
+    if ((r = ensure_device(c))) return r;
+    Staging t(c);
+    const size_t px = (size_t)w * h;
+    std::vector<f4> nr(px);
+    for (size_t i = 0; i < px; ++i) nr[i] = f4{normal[3 * i], normal[3 * i + 1], normal[3 * i + 2], 0.0f};
+    const f4* da = (const f4*)t.in(accum, px * 16);
+    const f4* dp = (const f4*)t.in(position, px * 16);
+    const f4* dn = (const f4*)t.in(nr.data(), px * 16);
+    const uint32_t* dm = (const uint32_t*)t.in(model, px * 4);
+    const float* dq = sumsq ? (const float*)t.in(sumsq, px * 4) : nullptr;
+    f4* dout = (f4*)t.out(px * 16);
+    if (t.err) return t.err;
+    if ((r = denoise_scratch(c, px))) return r;
+    launch_denoise(c->stream, (int)w, (int)h, k, da, dq, dp, dn, dm, (f4*)c->d_dn_a.p, (f4*)c->d_dn_b.p, (f4*)c->d_dn_nv.p, dout);
+    HIPCHK(c, hipGetLastError());
+    return t.download(out, dout, px * 16);
 }
 
 // ---- unit hooks

@@ -97,6 +97,23 @@ void launch_post_tonemap(hipStream_t s, uint32_t n, const f4* accum, f4* out);
 void launch_post_rgb8(hipStream_t s, uint32_t n, const f4* accum, uint8_t* out);
 void launch_post_deinterleave(hipStream_t s, uint32_t w, uint32_t h, uint32_t world, uint32_t strip, uint32_t pad_rows, const f4* parts, f4* full);
 
+// edge-aware a-trous denoiser (pt_denoise, pt_post_denoise; the definition is include/pt_api.h's), validated by the host
+struct DenoiseK
+{
+    float sigma_l, sigma_x;
+    uint32_t log2_sigma_n; // max(0, n_p . n_q) is squared this many times
+    uint32_t iterations;   // 1..8
+};
+// guides of a w x h image: position xyz | t, normal xyz | -, model (MISS_ID = miss); moments null = spatial variance.  Works in the three
+// scratch images cv_a, cv_b (colour | variance) and nv (normal | valid) and writes the result (c, 1) or (0, 0, 0, 0) to out
+void launch_denoise(hipStream_t s, int w, int h, const DenoiseK& p, const f4* accum, const float* moments, const f4* position, const f4* normal,
+                    const uint32_t* model, f4* cv_a, f4* cv_b, f4* nv, f4* out);
+// the camera rays of sample rp.first_sample of every local pixel into a hook queue (ray index = local pixel), n_and_heads[0] <- local pixels
+void launch_guide_rays(hipStream_t s, const RenderParams& rp, const CameraView& cam, RayQueue rq, uint32_t* n_and_heads);
+// their launch_trace_rays_closest hits -> position, normal, model guides
+void launch_guide_resolve(hipStream_t s, const SceneView& sv, uint32_t n, const CameraView& cam, RayQueue rq, const f4* hits, f4* position, f4* normal,
+                          uint32_t* model);
+
 // unit hooks
 // n_and_heads: word 0 = number of rays, words [32, 32 + kHeadWordsPerQueue) = zeroed claim cursors
 void launch_trace_rays_closest(hipStream_t s, const TraceLaunch& tl, uint32_t root, RayQueue rq, uint32_t n, uint32_t* n_and_heads, f4* hits);

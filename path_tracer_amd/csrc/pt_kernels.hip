@@ -2641,6 +2641,50 @@ __global__ void k_volume_probe(const SceneView sv, int material, uint32_t n, con
     o[8] = (float)(rng.k - draws);
 }
 
+// ------------------------------------------------------------------------------------------------ denoiser guides (pt_render_guides)
+// The camera ray of sample rp.first_sample of EVERY local pixel (no active rectangle: a ray outside it is answered by the root-box test)
+// as one ray of a hook queue, ray index = local pixel: exactly the ray k_generate makes for that (pixel, sample).
+__global__ void __launch_bounds__(256) k_guide_rays(const RenderParams rp, const CameraView cam, const RayQueue rq, uint32_t* __restrict__ n_and_heads)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i == 0u) n_and_heads[0] = rp.local_pixels;
+    if (i >= rp.local_pixels) return;
+    const uint32_t ly = fastdiv(i, rp.div_width), x = i - ly * rp.width;
+    const f3 dir = camera_ray_dir(rp, cam, x, global_row(rp, ly), rp.first_sample);
+    rq.a[i] = f4{cam.eye[0], cam.eye[1], cam.eye[2], __builtin_inff()};
+    rq.b[i] = f4{dir.x, dir.y, dir.z, asf(i)};
+}
+
+// first-hit guides of those rays: position r.at(t) | t as the render keeps it (r.at(1e5) | 1e5 for a miss, integrator.rs:156), the
+// face-forwarded world shading normal of the hit (HitInfo's, primitive.rs:161-165 + tlas.rs:105; 0 for a miss) and the hit's model
+// (BLAS index, MISS_ID for a miss) in full: its low byte is the id byte of main.rs:206
+__global__ void __launch_bounds__(256) k_guide_resolve(const SceneView sv, const uint32_t n, const CameraView cam, const RayQueue rq,
+                                                       const f4* __restrict__ hits, f4* __restrict__ position, f4* __restrict__ normal,
+                                                       uint32_t* __restrict__ model)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const f4 hit = hits[i];
+    const f3 d = xyz(rq.b[i]);
+    const f3 eye{cam.eye[0], cam.eye[1], cam.eye[2]};
+    const uint32_t hid = asu(hit.w);
+    if (hid == MISS_ID)
+    {
+        const f3 far = fma3(d, bc3(1e5f), eye);
+        position[i] = f4{far.x, far.y, far.z, 1e5f};
+        normal[i] = f4{0.0f, 0.0f, 0.0f, 0.0f};
+        model[i] = MISS_ID;
+        return;
+    }
+    const uint32_t inst = hid >> sv.prim_bits, tri = hid & ((1u << sv.prim_bits) - 1u);
+    bool front;
+    const f3 nrm = hit_normal(sv, inst, tri, hit.y, hit.z, d, front);
+    const f3 p = fma3(d, bc3(hit.x), eye);
+    position[i] = f4{p.x, p.y, p.z, hit.x};
+    normal[i] = f4{nrm.x, nrm.y, nrm.z, 0.0f};
+    model[i] = sv.instances[inst].blas;
+}
+
 } // namespace
 
 // ================================================================================================ launchers
@@ -2957,6 +3001,16 @@ void launch_volume_probe(hipStream_t s, const SceneView& sv, int material, uint3
                          const uint32_t* pixel, const uint32_t* sample, uint32_t draws, uint64_t seed, float* out9)
 {
     hipLaunchKernelGGL(k_volume_probe, dim3((n + 255u) / 256u), dim3(256), 0, s, sv, material, n, incoming, t_max, dist, pixel, sample, draws, seed, out9);
+}
+
+void launch_guide_rays(hipStream_t s, const RenderParams& rp, const CameraView& cam, RayQueue rq, uint32_t* n_and_heads)
+{
+    hipLaunchKernelGGL(k_guide_rays, dim3((rp.local_pixels + 255u) / 256u), dim3(256), 0, s, rp, cam, rq, n_and_heads);
+}
+void launch_guide_resolve(hipStream_t s, const SceneView& sv, uint32_t n, const CameraView& cam, RayQueue rq, const f4* hits, f4* position, f4* normal,
+                          uint32_t* model)
+{
+    hipLaunchKernelGGL(k_guide_resolve, dim3((n + 255u) / 256u), dim3(256), 0, s, sv, n, cam, rq, hits, position, normal, model);
 }
 
 } // namespace pt

@@ -6,11 +6,14 @@
 //   k_post_reproject    src/shaders/compute.wgsl:103-212      3x3 YCoCg variance clip, Catmull-Rom history, id disocclusion, 15 % blend
 //   k_post_tonemap      src/shaders/shader.wgsl:3-33,59-64    Uchimura "GT" curve on accumulation.rgb / accumulation.w
 //   k_post_rgb8         src/image_helper.rs:41-48 + src/image_helper/tonemapping.rs   the 8-bit gamma-2.2 image write_image saves
+//   k_dn_*              (no reference counterpart) pt_denoise's edge-aware a-trous filter on the accumulation and the first-hit guides
 //
 // WGSL leaves bilinear filter weights, mat*vec summation order, pow/exp precision and out-of-range casts to the GPU.  Here
 // they are exact binary32 operations in the written order, pow(x, c) = exp(c ln x) with pt_math.h's routines, saturating
 // casts, out-of-bounds textureLoad = 0 — the same definitions the oracle uses, so the two agree bit for bit.
 #include <hip/hip_runtime.h>
+
+#include <utility>
 
 #include "pt_kernels.h"
 
@@ -239,7 +242,187 @@ __global__ void __launch_bounds__(256) k_post_deinterleave(uint32_t w, uint32_t 
     full[i] = parts[((size_t)rank * pad_rows + ly) * w + x];
 }
 
+// ---- edge-aware a-trous denoiser (pt_denoise / pt_post_denoise): SVGF's spatial filter, every operation in the order include/pt_api.h
+// states.  One thread per pixel in 16 x 16 workgroups; what a tap reads is three 16-byte loads (colour | variance, position | t,
+// normal | valid) and the model word.  Per-pixel divisors are hoisted out of the tap loops; one exp_det per tap.
+constexpr float kDenoiseEps = 1e-6f;
+__device__ __forceinline__ float dn_lum(f4 c) { return (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z; }
+// max(0, n_p . n_q)^(2^log2_sn) and the plane term a_x = |n_p . (x_q - x_p)| / (sigma_x * |x_q - x_p|) (0 where x_q == x_p) of two hits
+__device__ __forceinline__ float dn_normal_w(f4 np, f4 nq, uint32_t log2_sn)
+{
+    const float nd = (np.x * nq.x + np.y * nq.y) + np.z * nq.z;
+    float wn = nd > 0.0f ? nd : 0.0f;
+    for (uint32_t k = 0; k < log2_sn; ++k) wn = wn * wn;
+    return wn;
+}
+__device__ __forceinline__ float dn_plane(f4 np, f4 xp, f4 xq, float sigma_x)
+{
+    const float dx = xq.x - xp.x, dy = xq.y - xp.y, dz = xq.z - xp.z;
+    const float d2 = (dx * dx + dy * dy) + dz * dz;
+    return d2 > 0.0f ? fabsf((np.x * dx + np.y * dy) + np.z * dz) / (sigma_x * sqrtf(d2)) : 0.0f;
+}
+
+// colour = acc.rgb / acc.w, variance = the adaptive criterion's e2 (moments) or 0 (the spatial pass fills it in), valid = acc.w != 0
+__global__ void __launch_bounds__(256) k_dn_prep(uint32_t n, const f4* __restrict__ accum, const float* __restrict__ moments, const f4* __restrict__ normal,
+                                                 f4* __restrict__ cv, f4* __restrict__ nv)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const f4 a = accum[i];
+    if (a.w == 0.0f)
+    {
+        cv[i] = f4{0.0f, 0.0f, 0.0f, 0.0f};
+        nv[i] = f4{0.0f, 0.0f, 0.0f, 0.0f};
+        return;
+    }
+    float var = 0.0f;
+    if (moments)
+    {
+        const float m = dn_lum(a) / a.w;
+        float v = moments[i] / a.w - m * m;
+        if (!(v > 0.0f)) v = 0.0f;
+        var = v / a.w;
+    }
+    const f4 nr = normal[i];
+    cv[i] = f4{a.x / a.w, a.y / a.w, a.z / a.w, var};
+    nv[i] = f4{nr.x, nr.y, nr.z, 1.0f};
+}
+
+// variance of l over the 7 x 7 neighbourhood, taps weighted by the model, normal and plane terms (no luminance term)
+__global__ void __launch_bounds__(256) k_dn_spatial_var(int w, int h, const DenoiseK p, const f4* __restrict__ cv_in, const f4* __restrict__ pos,
+                                                        const f4* __restrict__ nv, const uint32_t* __restrict__ model, f4* __restrict__ cv_out)
+{
+    const int x = blockIdx.x * 16 + threadIdx.x, y = blockIdx.y * 16 + threadIdx.y;
+    if (x >= w || y >= h) return;
+    const size_t i = (size_t)y * w + x;
+    const f4 cp = cv_in[i], np = nv[i];
+    if (np.w == 0.0f) { cv_out[i] = f4{0.0f, 0.0f, 0.0f, 0.0f}; return; }
+    const uint32_t mp = model[i];
+    const bool hit = mp != MISS_ID;
+    const f4 xp = pos[i];
+    float sw = 0.0f, sl = 0.0f, sll = 0.0f;
+    for (int dy = -3; dy <= 3; ++dy)
+    {
+        const int yy = y + dy;
+        if (yy < 0 || yy >= h) continue;
+        for (int dx = -3; dx <= 3; ++dx)
+        {
+            const int xx = x + dx;
+            if (xx < 0 || xx >= w) continue;
+            const size_t q = (size_t)yy * w + xx;
+            float wt = 1.0f;
+            if (dx != 0 || dy != 0)
+            {
+                const f4 nq = nv[q];
+                if (nq.w == 0.0f || model[q] != mp) continue;
+                if (hit) wt = dn_normal_w(np, nq, p.log2_sigma_n) * exp_det(-dn_plane(np, xp, pos[q], p.sigma_x));
+            }
+            const float l = dn_lum(cv_in[q]);
+            sw = sw + wt;
+            sl = sl + wt * l;
+            sll = sll + wt * (l * l);
+        }
+    }
+    const float mu = sl / sw;
+    float v = sll / sw - mu * mu;
+    if (!(v > 0.0f)) v = 0.0f;
+    cv_out[i] = f4{cp.x, cp.y, cp.z, v};
+}
+
+// one a-trous level, step s: g = 3 x 3 binomial blur of the variance, then the 5 x 5 B3-spline taps p + s (dx, dy) with edge-stopping weights.
+// FINAL writes the result (c', 1) / (0, 0, 0, 0) instead of (c', var')
+template <bool FINAL>
+__global__ void __launch_bounds__(256) k_dn_level(int w, int h, int s, const DenoiseK p, const f4* __restrict__ cv_in, const f4* __restrict__ pos,
+                                                  const f4* __restrict__ nv, const uint32_t* __restrict__ model, f4* __restrict__ cv_out)
+{
+    const int x = blockIdx.x * 16 + threadIdx.x, y = blockIdx.y * 16 + threadIdx.y;
+    if (x >= w || y >= h) return;
+    const size_t i = (size_t)y * w + x;
+    const f4 cp = cv_in[i], np = nv[i];
+    if (np.w == 0.0f) { cv_out[i] = f4{0.0f, 0.0f, 0.0f, 0.0f}; return; }
+    const uint32_t mp = model[i];
+    const bool hit = mp != MISS_ID;
+    const f4 xp = pos[i];
+    const float kb[3] = {0.25f, 0.5f, 0.25f};
+    float sg = 0.0f, sk = 0.0f;
+    for (int dy = -1; dy <= 1; ++dy)
+    {
+        const int yy = y + dy;
+        if (yy < 0 || yy >= h) continue;
+        for (int dx = -1; dx <= 1; ++dx)
+        {
+            const int xx = x + dx;
+            if (xx < 0 || xx >= w) continue;
+            const size_t q = (size_t)yy * w + xx;
+            if ((dx != 0 || dy != 0) && (nv[q].w == 0.0f || model[q] != mp)) continue;
+            const float k = kb[dx + 1] * kb[dy + 1];
+            sg = sg + k * cv_in[q].w;
+            sk = sk + k;
+        }
+    }
+    const float g = sg / sk;
+    const float inv = 1.0f / (p.sigma_l * sqrtf(g) + kDenoiseEps);
+    const float lp = dn_lum(cp);
+    const float hk[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
+    float sw = 0.0f, sr = 0.0f, sgc = 0.0f, sb = 0.0f, sv = 0.0f;
+    for (int dy = -2; dy <= 2; ++dy)
+    {
+        const int yy = y + s * dy;
+        if (yy < 0 || yy >= h) continue;
+        for (int dx = -2; dx <= 2; ++dx)
+        {
+            const int xx = x + s * dx;
+            if (xx < 0 || xx >= w) continue;
+            const size_t q = (size_t)yy * w + xx;
+            const f4 cq = cv_in[q];
+            float e = 1.0f;
+            if (dx != 0 || dy != 0)
+            {
+                const f4 nq = nv[q];
+                if (nq.w == 0.0f || model[q] != mp) continue;
+                const float al = fabsf(lp - dn_lum(cq)) * inv;
+                if (hit) e = dn_normal_w(np, nq, p.log2_sigma_n) * exp_det(-(dn_plane(np, xp, pos[q], p.sigma_x) + al));
+                else e = exp_det(-al);
+            }
+            const float wt = (hk[dx + 2] * hk[dy + 2]) * e;
+            sw = sw + wt;
+            sr = sr + wt * cq.x;
+            sgc = sgc + wt * cq.y;
+            sb = sb + wt * cq.z;
+            sv = sv + (wt * wt) * cq.w;
+        }
+    }
+    const f4 c{sr / sw, sgc / sw, sb / sw, 0.0f};
+    cv_out[i] = FINAL ? f4{c.x, c.y, c.z, 1.0f} : f4{c.x, c.y, c.z, sv / (sw * sw)};
+}
+
 } // namespace
+
+void launch_denoise(hipStream_t s, int w, int h, const DenoiseK& p, const f4* accum, const float* moments, const f4* position, const f4* normal,
+                    const uint32_t* model, f4* cv_a, f4* cv_b, f4* nv, f4* out)
+{
+    const uint32_t n = (uint32_t)w * (uint32_t)h;
+    const dim3 tile(16, 16), grid((w + 15) / 16, (h + 15) / 16);
+    hipLaunchKernelGGL(k_dn_prep, dim3((n + 255u) / 256u), dim3(256), 0, s, n, accum, moments, normal, cv_a, nv);
+    f4* cur = cv_a;
+    f4* other = cv_b;
+    if (!moments)
+    {
+        hipLaunchKernelGGL(k_dn_spatial_var, grid, tile, 0, s, w, h, p, (const f4*)cv_a, position, (const f4*)nv, model, cv_b);
+        std::swap(cur, other);
+    }
+    for (uint32_t it = 0; it < p.iterations; ++it)
+    {
+        const int step = 1 << it;
+        if (it + 1u == p.iterations)
+            hipLaunchKernelGGL(k_dn_level<true>, grid, tile, 0, s, w, h, step, p, (const f4*)cur, position, (const f4*)nv, model, out);
+        else
+        {
+            hipLaunchKernelGGL(k_dn_level<false>, grid, tile, 0, s, w, h, step, p, (const f4*)cur, position, (const f4*)nv, model, other);
+            std::swap(cur, other);
+        }
+    }
+}
 
 void launch_post_deinterleave(hipStream_t s, uint32_t w, uint32_t h, uint32_t world, uint32_t strip, uint32_t pad_rows, const f4* parts, f4* full)
 {

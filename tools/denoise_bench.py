@@ -1,0 +1,94 @@
+"""Denoiser record (profiles/r07_denoise.md): quality and cost of pt_render_guides + pt_denoise.
+
+Quality: RMSE of the noisy mean and of the denoised frame against a many-sample render of the same scene, for several sample counts and
+both variance sources (spatial variance; moments of PT_FLAG_ADAPTIVE), in linear radiance and in display space (the library's own GT tonemap,
+what pt_present shows).  The noisy frames use samples after the reference's, so the two are independent.
+Timing: wall clock of the blocking calls at the given size (median of --reps), guides and the filter separately.
+
+    python tools/denoise_bench.py [--size 256] [--ref-spp 4096] [--spp 1,4,16,64] [--width 1920 --height 1080 --reps 20] [--out file.json]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def rmse(a, b):
+    return float(np.sqrt(np.mean((a[..., :3].astype(np.float64) - b[..., :3].astype(np.float64)) ** 2)))
+
+
+def quality(api, scenes, name, size, ref_spp, spps, depth):
+    sc = {"cornell": scenes.cornell_box, "mixed": scenes.cornell_mixed}[name](size, size)
+    ref = api.Renderer(sc, size, size, max_bounces=depth)
+    racc, _, _ = ref.render(0, ref_spp, want_position=False)
+    ref_mean = racc / racc[..., 3:4]
+    ref_disp = ref.post_tonemap(racc)
+    rows = []
+    for spp in spps:
+        for flags, source in ((0, "spatial"), (api.FLAG_ADAPTIVE, "moments")):
+            r = api.Renderer(sc, size, size, max_bounces=depth, flags=flags)
+            acc, _, _ = r.render(ref_spp, spp, want_position=False)
+            r.render_guides(ref_spp + spp - 1)
+            den = r.denoise()
+            noisy = acc / acc[..., 3:4]
+            row = dict(scene=name, size=size, spp=spp, variance=source, rmse_noisy=rmse(noisy, ref_mean), rmse_denoised=rmse(den, ref_mean),
+                       display_rmse_noisy=rmse(r.post_tonemap(acc), ref_disp), display_rmse_denoised=rmse(r.post_tonemap(den), ref_disp))
+            row["ratio"] = row["rmse_denoised"] / row["rmse_noisy"]
+            row["display_ratio"] = row["display_rmse_denoised"] / row["display_rmse_noisy"]
+            print(json.dumps(row), flush=True)
+            rows.append(row)
+            r.close()
+    ref.close()
+    return rows
+
+
+def timing(api, scenes, w, h, reps, depth):
+    out = {}
+    for flags, source in ((0, "spatial"), (api.FLAG_ADAPTIVE, "moments")):
+        r = api.Renderer(scenes.cornell_box(w, h), w, h, max_bounces=depth, flags=flags)
+        r.render(0, 1, want_position=False)
+        tg, td = [], []
+        for k in range(reps + 2):
+            t0 = time.perf_counter(); r.render_guides(k); t1 = time.perf_counter()
+            r.denoise(download=False); t2 = time.perf_counter()
+            if k >= 2:
+                tg.append(t1 - t0); td.append(t2 - t1)
+        out[source] = dict(ms_guides=1e3 * float(np.median(tg)), ms_denoise=1e3 * float(np.median(td)))
+        r.close()
+    row = dict(width=w, height=h, reps=reps, **{f"{k}_{s}": v for s, d in out.items() for k, v in d.items()})
+    print(json.dumps(row), flush=True)
+    return row
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--size", type=int, default=256)
+    ap.add_argument("--ref-spp", type=int, default=4096)
+    ap.add_argument("--spp", default="1,4,16,64")
+    ap.add_argument("--scenes", default="cornell,mixed")
+    ap.add_argument("--bounces", type=int, default=3)
+    ap.add_argument("--width", type=int, default=1920)
+    ap.add_argument("--height", type=int, default=1080)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--no-quality", action="store_true")
+    ap.add_argument("--out")
+    a = ap.parse_args()
+    from path_tracer_amd import api, scenes
+    res = dict(quality=[], timing=None)
+    if not a.no_quality:
+        for name in a.scenes.split(","):
+            res["quality"] += quality(api, scenes, name, a.size, a.ref_spp, [int(s) for s in a.spp.split(",")], a.bounces)
+    if a.reps > 0:
+        res["timing"] = timing(api, scenes, a.width, a.height, a.reps, a.bounces)
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
