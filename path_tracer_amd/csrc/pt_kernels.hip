@@ -66,6 +66,18 @@ namespace {
 #ifndef PT_WAVES_GLOBAL_BVH_ANY
 #define PT_WAVES_GLOBAL_BVH_ANY 5
 #endif
+// One-ray walk (IDENT kernels), BVH in LDS: SIX workgroups of 256 per CU (six waves per SIMD), set as the cap of the resident grid (resident_grid), not as
+// the compiler's bound.  Built without fp32 pairing (csrc/Makefile) these kernels take 64-79 VGPRs and no scratch, so six fit — the "six is slower" above was
+// measured with 64-120 B of scratch.  Same-box A/B, Cornell frame, six runs each (profiles/r08_fp32_pairing.md): grid capped at five 53.79-54.22 ms, at six
+// 53.35-53.67; rank 0's 1/8 share 8.33-8.57 -> 8.21-8.25; one pipeline, k_trace_fused per launch 2506 -> 2340 us, the primary k_closest the same at either.
+// __launch_bounds__(256, 6) on top of the cap changes no instruction of these kernels (register names in a handful) and was SLOWER in every run, 54.66-55.25:
+// the bound stays at five, the wave count is pinned from above here and watched from below by tools/resource_table.py.
+// Six workgroups per CU need <= 26.6 KB of LDS each (the Cornell blob plus stacks: ~24 KB); larger scenes run what fits.
+#ifndef PT_TRACE_WAVES_LDS_IDENT
+#define PT_TRACE_WAVES_LDS_IDENT 6
+#endif
+// waves per SIMD a traversal kernel's resident grid is capped at (0: whatever the runtime reports for its registers and LDS)
+constexpr uint32_t trace_waves_cap(bool lds, bool ident) { return lds && ident ? PT_TRACE_WAVES_LDS_IDENT : 0; }
 // branch levels expanded per traversal step of k_closest (1 = one node per step)
 #ifndef PT_BRANCH_LEVELS
 #define PT_BRANCH_LEVELS 4
@@ -117,7 +129,7 @@ namespace {
 #endif
 // threads per shading workgroup (a workgroup makes one reservation per queue and iteration: block_append4)
 // waves per SIMD the surface shading kernels must leave room for (1: whatever the registers they want allow — 102-130 VGPRs: four, GGX with volumes three).
-// Five: the Lambertian kernel fits 96 VGPRs without scratch.  Round 3 measured that at FOUR traversal waves: the pass's own launches 22.39 -> 22.26 ms, the
+// Five: the Lambertian kernel fits 96 VGPRs without scratch (90-95 since round 8; with the inline shadow walk 90, where SLP pairing had cost 52 B of scratch).  Round 3 measured that at FOUR traversal waves: the pass's own launches 22.39 -> 22.26 ms, the
 // two-pipeline frame +1 ms.  Round 4, traversal kernels at five waves: one pipeline 62.35 -> 62.63 ms (nothing), but the default two-pipeline frame
 // 61.2 -> 59.0 ms and mixed materials 72.8 -> 70.0 ms: the fifth wave lets one pipeline's shading pass run beside the other's traversal.  Six (80 VGPRs, 60 B
 // of scratch): 64.4 / 76.0 ms.
@@ -125,13 +137,14 @@ namespace {
 #define PT_SHADE_WAVES 5
 #endif
 #ifndef PT_SHADE_WAVES_DIEL
-#define PT_SHADE_WAVES_DIEL 5   // (16 B of scratch)
+#define PT_SHADE_WAVES_DIEL 5   // (93 VGPRs, no scratch since the build dropped fp32 pairing: profiles/r08_fp32_pairing.md)
 #endif
 #ifndef PT_SHADE_WAVES_GGX
-#define PT_SHADE_WAVES_GGX 5    // (64 B of scratch, and still better than four waves: mixed materials 71.5 -> 70.3 ms)
+#define PT_SHADE_WAVES_GGX 5    // (better than four waves even with the 64 B of scratch it had until round 8: mixed materials 71.5 -> 70.3 ms; now 96 VGPRs, no scratch)
 #endif
 #ifndef PT_SHADE_WAVES_VOLUMES
-#define PT_SHADE_WAVES_VOLUMES 4 // kernels of scenes with participating media (five: 32-104 B of scratch; media scene 47.2 -> 48.7 ms)
+#define PT_SHADE_WAVES_VOLUMES 4 // kernels of scenes with participating media (five: 32-104 B of scratch; media scene 47.2 -> 48.7 ms.  Without fp32 pairing the specular and
+                                 // dielectric ones fit 96 VGPRs without scratch, the Lambertian and GGX ones want 113-120: cornell_media at 256 spp 163.2 / 163.8 ms at four, 164.2 / 163.8 at five)
 #endif
 constexpr int shade_waves(uint32_t qclass, bool volumes)
 {
@@ -2697,13 +2710,13 @@ void launch_generate(hipStream_t s, const RenderParams& rp, const CameraView& ca
 
 // A persistent grid must be RESIDENT: workgroups that the device cannot hold at once start only when others have left, and by then
 // the queue's dynamic part is gone and the late-comers' static chunks are the launch's tail.  So the grid is what the kernel's
-// registers and LDS allow per CU (asked of the runtime once per kernel variant and LDS size), times the CU count, capped by
-// tl.grid_blocks (the spill area is sized for that).
+// registers and LDS allow per CU (asked of the runtime once per kernel variant and LDS size; at most waves_cap waves per SIMD where the
+// kernel's wave count is pinned: trace_waves_cap), times the CU count, capped by tl.grid_blocks (the spill area is sized for that).
 #ifndef PT_RESIDENT_GRID
 #define PT_RESIDENT_GRID 1
 #endif
 template <typename K>
-static uint32_t resident_grid(K kernel, const TraceLaunch& tl, size_t lds)
+static uint32_t resident_grid(K kernel, const TraceLaunch& tl, size_t lds, uint32_t waves_cap)
 {
 #if PT_RESIDENT_GRID
     struct Key { const void* f; uint32_t threads; size_t lds; int dev; int per_cu; };
@@ -2711,13 +2724,15 @@ static uint32_t resident_grid(K kernel, const TraceLaunch& tl, size_t lds)
     static std::vector<Key> cache;
     int dev = 0;
     (void)hipGetDevice(&dev);
+    // a workgroup of block_threads threads is block_threads / 256 waves on each of the CU's four SIMDs
+    const uint32_t cap = waves_cap ? std::max(1u, waves_cap * 256u / tl.block_threads) : ~0u;
     std::lock_guard<std::mutex> lk(mu);
     for (const Key& k : cache)
-        if (k.f == (const void*)kernel && k.threads == tl.block_threads && k.lds == lds && k.dev == dev) return std::min<uint32_t>(tl.grid_blocks, tl.n_cus * (uint32_t)k.per_cu);
+        if (k.f == (const void*)kernel && k.threads == tl.block_threads && k.lds == lds && k.dev == dev) return std::min<uint32_t>(tl.grid_blocks, tl.n_cus * std::min((uint32_t)k.per_cu, cap));
     int per_cu = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, (int)tl.block_threads, lds) != hipSuccess || per_cu < 1) per_cu = 1;
     cache.push_back(Key{(const void*)kernel, tl.block_threads, lds, dev, per_cu});
-    return std::min<uint32_t>(tl.grid_blocks, tl.n_cus * (uint32_t)per_cu);
+    return std::min<uint32_t>(tl.grid_blocks, tl.n_cus * std::min((uint32_t)per_cu, cap));
 #else
     return tl.grid_blocks;
 #endif
@@ -2751,10 +2766,10 @@ static void with_trace_variant(const TraceLaunch& tl, bool ident, F&& f)
 }
 // a persistent traversal grid (resident_grid, per kernel) with the launch's dynamic LDS
 template <typename K, typename... A>
-static void launch_resident(K kernel, const TraceLaunch& tl, hipStream_t s, const A&... args)
+static void launch_resident(K kernel, uint32_t waves_cap, const TraceLaunch& tl, hipStream_t s, const A&... args)
 {
     const size_t lds = trace_lds_bytes(tl);
-    hipLaunchKernelGGL(kernel, dim3(resident_grid(kernel, tl, lds)), dim3(tl.block_threads), lds, s, args...);
+    hipLaunchKernelGGL(kernel, dim3(resident_grid(kernel, tl, lds, waves_cap)), dim3(tl.block_threads), lds, s, args...);
 }
 
 template <int MODE>
@@ -2763,7 +2778,7 @@ static void launch_closest_impl(hipStream_t s, const TraceLaunch& tl, uint32_t r
 {
     const ClosestKArgs ka{tl.scene, (const uint4*)tl.blob, rq.a, rq.b, n_ptr, heads, root, cap_in, out};
     with_trace_variant(tl, ident_walk(tl, tlas_bits(tl, root, MODE == CLOSEST_LIGHTS)), [&](auto bvh, auto spill, auto ident) {
-        launch_resident(k_closest<bvh, MODE, spill, ident>, tl, s, ka);
+        launch_resident(k_closest<bvh, MODE, spill, ident>, trace_waves_cap(bvh != 0, ident), tl, s, ka);
     });
 }
 template <int MODE>
@@ -2772,7 +2787,7 @@ static void launch_any_impl(hipStream_t s, const TraceLaunch& tl, uint32_t root,
 {
     const uint4* blob = (const uint4*)tl.blob;
     with_trace_variant(tl, ident_walk(tl, tlas_bits(tl, root, false)), [&](auto bvh, auto spill, auto ident) {
-        launch_resident(k_any<bvh, MODE, spill, ident>, tl, s, tl.scene, blob, root, rq.a, rq.b, n_ptr, cap_in, heads, occluded, radiance);
+        launch_resident(k_any<bvh, MODE, spill, ident>, trace_waves_cap(bvh != 0, ident), tl, s, tl.scene, blob, root, rq.a, rq.b, n_ptr, cap_in, heads, occluded, radiance);
     });
 }
 
@@ -2844,7 +2859,7 @@ void launch_trace_fused(hipStream_t s, const TraceLaunch& tl, const WavefrontBuf
     fa.world_root = tl.scene.world_root; fa.lights_root = tl.scene.lights_root; fa.cap_in = wb.cap_slots;
     const FusedKArgs ka{tl.scene, (const uint4*)tl.blob, fa, wout, lout};
     with_trace_variant(tl, ident_walk(tl, IDENT_TLAS_WORLD | IDENT_TLAS_LIGHTS), [&](auto bvh, auto spill, auto ident) {
-        launch_resident(k_trace_fused<bvh, spill, ident>, tl, s, ka);
+        launch_resident(k_trace_fused<bvh, spill, ident>, trace_waves_cap(bvh != 0, ident), tl, s, ka);
     });
 }
 void launch_trace_shadow(hipStream_t s, const TraceLaunch& tl, const WavefrontBuffers& wb, uint32_t b)

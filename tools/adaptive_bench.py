@@ -108,17 +108,19 @@ def run_config(name, uniform_spp, rels, growth, min_samples, cap_factor, records
     return uni, best
 
 
-def overhead(records, reps):
+def overhead(records, reps, scene="cornell_box", spp=256):
     """pt_render_adaptive with every pixel selected vs pt_render_device, Cornell 1080p x 256 spp; one context at a time (their pools
-    would not fit the device together), each warmed with the call it is timed with"""
-    sc = scenes.cornell_box(1920, 1080)
-    every = (256, 0.0, 0.0, 1 << 24, 0)
+    would not fit the device together), each warmed with the call it is timed with.  --overhead-scene cornell_mesh:6 is a scene whose
+    BVH stays in global memory: the adaptive path then runs k_shade_surface<LAMBERT, .., LIST> without the inline shadow walk."""
+    name, _, level = scene.partition(":")
+    sc = getattr(scenes, name)(1920, 1080, **({"level": int(level)} if level else {}))
+    every = (spp, 0.0, 0.0, 1 << 24, 0)
     cases = [("render", 0, False), ("render_flag", api.FLAG_ADAPTIVE, False), ("adaptive_all", api.FLAG_ADAPTIVE, True),
              ("render_nocull", api.FLAG_NO_PRIMARY_CULL, False), ("adaptive_all_nocull", api.FLAG_ADAPTIVE | api.FLAG_NO_PRIMARY_CULL, True)]
     t = {}
     for key, flags, adaptive in cases:
         r = api.Renderer(sc, 1920, 1080, max_bounces=8, flags=flags)
-        call = (lambda: r.render_adaptive(*every)) if adaptive else (lambda: r.render_device(0, 256))
+        call = (lambda: r.render_adaptive(*every)) if adaptive else (lambda: r.render_device(0, spp))
         call()
         t[key] = []
         for _ in range(reps):
@@ -130,7 +132,7 @@ def overhead(records, reps):
         r.close()
     med = {k: float(np.median(v)) for k, v in t.items()}
     pct = lambda a, b: round(100.0 * (med[a] / med[b] - 1.0), 2)
-    rec = {"what": "overhead", "config": "cornell 1920x1080 x 256 spp", "reps": reps, "ms": {k: [round(x, 2) for x in v] for k, v in t.items()},
+    rec = {"what": "overhead", "config": f"{scene} 1920x1080 x {spp} spp", "reps": reps, "ms": {k: [round(x, 2) for x in v] for k, v in t.items()},
            "median_ms": {k: round(v, 2) for k, v in med.items()}, "adaptive_all_vs_render_pct": pct("adaptive_all", "render"),
            "flag_vs_render_pct": pct("render_flag", "render"), "adaptive_all_vs_render_nocull_pct": pct("adaptive_all_nocull", "render_nocull")}
     records.append(emit(rec))
@@ -147,6 +149,8 @@ def main():
     ap.add_argument("--cap-factor", type=int, default=8, help="max_samples = cap-factor x the uniform spp")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--skip-overhead", action="store_true")
+    ap.add_argument("--overhead-scene", default="cornell_box", help="scene of the overhead measurement (scenes.NAME or NAME:level)")
+    ap.add_argument("--overhead-spp", type=int, default=256)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     records = []
@@ -156,7 +160,7 @@ def main():
         summary[name] = {"uniform_ms": uni["ms"], "uniform_paths": uni["paths"], "uniform_rmse": uni["rmse"],
                          "adaptive_equal_rmse": None if best is None else dict(best["equal_rmse"], rel_error=best["rel_error"])}
     if not a.skip_overhead:
-        overhead(records, a.reps)
+        overhead(records, a.reps, a.overhead_scene, a.overhead_spp)
     records.append(emit({"what": "summary", **summary}))
     if a.out:
         with open(a.out, "w") as f:

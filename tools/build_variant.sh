@@ -5,7 +5,7 @@ set -e
 cd "$(dirname "$0")/../path_tracer_amd/csrc"
 name=$1; shift
 mkdir -p ../../build/variants
-/opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fno-fast-math -fhip-fp32-correctly-rounded-divide-sqrt \
+/opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fno-fast-math -fhip-fp32-correctly-rounded-divide-sqrt -fno-slp-vectorize \
   -Wno-unused-parameter -Wno-missing-field-initializers "$@" -shared -o ../../build/variants/$name.so \
   -x hip pt_kernels.hip -x hip pt_post.hip -x hip pt_api.cpp -x hip pt_scene.cpp -x hip pt_png.cpp
 echo built build/variants/$name.so "$@"
