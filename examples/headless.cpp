@@ -7,6 +7,7 @@
 //   examples/headless --render FIRST COUNT [--load-state in.bin] [--save-state out.bin] ...   samples [FIRST, FIRST + COUNT) accumulated
 //       without the temporal pass; the frame's state (accumulation, first-hit position, id history) can be saved and picked up by another
 //       process: a long render stopped and continued (pt_read_frame / pt_write_accumulation)
+//   examples/headless ... --aperture A --focus F   thin lens of diameter A focused at distance F (default: the reference's pinhole, 0 and 950)
 //   examples/headless ... --denoise den.png   also writes the final frame through the edge-aware denoiser (guides of the last frame's sample)
 #include <chrono>
 #include <cstdio>
@@ -28,6 +29,7 @@ int main(int argc, char** argv)
     std::string models_dir = "models/cornell", out = "", load_state = "", save_state = "", denoise_out = "";
     bool render_mode = false;
     uint32_t render_first = 0, render_count = 0;
+    float aperture = 0.0f, focus = 950.0f; // main.rs:127's values: a pinhole
     for (int i = 1; i < argc; ++i)
     {
         const std::string a = argv[i];
@@ -43,6 +45,8 @@ int main(int argc, char** argv)
         else if (a == "--out") out = next("--out");
         else if (a == "--denoise") denoise_out = next("--denoise");
         else if (a == "--move") move = true;
+        else if (a == "--aperture") aperture = (float)std::atof(next("--aperture"));
+        else if (a == "--focus") focus = (float)std::atof(next("--focus"));
         else if (a == "--gpus") gpus = (uint32_t)std::atoi(next("--gpus"));
         else if (a == "--spp") spp = (uint32_t)std::atoi(next("--spp"));
         else if (a == "--render") { render_mode = true; render_first = (uint32_t)std::atoi(next("--render")); render_count = (uint32_t)std::atoi(next("--render")); }
@@ -55,7 +59,7 @@ int main(int argc, char** argv)
         }
         else if (a == "--help" || a == "-h")
         {
-            std::printf("usage: %s [--width W] [--height H] [--frames N] [--bounces B] [--move] [--models DIR] [--out file.png] [--denoise file.png]\n", argv[0]);
+            std::printf("usage: %s [--width W] [--height H] [--frames N] [--bounces B] [--move] [--models DIR] [--out file.png] [--denoise file.png] [--aperture A --focus F]\n", argv[0]);
             return 0;
         }
         else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
@@ -81,7 +85,7 @@ int main(int argc, char** argv)
 
         // Camera  main.rs:119-128
         const Vec3A look_from{0.0f, 50.0f, 1000.0f}, look_at{0.0f, 50.0f, 0.0f};
-        const Camera cam = Camera::New(look_from, look_at, 60.0f, (float)width / (float)height, 0.0f, 950.0f);
+        const Camera cam = Camera::New(look_from, look_at, 60.0f, (float)width / (float)height, aperture, focus);
         if (gpus > 0 || !devices.empty())
         {
             // several GPUs, one process: rows dealt to the devices in strips, one RCCL gather of the framebuffer (pt_multi)

@@ -134,7 +134,36 @@ int pt_camera_matrices(pt_ctx* ctx, float cam_to_world_3x4[12], float inv_proj_4
  * width*height*3 floats, row-major (the gamma-2.2 decode of load_image :25-33 is the caller's).  NULL / 0 restores the
  * reference's `Err` branch: constant ambient 0.006 (integrator.rs:263-266). */
 int pt_set_environment(pt_ctx* ctx, uint32_t width, uint32_t height, const float* rgb_linear);
-int pt_create_ray(pt_ctx* ctx, float s, float t, float o[3], float d[3]); /* host evaluation, for tests */
+int pt_create_ray(pt_ctx* ctx, float s, float t, float o[3], float d[3]); /* host evaluation, for tests; always the pinhole ray */
+
+/* ---- thin lens: Camera::new's 5th and 6th argument (camera.rs:17), which the reference reserves and never reads ------------------ */
+/* aperture = DIAMETER of the lens in world units, focus = distance of the plane of focus along the view axis.  aperture 0 (the default)
+ * IS the pinhole camera: the same rays, one stream draw consumed, the same kernels.  PT_ERR_ARG, before any device call, for a negative,
+ * NaN or infinite aperture, or with aperture > 0 a focus that is not finite and > 0.  The lens survives pt_set_camera and pt_camera_input;
+ * setting it makes the denoiser's guides stale like pt_set_camera, and pt_multi_* replicates it with the camera.
+ *
+ * With aperture > 0 "the camera ray of (pixel, sample)" is, everywhere (pt_render*, pt_frame, pt_render_adaptive, a miss's position
+ * r.at(1e5) | 1e5 and id 255, pt_render_guides, pt_multi_*), the following ray, in binary32 with every operation rounded once, no
+ * contraction, in this order.  eye, c0, c1 = translation and first two rotation columns of the camera matrix (pt_camera_matrices), M = the
+ * ray matrix (camera matrix * inverse projection):
+ *     seed     = draw 0 of the stream (pixel, sample)                                    -- main.rs:193
+ *     (jx, jy) = ss_sobol(n_sobol, sample, seed)                                        -- main.rs:194
+ *     u, v, ndc, the four sums r[i], rw = 1 / r[3], point = r.xyz * rw                  -- camera.rs:94-105, as the pinhole ray
+ *     q        = point - eye                                                            -- the pinhole ray before normalising
+ *     seed2    = draw 1 of the stream;  (lx, ly) = ss_sobol(n_sobol, sample, seed2)
+ *     rad = (aperture * 0.5f) * sqrt(lx);  phi = 6.2831855f * ly;  (sn, cs) = sincos_det(phi)
+ *     a = rad * cs;  b = rad * sn
+ *     o = eye + (c0 * a + c1 * b)                                                       -- per component
+ *     f = q * focus + eye                                                               -- per component, multiply then add
+ *     w = f - o;  d = w / sqrt((w.x * w.x + w.y * w.y) + w.z * w.z)                     -- glam's normalize
+ * and the path starts with TWO draws consumed (integrator.rs:153-161 with the rng one draw further).  q has axial component 1 (the
+ * projection's near plane), so f lies on the plane of focus: every lens ray of a pixel position passes through the same point there.
+ * The lens point is the polar map of a second Sobol point (sincos_det exists bit-exactly on host and device).
+ * Out of scope: polygonal apertures, motion blur, lens-aware denoiser weights (a defocused pixel's guides are one sample's hit). */
+int pt_set_lens(pt_ctx* ctx, float aperture, float focus);
+/* The camera ray of (global pixel = y * width + x, sample) as the render generates it, pinhole or lens, and the stream draws it consumed
+ * (1 or 2; draws may be NULL).  Host evaluation, no GPU. */
+int pt_primary_ray(pt_ctx* ctx, uint32_t pixel, uint32_t sample, float o[3], float d[3], uint32_t* draws);
 
 /* ---- the per-frame pixel loop  src/main.rs:181-207 + accumulate.wgsl:20-23 ------------------------------------- */
 /* Renders samples [first_sample, first_sample+n_samples) of every local pixel on the GPU and adds them, in sample
@@ -150,7 +179,8 @@ int pt_render(pt_ctx* ctx, uint32_t first_sample, uint32_t n_samples, float* dat
  * [rect[2], rect[2]+rect[3]) of this rank.  Every camera ray of a pixel outside it misses the world TLAS's root box (returned in
  * root_box as min xyz, max xyz when non-NULL), which is all TLAS::intersect would find out (tlas.rs:68-72): such pixels receive the miss
  * result of integrator.rs:263-266 without a path.  The whole frame when an environment map is set, when the box reaches behind the
- * image plane, or with PT_FLAG_NO_PRIMARY_CULL. */
+ * image plane, or with PT_FLAG_NO_PRIMARY_CULL.  Under a lens (pt_set_lens) the rectangle bounds the box as seen from every point of the
+ * lens, projected onto the plane of focus: wider than the pinhole's, still a proper part of the frame. */
 int pt_active_pixels(pt_ctx* ctx, uint32_t rect[4], float root_box[6]);
 /* same, results stay on the device (no host copy); *_dev may be NULL or device pointers of the sizes above */
 int pt_render_device(pt_ctx* ctx, uint32_t first_sample, uint32_t n_samples);

@@ -11,7 +11,7 @@
 //   Dielectric::new(colour, ior, volume)  material.rs:475    ptmi::Dielectric::New
 //   Model::new(path, material, matrices)  model.rs:36        ptmi::Model::New            (+ Model::FromTriangles for triangle soups)
 //   Scene::new(models)                    scene.rs:21        ptmi::Scene::New
-//   Camera::new(origin, target, fov, aspect, _, _)  camera.rs:17   ptmi::Camera::New
+//   Camera::new(origin, target, fov, aspect, aperture, focus)  camera.rs:17   ptmi::Camera::New (the thin lens the reference reserves)
 //   Camera::input(event, window, dt)      camera.rs:56       ptmi::Renderer::input
 //   the pixel loop + state.update(..)     main.rs:181-216    ptmi::Renderer::frame
 //   (cam.matrix * cam.inv_projection).inverse()  main.rs:128 ptmi::Renderer::inv_projection
@@ -124,7 +124,8 @@ struct Camera
 {
     Vec3A origin, target;
     float fov, aspect_ratio;
-    static Camera New(Vec3A origin, Vec3A target, float fov, float aspect_ratio, float /*aperture*/, float /*focus*/) { return {origin, target, fov, aspect_ratio}; }
+    float aperture, focus; // thin lens (pt_set_lens): lens DIAMETER in world units, 0 = pinhole; distance of the plane of focus
+    static Camera New(Vec3A origin, Vec3A target, float fov, float aspect_ratio, float aperture, float focus) { return {origin, target, fov, aspect_ratio, aperture, focus}; }
 };
 
 struct Frame
@@ -175,6 +176,7 @@ public:
     {
         const float eye[3] = {c.origin.x, c.origin.y, c.origin.z}, tgt[3] = {c.target.x, c.target.y, c.target.z};
         check(pt_set_camera(ctx_, eye, tgt, c.fov, c.aspect_ratio));
+        check(pt_set_lens(ctx_, c.aperture, c.focus));
     }
     // Camera::input: true where the reference's returns true
     bool input(pt_event event, float a, float b, float dt) { return check(pt_camera_input(ctx_, event, a, b, dt)) == 1; }
@@ -271,6 +273,7 @@ public:
         upload(c0, scene);
         const float eye[3] = {cam.origin.x, cam.origin.y, cam.origin.z}, tgt[3] = {cam.target.x, cam.target.y, cam.target.z};
         if (pt_set_camera(c0, eye, tgt, cam.fov, cam.aspect_ratio) < 0) throw Error(PT_ERR_STATE, pt_last_error(c0));
+        if (pt_set_lens(c0, cam.aperture, cam.focus) < 0) throw Error(PT_ERR_ARG, pt_last_error(c0));
     }
     ~MultiRenderer() { if (m_) pt_multi_destroy(m_); }
     MultiRenderer(const MultiRenderer&) = delete;

@@ -31,7 +31,7 @@ DEFAULT_SEED = 0x5EED5EED
 # every symbol include/pt_api.h declares
 EXPORTS = [
     "pt_create", "pt_destroy", "pt_last_error", "pt_set_config", "pt_add_material", "pt_add_model", "pt_add_model_obj", "pt_model_vertices", "pt_build", "pt_set_camera",
-    "pt_camera_matrices", "pt_set_environment", "pt_create_ray", "pt_render", "pt_render_device", "pt_reset_accumulation", "pt_accum_device_ptr",
+    "pt_camera_matrices", "pt_set_environment", "pt_create_ray", "pt_set_lens", "pt_primary_ray", "pt_render", "pt_render_device", "pt_reset_accumulation", "pt_accum_device_ptr",
     "pt_read_accumulation", "pt_read_frame", "pt_write_accumulation", "pt_render_samples", "pt_render_adaptive", "pt_adaptive_mask", "pt_read_moments", "pt_write_moments", "pt_active_pixels", "pt_local_rows", "pt_set_stream", "pt_synchronize", "pt_camera_input", "pt_camera_angles", "pt_frame", "pt_inv_projection", "pt_present", "pt_post_velocity", "pt_post_reproject", "pt_post_tonemap", "pt_post_rgb8", "pt_present_rgb8", "pt_write_image", "pt_trace_closest", "pt_trace_any",
     "pt_ss_sobol", "pt_math_batch", "pt_material_eval", "pt_volume_eval", "pt_blas_count", "pt_blas_dump", "pt_tlas_dump", "pt_tlas_instances", "pt_instance_materials", "pt_light_cdf",
     "pt_triangle_dump", "pt_get_stats", "pt_reset_stats", "pt_last_batch_counters", "pt_last_batch_shade_pids", "pt_last_batch_step_stats",
@@ -125,6 +125,8 @@ def lib():
         L.pt_camera_matrices.argtypes = [vp, vp, vp]
         L.pt_set_environment.argtypes = [vp, u32, u32, vp]
         L.pt_create_ray.argtypes = [vp, C.c_float, C.c_float, vp, vp]
+        L.pt_set_lens.argtypes = [vp, C.c_float, C.c_float]
+        L.pt_primary_ray.argtypes = [vp, u32, u32, vp, vp, C.POINTER(u32)]
         L.pt_render.argtypes = [vp, u32, u32, vp, vp, vp]
         L.pt_render_device.argtypes = [vp, u32, u32]
         L.pt_active_pixels.argtypes = [vp, vp, vp]
@@ -281,7 +283,13 @@ class Renderer:
         self._chk(self.L.pt_set_config(self.ctx, C.byref(self.cfg)))
 
     def set_camera(self, cam: CameraDesc):
+        """Camera::new: the view and, with it, the description's thin lens (aperture 0 = pinhole)"""
         self._chk(self.L.pt_set_camera(self.ctx, _f3(cam.origin), _f3(cam.target), cam.fov, cam.aspect_ratio))
+        self.set_lens(cam.aperture, cam.focus)
+
+    def set_lens(self, aperture: float, focus: float):
+        """thin lens (pt_set_lens): aperture = lens diameter in world units (0 = pinhole), focus = distance of the plane of focus"""
+        self._chk(self.L.pt_set_lens(self.ctx, aperture, focus))
 
     def camera_input(self, event, a=0.0, b=0.0, dt=0.0) -> bool:
         """Camera::input (camera.rs:56-92): event = EV_MOUSE_MOTION (a, b = delta) or EV_KEY_W/S/A/D; True if consumed"""
@@ -330,6 +338,14 @@ class Renderer:
         d = np.zeros(3, np.float32)
         self._chk(self.L.pt_create_ray(self.ctx, s, t, _p(o), _p(d)))
         return o, d
+
+    def primary_ray(self, pixel: int, sample: int):
+        """(origin, direction, stream draws consumed) of the camera ray of (global pixel, sample), pinhole or lens; host evaluation"""
+        o = np.zeros(3, np.float32)
+        d = np.zeros(3, np.float32)
+        n = C.c_uint32()
+        self._chk(self.L.pt_primary_ray(self.ctx, pixel, sample, _p(o), _p(d), C.byref(n)))
+        return o, d, n.value
 
     # ---- integrate over the frame
     def render(self, first_sample: int, n_samples: int, ident: Optional[np.ndarray] = None, want_position=True):

@@ -393,6 +393,12 @@ TraceLaunch trace_launch(pt_ctx* c, int pipe = 0, bool side_stream = false)
 // and a ray that clears the box by more than two pixels of angle (> 1e-3 rad at 1080p) fails the binary32 slab test by a margin six
 // orders above its rounding error.  Not done when an environment map is set (a miss then needs its own direction), when a corner
 // is not safely in front of the camera, or with PT_FLAG_NO_PRIMARY_CULL.
+//
+// Under a thin lens (pt_set_lens) the camera ray of a pixel leaves a point L of the lens disk and passes through f(pixel), the point where
+// the pixel's pinhole ray meets the plane of focus.  It can meet the box only if f lies in the box's projection FROM L onto that plane.  A
+// corner X at depth z > 0 projects to L + (X - L) * focus / z, which is affine in L: over the disk it stays inside the hull of its values
+// at the four corners of the disk's bounding square.  And f -> pixel is what X -> pixel is above (a point and its pinhole ray share a
+// pixel).  So the rectangle bounds 8 box corners x 4 lens corners, with the same margins and the same ways out.
 struct ActiveRect { uint32_t x0, w, ly0, rows; };
 ActiveRect active_rect(pt_ctx* c)
 {
@@ -439,6 +445,8 @@ ActiveRect active_rect(pt_ctx* c)
     if (!(fl > 0.0) || !std::isfinite(fl)) return full;
     double ext = 0.0;
     for (int k = 0; k < 3; ++k) { fwd[k] /= fl; ext = std::max(ext, std::fabs((double)root.mx[k] - (double)root.mn[k])); }
+    const LensView lens = c->scene.lens_view();
+    const double lens_r = lens.radius;
     double px_lo = 1e300, px_hi = -1e300, py_lo = 1e300, py_hi = -1e300;
     for (int corner = 0; corner < 8; ++corner)
     {
@@ -446,14 +454,27 @@ ActiveRect active_rect(pt_ctx* c)
         if (!std::isfinite(X[0]) || !std::isfinite(X[1]) || !std::isfinite(X[2])) return full;
         const double depth = (X[0] - eye[0]) * fwd[0] + (X[1] - eye[1]) * fwd[1] + (X[2] - eye[2]) * fwd[2];
         if (!(depth > 1e-3 * ext + 1e-6)) return full; // the box reaches (nearly) behind the camera plane: no rectangle bounds its image
-        double q[4];
-        for (int r = 0; r < 4; ++r) q[r] = inv[r] * X[0] + inv[4 + r] * X[1] + inv[8 + r] * X[2] + inv[12 + r];
-        if (!(std::fabs(q[3]) > 1e-300)) return full;
-        const double nx = q[0] / q[3], ny = q[1] / q[3];
-        if (!std::isfinite(nx) || !std::isfinite(ny)) return full;
-        const double px = (nx + 1.0) * 0.5 * W, py = (ny + 1.0) * 0.5 * H; // continuous pixel coordinates: pixel gx spans [gx - 0.5, gx + 0.5]
-        px_lo = std::min(px_lo, px); px_hi = std::max(px_hi, px);
-        py_lo = std::min(py_lo, py); py_hi = std::max(py_hi, py);
+        for (int lc = 0; lc < (lens_r > 0.0 ? 4 : 1); ++lc)
+        {
+            double P[3] = {X[0], X[1], X[2]};
+            if (lens_r > 0.0)
+            {
+                // the corner as seen from this corner of the lens's bounding square, on the plane of focus
+                const double sa = lc & 1 ? lens_r : -lens_r, sb = lc & 2 ? lens_r : -lens_r;
+                double L[3], z = 0.0;
+                for (int k = 0; k < 3; ++k) { L[k] = eye[k] + sa * lens.c0[k] + sb * lens.c1[k]; z += (X[k] - L[k]) * fwd[k]; }
+                if (!(z > 1e-3 * ext + 1e-6)) return full;
+                for (int k = 0; k < 3; ++k) P[k] = L[k] + (X[k] - L[k]) * ((double)lens.focus / z);
+            }
+            double q[4];
+            for (int r = 0; r < 4; ++r) q[r] = inv[r] * P[0] + inv[4 + r] * P[1] + inv[8 + r] * P[2] + inv[12 + r];
+            if (!(std::fabs(q[3]) > 1e-300)) return full;
+            const double nx = q[0] / q[3], ny = q[1] / q[3];
+            if (!std::isfinite(nx) || !std::isfinite(ny)) return full;
+            const double px = (nx + 1.0) * 0.5 * W, py = (ny + 1.0) * 0.5 * H; // continuous pixel coordinates: pixel gx spans [gx - 0.5, gx + 0.5]
+            px_lo = std::min(px_lo, px); px_hi = std::max(px_hi, px);
+            py_lo = std::min(py_lo, py); py_hi = std::max(py_hi, py);
+        }
     }
     const double margin = 3.0;
     const double gx0 = std::floor(px_lo - 0.5 - margin), gx1 = std::ceil(px_hi + 0.5 + margin) + 1.0;
@@ -727,6 +748,7 @@ struct BatchRun
     BatchSpec spec;
     RenderParams rp{};
     CameraView cam{};
+    LensView lens{};
     EnvView env{};
     TraceLaunch tl{}, tl_side{};
     hipStream_t s = nullptr;
@@ -781,10 +803,8 @@ int batch_begin(BatchRun& br, pt_ctx* c, const BatchSpec& spec)
     const WavefrontBuffers& wb = pp.wb;
     br.tl = trace_launch(c, pipe, false);
     br.tl_side = trace_launch(c, pipe, true);
-    std::memcpy(br.cam.ray_matrix, c->scene.camera.ray_matrix, 64);
-    br.cam.eye[0] = c->scene.camera.matrix.t.x;
-    br.cam.eye[1] = c->scene.camera.matrix.t.y;
-    br.cam.eye[2] = c->scene.camera.matrix.t.z;
+    br.cam = c->scene.camera_view();
+    br.lens = c->scene.lens_view();
     if (c->env_w)
     {
         br.env.data = (const f4*)c->d_env.p; // uploaded by the caller (ensure_environment)
@@ -802,7 +822,7 @@ int batch_begin(BatchRun& br, pt_ctx* c, const BatchSpec& spec)
     HIPCHK(c, hipMemsetAsync(wb.wave_times, 0, (size_t)br.rows * kWaveTimeSlots * 16, br.s));
     HIPCHK(c, hipMemsetAsync(wb.wave_times_any, 0, (size_t)br.rows * kWaveTimeSlots * 16, br.s));
 #endif
-    if (rp.n_paths) { Timer t(c, pp, br.s, T_GEN); launch_generate(br.s, rp, br.cam, wb, c->cur_list); }
+    if (rp.n_paths) { Timer t(c, pp, br.s, T_GEN); launch_generate(br.s, rp, br.cam, br.lens, wb, c->cur_list); }
     br.shade_blocks = (uint32_t)std::max<size_t>(1, std::min<size_t>(((size_t)rp.n_paths + 255) / 256, (size_t)c->n_cus * PT_SHADE_BLOCKS_PER_CU));
     br.nee = g.enable_nee != 0;
     // PT_FUSED_TRACE: the BSDF-sampled NEE rays of a bounce ride in the next bounce's world closest-hit launch (k_trace_fused) instead of
@@ -876,11 +896,11 @@ int batch_bounce(BatchRun& br, uint32_t b)
 #if !PT_JOIN_LATE
         batch_join_side(br);
 #endif
-        { Timer t(c, pp, s, T_WORLD); launch_trace_world(s, br.tl, wb, b, br.rp, br.cam, br.env); }
+        { Timer t(c, pp, s, T_WORLD); launch_trace_world(s, br.tl, wb, b, br.rp, br.cam, br.lens, br.env); }
         batch_join_side(br);
     }
     for (uint32_t q = 0; q < Q_COUNT; ++q)
-        if (c->class_present[q]) { Timer t(c, pp, s, T_SHADE); launch_shade(s, q, c->sv, br.rp, wb, b, br.shade_blocks, br.cam, br.env, &br.tl, c->cur_list); }
+        if (c->class_present[q]) { Timer t(c, pp, s, T_SHADE); launch_shade(s, q, c->sv, br.rp, wb, b, br.shade_blocks, br.cam, br.lens, br.env, &br.tl, c->cur_list); }
     // long bounce budgets (reference default MAX_BOUNCES = 1024): stop once no path is left
     if (g.max_bounces > 16 && b >= 8 && (b % 4) == 0 && b < g.max_bounces)
     {
@@ -908,7 +928,7 @@ int batch_end(BatchRun& br, hipEvent_t after)
     {
         batch_nee_launches(br, br.last_row - 1);
         batch_join_side(br);
-        { Timer t(c, pp, s, T_SHADE); launch_shade(s, Q_TERMINAL, c->sv, rp, wb, br.last_row, br.shade_blocks, br.cam, br.env); }
+        { Timer t(c, pp, s, T_SHADE); launch_shade(s, Q_TERMINAL, c->sv, rp, wb, br.last_row, br.shade_blocks, br.cam, br.lens, br.env); }
     }
     if (br.nee_err) return fail(c, PT_ERR_HIP, "stream fork/join failed");
     if (after && hipStreamWaitEvent(s, after, 0) != hipSuccess) return fail(c, PT_ERR_HIP, "hipStreamWaitEvent");
@@ -916,13 +936,13 @@ int batch_end(BatchRun& br, hipEvent_t after)
     {
         launch_store_samples(s, rp, wb, br.spec.samples_out);
         // pt_frame: the frame's own colour goes to the input texture, position / id history are still updated
-        if (br.spec.aux_with_samples) launch_accumulate(s, rp, br.cam, wb, (f4*)c->d_accum.p, (f4*)c->d_position.p, (uint32_t*)c->d_id.p, 1u, 0u);
+        if (br.spec.aux_with_samples) launch_accumulate(s, rp, br.cam, br.lens, wb, (f4*)c->d_accum.p, (f4*)c->d_position.p, (uint32_t*)c->d_id.p, 1u, 0u);
     }
     else
     {
         Timer t(c, pp, s, T_ACCUM);
         const bool adaptive = (c->cfg.flags & PT_FLAG_ADAPTIVE) != 0;
-        launch_accumulate(s, rp, br.cam, wb, (f4*)c->d_accum.p, (f4*)c->d_position.p, (uint32_t*)c->d_id.p, br.spec.write_position ? 1u : 0u, 1u,
+        launch_accumulate(s, rp, br.cam, br.lens, wb, (f4*)c->d_accum.p, (f4*)c->d_position.p, (uint32_t*)c->d_id.p, br.spec.write_position ? 1u : 0u, 1u,
                           adaptive ? (float*)c->d_moments.p : nullptr, adaptive ? c->cur_list : nullptr);
     }
     HIPCHK(c, hipEventRecord(pp.ev_done, s));
@@ -1312,6 +1332,18 @@ int pt_set_camera(pt_ctx* c, const float eye[3], const float target[3], float fo
     return PT_OK;
 }
 
+int pt_set_lens(pt_ctx* c, float aperture, float focus)                                 // Camera::new's 5th and 6th argument  camera.rs:17
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!(aperture >= 0.0f) || !std::isfinite(aperture)) return fail(c, PT_ERR_ARG, "aperture must be finite and >= 0");
+    if (aperture > 0.0f && (!(focus > 0.0f) || !std::isfinite(focus))) return fail(c, PT_ERR_ARG, "focus must be finite and > 0 when aperture > 0");
+    c->scene.camera.aperture = aperture;
+    c->scene.camera.focus = focus;
+    c->scene_version++; // the guides belong to the old camera; pt_multi replicates the lens with it
+    return PT_OK;
+}
+
 int pt_camera_input(pt_ctx* c, int event, float a, float b, float dt)                   // Camera::input  camera.rs:56-92
 {
     if (!c) return PT_ERR_ARG;
@@ -1368,6 +1400,18 @@ int pt_create_ray(pt_ctx* c, float s, float t, float o[3], float d[3])
 {
     if (!c || !c->scene.camera.set) return PT_ERR_STATE;
     c->scene.create_ray(s, t, o, d);
+    return PT_OK;
+}
+
+int pt_primary_ray(pt_ctx* c, uint32_t pixel, uint32_t sample, float o[3], float d[3], uint32_t* draws)
+{
+    if (!c || !o || !d) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->scene.camera.set) return fail(c, PT_ERR_STATE, "pt_set_camera has not been called");
+    const pt_config& g = c->cfg;
+    if (pixel >= g.width * g.height) return fail(c, PT_ERR_ARG, "pixel outside the frame");
+    const uint32_t n = c->scene.primary_ray(g.width, g.height, g.n_sobol, g.seed, pixel, sample, o, d);
+    if (draws) *draws = n;
     return PT_OK;
 }
 
@@ -1766,19 +1810,16 @@ int pt_render_guides(pt_ctx* c, uint32_t sample)
         rp.seed = g.seed;
         rp.div_width = fastdiv_make(rp.width);
         rp.div_strip_rows = fastdiv_make(rp.strip_rows);
-        CameraView cam{};
-        std::memcpy(cam.ray_matrix, c->scene.camera.ray_matrix, 64);
-        cam.eye[0] = c->scene.camera.matrix.t.x;
-        cam.eye[1] = c->scene.camera.matrix.t.y;
-        cam.eye[2] = c->scene.camera.matrix.t.z;
+        const CameraView cam = c->scene.camera_view();
+        const LensView lens = c->scene.lens_view();
         const RayQueue q{(f4*)c->d_gray_a.p, (f4*)c->d_gray_b.p};
         uint32_t* head = (uint32_t*)c->d_ghead.p;
         HIPCHK(c, hipMemsetAsync(head, 0, c->d_ghead.bytes, c->stream));
-        launch_guide_rays(c->stream, rp, cam, q, head);
+        launch_guide_rays(c->stream, rp, cam, lens, q, head);
         // (an empty world: every ray misses)
         if (c->sv.world_root == MISS_ID) HIPCHK(c, hipMemsetAsync(c->d_ghits.p, 0xff, (size_t)px * 16, c->stream));
         else launch_trace_rays_closest(c->stream, trace_launch(c), c->sv.world_root, q, px, head, (f4*)c->d_ghits.p);
-        launch_guide_resolve(c->stream, c->sv, px, cam, q, (const f4*)c->d_ghits.p, (f4*)c->d_gpos.p, (f4*)c->d_gnrm.p, (uint32_t*)c->d_gmodel.p);
+        launch_guide_resolve(c->stream, c->sv, px, cam, lens, q, (const f4*)c->d_ghits.p, (f4*)c->d_gpos.p, (f4*)c->d_gnrm.p, (uint32_t*)c->d_gmodel.p);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }

@@ -1,6 +1,7 @@
 // gfx950 (MI355X, wave64) kernels of the wavefront path tracer.
 //
-//   k_generate      main.rs:186-199   seed draw, shuffled-scrambled Sobol jitter, camera ray
+//   k_generate      main.rs:186-199   seed draw, shuffled-scrambled Sobol jitter, camera ray (pt_camera.h; k_generate_lens and the LENS
+//                   instantiations below: the thin lens of pt_set_lens, whose camera rays have origins of their own)
 //   k_closest       tlas.rs:66-110 + blas.rs:214-256 + boundingbox.rs:115-131 + primitive.rs:117-178
 //                   persistent-threads ordered traversal; BVH staged in LDS; per-lane stack in LDS;
 //                   ballot/mbcnt refill of idle lanes from the ray queue; material binning of the hits;
@@ -14,6 +15,7 @@
 // Arithmetic: pt_math.h / pt_materials.h.  Built with -ffp-contract=off; v_min/v_max are used in the slab test only
 // where they provably equal the SSE select semantics of the reference (see slab()).
 #include "pt_kernels.h"
+#include "pt_camera.h"
 #include "pt_materials.h"
 
 #include <algorithm>
@@ -746,7 +748,10 @@ __device__ __forceinline__ Blob stage_scene(const SceneView& sv, const uint4* __
 
 // CLOSEST_PRIMARY = CLOSEST_WORLD for bounce 0: every ray starts at the eye (only directions are stored, ray index == path id)
 // and a miss ends the path on the spot (integrator.rs:263-266 with accumulated = 0, path_weight = 1).
-enum { CLOSEST_WORLD = 0, CLOSEST_LIGHTS = 1, CLOSEST_HOOK = 2, CLOSEST_PRIMARY = 3 };
+// CLOSEST_PRIMARY_LENS = CLOSEST_PRIMARY under a thin lens (pt_set_lens): the camera rays' origins are read from the queue like any
+// bounce's and go into the shade records (ShadeQueue::c), since no two of them start at the same point.
+enum { CLOSEST_WORLD = 0, CLOSEST_LIGHTS = 1, CLOSEST_HOOK = 2, CLOSEST_PRIMARY = 3, CLOSEST_PRIMARY_LENS = 4 };
+constexpr bool closest_is_primary(int mode) { return mode == CLOSEST_PRIMARY || mode == CLOSEST_PRIMARY_LENS; }
 
 struct ClosestOut
 {
@@ -763,7 +768,7 @@ struct ClosestOut
     // CLOSEST_LIGHTS (fused NEE chain): world root for the follow-up any-hit, result codes by path id
     uint32_t world_root;
     uint8_t* occl;
-    // CLOSEST_PRIMARY
+    // CLOSEST_PRIMARY (eye: not CLOSEST_PRIMARY_LENS)
     f3 eye;
     f4* radiance;
     f4* first_pos;
@@ -1007,11 +1012,11 @@ __device__ __forceinline__ void closest_body(const SceneView& sv, const Blob& bl
             const uint64_t pm = __ballot(pending);
             if (pm != 0ull)
             {
-                if (MODE == CLOSEST_WORLD || MODE == CLOSEST_PRIMARY)
+                if (MODE == CLOSEST_WORLD || closest_is_primary(MODE))
                 {
                     if (IDENT && pending) { w.o = with_signs(ob.o, w_signs); w.d = with_signs(ob.d, w_signs >> 3); } // the world ray, bit-exact
                     uint64_t qm = pm;
-                    if (MODE == CLOSEST_PRIMARY)
+                    if (closest_is_primary(MODE))
                     {
                         // a primary miss is a finished path: accumulated = 0 + 0.006 * 1 (integrator.rs:265), defaults of :156-157
                         const bool missed = pending && bid == MISS_ID && out->finalize_miss != 0u;
@@ -1353,7 +1358,7 @@ __device__ __forceinline__ void closest_body(const SceneView& sv, const Blob& bl
             }
         }
     }
-    if (MODE == CLOSEST_WORLD || MODE == CLOSEST_PRIMARY)
+    if (MODE == CLOSEST_WORLD || closest_is_primary(MODE))
     {
         const ClosestOutPtr out = launder_args(outp);
         // hand back what is left of this wave's regions as holes (a hole is a path id of HOLE)
@@ -1662,34 +1667,6 @@ __device__ __forceinline__ PixelId path_pixel_list(const RenderParams& rp, const
     return PixelId{gy * rp.width + x, e.y + rp.first_sample + pp.s, e.x, x, gy};
 }
 
-// direction of the camera ray of (pixel gx, gy; sample): main.rs:193-199 + Camera::create_ray camera.rs:94-105
-__device__ __forceinline__ f3 camera_ray_dir(const RenderParams& rp, const CameraView& cam, uint32_t gx, uint32_t gy, uint32_t sample)
-{
-    Stream rng{stream_key(rp.seed, gy * rp.width + gx, sample), 0u};
-    const uint32_t seed = rng.u32();                                       // main.rs:193 (the stream's draw 0)
-    float jx, jy;
-    ss_sobol(rp.n_sobol, sample, seed, &jx, &jy);                          // main.rs:194
-    const float ox = jx - 0.5f, oy = jy - 0.5f;
-    const float u = ((float)gx + ox) / (float)rp.width;                    // main.rs:196
-    const float v = ((float)gy + oy) / (float)rp.height;                   // main.rs:197
-    // Camera::create_ray  camera.rs:94-105  (Mat4::project_point3, then normalise)
-    const float nx = u * 2.0f - 1.0f, ny = v * 2.0f - 1.0f, nz = 0.0f;
-    const float* M = cam.ray_matrix;
-    float r[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-    {
-        float t = M[i] * nx;
-        t = M[4 + i] * ny + t;
-        t = M[8 + i] * nz + t;
-        t = M[12 + i] + t;
-        r[i] = t;
-    }
-    const float rw = 1.0f / r[3];
-    const f3 eye{cam.eye[0], cam.eye[1], cam.eye[2]};
-    return unit3(f3{r[0] * rw, r[1] * rw, r[2] * rw} - eye);
-}
-
 // main.rs:186-199
 __global__ void __launch_bounds__(256) k_generate(const RenderParams rp, const CameraView cam, const RayQueue rq, Counters* ctr)
 {
@@ -1710,6 +1687,22 @@ __global__ void __launch_bounds__(256) k_generate_list(const RenderParams rp, co
     if (pid >= rp.n_paths) return;
     const PixelId px = path_pixel_list(rp, list, pid);
     const f3 dir = camera_ray_dir(rp, cam, px.gx, px.gy, px.sample);
+    rq.b[pid] = f4{dir.x, dir.y, dir.z, asf(pid)};
+}
+
+// thin lens (pt_set_lens): every camera ray has an origin of its own on the lens disk, stored beside its direction; bounce 0 then knows
+// TWO draws consumed.  LIST: over an adaptive list, as k_generate_list
+template <bool LIST>
+__global__ void __launch_bounds__(256) k_generate_lens(const RenderParams rp, const CameraView cam, const LensView lens, const RayQueue rq, Counters* ctr,
+                                                        const uint2* __restrict__ list)
+{
+    const uint32_t pid = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pid == 0u) ctr[0].n_closest = rp.n_paths;
+    if (pid >= rp.n_paths) return;
+    const PixelId px = LIST ? path_pixel_list(rp, list, pid) : path_pixel(rp, pid);
+    f3 o;
+    const f3 dir = camera_ray(rp, cam, lens, px.gx, px.gy, px.sample, &o);
+    rq.a[pid] = f4{o.x, o.y, o.z, __builtin_inff()};
     rq.b[pid] = f4{dir.x, dir.y, dir.z, asf(pid)};
 }
 
@@ -1798,6 +1791,8 @@ __device__ __forceinline__ void resolve_nee(const SceneView& sv, const ShadeIO& 
 
 // ------------------------------------------------------------------------------------------------ shading
 // Q_TERMINAL: misses (integrator.rs:254-269), emissive hits (:207-214) and paths that already ended but still owe an NEE resolve.
+// LENS (pt_set_lens): a camera ray's origin is its own, read from the ray queue at bounce 0 as at any other
+template <bool LENS = false>
 __global__ void __launch_bounds__(256) k_shade_terminal(const SceneView sv, const RenderParams rp, const ShadeIO io, const uint32_t bounce)
 {
     const uint32_t n = min(io.ctr->n_shade[Q_TERMINAL], io.cap_slots_term);
@@ -1813,7 +1808,7 @@ __global__ void __launch_bounds__(256) k_shade_terminal(const SceneView sv, cons
             hit = io.hits[entry];
             if (asu(hit.w) != MISS_ID) // a miss needs no origin, and its direction only for the environment lookup
             {
-                ra = bounce == 0u ? io.primary_a : io.rq_in.a[entry];
+                ra = (!LENS && bounce == 0u) ? io.primary_a : io.rq_in.a[entry];
                 rb = io.rq_in.b[entry];
             }
             else if (io.env.w != 0u) rb = io.rq_in.b[entry];
@@ -1974,7 +1969,8 @@ __device__ __forceinline__ const ShadeKArgs& shade_args()
     [[maybe_unused]] const RenderParams& rp = ka_.rp;                                                                              \
     [[maybe_unused]] const ShadeIO& io = ka_.io;
 // LIST (pt_render_adaptive): path ids index the adaptive list (ShadeIO::list, path_pixel_list) instead of the active rectangle
-template <uint32_t QCLASS, bool VOLUMES, bool INLINE = false, bool IDENT = false, bool LIST = false>
+// LENS (pt_set_lens; launched for bounce 0 only): the camera ray's origin comes with its record (ShadeQueue::c) and two draws are consumed
+template <uint32_t QCLASS, bool VOLUMES, bool INLINE = false, bool IDENT = false, bool LIST = false, bool LENS = false>
 __global__ void __launch_bounds__(PT_SHADE_THREADS, INLINE ? PT_SHADE_WAVES_INLINE : shade_waves(QCLASS, VOLUMES)) k_shade_surface(const ShadeKArgs kargs)
 {
     extern __shared__ uint4 smem_dyn[];
@@ -2029,8 +2025,8 @@ __global__ void __launch_bounds__(PT_SHADE_THREADS, INLINE ? PT_SHADE_WAVES_INLI
             PT_SHADE_ARGS
             pid = asu(rb.w);
             const f4 hit = nt_load(io.q_in.b + idx);
-            const f4 ra = bounce == 0u ? io.primary_a : nt_load(io.q_in.c + idx);
-            f4 pw4{1.0f, 1.0f, 1.0f, asf(1u)}; // bounce 0: path_weight = 1, accumulated = 0, the seed draw consumed
+            const f4 ra = (!LENS && bounce == 0u) ? io.primary_a : nt_load(io.q_in.c + idx);
+            f4 pw4{1.0f, 1.0f, 1.0f, asf(LENS ? 2u : 1u)}; // bounce 0: path_weight = 1, accumulated = 0, the seed draw consumed (LENS: and the lens point's)
             acc = f3{0.0f, 0.0f, 0.0f};
             flags = 0u;
             if (bounce != 0u)
@@ -2338,6 +2334,20 @@ __global__ void __launch_bounds__(PT_SHADE_THREADS, INLINE ? PT_SHADE_WAVES_INLI
 
 #undef PT_SHADE_ARGS
 
+// position r.at(1e5) of a camera ray that left the scene at once (integrator.rs:156), pinhole and thin lens
+struct CameraLensView : CameraView { LensView lens; };
+__device__ __forceinline__ f3 miss_position(const RenderParams& rp, const CameraView& cam, uint32_t gx, uint32_t gy, uint32_t sample)
+{
+    const f3 d = camera_ray_dir(rp, cam, gx, gy, sample);
+    return fma3(d, bc3(1e5f), f3{cam.eye[0], cam.eye[1], cam.eye[2]});
+}
+__device__ __forceinline__ f3 miss_position(const RenderParams& rp, const CameraLensView& cam, uint32_t gx, uint32_t gy, uint32_t sample)
+{
+    f3 o;
+    const f3 d = camera_ray(rp, cam, cam.lens, gx, gy, sample, &o);
+    return fma3(d, bc3(1e5f), o);
+}
+
 // integrator.rs:272-280: finite check, clamp_length_max(100), alpha 1
 __device__ __forceinline__ f3 finalise(f3 acc)
 {
@@ -2360,9 +2370,13 @@ __device__ __forceinline__ float luminance(float r, float g, float b) { return (
 // MOMENTS (PT_FLAG_ADAPTIVE): moments[pixel] += L * L once per sample beside the colour, in the same order, L = luminance of the finalised
 // sample.  LIST (pt_render_adaptive): one thread (quad) per entry of the adaptive list instead of per local pixel; unlisted pixels are
 // not touched, and entry k's sample s is the pixel's sample n_p + first_sample + s (path_pixel_list).
-template <bool FEW_PIXELS, bool MOMENTS = false, bool LIST = false>
-__global__ void __launch_bounds__(256) k_accumulate(const RenderParams rp, const CameraView cam, const PathState st, f4* accum, f4* position, uint32_t* id,
-                                                     const uint32_t write_position, const uint32_t add_to_accum, float* moments, const uint2* list)
+//
+// LENS (pt_set_lens): the camera ray of a miss is the lens ray, so r.at(1e5) starts at its point of the lens disk.  The lens rides behind
+// the camera in the LENS instantiations' camera argument only (CameraLensView): the pinhole instantiations' arguments are what they were.
+template <bool FEW_PIXELS, bool MOMENTS = false, bool LIST = false, bool LENS = false>
+__global__ void __launch_bounds__(256) k_accumulate(const RenderParams rp, const std::conditional_t<LENS, CameraLensView, CameraView> cam, const PathState st,
+                                                     f4* accum, f4* position, uint32_t* id, const uint32_t write_position, const uint32_t add_to_accum,
+                                                     float* moments, const uint2* list)
 {
     const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t t = FEW_PIXELS ? tid >> 2 : tid, q = FEW_PIXELS ? (tid & 3u) : 0u;
@@ -2389,8 +2403,7 @@ __global__ void __launch_bounds__(256) k_accumulate(const RenderParams rp, const
         id[lp] = idv;
         if (write_position)
         {
-            const f3 d = camera_ray_dir(rp, cam, x, global_row(rp, ly), rp.first_sample + rp.batch_samples - 1u);
-            const f3 far = fma3(d, bc3(1e5f), f3{cam.eye[0], cam.eye[1], cam.eye[2]});
+            const f3 far = miss_position(rp, cam, x, global_row(rp, ly), rp.first_sample + rp.batch_samples - 1u);
             position[lp] = f4{far.x, far.y, far.z, 1e5f};
         }
         return;
@@ -2471,8 +2484,7 @@ __global__ void __launch_bounds__(256) k_accumulate(const RenderParams rp, const
         // the batch's last sample.  A camera ray that left the scene at once has no record: r.at(1e5) of that sample's ray (integrator.rs:156)
         if (st.occl[pid_join(rp, rp.keep_s_pos, k)] == PRIMARY_MISS)
         {
-            const f3 d = camera_ray_dir(rp, cam, x, global_row(rp, ly), entry.y + rp.first_sample + rp.keep_s_pos);
-            const f3 far = fma3(d, bc3(1e5f), f3{cam.eye[0], cam.eye[1], cam.eye[2]});
+            const f3 far = miss_position(rp, cam, x, global_row(rp, ly), entry.y + rp.first_sample + rp.keep_s_pos);
             position[lp] = f4{far.x, far.y, far.z, 1e5f};
         }
         else position[lp] = st.first_pos[k];
@@ -2667,19 +2679,33 @@ __global__ void __launch_bounds__(256) k_guide_rays(const RenderParams rp, const
     rq.a[i] = f4{cam.eye[0], cam.eye[1], cam.eye[2], __builtin_inff()};
     rq.b[i] = f4{dir.x, dir.y, dir.z, asf(i)};
 }
+// thin lens (pt_set_lens): the lens ray k_generate_lens makes for that (pixel, sample)
+__global__ void __launch_bounds__(256) k_guide_rays_lens(const RenderParams rp, const CameraView cam, const LensView lens, const RayQueue rq,
+                                                          uint32_t* __restrict__ n_and_heads)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i == 0u) n_and_heads[0] = rp.local_pixels;
+    if (i >= rp.local_pixels) return;
+    const uint32_t ly = fastdiv(i, rp.div_width), x = i - ly * rp.width;
+    f3 o;
+    const f3 dir = camera_ray(rp, cam, lens, x, global_row(rp, ly), rp.first_sample, &o);
+    rq.a[i] = f4{o.x, o.y, o.z, __builtin_inff()};
+    rq.b[i] = f4{dir.x, dir.y, dir.z, asf(i)};
+}
 
 // first-hit guides of those rays: position r.at(t) | t as the render keeps it (r.at(1e5) | 1e5 for a miss, integrator.rs:156), the
 // face-forwarded world shading normal of the hit (HitInfo's, primitive.rs:161-165 + tlas.rs:105; 0 for a miss) and the hit's model
 // (BLAS index, MISS_ID for a miss) in full: its low byte is the id byte of main.rs:206
-__global__ void __launch_bounds__(256) k_guide_resolve(const SceneView sv, const uint32_t n, const CameraView cam, const RayQueue rq,
-                                                       const f4* __restrict__ hits, f4* __restrict__ position, f4* __restrict__ normal,
-                                                       uint32_t* __restrict__ model)
+// LENS (pt_set_lens): the ray's origin is its own (rq.a) instead of the eye
+template <bool LENS>
+__device__ __forceinline__ void guide_resolve_body(const SceneView& sv, const uint32_t n, const CameraView& cam, const RayQueue& rq, const f4* __restrict__ hits,
+                                                   f4* __restrict__ position, f4* __restrict__ normal, uint32_t* __restrict__ model)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const f4 hit = hits[i];
     const f3 d = xyz(rq.b[i]);
-    const f3 eye{cam.eye[0], cam.eye[1], cam.eye[2]};
+    const f3 eye = LENS ? xyz(rq.a[i]) : f3{cam.eye[0], cam.eye[1], cam.eye[2]};
     const uint32_t hid = asu(hit.w);
     if (hid == MISS_ID)
     {
@@ -2697,14 +2723,31 @@ __global__ void __launch_bounds__(256) k_guide_resolve(const SceneView sv, const
     normal[i] = f4{nrm.x, nrm.y, nrm.z, 0.0f};
     model[i] = sv.instances[inst].blas;
 }
+__global__ void __launch_bounds__(256) k_guide_resolve(const SceneView sv, const uint32_t n, const CameraView cam, const RayQueue rq,
+                                                       const f4* __restrict__ hits, f4* __restrict__ position, f4* __restrict__ normal,
+                                                       uint32_t* __restrict__ model)
+{
+    guide_resolve_body<false>(sv, n, cam, rq, hits, position, normal, model);
+}
+__global__ void __launch_bounds__(256) k_guide_resolve_lens(const SceneView sv, const uint32_t n, const CameraView cam, const RayQueue rq,
+                                                            const f4* __restrict__ hits, f4* __restrict__ position, f4* __restrict__ normal,
+                                                            uint32_t* __restrict__ model)
+{
+    guide_resolve_body<true>(sv, n, cam, rq, hits, position, normal, model);
+}
 
 } // namespace
 
 // ================================================================================================ launchers
-void launch_generate(hipStream_t s, const RenderParams& rp, const CameraView& cam, const WavefrontBuffers& wb, const uint2* list)
+void launch_generate(hipStream_t s, const RenderParams& rp, const CameraView& cam, const LensView& lens, const WavefrontBuffers& wb, const uint2* list)
 {
     const uint32_t blocks = (rp.n_paths + 255u) / 256u;
-    if (list) hipLaunchKernelGGL(k_generate_list, dim3(blocks), dim3(256), 0, s, rp, cam, wb.rq[0], wb.counters, list);
+    if (lens_set(lens))
+    {
+        if (list) hipLaunchKernelGGL(k_generate_lens<true>, dim3(blocks), dim3(256), 0, s, rp, cam, lens, wb.rq[0], wb.counters, list);
+        else hipLaunchKernelGGL(k_generate_lens<false>, dim3(blocks), dim3(256), 0, s, rp, cam, lens, wb.rq[0], wb.counters, list);
+    }
+    else if (list) hipLaunchKernelGGL(k_generate_list, dim3(blocks), dim3(256), 0, s, rp, cam, wb.rq[0], wb.counters, list);
     else hipLaunchKernelGGL(k_generate, dim3(blocks), dim3(256), 0, s, rp, cam, wb.rq[0], wb.counters);
 }
 
@@ -2824,7 +2867,7 @@ static ClosestOut world_out(const WavefrontBuffers& wb, uint32_t b, const Render
 }
 
 void launch_trace_world(hipStream_t s, const TraceLaunch& tl, const WavefrontBuffers& wb, uint32_t b, const RenderParams& rp, const CameraView& cam,
-                        const EnvView& env)
+                        const LensView& lens, const EnvView& env)
 {
     Counters* row = wb.counters + b;
     ClosestOut out = world_out(wb, b, rp, env);
@@ -2839,7 +2882,8 @@ void launch_trace_world(hipStream_t s, const TraceLaunch& tl, const WavefrontBuf
         out.keep_s_id = rp.keep_s_id; out.keep_s_pos = rp.keep_s_pos;
         out.blk_log = rp.blk_log; out.n_blk = rp.n_blk; out.blk_last = rp.blk_last; out.act_pixels = rp.act_pixels;
         out.div_blk_paths = rp.div_blk_paths; out.div_blk_last = rp.div_blk_last;
-        launch_closest_impl<CLOSEST_PRIMARY>(s, tl, tl.scene.world_root, wb.rq[0], &row->n_closest, wb.cap_slots, row_heads(wb, b, HEADS_CLOSEST), out);
+        if (lens_set(lens)) launch_closest_impl<CLOSEST_PRIMARY_LENS>(s, tl, tl.scene.world_root, wb.rq[0], &row->n_closest, wb.cap_slots, row_heads(wb, b, HEADS_CLOSEST), out);
+        else launch_closest_impl<CLOSEST_PRIMARY>(s, tl, tl.scene.world_root, wb.rq[0], &row->n_closest, wb.cap_slots, row_heads(wb, b, HEADS_CLOSEST), out);
     }
     else launch_closest_impl<CLOSEST_WORLD>(s, tl, tl.scene.world_root, wb.rq[b & 1u], &row->n_closest, wb.cap_slots, row_heads(wb, b, HEADS_CLOSEST), out);
 }
@@ -2893,8 +2937,9 @@ bool shade_traces_shadow(const TraceLaunch& tl)
            trace_lds_bytes(tl) + 1024 <= 32 * 1024;
 }
 void launch_shade(hipStream_t s, uint32_t qclass, const SceneView& sv, const RenderParams& rp, const WavefrontBuffers& wb, uint32_t b,
-                  uint32_t grid_blocks, const CameraView& cam, const EnvView& env, const TraceLaunch* tl, const uint2* list)
+                  uint32_t grid_blocks, const CameraView& cam, const LensView& lens, const EnvView& env, const TraceLaunch* tl, const uint2* list)
 {
+    const bool lens0 = b == 0u && lens_set(lens); // only bounce 0 knows of the camera: its rays' origins and the draws they consumed
     ShadeIO io{};
     io.env = env;
     io.primary_a = f4{cam.eye[0], cam.eye[1], cam.eye[2], __builtin_inff()};
@@ -2927,15 +2972,23 @@ void launch_shade(hipStream_t s, uint32_t qclass, const SceneView& sv, const Ren
     if (list && qclass != Q_TERMINAL) io.list = list; // (the surface passes read no terminal entries)
     const ShadeKArgs ka{sv, rp, io, b, inl ? (const uint4*)tl->blob : nullptr, inl ? tl->scene.world_root : 0u};
     const size_t lds = inl ? trace_lds_bytes(*tl) : 0;
-    // (LIST: the same classes over an adaptive list's paths, k_shade_surface_list)
+    // (LIST: the same classes over an adaptive list's paths; lens0: LENS)
+#define PT_SURF_L(LENS, Q, V, ...)                                                                                                      \
+    do {                                                                                                                                 \
+        if (list) hipLaunchKernelGGL((k_shade_surface<Q, V, __VA_ARGS__, true, LENS>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), lds, s, ka);  \
+        else hipLaunchKernelGGL((k_shade_surface<Q, V, __VA_ARGS__, false, LENS>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), lds, s, ka);      \
+    } while (0)
 #define PT_SURF(Q, V, ...)                                                                                                              \
     do {                                                                                                                                 \
-        if (list) hipLaunchKernelGGL((k_shade_surface<Q, V, __VA_ARGS__, true>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), lds, s, ka); \
-        else hipLaunchKernelGGL((k_shade_surface<Q, V, __VA_ARGS__>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), lds, s, ka);           \
+        if (lens0) PT_SURF_L(true, Q, V, __VA_ARGS__);                                                                                   \
+        else PT_SURF_L(false, Q, V, __VA_ARGS__);                                                                                        \
     } while (0)
     switch (qclass)
     {
-    case Q_TERMINAL: hipLaunchKernelGGL(k_shade_terminal, dim3(grid_blocks), dim3(256), 0, s, sv, rp, io, b); break;
+    case Q_TERMINAL:
+        if (lens0) hipLaunchKernelGGL(k_shade_terminal<true>, dim3(grid_blocks), dim3(256), 0, s, sv, rp, io, b);
+        else hipLaunchKernelGGL(k_shade_terminal<false>, dim3(grid_blocks), dim3(256), 0, s, sv, rp, io, b);
+        break;
     case Q_LAMBERT:
         if (inl && PT_IDENT_SHADE && ident_walk(*tl, IDENT_TLAS_WORLD)) PT_SURF(Q_LAMBERT, false, true, true);
         else if (inl) PT_SURF(Q_LAMBERT, false, true, false);
@@ -2957,20 +3010,30 @@ void launch_shade(hipStream_t s, uint32_t qclass, const SceneView& sv, const Ren
     default: break;
     }
 #undef PT_SURF
+#undef PT_SURF_L
 }
 
-void launch_accumulate(hipStream_t s, const RenderParams& rp, const CameraView& cam, const WavefrontBuffers& wb, f4* accum, f4* position, uint32_t* id,
-                       uint32_t write_position, uint32_t add_to_accum, float* moments, const uint2* list)
+void launch_accumulate(hipStream_t s, const RenderParams& rp, const CameraView& cam, const LensView& lens, const WavefrontBuffers& wb, f4* accum, f4* position,
+                       uint32_t* id, uint32_t write_position, uint32_t add_to_accum, float* moments, const uint2* list)
 {
     const uint32_t n = list ? rp.act_pixels : rp.local_pixels;
     if (n == 0u) return;
     const bool quad = n < (uint32_t)PT_ACC_QUAD_BELOW;
     const dim3 grid(quad ? (n * 4u + 255u) / 256u : (n + 255u) / 256u);
-    auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, rp, cam, wb.st, accum, position, id, write_position, add_to_accum, moments, list); };
+    auto go = [&](auto kernel, const auto& camera) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, rp, camera, wb.st, accum, position, id, write_position, add_to_accum, moments, list); };
     // (a list comes with moments: pt_render_adaptive)
-    if (list) quad ? go(k_accumulate<true, true, true>) : go(k_accumulate<false, true, true>);
-    else if (moments) quad ? go(k_accumulate<true, true>) : go(k_accumulate<false, true>);
-    else quad ? go(k_accumulate<true>) : go(k_accumulate<false>);
+    if (lens_set(lens))
+    {
+        CameraLensView cl{};
+        static_cast<CameraView&>(cl) = cam;
+        cl.lens = lens;
+        if (list) quad ? go(k_accumulate<true, true, true, true>, cl) : go(k_accumulate<false, true, true, true>, cl);
+        else if (moments) quad ? go(k_accumulate<true, true, false, true>, cl) : go(k_accumulate<false, true, false, true>, cl);
+        else quad ? go(k_accumulate<true, false, false, true>, cl) : go(k_accumulate<false, false, false, true>, cl);
+    }
+    else if (list) quad ? go(k_accumulate<true, true, true>, cam) : go(k_accumulate<false, true, true>, cam);
+    else if (moments) quad ? go(k_accumulate<true, true>, cam) : go(k_accumulate<false, true>, cam);
+    else quad ? go(k_accumulate<true>, cam) : go(k_accumulate<false>, cam);
 }
 uint32_t adaptive_select_blocks(uint32_t n_pixels) { return (n_pixels + kSelectPerBlock - 1u) / kSelectPerBlock; }
 void launch_adaptive_select(hipStream_t s, const f4* accum, const float* moments, uint32_t n_pixels, const AdaptiveCrit& cr, uint32_t* counts, uint2* list,
@@ -3018,14 +3081,16 @@ void launch_volume_probe(hipStream_t s, const SceneView& sv, int material, uint3
     hipLaunchKernelGGL(k_volume_probe, dim3((n + 255u) / 256u), dim3(256), 0, s, sv, material, n, incoming, t_max, dist, pixel, sample, draws, seed, out9);
 }
 
-void launch_guide_rays(hipStream_t s, const RenderParams& rp, const CameraView& cam, RayQueue rq, uint32_t* n_and_heads)
+void launch_guide_rays(hipStream_t s, const RenderParams& rp, const CameraView& cam, const LensView& lens, RayQueue rq, uint32_t* n_and_heads)
 {
-    hipLaunchKernelGGL(k_guide_rays, dim3((rp.local_pixels + 255u) / 256u), dim3(256), 0, s, rp, cam, rq, n_and_heads);
+    if (lens_set(lens)) hipLaunchKernelGGL(k_guide_rays_lens, dim3((rp.local_pixels + 255u) / 256u), dim3(256), 0, s, rp, cam, lens, rq, n_and_heads);
+    else hipLaunchKernelGGL(k_guide_rays, dim3((rp.local_pixels + 255u) / 256u), dim3(256), 0, s, rp, cam, rq, n_and_heads);
 }
-void launch_guide_resolve(hipStream_t s, const SceneView& sv, uint32_t n, const CameraView& cam, RayQueue rq, const f4* hits, f4* position, f4* normal,
-                          uint32_t* model)
+void launch_guide_resolve(hipStream_t s, const SceneView& sv, uint32_t n, const CameraView& cam, const LensView& lens, RayQueue rq, const f4* hits, f4* position,
+                          f4* normal, uint32_t* model)
 {
-    hipLaunchKernelGGL(k_guide_resolve, dim3((n + 255u) / 256u), dim3(256), 0, s, sv, n, cam, rq, hits, position, normal, model);
+    if (lens_set(lens)) hipLaunchKernelGGL(k_guide_resolve_lens, dim3((n + 255u) / 256u), dim3(256), 0, s, sv, n, cam, rq, hits, position, normal, model);
+    else hipLaunchKernelGGL(k_guide_resolve, dim3((n + 255u) / 256u), dim3(256), 0, s, sv, n, cam, rq, hits, position, normal, model);
 }
 
 } // namespace pt

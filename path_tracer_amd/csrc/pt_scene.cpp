@@ -7,6 +7,7 @@
 //   LightSampler::new        src/scene/light_sampler.rs:41-61
 //   Camera::new              src/camera.rs:17-31
 #include "pt_scene.h"
+#include "pt_camera.h"
 
 #include <algorithm>
 #include <chrono>
@@ -981,6 +982,35 @@ void HostScene::create_ray(float s, float t, float o[3], float d[3]) const      
     const f3 dir = unit3(point - camera.matrix.t);
     o[0] = camera.matrix.t.x; o[1] = camera.matrix.t.y; o[2] = camera.matrix.t.z;
     d[0] = dir.x; d[1] = dir.y; d[2] = dir.z;
+}
+
+CameraView HostScene::camera_view() const
+{
+    CameraView cv{};
+    std::memcpy(cv.ray_matrix, camera.ray_matrix, 64);
+    cv.eye[0] = camera.matrix.t.x; cv.eye[1] = camera.matrix.t.y; cv.eye[2] = camera.matrix.t.z;
+    return cv;
+}
+
+LensView HostScene::lens_view() const
+{
+    const m33& r = camera.matrix.m;
+    return LensView{{r.c0.x, r.c0.y, r.c0.z}, camera.aperture * 0.5f, {r.c1.x, r.c1.y, r.c1.z}, camera.focus};
+}
+
+uint32_t HostScene::primary_ray(uint32_t width, uint32_t height, uint32_t n_sobol, uint64_t seed, uint32_t pixel, uint32_t sample, float o[3], float d[3]) const
+{
+    RenderParams rp{};
+    rp.width = width; rp.height = height; rp.n_sobol = n_sobol; rp.seed = seed;
+    const CameraView cv = camera_view();
+    const LensView lens = lens_view();
+    const uint32_t gy = pixel / width, gx = pixel - gy * width;
+    f3 org{cv.eye[0], cv.eye[1], cv.eye[2]};
+    const bool with_lens = lens.radius > 0.0f;
+    const f3 dir = with_lens ? camera_ray(rp, cv, lens, gx, gy, sample, &org) : camera_ray_dir(rp, cv, gx, gy, sample);
+    o[0] = org.x; o[1] = org.y; o[2] = org.z;
+    d[0] = dir.x; d[1] = dir.y; d[2] = dir.z;
+    return with_lens ? 2u : 1u;
 }
 
 } // namespace pt

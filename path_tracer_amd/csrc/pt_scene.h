@@ -66,6 +66,8 @@ struct HostCamera
     xf34 matrix;          // camera-to-world
     float inv_proj[16];   // column-major
     float ray_matrix[16]; // matrix * inv_projection, column-major
+    // thin lens (Camera::new's 5th and 6th argument, camera.rs:17; pt_set_lens).  aperture 0 = pinhole.  Not touched by set_camera or the input
+    float aperture = 0, focus = 0;
 };
 
 struct FlatScene
@@ -109,6 +111,11 @@ public:
     int build(std::string* err);
     void set_camera(const float eye[3], const float target[3], float fov_deg, float aspect);
     void create_ray(float s, float t, float o[3], float d[3]) const;
+    // what the kernels are given of the camera (CameraView) and of its lens (LensView; radius 0 = pinhole)
+    CameraView camera_view() const;
+    LensView lens_view() const;
+    // the camera ray of (pixel, sample) as the kernels make it (pt_camera.h), pinhole or lens; returns the stream draws it consumed
+    uint32_t primary_ray(uint32_t width, uint32_t height, uint32_t n_sobol, uint64_t seed, uint32_t pixel, uint32_t sample, float o[3], float d[3]) const;
     void inv_projection(float out16[16]) const; // (matrix * inv_projection).inverse()  main.rs:128
     void camera_move(float dx, float dz, float dt);   // Camera::update_origin    camera.rs:33-39
     void camera_rotate(float dx, float dy, float dt); // Camera::update_rotation  camera.rs:41-54

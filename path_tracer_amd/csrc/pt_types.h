@@ -141,6 +141,15 @@ struct CameraView
     float eye[3];         // matrix.translation
     float pad;
 };
+// Thin lens (pt_set_lens).  An argument of its own for the lens variants of the camera kernels, so that CameraView and with it the
+// pinhole kernels' argument layout stay what they are.
+struct LensView
+{
+    float c0[3];   // camera matrix, first rotation column: the lens plane's x axis
+    float radius;  // aperture / 2; 0 = pinhole (no lens variant is launched)
+    float c1[3];   // second rotation column
+    float focus;   // distance of the plane of focus along the view axis
+};
 
 // Division by a launch-invariant divisor (Granlund-Montgomery / libdivide "branch-free" form): n / d = (((n - q) >> 1) + q) >> shift
 // with q = mulhi(magic, n), exact for every 32-bit n and d >= 2; d == 1 is flagged.  Built on the host (fastdiv_make).
@@ -263,7 +272,7 @@ enum : uint32_t { kTailStripes = 64u, kTailStrideWords = 32u, kTailWordsPerQueue
 
 // Shade queue of one surface class: what the shading pass needs of a hit, written by the traversal kernel in queue order and read
 // back linearly (no gather by ray index):  a = direction.xyz | path id,  b = t, u, v | hit id,  c = origin.xyz | unused.
-// `c` is not written at bounce 0 (every camera ray starts at the eye).  A slot whose path id is HOLE is skipped.
+// `c` is not written at bounce 0 (every camera ray starts at the eye) unless a thin lens is set.  A slot whose path id is HOLE is skipped.
 struct ShadeQueue
 {
     f4* a;

@@ -182,12 +182,14 @@ class CameraDesc:
     target: tuple
     fov: float          # vertical, degrees (camera.rs:20 `fov.to_radians()`)
     aspect_ratio: float
+    aperture: float = 0.0   # thin lens: DIAMETER in world units, 0 = pinhole (pt_set_lens)
+    focus: float = 0.0      # distance of the plane of focus along the view axis
 
 
 class Camera:
     @staticmethod
-    def new(origin, target, fov, aspect_ratio, _aperture=0.0, _focus=0.0) -> CameraDesc:
-        return CameraDesc(_c3(origin), _c3(target), float(fov), float(aspect_ratio))
+    def new(origin, target, fov, aspect_ratio, aperture=0.0, focus=0.0) -> CameraDesc:
+        return CameraDesc(_c3(origin), _c3(target), float(fov), float(aspect_ratio), float(aperture), float(focus))
 
 
 @dataclass

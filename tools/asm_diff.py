@@ -1,4 +1,6 @@
 """Compare two `make asm` outputs kernel by kernel (labels and comments normalised): SAME / DIFF / NEW per kernel.
+A kernel template that gained trailing parameters renames its old instantiations (k<a, b> becomes k<a, b, false>; a kernel that became a
+template, k becomes k<false>): such a kernel is compared with the one it was and marked `+param`.
 usage: python tools/asm_diff.py old.s new.s"""
 import re, subprocess, sys
 
@@ -16,13 +18,26 @@ def dem(n):
     m = re.search(r'(k_\w+(<[^>]*>)?)', d)
     return m.group(1) if m else d[:70]
 
+def was(name, old_names):
+    """the old name of a kernel whose template gained trailing `false` parameters, or None"""
+    d = dem(name)
+    while True:
+        d2 = re.sub(r'(, |<)false>$', lambda m: '>' if m.group(1) == ', ' else '', d)
+        if d2 == d: return None
+        d = d2
+        if d in old_names: return old_names[d]
+
 a, b = funcs(sys.argv[1]), funcs(sys.argv[2])
 print(len(a), 'kernels before,', len(b), 'after')
+old_names = {dem(n): n for n in a if n not in b}
+renamed = set()
 for n in b:
-    if n in a:
-        va = sum(1 for l in a[n] if l.startswith('v_')); vb = sum(1 for l in b[n] if l.startswith('v_'))
-        print('SAME' if a[n] == b[n] else 'DIFF', f'{len(a[n]):6d} {len(b[n]):6d}  valu {va:5d} {vb:5d} ', dem(n))
+    o = n if n in a else was(n, old_names)
+    if o is not None:
+        if o != n: renamed.add(o)
+        va = sum(1 for l in a[o] if l.startswith('v_')); vb = sum(1 for l in b[n] if l.startswith('v_'))
+        print('SAME' if a[o] == b[n] else 'DIFF', f'{len(a[o]):6d} {len(b[n]):6d}  valu {va:5d} {vb:5d} ', dem(n), '' if o == n else '+param')
     else:
         print('NEW ', f'{"":6s} {len(b[n]):6d}  valu {"":5s} {sum(1 for l in b[n] if l.startswith("v_")):5d} ', dem(n))
 for n in a:
-    if n not in b: print('GONE', dem(n))
+    if n not in b and n not in renamed: print('GONE', dem(n))
