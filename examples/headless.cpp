@@ -9,6 +9,9 @@
 //       process: a long render stopped and continued (pt_read_frame / pt_write_accumulation)
 //   examples/headless ... --aperture A --focus F   thin lens of diameter A focused at distance F (default: the reference's pinhole, 0 and 950)
 //   examples/headless ... --denoise den.png   also writes the final frame through the edge-aware denoiser (guides of the last frame's sample)
+//   examples/headless ... --bake-probes NX NY NZ SPP probes.txt   after the usual render, bakes SPP samples into an NX x NY x NZ grid of
+//       irradiance probes spanning the scene's bounds shrunk by 5 % per side (x fastest, then y, then z; stream keys 0, 1, ...) and
+//       writes one line per probe: its 27 raw spherical-harmonics sums [k][c] as hexadecimal floats (%a)
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -30,6 +33,8 @@ int main(int argc, char** argv)
     bool render_mode = false;
     uint32_t render_first = 0, render_count = 0;
     float aperture = 0.0f, focus = 950.0f; // main.rs:127's values: a pinhole
+    uint32_t probes[3] = {0, 0, 0}, probe_spp = 0;
+    std::string probes_out = "";
     for (int i = 1; i < argc; ++i)
     {
         const std::string a = argv[i];
@@ -50,6 +55,12 @@ int main(int argc, char** argv)
         else if (a == "--gpus") gpus = (uint32_t)std::atoi(next("--gpus"));
         else if (a == "--spp") spp = (uint32_t)std::atoi(next("--spp"));
         else if (a == "--render") { render_mode = true; render_first = (uint32_t)std::atoi(next("--render")); render_count = (uint32_t)std::atoi(next("--render")); }
+        else if (a == "--bake-probes")
+        {
+            for (uint32_t& n : probes) n = (uint32_t)std::atoi(next("--bake-probes"));
+            probe_spp = (uint32_t)std::atoi(next("--bake-probes"));
+            probes_out = next("--bake-probes");
+        }
         else if (a == "--load-state") load_state = next("--load-state");
         else if (a == "--save-state") save_state = next("--save-state");
         else if (a == "--devices")
@@ -59,7 +70,7 @@ int main(int argc, char** argv)
         }
         else if (a == "--help" || a == "-h")
         {
-            std::printf("usage: %s [--width W] [--height H] [--frames N] [--bounces B] [--move] [--models DIR] [--out file.png] [--denoise file.png] [--aperture A --focus F]\n", argv[0]);
+            std::printf("usage: %s [--width W] [--height H] [--frames N] [--bounces B] [--move] [--models DIR] [--out file.png] [--denoise file.png] [--aperture A --focus F] [--bake-probes NX NY NZ SPP file.txt]\n", argv[0]);
             return 0;
         }
         else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
@@ -104,6 +115,35 @@ int main(int argc, char** argv)
             return 0;
         }
         Renderer renderer(scene, cam, width, height, bounces);
+        // light probes for a run-time consumer: a regular grid inside the scene's bounds, baked by the path tracer
+        auto bake_probes = [&]() -> bool {
+            if (probes_out.empty()) return true;
+            const std::array<float, 6> box = renderer.root_box();
+            std::vector<float> pos;
+            float axis[3][2];
+            for (int k = 0; k < 3; ++k)
+            {
+                const float ext = box[3 + k] - box[k], margin = 0.05f * ext;
+                axis[k][0] = box[k] + margin;
+                axis[k][1] = box[3 + k] - margin;
+            }
+            auto at = [&](int k, uint32_t i) {
+                if (probes[k] < 2) return 0.5f * (axis[k][0] + axis[k][1]);
+                const float t = (float)i / (float)(probes[k] - 1), span = axis[k][1] - axis[k][0], step = span * t;
+                return axis[k][0] + step;
+            };
+            for (uint32_t z = 0; z < probes[2]; ++z)
+                for (uint32_t y = 0; y < probes[1]; ++y)
+                    for (uint32_t x = 0; x < probes[0]; ++x) { pos.push_back(at(0, x)); pos.push_back(at(1, y)); pos.push_back(at(2, z)); }
+            std::vector<float> sh;
+            renderer.bake_probes(pos, probe_spp, sh);
+            std::FILE* f = std::fopen(probes_out.c_str(), "w");
+            if (!f) { std::fprintf(stderr, "cannot write %s\n", probes_out.c_str()); return false; }
+            for (size_t j = 0; j < pos.size() / 3; ++j)
+                for (int k = 0; k < 27; ++k) std::fprintf(f, "%a%c", (double)sh[j * 27 + k], k == 26 ? '\n' : ' ');
+            std::fclose(f);
+            return true;
+        };
         if (render_mode)
         {
             // checkpoint / resume: the state file is {width, height, data rgba, position xyzt, id} of the frame as it lies on the device
@@ -134,7 +174,7 @@ int main(int argc, char** argv)
             }
             std::printf("{\"first_sample\": %u, \"samples\": %u, \"width\": %u, \"height\": %u}\n", render_first, render_count, width, height);
             if (!out.empty()) renderer.write_image(out);
-            return 0;
+            return bake_probes() ? 0 : 1;
         }
         Mat4 last_inv_proj = renderer.inv_projection();
 
@@ -164,6 +204,7 @@ int main(int argc, char** argv)
             renderer.denoise();
             renderer.write_denoised_image(denoise_out);
         }
+        if (!bake_probes()) return 1;
     }
     catch (const Error& e)
     {

@@ -313,6 +313,76 @@ int pt_write_denoised_image(pt_ctx* ctx, const char* path); /* pt_write_image of
 int pt_post_denoise(pt_ctx* ctx, uint32_t w, uint32_t h, const pt_denoise_params* p, const float* accum_rgba, const float* position_xyzt,
                     const float* normal_xyz, const uint32_t* model, const float* sumsq, float* out_rgba);
 
+/* ---- caller-supplied rays: "what radiance arrives along THIS ray?" ---------------------------------------------------- */
+/* Every render entry point above starts its paths at the context's camera.  pt_integrate_rays runs the same wavefront integrator over rays the
+ * caller supplies: light probes and lightmaps, cameras the library does not model (stereo pairs, panoramas, fisheyes, orthographic views,
+ * cube-map faces), a light meter.  A context that never calls these entry points allocates and launches nothing for them.
+ *
+ * Ray i is Ray::new(o[i], d[i]) with t_max = +inf; the direction is used as given, NOT normalised.  Its path is integrate()
+ * (integrator.rs:143-281) with the counter-based stream of (pixel = key[i], sample = sample[i]) under the context's seed, draws_consumed draws
+ * of it already spent (a camera ray: 1, a lens ray: 2), an empty volume stack, and the context's max_bounces, enable_nee and environment.
+ * key is a full 32-bit value and need not be a pixel of the image; sample likewise.
+ * Inputs: o_xyz, d_xyz 3 floats per ray, key, sample one word per ray.  Outputs per ray, any may be NULL:
+ *   radiance_rgba : 4 floats, exactly what pt_render_samples returns for a camera ray that is this ray with this key (the finalised sample:
+ *                   finite check, length clamp 100, alpha 1)
+ *   position_xyzt : 4 floats, the first hit r.at(t) | t; a miss gives r.at(1e5) | 1e5
+ *   id            : the id byte of that sample (the hit model's index, low byte); 255 for a miss
+ * A ray's result depends on nothing but (scene, config, ray, key, sample, draws_consumed): not on n, its index, its neighbours, the batch
+ * cut, the number of pipelines, where the BVH lives, the walk variant or the rank.  A rank context (world_size > 1) integrates all n rays:
+ * rays are not pixels.  ORDER MATTERS FOR SPEED, not for results: consecutive rays share a wave, so list rays that start near each other and
+ * point the same way next to each other (a camera's rays pixel-major with a pixel's samples consecutive is the order a render uses).
+ * The call never touches the accumulation, the position and id history, the moments or the guides, and does not make them stale.  No
+ * primary-ray cull applies.  pt_stats.paths grows by n and the three ray tallies count these rays like any others.
+ * Errors, all before any device call: PT_ERR_STATE without a built scene (no camera is needed) or with NEE enabled and no emissive model;
+ * PT_ERR_ARG for a NULL o_xyz, d_xyz, key, sample or p with n > 0, a non-zero reserved word, and in the host-pointer variant for a ray with a
+ * component of o or d that is not finite (pt_last_error names the first such ray).  n = 0 is PT_OK and does nothing.  n has no upper limit
+ * other than host and device memory: the list is cut into wavefront batches of at most 2^29 - 1 paths (the path-id width), sized to the
+ * device memory like a render's and alternating over the context's pipelines.  A failed call leaves the frame state as it was (the outputs
+ * are then undefined).  Blocking. */
+typedef struct pt_rays_params
+{
+    uint32_t draws_consumed; /* stream draws every path starts with already spent (a camera ray: 1, a lens ray: 2) */
+    uint32_t batch_rays;     /* 0 = as many as fit; otherwise rays per wavefront batch (a test knob, like batch_spp) */
+    uint32_t reserved[2];    /* must be 0 */
+} pt_rays_params;
+int pt_integrate_rays(pt_ctx* ctx, uint64_t n, const float* o_xyz, const float* d_xyz, const uint32_t* key, const uint32_t* sample,
+                      const pt_rays_params* p, float* radiance_rgba, float* position_xyzt, uint8_t* id);
+/* The same with every array a DEVICE pointer of the layout above (o_xyz, d_xyz: 3 packed floats per ray, 4-byte aligned; radiance_rgba,
+ * position_xyzt: 16-byte aligned); the inputs are read in place, the results stay on the device and are complete when the call returns.
+ * Finite ray components are the caller's precondition here (a ray with a NaN or infinite component has an undefined result; no other ray's
+ * result changes).  p is a host pointer. */
+int pt_integrate_rays_device(pt_ctx* ctx, uint64_t n, const float* o_xyz, const float* d_xyz, const uint32_t* key, const uint32_t* sample,
+                             const pt_rays_params* p, float* radiance_rgba, float* position_xyzt, uint8_t* id);
+
+/* ---- irradiance probes: incident radiance at a point, projected onto spherical harmonics bands 0-2 on the device ------------ */
+/* Probe j (j < n_probes) at position_xyz[j] casts samples [first_sample, first_sample + n_samples) uniformly over the sphere and folds what
+ * arrives into 9 coefficients per colour channel.  In binary32, every operation rounded once, no contraction, in this order, for sample s:
+ *     seed = draw 0 of the stream (key_base + j, s);  (u1, u2) = ss_sobol(n_sobol, s, seed)                  -- as main.rs:193-194
+ *     z = 1 - 2 * u1;  r2 = 1 - z * z;  r = sqrt(r2 > 0 ? r2 : 0);  phi = 6.2831855f * u2;  (sn, cs) = sincos_det(phi)
+ *     d = (r * cs, r * sn, z)                                                                                 -- not renormalised
+ *     L = radiance of pt_integrate_rays for (o = position[j], d, key_base + j, s, draws_consumed = 1)
+ *     y0 = 0.2820948f;  y1 = 0.48860252f * d.y;  y2 = 0.48860252f * d.z;  y3 = 0.48860252f * d.x
+ *     y4 = 1.0925484f * (d.x * d.y);  y5 = 1.0925484f * (d.y * d.z);  y6 = 0.31539157f * (3 * (d.z * d.z) - 1)
+ *     y7 = 1.0925484f * (d.x * d.z);  y8 = 0.54627424f * (d.x * d.x - d.y * d.y)
+ *     sh27[j][k][c] = sh27[j][k][c] + L[c] * y_k        for s ascending, k = 0..8, c = r, g, b
+ * sh27 (host, n_probes * 27 floats) is IN/OUT: the sums continue from what it holds (zero it for a fresh bake), so bake(0, a) followed by
+ * bake(a, b) is bake(0, a + b) bit for bit.  The sums are RAW: the Monte-Carlo factor 4 pi / n and any cosine-lobe convolution (irradiance
+ * from radiance) are the caller's.  The directions are made and the sums folded on the device; the rays go through pt_integrate_rays'
+ * batches probe-major with a probe's samples consecutive, and however they are cut the fold order is the sample order.
+ * pt_config.batch_spp, a render's test knob, cuts here too: wavefront batches of batch_spp * n_probes rays.  The frame is not touched.
+ * Errors, before any device call: PT_ERR_STATE as pt_integrate_rays; PT_ERR_ARG for a NULL position_xyz, p or sh27 with n_probes > 0,
+ * n_samples == 0, a non-zero reserved word, a position that is not finite, key_base + n_probes or first_sample + n_samples beyond 2^32.
+ * Out of scope: higher bands, cosine-convolved output, visibility or depth moments, probe placement. */
+typedef struct pt_probe_params
+{
+    uint32_t first_sample, n_samples; /* samples [first_sample, first_sample + n_samples) of every probe */
+    uint32_t key_base;                /* probe j draws from the stream of pixel key_base + j */
+    uint32_t reserved;                /* must be 0 */
+} pt_probe_params;
+int pt_bake_probes(pt_ctx* ctx, uint32_t n_probes, const float* position_xyz, const pt_probe_params* p, float* sh27);
+/* direction d and basis values y0..y8 of sample `sample` of the probe whose stream is pixel `key`, as the bake makes them.  Host evaluation, no GPU. */
+int pt_probe_ray(pt_ctx* ctx, uint32_t key, uint32_t sample, float d[3], float y9[9]);
+
 /* ---- unit hooks: TLAS::intersect / any_intersect  src/tlas.rs:66, 111 ------------------------------------------ */
 /* which: 0 world TLAS, 1 lights TLAS.  Host SoA in, host SoA out.  miss => inst = prim = 0xffffffff, t = +inf.
  * inst = TLAS leaf index in allocation order, prim = triangle index inside its BLAS (load order). */

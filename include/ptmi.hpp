@@ -134,6 +134,13 @@ struct Frame
     std::vector<uint32_t> id;          // W*H: (old << 16) | new                                        main.rs:137,206
 };
 
+// what Renderer::integrate_rays returns, per ray: the finalised sample (rgb, 1), the first hit (xyz, t) and its id byte (255 = miss)
+struct RayResults
+{
+    std::vector<float> radiance, position; // n * 4 each
+    std::vector<uint8_t> id;               // n
+};
+
 // Scene::new on a context: materials in first-use order, models, pt_build
 inline void upload(pt_ctx* ctx_, const Scene& scene)
 {
@@ -242,6 +249,36 @@ public:
     void render_guides(uint32_t sample) { check(pt_render_guides(ctx_, sample)); }
     void denoise(const pt_denoise_params& p = pt_denoise_params{}) { check(pt_denoise(ctx_, &p, nullptr)); }
     void write_denoised_image(const std::string& path) const { check(pt_write_denoised_image(ctx_, path.c_str())); }
+    // caller-supplied rays (pt_integrate_rays): o, d 3 floats per ray (d is used as given), key and sample one word per ray naming each path's
+    // stream.  Consecutive rays share a wave: order them coherently for speed; the results do not depend on the order.
+    RayResults integrate_rays(const std::vector<float>& o, const std::vector<float>& d, const std::vector<uint32_t>& key, const std::vector<uint32_t>& sample,
+                              uint32_t draws_consumed = 1, uint32_t batch_rays = 0)
+    {
+        const size_t n = key.size();
+        if (o.size() != 3 * n || d.size() != 3 * n || sample.size() != n) throw Error(PT_ERR_ARG, "integrate_rays: o, d, key and sample do not describe the same number of rays");
+        RayResults out;
+        out.radiance.resize(n * 4); out.position.resize(n * 4); out.id.resize(n);
+        pt_rays_params p{};
+        p.draws_consumed = draws_consumed; p.batch_rays = batch_rays;
+        check(pt_integrate_rays(ctx_, n, o.data(), d.data(), key.data(), sample.data(), &p, out.radiance.data(), out.position.data(), out.id.data()));
+        return out;
+    }
+    // irradiance probes (pt_bake_probes): adds samples [first_sample, first_sample + n_samples) of every probe (3 floats each) to the raw
+    // spherical-harmonics sums sh27 (27 floats per probe, [k][c]); an empty sh27 starts a fresh bake from zero
+    void bake_probes(const std::vector<float>& positions, uint32_t n_samples, std::vector<float>& sh27, uint32_t first_sample = 0, uint32_t key_base = 0)
+    {
+        if (positions.size() % 3 != 0) throw Error(PT_ERR_ARG, "bake_probes: positions are 3 floats per probe");
+        const size_t n = positions.size() / 3;
+        if (sh27.empty()) sh27.assign(n * 27, 0.0f);
+        if (sh27.size() != n * 27 || n > 0xffffffffull) throw Error(PT_ERR_ARG, "bake_probes: sh27 does not hold 27 values per probe");
+        pt_probe_params p{};
+        p.first_sample = first_sample; p.n_samples = n_samples; p.key_base = key_base;
+        check(pt_bake_probes(ctx_, (uint32_t)n, positions.data(), &p, sh27.data()));
+    }
+    // direction and y0..y8 of a probe sample as bake_probes makes them (host evaluation)
+    void probe_ray(uint32_t key, uint32_t sample, float d[3], float y9[9]) const { check(pt_probe_ray(ctx_, key, sample, d, y9)); }
+    // the world TLAS's root box: min xyz, max xyz
+    std::array<float, 6> root_box() const { uint32_t rect[4]; std::array<float, 6> b{}; check(pt_active_pixels(ctx_, rect, b.data())); return b; }
     pt_stats stats() const { pt_stats s{}; check(pt_get_stats(ctx_, &s)); return s; }
     pt_ctx* handle() const { return ctx_; }
 

@@ -38,6 +38,7 @@ EXPORTS = [
     "pt_multi_create", "pt_multi_destroy", "pt_multi_last_error", "pt_multi_ctx", "pt_multi_render", "pt_multi_framebuffer_device_ptr",
     "pt_multi_reset_accumulation", "pt_multi_get_stats", "pt_multi_used_rccl", "pt_multi_write_image",
     "pt_render_guides", "pt_read_guides", "pt_denoise", "pt_write_denoised_image", "pt_post_denoise",
+    "pt_integrate_rays", "pt_integrate_rays_device", "pt_bake_probes", "pt_probe_ray",
 ]
 
 
@@ -80,6 +81,16 @@ class Adaptive(C.Structure):
 class DenoiseParams(C.Structure):
     """pt_denoise_params: the a-trous filter's levels and edge-stopping widths (include/pt_api.h); 0 selects each default"""
     _fields_ = [("iterations", C.c_uint32), ("sigma_luminance", C.c_float), ("sigma_normal", C.c_uint32), ("sigma_plane", C.c_float)]
+
+
+class RaysParams(C.Structure):
+    """pt_rays_params: the draws a ray list's paths start with and the batch cut (include/pt_api.h)"""
+    _fields_ = [("draws_consumed", C.c_uint32), ("batch_rays", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class ProbeParams(C.Structure):
+    """pt_probe_params: the sample range and stream keys of a probe bake (include/pt_api.h)"""
+    _fields_ = [("first_sample", C.c_uint32), ("n_samples", C.c_uint32), ("key_base", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class PtError(RuntimeError):
@@ -189,6 +200,10 @@ def lib():
         L.pt_denoise.argtypes = [vp, C.POINTER(DenoiseParams), vp]
         L.pt_write_denoised_image.argtypes = [vp, C.c_char_p]
         L.pt_post_denoise.argtypes = [vp, u32, u32, C.POINTER(DenoiseParams), vp, vp, vp, vp, vp, vp]
+        L.pt_integrate_rays.argtypes = [vp, C.c_uint64, vp, vp, vp, vp, C.POINTER(RaysParams), vp, vp, vp]
+        L.pt_integrate_rays_device.argtypes = [vp, C.c_uint64, vp, vp, vp, vp, C.POINTER(RaysParams), vp, vp, vp]
+        L.pt_bake_probes.argtypes = [vp, u32, vp, C.POINTER(ProbeParams), vp]
+        L.pt_probe_ray.argtypes = [vp, u32, u32, vp, vp]
         _lib = L
     return _lib
 
@@ -535,6 +550,61 @@ class Renderer:
         prm = DenoiseParams(iterations, sigma_luminance, sigma_normal, sigma_plane)
         self._chk(self.L.pt_post_denoise(self.ctx, w, h, C.byref(prm), _p(accum), _p(position), _p(normal), _p(model), _p(q), _p(out)))
         return out
+
+    # ---- caller-supplied rays and irradiance probes
+    def integrate_rays(self, o, d, key, sample, draws_consumed=1, batch_rays=0):
+        """The radiance arriving along caller-supplied rays (pt_integrate_rays): o, d (n, 3) float32 (d is used as given), key and sample (n,)
+        uint32 naming each path's stream.  Returns (radiance (n, 4), first-hit position xyz|t (n, 4), id byte (n,)).  With torch tensors on the
+        GPU for all four inputs the rays are read in place and the three results are GPU tensors (pt_integrate_rays_device)."""
+        if type(o).__module__.startswith("torch"):
+            return self._integrate_rays_device(o, d, key, sample, draws_consumed, batch_rays)
+        o = np.ascontiguousarray(o, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(d, np.float32).reshape(-1, 3)
+        key = np.ascontiguousarray(key, np.uint32).reshape(-1)
+        sample = np.ascontiguousarray(sample, np.uint32).reshape(-1)
+        n = o.shape[0]
+        if d.shape[0] != n or key.size != n or sample.size != n:
+            raise PtError(-1, "integrate_rays: o, d, key and sample do not describe the same number of rays")
+        rad = np.zeros((n, 4), np.float32); pos = np.zeros((n, 4), np.float32); idb = np.zeros(n, np.uint8)
+        prm = RaysParams(draws_consumed, batch_rays)
+        self._chk(self.L.pt_integrate_rays(self.ctx, n, _p(o), _p(d), _p(key), _p(sample), C.byref(prm), _p(rad), _p(pos), _p(idb)))
+        return rad, pos, idb
+
+    def _integrate_rays_device(self, o, d, key, sample, draws_consumed, batch_rays):
+        import torch
+        n = o.shape[0]
+        ts = (o, d, key, sample)
+        if not all(t.is_cuda and t.is_contiguous() for t in ts) or o.dtype != torch.float32 or d.dtype != torch.float32 or \
+                key.dtype not in (torch.int32, torch.uint32) or sample.dtype not in (torch.int32, torch.uint32):
+            raise PtError(-1, "integrate_rays: device rays are contiguous GPU tensors, o and d float32, key and sample 32-bit integers")
+        if o.numel() != 3 * n or d.numel() != 3 * n or key.numel() != n or sample.numel() != n:
+            raise PtError(-1, "integrate_rays: o, d, key and sample do not describe the same number of rays")
+        rad = torch.zeros((n, 4), dtype=torch.float32, device=o.device); pos = torch.zeros((n, 4), dtype=torch.float32, device=o.device)
+        idb = torch.zeros(n, dtype=torch.uint8, device=o.device)
+        torch.cuda.synchronize(o.device)  # the library launches on its own stream
+        prm = RaysParams(draws_consumed, batch_rays)
+        ptr = lambda t: C.c_void_p(t.data_ptr())
+        self._chk(self.L.pt_integrate_rays_device(self.ctx, n, ptr(o), ptr(d), ptr(key), ptr(sample), C.byref(prm), ptr(rad), ptr(pos), ptr(idb)))
+        return rad, pos, idb
+
+    def bake_probes(self, positions, n_samples, first_sample=0, key_base=0, sh=None):
+        """Irradiance probes (pt_bake_probes): adds samples [first_sample, first_sample + n_samples) of every probe at positions (n, 3) to the raw
+        spherical-harmonics sums sh (n, 9, 3) float32 (None: a fresh bake from zero) and returns them.  The factor 4 pi / samples and the
+        cosine-lobe convolution are the caller's."""
+        pos = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
+        n = pos.shape[0]
+        out = np.zeros((n, 9, 3), np.float32) if sh is None else np.ascontiguousarray(sh, np.float32)
+        if out.size != n * 27:
+            raise PtError(-1, "bake_probes: sh does not hold 27 values per probe")
+        prm = ProbeParams(first_sample, n_samples, key_base, 0)
+        self._chk(self.L.pt_bake_probes(self.ctx, n, _p(pos), C.byref(prm), _p(out)))
+        return out.reshape(n, 9, 3)
+
+    def probe_ray(self, key: int, sample: int):
+        """(direction, y0..y8) of sample `sample` of the probe whose stream is pixel `key`, as bake_probes makes them; host evaluation"""
+        d = np.zeros(3, np.float32); y = np.zeros(9, np.float32)
+        self._chk(self.L.pt_probe_ray(self.ctx, key, sample, _p(d), _p(y)))
+        return d, y
 
     # ---- unit hooks
     def trace_closest(self, o, d, tmax=None, which=0):

@@ -19,6 +19,7 @@
 #include "pt_batch_plan.h"
 #include "pt_kernels.h"
 #include "pt_png.h"
+#include "pt_probe.h"
 #include "pt_scene.h"
 
 using namespace pt;
@@ -119,6 +120,7 @@ struct pt_ctx
         uint32_t slack_cfg = 0;         // pt_config.queue_slack the pool was sized with
         uint32_t pixels_cfg = 0;        // local pixel count the pool was sized with (first-hit buffers)
         size_t state_bytes = 0;
+        DevBuf ray_pos, ray_id;         // first-hit records of a ray batch, one per path (pt_integrate_rays; the pool's hold one per pixel)
         bool busy = false;              // a batch has been launched and not yet harvested
         uint32_t busy_rows = 0;
         uint64_t busy_paths = 0, busy_culled = 0;
@@ -165,6 +167,10 @@ struct pt_ctx
     uint64_t config_version = 0; // bumped by pt_set_config
     DevBuf d_dn_a, d_dn_b, d_dn_nv, d_dn_out;
     bool denoised_valid = false;
+
+    // pt_integrate_rays_device: the callers' stream keys side by side, 8 bytes per ray of the longest list so far (kept: allocating and freeing
+    // it per call would synchronise the device twice per call).  Nothing is allocated until the first call.
+    DevBuf d_ray_keys;
 
     // stats
     pt_stats stats{};
@@ -741,6 +747,17 @@ struct BatchSpec
     bool write_position = false;   // the last batch of the request: its first-hit positions are kept
     f4* samples_out = nullptr;     // the batch's samples go here instead of into the accumulation
     bool aux_with_samples = false; // pt_frame: position / id history are updated beside samples_out
+    const struct RayBatch* rays = nullptr; // a window of a caller's ray list instead of samples of pixels (pt_integrate_rays): ar = one row of its rays, count 1
+};
+// one batch of pt_integrate_rays: the window's rays, the draws they start with and where their results go (device pointers at the window's
+// first ray; any output may be null)
+struct RayBatch
+{
+    RayView view{};
+    uint32_t draws = 0;
+    f4* radiance = nullptr;
+    f4* position = nullptr;
+    uint8_t* id = nullptr;
 };
 struct BatchRun
 {
@@ -751,6 +768,7 @@ struct BatchRun
     LensView lens{};
     EnvView env{};
     TraceLaunch tl{}, tl_side{};
+    WavefrontBuffers wb{};         // the pipeline's; a ray batch keeps its first-hit records in Pipe::ray_pos / ray_id
     hipStream_t s = nullptr;
     uint32_t rows = 0, shade_blocks = 1, last_row = 0, cleared_rows = 0;
     bool nee = false, side_busy = false, stopped = false, fused = false;
@@ -800,7 +818,14 @@ int batch_begin(BatchRun& br, pt_ctx* c, const BatchSpec& spec)
     br.rows = g.max_bounces + 2;
     br.last_row = br.rows - 1;
     br.s = c->pipe_stream(pipe);
-    const WavefrontBuffers& wb = pp.wb;
+    br.wb = pp.wb;
+    if (spec.rays)
+    {
+        rp.ray_draws = spec.rays->draws;
+        br.wb.st.first_pos = (f4*)pp.ray_pos.p;
+        br.wb.st.first_id = (uint32_t*)pp.ray_id.p;
+    }
+    const WavefrontBuffers& wb = br.wb;
     br.tl = trace_launch(c, pipe, false);
     br.tl_side = trace_launch(c, pipe, true);
     br.cam = c->scene.camera_view();
@@ -822,7 +847,12 @@ int batch_begin(BatchRun& br, pt_ctx* c, const BatchSpec& spec)
     HIPCHK(c, hipMemsetAsync(wb.wave_times, 0, (size_t)br.rows * kWaveTimeSlots * 16, br.s));
     HIPCHK(c, hipMemsetAsync(wb.wave_times_any, 0, (size_t)br.rows * kWaveTimeSlots * 16, br.s));
 #endif
-    if (rp.n_paths) { Timer t(c, pp, br.s, T_GEN); launch_generate(br.s, rp, br.cam, br.lens, wb, c->cur_list); }
+    if (rp.n_paths)
+    {
+        Timer t(c, pp, br.s, T_GEN);
+        if (spec.rays) launch_generate_rays(br.s, rp, spec.rays->view, wb);
+        else launch_generate(br.s, rp, br.cam, br.lens, wb, c->cur_list);
+    }
     br.shade_blocks = (uint32_t)std::max<size_t>(1, std::min<size_t>(((size_t)rp.n_paths + 255) / 256, (size_t)c->n_cus * PT_SHADE_BLOCKS_PER_CU));
     br.nee = g.enable_nee != 0;
     // PT_FUSED_TRACE: the BSDF-sampled NEE rays of a bounce ride in the next bounce's world closest-hit launch (k_trace_fused) instead of
@@ -843,7 +873,7 @@ void batch_nee_launches(BatchRun& br, uint32_t row)
 {
     pt_ctx* c = br.c;
     pt_ctx::Pipe& pp = c->pipe[br.spec.pipe];
-    const WavefrontBuffers& wb = pp.wb;
+    const WavefrontBuffers& wb = br.wb;
     const bool timing_all = (c->cfg.flags & PT_FLAG_TIMING_ALL) != 0; // per-launch events want one stream
     // a small batch (an interactive 1-spp frame) gains nothing from the second stream and pays ~20 us per bounce for the two
     // cross-stream event waits: its two launches go out one after the other
@@ -873,7 +903,7 @@ int batch_bounce(BatchRun& br, uint32_t b)
     pt_ctx* c = br.c;
     pt_ctx::Pipe& pp = c->pipe[br.spec.pipe];
     const pt_config& g = c->cfg;
-    const WavefrontBuffers& wb = pp.wb;
+    const WavefrontBuffers& wb = br.wb;
     hipStream_t s = br.s;
     // bounce b touches rows b and b + 1 (the shading pass appends to the next bounce's queues)
     while (br.cleared_rows < std::min<uint32_t>(br.rows, b + 2u))
@@ -896,11 +926,11 @@ int batch_bounce(BatchRun& br, uint32_t b)
 #if !PT_JOIN_LATE
         batch_join_side(br);
 #endif
-        { Timer t(c, pp, s, T_WORLD); launch_trace_world(s, br.tl, wb, b, br.rp, br.cam, br.lens, br.env); }
+        { Timer t(c, pp, s, T_WORLD); launch_trace_world(s, br.tl, wb, b, br.rp, br.cam, br.lens, br.env, br.spec.rays != nullptr); }
         batch_join_side(br);
     }
     for (uint32_t q = 0; q < Q_COUNT; ++q)
-        if (c->class_present[q]) { Timer t(c, pp, s, T_SHADE); launch_shade(s, q, c->sv, br.rp, wb, b, br.shade_blocks, br.cam, br.lens, br.env, &br.tl, c->cur_list); }
+        if (c->class_present[q]) { Timer t(c, pp, s, T_SHADE); launch_shade(s, q, c->sv, br.rp, wb, b, br.shade_blocks, br.cam, br.lens, br.env, &br.tl, c->cur_list, br.spec.rays ? br.spec.rays->view.key : nullptr); }
     // long bounce budgets (reference default MAX_BOUNCES = 1024): stop once no path is left
     if (g.max_bounces > 16 && b >= 8 && (b % 4) == 0 && b < g.max_bounces)
     {
@@ -919,7 +949,7 @@ int batch_end(BatchRun& br, hipEvent_t after)
     pt_ctx* c = br.c;
     pt_ctx::Pipe& pp = c->pipe[br.spec.pipe];
     const pt_config& g = c->cfg;
-    const WavefrontBuffers& wb = pp.wb;
+    const WavefrontBuffers& wb = br.wb;
     hipStream_t s = br.s;
     const RenderParams& rp = br.rp;
     if (br.last_row == br.rows - 1) br.last_row = g.max_bounces + 1;
@@ -932,7 +962,12 @@ int batch_end(BatchRun& br, hipEvent_t after)
     }
     if (br.nee_err) return fail(c, PT_ERR_HIP, "stream fork/join failed");
     if (after && hipStreamWaitEvent(s, after, 0) != hipSuccess) return fail(c, PT_ERR_HIP, "hipStreamWaitEvent");
-    if (br.spec.samples_out)
+    if (br.spec.rays)
+    {
+        Timer t(c, pp, s, T_ACCUM);
+        launch_store_rays(s, rp, br.spec.rays->view, wb, br.spec.rays->radiance, br.spec.rays->position, br.spec.rays->id);
+    }
+    else if (br.spec.samples_out)
     {
         launch_store_samples(s, rp, wb, br.spec.samples_out);
         // pt_frame: the frame's own colour goes to the input texture, position / id history are still updated
@@ -952,8 +987,8 @@ int batch_end(BatchRun& br, hipEvent_t after)
     HIPCHK(c, hipMemcpyAsync(pp.h_heads, wb.heads, (size_t)used_rows * HEADS_PER_ROW * kHeadWordsPerQueue * 4, hipMemcpyDeviceToHost, s));
     pp.busy = true;
     pp.busy_rows = used_rows;
-    pp.busy_paths = (uint64_t)(c->cur_list ? rp.act_pixels : rp.local_pixels) * br.spec.count;
-    pp.busy_culled = c->cur_list ? 0u : (uint64_t)(rp.local_pixels - rp.act_pixels) * br.spec.count;
+    pp.busy_paths = (uint64_t)((c->cur_list || br.spec.rays) ? rp.act_pixels : rp.local_pixels) * br.spec.count;
+    pp.busy_culled = (c->cur_list || br.spec.rays) ? 0u : (uint64_t)(rp.local_pixels - rp.act_pixels) * br.spec.count;
     return PT_OK;
 }
 
@@ -1132,6 +1167,125 @@ int render_batches(pt_ctx* c, uint32_t first_sample, uint32_t n_samples, float* 
         return err;
     }
     c->stats.ms_total += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return PT_OK;
+}
+
+// ---- caller-supplied rays (pt_integrate_rays)
+// what a ray call can be refused for without touching the device, beyond its own arguments (no camera is needed)
+int rays_precheck(pt_ctx* c)
+{
+    if (!c->scene.built) return fail(c, PT_ERR_STATE, "pt_build has not been called");
+    if (c->cfg.enable_nee && c->scene.flat.lights.empty()) return fail(c, PT_ERR_STATE, "NEE is enabled but the scene has no emissive model");
+    return PT_OK;
+}
+
+// Integrates rays [0, n) of a device-resident table (o, d: 3 floats per ray; key: {pixel, sample} per ray) into device outputs indexed like
+// the table (any may be null).  The list is cut into windows of at most 2^29 - 1 rays, planned like a render's batches (plan_batches with
+// one "pixel" and a ray per "sample"), alternating over the pipelines; a window is one wavefront batch whose path ids index it.  The frame
+// (accumulation, history, moments, guides) is neither read nor written, so a failed call leaves it as it was.  Blocking.
+int integrate_rays_device(pt_ctx* c, uint64_t n, const float* o, const float* d, const uint2* key, uint32_t draws, uint32_t batch_rays, f4* radiance,
+                          f4* position, uint8_t* id)
+{
+    int r;
+    if (n == 0) return PT_OK;
+    if ((r = upload_scene(c)) || (r = ensure_environment(c))) return r;
+    const uint64_t kMaxWindow = (1ull << 29) - 1;
+    const auto t0 = std::chrono::steady_clock::now();
+    int err = PT_OK;
+    // (plan_batches counts in 32 bits: longer lists are planned in segments)
+    for (uint64_t seg0 = 0; seg0 < n && !err; seg0 += 0x80000000ull)
+    {
+        const uint32_t seg_n = (uint32_t)std::min<uint64_t>(n - seg0, 0x80000000ull);
+        PlanRequest q;
+        q.n_samples = seg_n;
+        q.act_pixels = 1;
+        q.pipelines = c->cfg.pipelines;
+        q.batch_spp = (uint32_t)std::min<uint64_t>(batch_rays, kMaxWindow);
+        q.lds_scene = c->lds_scene;
+        q.max_paths = (size_t)96 << 20;
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
+        {
+            size_t held = 0;
+            for (const pt_ctx::Pipe& pp : c->pipe)
+                for (const DevBuf& b : pp.pool) held += b.bytes;
+            uint32_t n_classes = 0;
+            for (uint32_t k = 1; k < Q_COUNT; ++k) n_classes += c->class_present[k] ? 1u : 0u;
+            q.max_paths = max_paths_for(free_b, held, n_classes, c->sv.has_volumes != 0);
+        }
+        for (int i = 0; i < pt_ctx::kMaxPipes; ++i) q.cap_paths[i] = c->pipe[i].cap_paths;
+        const BatchPlan plan = plan_batches(q);
+        if (!plan.batch) return fail(c, PT_ERR_ARG, "batch too large (path ids are 29-bit)");
+        const uint32_t batch = plan.batch, n_pipes = plan.n_pipes;
+        if (n_pipes > 1)
+            for (uint32_t i = 0; i < n_pipes; ++i)
+                if (!c->pipe[i].busy && c->pipe[i].cap_paths > (size_t)batch + batch / 4) free_pipe_pool(c->pipe[i]);
+        for (uint32_t i = 0; i < n_pipes; ++i)
+        {
+            pt_ctx::Pipe& pp = c->pipe[i];
+            if ((r = ensure_wavefront(c, (int)i, batch, c->cfg.max_bounces + 2))) return r;
+            if ((r = dev_alloc(c, pp.ray_pos, (size_t)std::max(batch, 64u) * 16)) || (r = dev_alloc(c, pp.ray_id, (size_t)std::max(batch, 64u) * 4))) return r;
+        }
+        if (n_pipes > 1)
+        {
+            HIPCHK(c, hipEventRecord(c->ev_start, c->stream));
+            for (uint32_t i = 1; i < n_pipes; ++i) HIPCHK(c, hipStreamWaitEvent(c->pipe_stream((int)i), c->ev_start, 0));
+        }
+        hipEvent_t prev_done = nullptr;
+        RayBatch rb[pt_ctx::kMaxPipes];
+        // batch k on pipeline k % n_pipes; the first n_pipes go out bounce by bounce across the pipelines, as in render_batches
+        for (uint32_t done = 0, k = 0; done < seg_n && !err;)
+        {
+            const uint32_t group = (k == 0 && PT_INTERLEAVE_FIRST) ? n_pipes : 1u;
+            BatchRun run[pt_ctx::kMaxPipes];
+            uint32_t m = 0;
+            for (; m < group && done < seg_n && !err; ++m, ++k)
+            {
+                const int pi = (int)(k % n_pipes);
+                const uint32_t cnt = std::min(batch, seg_n - done);
+                const uint64_t first = seg0 + done;
+                // the pipeline's previous batch must be done before its buffers (and its RayBatch) are reused
+                if (!(err = harvest_batch(c, pi)))
+                {
+                    rb[pi] = RayBatch{RayView{o + 3 * first, d + 3 * first, key + first}, draws, radiance ? radiance + first : nullptr,
+                                      position ? position + first : nullptr, id ? id + first : nullptr};
+                    BatchSpec spec{pi, 0u, 1u, ActiveRect{0u, cnt, 0u, 1u}};
+                    spec.rays = &rb[pi];
+                    err = batch_begin(run[m], c, spec);
+                }
+                done += cnt;
+            }
+            if (!err) err = run_group(c, run, m, prev_done);
+        }
+        for (uint32_t i = 0; i < n_pipes; ++i)
+        {
+            const int hr = harvest_batch(c, (int)i);
+            if (hr && !err) err = hr;
+        }
+    }
+    if (err)
+    {
+        // launches of the failed batch and of batches behind it may still be running: wait for everything (the outputs are then incomplete)
+        for (int i = 0; i < pt_ctx::kMaxPipes; ++i)
+        {
+            (void)hipStreamSynchronize(c->pipe_stream(i));
+            if (c->pipe[i].side_stream) (void)hipStreamSynchronize(c->pipe[i].side_stream);
+            c->pipe[i].busy = false;
+            c->pipe[i].ev_used = 0;
+        }
+        (void)hipGetLastError();
+        return err;
+    }
+    // (harvest_batch has waited for every pipeline: whatever the caller queues next on the context's stream comes after the results)
+    c->stats.ms_total += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return PT_OK;
+}
+
+// the arguments of pt_integrate_rays*: everything but the rays' values
+int rays_args_check(pt_ctx* c, uint64_t n, const float* o, const float* d, const uint32_t* key, const uint32_t* sample, const pt_rays_params* p)
+{
+    if (n > 0 && (!o || !d || !key || !sample || !p)) return fail(c, PT_ERR_ARG, "pt_integrate_rays: o_xyz, d_xyz, key, sample and p must not be NULL");
+    if (p && (p->reserved[0] || p->reserved[1])) return fail(c, PT_ERR_ARG, "pt_rays_params.reserved must be 0");
     return PT_OK;
 }
 
@@ -1911,6 +2065,106 @@ int pt_post_denoise(pt_ctx* c, uint32_t w, uint32_t h, const pt_denoise_params* 
     launch_denoise(c->stream, (int)w, (int)h, k, da, dq, dp, dn, dm, (f4*)c->d_dn_a.p, (f4*)c->d_dn_b.p, (f4*)c->d_dn_nv.p, dout);
     HIPCHK(c, hipGetLastError());
     return t.download(out, dout, px * 16);
+}
+
+// ---- caller-supplied rays and irradiance probes
+int pt_integrate_rays(pt_ctx* c, uint64_t n, const float* o, const float* d, const uint32_t* key, const uint32_t* sample, const pt_rays_params* p,
+                      float* radiance, float* position, uint8_t* id)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    int r;
+    if ((r = rays_precheck(c)) || (r = rays_args_check(c, n, o, d, key, sample, p))) return r;
+    for (uint64_t i = 0; i < n; ++i)
+        for (int k = 0; k < 3; ++k)
+            if (!std::isfinite(o[3 * i + k]) || !std::isfinite(d[3 * i + k]))
+                return fail(c, PT_ERR_ARG, "pt_integrate_rays: ray " + std::to_string(i) + " has a component of " + (std::isfinite(o[3 * i + k]) ? "d" : "o") + " that is not finite");
+    if (n == 0) return PT_OK;
+    if ((r = upload_scene(c))) return r;
+    std::vector<uint2> keys(n);
+    for (uint64_t i = 0; i < n; ++i) keys[i] = make_uint2(key[i], sample[i]);
+    Staging st(c);
+    const float* d_o = (const float*)st.in(o, n * 12);
+    const float* d_d = (const float*)st.in(d, n * 12);
+    const uint2* d_key = (const uint2*)st.in(keys.data(), n * 8);
+    f4* d_rad = radiance ? (f4*)st.out(n * 16) : nullptr;
+    f4* d_pos = position ? (f4*)st.out(n * 16) : nullptr;
+    uint8_t* d_id = id ? (uint8_t*)st.out(n) : nullptr;
+    if (st.err) return st.err;
+    if ((r = integrate_rays_device(c, n, d_o, d_d, d_key, p->draws_consumed, p->batch_rays, d_rad, d_pos, d_id))) return r;
+    if (radiance && (r = st.download(radiance, d_rad, n * 16))) return r;
+    if (position && (r = st.download(position, d_pos, n * 16))) return r;
+    if (id && (r = st.download(id, d_id, n))) return r;
+    return PT_OK;
+}
+
+int pt_integrate_rays_device(pt_ctx* c, uint64_t n, const float* o, const float* d, const uint32_t* key, const uint32_t* sample, const pt_rays_params* p,
+                             float* radiance, float* position, uint8_t* id)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    int r;
+    if ((r = rays_precheck(c)) || (r = rays_args_check(c, n, o, d, key, sample, p))) return r;
+    if (n == 0) return PT_OK;
+    if ((r = upload_scene(c))) return r;
+    // the stream keys side by side, as the shading passes read them: one 8-byte entry per ray
+    if ((r = dev_alloc(c, c->d_ray_keys, n * 8))) return r;
+    uint2* d_key = (uint2*)c->d_ray_keys.p;
+    launch_pack_ray_keys(c->stream, n, key, sample, d_key);
+    return integrate_rays_device(c, n, o, d, d_key, p->draws_consumed, p->batch_rays, (f4*)radiance, (f4*)position, id);
+}
+
+int pt_probe_ray(pt_ctx* c, uint32_t key, uint32_t sample, float d[3], float y9[9])
+{
+    if (!c || !d || !y9) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    probe_ray(c->cfg.seed, c->cfg.n_sobol, key, sample, d, y9);
+    return PT_OK;
+}
+
+int pt_bake_probes(pt_ctx* c, uint32_t n_probes, const float* position, const pt_probe_params* p, float* sh27)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    int r;
+    if ((r = rays_precheck(c))) return r;
+    if (n_probes > 0 && (!position || !p || !sh27)) return fail(c, PT_ERR_ARG, "pt_bake_probes: position_xyz, p and sh27 must not be NULL");
+    if (p)
+    {
+        if (p->reserved) return fail(c, PT_ERR_ARG, "pt_probe_params.reserved must be 0");
+        if (p->n_samples == 0) return fail(c, PT_ERR_ARG, "pt_probe_params.n_samples must be non-zero");
+        if ((uint64_t)p->key_base + n_probes > 0x100000000ull) return fail(c, PT_ERR_ARG, "pt_probe_params.key_base + n_probes wraps 32 bits");
+        if ((uint64_t)p->first_sample + p->n_samples > 0x100000000ull) return fail(c, PT_ERR_ARG, "pt_probe_params.first_sample + n_samples wraps 32 bits");
+    }
+    for (uint64_t i = 0; i < (uint64_t)n_probes * 3; ++i)
+        if (!std::isfinite(position[i])) return fail(c, PT_ERR_ARG, "pt_bake_probes: probe " + std::to_string(i / 3) + " has a position that is not finite");
+    if (n_probes == 0) return PT_OK;
+    if ((r = upload_scene(c))) return r;
+    // The bake's rays, probe-major with a probe's samples consecutive, go through a ray table of at most `chunk` rays at a time: filled on
+    // the device, integrated (in wavefront batches of their own), folded in sample order.  pt_config.batch_spp, a render's test knob, cuts
+    // here as well: wavefront batches of batch_spp * n_probes rays, and three of them per table, so that a probe's samples straddle both.
+    const uint64_t total = (uint64_t)n_probes * p->n_samples;
+    const uint64_t cut = (uint64_t)c->cfg.batch_spp * n_probes;
+    const uint32_t batch_rays = (uint32_t)std::min<uint64_t>(cut, (1ull << 29) - 1);
+    const uint32_t chunk = (uint32_t)std::min<uint64_t>(total, batch_rays ? 3ull * batch_rays : (1ull << 26));
+    Staging st(c);
+    const float* d_position = (const float*)st.in(position, (size_t)n_probes * 12);
+    float* d_sh = (float*)st.in(sh27, (size_t)n_probes * 27 * 4);
+    float* d_o = (float*)st.out((size_t)chunk * 12);
+    float* d_d = (float*)st.out((size_t)chunk * 12);
+    uint2* d_key = (uint2*)st.out((size_t)chunk * 8);
+    f4* d_rad = (f4*)st.out((size_t)chunk * 16);
+    if (st.err) return st.err;
+    const ProbeBake pb{d_position, n_probes, p->first_sample, p->n_samples, p->key_base, c->cfg.n_sobol, c->cfg.seed};
+    for (uint64_t first = 0; first < total; first += chunk)
+    {
+        const uint32_t cnt = (uint32_t)std::min<uint64_t>(chunk, total - first);
+        launch_probe_rays(c->stream, pb, first, cnt, d_o, d_d, d_key);
+        if ((r = integrate_rays_device(c, cnt, d_o, d_d, d_key, 1u, batch_rays, d_rad, nullptr, nullptr))) return r;
+        launch_probe_project(c->stream, pb, first, cnt, d_d, d_rad, d_sh);
+        HIPCHK(c, hipGetLastError());
+    }
+    return st.download(sh27, d_sh, (size_t)n_probes * 27 * 4);
 }
 
 // ---- unit hooks

@@ -59,6 +59,37 @@ inline ShadeQueue shade_queue(const WavefrontBuffers& wb, uint32_t q)
     return ShadeQueue{a, a + wb.q_stride, a + 2u * (size_t)wb.q_stride};
 }
 
+// One batch of a caller's ray list (pt_integrate_rays): the window's rays, every pointer already offset to the window's first ray.  Path id =
+// index inside the window, one path per ray (RenderParams: act_pixels = n_paths = the window's length, batch_samples = 1, so pid_split is the
+// identity and PathState::first_pos / first_id hold one record per path; RenderParams::ray_draws = the draws every path starts with).
+//   o, d : 3 floats per ray (the caller's layout); d is used as given
+//   key  : {pixel, sample} of the ray's stream (stream_key): what the pixel grid or an adaptive list supplies for a camera path
+struct RayView
+{
+    const float* o;
+    const float* d;
+    const uint2* key;
+};
+// out[i] <- {key[i], sample[i]}: RayView::key of a whole list from the caller's two arrays (device pointers)
+void launch_pack_ray_keys(hipStream_t s, uint64_t n, const uint32_t* key, const uint32_t* sample, uint2* out);
+// rq[0] <- the window's rays (t_max +inf, ray index = path id), counters[0].n_closest <- their number
+void launch_generate_rays(hipStream_t s, const RenderParams& rp, const RayView& rays, const WavefrontBuffers& wb);
+// the finisher of a ray batch in launch_accumulate's place: per path the finalised sample (rgb, 1), the first hit r.at(t) | t and its id byte
+// (a miss: r.at(1e5) | 1e5 and 255) to entry [path id] of the three outputs, each of which may be null
+void launch_store_rays(hipStream_t s, const RenderParams& rp, const RayView& rays, const WavefrontBuffers& wb, f4* radiance, f4* position, uint8_t* id);
+// irradiance probes (pt_bake_probes; the definition is include/pt_api.h's and pt_probe.h's).  Ray r of a bake is sample first_sample + r % n_samples
+// of probe r / n_samples.  launch_probe_rays fills rays [first, first + count) of the bake into a ray table at the same indices;
+// launch_probe_project folds the radiance of those rays (d, radiance: the same window, as integrated) into sh27 in sample order, one thread per
+// (probe, coefficient, channel)
+struct ProbeBake
+{
+    const float* position; // 3 floats per probe
+    uint32_t n_probes, first_sample, n_samples, key_base, n_sobol;
+    uint64_t seed;
+};
+void launch_probe_rays(hipStream_t s, const ProbeBake& pb, uint64_t first, uint32_t count, float* o, float* d, uint2* key);
+void launch_probe_project(hipStream_t s, const ProbeBake& pb, uint64_t first, uint32_t count, const float* d, const f4* radiance, float* sh27);
+
 // list: an adaptive list (launch_adaptive_select's {local pixel, n_p} entries, rp.act_pixels of them) whose pixels the batch's paths belong
 // to instead of the active rectangle's (pt_render_adaptive), or null
 // lens: with a radius above 0 (lens_set) the launchers that take one run the thin-lens variants of their kernels (pt_set_lens); the pinhole
@@ -66,8 +97,9 @@ inline ShadeQueue shade_queue(const WavefrontBuffers& wb, uint32_t q)
 inline bool lens_set(const LensView& lens) { return lens.radius > 0.0f; }
 void launch_generate(hipStream_t s, const RenderParams& rp, const CameraView& cam, const LensView& lens, const WavefrontBuffers& wb, const uint2* list = nullptr);
 // closest hit against the world TLAS for bounce `b`: reads rq[b&1], writes hits + shade queues of row b
+// (ray_list: bounce 0 of a ray batch, whose rays have origins of their own like a lens's)
 void launch_trace_world(hipStream_t s, const TraceLaunch& tl, const WavefrontBuffers& wb, uint32_t b, const RenderParams& rp, const CameraView& cam,
-                        const LensView& lens, const EnvView& env);
+                        const LensView& lens, const EnvView& env, bool ray_list = false);
 // the same for bounce b >= 1 together with the BSDF-sampled NEE launch of bounce b - 1, as ONE launch (a wave goes from queue to queue)
 void launch_trace_fused(hipStream_t s, const TraceLaunch& tl, const WavefrontBuffers& wb, uint32_t b, const RenderParams& rp, const EnvView& env);
 // NEE rays produced by the shading of bounce `b` (counter row b)
@@ -75,10 +107,11 @@ void launch_trace_shadow(hipStream_t s, const TraceLaunch& tl, const WavefrontBu
 // BSDF-sampled NEE rays: closest hit against the lights TLAS, then (same kernel, same lane) any-hit against the world
 void launch_trace_lchain(hipStream_t s, const TraceLaunch& tl, const WavefrontBuffers& wb, uint32_t b);
 // shading of bounce b for one queue class
+// (ray_keys: RayView::key of a ray batch, whose paths take their stream from it and start at RenderParams::ray_draws draws)
 // (tl: the scene's traversal launch description; with it the Lambert / GGX passes of an LDS-resident scene may trace their own shadow rays)
 void launch_shade(hipStream_t s, uint32_t qclass, const SceneView& sv, const RenderParams& rp, const WavefrontBuffers& wb, uint32_t b,
                   uint32_t grid_blocks, const CameraView& cam, const LensView& lens, const EnvView& env, const TraceLaunch* tl = nullptr,
-                  const uint2* list = nullptr);
+                  const uint2* list = nullptr, const uint2* ray_keys = nullptr);
 // true: the shading pass answers the explicit-light shadow rays itself and nothing is queued for launch_trace_shadow
 bool shade_traces_shadow(const TraceLaunch& tl);
 // accum[pixel] += sum over batch samples in order of (finalised rgb, 1); position/id of the last samples.  With moments also

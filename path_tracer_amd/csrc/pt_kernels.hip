@@ -16,6 +16,7 @@
 // where they provably equal the SSE select semantics of the reference (see slab()).
 #include "pt_kernels.h"
 #include "pt_camera.h"
+#include "pt_probe.h"
 #include "pt_materials.h"
 
 #include <algorithm>
@@ -1706,6 +1707,28 @@ __global__ void __launch_bounds__(256) k_generate_lens(const RenderParams rp, co
     rq.b[pid] = f4{dir.x, dir.y, dir.z, asf(pid)};
 }
 
+// Ray list (pt_integrate_rays): the batch's path ids index the window of the caller's rays (RayView), one path per ray, and a path's stream is
+// the one its table entry names: {pixel, sample} as given, not a pixel of the image.  (pid_split would return the same s = 0, k = pid.)
+__device__ __forceinline__ PixelId path_pixel_rays(const uint2* __restrict__ keys, uint32_t pid, uint32_t* s_local, uint32_t* k_out)
+{
+    *s_local = 0u;
+    *k_out = pid;
+    const uint2 e = keys[pid];
+    return PixelId{e.x, e.y, 0u, 0u, 0u};
+}
+
+// the camera's place in a ray batch: a copy of the window's rays into the bounce-0 queue
+__global__ void __launch_bounds__(256) k_generate_rays(const uint32_t n, const float* __restrict__ o, const float* __restrict__ d, const RayQueue rq, Counters* ctr)
+{
+    const uint32_t pid = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pid == 0u) ctr[0].n_closest = n;
+    if (pid >= n) return;
+    const float* po = o + 3u * (size_t)pid;
+    const float* pd = d + 3u * (size_t)pid;
+    rq.a[pid] = f4{po[0], po[1], po[2], __builtin_inff()};
+    rq.b[pid] = f4{pd[0], pd[1], pd[2], asf(pid)};
+}
+
 struct ShadeIO
 {
     PathState st;
@@ -1717,7 +1740,8 @@ struct ShadeIO
     union
     {
         const uint2* entries; // terminal pass: {ray index | ENTRY_DEAD, path id}
-        const uint2* list;    // surface passes of an adaptive render (k_shade_surface<..., LIST>): the list's {local pixel, n_p} entries
+        const uint2* list;    // surface passes of an adaptive render (k_shade_surface<..., LIST>): the list's {local pixel, n_p} entries;
+                              // of a ray batch (k_shade_surface<..., RAYS>): the window's {pixel, sample} stream keys (RayView::key)
     };
     ShadeQueue q_in;          // surface pass: this class's hit records in queue order
     const uint32_t* tails_in; // ... and the queue's striped tails
@@ -1970,7 +1994,9 @@ __device__ __forceinline__ const ShadeKArgs& shade_args()
     [[maybe_unused]] const ShadeIO& io = ka_.io;
 // LIST (pt_render_adaptive): path ids index the adaptive list (ShadeIO::list, path_pixel_list) instead of the active rectangle
 // LENS (pt_set_lens; launched for bounce 0 only): the camera ray's origin comes with its record (ShadeQueue::c) and two draws are consumed
-template <uint32_t QCLASS, bool VOLUMES, bool INLINE = false, bool IDENT = false, bool LIST = false, bool LENS = false>
+// RAYS (pt_integrate_rays): the path's stream is the one its entry of the ray table names (path_pixel_rays) and bounce 0 (launched with LENS: the
+// ray's origin is its own) starts at RenderParams::ray_draws draws
+template <uint32_t QCLASS, bool VOLUMES, bool INLINE = false, bool IDENT = false, bool LIST = false, bool LENS = false, bool RAYS = false>
 __global__ void __launch_bounds__(PT_SHADE_THREADS, INLINE ? PT_SHADE_WAVES_INLINE : shade_waves(QCLASS, VOLUMES)) k_shade_surface(const ShadeKArgs kargs)
 {
     extern __shared__ uint4 smem_dyn[];
@@ -2026,7 +2052,7 @@ __global__ void __launch_bounds__(PT_SHADE_THREADS, INLINE ? PT_SHADE_WAVES_INLI
             pid = asu(rb.w);
             const f4 hit = nt_load(io.q_in.b + idx);
             const f4 ra = (!LENS && bounce == 0u) ? io.primary_a : nt_load(io.q_in.c + idx);
-            f4 pw4{1.0f, 1.0f, 1.0f, asf(LENS ? 2u : 1u)}; // bounce 0: path_weight = 1, accumulated = 0, the seed draw consumed (LENS: and the lens point's)
+            f4 pw4{1.0f, 1.0f, 1.0f, asf(RAYS ? rp.ray_draws : LENS ? 2u : 1u)}; // bounce 0: path_weight = 1, accumulated = 0, the seed draw consumed (LENS: and the lens point's)
             acc = f3{0.0f, 0.0f, 0.0f};
             flags = 0u;
             if (bounce != 0u)
@@ -2054,7 +2080,9 @@ __global__ void __launch_bounds__(PT_SHADE_THREADS, INLINE ? PT_SHADE_WAVES_INLI
             const f3 normal = hit_normal(sv, inst, tri, hit.y, hit.z, rd, front);
             const f3 p = fma3(rd, bc3(hit.x), ro);                                     // r.at(hit_info.t)
             uint32_t s_local, k_pix;
-            const PixelId px = LIST ? path_pixel_list(rp, io.list, pid, &s_local, &k_pix) : path_pixel(rp, pid, &s_local, &k_pix);
+            const PixelId px = RAYS   ? path_pixel_rays(io.list, pid, &s_local, &k_pix)
+                               : LIST ? path_pixel_list(rp, io.list, pid, &s_local, &k_pix)
+                                      : path_pixel(rp, pid, &s_local, &k_pix);
             if (bounce == 0u)                                                          // integrator.rs:181-185
             {
                 if (s_local == rp.keep_s_pos) io.st.first_pos[k_pix] = f4{p.x, p.y, p.z, hit.x};
@@ -2507,6 +2535,86 @@ __global__ void __launch_bounds__(256) k_store_samples(const RenderParams rp, co
     out[i] = f4{c.x, c.y, c.z, 1.0f};
 }
 
+// key[i], sample[i] of the caller's two arrays -> the ray table's {pixel, sample} entries
+__global__ void __launch_bounds__(256) k_pack_ray_keys(const uint64_t n, const uint32_t* __restrict__ key, const uint32_t* __restrict__ sample, uint2* __restrict__ out)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = make_uint2(key[i], sample[i]);
+}
+
+// the finisher of a ray batch (pt_integrate_rays) in k_accumulate's place: the finalised sample, first hit and id byte of path i to entry i of the
+// outputs (each may be null).  A ray that left the scene at once has no record but its PRIMARY_MISS byte: the ambient term, r.at(1e5) of the
+// table's ray and id 255 (integrator.rs:156-157, 263-266), as k_accumulate rebuilds a camera ray's.
+__global__ void __launch_bounds__(256) k_store_rays(const uint32_t n, const float* __restrict__ o, const float* __restrict__ d, const PathState st,
+                                                     f4* __restrict__ radiance, f4* __restrict__ position, uint8_t* __restrict__ id)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const bool miss = st.occl[i] == PRIMARY_MISS;
+    if (radiance)
+    {
+        const f3 c = finalise(miss ? f3{0.006f, 0.006f, 0.006f} : xyz(st.radiance[i]));
+        radiance[i] = f4{c.x, c.y, c.z, 1.0f};
+    }
+    if (position)
+    {
+        f4 p;
+        if (miss)
+        {
+            const float* po = o + 3u * (size_t)i;
+            const float* pd = d + 3u * (size_t)i;
+            const f3 far = fma3(f3{pd[0], pd[1], pd[2]}, bc3(1e5f), f3{po[0], po[1], po[2]});
+            p = f4{far.x, far.y, far.z, 1e5f};
+        }
+        else p = st.first_pos[i];
+        position[i] = p;
+    }
+    if (id) id[i] = miss ? (uint8_t)255u : (uint8_t)st.first_id[i];
+}
+
+// ------------------------------------------------------------------------------------------------ irradiance probes (pt_bake_probes)
+// rays [first, first + count) of a bake into entries [0, count) of a ray table: sample first_sample + r % n_samples of probe r / n_samples
+__global__ void __launch_bounds__(256) k_probe_rays(const ProbeBake pb, const uint64_t first, const uint32_t count, float* __restrict__ o,
+                                                     float* __restrict__ d, uint2* __restrict__ key)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    const uint64_t r = first + i;
+    const uint32_t j = (uint32_t)(r / pb.n_samples), s = pb.first_sample + (uint32_t)(r - (uint64_t)j * pb.n_samples);
+    float dir[3], y[9];
+    probe_ray(pb.seed, pb.n_sobol, pb.key_base + j, s, dir, y);
+    const float* pp = pb.position + 3u * (size_t)j;
+    float* po = o + 3u * (size_t)i;
+    float* pd = d + 3u * (size_t)i;
+    po[0] = pp[0]; po[1] = pp[1]; po[2] = pp[2];
+    pd[0] = dir[0]; pd[1] = dir[1]; pd[2] = dir[2];
+    key[i] = make_uint2(pb.key_base + j, s);
+}
+// sh27[probe][k][c] += L[c] * y_k over the window's rays of that probe, in sample order: one thread per (probe, k, c), a serial fold by
+// definition (float addition does not associate) and no atomics.  The 27 threads of a probe read the same d and L (one fetch per wave).
+__global__ void __launch_bounds__(256) k_probe_project(const ProbeBake pb, const uint64_t first, const uint32_t count, const float* __restrict__ d,
+                                                        const f4* __restrict__ radiance, float* __restrict__ sh27)
+{
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t p0 = (uint32_t)(first / pb.n_samples), p1 = (uint32_t)((first + count - 1u) / pb.n_samples);
+    if (t / 27u > p1 - p0) return;
+    const uint32_t j = p0 + t / 27u, kc = t % 27u, k = kc / 3u, c = kc - 3u * k;
+    const uint64_t lo = (uint64_t)j * pb.n_samples, hi = lo + pb.n_samples;
+    const uint32_t i0 = (uint32_t)((lo > first ? lo : first) - first), i1 = (uint32_t)((hi < first + count ? hi : first + count) - first);
+    float acc = sh27[(size_t)j * 27u + kc];
+    for (uint32_t i = i0; i < i1; ++i)
+    {
+        const float* pd = d + 3u * (size_t)i;
+        const float dir[3] = {pd[0], pd[1], pd[2]};
+        float y[9];
+        probe_sh9(dir, y);
+        const f4 l4 = radiance[i];
+        const float l = c == 0u ? l4.x : c == 1u ? l4.y : l4.z;
+        acc = acc + l * y[k];
+    }
+    sh27[(size_t)j * 27u + kc] = acc;
+}
+
 // ------------------------------------------------------------------------------------------------ adaptive selection (PT_FLAG_ADAPTIVE)
 // The criterion of pt_api.h's pt_adaptive, in f32 with every operation correctly rounded and in this order (the tests restate it in
 // numpy bit for bit).  The count is an exact integer in [0, 2^24] or the pixel is bad (the call fails with PT_ERR_LIMIT).
@@ -2867,7 +2975,7 @@ static ClosestOut world_out(const WavefrontBuffers& wb, uint32_t b, const Render
 }
 
 void launch_trace_world(hipStream_t s, const TraceLaunch& tl, const WavefrontBuffers& wb, uint32_t b, const RenderParams& rp, const CameraView& cam,
-                        const LensView& lens, const EnvView& env)
+                        const LensView& lens, const EnvView& env, bool ray_list)
 {
     Counters* row = wb.counters + b;
     ClosestOut out = world_out(wb, b, rp, env);
@@ -2882,7 +2990,7 @@ void launch_trace_world(hipStream_t s, const TraceLaunch& tl, const WavefrontBuf
         out.keep_s_id = rp.keep_s_id; out.keep_s_pos = rp.keep_s_pos;
         out.blk_log = rp.blk_log; out.n_blk = rp.n_blk; out.blk_last = rp.blk_last; out.act_pixels = rp.act_pixels;
         out.div_blk_paths = rp.div_blk_paths; out.div_blk_last = rp.div_blk_last;
-        if (lens_set(lens)) launch_closest_impl<CLOSEST_PRIMARY_LENS>(s, tl, tl.scene.world_root, wb.rq[0], &row->n_closest, wb.cap_slots, row_heads(wb, b, HEADS_CLOSEST), out);
+        if (lens_set(lens) || ray_list) launch_closest_impl<CLOSEST_PRIMARY_LENS>(s, tl, tl.scene.world_root, wb.rq[0], &row->n_closest, wb.cap_slots, row_heads(wb, b, HEADS_CLOSEST), out);
         else launch_closest_impl<CLOSEST_PRIMARY>(s, tl, tl.scene.world_root, wb.rq[0], &row->n_closest, wb.cap_slots, row_heads(wb, b, HEADS_CLOSEST), out);
     }
     else launch_closest_impl<CLOSEST_WORLD>(s, tl, tl.scene.world_root, wb.rq[b & 1u], &row->n_closest, wb.cap_slots, row_heads(wb, b, HEADS_CLOSEST), out);
@@ -2937,9 +3045,11 @@ bool shade_traces_shadow(const TraceLaunch& tl)
            trace_lds_bytes(tl) + 1024 <= 32 * 1024;
 }
 void launch_shade(hipStream_t s, uint32_t qclass, const SceneView& sv, const RenderParams& rp, const WavefrontBuffers& wb, uint32_t b,
-                  uint32_t grid_blocks, const CameraView& cam, const LensView& lens, const EnvView& env, const TraceLaunch* tl, const uint2* list)
+                  uint32_t grid_blocks, const CameraView& cam, const LensView& lens, const EnvView& env, const TraceLaunch* tl, const uint2* list,
+                  const uint2* ray_keys)
 {
-    const bool lens0 = b == 0u && lens_set(lens); // only bounce 0 knows of the camera: its rays' origins and the draws they consumed
+    if (ray_keys) list = nullptr; // (a ray batch has no pixels)
+    const bool lens0 = b == 0u && (lens_set(lens) || ray_keys != nullptr); // only bounce 0 knows of the camera: its rays' origins and the draws they consumed
     ShadeIO io{};
     io.env = env;
     io.primary_a = f4{cam.eye[0], cam.eye[1], cam.eye[2], __builtin_inff()};
@@ -2970,12 +3080,14 @@ void launch_shade(hipStream_t s, uint32_t qclass, const SceneView& sv, const Ren
     const uint32_t surface_blocks = (grid_blocks * 256u + PT_SHADE_THREADS - 1u) / PT_SHADE_THREADS; // grid_blocks is in units of 256 threads
     const bool inl = tl && shade_traces_shadow(*tl);
     if (list && qclass != Q_TERMINAL) io.list = list; // (the surface passes read no terminal entries)
+    if (ray_keys && qclass != Q_TERMINAL) io.list = ray_keys;
     const ShadeKArgs ka{sv, rp, io, b, inl ? (const uint4*)tl->blob : nullptr, inl ? tl->scene.world_root : 0u};
     const size_t lds = inl ? trace_lds_bytes(*tl) : 0;
-    // (LIST: the same classes over an adaptive list's paths; lens0: LENS)
+    // (LIST: the same classes over an adaptive list's paths; lens0: LENS; ray_keys: RAYS)
 #define PT_SURF_L(LENS, Q, V, ...)                                                                                                      \
     do {                                                                                                                                 \
-        if (list) hipLaunchKernelGGL((k_shade_surface<Q, V, __VA_ARGS__, true, LENS>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), lds, s, ka);  \
+        if (ray_keys) hipLaunchKernelGGL((k_shade_surface<Q, V, __VA_ARGS__, false, LENS, true>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), lds, s, ka); \
+        else if (list) hipLaunchKernelGGL((k_shade_surface<Q, V, __VA_ARGS__, true, LENS>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), lds, s, ka);  \
         else hipLaunchKernelGGL((k_shade_surface<Q, V, __VA_ARGS__, false, LENS>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), lds, s, ka);      \
     } while (0)
 #define PT_SURF(Q, V, ...)                                                                                                              \
@@ -3043,6 +3155,31 @@ void launch_adaptive_select(hipStream_t s, const f4* accum, const float* moments
     if (blocks == 0u) return;
     hipLaunchKernelGGL(k_adaptive_count, dim3(blocks), dim3(256), 0, s, accum, moments, n_pixels, cr, counts, header);
     hipLaunchKernelGGL(k_adaptive_write, dim3(blocks), dim3(256), 0, s, accum, moments, n_pixels, cr, (const uint32_t*)counts, list, header);
+}
+void launch_generate_rays(hipStream_t s, const RenderParams& rp, const RayView& rays, const WavefrontBuffers& wb)
+{
+    hipLaunchKernelGGL(k_generate_rays, dim3((rp.n_paths + 255u) / 256u), dim3(256), 0, s, rp.n_paths, rays.o, rays.d, wb.rq[0], wb.counters);
+}
+void launch_pack_ray_keys(hipStream_t s, uint64_t n, const uint32_t* key, const uint32_t* sample, uint2* out)
+{
+    if (n == 0u) return;
+    hipLaunchKernelGGL(k_pack_ray_keys, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, s, n, key, sample, out);
+}
+void launch_store_rays(hipStream_t s, const RenderParams& rp, const RayView& rays, const WavefrontBuffers& wb, f4* radiance, f4* position, uint8_t* id)
+{
+    if (rp.n_paths == 0u) return;
+    hipLaunchKernelGGL(k_store_rays, dim3((rp.n_paths + 255u) / 256u), dim3(256), 0, s, rp.n_paths, rays.o, rays.d, wb.st, radiance, position, id);
+}
+void launch_probe_rays(hipStream_t s, const ProbeBake& pb, uint64_t first, uint32_t count, float* o, float* d, uint2* key)
+{
+    if (count == 0u) return;
+    hipLaunchKernelGGL(k_probe_rays, dim3((count + 255u) / 256u), dim3(256), 0, s, pb, first, count, o, d, key);
+}
+void launch_probe_project(hipStream_t s, const ProbeBake& pb, uint64_t first, uint32_t count, const float* d, const f4* radiance, float* sh27)
+{
+    if (count == 0u) return;
+    const uint64_t probes = (first + count - 1u) / pb.n_samples - first / pb.n_samples + 1u;
+    hipLaunchKernelGGL(k_probe_project, dim3((uint32_t)((probes * 27u + 255u) / 256u)), dim3(256), 0, s, pb, first, count, d, radiance, sh27);
 }
 void launch_store_samples(hipStream_t s, const RenderParams& rp, const WavefrontBuffers& wb, f4* out)
 {

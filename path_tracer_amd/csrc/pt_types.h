@@ -197,7 +197,7 @@ struct RenderParams
     // TLAS's root box onto the image plane, with a margin; pt_api.cpp).  Path id = sample * act_pixels + (row - act_ly0) * act_w +
     // (column - act_x0) in round 1-3's sample-major order (now: pid_join); pixels outside the rectangle get the miss result (integrator.rs:263-266) in k_accumulate.
     uint32_t act_x0, act_w, act_ly0, act_rows, act_pixels;
-    uint32_t pad[1];
+    uint32_t ray_draws;      // ray-list batches (RayView): stream draws every path starts with already spent; otherwise 0 and not read
     uint64_t seed;
     FastDiv div_blk_paths, div_blk_last, div_act_w, div_width, div_strip_rows; // div_blk_paths: by act_pixels << blk_log
 };

@@ -1,0 +1,275 @@
+"""GPU: caller-supplied rays (pt_integrate_rays, pt_integrate_rays_device) and irradiance probes (pt_bake_probes), bit for bit.  Expected values
+are the oracle's integrator walked from the same ray with the same stream key (Oracle.integrate), the library's own camera renders for
+camera rays, and the numpy restatement of the probe definition (test_rays_host.probe_rays) folded in sample order."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from conftest import ROOT, assert_bit_equal
+from test_rays_host import probe_rays
+
+pytestmark = pytest.mark.gpu
+
+F = np.float32
+W, H, DEPTH = 48, 32, 6
+ENV_SEED = 21
+N_RAYS = 4096
+
+
+@pytest.fixture(scope="module")
+def api():
+    from path_tracer_amd import api
+    api.lib()
+    return api
+
+
+def _scene(name, w=W, h=H):
+    from path_tracer_amd import scenes
+    return {"cornell": lambda: scenes.cornell_box(w, h), "cornell_mixed": lambda: scenes.cornell_mixed(w, h),
+            "media": lambda: scenes.cornell_media(w, h, level=2), "cornell_instanced": lambda: scenes.cornell_instanced(w, h),
+            "cornell_env": lambda: scenes.cornell_box(w, h)}[name]()
+
+
+def _env():
+    return (np.random.default_rng(ENV_SEED).uniform(0, 1, (17, 33, 3)) ** 3 * 4).astype(F)
+
+
+def _renderer(api, name, flags=0, **kw):
+    r = api.Renderer(_scene(name), W, H, max_bounces=DEPTH, flags=flags, **kw)
+    if name == "cornell_env":
+        r.set_environment(_env())
+    return r
+
+
+_ORACLE = {}
+
+
+def _oracle(O, name):
+    if name not in _ORACLE:
+        _ORACLE[name] = O.Oracle(_scene(name))
+        if name == "cornell_env":
+            _ORACLE[name].set_environment(_env())
+    return _ORACLE[name]
+
+
+def _random_rays(box, n, seed):
+    """origins uniform in the box grown by 10 % per side, unit directions (every tenth one scaled by a length in [0.25, 4]), keys over
+    all 32 bits, samples in [0, 2000)"""
+    rng = np.random.default_rng(seed)
+    lo, hi = box[:3].astype(np.float64), box[3:].astype(np.float64)
+    ext = hi - lo
+    o = rng.uniform(lo - 0.1 * ext, hi + 0.1 * ext, (n, 3)).astype(F)
+    d = rng.normal(size=(n, 3)).astype(F)
+    d = (d / np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])[:, None]).astype(F)
+    scaled = np.arange(n) % 10 == 3
+    d[scaled] = d[scaled] * rng.uniform(0.25, 4.0, n).astype(F)[scaled, None]
+    key = rng.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32)
+    sample = rng.integers(0, 2000, n).astype(np.uint32)
+    assert (key >= 1 << 31).any() and np.isfinite(o).all() and np.isfinite(d).all()
+    return o, d, key, sample
+
+
+def _oracle_rays(orc, o, d, key, sample, draws, depth=DEPTH):
+    n = len(key)
+    rad = np.zeros((n, 4), F); pos = np.zeros((n, 4), F); idb = np.zeros(n, np.uint8)
+    for i in range(n):
+        rad[i], pos[i], idb[i] = orc.integrate(o[i], d[i], int(key[i]), int(sample[i]), draws, max_bounces=depth)
+    return rad, pos, idb
+
+
+def _same_rays(got, want, what):
+    assert_bit_equal(got[0], want[0], what + ": radiance")
+    assert_bit_equal(got[1], want[1], what + ": position")
+    assert np.array_equal(got[2], want[2]), what + ": id byte"
+
+
+# ---- 1. camera rays come back as the render
+@pytest.mark.parametrize("name", ["cornell", "cornell_mixed"])
+@pytest.mark.parametrize("lens", [None, (40.0, 800.0)], ids=["pinhole", "lens"])
+def test_camera_rays_come_back_as_the_render(api, name, lens):
+    r = _renderer(api, name)
+    if lens:
+        r.set_lens(*lens)
+    pixels = np.arange(W * H, dtype=np.uint32)
+    for s in (0, 1, 511):
+        o = np.zeros((W * H, 3), F); d = np.zeros((W * H, 3), F)
+        draws = set()
+        for p in pixels:
+            o[p], d[p], k = r.primary_ray(int(p), s)
+            draws.add(k)
+        assert draws == {2 if lens else 1}
+        rad, pos, idb = r.integrate_rays(o, d, pixels, np.full(W * H, s, np.uint32), draws_consumed=draws.pop())
+        want = r.render_samples(s, 1)[0]
+        r.reset_accumulation()
+        _, wpos, wid = r.render(s, 1)
+        assert_bit_equal(rad.reshape(H, W, 4), want, f"{name} sample {s}: radiance")
+        assert_bit_equal(pos.reshape(H, W, 4), wpos, f"{name} sample {s}: position")
+        assert np.array_equal(idb.reshape(H, W), wid & 0xff), f"{name} sample {s}: id byte"
+
+
+# ---- 2. arbitrary rays against the oracle
+CASES = [("cornell", 0, 0), ("cornell", 2, 0), ("cornell", 16, 7), ("cornell_mixed", 0, 1), ("cornell_mixed", 2, 1), ("media", 0, 2), ("media", 2, 2),
+         ("cornell_instanced", 0, 7), ("cornell_instanced", 2, 7), ("cornell_env", 0, 1), ("cornell_env", 2, 1)]
+_EXPECT = {}
+
+
+@pytest.mark.parametrize("name,flags,draws", CASES)
+def test_arbitrary_rays_against_the_oracle(api, oracle_mod, name, flags, draws):
+    """4 096 rays per case, some starting outside the scene and some inside models and media: BVH in LDS, in global memory
+    (FLAG_NO_LDS_SCENE = 2), the general walk (16); draws_consumed 0, 1, 2 or 7"""
+    r = _renderer(api, name, flags)
+    box = r.active_pixels()[1]
+    o, d, key, sample = _random_rays(box, N_RAYS, 1000 + len(name))
+    if (name, draws) not in _EXPECT:
+        _EXPECT[(name, draws)] = _oracle_rays(_oracle(oracle_mod, name), o, d, key, sample, draws)
+    want = _EXPECT[(name, draws)]
+    assert (want[2] == 255).any() and (want[2] != 255).any()
+    _same_rays(r.integrate_rays(o, d, key, sample, draws_consumed=draws), want, f"{name} flags {flags} draws {draws}")
+
+
+# ---- 3. a ray's result depends on nothing but the ray
+def test_independence(api):
+    n = 10000
+    r = _renderer(api, "cornell")
+    o, d, key, sample = _random_rays(r.active_pixels()[1], n, 7)
+    base = r.integrate_rays(o, d, key, sample)
+    for batch in (1024, 64):
+        _same_rays(r.integrate_rays(o, d, key, sample, batch_rays=batch), base, f"batch_rays {batch}")
+    one = _renderer(api, "cornell", pipelines=1)
+    _same_rays(one.integrate_rays(o, d, key, sample, batch_rays=1024), base, "one pipeline")
+    rev = r.integrate_rays(o[::-1], d[::-1], key[::-1], sample[::-1], batch_rays=1024)
+    _same_rays([a[::-1] for a in rev], base, "the list reversed")
+    for m in (1, 63, 64, 65):
+        _same_rays(r.integrate_rays(o[:m], d[:m], key[:m], sample[:m]), [a[:m] for a in base], f"the first {m} rays alone")
+    twice = np.concatenate([np.arange(100), [5, 5, 17], np.arange(100, 200), [5]])
+    got = r.integrate_rays(o[twice], d[twice], key[twice], sample[twice])
+    _same_rays(got, [a[twice] for a in base], "rays listed more than once")
+
+
+# ---- 4. the frame is not touched
+@pytest.mark.parametrize("flags", [0, 32], ids=["plain", "adaptive"])
+def test_the_frame_is_not_touched(api, flags):
+    n = 3000
+    whole = _renderer(api, "cornell_mixed", flags)
+    want = whole.render(0, 10)
+    r = _renderer(api, "cornell_mixed", flags)
+    o, d, key, sample = _random_rays(r.active_pixels()[1], n, 11)
+    r.render(0, 5)
+    r.render_guides(4)
+    before = r.stats()
+    r.integrate_rays(o, d, key, sample, batch_rays=1000)
+    after = r.stats()
+    assert after.paths - before.paths == n
+    assert after.rays_closest - before.rays_closest >= n
+    assert after.rays_primary_culled == before.rays_primary_culled
+    den = r.denoise(iterations=1)       # the guides rendered before the call are still accepted
+    assert np.isfinite(den).all()
+    got = r.render(5, 5)
+    assert_bit_equal(got[0], want[0], "accumulation")
+    assert_bit_equal(got[1], want[1], "position")
+    assert np.array_equal(got[2], want[2]), "id history"
+    if flags:
+        assert_bit_equal(r.read_moments(), whole.read_moments(), "moments")
+
+
+# ---- 5. device pointers
+def test_device_variant(api):
+    import torch
+    n = 5000
+    r = _renderer(api, "cornell_mixed")
+    o, d, key, sample = _random_rays(r.active_pixels()[1], n, 13)
+    want = r.integrate_rays(o, d, key, sample, draws_consumed=2)
+    dev = lambda a: torch.from_numpy(a.view(np.int32) if a.dtype == np.uint32 else a).cuda()
+    got = r.integrate_rays(dev(o), dev(d), dev(key), dev(sample), draws_consumed=2, batch_rays=2048)
+    assert all(t.is_cuda for t in got)
+    _same_rays([t.cpu().numpy() for t in got], want, "device pointers")
+
+
+# ---- 6. probes
+def _fold(sh, rad, y, n_probes, n_samples):
+    """sh[j][k][c] += L[c] * y_k for s ascending, every product and sum rounded in binary32; rays probe-major"""
+    sh = sh.copy()
+    rad = rad.reshape(n_probes, n_samples, 4); y = y.reshape(n_probes, n_samples, 9)
+    for s in range(n_samples):
+        sh = sh + rad[:, s, None, :3] * y[:, s, :, None]
+    assert sh.dtype == F
+    return sh
+
+
+def _expected_sh(O, orc, positions, first, count, key_base, depth=DEPTH):
+    n = len(positions)
+    keys = np.repeat(np.arange(n) + key_base, count)
+    samples = np.tile(np.arange(first, first + count), n)
+    d, y = probe_rays(O, keys, samples)
+    rad, _, _ = _oracle_rays(orc, np.repeat(positions, count, 0), d, keys, samples, 1, depth)
+    return lambda sh: _fold(sh, rad, y, n, count)
+
+
+def _cornell_probes(r):
+    """eight probes: six spread over the room, one inside the tall box, one outside the room"""
+    from path_tracer_amd import scenes
+    box = r.active_pixels()[1]
+    lo, hi = box[:3], box[3:]
+    frac = np.array([[0.5, 0.5, 0.5], [0.1, 0.2, 0.3], [0.9, 0.8, 0.7], [0.3, 0.95, 0.5], [0.7, 0.05, 0.2], [0.5, 0.5, 0.9]], F)
+    pos = [lo + f * (hi - lo) for f in frac]
+    tall = [m.name for m in scenes.cornell_models()].index("cb_box_tall")
+    pos.append(r.model_vertices(tall)[0].reshape(-1, 3).mean(0))
+    pos.append(lo + np.array([1.6, 0.5, 0.5], F) * (hi - lo))
+    return np.array(pos, F)
+
+
+def test_probes_cornell(api, oracle_mod):
+    r = _renderer(api, "cornell")
+    pos = _cornell_probes(r)
+    fold = _expected_sh(oracle_mod, _oracle(oracle_mod, "cornell"), pos, 0, 256, 1000)
+    want = fold(np.zeros((8, 9, 3), F))
+    got = r.bake_probes(pos, 256, key_base=1000)
+    assert_bit_equal(got, want, "256 samples of 8 probes")
+    assert np.abs(got[:6, 0]).min() > 0 and not np.array_equal(got[6], got[0])
+    # a bake continues from what sh holds
+    part = r.bake_probes(pos, 100, key_base=1000)
+    part = r.bake_probes(pos, 156, first_sample=100, key_base=1000, sh=part)
+    assert_bit_equal(part, want, "bake(0, 100) then bake(100, 156)")
+    # wavefront batches of 16 * 8 rays, three to a ray table: a probe's 256 samples straddle both cuts
+    cut = _renderer(api, "cornell", batch_spp=16)
+    assert_bit_equal(cut.bake_probes(pos, 256, key_base=1000), want, "cut into batches")
+    # the frame of the context is not involved
+    assert r.stats().paths == 8 * (256 + 100 + 156)
+
+
+def test_probes_mixed_scene_in_global_memory(api, oracle_mod):
+    r = _renderer(api, "cornell_mixed", flags=2)
+    box = r.active_pixels()[1]
+    pos = np.array([box[:3] + f * (box[3:] - box[:3]) for f in ([0.5, 0.5, 0.5], [0.2, 0.3, 0.6], [0.8, 0.6, 0.3], [0.4, 0.9, 0.8])], F)
+    start = np.random.default_rng(3).uniform(-1, 1, (4, 9, 3)).astype(F)     # sums that continue from something
+    want = _expected_sh(oracle_mod, _oracle(oracle_mod, "cornell_mixed"), pos, 500, 64, 0xFFFFFFF0)(start)
+    assert_bit_equal(r.bake_probes(pos, 64, first_sample=500, key_base=0xFFFFFFF0, sh=start.copy()), want, "mixed scene, BVH in global memory")
+
+
+# ---- 7. the C++ surface
+def test_headless_bakes_probes(api, tmp_path):
+    """examples/headless --bake-probes 2 2 2 64 out.txt parses back to the Python surface's bake_probes for the same grid"""
+    from path_tracer_amd import build as B, scenes
+    from path_tracer_amd.scene_desc import Model, SceneDesc
+    Wd, Hd, BOUNCES = 48, 32, 4
+    exe = B.build_host_driver()
+    out_txt = tmp_path / "probes.txt"
+    run = subprocess.run([exe, "--width", str(Wd), "--height", str(Hd), "--frames", "1", "--bounces", str(BOUNCES), "--bake-probes", "2", "2", "2", "64",
+                          str(out_txt)], capture_output=True, text=True, cwd=ROOT)
+    assert run.returncode == 0, run.stderr
+    got = np.array([[float.fromhex(v) for v in line.split()] for line in out_txt.read_text().splitlines()], np.float64)
+    assert got.shape == (8, 27)
+    src = scenes.cornell_models()
+    sc = SceneDesc.new([Model.from_obj(os.path.join(ROOT, "models", "cornell", m.name + ".obj"), m.material) for m in src], scenes.reference_camera(Wd / Hd))
+    r = api.Renderer(sc, Wd, Hd, max_bounces=BOUNCES)
+    box = r.active_pixels()[1].astype(F)
+    lo, hi = box[:3], box[3:]
+    margin = F(0.05) * (hi - lo)
+    a, b = lo + margin, hi - margin
+    grid = np.array([[a[0] + (b[0] - a[0]) * (F(x) / F(1)), a[1] + (b[1] - a[1]) * (F(y) / F(1)), a[2] + (b[2] - a[2]) * (F(z) / F(1))]
+                     for z in range(2) for y in range(2) for x in range(2)], F)
+    want = r.bake_probes(grid, 64)
+    assert_bit_equal(got.astype(F).reshape(8, 9, 3), want, "headless --bake-probes")
+    assert np.array_equal(got, got.astype(F).astype(np.float64))
