@@ -8,6 +8,8 @@
 //       without the temporal pass; the frame's state (accumulation, first-hit position, id history) can be saved and picked up by another
 //       process: a long render stopped and continued (pt_read_frame / pt_write_accumulation)
 //   examples/headless ... --aperture A --focus F   thin lens of diameter A focused at distance F (default: the reference's pinhole, 0 and 950)
+//   examples/headless ... --slide DX DZ   frame f >= 1 first moves the short box to the translation (f * DX, 0, f * DZ) (pt_set_instances + pt_build:
+//                                          the BLASes are kept, the resident scene is patched) and the loop drives frame_moving instead of frame
 //   examples/headless ... --denoise den.png   also writes the final frame through the edge-aware denoiser (guides of the last frame's sample)
 //   examples/headless ... --bake-probes NX NY NZ SPP probes.txt   after the usual render, bakes SPP samples into an NX x NY x NZ grid of
 //       irradiance probes spanning the scene's bounds shrunk by 5 % per side (x fastest, then y, then z; stream keys 0, 1, ...) and
@@ -26,7 +28,8 @@ using namespace ptmi;
 int main(int argc, char** argv)
 {
     uint32_t width = 1920, height = 1080, frames = 64, bounces = 8; // IMAGE_WIDTH/HEIGHT main.rs:44-45; the reference's MAX_BOUNCES is 1024
-    bool move = false;
+    bool move = false, slide = false;
+    float slide_dx = 0.0f, slide_dz = 0.0f;
     uint32_t gpus = 0, spp = 64;
     std::vector<int32_t> devices;
     std::string models_dir = "models/cornell", out = "", load_state = "", save_state = "", denoise_out = "";
@@ -50,6 +53,7 @@ int main(int argc, char** argv)
         else if (a == "--out") out = next("--out");
         else if (a == "--denoise") denoise_out = next("--denoise");
         else if (a == "--move") move = true;
+        else if (a == "--slide") { slide = true; slide_dx = (float)std::atof(next("--slide")); slide_dz = (float)std::atof(next("--slide")); }
         else if (a == "--aperture") aperture = (float)std::atof(next("--aperture"));
         else if (a == "--focus") focus = (float)std::atof(next("--focus"));
         else if (a == "--gpus") gpus = (uint32_t)std::atoi(next("--gpus"));
@@ -70,7 +74,7 @@ int main(int argc, char** argv)
         }
         else if (a == "--help" || a == "-h")
         {
-            std::printf("usage: %s [--width W] [--height H] [--frames N] [--bounces B] [--move] [--models DIR] [--out file.png] [--denoise file.png] [--aperture A --focus F] [--bake-probes NX NY NZ SPP file.txt]\n", argv[0]);
+            std::printf("usage: %s [--width W] [--height H] [--frames N] [--bounces B] [--move] [--slide DX DZ] [--models DIR] [--out file.png] [--denoise file.png] [--aperture A --focus F] [--bake-probes NX NY NZ SPP file.txt]\n", argv[0]);
             return 0;
         }
         else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
@@ -188,7 +192,14 @@ int main(int argc, char** argv)
                 renderer.input(PT_EV_KEY_W, 0.0f, 0.0f, 2.0e-6f);
                 renderer.input(PT_EV_MOUSE_MOTION, 1.0f, 0.25f, 1.0e-6f);
             }
-            renderer.frame(frame, last_inv_proj);            // the pixel loop + state.update   main.rs:181-215
+            if (slide && frame >= 1)
+            {
+                // a pure translation passes Model::new's rigid assert whatever its size (model.rs:40-44)
+                const float f = (float)frame;
+                renderer.set_instances(5, {Affine3A{{1, 0, 0, f * slide_dx, 0, 1, 0, 0.0f, 0, 0, 1, f * slide_dz}}});
+            }
+            if (slide) renderer.frame_moving(frame, last_inv_proj);
+            else renderer.frame(frame, last_inv_proj);       // the pixel loop + state.update   main.rs:181-215
             last_inv_proj = renderer.inv_projection();       // main.rs:216
         }
         const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();

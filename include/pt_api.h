@@ -118,6 +118,29 @@ int pt_model_vertices(pt_ctx* ctx, int model, float* positions_xyz, float* norma
  * PT_ERR_LIMIT: the scene exceeds a packing limit, or the host ran out of memory building it (pt_add_model* likewise): no C++
  * exception crosses this boundary. */
 int pt_build(pt_ctx* ctx);
+/* Replaces the instance matrices of `model` (an index pt_add_model* returned): n_instances rigid 3x4 row-major transforms, checked exactly as
+ * pt_add_model checks them (PT_ERR_NONRIGID, PT_ERR_ARG for NULL with n_instances > 0 or a bad model index).  n_instances may differ from
+ * the model's current count; 0 removes the model from both TLASes (pt_add_model already accepts 0).  A refused call changes nothing: the
+ * scene stays built and renders as before.  An accepted call makes the scene un-built like pt_add_model does: the next pt_build applies it,
+ * and a render before that is PT_ERR_STATE.  Several calls may precede one pt_build.
+ * pt_build after it does the least work that still gives, word for word, the flattened scene a build from nothing gives: a BLAS lives in
+ * object space and is built once per model; the two TLASes and the light sampler are rebuilt; and when no model or material was added and
+ * every model kept its instance count, the next render patches the TLAS nodes and the instance records of the resident scene in place (two
+ * copies on the context's stream, nothing allocated) instead of uploading it again.  The accumulation is not touched: resetting it is the
+ * caller's, or pt_frame_moving's reprojection.  Guides go stale and pt_multi_render replicates, as after any pt_build. */
+int pt_set_instances(pt_ctx* ctx, int model, const float* affine3x4_rowmajor, uint32_t n_instances);
+/* which path ran, without a stopwatch (host only) */
+typedef struct pt_scene_info
+{
+    uint64_t blas_builds;      /* BLASes built since pt_create */
+    uint64_t tlas_builds;      /* pt_build calls that rebuilt the TLASes */
+    uint64_t uploads_full;     /* scene uploads that (re)allocated and copied everything */
+    uint64_t uploads_patched;  /* scene uploads that patched TLAS nodes and instance records in place (also the re-upload after a
+                                  pt_set_config that changed stack_lds_levels or PT_FLAG_NO_LDS_SCENE: the layout is unchanged) */
+    uint64_t last_upload_bytes;
+    uint64_t reserved[3];
+} pt_scene_info;
+int pt_get_scene_info(pt_ctx* ctx, pt_scene_info* out);
 
 /* ---- Camera::new / create_ray  src/camera.rs:17-31, 94-105 ---------------------------------------------------- */
 int pt_set_camera(pt_ctx* ctx, const float eye[3], const float target[3], float fov_y_deg, float aspect);
@@ -243,6 +266,24 @@ int pt_synchronize(pt_ctx* ctx);
  * reference hands them to state.update: this frame's (rgb,1), first-hit xyz|t, id history.  Single-rank contexts only. */
 int pt_frame(pt_ctx* ctx, uint32_t frame_index, const float* last_inv_projection, float* data_rgba, float* position_xyzt, uint32_t* id);
 int pt_inv_projection(pt_ctx* ctx, float out16_colmajor[16]); /* (cam.matrix * cam.inv_projection).inverse() of the current camera */
+/* pt_frame with a world that may have moved (pt_set_instances + pt_build between frames).  Single-rank, same buffers, same errors.  It
+ * renders sample frame_index exactly as pt_frame, then pt_render_guides(frame_index) (which it leaves valid: the interactive recipe becomes
+ * pt_frame_moving(k), pt_denoise), then State::update with the motion of the instances taken into account:
+ *   SNAPSHOT  The context remembers, per model, the forward instance matrices of the build in force when the previous pt_frame_moving
+ *     returned PT_OK (none before the first).  Instance i of the current world TLAS is (model m, ordinal j); its PREVIOUS MATRIX is matrix j
+ *     of model m in the snapshot if model m had the same instance count there, otherwise it has none.
+ *   X_PREV per pixel, binary32, every operation rounded once, no contraction.  x = position.xyz, i = the pixel's instance guide, inv = the
+ *     rows of inv_matrix12[i] (pt_tlas_instances), prv = the rows of the previous matrix:
+ *       miss, no previous matrix, or previous matrix bit-equal to matrix12[i]:  x_prev = x   (no arithmetic)
+ *       else  o[k]      = ((inv[k][0] * x.x + inv[k][1] * x.y) + inv[k][2] * x.z) + inv[k][3]        k = 0, 1, 2
+ *             x_prev[k] = ((prv[k][0] * o.x + prv[k][1] * o.y) + prv[k][2] * o.z) + prv[k][3]        (glam's transform_point3, twice)
+ *     `position` as returned is not changed; x_prev feeds the velocity only.
+ *   MOVED = pt_frame's camera test (last_inv_projection non-NULL and not == the current one) OR some current instance has a previous matrix
+ *     that is not bit-equal to its matrix OR some model's instance count differs from the snapshot's (a model added since had none
+ *     there).  Not moved: accumulate.wgsl, as pt_frame.  Moved: velocity.wgsl on (x_prev | t) with last_inv_projection (the current
+ *     camera's pt_inv_projection when it is NULL), then compute.wgsl and the copy, as pt_frame.
+ * On a scene nobody moved, any sequence of pt_frame_moving calls equals the same sequence of pt_frame calls bit for bit. */
+int pt_frame_moving(pt_ctx* ctx, uint32_t frame_index, const float* last_inv_projection, float* data_rgba, float* position_xyzt, uint32_t* id);
 /* State::render: GT tonemap of accumulation.rgb / accumulation.w (shader.wgsl:3-33,59-64), rgba f32, alpha 1, host buffer */
 int pt_present(pt_ctx* ctx, float* rgba);
 /* ImageHelper::write_image (src/image_helper.rs:37-58): accumulation.rgb / accumulation.w through tonemapping.rs's GT curve,
@@ -254,6 +295,12 @@ int pt_write_image(pt_ctx* ctx, const char* path);
 int pt_post_velocity(pt_ctx* ctx, uint32_t w, uint32_t h, const float* position, const float* last_inv_projection, float* velocity);
 int pt_post_reproject(pt_ctx* ctx, uint32_t w, uint32_t h, const float* input, const float* accum, const float* velocity, const uint32_t* id,
                       float* output);
+/* x_prev of pt_frame_moving on caller images: position xyzt and the instance image (0xffffffff = miss) in, x_prev | t out; the tables hold
+ * n_instances x 12 floats each (rows of the 3x4): the current matrices, their inverses, the previous matrices; has_prev[i] == 0 marks an
+ * instance without a previous matrix (NULL: every instance has one).  PT_ERR_ARG: a NULL image, a NULL table with n_instances > 0, an
+ * instance entry that is neither a miss nor below n_instances. */
+int pt_post_motion(pt_ctx* ctx, uint32_t w, uint32_t h, const float* position_xyzt, const uint32_t* instance, uint32_t n_instances,
+                   const float* matrix12, const float* inv_matrix12, const float* prev_matrix12, const uint8_t* has_prev, float* x_prev_xyzt);
 int pt_post_tonemap(pt_ctx* ctx, uint32_t w, uint32_t h, const float* accum, float* out);
 int pt_post_rgb8(pt_ctx* ctx, uint32_t w, uint32_t h, const float* accum, uint8_t* rgb);
 
@@ -271,6 +318,9 @@ int pt_post_rgb8(pt_ctx* ctx, uint32_t w, uint32_t h, const float* accum, uint8_
  * pt_read_guides copies them to the host (any pointer may be NULL): local_rows * width entries of xyzt, xyz and u32; PT_ERR_STATE without guides. */
 int pt_render_guides(pt_ctx* ctx, uint32_t sample);
 int pt_read_guides(pt_ctx* ctx, float* position_xyzt, float* normal_xyz, uint32_t* model);
+/* the fourth guide pt_render_guides keeps: the world-TLAS leaf of the hit in allocation order — the index pt_tlas_instances(ctx, 0, ..) and
+ * pt_instance_materials use — 0xffffffff for a miss; local_rows * width words.  PT_ERR_STATE without guides. */
+int pt_read_guide_instances(pt_ctx* ctx, uint32_t* instance);
 /* The filter, in f32 with every operation correctly rounded (no contraction) and in the order written.  exp is pt_math.h's exp_det.
  *   Pixel p is VALID when acc.w != 0; an invalid pixel is never a neighbour and its output is (0,0,0,0).  Every valid output is (c, 1).
  *   c_p = (acc.r / acc.w, acc.g / acc.w, acc.b / acc.w);  l(c) = (0.2126f * c.r + 0.7152f * c.g) + 0.0722f * c.b (of the current colour).

@@ -200,6 +200,25 @@ public:
         }
         else check(pt_frame(ctx_, frame_index, last_inv_projection.data(), nullptr, nullptr, nullptr));
     }
+    // frame() with a world that may have moved since the previous frame_moving (set_instances): the history is reprojected by the camera's
+    // and the instances' motion; leaves this sample's guides valid (frame_moving(k), then denoise)
+    void frame_moving(uint32_t frame_index, const Mat4& last_inv_projection, Frame* out = nullptr)
+    {
+        if (out)
+        {
+            out->data.resize((size_t)width_ * height_ * 4); out->position.resize((size_t)width_ * height_ * 4); out->id.resize((size_t)width_ * height_);
+            check(pt_frame_moving(ctx_, frame_index, last_inv_projection.data(), out->data.data(), out->position.data(), out->id.data()));
+        }
+        else check(pt_frame_moving(ctx_, frame_index, last_inv_projection.data(), nullptr, nullptr, nullptr));
+    }
+    // replaces the instance matrices of model `model` (index in Scene::models) and rebuilds: BLASes are kept, the TLASes are built again and,
+    // when the instance count is unchanged, the next render patches the resident scene in place
+    void set_instances(int model, const std::vector<Affine3A>& matrices)
+    {
+        check(pt_set_instances(ctx_, model, matrices.empty() ? nullptr : matrices[0].m.data(), (uint32_t)matrices.size()));
+        check(pt_build(ctx_));
+    }
+    pt_scene_info scene_info() const { pt_scene_info s{}; check(pt_get_scene_info(ctx_, &s)); return s; }
     // n_samples per pixel accumulated without the temporal pass (what the loop converges to for a camera at rest)
     void render(uint32_t first_sample, uint32_t n_samples) { check(pt_render_device(ctx_, first_sample, n_samples)); check(pt_synchronize(ctx_)); }
     void reset_accumulation() { check(pt_reset_accumulation(ctx_)); }

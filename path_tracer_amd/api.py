@@ -39,6 +39,7 @@ EXPORTS = [
     "pt_multi_reset_accumulation", "pt_multi_get_stats", "pt_multi_used_rccl", "pt_multi_write_image",
     "pt_render_guides", "pt_read_guides", "pt_denoise", "pt_write_denoised_image", "pt_post_denoise",
     "pt_integrate_rays", "pt_integrate_rays_device", "pt_bake_probes", "pt_probe_ray",
+    "pt_set_instances", "pt_get_scene_info", "pt_read_guide_instances", "pt_frame_moving", "pt_post_motion",
 ]
 
 
@@ -91,6 +92,15 @@ class RaysParams(C.Structure):
 class ProbeParams(C.Structure):
     """pt_probe_params: the sample range and stream keys of a probe bake (include/pt_api.h)"""
     _fields_ = [("first_sample", C.c_uint32), ("n_samples", C.c_uint32), ("key_base", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class SceneInfo(C.Structure):
+    """pt_scene_info: which build and upload paths ran (include/pt_api.h)"""
+    _fields_ = [("blas_builds", C.c_uint64), ("tlas_builds", C.c_uint64), ("uploads_full", C.c_uint64), ("uploads_patched", C.c_uint64),
+                ("last_upload_bytes", C.c_uint64), ("reserved", C.c_uint64 * 3)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
 
 
 class PtError(RuntimeError):
@@ -204,6 +214,11 @@ def lib():
         L.pt_integrate_rays_device.argtypes = [vp, C.c_uint64, vp, vp, vp, vp, C.POINTER(RaysParams), vp, vp, vp]
         L.pt_bake_probes.argtypes = [vp, u32, vp, C.POINTER(ProbeParams), vp]
         L.pt_probe_ray.argtypes = [vp, u32, u32, vp, vp]
+        L.pt_set_instances.argtypes = [vp, C.c_int, f32p, u32]
+        L.pt_get_scene_info.argtypes = [vp, C.POINTER(SceneInfo)]
+        L.pt_read_guide_instances.argtypes = [vp, vp]
+        L.pt_frame_moving.argtypes = [vp, u32, vp, vp, vp, vp]
+        L.pt_post_motion.argtypes = [vp, u32, u32, vp, vp, u32, vp, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -261,6 +276,17 @@ class Renderer:
 
     def rebuild(self):
         self._chk(self.L.pt_build(self.ctx))
+
+    def set_instances(self, model: int, matrices):
+        """replace the instance matrices of a model ([n, 3, 4] row-major rigid transforms, n may be 0); call rebuild() before the next render"""
+        m = np.ascontiguousarray(np.zeros((0, 3, 4), np.float32) if matrices is None else matrices, dtype=np.float32).reshape(-1, 3, 4)
+        self._chk(self.L.pt_set_instances(self.ctx, model, _p(m) if m.shape[0] else None, m.shape[0]))
+
+    def scene_info(self) -> SceneInfo:
+        """which build and upload paths ran: BLAS / TLAS builds, full and patched scene uploads, bytes of the last upload"""
+        out = SceneInfo()
+        self._chk(self.L.pt_get_scene_info(self.ctx, C.byref(out)))
+        return out
 
     # ---- plumbing
     def _chk(self, r, allow_positive=False):
@@ -472,6 +498,19 @@ class Renderer:
         self._chk(self.L.pt_frame(self.ctx, frame_index, _p(m), _p(data), _p(pos), _p(idb)))
         return data, pos, idb
 
+    def frame_moving(self, frame_index, last_inv_projection=None, ident=None, download=True):
+        """frame() with a world that may have moved since the previous frame_moving (set_instances + rebuild): the history is reprojected by
+        the camera's AND the instances' motion; leaves the guides of this sample valid (frame_moving(k), denoise())"""
+        m = None if last_inv_projection is None else np.ascontiguousarray(last_inv_projection, np.float32)
+        if not download:
+            self._chk(self.L.pt_frame_moving(self.ctx, frame_index, _p(m), None, None, None))
+            return None
+        h, w = self.cfg.height, self.cfg.width
+        data = np.zeros((h, w, 4), np.float32); pos = np.zeros((h, w, 4), np.float32)
+        idb = np.zeros((h, w), np.uint32) if ident is None else ident
+        self._chk(self.L.pt_frame_moving(self.ctx, frame_index, _p(m), _p(data), _p(pos), _p(idb)))
+        return data, pos, idb
+
     def present(self):
         out = np.zeros((self.cfg.height, self.cfg.width, 4), np.float32)
         self._chk(self.L.pt_present(self.ctx, _p(out)))
@@ -499,6 +538,19 @@ class Renderer:
         self._chk(self.L.pt_post_velocity(self.ctx, w, h, _p(position), _p(np.ascontiguousarray(last_inv_projection, np.float32)), _p(v)))
         return v
 
+    def post_motion(self, position, instance, matrix12, inv_matrix12, prev_matrix12, has_prev=None):
+        """x_prev of frame_moving on caller images: where each pixel's first hit was under its instance's previous matrix"""
+        position = np.ascontiguousarray(position, np.float32); instance = np.ascontiguousarray(instance, np.uint32)
+        h, w = position.shape[:2]
+        tabs = [np.ascontiguousarray(t, np.float32).reshape(-1, 12) for t in (matrix12, inv_matrix12, prev_matrix12)]
+        n = tabs[0].shape[0]
+        assert all(t.shape[0] == n for t in tabs)
+        hp = None if has_prev is None else np.ascontiguousarray(has_prev, np.uint8)
+        assert hp is None or hp.shape == (n,)
+        out = np.zeros((h, w, 4), np.float32)
+        self._chk(self.L.pt_post_motion(self.ctx, w, h, _p(position), _p(instance), n, *[_p(t) if n else None for t in tabs], _p(hp), _p(out)))
+        return out
+
     def post_reproject(self, inp, accum, velocity, ident):
         inp = np.ascontiguousarray(inp, np.float32); accum = np.ascontiguousarray(accum, np.float32)
         velocity = np.ascontiguousarray(velocity, np.float32); ident = np.ascontiguousarray(ident, np.uint32)
@@ -525,6 +577,12 @@ class Renderer:
         pos = np.zeros((rows, w, 4), np.float32); nrm = np.zeros((rows, w, 3), np.float32); model = np.zeros((rows, w), np.uint32)
         self._chk(self.L.pt_read_guides(self.ctx, _p(pos), _p(nrm), _p(model)))
         return pos, nrm, model
+
+    def read_guide_instances(self):
+        """the instance guide of the last render_guides: world-TLAS leaf (tlas_instances(0) index) of every pixel's hit, MISS = 0xffffffff"""
+        inst = np.zeros((len(self.local_rows()), self.cfg.width), np.uint32)
+        self._chk(self.L.pt_read_guide_instances(self.ctx, _p(inst)))
+        return inst
 
     def denoise(self, iterations=0, sigma_luminance=0.0, sigma_normal=0, sigma_plane=0.0, download=True):
         """filter the accumulation with the guides (and the moments where the context keeps valid ones); returns rgba (c, 1) per local pixel,

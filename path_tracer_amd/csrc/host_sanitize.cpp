@@ -7,6 +7,9 @@
 //   host_sanitize png <w> <h> <file>   encode a test image
 //   host_sanitize soup <n> <seed>      Scene::new over n random triangles (PTMI_BUILD_THREADS forks the SAH sweep: also built with
 //                                      -fsanitize=thread by `make host-tsan`); prints a checksum of the BLAS arena
+//   host_sanitize moves <n> <seed>     pt_set_instances' host side: n random moves (translations, quarter turns, instance counts 0..3) of the models
+//                                      of a small scene, an incremental build after each; the flattened scene must equal, byte for byte, the one
+//                                      a scene built from nothing with the same matrices flattens to; prints how many builds kept the BLAS part
 //   host_sanitize plan <row>...        pt_batch_plan.h: each row "b:free,held,classes,volumes" (max_paths_for) or
 //                                      "p:n_samples,act_pixels,samples_out,pipelines,batch_spp,lds_scene,max_paths,cap0,cap1,cap2,cap3"
 //                                      (plan_batches); prints a JSON list: max_paths, or [batch, n_batches, n_pipes] ([0, 0, 0]: refused)
@@ -119,6 +122,62 @@ int main(int argc, char** argv)
         }
         for (uint32_t v : b.prim_ids) mix(v);
         std::printf("{\"nodes\": %zu, \"depth\": %u, \"arena\": \"%016llx\"}\n", b.nodes.size(), b.depth, (unsigned long long)h);
+        return 0;
+    }
+    if (cmd == "moves" && argc >= 4)
+    {
+        uint64_t s = std::strtoull(argv[3], nullptr, 10) * 0x9E3779B97F4A7C15ull + 1;
+        auto rnd = [&]() { s ^= s << 13; s ^= s >> 7; s ^= s << 17; return (float)((s >> 40) & 0xffff) / 65535.0f; };
+        // the light of light_scene, a soup with leaves of several sizes and a quad
+        std::vector<float> p(400 * 9), nr(400 * 9, 0.0f);
+        for (size_t i = 0; i < 400; ++i)
+        {
+            const float c[3] = {rnd() * 200.0f - 100.0f, rnd() * 200.0f - 100.0f, rnd() * 200.0f - 100.0f};
+            for (int k = 0; k < 9; ++k) p[i * 9 + k] = c[k % 3] + rnd() * 4.0f - 2.0f;
+            for (int k = 0; k < 3; ++k) nr[i * 9 + k * 3 + 1] = 1.0f;
+        }
+        const float quad[18] = {-80, 0, -80, 80, 0, -80, 80, 0, 80, -80, 0, -80, 80, 0, 80, -80, 0, 80};
+        std::vector<std::vector<float>> mats(3, std::vector<float>(kIdentity, kIdentity + 12));
+        auto make = [&](HostScene& sc) -> bool {
+            const int mat = light_scene(sc);
+            if (mat < 0 || sc.add_model(p.data(), nr.data(), 400, mat, kIdentity, 1) < 0 || sc.add_model(quad, nr.data(), 2, mat, kIdentity, 1) < 0) return false;
+            return true;
+        };
+        HostScene moved;
+        std::string err;
+        if (!make(moved) || moved.build(&err) != 0) return 3;
+        auto same = [](const auto& a, const auto& b) { return a.size() == b.size() && (a.empty() || std::memcmp(a.data(), b.data(), a.size() * sizeof(a[0])) == 0); };
+        int kept = 0;
+        for (int e = 0, n = std::atoi(argv[2]); e < n; ++e)
+        {
+            const int model = (int)(rnd() * 3.0f) % 3;
+            const uint32_t count = rnd() < 0.7f ? (uint32_t)(mats[model].size() / 12) : (uint32_t)(rnd() * 4.0f) % 4u;
+            std::vector<float> m;
+            for (uint32_t i = 0; i < count; ++i)
+            {
+                static const float turn[12] = {0, 0, 1, 0, 0, 1, 0, 0, -1, 0, 0, 0};
+                const float* rot = rnd() < 0.5f ? kIdentity : turn;
+                for (int k = 0; k < 12; ++k) m.push_back(k % 4 == 3 ? std::floor(rnd() * 100.0f) - 50.0f : rot[k]);
+            }
+            if (model == 0 && count == 0) continue; // (keep a light: nothing here depends on it, the scene stays the usual kind)
+            const uint64_t epoch = moved.layout_epoch;
+            if (moved.set_instances(model, m.data(), count) != 0 || moved.build(&err) != 0) return 4;
+            kept += moved.layout_epoch == epoch ? 1 : 0;
+            mats[model] = m;
+            HostScene fresh;
+            if (!make(fresh)) return 3;
+            for (int k = 0; k < 3; ++k)
+                if (fresh.set_instances(k, mats[k].data(), (uint32_t)(mats[k].size() / 12)) != 0) return 5;
+            if (fresh.build(&err) != 0) return 6;
+            const FlatScene &a = moved.flat, &b = fresh.flat;
+            const bool ok = same(a.nodes, b.nodes) && same(a.tri_isect, b.tri_isect) && same(a.tri_shade, b.tri_shade) && same(a.tri_pos, b.tri_pos) &&
+                            same(a.tri_orig, b.tri_orig) && same(a.instances, b.instances) && same(a.big_leaves, b.big_leaves) && same(a.materials, b.materials) &&
+                            same(a.lights, b.lights) && same(a.tri_base, b.tri_base) && same(a.inst_base, b.inst_base) && a.world_root == b.world_root &&
+                            a.lights_root == b.lights_root && a.prim_bits == b.prim_bits && a.stack_entries == b.stack_entries && a.ident_tlas == b.ident_tlas &&
+                            std::memcmp(&a.light_weight_sum, &b.light_weight_sum, 4) == 0 && a.has_volumes == b.has_volumes;
+            if (!ok) { std::printf("{\"error\": \"move %d: the incremental build differs from a build from nothing\"}\n", e); return 7; }
+        }
+        std::printf("{\"moves\": %d, \"kept_blas_part\": %d, \"blas_builds\": %llu}\n", std::atoi(argv[2]), kept, (unsigned long long)moved.blas_builds);
         return 0;
     }
     if (cmd == "plan")

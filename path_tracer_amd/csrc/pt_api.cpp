@@ -142,6 +142,14 @@ struct pt_ctx
     uint32_t ident_tlas = 0;       // FlatScene::ident_tlas of the resident scene
     uint32_t block_threads = 256, trace_blocks = 1024;
     bool class_present[Q_COUNT] = {true, false, false, false, false};
+    // what of the scene lies on the device: the layout (HostScene::layout_epoch) the blob and the tables were uploaded for.  A build that kept
+    // the layout changes only the TLAS nodes and the instance records: upload_scene patches those two ranges in place from h_patch.
+    bool resident_valid = false;
+    uint64_t resident_epoch = 0;
+    size_t resident_blob_bytes = 0;
+    std::vector<uint8_t> h_patch;  // staging copy of a patch: TLAS nodes | instance records (in flight on `stream` until it is synchronised)
+    EventHandle ev_patch;
+    uint64_t uploads_full = 0, uploads_patched = 0, last_upload_bytes = 0;
 
     // frame
     std::vector<uint32_t> rows; // local row -> global row
@@ -160,12 +168,19 @@ struct pt_ctx
 
     // denoiser (pt_render_guides / pt_denoise): first-hit guides of one sample of every local pixel and what they belong to, the hook queue
     // they are traced through, the filter's scratch images and its last result.  Nothing is allocated until the first call.
-    DevBuf d_gpos, d_gnrm, d_gmodel, d_gray_a, d_gray_b, d_ghits, d_ghead;
+    DevBuf d_gpos, d_gnrm, d_gmodel, d_ginst, d_gray_a, d_gray_b, d_ghits, d_ghead;
     bool guides_valid = false;
     uint64_t guides_scene_version = 0, guides_config_version = 0;
     uint32_t guides_sample = 0;
     uint64_t config_version = 0; // bumped by pt_set_config
     DevBuf d_dn_a, d_dn_b, d_dn_nv, d_dn_out;
+
+    // pt_frame_moving: the forward instance matrices, per model, of the build in force when the previous call returned PT_OK (the snapshot)
+    // and the build it was taken from (a call on that very build has nothing to compare); the motion table and x_prev on the device.
+    std::vector<std::vector<xf34>> snap;
+    bool snap_valid = false;
+    uint64_t snap_build = 0;
+    DevBuf d_motion, d_xprev;
     bool denoised_valid = false;
 
     // pt_integrate_rays_device: the callers' stream keys side by side, 8 bytes per ray of the longest list so far (kept: allocating and freeing
@@ -288,34 +303,13 @@ int ensure_device(pt_ctx* c)
     return PT_OK;
 }
 
-int upload_scene(pt_ctx* c)
+// Everything the launches derive from the flattened scene `f`, resident at c->d_blob as nodes | tri_isect | instances | big leaves: the
+// scene view, where the BVH is read from, the traversal stack's split between LDS and the spill area (grown when a deeper TLAS needs
+// it), the launch geometry, the walk variant and the surface classes present.  A moved instance can change any of them.
+int derive_scene_view(pt_ctx* c, const FlatScene& f, size_t blob_bytes)
 {
-    if (c->scene_uploaded) return ensure_device(c);
-    if (!c->scene.built) return fail(c, PT_ERR_STATE, "pt_build has not been called");
-    int r = ensure_device(c);
-    if (r) return r;
-    const FlatScene& f = c->scene.flat;
-    const size_t nb = f.nodes.size() * sizeof(DNode), tb = f.tri_isect.size() * sizeof(DTriIsect), ib = f.instances.size() * sizeof(DInstance);
-    const size_t lb = (f.big_leaves.size() * 4 + 15) / 16 * 16; // big-leaf table {first, count}, usually empty
-    std::vector<uint8_t> blob(nb + tb + ib + lb);
-    std::memcpy(blob.data(), f.nodes.data(), nb);
-    std::memcpy(blob.data() + nb, f.tri_isect.data(), tb);
-    std::memcpy(blob.data() + nb + tb, f.instances.data(), ib);
-    if (lb) std::memcpy(blob.data() + nb + tb + ib, f.big_leaves.data(), f.big_leaves.size() * 4);
-    if ((r = dev_alloc(c, c->d_blob, blob.size()))) return r;
-    HIPCHK(c, hipMemcpy(c->d_blob.p, blob.data(), blob.size(), hipMemcpyHostToDevice));
-    auto up = [&](DevBuf& b, const void* src, size_t bytes) -> int {
-        int rr = dev_alloc(c, b, bytes);
-        if (rr) return rr;
-        if (bytes) HIPCHK(c, hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice));
-        return PT_OK;
-    };
-    if ((r = up(c->d_tri_shade, f.tri_shade.data(), f.tri_shade.size() * sizeof(DTriVerts)))) return r;
-    if ((r = up(c->d_tri_pos, f.tri_pos.data(), f.tri_pos.size() * sizeof(DTriVerts)))) return r;
-    if ((r = up(c->d_tri_orig, f.tri_orig.data(), f.tri_orig.size() * 4))) return r;
-    if ((r = up(c->d_materials, f.materials.data(), f.materials.size() * sizeof(DMaterial)))) return r;
-    if ((r = up(c->d_lights, f.lights.data(), f.lights.size() * sizeof(DLight)))) return r;
-
+    int r;
+    const size_t nb = f.nodes.size() * sizeof(DNode), tb = f.tri_isect.size() * sizeof(DTriIsect);
     SceneView& sv = c->sv;
     uint8_t* base = (uint8_t*)c->d_blob.p;
     sv.nodes = (const DNode*)base;
@@ -335,13 +329,13 @@ int upload_scene(pt_ctx* c)
     sv.lights_root = f.lights_root;
     sv.prim_bits = f.prim_bits;
     sv.light_weight_sum = f.light_weight_sum;
-    sv.blob_bytes = (uint32_t)blob.size();
+    sv.blob_bytes = (uint32_t)blob_bytes;
     sv.stack_entries = f.stack_entries;
     sv.has_volumes = f.has_volumes ? 1u : 0u;
     c->ident_tlas = f.ident_tlas;
 
     // launch geometry of the traversal kernels: BVH in LDS when it is small, per-lane stacks always in LDS
-    c->lds_scene = blob.size() <= 48 * 1024 && !(c->cfg.flags & PT_FLAG_NO_LDS_SCENE);
+    c->lds_scene = blob_bytes <= 48 * 1024 && !(c->cfg.flags & PT_FLAG_NO_LDS_SCENE);
     uint32_t threads = 256;
 #ifndef PT_STACK_LDS_LEVELS
 #define PT_STACK_LDS_LEVELS 14
@@ -369,10 +363,80 @@ int upload_scene(pt_ctx* c)
 
     for (uint32_t q = 0; q < Q_COUNT; ++q) c->class_present[q] = (q == Q_TERMINAL);
     for (const DInstance& in : f.instances) c->class_present[in.qclass & 0xffu] = true;
-    c->scene_uploaded = true;
-    c->stats.scene_bytes = blob.size();
+    c->stats.scene_bytes = blob_bytes;
     c->stats.lds_scene = c->lds_scene;
     c->stats.stack_entries = sv.stack_entries;
+    return PT_OK;
+}
+
+int upload_scene(pt_ctx* c)
+{
+    if (c->scene_uploaded) return ensure_device(c);
+    if (!c->scene.built) return fail(c, PT_ERR_STATE, "pt_build has not been called");
+    int r = ensure_device(c);
+    if (r) return r;
+    const FlatScene& f = c->scene.flat;
+    const size_t nb = f.nodes.size() * sizeof(DNode), tb = f.tri_isect.size() * sizeof(DTriIsect), ib = f.instances.size() * sizeof(DInstance);
+    const size_t lb = (f.big_leaves.size() * 4 + 15) / 16 * 16; // big-leaf table {first, count}, usually empty
+    const size_t blob_bytes = nb + tb + ib + lb;
+
+    // The patch path.  Node layout: world TLAS | lights TLAS | BLAS 0 ..; a TLAS over n leaves has 2n - 1 nodes whatever its shape.  With the
+    // layout the device holds (no model or material added, every instance count kept) every offset and the blob's size are what they were,
+    // and only the TLAS nodes in front and the instance records differ: two copies on the context's stream, behind whatever the
+    // pipelines still have in flight, and nothing allocated or freed (a deeper TLAS may grow the spill area in derive_scene_view).
+    if (c->resident_valid && c->resident_epoch == c->scene.layout_epoch && c->resident_blob_bytes == blob_bytes && c->d_blob.p)
+    {
+        const size_t tlas_nodes = c->scene.world.nodes.size() + c->scene.lights.nodes.size();
+        const size_t pn = tlas_nodes * sizeof(DNode);
+        if (pn > nb) return fail(c, PT_ERR_STATE, "internal: TLAS nodes exceed the node array");
+        HIPCHK(c, hipStreamSynchronize(c->stream)); // an earlier patch may still be reading h_patch
+        if (!c->ev_patch.p) HIPCHK(c, hipEventCreateWithFlags(c->ev_patch.out(), hipEventDisableTiming));
+        for (int i = 1; i < pt_ctx::kMaxPipes; ++i)
+        {
+            HIPCHK(c, hipEventRecord(c->ev_patch, c->pipe_stream(i)));
+            HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_patch, 0));
+        }
+        c->h_patch.resize(pn + ib);
+        if (pn) std::memcpy(c->h_patch.data(), f.nodes.data(), pn);
+        if (ib) std::memcpy(c->h_patch.data() + pn, f.instances.data(), ib);
+        uint8_t* base = (uint8_t*)c->d_blob.p;
+        if (pn) HIPCHK(c, hipMemcpyAsync(base, c->h_patch.data(), pn, hipMemcpyHostToDevice, c->stream));
+        if (ib) HIPCHK(c, hipMemcpyAsync(base + nb + tb, c->h_patch.data() + pn, ib, hipMemcpyHostToDevice, c->stream));
+        if ((r = derive_scene_view(c, f, blob_bytes))) { c->resident_valid = false; return r; }
+        c->scene_uploaded = true;
+        c->uploads_patched++;
+        c->last_upload_bytes = pn + ib;
+        return PT_OK;
+    }
+
+    c->resident_valid = false;
+    std::vector<uint8_t> blob(blob_bytes);
+    std::memcpy(blob.data(), f.nodes.data(), nb);
+    std::memcpy(blob.data() + nb, f.tri_isect.data(), tb);
+    std::memcpy(blob.data() + nb + tb, f.instances.data(), ib);
+    if (lb) std::memcpy(blob.data() + nb + tb + ib, f.big_leaves.data(), f.big_leaves.size() * 4);
+    if ((r = dev_alloc(c, c->d_blob, blob.size()))) return r;
+    HIPCHK(c, hipMemcpy(c->d_blob.p, blob.data(), blob.size(), hipMemcpyHostToDevice));
+    uint64_t copied = blob.size();
+    auto up = [&](DevBuf& b, const void* src, size_t bytes) -> int {
+        int rr = dev_alloc(c, b, bytes);
+        if (rr) return rr;
+        if (bytes) HIPCHK(c, hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice));
+        copied += bytes;
+        return PT_OK;
+    };
+    if ((r = up(c->d_tri_shade, f.tri_shade.data(), f.tri_shade.size() * sizeof(DTriVerts)))) return r;
+    if ((r = up(c->d_tri_pos, f.tri_pos.data(), f.tri_pos.size() * sizeof(DTriVerts)))) return r;
+    if ((r = up(c->d_tri_orig, f.tri_orig.data(), f.tri_orig.size() * 4))) return r;
+    if ((r = up(c->d_materials, f.materials.data(), f.materials.size() * sizeof(DMaterial)))) return r;
+    if ((r = up(c->d_lights, f.lights.data(), f.lights.size() * sizeof(DLight)))) return r;
+    if ((r = derive_scene_view(c, f, blob_bytes))) return r;
+    c->scene_uploaded = true;
+    c->resident_valid = true;
+    c->resident_epoch = c->scene.layout_epoch;
+    c->resident_blob_bytes = blob_bytes;
+    c->uploads_full++;
+    c->last_upload_bytes = copied;
     return PT_OK;
 }
 
@@ -1477,6 +1541,32 @@ int pt_build(pt_ctx* c)
     return PT_OK;
 }
 
+int pt_set_instances(pt_ctx* c, int model, const float* affines, uint32_t n_inst)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    int r;
+    try { r = c->scene.set_instances(model, affines, n_inst); }
+    catch (const std::exception& e) { return fail(c, PT_ERR_LIMIT, std::string("instance matrices do not fit in host memory: ") + e.what()); }
+    if (r == -4) return fail(c, PT_ERR_NONRIGID, "Model matrix can only contain translation and rotation");
+    if (r < 0) return fail(c, PT_ERR_ARG, "bad model index or matrices");
+    c->scene_uploaded = false;
+    return PT_OK;
+}
+
+int pt_get_scene_info(pt_ctx* c, pt_scene_info* out)
+{
+    if (!c || !out) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    std::memset(out, 0, sizeof(*out));
+    out->blas_builds = c->scene.blas_builds;
+    out->tlas_builds = c->scene.tlas_builds;
+    out->uploads_full = c->uploads_full;
+    out->uploads_patched = c->uploads_patched;
+    out->last_upload_bytes = c->last_upload_bytes;
+    return PT_OK;
+}
+
 int pt_set_camera(pt_ctx* c, const float eye[3], const float target[3], float fov_y_deg, float aspect)
 {
     if (!c || !eye || !target) return PT_ERR_ARG;
@@ -1774,10 +1864,54 @@ int pt_inv_projection(pt_ctx* c, float out16[16])
     return PT_OK;
 }
 
-int pt_frame(pt_ctx* c, uint32_t frame_index, const float* last_inv_projection, float* data, float* position, uint32_t* id)
+} // extern "C"
+
+namespace {
+void xf_rows(const xf34& x, float* o) // the 3x4 as the C-ABI hands matrices out: 12 floats, row by row
 {
-    if (!c) return PT_ERR_ARG;
-    std::lock_guard<std::mutex> lk(c->mu);
+    const float r[12] = {x.m.c0.x, x.m.c1.x, x.m.c2.x, x.t.x, x.m.c0.y, x.m.c1.y, x.m.c2.y, x.t.y, x.m.c0.z, x.m.c1.z, x.m.c2.z, x.t.z};
+    std::memcpy(o, r, sizeof(r));
+}
+
+// pt_frame_moving: when the build in force is not the one the snapshot was taken from, makes the motion table (once per build: the
+// snapshot is retaken when the call returns) and says whether the world moved since the snapshot: some instance has a previous matrix that
+// is not bit-equal to its matrix, or some model's instance count differs — a model added since then had none there.
+int prepare_motion(pt_ctx* c, bool* world_moved)
+{
+    *world_moved = false;
+    if (!c->snap_valid || c->snap_build == c->scene.tlas_builds) return PT_OK; // no snapshot yet, or taken from this very build
+    const HostScene& sc = c->scene;
+    bool moved = false;
+    for (size_t m = 0; m < sc.models.size(); ++m)
+        if ((m < c->snap.size() ? c->snap[m].size() : 0) != sc.models[m].matrices.size()) moved = true;
+    std::vector<MotionRow> rows(sc.world.instances.size());
+    std::vector<uint32_t> ordinal(sc.models.size(), 0u);
+    for (size_t i = 0; i < rows.size(); ++i)
+    {
+        const HostInstance& hi = sc.world.instances[i];
+        MotionRow& row = rows[i];
+        std::memset(&row, 0, sizeof(row));
+        const uint32_t j = ordinal[hi.model]++;
+        xf_rows(hi.inv, row.inv);
+        if (hi.model >= c->snap.size() || c->snap[hi.model].size() != sc.models[hi.model].matrices.size()) continue; // no previous matrix
+        float cur[12];
+        xf_rows(hi.fwd, cur);
+        xf_rows(c->snap[hi.model][j], row.prv);
+        row.moved = std::memcmp(cur, row.prv, sizeof(cur)) != 0 ? 1u : 0u;
+        moved = moved || row.moved;
+    }
+    int r;
+    if ((r = dev_alloc(c, c->d_motion, std::max<size_t>(rows.size(), 1) * sizeof(MotionRow)))) return r;
+    if (!rows.empty()) HIPCHK(c, hipMemcpy(c->d_motion.p, rows.data(), rows.size() * sizeof(MotionRow), hipMemcpyHostToDevice));
+    *world_moved = moved;
+    return PT_OK;
+}
+
+int render_guides_locked(pt_ctx* c, uint32_t sample);
+
+// pt_frame (moving = false) and pt_frame_moving under the context's lock
+int frame_locked(pt_ctx* c, uint32_t frame_index, const float* last_inv_projection, float* data, float* position, uint32_t* id, bool moving)
+{
     int r;
     if ((r = precheck(c))) return r;
     if (c->cfg.world_size != 1) return fail(c, PT_ERR_STATE, "pt_frame needs the whole frame on one rank (3x3 neighbourhoods cross row strips)");
@@ -1796,16 +1930,27 @@ int pt_frame(pt_ctx* c, uint32_t frame_index, const float* last_inv_projection, 
     hipStream_t s = c->stream;
     const int w = (int)c->cfg.width, h = (int)c->cfg.height;
     bool moved = false;                                                                                                    // state.rs:549 `inv_projection == last_inv_projection`
+    float cur[16];
+    c->scene.inv_projection(cur);
     if (last_inv_projection)
-    {
-        float cur[16];
-        c->scene.inv_projection(cur);
         for (int i = 0; i < 16; ++i) moved |= !(cur[i] == last_inv_projection[i]);
+    // a world that may have moved: the guides of this sample (their instance guide names every pixel's first-hit instance), then the
+    // first-hit points carried back by their instances' motion feed the velocity instead of the points themselves
+    bool world_moved = false;
+    if (moving && ((r = render_guides_locked(c, frame_index)) || (r = prepare_motion(c, &world_moved)))) return r;
+    const f4* vel_from = (const f4*)c->d_position.p;
+    if (world_moved)
+    {
+        if ((r = dev_alloc(c, c->d_xprev, std::max<size_t>(px, 1) * 16))) return r;
+        launch_post_motion(s, (uint32_t)px, (const f4*)c->d_position.p, (const uint32_t*)c->d_ginst.p, (uint32_t)c->scene.world.instances.size(),
+                           (const MotionRow*)c->d_motion.p, (f4*)c->d_xprev.p);
+        vel_from = (const f4*)c->d_xprev.p;
+        moved = true;
     }
     if (!moved) launch_post_accumulate(s, (uint32_t)px, (const f4*)c->d_input.p, (f4*)c->d_accum.p);           // state.rs:561-566
     else
     {
-        launch_post_velocity(s, w, h, (const f4*)c->d_position.p, last_inv_projection, (float*)c->d_velocity.p);            // state.rs:569-572
+        launch_post_velocity(s, w, h, vel_from, last_inv_projection ? last_inv_projection : cur, (float*)c->d_velocity.p);  // state.rs:569-572
         launch_post_reproject(s, w, h, (const f4*)c->d_input.p, (const f4*)c->d_accum.p, (const float*)c->d_velocity.p,
                               (const uint32_t*)c->d_id.p, (f4*)c->d_output.p);                                              // state.rs:574-578
         HIPCHK(c, hipMemcpyAsync(c->d_accum.p, c->d_output.p, px * 16, hipMemcpyDeviceToDevice, s));                        // state.rs:583
@@ -1815,7 +1960,32 @@ int pt_frame(pt_ctx* c, uint32_t frame_index, const float* last_inv_projection, 
     if (id) HIPCHK(c, hipMemcpyAsync(id, c->d_id.p, px * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     HIPCHK(c, hipGetLastError());
+    if (moving && !(c->snap_valid && c->snap_build == c->scene.tlas_builds))
+    {
+        // the snapshot the next call compares with: this build's matrices (a render needs a built scene, so the models hold exactly them)
+        c->snap.resize(c->scene.models.size());
+        for (size_t m = 0; m < c->scene.models.size(); ++m) c->snap[m] = c->scene.models[m].matrices;
+        c->snap_valid = true;
+        c->snap_build = c->scene.tlas_builds;
+    }
     return PT_OK;
+}
+} // namespace
+
+extern "C" {
+
+int pt_frame(pt_ctx* c, uint32_t frame_index, const float* last_inv_projection, float* data, float* position, uint32_t* id)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    return frame_locked(c, frame_index, last_inv_projection, data, position, id, false);
+}
+
+int pt_frame_moving(pt_ctx* c, uint32_t frame_index, const float* last_inv_projection, float* data, float* position, uint32_t* id)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    return frame_locked(c, frame_index, last_inv_projection, data, position, id, true);
 }
 
 int pt_present(pt_ctx* c, float* rgba)
@@ -1885,6 +2055,36 @@ int pt_post_velocity(pt_ctx* c, uint32_t w, uint32_t h, const float* position, c
     return t.download(velocity, dv, px * 8);
 }
 
+int pt_post_motion(pt_ctx* c, uint32_t w, uint32_t h, const float* position, const uint32_t* instance, uint32_t n_instances, const float* matrix12,
+                   const float* inv_matrix12, const float* prev_matrix12, const uint8_t* has_prev, float* x_prev)
+{
+    if (!c || !position || !instance || !x_prev || !w || !h) return PT_ERR_ARG;
+    if (n_instances && (!matrix12 || !inv_matrix12 || !prev_matrix12)) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    const size_t px = (size_t)w * h;
+    for (size_t i = 0; i < px; ++i)
+        if (instance[i] != MISS_ID && instance[i] >= n_instances) return fail(c, PT_ERR_ARG, "instance image names an instance outside the tables");
+    int r;
+    if ((r = ensure_device(c))) return r;
+    std::vector<MotionRow> rows(std::max<uint32_t>(n_instances, 1u));
+    std::memset(rows.data(), 0, rows.size() * sizeof(MotionRow));
+    for (uint32_t i = 0; i < n_instances; ++i)
+    {
+        std::memcpy(rows[i].inv, inv_matrix12 + 12 * (size_t)i, 48);
+        if (has_prev && !has_prev[i]) continue;
+        std::memcpy(rows[i].prv, prev_matrix12 + 12 * (size_t)i, 48);
+        rows[i].moved = std::memcmp(matrix12 + 12 * (size_t)i, rows[i].prv, 48) != 0 ? 1u : 0u;
+    }
+    Staging t(c);
+    const f4* dp = (const f4*)t.in(position, px * 16);
+    const uint32_t* di = (const uint32_t*)t.in(instance, px * 4);
+    const MotionRow* dr = (const MotionRow*)t.in(rows.data(), rows.size() * sizeof(MotionRow));
+    f4* dx = (f4*)t.out(px * 16);
+    if (t.err) return t.err;
+    launch_post_motion(c->stream, (uint32_t)px, dp, di, n_instances, dr, dx);
+    return t.download(x_prev, dx, px * 16);
+}
+
 int pt_post_reproject(pt_ctx* c, uint32_t w, uint32_t h, const float* input, const float* accum, const float* velocity, const uint32_t* id, float* output)
 {
     if (!c || !input || !accum || !velocity || !id || !output || !w || !h) return PT_ERR_ARG;
@@ -1934,10 +2134,11 @@ int pt_post_rgb8(pt_ctx* c, uint32_t w, uint32_t h, const float* accum, uint8_t*
 }
 
 // ---- denoiser: first-hit guides + edge-aware a-trous filter
-int pt_render_guides(pt_ctx* c, uint32_t sample)
+} // extern "C"
+
+namespace {
+int render_guides_locked(pt_ctx* c, uint32_t sample)
 {
-    if (!c) return PT_ERR_ARG;
-    std::lock_guard<std::mutex> lk(c->mu);
     if (!c->scene.built) return fail(c, PT_ERR_STATE, "pt_build has not been called");
     if (!c->scene.camera.set) return fail(c, PT_ERR_STATE, "pt_set_camera has not been called");
     int r;
@@ -1946,7 +2147,7 @@ int pt_render_guides(pt_ctx* c, uint32_t sample)
     const size_t n = std::max<uint32_t>(px, 1);
     for (DevBuf* b : {&c->d_gpos, &c->d_gnrm, &c->d_gray_a, &c->d_gray_b, &c->d_ghits})
         if ((r = dev_alloc(c, *b, n * 16))) return r;
-    if ((r = dev_alloc(c, c->d_gmodel, n * 4)) || (r = dev_alloc(c, c->d_ghead, ((size_t)32 + kHeadWordsPerQueue) * 4))) return r;
+    if ((r = dev_alloc(c, c->d_gmodel, n * 4)) || (r = dev_alloc(c, c->d_ginst, n * 4)) || (r = dev_alloc(c, c->d_ghead, ((size_t)32 + kHeadWordsPerQueue) * 4))) return r;
     c->guides_valid = false;
     if (px)
     {
@@ -1973,7 +2174,8 @@ int pt_render_guides(pt_ctx* c, uint32_t sample)
         // (an empty world: every ray misses)
         if (c->sv.world_root == MISS_ID) HIPCHK(c, hipMemsetAsync(c->d_ghits.p, 0xff, (size_t)px * 16, c->stream));
         else launch_trace_rays_closest(c->stream, trace_launch(c), c->sv.world_root, q, px, head, (f4*)c->d_ghits.p);
-        launch_guide_resolve(c->stream, c->sv, px, cam, lens, q, (const f4*)c->d_ghits.p, (f4*)c->d_gpos.p, (f4*)c->d_gnrm.p, (uint32_t*)c->d_gmodel.p);
+        launch_guide_resolve(c->stream, c->sv, px, cam, lens, q, (const f4*)c->d_ghits.p, (f4*)c->d_gpos.p, (f4*)c->d_gnrm.p, (uint32_t*)c->d_gmodel.p,
+                             (uint32_t*)c->d_ginst.p);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
@@ -1981,6 +2183,28 @@ int pt_render_guides(pt_ctx* c, uint32_t sample)
     c->guides_scene_version = c->scene_version;
     c->guides_config_version = c->config_version;
     c->guides_sample = sample;
+    return PT_OK;
+}
+} // namespace
+
+extern "C" {
+
+int pt_render_guides(pt_ctx* c, uint32_t sample)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    return render_guides_locked(c, sample);
+}
+
+int pt_read_guide_instances(pt_ctx* c, uint32_t* instance)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->guides_valid) return fail(c, PT_ERR_STATE, "no guides: pt_render_guides first");
+    const size_t px = c->local_pixels;
+    if (!px || !instance) return PT_OK;
+    HIPCHK(c, hipMemcpyAsync(instance, c->d_ginst.p, px * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return PT_OK;
 }
 
@@ -2368,11 +2592,7 @@ int pt_tlas_instances(pt_ctx* c, int which, uint32_t* n, float* matrix12, float*
     const HostTlas& t = which ? c->scene.lights : c->scene.world;
     *n = (uint32_t)t.instances.size();
     if (t.instances.size() > cap || !matrix12 || !inv_matrix12) return PT_ERR_ARG;
-    auto rows = [](const xf34& x, float* o) {
-        const float r[12] = {x.m.c0.x, x.m.c1.x, x.m.c2.x, x.t.x, x.m.c0.y, x.m.c1.y, x.m.c2.y, x.t.y, x.m.c0.z, x.m.c1.z, x.m.c2.z, x.t.z};
-        std::memcpy(o, r, sizeof(r));
-    };
-    for (size_t i = 0; i < t.instances.size(); ++i) { rows(t.instances[i].fwd, matrix12 + 12 * i); rows(t.instances[i].inv, inv_matrix12 + 12 * i); }
+    for (size_t i = 0; i < t.instances.size(); ++i) { xf_rows(t.instances[i].fwd, matrix12 + 12 * i); xf_rows(t.instances[i].inv, inv_matrix12 + 12 * i); }
     return PT_OK;
 }
 
@@ -2487,6 +2707,7 @@ int multi_replicate(pt_multi* m)
         std::lock_guard<std::mutex> lk(c->mu);
         c->scene = c0->scene;
         c->scene_uploaded = false;
+        c->resident_valid = false; // a replica takes the full upload
         c->h_env = c0->h_env;
         c->env_w = c0->env_w;
         c->env_h = c0->env_h;

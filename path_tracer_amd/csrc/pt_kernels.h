@@ -129,6 +129,15 @@ void launch_adaptive_select(hipStream_t s, const f4* accum, const float* moments
 // after the path (pt_post.hip)
 void launch_post_accumulate(hipStream_t s, uint32_t n, const f4* input, f4* accum);
 void launch_post_velocity(hipStream_t s, int w, int h, const f4* position, const float* m16, float* velocity_xy);
+// pt_frame_moving's motion table, one row per world-TLAS instance: rows of its inverse matrix now and of its forward matrix in the previous
+// frame's build; moved = 0 where it has no previous matrix or that matrix is bit-equal to the current one (the point is then passed on)
+struct MotionRow
+{
+    float inv[12], prv[12];
+    uint32_t moved, pad[3];
+};
+static_assert(sizeof(MotionRow) == 112, "");
+void launch_post_motion(hipStream_t s, uint32_t n, const f4* position, const uint32_t* instance, uint32_t n_instances, const MotionRow* rows, f4* x_prev);
 void launch_post_reproject(hipStream_t s, int w, int h, const f4* input, const f4* accum, const float* velocity_xy, const uint32_t* id, f4* output);
 void launch_post_tonemap(hipStream_t s, uint32_t n, const f4* accum, f4* out);
 void launch_post_rgb8(hipStream_t s, uint32_t n, const f4* accum, uint8_t* out);
@@ -149,7 +158,7 @@ void launch_denoise(hipStream_t s, int w, int h, const DenoiseK& p, const f4* ac
 void launch_guide_rays(hipStream_t s, const RenderParams& rp, const CameraView& cam, const LensView& lens, RayQueue rq, uint32_t* n_and_heads);
 // their launch_trace_rays_closest hits -> position, normal, model guides
 void launch_guide_resolve(hipStream_t s, const SceneView& sv, uint32_t n, const CameraView& cam, const LensView& lens, RayQueue rq, const f4* hits,
-                          f4* position, f4* normal, uint32_t* model);
+                          f4* position, f4* normal, uint32_t* model, uint32_t* instance);
 
 // unit hooks
 // n_and_heads: word 0 = number of rays, words [32, 32 + kHeadWordsPerQueue) = zeroed claim cursors

@@ -2803,11 +2803,13 @@ __global__ void __launch_bounds__(256) k_guide_rays_lens(const RenderParams rp, 
 
 // first-hit guides of those rays: position r.at(t) | t as the render keeps it (r.at(1e5) | 1e5 for a miss, integrator.rs:156), the
 // face-forwarded world shading normal of the hit (HitInfo's, primitive.rs:161-165 + tlas.rs:105; 0 for a miss) and the hit's model
-// (BLAS index, MISS_ID for a miss) in full: its low byte is the id byte of main.rs:206
+// (BLAS index, MISS_ID for a miss) in full: its low byte is the id byte of main.rs:206; and the world-TLAS leaf of the hit in allocation
+// order (the index of pt_tlas_instances(ctx, 0, ..); MISS_ID for a miss), which pt_frame_moving reprojects a moved instance's pixels by
 // LENS (pt_set_lens): the ray's origin is its own (rq.a) instead of the eye
 template <bool LENS>
 __device__ __forceinline__ void guide_resolve_body(const SceneView& sv, const uint32_t n, const CameraView& cam, const RayQueue& rq, const f4* __restrict__ hits,
-                                                   f4* __restrict__ position, f4* __restrict__ normal, uint32_t* __restrict__ model)
+                                                   f4* __restrict__ position, f4* __restrict__ normal, uint32_t* __restrict__ model,
+                                                   uint32_t* __restrict__ instance)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -2821,6 +2823,7 @@ __device__ __forceinline__ void guide_resolve_body(const SceneView& sv, const ui
         position[i] = f4{far.x, far.y, far.z, 1e5f};
         normal[i] = f4{0.0f, 0.0f, 0.0f, 0.0f};
         model[i] = MISS_ID;
+        instance[i] = MISS_ID;
         return;
     }
     const uint32_t inst = hid >> sv.prim_bits, tri = hid & ((1u << sv.prim_bits) - 1u);
@@ -2830,18 +2833,19 @@ __device__ __forceinline__ void guide_resolve_body(const SceneView& sv, const ui
     position[i] = f4{p.x, p.y, p.z, hit.x};
     normal[i] = f4{nrm.x, nrm.y, nrm.z, 0.0f};
     model[i] = sv.instances[inst].blas;
+    instance[i] = inst; // the world TLAS's records are the first of the instance array
 }
 __global__ void __launch_bounds__(256) k_guide_resolve(const SceneView sv, const uint32_t n, const CameraView cam, const RayQueue rq,
                                                        const f4* __restrict__ hits, f4* __restrict__ position, f4* __restrict__ normal,
-                                                       uint32_t* __restrict__ model)
+                                                       uint32_t* __restrict__ model, uint32_t* __restrict__ instance)
 {
-    guide_resolve_body<false>(sv, n, cam, rq, hits, position, normal, model);
+    guide_resolve_body<false>(sv, n, cam, rq, hits, position, normal, model, instance);
 }
 __global__ void __launch_bounds__(256) k_guide_resolve_lens(const SceneView sv, const uint32_t n, const CameraView cam, const RayQueue rq,
                                                             const f4* __restrict__ hits, f4* __restrict__ position, f4* __restrict__ normal,
-                                                            uint32_t* __restrict__ model)
+                                                            uint32_t* __restrict__ model, uint32_t* __restrict__ instance)
 {
-    guide_resolve_body<true>(sv, n, cam, rq, hits, position, normal, model);
+    guide_resolve_body<true>(sv, n, cam, rq, hits, position, normal, model, instance);
 }
 
 } // namespace
@@ -3224,10 +3228,10 @@ void launch_guide_rays(hipStream_t s, const RenderParams& rp, const CameraView& 
     else hipLaunchKernelGGL(k_guide_rays, dim3((rp.local_pixels + 255u) / 256u), dim3(256), 0, s, rp, cam, rq, n_and_heads);
 }
 void launch_guide_resolve(hipStream_t s, const SceneView& sv, uint32_t n, const CameraView& cam, const LensView& lens, RayQueue rq, const f4* hits, f4* position,
-                          f4* normal, uint32_t* model)
+                          f4* normal, uint32_t* model, uint32_t* instance)
 {
-    if (lens_set(lens)) hipLaunchKernelGGL(k_guide_resolve_lens, dim3((n + 255u) / 256u), dim3(256), 0, s, sv, n, cam, rq, hits, position, normal, model);
-    else hipLaunchKernelGGL(k_guide_resolve, dim3((n + 255u) / 256u), dim3(256), 0, s, sv, n, cam, rq, hits, position, normal, model);
+    if (lens_set(lens)) hipLaunchKernelGGL(k_guide_resolve_lens, dim3((n + 255u) / 256u), dim3(256), 0, s, sv, n, cam, rq, hits, position, normal, model, instance);
+    else hipLaunchKernelGGL(k_guide_resolve, dim3((n + 255u) / 256u), dim3(256), 0, s, sv, n, cam, rq, hits, position, normal, model, instance);
 }
 
 } // namespace pt

@@ -3,6 +3,7 @@
 //
 //   k_post_accumulate   src/shaders/accumulate.wgsl:20-23     static camera: accumulation += (rgb, 1)
 //   k_post_velocity     src/shaders/velocity.wgsl:16-39       per-pixel motion vector from the first-hit position
+//   k_post_motion       (no reference counterpart) where a pixel's first hit was in the previous frame, by its instance's motion
 //   k_post_reproject    src/shaders/compute.wgsl:103-212      3x3 YCoCg variance clip, Catmull-Rom history, id disocclusion, 15 % blend
 //   k_post_tonemap      src/shaders/shader.wgsl:3-33,59-64    Uchimura "GT" curve on accumulation.rgb / accumulation.w
 //   k_post_rgb8         src/image_helper.rs:41-48 + src/image_helper/tonemapping.rs   the 8-bit gamma-2.2 image write_image saves
@@ -155,6 +156,29 @@ __global__ void __launch_bounds__(256) k_post_velocity(int w, int h, const f4* _
     for (int k = 0; k < 4; ++k) r[k] = ((M.m[k] * P.x + M.m[4 + k] * P.y) + M.m[8 + k] * P.z) + M.m[12 + k] * 1.0f;
     const f3 d = w_divide(f4{r[0], r[1], r[2], r[3]});
     velocity[i] = make_float2(cu - (d.x * 0.5f + 0.5f), cv - (d.y * 0.5f + 0.5f));
+}
+
+// pt_frame_moving: the first-hit point of every pixel carried back to where its instance had it in the previous frame: into object space
+// with the instance's inverse matrix, out again with its previous forward matrix (glam's transform_point3, twice).  A miss, an instance
+// without a previous matrix or one that did not move passes the point on untouched, bit for bit.  w (the hit distance) is kept.
+__global__ void __launch_bounds__(256) k_post_motion(uint32_t n, const f4* __restrict__ position, const uint32_t* __restrict__ instance, uint32_t n_instances,
+                                                      const MotionRow* __restrict__ rows, f4* __restrict__ x_prev)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    f4 P = position[i];
+    const uint32_t inst = instance[i];
+    if (inst < n_instances && rows[inst].moved)
+    {
+        const MotionRow& m = rows[inst];
+        float o[3], q[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) o[k] = ((m.inv[4 * k] * P.x + m.inv[4 * k + 1] * P.y) + m.inv[4 * k + 2] * P.z) + m.inv[4 * k + 3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) q[k] = ((m.prv[4 * k] * o[0] + m.prv[4 * k + 1] * o[1]) + m.prv[4 * k + 2] * o[2]) + m.prv[4 * k + 3];
+        P = f4{q[0], q[1], q[2], P.w};
+    }
+    x_prev[i] = P;
 }
 
 __global__ void __launch_bounds__(256) k_post_reproject(int w, int h, const f4* __restrict__ input, const f4* __restrict__ accum,
@@ -441,6 +465,10 @@ void launch_post_velocity(hipStream_t s, int w, int h, const f4* position, const
     Mat4 M;
     for (int i = 0; i < 16; ++i) M.m[i] = m16[i];
     hipLaunchKernelGGL(k_post_velocity, dim3((w * h + 255) / 256), dim3(256), 0, s, w, h, position, M, reinterpret_cast<float2*>(velocity_xy));
+}
+void launch_post_motion(hipStream_t s, uint32_t n, const f4* position, const uint32_t* instance, uint32_t n_instances, const MotionRow* rows, f4* x_prev)
+{
+    hipLaunchKernelGGL(k_post_motion, dim3((n + 255u) / 256u), dim3(256), 0, s, n, position, instance, n_instances, rows, x_prev);
 }
 void launch_post_reproject(hipStream_t s, int w, int h, const f4* input, const f4* accum, const float* velocity_xy, const uint32_t* id, f4* output)
 {

@@ -329,6 +329,24 @@ f3 unit3_recip(f3 v) { float r = 1.0f / sqrtf(dot3(v, v)); return v * r; } // gl
 
 } // namespace
 
+namespace {
+// n rows-of-3x4 transforms as Model::new takes them; false where model.rs:40-44 panics
+bool rigid_matrices(const float* affines, uint32_t n_inst, std::vector<xf34>& out)
+{
+    for (uint32_t i = 0; i < n_inst; ++i)
+    {
+        const float* r = affines + (size_t)i * 12;
+        xf34 x{m33{f3{r[0], r[4], r[8]}, f3{r[1], r[5], r[9]}, f3{r[2], r[6], r[10]}}, f3{r[3], r[7], r[11]}};
+        // model.rs:40-44: to_scale_rotation_translation().0 == Vec3::ONE or panic
+        const float det = dot3(x.m.c2, cross3(x.m.c0, x.m.c1));
+        const float sx = len3(x.m.c0) * signum_rs(det), sy = len3(x.m.c1), sz = len3(x.m.c2);
+        if (!(sx == 1.0f && sy == 1.0f && sz == 1.0f)) return false;
+        out.push_back(x);
+    }
+    return true;
+}
+} // namespace
+
 int HostScene::add_material(int kind, const float colour[3], float roughness, float ior, bool has_volume, const float vol_abs[3], float k,
                             float c, float g)
 {
@@ -347,6 +365,7 @@ int HostScene::add_material(int kind, const float colour[3], float roughness, fl
     }
     materials.push_back(m);
     built = false;
+    ++layout_epoch;
     return (int)materials.size() - 1;
 }
 
@@ -364,19 +383,22 @@ int HostScene::add_model(const float* positions, const float* normals, uint32_t 
     m.material = material;
     m.positions.assign(positions, positions + (size_t)n_tris * 9);
     m.normals.assign(normals, normals + (size_t)n_tris * 9);
-    for (uint32_t i = 0; i < n_inst; ++i)
-    {
-        const float* r = affines + (size_t)i * 12;
-        xf34 x{m33{f3{r[0], r[4], r[8]}, f3{r[1], r[5], r[9]}, f3{r[2], r[6], r[10]}}, f3{r[3], r[7], r[11]}};
-        // model.rs:40-44: to_scale_rotation_translation().0 == Vec3::ONE or panic
-        const float det = dot3(x.m.c2, cross3(x.m.c0, x.m.c1));
-        const float sx = len3(x.m.c0) * signum_rs(det), sy = len3(x.m.c1), sz = len3(x.m.c2);
-        if (!(sx == 1.0f && sy == 1.0f && sz == 1.0f)) return -4;
-        m.matrices.push_back(x);
-    }
+    if (!rigid_matrices(affines, n_inst, m.matrices)) return -4;
     models.push_back(std::move(m));
     built = false;
+    ++layout_epoch;
     return (int)models.size() - 1;
+}
+
+int HostScene::set_instances(int model, const float* affines, uint32_t n_inst)
+{
+    if (model < 0 || model >= (int)models.size() || (n_inst && !affines)) return -1;
+    std::vector<xf34> matrices;
+    if (!rigid_matrices(affines, n_inst, matrices)) return -4;
+    if (matrices.size() != models[model].matrices.size()) ++layout_epoch;
+    models[model].matrices = std::move(matrices);
+    built = false;
+    return 0;
 }
 
 // load_obj  src/tlas/tlas_bvh/blas.rs:44-131: `v`, `vn` (normalised on load), `f` with v/vt/vn references (1-based, negative =
@@ -605,8 +627,15 @@ int HostScene::build(std::string* err)                                          
     auto now = [] { return std::chrono::steady_clock::now(); };
     auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
     const auto t0 = now();
-    blas.resize(models.size());
-    for (size_t i = 0; i < models.size(); ++i) build_blas(blas[i], models[i]);
+    // models have no geometry edit and a BLAS lives in object space: "model i already has a BLAS" is the whole dirty test
+    blas.reserve(models.size());
+    while (blas.size() < models.size())
+    {
+        HostBlas b;
+        build_blas(b, models[blas.size()]);
+        blas.push_back(std::move(b));
+        ++blas_builds;
+    }
     const auto t1 = now();
     std::vector<uint32_t> all(models.size()), emissive;
     std::iota(all.begin(), all.end(), 0u);
@@ -615,6 +644,7 @@ int HostScene::build(std::string* err)                                          
     build_tlas(world, all);
     build_tlas(lights, emissive);
     build_lights();
+    ++tlas_builds;
     const auto t2 = now();
     int r = flatten(err);
     if (dbg) fprintf(stderr, "[ptmi] scene build: BLAS %.1f ms, TLAS + lights %.1f ms, flatten %.1f ms\n", ms(t0, t1), ms(t1, t2), ms(t2, now()));
@@ -667,7 +697,21 @@ int HostScene::flatten(std::string* err)
         tri_cursor += (uint32_t)blas[i].prim_ids.size();
     }
     if (cursor > NODE_PAYLOAD_MASK || tri_cursor > NODE_PAYLOAD_MASK) { if (err) *err = "scene too large for 30-bit node payloads"; return -5; }
-    f.nodes.resize(cursor);
+    // Nothing behind the two TLASes depends on an instance matrix.  When no edit since the last flatten moved an offset (same layout_epoch:
+    // same models, materials and instance counts, hence the same 2n - 1 TLAS nodes in front), the BLAS nodes, the big-leaf table and the
+    // per-triangle tables of that flatten ARE what the loops below would write again, word for word: they are taken over instead.
+    const bool keep_blas = flat_valid && flat_epoch == layout_epoch && flat.nodes.size() == cursor && flat.tri_orig.size() == tri_cursor;
+    flat_valid = false;
+    if (keep_blas)
+    {
+        f.nodes = std::move(flat.nodes);
+        f.big_leaves = std::move(flat.big_leaves);
+        f.tri_isect = std::move(flat.tri_isect);
+        f.tri_shade = std::move(flat.tri_shade);
+        f.tri_pos = std::move(flat.tri_pos);
+        f.tri_orig = std::move(flat.tri_orig);
+    }
+    else f.nodes.resize(cursor);
     f.inst_base = {0u, (uint32_t)world.instances.size()};
 
     auto put_box = [](DNode& d, const HostBox& b) {
@@ -744,16 +788,20 @@ int HostScene::flatten(std::string* err)
 
     uint32_t max_blas_depth = 0;
     std::vector<uint32_t> blas_root_at(blas.size(), MISS_ID);
-    f.tri_isect.reserve(tri_cursor);
-    f.tri_shade.reserve(tri_cursor);
-    f.tri_pos.reserve(tri_cursor);
-    f.tri_orig.reserve(tri_cursor);
+    if (!keep_blas)
+    {
+        f.tri_isect.reserve(tri_cursor);
+        f.tri_shade.reserve(tri_cursor);
+        f.tri_pos.reserve(tri_cursor);
+        f.tri_orig.reserve(tri_cursor);
+    }
     for (size_t i = 0; i < blas.size(); ++i)
     {
         const HostBlas& bl = blas[i];
         max_blas_depth = std::max(max_blas_depth, bl.depth);
+        blas_root_at[i] = blas_base[i];                                                  // the root is the first node of its tree
+        if (keep_blas) continue;
         if (!layout(bl.nodes, bl.root, blas_base[i], slot_of)) { if (err) *err = "internal: BLAS arena holds nodes outside the tree"; return -5; }
-        blas_root_at[i] = blas_base[i];
         for (size_t n = 0; n < bl.nodes.size(); ++n)
         {
             DNode& d = f.nodes[slot_of[n]];
@@ -824,7 +872,7 @@ int HostScene::flatten(std::string* err)
 
     // leaf-order position of every load-order primitive, per model
     std::vector<std::vector<uint32_t>> where(blas.size());
-    for (size_t i = 0; i < blas.size(); ++i)
+    for (const uint32_t i : lights.models)
     {
         where[i].assign(blas[i].tris.size(), 0);
         for (size_t k = 0; k < blas[i].prim_ids.size(); ++k) where[i][blas[i].prim_ids[k]] = f.tri_base[i] + (uint32_t)k;
@@ -846,6 +894,8 @@ int HostScene::flatten(std::string* err)
     const uint32_t tlas_depth = std::max(world.depth, lights.depth);
     f.stack_entries = std::max(tlas_depth, (tlas_depth > 0 ? tlas_depth - 1 : 0) + max_blas_depth);
     flat = std::move(f);
+    flat_valid = true;
+    flat_epoch = layout_epoch;
     return 0;
 }
 

@@ -102,12 +102,21 @@ public:
     HostCamera camera;
     FlatScene flat;
     bool built = false;
+    // Incremental builds (pt_set_instances): BLASes live in object space, so one is built once per model and kept; layout_epoch counts the
+    // edits that move offsets in the flattened scene (a model or material added, an instance count changed) — an upload that finds the
+    // epoch it last saw can patch the TLAS nodes and instance records in place.
+    uint64_t layout_epoch = 0;
+    uint64_t blas_builds = 0, tlas_builds = 0;
+    bool flat_valid = false;    // `flat` is a finished flatten of layout_epoch flat_epoch: its BLAS nodes and per-triangle tables can be kept
+    uint64_t flat_epoch = 0;
 
     int add_material(int kind, const float colour[3], float roughness, float ior, bool has_volume, const float vol_abs[3], float k, float c,
                      float g);
     int add_model(const float* positions, const float* normals, uint32_t n_tris, int material, const float* affines, uint32_t n_inst);
     // load_obj (blas.rs:44-131) + add_model; returns the model index, -1 bad argument, -4 non-rigid, -6 unreadable file, -7 parse error
     int add_model_obj(const char* path, int material, const float* affines, uint32_t n_inst, std::string* err);
+    // replaces the instance matrices of a model (checked as add_model checks them); -1 bad argument, -4 non-rigid: nothing changed
+    int set_instances(int model, const float* affines, uint32_t n_inst);
     int build(std::string* err);
     void set_camera(const float eye[3], const float target[3], float fov_deg, float aspect);
     void create_ray(float s, float t, float o[3], float d[3]) const;
