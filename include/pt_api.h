@@ -133,14 +133,61 @@ int pt_set_instances(pt_ctx* ctx, int model, const float* affine3x4_rowmajor, ui
 typedef struct pt_scene_info
 {
     uint64_t blas_builds;      /* BLASes built since pt_create */
-    uint64_t tlas_builds;      /* pt_build calls that rebuilt the TLASes */
+    uint64_t tlas_builds;      /* pt_build calls that rebuilt the TLASes: those after an edit of a model, a material or an instance matrix.
+                                  A pt_build with nothing edited since the last one, or with texture / UV edits only, rebuilds none */
     uint64_t uploads_full;     /* scene uploads that (re)allocated and copied everything */
     uint64_t uploads_patched;  /* scene uploads that patched TLAS nodes and instance records in place (also the re-upload after a
                                   pt_set_config that changed stack_lds_levels or PT_FLAG_NO_LDS_SCENE: the layout is unchanged) */
     uint64_t last_upload_bytes;
-    uint64_t reserved[3];
+    uint64_t scene_bytes;      /* bytes of every table of the flattened scene a full upload copies (0: not built); textures and UVs count
+                                  only when some material references a texture */
+    uint64_t reserved[2];
 } pt_scene_info;
 int pt_get_scene_info(pt_ctx* ctx, pt_scene_info* out);
+
+/* ---- textured surface colour ------------------------------------------------------------------------------------ */
+/* The reference has one colour per material; this is the library's own addition, defined here and checked bit for bit.
+ *
+ * A TEXTURE is w x h linear-RGB texels (w*h*3 floats, row-major); gamma decoding is the caller's, as for pt_set_environment.  A material of any
+ * kind except PT_EMISSIVE may reference one texture.  A model may carry UVs: n_tris * 3 * 2 floats in load order, beside its positions and
+ * normals; a model without UVs has (0, 0) at every vertex.
+ *
+ * The SURFACE COLOUR at a hit is defined from the hit's instance, the triangle `prim` in the model's load order and the barycentrics u, v of
+ * the hit record, in binary32 with every operation rounded once and no contraction, in this order:
+ *     a, b, c = the triangle's three UVs (load-order vertices 0, 1, 2)
+ *     s = (a.s + u * (b.s - a.s)) + v * (c.s - a.s)        t likewise
+ *     s = s - floorf(s);  t = t - floorf(t)                -- repeat addressing
+ *     texel  = get_pixel_bilinear(texture, s, t)           -- image_helper.rs:61-88 exactly as the environment lookup evaluates it:
+ *                                                             x = (float)w * s, x0 = x `as u32` (saturating), xf = x - trunc(x), columns x0 % w and
+ *                                                             (x0 + 1) % w, rows likewise, and the four products (1-xf)(1-yf) c00, (1-xf) yf c01,
+ *                                                             xf (1-yf) c10, xf yf c11 summed left to right
+ *     colour = material.colour * texel                     -- per component
+ * An untextured material's surface colour is material.colour, with no arithmetic.  So a triangle whose three UVs are equal has that UV
+ * everywhere, and at s = i/w, t = j/h (w, h powers of two) the lookup returns texel (i, j) bit for bit.
+ * The surface colour replaces the material's colour at the hit being shaded everywhere the shading pass uses it: get_bsdf_pdf of every surface
+ * class, both direct-light estimates and the continuation's throughput.  Nothing else changes: RNG draws, ray tallies, shade classes, the
+ * light sampler, media and the first-hit outputs are what they are without textures.
+ *
+ * The three setters make the scene un-built, as pt_add_model does, and the next render uploads the scene in full; the next pt_build rebuilds
+ * no BLAS and no TLAS for them (pt_scene_info).  A scene none of whose materials references a texture flattens, uploads and renders exactly
+ * as it does without textures and UVs, with the same kernels; one with a textured material runs the TEX variants of the surface shading
+ * passes and queues all its shadow rays.  Errors, all before any device call: PT_ERR_ARG for w or h of 0, a NULL pointer, a texel that is
+ * negative or not finite, a UV that is not finite, a bad index, n_tris different from the model's, or an emissive material; PT_ERR_LIMIT
+ * for a texture side above 16384 texels or more than 2^28 texels in all textures together (texels are addressed by 32-bit offsets into one
+ * 16-byte-per-texel buffer).  A refused call changes nothing.
+ * Out of scope: mip maps and filter footprints, nearest filtering, normal / roughness / emission maps, changing texel data after upload,
+ * PNG decoding, and demodulating the denoiser's input by the albedo guide (the obvious follow-up). */
+int pt_add_texture(pt_ctx* ctx, uint32_t w, uint32_t h, const float* rgb_linear);        /* returns the texture index */
+int pt_set_material_texture(pt_ctx* ctx, int material, int texture);                     /* texture -1 clears */
+int pt_set_model_uvs(pt_ctx* ctx, int model, const float* uv, uint32_t n_tris);          /* NULL, 0 clears */
+/* as pt_model_vertices: cap_tris = 0 queries; *n_tris = 0 for a model without UVs.  pt_add_model_obj keeps `vt` (two numbers per line, a
+ * missing second is 0; the middle face reference by the index rules of the other two; an empty, 0, unparsable or out-of-range one gives
+ * (0, 0)); an OBJ without `vt` lines gives a model without UVs */
+int pt_model_uvs(pt_ctx* ctx, int model, float* uv, uint32_t cap_tris, uint32_t* n_tris);
+/* unit hook: the surface colour of n hits of a BUILT scene; instance = world-TLAS leaf in allocation order (pt_read_guide_instances).
+ * on_device 0 evaluates on the host and touches no GPU; 1 runs a kernel over the same function.  PT_ERR_STATE: not built */
+int pt_surface_colour(pt_ctx* ctx, int on_device, uint32_t n, const uint32_t* instance, const uint32_t* prim, const float* u, const float* v,
+                      float* rgb);
 
 /* ---- Camera::new / create_ray  src/camera.rs:17-31, 94-105 ---------------------------------------------------- */
 int pt_set_camera(pt_ctx* ctx, const float eye[3], const float target[3], float fov_y_deg, float aspect);
@@ -321,6 +368,9 @@ int pt_read_guides(pt_ctx* ctx, float* position_xyzt, float* normal_xyz, uint32_
 /* the fourth guide pt_render_guides keeps: the world-TLAS leaf of the hit in allocation order — the index pt_tlas_instances(ctx, 0, ..) and
  * pt_instance_materials use — 0xffffffff for a miss; local_rows * width words.  PT_ERR_STATE without guides. */
 int pt_read_guide_instances(pt_ctx* ctx, uint32_t* instance);
+/* the fifth guide: ALBEDO, local_rows * width rgb f32 — the surface colour at the first hit (pt_add_texture), an emissive hit's emitted colour,
+ * (0, 0, 0) for a miss.  pt_denoise does not use it yet: demodulating its input by the albedo is the follow-up.  PT_ERR_STATE without guides. */
+int pt_read_guide_albedo(pt_ctx* ctx, float* rgb);
 /* The filter, in f32 with every operation correctly rounded (no contraction) and in the order written.  exp is pt_math.h's exp_det.
  *   Pixel p is VALID when acc.w != 0; an invalid pixel is never a neighbour and its output is (0,0,0,0).  Every valid output is (c, 1).
  *   c_p = (acc.r / acc.w, acc.g / acc.w, acc.b / acc.w);  l(c) = (0.2126f * c.r + 0.7152f * c.g) + 0.0722f * c.b (of the current colour).
@@ -343,7 +393,7 @@ int pt_read_guide_instances(pt_ctx* ctx, uint32_t* instance);
  *       e = 1 for p; else a_l = |l_p - l_q| * inv, e = exp(-a_l) for two misses, wn * exp(-(a_x + a_l)) for two hits;
  *       w = (h[dx] * h[dy]) * e, h = (1, 4, 6, 4, 1) / 16;  sw += w; sc += w * c_q (per channel); sv += (w * w) * var_q;
  *     c' = sc / sw (per channel); var' = sv / (sw * sw).
- *   The result is (c', 1) of the last level.  Albedo is constant per model, so there is no demodulation.
+ *   The result is (c', 1) of the last level.  There is no demodulation (albedo was constant per model until textures; pt_read_guide_albedo).
  * pt_denoise filters the context's accumulation with its guides (and its moments where valid) and never changes the accumulation, id history,
  * position or moments; rgba (NULL: the result stays on the device) receives local_rows * width rgba f32.  PT_ERR_ARG: p NULL, iterations > 8,
  * a sigma that is negative, NaN or infinite, a sigma_normal that is not a power of two from 1 to 256 (checked before any device call).

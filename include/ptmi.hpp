@@ -17,9 +17,11 @@
 //   (cam.matrix * cam.inv_projection).inverse()  main.rs:128 ptmi::Renderer::inv_projection
 //   state.render()                        state.rs:629       ptmi::Renderer::present
 //   ImageHelper::write_image              image_helper.rs:37 ptmi::Renderer::write_image
+// The library's own additions have no line of the reference: ptmi::Texture with Material::Textured and Model::WithUVs (pt_add_texture).
 #pragma once
 #include <array>
 #include <cstdint>
+#include <memory>
 #include <optional>
 #include <stdexcept>
 #include <string>
@@ -57,12 +59,23 @@ struct Volume
     static Volume New(Vec3A absorption, float k, float c, float g) { return {absorption, k, c, g}; }
 };
 
+// w x h linear-RGB texels, row-major (pt_add_texture).  Copies share the texels, and two textures are the same texture when they share
+// them: materials that were given the same Texture reference one texture of the scene.
+struct Texture
+{
+    uint32_t w = 0, h = 0;
+    std::shared_ptr<const std::vector<float>> rgb; // w * h * 3
+    static Texture New(uint32_t w, uint32_t h, std::vector<float> rgb_linear) { return {w, h, std::make_shared<const std::vector<float>>(std::move(rgb_linear))}; }
+};
+
 struct Material
 {
     pt_material_desc d{};
+    std::optional<Texture> texture; // surface colour = colour * bilinear texel at the hit's UV; any kind but Emissive
+    Material Textured(const Texture& t) const { Material m = *this; m.texture = t; return m; }
     bool operator==(const Material& o) const
     {
-        return d.kind == o.d.kind && d.colour[0] == o.d.colour[0] && d.colour[1] == o.d.colour[1] && d.colour[2] == o.d.colour[2] &&
+        return (texture ? texture->rgb : nullptr) == (o.texture ? o.texture->rgb : nullptr) && d.kind == o.d.kind && d.colour[0] == o.d.colour[0] && d.colour[1] == o.d.colour[1] && d.colour[2] == o.d.colour[2] &&
                d.roughness == o.d.roughness && d.ior == o.d.ior && d.has_volume == o.d.has_volume &&
                (!d.has_volume || (d.vol_absorption[0] == o.d.vol_absorption[0] && d.vol_absorption[1] == o.d.vol_absorption[1] &&
                                   d.vol_absorption[2] == o.d.vol_absorption[2] && d.vol_k == o.d.vol_k && d.vol_c == o.d.vol_c && d.vol_g == o.d.vol_g));
@@ -107,11 +120,13 @@ struct Model
     std::vector<float> positions, normals; // ... or a triangle soup, 9 floats per triangle each
     Material material;
     std::vector<Affine3A> matrices;
-    static Model New(std::string file_path, Material material, std::vector<Affine3A> matrices) { return {std::move(file_path), {}, {}, material, std::move(matrices)}; }
+    std::vector<float> uvs;               // 6 floats per triangle (three UVs, load order), or empty: (0, 0) everywhere, or the OBJ's `vt`
+    static Model New(std::string file_path, Material material, std::vector<Affine3A> matrices) { return {std::move(file_path), {}, {}, material, std::move(matrices), {}}; }
     static Model FromTriangles(std::vector<float> positions, std::vector<float> normals, Material material, std::vector<Affine3A> matrices)
     {
-        return {"", std::move(positions), std::move(normals), material, std::move(matrices)};
+        return {"", std::move(positions), std::move(normals), material, std::move(matrices), {}};
     }
+    Model WithUVs(std::vector<float> uv) const { Model m = *this; m.uvs = std::move(uv); return m; }
 };
 
 struct Scene
@@ -146,15 +161,35 @@ inline void upload(pt_ctx* ctx_, const Scene& scene)
 {
     auto check = [&](int r) { if (r < 0) throw Error(r, pt_last_error(ctx_)); return r; };
         std::vector<Material> mats; // distinct materials in first-use order
+        std::vector<std::shared_ptr<const std::vector<float>>> texs; // distinct textures in first-use order
         for (const Model& m : scene.models)
         {
             size_t idx = 0;
             while (idx < mats.size() && !(mats[idx] == m.material)) ++idx;
-            if (idx == mats.size()) { mats.push_back(m.material); check(pt_add_material(ctx_, &m.material.d)); }
+            if (idx == mats.size())
+            {
+                mats.push_back(m.material);
+                check(pt_add_material(ctx_, &m.material.d));
+                if (m.material.texture)
+                {
+                    const Texture& t = *m.material.texture;
+                    size_t ti = 0;
+                    while (ti < texs.size() && texs[ti] != t.rgb) ++ti;
+                    if (ti == texs.size())
+                    {
+                        if (!t.rgb || t.rgb->size() != (size_t)t.w * t.h * 3) throw Error(PT_ERR_ARG, "Texture: not w * h * 3 floats");
+                        texs.push_back(t.rgb);
+                        check(pt_add_texture(ctx_, t.w, t.h, t.rgb->data()));
+                    }
+                    check(pt_set_material_texture(ctx_, (int)idx, (int)ti));
+                }
+            }
             const float* mat = m.matrices.empty() ? nullptr : m.matrices[0].m.data();
             const uint32_t n_inst = (uint32_t)m.matrices.size();
-            if (!m.path.empty()) check(pt_add_model_obj(ctx_, m.path.c_str(), (int)idx, mat, n_inst));
-            else check(pt_add_model(ctx_, m.positions.data(), m.normals.data(), (uint32_t)(m.positions.size() / 9), (int)idx, mat, n_inst));
+            int model;
+            if (!m.path.empty()) model = check(pt_add_model_obj(ctx_, m.path.c_str(), (int)idx, mat, n_inst));
+            else model = check(pt_add_model(ctx_, m.positions.data(), m.normals.data(), (uint32_t)(m.positions.size() / 9), (int)idx, mat, n_inst));
+            if (!m.uvs.empty()) check(pt_set_model_uvs(ctx_, model, m.uvs.data(), (uint32_t)(m.uvs.size() / 6)));
         }
         check(pt_build(ctx_));
 }
@@ -219,6 +254,23 @@ public:
         check(pt_build(ctx_));
     }
     pt_scene_info scene_info() const { pt_scene_info s{}; check(pt_get_scene_info(ctx_, &s)); return s; }
+    // the triangle soup of model `model` as loaded (9 floats per triangle): what UVs for an OBJ model are computed from
+    std::vector<float> model_positions(int model) const
+    {
+        uint32_t n = 0;
+        check(pt_model_vertices(ctx_, model, nullptr, nullptr, 0, &n));
+        std::vector<float> p((size_t)n * 9), nr((size_t)n * 9);
+        check(pt_model_vertices(ctx_, model, p.data(), nr.data(), n, &n));
+        return p;
+    }
+    // replaces (empty: clears) the UVs of a model, 6 floats per triangle, and rebuilds: no BLAS and no TLAS is built again
+    void set_model_uvs(int model, const std::vector<float>& uvs)
+    {
+        check(pt_set_model_uvs(ctx_, model, uvs.empty() ? nullptr : uvs.data(), (uint32_t)(uvs.size() / 6)));
+        check(pt_build(ctx_));
+    }
+    // the fifth guide of render_guides: surface colour at the first hit, W*H*3
+    std::vector<float> read_guide_albedo() const { std::vector<float> v((size_t)width_ * height_ * 3); check(pt_read_guide_albedo(ctx_, v.data())); return v; }
     // n_samples per pixel accumulated without the temporal pass (what the loop converges to for a camera at rest)
     void render(uint32_t first_sample, uint32_t n_samples) { check(pt_render_device(ctx_, first_sample, n_samples)); check(pt_synchronize(ctx_)); }
     void reset_accumulation() { check(pt_reset_accumulation(ctx_)); }

@@ -40,6 +40,7 @@ EXPORTS = [
     "pt_render_guides", "pt_read_guides", "pt_denoise", "pt_write_denoised_image", "pt_post_denoise",
     "pt_integrate_rays", "pt_integrate_rays_device", "pt_bake_probes", "pt_probe_ray",
     "pt_set_instances", "pt_get_scene_info", "pt_read_guide_instances", "pt_frame_moving", "pt_post_motion",
+    "pt_add_texture", "pt_set_material_texture", "pt_set_model_uvs", "pt_model_uvs", "pt_surface_colour", "pt_read_guide_albedo",
 ]
 
 
@@ -97,7 +98,7 @@ class ProbeParams(C.Structure):
 class SceneInfo(C.Structure):
     """pt_scene_info: which build and upload paths ran (include/pt_api.h)"""
     _fields_ = [("blas_builds", C.c_uint64), ("tlas_builds", C.c_uint64), ("uploads_full", C.c_uint64), ("uploads_patched", C.c_uint64),
-                ("last_upload_bytes", C.c_uint64), ("reserved", C.c_uint64 * 3)]
+                ("last_upload_bytes", C.c_uint64), ("scene_bytes", C.c_uint64), ("reserved", C.c_uint64 * 2)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
@@ -219,6 +220,12 @@ def lib():
         L.pt_read_guide_instances.argtypes = [vp, vp]
         L.pt_frame_moving.argtypes = [vp, u32, vp, vp, vp, vp]
         L.pt_post_motion.argtypes = [vp, u32, u32, vp, vp, u32, vp, vp, vp, vp, vp]
+        L.pt_add_texture.argtypes = [vp, u32, u32, vp]
+        L.pt_set_material_texture.argtypes = [vp, C.c_int, C.c_int]
+        L.pt_set_model_uvs.argtypes = [vp, C.c_int, vp, u32]
+        L.pt_model_uvs.argtypes = [vp, C.c_int, vp, u32, C.POINTER(u32)]
+        L.pt_surface_colour.argtypes = [vp, C.c_int, u32, vp, vp, vp, vp, vp]
+        L.pt_read_guide_albedo.argtypes = [vp, vp]
         _lib = L
     return _lib
 
@@ -245,6 +252,7 @@ class Renderer:
             raise PtError(-1, "pt_create failed (bad configuration)")
         self.desc = scene
         self._materials = []
+        self._textures = []
         for mod in scene.models:
             self.add_model(mod)
         self.rebuild()
@@ -262,17 +270,73 @@ class Renderer:
                 d.has_volume = 1
                 d.vol_absorption[:] = m.volume.absorption
                 d.vol_k, d.vol_c, d.vol_g = m.volume.k, m.volume.c, m.volume.g
-            self._chk(self.L.pt_add_material(self.ctx, C.byref(d)), allow_positive=True)
+            mi = self._chk(self.L.pt_add_material(self.ctx, C.byref(d)), allow_positive=True)
             self._materials.append(m)
+            if getattr(m, "texture", None) is not None:
+                self.set_material_texture(mi, self._texture_index(m.texture))
         return self._materials.index(m)
+
+    def _texture_index(self, t) -> int:
+        """pt_add_texture once per distinct Texture object"""
+        for i, have in enumerate(self._textures):
+            if have is t:
+                return i
+        self.add_texture(t.data)
+        self._textures[-1] = t
+        return len(self._textures) - 1
 
     def add_model(self, mod) -> int:
         """Model::new + push onto the scene's model list; call rebuild() (Scene::new) before the next render"""
         mi = self._material_index(mod.material)
         if getattr(mod, "obj_path", None):
-            return self._chk(self.L.pt_add_model_obj(self.ctx, mod.obj_path.encode(), mi, _p(mod.matrices), mod.matrices.shape[0]), allow_positive=True)
-        return self._chk(self.L.pt_add_model(self.ctx, _p(mod.positions), _p(mod.normals), mod.positions.shape[0], mi, _p(mod.matrices),
-                                             mod.matrices.shape[0]), allow_positive=True)
+            r = self._chk(self.L.pt_add_model_obj(self.ctx, mod.obj_path.encode(), mi, _p(mod.matrices), mod.matrices.shape[0]), allow_positive=True)
+        else:
+            r = self._chk(self.L.pt_add_model(self.ctx, _p(mod.positions), _p(mod.normals), mod.positions.shape[0], mi, _p(mod.matrices),
+                                              mod.matrices.shape[0]), allow_positive=True)
+        if getattr(mod, "uvs", None) is not None:
+            self.set_model_uvs(r, mod.uvs)
+        return r
+
+    # ---- textured surface colour (include/pt_api.h); the three setters un-build the scene: rebuild() before the next render
+    def add_texture(self, rgb) -> int:
+        """[h, w, 3] linear RGB, finite and non-negative; returns the texture index"""
+        a = np.ascontiguousarray(rgb, dtype=np.float32)
+        assert a.ndim == 3 and a.shape[2] == 3
+        r = self._chk(self.L.pt_add_texture(self.ctx, a.shape[1], a.shape[0], _p(a)), allow_positive=True)
+        self._textures.append(None)
+        return r
+
+    def set_material_texture(self, material: int, texture: int):
+        """texture -1 clears"""
+        self._chk(self.L.pt_set_material_texture(self.ctx, material, texture))
+
+    def set_model_uvs(self, model: int, uvs):
+        """[n_tris, 3, 2] in load order; None clears"""
+        if uvs is None:
+            self._chk(self.L.pt_set_model_uvs(self.ctx, model, None, 0))
+            return
+        a = np.ascontiguousarray(uvs, dtype=np.float32).reshape(-1, 3, 2)
+        self._chk(self.L.pt_set_model_uvs(self.ctx, model, _p(a), a.shape[0]))
+
+    def model_uvs(self, model):
+        """[n_tris, 3, 2], or None for a model without UVs"""
+        n = C.c_uint32()
+        self._chk(self.L.pt_model_uvs(self.ctx, model, None, 0, C.byref(n)))
+        if n.value == 0:
+            return None
+        uv = np.zeros((n.value, 3, 2), np.float32)
+        self._chk(self.L.pt_model_uvs(self.ctx, model, _p(uv), n.value, C.byref(n)))
+        return uv
+
+    def surface_colour(self, instance, prim, u, v, on_device=False):
+        """unit hook: the surface colour [n, 3] of hits (world-TLAS instance, load-order primitive, barycentrics) of the built scene;
+        on the host (no GPU) unless on_device"""
+        i = np.ascontiguousarray(instance, dtype=np.uint32); p = np.ascontiguousarray(prim, dtype=np.uint32)
+        uu = np.ascontiguousarray(u, dtype=np.float32); vv = np.ascontiguousarray(v, dtype=np.float32)
+        assert i.shape == p.shape == uu.shape == vv.shape and i.ndim == 1
+        out = np.zeros((i.shape[0], 3), np.float32)
+        self._chk(self.L.pt_surface_colour(self.ctx, int(bool(on_device)), i.shape[0], _p(i), _p(p), _p(uu), _p(vv), _p(out)))
+        return out
 
     def rebuild(self):
         self._chk(self.L.pt_build(self.ctx))
@@ -303,6 +367,7 @@ class Renderer:
         self.ctx = C.c_void_p(ctx)
         self.desc = None
         self._materials = []
+        self._textures = []
         self._borrowed = True
         return self
 
@@ -583,6 +648,12 @@ class Renderer:
         inst = np.zeros((len(self.local_rows()), self.cfg.width), np.uint32)
         self._chk(self.L.pt_read_guide_instances(self.ctx, _p(inst)))
         return inst
+
+    def read_guide_albedo(self):
+        """the albedo guide of the last render_guides: surface colour at the first hit (emitted colour of a light, 0 for a miss), rows x width x 3"""
+        al = np.zeros((len(self.local_rows()), self.cfg.width, 3), np.float32)
+        self._chk(self.L.pt_read_guide_albedo(self.ctx, _p(al)))
+        return al
 
     def denoise(self, iterations=0, sigma_luminance=0.0, sigma_normal=0, sigma_plane=0.0, download=True):
         """filter the accumulation with the guides (and the moments where the context keeps valid ones); returns rgba (c, 1) per local pixel,

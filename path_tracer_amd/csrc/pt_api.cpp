@@ -134,6 +134,9 @@ struct pt_ctx
     DevBuf d_spill;
     size_t spill_region_words = 0; // 8-byte words per traversal launch's spill area (d_spill holds two per pipeline)
     DevBuf d_blob, d_tri_shade, d_tri_pos, d_tri_orig, d_materials, d_lights, d_env;
+    DevBuf d_tri_uv, d_tex_table, d_tex_texels; // textured scenes only (FlatScene::has_textures)
+    TexView tex{};                 // over them; all null for an untextured scene
+    bool textured = false;
     std::vector<f4> h_env;
     uint32_t env_w = 0, env_h = 0;
     bool env_uploaded = false;
@@ -168,7 +171,7 @@ struct pt_ctx
 
     // denoiser (pt_render_guides / pt_denoise): first-hit guides of one sample of every local pixel and what they belong to, the hook queue
     // they are traced through, the filter's scratch images and its last result.  Nothing is allocated until the first call.
-    DevBuf d_gpos, d_gnrm, d_gmodel, d_ginst, d_gray_a, d_gray_b, d_ghits, d_ghead;
+    DevBuf d_gpos, d_gnrm, d_gmodel, d_ginst, d_galbedo, d_gray_a, d_gray_b, d_ghits, d_ghead;
     bool guides_valid = false;
     uint64_t guides_scene_version = 0, guides_config_version = 0;
     uint32_t guides_sample = 0;
@@ -430,6 +433,15 @@ int upload_scene(pt_ctx* c)
     if ((r = up(c->d_tri_orig, f.tri_orig.data(), f.tri_orig.size() * 4))) return r;
     if ((r = up(c->d_materials, f.materials.data(), f.materials.size() * sizeof(DMaterial)))) return r;
     if ((r = up(c->d_lights, f.lights.data(), f.lights.size() * sizeof(DLight)))) return r;
+    c->textured = f.has_textures;
+    c->tex = TexView{};
+    if (f.has_textures)
+    {
+        if ((r = up(c->d_tri_uv, f.tri_uv.data(), f.tri_uv.size() * sizeof(DTriUV)))) return r;
+        if ((r = up(c->d_tex_table, f.tex_table.data(), f.tex_table.size() * sizeof(DTexture)))) return r;
+        if ((r = up(c->d_tex_texels, f.tex_texels.data(), f.tex_texels.size() * sizeof(f4)))) return r;
+        c->tex = TexView{(const f4*)c->d_tex_texels.p, (const DTexture*)c->d_tex_table.p, (const DTriUV*)c->d_tri_uv.p};
+    }
     if ((r = derive_scene_view(c, f, blob_bytes))) return r;
     c->scene_uploaded = true;
     c->resident_valid = true;
@@ -451,6 +463,7 @@ TraceLaunch trace_launch(pt_ctx* c, int pipe = 0, bool side_stream = false)
     tl.grid_blocks = c->trace_blocks;
     tl.n_cus = (uint32_t)c->n_cus;
     tl.block_threads = c->block_threads;
+    tl.tex = c->textured ? &c->tex : nullptr;
     return tl;
 }
 
@@ -1564,7 +1577,106 @@ int pt_get_scene_info(pt_ctx* c, pt_scene_info* out)
     out->uploads_full = c->uploads_full;
     out->uploads_patched = c->uploads_patched;
     out->last_upload_bytes = c->last_upload_bytes;
+    out->scene_bytes = c->scene.built ? c->scene.flat.table_bytes() : 0;
     return PT_OK;
+}
+
+/* ---- textures (the definition is include/pt_api.h's) */
+int pt_add_texture(pt_ctx* c, uint32_t w, uint32_t h, const float* rgb_linear)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    int r;
+    try { r = c->scene.add_texture(w, h, rgb_linear); }
+    catch (const std::exception& e) { return fail(c, PT_ERR_LIMIT, std::string("texture does not fit in host memory: ") + e.what()); }
+    if (r == -5) return fail(c, PT_ERR_LIMIT, "a texture side is at most 16384 texels and all textures together hold at most 2^28");
+    if (r < 0) return fail(c, PT_ERR_ARG, "bad texture: a zero size, a NULL pointer, or a texel that is negative or not finite");
+    c->scene_uploaded = false;
+    return r;
+}
+
+int pt_set_material_texture(pt_ctx* c, int material, int texture)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (c->scene.set_material_texture(material, texture) < 0) return fail(c, PT_ERR_ARG, "bad material or texture index, or an emissive material");
+    c->scene_uploaded = false;
+    return PT_OK;
+}
+
+int pt_set_model_uvs(pt_ctx* c, int model, const float* uv, uint32_t n_tris)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    int r;
+    try { r = c->scene.set_model_uvs(model, uv, n_tris); }
+    catch (const std::exception& e) { return fail(c, PT_ERR_LIMIT, std::string("UVs do not fit in host memory: ") + e.what()); }
+    if (r < 0) return fail(c, PT_ERR_ARG, "bad model index, a triangle count that is not the model's, or a UV that is not finite");
+    c->scene_uploaded = false;
+    return PT_OK;
+}
+
+int pt_model_uvs(pt_ctx* c, int model, float* uv, uint32_t cap_tris, uint32_t* n_tris)
+{
+    if (!c || !n_tris) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (model < 0 || model >= (int)c->scene.models.size()) return fail(c, PT_ERR_ARG, "model index");
+    const HostModel& m = c->scene.models[model];
+    *n_tris = m.uvs.empty() ? 0u : m.n_tris;
+    if (cap_tris == 0 || m.uvs.empty()) return PT_OK;
+    if (cap_tris < m.n_tris || !uv) return fail(c, PT_ERR_ARG, "capacity");
+    std::memcpy(uv, m.uvs.data(), (size_t)m.n_tris * 24);
+    return PT_OK;
+}
+
+int pt_surface_colour(pt_ctx* c, int on_device, uint32_t n, const uint32_t* instance, const uint32_t* prim, const float* u, const float* v, float* rgb)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->scene.built) return fail(c, PT_ERR_STATE, "pt_build has not been called");
+    if (n == 0) return PT_OK;
+    if (!instance || !prim || !u || !v || !rgb) return fail(c, PT_ERR_ARG, "null pointer");
+    const FlatScene& f = c->scene.flat;
+    const HostTlas& world = c->scene.world;
+    // leaf-order triangle of every query: tri_orig inverted for the models asked about
+    std::vector<std::vector<uint32_t>> where(c->scene.blas.size());
+    std::vector<uint32_t> tri(n);
+    for (uint32_t i = 0; i < n; ++i)
+    {
+        if (instance[i] >= world.instances.size()) return fail(c, PT_ERR_ARG, "instance index");
+        const uint32_t mi = world.instances[instance[i]].model;
+        const HostBlas& bl = c->scene.blas[mi];
+        if (prim[i] >= bl.tris.size()) return fail(c, PT_ERR_ARG, "primitive index");
+        if (where[mi].empty())
+        {
+            where[mi].resize(bl.prim_ids.size());
+            for (size_t k = 0; k < bl.prim_ids.size(); ++k) where[mi][bl.prim_ids[k]] = f.tri_base[mi] + (uint32_t)k;
+        }
+        tri[i] = where[mi][prim[i]];
+    }
+    if (!on_device)
+    {
+        const TexView tv = f.tex_view();
+        for (uint32_t i = 0; i < n; ++i)
+        {
+            const DMaterial& dm = f.materials[f.instances[instance[i]].material];
+            const f3 col = surface_colour(tv, dm.texture, f3{dm.colour[0], dm.colour[1], dm.colour[2]}, tri[i], u[i], v[i]);
+            rgb[3 * (size_t)i] = col.x; rgb[3 * (size_t)i + 1] = col.y; rgb[3 * (size_t)i + 2] = col.z;
+        }
+        return PT_OK;
+    }
+    int r;
+    if ((r = upload_scene(c))) return r;
+    Staging st(c);
+    const uint32_t* d_inst = (const uint32_t*)st.in(instance, (size_t)n * 4);
+    const uint32_t* d_tri = (const uint32_t*)st.in(tri.data(), (size_t)n * 4);
+    const float* d_u = (const float*)st.in(u, (size_t)n * 4);
+    const float* d_v = (const float*)st.in(v, (size_t)n * 4);
+    float* d_rgb = (float*)st.out((size_t)n * 12);
+    if (st.err) return st.err;
+    launch_surface_colour(c->stream, c->sv, c->tex, n, d_inst, d_tri, d_u, d_v, d_rgb);
+    HIPCHK(c, hipGetLastError());
+    return st.download(rgb, d_rgb, (size_t)n * 12);
 }
 
 int pt_set_camera(pt_ctx* c, const float eye[3], const float target[3], float fov_y_deg, float aspect)
@@ -2147,6 +2259,7 @@ int render_guides_locked(pt_ctx* c, uint32_t sample)
     const size_t n = std::max<uint32_t>(px, 1);
     for (DevBuf* b : {&c->d_gpos, &c->d_gnrm, &c->d_gray_a, &c->d_gray_b, &c->d_ghits})
         if ((r = dev_alloc(c, *b, n * 16))) return r;
+    if ((r = dev_alloc(c, c->d_galbedo, n * 16))) return r;
     if ((r = dev_alloc(c, c->d_gmodel, n * 4)) || (r = dev_alloc(c, c->d_ginst, n * 4)) || (r = dev_alloc(c, c->d_ghead, ((size_t)32 + kHeadWordsPerQueue) * 4))) return r;
     c->guides_valid = false;
     if (px)
@@ -2176,6 +2289,7 @@ int render_guides_locked(pt_ctx* c, uint32_t sample)
         else launch_trace_rays_closest(c->stream, trace_launch(c), c->sv.world_root, q, px, head, (f4*)c->d_ghits.p);
         launch_guide_resolve(c->stream, c->sv, px, cam, lens, q, (const f4*)c->d_ghits.p, (f4*)c->d_gpos.p, (f4*)c->d_gnrm.p, (uint32_t*)c->d_gmodel.p,
                              (uint32_t*)c->d_ginst.p);
+        launch_guide_albedo(c->stream, c->sv, c->tex, px, (const f4*)c->d_ghits.p, (f4*)c->d_galbedo.p);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
@@ -2205,6 +2319,20 @@ int pt_read_guide_instances(pt_ctx* c, uint32_t* instance)
     if (!px || !instance) return PT_OK;
     HIPCHK(c, hipMemcpyAsync(instance, c->d_ginst.p, px * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PT_OK;
+}
+
+int pt_read_guide_albedo(pt_ctx* c, float* rgb)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->guides_valid) return fail(c, PT_ERR_STATE, "no guides: pt_render_guides first");
+    const size_t px = c->local_pixels;
+    if (!px || !rgb) return PT_OK;
+    std::vector<f4> al(px);
+    HIPCHK(c, hipMemcpyAsync(al.data(), c->d_galbedo.p, px * 16, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i < px; ++i) { rgb[3 * i] = al[i].x; rgb[3 * i + 1] = al[i].y; rgb[3 * i + 2] = al[i].z; }
     return PT_OK;
 }
 

@@ -16,6 +16,7 @@ struct TraceLaunch
     uint32_t grid_blocks;    // upper bound of the persistent grid (the launchers shrink it to what is resident at once)
     uint32_t n_cus;
     uint32_t block_threads;  // 64..256
+    const TexView* tex;      // the built scene has a textured material: its texture view (the surface passes are the TEX variants), else null
 };
 
 // dynamic LDS of a traversal workgroup: the staged BVH blob (LDS scenes) + the per-lane (node, t_enter) stacks
@@ -108,7 +109,8 @@ void launch_trace_shadow(hipStream_t s, const TraceLaunch& tl, const WavefrontBu
 void launch_trace_lchain(hipStream_t s, const TraceLaunch& tl, const WavefrontBuffers& wb, uint32_t b);
 // shading of bounce b for one queue class
 // (ray_keys: RayView::key of a ray batch, whose paths take their stream from it and start at RenderParams::ray_draws draws)
-// (tl: the scene's traversal launch description; with it the Lambert / GGX passes of an LDS-resident scene may trace their own shadow rays)
+// (tl: the scene's traversal launch description; with it the Lambert / GGX passes of an LDS-resident scene may trace their own shadow rays,
+//  and the passes of a textured scene (tl->tex) look the surface colour up)
 void launch_shade(hipStream_t s, uint32_t qclass, const SceneView& sv, const RenderParams& rp, const WavefrontBuffers& wb, uint32_t b,
                   uint32_t grid_blocks, const CameraView& cam, const LensView& lens, const EnvView& env, const TraceLaunch* tl = nullptr,
                   const uint2* list = nullptr, const uint2* ray_keys = nullptr);
@@ -159,6 +161,12 @@ void launch_guide_rays(hipStream_t s, const RenderParams& rp, const CameraView& 
 // their launch_trace_rays_closest hits -> position, normal, model guides
 void launch_guide_resolve(hipStream_t s, const SceneView& sv, uint32_t n, const CameraView& cam, const LensView& lens, RayQueue rq, const f4* hits,
                           f4* position, f4* normal, uint32_t* model, uint32_t* instance);
+// ... -> the albedo guide: the surface colour at the hit (an emissive hit: its emitted colour), (0, 0, 0) for a miss.  A launch of its own behind
+// the resolve, whose kernels and four guides stay what they were.  tex: the scene's texture view (all null for an untextured scene)
+void launch_guide_albedo(hipStream_t s, const SceneView& sv, const TexView& tex, uint32_t n, const f4* hits, f4* albedo);
+// unit hook (pt_surface_colour): rgb[i] <- surface colour of world instance[i], leaf-order triangle tri[i] at barycentrics u[i], v[i]
+void launch_surface_colour(hipStream_t s, const SceneView& sv, const TexView& tex, uint32_t n, const uint32_t* instance, const uint32_t* tri, const float* u,
+                           const float* v, float* rgb);
 
 // unit hooks
 // n_and_heads: word 0 = number of rays, words [32, 32 + kHeadWordsPerQueue) = zeroed claim cursors

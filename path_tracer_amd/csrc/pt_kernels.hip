@@ -1987,6 +1987,16 @@ __device__ __forceinline__ const ShadeKArgs& shade_args()
     asm volatile("" : "+s"(p));        // loads through p cannot move above this point
     return *(const ShadeKArgs*)p;
 }
+// TEX variants: the texture view rides behind the launch description in their argument only (as CameraLensView does for k_accumulate): the
+// other instantiations' arguments, and with them their code, are what they were
+struct ShadeKArgsTex : ShadeKArgs { TexView tex; };
+typedef const __attribute__((address_space(4))) ShadeKArgsTex* ShadeKArgsTexPtr;
+__device__ __forceinline__ const TexView& shade_args_tex()
+{
+    ShadeKArgsTexPtr p = (ShadeKArgsTexPtr)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return ((const ShadeKArgsTex*)p)->tex;
+}
 #define PT_SHADE_ARGS                                                                                                              \
     const ShadeKArgs& ka_ = shade_args();                                                                                          \
     [[maybe_unused]] const SceneView& sv = ka_.sv;                                                                                 \
@@ -1996,9 +2006,20 @@ __device__ __forceinline__ const ShadeKArgs& shade_args()
 // LENS (pt_set_lens; launched for bounce 0 only): the camera ray's origin comes with its record (ShadeQueue::c) and two draws are consumed
 // RAYS (pt_integrate_rays): the path's stream is the one its entry of the ray table names (path_pixel_rays) and bounce 0 (launched with LENS: the
 // ray's origin is its own) starts at RenderParams::ray_draws draws
-template <uint32_t QCLASS, bool VOLUMES, bool INLINE = false, bool IDENT = false, bool LIST = false, bool LENS = false, bool RAYS = false>
-__global__ void __launch_bounds__(PT_SHADE_THREADS, INLINE ? PT_SHADE_WAVES_INLINE : shade_waves(QCLASS, VOLUMES)) k_shade_surface(const ShadeKArgs kargs)
+// TEX (a built scene with a textured material; never with INLINE): the colour of the material at the hit is the surface colour (surface_colour,
+// pt_materials.h).  The lookup is a chain of dependent loads (instance -> material -> UVs and table -> four texels).  It sits where the
+// material is loaded, behind the NEE resolve: every TEX variant then has the registers, the scratch and the waves of its untextured twin.
+// PT_TEX_EARLY=1 starts it right behind the path record's loads instead, so that the two wait for memory together; the colour is then live
+// across the resolve and the specular / dielectric media variants drop from five waves to four and three others gain 12-40 bytes of
+// scratch (tools/resource_table.py; profiles/r12_textures.md), so that is not the build.
+#ifndef PT_TEX_EARLY
+#define PT_TEX_EARLY 0
+#endif
+template <uint32_t QCLASS, bool VOLUMES, bool INLINE = false, bool IDENT = false, bool LIST = false, bool LENS = false, bool RAYS = false, bool TEX = false>
+__global__ void __launch_bounds__(PT_SHADE_THREADS, INLINE ? PT_SHADE_WAVES_INLINE : shade_waves(QCLASS, VOLUMES))
+k_shade_surface(const std::conditional_t<TEX, ShadeKArgsTex, ShadeKArgs> kargs)
 {
+    static_assert(!(TEX && INLINE), "textured scenes queue their shadow rays");
     extern __shared__ uint4 smem_dyn[];
     // Only what the loop header needs is taken from the argument here; each section of an iteration re-reads the launch description from
     // the kernel-argument segment (PT_SHADE_ARGS: scalar loads that hit the constant cache) instead of keeping ~130 words of it in ~100
@@ -2055,15 +2076,23 @@ __global__ void __launch_bounds__(PT_SHADE_THREADS, INLINE ? PT_SHADE_WAVES_INLI
             f4 pw4{1.0f, 1.0f, 1.0f, asf(RAYS ? rp.ray_draws : LENS ? 2u : 1u)}; // bounce 0: path_weight = 1, accumulated = 0, the seed draw consumed (LENS: and the lens point's)
             acc = f3{0.0f, 0.0f, 0.0f};
             flags = 0u;
+            [[maybe_unused]] f3 surf{};
+            [[maybe_unused]] auto textured = [&]() -> f3 {
+                const uint32_t hid_ = asu(hit.w);
+                const DMaterial& dm = sv.materials[sv.instances[hid_ >> sv.prim_bits].material];
+                return surface_colour(shade_args_tex(), dm.texture, f3{dm.colour[0], dm.colour[1], dm.colour[2]}, hid_ & ((1u << sv.prim_bits) - 1u), hit.y, hit.z);
+            };
             if (bounce != 0u)
             {
                 const DPathRec& rec = io.st.rec[pid];
                 const f4 acc4 = rec.acc;
                 pw4 = rec.pw;
+                if (TEX && PT_TEX_EARLY) surf = textured();
                 acc = xyz(acc4);
                 flags = asu(acc4.w);
                 resolve_nee(sv, io, pid, rec, acc, flags);
             }
+            else if (TEX && PT_TEX_EARLY) surf = textured();
             pw = xyz(pw4);
 
             const f3 ro = xyz(ra), rd = xyz(rb);
@@ -2071,6 +2100,7 @@ __global__ void __launch_bounds__(PT_SHADE_THREADS, INLINE ? PT_SHADE_WAVES_INLI
             const uint32_t inst = hid >> sv.prim_bits, tri = hid & ((1u << sv.prim_bits) - 1u);
             const DInstance& in = sv.instances[inst];
             MatView mat = load_material(sv.materials, in.material);
+            if (TEX) mat.colour = PT_TEX_EARLY ? surf : textured();
             // the queue class fixes the material kind: let the compiler drop the other materials' code from this kernel
             if (QCLASS == Q_LAMBERT) mat.kind = (VOLUMES && mat.kind == MAT_EMISSIVE) ? (uint32_t)MAT_EMISSIVE : (uint32_t)MAT_LAMBERTIAN;
             else if (QCLASS == Q_SPECULAR) mat.kind = MAT_SPECULAR;
@@ -2848,6 +2878,32 @@ __global__ void __launch_bounds__(256) k_guide_resolve_lens(const SceneView sv, 
     guide_resolve_body<true>(sv, n, cam, rq, hits, position, normal, model, instance);
 }
 
+// the albedo guide of those hits and the unit hook of the surface colour: both over surface_colour (pt_materials.h), as the TEX shading passes are
+__device__ __forceinline__ f3 surface_colour_at(const SceneView& sv, const TexView& tex, uint32_t inst, uint32_t tri, float u, float v)
+{
+    const DMaterial& dm = sv.materials[sv.instances[inst].material];
+    return surface_colour(tex, dm.texture, f3{dm.colour[0], dm.colour[1], dm.colour[2]}, tri, u, v);
+}
+__global__ void __launch_bounds__(256) k_guide_albedo(const SceneView sv, const TexView tex, const uint32_t n, const f4* __restrict__ hits, f4* __restrict__ albedo)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const f4 hit = hits[i];
+    const uint32_t hid = asu(hit.w);
+    f3 c{0.0f, 0.0f, 0.0f};
+    if (hid != MISS_ID) c = surface_colour_at(sv, tex, hid >> sv.prim_bits, hid & ((1u << sv.prim_bits) - 1u), hit.y, hit.z);
+    albedo[i] = f4{c.x, c.y, c.z, 0.0f};
+}
+__global__ void __launch_bounds__(256) k_surface_colour(const SceneView sv, const TexView tex, const uint32_t n, const uint32_t* __restrict__ instance,
+                                                        const uint32_t* __restrict__ tri, const float* __restrict__ u, const float* __restrict__ v,
+                                                        float* __restrict__ rgb)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const f3 c = surface_colour_at(sv, tex, instance[i], tri[i], u[i], v[i]);
+    rgb[3u * (size_t)i] = c.x; rgb[3u * (size_t)i + 1u] = c.y; rgb[3u * (size_t)i + 2u] = c.z;
+}
+
 } // namespace
 
 // ================================================================================================ launchers
@@ -3040,18 +3096,20 @@ void launch_trace_lchain(hipStream_t s, const TraceLaunch& tl, const WavefrontBu
     out.occl = wb.st.occl;
     launch_closest_impl<CLOSEST_LIGHTS>(s, tl, tl.scene.lights_root, wb.rq_lchain[b & 1u], &row->n_lchain, wb.cap_slots, row_heads(wb, b, HEADS_LCHAIN), out);
 }
+// (A textured scene queues its shadow rays: the inline walk would need INLINE x TEX variants of the pass whose registers are the tightest.)
 // The Lambertian shading pass walks its own shadow rays when the scene's BVH and a workgroup's stacks take no more LDS than five workgroups per CU can share
 // (the pass keeps its five waves per SIMD), nothing spills from the stacks, the scene has no media (those kernels are short of registers as it is) and the
 // traversal workgroups have the shading pass's shape (the stack layout is per thread of a workgroup).
 bool shade_traces_shadow(const TraceLaunch& tl)
 {
-    return PT_INLINE_SHADOW != 0 && tl.lds_scene && tl.scene.stack_entries <= tl.scene.stack_lds && !tl.scene.has_volumes && tl.block_threads == PT_SHADE_THREADS &&
+    return PT_INLINE_SHADOW != 0 && !tl.tex && tl.lds_scene && tl.scene.stack_entries <= tl.scene.stack_lds && !tl.scene.has_volumes && tl.block_threads == PT_SHADE_THREADS &&
            trace_lds_bytes(tl) + 1024 <= 32 * 1024;
 }
 void launch_shade(hipStream_t s, uint32_t qclass, const SceneView& sv, const RenderParams& rp, const WavefrontBuffers& wb, uint32_t b,
                   uint32_t grid_blocks, const CameraView& cam, const LensView& lens, const EnvView& env, const TraceLaunch* tl, const uint2* list,
                   const uint2* ray_keys)
 {
+    const TexView* const tex = tl ? tl->tex : nullptr;
     if (ray_keys) list = nullptr; // (a ray batch has no pixels)
     const bool lens0 = b == 0u && (lens_set(lens) || ray_keys != nullptr); // only bounce 0 knows of the camera: its rays' origins and the draws they consumed
     ShadeIO io{};
@@ -3087,6 +3145,9 @@ void launch_shade(hipStream_t s, uint32_t qclass, const SceneView& sv, const Ren
     if (ray_keys && qclass != Q_TERMINAL) io.list = ray_keys;
     const ShadeKArgs ka{sv, rp, io, b, inl ? (const uint4*)tl->blob : nullptr, inl ? tl->scene.world_root : 0u};
     const size_t lds = inl ? trace_lds_bytes(*tl) : 0;
+    ShadeKArgsTex kat{};
+    static_cast<ShadeKArgs&>(kat) = ka;
+    if (tex) kat.tex = *tex;
     // (LIST: the same classes over an adaptive list's paths; lens0: LENS; ray_keys: RAYS)
 #define PT_SURF_L(LENS, Q, V, ...)                                                                                                      \
     do {                                                                                                                                 \
@@ -3099,6 +3160,32 @@ void launch_shade(hipStream_t s, uint32_t qclass, const SceneView& sv, const Ren
         if (lens0) PT_SURF_L(true, Q, V, __VA_ARGS__);                                                                                   \
         else PT_SURF_L(false, Q, V, __VA_ARGS__);                                                                                        \
     } while (0)
+    // the TEX variants of the same classes (a textured scene queues its shadow rays: shade_traces_shadow)
+#define PT_SURF_TEX_L(LENS, Q, V)                                                                                                       \
+    do {                                                                                                                                 \
+        if (ray_keys) hipLaunchKernelGGL((k_shade_surface<Q, V, false, false, false, LENS, true, true>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), 0, s, kat); \
+        else if (list) hipLaunchKernelGGL((k_shade_surface<Q, V, false, false, true, LENS, false, true>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), 0, s, kat); \
+        else hipLaunchKernelGGL((k_shade_surface<Q, V, false, false, false, LENS, false, true>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), 0, s, kat); \
+    } while (0)
+#define PT_SURF_TEX(Q)                                                                                                                  \
+    do {                                                                                                                                 \
+        if (lens0) { if (sv.has_volumes) PT_SURF_TEX_L(true, Q, true); else PT_SURF_TEX_L(true, Q, false); }                             \
+        else { if (sv.has_volumes) PT_SURF_TEX_L(false, Q, true); else PT_SURF_TEX_L(false, Q, false); }                                 \
+    } while (0)
+    if (tex && qclass != Q_TERMINAL)
+    {
+        switch (qclass)
+        {
+        case Q_LAMBERT: PT_SURF_TEX(Q_LAMBERT); break;
+        case Q_SPECULAR: PT_SURF_TEX(Q_SPECULAR); break;
+        case Q_DIELECTRIC: PT_SURF_TEX(Q_DIELECTRIC); break;
+        case Q_GGX: PT_SURF_TEX(Q_GGX); break;
+        default: break;
+        }
+        return;
+    }
+#undef PT_SURF_TEX
+#undef PT_SURF_TEX_L
     switch (qclass)
     {
     case Q_TERMINAL:
@@ -3232,6 +3319,18 @@ void launch_guide_resolve(hipStream_t s, const SceneView& sv, uint32_t n, const 
 {
     if (lens_set(lens)) hipLaunchKernelGGL(k_guide_resolve_lens, dim3((n + 255u) / 256u), dim3(256), 0, s, sv, n, cam, rq, hits, position, normal, model, instance);
     else hipLaunchKernelGGL(k_guide_resolve, dim3((n + 255u) / 256u), dim3(256), 0, s, sv, n, cam, rq, hits, position, normal, model, instance);
+}
+
+void launch_guide_albedo(hipStream_t s, const SceneView& sv, const TexView& tex, uint32_t n, const f4* hits, f4* albedo)
+{
+    if (n == 0u) return;
+    hipLaunchKernelGGL(k_guide_albedo, dim3((n + 255u) / 256u), dim3(256), 0, s, sv, tex, n, hits, albedo);
+}
+void launch_surface_colour(hipStream_t s, const SceneView& sv, const TexView& tex, uint32_t n, const uint32_t* instance, const uint32_t* tri, const float* u,
+                           const float* v, float* rgb)
+{
+    if (n == 0u) return;
+    hipLaunchKernelGGL(k_surface_colour, dim3((n + 255u) / 256u), dim3(256), 0, s, sv, tex, n, instance, tri, u, v, rgb);
 }
 
 } // namespace pt

@@ -137,18 +137,38 @@ PT_HD f3 beer_lambert(f3 absorption, float dist)
 // Equirect lookup of the environment on a miss  integrator.rs:256-262, image_helper.rs:61-88
 struct EnvView { const f4* data; uint32_t w, h, pad0, pad1; };
 PT_HD uint32_t sat_u32(float f) { return !(f > 0.0f) ? 0u : (f >= 4294967296.0f ? 0xffffffffu : (uint32_t)f); } // Rust `as u32`
+// get_pixel_bilinear(u, v) of a w x h image (image_helper.rs:61-88): the one lookup the environment and the textures share
+PT_HD f3 bilinear_rgb(const f4* data, uint32_t w, uint32_t h, float u, float v)
+{
+    float x = (float)w * u, y = (float)h * v;
+    uint32_t x0 = sat_u32(x), y0 = sat_u32(y);
+    float xf = x - truncf(x), yf = y - truncf(y);
+    const uint32_t xa = x0 % w, xb = (x0 + 1u) % w, ya = y0 % h, yb = (y0 + 1u) % h;
+    const f4 c00 = data[(size_t)ya * w + xa], c01 = data[(size_t)yb * w + xa];
+    const f4 c10 = data[(size_t)ya * w + xb], c11 = data[(size_t)yb * w + xb];
+    const f3 a{c00.x, c00.y, c00.z}, b{c01.x, c01.y, c01.z}, c{c10.x, c10.y, c10.z}, e{c11.x, c11.y, c11.z};
+    return (((1.0f - xf) * (1.0f - yf)) * a + ((1.0f - xf) * yf) * b + (xf * (1.0f - yf)) * c) + (xf * yf) * e;
+}
 PT_HD f3 env_lookup(const EnvView& env, f3 d)
 {
     float u = fma_rs(atan2_det(d.x, d.z), PT_FRAC_1_PI * 0.5f, 0.5f);
     float v = fma_rs(asin_det(d.y), -PT_FRAC_1_PI, 0.5f);
-    float x = (float)env.w * u, y = (float)env.h * v;
-    uint32_t x0 = sat_u32(x), y0 = sat_u32(y);
-    float xf = x - truncf(x), yf = y - truncf(y);
-    const uint32_t xa = x0 % env.w, xb = (x0 + 1u) % env.w, ya = y0 % env.h, yb = (y0 + 1u) % env.h;
-    const f4 c00 = env.data[(size_t)ya * env.w + xa], c01 = env.data[(size_t)yb * env.w + xa];
-    const f4 c10 = env.data[(size_t)ya * env.w + xb], c11 = env.data[(size_t)yb * env.w + xb];
-    const f3 a{c00.x, c00.y, c00.z}, b{c01.x, c01.y, c01.z}, c{c10.x, c10.y, c10.z}, e{c11.x, c11.y, c11.z};
-    return (((1.0f - xf) * (1.0f - yf)) * a + ((1.0f - xf) * yf) * b + (xf * (1.0f - yf)) * c) + (xf * yf) * e;
+    return bilinear_rgb(env.data, env.w, env.h, u, v);
+}
+
+// Surface colour of a hit (the definition is include/pt_api.h's): `colour` of the hit's material, times the bilinear texel at the hit's
+// interpolated, repeat-addressed UV when the material references a texture (`texture` = DMaterial::texture, index + 1).  tri: leaf order.
+// Every operation rounded once, in the order written (the library is built without contraction).
+PT_HD f3 surface_colour(const TexView& tv, uint32_t texture, f3 colour, uint32_t tri, float u, float v)
+{
+    if (texture == 0u) return colour;
+    const DTriUV uv = tv.tri_uv[tri];
+    const DTexture t = tv.table[texture - 1u];
+    float s = (uv.a[0] + u * (uv.b[0] - uv.a[0])) + v * (uv.c[0] - uv.a[0]);
+    float w = (uv.a[1] + u * (uv.b[1] - uv.a[1])) + v * (uv.c[1] - uv.a[1]);
+    s = s - floorf(s);
+    w = w - floorf(w);
+    return colour * bilinear_rgb(tv.texels + t.offset, t.w, t.h, s, w);
 }
 
 // MaterialTrait::scatter_direction

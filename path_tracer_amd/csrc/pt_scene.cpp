@@ -365,11 +365,17 @@ int HostScene::add_material(int kind, const float colour[3], float roughness, fl
     }
     materials.push_back(m);
     built = false;
+    tlas_valid = false;
     ++layout_epoch;
     return (int)materials.size() - 1;
 }
 
 int HostScene::add_model(const float* positions, const float* normals, uint32_t n_tris, int material, const float* affines, uint32_t n_inst)
+{
+    return add_model(positions, normals, n_tris, material, affines, n_inst, std::vector<float>());
+}
+
+int HostScene::add_model(const float* positions, const float* normals, uint32_t n_tris, int material, const float* affines, uint32_t n_inst, std::vector<float>&& uvs)
 {
     if (!positions || !normals || n_tris == 0 || material < 0 || material >= (int)materials.size() || (n_inst && !affines)) return -1;
     // Vertex positions must be numbers: a NaN or infinite coordinate makes every box it touches NaN / infinite, the builders'
@@ -384,8 +390,10 @@ int HostScene::add_model(const float* positions, const float* normals, uint32_t 
     m.positions.assign(positions, positions + (size_t)n_tris * 9);
     m.normals.assign(normals, normals + (size_t)n_tris * 9);
     if (!rigid_matrices(affines, n_inst, m.matrices)) return -4;
+    m.uvs = std::move(uvs);
     models.push_back(std::move(m));
     built = false;
+    tlas_valid = false;
     ++layout_epoch;
     return (int)models.size() - 1;
 }
@@ -398,6 +406,56 @@ int HostScene::set_instances(int model, const float* affines, uint32_t n_inst)
     if (matrices.size() != models[model].matrices.size()) ++layout_epoch;
     models[model].matrices = std::move(matrices);
     built = false;
+    tlas_valid = false;
+    return 0;
+}
+
+// Textures touch neither a BLAS nor a TLAS: they un-build the scene (the flattened tables change) and move the layout epoch (the next
+// upload is a full one), and HostScene::build then goes straight to flatten.
+int HostScene::add_texture(uint32_t w, uint32_t h, const float* rgb)
+{
+    if (w == 0 || h == 0 || !rgb) return -1;
+    if (w > kMaxTextureSide || h > kMaxTextureSide) return -5;
+    uint64_t total = (uint64_t)w * h;
+    for (const HostTexture& t : textures) total += (uint64_t)t.w * t.h;
+    if (total > kMaxTexels) return -5;
+    const size_t n = (size_t)w * h * 3;
+    for (size_t i = 0; i < n; ++i)
+        if (!finite_f(rgb[i]) || !(rgb[i] >= 0.0f)) return -1;
+    HostTexture t;
+    t.w = w;
+    t.h = h;
+    t.rgb.assign(rgb, rgb + n);
+    textures.push_back(std::move(t));
+    built = false;
+    ++layout_epoch;
+    return (int)textures.size() - 1;
+}
+
+int HostScene::set_material_texture(int material, int texture)
+{
+    if (material < 0 || material >= (int)materials.size() || texture < -1 || texture >= (int)textures.size()) return -1;
+    if (materials[material].kind == MAT_EMISSIVE) return -1;
+    materials[material].texture = (uint32_t)(texture + 1);
+    built = false;
+    ++layout_epoch;
+    return 0;
+}
+
+int HostScene::set_model_uvs(int model, const float* uv, uint32_t n_tris)
+{
+    if (model < 0 || model >= (int)models.size()) return -1;
+    HostModel& m = models[model];
+    if (!uv && n_tris == 0) m.uvs.clear();
+    else
+    {
+        if (!uv || n_tris != m.n_tris) return -1;
+        for (size_t i = 0; i < (size_t)n_tris * 6; ++i)
+            if (!finite_f(uv[i])) return -1;
+        m.uvs.assign(uv, uv + (size_t)n_tris * 6);
+    }
+    built = false;
+    ++layout_epoch;
     return 0;
 }
 
@@ -437,7 +495,8 @@ int HostScene::add_model_obj(const char* path, int material, const float* affine
     FILE* fp = fopen(path, "rb");
     if (!fp) { if (err) *err = std::string("cannot open ") + path; return -6; }
     std::vector<f3> positions{f3{0, 0, 0}}, normals{f3{0, 0, 0}}; // index 0 is a dummy: OBJ indices are 1-based  blas.rs:46-47
-    std::vector<float> out_p, out_n;
+    std::vector<std::pair<float, float>> uvs{{0.0f, 0.0f}};       // `vt`, 1-based like the others; index 0 (an empty or 0 reference) is (0, 0)
+    std::vector<float> out_p, out_n, out_uv;
     std::string line;
     int c;
     size_t line_no = 0;
@@ -472,9 +531,17 @@ int HostScene::add_model_obj(const char* path, int material, const float* affine
             if (tok[0] == "v") positions.push_back(v);
             else normals.push_back(unit3(v));                                                  // blas.rs:74
         }
+        else if (tok[0] == "vt")
+        {
+            std::pair<float, float> t{0.0f, 0.0f};                                               // `vt u [v [w]]`: two numbers are read, a missing v is 0
+            if (tok.size() < 2 || !parse_f32(tok[1], &t.first) || (tok.size() > 2 && !parse_f32(tok[2], &t.second))) return bad("expected two numbers");
+            if (!finite_f(t.first) || !finite_f(t.second)) return bad("texture coordinate is not a finite number");
+            uvs.push_back(t);
+        }
         else if (tok[0] == "f")
         {
-            std::vector<std::pair<size_t, size_t>> refs;
+            struct Ref { size_t first, second, uv; };                                           // position, normal, texture coordinate
+            std::vector<Ref> refs;
             for (size_t k = 1; k < tok.size(); ++k)
             {
                 std::vector<std::string> idx;
@@ -486,18 +553,22 @@ int HostScene::add_model_obj(const char* path, int material, const float* affine
                     if (b == std::string::npos) break;
                     a = b + 1;
                 }
-                size_t vi, ni;
+                size_t vi, ni, ti = 0;
                 if (idx.size() < 3) return bad("face reference needs v/vt/vn");                 // indices[2] panics in the reference
                 if (!parse_index(idx[0], positions.size(), &vi) || !parse_index(idx[2], normals.size(), &ni)) return bad("bad face index");
+                // the middle reference by the same rules; the reference never reads it, so one that is empty, unparsable or out of range is no
+                // error (files that loaded keep loading): it gives (0, 0) like an explicit 0
+                if (idx[1].empty() || !parse_index(idx[1], uvs.size(), &ti) || ti >= uvs.size()) ti = 0;
                 if (vi >= positions.size() || ni >= normals.size()) return bad("face index out of range");
-                refs.push_back({vi, ni});
+                refs.push_back({vi, ni, ti});
             }
             if (refs.size() < 3) continue;                                                       // `1..(len - 1)` is empty
             for (size_t k = 1; k + 1 < refs.size(); ++k)                                         // blas.rs:97-119
             {
-                const std::pair<size_t, size_t> tri[3] = {refs[0], refs[k], refs[k + 1]};
+                const Ref tri[3] = {refs[0], refs[k], refs[k + 1]};
                 for (const auto& r : tri)
                 {
+                    out_uv.insert(out_uv.end(), {uvs[r.uv].first, uvs[r.uv].second});
                     const f3 p = positions[r.first];
                     f3 n;
                     if (r.second != 0) n = normals[r.second];
@@ -510,7 +581,8 @@ int HostScene::add_model_obj(const char* path, int material, const float* affine
     }
     fclose(fp);
     if (out_p.empty()) { if (err) *err = std::string(path) + ": no faces"; return -7; }
-    return add_model(out_p.data(), out_n.data(), (uint32_t)(out_p.size() / 9), material, affines, n_inst);
+    if (uvs.size() == 1) out_uv.clear();                                                         // a file without `vt`: a model without UVs
+    return add_model(out_p.data(), out_n.data(), (uint32_t)(out_p.size() / 9), material, affines, n_inst, std::move(out_uv));
 }
 
 void HostScene::build_blas(HostBlas& out, const HostModel& m)                           // BLAS::new  blas.rs:174-201
@@ -637,14 +709,18 @@ int HostScene::build(std::string* err)                                          
         ++blas_builds;
     }
     const auto t1 = now();
-    std::vector<uint32_t> all(models.size()), emissive;
-    std::iota(all.begin(), all.end(), 0u);
-    for (uint32_t i = 0; i < models.size(); ++i)
-        if (materials[models[i].material].kind == MAT_EMISSIVE) emissive.push_back(i);
-    build_tlas(world, all);
-    build_tlas(lights, emissive);
-    build_lights();
-    ++tlas_builds;
+    if (!tlas_valid)
+    {
+        std::vector<uint32_t> all(models.size()), emissive;
+        std::iota(all.begin(), all.end(), 0u);
+        for (uint32_t i = 0; i < models.size(); ++i)
+            if (materials[models[i].material].kind == MAT_EMISSIVE) emissive.push_back(i);
+        build_tlas(world, all);
+        build_tlas(lights, emissive);
+        build_lights();
+        ++tlas_builds;
+        tlas_valid = true;
+    }
     const auto t2 = now();
     int r = flatten(err);
     if (dbg) fprintf(stderr, "[ptmi] scene build: BLAS %.1f ms, TLAS + lights %.1f ms, flatten %.1f ms\n", ms(t0, t1), ms(t1, t2), ms(t2, now()));
@@ -657,6 +733,7 @@ int HostScene::flatten(std::string* err)
     FlatScene f;
     f.materials = materials;
     for (const DMaterial& m : materials) f.has_volumes = f.has_volumes || m.has_volume != 0;
+    for (const DMaterial& m : materials) f.has_textures = f.has_textures || m.texture != 0;
     // One volume per model.  The reference keys its volume stack by the address of the material (volume.rs:146-162), and every BLAS
     // owns a copy of its model's material (blas.rs:167,197): two models of equal materials are two volumes, all instances of one model
     // are one.  The device keys the stack by material index, so the first model of a volume-bearing material keeps the index and
@@ -704,6 +781,9 @@ int HostScene::flatten(std::string* err)
     flat_valid = false;
     if (keep_blas)
     {
+        f.tri_uv = std::move(flat.tri_uv);        // (textures, texture references and UVs move the epoch: these are current too)
+        f.tex_table = std::move(flat.tex_table);
+        f.tex_texels = std::move(flat.tex_texels);
         f.nodes = std::move(flat.nodes);
         f.big_leaves = std::move(flat.big_leaves);
         f.tri_isect = std::move(flat.tri_isect);
@@ -794,6 +874,25 @@ int HostScene::flatten(std::string* err)
         f.tri_shade.reserve(tri_cursor);
         f.tri_pos.reserve(tri_cursor);
         f.tri_orig.reserve(tri_cursor);
+        if (f.has_textures)
+        {
+            f.tri_uv.reserve(tri_cursor);
+            uint32_t at = 0;
+            for (const HostTexture& t : textures)
+            {
+                f.tex_table.push_back(DTexture{at, t.w, t.h, 0u});
+                at += t.w * t.h;                                                         // (at most kMaxTexels in all: add_texture)
+            }
+            f.tex_texels.resize(at);
+            for (size_t i = 0; i < textures.size(); ++i)
+            {
+                const HostTexture& t = textures[i];
+                f4* dst = f.tex_texels.data() + f.tex_table[i].offset;
+                parallel_slices((size_t)t.w * t.h, [&](size_t lo, size_t hi) {
+                    for (size_t k = lo; k < hi; ++k) dst[k] = f4{t.rgb[3 * k], t.rgb[3 * k + 1], t.rgb[3 * k + 2], 0.0f};
+                });
+            }
+        }
     }
     for (size_t i = 0; i < blas.size(); ++i)
     {
@@ -825,6 +924,17 @@ int HostScene::flatten(std::string* err)
                 f.tri_orig[at + k] = id;
             }
         });
+        if (f.has_textures)
+        {
+            const std::vector<float>& uv = models[i].uvs;
+            f.tri_uv.resize(at + bl.prim_ids.size(), DTriUV{{0.0f, 0.0f}, {0.0f, 0.0f}, {0.0f, 0.0f}});
+            if (!uv.empty())
+                for (size_t k = 0; k < bl.prim_ids.size(); ++k)
+                {
+                    const float* p = &uv[(size_t)bl.prim_ids[k] * 6];
+                    f.tri_uv[at + k] = DTriUV{{p[0], p[1]}, {p[2], p[3]}, {p[4], p[5]}};
+                }
+        }
     }
     auto put_instances = [&](const HostTlas& t, uint32_t ident_bit) {
         bool all_identity = true;

@@ -52,9 +52,16 @@ struct HostTlas
 struct HostModel
 {
     std::vector<float> positions, normals; // n_tris * 9
+    std::vector<float> uvs;                // n_tris * 6 (three UVs per triangle, load order), or empty: (0, 0) at every vertex
     uint32_t n_tris = 0;
     int material = 0;
     std::vector<xf34> matrices;
+};
+
+struct HostTexture
+{
+    uint32_t w = 0, h = 0;
+    std::vector<float> rgb;                // w * h * 3, linear, row-major
 };
 
 struct HostLight { uint32_t blas, prim; float pdf, cdf; };
@@ -76,6 +83,9 @@ struct FlatScene
     std::vector<DTriIsect> tri_isect;
     std::vector<DTriVerts> tri_shade, tri_pos;
     std::vector<uint32_t> tri_orig;
+    std::vector<DTriUV> tri_uv;         // leaf order like tri_shade; empty unless some material references a texture (has_textures)
+    std::vector<DTexture> tex_table;    // ... and so are the texture table and the texels (every texture, in pt_add_texture order)
+    std::vector<f4> tex_texels;
     std::vector<DInstance> instances;
     std::vector<uint32_t> big_leaves;   // {first, count} pairs of the leaves NODE_TRIS cannot encode
     std::vector<DMaterial> materials;
@@ -88,6 +98,15 @@ struct FlatScene
     uint32_t ident_tlas = 0;            // IDENT_TLAS_WORLD / IDENT_TLAS_LIGHTS: every instance of that TLAS carries INSTANCE_IDENTITY
     float light_weight_sum = 0;
     bool has_volumes = false;
+    bool has_textures = false;          // some material references a texture: the shading passes are the TEX variants
+    TexView tex_view() const { return TexView{tex_texels.data(), tex_table.data(), tri_uv.data()}; } // over the host copies
+    // bytes of every table an upload copies (pt_scene_info::scene_bytes)
+    size_t table_bytes() const
+    {
+        return nodes.size() * sizeof(DNode) + tri_isect.size() * sizeof(DTriIsect) + instances.size() * sizeof(DInstance) + (big_leaves.size() * 4 + 15) / 16 * 16 +
+               (tri_shade.size() + tri_pos.size()) * sizeof(DTriVerts) + tri_orig.size() * 4 + materials.size() * sizeof(DMaterial) + lights.size() * sizeof(DLight) +
+               tri_uv.size() * sizeof(DTriUV) + tex_table.size() * sizeof(DTexture) + tex_texels.size() * sizeof(f4);
+    }
 };
 
 class HostScene
@@ -95,6 +114,7 @@ class HostScene
 public:
     std::vector<DMaterial> materials;
     std::vector<HostModel> models;
+    std::vector<HostTexture> textures;
     std::vector<HostBlas> blas;         // one per model
     HostTlas world, lights;
     std::vector<HostLight> light_items;
@@ -107,16 +127,25 @@ public:
     // epoch it last saw can patch the TLAS nodes and instance records in place.
     uint64_t layout_epoch = 0;
     uint64_t blas_builds = 0, tlas_builds = 0;
+    bool tlas_valid = false;    // the two TLASes and the light sampler are those of the current models, materials and matrices: an edit that
+                                // touches none of them (a texture, a material's texture reference, a model's UVs) leaves them standing
     bool flat_valid = false;    // `flat` is a finished flatten of layout_epoch flat_epoch: its BLAS nodes and per-triangle tables can be kept
     uint64_t flat_epoch = 0;
 
     int add_material(int kind, const float colour[3], float roughness, float ior, bool has_volume, const float vol_abs[3], float k, float c,
                      float g);
     int add_model(const float* positions, const float* normals, uint32_t n_tris, int material, const float* affines, uint32_t n_inst);
+    // (the OBJ reader's: with the UVs it read, empty for a file without `vt`)
+    int add_model(const float* positions, const float* normals, uint32_t n_tris, int material, const float* affines, uint32_t n_inst, std::vector<float>&& uvs);
     // load_obj (blas.rs:44-131) + add_model; returns the model index, -1 bad argument, -4 non-rigid, -6 unreadable file, -7 parse error
     int add_model_obj(const char* path, int material, const float* affines, uint32_t n_inst, std::string* err);
     // replaces the instance matrices of a model (checked as add_model checks them); -1 bad argument, -4 non-rigid: nothing changed
     int set_instances(int model, const float* affines, uint32_t n_inst);
+    // textures (the definition is include/pt_api.h's).  Each returns -1 for a bad argument, -5 for the packing limit; nothing changed then
+    enum : uint64_t { kMaxTextureSide = 16384u, kMaxTexels = 1ull << 28 }; // per side; texels of all textures together (32-bit f4 offsets, 4 GiB)
+    int add_texture(uint32_t w, uint32_t h, const float* rgb);
+    int set_material_texture(int material, int texture);             // -1 clears
+    int set_model_uvs(int model, const float* uv, uint32_t n_tris);  // nullptr, 0 clears
     int build(std::string* err);
     void set_camera(const float eye[3], const float target[3], float fov_deg, float aspect);
     void create_ray(float s, float t, float o[3], float d[3]) const;

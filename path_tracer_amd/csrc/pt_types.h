@@ -8,7 +8,8 @@
 //   tri_shade  : 48 B  vertex normals  (3 x float4, w unused)
 //   tri_pos    : 48 B  vertex positions (3 x float4, w unused)  - only light sampling reads it
 //   instances  : 144 B inverse 3x4 | blas root, blas id, material, class | copy of the BLAS root node | forward 3x4
-//   materials  : 48 B
+//   materials  : 64 B
+//   tri_uv     : 24 B  three UVs, BLAS-leaf order (textured scenes only) | tex_table : 16 B {offset, w, h} | tex_texels : 16 B rgb | -
 //   lights     : 16 B  { triangle, material, pdf, cdf }
 // Traversal touches nodes + tri_isect + instances only ("scene blob"); when that fits it is staged in LDS.
 #pragma once
@@ -78,9 +79,30 @@ struct alignas(16) DMaterial
     float vol_abs[3];   // absorption * k
     float vol_c;
     float vol_g;
-    float pad[3];
+    uint32_t texture;   // index + 1 into the texture table (TexView), 0 = none: the surface colour is `colour` itself
+    float pad[2];
 };
 static_assert(sizeof(DMaterial) == 64, "");
+
+// Textures (pt_add_texture): every texture's texels in ONE f4 buffer (rgb | unused), row-major, one after the other; the table says where.
+struct alignas(16) DTexture
+{
+    uint32_t offset;    // first texel in the texel buffer
+    uint32_t w, h;
+    uint32_t pad;
+};
+static_assert(sizeof(DTexture) == 16, "");
+// the three UVs of a triangle (load-order vertices 0, 1, 2), in BLAS leaf order like tri_shade; only scenes with a textured material have the array
+struct DTriUV { float a[2], b[2], c[2]; };
+static_assert(sizeof(DTriUV) == 24, "");
+// What a surface-colour lookup reads beside the SceneView.  A view of its own, handed only to the kernels that look textures up, so that the
+// SceneView and with it every other kernel's argument layout stay what they are.
+struct TexView
+{
+    const f4* texels;
+    const DTexture* table;
+    const DTriUV* tri_uv;
+};
 
 struct alignas(16) DLight
 {

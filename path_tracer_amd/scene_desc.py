@@ -37,6 +37,28 @@ class Volume:
         return Volume(tuple(float(x) for x in absorption), float(k), float(c), float(g))
 
 
+@dataclass(eq=False)
+class Texture:
+    """w x h linear-RGB texels (pt_add_texture; the library's own addition, the reference has none).  Compared and hashed by IDENTITY: two
+    materials share a texture when they hold the same object, and an untextured material compares exactly as it did before textures."""
+
+    data: np.ndarray  # [h, w, 3] float32, row 0 first, finite and non-negative
+
+    @staticmethod
+    def new(data) -> "Texture":
+        d = np.ascontiguousarray(data, dtype=np.float32)
+        assert d.ndim == 3 and d.shape[2] == 3 and d.shape[0] > 0 and d.shape[1] > 0
+        return Texture(d)
+
+    @property
+    def width(self) -> int:
+        return int(self.data.shape[1])
+
+    @property
+    def height(self) -> int:
+        return int(self.data.shape[0])
+
+
 @dataclass(frozen=True)
 class Material:
     kind: int
@@ -44,6 +66,12 @@ class Material:
     roughness: float = 0.0
     ior: float = 1.0
     volume: Optional[Volume] = None
+    texture: Optional[Texture] = None  # surface colour = colour * bilinear texel at the hit's UV (any kind but EMISSIVE); the oracle ignores it
+
+    def textured(self, texture: Optional[Texture]) -> "Material":
+        """this material with `texture` (None: without one)"""
+        assert texture is None or self.kind != EMISSIVE
+        return Material(self.kind, self.colour, self.roughness, self.ior, self.volume, texture)
 
 
 def _c3(v):
@@ -159,14 +187,18 @@ class Model:
     matrices: np.ndarray = field(default_factory=lambda: IDENTITY_3x4[None].copy())  # [n_inst, 3, 4] row-major
     name: str = ""
     obj_path: Optional[str] = None  # Model::new(path, ...): geometry read by the library's load_obj (blas.rs:44-131)
+    uvs: Optional[np.ndarray] = None  # [n_tris, 3, 2] float32 texture coordinates (pt_set_model_uvs); None: (0, 0) everywhere, or the OBJ's `vt`
 
     @staticmethod
-    def new(positions, normals, material: Material, matrices: Optional[Sequence] = None, name: str = "") -> "Model":
+    def new(positions, normals, material: Material, matrices: Optional[Sequence] = None, name: str = "", uvs=None) -> "Model":
         p = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3, 3)
         n = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3, 3)
         assert p.shape == n.shape and p.shape[0] > 0
         m = IDENTITY_3x4[None].copy() if matrices is None else np.ascontiguousarray(matrices, dtype=np.float32).reshape(-1, 3, 4)
-        return Model(p, n, material, m, name)
+        if uvs is not None:
+            uvs = np.ascontiguousarray(uvs, dtype=np.float32).reshape(-1, 3, 2)
+            assert uvs.shape[0] == p.shape[0]
+        return Model(p, n, material, m, name, uvs=uvs)
 
     @staticmethod
     def from_obj(path: str, material: Material, matrices: Optional[Sequence] = None, name: str = "") -> "Model":

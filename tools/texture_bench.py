@@ -1,0 +1,93 @@
+"""Texture record (profiles/r12_textures.md): what textured surface colour costs.  The 1080p Cornell frame untextured, with its floor, ceiling
+and walls on a 1024 x 1024 checker, and the same on an 8 x 8 one — same build, same process, interleaved: wall clock of the blocking
+pt_render_device per frame (median of --reps, after a warm-up frame of each).  The 8 x 8 texture lives in cache, so its ratio is the cost of the
+TEX shading variants (and of queueing the shadow rays the untextured frame walks inline); the 1024 x 1024 ratio adds the texel traffic.
+
+    python tools/texture_bench.py [--width 1920 --height 1080 --spp 256 --bounces 8 --reps 5 --repeat 8] [--out file.json]
+    python tools/texture_bench.py --only tex1024 --reps 1      one variant alone, e.g. under rocprofv3 --kernel-trace --stats
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def checker(n):
+    i, j = np.meshgrid(np.arange(n), np.arange(n))
+    return np.repeat(np.where((i + j) & 1, np.float32(0.2), np.float32(1.0))[..., None], 3, axis=2)
+
+
+def planar_uvs(positions, repeat):
+    """UVs over the two longest axes of the model's extent, `repeat` periods across it"""
+    p = np.asarray(positions, np.float32)
+    lo, hi = p.min(axis=(0, 1)), p.max(axis=(0, 1))
+    ax = np.sort(np.argsort(hi - lo)[1:])
+    return (p[:, :, ax] - lo[ax]) / (hi - lo)[ax] * np.float32(repeat)
+
+
+def textured_cornell(scenes, W, H, n, repeat):
+    from path_tracer_amd.scene_desc import Model, SceneDesc, Texture
+    tex = Texture.new(checker(n))
+    models = []
+    for m in scenes.cornell_models():
+        if m.name in ("cb_main", "cb_left", "cb_right"):
+            m = Model.new(m.positions, m.normals, m.material.textured(tex), m.matrices, m.name, uvs=planar_uvs(m.positions, repeat))
+        models.append(m)
+    return SceneDesc.new(models, scenes.reference_camera(W / H), f"cornell checker {n}")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--width", type=int, default=1920)
+    ap.add_argument("--height", type=int, default=1080)
+    ap.add_argument("--spp", type=int, default=256)
+    ap.add_argument("--bounces", type=int, default=8)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--repeat", type=float, default=8.0)
+    ap.add_argument("--only", choices=["plain", "tex8", "tex1024"])
+    ap.add_argument("--out")
+    a = ap.parse_args()
+    from path_tracer_amd import api, scenes
+    W, H = a.width, a.height
+    variants = {"plain": lambda: scenes.cornell_box(W, H), "tex8": lambda: textured_cornell(scenes, W, H, 8, a.repeat),
+                "tex1024": lambda: textured_cornell(scenes, W, H, 1024, a.repeat)}
+    if a.only:
+        variants = {a.only: variants[a.only]}
+    rs = {}
+    for name, make in variants.items():
+        r = api.Renderer(make(), W, H, max_bounces=a.bounces)
+        r.render_device(0, a.spp)          # warm-up: code objects, buffers, the scene upload
+        r.synchronize()
+        rs[name] = r
+    times = {name: [] for name in rs}
+    for rep in range(a.reps):              # interleaved: whatever else the machine does falls on all three
+        for name, r in rs.items():
+            r.reset_accumulation()
+            r.synchronize()
+            t0 = time.perf_counter()
+            r.render_device(0, a.spp)
+            r.synchronize()
+            times[name].append(1e3 * (time.perf_counter() - t0))
+    res = dict(width=W, height=H, spp=a.spp, bounces=a.bounces, reps=a.reps, variants={})
+    for name, r in rs.items():
+        t = times[name]
+        st = r.stats()
+        res["variants"][name] = dict(ms_per_frame=float(np.median(t)) if t else None, ms_min=min(t) if t else None, ms_max=max(t) if t else None,
+                                     scene_bytes=int(r.scene_info().scene_bytes), rays_any=int(st.rays_any))
+    if "plain" in rs and a.reps:
+        for name in rs:
+            if name != "plain":
+                res[name + "_over_plain"] = res["variants"][name]["ms_per_frame"] / res["variants"]["plain"]["ms_per_frame"]
+    print(json.dumps(res), flush=True)
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
