@@ -11,6 +11,9 @@
 //   examples/headless ... --slide DX DZ   frame f >= 1 first moves the short box to the translation (f * DX, 0, f * DZ) (pt_set_instances + pt_build:
 //                                          the BLASes are kept, the resident scene is patched) and the loop drives frame_moving instead of frame
 //   examples/headless ... --denoise den.png   also writes the final frame through the edge-aware denoiser (guides of the last frame's sample)
+//   examples/headless ... --denoise-albedo den.png   the same through the demodulated filter (pt_denoise_albedo): the mean albedo of every pixel
+//                                        is accumulated over the samples that were rendered, the frame divided by it, filtered and multiplied back,
+//                                        so textures (--checker) stay sharp; also with --render
 //   examples/headless ... --bake-probes NX NY NZ SPP probes.txt   after the usual render, bakes SPP samples into an NX x NY x NZ grid of
 //       irradiance probes spanning the scene's bounds shrunk by 5 % per side (x fastest, then y, then z; stream keys 0, 1, ...) and
 //       writes one line per probe: its 27 raw spherical-harmonics sums [k][c] as hexadecimal floats (%a)
@@ -35,7 +38,7 @@ int main(int argc, char** argv)
     float slide_dx = 0.0f, slide_dz = 0.0f;
     uint32_t gpus = 0, spp = 64;
     std::vector<int32_t> devices;
-    std::string models_dir = "models/cornell", out = "", load_state = "", save_state = "", denoise_out = "";
+    std::string models_dir = "models/cornell", out = "", load_state = "", save_state = "", denoise_out = "", denoise_albedo_out = "";
     bool render_mode = false;
     uint32_t render_first = 0, render_count = 0;
     float aperture = 0.0f, focus = 950.0f; // main.rs:127's values: a pinhole
@@ -55,6 +58,7 @@ int main(int argc, char** argv)
         else if (a == "--models") models_dir = next("--models");
         else if (a == "--out") out = next("--out");
         else if (a == "--denoise") denoise_out = next("--denoise");
+        else if (a == "--denoise-albedo") denoise_albedo_out = next("--denoise-albedo");
         else if (a == "--move") move = true;
         else if (a == "--slide") { slide = true; slide_dx = (float)std::atof(next("--slide")); slide_dz = (float)std::atof(next("--slide")); }
         else if (a == "--aperture") aperture = (float)std::atof(next("--aperture"));
@@ -78,7 +82,7 @@ int main(int argc, char** argv)
         }
         else if (a == "--help" || a == "-h")
         {
-            std::printf("usage: %s [--width W] [--height H] [--frames N] [--bounces B] [--move] [--slide DX DZ] [--models DIR] [--out file.png] [--denoise file.png] [--aperture A --focus F] [--bake-probes NX NY NZ SPP file.txt] [--checker N]\n", argv[0]);
+            std::printf("usage: %s [--width W] [--height H] [--frames N] [--bounces B] [--move] [--slide DX DZ] [--models DIR] [--out file.png] [--denoise file.png] [--denoise-albedo file.png] [--aperture A --focus F] [--bake-probes NX NY NZ SPP file.txt] [--checker N]\n", argv[0]);
             return 0;
         }
         else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
@@ -171,6 +175,13 @@ int main(int argc, char** argv)
             std::fclose(f);
             return true;
         };
+        // the demodulated denoiser on samples [first, first + count) of the frame: guides of the last sample, the mean albedo of all of them
+        auto denoise_albedo = [&](uint32_t first, uint32_t count) {
+            renderer.render_guides(first + count - 1);
+            renderer.accumulate_albedo(first, count);
+            renderer.denoise_albedo(PT_ALBEDO_MEAN);
+            renderer.write_denoised_image(denoise_albedo_out);
+        };
         if (render_mode)
         {
             // checkpoint / resume: the state file is {width, height, data rgba, position xyzt, id} of the frame as it lies on the device
@@ -201,6 +212,7 @@ int main(int argc, char** argv)
             }
             std::printf("{\"first_sample\": %u, \"samples\": %u, \"width\": %u, \"height\": %u}\n", render_first, render_count, width, height);
             if (!out.empty()) renderer.write_image(out);
+            if (!denoise_albedo_out.empty() && render_count) denoise_albedo(render_first, render_count);
             return bake_probes() ? 0 : 1;
         }
         Mat4 last_inv_proj = renderer.inv_projection();
@@ -238,6 +250,7 @@ int main(int argc, char** argv)
             renderer.denoise();
             renderer.write_denoised_image(denoise_out);
         }
+        if (!denoise_albedo_out.empty() && frames) denoise_albedo(0, frames);
         if (!bake_probes()) return 1;
     }
     catch (const Error& e)

@@ -176,7 +176,7 @@ int pt_get_scene_info(pt_ctx* ctx, pt_scene_info* out);
  * for a texture side above 16384 texels or more than 2^28 texels in all textures together (texels are addressed by 32-bit offsets into one
  * 16-byte-per-texel buffer).  A refused call changes nothing.
  * Out of scope: mip maps and filter footprints, nearest filtering, normal / roughness / emission maps, changing texel data after upload,
- * PNG decoding, and demodulating the denoiser's input by the albedo guide (the obvious follow-up). */
+ * PNG decoding.  (Demodulating the denoiser's input by the albedo is pt_denoise_albedo, below.) */
 int pt_add_texture(pt_ctx* ctx, uint32_t w, uint32_t h, const float* rgb_linear);        /* returns the texture index */
 int pt_set_material_texture(pt_ctx* ctx, int material, int texture);                     /* texture -1 clears */
 int pt_set_model_uvs(pt_ctx* ctx, int model, const float* uv, uint32_t n_tris);          /* NULL, 0 clears */
@@ -369,7 +369,7 @@ int pt_read_guides(pt_ctx* ctx, float* position_xyzt, float* normal_xyz, uint32_
  * pt_instance_materials use — 0xffffffff for a miss; local_rows * width words.  PT_ERR_STATE without guides. */
 int pt_read_guide_instances(pt_ctx* ctx, uint32_t* instance);
 /* the fifth guide: ALBEDO, local_rows * width rgb f32 — the surface colour at the first hit (pt_add_texture), an emissive hit's emitted colour,
- * (0, 0, 0) for a miss.  pt_denoise does not use it yet: demodulating its input by the albedo is the follow-up.  PT_ERR_STATE without guides. */
+ * (0, 0, 0) for a miss.  pt_denoise does not use it; pt_denoise_albedo(PT_ALBEDO_GUIDE) divides its input by it.  PT_ERR_STATE without guides. */
 int pt_read_guide_albedo(pt_ctx* ctx, float* rgb);
 /* The filter, in f32 with every operation correctly rounded (no contraction) and in the order written.  exp is pt_math.h's exp_det.
  *   Pixel p is VALID when acc.w != 0; an invalid pixel is never a neighbour and its output is (0,0,0,0).  Every valid output is (c, 1).
@@ -393,7 +393,7 @@ int pt_read_guide_albedo(pt_ctx* ctx, float* rgb);
  *       e = 1 for p; else a_l = |l_p - l_q| * inv, e = exp(-a_l) for two misses, wn * exp(-(a_x + a_l)) for two hits;
  *       w = (h[dx] * h[dy]) * e, h = (1, 4, 6, 4, 1) / 16;  sw += w; sc += w * c_q (per channel); sv += (w * w) * var_q;
  *     c' = sc / sw (per channel); var' = sv / (sw * sw).
- *   The result is (c', 1) of the last level.  There is no demodulation (albedo was constant per model until textures; pt_read_guide_albedo).
+ *   The result is (c', 1) of the last level.  There is no demodulation here (pt_denoise_albedo, below, adds it).
  * pt_denoise filters the context's accumulation with its guides (and its moments where valid) and never changes the accumulation, id history,
  * position or moments; rgba (NULL: the result stays on the device) receives local_rows * width rgba f32.  PT_ERR_ARG: p NULL, iterations > 8,
  * a sigma that is negative, NaN or infinite, a sigma_normal that is not a power of two from 1 to 256 (checked before any device call).
@@ -412,6 +412,51 @@ int pt_write_denoised_image(pt_ctx* ctx, const char* path); /* pt_write_image of
  * spatial variance) */
 int pt_post_denoise(pt_ctx* ctx, uint32_t w, uint32_t h, const pt_denoise_params* p, const float* accum_rgba, const float* position_xyzt,
                     const float* normal_xyz, const uint32_t* model, const float* sumsq, float* out_rgba);
+
+/* ---- demodulation: the filter on acc / albedo, so that texture detail survives it -------------------------------------------------- */
+/* pt_denoise tells surfaces apart by model; inside a model only its luminance term separates colours, and that term is scaled by a variance
+ * which texture contrast itself inflates: a textured surface comes out blurred.  These entry points divide the accumulation by the surface
+ * colour before the filter and multiply the result by it afterwards, so the filter sees the irradiance, which is smooth across texels.
+ * pt_denoise, pt_post_denoise, pt_render_guides and pt_read_guide_albedo are what they were, bit for bit, and a context that never calls the
+ * functions below allocates and launches nothing for them.
+ *
+ * MEAN ALBEDO.  The albedo guide is ONE sample's first hit, the accumulation the mean of many jittered samples; at a texel edge or a
+ * silhouette their ratio is off by the ratio of two texels.  pt_accumulate_albedo averages the albedo over the pixel as the render averages
+ * the radiance: for every local pixel (on any rank, ignoring the primary-cull rectangle, pinhole or lens) and every sample s of
+ * [first_sample, first_sample + n_samples) in ascending order,
+ *     S.r += a.r;  S.g += a.g;  S.b += a.b;  S.w += 1          -- one binary32 add each
+ * where a is what pt_render_guides(s) stores as that pixel's albedo guide (the surface colour at the first hit, an emissive hit's emitted
+ * colour), except that a sample which MISSES adds (1, 1, 1): the background passes through the demodulation undivided.  Calls continue the
+ * sums: (0, a) then (a, b) equals (0, a + b) bit for bit.  The sums go stale on exactly the events that make the guides stale (pt_set_camera,
+ * pt_camera_input, pt_set_lens, pt_build, pt_set_config, pt_set_environment); accumulating onto stale or reset sums starts from zero.  The
+ * call never touches the accumulation, the position and id history, the moments or the guides.  Errors, before any device call: PT_ERR_STATE
+ * without a built scene or a camera; PT_ERR_ARG for n_samples == 0 or first_sample + n_samples above 2^32.  pt_reset_albedo drops the sums.
+ * pt_read_albedo copies them out, local_rows * width entries of (sum r, sum g, sum b, n); PT_ERR_STATE without current sums. */
+int pt_accumulate_albedo(pt_ctx* ctx, uint32_t first_sample, uint32_t n_samples);
+int pt_reset_albedo(pt_ctx* ctx);
+int pt_read_albedo(pt_ctx* ctx, float* rgbn);
+/* THE DEMODULATED FILTER, in binary32 with every operation rounded once, no contraction, in this order.  Everything not restated is pt_denoise's.
+ *   A   = the pixel's albedo: PT_ALBEDO_GUIDE the albedo guide; PT_ALBEDO_MEAN (S.r / S.w, S.g / S.w, S.b / S.w) of the mean-albedo sums;
+ *         pt_post_denoise_albedo the caller's image.
+ *   k   = (1, 1, 1) when model_p is a miss; otherwise per channel k.ch = A.ch > 0x1p-10f ? A.ch : 0x1p-10f.
+ *   c'.ch = (acc.ch / k.ch) / acc.w, beside the plain colour c.ch = acc.ch / acc.w.
+ *   VARIANCE with moments: e2 exactly as pt_denoise computes it from the modulated (acc, Q); r = l(c) > 0 ? l(c') / l(c) : 1;
+ *         var' = (e2 * r) * r -- the relative error is kept.  (With k = 1, r is exactly 1; Q / l(k)^2 in its place can go negative under coloured
+ *         light on a coloured albedo, which clamps to 0 and switches the filter off.)  Without moments the 7 x 7 spatial pass runs on c'.
+ *   LEVELS: pt_denoise's, unchanged, on (c', var'), to c''.
+ *   OUTPUT of a valid pixel: (c''.r * k.r, c''.g * k.g, c''.b * k.b, 1); an invalid one gives (0, 0, 0, 0).
+ * So a frame of misses, or one whose albedo is 1 everywhere, gives pt_denoise's bits.
+ * pt_denoise_albedo: PT_ERR_ARG (before any device call) for what pt_denoise refuses and for an albedo_source other than the two; PT_ERR_STATE
+ * for what pt_denoise refuses and, with PT_ALBEDO_MEAN, for missing or stale sums.  pt_write_denoised_image writes its result like pt_denoise's.
+ * pt_post_denoise_albedo runs the same kernels on caller images (albedo_rgb: w * h rgb): PT_ERR_ARG, before any device call, for what
+ * pt_post_denoise refuses, a NULL albedo, and an albedo component that is negative or not finite.
+ * The interactive recipe: pt_frame(k), pt_render_guides(k), pt_accumulate_albedo over the samples in the frame, pt_denoise_albedo(PT_ALBEDO_MEAN).
+ * Out of scope: following specular or dielectric first hits to the first diffuse surface; demodulation inside pt_frame's temporal history;
+ * pt_multi_* variants; accumulating the albedo inside the render's own shading pass (the sums take a small pass of their own). */
+enum { PT_ALBEDO_GUIDE = 1, PT_ALBEDO_MEAN = 2 };
+int pt_denoise_albedo(pt_ctx* ctx, const pt_denoise_params* p, uint32_t albedo_source, float* rgba);
+int pt_post_denoise_albedo(pt_ctx* ctx, uint32_t w, uint32_t h, const pt_denoise_params* p, const float* accum_rgba, const float* position_xyzt,
+                           const float* normal_xyz, const uint32_t* model, const float* albedo_rgb, const float* sumsq, float* out_rgba);
 
 /* ---- caller-supplied rays: "what radiance arrives along THIS ray?" ---------------------------------------------------- */
 /* Every render entry point above starts its paths at the context's camera.  pt_integrate_rays runs the same wavefront integrator over rays the

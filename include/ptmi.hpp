@@ -320,6 +320,15 @@ public:
     void render_guides(uint32_t sample) { check(pt_render_guides(ctx_, sample)); }
     void denoise(const pt_denoise_params& p = pt_denoise_params{}) { check(pt_denoise(ctx_, &p, nullptr)); }
     void write_denoised_image(const std::string& path) const { check(pt_write_denoised_image(ctx_, path.c_str())); }
+    // the demodulated filter (pt_denoise_albedo): the mean albedo of samples [first, first + n) of every pixel, then denoise() on the
+    // accumulation divided by it (or by the albedo guide: PT_ALBEDO_GUIDE) and multiplied back; the result is written like denoise()'s
+    void accumulate_albedo(uint32_t first_sample, uint32_t n_samples) { check(pt_accumulate_albedo(ctx_, first_sample, n_samples)); }
+    void reset_albedo() { check(pt_reset_albedo(ctx_)); }
+    std::vector<float> read_albedo() const { std::vector<float> v((size_t)width_ * height_ * 4); check(pt_read_albedo(ctx_, v.data())); return v; }
+    void denoise_albedo(uint32_t albedo_source = PT_ALBEDO_MEAN, const pt_denoise_params& p = pt_denoise_params{})
+    {
+        check(pt_denoise_albedo(ctx_, &p, albedo_source, nullptr));
+    }
     // caller-supplied rays (pt_integrate_rays): o, d 3 floats per ray (d is used as given), key and sample one word per ray naming each path's
     // stream.  Consecutive rays share a wave: order them coherently for speed; the results do not depend on the order.
     RayResults integrate_rays(const std::vector<float>& o, const std::vector<float>& d, const std::vector<uint32_t>& key, const std::vector<uint32_t>& sample,

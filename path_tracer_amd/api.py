@@ -41,9 +41,11 @@ EXPORTS = [
     "pt_integrate_rays", "pt_integrate_rays_device", "pt_bake_probes", "pt_probe_ray",
     "pt_set_instances", "pt_get_scene_info", "pt_read_guide_instances", "pt_frame_moving", "pt_post_motion",
     "pt_add_texture", "pt_set_material_texture", "pt_set_model_uvs", "pt_model_uvs", "pt_surface_colour", "pt_read_guide_albedo",
+    "pt_accumulate_albedo", "pt_reset_albedo", "pt_read_albedo", "pt_denoise_albedo", "pt_post_denoise_albedo",
 ]
 
 
+ALBEDO_GUIDE, ALBEDO_MEAN = 1, 2   # pt_denoise_albedo's albedo_source
 EV_MOUSE_MOTION, EV_KEY_W, EV_KEY_S, EV_KEY_A, EV_KEY_D = range(5)
 
 
@@ -226,6 +228,11 @@ def lib():
         L.pt_model_uvs.argtypes = [vp, C.c_int, vp, u32, C.POINTER(u32)]
         L.pt_surface_colour.argtypes = [vp, C.c_int, u32, vp, vp, vp, vp, vp]
         L.pt_read_guide_albedo.argtypes = [vp, vp]
+        L.pt_accumulate_albedo.argtypes = [vp, u32, u32]
+        L.pt_reset_albedo.argtypes = [vp]
+        L.pt_read_albedo.argtypes = [vp, vp]
+        L.pt_denoise_albedo.argtypes = [vp, C.POINTER(DenoiseParams), u32, vp]
+        L.pt_post_denoise_albedo.argtypes = [vp, u32, u32, C.POINTER(DenoiseParams), vp, vp, vp, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -678,6 +685,46 @@ class Renderer:
         out = np.zeros((h, w, 4), np.float32)
         prm = DenoiseParams(iterations, sigma_luminance, sigma_normal, sigma_plane)
         self._chk(self.L.pt_post_denoise(self.ctx, w, h, C.byref(prm), _p(accum), _p(position), _p(normal), _p(model), _p(q), _p(out)))
+        return out
+
+    # ---- mean albedo and the demodulated filter (pt_denoise_albedo)
+    def accumulate_albedo(self, first_sample: int, n_samples: int):
+        """add the albedo guide of samples [first_sample, first_sample + n_samples) of every local pixel to the mean-albedo sums, in sample
+        order; a miss adds (1, 1, 1).  Calls continue the sums until they go stale (whatever makes the guides stale) or reset_albedo"""
+        self._chk(self.L.pt_accumulate_albedo(self.ctx, first_sample, n_samples))
+
+    def reset_albedo(self):
+        self._chk(self.L.pt_reset_albedo(self.ctx))
+
+    def read_albedo(self):
+        """the mean-albedo sums (sum r, sum g, sum b, n), local rows x width x 4"""
+        out = np.zeros((len(self.local_rows()), self.cfg.width, 4), np.float32)
+        self._chk(self.L.pt_read_albedo(self.ctx, _p(out)))
+        return out
+
+    def denoise_albedo(self, source=ALBEDO_MEAN, iterations=0, sigma_luminance=0.0, sigma_normal=0, sigma_plane=0.0, download=True):
+        """denoise() on the accumulation divided by the albedo (source: ALBEDO_GUIDE, the last render_guides' albedo guide, or ALBEDO_MEAN,
+        the accumulate_albedo sums), the result multiplied by it again: texture detail survives the filter"""
+        prm = DenoiseParams(iterations, sigma_luminance, sigma_normal, sigma_plane)
+        out = np.zeros((len(self.local_rows()), self.cfg.width, 4), np.float32) if download else None
+        self._chk(self.L.pt_denoise_albedo(self.ctx, C.byref(prm), source, _p(out)))
+        return out
+
+    def post_denoise_albedo(self, accum, position, normal, model, albedo, sumsq=None, iterations=0, sigma_luminance=0.0, sigma_normal=0,
+                            sigma_plane=0.0):
+        """the demodulated filter's kernels on caller images: post_denoise's, and an h x w x 3 albedo"""
+        accum = np.ascontiguousarray(accum, np.float32)
+        h, w = accum.shape[:2]
+        position = np.ascontiguousarray(position, np.float32); normal = np.ascontiguousarray(normal, np.float32)
+        model = np.ascontiguousarray(model, np.uint32); albedo = np.ascontiguousarray(albedo, np.float32)
+        q = None if sumsq is None else np.ascontiguousarray(sumsq, np.float32)
+        if (position.size != h * w * 4 or normal.size != h * w * 3 or model.size != h * w or albedo.size != h * w * 3
+                or (q is not None and q.size != h * w)):
+            raise PtError(-1, f"post_denoise_albedo: guides are not those of a {w}x{h} image")
+        out = np.zeros((h, w, 4), np.float32)
+        prm = DenoiseParams(iterations, sigma_luminance, sigma_normal, sigma_plane)
+        self._chk(self.L.pt_post_denoise_albedo(self.ctx, w, h, C.byref(prm), _p(accum), _p(position), _p(normal), _p(model), _p(albedo), _p(q),
+                                                _p(out)))
         return out
 
     # ---- caller-supplied rays and irradiance probes

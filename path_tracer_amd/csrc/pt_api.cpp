@@ -177,6 +177,11 @@ struct pt_ctx
     uint32_t guides_sample = 0;
     uint64_t config_version = 0; // bumped by pt_set_config
     DevBuf d_dn_a, d_dn_b, d_dn_nv, d_dn_out;
+    // mean albedo (pt_accumulate_albedo): sum r, g, b | n per local pixel, traced through the guides' hook queue; stale when the guides would
+    // be.  d_dn_k: pt_denoise_albedo's per-pixel divisor.  Nothing is allocated until the first call.
+    DevBuf d_albedo_sum, d_dn_k;
+    bool albedo_valid = false;
+    uint64_t albedo_scene_version = 0, albedo_config_version = 0;
 
     // pt_frame_moving: the forward instance matrices, per model, of the build in force when the previous call returned PT_OK (the snapshot)
     // and the build it was taken from (a call on that very build has nothing to compare); the motion table and x_prev on the device.
@@ -1422,6 +1427,12 @@ int denoise_params(pt_ctx* c, const pt_denoise_params* p, DenoiseK& k)
     return PT_OK;
 }
 
+// the mean-albedo sums exist and belong to the camera, scene and configuration in force (what keeps the guides current)
+bool albedo_current(const pt_ctx* c)
+{
+    return c->albedo_valid && c->albedo_scene_version == c->scene_version && c->albedo_config_version == c->config_version;
+}
+
 // the filter's scratch images for px pixels
 int denoise_scratch(pt_ctx* c, size_t px)
 {
@@ -2249,6 +2260,45 @@ int pt_post_rgb8(pt_ctx* c, uint32_t w, uint32_t h, const float* accum, uint8_t*
 } // extern "C"
 
 namespace {
+// the camera rays of `sample` of every local pixel through the hook queue: their closest hits, by local pixel, in d_ghits (enqueued, not waited for)
+int guide_trace(pt_ctx* c, uint32_t sample)
+{
+    const uint32_t px = c->local_pixels;
+    const pt_config& g = c->cfg;
+    RenderParams rp{};
+    rp.width = g.width;
+    rp.height = g.height;
+    rp.local_rows = (uint32_t)c->rows.size();
+    rp.local_pixels = px;
+    rp.rank = g.rank;
+    rp.world_size = g.world_size;
+    rp.strip_rows = g.strip_rows;
+    rp.first_sample = sample;
+    rp.n_sobol = g.n_sobol;
+    rp.seed = g.seed;
+    rp.div_width = fastdiv_make(rp.width);
+    rp.div_strip_rows = fastdiv_make(rp.strip_rows);
+    const CameraView cam = c->scene.camera_view();
+    const LensView lens = c->scene.lens_view();
+    const RayQueue q{(f4*)c->d_gray_a.p, (f4*)c->d_gray_b.p};
+    uint32_t* head = (uint32_t*)c->d_ghead.p;
+    HIPCHK(c, hipMemsetAsync(head, 0, c->d_ghead.bytes, c->stream));
+    launch_guide_rays(c->stream, rp, cam, lens, q, head);
+    // (an empty world: every ray misses)
+    if (c->sv.world_root == MISS_ID) HIPCHK(c, hipMemsetAsync(c->d_ghits.p, 0xff, (size_t)px * 16, c->stream));
+    else launch_trace_rays_closest(c->stream, trace_launch(c), c->sv.world_root, q, px, head, (f4*)c->d_ghits.p);
+    return PT_OK;
+}
+// the hook queue, its hits and its claim cursors for the local pixels
+int guide_scratch(pt_ctx* c)
+{
+    int r;
+    const size_t n = std::max<uint32_t>(c->local_pixels, 1);
+    for (DevBuf* b : {&c->d_gray_a, &c->d_gray_b, &c->d_ghits})
+        if ((r = dev_alloc(c, *b, n * 16))) return r;
+    return dev_alloc(c, c->d_ghead, ((size_t)32 + kHeadWordsPerQueue) * 4);
+}
+
 int render_guides_locked(pt_ctx* c, uint32_t sample)
 {
     if (!c->scene.built) return fail(c, PT_ERR_STATE, "pt_build has not been called");
@@ -2257,36 +2307,16 @@ int render_guides_locked(pt_ctx* c, uint32_t sample)
     if ((r = upload_scene(c))) return r;
     const uint32_t px = c->local_pixels;
     const size_t n = std::max<uint32_t>(px, 1);
-    for (DevBuf* b : {&c->d_gpos, &c->d_gnrm, &c->d_gray_a, &c->d_gray_b, &c->d_ghits})
+    for (DevBuf* b : {&c->d_gpos, &c->d_gnrm, &c->d_galbedo})
         if ((r = dev_alloc(c, *b, n * 16))) return r;
-    if ((r = dev_alloc(c, c->d_galbedo, n * 16))) return r;
-    if ((r = dev_alloc(c, c->d_gmodel, n * 4)) || (r = dev_alloc(c, c->d_ginst, n * 4)) || (r = dev_alloc(c, c->d_ghead, ((size_t)32 + kHeadWordsPerQueue) * 4))) return r;
+    if ((r = dev_alloc(c, c->d_gmodel, n * 4)) || (r = dev_alloc(c, c->d_ginst, n * 4)) || (r = guide_scratch(c))) return r;
     c->guides_valid = false;
     if (px)
     {
-        const pt_config& g = c->cfg;
-        RenderParams rp{};
-        rp.width = g.width;
-        rp.height = g.height;
-        rp.local_rows = (uint32_t)c->rows.size();
-        rp.local_pixels = px;
-        rp.rank = g.rank;
-        rp.world_size = g.world_size;
-        rp.strip_rows = g.strip_rows;
-        rp.first_sample = sample;
-        rp.n_sobol = g.n_sobol;
-        rp.seed = g.seed;
-        rp.div_width = fastdiv_make(rp.width);
-        rp.div_strip_rows = fastdiv_make(rp.strip_rows);
+        if ((r = guide_trace(c, sample))) return r;
         const CameraView cam = c->scene.camera_view();
         const LensView lens = c->scene.lens_view();
         const RayQueue q{(f4*)c->d_gray_a.p, (f4*)c->d_gray_b.p};
-        uint32_t* head = (uint32_t*)c->d_ghead.p;
-        HIPCHK(c, hipMemsetAsync(head, 0, c->d_ghead.bytes, c->stream));
-        launch_guide_rays(c->stream, rp, cam, lens, q, head);
-        // (an empty world: every ray misses)
-        if (c->sv.world_root == MISS_ID) HIPCHK(c, hipMemsetAsync(c->d_ghits.p, 0xff, (size_t)px * 16, c->stream));
-        else launch_trace_rays_closest(c->stream, trace_launch(c), c->sv.world_root, q, px, head, (f4*)c->d_ghits.p);
         launch_guide_resolve(c->stream, c->sv, px, cam, lens, q, (const f4*)c->d_ghits.p, (f4*)c->d_gpos.p, (f4*)c->d_gnrm.p, (uint32_t*)c->d_gmodel.p,
                              (uint32_t*)c->d_ginst.p);
         launch_guide_albedo(c->stream, c->sv, c->tex, px, (const f4*)c->d_ghits.p, (f4*)c->d_galbedo.p);
@@ -2415,6 +2445,124 @@ int pt_post_denoise(pt_ctx* c, uint32_t w, uint32_t h, const pt_denoise_params* 
     if (t.err) return t.err;
     if ((r = denoise_scratch(c, px))) return r;
     launch_denoise(c->stream, (int)w, (int)h, k, da, dq, dp, dn, dm, (f4*)c->d_dn_a.p, (f4*)c->d_dn_b.p, (f4*)c->d_dn_nv.p, dout);
+    HIPCHK(c, hipGetLastError());
+    return t.download(out, dout, px * 16);
+}
+
+// ---- mean albedo and the demodulated filter
+int pt_accumulate_albedo(pt_ctx* c, uint32_t first_sample, uint32_t n_samples)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->scene.built) return fail(c, PT_ERR_STATE, "pt_build has not been called");
+    if (!c->scene.camera.set) return fail(c, PT_ERR_STATE, "pt_set_camera has not been called");
+    if (n_samples == 0u) return fail(c, PT_ERR_ARG, "pt_accumulate_albedo: n_samples must be at least 1");
+    if ((uint64_t)first_sample + n_samples > 0x100000000ull) return fail(c, PT_ERR_ARG, "pt_accumulate_albedo: first_sample + n_samples exceeds 2^32");
+    int r;
+    if ((r = upload_scene(c))) return r;
+    const uint32_t px = c->local_pixels;
+    const size_t n = std::max<uint32_t>(px, 1);
+    if ((r = guide_scratch(c)) || (r = dev_alloc(c, c->d_albedo_sum, n * 16))) return r;
+    const bool fresh = !albedo_current(c);
+    c->albedo_valid = false; // a failure below leaves no sum
+    if (fresh) HIPCHK(c, hipMemsetAsync(c->d_albedo_sum.p, 0, n * 16, c->stream));
+    if (px)
+    {
+        for (uint32_t k = 0; k < n_samples; ++k)
+        {
+            if ((r = guide_trace(c, first_sample + k))) return r;
+            launch_albedo_accumulate(c->stream, c->sv, c->tex, px, (const f4*)c->d_ghits.p, (f4*)c->d_albedo_sum.p);
+        }
+        HIPCHK(c, hipGetLastError());
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->albedo_valid = true;
+    c->albedo_scene_version = c->scene_version;
+    c->albedo_config_version = c->config_version;
+    return PT_OK;
+}
+
+int pt_reset_albedo(pt_ctx* c)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    c->albedo_valid = false;
+    return PT_OK;
+}
+
+int pt_read_albedo(pt_ctx* c, float* rgbn)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!albedo_current(c)) return fail(c, PT_ERR_STATE, "no mean albedo (none accumulated, reset, or stale): pt_accumulate_albedo first");
+    const size_t px = c->local_pixels;
+    if (!px || !rgbn) return PT_OK;
+    HIPCHK(c, hipMemcpyAsync(rgbn, c->d_albedo_sum.p, px * 16, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PT_OK;
+}
+
+int pt_denoise_albedo(pt_ctx* c, const pt_denoise_params* p, uint32_t albedo_source, float* rgba)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    DenoiseK k{};
+    int r;
+    if ((r = denoise_params(c, p, k))) return r;
+    if (albedo_source != PT_ALBEDO_GUIDE && albedo_source != PT_ALBEDO_MEAN)
+        return fail(c, PT_ERR_ARG, "pt_denoise_albedo: albedo_source must be PT_ALBEDO_GUIDE or PT_ALBEDO_MEAN");
+    if (c->cfg.world_size != 1) return fail(c, PT_ERR_STATE, "pt_denoise_albedo needs the whole frame on one rank (the neighbourhoods cross row strips)");
+    if (!c->guides_valid) return fail(c, PT_ERR_STATE, "no guides: pt_render_guides first");
+    if (c->guides_scene_version != c->scene_version || c->guides_config_version != c->config_version)
+        return fail(c, PT_ERR_STATE, "the guides are stale (camera, scene, environment or configuration changed since pt_render_guides)");
+    if (!c->d_accum.p) return fail(c, PT_ERR_STATE, "nothing has been accumulated");
+    const bool mean = albedo_source == PT_ALBEDO_MEAN;
+    if (mean && !albedo_current(c)) return fail(c, PT_ERR_STATE, "no mean albedo (none accumulated, reset, or stale): pt_accumulate_albedo first");
+    if ((r = ensure_device(c))) return r;
+    const size_t px = c->local_pixels;
+    if ((r = denoise_scratch(c, px)) || (r = dev_alloc(c, c->d_dn_k, px * 16)) || (r = dev_alloc(c, c->d_dn_out, px * 16))) return r;
+    const bool moments = (c->cfg.flags & PT_FLAG_ADAPTIVE) && c->moments_valid && c->d_moments.p;
+    launch_denoise_albedo(c->stream, (int)c->cfg.width, (int)c->cfg.height, k, (const f4*)c->d_accum.p, moments ? (const float*)c->d_moments.p : nullptr,
+                          (const f4*)c->d_gpos.p, (const f4*)c->d_gnrm.p, (const uint32_t*)c->d_gmodel.p,
+                          (const f4*)(mean ? c->d_albedo_sum.p : c->d_galbedo.p), mean, (f4*)c->d_dn_a.p, (f4*)c->d_dn_b.p, (f4*)c->d_dn_nv.p,
+                          (f4*)c->d_dn_k.p, (f4*)c->d_dn_out.p);
+    HIPCHK(c, hipGetLastError());
+    if (rgba) HIPCHK(c, hipMemcpyAsync(rgba, c->d_dn_out.p, px * 16, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->denoised_valid = true;
+    return PT_OK;
+}
+
+int pt_post_denoise_albedo(pt_ctx* c, uint32_t w, uint32_t h, const pt_denoise_params* p, const float* accum, const float* position, const float* normal,
+                           const uint32_t* model, const float* albedo, const float* sumsq, float* out)
+{
+    if (!c) return PT_ERR_ARG;
+    if (!accum || !position || !normal || !model || !albedo || !out || !w || !h) return fail(c, PT_ERR_ARG, "pt_post_denoise_albedo: null image or empty size");
+    if ((uint64_t)w * h > 0x7fffffffull) return fail(c, PT_ERR_ARG, "pt_post_denoise_albedo: image too large");
+    std::lock_guard<std::mutex> lk(c->mu);
+    DenoiseK k{};
+    int r;
+    if ((r = denoise_params(c, p, k))) return r;
+    const size_t px = (size_t)w * h;
+    for (size_t i = 0; i < 3 * px; ++i)
+        if (!(albedo[i] >= 0.0f) || !std::isfinite(albedo[i]))
+            return fail(c, PT_ERR_ARG, "pt_post_denoise_albedo: pixel " + std::to_string(i / 3) + " has an albedo component that is negative or not finite");
+    if ((r = ensure_device(c))) return r;
+    Staging t(c);
+    std::vector<f4> nr(px), al(px);
+    for (size_t i = 0; i < px; ++i) nr[i] = f4{normal[3 * i], normal[3 * i + 1], normal[3 * i + 2], 0.0f};
+    for (size_t i = 0; i < px; ++i) al[i] = f4{albedo[3 * i], albedo[3 * i + 1], albedo[3 * i + 2], 0.0f};
+    const f4* da = (const f4*)t.in(accum, px * 16);
+    const f4* dp = (const f4*)t.in(position, px * 16);
+    const f4* dn = (const f4*)t.in(nr.data(), px * 16);
+    const f4* dal = (const f4*)t.in(al.data(), px * 16);
+    const uint32_t* dm = (const uint32_t*)t.in(model, px * 4);
+    const float* dq = sumsq ? (const float*)t.in(sumsq, px * 4) : nullptr;
+    f4* dout = (f4*)t.out(px * 16);
+    if (t.err) return t.err;
+    if ((r = denoise_scratch(c, px)) || (r = dev_alloc(c, c->d_dn_k, px * 16))) return r;
+    launch_denoise_albedo(c->stream, (int)w, (int)h, k, da, dq, dp, dn, dm, dal, false, (f4*)c->d_dn_a.p, (f4*)c->d_dn_b.p, (f4*)c->d_dn_nv.p,
+                          (f4*)c->d_dn_k.p, dout);
     HIPCHK(c, hipGetLastError());
     return t.download(out, dout, px * 16);
 }

@@ -156,6 +156,10 @@ struct DenoiseK
 // scratch images cv_a, cv_b (colour | variance) and nv (normal | valid) and writes the result (c, 1) or (0, 0, 0, 0) to out
 void launch_denoise(hipStream_t s, int w, int h, const DenoiseK& p, const f4* accum, const float* moments, const f4* position, const f4* normal,
                     const uint32_t* model, f4* cv_a, f4* cv_b, f4* nv, f4* out);
+// pt_denoise_albedo / pt_post_denoise_albedo: the same filter on the accumulation divided by the albedo (xyz per pixel; albedo_is_sum: the
+// mean-albedo sums, xyz / w), the last level multiplying it back.  kd: one more scratch image, the per-pixel divisor
+void launch_denoise_albedo(hipStream_t s, int w, int h, const DenoiseK& p, const f4* accum, const float* moments, const f4* position, const f4* normal,
+                           const uint32_t* model, const f4* albedo, bool albedo_is_sum, f4* cv_a, f4* cv_b, f4* nv, f4* kd, f4* out);
 // the camera rays of sample rp.first_sample of every local pixel into a hook queue (ray index = local pixel), n_and_heads[0] <- local pixels
 void launch_guide_rays(hipStream_t s, const RenderParams& rp, const CameraView& cam, const LensView& lens, RayQueue rq, uint32_t* n_and_heads);
 // their launch_trace_rays_closest hits -> position, normal, model guides
@@ -164,6 +168,8 @@ void launch_guide_resolve(hipStream_t s, const SceneView& sv, uint32_t n, const 
 // ... -> the albedo guide: the surface colour at the hit (an emissive hit: its emitted colour), (0, 0, 0) for a miss.  A launch of its own behind
 // the resolve, whose kernels and four guides stay what they were.  tex: the scene's texture view (all null for an untextured scene)
 void launch_guide_albedo(hipStream_t s, const SceneView& sv, const TexView& tex, uint32_t n, const f4* hits, f4* albedo);
+// pt_accumulate_albedo: sum[i] += (that sample's albedo guide, 1), with (1, 1, 1) for a miss; one thread per pixel, no atomics
+void launch_albedo_accumulate(hipStream_t s, const SceneView& sv, const TexView& tex, uint32_t n, const f4* hits, f4* sum);
 // unit hook (pt_surface_colour): rgb[i] <- surface colour of world instance[i], leaf-order triangle tri[i] at barycentrics u[i], v[i]
 void launch_surface_colour(hipStream_t s, const SceneView& sv, const TexView& tex, uint32_t n, const uint32_t* instance, const uint32_t* tri, const float* u,
                            const float* v, float* rgb);

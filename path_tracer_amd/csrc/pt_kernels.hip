@@ -2894,6 +2894,20 @@ __global__ void __launch_bounds__(256) k_guide_albedo(const SceneView sv, const 
     if (hid != MISS_ID) c = surface_colour_at(sv, tex, hid >> sv.prim_bits, hid & ((1u << sv.prim_bits) - 1u), hit.y, hit.z);
     albedo[i] = f4{c.x, c.y, c.z, 0.0f};
 }
+// pt_accumulate_albedo: the albedo guide of one more sample added to the pixel's sums (r, g, b, n), one binary32 add per component; a miss adds
+// (1, 1, 1), so that the background passes the demodulation undivided.  One thread owns a pixel and launches follow each other in sample
+// order on one stream: no atomics, and the order of a pixel's adds is the order of its samples.
+__global__ void __launch_bounds__(256) k_albedo_accumulate(const SceneView sv, const TexView tex, const uint32_t n, const f4* __restrict__ hits, f4* __restrict__ sum)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const f4 hit = hits[i];
+    const uint32_t hid = asu(hit.w);
+    f3 c{1.0f, 1.0f, 1.0f};
+    if (hid != MISS_ID) c = surface_colour_at(sv, tex, hid >> sv.prim_bits, hid & ((1u << sv.prim_bits) - 1u), hit.y, hit.z);
+    const f4 s = sum[i];
+    sum[i] = f4{s.x + c.x, s.y + c.y, s.z + c.z, s.w + 1.0f};
+}
 __global__ void __launch_bounds__(256) k_surface_colour(const SceneView sv, const TexView tex, const uint32_t n, const uint32_t* __restrict__ instance,
                                                         const uint32_t* __restrict__ tri, const float* __restrict__ u, const float* __restrict__ v,
                                                         float* __restrict__ rgb)
@@ -3325,6 +3339,11 @@ void launch_guide_albedo(hipStream_t s, const SceneView& sv, const TexView& tex,
 {
     if (n == 0u) return;
     hipLaunchKernelGGL(k_guide_albedo, dim3((n + 255u) / 256u), dim3(256), 0, s, sv, tex, n, hits, albedo);
+}
+void launch_albedo_accumulate(hipStream_t s, const SceneView& sv, const TexView& tex, uint32_t n, const f4* hits, f4* sum)
+{
+    if (n == 0u) return;
+    hipLaunchKernelGGL(k_albedo_accumulate, dim3((n + 255u) / 256u), dim3(256), 0, s, sv, tex, n, hits, sum);
 }
 void launch_surface_colour(hipStream_t s, const SceneView& sv, const TexView& tex, uint32_t n, const uint32_t* instance, const uint32_t* tri, const float* u,
                            const float* v, float* rgb)

@@ -312,6 +312,50 @@ __global__ void __launch_bounds__(256) k_dn_prep(uint32_t n, const f4* __restric
     nv[i] = f4{nr.x, nr.y, nr.z, 1.0f};
 }
 
+// pt_denoise_albedo's prep: the same with the colour divided by the albedo first.  A = the albedo image (MEAN: the sums' S.rgb / S.w);
+// k = (1, 1, 1) for a miss, else A floored at 2^-10 per channel; colour c' = (acc / k) / acc.w; with moments the variance e2 of the modulated
+// colour scaled by r * r, r = l(c') / l(c) (1 where l(c) is not positive), which keeps the relative error.  k goes to kd for the last level.
+constexpr float kAlbedoFloor = 0x1p-10f;
+template <bool MEAN>
+__global__ void __launch_bounds__(256) k_dn_prep_albedo(uint32_t n, const f4* __restrict__ accum, const float* __restrict__ moments, const f4* __restrict__ normal,
+                                                        const uint32_t* __restrict__ model, const f4* __restrict__ albedo, f4* __restrict__ cv,
+                                                        f4* __restrict__ nv, f4* __restrict__ kd)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const f4 a = accum[i];
+    if (a.w == 0.0f)
+    {
+        cv[i] = f4{0.0f, 0.0f, 0.0f, 0.0f};
+        nv[i] = f4{0.0f, 0.0f, 0.0f, 0.0f};
+        kd[i] = f4{0.0f, 0.0f, 0.0f, 0.0f};
+        return;
+    }
+    f4 k{1.0f, 1.0f, 1.0f, 0.0f};
+    if (model[i] != MISS_ID)
+    {
+        f4 A = albedo[i];
+        if (MEAN) A = f4{A.x / A.w, A.y / A.w, A.z / A.w, 0.0f};
+        k = f4{A.x > kAlbedoFloor ? A.x : kAlbedoFloor, A.y > kAlbedoFloor ? A.y : kAlbedoFloor, A.z > kAlbedoFloor ? A.z : kAlbedoFloor, 0.0f};
+    }
+    const f4 cd{(a.x / k.x) / a.w, (a.y / k.y) / a.w, (a.z / k.z) / a.w, 0.0f};
+    float var = 0.0f;
+    if (moments)
+    {
+        const float m = dn_lum(a) / a.w;
+        float v = moments[i] / a.w - m * m;
+        if (!(v > 0.0f)) v = 0.0f;
+        const float e2 = v / a.w;
+        const float lc = dn_lum(f4{a.x / a.w, a.y / a.w, a.z / a.w, 0.0f});
+        const float r = lc > 0.0f ? dn_lum(cd) / lc : 1.0f;
+        var = (e2 * r) * r;
+    }
+    const f4 nr = normal[i];
+    cv[i] = f4{cd.x, cd.y, cd.z, var};
+    nv[i] = f4{nr.x, nr.y, nr.z, 1.0f};
+    kd[i] = k;
+}
+
 // variance of l over the 7 x 7 neighbourhood, taps weighted by the model, normal and plane terms (no luminance term)
 __global__ void __launch_bounds__(256) k_dn_spatial_var(int w, int h, const DenoiseK p, const f4* __restrict__ cv_in, const f4* __restrict__ pos,
                                                         const f4* __restrict__ nv, const uint32_t* __restrict__ model, f4* __restrict__ cv_out)
@@ -354,10 +398,12 @@ __global__ void __launch_bounds__(256) k_dn_spatial_var(int w, int h, const Deno
 }
 
 // one a-trous level, step s: g = 3 x 3 binomial blur of the variance, then the 5 x 5 B3-spline taps p + s (dx, dy) with edge-stopping weights.
-// FINAL writes the result (c', 1) / (0, 0, 0, 0) instead of (c', var')
-template <bool FINAL>
+// FINAL writes the result (c', 1) / (0, 0, 0, 0) instead of (c', var'); REMOD (pt_denoise_albedo's last level, FINAL) multiplies that result
+// by the divisor k the prep kernel kept in kmul, per channel (kmul is not read otherwise)
+template <bool FINAL, bool REMOD = false>
 __global__ void __launch_bounds__(256) k_dn_level(int w, int h, int s, const DenoiseK p, const f4* __restrict__ cv_in, const f4* __restrict__ pos,
-                                                  const f4* __restrict__ nv, const uint32_t* __restrict__ model, f4* __restrict__ cv_out)
+                                                  const f4* __restrict__ nv, const uint32_t* __restrict__ model, f4* __restrict__ cv_out,
+                                                  const f4* __restrict__ kmul)
 {
     const int x = blockIdx.x * 16 + threadIdx.x, y = blockIdx.y * 16 + threadIdx.y;
     if (x >= w || y >= h) return;
@@ -417,17 +463,21 @@ __global__ void __launch_bounds__(256) k_dn_level(int w, int h, int s, const Den
         }
     }
     const f4 c{sr / sw, sgc / sw, sb / sw, 0.0f};
-    cv_out[i] = FINAL ? f4{c.x, c.y, c.z, 1.0f} : f4{c.x, c.y, c.z, sv / (sw * sw)};
+    static_assert(FINAL || !REMOD, "");
+    if (REMOD)
+    {
+        const f4 k = kmul[i];
+        cv_out[i] = f4{c.x * k.x, c.y * k.y, c.z * k.z, 1.0f};
+    }
+    else cv_out[i] = FINAL ? f4{c.x, c.y, c.z, 1.0f} : f4{c.x, c.y, c.z, sv / (sw * sw)};
 }
 
-} // namespace
-
-void launch_denoise(hipStream_t s, int w, int h, const DenoiseK& p, const f4* accum, const float* moments, const f4* position, const f4* normal,
-                    const uint32_t* model, f4* cv_a, f4* cv_b, f4* nv, f4* out)
+// the spatial variance where there are no moments, then the levels, on the prepared (colour | variance) in cv_a; kmul: the last level
+// multiplies its result by it (pt_denoise_albedo), null: it does not
+void denoise_levels(hipStream_t s, int w, int h, const DenoiseK& p, bool moments, const f4* position, const uint32_t* model, f4* cv_a, f4* cv_b, f4* nv,
+                    const f4* kmul, f4* out)
 {
-    const uint32_t n = (uint32_t)w * (uint32_t)h;
     const dim3 tile(16, 16), grid((w + 15) / 16, (h + 15) / 16);
-    hipLaunchKernelGGL(k_dn_prep, dim3((n + 255u) / 256u), dim3(256), 0, s, n, accum, moments, normal, cv_a, nv);
     f4* cur = cv_a;
     f4* other = cv_b;
     if (!moments)
@@ -439,13 +489,34 @@ void launch_denoise(hipStream_t s, int w, int h, const DenoiseK& p, const f4* ac
     {
         const int step = 1 << it;
         if (it + 1u == p.iterations)
-            hipLaunchKernelGGL(k_dn_level<true>, grid, tile, 0, s, w, h, step, p, (const f4*)cur, position, (const f4*)nv, model, out);
+        {
+            if (kmul) hipLaunchKernelGGL((k_dn_level<true, true>), grid, tile, 0, s, w, h, step, p, (const f4*)cur, position, (const f4*)nv, model, out, kmul);
+            else hipLaunchKernelGGL(k_dn_level<true>, grid, tile, 0, s, w, h, step, p, (const f4*)cur, position, (const f4*)nv, model, out, kmul);
+        }
         else
         {
-            hipLaunchKernelGGL(k_dn_level<false>, grid, tile, 0, s, w, h, step, p, (const f4*)cur, position, (const f4*)nv, model, other);
+            hipLaunchKernelGGL(k_dn_level<false>, grid, tile, 0, s, w, h, step, p, (const f4*)cur, position, (const f4*)nv, model, other, (const f4*)nullptr);
             std::swap(cur, other);
         }
     }
+}
+} // namespace
+
+void launch_denoise(hipStream_t s, int w, int h, const DenoiseK& p, const f4* accum, const float* moments, const f4* position, const f4* normal,
+                    const uint32_t* model, f4* cv_a, f4* cv_b, f4* nv, f4* out)
+{
+    const uint32_t n = (uint32_t)w * (uint32_t)h;
+    hipLaunchKernelGGL(k_dn_prep, dim3((n + 255u) / 256u), dim3(256), 0, s, n, accum, moments, normal, cv_a, nv);
+    denoise_levels(s, w, h, p, moments != nullptr, position, model, cv_a, cv_b, nv, nullptr, out);
+}
+
+void launch_denoise_albedo(hipStream_t s, int w, int h, const DenoiseK& p, const f4* accum, const float* moments, const f4* position, const f4* normal,
+                           const uint32_t* model, const f4* albedo, bool albedo_is_sum, f4* cv_a, f4* cv_b, f4* nv, f4* kd, f4* out)
+{
+    const uint32_t n = (uint32_t)w * (uint32_t)h;
+    if (albedo_is_sum) hipLaunchKernelGGL(k_dn_prep_albedo<true>, dim3((n + 255u) / 256u), dim3(256), 0, s, n, accum, moments, normal, model, albedo, cv_a, nv, kd);
+    else hipLaunchKernelGGL(k_dn_prep_albedo<false>, dim3((n + 255u) / 256u), dim3(256), 0, s, n, accum, moments, normal, model, albedo, cv_a, nv, kd);
+    denoise_levels(s, w, h, p, moments != nullptr, position, model, cv_a, cv_b, nv, (const f4*)kd, out);
 }
 
 void launch_post_deinterleave(hipStream_t s, uint32_t w, uint32_t h, uint32_t world, uint32_t strip, uint32_t pad_rows, const f4* parts, f4* full)

@@ -5,7 +5,10 @@ both variance sources (spatial variance; moments of PT_FLAG_ADAPTIVE), in linear
 what pt_present shows).  The noisy frames use samples after the reference's, so the two are independent.
 Timing: wall clock of the blocking calls at the given size (median of --reps), guides and the filter separately.
 
-    python tools/denoise_bench.py [--size 256] [--ref-spp 4096] [--spp 1,4,16,64] [--width 1920 --height 1080 --reps 20] [--out file.json]
+--albedo adds the demodulated filter (pt_denoise_albedo, profiles/r13_denoise_albedo.md): its RMSE with the albedo guide and with the mean
+albedo beside pt_denoise's, its cost beside pt_denoise's, and the cost of one sample of pt_accumulate_albedo beside one pt_render_guides.
+
+    python tools/denoise_bench.py [--albedo] [--size 256] [--ref-spp 4096] [--spp 1,4,16,64] [--width 1920 --height 1080 --reps 20] [--out file.json]
 """
 import argparse
 import json
@@ -22,7 +25,7 @@ def rmse(a, b):
     return float(np.sqrt(np.mean((a[..., :3].astype(np.float64) - b[..., :3].astype(np.float64)) ** 2)))
 
 
-def quality(api, scenes, name, size, ref_spp, spps, depth):
+def quality(api, scenes, name, size, ref_spp, spps, depth, albedo=False):
     sc = {"cornell": scenes.cornell_box, "mixed": scenes.cornell_mixed}[name](size, size)
     ref = api.Renderer(sc, size, size, max_bounces=depth)
     racc, _, _ = ref.render(0, ref_spp, want_position=False)
@@ -40,6 +43,12 @@ def quality(api, scenes, name, size, ref_spp, spps, depth):
                        display_rmse_noisy=rmse(r.post_tonemap(acc), ref_disp), display_rmse_denoised=rmse(r.post_tonemap(den), ref_disp))
             row["ratio"] = row["rmse_denoised"] / row["rmse_noisy"]
             row["display_ratio"] = row["display_rmse_denoised"] / row["display_rmse_noisy"]
+            if albedo:
+                r.accumulate_albedo(ref_spp, spp)
+                for key, src in (("guide", api.ALBEDO_GUIDE), ("mean", api.ALBEDO_MEAN)):
+                    dal = r.denoise_albedo(src)
+                    row[f"rmse_albedo_{key}"] = rmse(dal, ref_mean)
+                    row[f"display_rmse_albedo_{key}"] = rmse(r.post_tonemap(dal), ref_disp)
             print(json.dumps(row), flush=True)
             rows.append(row)
             r.close()
@@ -47,7 +56,7 @@ def quality(api, scenes, name, size, ref_spp, spps, depth):
     return rows
 
 
-def timing(api, scenes, w, h, reps, depth):
+def timing(api, scenes, w, h, reps, depth, albedo=False):
     out = {}
     for flags, source in ((0, "spatial"), (api.FLAG_ADAPTIVE, "moments")):
         r = api.Renderer(scenes.cornell_box(w, h), w, h, max_bounces=depth, flags=flags)
@@ -59,6 +68,16 @@ def timing(api, scenes, w, h, reps, depth):
             if k >= 2:
                 tg.append(t1 - t0); td.append(t2 - t1)
         out[source] = dict(ms_guides=1e3 * float(np.median(tg)), ms_denoise=1e3 * float(np.median(td)))
+        if albedo:
+            ta, tdg, tdm = [], [], []
+            for k in range(reps + 2):
+                t0 = time.perf_counter(); r.accumulate_albedo(4 * k, 4); t1 = time.perf_counter()
+                r.denoise_albedo(api.ALBEDO_GUIDE, download=False); t2 = time.perf_counter()
+                r.denoise_albedo(api.ALBEDO_MEAN, download=False); t3 = time.perf_counter()
+                if k >= 2:
+                    ta.append((t1 - t0) / 4); tdg.append(t2 - t1); tdm.append(t3 - t2)
+            out[source].update(ms_accumulate_albedo_per_sample=1e3 * float(np.median(ta)), ms_denoise_albedo_guide=1e3 * float(np.median(tdg)),
+                               ms_denoise_albedo_mean=1e3 * float(np.median(tdm)))
         r.close()
     row = dict(width=w, height=h, reps=reps, **{f"{k}_{s}": v for s, d in out.items() for k, v in d.items()})
     print(json.dumps(row), flush=True)
@@ -76,15 +95,16 @@ def main():
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--no-quality", action="store_true")
+    ap.add_argument("--albedo", action="store_true", help="also measure pt_accumulate_albedo and pt_denoise_albedo")
     ap.add_argument("--out")
     a = ap.parse_args()
     from path_tracer_amd import api, scenes
     res = dict(quality=[], timing=None)
     if not a.no_quality:
         for name in a.scenes.split(","):
-            res["quality"] += quality(api, scenes, name, a.size, a.ref_spp, [int(s) for s in a.spp.split(",")], a.bounces)
+            res["quality"] += quality(api, scenes, name, a.size, a.ref_spp, [int(s) for s in a.spp.split(",")], a.bounces, a.albedo)
     if a.reps > 0:
-        res["timing"] = timing(api, scenes, a.width, a.height, a.reps, a.bounces)
+        res["timing"] = timing(api, scenes, a.width, a.height, a.reps, a.bounces, a.albedo)
     if a.out:
         with open(a.out, "w") as f:
             json.dump(res, f, indent=1)
