@@ -8,6 +8,8 @@
 //       without the temporal pass; the frame's state (accumulation, first-hit position, id history) can be saved and picked up by another
 //       process: a long render stopped and continued (pt_read_frame / pt_write_accumulation)
 //   examples/headless ... --aperture A --focus F   thin lens of diameter A focused at distance F (default: the reference's pinhole, 0 and 950)
+//   examples/headless ... --projection panorama[:SX:SY] | ortho:HEIGHT   a panoramic camera covering SX x SY degrees (default 360 x 180) or an orthographic one
+//                                          whose view volume is HEIGHT world units high (pt_set_projection); not with --aperture, --move or --slide
 //   examples/headless ... --slide DX DZ   frame f >= 1 first moves the short box to the translation (f * DX, 0, f * DZ) (pt_set_instances + pt_build:
 //                                          the BLASes are kept, the resident scene is patched) and the loop drives frame_moving instead of frame
 //   examples/headless ... --denoise den.png   also writes the final frame through the edge-aware denoiser (guides of the last frame's sample)
@@ -44,6 +46,7 @@ int main(int argc, char** argv)
     float aperture = 0.0f, focus = 950.0f; // main.rs:127's values: a pinhole
     uint32_t probes[3] = {0, 0, 0}, probe_spp = 0, checker = 0;
     std::string probes_out = "";
+    pt_projection projection{}; // PT_PROJ_PERSPECTIVE
     for (int i = 1; i < argc; ++i)
     {
         const std::string a = argv[i];
@@ -63,6 +66,16 @@ int main(int argc, char** argv)
         else if (a == "--slide") { slide = true; slide_dx = (float)std::atof(next("--slide")); slide_dz = (float)std::atof(next("--slide")); }
         else if (a == "--aperture") aperture = (float)std::atof(next("--aperture"));
         else if (a == "--focus") focus = (float)std::atof(next("--focus"));
+        else if (a == "--projection")
+        {
+            const std::string v = next("--projection");
+            float x = 0.0f, y = 0.0f;
+            if (v == "perspective") projection = pt_projection{};
+            else if (v == "panorama") { projection = pt_projection{}; projection.kind = PT_PROJ_PANORAMA; }
+            else if (std::sscanf(v.c_str(), "panorama:%f:%f", &x, &y) == 2) { projection = pt_projection{}; projection.kind = PT_PROJ_PANORAMA; projection.span_x_deg = x; projection.span_y_deg = y; }
+            else if (std::sscanf(v.c_str(), "ortho:%f", &x) == 1) { projection = pt_projection{}; projection.kind = PT_PROJ_ORTHOGRAPHIC; projection.ortho_height = x; }
+            else { std::fprintf(stderr, "--projection takes perspective, panorama, panorama:SX:SY or ortho:HEIGHT\n"); return 2; }
+        }
         else if (a == "--gpus") gpus = (uint32_t)std::atoi(next("--gpus"));
         else if (a == "--checker") checker = (uint32_t)std::atoi(next("--checker"));
         else if (a == "--spp") spp = (uint32_t)std::atoi(next("--spp"));
@@ -82,7 +95,7 @@ int main(int argc, char** argv)
         }
         else if (a == "--help" || a == "-h")
         {
-            std::printf("usage: %s [--width W] [--height H] [--frames N] [--bounces B] [--move] [--slide DX DZ] [--models DIR] [--out file.png] [--denoise file.png] [--denoise-albedo file.png] [--aperture A --focus F] [--bake-probes NX NY NZ SPP file.txt] [--checker N]\n", argv[0]);
+            std::printf("usage: %s [--width W] [--height H] [--frames N] [--bounces B] [--move] [--slide DX DZ] [--models DIR] [--out file.png] [--denoise file.png] [--denoise-albedo file.png] [--aperture A --focus F] [--projection panorama[:SX:SY]|ortho:HEIGHT] [--bake-probes NX NY NZ SPP file.txt] [--checker N]\n", argv[0]);
             return 0;
         }
         else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
@@ -122,6 +135,7 @@ int main(int argc, char** argv)
             // several GPUs, one process: rows dealt to the devices in strips, one RCCL gather of the framebuffer (pt_multi)
             if (devices.empty()) for (uint32_t d = 0; d < gpus; ++d) devices.push_back((int32_t)d);
             MultiRenderer multi(scene, cam, width, height, bounces, devices);
+            multi.set_projection(projection);
             multi.render(0, 1);                                  // scene upload, RCCL communicator set-up
             multi.reset_accumulation();
             const auto m0 = std::chrono::steady_clock::now();
@@ -135,6 +149,7 @@ int main(int argc, char** argv)
             return 0;
         }
         Renderer renderer(scene, cam, width, height, bounces);
+        renderer.set_projection(projection);
         if (checker)
         {
             const std::vector<float> p = renderer.model_positions(1);

@@ -231,9 +231,53 @@ int pt_create_ray(pt_ctx* ctx, float s, float t, float o[3], float d[3]); /* hos
  * The lens point is the polar map of a second Sobol point (sincos_det exists bit-exactly on host and device).
  * Out of scope: polygonal apertures, motion blur, lens-aware denoiser weights (a defocused pixel's guides are one sample's hit). */
 int pt_set_lens(pt_ctx* ctx, float aperture, float focus);
-/* The camera ray of (global pixel = y * width + x, sample) as the render generates it, pinhole or lens, and the stream draws it consumed
- * (1 or 2; draws may be NULL).  Host evaluation, no GPU. */
+/* The camera ray of (global pixel = y * width + x, sample) as the render generates it, pinhole or lens (or, under pt_set_projection below,
+ * panoramic or orthographic), and the stream draws it consumed (2 under a lens, else 1; draws may be NULL).  Host evaluation, no GPU. */
 int pt_primary_ray(pt_ctx* ctx, uint32_t pixel, uint32_t sample, float o[3], float d[3], uint32_t* draws);
+
+/* ---- panoramic and orthographic cameras ------------------------------------------------------------------------------------------ */
+/* PT_PROJ_PERSPECTIVE (the default; NULL restores it) IS the camera above: the same rays, the same kernels.  The projection survives
+ * pt_set_camera and pt_camera_input; setting it makes the denoiser's guides and the mean-albedo sums stale like pt_set_lens, and pt_multi_*
+ * replicates it with the camera.  Errors are returned before any device call and change nothing (pt_get_projection still returns the
+ * prior value): PT_ERR_ARG for an unknown kind, a non-zero reserved word, a span that is negative, NaN or infinite, span_x_deg > 360 or
+ * span_y_deg > 180, or with ORTHOGRAPHIC an ortho_height that is not finite and > 0; PT_ERR_STATE for a non-perspective kind while the lens
+ * aperture is > 0 (and pt_set_lens with aperture > 0 returns PT_ERR_STATE under a non-perspective kind).
+ *
+ * Under PANORAMA or ORTHOGRAPHIC "the camera ray of (pixel, sample)" is, everywhere pt_set_lens lists (pt_render*, pt_frame,
+ * pt_render_adaptive, a miss's position r.at(1e5) | 1e5, pt_render_guides, pt_accumulate_albedo, pt_primary_ray, pt_multi_*), the following
+ * ray, in binary32 with every operation rounded once, no contraction, in this order.  eye, c0, c1, c2 = translation and rotation columns
+ * of the camera matrix (pt_camera_matrices); the camera looks along -c2:
+ *     seed = draw 0 of the stream;  (jx, jy) = ss_sobol(n_sobol, sample, seed)          -- main.rs:193-194
+ *     u = ((float)gx + (jx - 0.5f)) / (float)width;  v likewise with gy, height         -- main.rs:196-197
+ *     nx = u * 2 - 1;  ny = v * 2 - 1                                                   -- as camera.rs:94-105; row 0 = bottom
+ *   PANORAMA      ax = (span_x_deg * 0.5f) * 0.017453292f;  ay = (span_y_deg * 0.5f) * 0.017453292f   (host, once; a span of 0 = 360 / 180)
+ *                 phi = ax * nx;  theta = ay * ny
+ *                 (sp, cp) = sincos_det(phi);  (st, ct) = sincos_det(theta)
+ *                 dc = (ct * sp,  st,  -(ct * cp))
+ *                 w = (c0 * dc.x + c1 * dc.y) + c2 * dc.z          -- per component
+ *                 o = eye;  d = w / sqrt((w.x * w.x + w.y * w.y) + w.z * w.z)
+ *   ORTHOGRAPHIC  hh = ortho_height * 0.5f;  hw = hh * aspect      (host, once; aspect as given to pt_set_camera)
+ *                 a = hw * nx;  b = hh * ny
+ *                 o = eye + (c0 * a + c1 * b)                      -- per component
+ *                 n = -c2;  d = n / sqrt((n.x * n.x + n.y * n.y) + n.z * n.z)   (host, once)
+ * and the path starts with ONE draw consumed.  fov_y is ignored by both, aspect by PANORAMA.  A full panorama (360 x 180) is the
+ * equirectangular image of the scene around the eye: a reflection probe.
+ *
+ * Under a non-perspective projection pt_active_pixels returns the whole frame (the primary cull's image-plane argument does not hold: no
+ * pixel is answered without a ray); pt_create_ray stays the pinhole ray; pt_frame and pt_frame_moving accumulate as ever while nothing
+ * moved and return PT_ERR_STATE where they would reproject (velocity.wgsl is a perspective reprojection); pt_render_guides and pt_denoise
+ * work as under the pinhole (the denoiser's plane term needs no camera).
+ * Out of scope: fisheye and cube-map projections (a cube face is a 90-degree perspective camera), a lens under these projections,
+ * temporal reprojection under them, a primary cull for the orthographic camera, mirroring a panorama into pt_set_environment's layout. */
+enum pt_projection_kind { PT_PROJ_PERSPECTIVE = 0, PT_PROJ_PANORAMA = 1, PT_PROJ_ORTHOGRAPHIC = 2 };
+typedef struct pt_projection {
+    uint32_t kind;
+    float span_x_deg, span_y_deg; /* PANORAMA: azimuth / elevation covered by the image; 0 => 360 / 180 */
+    float ortho_height;           /* ORTHOGRAPHIC: world-space height of the view volume (> 0, finite) */
+    uint32_t reserved[4];         /* must be 0 */
+} pt_projection;
+int pt_set_projection(pt_ctx* ctx, const pt_projection* projection); /* NULL restores PERSPECTIVE */
+int pt_get_projection(pt_ctx* ctx, pt_projection* out);
 
 /* ---- the per-frame pixel loop  src/main.rs:181-207 + accumulate.wgsl:20-23 ------------------------------------- */
 /* Renders samples [first_sample, first_sample+n_samples) of every local pixel on the GPU and adds them, in sample
@@ -250,7 +294,8 @@ int pt_render(pt_ctx* ctx, uint32_t first_sample, uint32_t n_samples, float* dat
  * root_box as min xyz, max xyz when non-NULL), which is all TLAS::intersect would find out (tlas.rs:68-72): such pixels receive the miss
  * result of integrator.rs:263-266 without a path.  The whole frame when an environment map is set, when the box reaches behind the
  * image plane, or with PT_FLAG_NO_PRIMARY_CULL.  Under a lens (pt_set_lens) the rectangle bounds the box as seen from every point of the
- * lens, projected onto the plane of focus: wider than the pinhole's, still a proper part of the frame. */
+ * lens, projected onto the plane of focus: wider than the pinhole's, still a proper part of the frame.  Under a panoramic or orthographic
+ * projection (pt_set_projection) the whole frame. */
 int pt_active_pixels(pt_ctx* ctx, uint32_t rect[4], float root_box[6]);
 /* same, results stay on the device (no host copy); *_dev may be NULL or device pointers of the sizes above */
 int pt_render_device(pt_ctx* ctx, uint32_t first_sample, uint32_t n_samples);
@@ -428,7 +473,8 @@ int pt_post_denoise(pt_ctx* ctx, uint32_t w, uint32_t h, const pt_denoise_params
  * where a is what pt_render_guides(s) stores as that pixel's albedo guide (the surface colour at the first hit, an emissive hit's emitted
  * colour), except that a sample which MISSES adds (1, 1, 1): the background passes through the demodulation undivided.  Calls continue the
  * sums: (0, a) then (a, b) equals (0, a + b) bit for bit.  The sums go stale on exactly the events that make the guides stale (pt_set_camera,
- * pt_camera_input, pt_set_lens, pt_build, pt_set_config, pt_set_environment); accumulating onto stale or reset sums starts from zero.  The
+ * pt_camera_input, pt_set_lens, pt_set_projection, pt_build, pt_set_config, pt_set_environment); accumulating onto stale or reset sums
+ * starts from zero.  The
  * call never touches the accumulation, the position and id history, the moments or the guides.  Errors, before any device call: PT_ERR_STATE
  * without a built scene or a camera; PT_ERR_ARG for n_samples == 0 or first_sample + n_samples above 2^32.  pt_reset_albedo drops the sums.
  * pt_read_albedo copies them out, local_rows * width entries of (sum r, sum g, sum b, n); PT_ERR_STATE without current sums. */

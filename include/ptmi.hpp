@@ -220,6 +220,12 @@ public:
         check(pt_set_camera(ctx_, eye, tgt, c.fov, c.aspect_ratio));
         check(pt_set_lens(ctx_, c.aperture, c.focus));
     }
+    // panoramic / orthographic camera (pt_set_projection); the projection survives set_camera and input, and excludes a lens
+    void set_projection(const pt_projection& p) { check(pt_set_projection(ctx_, &p)); }
+    void set_panorama(float span_x_deg = 0.0f, float span_y_deg = 0.0f) { pt_projection p{}; p.kind = PT_PROJ_PANORAMA; p.span_x_deg = span_x_deg; p.span_y_deg = span_y_deg; set_projection(p); }
+    void set_orthographic(float height) { pt_projection p{}; p.kind = PT_PROJ_ORTHOGRAPHIC; p.ortho_height = height; set_projection(p); }
+    void set_perspective() { check(pt_set_projection(ctx_, nullptr)); }
+    pt_projection projection() const { pt_projection p{}; check(pt_get_projection(ctx_, &p)); return p; }
     // Camera::input: true where the reference's returns true
     bool input(pt_event event, float a, float b, float dt) { return check(pt_camera_input(ctx_, event, a, b, dt)) == 1; }
     Mat4 inv_projection() const { Mat4 m{}; check(pt_inv_projection(ctx_, m.data())); return m; }
@@ -400,6 +406,13 @@ public:
     {
         if (out) out->resize((size_t)width_ * height_ * 4);
         check(pt_multi_render(m_, first_sample, n_samples, out ? out->data() : nullptr));
+    }
+    // the projection of rank 0's camera, replicated to every device by the next render (pt_set_projection)
+    void set_projection(const pt_projection& p)
+    {
+        pt_ctx* c0 = pt_multi_ctx(m_, 0);
+        const int r = pt_set_projection(c0, &p);
+        if (r < 0) throw Error(r, pt_last_error(c0));
     }
     void reset_accumulation() { check(pt_multi_reset_accumulation(m_)); }
     void write_image(const std::string& path) { check(pt_multi_write_image(m_, path.c_str())); }

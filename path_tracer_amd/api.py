@@ -42,16 +42,22 @@ EXPORTS = [
     "pt_set_instances", "pt_get_scene_info", "pt_read_guide_instances", "pt_frame_moving", "pt_post_motion",
     "pt_add_texture", "pt_set_material_texture", "pt_set_model_uvs", "pt_model_uvs", "pt_surface_colour", "pt_read_guide_albedo",
     "pt_accumulate_albedo", "pt_reset_albedo", "pt_read_albedo", "pt_denoise_albedo", "pt_post_denoise_albedo",
+    "pt_set_projection", "pt_get_projection",
 ]
 
 
 ALBEDO_GUIDE, ALBEDO_MEAN = 1, 2   # pt_denoise_albedo's albedo_source
+PROJ_PERSPECTIVE, PROJ_PANORAMA, PROJ_ORTHOGRAPHIC = range(3)   # pt_projection_kind
 EV_MOUSE_MOTION, EV_KEY_W, EV_KEY_S, EV_KEY_A, EV_KEY_D = range(5)
 
 
 class MaterialDesc(C.Structure):
     _fields_ = [("kind", C.c_int32), ("colour", C.c_float * 3), ("roughness", C.c_float), ("ior", C.c_float), ("has_volume", C.c_int32),
                 ("vol_absorption", C.c_float * 3), ("vol_k", C.c_float), ("vol_c", C.c_float), ("vol_g", C.c_float)]
+
+
+class Projection(C.Structure):
+    _fields_ = [("kind", C.c_uint32), ("span_x_deg", C.c_float), ("span_y_deg", C.c_float), ("ortho_height", C.c_float), ("reserved", C.c_uint32 * 4)]
 
 
 class Config(C.Structure):
@@ -151,6 +157,8 @@ def lib():
         L.pt_create_ray.argtypes = [vp, C.c_float, C.c_float, vp, vp]
         L.pt_set_lens.argtypes = [vp, C.c_float, C.c_float]
         L.pt_primary_ray.argtypes = [vp, u32, u32, vp, vp, C.POINTER(u32)]
+        L.pt_set_projection.argtypes = [vp, C.POINTER(Projection)]
+        L.pt_get_projection.argtypes = [vp, C.POINTER(Projection)]
         L.pt_render.argtypes = [vp, u32, u32, vp, vp, vp]
         L.pt_render_device.argtypes = [vp, u32, u32]
         L.pt_active_pixels.argtypes = [vp, vp, vp]
@@ -404,6 +412,18 @@ class Renderer:
         """thin lens (pt_set_lens): aperture = lens diameter in world units (0 = pinhole), focus = distance of the plane of focus"""
         self._chk(self.L.pt_set_lens(self.ctx, aperture, focus))
 
+    def set_projection(self, kind: int, span_x: float = 0.0, span_y: float = 0.0, ortho_height: float = 0.0):
+        """pt_set_projection: PROJ_PERSPECTIVE (the camera as it is), PROJ_PANORAMA (span_x x span_y degrees of azimuth / elevation, 0 = 360 / 180)
+        or PROJ_ORTHOGRAPHIC (a view volume ortho_height world units high)"""
+        p = Projection(int(kind), span_x, span_y, ortho_height)
+        self._chk(self.L.pt_set_projection(self.ctx, C.byref(p)))
+
+    def get_projection(self):
+        """(kind, span_x, span_y, ortho_height) as pt_set_projection last accepted them"""
+        p = Projection()
+        self._chk(self.L.pt_get_projection(self.ctx, C.byref(p)))
+        return int(p.kind), float(p.span_x_deg), float(p.span_y_deg), float(p.ortho_height)
+
     def camera_input(self, event, a=0.0, b=0.0, dt=0.0) -> bool:
         """Camera::input (camera.rs:56-92): event = EV_MOUSE_MOTION (a, b = delta) or EV_KEY_W/S/A/D; True if consumed"""
         return bool(self._chk(self.L.pt_camera_input(self.ctx, int(event), a, b, dt), allow_positive=True))
@@ -453,7 +473,7 @@ class Renderer:
         return o, d
 
     def primary_ray(self, pixel: int, sample: int):
-        """(origin, direction, stream draws consumed) of the camera ray of (global pixel, sample), pinhole or lens; host evaluation"""
+        """(origin, direction, stream draws consumed) of the camera ray of (global pixel, sample) under the lens or projection in force; host evaluation"""
         o = np.zeros(3, np.float32)
         d = np.zeros(3, np.float32)
         n = C.c_uint32()

@@ -493,6 +493,7 @@ ActiveRect active_rect(pt_ctx* c)
     const uint32_t W = c->cfg.width, H = c->cfg.height, local_rows = (uint32_t)c->rows.size();
     const ActiveRect full{0u, W, 0u, local_rows};
     if ((c->cfg.flags & PT_FLAG_NO_PRIMARY_CULL) || c->env_w || !c->scene.built || !c->scene.camera.set) return full;
+    if (c->scene.camera.proj_kind != PROJ_PERSPECTIVE) return full; // pt_set_projection: the image-plane argument below is the perspective camera's
     const FlatScene& f = c->scene.flat;
     if (f.world_root == MISS_ID || f.world_root >= f.nodes.size()) return full;
     const DNode& root = f.nodes[f.world_root];
@@ -847,7 +848,7 @@ struct BatchRun
     BatchSpec spec;
     RenderParams rp{};
     CameraView cam{};
-    LensView lens{};
+    CameraOptics lens{}; // the lens or the projection, whichever is set
     EnvView env{};
     TraceLaunch tl{}, tl_side{};
     WavefrontBuffers wb{};         // the pipeline's; a ray batch keeps its first-hit records in Pipe::ray_pos / ray_id
@@ -911,7 +912,7 @@ int batch_begin(BatchRun& br, pt_ctx* c, const BatchSpec& spec)
     br.tl = trace_launch(c, pipe, false);
     br.tl_side = trace_launch(c, pipe, true);
     br.cam = c->scene.camera_view();
-    br.lens = c->scene.lens_view();
+    br.lens = c->scene.optics_view();
     if (c->env_w)
     {
         br.env.data = (const f4*)c->d_env.p; // uploaded by the caller (ensure_environment)
@@ -1705,9 +1706,49 @@ int pt_set_lens(pt_ctx* c, float aperture, float focus)                         
     std::lock_guard<std::mutex> lk(c->mu);
     if (!(aperture >= 0.0f) || !std::isfinite(aperture)) return fail(c, PT_ERR_ARG, "aperture must be finite and >= 0");
     if (aperture > 0.0f && (!(focus > 0.0f) || !std::isfinite(focus))) return fail(c, PT_ERR_ARG, "focus must be finite and > 0 when aperture > 0");
+    if (aperture > 0.0f && c->scene.camera.proj_kind != PROJ_PERSPECTIVE) return fail(c, PT_ERR_STATE, "a lens needs the perspective projection (pt_set_projection)");
     c->scene.camera.aperture = aperture;
     c->scene.camera.focus = focus;
     c->scene_version++; // the guides belong to the old camera; pt_multi replicates the lens with it
+    return PT_OK;
+}
+
+static_assert((uint32_t)PT_PROJ_PERSPECTIVE == PROJ_PERSPECTIVE && (uint32_t)PT_PROJ_PANORAMA == PROJ_PANORAMA && (uint32_t)PT_PROJ_ORTHOGRAPHIC == PROJ_ORTHOGRAPHIC, "");
+int pt_set_projection(pt_ctx* c, const pt_projection* p)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    const pt_projection none{};
+    if (!p) p = &none;
+    if (p->kind > PT_PROJ_ORTHOGRAPHIC) return fail(c, PT_ERR_ARG, "unknown projection kind");
+    for (uint32_t w : p->reserved)
+        if (w != 0u) return fail(c, PT_ERR_ARG, "pt_projection::reserved must be 0");
+    if (!(p->span_x_deg >= 0.0f) || !std::isfinite(p->span_x_deg) || !(p->span_y_deg >= 0.0f) || !std::isfinite(p->span_y_deg))
+        return fail(c, PT_ERR_ARG, "spans must be finite and >= 0");
+    if (p->span_x_deg > 360.0f || p->span_y_deg > 180.0f) return fail(c, PT_ERR_ARG, "span_x_deg is at most 360 and span_y_deg at most 180");
+    if (p->kind == PT_PROJ_ORTHOGRAPHIC && (!(p->ortho_height > 0.0f) || !std::isfinite(p->ortho_height)))
+        return fail(c, PT_ERR_ARG, "ortho_height must be finite and > 0");
+    if (p->kind != PT_PROJ_PERSPECTIVE && c->scene.camera.aperture > 0.0f)
+        return fail(c, PT_ERR_STATE, "a panoramic or orthographic camera has no lens: pt_set_lens(ctx, 0, 0) first");
+    HostCamera& cam = c->scene.camera;
+    cam.proj_kind = p->kind;
+    cam.span_x_deg = p->span_x_deg;
+    cam.span_y_deg = p->span_y_deg;
+    cam.ortho_height = p->ortho_height;
+    c->scene_version++; // the guides and the mean-albedo sums belong to the old camera; pt_multi replicates the projection with it
+    return PT_OK;
+}
+
+int pt_get_projection(pt_ctx* c, pt_projection* out)
+{
+    if (!c || !out) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    const HostCamera& cam = c->scene.camera;
+    *out = pt_projection{};
+    out->kind = cam.proj_kind;
+    out->span_x_deg = cam.span_x_deg;
+    out->span_y_deg = cam.span_y_deg;
+    out->ortho_height = cam.ortho_height;
     return PT_OK;
 }
 
@@ -2039,6 +2080,15 @@ int frame_locked(pt_ctx* c, uint32_t frame_index, const float* last_inv_projecti
     if ((r = precheck(c))) return r;
     if (c->cfg.world_size != 1) return fail(c, PT_ERR_STATE, "pt_frame needs the whole frame on one rank (3x3 neighbourhoods cross row strips)");
     if ((r = upload_scene(c)) || (r = ensure_frame(c))) return r;
+    // velocity.wgsl is a perspective reprojection: under a panoramic or orthographic camera only the accumulate branch exists
+    const bool projected = c->scene.camera.proj_kind != PROJ_PERSPECTIVE;
+    if (projected && last_inv_projection)
+    {
+        float now[16];
+        c->scene.inv_projection(now);
+        for (int i = 0; i < 16; ++i)
+            if (!(now[i] == last_inv_projection[i])) return fail(c, PT_ERR_STATE, "the camera moved: no temporal reprojection under a panoramic or orthographic projection");
+    }
     const size_t px = c->local_pixels;
     if ((r = dev_alloc(c, c->d_input, px * 16)) || (r = dev_alloc(c, c->d_velocity, px * 8)) || (r = dev_alloc(c, c->d_output, px * 16))) return r;
     if (id) HIPCHK(c, hipMemcpyAsync(c->d_id.p, id, px * 4, hipMemcpyHostToDevice, c->stream));
@@ -2062,6 +2112,7 @@ int frame_locked(pt_ctx* c, uint32_t frame_index, const float* last_inv_projecti
     bool world_moved = false;
     if (moving && ((r = render_guides_locked(c, frame_index)) || (r = prepare_motion(c, &world_moved)))) return r;
     const f4* vel_from = (const f4*)c->d_position.p;
+    if (world_moved && projected) return fail(c, PT_ERR_STATE, "an instance moved: no temporal reprojection under a panoramic or orthographic projection");
     if (world_moved)
     {
         if ((r = dev_alloc(c, c->d_xprev, std::max<size_t>(px, 1) * 16))) return r;
@@ -2279,7 +2330,7 @@ int guide_trace(pt_ctx* c, uint32_t sample)
     rp.div_width = fastdiv_make(rp.width);
     rp.div_strip_rows = fastdiv_make(rp.strip_rows);
     const CameraView cam = c->scene.camera_view();
-    const LensView lens = c->scene.lens_view();
+    const CameraOptics lens = c->scene.optics_view();
     const RayQueue q{(f4*)c->d_gray_a.p, (f4*)c->d_gray_b.p};
     uint32_t* head = (uint32_t*)c->d_ghead.p;
     HIPCHK(c, hipMemsetAsync(head, 0, c->d_ghead.bytes, c->stream));
@@ -2315,7 +2366,7 @@ int render_guides_locked(pt_ctx* c, uint32_t sample)
     {
         if ((r = guide_trace(c, sample))) return r;
         const CameraView cam = c->scene.camera_view();
-        const LensView lens = c->scene.lens_view();
+        const CameraOptics lens = c->scene.optics_view();
         const RayQueue q{(f4*)c->d_gray_a.p, (f4*)c->d_gray_b.p};
         launch_guide_resolve(c->stream, c->sv, px, cam, lens, q, (const f4*)c->d_ghits.p, (f4*)c->d_gpos.p, (f4*)c->d_gnrm.p, (uint32_t*)c->d_gmodel.p,
                              (uint32_t*)c->d_ginst.p);

@@ -1,5 +1,6 @@
 // The camera ray of (pixel, sample): one definition for the gfx950 kernels and for the host evaluation (pt_primary_ray).
-// Pinhole: main.rs:193-199 + Camera::create_ray camera.rs:94-105.  Thin lens: include/pt_api.h, pt_set_lens.
+// Pinhole: main.rs:193-199 + Camera::create_ray camera.rs:94-105.  Thin lens: include/pt_api.h, pt_set_lens.  Panoramic and orthographic:
+// include/pt_api.h, pt_set_projection.
 #pragma once
 #include "pt_types.h"
 
@@ -59,6 +60,57 @@ PT_HD f3 camera_ray(const RenderParams& rp, const CameraView& cam, const LensVie
     const f3 f = q * lens.focus + eye;
     *origin = o;
     return unit3(f - o);
+}
+
+// Panoramic and orthographic cameras (include/pt_api.h, pt_set_projection).  Both take the jittered position of the pinhole ray
+// (main.rs:193-197, camera.rs:96: ndc in [-1, 1], row 0 = bottom), consume ONE draw of the stream and round every operation once, in
+// the order written.  (The pinhole's own lines above stay as they are: its kernels keep their instruction streams.)
+PT_HD void camera_ndc(const RenderParams& rp, uint32_t gx, uint32_t gy, uint32_t sample, float* nx, float* ny)
+{
+    Stream rng{stream_key(rp.seed, gy * rp.width + gx, sample), 0u};
+    const uint32_t seed = rng.u32();
+    float jx, jy;
+    ss_sobol(rp.n_sobol, sample, seed, &jx, &jy);
+    const float ox = jx - 0.5f, oy = jy - 0.5f;
+    const float u = ((float)gx + ox) / (float)rp.width;
+    const float v = ((float)gy + oy) / (float)rp.height;
+    *nx = u * 2.0f - 1.0f;
+    *ny = v * 2.0f - 1.0f;
+}
+
+// PANORAMA: azimuth phi = ax * nx about the camera's y axis, elevation theta = ay * ny; the ray leaves the eye
+PT_HD f3 camera_ray_panorama(const RenderParams& rp, const CameraView& cam, const ProjView& proj, uint32_t gx, uint32_t gy, uint32_t sample, f3* origin)
+{
+    float nx, ny;
+    camera_ndc(rp, gx, gy, sample, &nx, &ny);
+    const float phi = proj.sx * nx, theta = proj.sy * ny;
+    float sp, cp, st, ct;
+    sincos_det(phi, &sp, &cp);
+    sincos_det(theta, &st, &ct);
+    const float dx = ct * sp, dy = st, dz = -(ct * cp);
+    const f3 c0{proj.c0[0], proj.c0[1], proj.c0[2]}, c1{proj.c1[0], proj.c1[1], proj.c1[2]}, c2{proj.c2[0], proj.c2[1], proj.c2[2]};
+    const f3 w = (c0 * dx + c1 * dy) + c2 * dz;
+    *origin = f3{cam.eye[0], cam.eye[1], cam.eye[2]};
+    return unit3(w);
+}
+
+// ORTHOGRAPHIC: every ray runs along the view axis (proj.c2 holds -c2 normalised) from its point of the view volume's near face
+PT_HD f3 camera_ray_orthographic(const RenderParams& rp, const CameraView& cam, const ProjView& proj, uint32_t gx, uint32_t gy, uint32_t sample, f3* origin)
+{
+    float nx, ny;
+    camera_ndc(rp, gx, gy, sample, &nx, &ny);
+    const float a = proj.sx * nx, b = proj.sy * ny;
+    const f3 eye{cam.eye[0], cam.eye[1], cam.eye[2]};
+    const f3 c0{proj.c0[0], proj.c0[1], proj.c0[2]}, c1{proj.c1[0], proj.c1[1], proj.c1[2]};
+    *origin = eye + (c0 * a + c1 * b);
+    return f3{proj.c2[0], proj.c2[1], proj.c2[2]};
+}
+
+// either, by the view's kind (launch-invariant: where a kernel calls this the branch is uniform)
+PT_HD f3 camera_ray_projected(const RenderParams& rp, const CameraView& cam, const ProjView& proj, uint32_t gx, uint32_t gy, uint32_t sample, f3* origin)
+{
+    return proj.kind == PROJ_PANORAMA ? camera_ray_panorama(rp, cam, proj, gx, gy, sample, origin)
+                                      : camera_ray_orthographic(rp, cam, proj, gx, gy, sample, origin);
 }
 
 } // namespace pt

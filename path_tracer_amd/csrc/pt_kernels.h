@@ -93,14 +93,17 @@ void launch_probe_project(hipStream_t s, const ProbeBake& pb, uint64_t first, ui
 
 // list: an adaptive list (launch_adaptive_select's {local pixel, n_p} entries, rp.act_pixels of them) whose pixels the batch's paths belong
 // to instead of the active rectangle's (pt_render_adaptive), or null
-// lens: with a radius above 0 (lens_set) the launchers that take one run the thin-lens variants of their kernels (pt_set_lens); the pinhole
+// opt.lens: with a radius above 0 (lens_set) the launchers that take one run the thin-lens variants of their kernels (pt_set_lens); the pinhole
 // kernels are the ones they always were
 inline bool lens_set(const LensView& lens) { return lens.radius > 0.0f; }
-void launch_generate(hipStream_t s, const RenderParams& rp, const CameraView& cam, const LensView& lens, const WavefrontBuffers& wb, const uint2* list = nullptr);
+// opt.proj: with a kind other than PROJ_PERSPECTIVE (proj_set) they run the projection variants (pt_set_projection), whose camera rays carry origins
+// of their own like a lens's but consume one draw
+inline bool proj_set(const ProjView& proj) { return proj.kind != PROJ_PERSPECTIVE; }
+void launch_generate(hipStream_t s, const RenderParams& rp, const CameraView& cam, const CameraOptics& opt, const WavefrontBuffers& wb, const uint2* list = nullptr);
 // closest hit against the world TLAS for bounce `b`: reads rq[b&1], writes hits + shade queues of row b
 // (ray_list: bounce 0 of a ray batch, whose rays have origins of their own like a lens's)
 void launch_trace_world(hipStream_t s, const TraceLaunch& tl, const WavefrontBuffers& wb, uint32_t b, const RenderParams& rp, const CameraView& cam,
-                        const LensView& lens, const EnvView& env, bool ray_list = false);
+                        const CameraOptics& opt, const EnvView& env, bool ray_list = false);
 // the same for bounce b >= 1 together with the BSDF-sampled NEE launch of bounce b - 1, as ONE launch (a wave goes from queue to queue)
 void launch_trace_fused(hipStream_t s, const TraceLaunch& tl, const WavefrontBuffers& wb, uint32_t b, const RenderParams& rp, const EnvView& env);
 // NEE rays produced by the shading of bounce `b` (counter row b)
@@ -112,14 +115,14 @@ void launch_trace_lchain(hipStream_t s, const TraceLaunch& tl, const WavefrontBu
 // (tl: the scene's traversal launch description; with it the Lambert / GGX passes of an LDS-resident scene may trace their own shadow rays,
 //  and the passes of a textured scene (tl->tex) look the surface colour up)
 void launch_shade(hipStream_t s, uint32_t qclass, const SceneView& sv, const RenderParams& rp, const WavefrontBuffers& wb, uint32_t b,
-                  uint32_t grid_blocks, const CameraView& cam, const LensView& lens, const EnvView& env, const TraceLaunch* tl = nullptr,
+                  uint32_t grid_blocks, const CameraView& cam, const CameraOptics& opt, const EnvView& env, const TraceLaunch* tl = nullptr,
                   const uint2* list = nullptr, const uint2* ray_keys = nullptr);
 // true: the shading pass answers the explicit-light shadow rays itself and nothing is queued for launch_trace_shadow
 bool shade_traces_shadow(const TraceLaunch& tl);
 // accum[pixel] += sum over batch samples in order of (finalised rgb, 1); position/id of the last samples.  With moments also
 // moments[pixel] += L * L of each finalised sample beside it (PT_FLAG_ADAPTIVE); with a list (which needs moments) only the listed
 // pixels, in list order
-void launch_accumulate(hipStream_t s, const RenderParams& rp, const CameraView& cam, const LensView& lens, const WavefrontBuffers& wb, f4* accum, f4* position,
+void launch_accumulate(hipStream_t s, const RenderParams& rp, const CameraView& cam, const CameraOptics& opt, const WavefrontBuffers& wb, f4* accum, f4* position,
                        uint32_t* id, uint32_t write_position, uint32_t add_to_accum, float* moments = nullptr, const uint2* list = nullptr);
 void launch_store_samples(hipStream_t s, const RenderParams& rp, const WavefrontBuffers& wb, f4* out);
 // adaptive selection of n_pixels local pixels: list <- {pixel, n_p} of every active pixel in ascending order, header[0] <- their number,
@@ -161,9 +164,9 @@ void launch_denoise(hipStream_t s, int w, int h, const DenoiseK& p, const f4* ac
 void launch_denoise_albedo(hipStream_t s, int w, int h, const DenoiseK& p, const f4* accum, const float* moments, const f4* position, const f4* normal,
                            const uint32_t* model, const f4* albedo, bool albedo_is_sum, f4* cv_a, f4* cv_b, f4* nv, f4* kd, f4* out);
 // the camera rays of sample rp.first_sample of every local pixel into a hook queue (ray index = local pixel), n_and_heads[0] <- local pixels
-void launch_guide_rays(hipStream_t s, const RenderParams& rp, const CameraView& cam, const LensView& lens, RayQueue rq, uint32_t* n_and_heads);
+void launch_guide_rays(hipStream_t s, const RenderParams& rp, const CameraView& cam, const CameraOptics& opt, RayQueue rq, uint32_t* n_and_heads);
 // their launch_trace_rays_closest hits -> position, normal, model guides
-void launch_guide_resolve(hipStream_t s, const SceneView& sv, uint32_t n, const CameraView& cam, const LensView& lens, RayQueue rq, const f4* hits,
+void launch_guide_resolve(hipStream_t s, const SceneView& sv, uint32_t n, const CameraView& cam, const CameraOptics& opt, RayQueue rq, const f4* hits,
                           f4* position, f4* normal, uint32_t* model, uint32_t* instance);
 // ... -> the albedo guide: the surface colour at the hit (an emissive hit: its emitted colour), (0, 0, 0) for a miss.  A launch of its own behind
 // the resolve, whose kernels and four guides stay what they were.  tex: the scene's texture view (all null for an untextured scene)

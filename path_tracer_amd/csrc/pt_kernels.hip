@@ -1,7 +1,8 @@
 // gfx950 (MI355X, wave64) kernels of the wavefront path tracer.
 //
 //   k_generate      main.rs:186-199   seed draw, shuffled-scrambled Sobol jitter, camera ray (pt_camera.h; k_generate_lens and the LENS
-//                   instantiations below: the thin lens of pt_set_lens, whose camera rays have origins of their own)
+//                   instantiations below: the thin lens of pt_set_lens, whose camera rays have origins of their own; k_generate_proj and the
+//                   ONE_DRAW / PROJ instantiations: the panoramic and orthographic cameras of pt_set_projection, which ride on the lens's)
 //   k_closest       tlas.rs:66-110 + blas.rs:214-256 + boundingbox.rs:115-131 + primitive.rs:117-178
 //                   persistent-threads ordered traversal; BVH staged in LDS; per-lane stack in LDS;
 //                   ballot/mbcnt refill of idle lanes from the ray queue; material binning of the hits;
@@ -1707,6 +1708,24 @@ __global__ void __launch_bounds__(256) k_generate_lens(const RenderParams rp, co
     rq.b[pid] = f4{dir.x, dir.y, dir.z, asf(pid)};
 }
 
+// panoramic and orthographic cameras (pt_set_projection; KIND = PROJ_PANORAMA / PROJ_ORTHOGRAPHIC): the ray's origin is stored beside its
+// direction as the lens's is (an orthographic ray's is its own; a panorama's is the eye, so that both run one set of bounce-0 kernels) and
+// bounce 0 knows ONE draw consumed.  A kernel per kind: the panorama's two sincos_det are not in the orthographic kernel.
+template <bool LIST, uint32_t KIND>
+__global__ void __launch_bounds__(256) k_generate_proj(const RenderParams rp, const CameraView cam, const ProjView proj, const RayQueue rq, Counters* ctr,
+                                                        const uint2* __restrict__ list)
+{
+    const uint32_t pid = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pid == 0u) ctr[0].n_closest = rp.n_paths;
+    if (pid >= rp.n_paths) return;
+    const PixelId px = LIST ? path_pixel_list(rp, list, pid) : path_pixel(rp, pid);
+    f3 o;
+    const f3 dir = KIND == PROJ_PANORAMA ? camera_ray_panorama(rp, cam, proj, px.gx, px.gy, px.sample, &o)
+                                         : camera_ray_orthographic(rp, cam, proj, px.gx, px.gy, px.sample, &o);
+    rq.a[pid] = f4{o.x, o.y, o.z, __builtin_inff()};
+    rq.b[pid] = f4{dir.x, dir.y, dir.z, asf(pid)};
+}
+
 // Ray list (pt_integrate_rays): the batch's path ids index the window of the caller's rays (RayView), one path per ray, and a path's stream is
 // the one its table entry names: {pixel, sample} as given, not a pixel of the image.  (pid_split would return the same s = 0, k = pid.)
 __device__ __forceinline__ PixelId path_pixel_rays(const uint2* __restrict__ keys, uint32_t pid, uint32_t* s_local, uint32_t* k_out)
@@ -2004,6 +2023,7 @@ __device__ __forceinline__ const TexView& shade_args_tex()
     [[maybe_unused]] const ShadeIO& io = ka_.io;
 // LIST (pt_render_adaptive): path ids index the adaptive list (ShadeIO::list, path_pixel_list) instead of the active rectangle
 // LENS (pt_set_lens; launched for bounce 0 only): the camera ray's origin comes with its record (ShadeQueue::c) and two draws are consumed
+// ONE_DRAW (pt_set_projection; with LENS): a panoramic or orthographic camera ray has an origin of its own like a lens ray and consumed one draw
 // RAYS (pt_integrate_rays): the path's stream is the one its entry of the ray table names (path_pixel_rays) and bounce 0 (launched with LENS: the
 // ray's origin is its own) starts at RenderParams::ray_draws draws
 // TEX (a built scene with a textured material; never with INLINE): the colour of the material at the hit is the surface colour (surface_colour,
@@ -2015,7 +2035,8 @@ __device__ __forceinline__ const TexView& shade_args_tex()
 #ifndef PT_TEX_EARLY
 #define PT_TEX_EARLY 0
 #endif
-template <uint32_t QCLASS, bool VOLUMES, bool INLINE = false, bool IDENT = false, bool LIST = false, bool LENS = false, bool RAYS = false, bool TEX = false>
+template <uint32_t QCLASS, bool VOLUMES, bool INLINE = false, bool IDENT = false, bool LIST = false, bool LENS = false, bool RAYS = false, bool TEX = false,
+          bool ONE_DRAW = false>
 __global__ void __launch_bounds__(PT_SHADE_THREADS, INLINE ? PT_SHADE_WAVES_INLINE : shade_waves(QCLASS, VOLUMES))
 k_shade_surface(const std::conditional_t<TEX, ShadeKArgsTex, ShadeKArgs> kargs)
 {
@@ -2073,7 +2094,7 @@ k_shade_surface(const std::conditional_t<TEX, ShadeKArgsTex, ShadeKArgs> kargs)
             pid = asu(rb.w);
             const f4 hit = nt_load(io.q_in.b + idx);
             const f4 ra = (!LENS && bounce == 0u) ? io.primary_a : nt_load(io.q_in.c + idx);
-            f4 pw4{1.0f, 1.0f, 1.0f, asf(RAYS ? rp.ray_draws : LENS ? 2u : 1u)}; // bounce 0: path_weight = 1, accumulated = 0, the seed draw consumed (LENS: and the lens point's)
+            f4 pw4{1.0f, 1.0f, 1.0f, asf(RAYS ? rp.ray_draws : (LENS && !ONE_DRAW) ? 2u : 1u)}; // bounce 0: path_weight = 1, accumulated = 0, the seed draw consumed (LENS: and the lens point's)
             acc = f3{0.0f, 0.0f, 0.0f};
             flags = 0u;
             [[maybe_unused]] f3 surf{};
@@ -2394,6 +2415,7 @@ k_shade_surface(const std::conditional_t<TEX, ShadeKArgsTex, ShadeKArgs> kargs)
 
 // position r.at(1e5) of a camera ray that left the scene at once (integrator.rs:156), pinhole and thin lens
 struct CameraLensView : CameraView { LensView lens; };
+struct CameraProjView : CameraView { ProjView proj; };
 __device__ __forceinline__ f3 miss_position(const RenderParams& rp, const CameraView& cam, uint32_t gx, uint32_t gy, uint32_t sample)
 {
     const f3 d = camera_ray_dir(rp, cam, gx, gy, sample);
@@ -2403,6 +2425,13 @@ __device__ __forceinline__ f3 miss_position(const RenderParams& rp, const Camera
 {
     f3 o;
     const f3 d = camera_ray(rp, cam, cam.lens, gx, gy, sample, &o);
+    return fma3(d, bc3(1e5f), o);
+}
+// ... panoramic and orthographic (pt_set_projection): the kind is launch-invariant, the branch uniform
+__device__ __forceinline__ f3 miss_position(const RenderParams& rp, const CameraProjView& cam, uint32_t gx, uint32_t gy, uint32_t sample)
+{
+    f3 o;
+    const f3 d = camera_ray_projected(rp, cam, cam.proj, gx, gy, sample, &o);
     return fma3(d, bc3(1e5f), o);
 }
 
@@ -2431,8 +2460,10 @@ __device__ __forceinline__ float luminance(float r, float g, float b) { return (
 //
 // LENS (pt_set_lens): the camera ray of a miss is the lens ray, so r.at(1e5) starts at its point of the lens disk.  The lens rides behind
 // the camera in the LENS instantiations' camera argument only (CameraLensView): the pinhole instantiations' arguments are what they were.
-template <bool FEW_PIXELS, bool MOMENTS = false, bool LIST = false, bool LENS = false>
-__global__ void __launch_bounds__(256) k_accumulate(const RenderParams rp, const std::conditional_t<LENS, CameraLensView, CameraView> cam, const PathState st,
+// PROJ (pt_set_projection): likewise the panoramic or orthographic ray, whose constants ride behind the camera (CameraProjView)
+template <bool FEW_PIXELS, bool MOMENTS = false, bool LIST = false, bool LENS = false, bool PROJ = false>
+__global__ void __launch_bounds__(256) k_accumulate(const RenderParams rp,
+                                                     const std::conditional_t<PROJ, CameraProjView, std::conditional_t<LENS, CameraLensView, CameraView>> cam, const PathState st,
                                                      f4* accum, f4* position, uint32_t* id, const uint32_t write_position, const uint32_t add_to_accum,
                                                      float* moments, const uint2* list)
 {
@@ -2830,12 +2861,27 @@ __global__ void __launch_bounds__(256) k_guide_rays_lens(const RenderParams rp, 
     rq.a[i] = f4{o.x, o.y, o.z, __builtin_inff()};
     rq.b[i] = f4{dir.x, dir.y, dir.z, asf(i)};
 }
+// panoramic and orthographic cameras (pt_set_projection): the ray k_generate_proj<.., KIND> makes for that (pixel, sample)
+template <uint32_t KIND>
+__global__ void __launch_bounds__(256) k_guide_rays_proj(const RenderParams rp, const CameraView cam, const ProjView proj, const RayQueue rq,
+                                                          uint32_t* __restrict__ n_and_heads)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i == 0u) n_and_heads[0] = rp.local_pixels;
+    if (i >= rp.local_pixels) return;
+    const uint32_t ly = fastdiv(i, rp.div_width), x = i - ly * rp.width;
+    f3 o;
+    const f3 dir = KIND == PROJ_PANORAMA ? camera_ray_panorama(rp, cam, proj, x, global_row(rp, ly), rp.first_sample, &o)
+                                         : camera_ray_orthographic(rp, cam, proj, x, global_row(rp, ly), rp.first_sample, &o);
+    rq.a[i] = f4{o.x, o.y, o.z, __builtin_inff()};
+    rq.b[i] = f4{dir.x, dir.y, dir.z, asf(i)};
+}
 
 // first-hit guides of those rays: position r.at(t) | t as the render keeps it (r.at(1e5) | 1e5 for a miss, integrator.rs:156), the
 // face-forwarded world shading normal of the hit (HitInfo's, primitive.rs:161-165 + tlas.rs:105; 0 for a miss) and the hit's model
 // (BLAS index, MISS_ID for a miss) in full: its low byte is the id byte of main.rs:206; and the world-TLAS leaf of the hit in allocation
 // order (the index of pt_tlas_instances(ctx, 0, ..); MISS_ID for a miss), which pt_frame_moving reprojects a moved instance's pixels by
-// LENS (pt_set_lens): the ray's origin is its own (rq.a) instead of the eye
+// LENS (pt_set_lens, and pt_set_projection's rays, which are queued with their origins too): the ray's origin is its own (rq.a) instead of the eye
 template <bool LENS>
 __device__ __forceinline__ void guide_resolve_body(const SceneView& sv, const uint32_t n, const CameraView& cam, const RayQueue& rq, const f4* __restrict__ hits,
                                                    f4* __restrict__ position, f4* __restrict__ normal, uint32_t* __restrict__ model,
@@ -2921,11 +2967,18 @@ __global__ void __launch_bounds__(256) k_surface_colour(const SceneView sv, cons
 } // namespace
 
 // ================================================================================================ launchers
-void launch_generate(hipStream_t s, const RenderParams& rp, const CameraView& cam, const LensView& lens, const WavefrontBuffers& wb, const uint2* list)
+void launch_generate(hipStream_t s, const RenderParams& rp, const CameraView& cam, const CameraOptics& opt, const WavefrontBuffers& wb, const uint2* list)
 {
     const uint32_t blocks = (rp.n_paths + 255u) / 256u;
-    if (lens_set(lens))
+    if (proj_set(opt.proj))
     {
+        auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, s, rp, cam, opt.proj, wb.rq[0], wb.counters, list); };
+        if (opt.proj.kind == PROJ_PANORAMA) list ? go(k_generate_proj<true, PROJ_PANORAMA>) : go(k_generate_proj<false, PROJ_PANORAMA>);
+        else list ? go(k_generate_proj<true, PROJ_ORTHOGRAPHIC>) : go(k_generate_proj<false, PROJ_ORTHOGRAPHIC>);
+    }
+    else if (lens_set(opt.lens))
+    {
+        const LensView& lens = opt.lens;
         if (list) hipLaunchKernelGGL(k_generate_lens<true>, dim3(blocks), dim3(256), 0, s, rp, cam, lens, wb.rq[0], wb.counters, list);
         else hipLaunchKernelGGL(k_generate_lens<false>, dim3(blocks), dim3(256), 0, s, rp, cam, lens, wb.rq[0], wb.counters, list);
     }
@@ -3049,7 +3102,7 @@ static ClosestOut world_out(const WavefrontBuffers& wb, uint32_t b, const Render
 }
 
 void launch_trace_world(hipStream_t s, const TraceLaunch& tl, const WavefrontBuffers& wb, uint32_t b, const RenderParams& rp, const CameraView& cam,
-                        const LensView& lens, const EnvView& env, bool ray_list)
+                        const CameraOptics& opt, const EnvView& env, bool ray_list)
 {
     Counters* row = wb.counters + b;
     ClosestOut out = world_out(wb, b, rp, env);
@@ -3064,7 +3117,7 @@ void launch_trace_world(hipStream_t s, const TraceLaunch& tl, const WavefrontBuf
         out.keep_s_id = rp.keep_s_id; out.keep_s_pos = rp.keep_s_pos;
         out.blk_log = rp.blk_log; out.n_blk = rp.n_blk; out.blk_last = rp.blk_last; out.act_pixels = rp.act_pixels;
         out.div_blk_paths = rp.div_blk_paths; out.div_blk_last = rp.div_blk_last;
-        if (lens_set(lens) || ray_list) launch_closest_impl<CLOSEST_PRIMARY_LENS>(s, tl, tl.scene.world_root, wb.rq[0], &row->n_closest, wb.cap_slots, row_heads(wb, b, HEADS_CLOSEST), out);
+        if (lens_set(opt.lens) || proj_set(opt.proj) || ray_list) launch_closest_impl<CLOSEST_PRIMARY_LENS>(s, tl, tl.scene.world_root, wb.rq[0], &row->n_closest, wb.cap_slots, row_heads(wb, b, HEADS_CLOSEST), out);
         else launch_closest_impl<CLOSEST_PRIMARY>(s, tl, tl.scene.world_root, wb.rq[0], &row->n_closest, wb.cap_slots, row_heads(wb, b, HEADS_CLOSEST), out);
     }
     else launch_closest_impl<CLOSEST_WORLD>(s, tl, tl.scene.world_root, wb.rq[b & 1u], &row->n_closest, wb.cap_slots, row_heads(wb, b, HEADS_CLOSEST), out);
@@ -3120,12 +3173,13 @@ bool shade_traces_shadow(const TraceLaunch& tl)
            trace_lds_bytes(tl) + 1024 <= 32 * 1024;
 }
 void launch_shade(hipStream_t s, uint32_t qclass, const SceneView& sv, const RenderParams& rp, const WavefrontBuffers& wb, uint32_t b,
-                  uint32_t grid_blocks, const CameraView& cam, const LensView& lens, const EnvView& env, const TraceLaunch* tl, const uint2* list,
+                  uint32_t grid_blocks, const CameraView& cam, const CameraOptics& opt, const EnvView& env, const TraceLaunch* tl, const uint2* list,
                   const uint2* ray_keys)
 {
     const TexView* const tex = tl ? tl->tex : nullptr;
     if (ray_keys) list = nullptr; // (a ray batch has no pixels)
-    const bool lens0 = b == 0u && (lens_set(lens) || ray_keys != nullptr); // only bounce 0 knows of the camera: its rays' origins and the draws they consumed
+    const bool proj0 = b == 0u && proj_set(opt.proj) && ray_keys == nullptr;   // projection (pt_set_projection): origins of their own, ONE draw consumed
+    const bool lens0 = proj0 || (b == 0u && (lens_set(opt.lens) || ray_keys != nullptr)); // only bounce 0 knows of the camera: its rays' origins and the draws they consumed
     ShadeIO io{};
     io.env = env;
     io.primary_a = f4{cam.eye[0], cam.eye[1], cam.eye[2], __builtin_inff()};
@@ -3169,9 +3223,15 @@ void launch_shade(hipStream_t s, uint32_t qclass, const SceneView& sv, const Ren
         else if (list) hipLaunchKernelGGL((k_shade_surface<Q, V, __VA_ARGS__, true, LENS>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), lds, s, ka);  \
         else hipLaunchKernelGGL((k_shade_surface<Q, V, __VA_ARGS__, false, LENS>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), lds, s, ka);      \
     } while (0)
+#define PT_SURF_P(Q, V, ...)                                                                                                            \
+    do {                                                                                                                                 \
+        if (list) hipLaunchKernelGGL((k_shade_surface<Q, V, __VA_ARGS__, true, true, false, false, true>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), lds, s, ka); \
+        else hipLaunchKernelGGL((k_shade_surface<Q, V, __VA_ARGS__, false, true, false, false, true>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), lds, s, ka); \
+    } while (0)
 #define PT_SURF(Q, V, ...)                                                                                                              \
     do {                                                                                                                                 \
-        if (lens0) PT_SURF_L(true, Q, V, __VA_ARGS__);                                                                                   \
+        if (proj0) PT_SURF_P(Q, V, __VA_ARGS__);                                                                                         \
+        else if (lens0) PT_SURF_L(true, Q, V, __VA_ARGS__);                                                                              \
         else PT_SURF_L(false, Q, V, __VA_ARGS__);                                                                                        \
     } while (0)
     // the TEX variants of the same classes (a textured scene queues its shadow rays: shade_traces_shadow)
@@ -3181,9 +3241,15 @@ void launch_shade(hipStream_t s, uint32_t qclass, const SceneView& sv, const Ren
         else if (list) hipLaunchKernelGGL((k_shade_surface<Q, V, false, false, true, LENS, false, true>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), 0, s, kat); \
         else hipLaunchKernelGGL((k_shade_surface<Q, V, false, false, false, LENS, false, true>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), 0, s, kat); \
     } while (0)
+#define PT_SURF_TEX_P(Q, V)                                                                                                            \
+    do {                                                                                                                                 \
+        if (list) hipLaunchKernelGGL((k_shade_surface<Q, V, false, false, true, true, false, true, true>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), 0, s, kat); \
+        else hipLaunchKernelGGL((k_shade_surface<Q, V, false, false, false, true, false, true, true>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), 0, s, kat); \
+    } while (0)
 #define PT_SURF_TEX(Q)                                                                                                                  \
     do {                                                                                                                                 \
-        if (lens0) { if (sv.has_volumes) PT_SURF_TEX_L(true, Q, true); else PT_SURF_TEX_L(true, Q, false); }                             \
+        if (proj0) { if (sv.has_volumes) PT_SURF_TEX_P(Q, true); else PT_SURF_TEX_P(Q, false); }                                        \
+        else if (lens0) { if (sv.has_volumes) PT_SURF_TEX_L(true, Q, true); else PT_SURF_TEX_L(true, Q, false); }                             \
         else { if (sv.has_volumes) PT_SURF_TEX_L(false, Q, true); else PT_SURF_TEX_L(false, Q, false); }                                 \
     } while (0)
     if (tex && qclass != Q_TERMINAL)
@@ -3200,6 +3266,7 @@ void launch_shade(hipStream_t s, uint32_t qclass, const SceneView& sv, const Ren
     }
 #undef PT_SURF_TEX
 #undef PT_SURF_TEX_L
+#undef PT_SURF_TEX_P
     switch (qclass)
     {
     case Q_TERMINAL:
@@ -3228,9 +3295,10 @@ void launch_shade(hipStream_t s, uint32_t qclass, const SceneView& sv, const Ren
     }
 #undef PT_SURF
 #undef PT_SURF_L
+#undef PT_SURF_P
 }
 
-void launch_accumulate(hipStream_t s, const RenderParams& rp, const CameraView& cam, const LensView& lens, const WavefrontBuffers& wb, f4* accum, f4* position,
+void launch_accumulate(hipStream_t s, const RenderParams& rp, const CameraView& cam, const CameraOptics& opt, const WavefrontBuffers& wb, f4* accum, f4* position,
                        uint32_t* id, uint32_t write_position, uint32_t add_to_accum, float* moments, const uint2* list)
 {
     const uint32_t n = list ? rp.act_pixels : rp.local_pixels;
@@ -3239,11 +3307,20 @@ void launch_accumulate(hipStream_t s, const RenderParams& rp, const CameraView& 
     const dim3 grid(quad ? (n * 4u + 255u) / 256u : (n + 255u) / 256u);
     auto go = [&](auto kernel, const auto& camera) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, rp, camera, wb.st, accum, position, id, write_position, add_to_accum, moments, list); };
     // (a list comes with moments: pt_render_adaptive)
-    if (lens_set(lens))
+    if (proj_set(opt.proj))
+    {
+        CameraProjView cp{};
+        static_cast<CameraView&>(cp) = cam;
+        cp.proj = opt.proj;
+        if (list) quad ? go(k_accumulate<true, true, true, false, true>, cp) : go(k_accumulate<false, true, true, false, true>, cp);
+        else if (moments) quad ? go(k_accumulate<true, true, false, false, true>, cp) : go(k_accumulate<false, true, false, false, true>, cp);
+        else quad ? go(k_accumulate<true, false, false, false, true>, cp) : go(k_accumulate<false, false, false, false, true>, cp);
+    }
+    else if (lens_set(opt.lens))
     {
         CameraLensView cl{};
         static_cast<CameraView&>(cl) = cam;
-        cl.lens = lens;
+        cl.lens = opt.lens;
         if (list) quad ? go(k_accumulate<true, true, true, true>, cl) : go(k_accumulate<false, true, true, true>, cl);
         else if (moments) quad ? go(k_accumulate<true, true, false, true>, cl) : go(k_accumulate<false, true, false, true>, cl);
         else quad ? go(k_accumulate<true, false, false, true>, cl) : go(k_accumulate<false, false, false, true>, cl);
@@ -3323,15 +3400,20 @@ void launch_volume_probe(hipStream_t s, const SceneView& sv, int material, uint3
     hipLaunchKernelGGL(k_volume_probe, dim3((n + 255u) / 256u), dim3(256), 0, s, sv, material, n, incoming, t_max, dist, pixel, sample, draws, seed, out9);
 }
 
-void launch_guide_rays(hipStream_t s, const RenderParams& rp, const CameraView& cam, const LensView& lens, RayQueue rq, uint32_t* n_and_heads)
+void launch_guide_rays(hipStream_t s, const RenderParams& rp, const CameraView& cam, const CameraOptics& opt, RayQueue rq, uint32_t* n_and_heads)
 {
-    if (lens_set(lens)) hipLaunchKernelGGL(k_guide_rays_lens, dim3((rp.local_pixels + 255u) / 256u), dim3(256), 0, s, rp, cam, lens, rq, n_and_heads);
+    if (proj_set(opt.proj))
+    {
+        if (opt.proj.kind == PROJ_PANORAMA) hipLaunchKernelGGL(k_guide_rays_proj<PROJ_PANORAMA>, dim3((rp.local_pixels + 255u) / 256u), dim3(256), 0, s, rp, cam, opt.proj, rq, n_and_heads);
+        else hipLaunchKernelGGL(k_guide_rays_proj<PROJ_ORTHOGRAPHIC>, dim3((rp.local_pixels + 255u) / 256u), dim3(256), 0, s, rp, cam, opt.proj, rq, n_and_heads);
+    }
+    else if (lens_set(opt.lens)) hipLaunchKernelGGL(k_guide_rays_lens, dim3((rp.local_pixels + 255u) / 256u), dim3(256), 0, s, rp, cam, opt.lens, rq, n_and_heads);
     else hipLaunchKernelGGL(k_guide_rays, dim3((rp.local_pixels + 255u) / 256u), dim3(256), 0, s, rp, cam, rq, n_and_heads);
 }
-void launch_guide_resolve(hipStream_t s, const SceneView& sv, uint32_t n, const CameraView& cam, const LensView& lens, RayQueue rq, const f4* hits, f4* position,
+void launch_guide_resolve(hipStream_t s, const SceneView& sv, uint32_t n, const CameraView& cam, const CameraOptics& opt, RayQueue rq, const f4* hits, f4* position,
                           f4* normal, uint32_t* model, uint32_t* instance)
 {
-    if (lens_set(lens)) hipLaunchKernelGGL(k_guide_resolve_lens, dim3((n + 255u) / 256u), dim3(256), 0, s, sv, n, cam, rq, hits, position, normal, model, instance);
+    if (lens_set(opt.lens) || proj_set(opt.proj)) hipLaunchKernelGGL(k_guide_resolve_lens, dim3((n + 255u) / 256u), dim3(256), 0, s, sv, n, cam, rq, hits, position, normal, model, instance);
     else hipLaunchKernelGGL(k_guide_resolve, dim3((n + 255u) / 256u), dim3(256), 0, s, sv, n, cam, rq, hits, position, normal, model, instance);
 }
 

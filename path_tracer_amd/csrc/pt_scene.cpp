@@ -1087,6 +1087,7 @@ void HostScene::set_camera(const float eye_[3], const float target_[3], float fo
     const float sx = 1.0f / (std::sqrt(dot3(r.c0, r.c0)) * sgn), sy = 1.0f / std::sqrt(dot3(r.c1, r.c1)), sz = 1.0f / std::sqrt(dot3(r.c2, r.c2));
     const quat q = quat_from_axes(r.c0 * sx, r.c1 * sy, r.c2 * sz);
     euler_yxz_of(q, &camera.pitch, &camera.yaw);
+    camera.aspect = aspect;
     camera.set = true;
 }
 
@@ -1158,6 +1159,33 @@ LensView HostScene::lens_view() const
     return LensView{{r.c0.x, r.c0.y, r.c0.z}, camera.aperture * 0.5f, {r.c1.x, r.c1.y, r.c1.z}, camera.focus};
 }
 
+// the per-ray constants of include/pt_api.h's definitions, each rounded once on the host
+ProjView HostScene::proj_view() const
+{
+    ProjView pv{};
+    pv.kind = camera.proj_kind;
+    if (pv.kind == PROJ_PERSPECTIVE) return pv;
+    const m33& r = camera.matrix.m;
+    pv.c0[0] = r.c0.x; pv.c0[1] = r.c0.y; pv.c0[2] = r.c0.z;
+    pv.c1[0] = r.c1.x; pv.c1[1] = r.c1.y; pv.c1[2] = r.c1.z;
+    if (pv.kind == PROJ_PANORAMA)
+    {
+        const float sx = camera.span_x_deg == 0.0f ? 360.0f : camera.span_x_deg, sy = camera.span_y_deg == 0.0f ? 180.0f : camera.span_y_deg;
+        pv.sx = (sx * 0.5f) * 0.017453292f;
+        pv.sy = (sy * 0.5f) * 0.017453292f;
+        pv.c2[0] = r.c2.x; pv.c2[1] = r.c2.y; pv.c2[2] = r.c2.z;
+    }
+    else
+    {
+        const float hh = camera.ortho_height * 0.5f;
+        pv.sx = hh * camera.aspect;
+        pv.sy = hh;
+        const f3 d = unit3(-r.c2);
+        pv.c2[0] = d.x; pv.c2[1] = d.y; pv.c2[2] = d.z;
+    }
+    return pv;
+}
+
 uint32_t HostScene::primary_ray(uint32_t width, uint32_t height, uint32_t n_sobol, uint64_t seed, uint32_t pixel, uint32_t sample, float o[3], float d[3]) const
 {
     RenderParams rp{};
@@ -1166,6 +1194,14 @@ uint32_t HostScene::primary_ray(uint32_t width, uint32_t height, uint32_t n_sobo
     const LensView lens = lens_view();
     const uint32_t gy = pixel / width, gx = pixel - gy * width;
     f3 org{cv.eye[0], cv.eye[1], cv.eye[2]};
+    const ProjView proj = proj_view();
+    if (proj.kind != PROJ_PERSPECTIVE)
+    {
+        const f3 dir = camera_ray_projected(rp, cv, proj, gx, gy, sample, &org);
+        o[0] = org.x; o[1] = org.y; o[2] = org.z;
+        d[0] = dir.x; d[1] = dir.y; d[2] = dir.z;
+        return 1u;
+    }
     const bool with_lens = lens.radius > 0.0f;
     const f3 dir = with_lens ? camera_ray(rp, cv, lens, gx, gy, sample, &org) : camera_ray_dir(rp, cv, gx, gy, sample);
     o[0] = org.x; o[1] = org.y; o[2] = org.z;

@@ -75,6 +75,11 @@ struct HostCamera
     float ray_matrix[16]; // matrix * inv_projection, column-major
     // thin lens (Camera::new's 5th and 6th argument, camera.rs:17; pt_set_lens).  aperture 0 = pinhole.  Not touched by set_camera or the input
     float aperture = 0, focus = 0;
+    // panoramic / orthographic projection (pt_set_projection): kind PROJ_PERSPECTIVE = the camera above.  Not touched by set_camera or the input
+    // either; aspect is set_camera's (the orthographic view volume's width is its height times it)
+    uint32_t proj_kind = PROJ_PERSPECTIVE;
+    float span_x_deg = 0, span_y_deg = 0, ortho_height = 0;
+    float aspect = 1;
 };
 
 struct FlatScene
@@ -152,7 +157,9 @@ public:
     // what the kernels are given of the camera (CameraView) and of its lens (LensView; radius 0 = pinhole)
     CameraView camera_view() const;
     LensView lens_view() const;
-    // the camera ray of (pixel, sample) as the kernels make it (pt_camera.h), pinhole or lens; returns the stream draws it consumed
+    ProjView proj_view() const; // (kind PROJ_PERSPECTIVE: nothing else is read)
+    CameraOptics optics_view() const { return CameraOptics{lens_view(), proj_view()}; }
+    // the camera ray of (pixel, sample) as the kernels make it (pt_camera.h), pinhole, lens, panoramic or orthographic; returns the stream draws it consumed
     uint32_t primary_ray(uint32_t width, uint32_t height, uint32_t n_sobol, uint64_t seed, uint32_t pixel, uint32_t sample, float o[3], float d[3]) const;
     void inv_projection(float out16[16]) const; // (matrix * inv_projection).inverse()  main.rs:128
     void camera_move(float dx, float dz, float dt);   // Camera::update_origin    camera.rs:33-39

@@ -172,6 +172,25 @@ struct LensView
     float c1[3];   // second rotation column
     float focus;   // distance of the plane of focus along the view axis
 };
+// Panoramic and orthographic cameras (pt_set_projection): the per-ray constants of their camera rays (pt_camera.h), an argument of its own
+// for the projection variants of the camera kernels like LensView.  kind PROJ_PERSPECTIVE: no projection variant is launched.
+enum : uint32_t { PROJ_PERSPECTIVE = 0u, PROJ_PANORAMA = 1u, PROJ_ORTHOGRAPHIC = 2u };
+struct ProjView
+{
+    float c0[3];   // camera matrix, first rotation column
+    uint32_t kind;
+    float c1[3];   // second rotation column
+    float sx;      // PANORAMA: ax = radians of half the azimuth span;    ORTHOGRAPHIC: hw = half the view volume's width
+    float c2[3];   // PANORAMA: third rotation column;                    ORTHOGRAPHIC: the ray direction, -c2 normalised
+    float sy;      // PANORAMA: ay = radians of half the elevation span;  ORTHOGRAPHIC: hh = half the view volume's height
+};
+// what the launchers are told of the camera beyond CameraView (host side only: a kernel takes the one view its variant reads).  At most one
+// of the two is set (pt_set_lens and pt_set_projection exclude each other)
+struct CameraOptics
+{
+    LensView lens;
+    ProjView proj;
+};
 
 // Division by a launch-invariant divisor (Granlund-Montgomery / libdivide "branch-free" form): n / d = (((n - q) >> 1) + q) >> shift
 // with q = mulhi(magic, n), exact for every 32-bit n and d >= 2; d == 1 is flagged.  Built on the host (fastdiv_make).
