@@ -594,6 +594,11 @@ int pt_material_eval(pt_ctx* ctx, int material, uint32_t n, const float* incomin
  * A material without scattering draws nothing; without absorption the transmission is 1. */
 int pt_volume_eval(pt_ctx* ctx, int material, uint32_t n, const float* incoming_xyz, const float* t_max, const float* dist,
                    const uint32_t* pixel, const uint32_t* sample, uint32_t draws_consumed, float* out9);
+/* MaterialTrait::get_bsdf_pdf on the device as next-event estimation calls it (integrator.rs:41-46): at n caller-chosen outgoing
+ * directions (the light's, anywhere on the sphere) instead of the material's own sample; the ray travels along incoming, as in
+ * pt_material_eval.  out[i*4..] = bsdf rgb, pdf.  No draw is consumed. */
+int pt_bsdf_eval(pt_ctx* ctx, int material, uint32_t n, const float* incoming_xyz, const float* outgoing_xyz, const float* normal_xyz,
+                 const uint8_t* front, float* out4);
 
 /* ---- host-builder introspection (CPU only; compared against the oracle's builders) ----------------------------- */
 int pt_blas_count(pt_ctx* ctx);

@@ -94,6 +94,7 @@ def lib():
                                         C.c_uint32, C.c_void_p]
         L.pto_volume_eval.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_float, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32,
                                       C.c_void_p]
+        L.pto_bsdf_eval.argtypes = [C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 5
         _lib = L
     return _lib
 
@@ -307,6 +308,15 @@ class Oracle:
         i = np.ascontiguousarray(incoming, np.float32); n = np.ascontiguousarray(normal, np.float32)
         r = self.L.pto_material_eval(self.ctx, material, _p(i), _p(n), int(front), seed, pixel, sample, draws_consumed, _p(out))
         assert r == 0
+        return out
+
+    def bsdf_eval(self, material, incoming, outgoing, normal, front):
+        """pto_bsdf_eval for n rows: bsdf rgb, pdf of the material at caller-chosen outgoing directions"""
+        i = np.ascontiguousarray(incoming, np.float32); w = np.ascontiguousarray(outgoing, np.float32)
+        n = np.ascontiguousarray(normal, np.float32); f = np.ascontiguousarray(front, np.uint8)
+        out = np.zeros((i.shape[0], 4), np.float32)
+        r = self.L.pto_bsdf_eval(self.ctx, material, i.shape[0], _p(i), _p(w), _p(n), _p(f), _p(out))
+        assert r == 0, r
         return out
 
 

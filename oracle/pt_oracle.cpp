@@ -2004,6 +2004,23 @@ int pto_material_eval(pto_ctx* c, int material, const float incoming[3], const f
     return 0;
 }
 
+// get_bsdf_pdf as sample_light calls it (integrator.rs:41-46): at n caller-chosen outgoing directions; out4[i*4..] = bsdf rgb, pdf
+int pto_bsdf_eval(pto_ctx* c, int material, uint32_t n, const float* incoming, const float* outgoing, const float* normal, const uint8_t* front,
+                  float* out4)
+{
+    if (material < 0 || material >= (int)c->materials.size()) return -1;
+    const Material& m = c->materials[material];
+    for (uint32_t i = 0; i < n; ++i)
+    {
+        V3 in{incoming[3 * i], incoming[3 * i + 1], incoming[3 * i + 2]}, wo{outgoing[3 * i], outgoing[3 * i + 1], outgoing[3 * i + 2]};
+        HitInfo hi{V3{normal[3 * i], normal[3 * i + 1], normal[3 * i + 2]}, 0, 0, 0, front[i] != 0};
+        BsdfPdf bp = m.get_bsdf_pdf(-in, wo, hi);
+        out4[4 * i] = bp.bsdf.x; out4[4 * i + 1] = bp.bsdf.y; out4[4 * i + 2] = bp.bsdf.z;
+        out4[4 * i + 3] = bp.pdf;
+    }
+    return 0;
+}
+
 int pto_volume_eval(pto_ctx* c, int material, const float incoming[3], float t_max, float dist, uint64_t seed, uint32_t pixel, uint32_t sample,
                     uint32_t draws_consumed, float out[9])
 {

@@ -107,6 +107,8 @@ void pto_math_batch(int fn, uint32_t n, const float* a, const float* b, float* o
 int pto_material_eval(pto_ctx*, int material, const float incoming[3], const float normal[3], int front_facing, uint64_t seed,
                       uint32_t pixel, uint32_t sample, uint32_t draws_consumed, float out[9]);
 /* VolumeScatter::scatter + VolumeAbsorption::get_transmission of the material's volume; out = scattered, t, dir xyz, transmission rgb, draws */
+int pto_bsdf_eval(pto_ctx*, int material, uint32_t n, const float* incoming_xyz, const float* outgoing_xyz, const float* normal_xyz,
+                  const uint8_t* front, float* out4);
 int pto_volume_eval(pto_ctx*, int material, const float incoming[3], float t_max, float dist, uint64_t seed, uint32_t pixel, uint32_t sample,
                     uint32_t draws_consumed, float out[9]);
 

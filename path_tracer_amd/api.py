@@ -33,7 +33,7 @@ EXPORTS = [
     "pt_create", "pt_destroy", "pt_last_error", "pt_set_config", "pt_add_material", "pt_add_model", "pt_add_model_obj", "pt_model_vertices", "pt_build", "pt_set_camera",
     "pt_camera_matrices", "pt_set_environment", "pt_create_ray", "pt_set_lens", "pt_primary_ray", "pt_render", "pt_render_device", "pt_reset_accumulation", "pt_accum_device_ptr",
     "pt_read_accumulation", "pt_read_frame", "pt_write_accumulation", "pt_render_samples", "pt_render_adaptive", "pt_adaptive_mask", "pt_read_moments", "pt_write_moments", "pt_active_pixels", "pt_local_rows", "pt_set_stream", "pt_synchronize", "pt_camera_input", "pt_camera_angles", "pt_frame", "pt_inv_projection", "pt_present", "pt_post_velocity", "pt_post_reproject", "pt_post_tonemap", "pt_post_rgb8", "pt_present_rgb8", "pt_write_image", "pt_trace_closest", "pt_trace_any",
-    "pt_ss_sobol", "pt_math_batch", "pt_material_eval", "pt_volume_eval", "pt_blas_count", "pt_blas_dump", "pt_tlas_dump", "pt_tlas_instances", "pt_instance_materials", "pt_light_cdf",
+    "pt_ss_sobol", "pt_math_batch", "pt_material_eval", "pt_volume_eval", "pt_bsdf_eval", "pt_blas_count", "pt_blas_dump", "pt_tlas_dump", "pt_tlas_instances", "pt_instance_materials", "pt_light_cdf",
     "pt_triangle_dump", "pt_get_stats", "pt_reset_stats", "pt_last_batch_counters", "pt_last_batch_shade_pids", "pt_last_batch_step_stats",
     "pt_multi_create", "pt_multi_destroy", "pt_multi_last_error", "pt_multi_ctx", "pt_multi_render", "pt_multi_framebuffer_device_ptr",
     "pt_multi_reset_accumulation", "pt_multi_get_stats", "pt_multi_used_rccl", "pt_multi_write_image",
@@ -205,6 +205,7 @@ def lib():
         L.pt_math_batch.argtypes = [vp, C.c_int, u32, vp, vp, vp, vp]
         L.pt_material_eval.argtypes = [vp, C.c_int, u32, vp, vp, vp, vp, vp, u32, vp]
         L.pt_volume_eval.argtypes = [vp, C.c_int, u32, vp, vp, vp, vp, vp, u32, vp]
+        L.pt_bsdf_eval.argtypes = [vp, C.c_int, u32, vp, vp, vp, vp, vp]
         L.pt_blas_count.argtypes = [vp]
         L.pt_blas_dump.argtypes = [vp, C.c_int] + [vp] * 8 + [u32, u32]
         L.pt_tlas_dump.argtypes = [vp, C.c_int] + [vp] * 6 + [u32]
@@ -849,6 +850,14 @@ class Renderer:
         px = np.ascontiguousarray(pixel, np.uint32); sm = np.ascontiguousarray(sample, np.uint32)
         out = np.zeros((i.shape[0], 9), np.float32)
         self._chk(self.L.pt_volume_eval(self.ctx, material, i.shape[0], _p(i), _p(tm), _p(d), _p(px), _p(sm), draws_consumed, _p(out)))
+        return out
+
+    def bsdf_eval(self, material, incoming, outgoing, normal, front):
+        """[n, 4]: bsdf rgb, pdf of the material at caller-chosen outgoing directions, as next-event estimation asks (pt_bsdf_eval)"""
+        i = np.ascontiguousarray(incoming, np.float32); w = np.ascontiguousarray(outgoing, np.float32)
+        n = np.ascontiguousarray(normal, np.float32); f = np.ascontiguousarray(front, np.uint8)
+        out = np.zeros((i.shape[0], 4), np.float32)
+        self._chk(self.L.pt_bsdf_eval(self.ctx, material, i.shape[0], _p(i), _p(w), _p(n), _p(f), _p(out)))
         return out
 
     def model_vertices(self, model):

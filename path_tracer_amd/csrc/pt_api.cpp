@@ -2871,6 +2871,26 @@ int pt_volume_eval(pt_ctx* c, int material, uint32_t n, const float* incoming, c
     return t.download(out9, dout, (size_t)n * 36);
 }
 
+int pt_bsdf_eval(pt_ctx* c, int material, uint32_t n, const float* incoming, const float* outgoing, const float* normal, const uint8_t* front,
+                 float* out4)
+{
+    if (!c || !incoming || !outgoing || !normal || !front || !out4) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (material < 0 || material >= (int)c->scene.materials.size()) return fail(c, PT_ERR_ARG, "material index");
+    if (n == 0) return PT_OK;
+    int r;
+    if ((r = upload_scene(c))) return r;
+    Staging t(c);
+    const float* di = (const float*)t.in(incoming, (size_t)n * 12);
+    const float* dw = (const float*)t.in(outgoing, (size_t)n * 12);
+    const float* dn = (const float*)t.in(normal, (size_t)n * 12);
+    const uint8_t* df = (const uint8_t*)t.in(front, n);
+    float* dout = (float*)t.out((size_t)n * 16);
+    if (t.err) return t.err;
+    launch_bsdf_probe(c->stream, c->sv, material, n, di, dw, dn, df, dout);
+    return t.download(out4, dout, (size_t)n * 16);
+}
+
 // ---- host-builder introspection
 int pt_blas_count(pt_ctx* c) { return (c && c->scene.built) ? (int)c->scene.blas.size() : PT_ERR_STATE; }
 

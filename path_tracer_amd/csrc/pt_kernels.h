@@ -187,5 +187,7 @@ void launch_material_probe(hipStream_t s, const SceneView& sv, int material, uin
                            const uint8_t* front, const uint32_t* pixel, const uint32_t* sample, uint32_t draws, uint64_t seed, float* out9);
 void launch_volume_probe(hipStream_t s, const SceneView& sv, int material, uint32_t n, const float* incoming, const float* t_max, const float* dist,
                          const uint32_t* pixel, const uint32_t* sample, uint32_t draws, uint64_t seed, float* out9);
+void launch_bsdf_probe(hipStream_t s, const SceneView& sv, int material, uint32_t n, const float* incoming, const float* outgoing,
+                       const float* normal, const uint8_t* front, float* out4);
 
 } // namespace pt

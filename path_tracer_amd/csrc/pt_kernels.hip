@@ -2835,6 +2835,22 @@ __global__ void k_volume_probe(const SceneView sv, int material, uint32_t n, con
     o[8] = (float)(rng.k - draws);
 }
 
+// MaterialTrait::get_bsdf_pdf as next-event estimation calls it (integrator.rs:41-46): at a caller-chosen outgoing direction, which is the
+// light's and need not lie anywhere near the lobe.  out4[i*4..] = bsdf rgb, pdf of mat_bsdf_pdf(m, -incoming, outgoing, normal, front)
+__global__ void k_bsdf_probe(const SceneView sv, int material, uint32_t n, const float* incoming, const float* outgoing, const float* normal,
+                             const uint8_t* front, float* out4)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const MatView m = load_material(sv.materials, (uint32_t)material);
+    const f3 in{incoming[3 * i], incoming[3 * i + 1], incoming[3 * i + 2]}, wo{outgoing[3 * i], outgoing[3 * i + 1], outgoing[3 * i + 2]};
+    const f3 nn{normal[3 * i], normal[3 * i + 1], normal[3 * i + 2]};
+    const BsdfSample bp = mat_bsdf_pdf(m, -in, wo, nn, front[i] != 0);
+    float* o = out4 + 4 * i;
+    o[0] = bp.bsdf.x; o[1] = bp.bsdf.y; o[2] = bp.bsdf.z;
+    o[3] = bp.pdf;
+}
+
 // ------------------------------------------------------------------------------------------------ denoiser guides (pt_render_guides)
 // The camera ray of sample rp.first_sample of EVERY local pixel (no active rectangle: a ray outside it is answered by the root-box test)
 // as one ray of a hook queue, ray index = local pixel: exactly the ray k_generate makes for that (pixel, sample).
@@ -3398,6 +3414,11 @@ void launch_volume_probe(hipStream_t s, const SceneView& sv, int material, uint3
                          const uint32_t* pixel, const uint32_t* sample, uint32_t draws, uint64_t seed, float* out9)
 {
     hipLaunchKernelGGL(k_volume_probe, dim3((n + 255u) / 256u), dim3(256), 0, s, sv, material, n, incoming, t_max, dist, pixel, sample, draws, seed, out9);
+}
+void launch_bsdf_probe(hipStream_t s, const SceneView& sv, int material, uint32_t n, const float* incoming, const float* outgoing,
+                       const float* normal, const uint8_t* front, float* out4)
+{
+    hipLaunchKernelGGL(k_bsdf_probe, dim3((n + 255u) / 256u), dim3(256), 0, s, sv, material, n, incoming, outgoing, normal, front, out4);
 }
 
 void launch_guide_rays(hipStream_t s, const RenderParams& rp, const CameraView& cam, const CameraOptics& opt, RayQueue rq, uint32_t* n_and_heads)
