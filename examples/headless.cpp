@@ -19,6 +19,10 @@
 //   examples/headless ... --bake-probes NX NY NZ SPP probes.txt   after the usual render, bakes SPP samples into an NX x NY x NZ grid of
 //       irradiance probes spanning the scene's bounds shrunk by 5 % per side (x fastest, then y, then z; stream keys 0, 1, ...) and
 //       writes one line per probe: its 27 raw spherical-harmonics sums [k][c] as hexadecimal floats (%a)
+//   examples/headless ... --bake-lightmap W H SPP PASSES map.txt   after the usual render, bakes SPP samples per texel into a W x H lightmap of the floor,
+//       ceiling and back wall (cb_main.obj, model 1) under --checker's planar UVs, in which floor and ceiling overlap and the lower triangle index
+//       wins (rays start 0.25 off the surface, stream keys = texel indices), dilates it PASSES times and writes one line per texel:
+//       its coverage byte (1 baked, 2 dilated, 0 neither) and the three raw sums as hexadecimal floats (%a)
 //   examples/headless ... --checker N   an N x N checker (texels 1 and 0.2, bilinear, repeating) on the floor, ceiling and back wall (cb_main.obj) with
 //                                        planar UVs: a vertex's (x, z) over the model's own extent in x and z
 #include <algorithm>
@@ -46,6 +50,8 @@ int main(int argc, char** argv)
     float aperture = 0.0f, focus = 950.0f; // main.rs:127's values: a pinhole
     uint32_t probes[3] = {0, 0, 0}, probe_spp = 0, checker = 0;
     std::string probes_out = "";
+    uint32_t lightmap[4] = {0, 0, 0, 0}; // W H SPP PASSES
+    std::string lightmap_out = "";
     pt_projection projection{}; // PT_PROJ_PERSPECTIVE
     for (int i = 1; i < argc; ++i)
     {
@@ -86,6 +92,11 @@ int main(int argc, char** argv)
             probe_spp = (uint32_t)std::atoi(next("--bake-probes"));
             probes_out = next("--bake-probes");
         }
+        else if (a == "--bake-lightmap")
+        {
+            for (uint32_t& n : lightmap) n = (uint32_t)std::atoi(next("--bake-lightmap"));
+            lightmap_out = next("--bake-lightmap");
+        }
         else if (a == "--load-state") load_state = next("--load-state");
         else if (a == "--save-state") save_state = next("--save-state");
         else if (a == "--devices")
@@ -95,7 +106,7 @@ int main(int argc, char** argv)
         }
         else if (a == "--help" || a == "-h")
         {
-            std::printf("usage: %s [--width W] [--height H] [--frames N] [--bounces B] [--move] [--slide DX DZ] [--models DIR] [--out file.png] [--denoise file.png] [--denoise-albedo file.png] [--aperture A --focus F] [--projection panorama[:SX:SY]|ortho:HEIGHT] [--bake-probes NX NY NZ SPP file.txt] [--checker N]\n", argv[0]);
+            std::printf("usage: %s [--width W] [--height H] [--frames N] [--bounces B] [--move] [--slide DX DZ] [--models DIR] [--out file.png] [--denoise file.png] [--denoise-albedo file.png] [--aperture A --focus F] [--projection panorama[:SX:SY]|ortho:HEIGHT] [--bake-probes NX NY NZ SPP file.txt] [--bake-lightmap W H SPP PASSES file.txt] [--checker N]\n", argv[0]);
             return 0;
         }
         else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
@@ -150,7 +161,7 @@ int main(int argc, char** argv)
         }
         Renderer renderer(scene, cam, width, height, bounces);
         renderer.set_projection(projection);
-        if (checker)
+        if (checker || !lightmap_out.empty())
         {
             const std::vector<float> p = renderer.model_positions(1);
             float lo[2] = {p[0], p[2]}, hi[2] = {p[0], p[2]};
@@ -187,6 +198,18 @@ int main(int argc, char** argv)
             if (!f) { std::fprintf(stderr, "cannot write %s\n", probes_out.c_str()); return false; }
             for (size_t j = 0; j < pos.size() / 3; ++j)
                 for (int k = 0; k < 27; ++k) std::fprintf(f, "%a%c", (double)sh[j * 27 + k], k == 26 ? '\n' : ' ');
+            std::fclose(f);
+            return true;
+        };
+        // a lightmap for a run-time consumer: the room's shell under the planar UVs above, baked by the path tracer and dilated
+        auto bake_lightmap = [&]() -> bool {
+            if (lightmap_out.empty()) return true;
+            std::vector<float> sums;
+            std::vector<uint8_t> cov = renderer.bake_lightmap(1, 0, lightmap[0], lightmap[1], lightmap[2], sums, 0, 0, 0.25f);
+            renderer.dilate_lightmap(lightmap[0], lightmap[1], lightmap[3], sums, cov);
+            std::FILE* f = std::fopen(lightmap_out.c_str(), "w");
+            if (!f) { std::fprintf(stderr, "cannot write %s\n", lightmap_out.c_str()); return false; }
+            for (size_t k = 0; k < cov.size(); ++k) std::fprintf(f, "%u %a %a %a\n", (unsigned)cov[k], (double)sums[3 * k], (double)sums[3 * k + 1], (double)sums[3 * k + 2]);
             std::fclose(f);
             return true;
         };
@@ -228,7 +251,7 @@ int main(int argc, char** argv)
             std::printf("{\"first_sample\": %u, \"samples\": %u, \"width\": %u, \"height\": %u}\n", render_first, render_count, width, height);
             if (!out.empty()) renderer.write_image(out);
             if (!denoise_albedo_out.empty() && render_count) denoise_albedo(render_first, render_count);
-            return bake_probes() ? 0 : 1;
+            return bake_probes() && bake_lightmap() ? 0 : 1;
         }
         Mat4 last_inv_proj = renderer.inv_projection();
 
@@ -266,7 +289,7 @@ int main(int argc, char** argv)
             renderer.write_denoised_image(denoise_out);
         }
         if (!denoise_albedo_out.empty() && frames) denoise_albedo(0, frames);
-        if (!bake_probes()) return 1;
+        if (!bake_probes() || !bake_lightmap()) return 1;
     }
     catch (const Error& e)
     {

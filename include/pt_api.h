@@ -574,6 +574,77 @@ int pt_bake_probes(pt_ctx* ctx, uint32_t n_probes, const float* position_xyz, co
 /* direction d and basis values y0..y8 of sample `sample` of the probe whose stream is pixel `key`, as the bake makes them.  Host evaluation, no GPU. */
 int pt_probe_ray(pt_ctx* ctx, uint32_t key, uint32_t sample, float d[3], float y9[9]);
 
+/* ---- lightmaps: per-texel sums of incident radiance over a model's UV layout, cosine-distributed, made and folded on the device ------ */
+/* A lightmap belongs to ONE placement of ONE model: `model` is the model index, `instance` the index into that model's instance matrices as last
+ * given to pt_add_model* / pt_set_instances.  The model's UVs (pt_set_model_uvs, `vt` lines of an OBJ) are its lightmap layout; the map is w x h
+ * texels and texel (i, j) has index k = j * w + i.  There is no repeat addressing here: UVs outside [0, 1]^2 cover nothing.
+ *
+ * COVERAGE, in binary64, every operation rounded once, no contraction; float UVs are converted to double first.
+ *     p = ((double)i + 0.5) / (double)w , ((double)j + 0.5) / (double)h
+ *     E(p, q, r) = (q.s - p.s) * (r.t - p.t) - (q.t - p.t) * (r.s - p.s)
+ *     for triangle T of the model in load order, UVs a, b, c:
+ *         A = E(a, b, c);  skip T if A == 0
+ *         u = E(a, p, c) / A;  v = E(a, b, p) / A
+ *         T contains p  iff  u >= 0 && v >= 0 && u + v <= 1
+ *     texel k is COVERED by the lowest-indexed triangle that contains p; prim = its index, (u, v) = that triangle's values rounded to binary32
+ *   Either winding of a UV triangle works (the signed area normalises it); a centre on a shared edge belongs to the lower index; overlapping
+ *   charts are the caller's problem and still deterministic.  A texel whose centre no triangle contains is UNCOVERED and is never written.
+ *   A triangle is only asked about the centres of columns floor(min s * w) - 1 .. floor(max s * w) + 1 and the rows alike (min, max over its
+ *   three UVs, the products in binary64), clamped to the map: its UV bounding box and a ring of one texel, which holds every centre the
+ *   predicate accepts unless the triangle is degenerate to within rounding.
+ * SURFACE POINT AND NORMAL of a covered texel, binary32 from here on, one rounding per operation, no contraction.  Pa, Pb, Pc and Na, Nb, Nc
+ * are the triangle's load-order vertex positions and normals, M the instance's forward 3x4 (columns c0 c1 c2, translation t).
+ *     P_obj = (Pa + u * (Pb - Pa)) + v * (Pc - Pa)                       -- per component, as the UV interpolation of pt_add_texture
+ *     wgt = 1 - u - v;   n_obj = unit3((Na * wgt + Nb * u) + Nc * v)     -- the shading normal of a hit, WITHOUT its face-forward flip
+ *     P = ((M.c0 * P_obj.x + M.c1 * P_obj.y) + M.c2 * P_obj.z) + M.t
+ *     n = (M.c0 * n_obj.x + M.c1 * n_obj.y) + M.c2 * n_obj.z             -- not renormalised
+ *     o = P + bias * n                                                   -- two roundings per component
+ * SAMPLE s of texel k:
+ *     seed0 = draw 0 of the stream (key_base + k, s);  (u1, u2) = ss_sobol(n_sobol, s, seed0)            -- as main.rs:193-194
+ *     r = sqrt(u1);  z = sqrt(1 - r * r);  phi = 6.2831855f * u2;  (sn, cs) = sincos_det(phi)            -- utility.rs:7-19 on a Sobol point
+ *     d = onb_from_normal(n) * (cs * r, sn * r, z)                                                       -- material/onb.rs:1-7, Mat3A * Vec3A
+ *     L = radiance of pt_integrate_rays for (o, d, key = key_base + k, sample = s, draws_consumed = 1)
+ *     sum[k][c] = sum[k][c] + L[c]        for s ascending, c = r, g, b
+ * rgb_sum (host, w * h * 3 floats) is IN/OUT: the sums continue from what it holds, so bake(0, a) followed by bake(a, b) is bake(0, a + b) bit
+ * for bit.  The sums are RAW: with cosine-distributed directions the irradiance is pi * sum / n, and that factor is the caller's.  The key is the
+ * TEXEL INDEX, not the covered rank: a texel's result depends on nothing but the scene, the config, its own triangle and (key_base, s, bias) -
+ * not on the other texels, the batch cut, the ray order, where the BVH lives or the walk variant.  The rays go through pt_integrate_rays'
+ * batches texel-major (covered texels ascending) with a texel's samples consecutive, at most 2^26 to a table; pt_config.batch_spp cuts here too:
+ * wavefront batches of batch_spp * covered rays, three to a table.  The frame is not touched; pt_stats.paths grows by covered * n_samples.
+ * coverage (host, w * h bytes, may be NULL) receives 1 for a covered texel and 0 otherwise.  Blocking.
+ * Errors, all before any device call (a refused call changes nothing): PT_ERR_STATE as pt_integrate_rays, and for a model without UVs;
+ * PT_ERR_ARG for a bad model or instance index, w or h of 0, n_samples == 0, a bias that is not finite, a NULL p or rgb_sum, a non-zero
+ * reserved word, key_base + w * h or first_sample + n_samples beyond 2^32; PT_ERR_LIMIT for a side above 16384 or more than 2^26 texels.
+ * A map with no covered texel is PT_OK and integrates nothing.
+ * Out of scope: unwrapping and atlas packing, conservative or supersampled coverage, direct light sampled at the texel, directional maps,
+ * denoising, feeding a baked map back into a render, pt_multi_* variants. */
+typedef struct pt_lightmap_params
+{
+    int32_t model;                    /* model index */
+    uint32_t instance;                /* index into that model's instance matrices */
+    uint32_t w, h;                    /* texels */
+    uint32_t first_sample, n_samples; /* samples [first_sample, first_sample + n_samples) of every covered texel */
+    uint32_t key_base;                /* texel k draws from the stream of pixel key_base + k */
+    float bias;                       /* the rays start at P + bias * n */
+    uint32_t reserved[4];             /* must be 0 */
+} pt_lightmap_params;
+int pt_bake_lightmap(pt_ctx* ctx, const pt_lightmap_params* p, float* rgb_sum, uint8_t* coverage);
+/* the texel table of a map, the unit hook of the above (host pointers, any may be NULL): prim w * h words, 0xffffffff for an uncovered texel;
+ * uv2 (u, v); position_xyz P; normal_xyz n; an uncovered texel gets zeros in the last three.  on_device = 0 evaluates on the host and touches
+ * no GPU; on_device = 1 runs the bake's own kernels.  Errors as pt_bake_lightmap's for model, instance, w and h (NEE without a light is no
+ * error here: nothing is integrated). */
+int pt_lightmap_texels(pt_ctx* ctx, int model, uint32_t instance, uint32_t w, uint32_t h, int on_device, uint32_t* prim, float* uv2,
+                       float* position_xyz, float* normal_xyz);
+/* direction d of sample `sample` of the texel whose stream is pixel `key` (key_base + k) over the normal n, as the bake makes it.  Host evaluation, no GPU. */
+int pt_lightmap_ray(pt_ctx* ctx, uint32_t key, uint32_t sample, const float normal[3], float d[3]);
+/* DILATION.  Centre sampling leaves the texels along chart borders uncovered, and bilinear filtering of the finished map then bleeds black into
+ * the charts.  One pass: every texel whose coverage byte is 0 and that has at least one of its eight neighbours (no wrap at the borders) with
+ * a non-zero byte at the start of the pass takes, per channel, (0 + the values of those neighbours, added in the order dy = -1..1 outer,
+ * dx = -1..1 inner, binary32) / (float)count, and its byte becomes 2.  `passes` passes run with ping-pong buffers on the device; rgb (w * h * 3
+ * floats: sums or finished irradiance alike) and coverage (w * h bytes) are IN/OUT host pointers.  PT_ERR_ARG for a NULL pointer or a side of
+ * 0, PT_ERR_LIMIT as pt_bake_lightmap, both before any device call; passes == 0 does nothing. */
+int pt_lightmap_dilate(pt_ctx* ctx, uint32_t w, uint32_t h, uint32_t passes, float* rgb, uint8_t* coverage);
+
 /* ---- unit hooks: TLAS::intersect / any_intersect  src/tlas.rs:66, 111 ------------------------------------------ */
 /* which: 0 world TLAS, 1 lights TLAS.  Host SoA in, host SoA out.  miss => inst = prim = 0xffffffff, t = +inf.
  * inst = TLAS leaf index in allocation order, prim = triangle index inside its BLAS (load order). */

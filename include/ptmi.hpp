@@ -363,6 +363,28 @@ public:
     }
     // direction and y0..y8 of a probe sample as bake_probes makes them (host evaluation)
     void probe_ray(uint32_t key, uint32_t sample, float d[3], float y9[9]) const { check(pt_probe_ray(ctx_, key, sample, d, y9)); }
+    // a lightmap of one placement of a model over its UVs (pt_bake_lightmap): adds samples [first_sample, first_sample + n_samples) of every
+    // covered texel to the raw sums rgb_sum (w * h * 3; empty: a fresh bake from zero) and returns the coverage bytes (1 covered, 0 not)
+    std::vector<uint8_t> bake_lightmap(int model, uint32_t instance, uint32_t w, uint32_t h, uint32_t n_samples, std::vector<float>& rgb_sum,
+                                       uint32_t first_sample = 0, uint32_t key_base = 0, float bias = 0.0f)
+    {
+        const size_t px = (size_t)w * h;
+        if (rgb_sum.empty()) rgb_sum.assign(px * 3, 0.0f);
+        if (rgb_sum.size() != px * 3) throw Error(PT_ERR_ARG, "bake_lightmap: rgb_sum does not hold 3 values per texel");
+        std::vector<uint8_t> coverage(px);
+        pt_lightmap_params p{};
+        p.model = model; p.instance = instance; p.w = w; p.h = h;
+        p.first_sample = first_sample; p.n_samples = n_samples; p.key_base = key_base; p.bias = bias;
+        check(pt_bake_lightmap(ctx_, &p, rgb_sum.data(), coverage.data()));
+        return coverage;
+    }
+    // `passes` dilation passes over a w x h map and its coverage bytes (pt_lightmap_dilate); filled texels carry the byte 2
+    void dilate_lightmap(uint32_t w, uint32_t h, uint32_t passes, std::vector<float>& rgb, std::vector<uint8_t>& coverage)
+    {
+        const size_t px = (size_t)w * h;
+        if (rgb.size() != px * 3 || coverage.size() != px) throw Error(PT_ERR_ARG, "dilate_lightmap: rgb holds 3 values and coverage one byte per texel");
+        check(pt_lightmap_dilate(ctx_, w, h, passes, rgb.data(), coverage.data()));
+    }
     // the world TLAS's root box: min xyz, max xyz
     std::array<float, 6> root_box() const { uint32_t rect[4]; std::array<float, 6> b{}; check(pt_active_pixels(ctx_, rect, b.data())); return b; }
     pt_stats stats() const { pt_stats s{}; check(pt_get_stats(ctx_, &s)); return s; }

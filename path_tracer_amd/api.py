@@ -43,6 +43,7 @@ EXPORTS = [
     "pt_add_texture", "pt_set_material_texture", "pt_set_model_uvs", "pt_model_uvs", "pt_surface_colour", "pt_read_guide_albedo",
     "pt_accumulate_albedo", "pt_reset_albedo", "pt_read_albedo", "pt_denoise_albedo", "pt_post_denoise_albedo",
     "pt_set_projection", "pt_get_projection",
+    "pt_bake_lightmap", "pt_lightmap_texels", "pt_lightmap_ray", "pt_lightmap_dilate",
 ]
 
 
@@ -101,6 +102,12 @@ class RaysParams(C.Structure):
 class ProbeParams(C.Structure):
     """pt_probe_params: the sample range and stream keys of a probe bake (include/pt_api.h)"""
     _fields_ = [("first_sample", C.c_uint32), ("n_samples", C.c_uint32), ("key_base", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class LightmapParams(C.Structure):
+    """pt_lightmap_params: the placement, size, sample range, stream keys and ray bias of a lightmap bake (include/pt_api.h)"""
+    _fields_ = [("model", C.c_int32), ("instance", C.c_uint32), ("w", C.c_uint32), ("h", C.c_uint32), ("first_sample", C.c_uint32),
+                ("n_samples", C.c_uint32), ("key_base", C.c_uint32), ("bias", C.c_float), ("reserved", C.c_uint32 * 4)]
 
 
 class SceneInfo(C.Structure):
@@ -242,6 +249,10 @@ def lib():
         L.pt_read_albedo.argtypes = [vp, vp]
         L.pt_denoise_albedo.argtypes = [vp, C.POINTER(DenoiseParams), u32, vp]
         L.pt_post_denoise_albedo.argtypes = [vp, u32, u32, C.POINTER(DenoiseParams), vp, vp, vp, vp, vp, vp, vp]
+        L.pt_bake_lightmap.argtypes = [vp, C.POINTER(LightmapParams), vp, vp]
+        L.pt_lightmap_texels.argtypes = [vp, C.c_int, u32, u32, u32, C.c_int, vp, vp, vp, vp]
+        L.pt_lightmap_ray.argtypes = [vp, u32, u32, vp, vp]
+        L.pt_lightmap_dilate.argtypes = [vp, u32, u32, u32, vp, vp]
         _lib = L
     return _lib
 
@@ -802,6 +813,43 @@ class Renderer:
         d = np.zeros(3, np.float32); y = np.zeros(9, np.float32)
         self._chk(self.L.pt_probe_ray(self.ctx, key, sample, _p(d), _p(y)))
         return d, y
+
+    # ---- lightmaps
+    def bake_lightmap(self, model, instance, w, h, n_samples, first_sample=0, key_base=0, bias=0.0, sums=None):
+        """A lightmap of one placement of a model over its UV layout (pt_bake_lightmap): adds samples [first_sample, first_sample + n_samples) of
+        every covered texel to the raw sums (h, w, 3) float32 (None: a fresh bake from zero) and returns (sums, coverage (h, w) uint8).  With
+        cosine-distributed directions the irradiance is pi * sums / samples; that factor is the caller's."""
+        out = np.zeros((h, w, 3), np.float32) if sums is None else np.ascontiguousarray(sums, np.float32)
+        if out.size != w * h * 3:
+            raise PtError(-1, "bake_lightmap: sums does not hold 3 values per texel")
+        cov = np.zeros((h, w), np.uint8)
+        prm = LightmapParams(model, instance, w, h, first_sample, n_samples, key_base, bias)
+        self._chk(self.L.pt_bake_lightmap(self.ctx, C.byref(prm), _p(out), _p(cov)))
+        return out.reshape(h, w, 3), cov
+
+    def lightmap_texels(self, model, instance, w, h, on_device=False):
+        """unit hook: the texel table of a map, (prim (h, w) uint32 with 0xffffffff for an uncovered texel, uv (h, w, 2), position (h, w, 3),
+        normal (h, w, 3)); on the host (no GPU) unless on_device"""
+        prim = np.zeros((h, w), np.uint32); uv = np.zeros((h, w, 2), np.float32)
+        pos = np.zeros((h, w, 3), np.float32); nrm = np.zeros((h, w, 3), np.float32)
+        self._chk(self.L.pt_lightmap_texels(self.ctx, model, instance, w, h, int(bool(on_device)), _p(prim), _p(uv), _p(pos), _p(nrm)))
+        return prim, uv, pos, nrm
+
+    def lightmap_ray(self, key: int, sample: int, normal):
+        """direction of sample `sample` of the texel whose stream is pixel `key` over `normal`, as bake_lightmap makes it; host evaluation"""
+        n = np.ascontiguousarray(normal, np.float32).reshape(3)
+        d = np.zeros(3, np.float32)
+        self._chk(self.L.pt_lightmap_ray(self.ctx, key, sample, _p(n), _p(d)))
+        return d
+
+    def dilate_lightmap(self, rgb, coverage, passes=1):
+        """`passes` dilation passes (pt_lightmap_dilate) of a map (h, w, 3) float32 with coverage bytes (h, w); returns new (rgb, coverage),
+        filled texels carrying the byte 2"""
+        a = np.array(rgb, np.float32, order="C"); cv = np.array(coverage, np.uint8, order="C")
+        if a.ndim != 3 or a.shape[2] != 3 or cv.shape != a.shape[:2]:
+            raise PtError(-1, "dilate_lightmap: rgb is (h, w, 3) and coverage (h, w)")
+        self._chk(self.L.pt_lightmap_dilate(self.ctx, a.shape[1], a.shape[0], passes, _p(a), _p(cv)))
+        return a, cv
 
     # ---- unit hooks
     def trace_closest(self, o, d, tmax=None, which=0):

@@ -19,6 +19,7 @@
 #include "pt_batch_plan.h"
 #include "pt_kernels.h"
 #include "pt_png.h"
+#include "pt_lightmap.h"
 #include "pt_probe.h"
 #include "pt_scene.h"
 
@@ -1372,6 +1373,85 @@ int rays_args_check(pt_ctx* c, uint64_t n, const float* o, const float* d, const
     return PT_OK;
 }
 
+// ---- lightmaps (pt_bake_lightmap; the arithmetic is pt_lightmap.h's)
+// what every lightmap call checks of its map before anything else happens
+int lightmap_check(pt_ctx* c, int model, uint32_t instance, uint32_t w, uint32_t h)
+{
+    if (!c->scene.built) return fail(c, PT_ERR_STATE, "pt_build has not been called");
+    if (model < 0 || model >= (int)c->scene.models.size()) return fail(c, PT_ERR_ARG, "lightmap: model index");
+    const HostModel& m = c->scene.models[model];
+    if (instance >= m.matrices.size()) return fail(c, PT_ERR_ARG, "lightmap: instance index");
+    if (w == 0 || h == 0) return fail(c, PT_ERR_ARG, "lightmap: w and h must be non-zero");
+    if (w > 16384u || h > 16384u || (uint64_t)w * h > (1ull << 26)) return fail(c, PT_ERR_LIMIT, "lightmap: a side is at most 16384 texels and a map holds at most 2^26");
+    if (m.uvs.empty()) return fail(c, PT_ERR_STATE, "lightmap: the model has no UVs (pt_set_model_uvs)");
+    return PT_OK;
+}
+
+// owner[k] = the lowest triangle index whose UVs contain the centre of texel k, MISS_ID where none does: the walk k_lm_cover does, triangle by
+// triangle over its texel rectangle, with a running minimum in the atomic's place
+void lightmap_owner_host(const HostModel& m, uint32_t w, uint32_t h, std::vector<uint32_t>& owner)
+{
+    owner.assign((size_t)w * h, MISS_ID);
+    for (uint32_t t = 0; t < m.n_tris; ++t)
+    {
+        const float* uv = m.uvs.data() + 6u * (size_t)t;
+        LmBox box;
+        if (!lm_box(uv, w, h, &box)) continue;
+        for (uint32_t j = box.j0; j < box.j0 + box.bh; ++j)
+            for (uint32_t i = box.i0; i < box.i0 + box.bw; ++i)
+            {
+                double u, v;
+                uint32_t& o = owner[(size_t)j * w + i];
+                if (t < o && lm_contains(uv, lm_centre(i, w), lm_centre(j, h), &u, &v)) o = t;
+            }
+    }
+}
+
+// the coverage launch's work items: every triangle's texel rectangle in slices of kLightmapSlice texels
+std::vector<uint2> lightmap_items(const HostModel& m, uint32_t w, uint32_t h)
+{
+    std::vector<uint2> items;
+    for (uint32_t t = 0; t < m.n_tris; ++t)
+    {
+        LmBox box;
+        if (!lm_box(m.uvs.data() + 6u * (size_t)t, w, h, &box)) continue;
+        const uint32_t n = box.bw * box.bh;
+        for (uint32_t first = 0; first < n; first += kLightmapSlice) items.push_back(make_uint2(t, first));
+    }
+    return items;
+}
+
+// the texel table of a map on the device, in buffers of `st`: coverage and resolve.  The model's load-order arrays and the one matrix are
+// uploaded for the call; the resident scene is not involved.
+struct LightmapDev
+{
+    uint32_t* prim;
+    float *uv2, *position, *normal;
+    uint8_t* coverage;
+};
+int lightmap_texels_device(pt_ctx* c, Staging& st, const HostModel& m, uint32_t instance, uint32_t w, uint32_t h, LightmapDev& out)
+{
+    const size_t px = (size_t)w * h;
+    const std::vector<uint2> items = lightmap_items(m, w, h);
+    LightmapView lm{};
+    lm.uv = (const float*)st.in(m.uvs.data(), (size_t)m.n_tris * 24);
+    lm.positions = (const float*)st.in(m.positions.data(), (size_t)m.n_tris * 36);
+    lm.normals = (const float*)st.in(m.normals.data(), (size_t)m.n_tris * 36);
+    lm.n_tris = m.n_tris; lm.w = w; lm.h = h;
+    lm.m = m.matrices[instance];
+    const uint2* d_items = items.empty() ? nullptr : (const uint2*)st.in(items.data(), items.size() * 8);
+    out.prim = (uint32_t*)st.out(px * 4);
+    out.uv2 = (float*)st.out(px * 8);
+    out.position = (float*)st.out(px * 12);
+    out.normal = (float*)st.out(px * 12);
+    out.coverage = (uint8_t*)st.out(px);
+    if (st.err) return st.err;
+    launch_lightmap_cover(c->stream, lm, d_items, (uint32_t)items.size(), out.prim);
+    launch_lightmap_resolve(c->stream, lm, out.prim, out.uv2, out.position, out.normal, out.coverage);
+    HIPCHK(c, hipGetLastError());
+    return PT_OK;
+}
+
 // ---- adaptive sampling (PT_FLAG_ADAPTIVE)
 // everything that can be refused without touching the device
 int adaptive_check(pt_ctx* c, const pt_adaptive* a)
@@ -2716,6 +2796,139 @@ int pt_bake_probes(pt_ctx* c, uint32_t n_probes, const float* position, const pt
         HIPCHK(c, hipGetLastError());
     }
     return st.download(sh27, d_sh, (size_t)n_probes * 27 * 4);
+}
+
+// ---- lightmaps
+int pt_lightmap_ray(pt_ctx* c, uint32_t key, uint32_t sample, const float normal[3], float d[3])
+{
+    if (!c || !normal || !d) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    const f3 r = lightmap_ray(c->cfg.seed, c->cfg.n_sobol, key, sample, f3{normal[0], normal[1], normal[2]});
+    d[0] = r.x; d[1] = r.y; d[2] = r.z;
+    return PT_OK;
+}
+
+int pt_lightmap_texels(pt_ctx* c, int model, uint32_t instance, uint32_t w, uint32_t h, int on_device, uint32_t* prim, float* uv2, float* position,
+                       float* normal)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    int r;
+    if ((r = lightmap_check(c, model, instance, w, h))) return r;
+    const HostModel& m = c->scene.models[model];
+    const size_t px = (size_t)w * h;
+    if (!on_device)
+    {
+        std::vector<uint32_t> owner;
+        try { lightmap_owner_host(m, w, h, owner); }
+        catch (const std::exception& e) { return fail(c, PT_ERR_LIMIT, std::string("the texel table does not fit in host memory: ") + e.what()); }
+        for (size_t k = 0; k < px; ++k)
+        {
+            const uint32_t t = owner[k];
+            float u32 = 0.0f, v32 = 0.0f;
+            f3 P{0.0f, 0.0f, 0.0f}, n{0.0f, 0.0f, 0.0f};
+            if (t != MISS_ID)
+            {
+                double u = 0.0, v = 0.0;
+                (void)lm_contains(m.uvs.data() + 6u * (size_t)t, lm_centre((uint32_t)(k % w), w), lm_centre((uint32_t)(k / w), h), &u, &v);
+                u32 = (float)u; v32 = (float)v;
+                lm_surface(m.positions.data() + 9u * (size_t)t, m.normals.data() + 9u * (size_t)t, m.matrices[instance], u32, v32, &P, &n);
+            }
+            if (prim) prim[k] = t;
+            if (uv2) { uv2[2 * k] = u32; uv2[2 * k + 1] = v32; }
+            if (position) { position[3 * k] = P.x; position[3 * k + 1] = P.y; position[3 * k + 2] = P.z; }
+            if (normal) { normal[3 * k] = n.x; normal[3 * k + 1] = n.y; normal[3 * k + 2] = n.z; }
+        }
+        return PT_OK;
+    }
+    if ((r = ensure_device(c))) return r;
+    Staging st(c);
+    LightmapDev t{};
+    if ((r = lightmap_texels_device(c, st, m, instance, w, h, t))) return r;
+    if (prim && (r = st.download(prim, t.prim, px * 4))) return r;
+    if (uv2 && (r = st.download(uv2, t.uv2, px * 8))) return r;
+    if (position && (r = st.download(position, t.position, px * 12))) return r;
+    if (normal && (r = st.download(normal, t.normal, px * 12))) return r;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PT_OK;
+}
+
+int pt_bake_lightmap(pt_ctx* c, const pt_lightmap_params* p, float* rgb_sum, uint8_t* coverage)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    int r;
+    if ((r = rays_precheck(c))) return r;
+    if (!p || !rgb_sum) return fail(c, PT_ERR_ARG, "pt_bake_lightmap: p and rgb_sum must not be NULL");
+    if (p->reserved[0] || p->reserved[1] || p->reserved[2] || p->reserved[3]) return fail(c, PT_ERR_ARG, "pt_lightmap_params.reserved must be 0");
+    if ((r = lightmap_check(c, p->model, p->instance, p->w, p->h))) return r;
+    if (p->n_samples == 0) return fail(c, PT_ERR_ARG, "pt_lightmap_params.n_samples must be non-zero");
+    if (!std::isfinite(p->bias)) return fail(c, PT_ERR_ARG, "pt_lightmap_params.bias must be finite");
+    const size_t px = (size_t)p->w * p->h;
+    if ((uint64_t)p->key_base + px > 0x100000000ull) return fail(c, PT_ERR_ARG, "pt_lightmap_params.key_base + w * h wraps 32 bits");
+    if ((uint64_t)p->first_sample + p->n_samples > 0x100000000ull) return fail(c, PT_ERR_ARG, "pt_lightmap_params.first_sample + n_samples wraps 32 bits");
+    if ((r = upload_scene(c))) return r;
+    const HostModel& m = c->scene.models[p->model];
+    Staging st(c);
+    LightmapDev t{};
+    if ((r = lightmap_texels_device(c, st, m, p->instance, p->w, p->h, t))) return r;
+    // the covered texels in ascending order, so that neighbouring texels share a wave: the coverage bytes come back and are scanned here
+    std::vector<uint8_t> cov(px);
+    if ((r = st.download(cov.data(), t.coverage, px))) return r;
+    std::vector<uint32_t> texels;
+    for (size_t k = 0; k < px; ++k)
+        if (cov[k]) texels.push_back((uint32_t)k);
+    const uint32_t n_cov = (uint32_t)texels.size();
+    if (n_cov > 0)
+    {
+        // The bake's rays, texel-major with a texel's samples consecutive, go through a ray table of at most `chunk` rays at a time, as
+        // pt_bake_probes' do: filled on the device, integrated (in wavefront batches of their own), folded in sample order.  pt_config.batch_spp
+        // cuts here as well: wavefront batches of batch_spp * covered rays, three per table, so that a texel's samples straddle both.
+        const uint64_t total = (uint64_t)n_cov * p->n_samples;
+        const uint64_t cut = (uint64_t)c->cfg.batch_spp * n_cov;
+        const uint32_t batch_rays = (uint32_t)std::min<uint64_t>(cut, (1ull << 29) - 1);
+        const uint32_t chunk = (uint32_t)std::min<uint64_t>(total, batch_rays ? std::min<uint64_t>(3ull * batch_rays, 1ull << 26) : (1ull << 26));
+        const uint32_t* d_texels = (const uint32_t*)st.in(texels.data(), (size_t)n_cov * 4);
+        float* d_sum = (float*)st.in(rgb_sum, px * 12);
+        float* d_o = (float*)st.out((size_t)chunk * 12);
+        float* d_d = (float*)st.out((size_t)chunk * 12);
+        uint2* d_key = (uint2*)st.out((size_t)chunk * 8);
+        f4* d_rad = (f4*)st.out((size_t)chunk * 16);
+        if (st.err) return st.err;
+        const LightmapBake lb{d_texels, t.position, t.normal, n_cov, p->first_sample, p->n_samples, p->key_base, c->cfg.n_sobol, p->bias, c->cfg.seed};
+        for (uint64_t first = 0; first < total; first += chunk)
+        {
+            const uint32_t cnt = (uint32_t)std::min<uint64_t>(chunk, total - first);
+            launch_lightmap_rays(c->stream, lb, first, cnt, d_o, d_d, d_key);
+            if ((r = integrate_rays_device(c, cnt, d_o, d_d, d_key, 1u, batch_rays, d_rad, nullptr, nullptr))) return r;
+            launch_lightmap_fold(c->stream, lb, first, cnt, d_rad, d_sum);
+            HIPCHK(c, hipGetLastError());
+        }
+        if ((r = st.download(rgb_sum, d_sum, px * 12))) return r;
+    }
+    if (coverage) std::memcpy(coverage, cov.data(), px);
+    return PT_OK;
+}
+
+int pt_lightmap_dilate(pt_ctx* c, uint32_t w, uint32_t h, uint32_t passes, float* rgb, uint8_t* coverage)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!rgb || !coverage) return fail(c, PT_ERR_ARG, "pt_lightmap_dilate: rgb and coverage must not be NULL");
+    if (w == 0 || h == 0) return fail(c, PT_ERR_ARG, "lightmap: w and h must be non-zero");
+    if (w > 16384u || h > 16384u || (uint64_t)w * h > (1ull << 26)) return fail(c, PT_ERR_LIMIT, "lightmap: a side is at most 16384 texels and a map holds at most 2^26");
+    if (passes == 0) return PT_OK;
+    int r;
+    if ((r = ensure_device(c))) return r;
+    const size_t px = (size_t)w * h;
+    Staging st(c);
+    float* d_rgb[2] = {(float*)st.in(rgb, px * 12), (float*)st.out(px * 12)};
+    uint8_t* d_cov[2] = {(uint8_t*)st.in(coverage, px), (uint8_t*)st.out(px)};
+    if (st.err) return st.err;
+    for (uint32_t i = 0; i < passes; ++i) launch_lightmap_dilate(c->stream, w, h, d_rgb[i & 1u], d_cov[i & 1u], d_rgb[(i + 1u) & 1u], d_cov[(i + 1u) & 1u]);
+    HIPCHK(c, hipGetLastError());
+    if ((r = st.download(rgb, d_rgb[passes & 1u], px * 12))) return r;
+    return st.download(coverage, d_cov[passes & 1u], px);
 }
 
 // ---- unit hooks

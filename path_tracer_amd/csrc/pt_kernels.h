@@ -91,6 +91,41 @@ struct ProbeBake
 void launch_probe_rays(hipStream_t s, const ProbeBake& pb, uint64_t first, uint32_t count, float* o, float* d, uint2* key);
 void launch_probe_project(hipStream_t s, const ProbeBake& pb, uint64_t first, uint32_t count, const float* d, const f4* radiance, float* sh27);
 
+// lightmaps (pt_bake_lightmap; the definition is include/pt_api.h's and pt_lightmap.h's; the kernels are pt_lightmap.hip's).  One placement of one
+// model, uploaded per call: its load-order UVs (6 floats per triangle), positions and normals (9 each) and the instance's forward matrix.
+struct LightmapView
+{
+    const float* uv;
+    const float* positions;
+    const float* normals;
+    uint32_t n_tris, w, h;
+    xf34 m;
+};
+// a coverage work item {triangle, first} walks texels [first, first + kLightmapSlice) of the triangle's texel rectangle (lm_box), so a triangle
+// with a huge rectangle is many items
+constexpr uint32_t kLightmapSlice = 2048u;
+// owner[k] <- the lowest triangle index whose UVs contain the centre of texel k, MISS_ID where none does (w * h words)
+void launch_lightmap_cover(hipStream_t s, const LightmapView& lm, const uint2* items, uint32_t n_items, uint32_t* owner);
+// per texel: (u, v) of its owner, the surface point and the normal (3 floats each), the coverage byte (1 / 0); an uncovered texel gets zeros
+void launch_lightmap_resolve(hipStream_t s, const LightmapView& lm, const uint32_t* owner, float* uv2, float* position, float* normal, uint8_t* coverage);
+// Ray r of a bake is sample first_sample + r % n_samples of covered texel texels[r / n_samples] (texel indices, ascending); position and normal
+// are launch_lightmap_resolve's, sum the map's w * h * 3 sums.  launch_lightmap_rays fills rays [first, first + count) of the bake into a ray
+// table at indices [0, count); launch_lightmap_fold adds the radiance of those rays (the same window, as integrated) to sum in sample order, one
+// thread per (covered texel, channel)
+struct LightmapBake
+{
+    const uint32_t* texels;
+    const float* position;
+    const float* normal;
+    uint32_t n_covered, first_sample, n_samples, key_base, n_sobol;
+    float bias;
+    uint64_t seed;
+};
+void launch_lightmap_rays(hipStream_t s, const LightmapBake& lb, uint64_t first, uint32_t count, float* o, float* d, uint2* key);
+void launch_lightmap_fold(hipStream_t s, const LightmapBake& lb, uint64_t first, uint32_t count, const f4* radiance, float* sum);
+// one dilation pass (lm_dilate) of a w x h map from (rgb, cov) to (rgb_out, cov_out)
+void launch_lightmap_dilate(hipStream_t s, uint32_t w, uint32_t h, const float* rgb, const uint8_t* cov, float* rgb_out, uint8_t* cov_out);
+
 // list: an adaptive list (launch_adaptive_select's {local pixel, n_p} entries, rp.act_pixels of them) whose pixels the batch's paths belong
 // to instead of the active rectangle's (pt_render_adaptive), or null
 // opt.lens: with a radius above 0 (lens_set) the launchers that take one run the thin-lens variants of their kernels (pt_set_lens); the pinhole

@@ -1,0 +1,103 @@
+// Lightmap texels: which triangle of a model's UV layout covers a texel centre, the surface point and normal there under one instance
+// matrix, the cosine-distributed sample directions over it and one dilation step.  One definition for the gfx950 kernels (pt_lightmap.hip)
+// and for the host evaluations (pt_lightmap_texels with on_device = 0, pt_lightmap_ray).  include/pt_api.h, pt_bake_lightmap, states it
+// operation for operation; every operation is rounded once, in this order (the library is built without contraction).
+#pragma once
+#include "pt_types.h"
+
+namespace pt {
+
+// E(p, q, r) of the coverage rule: twice the signed area of (p, q, r), binary64
+PT_HD double lm_edge(double ps, double pt_, double qs, double qt, double rs, double rt) { return (qs - ps) * (rt - pt_) - (qt - pt_) * (rs - ps); }
+
+// centre of texel column i of a map w wide (rows alike)
+PT_HD double lm_centre(uint32_t i, uint32_t w) { return ((double)i + 0.5) / (double)w; }
+
+// does the UV triangle uv (a.s a.t b.s b.t c.s c.t) contain p?  u, v: its barycentrics of p (valid when A != 0)
+PT_HD bool lm_contains(const float uv[6], double ps, double pt_, double* u, double* v)
+{
+    const double as = (double)uv[0], at = (double)uv[1], bs = (double)uv[2], bt = (double)uv[3], cs = (double)uv[4], ct = (double)uv[5];
+    const double A = lm_edge(as, at, bs, bt, cs, ct);
+    if (A == 0.0) return false;
+    *u = lm_edge(as, at, ps, pt_, cs, ct) / A;
+    *v = lm_edge(as, at, bs, bt, ps, pt_) / A;
+    return *u >= 0.0 && *v >= 0.0 && *u + *v <= 1.0;
+}
+
+// The texel rectangle a triangle's centres are looked for in: columns floor(min s * w) - 1 .. floor(max s * w) + 1 and the rows alike, clamped
+// to the map; false when it is empty.  floor(x * w) is the column x lies in, so the rectangle holds every centre of the UV bounding box and a
+// ring of one texel around it.
+struct LmBox { uint32_t i0, j0, bw, bh; };
+PT_HD bool lm_span(double lo, double hi, uint32_t n, uint32_t* first, uint32_t* count)
+{
+    double a = __builtin_floor(lo * (double)n) - 1.0, b = __builtin_floor(hi * (double)n) + 1.0;
+    if (!(b >= 0.0) || !(a <= (double)(n - 1u))) return false;
+    if (a < 0.0) a = 0.0;
+    if (b > (double)(n - 1u)) b = (double)(n - 1u);
+    *first = (uint32_t)a;
+    *count = (uint32_t)b - (uint32_t)a + 1u;
+    return true;
+}
+PT_HD bool lm_box(const float uv[6], uint32_t w, uint32_t h, LmBox* box)
+{
+    const double s0 = (double)min_sse(min_sse(uv[0], uv[2]), uv[4]), s1 = (double)max_sse(max_sse(uv[0], uv[2]), uv[4]);
+    const double t0 = (double)min_sse(min_sse(uv[1], uv[3]), uv[5]), t1 = (double)max_sse(max_sse(uv[1], uv[3]), uv[5]);
+    return lm_span(s0, s1, w, &box->i0, &box->bw) && lm_span(t0, t1, h, &box->j0, &box->bh);
+}
+
+// surface point and normal of barycentrics (u, v) on the triangle with load-order positions p9 and normals n9 (a b c, xyz each), under
+// the instance's forward matrix m
+PT_HD void lm_surface(const float p9[9], const float n9[9], const xf34& m, float u, float v, f3* P, f3* n)
+{
+    const f3 pa{p9[0], p9[1], p9[2]}, pb{p9[3], p9[4], p9[5]}, pc{p9[6], p9[7], p9[8]};
+    const f3 na{n9[0], n9[1], n9[2]}, nb{n9[3], n9[4], n9[5]}, nc{n9[6], n9[7], n9[8]};
+    const f3 p_obj = (pa + u * (pb - pa)) + v * (pc - pa);
+    const float wgt = 1.0f - u - v;
+    const f3 n_obj = unit3((na * wgt + nb * u) + nc * v);
+    *P = xf_point(m, p_obj);
+    *n = xf_vector(m, n_obj);
+}
+
+// origin of a texel's rays
+PT_HD f3 lm_origin(f3 P, f3 n, float bias) { return P + bias * n; }
+
+// direction of sample `sample` of the texel whose stream is pixel `key`, over the normal n: cosine_vector's arithmetic on the Sobol point seeded
+// by the stream's draw 0 (as a camera ray's jitter, main.rs:193-194).  ONE draw of the stream is consumed.
+PT_HD f3 lightmap_ray(uint64_t seed, uint32_t n_sobol, uint32_t key, uint32_t sample, f3 n)
+{
+    Stream rng{stream_key(seed, key, sample), 0u};
+    const uint32_t seed0 = rng.u32();
+    float u1, u2;
+    ss_sobol(n_sobol, sample, seed0, &u1, &u2);
+    const float r = sqrtf(u1);
+    const float z = sqrtf(1.0f - r * r);
+    const float phi = 6.2831855f * u2;
+    float sn, cs;
+    sincos_det(phi, &sn, &cs);
+    return mul(onb_from_normal(n), f3{cs * r, sn * r, z});
+}
+
+// One dilation step of texel (i, j): false when the texel keeps its value (it is covered, or none of its eight neighbours is); otherwise the
+// mean of the neighbours with a non-zero coverage byte, added dy = -1..1 outer, dx = -1..1 inner
+PT_HD bool lm_dilate(const float* rgb, const uint8_t* cov, uint32_t w, uint32_t h, uint32_t i, uint32_t j, float out[3])
+{
+    if (cov[(size_t)j * w + i]) return false;
+    float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
+    uint32_t count = 0;
+    for (int dy = -1; dy <= 1; ++dy)
+        for (int dx = -1; dx <= 1; ++dx)
+        {
+            const int64_t x = (int64_t)i + dx, y = (int64_t)j + dy;
+            if ((dx == 0 && dy == 0) || x < 0 || y < 0 || x >= (int64_t)w || y >= (int64_t)h) continue;
+            const size_t q = (size_t)y * w + (size_t)x;
+            if (!cov[q]) continue;
+            s0 = s0 + rgb[3 * q]; s1 = s1 + rgb[3 * q + 1]; s2 = s2 + rgb[3 * q + 2];
+            ++count;
+        }
+    if (!count) return false;
+    const float n = (float)count;
+    out[0] = s0 / n; out[1] = s1 / n; out[2] = s2 / n;
+    return true;
+}
+
+} // namespace pt

@@ -1,0 +1,163 @@
+// Lightmap baking (pt_bake_lightmap, pt_lightmap_texels, pt_lightmap_dilate) as gfx950 kernels; no reference counterpart.  The arithmetic is
+// pt_lightmap.h's, shared with the host evaluations; include/pt_api.h states it.
+//
+//   k_lm_cover     a workgroup per (triangle, slice of its texel rectangle): the coverage predicate, atomicMin of the triangle index
+//   k_lm_resolve   a thread per texel: (u, v) of the owner, surface point and normal under the instance matrix, coverage byte
+//   k_lm_rays      a thread per ray: origin P + bias * n, a cosine-distributed direction over n, the stream key
+//   k_lm_fold      a thread per (covered texel, channel): the window's radiance added to the texel's sum in sample order
+//   k_lm_dilate    a thread per texel: one dilation pass from one buffer pair to the other
+#include <hip/hip_runtime.h>
+
+#include "pt_kernels.h"
+#include "pt_lightmap.h"
+
+namespace pt {
+namespace {
+
+__global__ void __launch_bounds__(256) k_lm_fill(const uint32_t n, const uint32_t value, uint32_t* __restrict__ out)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = value;
+}
+
+// Work item {triangle, first}: texels [first, first + kLightmapSlice) of the triangle's rectangle, row-major inside it.  Whatever order the
+// items run in, the lowest triangle index that contains a centre ends up as its owner.
+__global__ void __launch_bounds__(256) k_lm_cover(const LightmapView lm, const uint2* __restrict__ items, uint32_t* __restrict__ owner)
+{
+    const uint2 item = items[blockIdx.x];
+    const uint32_t tri = item.x;
+    if (tri >= lm.n_tris) return;
+    const float* puv = lm.uv + 6u * (size_t)tri;
+    const float uv[6] = {puv[0], puv[1], puv[2], puv[3], puv[4], puv[5]};
+    LmBox box;
+    if (!lm_box(uv, lm.w, lm.h, &box)) return;
+    const uint32_t n = box.bw * box.bh; // at most w * h <= 2^26
+    const uint32_t end = item.y + kLightmapSlice < n ? item.y + kLightmapSlice : n;
+    for (uint32_t t = item.y + threadIdx.x; t < end; t += blockDim.x)
+    {
+        const uint32_t dj = t / box.bw, i = box.i0 + (t - dj * box.bw), j = box.j0 + dj;
+        double u, v;
+        if (lm_contains(uv, lm_centre(i, lm.w), lm_centre(j, lm.h), &u, &v)) atomicMin(owner + ((size_t)j * lm.w + i), tri);
+    }
+}
+
+__global__ void __launch_bounds__(256) k_lm_resolve(const LightmapView lm, const uint32_t* __restrict__ owner, float* __restrict__ uv2,
+                                                     float* __restrict__ position, float* __restrict__ normal, uint8_t* __restrict__ coverage)
+{
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= lm.w * lm.h) return;
+    const uint32_t tri = owner[k];
+    float u32 = 0.0f, v32 = 0.0f;
+    f3 P{0.0f, 0.0f, 0.0f}, n{0.0f, 0.0f, 0.0f};
+    if (tri < lm.n_tris)
+    {
+        const float* puv = lm.uv + 6u * (size_t)tri;
+        const float uv[6] = {puv[0], puv[1], puv[2], puv[3], puv[4], puv[5]};
+        const uint32_t j = k / lm.w, i = k - j * lm.w;
+        double u = 0.0, v = 0.0;
+        (void)lm_contains(uv, lm_centre(i, lm.w), lm_centre(j, lm.h), &u, &v);
+        u32 = (float)u; v32 = (float)v;
+        float p9[9], n9[9];
+        for (int q = 0; q < 9; ++q) { p9[q] = lm.positions[9u * (size_t)tri + q]; n9[q] = lm.normals[9u * (size_t)tri + q]; }
+        lm_surface(p9, n9, lm.m, u32, v32, &P, &n);
+    }
+    uv2[2u * (size_t)k] = u32; uv2[2u * (size_t)k + 1u] = v32;
+    float* pp = position + 3u * (size_t)k;
+    float* pn = normal + 3u * (size_t)k;
+    pp[0] = P.x; pp[1] = P.y; pp[2] = P.z;
+    pn[0] = n.x; pn[1] = n.y; pn[2] = n.z;
+    coverage[k] = tri < lm.n_tris ? (uint8_t)1u : (uint8_t)0u;
+}
+
+// rays [first, first + count) of a bake into entries [0, count) of a ray table: sample first_sample + r % n_samples of covered texel r / n_samples
+__global__ void __launch_bounds__(256) k_lm_rays(const LightmapBake lb, const uint64_t first, const uint32_t count, float* __restrict__ o,
+                                                  float* __restrict__ d, uint2* __restrict__ key)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    const uint64_t r = first + i;
+    const uint32_t rank = (uint32_t)(r / lb.n_samples), s = lb.first_sample + (uint32_t)(r - (uint64_t)rank * lb.n_samples);
+    const uint32_t k = lb.texels[rank];
+    const float* pp = lb.position + 3u * (size_t)k;
+    const float* pn = lb.normal + 3u * (size_t)k;
+    const f3 n{pn[0], pn[1], pn[2]};
+    const f3 org = lm_origin(f3{pp[0], pp[1], pp[2]}, n, lb.bias);
+    const f3 dir = lightmap_ray(lb.seed, lb.n_sobol, lb.key_base + k, s, n);
+    float* po = o + 3u * (size_t)i;
+    float* pd = d + 3u * (size_t)i;
+    po[0] = org.x; po[1] = org.y; po[2] = org.z;
+    pd[0] = dir.x; pd[1] = dir.y; pd[2] = dir.z;
+    key[i] = make_uint2(lb.key_base + k, s);
+}
+
+// sum[texel][c] += L[c] over the window's rays of that texel, in sample order: one thread per (covered texel, channel), a serial fold by
+// definition (float addition does not associate) and no atomics.  The adds form one dependent chain; the loads do not depend on it, so eight
+// samples are fetched before their adds, and the next eight can be in flight while those adds run.
+__global__ void __launch_bounds__(256) k_lm_fold(const LightmapBake lb, const uint64_t first, const uint32_t count, const f4* __restrict__ radiance,
+                                                  float* __restrict__ sum)
+{
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t p0 = (uint32_t)(first / lb.n_samples), p1 = (uint32_t)((first + count - 1u) / lb.n_samples);
+    if (t / 3u > p1 - p0) return;
+    const uint32_t rank = p0 + t / 3u, c = t % 3u;
+    const uint64_t lo = (uint64_t)rank * lb.n_samples, hi = lo + lb.n_samples;
+    const uint32_t i0 = (uint32_t)((lo > first ? lo : first) - first), i1 = (uint32_t)((hi < first + count ? hi : first + count) - first);
+    float* dst = sum + 3u * (size_t)lb.texels[rank] + c;
+    const float* src = (const float*)radiance + c;
+    float acc = *dst;
+    uint32_t i = i0;
+    for (; i + 8u <= i1; i += 8u)
+    {
+        float l[8];
+#pragma unroll
+        for (uint32_t q = 0; q < 8u; ++q) l[q] = src[4u * (size_t)(i + q)];
+#pragma unroll
+        for (uint32_t q = 0; q < 8u; ++q) acc = acc + l[q];
+    }
+    for (; i < i1; ++i) acc = acc + src[4u * (size_t)i];
+    *dst = acc;
+}
+
+__global__ void __launch_bounds__(256) k_lm_dilate(const uint32_t w, const uint32_t h, const float* __restrict__ rgb, const uint8_t* __restrict__ cov,
+                                                    float* __restrict__ rgb_out, uint8_t* __restrict__ cov_out)
+{
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= w * h) return;
+    const uint32_t j = k / w, i = k - j * w;
+    float out[3];
+    const bool filled = lm_dilate(rgb, cov, w, h, i, j, out);
+    if (!filled) { out[0] = rgb[3u * (size_t)k]; out[1] = rgb[3u * (size_t)k + 1u]; out[2] = rgb[3u * (size_t)k + 2u]; }
+    rgb_out[3u * (size_t)k] = out[0]; rgb_out[3u * (size_t)k + 1u] = out[1]; rgb_out[3u * (size_t)k + 2u] = out[2];
+    cov_out[k] = filled ? (uint8_t)2u : cov[k];
+}
+
+inline dim3 blocks_for(uint64_t n) { return dim3((uint32_t)((n + 255u) / 256u)); }
+
+} // namespace
+
+void launch_lightmap_cover(hipStream_t s, const LightmapView& lm, const uint2* items, uint32_t n_items, uint32_t* owner)
+{
+    hipLaunchKernelGGL(k_lm_fill, blocks_for((uint64_t)lm.w * lm.h), dim3(256), 0, s, lm.w * lm.h, MISS_ID, owner);
+    if (n_items) hipLaunchKernelGGL(k_lm_cover, dim3(n_items), dim3(256), 0, s, lm, items, owner);
+}
+void launch_lightmap_resolve(hipStream_t s, const LightmapView& lm, const uint32_t* owner, float* uv2, float* position, float* normal, uint8_t* coverage)
+{
+    hipLaunchKernelGGL(k_lm_resolve, blocks_for((uint64_t)lm.w * lm.h), dim3(256), 0, s, lm, owner, uv2, position, normal, coverage);
+}
+void launch_lightmap_rays(hipStream_t s, const LightmapBake& lb, uint64_t first, uint32_t count, float* o, float* d, uint2* key)
+{
+    if (count == 0) return;
+    hipLaunchKernelGGL(k_lm_rays, blocks_for(count), dim3(256), 0, s, lb, first, count, o, d, key);
+}
+void launch_lightmap_fold(hipStream_t s, const LightmapBake& lb, uint64_t first, uint32_t count, const f4* radiance, float* sum)
+{
+    if (count == 0) return;
+    const uint64_t texels = (first + count - 1u) / lb.n_samples - first / lb.n_samples + 1u;
+    hipLaunchKernelGGL(k_lm_fold, blocks_for(texels * 3u), dim3(256), 0, s, lb, first, count, radiance, sum);
+}
+void launch_lightmap_dilate(hipStream_t s, uint32_t w, uint32_t h, const float* rgb, const uint8_t* cov, float* rgb_out, uint8_t* cov_out)
+{
+    hipLaunchKernelGGL(k_lm_dilate, blocks_for((uint64_t)w * h), dim3(256), 0, s, w, h, rgb, cov, rgb_out, cov_out);
+}
+
+} // namespace pt

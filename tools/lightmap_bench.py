@@ -1,0 +1,105 @@
+#!/usr/bin/env python3
+"""What a lightmap bake costs over the bare integrator (profiles/r15_lightmap.md): a SIZE x SIZE x SPP map of a Cornell box model under the
+tests' box atlas (no overlap), beside pt_integrate_rays_device given a ray table of the same shape rebuilt in torch from lightmap_texels -
+the same origins P + bias * n, stream keys and samples, texel-major with a texel's samples consecutive, and cosine-distributed directions over
+the same normals from torch's generator (the bake's own Sobol points have no device-side hook; the distribution and the order are the bake's).
+The difference is coverage, resolve, ray generation, fold and the map's copies; the texel table alone is timed too.
+
+    python tools/lightmap_bench.py [--size 1024] [--spp 64] [--reps 3] [--model cb_box_short] [--only bake|rays] [--out report.json]
+
+--only bake with --reps 1 is the run to put under rocprofv3 --kernel-trace --stats for the per-kernel table (tools/kernel_times.py)."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+W, H, DEPTH, BIAS = 1920, 1080, 8, 0.25
+
+
+def torch_rays(torch, table, spp):
+    """the bake's ray table on the device: (o, d, key, sample), texel-major"""
+    prim, _, position, normal = table
+    dev = torch.device("cuda")
+    k = torch.from_numpy(np.flatnonzero(prim.reshape(-1) != 0xFFFFFFFF).astype(np.int64)).to(dev)
+    P = torch.from_numpy(position.reshape(-1, 3)).to(dev)[k]
+    n = torch.from_numpy(normal.reshape(-1, 3)).to(dev)[k]
+    o = (P + BIAS * n).repeat_interleave(spp, 0).contiguous()
+    n = n.repeat_interleave(spp, 0)
+    gen = torch.Generator(device=dev).manual_seed(15)
+    u = torch.rand((n.shape[0], 2), generator=gen, device=dev)
+    r, phi = u[:, 0].sqrt(), 6.2831855 * u[:, 1]
+    local = torch.stack([phi.cos() * r, phi.sin() * r, (1 - r * r).clamp_min(0).sqrt()], 1)
+    # any orthonormal pair around n (material/onb.rs)
+    sign = torch.copysign(torch.ones_like(n[:, 2]), n[:, 2])
+    a = -1.0 / (sign + n[:, 2])
+    b = n[:, 0] * n[:, 1] * a
+    c0 = torch.stack([1.0 + sign * n[:, 0] * n[:, 0] * a, sign * b, -sign * n[:, 0]], 1)
+    c1 = torch.stack([b, sign + n[:, 1] * n[:, 1] * a, -n[:, 1]], 1)
+    d = (c0 * local[:, 0:1] + c1 * local[:, 1:2] + n * local[:, 2:3]).contiguous()
+    key = k.to(torch.int32).repeat_interleave(spp).contiguous()
+    sample = torch.arange(spp, dtype=torch.int32, device=dev).repeat(k.shape[0]).contiguous()
+    return o, d, key, sample
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--size", type=int, default=1024)
+    ap.add_argument("--spp", type=int, default=64)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--model", default="cb_box_short")
+    ap.add_argument("--only", choices=["bake", "rays"], default=None)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("lightmap_bench needs the GPU: there is nothing to time without one")
+    import lightmap_common as LC
+    from path_tracer_amd import api
+    sc, model = LC.cornell_atlas_scene(args.model, W, H)
+    r = api.Renderer(sc, W, H, max_bounces=DEPTH)
+    size, spp = args.size, args.spp
+    # warm-up: scene upload, code objects, the wavefront pool at the size the timed calls use
+    r.bake_lightmap(model, 0, size, size, 1, bias=BIAS)
+    table = r.lightmap_texels(model, 0, size, size, on_device=True)
+    covered = int((table[0] != 0xFFFFFFFF).sum())
+    report = {"size": size, "spp": spp, "model": args.model, "covered": covered, "rays": covered * spp, "bake_ms": [], "rays_ms": [], "texels_ms": []}
+    rays = None
+    if args.only != "bake":
+        rays = torch_rays(torch, table, spp)
+        r.integrate_rays(rays[0][:covered], rays[1][:covered], rays[2][:covered], rays[3][:covered])
+    for _ in range(args.reps):          # the two routes alternate, so that a drift of the shared machine touches both
+        if args.only != "rays":
+            t0 = time.perf_counter()
+            r.lightmap_texels(model, 0, size, size, on_device=True)
+            report["texels_ms"].append(1e3 * (time.perf_counter() - t0))
+            t0 = time.perf_counter()
+            sums, _ = r.bake_lightmap(model, 0, size, size, spp, bias=BIAS)      # blocking
+            report["bake_ms"].append(1e3 * (time.perf_counter() - t0))
+        if args.only != "bake":
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = r.integrate_rays(*rays)                                        # blocking: the results are complete when it returns
+            torch.cuda.synchronize()
+            report["rays_ms"].append(1e3 * (time.perf_counter() - t0))
+            del out
+    if report["bake_ms"]:
+        report["mean_irradiance"] = float(np.pi * sums[table[0] != 0xFFFFFFFF].mean() / spp)
+    if report["bake_ms"] and report["rays_ms"]:
+        report["over_the_integrator_ms"] = min(report["bake_ms"]) - min(report["rays_ms"])
+    line = json.dumps(report)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
