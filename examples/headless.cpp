@@ -16,6 +16,9 @@
 //   examples/headless ... --denoise-albedo den.png   the same through the demodulated filter (pt_denoise_albedo): the mean albedo of every pixel
 //                                        is accumulated over the samples that were rendered, the frame divided by it, filtered and multiplied back,
 //                                        so textures (--checker) stay sharp; also with --render
+//   examples/headless ... --follow K   --denoise and --denoise-albedo take their guides (and the mean albedo) through mirrors and glass, up to K
+//                                        of them per pixel, to the first rough surface (pt_render_guides_followed); K = 0..8, default 0
+//   examples/headless ... --mirror-glass   the tall box is a mirror (main.rs:90) and the short box glass (main.rs:89): what --follow is for
 //   examples/headless ... --bake-probes NX NY NZ SPP probes.txt   after the usual render, bakes SPP samples into an NX x NY x NZ grid of
 //       irradiance probes spanning the scene's bounds shrunk by 5 % per side (x fastest, then y, then z; stream keys 0, 1, ...) and
 //       writes one line per probe: its 27 raw spherical-harmonics sums [k][c] as hexadecimal floats (%a)
@@ -40,7 +43,7 @@ using namespace ptmi;
 int main(int argc, char** argv)
 {
     uint32_t width = 1920, height = 1080, frames = 64, bounces = 8; // IMAGE_WIDTH/HEIGHT main.rs:44-45; the reference's MAX_BOUNCES is 1024
-    bool move = false, slide = false;
+    bool move = false, slide = false, mirror_glass = false;
     float slide_dx = 0.0f, slide_dz = 0.0f;
     uint32_t gpus = 0, spp = 64;
     std::vector<int32_t> devices;
@@ -48,7 +51,7 @@ int main(int argc, char** argv)
     bool render_mode = false;
     uint32_t render_first = 0, render_count = 0;
     float aperture = 0.0f, focus = 950.0f; // main.rs:127's values: a pinhole
-    uint32_t probes[3] = {0, 0, 0}, probe_spp = 0, checker = 0;
+    uint32_t probes[3] = {0, 0, 0}, probe_spp = 0, checker = 0, follow = 0;
     std::string probes_out = "";
     uint32_t lightmap[4] = {0, 0, 0, 0}; // W H SPP PASSES
     std::string lightmap_out = "";
@@ -68,6 +71,8 @@ int main(int argc, char** argv)
         else if (a == "--out") out = next("--out");
         else if (a == "--denoise") denoise_out = next("--denoise");
         else if (a == "--denoise-albedo") denoise_albedo_out = next("--denoise-albedo");
+        else if (a == "--follow") follow = (uint32_t)std::atoi(next("--follow"));
+        else if (a == "--mirror-glass") mirror_glass = true;
         else if (a == "--move") move = true;
         else if (a == "--slide") { slide = true; slide_dx = (float)std::atof(next("--slide")); slide_dz = (float)std::atof(next("--slide")); }
         else if (a == "--aperture") aperture = (float)std::atof(next("--aperture"));
@@ -106,7 +111,7 @@ int main(int argc, char** argv)
         }
         else if (a == "--help" || a == "-h")
         {
-            std::printf("usage: %s [--width W] [--height H] [--frames N] [--bounces B] [--move] [--slide DX DZ] [--models DIR] [--out file.png] [--denoise file.png] [--denoise-albedo file.png] [--aperture A --focus F] [--projection panorama[:SX:SY]|ortho:HEIGHT] [--bake-probes NX NY NZ SPP file.txt] [--bake-lightmap W H SPP PASSES file.txt] [--checker N]\n", argv[0]);
+            std::printf("usage: %s [--width W] [--height H] [--frames N] [--bounces B] [--move] [--slide DX DZ] [--models DIR] [--out file.png] [--denoise file.png] [--denoise-albedo file.png] [--follow K] [--mirror-glass] [--aperture A --focus F] [--projection panorama[:SX:SY]|ortho:HEIGHT] [--bake-probes NX NY NZ SPP file.txt] [--bake-lightmap W H SPP PASSES file.txt] [--checker N]\n", argv[0]);
             return 0;
         }
         else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
@@ -134,8 +139,8 @@ int main(int argc, char** argv)
             Model::New(models_dir + "/cb_main.obj", main_gray, one),
             Model::New(models_dir + "/cb_right.obj", diffuse_red, one),
             Model::New(models_dir + "/cb_left.obj", diffuse_green, one),
-            Model::New(models_dir + "/cb_box_tall.obj", diffuse_gray, one),
-            Model::New(models_dir + "/cb_box_short.obj", diffuse_gray, one),
+            Model::New(models_dir + "/cb_box_tall.obj", mirror_glass ? Specular::New(Vec3A::splat(1.0f)) : diffuse_gray, one),
+            Model::New(models_dir + "/cb_box_short.obj", mirror_glass ? Dielectric::New(Vec3A::splat(0.95f), 1.5f, std::nullopt) : diffuse_gray, one),
         });
 
         // Camera  main.rs:119-128
@@ -215,8 +220,8 @@ int main(int argc, char** argv)
         };
         // the demodulated denoiser on samples [first, first + count) of the frame: guides of the last sample, the mean albedo of all of them
         auto denoise_albedo = [&](uint32_t first, uint32_t count) {
-            renderer.render_guides(first + count - 1);
-            renderer.accumulate_albedo(first, count);
+            renderer.render_guides_followed(first + count - 1, follow);
+            renderer.accumulate_albedo_followed(first, count, follow);
             renderer.denoise_albedo(PT_ALBEDO_MEAN);
             renderer.write_denoised_image(denoise_albedo_out);
         };
@@ -284,7 +289,7 @@ int main(int argc, char** argv)
         if (!denoise_out.empty() && frames)
         {
             // the interactive recipe: guides of the last frame's sample, then the filter (pt_api.h)
-            renderer.render_guides(frames - 1);
+            renderer.render_guides_followed(frames - 1, follow);
             renderer.denoise();
             renderer.write_denoised_image(denoise_out);
         }

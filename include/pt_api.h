@@ -416,6 +416,56 @@ int pt_read_guide_instances(pt_ctx* ctx, uint32_t* instance);
 /* the fifth guide: ALBEDO, local_rows * width rgb f32 — the surface colour at the first hit (pt_add_texture), an emissive hit's emitted colour,
  * (0, 0, 0) for a miss.  pt_denoise does not use it; pt_denoise_albedo(PT_ALBEDO_GUIDE) divides its input by it.  PT_ERR_STATE without guides. */
 int pt_read_guide_albedo(pt_ctx* ctx, float* rgb);
+/* FOLLOWED GUIDES.  The first hit of a mirror or a pane of glass says nothing about what the pixel shows: every pixel of a flat mirror has
+ * the mirror's model, normal and plane, so the filter sees no edge in the reflection and smears it; glass adds an albedo guide that is its
+ * tint, not the colour behind it.  pt_render_guides_followed follows PT_SPECULAR and PT_DIELECTRIC hits, up to max_hops of them per pixel,
+ * and writes the guides of the surface the chain ends on into the same device buffers (pt_render_guides and all it writes are what they
+ * were, bit for bit; max_hops = 0 IS pt_render_guides).
+ *   The chain of a pixel, binary32, every operation rounded once, no contraction.  Ray 0 = the camera ray of (pixel, sample) exactly as
+ *   pt_render_guides queues it (pinhole, lens, panorama, orthographic).  At hop h = 0, 1, ...: trace ray h = (o, d) against the world TLAS
+ *   with t_max = +inf (the walk of every other trace: t_min = PT_EPSILON inside the traversal, no origin offset).
+ *     miss                      : the chain ends as a miss.
+ *     hit at t                  : p = fma(d, t, o) per component; n, front = the face-forwarded shading normal as in the normal guide; m = the
+ *                                 instance's material.
+ *     m.kind not PT_SPECULAR / PT_DIELECTRIC (PT_GGX_* included, whatever the roughness), or h == max_hops: the chain ends on this surface.
+ *     otherwise ray h + 1 = (p, wo), wo used as returned (not renormalised):
+ *       PT_SPECULAR   : wo = reflect(d, n) = d - 2 * dot(n, d) * n                                                   utility.rs:21
+ *       PT_DIELECTRIC : eta = front ? 1 / ior : ior; wo = refract(d, n, eta) (utility.rs:23-36), or reflect(d, n) where that has a NaN
+ *                       component (total internal reflection).  The Fresnel coin is NOT tossed and no stream draw is consumed: a glass
+ *                       pixel always shows what lies behind the glass, so that neighbouring pixels get coherent guides.
+ *     Media are ignored (no volume stack, no scattering).
+ *   Guides of a pixel whose chain took H hops (H = 0: the first hit was not followed), c_i = the surface colour of hit i as pt_add_texture
+ *   defines it (an emissive hit: its emitted colour):
+ *     ended on a surface : position = the final p | ((t_0 + t_1) + ...) + t_H; normal = the final n; instance = the final hit's world-TLAS
+ *                          leaf; model = the final hit's model index | H << 28 (a reflection and the surface seen directly beside it are
+ *                          different "models" to the filter, which only compares the word for equality and against 0xffffffff; a scene of
+ *                          2^28 or more models is PT_ERR_LIMIT); albedo = ((c_0 * c_1) * ...) * c_H per component; hops = H.
+ *     ended as a miss    : model = instance = 0xffffffff, normal = 0, position = the last ray's r.at(1e5) | 1e5, albedo = (0, 0, 0), hops = H.
+ * The followed guides go stale on the events that make first-hit guides stale, and pt_denoise, pt_denoise_albedo(PT_ALBEDO_GUIDE),
+ * pt_read_guides, pt_read_guide_instances and pt_read_guide_albedo work on them unchanged.  pt_frame_moving keeps writing FIRST-HIT guides
+ * (its reprojection needs the first hit's instance): render the followed guides after it.  pt_read_guide_hops copies the hop guide,
+ * local_rows * width bytes; after a plain pt_render_guides (or pt_frame_moving) it is all zeros.
+ * pt_accumulate_albedo_followed is pt_accumulate_albedo with that albedo product per sample ((1, 1, 1) for a chain that ended as a miss),
+ * same order and continuation rules.  The sums remember their max_hops: accumulating with another starts from zero, like accumulating onto
+ * stale sums (pt_accumulate_albedo is max_hops = 0), and pt_denoise_albedo(PT_ALBEDO_MEAN) returns PT_ERR_STATE when the guides' max_hops
+ * and the sums' differ.
+ * Errors, before any device call and changing nothing: PT_ERR_ARG for params NULL, max_hops > 8 or a non-zero reserved word (the accumulate
+ * call: also what pt_accumulate_albedo refuses); PT_ERR_STATE as pt_render_guides.  A rank context works on its own rows.
+ * Out of scope: the Fresnel-reflected lobe of glass (or both lobes); low-roughness GGX; mirrored "virtual" positions and motion vectors for
+ * reflections in pt_frame_moving; pt_multi_* variants; a hop tag for chains that ended as a miss. */
+typedef struct pt_guide_params
+{
+    uint32_t max_hops;    /* 0..8: delta surfaces followed per pixel; 0 IS pt_render_guides */
+    uint32_t reserved[3]; /* must be 0 */
+} pt_guide_params;
+int pt_render_guides_followed(pt_ctx* ctx, uint32_t sample, const pt_guide_params* params);
+int pt_read_guide_hops(pt_ctx* ctx, uint8_t* hops);
+int pt_accumulate_albedo_followed(pt_ctx* ctx, uint32_t first_sample, uint32_t n_samples, const pt_guide_params* params);
+/* unit hook: the follow-on direction at n hits of material `material` (incoming direction, face-forwarded normal, front face);
+ * out4 = wo xyz | followed (1.0 / 0.0; a kind that ends the chain gives wo = 0).  on_device 0 evaluates on the host and touches no GPU;
+ * 1 runs a kernel over the same function */
+int pt_guide_follow_dir(pt_ctx* ctx, int on_device, int material, uint32_t n, const float* incoming_xyz, const float* normal_xyz,
+                        const uint8_t* front, float* out4);
 /* The filter, in f32 with every operation correctly rounded (no contraction) and in the order written.  exp is pt_math.h's exp_det.
  *   Pixel p is VALID when acc.w != 0; an invalid pixel is never a neighbour and its output is (0,0,0,0).  Every valid output is (c, 1).
  *   c_p = (acc.r / acc.w, acc.g / acc.w, acc.b / acc.w);  l(c) = (0.2126f * c.r + 0.7152f * c.g) + 0.0722f * c.b (of the current colour).

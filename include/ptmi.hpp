@@ -324,11 +324,28 @@ public:
     // denoising: first-hit guides of one sample, then the edge-aware a-trous filter of the accumulation (pt_denoise); the result stays on
     // the device for write_denoised_image
     void render_guides(uint32_t sample) { check(pt_render_guides(ctx_, sample)); }
+    // the same with mirrors and glass followed, up to max_hops of them per pixel, to the first rough surface (pt_render_guides_followed):
+    // the guides are that surface's, the model guide carries the hops in bits 31..28.  frame_moving writes first-hit guides: call this after it
+    void render_guides_followed(uint32_t sample, uint32_t max_hops)
+    {
+        pt_guide_params p{};
+        p.max_hops = max_hops;
+        check(pt_render_guides_followed(ctx_, sample, &p));
+    }
+    // the hop guide: how many mirror / glass surfaces every pixel's chain followed, W*H bytes (zeros after render_guides)
+    std::vector<uint8_t> read_guide_hops() const { std::vector<uint8_t> v((size_t)width_ * height_); check(pt_read_guide_hops(ctx_, v.data())); return v; }
     void denoise(const pt_denoise_params& p = pt_denoise_params{}) { check(pt_denoise(ctx_, &p, nullptr)); }
     void write_denoised_image(const std::string& path) const { check(pt_write_denoised_image(ctx_, path.c_str())); }
     // the demodulated filter (pt_denoise_albedo): the mean albedo of samples [first, first + n) of every pixel, then denoise() on the
     // accumulation divided by it (or by the albedo guide: PT_ALBEDO_GUIDE) and multiplied back; the result is written like denoise()'s
     void accumulate_albedo(uint32_t first_sample, uint32_t n_samples) { check(pt_accumulate_albedo(ctx_, first_sample, n_samples)); }
+    // ... of the followed chains' albedo products: what denoise_albedo(PT_ALBEDO_MEAN) wants beside render_guides_followed(.., max_hops)
+    void accumulate_albedo_followed(uint32_t first_sample, uint32_t n_samples, uint32_t max_hops)
+    {
+        pt_guide_params p{};
+        p.max_hops = max_hops;
+        check(pt_accumulate_albedo_followed(ctx_, first_sample, n_samples, &p));
+    }
     void reset_albedo() { check(pt_reset_albedo(ctx_)); }
     std::vector<float> read_albedo() const { std::vector<float> v((size_t)width_ * height_ * 4); check(pt_read_albedo(ctx_, v.data())); return v; }
     void denoise_albedo(uint32_t albedo_source = PT_ALBEDO_MEAN, const pt_denoise_params& p = pt_denoise_params{})

@@ -44,6 +44,7 @@ EXPORTS = [
     "pt_accumulate_albedo", "pt_reset_albedo", "pt_read_albedo", "pt_denoise_albedo", "pt_post_denoise_albedo",
     "pt_set_projection", "pt_get_projection",
     "pt_bake_lightmap", "pt_lightmap_texels", "pt_lightmap_ray", "pt_lightmap_dilate",
+    "pt_render_guides_followed", "pt_read_guide_hops", "pt_accumulate_albedo_followed", "pt_guide_follow_dir",
 ]
 
 
@@ -92,6 +93,11 @@ class Adaptive(C.Structure):
 class DenoiseParams(C.Structure):
     """pt_denoise_params: the a-trous filter's levels and edge-stopping widths (include/pt_api.h); 0 selects each default"""
     _fields_ = [("iterations", C.c_uint32), ("sigma_luminance", C.c_float), ("sigma_normal", C.c_uint32), ("sigma_plane", C.c_float)]
+
+
+class GuideParams(C.Structure):
+    """pt_guide_params: how many mirror / glass surfaces the guide chains follow per pixel (include/pt_api.h)"""
+    _fields_ = [("max_hops", C.c_uint32), ("reserved", C.c_uint32 * 3)]
 
 
 class RaysParams(C.Structure):
@@ -253,6 +259,10 @@ def lib():
         L.pt_lightmap_texels.argtypes = [vp, C.c_int, u32, u32, u32, C.c_int, vp, vp, vp, vp]
         L.pt_lightmap_ray.argtypes = [vp, u32, u32, vp, vp]
         L.pt_lightmap_dilate.argtypes = [vp, u32, u32, u32, vp, vp]
+        L.pt_render_guides_followed.argtypes = [vp, u32, C.POINTER(GuideParams)]
+        L.pt_read_guide_hops.argtypes = [vp, vp]
+        L.pt_accumulate_albedo_followed.argtypes = [vp, u32, u32, C.POINTER(GuideParams)]
+        L.pt_guide_follow_dir.argtypes = [vp, C.c_int, C.c_int, u32, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -671,9 +681,21 @@ class Renderer:
         return out
 
     # ---- denoising: first-hit guides + edge-aware a-trous filter
-    def render_guides(self, sample: int):
-        """trace the camera ray of `sample` of every local pixel: first-hit position, normal and model guides stay on the device"""
-        self._chk(self.L.pt_render_guides(self.ctx, sample))
+    def render_guides(self, sample: int, follow: int = 0):
+        """trace the camera ray of `sample` of every local pixel: first-hit position, normal and model guides stay on the device.
+        follow = K > 0 (pt_render_guides_followed): mirrors and glass are followed, up to K of them per pixel, and the guides are those
+        of the surface the chain ends on (the model guide carries the hops in bits 31..28); after frame_moving, render these after it"""
+        if follow:
+            prm = GuideParams(follow)
+            self._chk(self.L.pt_render_guides_followed(self.ctx, sample, C.byref(prm)))
+        else:
+            self._chk(self.L.pt_render_guides(self.ctx, sample))
+
+    def read_guide_hops(self):
+        """the hop guide of the last render_guides: how many mirror / glass surfaces every pixel's chain followed (zeros unless follow)"""
+        hops = np.zeros((len(self.local_rows()), self.cfg.width), np.uint8)
+        self._chk(self.L.pt_read_guide_hops(self.ctx, _p(hops)))
+        return hops
 
     def read_guides(self):
         """(position xyzt, normal xyz, model u32; MISS = 0xffffffff) of the last render_guides, local rows x width"""
@@ -720,10 +742,15 @@ class Renderer:
         return out
 
     # ---- mean albedo and the demodulated filter (pt_denoise_albedo)
-    def accumulate_albedo(self, first_sample: int, n_samples: int):
+    def accumulate_albedo(self, first_sample: int, n_samples: int, follow: int = 0):
         """add the albedo guide of samples [first_sample, first_sample + n_samples) of every local pixel to the mean-albedo sums, in sample
-        order; a miss adds (1, 1, 1).  Calls continue the sums until they go stale (whatever makes the guides stale) or reset_albedo"""
-        self._chk(self.L.pt_accumulate_albedo(self.ctx, first_sample, n_samples))
+        order; a miss adds (1, 1, 1).  Calls continue the sums until they go stale (whatever makes the guides stale) or reset_albedo.
+        follow = K > 0 (pt_accumulate_albedo_followed): the albedo product of render_guides(.., follow=K); sums made with another K restart"""
+        if follow:
+            prm = GuideParams(follow)
+            self._chk(self.L.pt_accumulate_albedo_followed(self.ctx, first_sample, n_samples, C.byref(prm)))
+        else:
+            self._chk(self.L.pt_accumulate_albedo(self.ctx, first_sample, n_samples))
 
     def reset_albedo(self):
         self._chk(self.L.pt_reset_albedo(self.ctx))
@@ -906,6 +933,14 @@ class Renderer:
         n = np.ascontiguousarray(normal, np.float32); f = np.ascontiguousarray(front, np.uint8)
         out = np.zeros((i.shape[0], 4), np.float32)
         self._chk(self.L.pt_bsdf_eval(self.ctx, material, i.shape[0], _p(i), _p(w), _p(n), _p(f), _p(out)))
+        return out
+
+    def guide_follow_dir(self, material, incoming, normal, front, on_device=False):
+        """[n, 4]: the direction the guide chain goes on in at hits of the material (xyz) and whether it is followed at all (1 / 0);
+        on the host (no GPU) unless on_device (pt_guide_follow_dir)"""
+        i = np.ascontiguousarray(incoming, np.float32); n = np.ascontiguousarray(normal, np.float32); f = np.ascontiguousarray(front, np.uint8)
+        out = np.zeros((i.shape[0], 4), np.float32)
+        self._chk(self.L.pt_guide_follow_dir(self.ctx, int(bool(on_device)), material, i.shape[0], _p(i), _p(n), _p(f), _p(out)))
         return out
 
     def model_vertices(self, model):

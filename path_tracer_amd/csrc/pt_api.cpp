@@ -183,6 +183,11 @@ struct pt_ctx
     DevBuf d_albedo_sum, d_dn_k;
     bool albedo_valid = false;
     uint64_t albedo_scene_version = 0, albedo_config_version = 0;
+    // followed guides (pt_render_guides_followed / pt_accumulate_albedo_followed): the second hook queue the chains alternate with, its
+    // head words, a chain's running albedo product | t sum per pixel and the hop guide; allocated by those two calls only.  The max_hops
+    // the guides and the sums were made with (0: first-hit).
+    DevBuf d_gray2_a, d_gray2_b, d_ghead2, d_gstate, d_ghops;
+    uint32_t guides_max_hops = 0, albedo_max_hops = 0;
 
     // pt_frame_moving: the forward instance matrices, per model, of the build in force when the previous call returned PT_OK (the snapshot)
     // and the build it was taken from (a call on that very build has nothing to compare); the motion table and x_prev on the device.
@@ -2458,8 +2463,66 @@ int render_guides_locked(pt_ctx* c, uint32_t sample)
     c->guides_scene_version = c->scene_version;
     c->guides_config_version = c->config_version;
     c->guides_sample = sample;
+    c->guides_max_hops = 0;
     return PT_OK;
 }
+
+// pt_guide_params as the two followed calls take it
+int follow_params(pt_ctx* c, const pt_guide_params* gp, const char* who)
+{
+    if (!gp) return fail(c, PT_ERR_ARG, std::string(who) + ": params must not be NULL");
+    if (gp->max_hops > 8u) return fail(c, PT_ERR_ARG, std::string(who) + ": max_hops is at most 8");
+    if (gp->reserved[0] || gp->reserved[1] || gp->reserved[2]) return fail(c, PT_ERR_ARG, std::string(who) + ": the reserved words must be 0");
+    return PT_OK;
+}
+// the second hook queue, its head words and the chains' per-pixel state
+int follow_scratch(pt_ctx* c)
+{
+    int r;
+    const size_t n = std::max<uint32_t>(c->local_pixels, 1);
+    for (DevBuf* b : {&c->d_gray2_a, &c->d_gray2_b, &c->d_gstate})
+        if ((r = dev_alloc(c, *b, n * 16))) return r;
+    return dev_alloc(c, c->d_ghead2, ((size_t)32 + kHeadWordsPerQueue) * 4);
+}
+// the chains of `sample` of every local pixel, hop by hop (enqueued, not waited for): trace the queue, then k_guide_follow, which ends
+// chains into the guides (sum null) or into the mean-albedo sums and queues the others' next rays into the other hook queue.  That
+// queue's count stays on the device, in the head word the next trace reads; a hop nobody reached is two empty launches.
+int follow_chains(pt_ctx* c, uint32_t sample, uint32_t max_hops, f4* sum)
+{
+    int r;
+    if ((r = guide_trace(c, sample))) return r; // hop 0: the camera rays, slot = local pixel
+    const RayQueue q[2] = {RayQueue{(f4*)c->d_gray_a.p, (f4*)c->d_gray_b.p}, RayQueue{(f4*)c->d_gray2_a.p, (f4*)c->d_gray2_b.p}};
+    uint32_t* const head[2] = {(uint32_t*)c->d_ghead.p, (uint32_t*)c->d_ghead2.p};
+    // (an empty world: every chain ends at hop 0 as a miss)
+    const uint32_t last = c->sv.world_root == MISS_ID ? 0u : max_hops;
+    for (uint32_t h = 0; h <= last; ++h)
+    {
+        const uint32_t cur = h & 1u, nxt = cur ^ 1u;
+        if (h) launch_trace_rays_closest(c->stream, trace_launch(c), c->sv.world_root, q[cur], c->local_pixels, head[cur], (f4*)c->d_ghits.p);
+        HIPCHK(c, hipMemsetAsync(head[nxt], 0, c->d_ghead.bytes, c->stream));
+        FollowArgs a{};
+        a.in = q[cur];
+        a.next = q[nxt];
+        a.hits = (const f4*)c->d_ghits.p;
+        a.n_in = head[cur];
+        a.n_next = head[nxt];
+        a.state = (f4*)c->d_gstate.p;
+        a.position = (f4*)c->d_gpos.p;
+        a.normal = (f4*)c->d_gnrm.p;
+        a.albedo = (f4*)c->d_galbedo.p;
+        a.model = (uint32_t*)c->d_gmodel.p;
+        a.instance = (uint32_t*)c->d_ginst.p;
+        a.hops = (uint8_t*)c->d_ghops.p;
+        a.sum = sum;
+        a.cap = c->local_pixels;
+        a.hop = h;
+        a.max_hops = max_hops;
+        launch_guide_follow(c->stream, c->sv, c->tex, a);
+    }
+    return PT_OK;
+}
+
+int accumulate_albedo_locked(pt_ctx* c, uint32_t first_sample, uint32_t n_samples, uint32_t max_hops, const char* who);
 } // namespace
 
 extern "C" {
@@ -2469,6 +2532,53 @@ int pt_render_guides(pt_ctx* c, uint32_t sample)
     if (!c) return PT_ERR_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
     return render_guides_locked(c, sample);
+}
+
+int pt_render_guides_followed(pt_ctx* c, uint32_t sample, const pt_guide_params* gp)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    int r;
+    if ((r = follow_params(c, gp, "pt_render_guides_followed"))) return r;
+    const uint32_t max_hops = gp->max_hops;
+    if (max_hops == 0u) return render_guides_locked(c, sample); // 0 IS pt_render_guides
+    if (!c->scene.built) return fail(c, PT_ERR_STATE, "pt_build has not been called");
+    if (!c->scene.camera.set) return fail(c, PT_ERR_STATE, "pt_set_camera has not been called");
+    if (c->scene.blas.size() >= ((size_t)1 << 28)) return fail(c, PT_ERR_LIMIT, "pt_render_guides_followed: the model guide keeps the hops in bits 31..28, so a scene has fewer than 2^28 models");
+    if ((r = upload_scene(c))) return r;
+    const uint32_t px = c->local_pixels;
+    const size_t n = std::max<uint32_t>(px, 1);
+    for (DevBuf* b : {&c->d_gpos, &c->d_gnrm, &c->d_galbedo})
+        if ((r = dev_alloc(c, *b, n * 16))) return r;
+    if ((r = dev_alloc(c, c->d_gmodel, n * 4)) || (r = dev_alloc(c, c->d_ginst, n * 4)) || (r = dev_alloc(c, c->d_ghops, n)) || (r = guide_scratch(c)) ||
+        (r = follow_scratch(c)))
+        return r;
+    c->guides_valid = false;
+    if (px)
+    {
+        if ((r = follow_chains(c, sample, max_hops, nullptr))) return r;
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    c->guides_valid = true;
+    c->guides_scene_version = c->scene_version;
+    c->guides_config_version = c->config_version;
+    c->guides_sample = sample;
+    c->guides_max_hops = max_hops;
+    return PT_OK;
+}
+
+int pt_read_guide_hops(pt_ctx* c, uint8_t* hops)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->guides_valid) return fail(c, PT_ERR_STATE, "no guides: pt_render_guides first");
+    const size_t px = c->local_pixels;
+    if (!px || !hops) return PT_OK;
+    if (c->guides_max_hops == 0u) { std::memset(hops, 0, px); return PT_OK; } // first-hit guides: no chain was followed
+    HIPCHK(c, hipMemcpyAsync(hops, c->d_ghops.p, px, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PT_OK;
 }
 
 int pt_read_guide_instances(pt_ctx* c, uint32_t* instance)
@@ -2581,26 +2691,32 @@ int pt_post_denoise(pt_ctx* c, uint32_t w, uint32_t h, const pt_denoise_params* 
 }
 
 // ---- mean albedo and the demodulated filter
-int pt_accumulate_albedo(pt_ctx* c, uint32_t first_sample, uint32_t n_samples)
+} // extern "C"
+namespace {
+// pt_accumulate_albedo (max_hops 0: first hits, its own kernels) and pt_accumulate_albedo_followed
+int accumulate_albedo_locked(pt_ctx* c, uint32_t first_sample, uint32_t n_samples, uint32_t max_hops, const char* who)
 {
-    if (!c) return PT_ERR_ARG;
-    std::lock_guard<std::mutex> lk(c->mu);
     if (!c->scene.built) return fail(c, PT_ERR_STATE, "pt_build has not been called");
     if (!c->scene.camera.set) return fail(c, PT_ERR_STATE, "pt_set_camera has not been called");
-    if (n_samples == 0u) return fail(c, PT_ERR_ARG, "pt_accumulate_albedo: n_samples must be at least 1");
-    if ((uint64_t)first_sample + n_samples > 0x100000000ull) return fail(c, PT_ERR_ARG, "pt_accumulate_albedo: first_sample + n_samples exceeds 2^32");
+    if (n_samples == 0u) return fail(c, PT_ERR_ARG, std::string(who) + ": n_samples must be at least 1");
+    if ((uint64_t)first_sample + n_samples > 0x100000000ull) return fail(c, PT_ERR_ARG, std::string(who) + ": first_sample + n_samples exceeds 2^32");
     int r;
     if ((r = upload_scene(c))) return r;
     const uint32_t px = c->local_pixels;
     const size_t n = std::max<uint32_t>(px, 1);
-    if ((r = guide_scratch(c)) || (r = dev_alloc(c, c->d_albedo_sum, n * 16))) return r;
-    const bool fresh = !albedo_current(c);
+    if ((r = guide_scratch(c)) || (r = dev_alloc(c, c->d_albedo_sum, n * 16)) || (max_hops && (r = follow_scratch(c)))) return r;
+    const bool fresh = !albedo_current(c) || c->albedo_max_hops != max_hops; // sums of other chains are no sums to go on from
     c->albedo_valid = false; // a failure below leaves no sum
     if (fresh) HIPCHK(c, hipMemsetAsync(c->d_albedo_sum.p, 0, n * 16, c->stream));
     if (px)
     {
         for (uint32_t k = 0; k < n_samples; ++k)
         {
+            if (max_hops)
+            {
+                if ((r = follow_chains(c, first_sample + k, max_hops, (f4*)c->d_albedo_sum.p))) return r;
+                continue;
+            }
             if ((r = guide_trace(c, first_sample + k))) return r;
             launch_albedo_accumulate(c->stream, c->sv, c->tex, px, (const f4*)c->d_ghits.p, (f4*)c->d_albedo_sum.p);
         }
@@ -2610,7 +2726,26 @@ int pt_accumulate_albedo(pt_ctx* c, uint32_t first_sample, uint32_t n_samples)
     c->albedo_valid = true;
     c->albedo_scene_version = c->scene_version;
     c->albedo_config_version = c->config_version;
+    c->albedo_max_hops = max_hops;
     return PT_OK;
+}
+} // namespace
+extern "C" {
+
+int pt_accumulate_albedo(pt_ctx* c, uint32_t first_sample, uint32_t n_samples)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    return accumulate_albedo_locked(c, first_sample, n_samples, 0u, "pt_accumulate_albedo");
+}
+
+int pt_accumulate_albedo_followed(pt_ctx* c, uint32_t first_sample, uint32_t n_samples, const pt_guide_params* gp)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    int r;
+    if ((r = follow_params(c, gp, "pt_accumulate_albedo_followed"))) return r;
+    return accumulate_albedo_locked(c, first_sample, n_samples, gp->max_hops, "pt_accumulate_albedo_followed");
 }
 
 int pt_reset_albedo(pt_ctx* c)
@@ -2649,6 +2784,8 @@ int pt_denoise_albedo(pt_ctx* c, const pt_denoise_params* p, uint32_t albedo_sou
     if (!c->d_accum.p) return fail(c, PT_ERR_STATE, "nothing has been accumulated");
     const bool mean = albedo_source == PT_ALBEDO_MEAN;
     if (mean && !albedo_current(c)) return fail(c, PT_ERR_STATE, "no mean albedo (none accumulated, reset, or stale): pt_accumulate_albedo first");
+    if (mean && c->albedo_max_hops != c->guides_max_hops)
+        return fail(c, PT_ERR_STATE, "the guides and the mean albedo were made with different max_hops (pt_render_guides_followed / pt_accumulate_albedo_followed)");
     if ((r = ensure_device(c))) return r;
     const size_t px = c->local_pixels;
     if ((r = denoise_scratch(c, px)) || (r = dev_alloc(c, c->d_dn_k, px * 16)) || (r = dev_alloc(c, c->d_dn_out, px * 16))) return r;
@@ -3101,6 +3238,37 @@ int pt_bsdf_eval(pt_ctx* c, int material, uint32_t n, const float* incoming, con
     float* dout = (float*)t.out((size_t)n * 16);
     if (t.err) return t.err;
     launch_bsdf_probe(c->stream, c->sv, material, n, di, dw, dn, df, dout);
+    return t.download(out4, dout, (size_t)n * 16);
+}
+
+int pt_guide_follow_dir(pt_ctx* c, int on_device, int material, uint32_t n, const float* incoming, const float* normal, const uint8_t* front, float* out4)
+{
+    if (!c || !incoming || !normal || !front || !out4) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (material < 0 || material >= (int)c->scene.materials.size()) return fail(c, PT_ERR_ARG, "material index");
+    if (n == 0) return PT_OK;
+    if (!on_device)
+    {
+        const DMaterial& dm = c->scene.materials[material];
+        for (uint32_t i = 0; i < n; ++i)
+        {
+            const FollowDir f = guide_follow_dir(dm.kind, dm.ior, f3{incoming[3 * i], incoming[3 * i + 1], incoming[3 * i + 2]},
+                                                 f3{normal[3 * i], normal[3 * i + 1], normal[3 * i + 2]}, front[i] != 0);
+            float* o = out4 + 4 * (size_t)i;
+            o[0] = f.wo.x; o[1] = f.wo.y; o[2] = f.wo.z;
+            o[3] = f.followed ? 1.0f : 0.0f;
+        }
+        return PT_OK;
+    }
+    int r;
+    if ((r = upload_scene(c))) return r;
+    Staging t(c);
+    const float* di = (const float*)t.in(incoming, (size_t)n * 12);
+    const float* dn = (const float*)t.in(normal, (size_t)n * 12);
+    const uint8_t* df = (const uint8_t*)t.in(front, n);
+    float* dout = (float*)t.out((size_t)n * 16);
+    if (t.err) return t.err;
+    launch_guide_follow_dir(c->stream, c->sv, material, n, di, dn, df, dout);
     return t.download(out4, dout, (size_t)n * 16);
 }
 

@@ -213,6 +213,26 @@ void launch_surface_colour(hipStream_t s, const SceneView& sv, const TexView& te
                            const float* v, float* rgb);
 
 // unit hooks
+// pt_render_guides_followed / pt_accumulate_albedo_followed: hop `hop` of the guide chains.  `in`: the hook queue launch_trace_rays_closest just
+// traced into hits (n_in: its count word); chains that go on are appended to `next` (n_next: its count word, zero before the launch; both
+// queues hold cap slots).  sum null: a chain that ends writes the six guides of its pixel; else it adds its albedo product to sum[pixel]
+struct FollowArgs
+{
+    RayQueue in, next;
+    const f4* hits;
+    const uint32_t* n_in;
+    uint32_t* n_next;
+    f4* state;             // per pixel: running albedo product | t sum of a chain that goes on
+    f4 *position, *normal, *albedo;
+    uint32_t *model, *instance;
+    uint8_t* hops;
+    f4* sum;
+    uint32_t cap, hop, max_hops;
+};
+void launch_guide_follow(hipStream_t s, const SceneView& sv, const TexView& tex, const FollowArgs& a);
+// pt_guide_follow_dir(on_device = 1): guide_follow_dir (pt_materials.h) of n hits of `material`, out4 = wo | followed
+void launch_guide_follow_dir(hipStream_t s, const SceneView& sv, int material, uint32_t n, const float* incoming, const float* normal, const uint8_t* front,
+                             float* out4);
 // n_and_heads: word 0 = number of rays, words [32, 32 + kHeadWordsPerQueue) = zeroed claim cursors
 void launch_trace_rays_closest(hipStream_t s, const TraceLaunch& tl, uint32_t root, RayQueue rq, uint32_t n, uint32_t* n_and_heads, f4* hits);
 void launch_trace_rays_any(hipStream_t s, const TraceLaunch& tl, uint32_t root, RayQueue rq, uint32_t n, uint32_t* n_and_heads, uint32_t* occluded);

@@ -2970,6 +2970,114 @@ __global__ void __launch_bounds__(256) k_albedo_accumulate(const SceneView sv, c
     const f4 s = sum[i];
     sum[i] = f4{s.x + c.x, s.y + c.y, s.z + c.z, s.w + 1.0f};
 }
+// ---- followed guides (pt_render_guides_followed, pt_accumulate_albedo_followed; include/pt_api.h states the chain)
+// Hop a.hop of every live chain: one thread per ray slot of the `in` hook queue (slot = local pixel at hop 0, compacted afterwards; the
+// ray's pixel rides in rq.b[].w), its closest hit in hits[slot].  A chain that ends here (a miss, a rough surface, the hop cap) writes
+// its pixel's final guides (ACCUM: adds its albedo product to the pixel's mean-albedo sums, one thread owning the pixel as in
+// k_albedo_accumulate); one that goes on parks its running albedo product | t sum in state[pixel] and appends ray hop + 1 to the `next`
+// queue: one ballot and one atomic on the queue's count word per wave, the lane's rank by mbcnt.  That word is what the next hop's
+// k_closest and k_guide_follow read as their ray count, so nothing comes back to the host between hops.  Where a chain lands in `next`
+// shows in nothing it writes: every output is addressed by pixel.
+template <bool ACCUM, bool FIRST>
+__global__ void __launch_bounds__(256, 8) k_guide_follow(const SceneView sv, const TexView tex, const FollowArgs a)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t n = min(*a.n_in, a.cap);
+    bool go_on = false;
+    f4 next_a{}, next_b{};
+    if (i < n)
+    {
+        const f4 hit = a.hits[i];
+        const f4 rb = a.in.b[i];
+        const uint32_t px = asu(rb.w);
+        const f3 d = xyz(rb);
+        f3 c{ACCUM ? 1.0f : 0.0f, ACCUM ? 1.0f : 0.0f, ACCUM ? 1.0f : 0.0f}; // what a chain that ended as a miss leaves
+        const uint32_t hid = asu(hit.w);
+        if (hid == MISS_ID)
+        {
+            if (!ACCUM)
+            {
+                const f3 far = fma3(d, bc3(1e5f), xyz(a.in.a[i]));
+                a.position[px] = f4{far.x, far.y, far.z, 1e5f};
+                a.normal[px] = f4{0.0f, 0.0f, 0.0f, 0.0f};
+                a.model[px] = MISS_ID;
+                a.instance[px] = MISS_ID;
+            }
+        }
+        else
+        {
+            // (one gather after the other, each behind a compiler barrier: hoisting all their loads to the top costs scratch at 64 VGPRs)
+            const uint32_t inst = hid >> sv.prim_bits, tri = hid & ((1u << sv.prim_bits) - 1u);
+            const DMaterial& dm = sv.materials[sv.instances[inst].material];
+            c = surface_colour(tex, dm.texture, f3{dm.colour[0], dm.colour[1], dm.colour[2]}, tri, hit.y, hit.z);
+            float t = hit.x;
+            if (!FIRST)
+            {
+                const f4 s = a.state[px];
+                c = xyz(s) * c;
+                t = s.w + t;
+            }
+            __asm__ volatile("" ::: "memory");
+            bool front;
+            const f3 nrm = hit_normal(sv, inst, tri, hit.y, hit.z, d, front);
+            const FollowDir f = guide_follow_dir(dm.kind, dm.ior, d, nrm, front);
+            go_on = f.followed && a.hop < a.max_hops;
+            __asm__ volatile("" ::: "memory");
+            const f3 p = fma3(d, bc3(hit.x), xyz(a.in.a[i]));
+            if (go_on)
+            {
+                a.state[px] = f4{c.x, c.y, c.z, t};
+                next_a = f4{p.x, p.y, p.z, __builtin_inff()};
+                next_b = f4{f.wo.x, f.wo.y, f.wo.z, asf(px)};
+            }
+            else if (!ACCUM)
+            {
+                a.position[px] = f4{p.x, p.y, p.z, t};
+                a.normal[px] = f4{nrm.x, nrm.y, nrm.z, 0.0f};
+                a.model[px] = sv.instances[inst].blas | (a.hop << 28);
+                a.instance[px] = inst;
+            }
+        }
+        if (!go_on)
+        {
+            if (ACCUM)
+            {
+                const f4 s = a.sum[px];
+                a.sum[px] = f4{s.x + c.x, s.y + c.y, s.z + c.z, s.w + 1.0f};
+            }
+            else
+            {
+                a.albedo[px] = f4{c.x, c.y, c.z, 0.0f};
+                a.hops[px] = (uint8_t)a.hop;
+            }
+        }
+    }
+    // every lane of the block is here (no early exit above), so lane 0 of each wave can reserve for it
+    const uint64_t m = __ballot(go_on);
+    if (m == 0ull) return;
+    uint32_t base = 0u;
+    if (lane_id() == 0u) base = atomicAdd(a.n_next, (uint32_t)__popcll(m));
+    base = __builtin_amdgcn_readfirstlane(base);
+    if (go_on)
+    {
+        const uint32_t pos = base + mbcnt64(m); // < the chains that go on <= n <= a.cap, the queues' slots
+        a.next.a[pos] = next_a;
+        a.next.b[pos] = next_b;
+    }
+}
+// unit hook of guide_follow_dir: out4 = wo | followed
+__global__ void __launch_bounds__(256) k_guide_follow_dir(const SceneView sv, const int material, const uint32_t n, const float* __restrict__ incoming,
+                                                          const float* __restrict__ normal, const uint8_t* __restrict__ front, float* __restrict__ out4)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const DMaterial& dm = sv.materials[material];
+    const FollowDir f = guide_follow_dir(dm.kind, dm.ior, f3{incoming[3 * i], incoming[3 * i + 1], incoming[3 * i + 2]},
+                                         f3{normal[3 * i], normal[3 * i + 1], normal[3 * i + 2]}, front[i] != 0);
+    float* o = out4 + 4 * (size_t)i;
+    o[0] = f.wo.x; o[1] = f.wo.y; o[2] = f.wo.z;
+    o[3] = f.followed ? 1.0f : 0.0f;
+}
 __global__ void __launch_bounds__(256) k_surface_colour(const SceneView sv, const TexView tex, const uint32_t n, const uint32_t* __restrict__ instance,
                                                         const uint32_t* __restrict__ tri, const float* __restrict__ u, const float* __restrict__ v,
                                                         float* __restrict__ rgb)
@@ -3447,6 +3555,20 @@ void launch_albedo_accumulate(hipStream_t s, const SceneView& sv, const TexView&
 {
     if (n == 0u) return;
     hipLaunchKernelGGL(k_albedo_accumulate, dim3((n + 255u) / 256u), dim3(256), 0, s, sv, tex, n, hits, sum);
+}
+void launch_guide_follow(hipStream_t s, const SceneView& sv, const TexView& tex, const FollowArgs& a)
+{
+    if (a.cap == 0u) return;
+    const dim3 grid((a.cap + 255u) / 256u);
+    auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, sv, tex, a); };
+    if (a.sum) a.hop == 0u ? go(k_guide_follow<true, true>) : go(k_guide_follow<true, false>);
+    else a.hop == 0u ? go(k_guide_follow<false, true>) : go(k_guide_follow<false, false>);
+}
+void launch_guide_follow_dir(hipStream_t s, const SceneView& sv, int material, uint32_t n, const float* incoming, const float* normal, const uint8_t* front,
+                             float* out4)
+{
+    if (n == 0u) return;
+    hipLaunchKernelGGL(k_guide_follow_dir, dim3((n + 255u) / 256u), dim3(256), 0, s, sv, material, n, incoming, normal, front, out4);
 }
 void launch_surface_colour(hipStream_t s, const SceneView& sv, const TexView& tex, uint32_t n, const uint32_t* instance, const uint32_t* tri, const float* u,
                            const float* v, float* rgb)

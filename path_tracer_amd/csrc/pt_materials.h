@@ -201,6 +201,22 @@ PT_HD f3 mat_scatter(const MatView& m, Stream& rng, f3 incoming, f3 normal, bool
     }
 }
 
+// pt_render_guides_followed: where the guide chain goes on from a hit (include/pt_api.h).  A mirror reflects; glass refracts, without the
+// Fresnel coin (no draw), and reflects only where refraction is impossible; every other kind ends the chain.  Shared by k_guide_follow,
+// the unit hook's kernel and the hook's host evaluation.
+struct FollowDir { f3 wo; bool followed; };
+PT_HD FollowDir guide_follow_dir(uint32_t kind, float ior, f3 incoming, f3 normal, bool front)
+{
+    if (kind == MAT_SPECULAR) return FollowDir{reflect_rs(incoming, normal), true};
+    if (kind == MAT_DIELECTRIC)
+    {
+        const float eta = front ? (1.0f / ior) : ior;
+        const f3 refracted = refract_rs(incoming, normal, eta);
+        return FollowDir{anynan3(refracted) ? reflect_rs(incoming, normal) : refracted, true};
+    }
+    return FollowDir{f3{0.0f, 0.0f, 0.0f}, false};
+}
+
 // MaterialTrait::get_bsdf_pdf(incoming, outgoing, hit)
 PT_HD BsdfSample mat_bsdf_pdf(const MatView& m, f3 incoming, f3 outgoing, f3 normal, bool front)
 {

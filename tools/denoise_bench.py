@@ -8,7 +8,11 @@ Timing: wall clock of the blocking calls at the given size (median of --reps), g
 --albedo adds the demodulated filter (pt_denoise_albedo, profiles/r13_denoise_albedo.md): its RMSE with the albedo guide and with the mean
 albedo beside pt_denoise's, its cost beside pt_denoise's, and the cost of one sample of pt_accumulate_albedo beside one pt_render_guides.
 
-    python tools/denoise_bench.py [--albedo] [--size 256] [--ref-spp 4096] [--spp 1,4,16,64] [--width 1920 --height 1080 --reps 20] [--out file.json]
+--follow K takes the guides (and the mean albedo) through mirrors and glass, up to K per pixel (pt_render_guides_followed,
+profiles/r16_followed_guides.md), and adds the cost of the guides on the mixed Cornell box at the timing size: the plain call and max_hops
+1, 2 and 8 measured in turn, --reps rounds (median, min and max of each).
+
+    python tools/denoise_bench.py [--albedo] [--follow K] [--size 256] [--ref-spp 4096] [--spp 1,4,16,64] [--width 1920 --height 1080 --reps 20] [--out file.json]
 """
 import argparse
 import json
@@ -25,7 +29,7 @@ def rmse(a, b):
     return float(np.sqrt(np.mean((a[..., :3].astype(np.float64) - b[..., :3].astype(np.float64)) ** 2)))
 
 
-def quality(api, scenes, name, size, ref_spp, spps, depth, albedo=False):
+def quality(api, scenes, name, size, ref_spp, spps, depth, albedo=False, follow=0):
     sc = {"cornell": scenes.cornell_box, "mixed": scenes.cornell_mixed}[name](size, size)
     ref = api.Renderer(sc, size, size, max_bounces=depth)
     racc, _, _ = ref.render(0, ref_spp, want_position=False)
@@ -36,15 +40,15 @@ def quality(api, scenes, name, size, ref_spp, spps, depth, albedo=False):
         for flags, source in ((0, "spatial"), (api.FLAG_ADAPTIVE, "moments")):
             r = api.Renderer(sc, size, size, max_bounces=depth, flags=flags)
             acc, _, _ = r.render(ref_spp, spp, want_position=False)
-            r.render_guides(ref_spp + spp - 1)
+            r.render_guides(ref_spp + spp - 1, follow=follow)
             den = r.denoise()
             noisy = acc / acc[..., 3:4]
-            row = dict(scene=name, size=size, spp=spp, variance=source, rmse_noisy=rmse(noisy, ref_mean), rmse_denoised=rmse(den, ref_mean),
+            row = dict(follow=follow, scene=name, size=size, spp=spp, variance=source, rmse_noisy=rmse(noisy, ref_mean), rmse_denoised=rmse(den, ref_mean),
                        display_rmse_noisy=rmse(r.post_tonemap(acc), ref_disp), display_rmse_denoised=rmse(r.post_tonemap(den), ref_disp))
             row["ratio"] = row["rmse_denoised"] / row["rmse_noisy"]
             row["display_ratio"] = row["display_rmse_denoised"] / row["display_rmse_noisy"]
             if albedo:
-                r.accumulate_albedo(ref_spp, spp)
+                r.accumulate_albedo(ref_spp, spp, follow=follow)
                 for key, src in (("guide", api.ALBEDO_GUIDE), ("mean", api.ALBEDO_MEAN)):
                     dal = r.denoise_albedo(src)
                     row[f"rmse_albedo_{key}"] = rmse(dal, ref_mean)
@@ -84,6 +88,25 @@ def timing(api, scenes, w, h, reps, depth, albedo=False):
     return row
 
 
+def follow_timing(api, scenes, w, h, reps, depth):
+    """pt_render_guides and pt_render_guides_followed at max_hops 1, 2, 8 on the mixed Cornell box, one after the other in every round"""
+    r = api.Renderer(scenes.cornell_mixed(w, h), w, h, max_bounces=depth)
+    hops = (0, 1, 2, 8)
+    t = {k: [] for k in hops}
+    for k in range(reps + 2):
+        for f in hops:
+            t0 = time.perf_counter(); r.render_guides(k, follow=f); t1 = time.perf_counter()
+            if k >= 2:
+                t[f].append(1e3 * (t1 - t0))
+    followed = float((r.read_guide_hops() > 0).mean())
+    r.close()
+    row = dict(scene="mixed", width=w, height=h, reps=reps, followed_fraction_at_8=followed)
+    for f in hops:
+        row[f"ms_guides_follow_{f}"] = dict(median=float(np.median(t[f])), min=float(np.min(t[f])), max=float(np.max(t[f])))
+    print(json.dumps(row), flush=True)
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=256)
@@ -96,15 +119,18 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--no-quality", action="store_true")
     ap.add_argument("--albedo", action="store_true", help="also measure pt_accumulate_albedo and pt_denoise_albedo")
+    ap.add_argument("--follow", type=int, default=0, help="follow up to K mirror / glass surfaces per pixel in the guides (0..8)")
     ap.add_argument("--out")
     a = ap.parse_args()
     from path_tracer_amd import api, scenes
     res = dict(quality=[], timing=None)
     if not a.no_quality:
         for name in a.scenes.split(","):
-            res["quality"] += quality(api, scenes, name, a.size, a.ref_spp, [int(s) for s in a.spp.split(",")], a.bounces, a.albedo)
+            res["quality"] += quality(api, scenes, name, a.size, a.ref_spp, [int(s) for s in a.spp.split(",")], a.bounces, a.albedo, a.follow)
     if a.reps > 0:
         res["timing"] = timing(api, scenes, a.width, a.height, a.reps, a.bounces, a.albedo)
+        if a.follow:
+            res["follow_timing"] = follow_timing(api, scenes, a.width, a.height, a.reps, a.bounces)
     if a.out:
         with open(a.out, "w") as f:
             json.dump(res, f, indent=1)
