@@ -28,6 +28,8 @@
 //       its coverage byte (1 baked, 2 dilated, 0 neither) and the three raw sums as hexadecimal floats (%a)
 //   examples/headless ... --checker N   an N x N checker (texels 1 and 0.2, bilinear, repeating) on the floor, ceiling and back wall (cb_main.obj) with
 //                                        planar UVs: a vertex's (x, z) over the model's own extent in x and z
+//   examples/headless ... --emission-checker N   the same N x N checker as the EMISSION texture of the light (cb_light.obj) under the same planar UVs:
+//                                        a textured area light (pt_set_material_emission_texture)
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -51,7 +53,7 @@ int main(int argc, char** argv)
     bool render_mode = false;
     uint32_t render_first = 0, render_count = 0;
     float aperture = 0.0f, focus = 950.0f; // main.rs:127's values: a pinhole
-    uint32_t probes[3] = {0, 0, 0}, probe_spp = 0, checker = 0, follow = 0;
+    uint32_t probes[3] = {0, 0, 0}, probe_spp = 0, checker = 0, emission_checker = 0, follow = 0;
     std::string probes_out = "";
     uint32_t lightmap[4] = {0, 0, 0, 0}; // W H SPP PASSES
     std::string lightmap_out = "";
@@ -89,6 +91,7 @@ int main(int argc, char** argv)
         }
         else if (a == "--gpus") gpus = (uint32_t)std::atoi(next("--gpus"));
         else if (a == "--checker") checker = (uint32_t)std::atoi(next("--checker"));
+        else if (a == "--emission-checker") emission_checker = (uint32_t)std::atoi(next("--emission-checker"));
         else if (a == "--spp") spp = (uint32_t)std::atoi(next("--spp"));
         else if (a == "--render") { render_mode = true; render_first = (uint32_t)std::atoi(next("--render")); render_count = (uint32_t)std::atoi(next("--render")); }
         else if (a == "--bake-probes")
@@ -111,7 +114,7 @@ int main(int argc, char** argv)
         }
         else if (a == "--help" || a == "-h")
         {
-            std::printf("usage: %s [--width W] [--height H] [--frames N] [--bounces B] [--move] [--slide DX DZ] [--models DIR] [--out file.png] [--denoise file.png] [--denoise-albedo file.png] [--follow K] [--mirror-glass] [--aperture A --focus F] [--projection panorama[:SX:SY]|ortho:HEIGHT] [--bake-probes NX NY NZ SPP file.txt] [--bake-lightmap W H SPP PASSES file.txt] [--checker N]\n", argv[0]);
+            std::printf("usage: %s [--width W] [--height H] [--frames N] [--bounces B] [--move] [--slide DX DZ] [--models DIR] [--out file.png] [--denoise file.png] [--denoise-albedo file.png] [--follow K] [--mirror-glass] [--aperture A --focus F] [--projection panorama[:SX:SY]|ortho:HEIGHT] [--bake-probes NX NY NZ SPP file.txt] [--bake-lightmap W H SPP PASSES file.txt] [--checker N] [--emission-checker N]\n", argv[0]);
             return 0;
         }
         else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
@@ -123,19 +126,20 @@ int main(int argc, char** argv)
         const Material diffuse_green = Lambertian::New({0.12f, 0.45f, 0.15f});
         const Material diffuse_red = Lambertian::New({0.65f, 0.05f, 0.05f});
         const Material light = Emissive::New(Vec3A::splat(15.0f));
-        Material main_gray = diffuse_gray;
-        if (checker)
-        {
+        Material main_gray = diffuse_gray, lamp = light;
+        auto checker_texture = [](uint32_t n) {
             std::vector<float> texels;
-            for (uint32_t j = 0; j < checker; ++j)
-                for (uint32_t i = 0; i < checker; ++i) texels.insert(texels.end(), 3, ((i + j) & 1u) ? 0.2f : 1.0f);
-            main_gray = diffuse_gray.Textured(Texture::New(checker, checker, std::move(texels)));
-        }
+            for (uint32_t j = 0; j < n; ++j)
+                for (uint32_t i = 0; i < n; ++i) texels.insert(texels.end(), 3, ((i + j) & 1u) ? 0.2f : 1.0f);
+            return Texture::New(n, n, std::move(texels));
+        };
+        if (checker) main_gray = diffuse_gray.Textured(checker_texture(checker));
+        if (emission_checker) lamp = light.EmissionTextured(checker_texture(emission_checker));
 
         // Models and BVHs  main.rs:94-117 (the two blocks the reference has commented out stand in for its dragon, whose file it does not ship)
         const std::vector<Affine3A> one{Affine3A::IDENTITY()};
         const Scene scene = Scene::New({
-            Model::New(models_dir + "/cb_light.obj", light, one),
+            Model::New(models_dir + "/cb_light.obj", lamp, one),
             Model::New(models_dir + "/cb_main.obj", main_gray, one),
             Model::New(models_dir + "/cb_right.obj", diffuse_red, one),
             Model::New(models_dir + "/cb_left.obj", diffuse_green, one),
@@ -166,17 +170,19 @@ int main(int argc, char** argv)
         }
         Renderer renderer(scene, cam, width, height, bounces);
         renderer.set_projection(projection);
-        if (checker || !lightmap_out.empty())
-        {
-            const std::vector<float> p = renderer.model_positions(1);
+        // planar UVs: a vertex's (x, z) over the model's own extent in x and z
+        auto planar_uvs = [&](int model) {
+            const std::vector<float> p = renderer.model_positions(model);
             float lo[2] = {p[0], p[2]}, hi[2] = {p[0], p[2]};
             for (size_t v = 0; v < p.size() / 3; ++v)
                 for (int k = 0; k < 2; ++k) { lo[k] = std::min(lo[k], p[3 * v + 2 * k]); hi[k] = std::max(hi[k], p[3 * v + 2 * k]); }
             std::vector<float> uv;
             for (size_t v = 0; v < p.size() / 3; ++v)
                 for (int k = 0; k < 2; ++k) uv.push_back((p[3 * v + 2 * k] - lo[k]) / (hi[k] - lo[k]));
-            renderer.set_model_uvs(1, uv);
-        }
+            renderer.set_model_uvs(model, uv);
+        };
+        if (checker || !lightmap_out.empty()) planar_uvs(1);
+        if (emission_checker) planar_uvs(0);
         // light probes for a run-time consumer: a regular grid inside the scene's bounds, baked by the path tracer
         auto bake_probes = [&]() -> bool {
             if (probes_out.empty()) return true;

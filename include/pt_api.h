@@ -149,7 +149,7 @@ int pt_get_scene_info(pt_ctx* ctx, pt_scene_info* out);
 /* The reference has one colour per material; this is the library's own addition, defined here and checked bit for bit.
  *
  * A TEXTURE is w x h linear-RGB texels (w*h*3 floats, row-major); gamma decoding is the caller's, as for pt_set_environment.  A material of any
- * kind except PT_EMISSIVE may reference one texture.  A model may carry UVs: n_tris * 3 * 2 floats in load order, beside its positions and
+ * kind except PT_EMISSIVE may reference one texture as its surface colour (an emissive one: pt_set_material_emission_texture, below).  A model may carry UVs: n_tris * 3 * 2 floats in load order, beside its positions and
  * normals; a model without UVs has (0, 0) at every vertex.
  *
  * The SURFACE COLOUR at a hit is defined from the hit's instance, the triangle `prim` in the model's load order and the barycentrics u, v of
@@ -175,7 +175,7 @@ int pt_get_scene_info(pt_ctx* ctx, pt_scene_info* out);
  * negative or not finite, a UV that is not finite, a bad index, n_tris different from the model's, or an emissive material; PT_ERR_LIMIT
  * for a texture side above 16384 texels or more than 2^28 texels in all textures together (texels are addressed by 32-bit offsets into one
  * 16-byte-per-texel buffer).  A refused call changes nothing.
- * Out of scope: mip maps and filter footprints, nearest filtering, normal / roughness / emission maps, changing texel data after upload,
+ * Out of scope: mip maps and filter footprints, nearest filtering, normal / roughness maps, changing texel data after upload,
  * PNG decoding.  (Demodulating the denoiser's input by the albedo is pt_denoise_albedo, below.) */
 int pt_add_texture(pt_ctx* ctx, uint32_t w, uint32_t h, const float* rgb_linear);        /* returns the texture index */
 int pt_set_material_texture(pt_ctx* ctx, int material, int texture);                     /* texture -1 clears */
@@ -188,6 +188,49 @@ int pt_model_uvs(pt_ctx* ctx, int model, float* uv, uint32_t cap_tris, uint32_t*
  * on_device 0 evaluates on the host and touches no GPU; 1 runs a kernel over the same function.  PT_ERR_STATE: not built */
 int pt_surface_colour(pt_ctx* ctx, int on_device, uint32_t n, const uint32_t* instance, const uint32_t* prim, const float* u, const float* v,
                       float* rgb);
+
+/* ---- emission textures: textured area lights ----------------------------------------------------------------------- */
+/* The reference's lights radiate one colour per material (material.get_emitted()); this is the library's own addition, defined here and
+ * checked bit for bit.  A PT_EMISSIVE material may reference one texture of pt_add_texture as its EMISSION TEXTURE.
+ *
+ * pt_set_material_emission_texture is accepted only for a PT_EMISSIVE material: PT_ERR_ARG, before any device call, for any other kind or a
+ * bad material or texture index, and a refused call changes nothing.  (pt_set_material_texture keeps refusing emissive materials.)  An
+ * accepted call makes the scene un-built like the other texture setters; the next pt_build rebuilds no BLAS and no TLAS (pt_scene_info's
+ * counters do not move) but does rebuild the light sampler (pt_light_cdf), as does pt_set_model_uvs on a model of such a material; the next
+ * render uploads in full, and pt_multi_render replicates it with the scene.
+ *
+ * All arithmetic is binary32, one rounding per operation, no contraction.
+ * The EMITTED COLOUR at (instance, prim, u, v) is the SURFACE COLOUR exactly as defined above: material.colour * texel, with the same UV
+ * interpolation, repeat addressing and bilinear lookup; the material's colour is the tint, and a model without UVs has (0, 0) everywhere.  It
+ * replaces material.get_emitted() at the three sites the integrator reads it:
+ *   1. an emissive hit (integrator.rs:207-214), with the hit record's (prim, u, v) — in the terminal pass and, in a scene with media, in the
+ *      surface pass that shades emissive hits behind the media;
+ *   2. estimate_direct_explicit (integrator.rs:25-74), at the sampled point: the triangle the sampler picked, (u, v) = (lu, lv) after the flip
+ *      of primitive.rs:81-88 (the point is lw*A + lu*B + lv*C, the hit record's convention);
+ *   3. estimate_direct_bsdf (integrator.rs:77-130), with the light hit's (prim, u, v) from lights.intersect.
+ * The LIGHT WEIGHT of a triangle is area * len(Ec), Ec = the emitted colour at u = v = 0.33333334f.  It replaces
+ * material.get_emitted().length() both in the weights handed to LightSampler::new and in get_sample_pdf (light_sampler.rs:39, as used at
+ * integrator.rs:61 and :111), so the pdf in the MIS weights is the pdf the sampler really has.  For a triangle whose three UVs are equal the
+ * interpolation adds exact zeros: Ec is the material colour times that texel, bit for bit.
+ * Nothing else changes: RNG draws, ray tallies, shade classes, media and positions are what they are without the texture, and an untextured
+ * emissive material follows the old expressions with no arithmetic added.
+ *
+ * The weight is a ONE-POINT QUADRATURE.  A triangle whose centroid texel is black gets weight 0 and is never sampled explicitly; the estimator
+ * stays unbiased, because the BSDF-sampled hits of that triangle get mis2(pw, 0) = 1.  If a zero-weight triangle is the first or last entry
+ * of the CDF, the draw x == 0 or the reference's end-of-CDF clamp can pick it: the sample then divides by a zero pdf, fails the finite check
+ * and is dropped like any NaN sample (probability about 2^-24 per draw); this is documented, not repaired.
+ * If some emissive material has an emission texture and the weight sum is not > 0, every call that refuses "NEE is enabled but the scene has
+ * no emissive model" refuses the same way: PT_ERR_STATE, before any device call.  Scenes without an emission texture behave as ever, black
+ * lights included.
+ *
+ * Where the albedo guide, the mean-albedo sums and the followed guides' c_i say "an emissive hit: its emitted colour", that colour is the
+ * textured one, and pt_surface_colour returns it for instances of such a material.
+ * A scene whose only texture is an emission texture is a textured scene: it runs the TEX variants and queues its shadow rays; with an
+ * emission texture the terminal pass is a TEX variant too, and paths that end at a light are finished there instead of in the traversal.
+ * Out of scope: weights from a true integral of the texture over the triangle, importance sampling inside a triangle, emission on
+ * non-emissive kinds, environment-map sampling, and feeding a baked lightmap back as an emission texture (its texel centres sit half a
+ * texel off the lookup's corners). */
+int pt_set_material_emission_texture(pt_ctx* ctx, int material, int texture);            /* texture -1 clears */
 
 /* ---- Camera::new / create_ray  src/camera.rs:17-31, 94-105 ---------------------------------------------------- */
 int pt_set_camera(pt_ctx* ctx, const float eye[3], const float target[3], float fov_y_deg, float aspect);

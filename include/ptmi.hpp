@@ -17,7 +17,8 @@
 //   (cam.matrix * cam.inv_projection).inverse()  main.rs:128 ptmi::Renderer::inv_projection
 //   state.render()                        state.rs:629       ptmi::Renderer::present
 //   ImageHelper::write_image              image_helper.rs:37 ptmi::Renderer::write_image
-// The library's own additions have no line of the reference: ptmi::Texture with Material::Textured and Model::WithUVs (pt_add_texture).
+// The library's own additions have no line of the reference: ptmi::Texture with Material::Textured and Model::WithUVs (pt_add_texture),
+// Material::EmissionTextured (pt_set_material_emission_texture).
 #pragma once
 #include <array>
 #include <cstdint>
@@ -73,9 +74,12 @@ struct Material
     pt_material_desc d{};
     std::optional<Texture> texture; // surface colour = colour * bilinear texel at the hit's UV; any kind but Emissive
     Material Textured(const Texture& t) const { Material m = *this; m.texture = t; return m; }
+    std::optional<Texture> emission_texture; // Emissive only: emitted colour = colour * bilinear texel at the light's UV (a textured area light)
+    Material EmissionTextured(const Texture& t) const { Material m = *this; m.emission_texture = t; return m; }
     bool operator==(const Material& o) const
     {
-        return (texture ? texture->rgb : nullptr) == (o.texture ? o.texture->rgb : nullptr) && d.kind == o.d.kind && d.colour[0] == o.d.colour[0] && d.colour[1] == o.d.colour[1] && d.colour[2] == o.d.colour[2] &&
+        return (texture ? texture->rgb : nullptr) == (o.texture ? o.texture->rgb : nullptr) &&
+               (emission_texture ? emission_texture->rgb : nullptr) == (o.emission_texture ? o.emission_texture->rgb : nullptr) && d.kind == o.d.kind && d.colour[0] == o.d.colour[0] && d.colour[1] == o.d.colour[1] && d.colour[2] == o.d.colour[2] &&
                d.roughness == o.d.roughness && d.ior == o.d.ior && d.has_volume == o.d.has_volume &&
                (!d.has_volume || (d.vol_absorption[0] == o.d.vol_absorption[0] && d.vol_absorption[1] == o.d.vol_absorption[1] &&
                                   d.vol_absorption[2] == o.d.vol_absorption[2] && d.vol_k == o.d.vol_k && d.vol_c == o.d.vol_c && d.vol_g == o.d.vol_g));
@@ -170,9 +174,7 @@ inline void upload(pt_ctx* ctx_, const Scene& scene)
             {
                 mats.push_back(m.material);
                 check(pt_add_material(ctx_, &m.material.d));
-                if (m.material.texture)
-                {
-                    const Texture& t = *m.material.texture;
+                auto texture_index = [&](const Texture& t) {
                     size_t ti = 0;
                     while (ti < texs.size() && texs[ti] != t.rgb) ++ti;
                     if (ti == texs.size())
@@ -181,8 +183,10 @@ inline void upload(pt_ctx* ctx_, const Scene& scene)
                         texs.push_back(t.rgb);
                         check(pt_add_texture(ctx_, t.w, t.h, t.rgb->data()));
                     }
-                    check(pt_set_material_texture(ctx_, (int)idx, (int)ti));
-                }
+                    return (int)ti;
+                };
+                if (m.material.texture) check(pt_set_material_texture(ctx_, (int)idx, texture_index(*m.material.texture)));
+                if (m.material.emission_texture) check(pt_set_material_emission_texture(ctx_, (int)idx, texture_index(*m.material.emission_texture)));
             }
             const float* mat = m.matrices.empty() ? nullptr : m.matrices[0].m.data();
             const uint32_t n_inst = (uint32_t)m.matrices.size();

@@ -41,6 +41,7 @@ EXPORTS = [
     "pt_integrate_rays", "pt_integrate_rays_device", "pt_bake_probes", "pt_probe_ray",
     "pt_set_instances", "pt_get_scene_info", "pt_read_guide_instances", "pt_frame_moving", "pt_post_motion",
     "pt_add_texture", "pt_set_material_texture", "pt_set_model_uvs", "pt_model_uvs", "pt_surface_colour", "pt_read_guide_albedo",
+    "pt_set_material_emission_texture",
     "pt_accumulate_albedo", "pt_reset_albedo", "pt_read_albedo", "pt_denoise_albedo", "pt_post_denoise_albedo",
     "pt_set_projection", "pt_get_projection",
     "pt_bake_lightmap", "pt_lightmap_texels", "pt_lightmap_ray", "pt_lightmap_dilate",
@@ -246,6 +247,7 @@ def lib():
         L.pt_post_motion.argtypes = [vp, u32, u32, vp, vp, u32, vp, vp, vp, vp, vp]
         L.pt_add_texture.argtypes = [vp, u32, u32, vp]
         L.pt_set_material_texture.argtypes = [vp, C.c_int, C.c_int]
+        L.pt_set_material_emission_texture.argtypes = [vp, C.c_int, C.c_int]
         L.pt_set_model_uvs.argtypes = [vp, C.c_int, vp, u32]
         L.pt_model_uvs.argtypes = [vp, C.c_int, vp, u32, C.POINTER(u32)]
         L.pt_surface_colour.argtypes = [vp, C.c_int, u32, vp, vp, vp, vp, vp]
@@ -311,6 +313,8 @@ class Renderer:
             self._materials.append(m)
             if getattr(m, "texture", None) is not None:
                 self.set_material_texture(mi, self._texture_index(m.texture))
+            if getattr(m, "emission_texture", None) is not None:
+                self.set_material_emission_texture(mi, self._texture_index(m.emission_texture))
         return self._materials.index(m)
 
     def _texture_index(self, t) -> int:
@@ -346,6 +350,10 @@ class Renderer:
     def set_material_texture(self, material: int, texture: int):
         """texture -1 clears"""
         self._chk(self.L.pt_set_material_texture(self.ctx, material, texture))
+
+    def set_material_emission_texture(self, material: int, texture: int):
+        """the emission texture of an EMISSIVE material (textured area light; include/pt_api.h); texture -1 clears"""
+        self._chk(self.L.pt_set_material_emission_texture(self.ctx, material, texture))
 
     def set_model_uvs(self, model: int, uvs):
         """[n_tris, 3, 2] in load order; None clears"""

@@ -475,6 +475,7 @@ TraceLaunch trace_launch(pt_ctx* c, int pipe = 0, bool side_stream = false)
     tl.n_cus = (uint32_t)c->n_cus;
     tl.block_threads = c->block_threads;
     tl.tex = c->textured ? &c->tex : nullptr;
+    tl.emission_tex = c->textured && c->scene.flat.has_emission_textures;
     return tl;
 }
 
@@ -948,7 +949,8 @@ int batch_begin(BatchRun& br, pt_ctx* c, const BatchSpec& spec)
     // a launch of their own on the side stream.  Same-box A/B: LDS-resident scenes whole frame +-0, 1/4 share 18.45 -> 18.3 ms, 1-spp
     // frame 1.24 -> 1.18 ms; BVHs in global memory lose 3 % (82 k mesh 14.2 -> 14.65 ms, 328 k 25.4 -> 26.3 ms: their NEE rays are long and
     // used to overlap the shadow-ray launch), so only the former.  Per-launch event timing (PT_FLAG_TIMING_ALL) keeps the launches apart.
-    br.fused = PT_FUSED_TRACE != 0 && c->lds_scene && !(g.flags & PT_FLAG_TIMING_ALL);
+    // (a scene with an emission texture keeps the launches apart: its world launch is the one that leaves light hits to the terminal pass)
+    br.fused = PT_FUSED_TRACE != 0 && c->lds_scene && !(g.flags & PT_FLAG_TIMING_ALL) && !br.tl.emission_tex;
     // the Lambertian shading pass of an LDS-resident scene walks its own shadow rays; GGX surfaces (the only other class that casts them) still queue theirs
     br.no_shadow_queue = shade_traces_shadow(br.tl) && !c->class_present[Q_GGX];
     return PT_OK;
@@ -1047,7 +1049,7 @@ int batch_end(BatchRun& br, hipEvent_t after)
     {
         batch_nee_launches(br, br.last_row - 1);
         batch_join_side(br);
-        { Timer t(c, pp, s, T_SHADE); launch_shade(s, Q_TERMINAL, c->sv, rp, wb, br.last_row, br.shade_blocks, br.cam, br.lens, br.env); }
+        { Timer t(c, pp, s, T_SHADE); launch_shade(s, Q_TERMINAL, c->sv, rp, wb, br.last_row, br.shade_blocks, br.cam, br.lens, br.env, &br.tl); }
     }
     if (br.nee_err) return fail(c, PT_ERR_HIP, "stream fork/join failed");
     if (after && hipStreamWaitEvent(s, after, 0) != hipSuccess) return fail(c, PT_ERR_HIP, "hipStreamWaitEvent");
@@ -1107,11 +1109,19 @@ int ensure_environment(pt_ctx* c)
     return PT_OK;
 }
 
+// NEE has nothing to sample: no light triangle at all, or (pt_set_material_emission_texture) an emission texture that leaves the light
+// sampler without a positive weight sum.  Scenes without an emission texture are judged as ever, black lights included.
+bool no_light_to_sample(const pt_ctx* c)
+{
+    const FlatScene& f = c->scene.flat;
+    return f.lights.empty() || (f.has_emission_textures && !(f.light_weight_sum > 0.0f));
+}
+
 int precheck(pt_ctx* c)
 {
     if (!c->scene.built) return fail(c, PT_ERR_STATE, "pt_build has not been called");
     if (!c->scene.camera.set) return fail(c, PT_ERR_STATE, "pt_set_camera has not been called");
-    if (c->cfg.enable_nee && c->scene.flat.lights.empty()) return fail(c, PT_ERR_STATE, "NEE is enabled but the scene has no emissive model");
+    if (c->cfg.enable_nee && no_light_to_sample(c)) return fail(c, PT_ERR_STATE, "NEE is enabled but the scene has no emissive model");
     return PT_OK;
 }
 
@@ -1264,7 +1274,7 @@ int render_batches(pt_ctx* c, uint32_t first_sample, uint32_t n_samples, float* 
 int rays_precheck(pt_ctx* c)
 {
     if (!c->scene.built) return fail(c, PT_ERR_STATE, "pt_build has not been called");
-    if (c->cfg.enable_nee && c->scene.flat.lights.empty()) return fail(c, PT_ERR_STATE, "NEE is enabled but the scene has no emissive model");
+    if (c->cfg.enable_nee && no_light_to_sample(c)) return fail(c, PT_ERR_STATE, "NEE is enabled but the scene has no emissive model");
     return PT_OK;
 }
 
@@ -1697,6 +1707,15 @@ int pt_set_material_texture(pt_ctx* c, int material, int texture)
     if (!c) return PT_ERR_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
     if (c->scene.set_material_texture(material, texture) < 0) return fail(c, PT_ERR_ARG, "bad material or texture index, or an emissive material");
+    c->scene_uploaded = false;
+    return PT_OK;
+}
+
+int pt_set_material_emission_texture(pt_ctx* c, int material, int texture)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (c->scene.set_material_emission_texture(material, texture) < 0) return fail(c, PT_ERR_ARG, "bad material or texture index, or a material that is not emissive");
     c->scene_uploaded = false;
     return PT_OK;
 }

@@ -17,6 +17,8 @@ struct TraceLaunch
     uint32_t n_cus;
     uint32_t block_threads;  // 64..256
     const TexView* tex;      // the built scene has a textured material: its texture view (the surface passes are the TEX variants), else null
+    bool emission_tex;       // ... and some EMISSIVE material is among them (pt_set_material_emission_texture): a light hit's colour is looked up, so the
+                             // terminal pass is its TEX variant and the world closest-hit launches leave light hits to it (CLOSEST_WORLD_EMTEX)
 };
 
 // dynamic LDS of a traversal workgroup: the staged BVH blob (LDS scenes) + the per-lane (node, t_enter) stacks

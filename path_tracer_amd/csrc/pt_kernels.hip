@@ -752,8 +752,12 @@ __device__ __forceinline__ Blob stage_scene(const SceneView& sv, const uint4* __
 // and a miss ends the path on the spot (integrator.rs:263-266 with accumulated = 0, path_weight = 1).
 // CLOSEST_PRIMARY_LENS = CLOSEST_PRIMARY under a thin lens (pt_set_lens): the camera rays' origins are read from the queue like any
 // bounce's and go into the shade records (ShadeQueue::c), since no two of them start at the same point.
-enum { CLOSEST_WORLD = 0, CLOSEST_LIGHTS = 1, CLOSEST_HOOK = 2, CLOSEST_PRIMARY = 3, CLOSEST_PRIMARY_LENS = 4 };
+// CLOSEST_WORLD_EMTEX = CLOSEST_WORLD of a scene with an emission texture (pt_set_material_emission_texture): a path that ends at a light
+// is NOT finished here, where the emitted colour of the hit point cannot be looked up, but goes to the terminal queue with its hit record
+// (k_shade_terminal<LENS, TexView>); a miss is finished here as ever.
+enum { CLOSEST_WORLD = 0, CLOSEST_LIGHTS = 1, CLOSEST_HOOK = 2, CLOSEST_PRIMARY = 3, CLOSEST_PRIMARY_LENS = 4, CLOSEST_WORLD_EMTEX = 5 };
 constexpr bool closest_is_primary(int mode) { return mode == CLOSEST_PRIMARY || mode == CLOSEST_PRIMARY_LENS; }
+constexpr bool closest_is_world(int mode) { return mode == CLOSEST_WORLD || mode == CLOSEST_WORLD_EMTEX; }
 
 struct ClosestOut
 {
@@ -1014,7 +1018,7 @@ __device__ __forceinline__ void closest_body(const SceneView& sv, const Blob& bl
             const uint64_t pm = __ballot(pending);
             if (pm != 0ull)
             {
-                if (MODE == CLOSEST_WORLD || closest_is_primary(MODE))
+                if (closest_is_world(MODE) || closest_is_primary(MODE))
                 {
                     if (IDENT && pending) { w.o = with_signs(ob.o, w_signs); w.d = with_signs(ob.d, w_signs >> 3); } // the world ray, bit-exact
                     uint64_t qm = pm;
@@ -1045,7 +1049,7 @@ __device__ __forceinline__ void closest_body(const SceneView& sv, const Blob& bl
                         qm = __ballot(pending && !missed);
                         pending = pending && !missed;
                     }
-                    if (MODE == CLOSEST_WORLD)
+                    if (closest_is_world(MODE))
                     {
                         // A path that ends here — the ray left the scene (integrator.rs:263-266, no environment map) or found a light
                         // (:207-214) — is finished in this kernel, whose memory pipes are idle, instead of a terminal-queue round trip:
@@ -1059,7 +1063,7 @@ __device__ __forceinline__ void closest_body(const SceneView& sv, const Blob& bl
                             else
                             {
                                 const uint4 meta = bl.inst[INST_WORDS * (bid >> prim_bits) + INST_META_WORD];
-                                emissive = ends = (meta.w & 0xffu) == (uint32_t)Q_TERMINAL;
+                                emissive = ends = MODE == CLOSEST_WORLD && (meta.w & 0xffu) == (uint32_t)Q_TERMINAL; // (EMTEX: the terminal pass shades a light hit)
                                 mat_id = meta.z;
                             }
                         }
@@ -1360,7 +1364,7 @@ __device__ __forceinline__ void closest_body(const SceneView& sv, const Blob& bl
             }
         }
     }
-    if (MODE == CLOSEST_WORLD || closest_is_primary(MODE))
+    if (closest_is_world(MODE) || closest_is_primary(MODE))
     {
         const ClosestOutPtr out = launder_args(outp);
         // hand back what is left of this wave's regions as holes (a hole is a path id of HOLE)
@@ -1796,7 +1800,12 @@ __device__ __forceinline__ f3 hit_normal(const SceneView& sv, uint32_t inst, uin
 }
 
 // add the previous bounce's direct-light estimate: accumulated += path_weight * (explicit + bsdf)   integrator.rs:231-234
-__device__ __forceinline__ void resolve_nee(const SceneView& sv, const ShadeIO& io, uint32_t pid, const DPathRec& rec, f3& acc, uint32_t& flags)
+// TEX (a textured scene): the light's emitted colour is its surface colour at the light hit, and the pdf the sampler has for the hit triangle
+// is the host's own weight / sum (HostScene::build_lights: area * |emitted colour at kLightWeightUV| / sum), which a textured scene keeps per
+// light triangle in tri_shade[tri].a.w: the same operations as below, done once on the host.  get_tex() is the kernel's texture view
+template <bool TEX = false, typename GetTex = int>
+__device__ __forceinline__ void resolve_nee(const SceneView& sv, const ShadeIO& io, uint32_t pid, const DPathRec& rec, f3& acc, uint32_t& flags,
+                                            [[maybe_unused]] GetTex get_tex = GetTex{})
 {
     if (!(flags & FLAG_NEE_PENDING)) return;
     const f4 e4 = rec.nee_e;
@@ -1815,10 +1824,16 @@ __device__ __forceinline__ void resolve_nee(const SceneView& sv, const ShadeIO& 
             const uint32_t inst = lid >> sv.prim_bits, tri = lid & ((1u << sv.prim_bits) - 1u);
             const DInstance& in = sv.instances[inst];
             const DMaterial& lm = sv.materials[in.material];
-            const f3 emitted{lm.colour[0], lm.colour[1], lm.colour[2]};
+            f3 emitted{lm.colour[0], lm.colour[1], lm.colour[2]};
             const DTriIsect ti = sv.tri_isect[tri];
             const float area = 0.5f * len3(xyz(ti.n0));                    // primitive.rs:94
-            const float sample_pdf = (area * len3(emitted) / sv.light_weight_sum) / area; // light_sampler.rs:39, integrator.rs:111
+            float sample_pdf;                                             // light_sampler.rs:39, integrator.rs:111
+            if constexpr (TEX)
+            {
+                sample_pdf = sv.tri_shade[tri].a.w / area;
+                emitted = surface_colour(get_tex(), lm.texture, emitted, tri, lh.y, lh.z);
+            }
+            else sample_pdf = (area * len3(emitted) / sv.light_weight_sum) / area;
             const f3 dir = xyz(io.rq_lchain_prev.b[slot]);
             bool ff;
             const f3 ln = hit_normal(sv, inst, tri, lh.y, lh.z, dir, ff);
@@ -1835,9 +1850,15 @@ __device__ __forceinline__ void resolve_nee(const SceneView& sv, const ShadeIO& 
 // ------------------------------------------------------------------------------------------------ shading
 // Q_TERMINAL: misses (integrator.rs:254-269), emissive hits (:207-214) and paths that already ended but still owe an NEE resolve.
 // LENS (pt_set_lens): a camera ray's origin is its own, read from the ray queue at bounce 0 as at any other
-template <bool LENS = false>
-__global__ void __launch_bounds__(256) k_shade_terminal(const SceneView sv, const RenderParams rp, const ShadeIO io, const uint32_t bounce)
+template <typename T>
+__device__ __forceinline__ const T& first_of(const T& t) { return t; }
+// Tex (the terminal pass of a scene with an emission texture: one trailing TexView argument, which no other instantiation has): an emissive
+// hit's emitted colour is its surface colour, and so is the light's in the resolve (resolve_nee<TEX>)
+template <bool LENS = false, typename... Tex>
+__global__ void __launch_bounds__(256) k_shade_terminal(const SceneView sv, const RenderParams rp, const ShadeIO io, const uint32_t bounce, const Tex... tex)
 {
+    constexpr bool TEX = sizeof...(Tex) != 0;
+    static_assert(sizeof...(Tex) <= 1, "at most the texture view");
     const uint32_t n = min(io.ctr->n_shade[Q_TERMINAL], io.cap_slots_term);
     for (uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += gridDim.x * blockDim.x)
     {
@@ -1864,7 +1885,8 @@ __global__ void __launch_bounds__(256) k_shade_terminal(const SceneView sv, cons
             const f4 acc4 = rec.acc;
             acc = xyz(acc4);
             flags = asu(acc4.w);
-            resolve_nee(sv, io, pid, rec, acc, flags);
+            if constexpr (TEX) resolve_nee<true>(sv, io, pid, rec, acc, flags, [&]() -> const TexView& { return first_of(tex...); });
+            else resolve_nee(sv, io, pid, rec, acc, flags);
         }
         if (!dead)
         {
@@ -1891,7 +1913,11 @@ __global__ void __launch_bounds__(256) k_shade_terminal(const SceneView sv, cons
                 }
                 const DMaterial& m = sv.materials[in.material];
                 if (!rp.enable_nee || (flags & FLAG_LAST_DELTA) || bounce == 0u)       // integrator.rs:209-212
-                    acc = fma3(f3{m.colour[0], m.colour[1], m.colour[2]}, pw, acc);
+                {
+                    f3 emitted{m.colour[0], m.colour[1], m.colour[2]};
+                    if constexpr (TEX) emitted = surface_colour(first_of(tex...), m.texture, emitted, hid & ((1u << sv.prim_bits) - 1u), hit.y, hit.z);
+                    acc = fma3(emitted, pw, acc);
+                }
             }
         }
         io.st.radiance[pid] = f4{acc.x, acc.y, acc.z, 0.0f}; // every entry of this queue is a finished path
@@ -2035,12 +2061,16 @@ __device__ __forceinline__ const TexView& shade_args_tex()
 #ifndef PT_TEX_EARLY
 #define PT_TEX_EARLY 0
 #endif
+// EMTEX (with TEX: some emissive material has an emission texture, pt_set_material_emission_texture): the emitted colour of a light is its
+// surface colour too, at the point the explicit estimate sampled and at the light hit of the resolve (resolve_nee<true>).  A parameter of its
+// own: the TEX variants of a scene whose lights are untextured stay the kernels they were.
 template <uint32_t QCLASS, bool VOLUMES, bool INLINE = false, bool IDENT = false, bool LIST = false, bool LENS = false, bool RAYS = false, bool TEX = false,
-          bool ONE_DRAW = false>
+          bool ONE_DRAW = false, bool EMTEX = false>
 __global__ void __launch_bounds__(PT_SHADE_THREADS, INLINE ? PT_SHADE_WAVES_INLINE : shade_waves(QCLASS, VOLUMES))
 k_shade_surface(const std::conditional_t<TEX, ShadeKArgsTex, ShadeKArgs> kargs)
 {
     static_assert(!(TEX && INLINE), "textured scenes queue their shadow rays");
+    static_assert(TEX || !EMTEX, "an emission texture makes a textured scene");
     extern __shared__ uint4 smem_dyn[];
     // Only what the loop header needs is taken from the argument here; each section of an iteration re-reads the launch description from
     // the kernel-argument segment (PT_SHADE_ARGS: scalar loads that hit the constant cache) instead of keeping ~130 words of it in ~100
@@ -2111,7 +2141,8 @@ k_shade_surface(const std::conditional_t<TEX, ShadeKArgsTex, ShadeKArgs> kargs)
                 if (TEX && PT_TEX_EARLY) surf = textured();
                 acc = xyz(acc4);
                 flags = asu(acc4.w);
-                resolve_nee(sv, io, pid, rec, acc, flags);
+                if constexpr (EMTEX) resolve_nee<true>(sv, io, pid, rec, acc, flags, [&]() -> const TexView& { return shade_args_tex(); });
+                else resolve_nee(sv, io, pid, rec, acc, flags);
             }
             else if (TEX && PT_TEX_EARLY) surf = textured();
             pw = xyz(pw4);
@@ -2266,7 +2297,10 @@ k_shade_surface(const std::conditional_t<TEX, ShadeKArgsTex, ShadeKArgs> kargs)
                         const float light_pdf = sample_pdf * (dist2 / cosine);         // integrator.rs:65
                         const float weight = mis2(light_pdf, bp.pdf);
                         const DMaterial& lm = sv.materials[L.material];
-                        ce = f3{lm.colour[0], lm.colour[1], lm.colour[2]} * weight * mat_weakening(mat.kind, dir, normal) * bp.bsdf / light_pdf;
+                        f3 emitted{lm.colour[0], lm.colour[1], lm.colour[2]};
+                        // EMTEX: the emitted colour at the sampled point, whose barycentrics (lu, lv) are the hit record's convention
+                        if constexpr (EMTEX) emitted = surface_colour(shade_args_tex(), lm.texture, emitted, L.tri, lu, lv);
+                        ce = emitted * weight * mat_weakening(mat.kind, dir, normal) * bp.bsdf / light_pdf;
                         want_shadow = true;
                         sh_a = f4{p.x, p.y, p.z, (1.0f - PT_EPSILON) * dist};          // integrator.rs:56
                         sh_b = f4{dir.x, dir.y, dir.z, asf(pid)};
@@ -3244,6 +3278,7 @@ void launch_trace_world(hipStream_t s, const TraceLaunch& tl, const WavefrontBuf
         if (lens_set(opt.lens) || proj_set(opt.proj) || ray_list) launch_closest_impl<CLOSEST_PRIMARY_LENS>(s, tl, tl.scene.world_root, wb.rq[0], &row->n_closest, wb.cap_slots, row_heads(wb, b, HEADS_CLOSEST), out);
         else launch_closest_impl<CLOSEST_PRIMARY>(s, tl, tl.scene.world_root, wb.rq[0], &row->n_closest, wb.cap_slots, row_heads(wb, b, HEADS_CLOSEST), out);
     }
+    else if (tl.emission_tex) launch_closest_impl<CLOSEST_WORLD_EMTEX>(s, tl, tl.scene.world_root, wb.rq[b & 1u], &row->n_closest, wb.cap_slots, row_heads(wb, b, HEADS_CLOSEST), out);
     else launch_closest_impl<CLOSEST_WORLD>(s, tl, tl.scene.world_root, wb.rq[b & 1u], &row->n_closest, wb.cap_slots, row_heads(wb, b, HEADS_CLOSEST), out);
 }
 // world closest hit of bounce b (b >= 1) + the BSDF-sampled NEE rays of bounce b - 1 in one launch (k_trace_fused)
@@ -3359,23 +3394,35 @@ void launch_shade(hipStream_t s, uint32_t qclass, const SceneView& sv, const Ren
         else PT_SURF_L(false, Q, V, __VA_ARGS__);                                                                                        \
     } while (0)
     // the TEX variants of the same classes (a textured scene queues its shadow rays: shade_traces_shadow)
-#define PT_SURF_TEX_L(LENS, Q, V)                                                                                                       \
+    // (E: EMTEX, the scene has an emission texture)
+#define PT_SURF_TEX_L(LENS, Q, V, E)                                                                                                    \
     do {                                                                                                                                 \
-        if (ray_keys) hipLaunchKernelGGL((k_shade_surface<Q, V, false, false, false, LENS, true, true>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), 0, s, kat); \
-        else if (list) hipLaunchKernelGGL((k_shade_surface<Q, V, false, false, true, LENS, false, true>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), 0, s, kat); \
-        else hipLaunchKernelGGL((k_shade_surface<Q, V, false, false, false, LENS, false, true>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), 0, s, kat); \
+        if (ray_keys) hipLaunchKernelGGL((k_shade_surface<Q, V, false, false, false, LENS, true, true, false, E>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), 0, s, kat); \
+        else if (list) hipLaunchKernelGGL((k_shade_surface<Q, V, false, false, true, LENS, false, true, false, E>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), 0, s, kat); \
+        else hipLaunchKernelGGL((k_shade_surface<Q, V, false, false, false, LENS, false, true, false, E>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), 0, s, kat); \
     } while (0)
-#define PT_SURF_TEX_P(Q, V)                                                                                                            \
+#define PT_SURF_TEX_P(Q, V, E)                                                                                                         \
     do {                                                                                                                                 \
-        if (list) hipLaunchKernelGGL((k_shade_surface<Q, V, false, false, true, true, false, true, true>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), 0, s, kat); \
-        else hipLaunchKernelGGL((k_shade_surface<Q, V, false, false, false, true, false, true, true>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), 0, s, kat); \
+        if (list) hipLaunchKernelGGL((k_shade_surface<Q, V, false, false, true, true, false, true, true, E>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), 0, s, kat); \
+        else hipLaunchKernelGGL((k_shade_surface<Q, V, false, false, false, true, false, true, true, E>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), 0, s, kat); \
+    } while (0)
+#define PT_SURF_TEX_E(Q, E)                                                                                                             \
+    do {                                                                                                                                 \
+        if (proj0) { if (sv.has_volumes) PT_SURF_TEX_P(Q, true, E); else PT_SURF_TEX_P(Q, false, E); }                                  \
+        else if (lens0) { if (sv.has_volumes) PT_SURF_TEX_L(true, Q, true, E); else PT_SURF_TEX_L(true, Q, false, E); }                 \
+        else { if (sv.has_volumes) PT_SURF_TEX_L(false, Q, true, E); else PT_SURF_TEX_L(false, Q, false, E); }                          \
     } while (0)
 #define PT_SURF_TEX(Q)                                                                                                                  \
     do {                                                                                                                                 \
-        if (proj0) { if (sv.has_volumes) PT_SURF_TEX_P(Q, true); else PT_SURF_TEX_P(Q, false); }                                        \
-        else if (lens0) { if (sv.has_volumes) PT_SURF_TEX_L(true, Q, true); else PT_SURF_TEX_L(true, Q, false); }                             \
-        else { if (sv.has_volumes) PT_SURF_TEX_L(false, Q, true); else PT_SURF_TEX_L(false, Q, false); }                                 \
+        if (tl->emission_tex) PT_SURF_TEX_E(Q, true);                                                                                    \
+        else PT_SURF_TEX_E(Q, false);                                                                                                    \
     } while (0)
+    if (tex && tl->emission_tex && qclass == Q_TERMINAL)
+    {
+        if (lens0) hipLaunchKernelGGL((k_shade_terminal<true, TexView>), dim3(grid_blocks), dim3(256), 0, s, sv, rp, io, b, *tex);
+        else hipLaunchKernelGGL((k_shade_terminal<false, TexView>), dim3(grid_blocks), dim3(256), 0, s, sv, rp, io, b, *tex);
+        return;
+    }
     if (tex && qclass != Q_TERMINAL)
     {
         switch (qclass)
@@ -3389,6 +3436,7 @@ void launch_shade(hipStream_t s, uint32_t qclass, const SceneView& sv, const Ren
         return;
     }
 #undef PT_SURF_TEX
+#undef PT_SURF_TEX_E
 #undef PT_SURF_TEX_L
 #undef PT_SURF_TEX_P
     switch (qclass)

@@ -8,6 +8,7 @@
 //   Camera::new              src/camera.rs:17-31
 #include "pt_scene.h"
 #include "pt_camera.h"
+#include "pt_materials.h"
 
 #include <algorithm>
 #include <chrono>
@@ -442,6 +443,17 @@ int HostScene::set_material_texture(int material, int texture)
     return 0;
 }
 
+int HostScene::set_material_emission_texture(int material, int texture)
+{
+    if (material < 0 || material >= (int)materials.size() || texture < -1 || texture >= (int)textures.size()) return -1;
+    if (materials[material].kind != MAT_EMISSIVE) return -1;
+    materials[material].texture = (uint32_t)(texture + 1);
+    built = false;
+    lights_valid = false; // the weights of this material's triangles follow the texture
+    ++layout_epoch;
+    return 0;
+}
+
 int HostScene::set_model_uvs(int model, const float* uv, uint32_t n_tris)
 {
     if (model < 0 || model >= (int)models.size()) return -1;
@@ -454,6 +466,7 @@ int HostScene::set_model_uvs(int model, const float* uv, uint32_t n_tris)
             if (!finite_f(uv[i])) return -1;
         m.uvs.assign(uv, uv + (size_t)n_tris * 6);
     }
+    if (materials[m.material].kind == MAT_EMISSIVE && materials[m.material].texture != 0u) lights_valid = false; // its weights follow the UVs
     built = false;
     ++layout_epoch;
     return 0;
@@ -672,10 +685,33 @@ void HostScene::build_lights()                                                  
     {
         const HostBlas& bl = blas[lights.models[a]];
         const DMaterial& mat = materials[bl.material];
-        const float emitted_len = len3(f3{mat.colour[0], mat.colour[1], mat.colour[2]});
+        const f3 colour{mat.colour[0], mat.colour[1], mat.colour[2]};
+        float emitted_len = len3(colour);
+        // An emission texture (pt_api.h, LIGHT WEIGHT): the emitted colour at the barycentrics (1/3, 1/3), through the one surface_colour the
+        // kernels share, over a view of this model's UVs (load order) and this texture alone
+        std::vector<f4> texels;
+        DTexture entry{0u, 0u, 0u, 0u};
+        const std::vector<float>& uv = models[lights.models[a]].uvs;
+        if (mat.texture != 0u)
+        {
+            const HostTexture& t = textures[mat.texture - 1u];
+            entry = DTexture{0u, t.w, t.h, 0u};
+            texels.resize((size_t)t.w * t.h);
+            for (size_t k = 0; k < texels.size(); ++k) texels[k] = f4{t.rgb[3 * k], t.rgb[3 * k + 1], t.rgb[3 * k + 2], 0.0f};
+        }
         for (uint32_t p = 0; p < bl.tris.size(); ++p)
         {
             const float area = 0.5f * len3(f3{bl.tris[p].n0.x, bl.tris[p].n0.y, bl.tris[p].n0.z}); // primitive.rs:94
+            if (mat.texture != 0u)
+            {
+                DTriUV tuv{{0.0f, 0.0f}, {0.0f, 0.0f}, {0.0f, 0.0f}};
+                if (!uv.empty())
+                {
+                    const float* q = &uv[(size_t)p * 6];
+                    tuv = DTriUV{{q[0], q[1]}, {q[2], q[3]}, {q[4], q[5]}};
+                }
+                emitted_len = len3(surface_colour(TexView{texels.data(), &entry, &tuv}, 1u, colour, 0u, kLightWeightUV, kLightWeightUV));
+            }
             weights.push_back(area * emitted_len);
             light_items.push_back(HostLight{a, p, 0, 0});
         }
@@ -720,6 +756,12 @@ int HostScene::build(std::string* err)                                          
         build_lights();
         ++tlas_builds;
         tlas_valid = true;
+        lights_valid = true;
+    }
+    if (!lights_valid) // an emission texture or its UVs changed: the sampler's weights alone
+    {
+        build_lights();
+        lights_valid = true;
     }
     const auto t2 = now();
     int r = flatten(err);
@@ -734,6 +776,7 @@ int HostScene::flatten(std::string* err)
     f.materials = materials;
     for (const DMaterial& m : materials) f.has_volumes = f.has_volumes || m.has_volume != 0;
     for (const DMaterial& m : materials) f.has_textures = f.has_textures || m.texture != 0;
+    for (const DMaterial& m : materials) f.has_emission_textures = f.has_emission_textures || (m.texture != 0 && m.kind == MAT_EMISSIVE);
     // One volume per model.  The reference keys its volume stack by the address of the material (volume.rs:146-162), and every BLAS
     // owns a copy of its model's material (blas.rs:167,197): two models of equal materials are two volumes, all instances of one model
     // are one.  The device keys the stack by material index, so the first model of a volume-bearing material keeps the index and
@@ -991,6 +1034,9 @@ int HostScene::flatten(std::string* err)
     {
         const uint32_t mi = lights.models[l.blas];
         f.lights.push_back(DLight{where[mi][l.prim], (uint32_t)blas[mi].material, l.pdf, l.cdf});
+        // a textured scene's NEE resolve reads the sampler's pdf of the light triangle it hit from the triangle itself (resolve_nee<TEX>);
+        // the word is unused otherwise and stays 0 in an untextured scene, whose tables are then what they always were
+        if (f.has_textures) f.tri_shade[where[mi][l.prim]].a.w = l.pdf;
     }
     f.light_weight_sum = light_weight_sum;
 

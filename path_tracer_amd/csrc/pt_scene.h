@@ -103,7 +103,8 @@ struct FlatScene
     uint32_t ident_tlas = 0;            // IDENT_TLAS_WORLD / IDENT_TLAS_LIGHTS: every instance of that TLAS carries INSTANCE_IDENTITY
     float light_weight_sum = 0;
     bool has_volumes = false;
-    bool has_textures = false;          // some material references a texture: the shading passes are the TEX variants
+    bool has_textures = false;          // some material references a texture, as its surface colour or as its emission: the shading passes are the TEX variants
+    bool has_emission_textures = false; // ... and some EMISSIVE material does (pt_set_material_emission_texture)
     TexView tex_view() const { return TexView{tex_texels.data(), tex_table.data(), tri_uv.data()}; } // over the host copies
     // bytes of every table an upload copies (pt_scene_info::scene_bytes)
     size_t table_bytes() const
@@ -134,6 +135,7 @@ public:
     uint64_t blas_builds = 0, tlas_builds = 0;
     bool tlas_valid = false;    // the two TLASes and the light sampler are those of the current models, materials and matrices: an edit that
                                 // touches none of them (a texture, a material's texture reference, a model's UVs) leaves them standing
+    bool lights_valid = false;  // the light sampler's weights are current: an emission texture, or new UVs on a model that has one, ends that
     bool flat_valid = false;    // `flat` is a finished flatten of layout_epoch flat_epoch: its BLAS nodes and per-triangle tables can be kept
     uint64_t flat_epoch = 0;
 
@@ -150,6 +152,7 @@ public:
     enum : uint64_t { kMaxTextureSide = 16384u, kMaxTexels = 1ull << 28 }; // per side; texels of all textures together (32-bit f4 offsets, 4 GiB)
     int add_texture(uint32_t w, uint32_t h, const float* rgb);
     int set_material_texture(int material, int texture);             // -1 clears
+    int set_material_emission_texture(int material, int texture);    // -1 clears; EMISSIVE materials only (the light sampler is rebuilt)
     int set_model_uvs(int model, const float* uv, uint32_t n_tris);  // nullptr, 0 clears
     int build(std::string* err);
     void set_camera(const float eye[3], const float target[3], float fov_deg, float aspect);

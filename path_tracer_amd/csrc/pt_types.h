@@ -5,7 +5,7 @@
 //                b>>30 = kind: 0 branch (a = left, b&mask = right), 1 triangle leaf (a = first triangle, b&mask = count),
 //                             2 instance leaf (a = instance record)
 //   tri_isect  : 48 B  Havel-Herout planes n0|d0, n1|d1, n2|d2 (primitive.rs:20-26), BLAS-leaf order
-//   tri_shade  : 48 B  vertex normals  (3 x float4, w unused)
+//   tri_shade  : 48 B  vertex normals  (3 x float4, w unused; a.w of a light triangle in a textured scene: its light-sampler pdf)
 //   tri_pos    : 48 B  vertex positions (3 x float4, w unused)  - only light sampling reads it
 //   instances  : 144 B inverse 3x4 | blas root, blas id, material, class | copy of the BLAS root node | forward 3x4
 //   materials  : 64 B
@@ -103,6 +103,10 @@ struct TexView
     const DTexture* table;
     const DTriUV* tri_uv;
 };
+
+// the barycentrics (u = v) of the light sampler's one-point quadrature (pt_api.h, LIGHT WEIGHT): a light triangle's weight is its area times
+// the length of its emitted colour there.  One constant for the host's weights (HostScene::build_lights) and the kernels' pdf (resolve_nee)
+constexpr float kLightWeightUV = 0.33333334f;
 
 struct alignas(16) DLight
 {

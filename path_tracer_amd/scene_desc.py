@@ -67,11 +67,17 @@ class Material:
     ior: float = 1.0
     volume: Optional[Volume] = None
     texture: Optional[Texture] = None  # surface colour = colour * bilinear texel at the hit's UV (any kind but EMISSIVE); the oracle ignores it
+    emission_texture: Optional[Texture] = None  # EMISSIVE only: emitted colour = colour * bilinear texel (pt_set_material_emission_texture); the oracle ignores it
 
     def textured(self, texture: Optional[Texture]) -> "Material":
         """this material with `texture` (None: without one)"""
         assert texture is None or self.kind != EMISSIVE
-        return Material(self.kind, self.colour, self.roughness, self.ior, self.volume, texture)
+        return Material(self.kind, self.colour, self.roughness, self.ior, self.volume, texture, self.emission_texture)
+
+    def emission_textured(self, texture: Optional[Texture]) -> "Material":
+        """this EMISSIVE material with `texture` as its emission texture (None: without one)"""
+        assert texture is None or self.kind == EMISSIVE
+        return Material(self.kind, self.colour, self.roughness, self.ior, self.volume, self.texture, texture)
 
 
 def _c3(v):

@@ -1,6 +1,7 @@
 """Compare two `make asm` outputs kernel by kernel (labels and comments normalised): SAME / DIFF / NEW per kernel.
 A kernel template that gained trailing parameters renames its old instantiations (k<a, b> becomes k<a, b, false>; a kernel that became a
-template, k becomes k<false>): such a kernel is compared with the one it was and marked `+param`.
+template, k becomes k<false>; one that gained a trailing parameter PACK keeps k<a, b> with the empty pack, under another symbol): such a
+kernel is compared with the one it was and marked `+param`.
 usage: python tools/asm_diff.py old.s new.s"""
 import re, subprocess, sys
 
@@ -19,8 +20,9 @@ def dem(n):
     return m.group(1) if m else d[:70]
 
 def was(name, old_names):
-    """the old name of a kernel whose template gained trailing `false` parameters, or None"""
+    """the old name of a kernel whose template gained trailing `false` parameters or an empty parameter pack, or None"""
     d = dem(name)
+    if d in old_names: return old_names[d]
     while True:
         d2 = re.sub(r'(, |<)false>$', lambda m: '>' if m.group(1) == ', ' else '', d)
         if d2 == d: return None

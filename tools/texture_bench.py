@@ -5,6 +5,8 @@ TEX shading variants (and of queueing the shadow rays the untextured frame walks
 
     python tools/texture_bench.py [--width 1920 --height 1080 --spp 256 --bounces 8 --reps 5 --repeat 8] [--out file.json]
     python tools/texture_bench.py --only tex1024 --reps 1      one variant alone, e.g. under rocprofv3 --kernel-trace --stats
+    python tools/texture_bench.py --emission --reps 5          adds `emit8`: the untextured frame with its LIGHT on an 8 x 8 checker emission texture
+                                                               (profiles/r17_emission_textures.md): emit8_over_plain beside tex8_over_plain
 """
 import argparse
 import json
@@ -41,6 +43,18 @@ def textured_cornell(scenes, W, H, n, repeat):
     return SceneDesc.new(models, scenes.reference_camera(W / H), f"cornell checker {n}")
 
 
+def emission_cornell(scenes, W, H, n):
+    """the Cornell frame with an n x n checker as the emission texture of its light, UVs planar over the light's extent"""
+    from path_tracer_amd.scene_desc import Model, SceneDesc, Texture
+    tex = Texture.new(checker(n))
+    models = []
+    for m in scenes.cornell_models():
+        if m.name == "cb_light":
+            m = Model.new(m.positions, m.normals, m.material.emission_textured(tex), m.matrices, m.name, uvs=planar_uvs(m.positions, 1.0))
+        models.append(m)
+    return SceneDesc.new(models, scenes.reference_camera(W / H), f"cornell emission checker {n}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--width", type=int, default=1920)
@@ -49,13 +63,16 @@ def main():
     ap.add_argument("--bounces", type=int, default=8)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--repeat", type=float, default=8.0)
-    ap.add_argument("--only", choices=["plain", "tex8", "tex1024"])
+    ap.add_argument("--only", choices=["plain", "tex8", "tex1024", "emit8"])
+    ap.add_argument("--emission", action="store_true", help="also measure emit8: the light on an 8 x 8 checker emission texture")
     ap.add_argument("--out")
     a = ap.parse_args()
     from path_tracer_amd import api, scenes
     W, H = a.width, a.height
     variants = {"plain": lambda: scenes.cornell_box(W, H), "tex8": lambda: textured_cornell(scenes, W, H, 8, a.repeat),
                 "tex1024": lambda: textured_cornell(scenes, W, H, 1024, a.repeat)}
+    if a.emission or a.only == "emit8":
+        variants["emit8"] = lambda: emission_cornell(scenes, W, H, 8)
     if a.only:
         variants = {a.only: variants[a.only]}
     rs = {}
@@ -65,7 +82,7 @@ def main():
         r.synchronize()
         rs[name] = r
     times = {name: [] for name in rs}
-    for rep in range(a.reps):              # interleaved: whatever else the machine does falls on all three
+    for rep in range(a.reps):              # interleaved: whatever else the machine does falls on all of them
         for name, r in rs.items():
             r.reset_accumulation()
             r.synchronize()
