@@ -30,8 +30,13 @@
 //                                        planar UVs: a vertex's (x, z) over the model's own extent in x and z
 //   examples/headless ... --emission-checker N   the same N x N checker as the EMISSION texture of the light (cb_light.obj) under the same planar UVs:
 //                                        a textured area light (pt_set_material_emission_texture)
+//   examples/headless ... --normal-ripples N   an N x N procedural ripple NORMAL map (pt_set_material_normal_texture) on cb_main.obj: texel (i, j) is the
+//                                        tangent-space vector (0.3 * tri((i + 0.5) / N), 0.3 * tri((j + 0.5) / N), z), tri(a) = 4 * |a - 0.5| - 1, z making it
+//                                        a unit vector, encoded 0.5 * v + 0.5 (every step one binary32 operation).  UVs: s = x, t = y + z over the model's own
+//                                        extents, so that the floor, the ceiling and the back wall all have a tangent frame
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -53,7 +58,7 @@ int main(int argc, char** argv)
     bool render_mode = false;
     uint32_t render_first = 0, render_count = 0;
     float aperture = 0.0f, focus = 950.0f; // main.rs:127's values: a pinhole
-    uint32_t probes[3] = {0, 0, 0}, probe_spp = 0, checker = 0, emission_checker = 0, follow = 0;
+    uint32_t probes[3] = {0, 0, 0}, probe_spp = 0, checker = 0, emission_checker = 0, normal_ripples = 0, follow = 0;
     std::string probes_out = "";
     uint32_t lightmap[4] = {0, 0, 0, 0}; // W H SPP PASSES
     std::string lightmap_out = "";
@@ -91,6 +96,7 @@ int main(int argc, char** argv)
         }
         else if (a == "--gpus") gpus = (uint32_t)std::atoi(next("--gpus"));
         else if (a == "--checker") checker = (uint32_t)std::atoi(next("--checker"));
+        else if (a == "--normal-ripples") normal_ripples = (uint32_t)std::atoi(next("--normal-ripples"));
         else if (a == "--emission-checker") emission_checker = (uint32_t)std::atoi(next("--emission-checker"));
         else if (a == "--spp") spp = (uint32_t)std::atoi(next("--spp"));
         else if (a == "--render") { render_mode = true; render_first = (uint32_t)std::atoi(next("--render")); render_count = (uint32_t)std::atoi(next("--render")); }
@@ -114,10 +120,16 @@ int main(int argc, char** argv)
         }
         else if (a == "--help" || a == "-h")
         {
-            std::printf("usage: %s [--width W] [--height H] [--frames N] [--bounces B] [--move] [--slide DX DZ] [--models DIR] [--out file.png] [--denoise file.png] [--denoise-albedo file.png] [--follow K] [--mirror-glass] [--aperture A --focus F] [--projection panorama[:SX:SY]|ortho:HEIGHT] [--bake-probes NX NY NZ SPP file.txt] [--bake-lightmap W H SPP PASSES file.txt] [--checker N] [--emission-checker N]\n", argv[0]);
+            std::printf("usage: %s [--width W] [--height H] [--frames N] [--bounces B] [--move] [--slide DX DZ] [--models DIR] [--out file.png] [--denoise file.png] [--denoise-albedo file.png] [--follow K] [--mirror-glass] [--aperture A --focus F] [--projection panorama[:SX:SY]|ortho:HEIGHT] [--bake-probes NX NY NZ SPP file.txt] [--bake-lightmap W H SPP PASSES file.txt] [--checker N] [--emission-checker N] [--normal-ripples N]\n", argv[0]);
             return 0;
         }
         else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
+    }
+    if (normal_ripples && (checker || !lightmap_out.empty()))
+    {
+        // both want the UVs of cb_main.obj: the checker and the lightmap the planar (x, z) ones, the ripples (x, y + z)
+        std::fprintf(stderr, "--normal-ripples cannot be combined with --checker or --bake-lightmap: each sets the UVs of cb_main.obj\n");
+        return 2;
     }
     try
     {
@@ -135,6 +147,21 @@ int main(int argc, char** argv)
         };
         if (checker) main_gray = diffuse_gray.Textured(checker_texture(checker));
         if (emission_checker) lamp = light.EmissionTextured(checker_texture(emission_checker));
+        if (normal_ripples)
+        {
+            const uint32_t n = normal_ripples;
+            std::vector<float> texels;
+            auto tri = [n](uint32_t i) { const float a = ((float)i + 0.5f) / (float)n; return 0.3f * (4.0f * std::fabs(a - 0.5f) - 1.0f); };
+            for (uint32_t j = 0; j < n; ++j)
+                for (uint32_t i = 0; i < n; ++i)
+                {
+                    const float x = tri(i), y = tri(j);
+                    const float z = std::sqrt((1.0f - x * x) - y * y);
+                    const float v[3] = {x, y, z};
+                    for (float c : v) texels.push_back(0.5f * c + 0.5f);
+                }
+            main_gray = main_gray.NormalMapped(Texture::New(n, n, std::move(texels)));
+        }
 
         // Models and BVHs  main.rs:94-117 (the two blocks the reference has commented out stand in for its dragon, whose file it does not ship)
         const std::vector<Affine3A> one{Affine3A::IDENTITY()};
@@ -183,6 +210,19 @@ int main(int argc, char** argv)
         };
         if (checker || !lightmap_out.empty()) planar_uvs(1);
         if (emission_checker) planar_uvs(0);
+        if (normal_ripples)
+        {
+            // s = x, t = y + z, each over the model's own extent: no face of the room is degenerate in them
+            const std::vector<float> p = renderer.model_positions(1);
+            auto st = [&](size_t v, int k) { return k == 0 ? p[3 * v] : p[3 * v + 1] + p[3 * v + 2]; };
+            float lo[2] = {st(0, 0), st(0, 1)}, hi[2] = {st(0, 0), st(0, 1)};
+            for (size_t v = 0; v < p.size() / 3; ++v)
+                for (int k = 0; k < 2; ++k) { lo[k] = std::min(lo[k], st(v, k)); hi[k] = std::max(hi[k], st(v, k)); }
+            std::vector<float> uv;
+            for (size_t v = 0; v < p.size() / 3; ++v)
+                for (int k = 0; k < 2; ++k) uv.push_back((st(v, k) - lo[k]) / (hi[k] - lo[k]));
+            renderer.set_model_uvs(1, uv);
+        }
         // light probes for a run-time consumer: a regular grid inside the scene's bounds, baked by the path tracer
         auto bake_probes = [&]() -> bool {
             if (probes_out.empty()) return true;

@@ -175,7 +175,7 @@ int pt_get_scene_info(pt_ctx* ctx, pt_scene_info* out);
  * negative or not finite, a UV that is not finite, a bad index, n_tris different from the model's, or an emissive material; PT_ERR_LIMIT
  * for a texture side above 16384 texels or more than 2^28 texels in all textures together (texels are addressed by 32-bit offsets into one
  * 16-byte-per-texel buffer).  A refused call changes nothing.
- * Out of scope: mip maps and filter footprints, nearest filtering, normal / roughness maps, changing texel data after upload,
+ * Out of scope: mip maps and filter footprints, nearest filtering, roughness maps (normal maps: pt_set_material_normal_texture, below), changing texel data after upload,
  * PNG decoding.  (Demodulating the denoiser's input by the albedo is pt_denoise_albedo, below.) */
 int pt_add_texture(pt_ctx* ctx, uint32_t w, uint32_t h, const float* rgb_linear);        /* returns the texture index */
 int pt_set_material_texture(pt_ctx* ctx, int material, int texture);                     /* texture -1 clears */
@@ -231,6 +231,64 @@ int pt_surface_colour(pt_ctx* ctx, int on_device, uint32_t n, const uint32_t* in
  * non-emissive kinds, environment-map sampling, and feeding a baked lightmap back as an emission texture (its texel centres sit half a
  * texel off the lookup's corners). */
 int pt_set_material_emission_texture(pt_ctx* ctx, int material, int texture);            /* texture -1 clears */
+
+/* ---- normal maps: tangent-space shading normals from a texture --------------------------------------------------------- */
+/* The reference shades with the interpolated vertex normal; this is the library's own addition, defined here and checked bit for bit.
+ * A material of any kind except PT_EMISSIVE may reference one texture of pt_add_texture as its NORMAL TEXTURE, independently of its colour
+ * texture (either, both or neither).  Texels are the usual encoding: rgb in [0, 1] stands for a tangent-space vector in [-1, 1]^3.
+ *
+ * All arithmetic is binary32, one rounding per operation, no contraction, in the order written (dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z,
+ * cross(a, b) = (a.y*b.z - a.z*b.y, a.z*b.x - a.x*b.z, a.x*b.y - a.y*b.x), unit3(a) = a / sqrt(dot(a, a)) per component, glam's).
+ * For a hit (instance, load-order triangle, barycentrics u, v, world direction d) let N = unit3((Na * (1 - u - v) + Nb * u) + Nc * v) be the
+ * object-space interpolated normal and front = dot(d_obj, N) < 0 (d_obj: the rows of the instance's inverse 3x3 applied to d), as without a map.
+ * The SHADING NORMAL is
+ *     s, t    = the hit's interpolated, repeat-addressed UV      -- exactly the surface colour's s, t
+ *     c       = get_pixel_bilinear(normal texture, s, t)         -- as the surface colour's texel, with ONE exception: when the four texels the
+ *                                                                   lookup reads are equal (r, g and b), c is that texel, with no arithmetic.  (The
+ *                                                                   four weights need not sum to exactly 1 in binary32: without the exception a
+ *                                                                   constant map would come back an ulp off at some UVs.)
+ *     x, y, z = 2*c.r - 1, 2*c.g - 1, 2*c.b - 1
+ *     if x == 0 and y == 0:  N' = N                              -- no arithmetic: a flat texel (0.5, 0.5, any) IS the plain normal, bit for bit
+ *     else if T == (0, 0, 0): N' = N                             -- a triangle without a tangent, below
+ *     else:
+ *         Tp = unit3(T - N * dot(N, T))                          -- Gram-Schmidt at the hit
+ *         Bp = cross(N, Tp) * sign
+ *         N' = unit3((Tp * x + Bp * y) + N * z)
+ *     if not front: N' = -N'                                     -- front is the flag of the UNPERTURBED N
+ *     world normal = (R.r0 . N', R.r1 . N', R.r2 . N'), R = the rows of the instance's forward 3x3, each dot as above; not renormalised, as today
+ * TANGENTS are per triangle, computed on the host from the object-space positions p0, p1, p2 and UVs a, b, c (s, t pairs) in load order:
+ *     e1 = p1 - p0;  e2 = p2 - p0;  d1 = b - a;  d2 = c - a
+ *     det  = d1.s * d2.t - d2.s * d1.t
+ *     T    = (e1 * d2.t - e2 * d1.t) / det                       -- vector * scalar, vector - vector, vector / scalar, per component
+ *     B    = (e2 * d1.s - e1 * d2.s) / det
+ *     sign = dot(cross(e1, e2), cross(T, B)) < 0 ? -1 : +1       -- the handedness of (T, B, geometric normal)
+ * A triangle with det == 0 or a T that is not finite has T = (0, 0, 0), sign = +1, and so has every triangle of a model without UVs: their
+ * hits keep N' = N whatever the texel.  (A T parallel to N makes Tp a NaN vector and the sample fails the integrator's finite check and is
+ * dropped; that needs a vertex normal perpendicular to its own face and is not repaired.)
+ *
+ * N' replaces the shading normal everywhere the surface shading pass uses it for the hit being shaded: the scatter direction, get_bsdf_pdf and
+ * the weakening, both direct-light estimates (the cosine tests and the BSDF at the surface), reflection and refraction.  These do not change:
+ * front, the ray origin p, RNG draws, ray tallies, shade classes, the light sampler, media, the first-hit outputs (position, id), and the
+ * normal at a sampled or hit point ON a light (lights are emissive and have no map).  A perturbed normal that faces away from the viewer is
+ * used as it is: the material functions then do what they do with a negative cosine (a Lambertian weakening is an absolute value; a sample
+ * that comes out non-finite is dropped by the integrator's finite check as ever); nothing is clamped or re-reflected.
+ *
+ * pt_set_material_normal_texture makes the scene un-built like the other texture setters; the next pt_build rebuilds no BLAS and no TLAS and
+ * the next render uploads in full; pt_set_instances + pt_build afterwards keeps the patch path.  PT_ERR_ARG, before any device call, for a bad
+ * material or texture index or a PT_EMISSIVE material (so also for one that has an emission texture); a refused call changes nothing.  A scene
+ * with a normal-mapped material is a textured scene (UVs, texel tables, TEX variants, queued shadow rays) that also carries one 16-byte
+ * tangent per triangle and runs the normal-map variants of the surface passes; a scene without one flattens to the bytes and launches the
+ * kernels it does without this entry point.
+ * Out of scope: a strength / scale factor, object-space normal maps, roughness / height / parallax maps, mip maps, per-vertex tangents (the
+ * tangent is per triangle, so it is discontinuous across the edges of a curved mesh), the guides (pt_render_guides' normal guide and
+ * pt_guide_follow_dir keep the unperturbed normal: a followed reflection in a rippled mirror is the smooth mirror's), the lightmap baker's
+ * hemisphere, and microfacet-style fixes for perturbed normals below the horizon. */
+int pt_set_material_normal_texture(pt_ctx* ctx, int material, int texture);              /* texture -1 clears */
+/* unit hook: the world shading normal (as defined above; without a normal texture: the face-forwarded interpolated normal) and the front flag
+ * of n hits of a BUILT scene; instance = world-TLAS leaf in allocation order, prim in load order, dir = the ray's world direction.
+ * on_device 0 evaluates on the host and touches no GPU; 1 runs a kernel over the same function.  PT_ERR_STATE: not built */
+int pt_shading_normal(pt_ctx* ctx, int on_device, uint32_t n, const uint32_t* instance, const uint32_t* prim, const float* u, const float* v,
+                      const float* dir_xyz, float* out_normal_xyz, uint8_t* out_front);
 
 /* ---- Camera::new / create_ray  src/camera.rs:17-31, 94-105 ---------------------------------------------------- */
 int pt_set_camera(pt_ctx* ctx, const float eye[3], const float target[3], float fov_y_deg, float aspect);

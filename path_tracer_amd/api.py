@@ -41,7 +41,7 @@ EXPORTS = [
     "pt_integrate_rays", "pt_integrate_rays_device", "pt_bake_probes", "pt_probe_ray",
     "pt_set_instances", "pt_get_scene_info", "pt_read_guide_instances", "pt_frame_moving", "pt_post_motion",
     "pt_add_texture", "pt_set_material_texture", "pt_set_model_uvs", "pt_model_uvs", "pt_surface_colour", "pt_read_guide_albedo",
-    "pt_set_material_emission_texture",
+    "pt_set_material_emission_texture", "pt_set_material_normal_texture", "pt_shading_normal",
     "pt_accumulate_albedo", "pt_reset_albedo", "pt_read_albedo", "pt_denoise_albedo", "pt_post_denoise_albedo",
     "pt_set_projection", "pt_get_projection",
     "pt_bake_lightmap", "pt_lightmap_texels", "pt_lightmap_ray", "pt_lightmap_dilate",
@@ -248,6 +248,8 @@ def lib():
         L.pt_add_texture.argtypes = [vp, u32, u32, vp]
         L.pt_set_material_texture.argtypes = [vp, C.c_int, C.c_int]
         L.pt_set_material_emission_texture.argtypes = [vp, C.c_int, C.c_int]
+        L.pt_set_material_normal_texture.argtypes = [vp, C.c_int, C.c_int]
+        L.pt_shading_normal.argtypes = [vp, C.c_int, u32, vp, vp, vp, vp, vp, vp, vp]
         L.pt_set_model_uvs.argtypes = [vp, C.c_int, vp, u32]
         L.pt_model_uvs.argtypes = [vp, C.c_int, vp, u32, C.POINTER(u32)]
         L.pt_surface_colour.argtypes = [vp, C.c_int, u32, vp, vp, vp, vp, vp]
@@ -315,6 +317,8 @@ class Renderer:
                 self.set_material_texture(mi, self._texture_index(m.texture))
             if getattr(m, "emission_texture", None) is not None:
                 self.set_material_emission_texture(mi, self._texture_index(m.emission_texture))
+            if getattr(m, "normal_texture", None) is not None:
+                self.set_material_normal_texture(mi, self._texture_index(m.normal_texture))
         return self._materials.index(m)
 
     def _texture_index(self, t) -> int:
@@ -355,6 +359,10 @@ class Renderer:
         """the emission texture of an EMISSIVE material (textured area light; include/pt_api.h); texture -1 clears"""
         self._chk(self.L.pt_set_material_emission_texture(self.ctx, material, texture))
 
+    def set_material_normal_texture(self, material: int, texture: int):
+        """the tangent-space normal map of a material of any kind but EMISSIVE (include/pt_api.h); texture -1 clears"""
+        self._chk(self.L.pt_set_material_normal_texture(self.ctx, material, texture))
+
     def set_model_uvs(self, model: int, uvs):
         """[n_tris, 3, 2] in load order; None clears"""
         if uvs is None:
@@ -382,6 +390,18 @@ class Renderer:
         out = np.zeros((i.shape[0], 3), np.float32)
         self._chk(self.L.pt_surface_colour(self.ctx, int(bool(on_device)), i.shape[0], _p(i), _p(p), _p(uu), _p(vv), _p(out)))
         return out
+
+    def shading_normal(self, instance, prim, u, v, direction, on_device=False):
+        """unit hook: the world shading normal [n, 3] and the front flag [n] (uint8) of hits (world-TLAS instance, load-order primitive,
+        barycentrics, world ray direction [n, 3]) of the built scene, normal maps applied; on the host (no GPU) unless on_device"""
+        i = np.ascontiguousarray(instance, dtype=np.uint32); p = np.ascontiguousarray(prim, dtype=np.uint32)
+        uu = np.ascontiguousarray(u, dtype=np.float32); vv = np.ascontiguousarray(v, dtype=np.float32)
+        d = np.ascontiguousarray(direction, dtype=np.float32)
+        assert i.shape == p.shape == uu.shape == vv.shape and i.ndim == 1 and d.shape == (i.shape[0], 3)
+        out = np.zeros((i.shape[0], 3), np.float32)
+        front = np.zeros(i.shape[0], np.uint8)
+        self._chk(self.L.pt_shading_normal(self.ctx, int(bool(on_device)), i.shape[0], _p(i), _p(p), _p(uu), _p(vv), _p(d), _p(out), _p(front)))
+        return out, front
 
     def rebuild(self):
         self._chk(self.L.pt_build(self.ctx))

@@ -13,6 +13,9 @@
 //   host_sanitize plan <row>...        pt_batch_plan.h: each row "b:free,held,classes,volumes" (max_paths_for) or
 //                                      "p:n_samples,act_pixels,samples_out,pipelines,batch_spp,lds_scene,max_paths,cap0,cap1,cap2,cap3"
 //                                      (plan_batches); prints a JSON list: max_paths, or [batch, n_batches, n_pipes] ([0, 0, 0]: refused)
+//   host_sanitize normals <n> <seed>   normal maps' host side: n random triangles with random UVs (degenerate, huge and mirrored ones among them) under a
+//                                      normal texture, Scene::new, then shading_normal (pt_materials.h) at random hits over the flattened tables;
+//                                      prints how many triangles got a tangent and a checksum of the normals
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -22,6 +25,7 @@
 #include <vector>
 
 #include "pt_batch_plan.h"
+#include "pt_materials.h"
 #include "pt_png.h"
 #include "pt_scene.h"
 
@@ -178,6 +182,54 @@ int main(int argc, char** argv)
             if (!ok) { std::printf("{\"error\": \"move %d: the incremental build differs from a build from nothing\"}\n", e); return 7; }
         }
         std::printf("{\"moves\": %d, \"kept_blas_part\": %d, \"blas_builds\": %llu}\n", std::atoi(argv[2]), kept, (unsigned long long)moved.blas_builds);
+        return 0;
+    }
+    if (cmd == "normals" && argc >= 4)
+    {
+        const uint32_t n = (uint32_t)std::atoi(argv[2]);
+        uint64_t s = 0x9E3779B97F4A7C15ull ^ (uint64_t)std::atoll(argv[3]);
+        auto rnd = [&]() { s ^= s << 13; s ^= s >> 7; s ^= s << 17; return (float)((s >> 40) & 0xffff) / 65535.0f; };
+        HostScene sc;
+        const int mat = light_scene(sc);
+        if (mat < 0 || n == 0) return 3;
+        std::vector<float> p, nr, uv, texels;
+        for (uint32_t t = 0; t < n; ++t)
+        {
+            const float c[3] = {200.0f * rnd() - 100.0f, 200.0f * rnd() - 100.0f, 200.0f * rnd() - 100.0f};
+            for (int v = 0; v < 3; ++v)
+                for (int k = 0; k < 3; ++k) { p.push_back(c[k] + 10.0f * rnd() - 5.0f); nr.push_back(k == 1 ? 1.0f : 0.2f * rnd() - 0.1f); }
+            const uint32_t shape = t % 5u; // general, all equal, collinear, around 1e6, mirrored
+            const float a[2] = {4.0f * rnd() - 2.0f, 4.0f * rnd() - 2.0f};
+            for (int v = 0; v < 3; ++v)
+                for (int k = 0; k < 2; ++k)
+                    uv.push_back(shape == 1u ? a[k] : shape == 2u ? a[0] + 0.25f * (float)v : shape == 3u ? 1.0e6f + 3.0f * rnd() : (shape == 4u && v ? -1.0f : 1.0f) * (a[k] + rnd()));
+        }
+        for (int k = 0; k < 5 * 3; ++k) { texels.push_back(rnd()); texels.push_back(rnd()); texels.push_back(0.5f + 0.5f * rnd()); }
+        const int model = sc.add_model(p.data(), nr.data(), n, mat, kIdentity, 1);
+        const int tex = sc.add_texture(5, 3, texels.data());
+        if (model < 0 || tex < 0 || sc.set_model_uvs(model, uv.data(), n) != 0) return 4;
+        if (sc.set_material_normal_texture(1, tex) != -1 || sc.set_material_normal_texture(mat, 7) != -1 || sc.set_material_normal_texture(mat, tex) != 0) return 5;
+        std::string err;
+        if (sc.build(&err) != 0) { std::printf("{\"error\": \"%s\"}\n", err.c_str()); return 0; }
+        const FlatScene& f = sc.flat;
+        if (!f.has_normal_maps || f.tri_tan.size() != f.tri_orig.size() || f.tri_uv.size() != f.tri_orig.size()) return 6;
+        uint32_t with_tangent = 0;
+        for (const f4& t : f.tri_tan) with_tangent += (t.x != 0.0f || t.y != 0.0f || t.z != 0.0f) ? 1u : 0u;
+        const TexNView tv = f.texn_view();
+        double acc = 0.0;
+        for (uint32_t q = 0; q < 4u * n; ++q)
+        {
+            const uint32_t inst = (uint32_t)(rnd() * 1.999f) % (uint32_t)sc.world.instances.size();
+            const uint32_t mi = sc.world.instances[inst].model;
+            const uint32_t tri = f.tri_base[mi] + (uint32_t)(rnd() * (float)sc.blas[mi].tris.size()) % (uint32_t)sc.blas[mi].tris.size();
+            const float u = rnd(), v = rnd() * (1.0f - u);
+            bool front;
+            const f3 nn = shading_normal(f.tri_shade.data(), f.instances.data(), f.materials.data(), tv, inst, tri, u, v, f3{rnd() - 0.5f, rnd() - 0.5f, rnd() - 0.5f}, front);
+            if (std::isfinite(nn.x) && std::isfinite(nn.y) && std::isfinite(nn.z)) acc += nn.x + 2.0 * nn.y + 3.0 * nn.z + (front ? 1.0 : 0.0);
+        }
+        // clearing takes the tangents out again
+        if (sc.set_material_normal_texture(mat, -1) != 0 || sc.build(&err) != 0 || !sc.flat.tri_tan.empty() || sc.flat.has_textures) return 7;
+        std::printf("{\"triangles\": %u, \"with_tangent\": %u, \"checksum\": %.6f}\n", n, with_tangent, acc);
         return 0;
     }
     if (cmd == "plan")

@@ -136,7 +136,8 @@ struct pt_ctx
     size_t spill_region_words = 0; // 8-byte words per traversal launch's spill area (d_spill holds two per pipeline)
     DevBuf d_blob, d_tri_shade, d_tri_pos, d_tri_orig, d_materials, d_lights, d_env;
     DevBuf d_tri_uv, d_tex_table, d_tex_texels; // textured scenes only (FlatScene::has_textures)
-    TexView tex{};                 // over them; all null for an untextured scene
+    DevBuf d_tri_tan;              // scenes with a normal map only (FlatScene::has_normal_maps)
+    TexNView tex{};                // over them; all null for an untextured scene, tri_tan null without a normal map
     bool textured = false;
     std::vector<f4> h_env;
     uint32_t env_w = 0, env_h = 0;
@@ -445,13 +446,18 @@ int upload_scene(pt_ctx* c)
     if ((r = up(c->d_materials, f.materials.data(), f.materials.size() * sizeof(DMaterial)))) return r;
     if ((r = up(c->d_lights, f.lights.data(), f.lights.size() * sizeof(DLight)))) return r;
     c->textured = f.has_textures;
-    c->tex = TexView{};
+    c->tex = TexNView{};
     if (f.has_textures)
     {
         if ((r = up(c->d_tri_uv, f.tri_uv.data(), f.tri_uv.size() * sizeof(DTriUV)))) return r;
         if ((r = up(c->d_tex_table, f.tex_table.data(), f.tex_table.size() * sizeof(DTexture)))) return r;
         if ((r = up(c->d_tex_texels, f.tex_texels.data(), f.tex_texels.size() * sizeof(f4)))) return r;
-        c->tex = TexView{(const f4*)c->d_tex_texels.p, (const DTexture*)c->d_tex_table.p, (const DTriUV*)c->d_tri_uv.p};
+        c->tex = TexNView{TexView{(const f4*)c->d_tex_texels.p, (const DTexture*)c->d_tex_table.p, (const DTriUV*)c->d_tri_uv.p}, nullptr};
+        if (f.has_normal_maps)
+        {
+            if ((r = up(c->d_tri_tan, f.tri_tan.data(), f.tri_tan.size() * sizeof(f4)))) return r;
+            c->tex.tri_tan = (const f4*)c->d_tri_tan.p;
+        }
     }
     if ((r = derive_scene_view(c, f, blob_bytes))) return r;
     c->scene_uploaded = true;
@@ -476,6 +482,7 @@ TraceLaunch trace_launch(pt_ctx* c, int pipe = 0, bool side_stream = false)
     tl.block_threads = c->block_threads;
     tl.tex = c->textured ? &c->tex : nullptr;
     tl.emission_tex = c->textured && c->scene.flat.has_emission_textures;
+    tl.tri_tan = c->textured ? c->tex.tri_tan : nullptr;
     return tl;
 }
 
@@ -1720,6 +1727,15 @@ int pt_set_material_emission_texture(pt_ctx* c, int material, int texture)
     return PT_OK;
 }
 
+int pt_set_material_normal_texture(pt_ctx* c, int material, int texture)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (c->scene.set_material_normal_texture(material, texture) < 0) return fail(c, PT_ERR_ARG, "bad material or texture index, or an emissive material");
+    c->scene_uploaded = false;
+    return PT_OK;
+}
+
 int pt_set_model_uvs(pt_ctx* c, int model, const float* uv, uint32_t n_tris)
 {
     if (!c) return PT_ERR_ARG;
@@ -1793,6 +1809,67 @@ int pt_surface_colour(pt_ctx* c, int on_device, uint32_t n, const uint32_t* inst
     launch_surface_colour(c->stream, c->sv, c->tex, n, d_inst, d_tri, d_u, d_v, d_rgb);
     HIPCHK(c, hipGetLastError());
     return st.download(rgb, d_rgb, (size_t)n * 12);
+}
+
+int pt_shading_normal(pt_ctx* c, int on_device, uint32_t n, const uint32_t* instance, const uint32_t* prim, const float* u, const float* v, const float* dir_xyz,
+                      float* out_normal_xyz, uint8_t* out_front)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->scene.built) return fail(c, PT_ERR_STATE, "pt_build has not been called");
+    if (n == 0) return PT_OK;
+    if (!instance || !prim || !u || !v || !dir_xyz || !out_normal_xyz || !out_front) return fail(c, PT_ERR_ARG, "null pointer");
+    const FlatScene& f = c->scene.flat;
+    const HostTlas& world = c->scene.world;
+    // leaf-order triangle of every query: tri_orig inverted for the models asked about
+    std::vector<std::vector<uint32_t>> where(c->scene.blas.size());
+    std::vector<uint32_t> tri(n);
+    for (uint32_t i = 0; i < n; ++i)
+    {
+        if (instance[i] >= world.instances.size()) return fail(c, PT_ERR_ARG, "instance index");
+        const uint32_t mi = world.instances[instance[i]].model;
+        const HostBlas& bl = c->scene.blas[mi];
+        if (prim[i] >= bl.tris.size()) return fail(c, PT_ERR_ARG, "primitive index");
+        if (where[mi].empty())
+        {
+            where[mi].resize(bl.prim_ids.size());
+            for (size_t k = 0; k < bl.prim_ids.size(); ++k) where[mi][bl.prim_ids[k]] = f.tri_base[mi] + (uint32_t)k;
+        }
+        tri[i] = where[mi][prim[i]];
+    }
+    if (!on_device)
+    {
+        const TexNView tv = f.texn_view();
+        for (uint32_t i = 0; i < n; ++i)
+        {
+            bool front;
+            const f3 nn = shading_normal(f.tri_shade.data(), f.instances.data(), f.materials.data(), tv, instance[i], tri[i], u[i], v[i],
+                                         f3{dir_xyz[3 * (size_t)i], dir_xyz[3 * (size_t)i + 1], dir_xyz[3 * (size_t)i + 2]}, front);
+            out_normal_xyz[3 * (size_t)i] = nn.x; out_normal_xyz[3 * (size_t)i + 1] = nn.y; out_normal_xyz[3 * (size_t)i + 2] = nn.z;
+            out_front[i] = front ? 1 : 0;
+        }
+        return PT_OK;
+    }
+    int r;
+    if ((r = upload_scene(c))) return r;
+    Staging st(c);
+    const uint32_t* d_inst = (const uint32_t*)st.in(instance, (size_t)n * 4);
+    const uint32_t* d_tri = (const uint32_t*)st.in(tri.data(), (size_t)n * 4);
+    const float* d_u = (const float*)st.in(u, (size_t)n * 4);
+    const float* d_v = (const float*)st.in(v, (size_t)n * 4);
+    const float* d_dir = (const float*)st.in(dir_xyz, (size_t)n * 12);
+    float* d_out = (float*)st.out((size_t)n * 16);
+    if (st.err) return st.err;
+    launch_shading_normal(c->stream, c->sv, c->tex, n, d_inst, d_tri, d_u, d_v, d_dir, d_out);
+    HIPCHK(c, hipGetLastError());
+    std::vector<float> out4((size_t)n * 4);
+    if ((r = st.download(out4.data(), d_out, (size_t)n * 16))) return r;
+    for (uint32_t i = 0; i < n; ++i)
+    {
+        for (int k = 0; k < 3; ++k) out_normal_xyz[3 * (size_t)i + k] = out4[4 * (size_t)i + k];
+        out_front[i] = out4[4 * (size_t)i + 3] != 0.0f ? 1 : 0;
+    }
+    return PT_OK;
 }
 
 int pt_set_camera(pt_ctx* c, const float eye[3], const float target[3], float fov_y_deg, float aspect)

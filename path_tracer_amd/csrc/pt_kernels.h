@@ -19,6 +19,8 @@ struct TraceLaunch
     const TexView* tex;      // the built scene has a textured material: its texture view (the surface passes are the TEX variants), else null
     bool emission_tex;       // ... and some EMISSIVE material is among them (pt_set_material_emission_texture): a light hit's colour is looked up, so the
                              // terminal pass is its TEX variant and the world closest-hit launches leave light hits to it (CLOSEST_WORLD_EMTEX)
+    const f4* tri_tan;       // ... and some material has a normal map (pt_set_material_normal_texture): the per-triangle tangents (the surface passes are
+                             // the normal-map variants), else null
 };
 
 // dynamic LDS of a traversal workgroup: the staged BVH blob (LDS scenes) + the per-lane (node, t_enter) stacks
@@ -213,6 +215,10 @@ void launch_albedo_accumulate(hipStream_t s, const SceneView& sv, const TexView&
 // unit hook (pt_surface_colour): rgb[i] <- surface colour of world instance[i], leaf-order triangle tri[i] at barycentrics u[i], v[i]
 void launch_surface_colour(hipStream_t s, const SceneView& sv, const TexView& tex, uint32_t n, const uint32_t* instance, const uint32_t* tri, const float* u,
                            const float* v, float* rgb);
+// unit hook (pt_shading_normal): out4[i] <- shading_normal (pt_materials.h) of world instance[i], leaf-order triangle tri[i] at barycentrics u[i], v[i]
+// for the world direction dir[i] | front.  tex.tri_tan is null in a scene without a normal map (no material then asks for it)
+void launch_shading_normal(hipStream_t s, const SceneView& sv, const TexNView& tex, uint32_t n, const uint32_t* instance, const uint32_t* tri, const float* u,
+                           const float* v, const float* dir, float* out4);
 
 // unit hooks
 // pt_render_guides_followed / pt_accumulate_albedo_followed: hop `hop` of the guide chains.  `in`: the hook queue launch_trace_rays_closest just

@@ -2042,6 +2042,16 @@ __device__ __forceinline__ const TexView& shade_args_tex()
     asm volatile("" : "+s"(p));
     return ((const ShadeKArgsTex*)p)->tex;
 }
+// NMAP variants: the tangent pointer rides behind the texture view in the same way (TexNView begins with the TexView, at ShadeKArgsTex's offset)
+struct ShadeKArgsNmap : ShadeKArgs { TexNView tex; };
+static_assert(sizeof(ShadeKArgsNmap) == sizeof(ShadeKArgsTex) + sizeof(const f4*) && alignof(TexNView) == alignof(TexView), "the texture view sits where ShadeKArgsTex has it: shade_args_tex serves both");
+typedef const __attribute__((address_space(4))) ShadeKArgsNmap* ShadeKArgsNmapPtr;
+__device__ __forceinline__ const TexNView& shade_args_texn()
+{
+    ShadeKArgsNmapPtr p = (ShadeKArgsNmapPtr)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return ((const ShadeKArgsNmap*)p)->tex;
+}
 #define PT_SHADE_ARGS                                                                                                              \
     const ShadeKArgs& ka_ = shade_args();                                                                                          \
     [[maybe_unused]] const SceneView& sv = ka_.sv;                                                                                 \
@@ -2064,13 +2074,18 @@ __device__ __forceinline__ const TexView& shade_args_tex()
 // EMTEX (with TEX: some emissive material has an emission texture, pt_set_material_emission_texture): the emitted colour of a light is its
 // surface colour too, at the point the explicit estimate sampled and at the light hit of the resolve (resolve_nee<true>).  A parameter of its
 // own: the TEX variants of a scene whose lights are untextured stay the kernels they were.
+// NMAP (with TEX: some material has a normal map, pt_set_material_normal_texture): the shading normal of the hit is shading_normal
+// (pt_materials.h), the interpolated normal perturbed by the map's texel in the triangle's tangent frame; `front` stays the unperturbed normal's.
+// The lookup is a second chain of the same kind (instance -> material -> UVs / tangent / table -> four texels) and sits where hit_normal sits,
+// right behind the colour lookup.  A parameter of its own like EMTEX: every other variant stays the kernel it was.
 template <uint32_t QCLASS, bool VOLUMES, bool INLINE = false, bool IDENT = false, bool LIST = false, bool LENS = false, bool RAYS = false, bool TEX = false,
-          bool ONE_DRAW = false, bool EMTEX = false>
+          bool ONE_DRAW = false, bool EMTEX = false, bool NMAP = false>
 __global__ void __launch_bounds__(PT_SHADE_THREADS, INLINE ? PT_SHADE_WAVES_INLINE : shade_waves(QCLASS, VOLUMES))
-k_shade_surface(const std::conditional_t<TEX, ShadeKArgsTex, ShadeKArgs> kargs)
+k_shade_surface(const std::conditional_t<NMAP, ShadeKArgsNmap, std::conditional_t<TEX, ShadeKArgsTex, ShadeKArgs>> kargs)
 {
     static_assert(!(TEX && INLINE), "textured scenes queue their shadow rays");
     static_assert(TEX || !EMTEX, "an emission texture makes a textured scene");
+    static_assert(TEX || !NMAP, "a normal map makes a textured scene");
     extern __shared__ uint4 smem_dyn[];
     // Only what the loop header needs is taken from the argument here; each section of an iteration re-reads the launch description from
     // the kernel-argument segment (PT_SHADE_ARGS: scalar loads that hit the constant cache) instead of keeping ~130 words of it in ~100
@@ -2159,7 +2174,9 @@ k_shade_surface(const std::conditional_t<TEX, ShadeKArgsTex, ShadeKArgs> kargs)
             else if (QCLASS == Q_DIELECTRIC) mat.kind = MAT_DIELECTRIC;
             else mat.kind = mat.kind == MAT_GGX_DIELECTRIC ? (uint32_t)MAT_GGX_DIELECTRIC : (uint32_t)MAT_GGX_METAL;
             bool front;
-            const f3 normal = hit_normal(sv, inst, tri, hit.y, hit.z, rd, front);
+            f3 normal;
+            if constexpr (NMAP) normal = shading_normal(sv.tri_shade, sv.instances, sv.materials, shade_args_texn(), inst, tri, hit.y, hit.z, rd, front);
+            else normal = hit_normal(sv, inst, tri, hit.y, hit.z, rd, front);
             const f3 p = fma3(rd, bc3(hit.x), ro);                                     // r.at(hit_info.t)
             uint32_t s_local, k_pix;
             const PixelId px = RAYS   ? path_pixel_rays(io.list, pid, &s_local, &k_pix)
@@ -3121,6 +3138,20 @@ __global__ void __launch_bounds__(256) k_surface_colour(const SceneView sv, cons
     const f3 c = surface_colour_at(sv, tex, instance[i], tri[i], u[i], v[i]);
     rgb[3u * (size_t)i] = c.x; rgb[3u * (size_t)i + 1u] = c.y; rgb[3u * (size_t)i + 2u] = c.z;
 }
+// unit hook of shading_normal: out4 = world shading normal | front
+__global__ void __launch_bounds__(256) k_shading_normal(const SceneView sv, const TexNView tex, const uint32_t n, const uint32_t* __restrict__ instance,
+                                                        const uint32_t* __restrict__ tri, const float* __restrict__ u, const float* __restrict__ v,
+                                                        const float* __restrict__ dir, float* __restrict__ out4)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    bool front;
+    const f3 nn = shading_normal(sv.tri_shade, sv.instances, sv.materials, tex, instance[i], tri[i], u[i], v[i],
+                                 f3{dir[3u * (size_t)i], dir[3u * (size_t)i + 1u], dir[3u * (size_t)i + 2u]}, front);
+    float* o = out4 + 4u * (size_t)i;
+    o[0] = nn.x; o[1] = nn.y; o[2] = nn.z;
+    o[3] = front ? 1.0f : 0.0f;
+}
 
 } // namespace
 
@@ -3394,33 +3425,53 @@ void launch_shade(hipStream_t s, uint32_t qclass, const SceneView& sv, const Ren
         else PT_SURF_L(false, Q, V, __VA_ARGS__);                                                                                        \
     } while (0)
     // the TEX variants of the same classes (a textured scene queues its shadow rays: shade_traces_shadow)
-    // (E: EMTEX, the scene has an emission texture)
-#define PT_SURF_TEX_L(LENS, Q, V, E)                                                                                                    \
+    // (E: EMTEX, the scene has an emission texture; NM: NMAP, it has a normal map and KA is the argument with the tangents behind the texture view)
+#define PT_SURF_TEX_L(LENS, Q, V, E, NM, KA)                                                                                                    \
     do {                                                                                                                                 \
-        if (ray_keys) hipLaunchKernelGGL((k_shade_surface<Q, V, false, false, false, LENS, true, true, false, E>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), 0, s, kat); \
-        else if (list) hipLaunchKernelGGL((k_shade_surface<Q, V, false, false, true, LENS, false, true, false, E>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), 0, s, kat); \
-        else hipLaunchKernelGGL((k_shade_surface<Q, V, false, false, false, LENS, false, true, false, E>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), 0, s, kat); \
+        if (ray_keys) hipLaunchKernelGGL((k_shade_surface<Q, V, false, false, false, LENS, true, true, false, E, NM>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), 0, s, KA); \
+        else if (list) hipLaunchKernelGGL((k_shade_surface<Q, V, false, false, true, LENS, false, true, false, E, NM>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), 0, s, KA); \
+        else hipLaunchKernelGGL((k_shade_surface<Q, V, false, false, false, LENS, false, true, false, E, NM>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), 0, s, KA); \
     } while (0)
-#define PT_SURF_TEX_P(Q, V, E)                                                                                                         \
+#define PT_SURF_TEX_P(Q, V, E, NM, KA)                                                                                                         \
     do {                                                                                                                                 \
-        if (list) hipLaunchKernelGGL((k_shade_surface<Q, V, false, false, true, true, false, true, true, E>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), 0, s, kat); \
-        else hipLaunchKernelGGL((k_shade_surface<Q, V, false, false, false, true, false, true, true, E>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), 0, s, kat); \
+        if (list) hipLaunchKernelGGL((k_shade_surface<Q, V, false, false, true, true, false, true, true, E, NM>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), 0, s, KA); \
+        else hipLaunchKernelGGL((k_shade_surface<Q, V, false, false, false, true, false, true, true, E, NM>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), 0, s, KA); \
     } while (0)
-#define PT_SURF_TEX_E(Q, E)                                                                                                             \
+#define PT_SURF_TEX_E(Q, E, NM, KA)                                                                                                             \
     do {                                                                                                                                 \
-        if (proj0) { if (sv.has_volumes) PT_SURF_TEX_P(Q, true, E); else PT_SURF_TEX_P(Q, false, E); }                                  \
-        else if (lens0) { if (sv.has_volumes) PT_SURF_TEX_L(true, Q, true, E); else PT_SURF_TEX_L(true, Q, false, E); }                 \
-        else { if (sv.has_volumes) PT_SURF_TEX_L(false, Q, true, E); else PT_SURF_TEX_L(false, Q, false, E); }                          \
+        if (proj0) { if (sv.has_volumes) PT_SURF_TEX_P(Q, true, E, NM, KA); else PT_SURF_TEX_P(Q, false, E, NM, KA); }                  \
+        else if (lens0) { if (sv.has_volumes) PT_SURF_TEX_L(true, Q, true, E, NM, KA); else PT_SURF_TEX_L(true, Q, false, E, NM, KA); } \
+        else { if (sv.has_volumes) PT_SURF_TEX_L(false, Q, true, E, NM, KA); else PT_SURF_TEX_L(false, Q, false, E, NM, KA); }          \
     } while (0)
 #define PT_SURF_TEX(Q)                                                                                                                  \
     do {                                                                                                                                 \
-        if (tl->emission_tex) PT_SURF_TEX_E(Q, true);                                                                                    \
-        else PT_SURF_TEX_E(Q, false);                                                                                                    \
+        if (tl->emission_tex) PT_SURF_TEX_E(Q, true, false, kat);                                                                        \
+        else PT_SURF_TEX_E(Q, false, false, kat);                                                                                        \
+    } while (0)
+#define PT_SURF_NMAP(Q)                                                                                                                 \
+    do {                                                                                                                                 \
+        if (tl->emission_tex) PT_SURF_TEX_E(Q, true, true, kan);                                                                         \
+        else PT_SURF_TEX_E(Q, false, true, kan);                                                                                         \
     } while (0)
     if (tex && tl->emission_tex && qclass == Q_TERMINAL)
     {
         if (lens0) hipLaunchKernelGGL((k_shade_terminal<true, TexView>), dim3(grid_blocks), dim3(256), 0, s, sv, rp, io, b, *tex);
         else hipLaunchKernelGGL((k_shade_terminal<false, TexView>), dim3(grid_blocks), dim3(256), 0, s, sv, rp, io, b, *tex);
+        return;
+    }
+    if (tex && tl->tri_tan && qclass != Q_TERMINAL) // a scene with a normal map: the argument with the tangents, built for these launches alone
+    {
+        ShadeKArgsNmap kan{};
+        static_cast<ShadeKArgs&>(kan) = ka;
+        kan.tex = TexNView{*tex, tl->tri_tan};
+        switch (qclass)
+        {
+        case Q_LAMBERT: PT_SURF_NMAP(Q_LAMBERT); break;
+        case Q_SPECULAR: PT_SURF_NMAP(Q_SPECULAR); break;
+        case Q_DIELECTRIC: PT_SURF_NMAP(Q_DIELECTRIC); break;
+        case Q_GGX: PT_SURF_NMAP(Q_GGX); break;
+        default: break;
+        }
         return;
     }
     if (tex && qclass != Q_TERMINAL)
@@ -3436,6 +3487,7 @@ void launch_shade(hipStream_t s, uint32_t qclass, const SceneView& sv, const Ren
         return;
     }
 #undef PT_SURF_TEX
+#undef PT_SURF_NMAP
 #undef PT_SURF_TEX_E
 #undef PT_SURF_TEX_L
 #undef PT_SURF_TEX_P
@@ -3623,6 +3675,12 @@ void launch_surface_colour(hipStream_t s, const SceneView& sv, const TexView& te
 {
     if (n == 0u) return;
     hipLaunchKernelGGL(k_surface_colour, dim3((n + 255u) / 256u), dim3(256), 0, s, sv, tex, n, instance, tri, u, v, rgb);
+}
+void launch_shading_normal(hipStream_t s, const SceneView& sv, const TexNView& tex, uint32_t n, const uint32_t* instance, const uint32_t* tri, const float* u,
+                           const float* v, const float* dir, float* out4)
+{
+    if (n == 0u) return;
+    hipLaunchKernelGGL(k_shading_normal, dim3((n + 255u) / 256u), dim3(256), 0, s, sv, tex, n, instance, tri, u, v, dir, out4);
 }
 
 } // namespace pt

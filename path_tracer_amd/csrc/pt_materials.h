@@ -137,8 +137,10 @@ PT_HD f3 beer_lambert(f3 absorption, float dist)
 // Equirect lookup of the environment on a miss  integrator.rs:256-262, image_helper.rs:61-88
 struct EnvView { const f4* data; uint32_t w, h, pad0, pad1; };
 PT_HD uint32_t sat_u32(float f) { return !(f > 0.0f) ? 0u : (f >= 4294967296.0f ? 0xffffffffu : (uint32_t)f); } // Rust `as u32`
-// get_pixel_bilinear(u, v) of a w x h image (image_helper.rs:61-88): the one lookup the environment and the textures share
-PT_HD f3 bilinear_rgb(const f4* data, uint32_t w, uint32_t h, float u, float v)
+// get_pixel_bilinear(u, v) of a w x h image (image_helper.rs:61-88): the one lookup the environment and the textures share.  Its two halves:
+// the four texels with the fractions, and their blend
+struct BilinearTap { f3 a, b, c, e; float xf, yf; };
+PT_HD BilinearTap bilinear_fetch(const f4* data, uint32_t w, uint32_t h, float u, float v)
 {
     float x = (float)w * u, y = (float)h * v;
     uint32_t x0 = sat_u32(x), y0 = sat_u32(y);
@@ -146,9 +148,13 @@ PT_HD f3 bilinear_rgb(const f4* data, uint32_t w, uint32_t h, float u, float v)
     const uint32_t xa = x0 % w, xb = (x0 + 1u) % w, ya = y0 % h, yb = (y0 + 1u) % h;
     const f4 c00 = data[(size_t)ya * w + xa], c01 = data[(size_t)yb * w + xa];
     const f4 c10 = data[(size_t)ya * w + xb], c11 = data[(size_t)yb * w + xb];
-    const f3 a{c00.x, c00.y, c00.z}, b{c01.x, c01.y, c01.z}, c{c10.x, c10.y, c10.z}, e{c11.x, c11.y, c11.z};
-    return (((1.0f - xf) * (1.0f - yf)) * a + ((1.0f - xf) * yf) * b + (xf * (1.0f - yf)) * c) + (xf * yf) * e;
+    return BilinearTap{f3{c00.x, c00.y, c00.z}, f3{c01.x, c01.y, c01.z}, f3{c10.x, c10.y, c10.z}, f3{c11.x, c11.y, c11.z}, xf, yf};
 }
+PT_HD f3 bilinear_blend(const BilinearTap& t)
+{
+    return (((1.0f - t.xf) * (1.0f - t.yf)) * t.a + ((1.0f - t.xf) * t.yf) * t.b + (t.xf * (1.0f - t.yf)) * t.c) + (t.xf * t.yf) * t.e;
+}
+PT_HD f3 bilinear_rgb(const f4* data, uint32_t w, uint32_t h, float u, float v) { return bilinear_blend(bilinear_fetch(data, w, h, u, v)); }
 PT_HD f3 env_lookup(const EnvView& env, f3 d)
 {
     float u = fma_rs(atan2_det(d.x, d.z), PT_FRAC_1_PI * 0.5f, 0.5f);
@@ -169,6 +175,61 @@ PT_HD f3 surface_colour(const TexView& tv, uint32_t texture, f3 colour, uint32_t
     s = s - floorf(s);
     w = w - floorf(w);
     return colour * bilinear_rgb(tv.texels + t.offset, t.w, t.h, s, w);
+}
+
+// The normal map's lookup: bilinear_rgb, except that four EQUAL texels (rgb) are that texel, with no arithmetic.  The four bilinear weights do
+// not always sum to exactly 1 in binary32, so a constant region of a map would otherwise come back an ulp off at some UVs, and a flat map
+// would not be the plain normal bit for bit there.
+PT_HD f3 bilinear_rgb_const(const f4* data, uint32_t w, uint32_t h, float u, float v)
+{
+    const BilinearTap t = bilinear_fetch(data, w, h, u, v);
+    const f3 a = t.a, b = t.b, c = t.c, e = t.e;
+    if (a.x == b.x && a.x == c.x && a.x == e.x && a.y == b.y && a.y == c.y && a.y == e.y && a.z == b.z && a.z == c.z && a.z == e.z) return a;
+    return bilinear_blend(t);
+}
+
+// Normal maps (pt_set_material_normal_texture; the definition is include/pt_api.h's).  n: the object-space unit3(interpolated vertex normals)
+// of the hit, before face-forwarding; `normal_texture` = DMaterial::normal_texture (index + 1); tri: leaf order.  Returns the object-space
+// N': n itself, bit for bit, without a normal texture, at a flat texel (x == 0 and y == 0) and on a triangle without a tangent (T == 0).
+// Every operation rounded once, in the order written.
+PT_HD f3 perturbed_normal(const TexNView& tv, uint32_t normal_texture, f3 n, uint32_t tri, float u, float v)
+{
+    if (normal_texture == 0u) return n;
+    const DTriUV uv = tv.tri_uv[tri];
+    const DTexture t = tv.table[normal_texture - 1u];
+    float s = (uv.a[0] + u * (uv.b[0] - uv.a[0])) + v * (uv.c[0] - uv.a[0]);   // surface_colour's s, t
+    float w = (uv.a[1] + u * (uv.b[1] - uv.a[1])) + v * (uv.c[1] - uv.a[1]);
+    s = s - floorf(s);
+    w = w - floorf(w);
+    const f3 c = bilinear_rgb_const(tv.texels + t.offset, t.w, t.h, s, w);
+    const float x = 2.0f * c.x - 1.0f, y = 2.0f * c.y - 1.0f, z = 2.0f * c.z - 1.0f;
+    if (x == 0.0f && y == 0.0f) return n;
+    const f4 tan = tv.tri_tan[tri];
+    const f3 tg{tan.x, tan.y, tan.z};
+    if (tg.x == 0.0f && tg.y == 0.0f && tg.z == 0.0f) return n;                // degenerate UVs, or a model without UVs
+    const f3 tp = unit3(tg - n * dot3(n, tg));                                 // Gram-Schmidt at the hit
+    const f3 bp = cross3(n, tp) * tan.w;                                       // tan.w = +1 / -1, handedness of (T, B, geometric normal)
+    return unit3((tp * x + bp * y) + n * z);
+}
+// The shading normal of a hit in world space: hit_normal (pt_kernels.hip: Triangle::get_normal, face-forward in object space, the deferred
+// instance transform) with N' = perturbed_normal in place of N.  `front` is the flag of the UNPERTURBED N; a back-face hit flips N'.  Shared by
+// the normal-map variants of the surface passes, the unit hook's kernel and the hook's host evaluation.
+PT_HD f3 shading_normal(const DTriVerts* tri_shade, const DInstance* instances, const DMaterial* materials, const TexNView& tv, uint32_t inst,
+                        uint32_t tri, float u, float v, f3 dir_world, bool& front)
+{
+    const DTriVerts tv3 = tri_shade[tri];
+    const float wgt = 1.0f - u - v;
+    const m33 nm{f3{tv3.a.x, tv3.a.y, tv3.a.z}, f3{tv3.b.x, tv3.b.y, tv3.b.z}, f3{tv3.c.x, tv3.c.y, tv3.c.z}};
+    const f3 n = unit3(mul(nm, f3{wgt, u, v}));
+    const DInstance& in = instances[inst];
+    const f3 d_obj{(in.inv[0] * dir_world.x + in.inv[1] * dir_world.y) + in.inv[2] * dir_world.z,
+                   (in.inv[4] * dir_world.x + in.inv[5] * dir_world.y) + in.inv[6] * dir_world.z,
+                   (in.inv[8] * dir_world.x + in.inv[9] * dir_world.y) + in.inv[10] * dir_world.z};
+    front = dot3(d_obj, n) < 0.0f;
+    f3 m = perturbed_normal(tv, materials[in.material].normal_texture, n, tri, u, v);
+    if (!front) m = -m;
+    return f3{(in.fwd[0] * m.x + in.fwd[1] * m.y) + in.fwd[2] * m.z, (in.fwd[4] * m.x + in.fwd[5] * m.y) + in.fwd[6] * m.z,
+              (in.fwd[8] * m.x + in.fwd[9] * m.y) + in.fwd[10] * m.z};
 }
 
 // MaterialTrait::scatter_direction

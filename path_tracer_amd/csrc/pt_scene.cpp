@@ -454,6 +454,31 @@ int HostScene::set_material_emission_texture(int material, int texture)
     return 0;
 }
 
+int HostScene::set_material_normal_texture(int material, int texture)
+{
+    if (material < 0 || material >= (int)materials.size() || texture < -1 || texture >= (int)textures.size()) return -1;
+    if (materials[material].kind == MAT_EMISSIVE) return -1; // lights have no map (and `texture` of an emissive material is its emission)
+    materials[material].normal_texture = (uint32_t)(texture + 1);
+    built = false;
+    ++layout_epoch; // the tangent array comes or goes with the first / last reference: the next upload is a full one
+    return 0;
+}
+
+// The tangent of one triangle for its normal map (pt_api.h, TANGENTS): object-space positions p0 p1 p2, UVs a b c (s, t pairs) in load order;
+// T.xyz | sign.  Every operation one binary32 operation, in the header's order
+static f4 triangle_tangent(const f3 p[3], const float* uv)
+{
+    const f3 e1 = p[1] - p[0], e2 = p[2] - p[0];
+    const float d1s = uv[2] - uv[0], d1t = uv[3] - uv[1], d2s = uv[4] - uv[0], d2t = uv[5] - uv[1];
+    const float det = d1s * d2t - d2s * d1t;
+    if (det == 0.0f) return f4{0.0f, 0.0f, 0.0f, 1.0f};
+    const f3 t = (e1 * d2t - e2 * d1t) / det;
+    const f3 b = (e2 * d1s - e1 * d2s) / det;
+    if (!finite_f(t.x) || !finite_f(t.y) || !finite_f(t.z)) return f4{0.0f, 0.0f, 0.0f, 1.0f};
+    const float sign = dot3(cross3(e1, e2), cross3(t, b)) < 0.0f ? -1.0f : 1.0f;
+    return f4{t.x, t.y, t.z, sign};
+}
+
 int HostScene::set_model_uvs(int model, const float* uv, uint32_t n_tris)
 {
     if (model < 0 || model >= (int)models.size()) return -1;
@@ -777,6 +802,8 @@ int HostScene::flatten(std::string* err)
     for (const DMaterial& m : materials) f.has_volumes = f.has_volumes || m.has_volume != 0;
     for (const DMaterial& m : materials) f.has_textures = f.has_textures || m.texture != 0;
     for (const DMaterial& m : materials) f.has_emission_textures = f.has_emission_textures || (m.texture != 0 && m.kind == MAT_EMISSIVE);
+    for (const DMaterial& m : materials) f.has_normal_maps = f.has_normal_maps || m.normal_texture != 0;
+    f.has_textures = f.has_textures || f.has_normal_maps; // (a normal map is looked up like a colour texture: UVs, table and texels)
     // One volume per model.  The reference keys its volume stack by the address of the material (volume.rs:146-162), and every BLAS
     // owns a copy of its model's material (blas.rs:167,197): two models of equal materials are two volumes, all instances of one model
     // are one.  The device keys the stack by material index, so the first model of a volume-bearing material keeps the index and
@@ -827,6 +854,7 @@ int HostScene::flatten(std::string* err)
         f.tri_uv = std::move(flat.tri_uv);        // (textures, texture references and UVs move the epoch: these are current too)
         f.tex_table = std::move(flat.tex_table);
         f.tex_texels = std::move(flat.tex_texels);
+        f.tri_tan = std::move(flat.tri_tan);
         f.nodes = std::move(flat.nodes);
         f.big_leaves = std::move(flat.big_leaves);
         f.tri_isect = std::move(flat.tri_isect);
@@ -977,6 +1005,13 @@ int HostScene::flatten(std::string* err)
                     const float* p = &uv[(size_t)bl.prim_ids[k] * 6];
                     f.tri_uv[at + k] = DTriUV{{p[0], p[1]}, {p[2], p[3]}, {p[4], p[5]}};
                 }
+        }
+        if (f.has_normal_maps)
+        {
+            const std::vector<float>& uv = models[i].uvs;
+            f.tri_tan.resize(at + bl.prim_ids.size(), f4{0.0f, 0.0f, 0.0f, 1.0f});   // a model without UVs: no tangent, its hits keep N
+            if (!uv.empty())
+                for (size_t k = 0; k < bl.prim_ids.size(); ++k) f.tri_tan[at + k] = triangle_tangent(bl.tris[bl.prim_ids[k]].p, &uv[(size_t)bl.prim_ids[k] * 6]);
         }
     }
     auto put_instances = [&](const HostTlas& t, uint32_t ident_bit) {

@@ -91,6 +91,7 @@ struct FlatScene
     std::vector<DTriUV> tri_uv;         // leaf order like tri_shade; empty unless some material references a texture (has_textures)
     std::vector<DTexture> tex_table;    // ... and so are the texture table and the texels (every texture, in pt_add_texture order)
     std::vector<f4> tex_texels;
+    std::vector<f4> tri_tan;            // per-triangle tangent.xyz | handedness, leaf order like tri_uv; empty unless some material references a normal map (has_normal_maps)
     std::vector<DInstance> instances;
     std::vector<uint32_t> big_leaves;   // {first, count} pairs of the leaves NODE_TRIS cannot encode
     std::vector<DMaterial> materials;
@@ -105,13 +106,15 @@ struct FlatScene
     bool has_volumes = false;
     bool has_textures = false;          // some material references a texture, as its surface colour or as its emission: the shading passes are the TEX variants
     bool has_emission_textures = false; // ... and some EMISSIVE material does (pt_set_material_emission_texture)
+    bool has_normal_maps = false;       // some material references a normal texture (pt_set_material_normal_texture): has_textures too, and tri_tan is written
     TexView tex_view() const { return TexView{tex_texels.data(), tex_table.data(), tri_uv.data()}; } // over the host copies
+    TexNView texn_view() const { return TexNView{tex_view(), tri_tan.data()}; }
     // bytes of every table an upload copies (pt_scene_info::scene_bytes)
     size_t table_bytes() const
     {
         return nodes.size() * sizeof(DNode) + tri_isect.size() * sizeof(DTriIsect) + instances.size() * sizeof(DInstance) + (big_leaves.size() * 4 + 15) / 16 * 16 +
                (tri_shade.size() + tri_pos.size()) * sizeof(DTriVerts) + tri_orig.size() * 4 + materials.size() * sizeof(DMaterial) + lights.size() * sizeof(DLight) +
-               tri_uv.size() * sizeof(DTriUV) + tex_table.size() * sizeof(DTexture) + tex_texels.size() * sizeof(f4);
+               tri_uv.size() * sizeof(DTriUV) + tex_table.size() * sizeof(DTexture) + tex_texels.size() * sizeof(f4) + tri_tan.size() * sizeof(f4);
     }
 };
 
@@ -153,6 +156,7 @@ public:
     int add_texture(uint32_t w, uint32_t h, const float* rgb);
     int set_material_texture(int material, int texture);             // -1 clears
     int set_material_emission_texture(int material, int texture);    // -1 clears; EMISSIVE materials only (the light sampler is rebuilt)
+    int set_material_normal_texture(int material, int texture);      // -1 clears; any kind but EMISSIVE
     int set_model_uvs(int model, const float* uv, uint32_t n_tris);  // nullptr, 0 clears
     int build(std::string* err);
     void set_camera(const float eye[3], const float target[3], float fov_deg, float aspect);

@@ -10,6 +10,7 @@
 //   instances  : 144 B inverse 3x4 | blas root, blas id, material, class | copy of the BLAS root node | forward 3x4
 //   materials  : 64 B
 //   tri_uv     : 24 B  three UVs, BLAS-leaf order (textured scenes only) | tex_table : 16 B {offset, w, h} | tex_texels : 16 B rgb | -
+//   tri_tan    : 16 B  tangent.xyz | handedness, BLAS-leaf order (scenes with a normal map only)
 //   lights     : 16 B  { triangle, material, pdf, cdf }
 // Traversal touches nodes + tri_isect + instances only ("scene blob"); when that fits it is staged in LDS.
 #pragma once
@@ -80,7 +81,8 @@ struct alignas(16) DMaterial
     float vol_c;
     float vol_g;
     uint32_t texture;   // index + 1 into the texture table (TexView), 0 = none: the surface colour is `colour` itself
-    float pad[2];
+    uint32_t normal_texture; // index + 1 of the normal map (pt_set_material_normal_texture), 0 = none: the shading normal is the interpolated one
+    float pad;
 };
 static_assert(sizeof(DMaterial) == 64, "");
 
@@ -102,6 +104,13 @@ struct TexView
     const f4* texels;
     const DTexture* table;
     const DTriUV* tri_uv;
+};
+// ... and what a normal-map lookup (shading_normal, pt_materials.h) reads: the per-triangle tangents {T.xyz, sign} in BLAS leaf order like tri_uv.
+// A view of its own on top of TexView, handed only to the normal-map variants of the surface passes and to the unit hook's kernel: the kernels
+// that take a TexView between other arguments keep their argument layout.  tri_tan is null in a scene without a normal map.
+struct TexNView : TexView
+{
+    const f4* tri_tan;
 };
 
 // the barycentrics (u = v) of the light sampler's one-point quadrature (pt_api.h, LIGHT WEIGHT): a light triangle's weight is its area times

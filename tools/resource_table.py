@@ -4,6 +4,8 @@ waves per SIMD / scratch bytes per lane / VGPRs (spilled VGPRs), and per kernel 
 packed fp32 operations and scratch accesses.  The flags are csrc/Makefile's FLAGS plus what is given.
 
     python tools/resource_table.py [--src pt_kernels.hip] [--a=<flags>] [--b=<flags>] [--only-changed] [--keep DIR] [--csrc-a DIR]
+    python tools/resource_table.py --twins [--only NAME] [--b=<flags>]   ONE build (--only: kernels whose name contains NAME): every kernel whose LAST template argument is `true` beside its twin, the same
+                                                              instantiation with that argument `false` (a variant a template gained beside the kernel it had)
 
 The default, --a=-fslp-vectorize --b= , compares the SLP vectoriser's pairing with the build's flags (profiles/r08_fp32_pairing.md);
 --csrc-a takes the left column's sources (not its flags) from another checkout's path_tracer_amd/csrc."""
@@ -85,9 +87,34 @@ def main():
     ap.add_argument("--only-changed", action="store_true")
     ap.add_argument("--csrc-a", default=CSRC, help="source directory of the left column (another checkout's path_tracer_amd/csrc)")
     ap.add_argument("--keep", default=None, help="directory that keeps the two assembly files")
+    ap.add_argument("--twins", action="store_true", help="one build (--b): kernels whose last template argument is true beside their twins with it false")
+    ap.add_argument("--only", default="", help="with --twins: only kernels whose demangled name contains this")
     args = ap.parse_args()
     keep = args.keep or tempfile.mkdtemp(prefix="resource_table_")
     os.makedirs(keep, exist_ok=True)
+    if args.twins:
+        rb, cb = compile_one(args.src, (args.b, 1), keep)
+        names = demangle(list(rb))
+        by_short = {names[n]: n for n in rb}
+        print(f"`{args.src}`: waves per SIMD / scratch B per lane / VGPRs of the twin (last template argument false) and of the variant (true); static VALU, scratch accesses\n")
+        print("| variant | twin | variant | VALU | scratch ops |\n|---|---|---|---|---|")
+        n_pairs = fewer_waves = more_scratch = 0
+        for n in rb:
+            if not names[n].endswith(", true>") or args.only not in names[n]:
+                continue
+            t = by_short.get(names[n][:-len("true>")] + "false>")
+            if t is None:
+                continue
+            a, b = rb[t], rb[n]
+            n_pairs += 1
+            worse = []
+            if int(b["Occupancy [waves/SIMD]"]) < int(a["Occupancy [waves/SIMD]"]):
+                fewer_waves += 1; worse.append("fewer waves")
+            if int(b["ScratchSize [bytes/lane]"]) > int(a["ScratchSize [bytes/lane]"]):
+                more_scratch += 1; worse.append("more scratch")
+            print(f"| `{names[n]}`{' **' + ', '.join(worse) + '**' if worse else ''} | {cell(a)} | {cell(b)} | {cb[t]['valu']} -> {cb[n]['valu']} | {cb[t]['scratch']} -> {cb[n]['scratch']} |")
+        print(f"\n{n_pairs} variants with a twin; fewer waves per SIMD: {fewer_waves}; more scratch: {more_scratch}")
+        return
     with concurrent.futures.ThreadPoolExecutor(2) as ex:
         fa, fb = ex.submit(compile_one, args.src, (args.a, 0), keep, os.path.abspath(args.csrc_a)), ex.submit(compile_one, args.src, (args.b, 1), keep)
         (ra, ca), (rb, cb) = fa.result(), fb.result()

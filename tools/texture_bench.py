@@ -7,6 +7,8 @@ TEX shading variants (and of queueing the shadow rays the untextured frame walks
     python tools/texture_bench.py --only tex1024 --reps 1      one variant alone, e.g. under rocprofv3 --kernel-trace --stats
     python tools/texture_bench.py --emission --reps 5          adds `emit8`: the untextured frame with its LIGHT on an 8 x 8 checker emission texture
                                                                (profiles/r17_emission_textures.md): emit8_over_plain beside tex8_over_plain
+    python tools/texture_bench.py --normal --reps 5            adds `nmap8`: the frame with its floor, ceiling and walls under an 8 x 8 ripple NORMAL map instead
+                                                               of the checker, same UVs (profiles/r18_normal_maps.md): nmap8_over_plain, nmap8_over_tex8
 """
 import argparse
 import json
@@ -43,6 +45,28 @@ def textured_cornell(scenes, W, H, n, repeat):
     return SceneDesc.new(models, scenes.reference_camera(W / H), f"cornell checker {n}")
 
 
+def ripples(n):
+    """the n x n ripple normal map of examples/headless --normal-ripples: tangent-space (0.3 tri(i), 0.3 tri(j), z) encoded 0.5 * v + 0.5"""
+    f = np.float32
+    a = (np.arange(n, dtype=f) + f(0.5)) / f(n)
+    tri = f(0.3) * (f(4.0) * np.abs(a - f(0.5)) - f(1.0))
+    x, y = np.meshgrid(tri, tri)
+    z = np.sqrt((f(1.0) - x * x) - y * y)
+    return f(0.5) * np.stack([x, y, z], axis=2).astype(f) + f(0.5)
+
+
+def rippled_cornell(scenes, W, H, n, repeat):
+    """textured_cornell's models and UVs under an n x n ripple normal map instead of the checker"""
+    from path_tracer_amd.scene_desc import Model, SceneDesc, Texture
+    tex = Texture.new(ripples(n))
+    models = []
+    for m in scenes.cornell_models():
+        if m.name in ("cb_main", "cb_left", "cb_right"):
+            m = Model.new(m.positions, m.normals, m.material.normal_mapped(tex), m.matrices, m.name, uvs=planar_uvs(m.positions, repeat))
+        models.append(m)
+    return SceneDesc.new(models, scenes.reference_camera(W / H), f"cornell ripples {n}")
+
+
 def emission_cornell(scenes, W, H, n):
     """the Cornell frame with an n x n checker as the emission texture of its light, UVs planar over the light's extent"""
     from path_tracer_amd.scene_desc import Model, SceneDesc, Texture
@@ -63,7 +87,8 @@ def main():
     ap.add_argument("--bounces", type=int, default=8)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--repeat", type=float, default=8.0)
-    ap.add_argument("--only", choices=["plain", "tex8", "tex1024", "emit8"])
+    ap.add_argument("--only", choices=["plain", "tex8", "tex1024", "emit8", "nmap8"])
+    ap.add_argument("--normal", action="store_true", help="also measure nmap8: the walls under an 8 x 8 ripple normal map")
     ap.add_argument("--emission", action="store_true", help="also measure emit8: the light on an 8 x 8 checker emission texture")
     ap.add_argument("--out")
     a = ap.parse_args()
@@ -73,6 +98,8 @@ def main():
                 "tex1024": lambda: textured_cornell(scenes, W, H, 1024, a.repeat)}
     if a.emission or a.only == "emit8":
         variants["emit8"] = lambda: emission_cornell(scenes, W, H, 8)
+    if a.normal or a.only == "nmap8":
+        variants["nmap8"] = lambda: rippled_cornell(scenes, W, H, 8, a.repeat)
     if a.only:
         variants = {a.only: variants[a.only]}
     rs = {}
@@ -100,6 +127,8 @@ def main():
         for name in rs:
             if name != "plain":
                 res[name + "_over_plain"] = res["variants"][name]["ms_per_frame"] / res["variants"]["plain"]["ms_per_frame"]
+    if "nmap8" in rs and "tex8" in rs and a.reps:
+        res["nmap8_over_tex8"] = res["variants"]["nmap8"]["ms_per_frame"] / res["variants"]["tex8"]["ms_per_frame"]
     print(json.dumps(res), flush=True)
     if a.out:
         with open(a.out, "w") as f:
