@@ -32,7 +32,7 @@ using namespace pt;
 #define PT_JOIN_LATE 0 // same-box A/B: joining the side stream only before the shading pass costs +2 ms per frame (the two traversal kernels fight for wave slots), 0.1 ms less for a 1/8 share
 #endif
 #ifndef PT_INTERLEAVE_FIRST
-#define PT_INTERLEAVE_FIRST 1 // the first batches of the pipelines are enqueued bounce by bounce across the pipelines (render_batches)
+#define PT_INTERLEAVE_FIRST 1 // the first batches of the pipelines are enqueued bounce by bounce across the pipelines (run_batches)
 #endif
 #ifndef PT_WAVE_TIMES
 #define PT_WAVE_TIMES 0
@@ -1170,41 +1170,75 @@ int download_frame(pt_ctx* c, float* data, float* position, uint32_t* id)
     return PT_OK;
 }
 
-int render_batches(pt_ctx* c, uint32_t first_sample, uint32_t n_samples, float* samples_out)
+// the most paths one batch may hold: what the device has free and the pipelines' pools already hold, for the scene's surface classes
+size_t path_budget(const pt_ctx* c)
+{
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return (size_t)96 << 20;
+    size_t held = 0;
+    for (const pt_ctx::Pipe& pp : c->pipe)
+        for (const DevBuf& b : pp.pool) held += b.bytes;
+    uint32_t n_classes = 0;
+    for (uint32_t k = 1; k < Q_COUNT; ++k) n_classes += c->class_present[k] ? 1u : 0u;
+    return max_paths_for(free_b, held, n_classes, c->sv.has_volumes != 0);
+}
+
+// launches of a failed batch (and of batches pipelined behind it) may still be running on the pipelines' streams: wait for everything
+void drain_pipelines(pt_ctx* c)
+{
+    for (int i = 0; i < pt_ctx::kMaxPipes; ++i)
+    {
+        (void)hipStreamSynchronize(c->pipe_stream(i));
+        if (c->pipe[i].side_stream) (void)hipStreamSynchronize(c->pipe[i].side_stream);
+        c->pipe[i].busy = false;
+        c->pipe[i].ev_used = 0; // (batches that were never harvested: their timers are void as well)
+    }
+    (void)hipGetLastError();
+}
+
+// What run_batches is asked for: n_samples samples of each of act_pixels pixels (a ray list: one "pixel", a ray per "sample"), cut into
+// wavefront batches by plan_batches.
+struct BatchRequest
+{
+    uint32_t n_samples = 0;
+    size_t act_pixels = 1;
+    uint32_t batch_spp = 0;    // the caller's cut (0: none)
+    bool samples_out = false;  // the samples come back per batch instead of being accumulated
+    bool release_idle = false; // pipelines the plan leaves idle give their pools back
+    bool stream_after = false; // the context's stream is put behind the last batch's accumulation
+    const char* what = "";     // the request's name in the PTMI_DEBUG_BATCH line
+};
+
+// The batches of one request over the pipelines: planned in one place (plan_batches, within path_budget), their pools made, then launched
+// and harvested.  What differs between a render and a ray list is the caller's, stats.ms_total included (add_ms_total: a render's clock
+// starts when its pools stand, a ray call's covers planning and every segment):
+//   int planned(batch, n_pipes)        the plan is known and the pools stand: whatever else the batches need (nothing is in flight)
+//   BatchSpec spec(pipe, done, cnt)    samples [done, done + cnt) of the request as a batch of pipeline `pipe`, which is idle
+//   int group_done(first)              a group has been enqueued (first: its first batch)
+//   void failed()                      a batch failed and the pipelines have been drained
+template <class Caller>
+int run_batches(pt_ctx* c, const BatchRequest& rq, Caller& call)
 {
     int r;
-    if ((r = precheck(c))) return r;
-    if (n_samples == 0 || c->local_pixels == 0) return PT_OK;
-    if ((r = upload_scene(c)) || (r = ensure_frame(c)) || (r = ensure_environment(c))) return r;
     PlanRequest q;
-    q.n_samples = n_samples;
-    q.samples_out = samples_out != nullptr;
+    q.n_samples = rq.n_samples;
+    q.samples_out = rq.samples_out;
     q.pipelines = c->cfg.pipelines;
-    q.batch_spp = c->cfg.batch_spp;
+    q.batch_spp = rq.batch_spp;
     q.lds_scene = c->lds_scene;
-    q.max_paths = (size_t)96 << 20;
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
-    {
-        size_t held = 0;
-        for (const pt_ctx::Pipe& pp : c->pipe)
-            for (const DevBuf& b : pp.pool) held += b.bytes;
-        uint32_t n_classes = 0;
-        for (uint32_t k = 1; k < Q_COUNT; ++k) n_classes += c->class_present[k] ? 1u : 0u;
-        q.max_paths = max_paths_for(free_b, held, n_classes, c->sv.has_volumes != 0);
-    }
-    const ActiveRect ar = render_rect(c);
-    q.act_pixels = std::max<size_t>((size_t)ar.w * ar.rows, 1);
+    q.max_paths = path_budget(c);
+    q.act_pixels = rq.act_pixels;
     for (int i = 0; i < pt_ctx::kMaxPipes; ++i) q.cap_paths[i] = c->pipe[i].cap_paths;
     const BatchPlan plan = plan_batches(q);
     if (!plan.batch) return fail(c, PT_ERR_ARG, "batch too large (path ids are 29-bit)");
-    const uint32_t batch = plan.batch, n_pipes = plan.n_pipes;
-    // pipelines this call does not use give their memory back
-    for (int i = (int)n_pipes; i < pt_ctx::kMaxPipes; ++i)
-        if (!c->pipe[i].busy && c->pipe[i].cap_paths) free_pipe_pool(c->pipe[i]);
+    const uint32_t batch = plan.batch, n_pipes = plan.n_pipes, n_samples = rq.n_samples;
+    // pipelines the request does not use give their memory back
+    if (rq.release_idle)
+        for (int i = (int)n_pipes; i < pt_ctx::kMaxPipes; ++i)
+            if (!c->pipe[i].busy && c->pipe[i].cap_paths) free_pipe_pool(c->pipe[i]);
     if (std::getenv("PTMI_DEBUG_BATCH"))
-        std::fprintf(stderr, "[ptmi] render %u spp: max_paths %zu act_pixels %zu batch %u x %u on %u pipelines; pools before: %zu %zu paths\n", n_samples, q.max_paths, q.act_pixels, batch,
-                     plan.n_batches, n_pipes, c->pipe[0].cap_paths, c->pipe[1].cap_paths);
+        std::fprintf(stderr, "[ptmi] %s %u spp: max_paths %zu act_pixels %zu batch %u x %u on %u pipelines; pools before: %zu %zu paths\n", rq.what, n_samples,
+                     q.max_paths, q.act_pixels, batch, plan.n_batches, n_pipes, c->pipe[0].cap_paths, c->pipe[1].cap_paths);
     // ... and a pipeline that kept a larger pool from an earlier request (a whole frame resident on pipeline 0, say) gives it back when
     // the pipelines have to share the budget: its old pool plus the others' new ones could exceed what max_paths was computed from
     const size_t need_paths = (size_t)batch * q.act_pixels;
@@ -1213,10 +1247,7 @@ int render_batches(pt_ctx* c, uint32_t first_sample, uint32_t n_samples, float* 
             if (!c->pipe[i].busy && c->pipe[i].cap_paths > need_paths + need_paths / 4) free_pipe_pool(c->pipe[i]);
     for (uint32_t i = 0; i < n_pipes; ++i)
         if ((r = ensure_wavefront(c, (int)i, need_paths, c->cfg.max_bounces + 2))) return r;
-    Staging st(c);
-    f4* d_samples = samples_out ? (f4*)st.out((size_t)batch * c->local_pixels * 16) : nullptr;
-    if (st.err) return st.err;
-    const auto t0 = std::chrono::steady_clock::now();
+    if ((r = call.planned(batch, n_pipes))) return r;
     // the other pipelines start after whatever the caller queued on pipeline 0's stream (accumulation resets, uploads)
     if (n_pipes > 1)
     {
@@ -1240,12 +1271,11 @@ int render_batches(pt_ctx* c, uint32_t first_sample, uint32_t n_samples, float* 
             const int pi = (int)(k % n_pipes);
             const uint32_t cnt = std::min(batch, n_samples - done);
             // the pipeline's previous batch must be done before its buffers are reused
-            if (!(err = harvest_batch(c, pi))) err = batch_begin(run[n], c, BatchSpec{pi, first_sample + done, cnt, ar, done + cnt == n_samples, d_samples});
+            if (!(err = harvest_batch(c, pi))) err = batch_begin(run[n], c, call.spec(pi, done, cnt));
             done += cnt;
         }
         if (!err) err = run_group(c, run, n, prev_done);
-        if (!err && samples_out && !(err = harvest_batch(c, run[0].spec.pipe)))
-            err = st.download(samples_out + (size_t)(run[0].spec.first_sample - first_sample) * c->local_pixels * 4, d_samples, (size_t)run[0].spec.count * c->local_pixels * 16);
+        if (!err) err = call.group_done(run[0]);
     }
     for (uint32_t i = 0; i < n_pipes; ++i)
     {
@@ -1254,25 +1284,71 @@ int render_batches(pt_ctx* c, uint32_t first_sample, uint32_t n_samples, float* 
     }
     // whatever the caller queues next on pipeline 0's stream comes after the last accumulation (harvest_batch has waited for every
     // pipeline, so this is already true for the host; the event keeps stream order explicit for callers that share the stream)
-    if (!err && prev_done && n_pipes > 1) HIPCHK(c, hipStreamWaitEvent(c->stream, prev_done, 0));
+    if (!err && rq.stream_after && prev_done && n_pipes > 1) HIPCHK(c, hipStreamWaitEvent(c->stream, prev_done, 0));
     if (err)
     {
-        // Launches of the failed batch (and of batches pipelined behind it) may still be running on the pipelines' streams, and on
-        // PT_ERR_LIMIT some batches have added incomplete samples to the frame: wait for everything, then drop the partial sums so that
-        // nothing stale can be read back as a result (pt_api.h: the accumulation is reset by a failed render).
-        for (int i = 0; i < pt_ctx::kMaxPipes; ++i)
-        {
-            (void)hipStreamSynchronize(c->pipe_stream(i));
-            if (c->pipe[i].side_stream) (void)hipStreamSynchronize(c->pipe[i].side_stream);
-            c->pipe[i].busy = false;
-            c->pipe[i].ev_used = 0; // (batches that were never harvested: their timers are void as well)
-        }
-        (void)hipGetLastError();
+        drain_pipelines(c);
+        call.failed();
+    }
+    return err;
+}
+
+// a request's wall time from t0 on, into the statistics
+void add_ms_total(pt_ctx* c, std::chrono::steady_clock::time_point t0)
+{
+    c->stats.ms_total += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// a render's batches: samples of the active pixels, accumulated in sample order or (samples_out) brought back group by group
+struct RenderBatches
+{
+    pt_ctx* c;
+    uint32_t first_sample, n_samples;
+    ActiveRect ar;
+    float* samples_out;
+    Staging& st; // the caller's: it outlives the batches
+    f4* d_samples = nullptr;
+    std::chrono::steady_clock::time_point t0{};
+    int planned(uint32_t batch, uint32_t)
+    {
+        if (samples_out) d_samples = (f4*)st.out((size_t)batch * c->local_pixels * 16);
+        t0 = std::chrono::steady_clock::now();
+        return st.err;
+    }
+    BatchSpec spec(int pipe, uint32_t done, uint32_t cnt) const { return BatchSpec{pipe, first_sample + done, cnt, ar, done + cnt == n_samples, d_samples}; }
+    int group_done(const BatchRun& first)
+    {
+        int r;
+        if (!samples_out) return PT_OK;
+        if ((r = harvest_batch(c, first.spec.pipe))) return r;
+        return st.download(samples_out + (size_t)(first.spec.first_sample - first_sample) * c->local_pixels * 4, d_samples, (size_t)first.spec.count * c->local_pixels * 16);
+    }
+    // On PT_ERR_LIMIT some batches have added incomplete samples to the frame: drop the partial sums so that nothing stale can be read back
+    // as a result (pt_api.h: the accumulation is reset by a failed render).
+    void failed()
+    {
         (void)clear_accumulation(c);
         (void)hipStreamSynchronize(c->stream);
-        return err;
     }
-    c->stats.ms_total += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+};
+
+int render_batches(pt_ctx* c, uint32_t first_sample, uint32_t n_samples, float* samples_out)
+{
+    int r;
+    if ((r = precheck(c))) return r;
+    if (n_samples == 0 || c->local_pixels == 0) return PT_OK;
+    if ((r = upload_scene(c)) || (r = ensure_frame(c)) || (r = ensure_environment(c))) return r;
+    Staging st(c);
+    RenderBatches call{c, first_sample, n_samples, render_rect(c), samples_out, st};
+    BatchRequest rq;
+    rq.n_samples = n_samples;
+    rq.act_pixels = std::max<size_t>((size_t)call.ar.w * call.ar.rows, 1);
+    rq.batch_spp = c->cfg.batch_spp;
+    rq.samples_out = samples_out != nullptr;
+    rq.release_idle = rq.stream_after = true;
+    rq.what = "render";
+    if ((r = run_batches(c, rq, call))) return r;
+    add_ms_total(c, call.t0);
     return PT_OK;
 }
 
@@ -1285,105 +1361,89 @@ int rays_precheck(pt_ctx* c)
     return PT_OK;
 }
 
+// a ray list's batches: windows of the rays from seg0 on, each one row of rays whose path ids index it.  The frame is not touched, so a
+// failure has nothing to take back (the outputs are then incomplete).
+struct RayBatches
+{
+    pt_ctx* c;
+    const float *o, *d;
+    const uint2* key;
+    uint32_t draws;
+    f4 *radiance, *position;
+    uint8_t* id;
+    uint64_t seg0 = 0;
+    RayBatch rb[pt_ctx::kMaxPipes] = {}; // one per pipeline: its batch in flight reads it
+    int planned(uint32_t batch, uint32_t n_pipes)
+    {
+        int r;
+        for (uint32_t i = 0; i < n_pipes; ++i)
+            if ((r = dev_alloc(c, c->pipe[i].ray_pos, (size_t)std::max(batch, 64u) * 16)) || (r = dev_alloc(c, c->pipe[i].ray_id, (size_t)std::max(batch, 64u) * 4))) return r;
+        return PT_OK;
+    }
+    BatchSpec spec(int pipe, uint32_t done, uint32_t cnt)
+    {
+        const uint64_t first = seg0 + done;
+        rb[pipe] = RayBatch{RayView{o + 3 * first, d + 3 * first, key + first}, draws, radiance ? radiance + first : nullptr, position ? position + first : nullptr,
+                            id ? id + first : nullptr};
+        BatchSpec s{pipe, 0u, 1u, ActiveRect{0u, cnt, 0u, 1u}};
+        s.rays = &rb[pipe];
+        return s;
+    }
+    int group_done(const BatchRun&) { return PT_OK; }
+    void failed() {}
+};
+
 // Integrates rays [0, n) of a device-resident table (o, d: 3 floats per ray; key: {pixel, sample} per ray) into device outputs indexed like
-// the table (any may be null).  The list is cut into windows of at most 2^29 - 1 rays, planned like a render's batches (plan_batches with
+// the table (any may be null).  The list is cut into windows of at most 2^29 - 1 rays, planned like a render's batches (run_batches with
 // one "pixel" and a ray per "sample"), alternating over the pipelines; a window is one wavefront batch whose path ids index it.  The frame
-// (accumulation, history, moments, guides) is neither read nor written, so a failed call leaves it as it was.  Blocking.
+// (accumulation, history, moments, guides) is neither read nor written, so a failed call leaves it as it was.  Blocking: run_batches has
+// waited for every pipeline, so whatever the caller queues next on the context's stream comes after the results.
 int integrate_rays_device(pt_ctx* c, uint64_t n, const float* o, const float* d, const uint2* key, uint32_t draws, uint32_t batch_rays, f4* radiance,
                           f4* position, uint8_t* id)
 {
     int r;
     if (n == 0) return PT_OK;
     if ((r = upload_scene(c)) || (r = ensure_environment(c))) return r;
-    const uint64_t kMaxWindow = (1ull << 29) - 1;
+    RayBatches call{c, o, d, key, draws, radiance, position, id};
+    BatchRequest rq;
+    rq.batch_spp = (uint32_t)std::min<uint64_t>(batch_rays, (1ull << 29) - 1);
+    rq.what = "rays";
     const auto t0 = std::chrono::steady_clock::now();
-    int err = PT_OK;
     // (plan_batches counts in 32 bits: longer lists are planned in segments)
-    for (uint64_t seg0 = 0; seg0 < n && !err; seg0 += 0x80000000ull)
+    for (call.seg0 = 0; call.seg0 < n; call.seg0 += 0x80000000ull)
     {
-        const uint32_t seg_n = (uint32_t)std::min<uint64_t>(n - seg0, 0x80000000ull);
-        PlanRequest q;
-        q.n_samples = seg_n;
-        q.act_pixels = 1;
-        q.pipelines = c->cfg.pipelines;
-        q.batch_spp = (uint32_t)std::min<uint64_t>(batch_rays, kMaxWindow);
-        q.lds_scene = c->lds_scene;
-        q.max_paths = (size_t)96 << 20;
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
-        {
-            size_t held = 0;
-            for (const pt_ctx::Pipe& pp : c->pipe)
-                for (const DevBuf& b : pp.pool) held += b.bytes;
-            uint32_t n_classes = 0;
-            for (uint32_t k = 1; k < Q_COUNT; ++k) n_classes += c->class_present[k] ? 1u : 0u;
-            q.max_paths = max_paths_for(free_b, held, n_classes, c->sv.has_volumes != 0);
-        }
-        for (int i = 0; i < pt_ctx::kMaxPipes; ++i) q.cap_paths[i] = c->pipe[i].cap_paths;
-        const BatchPlan plan = plan_batches(q);
-        if (!plan.batch) return fail(c, PT_ERR_ARG, "batch too large (path ids are 29-bit)");
-        const uint32_t batch = plan.batch, n_pipes = plan.n_pipes;
-        if (n_pipes > 1)
-            for (uint32_t i = 0; i < n_pipes; ++i)
-                if (!c->pipe[i].busy && c->pipe[i].cap_paths > (size_t)batch + batch / 4) free_pipe_pool(c->pipe[i]);
-        for (uint32_t i = 0; i < n_pipes; ++i)
-        {
-            pt_ctx::Pipe& pp = c->pipe[i];
-            if ((r = ensure_wavefront(c, (int)i, batch, c->cfg.max_bounces + 2))) return r;
-            if ((r = dev_alloc(c, pp.ray_pos, (size_t)std::max(batch, 64u) * 16)) || (r = dev_alloc(c, pp.ray_id, (size_t)std::max(batch, 64u) * 4))) return r;
-        }
-        if (n_pipes > 1)
-        {
-            HIPCHK(c, hipEventRecord(c->ev_start, c->stream));
-            for (uint32_t i = 1; i < n_pipes; ++i) HIPCHK(c, hipStreamWaitEvent(c->pipe_stream((int)i), c->ev_start, 0));
-        }
-        hipEvent_t prev_done = nullptr;
-        RayBatch rb[pt_ctx::kMaxPipes];
-        // batch k on pipeline k % n_pipes; the first n_pipes go out bounce by bounce across the pipelines, as in render_batches
-        for (uint32_t done = 0, k = 0; done < seg_n && !err;)
-        {
-            const uint32_t group = (k == 0 && PT_INTERLEAVE_FIRST) ? n_pipes : 1u;
-            BatchRun run[pt_ctx::kMaxPipes];
-            uint32_t m = 0;
-            for (; m < group && done < seg_n && !err; ++m, ++k)
-            {
-                const int pi = (int)(k % n_pipes);
-                const uint32_t cnt = std::min(batch, seg_n - done);
-                const uint64_t first = seg0 + done;
-                // the pipeline's previous batch must be done before its buffers (and its RayBatch) are reused
-                if (!(err = harvest_batch(c, pi)))
-                {
-                    rb[pi] = RayBatch{RayView{o + 3 * first, d + 3 * first, key + first}, draws, radiance ? radiance + first : nullptr,
-                                      position ? position + first : nullptr, id ? id + first : nullptr};
-                    BatchSpec spec{pi, 0u, 1u, ActiveRect{0u, cnt, 0u, 1u}};
-                    spec.rays = &rb[pi];
-                    err = batch_begin(run[m], c, spec);
-                }
-                done += cnt;
-            }
-            if (!err) err = run_group(c, run, m, prev_done);
-        }
-        for (uint32_t i = 0; i < n_pipes; ++i)
-        {
-            const int hr = harvest_batch(c, (int)i);
-            if (hr && !err) err = hr;
-        }
+        rq.n_samples = (uint32_t)std::min<uint64_t>(n - call.seg0, 0x80000000ull);
+        if ((r = run_batches(c, rq, call))) return r;
     }
-    if (err)
+    add_ms_total(c, t0);
+    return PT_OK;
+}
+
+// The rays of a bake (pt_bake_probes, pt_bake_lightmap), item-major with an item's samples consecutive, go through a ray table of at most
+// `chunk` rays at a time, in buffers of `st`: filled on the device (fill), integrated (in wavefront batches of their own), folded in sample
+// order (fold).  pt_config.batch_spp, a render's test knob, cuts here as well: wavefront batches of batch_spp * n_items rays, and three of
+// them per table (2^26 rays at the most), so that an item's samples straddle both.  Results do not depend on either cut.
+template <class Fill, class Fold>
+int bake_rays(pt_ctx* c, Staging& st, uint32_t n_items, uint32_t n_samples, Fill&& fill, Fold&& fold)
+{
+    const uint64_t total = (uint64_t)n_items * n_samples;
+    const uint64_t cut = (uint64_t)c->cfg.batch_spp * n_items;
+    const uint32_t batch_rays = (uint32_t)std::min<uint64_t>(cut, (1ull << 29) - 1);
+    const uint32_t chunk = (uint32_t)std::min<uint64_t>(total, batch_rays ? std::min<uint64_t>(3ull * batch_rays, 1ull << 26) : (1ull << 26));
+    float* d_o = (float*)st.out((size_t)chunk * 12);
+    float* d_d = (float*)st.out((size_t)chunk * 12);
+    uint2* d_key = (uint2*)st.out((size_t)chunk * 8);
+    f4* d_rad = (f4*)st.out((size_t)chunk * 16);
+    if (st.err) return st.err;
+    int r;
+    for (uint64_t first = 0; first < total; first += chunk)
     {
-        // launches of the failed batch and of batches behind it may still be running: wait for everything (the outputs are then incomplete)
-        for (int i = 0; i < pt_ctx::kMaxPipes; ++i)
-        {
-            (void)hipStreamSynchronize(c->pipe_stream(i));
-            if (c->pipe[i].side_stream) (void)hipStreamSynchronize(c->pipe[i].side_stream);
-            c->pipe[i].busy = false;
-            c->pipe[i].ev_used = 0;
-        }
-        (void)hipGetLastError();
-        return err;
+        const uint32_t cnt = (uint32_t)std::min<uint64_t>(chunk, total - first);
+        fill(first, cnt, d_o, d_d, d_key);
+        if ((r = integrate_rays_device(c, cnt, d_o, d_d, d_key, 1u, batch_rays, d_rad, nullptr, nullptr))) return r;
+        fold(first, cnt, d_d, d_rad);
+        HIPCHK(c, hipGetLastError());
     }
-    // (harvest_batch has waited for every pipeline: whatever the caller queues next on the context's stream comes after the results)
-    c->stats.ms_total += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return PT_OK;
 }
 
@@ -1709,31 +1769,29 @@ int pt_add_texture(pt_ctx* c, uint32_t w, uint32_t h, const float* rgb_linear)
     return r;
 }
 
-int pt_set_material_texture(pt_ctx* c, int material, int texture)
+// the three pt_set_material_*texture calls: HostScene's setter, `what` when it refuses
+static int set_material_texture(pt_ctx* c, int (HostScene::*set)(int, int), int material, int texture, const char* what)
 {
     if (!c) return PT_ERR_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
-    if (c->scene.set_material_texture(material, texture) < 0) return fail(c, PT_ERR_ARG, "bad material or texture index, or an emissive material");
+    if ((c->scene.*set)(material, texture) < 0) return fail(c, PT_ERR_ARG, what);
     c->scene_uploaded = false;
     return PT_OK;
+}
+
+int pt_set_material_texture(pt_ctx* c, int material, int texture)
+{
+    return set_material_texture(c, &HostScene::set_material_texture, material, texture, "bad material or texture index, or an emissive material");
 }
 
 int pt_set_material_emission_texture(pt_ctx* c, int material, int texture)
 {
-    if (!c) return PT_ERR_ARG;
-    std::lock_guard<std::mutex> lk(c->mu);
-    if (c->scene.set_material_emission_texture(material, texture) < 0) return fail(c, PT_ERR_ARG, "bad material or texture index, or a material that is not emissive");
-    c->scene_uploaded = false;
-    return PT_OK;
+    return set_material_texture(c, &HostScene::set_material_emission_texture, material, texture, "bad material or texture index, or a material that is not emissive");
 }
 
 int pt_set_material_normal_texture(pt_ctx* c, int material, int texture)
 {
-    if (!c) return PT_ERR_ARG;
-    std::lock_guard<std::mutex> lk(c->mu);
-    if (c->scene.set_material_normal_texture(material, texture) < 0) return fail(c, PT_ERR_ARG, "bad material or texture index, or an emissive material");
-    c->scene_uploaded = false;
-    return PT_OK;
+    return set_material_texture(c, &HostScene::set_material_normal_texture, material, texture, "bad material or texture index, or an emissive material");
 }
 
 int pt_set_model_uvs(pt_ctx* c, int model, const float* uv, uint32_t n_tris)
@@ -1761,18 +1819,14 @@ int pt_model_uvs(pt_ctx* c, int model, float* uv, uint32_t cap_tris, uint32_t* n
     return PT_OK;
 }
 
-int pt_surface_colour(pt_ctx* c, int on_device, uint32_t n, const uint32_t* instance, const uint32_t* prim, const float* u, const float* v, float* rgb)
+// ---- the unit hooks pt_surface_colour and pt_shading_normal: n queries {world instance, load-order primitive, u, v}
+// tri[i] <- the leaf-order triangle of query i: tri_orig inverted for the models asked about
+static int leaf_order_tris(pt_ctx* c, uint32_t n, const uint32_t* instance, const uint32_t* prim, std::vector<uint32_t>& tri)
 {
-    if (!c) return PT_ERR_ARG;
-    std::lock_guard<std::mutex> lk(c->mu);
-    if (!c->scene.built) return fail(c, PT_ERR_STATE, "pt_build has not been called");
-    if (n == 0) return PT_OK;
-    if (!instance || !prim || !u || !v || !rgb) return fail(c, PT_ERR_ARG, "null pointer");
     const FlatScene& f = c->scene.flat;
     const HostTlas& world = c->scene.world;
-    // leaf-order triangle of every query: tri_orig inverted for the models asked about
     std::vector<std::vector<uint32_t>> where(c->scene.blas.size());
-    std::vector<uint32_t> tri(n);
+    tri.resize(n);
     for (uint32_t i = 0; i < n; ++i)
     {
         if (instance[i] >= world.instances.size()) return fail(c, PT_ERR_ARG, "instance index");
@@ -1786,6 +1840,31 @@ int pt_surface_colour(pt_ctx* c, int on_device, uint32_t n, const uint32_t* inst
         }
         tri[i] = where[mi][prim[i]];
     }
+    return PT_OK;
+}
+// the queries on the device, in buffers of `st` (null after a failure: st.err)
+struct SurfaceQueries { const uint32_t *instance, *tri; const float *u, *v; };
+static SurfaceQueries upload_queries(Staging& st, uint32_t n, const uint32_t* instance, const std::vector<uint32_t>& tri, const float* u, const float* v)
+{
+    SurfaceQueries q;
+    q.instance = (const uint32_t*)st.in(instance, (size_t)n * 4);
+    q.tri = (const uint32_t*)st.in(tri.data(), (size_t)n * 4);
+    q.u = (const float*)st.in(u, (size_t)n * 4);
+    q.v = (const float*)st.in(v, (size_t)n * 4);
+    return q;
+}
+
+int pt_surface_colour(pt_ctx* c, int on_device, uint32_t n, const uint32_t* instance, const uint32_t* prim, const float* u, const float* v, float* rgb)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->scene.built) return fail(c, PT_ERR_STATE, "pt_build has not been called");
+    if (n == 0) return PT_OK;
+    if (!instance || !prim || !u || !v || !rgb) return fail(c, PT_ERR_ARG, "null pointer");
+    const FlatScene& f = c->scene.flat;
+    std::vector<uint32_t> tri;
+    int r;
+    if ((r = leaf_order_tris(c, n, instance, prim, tri))) return r;
     if (!on_device)
     {
         const TexView tv = f.tex_view();
@@ -1797,16 +1876,12 @@ int pt_surface_colour(pt_ctx* c, int on_device, uint32_t n, const uint32_t* inst
         }
         return PT_OK;
     }
-    int r;
     if ((r = upload_scene(c))) return r;
     Staging st(c);
-    const uint32_t* d_inst = (const uint32_t*)st.in(instance, (size_t)n * 4);
-    const uint32_t* d_tri = (const uint32_t*)st.in(tri.data(), (size_t)n * 4);
-    const float* d_u = (const float*)st.in(u, (size_t)n * 4);
-    const float* d_v = (const float*)st.in(v, (size_t)n * 4);
+    const SurfaceQueries q = upload_queries(st, n, instance, tri, u, v);
     float* d_rgb = (float*)st.out((size_t)n * 12);
     if (st.err) return st.err;
-    launch_surface_colour(c->stream, c->sv, c->tex, n, d_inst, d_tri, d_u, d_v, d_rgb);
+    launch_surface_colour(c->stream, c->sv, c->tex, n, q.instance, q.tri, q.u, q.v, d_rgb);
     HIPCHK(c, hipGetLastError());
     return st.download(rgb, d_rgb, (size_t)n * 12);
 }
@@ -1820,23 +1895,9 @@ int pt_shading_normal(pt_ctx* c, int on_device, uint32_t n, const uint32_t* inst
     if (n == 0) return PT_OK;
     if (!instance || !prim || !u || !v || !dir_xyz || !out_normal_xyz || !out_front) return fail(c, PT_ERR_ARG, "null pointer");
     const FlatScene& f = c->scene.flat;
-    const HostTlas& world = c->scene.world;
-    // leaf-order triangle of every query: tri_orig inverted for the models asked about
-    std::vector<std::vector<uint32_t>> where(c->scene.blas.size());
-    std::vector<uint32_t> tri(n);
-    for (uint32_t i = 0; i < n; ++i)
-    {
-        if (instance[i] >= world.instances.size()) return fail(c, PT_ERR_ARG, "instance index");
-        const uint32_t mi = world.instances[instance[i]].model;
-        const HostBlas& bl = c->scene.blas[mi];
-        if (prim[i] >= bl.tris.size()) return fail(c, PT_ERR_ARG, "primitive index");
-        if (where[mi].empty())
-        {
-            where[mi].resize(bl.prim_ids.size());
-            for (size_t k = 0; k < bl.prim_ids.size(); ++k) where[mi][bl.prim_ids[k]] = f.tri_base[mi] + (uint32_t)k;
-        }
-        tri[i] = where[mi][prim[i]];
-    }
+    std::vector<uint32_t> tri;
+    int r;
+    if ((r = leaf_order_tris(c, n, instance, prim, tri))) return r;
     if (!on_device)
     {
         const TexNView tv = f.texn_view();
@@ -1850,17 +1911,13 @@ int pt_shading_normal(pt_ctx* c, int on_device, uint32_t n, const uint32_t* inst
         }
         return PT_OK;
     }
-    int r;
     if ((r = upload_scene(c))) return r;
     Staging st(c);
-    const uint32_t* d_inst = (const uint32_t*)st.in(instance, (size_t)n * 4);
-    const uint32_t* d_tri = (const uint32_t*)st.in(tri.data(), (size_t)n * 4);
-    const float* d_u = (const float*)st.in(u, (size_t)n * 4);
-    const float* d_v = (const float*)st.in(v, (size_t)n * 4);
+    const SurfaceQueries q = upload_queries(st, n, instance, tri, u, v);
     const float* d_dir = (const float*)st.in(dir_xyz, (size_t)n * 12);
     float* d_out = (float*)st.out((size_t)n * 16);
     if (st.err) return st.err;
-    launch_shading_normal(c->stream, c->sv, c->tex, n, d_inst, d_tri, d_u, d_v, d_dir, d_out);
+    launch_shading_normal(c->stream, c->sv, c->tex, n, q.instance, q.tri, q.u, q.v, d_dir, d_out);
     HIPCHK(c, hipGetLastError());
     std::vector<float> out4((size_t)n * 4);
     if ((r = st.download(out4.data(), d_out, (size_t)n * 16))) return r;
@@ -2252,7 +2309,7 @@ int prepare_motion(pt_ctx* c, bool* world_moved)
     return PT_OK;
 }
 
-int render_guides_locked(pt_ctx* c, uint32_t sample);
+int render_guides_locked(pt_ctx* c, uint32_t sample, uint32_t max_hops = 0u);
 
 // pt_frame (moving = false) and pt_frame_moving under the context's lock
 int frame_locked(pt_ctx* c, uint32_t frame_index, const float* last_inv_projection, float* data, float* position, uint32_t* id, bool moving)
@@ -2521,46 +2578,18 @@ int guide_trace(pt_ctx* c, uint32_t sample)
     else launch_trace_rays_closest(c->stream, trace_launch(c), c->sv.world_root, q, px, head, (f4*)c->d_ghits.p);
     return PT_OK;
 }
-// the hook queue, its hits and its claim cursors for the local pixels
-int guide_scratch(pt_ctx* c)
+// the hook queue, its hits and its claim cursors for the local pixels; chains that go on (max_hops > 0) need the second hook queue they
+// alternate with, its head words and their per-pixel state as well
+int guide_scratch(pt_ctx* c, uint32_t max_hops)
 {
     int r;
     const size_t n = std::max<uint32_t>(c->local_pixels, 1);
     for (DevBuf* b : {&c->d_gray_a, &c->d_gray_b, &c->d_ghits})
         if ((r = dev_alloc(c, *b, n * 16))) return r;
-    return dev_alloc(c, c->d_ghead, ((size_t)32 + kHeadWordsPerQueue) * 4);
-}
-
-int render_guides_locked(pt_ctx* c, uint32_t sample)
-{
-    if (!c->scene.built) return fail(c, PT_ERR_STATE, "pt_build has not been called");
-    if (!c->scene.camera.set) return fail(c, PT_ERR_STATE, "pt_set_camera has not been called");
-    int r;
-    if ((r = upload_scene(c))) return r;
-    const uint32_t px = c->local_pixels;
-    const size_t n = std::max<uint32_t>(px, 1);
-    for (DevBuf* b : {&c->d_gpos, &c->d_gnrm, &c->d_galbedo})
+    if ((r = dev_alloc(c, c->d_ghead, ((size_t)32 + kHeadWordsPerQueue) * 4)) || !max_hops) return r;
+    for (DevBuf* b : {&c->d_gray2_a, &c->d_gray2_b, &c->d_gstate})
         if ((r = dev_alloc(c, *b, n * 16))) return r;
-    if ((r = dev_alloc(c, c->d_gmodel, n * 4)) || (r = dev_alloc(c, c->d_ginst, n * 4)) || (r = guide_scratch(c))) return r;
-    c->guides_valid = false;
-    if (px)
-    {
-        if ((r = guide_trace(c, sample))) return r;
-        const CameraView cam = c->scene.camera_view();
-        const CameraOptics lens = c->scene.optics_view();
-        const RayQueue q{(f4*)c->d_gray_a.p, (f4*)c->d_gray_b.p};
-        launch_guide_resolve(c->stream, c->sv, px, cam, lens, q, (const f4*)c->d_ghits.p, (f4*)c->d_gpos.p, (f4*)c->d_gnrm.p, (uint32_t*)c->d_gmodel.p,
-                             (uint32_t*)c->d_ginst.p);
-        launch_guide_albedo(c->stream, c->sv, c->tex, px, (const f4*)c->d_ghits.p, (f4*)c->d_galbedo.p);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
-    c->guides_valid = true;
-    c->guides_scene_version = c->scene_version;
-    c->guides_config_version = c->config_version;
-    c->guides_sample = sample;
-    c->guides_max_hops = 0;
-    return PT_OK;
+    return dev_alloc(c, c->d_ghead2, ((size_t)32 + kHeadWordsPerQueue) * 4);
 }
 
 // pt_guide_params as the two followed calls take it
@@ -2571,18 +2600,10 @@ int follow_params(pt_ctx* c, const pt_guide_params* gp, const char* who)
     if (gp->reserved[0] || gp->reserved[1] || gp->reserved[2]) return fail(c, PT_ERR_ARG, std::string(who) + ": the reserved words must be 0");
     return PT_OK;
 }
-// the second hook queue, its head words and the chains' per-pixel state
-int follow_scratch(pt_ctx* c)
-{
-    int r;
-    const size_t n = std::max<uint32_t>(c->local_pixels, 1);
-    for (DevBuf* b : {&c->d_gray2_a, &c->d_gray2_b, &c->d_gstate})
-        if ((r = dev_alloc(c, *b, n * 16))) return r;
-    return dev_alloc(c, c->d_ghead2, ((size_t)32 + kHeadWordsPerQueue) * 4);
-}
 // the chains of `sample` of every local pixel, hop by hop (enqueued, not waited for): trace the queue, then k_guide_follow, which ends
 // chains into the guides (sum null) or into the mean-albedo sums and queues the others' next rays into the other hook queue.  That
-// queue's count stays on the device, in the head word the next trace reads; a hop nobody reached is two empty launches.
+// queue's count stays on the device, in the head word the next trace reads; a hop nobody reached is two empty launches.  No chain goes
+// on from the last hop, so that launch gets no next queue (max_hops 0, the first-hit guides, never has one).
 int follow_chains(pt_ctx* c, uint32_t sample, uint32_t max_hops, f4* sum)
 {
     int r;
@@ -2595,14 +2616,17 @@ int follow_chains(pt_ctx* c, uint32_t sample, uint32_t max_hops, f4* sum)
     {
         const uint32_t cur = h & 1u, nxt = cur ^ 1u;
         if (h) launch_trace_rays_closest(c->stream, trace_launch(c), c->sv.world_root, q[cur], c->local_pixels, head[cur], (f4*)c->d_ghits.p);
-        HIPCHK(c, hipMemsetAsync(head[nxt], 0, c->d_ghead.bytes, c->stream));
         FollowArgs a{};
         a.in = q[cur];
-        a.next = q[nxt];
         a.hits = (const f4*)c->d_ghits.p;
         a.n_in = head[cur];
-        a.n_next = head[nxt];
-        a.state = (f4*)c->d_gstate.p;
+        if (h < last)
+        {
+            HIPCHK(c, hipMemsetAsync(head[nxt], 0, c->d_ghead.bytes, c->stream));
+            a.next = q[nxt];
+            a.n_next = head[nxt];
+        }
+        a.state = max_hops ? (f4*)c->d_gstate.p : nullptr;
         a.position = (f4*)c->d_gpos.p;
         a.normal = (f4*)c->d_gnrm.p;
         a.albedo = (f4*)c->d_galbedo.p;
@@ -2615,6 +2639,69 @@ int follow_chains(pt_ctx* c, uint32_t sample, uint32_t max_hops, f4* sum)
         a.max_hops = max_hops;
         launch_guide_follow(c->stream, c->sv, c->tex, a);
     }
+    return PT_OK;
+}
+
+// The guides of `sample` of every local pixel: the chains of at most max_hops hops, 0 being the first hits (pt_render_guides,
+// pt_render_guides_followed and pt_frame_moving, under the context's lock).  The one place that says what the guides belong to.
+int render_guides_locked(pt_ctx* c, uint32_t sample, uint32_t max_hops)
+{
+    if (!c->scene.built) return fail(c, PT_ERR_STATE, "pt_build has not been called");
+    if (!c->scene.camera.set) return fail(c, PT_ERR_STATE, "pt_set_camera has not been called");
+    if (max_hops && c->scene.blas.size() >= ((size_t)1 << 28))
+        return fail(c, PT_ERR_LIMIT, "pt_render_guides_followed: the model guide keeps the hops in bits 31..28, so a scene has fewer than 2^28 models");
+    int r;
+    if ((r = upload_scene(c))) return r;
+    const uint32_t px = c->local_pixels;
+    const size_t n = std::max<uint32_t>(px, 1);
+    for (DevBuf* b : {&c->d_gpos, &c->d_gnrm, &c->d_galbedo})
+        if ((r = dev_alloc(c, *b, n * 16))) return r;
+    if ((r = dev_alloc(c, c->d_gmodel, n * 4)) || (r = dev_alloc(c, c->d_ginst, n * 4)) || (r = dev_alloc(c, c->d_ghops, n)) || (r = guide_scratch(c, max_hops))) return r;
+    c->guides_valid = false;
+    if (px)
+    {
+        if ((r = follow_chains(c, sample, max_hops, nullptr))) return r;
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    c->guides_valid = true;
+    c->guides_scene_version = c->scene_version;
+    c->guides_config_version = c->config_version;
+    c->guides_sample = sample;
+    c->guides_max_hops = max_hops;
+    return PT_OK;
+}
+
+// px device f4s as xyz triples on the host (xyz may be null); synchronises the context's stream, copies queued before included
+int download_xyz(pt_ctx* c, const void* src, size_t px, float* xyz)
+{
+    std::vector<f4> v(xyz ? px : 0);
+    if (xyz) HIPCHK(c, hipMemcpyAsync(v.data(), src, px * 16, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i < v.size(); ++i) { xyz[3 * i] = v[i].x; xyz[3 * i + 1] = v[i].y; xyz[3 * i + 2] = v[i].z; }
+    return PT_OK;
+}
+
+// What pt_denoise and pt_denoise_albedo (`who`; albedo_source: the latter's, else null) check and make ready before their launch: the
+// parameters, one rank, guides present and current, something accumulated, a mean albedo that goes with the guides where that is the
+// source; only then the device, the filter's scratch and result images, and the moments if they describe the accumulation (else null)
+int denoise_ready(pt_ctx* c, const pt_denoise_params* p, const char* who, const uint32_t* albedo_source, DenoiseK& k, const float** moments)
+{
+    int r;
+    if ((r = denoise_params(c, p, k))) return r;
+    if (albedo_source && *albedo_source != PT_ALBEDO_GUIDE && *albedo_source != PT_ALBEDO_MEAN)
+        return fail(c, PT_ERR_ARG, "pt_denoise_albedo: albedo_source must be PT_ALBEDO_GUIDE or PT_ALBEDO_MEAN");
+    if (c->cfg.world_size != 1) return fail(c, PT_ERR_STATE, std::string(who) + " needs the whole frame on one rank (the neighbourhoods cross row strips)");
+    if (!c->guides_valid) return fail(c, PT_ERR_STATE, "no guides: pt_render_guides first");
+    if (c->guides_scene_version != c->scene_version || c->guides_config_version != c->config_version)
+        return fail(c, PT_ERR_STATE, "the guides are stale (camera, scene, environment or configuration changed since pt_render_guides)");
+    if (!c->d_accum.p) return fail(c, PT_ERR_STATE, "nothing has been accumulated");
+    const bool mean = albedo_source && *albedo_source == PT_ALBEDO_MEAN;
+    if (mean && !albedo_current(c)) return fail(c, PT_ERR_STATE, "no mean albedo (none accumulated, reset, or stale): pt_accumulate_albedo first");
+    if (mean && c->albedo_max_hops != c->guides_max_hops)
+        return fail(c, PT_ERR_STATE, "the guides and the mean albedo were made with different max_hops (pt_render_guides_followed / pt_accumulate_albedo_followed)");
+    if ((r = ensure_device(c)) || (r = denoise_scratch(c, c->local_pixels)) || (r = dev_alloc(c, c->d_dn_out, (size_t)c->local_pixels * 16))) return r;
+    *moments = ((c->cfg.flags & PT_FLAG_ADAPTIVE) && c->moments_valid) ? (const float*)c->d_moments.p : nullptr;
     return PT_OK;
 }
 
@@ -2636,32 +2723,7 @@ int pt_render_guides_followed(pt_ctx* c, uint32_t sample, const pt_guide_params*
     std::lock_guard<std::mutex> lk(c->mu);
     int r;
     if ((r = follow_params(c, gp, "pt_render_guides_followed"))) return r;
-    const uint32_t max_hops = gp->max_hops;
-    if (max_hops == 0u) return render_guides_locked(c, sample); // 0 IS pt_render_guides
-    if (!c->scene.built) return fail(c, PT_ERR_STATE, "pt_build has not been called");
-    if (!c->scene.camera.set) return fail(c, PT_ERR_STATE, "pt_set_camera has not been called");
-    if (c->scene.blas.size() >= ((size_t)1 << 28)) return fail(c, PT_ERR_LIMIT, "pt_render_guides_followed: the model guide keeps the hops in bits 31..28, so a scene has fewer than 2^28 models");
-    if ((r = upload_scene(c))) return r;
-    const uint32_t px = c->local_pixels;
-    const size_t n = std::max<uint32_t>(px, 1);
-    for (DevBuf* b : {&c->d_gpos, &c->d_gnrm, &c->d_galbedo})
-        if ((r = dev_alloc(c, *b, n * 16))) return r;
-    if ((r = dev_alloc(c, c->d_gmodel, n * 4)) || (r = dev_alloc(c, c->d_ginst, n * 4)) || (r = dev_alloc(c, c->d_ghops, n)) || (r = guide_scratch(c)) ||
-        (r = follow_scratch(c)))
-        return r;
-    c->guides_valid = false;
-    if (px)
-    {
-        if ((r = follow_chains(c, sample, max_hops, nullptr))) return r;
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
-    c->guides_valid = true;
-    c->guides_scene_version = c->scene_version;
-    c->guides_config_version = c->config_version;
-    c->guides_sample = sample;
-    c->guides_max_hops = max_hops;
-    return PT_OK;
+    return render_guides_locked(c, sample, gp->max_hops); // 0 IS pt_render_guides
 }
 
 int pt_read_guide_hops(pt_ctx* c, uint8_t* hops)
@@ -2671,7 +2733,6 @@ int pt_read_guide_hops(pt_ctx* c, uint8_t* hops)
     if (!c->guides_valid) return fail(c, PT_ERR_STATE, "no guides: pt_render_guides first");
     const size_t px = c->local_pixels;
     if (!px || !hops) return PT_OK;
-    if (c->guides_max_hops == 0u) { std::memset(hops, 0, px); return PT_OK; } // first-hit guides: no chain was followed
     HIPCHK(c, hipMemcpyAsync(hops, c->d_ghops.p, px, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return PT_OK;
@@ -2696,11 +2757,7 @@ int pt_read_guide_albedo(pt_ctx* c, float* rgb)
     if (!c->guides_valid) return fail(c, PT_ERR_STATE, "no guides: pt_render_guides first");
     const size_t px = c->local_pixels;
     if (!px || !rgb) return PT_OK;
-    std::vector<f4> al(px);
-    HIPCHK(c, hipMemcpyAsync(al.data(), c->d_galbedo.p, px * 16, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (size_t i = 0; i < px; ++i) { rgb[3 * i] = al[i].x; rgb[3 * i + 1] = al[i].y; rgb[3 * i + 2] = al[i].z; }
-    return PT_OK;
+    return download_xyz(c, c->d_galbedo.p, px, rgb);
 }
 
 int pt_read_guides(pt_ctx* c, float* position, float* normal, uint32_t* model)
@@ -2712,11 +2769,7 @@ int pt_read_guides(pt_ctx* c, float* position, float* normal, uint32_t* model)
     if (!px) return PT_OK;
     if (position) HIPCHK(c, hipMemcpyAsync(position, c->d_gpos.p, px * 16, hipMemcpyDeviceToHost, c->stream));
     if (model) HIPCHK(c, hipMemcpyAsync(model, c->d_gmodel.p, px * 4, hipMemcpyDeviceToHost, c->stream));
-    std::vector<f4> nr(normal ? px : 0);
-    if (normal) HIPCHK(c, hipMemcpyAsync(nr.data(), c->d_gnrm.p, px * 16, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (size_t i = 0; i < nr.size(); ++i) { normal[3 * i] = nr[i].x; normal[3 * i + 1] = nr[i].y; normal[3 * i + 2] = nr[i].z; }
-    return PT_OK;
+    return download_xyz(c, c->d_gnrm.p, px, normal);
 }
 
 int pt_denoise(pt_ctx* c, const pt_denoise_params* p, float* rgba)
@@ -2724,20 +2777,12 @@ int pt_denoise(pt_ctx* c, const pt_denoise_params* p, float* rgba)
     if (!c) return PT_ERR_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
     DenoiseK k{};
+    const float* moments;
     int r;
-    if ((r = denoise_params(c, p, k))) return r;
-    if (c->cfg.world_size != 1) return fail(c, PT_ERR_STATE, "pt_denoise needs the whole frame on one rank (the neighbourhoods cross row strips)");
-    if (!c->guides_valid) return fail(c, PT_ERR_STATE, "no guides: pt_render_guides first");
-    if (c->guides_scene_version != c->scene_version || c->guides_config_version != c->config_version)
-        return fail(c, PT_ERR_STATE, "the guides are stale (camera, scene, environment or configuration changed since pt_render_guides)");
-    if (!c->d_accum.p) return fail(c, PT_ERR_STATE, "nothing has been accumulated");
-    if ((r = ensure_device(c))) return r;
+    if ((r = denoise_ready(c, p, "pt_denoise", nullptr, k, &moments))) return r;
     const size_t px = c->local_pixels;
-    if ((r = denoise_scratch(c, px)) || (r = dev_alloc(c, c->d_dn_out, px * 16))) return r;
-    const bool moments = (c->cfg.flags & PT_FLAG_ADAPTIVE) && c->moments_valid && c->d_moments.p;
-    launch_denoise(c->stream, (int)c->cfg.width, (int)c->cfg.height, k, (const f4*)c->d_accum.p, moments ? (const float*)c->d_moments.p : nullptr,
-                   (const f4*)c->d_gpos.p, (const f4*)c->d_gnrm.p, (const uint32_t*)c->d_gmodel.p, (f4*)c->d_dn_a.p, (f4*)c->d_dn_b.p,
-                   (f4*)c->d_dn_nv.p, (f4*)c->d_dn_out.p);
+    launch_denoise(c->stream, (int)c->cfg.width, (int)c->cfg.height, k, (const f4*)c->d_accum.p, moments, (const f4*)c->d_gpos.p, (const f4*)c->d_gnrm.p,
+                   (const uint32_t*)c->d_gmodel.p, (f4*)c->d_dn_a.p, (f4*)c->d_dn_b.p, (f4*)c->d_dn_nv.p, (f4*)c->d_dn_out.p);
     HIPCHK(c, hipGetLastError());
     if (rgba) HIPCHK(c, hipMemcpyAsync(rgba, c->d_dn_out.p, px * 16, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2789,7 +2834,7 @@ int pt_post_denoise(pt_ctx* c, uint32_t w, uint32_t h, const pt_denoise_params* 
 // ---- mean albedo and the demodulated filter
 } // extern "C"
 namespace {
-// pt_accumulate_albedo (max_hops 0: first hits, its own kernels) and pt_accumulate_albedo_followed
+// pt_accumulate_albedo (max_hops 0: first hits) and pt_accumulate_albedo_followed
 int accumulate_albedo_locked(pt_ctx* c, uint32_t first_sample, uint32_t n_samples, uint32_t max_hops, const char* who)
 {
     if (!c->scene.built) return fail(c, PT_ERR_STATE, "pt_build has not been called");
@@ -2800,22 +2845,14 @@ int accumulate_albedo_locked(pt_ctx* c, uint32_t first_sample, uint32_t n_sample
     if ((r = upload_scene(c))) return r;
     const uint32_t px = c->local_pixels;
     const size_t n = std::max<uint32_t>(px, 1);
-    if ((r = guide_scratch(c)) || (r = dev_alloc(c, c->d_albedo_sum, n * 16)) || (max_hops && (r = follow_scratch(c)))) return r;
+    if ((r = guide_scratch(c, max_hops)) || (r = dev_alloc(c, c->d_albedo_sum, n * 16))) return r;
     const bool fresh = !albedo_current(c) || c->albedo_max_hops != max_hops; // sums of other chains are no sums to go on from
     c->albedo_valid = false; // a failure below leaves no sum
     if (fresh) HIPCHK(c, hipMemsetAsync(c->d_albedo_sum.p, 0, n * 16, c->stream));
     if (px)
     {
         for (uint32_t k = 0; k < n_samples; ++k)
-        {
-            if (max_hops)
-            {
-                if ((r = follow_chains(c, first_sample + k, max_hops, (f4*)c->d_albedo_sum.p))) return r;
-                continue;
-            }
-            if ((r = guide_trace(c, first_sample + k))) return r;
-            launch_albedo_accumulate(c->stream, c->sv, c->tex, px, (const f4*)c->d_ghits.p, (f4*)c->d_albedo_sum.p);
-        }
+            if ((r = follow_chains(c, first_sample + k, max_hops, (f4*)c->d_albedo_sum.p))) return r;
         HIPCHK(c, hipGetLastError());
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2869,26 +2906,14 @@ int pt_denoise_albedo(pt_ctx* c, const pt_denoise_params* p, uint32_t albedo_sou
     if (!c) return PT_ERR_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
     DenoiseK k{};
+    const float* moments;
     int r;
-    if ((r = denoise_params(c, p, k))) return r;
-    if (albedo_source != PT_ALBEDO_GUIDE && albedo_source != PT_ALBEDO_MEAN)
-        return fail(c, PT_ERR_ARG, "pt_denoise_albedo: albedo_source must be PT_ALBEDO_GUIDE or PT_ALBEDO_MEAN");
-    if (c->cfg.world_size != 1) return fail(c, PT_ERR_STATE, "pt_denoise_albedo needs the whole frame on one rank (the neighbourhoods cross row strips)");
-    if (!c->guides_valid) return fail(c, PT_ERR_STATE, "no guides: pt_render_guides first");
-    if (c->guides_scene_version != c->scene_version || c->guides_config_version != c->config_version)
-        return fail(c, PT_ERR_STATE, "the guides are stale (camera, scene, environment or configuration changed since pt_render_guides)");
-    if (!c->d_accum.p) return fail(c, PT_ERR_STATE, "nothing has been accumulated");
+    if ((r = denoise_ready(c, p, "pt_denoise_albedo", &albedo_source, k, &moments))) return r;
     const bool mean = albedo_source == PT_ALBEDO_MEAN;
-    if (mean && !albedo_current(c)) return fail(c, PT_ERR_STATE, "no mean albedo (none accumulated, reset, or stale): pt_accumulate_albedo first");
-    if (mean && c->albedo_max_hops != c->guides_max_hops)
-        return fail(c, PT_ERR_STATE, "the guides and the mean albedo were made with different max_hops (pt_render_guides_followed / pt_accumulate_albedo_followed)");
-    if ((r = ensure_device(c))) return r;
     const size_t px = c->local_pixels;
-    if ((r = denoise_scratch(c, px)) || (r = dev_alloc(c, c->d_dn_k, px * 16)) || (r = dev_alloc(c, c->d_dn_out, px * 16))) return r;
-    const bool moments = (c->cfg.flags & PT_FLAG_ADAPTIVE) && c->moments_valid && c->d_moments.p;
-    launch_denoise_albedo(c->stream, (int)c->cfg.width, (int)c->cfg.height, k, (const f4*)c->d_accum.p, moments ? (const float*)c->d_moments.p : nullptr,
-                          (const f4*)c->d_gpos.p, (const f4*)c->d_gnrm.p, (const uint32_t*)c->d_gmodel.p,
-                          (const f4*)(mean ? c->d_albedo_sum.p : c->d_galbedo.p), mean, (f4*)c->d_dn_a.p, (f4*)c->d_dn_b.p, (f4*)c->d_dn_nv.p,
+    if ((r = dev_alloc(c, c->d_dn_k, px * 16))) return r;
+    launch_denoise_albedo(c->stream, (int)c->cfg.width, (int)c->cfg.height, k, (const f4*)c->d_accum.p, moments, (const f4*)c->d_gpos.p,
+                          (const f4*)c->d_gnrm.p, (const uint32_t*)c->d_gmodel.p, (const f4*)(mean ? c->d_albedo_sum.p : c->d_galbedo.p), mean, (f4*)c->d_dn_a.p, (f4*)c->d_dn_b.p, (f4*)c->d_dn_nv.p,
                           (f4*)c->d_dn_k.p, (f4*)c->d_dn_out.p);
     HIPCHK(c, hipGetLastError());
     if (rgba) HIPCHK(c, hipMemcpyAsync(rgba, c->d_dn_out.p, px * 16, hipMemcpyDeviceToHost, c->stream));
@@ -3004,30 +3029,14 @@ int pt_bake_probes(pt_ctx* c, uint32_t n_probes, const float* position, const pt
         if (!std::isfinite(position[i])) return fail(c, PT_ERR_ARG, "pt_bake_probes: probe " + std::to_string(i / 3) + " has a position that is not finite");
     if (n_probes == 0) return PT_OK;
     if ((r = upload_scene(c))) return r;
-    // The bake's rays, probe-major with a probe's samples consecutive, go through a ray table of at most `chunk` rays at a time: filled on
-    // the device, integrated (in wavefront batches of their own), folded in sample order.  pt_config.batch_spp, a render's test knob, cuts
-    // here as well: wavefront batches of batch_spp * n_probes rays, and three of them per table, so that a probe's samples straddle both.
-    const uint64_t total = (uint64_t)n_probes * p->n_samples;
-    const uint64_t cut = (uint64_t)c->cfg.batch_spp * n_probes;
-    const uint32_t batch_rays = (uint32_t)std::min<uint64_t>(cut, (1ull << 29) - 1);
-    const uint32_t chunk = (uint32_t)std::min<uint64_t>(total, batch_rays ? 3ull * batch_rays : (1ull << 26));
     Staging st(c);
     const float* d_position = (const float*)st.in(position, (size_t)n_probes * 12);
     float* d_sh = (float*)st.in(sh27, (size_t)n_probes * 27 * 4);
-    float* d_o = (float*)st.out((size_t)chunk * 12);
-    float* d_d = (float*)st.out((size_t)chunk * 12);
-    uint2* d_key = (uint2*)st.out((size_t)chunk * 8);
-    f4* d_rad = (f4*)st.out((size_t)chunk * 16);
-    if (st.err) return st.err;
     const ProbeBake pb{d_position, n_probes, p->first_sample, p->n_samples, p->key_base, c->cfg.n_sobol, c->cfg.seed};
-    for (uint64_t first = 0; first < total; first += chunk)
-    {
-        const uint32_t cnt = (uint32_t)std::min<uint64_t>(chunk, total - first);
-        launch_probe_rays(c->stream, pb, first, cnt, d_o, d_d, d_key);
-        if ((r = integrate_rays_device(c, cnt, d_o, d_d, d_key, 1u, batch_rays, d_rad, nullptr, nullptr))) return r;
-        launch_probe_project(c->stream, pb, first, cnt, d_d, d_rad, d_sh);
-        HIPCHK(c, hipGetLastError());
-    }
+    if ((r = bake_rays(c, st, n_probes, p->n_samples,
+                       [&](uint64_t first, uint32_t cnt, float* o, float* d, uint2* key) { launch_probe_rays(c->stream, pb, first, cnt, o, d, key); },
+                       [&](uint64_t first, uint32_t cnt, const float* d, const f4* rad) { launch_probe_project(c->stream, pb, first, cnt, d, rad, d_sh); })))
+        return r;
     return st.download(sh27, d_sh, (size_t)n_probes * 27 * 4);
 }
 
@@ -3114,29 +3123,13 @@ int pt_bake_lightmap(pt_ctx* c, const pt_lightmap_params* p, float* rgb_sum, uin
     const uint32_t n_cov = (uint32_t)texels.size();
     if (n_cov > 0)
     {
-        // The bake's rays, texel-major with a texel's samples consecutive, go through a ray table of at most `chunk` rays at a time, as
-        // pt_bake_probes' do: filled on the device, integrated (in wavefront batches of their own), folded in sample order.  pt_config.batch_spp
-        // cuts here as well: wavefront batches of batch_spp * covered rays, three per table, so that a texel's samples straddle both.
-        const uint64_t total = (uint64_t)n_cov * p->n_samples;
-        const uint64_t cut = (uint64_t)c->cfg.batch_spp * n_cov;
-        const uint32_t batch_rays = (uint32_t)std::min<uint64_t>(cut, (1ull << 29) - 1);
-        const uint32_t chunk = (uint32_t)std::min<uint64_t>(total, batch_rays ? std::min<uint64_t>(3ull * batch_rays, 1ull << 26) : (1ull << 26));
         const uint32_t* d_texels = (const uint32_t*)st.in(texels.data(), (size_t)n_cov * 4);
         float* d_sum = (float*)st.in(rgb_sum, px * 12);
-        float* d_o = (float*)st.out((size_t)chunk * 12);
-        float* d_d = (float*)st.out((size_t)chunk * 12);
-        uint2* d_key = (uint2*)st.out((size_t)chunk * 8);
-        f4* d_rad = (f4*)st.out((size_t)chunk * 16);
-        if (st.err) return st.err;
         const LightmapBake lb{d_texels, t.position, t.normal, n_cov, p->first_sample, p->n_samples, p->key_base, c->cfg.n_sobol, p->bias, c->cfg.seed};
-        for (uint64_t first = 0; first < total; first += chunk)
-        {
-            const uint32_t cnt = (uint32_t)std::min<uint64_t>(chunk, total - first);
-            launch_lightmap_rays(c->stream, lb, first, cnt, d_o, d_d, d_key);
-            if ((r = integrate_rays_device(c, cnt, d_o, d_d, d_key, 1u, batch_rays, d_rad, nullptr, nullptr))) return r;
-            launch_lightmap_fold(c->stream, lb, first, cnt, d_rad, d_sum);
-            HIPCHK(c, hipGetLastError());
-        }
+        if ((r = bake_rays(c, st, n_cov, p->n_samples,
+                           [&](uint64_t first, uint32_t cnt, float* o, float* d, uint2* key) { launch_lightmap_rays(c->stream, lb, first, cnt, o, d, key); },
+                           [&](uint64_t first, uint32_t cnt, const float*, const f4* rad) { launch_lightmap_fold(c->stream, lb, first, cnt, rad, d_sum); })))
+            return r;
         if ((r = st.download(rgb_sum, d_sum, px * 12))) return r;
     }
     if (coverage) std::memcpy(coverage, cov.data(), px);

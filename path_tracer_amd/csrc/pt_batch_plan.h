@@ -1,4 +1,4 @@
-// How a render request is cut into batches of samples and spread over the wavefront pipelines (pt_api.cpp: render_batches), and how
+// How a render request is cut into batches of samples and spread over the wavefront pipelines (pt_api.cpp: run_batches), and how
 // many paths of wavefront state the device memory holds.  Plain arithmetic on a few integers, free of HIP so that the host sanitizer
 // driver (host_sanitize.cpp plan) can test it on the CPU.
 #pragma once

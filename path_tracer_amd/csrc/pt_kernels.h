@@ -204,14 +204,6 @@ void launch_denoise_albedo(hipStream_t s, int w, int h, const DenoiseK& p, const
                            const uint32_t* model, const f4* albedo, bool albedo_is_sum, f4* cv_a, f4* cv_b, f4* nv, f4* kd, f4* out);
 // the camera rays of sample rp.first_sample of every local pixel into a hook queue (ray index = local pixel), n_and_heads[0] <- local pixels
 void launch_guide_rays(hipStream_t s, const RenderParams& rp, const CameraView& cam, const CameraOptics& opt, RayQueue rq, uint32_t* n_and_heads);
-// their launch_trace_rays_closest hits -> position, normal, model guides
-void launch_guide_resolve(hipStream_t s, const SceneView& sv, uint32_t n, const CameraView& cam, const CameraOptics& opt, RayQueue rq, const f4* hits,
-                          f4* position, f4* normal, uint32_t* model, uint32_t* instance);
-// ... -> the albedo guide: the surface colour at the hit (an emissive hit: its emitted colour), (0, 0, 0) for a miss.  A launch of its own behind
-// the resolve, whose kernels and four guides stay what they were.  tex: the scene's texture view (all null for an untextured scene)
-void launch_guide_albedo(hipStream_t s, const SceneView& sv, const TexView& tex, uint32_t n, const f4* hits, f4* albedo);
-// pt_accumulate_albedo: sum[i] += (that sample's albedo guide, 1), with (1, 1, 1) for a miss; one thread per pixel, no atomics
-void launch_albedo_accumulate(hipStream_t s, const SceneView& sv, const TexView& tex, uint32_t n, const f4* hits, f4* sum);
 // unit hook (pt_surface_colour): rgb[i] <- surface colour of world instance[i], leaf-order triangle tri[i] at barycentrics u[i], v[i]
 void launch_surface_colour(hipStream_t s, const SceneView& sv, const TexView& tex, uint32_t n, const uint32_t* instance, const uint32_t* tri, const float* u,
                            const float* v, float* rgb);
@@ -221,16 +213,17 @@ void launch_shading_normal(hipStream_t s, const SceneView& sv, const TexNView& t
                            const float* v, const float* dir, float* out4);
 
 // unit hooks
-// pt_render_guides_followed / pt_accumulate_albedo_followed: hop `hop` of the guide chains.  `in`: the hook queue launch_trace_rays_closest just
-// traced into hits (n_in: its count word); chains that go on are appended to `next` (n_next: its count word, zero before the launch; both
-// queues hold cap slots).  sum null: a chain that ends writes the six guides of its pixel; else it adds its albedo product to sum[pixel]
+// pt_render_guides[_followed] / pt_accumulate_albedo[_followed]: hop `hop` of the guide chains (first-hit guides: max_hops 0).  `in`: the hook queue
+// launch_trace_rays_closest just traced into hits (n_in: its count word); chains that go on are appended to `next` (n_next: its count word, zero
+// before the launch; both queues hold cap slots; all null at the last hop, where no chain goes on).  sum null: a chain that ends writes the six
+// guides of its pixel; else it adds its albedo product to sum[pixel]
 struct FollowArgs
 {
     RayQueue in, next;
     const f4* hits;
     const uint32_t* n_in;
     uint32_t* n_next;
-    f4* state;             // per pixel: running albedo product | t sum of a chain that goes on
+    f4* state;             // per pixel: running albedo product | t sum of a chain that goes on (may be null at max_hops 0)
     f4 *position, *normal, *albedo;
     uint32_t *model, *instance;
     uint8_t* hops;

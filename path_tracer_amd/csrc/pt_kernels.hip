@@ -2944,91 +2944,28 @@ __global__ void __launch_bounds__(256) k_guide_rays_proj(const RenderParams rp, 
     rq.b[i] = f4{dir.x, dir.y, dir.z, asf(i)};
 }
 
-// first-hit guides of those rays: position r.at(t) | t as the render keeps it (r.at(1e5) | 1e5 for a miss, integrator.rs:156), the
-// face-forwarded world shading normal of the hit (HitInfo's, primitive.rs:161-165 + tlas.rs:105; 0 for a miss) and the hit's model
-// (BLAS index, MISS_ID for a miss) in full: its low byte is the id byte of main.rs:206; and the world-TLAS leaf of the hit in allocation
-// order (the index of pt_tlas_instances(ctx, 0, ..); MISS_ID for a miss), which pt_frame_moving reprojects a moved instance's pixels by
-// LENS (pt_set_lens, and pt_set_projection's rays, which are queued with their origins too): the ray's origin is its own (rq.a) instead of the eye
-template <bool LENS>
-__device__ __forceinline__ void guide_resolve_body(const SceneView& sv, const uint32_t n, const CameraView& cam, const RayQueue& rq, const f4* __restrict__ hits,
-                                                   f4* __restrict__ position, f4* __restrict__ normal, uint32_t* __restrict__ model,
-                                                   uint32_t* __restrict__ instance)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const f4 hit = hits[i];
-    const f3 d = xyz(rq.b[i]);
-    const f3 eye = LENS ? xyz(rq.a[i]) : f3{cam.eye[0], cam.eye[1], cam.eye[2]};
-    const uint32_t hid = asu(hit.w);
-    if (hid == MISS_ID)
-    {
-        const f3 far = fma3(d, bc3(1e5f), eye);
-        position[i] = f4{far.x, far.y, far.z, 1e5f};
-        normal[i] = f4{0.0f, 0.0f, 0.0f, 0.0f};
-        model[i] = MISS_ID;
-        instance[i] = MISS_ID;
-        return;
-    }
-    const uint32_t inst = hid >> sv.prim_bits, tri = hid & ((1u << sv.prim_bits) - 1u);
-    bool front;
-    const f3 nrm = hit_normal(sv, inst, tri, hit.y, hit.z, d, front);
-    const f3 p = fma3(d, bc3(hit.x), eye);
-    position[i] = f4{p.x, p.y, p.z, hit.x};
-    normal[i] = f4{nrm.x, nrm.y, nrm.z, 0.0f};
-    model[i] = sv.instances[inst].blas;
-    instance[i] = inst; // the world TLAS's records are the first of the instance array
-}
-__global__ void __launch_bounds__(256) k_guide_resolve(const SceneView sv, const uint32_t n, const CameraView cam, const RayQueue rq,
-                                                       const f4* __restrict__ hits, f4* __restrict__ position, f4* __restrict__ normal,
-                                                       uint32_t* __restrict__ model, uint32_t* __restrict__ instance)
-{
-    guide_resolve_body<false>(sv, n, cam, rq, hits, position, normal, model, instance);
-}
-__global__ void __launch_bounds__(256) k_guide_resolve_lens(const SceneView sv, const uint32_t n, const CameraView cam, const RayQueue rq,
-                                                            const f4* __restrict__ hits, f4* __restrict__ position, f4* __restrict__ normal,
-                                                            uint32_t* __restrict__ model, uint32_t* __restrict__ instance)
-{
-    guide_resolve_body<true>(sv, n, cam, rq, hits, position, normal, model, instance);
-}
-
-// the albedo guide of those hits and the unit hook of the surface colour: both over surface_colour (pt_materials.h), as the TEX shading passes are
+// the unit hook of the surface colour, over surface_colour (pt_materials.h) as the TEX shading passes and the guides are
 __device__ __forceinline__ f3 surface_colour_at(const SceneView& sv, const TexView& tex, uint32_t inst, uint32_t tri, float u, float v)
 {
     const DMaterial& dm = sv.materials[sv.instances[inst].material];
     return surface_colour(tex, dm.texture, f3{dm.colour[0], dm.colour[1], dm.colour[2]}, tri, u, v);
 }
-__global__ void __launch_bounds__(256) k_guide_albedo(const SceneView sv, const TexView tex, const uint32_t n, const f4* __restrict__ hits, f4* __restrict__ albedo)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const f4 hit = hits[i];
-    const uint32_t hid = asu(hit.w);
-    f3 c{0.0f, 0.0f, 0.0f};
-    if (hid != MISS_ID) c = surface_colour_at(sv, tex, hid >> sv.prim_bits, hid & ((1u << sv.prim_bits) - 1u), hit.y, hit.z);
-    albedo[i] = f4{c.x, c.y, c.z, 0.0f};
-}
-// pt_accumulate_albedo: the albedo guide of one more sample added to the pixel's sums (r, g, b, n), one binary32 add per component; a miss adds
-// (1, 1, 1), so that the background passes the demodulation undivided.  One thread owns a pixel and launches follow each other in sample
-// order on one stream: no atomics, and the order of a pixel's adds is the order of its samples.
-__global__ void __launch_bounds__(256) k_albedo_accumulate(const SceneView sv, const TexView tex, const uint32_t n, const f4* __restrict__ hits, f4* __restrict__ sum)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const f4 hit = hits[i];
-    const uint32_t hid = asu(hit.w);
-    f3 c{1.0f, 1.0f, 1.0f};
-    if (hid != MISS_ID) c = surface_colour_at(sv, tex, hid >> sv.prim_bits, hid & ((1u << sv.prim_bits) - 1u), hit.y, hit.z);
-    const f4 s = sum[i];
-    sum[i] = f4{s.x + c.x, s.y + c.y, s.z + c.z, s.w + 1.0f};
-}
-// ---- followed guides (pt_render_guides_followed, pt_accumulate_albedo_followed; include/pt_api.h states the chain)
+// ---- the guides (pt_render_guides, pt_render_guides_followed, pt_accumulate_albedo[_followed]; include/pt_api.h states the chain)
 // Hop a.hop of every live chain: one thread per ray slot of the `in` hook queue (slot = local pixel at hop 0, compacted afterwards; the
-// ray's pixel rides in rq.b[].w), its closest hit in hits[slot].  A chain that ends here (a miss, a rough surface, the hop cap) writes
-// its pixel's final guides (ACCUM: adds its albedo product to the pixel's mean-albedo sums, one thread owning the pixel as in
-// k_albedo_accumulate); one that goes on parks its running albedo product | t sum in state[pixel] and appends ray hop + 1 to the `next`
-// queue: one ballot and one atomic on the queue's count word per wave, the lane's rank by mbcnt.  That word is what the next hop's
-// k_closest and k_guide_follow read as their ray count, so nothing comes back to the host between hops.  Where a chain lands in `next`
-// shows in nothing it writes: every output is addressed by pixel.
+// ray's pixel rides in rq.b[].w, its origin in rq.a[]), its closest hit in hits[slot].  A chain that ends here (a miss, a rough surface,
+// the hop cap) writes its pixel's final guides: position r.at(t) | t as the render keeps it (r.at(1e5) | 1e5 for a miss,
+// integrator.rs:156; t summed over the hops), the face-forwarded world shading normal of the hit (HitInfo's, primitive.rs:161-165 +
+// tlas.rs:105; 0 for a miss), the hit's model (BLAS index, its hop count in bits 31..28; MISS_ID for a miss: the low byte is the id byte
+// of main.rs:206), the world-TLAS leaf of the hit in allocation order (the index of pt_tlas_instances(ctx, 0, ..); MISS_ID for a miss),
+// which pt_frame_moving reprojects a moved instance's pixels by, the albedo product (0 for a miss) and the hop count.  ACCUM: it adds its
+// albedo product and 1 to the pixel's mean-albedo sums instead, one binary32 add per component and (1, 1, 1) for a miss, so that the
+// background passes the demodulation undivided; one thread owns a pixel and launches follow each other in sample order on one stream: no
+// atomics, and the order of a pixel's adds is the order of its samples.  A chain that goes on parks its running albedo product | t sum in
+// state[pixel] and appends ray hop + 1 to the `next` queue: one ballot and one atomic on the queue's count word per wave, the lane's rank
+// by mbcnt.  That word is what the next hop's k_closest and k_guide_follow read as their ray count, so nothing comes back to the host
+// between hops.  Where a chain lands in `next` shows in nothing it writes: every output is addressed by pixel.
+// First-hit guides are the chains of max_hops = 0.  At the last hop (a.hop == a.max_hops) no lane goes on, so `next` and n_next are never
+// dereferenced, and hop 0 never reads `state`: the host passes null for what a launch cannot touch (all three at max_hops = 0).
 template <bool ACCUM, bool FIRST>
 __global__ void __launch_bounds__(256, 8) k_guide_follow(const SceneView sv, const TexView tex, const FollowArgs a)
 {
@@ -3638,23 +3575,6 @@ void launch_guide_rays(hipStream_t s, const RenderParams& rp, const CameraView& 
     }
     else if (lens_set(opt.lens)) hipLaunchKernelGGL(k_guide_rays_lens, dim3((rp.local_pixels + 255u) / 256u), dim3(256), 0, s, rp, cam, opt.lens, rq, n_and_heads);
     else hipLaunchKernelGGL(k_guide_rays, dim3((rp.local_pixels + 255u) / 256u), dim3(256), 0, s, rp, cam, rq, n_and_heads);
-}
-void launch_guide_resolve(hipStream_t s, const SceneView& sv, uint32_t n, const CameraView& cam, const CameraOptics& opt, RayQueue rq, const f4* hits, f4* position,
-                          f4* normal, uint32_t* model, uint32_t* instance)
-{
-    if (lens_set(opt.lens) || proj_set(opt.proj)) hipLaunchKernelGGL(k_guide_resolve_lens, dim3((n + 255u) / 256u), dim3(256), 0, s, sv, n, cam, rq, hits, position, normal, model, instance);
-    else hipLaunchKernelGGL(k_guide_resolve, dim3((n + 255u) / 256u), dim3(256), 0, s, sv, n, cam, rq, hits, position, normal, model, instance);
-}
-
-void launch_guide_albedo(hipStream_t s, const SceneView& sv, const TexView& tex, uint32_t n, const f4* hits, f4* albedo)
-{
-    if (n == 0u) return;
-    hipLaunchKernelGGL(k_guide_albedo, dim3((n + 255u) / 256u), dim3(256), 0, s, sv, tex, n, hits, albedo);
-}
-void launch_albedo_accumulate(hipStream_t s, const SceneView& sv, const TexView& tex, uint32_t n, const f4* hits, f4* sum)
-{
-    if (n == 0u) return;
-    hipLaunchKernelGGL(k_albedo_accumulate, dim3((n + 255u) / 256u), dim3(256), 0, s, sv, tex, n, hits, sum);
 }
 void launch_guide_follow(hipStream_t s, const SceneView& sv, const TexView& tex, const FollowArgs& a)
 {
