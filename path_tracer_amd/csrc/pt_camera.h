@@ -1,7 +1,8 @@
 // The camera ray of (pixel, sample): one definition for the gfx950 kernels and for the host evaluation (pt_primary_ray).
 // Pinhole: main.rs:193-199 + Camera::create_ray camera.rs:94-105.  Thin lens: include/pt_api.h, pt_set_lens.  Panoramic and orthographic:
-// include/pt_api.h, pt_set_projection.
+// include/pt_api.h, pt_set_projection.  primary_ray at the end is the one entry the kernels use: the camera's kind is the type of its view.
 #pragma once
+#include <type_traits>
 #include "pt_types.h"
 
 namespace pt {
@@ -111,6 +112,37 @@ PT_HD f3 camera_ray_projected(const RenderParams& rp, const CameraView& cam, con
 {
     return proj.kind == PROJ_PANORAMA ? camera_ray_panorama(rp, cam, proj, gx, gy, sample, origin)
                                       : camera_ray_orthographic(rp, cam, proj, gx, gy, sample, origin);
+}
+
+// ---- the camera kind as one axis.  A kernel that makes camera rays takes ONE camera argument whose type says which ray it makes: the
+// pinhole's CameraView alone, or the view with the lens or the projection constants behind it (all float / uint32_t: the argument lays out as
+// the pair of views would).  The host derives the kind from CameraOptics (camera_kind, pt_kernels.h) once per launch.
+enum CameraKind : uint32_t { CAM_PINHOLE, CAM_LENS, CAM_PANORAMA, CAM_ORTHOGRAPHIC, CAM_KINDS, CAM_BY_VIEW = CAM_KINDS };
+struct CameraLensView : CameraView { LensView lens; };
+struct CameraProjView : CameraView { ProjView proj; };
+template <uint32_t KIND>
+using CameraArg = std::conditional_t<KIND == CAM_PINHOLE, CameraView, std::conditional_t<KIND == CAM_LENS, CameraLensView, CameraProjView>>;
+
+// The camera ray of (pixel gx, gy; sample) by the type of `cam`: its direction, and its origin in *origin (the pinhole's and the panorama's is
+// the eye).  KIND is read by the projection overload only: CAM_PANORAMA / CAM_ORTHOGRAPHIC where the caller was built for one of them (the
+// panorama's two sincos_det are then not in the orthographic kernel), CAM_BY_VIEW to go by cam.proj.kind (launch-invariant: the branch is uniform)
+template <uint32_t KIND = CAM_BY_VIEW>
+PT_HD f3 primary_ray(const RenderParams& rp, const CameraView& cam, uint32_t gx, uint32_t gy, uint32_t sample, f3* origin)
+{
+    *origin = f3{cam.eye[0], cam.eye[1], cam.eye[2]};
+    return camera_ray_dir(rp, cam, gx, gy, sample);
+}
+template <uint32_t KIND = CAM_BY_VIEW>
+PT_HD f3 primary_ray(const RenderParams& rp, const CameraLensView& cam, uint32_t gx, uint32_t gy, uint32_t sample, f3* origin)
+{
+    return camera_ray(rp, cam, cam.lens, gx, gy, sample, origin);
+}
+template <uint32_t KIND = CAM_BY_VIEW>
+PT_HD f3 primary_ray(const RenderParams& rp, const CameraProjView& cam, uint32_t gx, uint32_t gy, uint32_t sample, f3* origin)
+{
+    if (KIND == CAM_PANORAMA) return camera_ray_panorama(rp, cam, cam.proj, gx, gy, sample, origin);
+    if (KIND == CAM_ORTHOGRAPHIC) return camera_ray_orthographic(rp, cam, cam.proj, gx, gy, sample, origin);
+    return camera_ray_projected(rp, cam, cam.proj, gx, gy, sample, origin);
 }
 
 } // namespace pt

@@ -1,8 +1,8 @@
 // gfx950 (MI355X, wave64) kernels of the wavefront path tracer.
 //
-//   k_generate      main.rs:186-199   seed draw, shuffled-scrambled Sobol jitter, camera ray (pt_camera.h; k_generate_lens and the LENS
-//                   instantiations below: the thin lens of pt_set_lens, whose camera rays have origins of their own; k_generate_proj and the
-//                   ONE_DRAW / PROJ instantiations: the panoramic and orthographic cameras of pt_set_projection, which ride on the lens's)
+//   k_generate      main.rs:186-199   seed draw, shuffled-scrambled Sobol jitter, camera ray (pt_camera.h: primary_ray by the camera kind CAM --
+//                   pinhole, the thin lens of pt_set_lens, the panoramic and orthographic cameras of pt_set_projection; the last three's
+//                   rays have origins of their own, which bounce 0's FIRST_OWN_* variants of the passes below read)
 //   k_closest       tlas.rs:66-110 + blas.rs:214-256 + boundingbox.rs:115-131 + primitive.rs:117-178
 //                   persistent-threads ordered traversal; BVH staged in LDS; per-lane stack in LDS;
 //                   ballot/mbcnt refill of idle lanes from the ray queue; material binning of the hits;
@@ -21,6 +21,8 @@
 #include "pt_materials.h"
 
 #include <algorithm>
+#include <cstdio>
+#include <cstdlib>
 #include <mutex>
 #include <type_traits>
 #include <vector>
@@ -1673,60 +1675,20 @@ __device__ __forceinline__ PixelId path_pixel_list(const RenderParams& rp, const
     return PixelId{gy * rp.width + x, e.y + rp.first_sample + pp.s, e.x, x, gy};
 }
 
-// main.rs:186-199
-__global__ void __launch_bounds__(256) k_generate(const RenderParams rp, const CameraView cam, const RayQueue rq, Counters* ctr)
-{
-    const uint32_t pid = blockIdx.x * blockDim.x + threadIdx.x;
-    if (pid == 0u) ctr[0].n_closest = rp.n_paths;
-    if (pid >= rp.n_paths) return;
-    const PixelId px = path_pixel(rp, pid);
-    const f3 dir = camera_ray_dir(rp, cam, px.gx, px.gy, px.sample);
-    rq.b[pid] = f4{dir.x, dir.y, dir.z, asf(pid)};
-    // no state is initialised: bounce 0 knows path_weight = 1, accumulated = 0, one draw consumed (integrator.rs:153-161)
-}
-
-// k_generate over an adaptive list (path_pixel_list)
-__global__ void __launch_bounds__(256) k_generate_list(const RenderParams rp, const CameraView cam, const RayQueue rq, Counters* ctr, const uint2* __restrict__ list)
-{
-    const uint32_t pid = blockIdx.x * blockDim.x + threadIdx.x;
-    if (pid == 0u) ctr[0].n_closest = rp.n_paths;
-    if (pid >= rp.n_paths) return;
-    const PixelId px = path_pixel_list(rp, list, pid);
-    const f3 dir = camera_ray_dir(rp, cam, px.gx, px.gy, px.sample);
-    rq.b[pid] = f4{dir.x, dir.y, dir.z, asf(pid)};
-}
-
-// thin lens (pt_set_lens): every camera ray has an origin of its own on the lens disk, stored beside its direction; bounce 0 then knows
-// TWO draws consumed.  LIST: over an adaptive list, as k_generate_list
-template <bool LIST>
-__global__ void __launch_bounds__(256) k_generate_lens(const RenderParams rp, const CameraView cam, const LensView lens, const RayQueue rq, Counters* ctr,
-                                                        const uint2* __restrict__ list)
+// main.rs:186-199.  CAM (CameraKind, pt_camera.h): the camera ray is primary_ray's for the kind.  Every kind but the pinhole stores the ray's
+// origin beside its direction (a lens ray's and an orthographic ray's are their own; a panorama's is the eye, so that both projections run one
+// set of bounce-0 kernels); the pinhole's bounce 0 knows the eye.  No state is initialised: bounce 0 knows path_weight = 1, accumulated = 0
+// and the draws consumed (integrator.rs:153-161; the lens TWO, the others ONE).  LIST: over an adaptive list (path_pixel_list)
+template <uint32_t CAM, bool LIST>
+__global__ void __launch_bounds__(256) k_generate(const RenderParams rp, const CameraArg<CAM> cam, const RayQueue rq, Counters* ctr, const uint2* __restrict__ list)
 {
     const uint32_t pid = blockIdx.x * blockDim.x + threadIdx.x;
     if (pid == 0u) ctr[0].n_closest = rp.n_paths;
     if (pid >= rp.n_paths) return;
     const PixelId px = LIST ? path_pixel_list(rp, list, pid) : path_pixel(rp, pid);
     f3 o;
-    const f3 dir = camera_ray(rp, cam, lens, px.gx, px.gy, px.sample, &o);
-    rq.a[pid] = f4{o.x, o.y, o.z, __builtin_inff()};
-    rq.b[pid] = f4{dir.x, dir.y, dir.z, asf(pid)};
-}
-
-// panoramic and orthographic cameras (pt_set_projection; KIND = PROJ_PANORAMA / PROJ_ORTHOGRAPHIC): the ray's origin is stored beside its
-// direction as the lens's is (an orthographic ray's is its own; a panorama's is the eye, so that both run one set of bounce-0 kernels) and
-// bounce 0 knows ONE draw consumed.  A kernel per kind: the panorama's two sincos_det are not in the orthographic kernel.
-template <bool LIST, uint32_t KIND>
-__global__ void __launch_bounds__(256) k_generate_proj(const RenderParams rp, const CameraView cam, const ProjView proj, const RayQueue rq, Counters* ctr,
-                                                        const uint2* __restrict__ list)
-{
-    const uint32_t pid = blockIdx.x * blockDim.x + threadIdx.x;
-    if (pid == 0u) ctr[0].n_closest = rp.n_paths;
-    if (pid >= rp.n_paths) return;
-    const PixelId px = LIST ? path_pixel_list(rp, list, pid) : path_pixel(rp, pid);
-    f3 o;
-    const f3 dir = KIND == PROJ_PANORAMA ? camera_ray_panorama(rp, cam, proj, px.gx, px.gy, px.sample, &o)
-                                         : camera_ray_orthographic(rp, cam, proj, px.gx, px.gy, px.sample, &o);
-    rq.a[pid] = f4{o.x, o.y, o.z, __builtin_inff()};
+    const f3 dir = primary_ray<CAM>(rp, cam, px.gx, px.gy, px.sample, &o);
+    if (CAM != CAM_PINHOLE) rq.a[pid] = f4{o.x, o.y, o.z, __builtin_inff()};
     rq.b[pid] = f4{dir.x, dir.y, dir.z, asf(pid)};
 }
 
@@ -1763,8 +1725,8 @@ struct ShadeIO
     union
     {
         const uint2* entries; // terminal pass: {ray index | ENTRY_DEAD, path id}
-        const uint2* list;    // surface passes of an adaptive render (k_shade_surface<..., LIST>): the list's {local pixel, n_p} entries;
-                              // of a ray batch (k_shade_surface<..., RAYS>): the window's {pixel, sample} stream keys (RayView::key)
+        const uint2* list;    // surface passes of an adaptive render (k_shade_surface<.., PATHS_LIST, ..>): the list's {local pixel, n_p} entries;
+                              // of a ray batch (k_shade_surface<.., PATHS_RAYS, ..>): the window's {pixel, sample} stream keys (RayView::key)
     };
     ShadeQueue q_in;          // surface pass: this class's hit records in queue order
     const uint32_t* tails_in; // ... and the queue's striped tails
@@ -1925,7 +1887,7 @@ __global__ void __launch_bounds__(256) k_shade_terminal(const SceneView sv, cons
 }
 
 // TLAS::any_intersect for ONE ray per lane, run by the whole wave until its last ray is done (no refill): the shading pass of an LDS-resident scene
-// answers its own explicit-light shadow ray with it (k_shade_surface<.., INLINE>).  Steps as in any_body: a node's box is tested when its parent is
+// answers its own explicit-light shadow ray with it (k_shade_surface<.., SHADOW_INLINE.., ..>).  Steps as in any_body: a node's box is tested when its parent is
 // expanded, only nodes that were met go on the stack; the answer is a disjunction, so the order cannot change it.
 template <bool IDENT>
 __device__ __forceinline__ bool inline_any(const Blob& bl, const Stack8<false>& stk, const uint32_t root, const f4 ra, const f4 rb, const bool want)
@@ -2057,12 +2019,26 @@ __device__ __forceinline__ const TexNView& shade_args_texn()
     [[maybe_unused]] const SceneView& sv = ka_.sv;                                                                                 \
     [[maybe_unused]] const RenderParams& rp = ka_.rp;                                                                              \
     [[maybe_unused]] const ShadeIO& io = ka_.io;
-// LIST (pt_render_adaptive): path ids index the adaptive list (ShadeIO::list, path_pixel_list) instead of the active rectangle
-// LENS (pt_set_lens; launched for bounce 0 only): the camera ray's origin comes with its record (ShadeQueue::c) and two draws are consumed
-// ONE_DRAW (pt_set_projection; with LENS): a panoramic or orthographic camera ray has an origin of its own like a lens ray and consumed one draw
-// RAYS (pt_integrate_rays): the path's stream is the one its entry of the ray table names (path_pixel_rays) and bounce 0 (launched with LENS: the
-// ray's origin is its own) starts at RenderParams::ray_draws draws
-// TEX (a built scene with a textured material; never with INLINE): the colour of the material at the hit is the surface colour (surface_colour,
+// The variants of the pass are the points of six axes (DESIGN.md has the table; QCLASS is the queue class Q_LAMBERT .. Q_GGX):
+enum ShadeMedia : uint32_t { MEDIA_NONE, MEDIA_VOLUMES, MEDIA_COUNT };                    // SceneView::has_volumes
+enum ShadeShadow : uint32_t { SHADOW_QUEUED, SHADOW_INLINE, SHADOW_INLINE_IDENT, SHADOW_COUNT }; // the explicit-light shadow ray: queued for k_any<SHADOW>, walked here (inline_any), walked here with one ray (ident_ray)
+enum ShadePaths : uint32_t { PATHS_RECT, PATHS_LIST, PATHS_RAYS, PATHS_COUNT };           // path ids index the active rectangle, an adaptive list (ShadeIO::list, path_pixel_list) or a ray table (path_pixel_rays)
+enum ShadeFirst : uint32_t { FIRST_SHARED, FIRST_OWN_TWO_DRAWS, FIRST_OWN_ONE_DRAW, FIRST_COUNT }; // the ray's origin is the eye's / the queue's own (every bounce but 0; bounce 0 of the pinhole), or comes with its record at bounce 0:
+                                                                                         // a lens ray (two draws consumed; a ray table's: rp.ray_draws), a projected ray (one)
+enum ShadeSurface : uint32_t { SURF_PLAIN, SURF_TEX, SURF_TEX_EMTEX, SURF_TEX_NMAP, SURF_TEX_EMTEX_NMAP, SURF_COUNT };
+constexpr bool surf_emtex(uint32_t surface) { return surface == SURF_TEX_EMTEX || surface == SURF_TEX_EMTEX_NMAP; }
+constexpr bool surf_nmap(uint32_t surface) { return surface == SURF_TEX_NMAP || surface == SURF_TEX_EMTEX_NMAP; }
+// the points that exist: the inline walk is the untextured Lambertian pass's of a scene without media (shade_traces_shadow: a textured scene
+// queues its shadow rays), and a ray table's bounce 0 takes its draw count from the launch, never "one"
+constexpr bool shade_variant_ok(uint32_t q, uint32_t media, uint32_t shadow, uint32_t paths, uint32_t first, uint32_t surface)
+{
+    return q != Q_TERMINAL && q < Q_COUNT && media < MEDIA_COUNT && shadow < SHADOW_COUNT && paths < PATHS_COUNT && first < FIRST_COUNT && surface < SURF_COUNT &&
+           (shadow == SHADOW_QUEUED || (q == Q_LAMBERT && media == MEDIA_NONE && surface == SURF_PLAIN)) && !(paths == PATHS_RAYS && first == FIRST_OWN_ONE_DRAW);
+}
+// the argument follows from SURFACE: the texture view, and behind it the tangents, ride behind the launch description
+template <uint32_t SURFACE>
+using ShadeArg = std::conditional_t<surf_nmap(SURFACE), ShadeKArgsNmap, std::conditional_t<SURFACE != SURF_PLAIN, ShadeKArgsTex, ShadeKArgs>>;
+// SURF_TEX.. (a built scene with a textured material): the colour of the material at the hit is the surface colour (surface_colour,
 // pt_materials.h).  The lookup is a chain of dependent loads (instance -> material -> UVs and table -> four texels).  It sits where the
 // material is loaded, behind the NEE resolve: every TEX variant then has the registers, the scratch and the waves of its untextured twin.
 // PT_TEX_EARLY=1 starts it right behind the path record's loads instead, so that the two wait for memory together; the colour is then live
@@ -2071,21 +2047,18 @@ __device__ __forceinline__ const TexNView& shade_args_texn()
 #ifndef PT_TEX_EARLY
 #define PT_TEX_EARLY 0
 #endif
-// EMTEX (with TEX: some emissive material has an emission texture, pt_set_material_emission_texture): the emitted colour of a light is its
-// surface colour too, at the point the explicit estimate sampled and at the light hit of the resolve (resolve_nee<true>).  A parameter of its
-// own: the TEX variants of a scene whose lights are untextured stay the kernels they were.
-// NMAP (with TEX: some material has a normal map, pt_set_material_normal_texture): the shading normal of the hit is shading_normal
-// (pt_materials.h), the interpolated normal perturbed by the map's texel in the triangle's tangent frame; `front` stays the unperturbed normal's.
-// The lookup is a second chain of the same kind (instance -> material -> UVs / tangent / table -> four texels) and sits where hit_normal sits,
-// right behind the colour lookup.  A parameter of its own like EMTEX: every other variant stays the kernel it was.
-template <uint32_t QCLASS, bool VOLUMES, bool INLINE = false, bool IDENT = false, bool LIST = false, bool LENS = false, bool RAYS = false, bool TEX = false,
-          bool ONE_DRAW = false, bool EMTEX = false, bool NMAP = false>
-__global__ void __launch_bounds__(PT_SHADE_THREADS, INLINE ? PT_SHADE_WAVES_INLINE : shade_waves(QCLASS, VOLUMES))
-k_shade_surface(const std::conditional_t<NMAP, ShadeKArgsNmap, std::conditional_t<TEX, ShadeKArgsTex, ShadeKArgs>> kargs)
+// ..EMTEX (some emissive material has an emission texture): a light's emitted colour is its surface colour too, at the point the explicit
+// estimate sampled and at the light hit of the resolve (resolve_nee<true>).  ..NMAP (some material has a normal map): the shading normal is
+// shading_normal (pt_materials.h), a second chain of the same kind right behind the colour lookup; `front` stays the unperturbed normal's.
+// Each is a value of its own: the TEX variants of a scene without textured lights or normal maps stay the kernels they were.
+template <uint32_t QCLASS, uint32_t MEDIA, uint32_t SHADOW, uint32_t PATHS, uint32_t FIRST, uint32_t SURFACE>
+__global__ void __launch_bounds__(PT_SHADE_THREADS, SHADOW != SHADOW_QUEUED ? PT_SHADE_WAVES_INLINE : shade_waves(QCLASS, MEDIA == MEDIA_VOLUMES))
+k_shade_surface(const ShadeArg<SURFACE> kargs)
 {
-    static_assert(!(TEX && INLINE), "textured scenes queue their shadow rays");
-    static_assert(TEX || !EMTEX, "an emission texture makes a textured scene");
-    static_assert(TEX || !NMAP, "a normal map makes a textured scene");
+    static_assert(shade_variant_ok(QCLASS, MEDIA, SHADOW, PATHS, FIRST, SURFACE), "no such variant of the surface pass");
+    constexpr bool VOLUMES = MEDIA == MEDIA_VOLUMES, INLINE = SHADOW != SHADOW_QUEUED, IDENT = SHADOW == SHADOW_INLINE_IDENT;
+    constexpr bool LIST = PATHS == PATHS_LIST, RAYS = PATHS == PATHS_RAYS, LENS = FIRST != FIRST_SHARED, ONE_DRAW = FIRST == FIRST_OWN_ONE_DRAW;
+    constexpr bool TEX = SURFACE != SURF_PLAIN, EMTEX = surf_emtex(SURFACE), NMAP = surf_nmap(SURFACE);
     extern __shared__ uint4 smem_dyn[];
     // Only what the loop header needs is taken from the argument here; each section of an iteration re-reads the launch description from
     // the kernel-argument segment (PT_SHADE_ARGS: scalar loads that hit the constant cache) instead of keeping ~130 words of it in ~100
@@ -2464,25 +2437,12 @@ k_shade_surface(const std::conditional_t<NMAP, ShadeKArgsNmap, std::conditional_
 
 #undef PT_SHADE_ARGS
 
-// position r.at(1e5) of a camera ray that left the scene at once (integrator.rs:156), pinhole and thin lens
-struct CameraLensView : CameraView { LensView lens; };
-struct CameraProjView : CameraView { ProjView proj; };
-__device__ __forceinline__ f3 miss_position(const RenderParams& rp, const CameraView& cam, uint32_t gx, uint32_t gy, uint32_t sample)
-{
-    const f3 d = camera_ray_dir(rp, cam, gx, gy, sample);
-    return fma3(d, bc3(1e5f), f3{cam.eye[0], cam.eye[1], cam.eye[2]});
-}
-__device__ __forceinline__ f3 miss_position(const RenderParams& rp, const CameraLensView& cam, uint32_t gx, uint32_t gy, uint32_t sample)
+// position r.at(1e5) of a camera ray that left the scene at once (integrator.rs:156), for whichever camera view it is given
+template <typename CAM>
+__device__ __forceinline__ f3 miss_position(const RenderParams& rp, const CAM& cam, uint32_t gx, uint32_t gy, uint32_t sample)
 {
     f3 o;
-    const f3 d = camera_ray(rp, cam, cam.lens, gx, gy, sample, &o);
-    return fma3(d, bc3(1e5f), o);
-}
-// ... panoramic and orthographic (pt_set_projection): the kind is launch-invariant, the branch uniform
-__device__ __forceinline__ f3 miss_position(const RenderParams& rp, const CameraProjView& cam, uint32_t gx, uint32_t gy, uint32_t sample)
-{
-    f3 o;
-    const f3 d = camera_ray_projected(rp, cam, cam.proj, gx, gy, sample, &o);
+    const f3 d = primary_ray(rp, cam, gx, gy, sample, &o);
     return fma3(d, bc3(1e5f), o);
 }
 
@@ -2509,12 +2469,11 @@ __device__ __forceinline__ float luminance(float r, float g, float b) { return (
 // sample.  LIST (pt_render_adaptive): one thread (quad) per entry of the adaptive list instead of per local pixel; unlisted pixels are
 // not touched, and entry k's sample s is the pixel's sample n_p + first_sample + s (path_pixel_list).
 //
-// LENS (pt_set_lens): the camera ray of a miss is the lens ray, so r.at(1e5) starts at its point of the lens disk.  The lens rides behind
-// the camera in the LENS instantiations' camera argument only (CameraLensView): the pinhole instantiations' arguments are what they were.
-// PROJ (pt_set_projection): likewise the panoramic or orthographic ray, whose constants ride behind the camera (CameraProjView)
-template <bool FEW_PIXELS, bool MOMENTS = false, bool LIST = false, bool LENS = false, bool PROJ = false>
-__global__ void __launch_bounds__(256) k_accumulate(const RenderParams rp,
-                                                     const std::conditional_t<PROJ, CameraProjView, std::conditional_t<LENS, CameraLensView, CameraView>> cam, const PathState st,
+// CAM (CameraView, CameraLensView or CameraProjView: pt_camera.h): the camera ray of a miss is that view's, so r.at(1e5) starts at the lens
+// ray's point of the lens disk or at the projected ray's origin.  The lens or the projection rides behind the camera in that argument only:
+// the pinhole instantiations' arguments are what they were.
+template <typename CAM, bool FEW_PIXELS, bool MOMENTS = false, bool LIST = false>
+__global__ void __launch_bounds__(256) k_accumulate(const RenderParams rp, const CAM cam, const PathState st,
                                                      f4* accum, f4* position, uint32_t* id, const uint32_t write_position, const uint32_t add_to_accum,
                                                      float* moments, const uint2* list)
 {
@@ -2904,42 +2863,16 @@ __global__ void k_bsdf_probe(const SceneView sv, int material, uint32_t n, const
 
 // ------------------------------------------------------------------------------------------------ denoiser guides (pt_render_guides)
 // The camera ray of sample rp.first_sample of EVERY local pixel (no active rectangle: a ray outside it is answered by the root-box test)
-// as one ray of a hook queue, ray index = local pixel: exactly the ray k_generate makes for that (pixel, sample).
-__global__ void __launch_bounds__(256) k_guide_rays(const RenderParams rp, const CameraView cam, const RayQueue rq, uint32_t* __restrict__ n_and_heads)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i == 0u) n_and_heads[0] = rp.local_pixels;
-    if (i >= rp.local_pixels) return;
-    const uint32_t ly = fastdiv(i, rp.div_width), x = i - ly * rp.width;
-    const f3 dir = camera_ray_dir(rp, cam, x, global_row(rp, ly), rp.first_sample);
-    rq.a[i] = f4{cam.eye[0], cam.eye[1], cam.eye[2], __builtin_inff()};
-    rq.b[i] = f4{dir.x, dir.y, dir.z, asf(i)};
-}
-// thin lens (pt_set_lens): the lens ray k_generate_lens makes for that (pixel, sample)
-__global__ void __launch_bounds__(256) k_guide_rays_lens(const RenderParams rp, const CameraView cam, const LensView lens, const RayQueue rq,
-                                                          uint32_t* __restrict__ n_and_heads)
+// as one ray of a hook queue, ray index = local pixel: exactly the ray k_generate<CAM> makes for that (pixel, sample).
+template <uint32_t CAM>
+__global__ void __launch_bounds__(256) k_guide_rays(const RenderParams rp, const CameraArg<CAM> cam, const RayQueue rq, uint32_t* __restrict__ n_and_heads)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i == 0u) n_and_heads[0] = rp.local_pixels;
     if (i >= rp.local_pixels) return;
     const uint32_t ly = fastdiv(i, rp.div_width), x = i - ly * rp.width;
     f3 o;
-    const f3 dir = camera_ray(rp, cam, lens, x, global_row(rp, ly), rp.first_sample, &o);
-    rq.a[i] = f4{o.x, o.y, o.z, __builtin_inff()};
-    rq.b[i] = f4{dir.x, dir.y, dir.z, asf(i)};
-}
-// panoramic and orthographic cameras (pt_set_projection): the ray k_generate_proj<.., KIND> makes for that (pixel, sample)
-template <uint32_t KIND>
-__global__ void __launch_bounds__(256) k_guide_rays_proj(const RenderParams rp, const CameraView cam, const ProjView proj, const RayQueue rq,
-                                                          uint32_t* __restrict__ n_and_heads)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i == 0u) n_and_heads[0] = rp.local_pixels;
-    if (i >= rp.local_pixels) return;
-    const uint32_t ly = fastdiv(i, rp.div_width), x = i - ly * rp.width;
-    f3 o;
-    const f3 dir = KIND == PROJ_PANORAMA ? camera_ray_panorama(rp, cam, proj, x, global_row(rp, ly), rp.first_sample, &o)
-                                         : camera_ray_orthographic(rp, cam, proj, x, global_row(rp, ly), rp.first_sample, &o);
+    const f3 dir = primary_ray<CAM>(rp, cam, x, global_row(rp, ly), rp.first_sample, &o);
     rq.a[i] = f4{o.x, o.y, o.z, __builtin_inff()};
     rq.b[i] = f4{dir.x, dir.y, dir.z, asf(i)};
 }
@@ -3093,23 +3026,48 @@ __global__ void __launch_bounds__(256) k_shading_normal(const SceneView sv, cons
 } // namespace
 
 // ================================================================================================ launchers
+// A launcher decides each axis of its kernel's variant once, as a plain integer, and turns the integers into template arguments here:
+// f(std::integral_constant<uint32_t, value>{}) for a value below N ...
+template <uint32_t N, typename F>
+static void pick(uint32_t value, F&& f)
+{
+    if constexpr (N > 1u)
+        if (value != N - 1u) return pick<N - 1u>(value, f);
+    f(std::integral_constant<uint32_t, N - 1u>{});
+}
+// ... and f(constant...) for one value per axis, value[k] below the k-th N
+template <uint32_t... N, typename F, typename... C>
+static void pick_axes(const uint32_t (&value)[sizeof...(N)], F&& f, C... held)
+{
+    [[maybe_unused]] constexpr uint32_t bound[] = {N...};
+    constexpr size_t k = sizeof...(C);
+    if constexpr (k == sizeof...(N)) f(held...);
+    else pick<bound[k]>(value[k], [&](auto c) { pick_axes<N...>(value, f, held..., c); });
+}
+
+// How a camera kind reaches a kernel: camera_kind reads it off the optics, pick makes it a constant, camera_arg builds the one argument of
+// that kind (CameraArg, pt_camera.h) and the kernel's primary_ray overload is chosen by the argument's type.
+static uint32_t camera_kind(const CameraOptics& opt)
+{
+    if (proj_set(opt.proj)) return opt.proj.kind == PROJ_PANORAMA ? CAM_PANORAMA : CAM_ORTHOGRAPHIC;
+    return lens_set(opt.lens) ? CAM_LENS : CAM_PINHOLE;
+}
+template <uint32_t KIND>
+static CameraArg<KIND> camera_arg(const CameraView& cam, const CameraOptics& opt)
+{
+    CameraArg<KIND> c{};
+    static_cast<CameraView&>(c) = cam;
+    if constexpr (KIND == CAM_LENS) c.lens = opt.lens;
+    else if constexpr (KIND != CAM_PINHOLE) c.proj = opt.proj;
+    return c;
+}
+
 void launch_generate(hipStream_t s, const RenderParams& rp, const CameraView& cam, const CameraOptics& opt, const WavefrontBuffers& wb, const uint2* list)
 {
     const uint32_t blocks = (rp.n_paths + 255u) / 256u;
-    if (proj_set(opt.proj))
-    {
-        auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, s, rp, cam, opt.proj, wb.rq[0], wb.counters, list); };
-        if (opt.proj.kind == PROJ_PANORAMA) list ? go(k_generate_proj<true, PROJ_PANORAMA>) : go(k_generate_proj<false, PROJ_PANORAMA>);
-        else list ? go(k_generate_proj<true, PROJ_ORTHOGRAPHIC>) : go(k_generate_proj<false, PROJ_ORTHOGRAPHIC>);
-    }
-    else if (lens_set(opt.lens))
-    {
-        const LensView& lens = opt.lens;
-        if (list) hipLaunchKernelGGL(k_generate_lens<true>, dim3(blocks), dim3(256), 0, s, rp, cam, lens, wb.rq[0], wb.counters, list);
-        else hipLaunchKernelGGL(k_generate_lens<false>, dim3(blocks), dim3(256), 0, s, rp, cam, lens, wb.rq[0], wb.counters, list);
-    }
-    else if (list) hipLaunchKernelGGL(k_generate_list, dim3(blocks), dim3(256), 0, s, rp, cam, wb.rq[0], wb.counters, list);
-    else hipLaunchKernelGGL(k_generate, dim3(blocks), dim3(256), 0, s, rp, cam, wb.rq[0], wb.counters);
+    pick_axes<CAM_KINDS, 2>({camera_kind(opt), list ? 1u : 0u}, [&](auto kind, auto ls) {
+        hipLaunchKernelGGL((k_generate<kind, ls != 0u>), dim3(blocks), dim3(256), 0, s, rp, camera_arg<kind>(cam, opt), wb.rq[0], wb.counters, list);
+    });
 }
 
 // A persistent grid must be RESIDENT: workgroups that the device cannot hold at once start only when others have left, and by then
@@ -3156,17 +3114,7 @@ static bool ident_walk(const TraceLaunch& tl, uint32_t bits) { return (tl.ident_
 template <typename F>
 static void with_trace_variant(const TraceLaunch& tl, bool ident, F&& f)
 {
-    const bool spill = tl.scene.stack_entries > tl.scene.stack_lds;
-    auto bvh = [&](auto sp, auto id) {
-        if (tl.lds_scene) f(std::integral_constant<int, 1>{}, sp, id);
-        else f(std::integral_constant<int, 0>{}, sp, id);
-    };
-    auto stack = [&](auto id) {
-        if (spill) bvh(std::true_type{}, id);
-        else bvh(std::false_type{}, id);
-    };
-    if (ident) stack(std::true_type{});
-    else stack(std::false_type{});
+    pick_axes<2, 2, 2>({tl.lds_scene ? 1u : 0u, tl.scene.stack_entries > tl.scene.stack_lds ? 1u : 0u, ident ? 1u : 0u}, f);
 }
 // a persistent traversal grid (resident_grid, per kernel) with the launch's dynamic LDS
 template <typename K, typename... A>
@@ -3339,124 +3287,40 @@ void launch_shade(hipStream_t s, uint32_t qclass, const SceneView& sv, const Ren
     if (list && qclass != Q_TERMINAL) io.list = list; // (the surface passes read no terminal entries)
     if (ray_keys && qclass != Q_TERMINAL) io.list = ray_keys;
     const ShadeKArgs ka{sv, rp, io, b, inl ? (const uint4*)tl->blob : nullptr, inl ? tl->scene.world_root : 0u};
-    const size_t lds = inl ? trace_lds_bytes(*tl) : 0;
-    ShadeKArgsTex kat{};
-    static_cast<ShadeKArgs&>(kat) = ka;
-    if (tex) kat.tex = *tex;
-    // (LIST: the same classes over an adaptive list's paths; lens0: LENS; ray_keys: RAYS)
-#define PT_SURF_L(LENS, Q, V, ...)                                                                                                      \
-    do {                                                                                                                                 \
-        if (ray_keys) hipLaunchKernelGGL((k_shade_surface<Q, V, __VA_ARGS__, false, LENS, true>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), lds, s, ka); \
-        else if (list) hipLaunchKernelGGL((k_shade_surface<Q, V, __VA_ARGS__, true, LENS>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), lds, s, ka);  \
-        else hipLaunchKernelGGL((k_shade_surface<Q, V, __VA_ARGS__, false, LENS>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), lds, s, ka);      \
-    } while (0)
-#define PT_SURF_P(Q, V, ...)                                                                                                            \
-    do {                                                                                                                                 \
-        if (list) hipLaunchKernelGGL((k_shade_surface<Q, V, __VA_ARGS__, true, true, false, false, true>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), lds, s, ka); \
-        else hipLaunchKernelGGL((k_shade_surface<Q, V, __VA_ARGS__, false, true, false, false, true>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), lds, s, ka); \
-    } while (0)
-#define PT_SURF(Q, V, ...)                                                                                                              \
-    do {                                                                                                                                 \
-        if (proj0) PT_SURF_P(Q, V, __VA_ARGS__);                                                                                         \
-        else if (lens0) PT_SURF_L(true, Q, V, __VA_ARGS__);                                                                              \
-        else PT_SURF_L(false, Q, V, __VA_ARGS__);                                                                                        \
-    } while (0)
-    // the TEX variants of the same classes (a textured scene queues its shadow rays: shade_traces_shadow)
-    // (E: EMTEX, the scene has an emission texture; NM: NMAP, it has a normal map and KA is the argument with the tangents behind the texture view)
-#define PT_SURF_TEX_L(LENS, Q, V, E, NM, KA)                                                                                                    \
-    do {                                                                                                                                 \
-        if (ray_keys) hipLaunchKernelGGL((k_shade_surface<Q, V, false, false, false, LENS, true, true, false, E, NM>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), 0, s, KA); \
-        else if (list) hipLaunchKernelGGL((k_shade_surface<Q, V, false, false, true, LENS, false, true, false, E, NM>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), 0, s, KA); \
-        else hipLaunchKernelGGL((k_shade_surface<Q, V, false, false, false, LENS, false, true, false, E, NM>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), 0, s, KA); \
-    } while (0)
-#define PT_SURF_TEX_P(Q, V, E, NM, KA)                                                                                                         \
-    do {                                                                                                                                 \
-        if (list) hipLaunchKernelGGL((k_shade_surface<Q, V, false, false, true, true, false, true, true, E, NM>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), 0, s, KA); \
-        else hipLaunchKernelGGL((k_shade_surface<Q, V, false, false, false, true, false, true, true, E, NM>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), 0, s, KA); \
-    } while (0)
-#define PT_SURF_TEX_E(Q, E, NM, KA)                                                                                                             \
-    do {                                                                                                                                 \
-        if (proj0) { if (sv.has_volumes) PT_SURF_TEX_P(Q, true, E, NM, KA); else PT_SURF_TEX_P(Q, false, E, NM, KA); }                  \
-        else if (lens0) { if (sv.has_volumes) PT_SURF_TEX_L(true, Q, true, E, NM, KA); else PT_SURF_TEX_L(true, Q, false, E, NM, KA); } \
-        else { if (sv.has_volumes) PT_SURF_TEX_L(false, Q, true, E, NM, KA); else PT_SURF_TEX_L(false, Q, false, E, NM, KA); }          \
-    } while (0)
-#define PT_SURF_TEX(Q)                                                                                                                  \
-    do {                                                                                                                                 \
-        if (tl->emission_tex) PT_SURF_TEX_E(Q, true, false, kat);                                                                        \
-        else PT_SURF_TEX_E(Q, false, false, kat);                                                                                        \
-    } while (0)
-#define PT_SURF_NMAP(Q)                                                                                                                 \
-    do {                                                                                                                                 \
-        if (tl->emission_tex) PT_SURF_TEX_E(Q, true, true, kan);                                                                         \
-        else PT_SURF_TEX_E(Q, false, true, kan);                                                                                         \
-    } while (0)
-    if (tex && tl->emission_tex && qclass == Q_TERMINAL)
+    const TexNView texn = tex ? TexNView{*tex, tl->tri_tan} : TexNView{};
+    if (qclass == Q_TERMINAL)
     {
-        if (lens0) hipLaunchKernelGGL((k_shade_terminal<true, TexView>), dim3(grid_blocks), dim3(256), 0, s, sv, rp, io, b, *tex);
-        else hipLaunchKernelGGL((k_shade_terminal<false, TexView>), dim3(grid_blocks), dim3(256), 0, s, sv, rp, io, b, *tex);
+        // (TexView: the terminal pass of a scene with an emission texture looks a light hit's colour up)
+        pick<2>(lens0 ? 1u : 0u, [&](auto lens) {
+            if (tex && tl->emission_tex) hipLaunchKernelGGL((k_shade_terminal<lens != 0u, TexView>), dim3(grid_blocks), dim3(256), 0, s, sv, rp, io, b, *tex);
+            else hipLaunchKernelGGL((k_shade_terminal<lens != 0u>), dim3(grid_blocks), dim3(256), 0, s, sv, rp, io, b);
+        });
         return;
     }
-    if (tex && tl->tri_tan && qclass != Q_TERMINAL) // a scene with a normal map: the argument with the tangents, built for these launches alone
+    // the six axes of the surface pass (k_shade_surface), each decided here and nowhere else
+    const uint32_t media = sv.has_volumes ? MEDIA_VOLUMES : MEDIA_NONE;
+    const uint32_t shadow = !(inl && qclass == Q_LAMBERT) ? SHADOW_QUEUED : (PT_IDENT_SHADE && ident_walk(*tl, IDENT_TLAS_WORLD)) ? SHADOW_INLINE_IDENT : SHADOW_INLINE;
+    const uint32_t paths = ray_keys ? PATHS_RAYS : list ? PATHS_LIST : PATHS_RECT;
+    const uint32_t first = proj0 ? FIRST_OWN_ONE_DRAW : lens0 ? FIRST_OWN_TWO_DRAWS : FIRST_SHARED;
+    const uint32_t surface = !tex ? SURF_PLAIN : tl->tri_tan ? (tl->emission_tex ? SURF_TEX_EMTEX_NMAP : SURF_TEX_NMAP) : (tl->emission_tex ? SURF_TEX_EMTEX : SURF_TEX);
+    const size_t lds = inl ? trace_lds_bytes(*tl) : 0; // (an untextured scene whose Lambertian pass walks its shadow rays: every class's launch carries the walk's LDS)
+    bool launched = false;
+    pick_axes<Q_COUNT, MEDIA_COUNT, SHADOW_COUNT, PATHS_COUNT, FIRST_COUNT, SURF_COUNT>({qclass, media, shadow, paths, first, surface},
+        [&](auto q, auto md, auto sh, auto pa, auto fi, auto su) {
+            if constexpr (shade_variant_ok(q, md, sh, pa, fi, su)) // (the other points are no kernels: nothing is instantiated for them)
+            {
+                launched = true;
+                ShadeArg<su> arg{};
+                static_cast<ShadeKArgs&>(arg) = ka;
+                if constexpr (su != SURF_PLAIN) arg.tex = texn; // (ShadeKArgsTex keeps the texture view, ShadeKArgsNmap the tangents behind it too)
+                hipLaunchKernelGGL((k_shade_surface<q, md, sh, pa, fi, su>), dim3(surface_blocks), dim3(PT_SHADE_THREADS), lds, s, arg);
+            }
+        });
+    if (!launched) // a missing kernel is an error, never a skipped pass
     {
-        ShadeKArgsNmap kan{};
-        static_cast<ShadeKArgs&>(kan) = ka;
-        kan.tex = TexNView{*tex, tl->tri_tan};
-        switch (qclass)
-        {
-        case Q_LAMBERT: PT_SURF_NMAP(Q_LAMBERT); break;
-        case Q_SPECULAR: PT_SURF_NMAP(Q_SPECULAR); break;
-        case Q_DIELECTRIC: PT_SURF_NMAP(Q_DIELECTRIC); break;
-        case Q_GGX: PT_SURF_NMAP(Q_GGX); break;
-        default: break;
-        }
-        return;
+        fprintf(stderr, "launch_shade: no surface pass for class %u, media %u, shadow %u, paths %u, first %u, surface %u\n", qclass, media, shadow, paths, first, surface);
+        abort();
     }
-    if (tex && qclass != Q_TERMINAL)
-    {
-        switch (qclass)
-        {
-        case Q_LAMBERT: PT_SURF_TEX(Q_LAMBERT); break;
-        case Q_SPECULAR: PT_SURF_TEX(Q_SPECULAR); break;
-        case Q_DIELECTRIC: PT_SURF_TEX(Q_DIELECTRIC); break;
-        case Q_GGX: PT_SURF_TEX(Q_GGX); break;
-        default: break;
-        }
-        return;
-    }
-#undef PT_SURF_TEX
-#undef PT_SURF_NMAP
-#undef PT_SURF_TEX_E
-#undef PT_SURF_TEX_L
-#undef PT_SURF_TEX_P
-    switch (qclass)
-    {
-    case Q_TERMINAL:
-        if (lens0) hipLaunchKernelGGL(k_shade_terminal<true>, dim3(grid_blocks), dim3(256), 0, s, sv, rp, io, b);
-        else hipLaunchKernelGGL(k_shade_terminal<false>, dim3(grid_blocks), dim3(256), 0, s, sv, rp, io, b);
-        break;
-    case Q_LAMBERT:
-        if (inl && PT_IDENT_SHADE && ident_walk(*tl, IDENT_TLAS_WORLD)) PT_SURF(Q_LAMBERT, false, true, true);
-        else if (inl) PT_SURF(Q_LAMBERT, false, true, false);
-        else if (sv.has_volumes) PT_SURF(Q_LAMBERT, true, false, false);
-        else PT_SURF(Q_LAMBERT, false, false, false);
-        break;
-    case Q_SPECULAR:
-        if (sv.has_volumes) PT_SURF(Q_SPECULAR, true, false, false);
-        else PT_SURF(Q_SPECULAR, false, false, false);
-        break;
-    case Q_DIELECTRIC:
-        if (sv.has_volumes) PT_SURF(Q_DIELECTRIC, true, false, false);
-        else PT_SURF(Q_DIELECTRIC, false, false, false);
-        break;
-    case Q_GGX:
-        if (sv.has_volumes) PT_SURF(Q_GGX, true, false, false);
-        else PT_SURF(Q_GGX, false, false, false);
-        break;
-    default: break;
-    }
-#undef PT_SURF
-#undef PT_SURF_L
-#undef PT_SURF_P
 }
 
 void launch_accumulate(hipStream_t s, const RenderParams& rp, const CameraView& cam, const CameraOptics& opt, const WavefrontBuffers& wb, f4* accum, f4* position,
@@ -3466,29 +3330,11 @@ void launch_accumulate(hipStream_t s, const RenderParams& rp, const CameraView& 
     if (n == 0u) return;
     const bool quad = n < (uint32_t)PT_ACC_QUAD_BELOW;
     const dim3 grid(quad ? (n * 4u + 255u) / 256u : (n + 255u) / 256u);
-    auto go = [&](auto kernel, const auto& camera) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, rp, camera, wb.st, accum, position, id, write_position, add_to_accum, moments, list); };
     // (a list comes with moments: pt_render_adaptive)
-    if (proj_set(opt.proj))
-    {
-        CameraProjView cp{};
-        static_cast<CameraView&>(cp) = cam;
-        cp.proj = opt.proj;
-        if (list) quad ? go(k_accumulate<true, true, true, false, true>, cp) : go(k_accumulate<false, true, true, false, true>, cp);
-        else if (moments) quad ? go(k_accumulate<true, true, false, false, true>, cp) : go(k_accumulate<false, true, false, false, true>, cp);
-        else quad ? go(k_accumulate<true, false, false, false, true>, cp) : go(k_accumulate<false, false, false, false, true>, cp);
-    }
-    else if (lens_set(opt.lens))
-    {
-        CameraLensView cl{};
-        static_cast<CameraView&>(cl) = cam;
-        cl.lens = opt.lens;
-        if (list) quad ? go(k_accumulate<true, true, true, true>, cl) : go(k_accumulate<false, true, true, true>, cl);
-        else if (moments) quad ? go(k_accumulate<true, true, false, true>, cl) : go(k_accumulate<false, true, false, true>, cl);
-        else quad ? go(k_accumulate<true, false, false, true>, cl) : go(k_accumulate<false, false, false, true>, cl);
-    }
-    else if (list) quad ? go(k_accumulate<true, true, true>, cam) : go(k_accumulate<false, true, true>, cam);
-    else if (moments) quad ? go(k_accumulate<true, true>, cam) : go(k_accumulate<false, true>, cam);
-    else quad ? go(k_accumulate<true>, cam) : go(k_accumulate<false>, cam);
+    pick_axes<CAM_KINDS, 2, 3>({camera_kind(opt), quad ? 1u : 0u, list ? 2u : moments ? 1u : 0u}, [&](auto kind, auto few, auto mode) {
+        hipLaunchKernelGGL((k_accumulate<CameraArg<kind>, few != 0u, mode >= 1u, mode == 2u>), grid, dim3(256), 0, s, rp, camera_arg<kind>(cam, opt), wb.st, accum, position, id,
+                           write_position, add_to_accum, moments, list);
+    });
 }
 uint32_t adaptive_select_blocks(uint32_t n_pixels) { return (n_pixels + kSelectPerBlock - 1u) / kSelectPerBlock; }
 void launch_adaptive_select(hipStream_t s, const f4* accum, const float* moments, uint32_t n_pixels, const AdaptiveCrit& cr, uint32_t* counts, uint2* list,
@@ -3568,13 +3414,9 @@ void launch_bsdf_probe(hipStream_t s, const SceneView& sv, int material, uint32_
 
 void launch_guide_rays(hipStream_t s, const RenderParams& rp, const CameraView& cam, const CameraOptics& opt, RayQueue rq, uint32_t* n_and_heads)
 {
-    if (proj_set(opt.proj))
-    {
-        if (opt.proj.kind == PROJ_PANORAMA) hipLaunchKernelGGL(k_guide_rays_proj<PROJ_PANORAMA>, dim3((rp.local_pixels + 255u) / 256u), dim3(256), 0, s, rp, cam, opt.proj, rq, n_and_heads);
-        else hipLaunchKernelGGL(k_guide_rays_proj<PROJ_ORTHOGRAPHIC>, dim3((rp.local_pixels + 255u) / 256u), dim3(256), 0, s, rp, cam, opt.proj, rq, n_and_heads);
-    }
-    else if (lens_set(opt.lens)) hipLaunchKernelGGL(k_guide_rays_lens, dim3((rp.local_pixels + 255u) / 256u), dim3(256), 0, s, rp, cam, opt.lens, rq, n_and_heads);
-    else hipLaunchKernelGGL(k_guide_rays, dim3((rp.local_pixels + 255u) / 256u), dim3(256), 0, s, rp, cam, rq, n_and_heads);
+    pick<CAM_KINDS>(camera_kind(opt), [&](auto kind) {
+        hipLaunchKernelGGL(k_guide_rays<kind>, dim3((rp.local_pixels + 255u) / 256u), dim3(256), 0, s, rp, camera_arg<kind>(cam, opt), rq, n_and_heads);
+    });
 }
 void launch_guide_follow(hipStream_t s, const SceneView& sv, const TexView& tex, const FollowArgs& a)
 {

@@ -45,16 +45,19 @@ def _scene(name, proj, w=W, h=H, models=None):
 class Expect:
     """per-sample radiance, first-hit position and id byte of every pixel of a scene under a projection, from the oracle; cached by sample"""
 
-    def __init__(self, O, name, proj, w=W, h=H, depth=DEPTH, models=None):
+    def __init__(self, O, name, proj, w=W, h=H, depth=DEPTH, models=None, scene=None, params=None):
+        """scene: a description of the caller's own, under ITS camera pose, in place of the named scene under the projection's pose;
+        params: pt_projection fields of the caller's own in place of PROJECTIONS[proj]'s"""
+        self.params = params if params is not None else PROJECTIONS[proj][0]
         self.O, self.proj, self.w, self.h, self.depth = O, proj, w, h, depth
-        self.scene = _scene(name, proj, w, h, models)
+        self.scene = scene if scene is not None else _scene(name, proj, w, h, models)
         self.orc = O.Oracle(self.scene)
         if name == "mixed_env":
             self.orc.set_environment(_env())
         self.cache = {}
 
     def rays(self, s, pixels=None):
-        kind, sx, sy, oh = PROJECTIONS[self.proj][0]
+        kind, sx, sy, oh = self.params
         pixels = np.arange(self.w * self.h) if pixels is None else pixels
         return projection_rays(self.O, self.orc, self.w, self.h, pixels, s, kind, sx, sy, oh, aspect=self.w / self.h)
 

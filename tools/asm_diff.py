@@ -1,7 +1,8 @@
 """Compare two `make asm` outputs kernel by kernel (labels and comments normalised): SAME / DIFF / NEW per kernel.
 A kernel template that gained trailing parameters renames its old instantiations (k<a, b> becomes k<a, b, false>; a kernel that became a
 template, k becomes k<false>; one that gained a trailing parameter PACK keeps k<a, b> with the empty pack, under another symbol): such a
-kernel is compared with the one it was and marked `+param`.
+kernel is compared with the one it was and marked `+param`.  r20_name holds the one renaming that is no such growth: the surface pass's
+eleven positional parameters became six named axes and the camera kernels one template over the camera kind.
 usage: python tools/asm_diff.py old.s new.s"""
 import re, subprocess, sys
 
@@ -29,9 +30,30 @@ def was(name, old_names):
         d = d2
         if d in old_names: return old_names[d]
 
+def r20_name(d):
+    """the name since the variant axes of a kernel as named before them (demangled, as dem gives it), or d itself"""
+    m = re.fullmatch(r'(k_\w+?)(?:<(.*)>)?', d)
+    k, t = m.group(1), (m.group(2).split(', ') if m.group(2) else [])
+    u = lambda i: f'{i}u'
+    on = lambda x: x == 'true'
+    if k == 'k_shade_surface' and len(t) == 11:
+        q, vol, inl, ident, lst, lens, rays, tex, one, em, nm = [t[0]] + [on(x) for x in t[1:]]
+        surface = 0 if not tex else (4 if em else 3) if nm else (2 if em else 1)
+        axes = [int(vol), (2 if ident else 1) if inl else 0, 2 if rays else int(lst), (2 if one else 1) if lens else 0, surface]
+        return f'{k}<{", ".join([q] + [u(x) for x in axes])}>'
+    cam = {'k_generate': ('0u', 'false'), 'k_generate_list': ('0u', 'true'), 'k_guide_rays': ('0u',), 'k_guide_rays_lens': ('1u',)}
+    if d in cam: return f'{k.replace("_list", "").replace("_lens", "")}<{", ".join(cam[d])}>'
+    if k == 'k_generate_lens': return f'k_generate<1u, {t[0]}>'
+    if k == 'k_generate_proj': return f'k_generate<{u(int(t[1][:-1]) + 1)}, {t[0]}>'          # PROJ_PANORAMA 1, PROJ_ORTHOGRAPHIC 2 -> CAM_PANORAMA 2, CAM_ORTHOGRAPHIC 3
+    if k == 'k_guide_rays_proj': return f'k_guide_rays<{u(int(t[0][:-1]) + 1)}>'
+    if k == 'k_accumulate' and len(t) == 5:
+        view = 'pt::CameraProjView' if on(t[4]) else 'pt::CameraLensView' if on(t[3]) else 'pt::CameraView'
+        return f'{k}<{", ".join([view] + t[:3])}>'
+    return d
+
 a, b = funcs(sys.argv[1]), funcs(sys.argv[2])
 print(len(a), 'kernels before,', len(b), 'after')
-old_names = {dem(n): n for n in a if n not in b}
+old_names = {r20_name(dem(n)): n for n in a if n not in b}
 renamed = set()
 for n in b:
     o = n if n in a else was(n, old_names)

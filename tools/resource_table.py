@@ -4,8 +4,10 @@ waves per SIMD / scratch bytes per lane / VGPRs (spilled VGPRs), and per kernel 
 packed fp32 operations and scratch accesses.  The flags are csrc/Makefile's FLAGS plus what is given.
 
     python tools/resource_table.py [--src pt_kernels.hip] [--a=<flags>] [--b=<flags>] [--only-changed] [--keep DIR] [--csrc-a DIR]
-    python tools/resource_table.py --twins [--only NAME] [--b=<flags>]   ONE build (--only: kernels whose name contains NAME): every kernel whose LAST template argument is `true` beside its twin, the same
-                                                              instantiation with that argument `false` (a variant a template gained beside the kernel it had)
+    python tools/resource_table.py --twins [--axis SURFACE] [--only NAME] [--b=<flags>]   ONE build: every k_shade_surface instantiation whose named axis (QCLASS, MEDIA,
+                                                              SHADOW, PATHS, FIRST or SURFACE: the kernel's template parameters in order) is above its base
+                                                              value beside its twin, the same instantiation with that axis AT its base value (--only:
+                                                              kernels whose name contains NAME)
 
 The default, --a=-fslp-vectorize --b= , compares the SLP vectoriser's pairing with the build's flags (profiles/r08_fp32_pairing.md);
 --csrc-a takes the left column's sources (not its flags) from another checkout's path_tracer_amd/csrc."""
@@ -75,6 +77,22 @@ def demangle(names):
     return short
 
 
+SHADE_AXES = ["QCLASS", "MEDIA", "SHADOW", "PATHS", "FIRST", "SURFACE"]   # k_shade_surface's template parameters, in order
+AXIS_BASE = {"QCLASS": "1u"}                                            # Q_LAMBERT; every other axis starts at 0
+
+
+def twin_of(short, axis):
+    """the name of a k_shade_surface instantiation with `axis` at its base value, or None if it is there already (or is another kernel)"""
+    m = re.fullmatch(r"(k_shade_surface)<(.*)>", short)
+    if not m:
+        return None
+    args = m.group(2).split(", ")
+    k, base = SHADE_AXES.index(axis), AXIS_BASE.get(axis, "0u")
+    if len(args) != len(SHADE_AXES) or args[k] == base:
+        return None
+    return f"{m.group(1)}<{', '.join(args[:k] + [base] + args[k + 1:])}>"
+
+
 def cell(r):
     return f"{r['Occupancy [waves/SIMD]']} / {r['ScratchSize [bytes/lane]']} / {r['VGPRs']}" + (f" ({r['VGPRs Spill']} spilled)" if r["VGPRs Spill"] != "0" else "")
 
@@ -87,7 +105,8 @@ def main():
     ap.add_argument("--only-changed", action="store_true")
     ap.add_argument("--csrc-a", default=CSRC, help="source directory of the left column (another checkout's path_tracer_amd/csrc)")
     ap.add_argument("--keep", default=None, help="directory that keeps the two assembly files")
-    ap.add_argument("--twins", action="store_true", help="one build (--b): kernels whose last template argument is true beside their twins with it false")
+    ap.add_argument("--twins", action="store_true", help="one build (--b): k_shade_surface variants beside their twins with --axis at its base value")
+    ap.add_argument("--axis", default="SURFACE", choices=SHADE_AXES, help="with --twins: the axis whose base value makes the twin")
     ap.add_argument("--only", default="", help="with --twins: only kernels whose demangled name contains this")
     args = ap.parse_args()
     keep = args.keep or tempfile.mkdtemp(prefix="resource_table_")
@@ -96,13 +115,14 @@ def main():
         rb, cb = compile_one(args.src, (args.b, 1), keep)
         names = demangle(list(rb))
         by_short = {names[n]: n for n in rb}
-        print(f"`{args.src}`: waves per SIMD / scratch B per lane / VGPRs of the twin (last template argument false) and of the variant (true); static VALU, scratch accesses\n")
+        print(f"`{args.src}`: waves per SIMD / scratch B per lane / VGPRs of the twin ({args.axis} at its base value) and of the variant; static VALU, scratch accesses\n")
         print("| variant | twin | variant | VALU | scratch ops |\n|---|---|---|---|---|")
         n_pairs = fewer_waves = more_scratch = 0
         for n in rb:
-            if not names[n].endswith(", true>") or args.only not in names[n]:
+            twin = twin_of(names[n], args.axis)
+            if twin is None or args.only not in names[n]:
                 continue
-            t = by_short.get(names[n][:-len("true>")] + "false>")
+            t = by_short.get(twin)
             if t is None:
                 continue
             a, b = rb[t], rb[n]
