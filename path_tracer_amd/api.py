@@ -35,6 +35,7 @@ EXPORTS = [
     "pt_read_accumulation", "pt_read_frame", "pt_write_accumulation", "pt_render_samples", "pt_render_adaptive", "pt_adaptive_mask", "pt_read_moments", "pt_write_moments", "pt_active_pixels", "pt_local_rows", "pt_set_stream", "pt_synchronize", "pt_camera_input", "pt_camera_angles", "pt_frame", "pt_inv_projection", "pt_present", "pt_post_velocity", "pt_post_reproject", "pt_post_tonemap", "pt_post_rgb8", "pt_present_rgb8", "pt_write_image", "pt_trace_closest", "pt_trace_any",
     "pt_ss_sobol", "pt_math_batch", "pt_material_eval", "pt_volume_eval", "pt_bsdf_eval", "pt_blas_count", "pt_blas_dump", "pt_tlas_dump", "pt_tlas_instances", "pt_instance_materials", "pt_light_cdf",
     "pt_triangle_dump", "pt_get_stats", "pt_reset_stats", "pt_last_batch_counters", "pt_last_batch_shade_pids", "pt_last_batch_step_stats",
+    "pt_variant_axes", "pt_variant_compiled", "pt_last_launches",
     "pt_multi_create", "pt_multi_destroy", "pt_multi_last_error", "pt_multi_ctx", "pt_multi_render", "pt_multi_framebuffer_device_ptr",
     "pt_multi_reset_accumulation", "pt_multi_get_stats", "pt_multi_used_rccl", "pt_multi_write_image",
     "pt_render_guides", "pt_read_guides", "pt_denoise", "pt_write_denoised_image", "pt_post_denoise",
@@ -49,6 +50,8 @@ EXPORTS = [
 ]
 
 
+LAUNCHERS = ("shade", "terminal", "closest", "any", "fused", "generate", "guide_rays", "accumulate")   # pt_launcher
+LAUNCHES_BATCH, LAUNCHES_HOOK = 0, 1   # pt_last_launches' which
 ALBEDO_GUIDE, ALBEDO_MEAN = 1, 2   # pt_denoise_albedo's albedo_source
 PROJ_PERSPECTIVE, PROJ_PANORAMA, PROJ_ORTHOGRAPHIC = range(3)   # pt_projection_kind
 EV_MOUSE_MOTION, EV_KEY_W, EV_KEY_S, EV_KEY_A, EV_KEY_D = range(5)
@@ -230,6 +233,9 @@ def lib():
         L.pt_get_stats.argtypes = [vp, C.POINTER(Stats)]
         L.pt_reset_stats.argtypes = [vp]
         L.pt_last_batch_counters.argtypes = [vp, vp, u32, C.POINTER(u32)]
+        L.pt_last_launches.argtypes = [vp, u32, vp, u32, C.POINTER(u32)]
+        L.pt_variant_axes.argtypes = [u32, vp]
+        L.pt_variant_compiled.argtypes = [u32, vp]
         L.pt_last_batch_shade_pids.argtypes = [vp, u32, u32, u32, vp]
         L.pt_render_guides.argtypes = [vp, u32]
         L.pt_read_guides.argtypes = [vp, vp, vp, vp]
@@ -277,6 +283,28 @@ def _p(a):
 
 def _f3(v):
     return (C.c_float * 3)(*[float(x) for x in v])
+
+
+def variant_axes(launcher):
+    """pt_variant_axes: the number of values of each axis of a keyed launcher (a name of LAUNCHERS), in order.  Needs no device."""
+    b = np.zeros(6, np.uint32)
+    n = lib().pt_variant_axes(LAUNCHERS.index(launcher), _p(b))
+    if n <= 0:
+        raise PtError(n, f"no launcher {launcher}")
+    return tuple(int(v) for v in b[:n])
+
+
+def variant_compiled(launcher, axes):
+    """pt_variant_compiled: is this point of the launcher's axes a kernel of the library?  Needs no device."""
+    a = np.zeros(6, np.uint32)
+    a[: len(axes)] = axes
+    return bool(lib().pt_variant_compiled(LAUNCHERS.index(launcher), _p(a)))
+
+
+def compiled_variants(launcher):
+    """every compiled point of a keyed launcher's axes as (launcher, axis values)"""
+    import itertools
+    return {(launcher, p) for p in itertools.product(*[range(n) for n in variant_axes(launcher)]) if variant_compiled(launcher, p)}
 
 
 class Renderer:
@@ -1035,6 +1063,14 @@ class Renderer:
         n = C.c_uint32()
         self._chk(self.L.pt_last_batch_counters(self.ctx, _p(rows), rows.shape[0], C.byref(n)))
         return rows[: n.value]
+
+    def last_launches(self, which=LAUNCHES_BATCH):
+        """pt_last_launches: the keyed launches of the last batch (or hook request) as (launcher name, counter row, axis values) tuples"""
+        n = C.c_uint32()
+        self._chk(self.L.pt_last_launches(self.ctx, which, None, 0, C.byref(n)))
+        rows = np.zeros((max(n.value, 1), 8), np.uint32)
+        self._chk(self.L.pt_last_launches(self.ctx, which, _p(rows), rows.shape[0], C.byref(n)))
+        return [(LAUNCHERS[int(r[0])], int(r[1]), tuple(int(v) for v in r[2:2 + len(variant_axes(LAUNCHERS[int(r[0])]))])) for r in rows[: n.value]]
 
     def last_batch_shade_pids(self, qclass, first, count):
         out = np.zeros(count, np.uint32)

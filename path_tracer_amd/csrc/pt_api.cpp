@@ -125,6 +125,7 @@ struct pt_ctx
         bool busy = false;              // a batch has been launched and not yet harvested
         uint32_t busy_rows = 0;
         uint64_t busy_paths = 0, busy_culled = 0;
+        LaunchLog log;                  // the keyed launches of the pipeline's last batch (pt_last_launches)
     };
     static constexpr int kMaxPipes = (int)kMaxPipelines;
     Pipe pipe[kMaxPipes];
@@ -205,6 +206,7 @@ struct pt_ctx
     // stats
     pt_stats stats{};
     int last_pipe = 0; // pipeline whose counters pt_last_batch_counters reports
+    LaunchLog hook_log; // the keyed launches of the last request that went through the hook queue (pt_last_launches)
 };
 
 namespace {
@@ -281,8 +283,15 @@ int normalise_config(pt_ctx* c, const pt_config* in)
     if (g.strip_rows == 0) g.strip_rows = 4;
     if (g.rank >= g.world_size) return fail(c, PT_ERR_ARG, "rank >= world_size");
     if ((uint64_t)g.width * g.height > 0x7fffffffull) return fail(c, PT_ERR_ARG, "image too large");
+    const pt_config old = c->cfg;
     c->cfg = g;
     compute_rows(c);
+    if (c->local_pixels > accumulate_max_pixels()) // (the accumulation pass has no kernel for more)
+    {
+        c->cfg = old;
+        compute_rows(c);
+        return fail(c, PT_ERR_ARG, "image too large: more than 2^30 - 1 pixels on one device");
+    }
     return PT_OK;
 }
 
@@ -882,6 +891,8 @@ int batch_begin(BatchRun& br, pt_ctx* c, const BatchSpec& spec)
     br = BatchRun{};
     br.c = c;
     br.spec = spec;
+    pp.log.clear();
+    const LaunchLogScope logging(&pp.log);
     RenderParams& rp = br.rp;
     rp.width = g.width;
     rp.height = g.height;
@@ -1003,6 +1014,7 @@ int batch_bounce(BatchRun& br, uint32_t b)
     const pt_config& g = c->cfg;
     const WavefrontBuffers& wb = br.wb;
     hipStream_t s = br.s;
+    const LaunchLogScope logging(&pp.log);
     // bounce b touches rows b and b + 1 (the shading pass appends to the next bounce's queues)
     while (br.cleared_rows < std::min<uint32_t>(br.rows, b + 2u))
     {
@@ -1050,6 +1062,7 @@ int batch_end(BatchRun& br, hipEvent_t after)
     const WavefrontBuffers& wb = br.wb;
     hipStream_t s = br.s;
     const RenderParams& rp = br.rp;
+    const LaunchLogScope logging(&pp.log);
     if (br.last_row == br.rows - 1) br.last_row = g.max_bounces + 1;
     // the last shading pass may still owe direct-light estimates: trace them, then a resolve-only terminal pass
     if (br.nee)
@@ -2607,6 +2620,8 @@ int follow_params(pt_ctx* c, const pt_guide_params* gp, const char* who)
 int follow_chains(pt_ctx* c, uint32_t sample, uint32_t max_hops, f4* sum)
 {
     int r;
+    c->hook_log.clear();
+    const LaunchLogScope logging(&c->hook_log);
     if ((r = guide_trace(c, sample))) return r; // hop 0: the camera rays, slot = local pixel
     const RayQueue q[2] = {RayQueue{(f4*)c->d_gray_a.p, (f4*)c->d_gray_b.p}, RayQueue{(f4*)c->d_gray2_a.p, (f4*)c->d_gray2_b.p}};
     uint32_t* const head[2] = {(uint32_t*)c->d_ghead.p, (uint32_t*)c->d_ghead2.p};
@@ -3193,7 +3208,11 @@ int pt_trace_closest(pt_ctx* c, int which, uint32_t n, const float* o, const flo
     uint32_t* dh = upload_rays(st, n, o, d, tmax, q);
     f4* dhit = (f4*)st.out((size_t)n * 16);
     if (st.err) return st.err;
-    launch_trace_rays_closest(c->stream, trace_launch(c), root, q, n, dh, dhit);
+    {
+        c->hook_log.clear();
+        const LaunchLogScope logging(&c->hook_log);
+        launch_trace_rays_closest(c->stream, trace_launch(c), root, q, n, dh, dhit);
+    }
     std::vector<f4> h(n);
     if ((r = st.download(h.data(), dhit, (size_t)n * 16))) return r;
     const FlatScene& f = c->scene.flat;
@@ -3226,7 +3245,11 @@ int pt_trace_any(pt_ctx* c, int which, uint32_t n, const float* o, const float* 
     uint32_t* dh = upload_rays(st, n, o, d, tmax, q);
     uint32_t* docc = (uint32_t*)st.out((size_t)n * 4);
     if (st.err) return st.err;
-    launch_trace_rays_any(c->stream, trace_launch(c), root, q, n, dh, docc);
+    {
+        c->hook_log.clear();
+        const LaunchLogScope logging(&c->hook_log);
+        launch_trace_rays_any(c->stream, trace_launch(c), root, q, n, dh, docc);
+    }
     std::vector<uint32_t> h(n);
     if ((r = st.download(h.data(), docc, (size_t)n * 4))) return r;
     for (uint32_t i = 0; i < n; ++i) hit[i] = h[i] ? 1 : 0;
@@ -3734,6 +3757,25 @@ int pt_last_batch_counters(pt_ctx* c, uint32_t* rows16, uint32_t cap_rows, uint3
     *n_rows = rows;
     return PT_OK;
 }
+
+int pt_last_launches(pt_ctx* c, uint32_t which, uint32_t* rows8, uint32_t cap_rows, uint32_t* n_rows)
+{
+    if (!c || !n_rows || which > PT_LAUNCHES_HOOK || (cap_rows && !rows8)) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    const LaunchLog& log = which == PT_LAUNCHES_HOOK ? c->hook_log : c->pipe[c->last_pipe].log;
+    static_assert(sizeof(LaunchRow) == 32, "pt_last_launches hands the rows out as they are");
+    if (cap_rows && !log.empty()) std::memcpy(rows8, log.data(), std::min<size_t>(cap_rows, log.size()) * sizeof(LaunchRow));
+    *n_rows = (uint32_t)log.size();
+    return PT_OK;
+}
+int pt_variant_axes(uint32_t launcher, uint32_t bounds6[6])
+{
+    if (!bounds6) return PT_ERR_ARG;
+    static_assert(kLaunchAxes == 6 && (uint32_t)LAUNCH_COUNT == (uint32_t)PT_LAUNCHER_COUNT, "include/pt_api.h");
+    const uint32_t n = variant_axes(launcher, bounds6);
+    return n ? (int)n : PT_ERR_ARG;
+}
+int pt_variant_compiled(uint32_t launcher, const uint32_t axes6[6]) { return axes6 && variant_compiled(launcher, axes6) ? 1 : 0; }
 
 // diagnostic (tools/shade_access_bench.py): the path ids of the LAST batch's last bounce in the order its shading pass read them — word 3 of
 // array `a` of the class's shade queue, which nothing overwrites after the batch's last traversal launch.  HOLE (0xffffffff) = a slot no ray took.

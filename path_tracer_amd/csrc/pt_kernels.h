@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <vector>
+
 #include "pt_materials.h"
 #include "pt_types.h"
 
@@ -129,6 +131,45 @@ void launch_lightmap_rays(hipStream_t s, const LightmapBake& lb, uint64_t first,
 void launch_lightmap_fold(hipStream_t s, const LightmapBake& lb, uint64_t first, uint32_t count, const f4* radiance, float* sum);
 // one dilation pass (lm_dilate) of a w x h map from (rgb, cov) to (rgb_out, cov_out)
 void launch_lightmap_dilate(hipStream_t s, uint32_t w, uint32_t h, const float* rgb, const uint8_t* cov, float* rgb_out, uint8_t* cov_out);
+
+// ---- the keyed launchers' variants, for tests (pt_variant_axes, pt_variant_compiled, pt_last_launches; include/pt_api.h has the axes' values).
+// A keyed launcher turns integers into template arguments (pick_axes, pt_kernels.hip); the axes' bounds and the predicate that says which of
+// their points are kernels are the ones the launcher itself instantiates from.
+enum Launcher : uint32_t
+{
+    LAUNCH_SHADE,      // k_shade_surface: qclass, media, shadow, paths, first, surface
+    LAUNCH_TERMINAL,   // k_shade_terminal: lens, emission texture
+    LAUNCH_CLOSEST,    // k_closest: MODE, bvh, spill, ident
+    LAUNCH_ANY,        // k_any: MODE, bvh, spill, ident
+    LAUNCH_FUSED,      // k_trace_fused: bvh, spill, ident
+    LAUNCH_GENERATE,   // k_generate: camera kind, list
+    LAUNCH_GUIDE_RAYS, // k_guide_rays: camera kind
+    LAUNCH_ACCUMULATE, // k_accumulate: camera kind, few, mode (0 sums, 1 sums and moments, 2 those of a list)
+    LAUNCH_COUNT
+};
+constexpr uint32_t kLaunchAxes = 6;
+// bound[k] <- the number of values of the launcher's k-th axis; the number of axes (0: no such launcher)
+uint32_t variant_axes(uint32_t launcher, uint32_t bound[kLaunchAxes]);
+// true: the point (its first variant_axes values) is a kernel of the code object
+bool variant_compiled(uint32_t launcher, const uint32_t axis[kLaunchAxes]);
+// One row per keyed launch, written where the launcher has decided the axes: the launcher, the counter row (bounce) it works on (0 where
+// it has none) and the axis values it dispatched on, unused ones 0.
+struct LaunchRow
+{
+    uint32_t launcher, b, axis[kLaunchAxes];
+};
+typedef std::vector<LaunchRow> LaunchLog;
+// while one lives, the keyed launches of its thread are appended to `log` (null: to none); scopes nest
+struct LaunchLogScope
+{
+    explicit LaunchLogScope(LaunchLog* log);
+    ~LaunchLogScope();
+    LaunchLogScope(const LaunchLogScope&) = delete;
+    LaunchLogScope& operator=(const LaunchLogScope&) = delete;
+    LaunchLog* prev;
+};
+// the most local pixels launch_accumulate has a kernel for
+uint32_t accumulate_max_pixels();
 
 // list: an adaptive list (launch_adaptive_select's {local pixel, n_p} entries, rp.act_pixels of them) whose pixels the batch's paths belong
 // to instead of the active rectangle's (pt_render_adaptive), or null

@@ -25,6 +25,7 @@
 #include <cstdlib>
 #include <mutex>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 namespace pt {
@@ -757,7 +758,7 @@ __device__ __forceinline__ Blob stage_scene(const SceneView& sv, const uint4* __
 // CLOSEST_WORLD_EMTEX = CLOSEST_WORLD of a scene with an emission texture (pt_set_material_emission_texture): a path that ends at a light
 // is NOT finished here, where the emitted colour of the hit point cannot be looked up, but goes to the terminal queue with its hit record
 // (k_shade_terminal<LENS, TexView>); a miss is finished here as ever.
-enum { CLOSEST_WORLD = 0, CLOSEST_LIGHTS = 1, CLOSEST_HOOK = 2, CLOSEST_PRIMARY = 3, CLOSEST_PRIMARY_LENS = 4, CLOSEST_WORLD_EMTEX = 5 };
+enum { CLOSEST_WORLD = 0, CLOSEST_LIGHTS = 1, CLOSEST_HOOK = 2, CLOSEST_PRIMARY = 3, CLOSEST_PRIMARY_LENS = 4, CLOSEST_WORLD_EMTEX = 5, CLOSEST_MODES = 6 };
 constexpr bool closest_is_primary(int mode) { return mode == CLOSEST_PRIMARY || mode == CLOSEST_PRIMARY_LENS; }
 constexpr bool closest_is_world(int mode) { return mode == CLOSEST_WORLD || mode == CLOSEST_WORLD_EMTEX; }
 
@@ -1399,7 +1400,7 @@ __global__ void __launch_bounds__(256, BVH != 0 ? PT_WAVES_LDS_BVH : PT_WAVES_GL
 }
 
 // ------------------------------------------------------------------------------------------------ any hit
-enum { ANY_SHADOW = 0, ANY_HOOK = 2 };
+enum { ANY_SHADOW = 0, ANY_HOOK = 2, ANY_MODES = 3 };
 
 // TLAS::any_intersect / BLAS::any_intersect (tlas.rs:111-144, blas.rs:257-294) pop a node, test ITS box and push both children
 // untested.  The answer is a disjunction over the triangles of every leaf whose box the ray meets, each tested with that
@@ -3045,6 +3046,85 @@ static void pick_axes(const uint32_t (&value)[sizeof...(N)], F&& f, C... held)
     else pick<bound[k]>(value[k], [&](auto c) { pick_axes<N...>(value, f, held..., c); });
 }
 
+// The launch log (pt_kernels.h): the thread's current one, and the row a keyed launcher writes where it has decided its axes.
+static thread_local LaunchLog* t_launch_log = nullptr;
+LaunchLogScope::LaunchLogScope(LaunchLog* log) : prev(t_launch_log) { t_launch_log = log; }
+LaunchLogScope::~LaunchLogScope() { t_launch_log = prev; }
+template <size_t N>
+static void log_launch(uint32_t launcher, uint32_t b, const uint32_t (&value)[N])
+{
+    static_assert(N <= kLaunchAxes, "");
+    if (!t_launch_log) return;
+    LaunchRow row{launcher, b, {}};
+    for (size_t k = 0; k < N; ++k) row.axis[k] = value[k];
+    t_launch_log->push_back(row);
+}
+// ... pick_axes over the launcher's bounds (launch_axes<LAUNCHER>, an integer_sequence), with the row logged: the values the log holds are
+// the ones the kernel is picked by
+template <uint32_t... N, typename F>
+static void pick_axes_of(std::integer_sequence<uint32_t, N...>, const uint32_t (&value)[sizeof...(N)], F&& f)
+{
+    pick_axes<N...>(value, f);
+}
+template <uint32_t LAUNCHER, uint32_t... N, typename F>
+static void pick_logged(std::integer_sequence<uint32_t, N...> axes, uint32_t b, const uint32_t (&value)[sizeof...(N)], F&& f)
+{
+    log_launch(LAUNCHER, b, value);
+    pick_axes_of(axes, value, f);
+}
+// The axes of the keyed launchers (launch_axes) and the points of them that are kernels: the predicates below are what the launchers
+// instantiate under (a static_assert or an `if constexpr`) and what variant_compiled answers with.
+constexpr bool closest_mode_ok(uint32_t mode) { return mode < CLOSEST_MODES; }
+constexpr bool any_mode_ok(uint32_t mode) { return mode == ANY_SHADOW || mode == ANY_HOOK; }
+// the fused launch is the LDS-resident scenes' (pt_api.cpp: a BVH in global memory keeps the two launches apart), so it has no global-BVH kernels
+constexpr bool fused_variant_ok(uint32_t bvh, uint32_t spill, uint32_t ident) { return bvh == 1u && spill < 2u && ident < 2u; }
+// one thread per pixel is the pass of frames of PT_ACC_QUAD_BELOW pixels and more: no kernel where the quad pass takes every frame there can be
+constexpr bool accumulate_variant_ok(uint32_t kind, uint32_t few, uint32_t mode)
+{
+    return kind < CAM_KINDS && mode < 3u && (few == 1u || (few == 0u && (uint64_t)PT_ACC_QUAD_BELOW < (1ull << 30)));
+}
+template <uint32_t LAUNCHER> struct launch_axes;
+template <> struct launch_axes<LAUNCH_SHADE> : std::integer_sequence<uint32_t, Q_COUNT, MEDIA_COUNT, SHADOW_COUNT, PATHS_COUNT, FIRST_COUNT, SURF_COUNT> {};
+template <> struct launch_axes<LAUNCH_TERMINAL> : std::integer_sequence<uint32_t, 2, 2> {};
+template <> struct launch_axes<LAUNCH_CLOSEST> : std::integer_sequence<uint32_t, CLOSEST_MODES, 2, 2, 2> {};
+template <> struct launch_axes<LAUNCH_ANY> : std::integer_sequence<uint32_t, ANY_MODES, 2, 2, 2> {};
+template <> struct launch_axes<LAUNCH_FUSED> : std::integer_sequence<uint32_t, 2, 2, 2> {};
+template <> struct launch_axes<LAUNCH_GENERATE> : std::integer_sequence<uint32_t, CAM_KINDS, 2> {};
+template <> struct launch_axes<LAUNCH_GUIDE_RAYS> : std::integer_sequence<uint32_t, CAM_KINDS> {};
+template <> struct launch_axes<LAUNCH_ACCUMULATE> : std::integer_sequence<uint32_t, CAM_KINDS, 2, 3> {};
+template <uint32_t... N>
+static uint32_t copy_bounds(std::integer_sequence<uint32_t, N...>, uint32_t bound[kLaunchAxes])
+{
+    const uint32_t b[] = {N...};
+    for (size_t k = 0; k < sizeof...(N); ++k) bound[k] = b[k];
+    return (uint32_t)sizeof...(N);
+}
+uint32_t variant_axes(uint32_t launcher, uint32_t bound[kLaunchAxes])
+{
+    for (uint32_t k = 0; k < kLaunchAxes; ++k) bound[k] = 0u;
+    uint32_t n = 0;
+    if (launcher < LAUNCH_COUNT) pick<LAUNCH_COUNT>(launcher, [&](auto l) { n = copy_bounds(launch_axes<l>{}, bound); });
+    return n;
+}
+bool variant_compiled(uint32_t launcher, const uint32_t a[kLaunchAxes])
+{
+    uint32_t bound[kLaunchAxes];
+    const uint32_t n = variant_axes(launcher, bound);
+    if (n == 0u) return false;
+    for (uint32_t k = 0; k < n; ++k)
+        if (a[k] >= bound[k]) return false;
+    switch (launcher)
+    {
+    case LAUNCH_SHADE: return shade_variant_ok(a[0], a[1], a[2], a[3], a[4], a[5]);
+    case LAUNCH_CLOSEST: return closest_mode_ok(a[0]);
+    case LAUNCH_ANY: return any_mode_ok(a[0]);
+    case LAUNCH_FUSED: return fused_variant_ok(a[0], a[1], a[2]);
+    case LAUNCH_ACCUMULATE: return accumulate_variant_ok(a[0], a[1], a[2]);
+    default: return true; // every point inside the bounds
+    }
+}
+uint32_t accumulate_max_pixels() { return accumulate_variant_ok(0u, 0u, 0u) ? ~0u : (uint32_t)PT_ACC_QUAD_BELOW - 1u; }
+
 // How a camera kind reaches a kernel: camera_kind reads it off the optics, pick makes it a constant, camera_arg builds the one argument of
 // that kind (CameraArg, pt_camera.h) and the kernel's primary_ray overload is chosen by the argument's type.
 static uint32_t camera_kind(const CameraOptics& opt)
@@ -3065,7 +3145,7 @@ static CameraArg<KIND> camera_arg(const CameraView& cam, const CameraOptics& opt
 void launch_generate(hipStream_t s, const RenderParams& rp, const CameraView& cam, const CameraOptics& opt, const WavefrontBuffers& wb, const uint2* list)
 {
     const uint32_t blocks = (rp.n_paths + 255u) / 256u;
-    pick_axes<CAM_KINDS, 2>({camera_kind(opt), list ? 1u : 0u}, [&](auto kind, auto ls) {
+    pick_logged<LAUNCH_GENERATE>(launch_axes<LAUNCH_GENERATE>{}, 0u, {camera_kind(opt), list ? 1u : 0u}, [&](auto kind, auto ls) {
         hipLaunchKernelGGL((k_generate<kind, ls != 0u>), dim3(blocks), dim3(256), 0, s, rp, camera_arg<kind>(cam, opt), wb.rq[0], wb.counters, list);
     });
 }
@@ -3111,10 +3191,14 @@ static bool ident_walk(const TraceLaunch& tl, uint32_t bits) { return (tl.ident_
 
 // The traversal kernels' variant for a launch, picked once: f(BVH, SPILL, IDENT) with each as a std::integral_constant.  BVH 1: the
 // scene's BVH is staged in LDS; SPILL: the stack's deepest levels live in global memory (Stack8<true>); IDENT: ident_walk.
-template <typename F>
-static void with_trace_variant(const TraceLaunch& tl, bool ident, F&& f)
+// (LAUNCHER, mode, b: the launch log's row; mode is the kernel's MODE where it has one)
+template <uint32_t LAUNCHER, typename F>
+static void with_trace_variant(uint32_t mode, uint32_t b, const TraceLaunch& tl, bool ident, F&& f)
 {
-    pick_axes<2, 2, 2>({tl.lds_scene ? 1u : 0u, tl.scene.stack_entries > tl.scene.stack_lds ? 1u : 0u, ident ? 1u : 0u}, f);
+    const uint32_t bvh = tl.lds_scene ? 1u : 0u, spill = tl.scene.stack_entries > tl.scene.stack_lds ? 1u : 0u, id = ident ? 1u : 0u;
+    if constexpr (LAUNCHER == LAUNCH_FUSED) log_launch(LAUNCHER, b, {bvh, spill, id});
+    else log_launch(LAUNCHER, b, {mode, bvh, spill, id});
+    pick_axes_of(launch_axes<LAUNCH_FUSED>{}, {bvh, spill, id}, f); // (BVH, spill, walk: the fused launcher's axes, and the last three of k_closest's and k_any's)
 }
 // a persistent traversal grid (resident_grid, per kernel) with the launch's dynamic LDS
 template <typename K, typename... A>
@@ -3126,19 +3210,21 @@ static void launch_resident(K kernel, uint32_t waves_cap, const TraceLaunch& tl,
 
 template <int MODE>
 static void launch_closest_impl(hipStream_t s, const TraceLaunch& tl, uint32_t root, const RayQueue& rq, const uint32_t* n_ptr, uint32_t cap_in,
-                                uint32_t* heads, const ClosestOut& out)
+                                uint32_t* heads, const ClosestOut& out, uint32_t b = 0u)
 {
+    static_assert(closest_mode_ok(MODE), "no such mode of k_closest");
     const ClosestKArgs ka{tl.scene, (const uint4*)tl.blob, rq.a, rq.b, n_ptr, heads, root, cap_in, out};
-    with_trace_variant(tl, ident_walk(tl, tlas_bits(tl, root, MODE == CLOSEST_LIGHTS)), [&](auto bvh, auto spill, auto ident) {
+    with_trace_variant<LAUNCH_CLOSEST>(MODE, b, tl, ident_walk(tl, tlas_bits(tl, root, MODE == CLOSEST_LIGHTS)), [&](auto bvh, auto spill, auto ident) {
         launch_resident(k_closest<bvh, MODE, spill, ident>, trace_waves_cap(bvh != 0, ident), tl, s, ka);
     });
 }
 template <int MODE>
 static void launch_any_impl(hipStream_t s, const TraceLaunch& tl, uint32_t root, const RayQueue& rq, const uint32_t* n_ptr, uint32_t cap_in,
-                            uint32_t* heads, uint32_t* occluded, f4* radiance = nullptr)
+                            uint32_t* heads, uint32_t* occluded, f4* radiance = nullptr, uint32_t b = 0u)
 {
+    static_assert(any_mode_ok(MODE), "no such mode of k_any");
     const uint4* blob = (const uint4*)tl.blob;
-    with_trace_variant(tl, ident_walk(tl, tlas_bits(tl, root, false)), [&](auto bvh, auto spill, auto ident) {
+    with_trace_variant<LAUNCH_ANY>(MODE, b, tl, ident_walk(tl, tlas_bits(tl, root, false)), [&](auto bvh, auto spill, auto ident) {
         launch_resident(k_any<bvh, MODE, spill, ident>, trace_waves_cap(bvh != 0, ident), tl, s, tl.scene, blob, root, rq.a, rq.b, n_ptr, cap_in, heads, occluded, radiance);
     });
 }
@@ -3191,11 +3277,11 @@ void launch_trace_world(hipStream_t s, const TraceLaunch& tl, const WavefrontBuf
         out.keep_s_id = rp.keep_s_id; out.keep_s_pos = rp.keep_s_pos;
         out.blk_log = rp.blk_log; out.n_blk = rp.n_blk; out.blk_last = rp.blk_last; out.act_pixels = rp.act_pixels;
         out.div_blk_paths = rp.div_blk_paths; out.div_blk_last = rp.div_blk_last;
-        if (lens_set(opt.lens) || proj_set(opt.proj) || ray_list) launch_closest_impl<CLOSEST_PRIMARY_LENS>(s, tl, tl.scene.world_root, wb.rq[0], &row->n_closest, wb.cap_slots, row_heads(wb, b, HEADS_CLOSEST), out);
-        else launch_closest_impl<CLOSEST_PRIMARY>(s, tl, tl.scene.world_root, wb.rq[0], &row->n_closest, wb.cap_slots, row_heads(wb, b, HEADS_CLOSEST), out);
+        if (lens_set(opt.lens) || proj_set(opt.proj) || ray_list) launch_closest_impl<CLOSEST_PRIMARY_LENS>(s, tl, tl.scene.world_root, wb.rq[0], &row->n_closest, wb.cap_slots, row_heads(wb, b, HEADS_CLOSEST), out, b);
+        else launch_closest_impl<CLOSEST_PRIMARY>(s, tl, tl.scene.world_root, wb.rq[0], &row->n_closest, wb.cap_slots, row_heads(wb, b, HEADS_CLOSEST), out, b);
     }
-    else if (tl.emission_tex) launch_closest_impl<CLOSEST_WORLD_EMTEX>(s, tl, tl.scene.world_root, wb.rq[b & 1u], &row->n_closest, wb.cap_slots, row_heads(wb, b, HEADS_CLOSEST), out);
-    else launch_closest_impl<CLOSEST_WORLD>(s, tl, tl.scene.world_root, wb.rq[b & 1u], &row->n_closest, wb.cap_slots, row_heads(wb, b, HEADS_CLOSEST), out);
+    else if (tl.emission_tex) launch_closest_impl<CLOSEST_WORLD_EMTEX>(s, tl, tl.scene.world_root, wb.rq[b & 1u], &row->n_closest, wb.cap_slots, row_heads(wb, b, HEADS_CLOSEST), out, b);
+    else launch_closest_impl<CLOSEST_WORLD>(s, tl, tl.scene.world_root, wb.rq[b & 1u], &row->n_closest, wb.cap_slots, row_heads(wb, b, HEADS_CLOSEST), out, b);
 }
 // world closest hit of bounce b (b >= 1) + the BSDF-sampled NEE rays of bounce b - 1 in one launch (k_trace_fused)
 void launch_trace_fused(hipStream_t s, const TraceLaunch& tl, const WavefrontBuffers& wb, uint32_t b, const RenderParams& rp, const EnvView& env)
@@ -3212,9 +3298,19 @@ void launch_trace_fused(hipStream_t s, const TraceLaunch& tl, const WavefrontBuf
     fa.la = wb.rq_lchain[(b - 1u) & 1u].a; fa.lb = wb.rq_lchain[(b - 1u) & 1u].b; fa.ln = &prev->n_lchain; fa.lheads = row_heads(wb, b - 1u, HEADS_LCHAIN);
     fa.world_root = tl.scene.world_root; fa.lights_root = tl.scene.lights_root; fa.cap_in = wb.cap_slots;
     const FusedKArgs ka{tl.scene, (const uint4*)tl.blob, fa, wout, lout};
-    with_trace_variant(tl, ident_walk(tl, IDENT_TLAS_WORLD | IDENT_TLAS_LIGHTS), [&](auto bvh, auto spill, auto ident) {
-        launch_resident(k_trace_fused<bvh, spill, ident>, trace_waves_cap(bvh != 0, ident), tl, s, ka);
+    bool launched = false;
+    with_trace_variant<LAUNCH_FUSED>(0u, b, tl, ident_walk(tl, IDENT_TLAS_WORLD | IDENT_TLAS_LIGHTS), [&](auto bvh, auto spill, auto ident) {
+        if constexpr (fused_variant_ok(bvh, spill, ident))
+        {
+            launched = true;
+            launch_resident(k_trace_fused<bvh, spill, ident>, trace_waves_cap(bvh != 0, ident), tl, s, ka);
+        }
     });
+    if (!launched) // a missing kernel is an error, never a skipped pass
+    {
+        fprintf(stderr, "launch_trace_fused: no fused traversal for a BVH in global memory\n");
+        abort();
+    }
 }
 void launch_trace_shadow(hipStream_t s, const TraceLaunch& tl, const WavefrontBuffers& wb, uint32_t b)
 {
@@ -3226,7 +3322,7 @@ void launch_trace_shadow(hipStream_t s, const TraceLaunch& tl, const WavefrontBu
     }
 #endif
     launch_any_impl<ANY_SHADOW>(s, tl, tl.scene.world_root, wb.rq_shadow, &row->n_shadow, wb.cap_slots, row_heads(wb, b, HEADS_SHADOW),
-                                reinterpret_cast<uint32_t*>(wb.st.rec), wb.st.radiance);
+                                reinterpret_cast<uint32_t*>(wb.st.rec), wb.st.radiance, b);
 }
 void launch_trace_lchain(hipStream_t s, const TraceLaunch& tl, const WavefrontBuffers& wb, uint32_t b)
 {
@@ -3236,7 +3332,7 @@ void launch_trace_lchain(hipStream_t s, const TraceLaunch& tl, const WavefrontBu
     out.n_shade = nullptr;
     out.world_root = tl.scene.world_root;
     out.occl = wb.st.occl;
-    launch_closest_impl<CLOSEST_LIGHTS>(s, tl, tl.scene.lights_root, wb.rq_lchain[b & 1u], &row->n_lchain, wb.cap_slots, row_heads(wb, b, HEADS_LCHAIN), out);
+    launch_closest_impl<CLOSEST_LIGHTS>(s, tl, tl.scene.lights_root, wb.rq_lchain[b & 1u], &row->n_lchain, wb.cap_slots, row_heads(wb, b, HEADS_LCHAIN), out, b);
 }
 // (A textured scene queues its shadow rays: the inline walk would need INLINE x TEX variants of the pass whose registers are the tightest.)
 // The Lambertian shading pass walks its own shadow rays when the scene's BVH and a workgroup's stacks take no more LDS than five workgroups per CU can share
@@ -3291,8 +3387,8 @@ void launch_shade(hipStream_t s, uint32_t qclass, const SceneView& sv, const Ren
     if (qclass == Q_TERMINAL)
     {
         // (TexView: the terminal pass of a scene with an emission texture looks a light hit's colour up)
-        pick<2>(lens0 ? 1u : 0u, [&](auto lens) {
-            if (tex && tl->emission_tex) hipLaunchKernelGGL((k_shade_terminal<lens != 0u, TexView>), dim3(grid_blocks), dim3(256), 0, s, sv, rp, io, b, *tex);
+        pick_logged<LAUNCH_TERMINAL>(launch_axes<LAUNCH_TERMINAL>{}, b, {lens0 ? 1u : 0u, tex && tl->emission_tex ? 1u : 0u}, [&](auto lens, auto emtex) {
+            if constexpr (emtex != 0u) hipLaunchKernelGGL((k_shade_terminal<lens != 0u, TexView>), dim3(grid_blocks), dim3(256), 0, s, sv, rp, io, b, *tex);
             else hipLaunchKernelGGL((k_shade_terminal<lens != 0u>), dim3(grid_blocks), dim3(256), 0, s, sv, rp, io, b);
         });
         return;
@@ -3305,7 +3401,7 @@ void launch_shade(hipStream_t s, uint32_t qclass, const SceneView& sv, const Ren
     const uint32_t surface = !tex ? SURF_PLAIN : tl->tri_tan ? (tl->emission_tex ? SURF_TEX_EMTEX_NMAP : SURF_TEX_NMAP) : (tl->emission_tex ? SURF_TEX_EMTEX : SURF_TEX);
     const size_t lds = inl ? trace_lds_bytes(*tl) : 0; // (an untextured scene whose Lambertian pass walks its shadow rays: every class's launch carries the walk's LDS)
     bool launched = false;
-    pick_axes<Q_COUNT, MEDIA_COUNT, SHADOW_COUNT, PATHS_COUNT, FIRST_COUNT, SURF_COUNT>({qclass, media, shadow, paths, first, surface},
+    pick_logged<LAUNCH_SHADE>(launch_axes<LAUNCH_SHADE>{}, b, {qclass, media, shadow, paths, first, surface},
         [&](auto q, auto md, auto sh, auto pa, auto fi, auto su) {
             if constexpr (shade_variant_ok(q, md, sh, pa, fi, su)) // (the other points are no kernels: nothing is instantiated for them)
             {
@@ -3331,10 +3427,20 @@ void launch_accumulate(hipStream_t s, const RenderParams& rp, const CameraView& 
     const bool quad = n < (uint32_t)PT_ACC_QUAD_BELOW;
     const dim3 grid(quad ? (n * 4u + 255u) / 256u : (n + 255u) / 256u);
     // (a list comes with moments: pt_render_adaptive)
-    pick_axes<CAM_KINDS, 2, 3>({camera_kind(opt), quad ? 1u : 0u, list ? 2u : moments ? 1u : 0u}, [&](auto kind, auto few, auto mode) {
-        hipLaunchKernelGGL((k_accumulate<CameraArg<kind>, few != 0u, mode >= 1u, mode == 2u>), grid, dim3(256), 0, s, rp, camera_arg<kind>(cam, opt), wb.st, accum, position, id,
-                           write_position, add_to_accum, moments, list);
+    bool launched = false;
+    pick_logged<LAUNCH_ACCUMULATE>(launch_axes<LAUNCH_ACCUMULATE>{}, 0u, {camera_kind(opt), quad ? 1u : 0u, list ? 2u : moments ? 1u : 0u}, [&](auto kind, auto few, auto mode) {
+        if constexpr (accumulate_variant_ok(kind, few, mode))
+        {
+            launched = true;
+            hipLaunchKernelGGL((k_accumulate<CameraArg<kind>, few != 0u, mode >= 1u, mode == 2u>), grid, dim3(256), 0, s, rp, camera_arg<kind>(cam, opt), wb.st, accum, position, id,
+                               write_position, add_to_accum, moments, list);
+        }
     });
+    if (!launched) // (pt_set_config admits no frame of more than accumulate_max_pixels local pixels)
+    {
+        fprintf(stderr, "launch_accumulate: no kernel for %u pixels\n", n);
+        abort();
+    }
 }
 uint32_t adaptive_select_blocks(uint32_t n_pixels) { return (n_pixels + kSelectPerBlock - 1u) / kSelectPerBlock; }
 void launch_adaptive_select(hipStream_t s, const f4* accum, const float* moments, uint32_t n_pixels, const AdaptiveCrit& cr, uint32_t* counts, uint2* list,
@@ -3414,7 +3520,7 @@ void launch_bsdf_probe(hipStream_t s, const SceneView& sv, int material, uint32_
 
 void launch_guide_rays(hipStream_t s, const RenderParams& rp, const CameraView& cam, const CameraOptics& opt, RayQueue rq, uint32_t* n_and_heads)
 {
-    pick<CAM_KINDS>(camera_kind(opt), [&](auto kind) {
+    pick_logged<LAUNCH_GUIDE_RAYS>(launch_axes<LAUNCH_GUIDE_RAYS>{}, 0u, {camera_kind(opt)}, [&](auto kind) {
         hipLaunchKernelGGL(k_guide_rays<kind>, dim3((rp.local_pixels + 255u) / 256u), dim3(256), 0, s, rp, camera_arg<kind>(cam, opt), rq, n_and_heads);
     });
 }

@@ -7,20 +7,15 @@ import numpy as np
 import pytest
 
 from conftest import assert_bit_equal
-from emission_common import emission_corner_scene
-from projection_common import ORTHOGRAPHIC, PANORAMA
-from textures_common import box, corner_scene
+from variant_census_common import CAMERAS, DEPTH, EXTRAS, LENS, PinholeExpect, H, M, W  # noqa: F401  (the rooms and expectations are the census's)
+from variant_census_common import expect, room, with_all_classes as _with_all_classes  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 F = np.float32
-W, H, DEPTH, M = 32, 24, 4, 3
-LENS = (0.6, 9.0)
-CAMERAS = {"lens": None, "panorama": (PANORAMA, 360.0, 180.0, 0.0), "ortho": (ORTHOGRAPHIC, 0.0, 0.0, 18.0)}
 # surface -> (room, flat normal maps on top): TEX, TEX + NMAP, TEX + EMTEX, all three.  The corner room keeps its glass boxes (media), the
 # lamps room is built without them, so both halves of the variants run
 SURFACES = {"tex": ("corner", False), "tex_nmap": ("corner", True), "tex_emtex": ("lamps", False), "tex_emtex_nmap": ("lamps", True)}
-EXTRAS = ("extra_mirror", "extra_glass")
 
 
 @pytest.fixture(scope="module")
@@ -30,25 +25,13 @@ def api():
     return api
 
 
-def _with_all_classes(desc):
-    """desc plus an untextured mirror box and a smooth glass box (no volume): with the room's Lambertian walls and GGX boxes the scene then
-    holds all four shading classes"""
-    from path_tracer_amd.scene_desc import Dielectric, Model, SceneDesc, Specular
-    mp, mn = box((7.2, -9.99, -6.5), (9.7, 4.0, -3.5))
-    gp, gn = box((-9.5, -9.99, -9.5), (-6.5, 2.0, -6.5))
-    extras = [Model.new(mp, mn, Specular.new((0.95, 0.9, 0.85)), None, EXTRAS[0]), Model.new(gp, gn, Dielectric.new((0.9, 1.0, 0.95), 1.5), None, EXTRAS[1])]
-    return SceneDesc.new(list(desc.models) + extras, desc.camera, desc.name)
-
-
-_ROOMS = {}
-
-
 def _room(name):
-    """(textured description, untextured equivalent) of a room, both with the two extra boxes"""
-    if name not in _ROOMS:
-        tex, plain = corner_scene(W, H, media=True) if name == "corner" else emission_corner_scene(W, H, media=False)
-        _ROOMS[name] = (_with_all_classes(tex), _with_all_classes(plain))
-    return _ROOMS[name]
+    """(textured description, untextured equivalent) of a room, both with the two extra boxes (and without the census's panel)"""
+    return room(name, panel=False)
+
+
+def _expect(O, name, camera):
+    return expect(O, name, camera, panel=False)
 
 
 def _textured(surface):
@@ -56,42 +39,6 @@ def _textured(surface):
     room, flat = SURFACES[surface]
     tex = _room(room)[0]
     return flat_mapped(tex) if flat else tex
-
-
-class PinholeExpect:
-    """the oracle's own camera: per-sample radiance and whole frames of the first n samples"""
-
-    def __init__(self, O, scene):
-        self.orc = O.Oracle(scene)
-        self.samples = self.orc.render_samples(W, H, 2 * M, max_bounces=DEPTH)
-        self.frames = {}
-
-    def sample(self, s):
-        return (self.samples[s],)
-
-    def frame(self, n):
-        if n not in self.frames:
-            self.frames[n] = self.orc.render(W, H, n, max_bounces=DEPTH)[:3]
-        return self.frames[n]
-
-
-_EXPECT = {}
-
-
-def _expect(O, room, camera):
-    """the oracle's expectation of a plain room under a camera, one per (room, camera)"""
-    key = (room, camera)
-    if key not in _EXPECT:
-        plain = _room(room)[1]
-        if camera == "pinhole":
-            _EXPECT[key] = PinholeExpect(O, plain)
-        elif camera == "lens":
-            from test_gpu_lens import Expect
-            _EXPECT[key] = Expect(O, room, lens=LENS, w=W, h=H, depth=DEPTH, scene=plain)
-        else:
-            from test_gpu_projection import Expect
-            _EXPECT[key] = Expect(O, room, camera, w=W, h=H, depth=DEPTH, scene=plain, params=CAMERAS[camera])
-    return _EXPECT[key]
 
 
 def _renderer(api, surface, camera, flags=0):
