@@ -12,6 +12,9 @@
 //                                          whose view volume is HEIGHT world units high (pt_set_projection); not with --aperture, --move or --slide
 //   examples/headless ... --slide DX DZ   frame f >= 1 first moves the short box to the translation (f * DX, 0, f * DZ) (pt_set_instances + pt_build:
 //                                          the BLASes are kept, the resident scene is patched) and the loop drives frame_moving instead of frame
+//   examples/headless ... --temporal out.png   the loop drives frame_temporal instead: the scripted frames (--move, --slide) go through the temporal
+//                                          stage of the denoiser (reprojected history, history length, luminance moments, then the a-trous levels) and the
+//                                          last frame's result is written
 //   examples/headless ... --denoise den.png   also writes the final frame through the edge-aware denoiser (guides of the last frame's sample)
 //   examples/headless ... --denoise-albedo den.png   the same through the demodulated filter (pt_denoise_albedo): the mean albedo of every pixel
 //                                        is accumulated over the samples that were rendered, the frame divided by it, filtered and multiplied back,
@@ -54,7 +57,7 @@ int main(int argc, char** argv)
     float slide_dx = 0.0f, slide_dz = 0.0f;
     uint32_t gpus = 0, spp = 64;
     std::vector<int32_t> devices;
-    std::string models_dir = "models/cornell", out = "", load_state = "", save_state = "", denoise_out = "", denoise_albedo_out = "";
+    std::string models_dir = "models/cornell", out = "", load_state = "", save_state = "", denoise_out = "", denoise_albedo_out = "", temporal_out = "";
     bool render_mode = false;
     uint32_t render_first = 0, render_count = 0;
     float aperture = 0.0f, focus = 950.0f; // main.rs:127's values: a pinhole
@@ -77,6 +80,7 @@ int main(int argc, char** argv)
         else if (a == "--models") models_dir = next("--models");
         else if (a == "--out") out = next("--out");
         else if (a == "--denoise") denoise_out = next("--denoise");
+        else if (a == "--temporal") temporal_out = next("--temporal");
         else if (a == "--denoise-albedo") denoise_albedo_out = next("--denoise-albedo");
         else if (a == "--follow") follow = (uint32_t)std::atoi(next("--follow"));
         else if (a == "--mirror-glass") mirror_glass = true;
@@ -120,7 +124,7 @@ int main(int argc, char** argv)
         }
         else if (a == "--help" || a == "-h")
         {
-            std::printf("usage: %s [--width W] [--height H] [--frames N] [--bounces B] [--move] [--slide DX DZ] [--models DIR] [--out file.png] [--denoise file.png] [--denoise-albedo file.png] [--follow K] [--mirror-glass] [--aperture A --focus F] [--projection panorama[:SX:SY]|ortho:HEIGHT] [--bake-probes NX NY NZ SPP file.txt] [--bake-lightmap W H SPP PASSES file.txt] [--checker N] [--emission-checker N] [--normal-ripples N]\n", argv[0]);
+            std::printf("usage: %s [--width W] [--height H] [--frames N] [--bounces B] [--move] [--slide DX DZ] [--models DIR] [--out file.png] [--temporal file.png] [--denoise file.png] [--denoise-albedo file.png] [--follow K] [--mirror-glass] [--aperture A --focus F] [--projection panorama[:SX:SY]|ortho:HEIGHT] [--bake-probes NX NY NZ SPP file.txt] [--bake-lightmap W H SPP PASSES file.txt] [--checker N] [--emission-checker N] [--normal-ripples N]\n", argv[0]);
             return 0;
         }
         else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
@@ -129,6 +133,12 @@ int main(int argc, char** argv)
     {
         // both want the UVs of cb_main.obj: the checker and the lightmap the planar (x, z) ones, the ripples (x, y + z)
         std::fprintf(stderr, "--normal-ripples cannot be combined with --checker or --bake-lightmap: each sets the UVs of cb_main.obj\n");
+        return 2;
+    }
+    if (!temporal_out.empty() && (!out.empty() || !denoise_out.empty() || !denoise_albedo_out.empty() || render_mode || gpus > 0 || !devices.empty()))
+    {
+        // frame_temporal leaves the accumulation alone: there is nothing in it for these to write
+        std::fprintf(stderr, "--temporal cannot be combined with --out, --denoise, --denoise-albedo, --render or --gpus: its frames do not accumulate\n");
         return 2;
     }
     try
@@ -322,7 +332,8 @@ int main(int argc, char** argv)
                 const float f = (float)frame;
                 renderer.set_instances(5, {Affine3A{{1, 0, 0, f * slide_dx, 0, 1, 0, 0.0f, 0, 0, 1, f * slide_dz}}});
             }
-            if (slide) renderer.frame_moving(frame, last_inv_proj);
+            if (!temporal_out.empty()) renderer.frame_temporal(frame, last_inv_proj);
+            else if (slide) renderer.frame_moving(frame, last_inv_proj);
             else renderer.frame(frame, last_inv_proj);       // the pixel loop + state.update   main.rs:181-215
             last_inv_proj = renderer.inv_projection();       // main.rs:216
         }
@@ -332,6 +343,7 @@ int main(int argc, char** argv)
         std::printf("{\"frames\": %u, \"width\": %u, \"height\": %u, \"ms_per_frame\": %.3f, \"Mray_per_s\": %.1f}\n", frames, width, height,
                     1e3 * seconds / (frames ? frames : 1), rays / seconds / 1e6);
         if (!out.empty()) renderer.write_image(out);         // ImageHelper::write_image
+        if (!temporal_out.empty() && frames) renderer.write_denoised_image(temporal_out);
         if (!denoise_out.empty() && frames)
         {
             // the interactive recipe: guides of the last frame's sample, then the filter (pt_api.h)

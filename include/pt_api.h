@@ -655,6 +655,75 @@ int pt_denoise_albedo(pt_ctx* ctx, const pt_denoise_params* p, uint32_t albedo_s
 int pt_post_denoise_albedo(pt_ctx* ctx, uint32_t w, uint32_t h, const pt_denoise_params* p, const float* accum_rgba, const float* position_xyzt,
                            const float* normal_xyz, const uint32_t* model, const float* albedo_rgb, const float* sumsq, float* out_rgba);
 
+/* ---- the temporal stage: reprojected history, history length and luminance moments (SVGF's temporal part) ------------------------------ */
+/* pt_frame_moving's State::update is the reference's TAA blend (a fixed 15 %, acc.w = 1, no second moment), so pt_denoise after it falls back to
+ * the 7 x 7 spatial variance, which at 1 spp is noise.  pt_frame_temporal keeps, per pixel and between calls, a history H = (C.r, C.g, C.b, N)
+ * (N: the history length, an integer held in f32, 0 = none, at most 65535), the moments M = (mu1, mu2) of luminance, and the previous call's
+ * guides X' | t' (position), n' (normal), m' (model word); it accepts a reprojected tap only where the geometry agrees and hands pt_denoise's
+ * levels a variance each pixel has observed over time.  pt_frame, pt_frame_moving, pt_denoise and pt_denoise_albedo are what they were, bit
+ * for bit, and a context that never calls the functions below allocates and launches nothing for them.
+ *
+ * ONE STEP for pixel p = (x, y) of a w x h frame, in binary32 with every operation rounded once, no contraction, in this order.
+ *   l(c) = (0.2126f * c.r + 0.7152f * c.g) + 0.0722f * c.b.  Inputs: cur = this frame's finalised sample rgb; the current guides x_p | t_p,
+ *   n_p, m_p; xprev_p = the hit carried back as pt_frame_moving defines X_PREV (x_p where nothing moved); nprev_p = n_p carried back by the
+ *   LINEAR parts of the same two matrices (the transform is rigid, so a direction transforms by the 3 x 3):
+ *       o[k] = (inv[k][0] * n.x + inv[k][1] * n.y) + inv[k][2] * n.z;  nprev[k] = (prv[k][0] * o.x + prv[k][1] * o.y) + prv[k][2] * o.z
+ *   and n_p with no arithmetic where X_PREV does none; the velocity vel_p.
+ *   1. TAPS, a list of (q, b).  At rest (NOT MOVED of pt_frame_moving; a NULL velocity in pt_post_temporal): [(p, 1)], no arithmetic.  Moved:
+ *        cu = ((float)x + 0.5f) / (float)w;  cv likewise;  pu = cu - vel.x;  pv = cv - vel.y;  fx = pu * w - 0.5f;  fy = pv * h - 0.5f;
+ *        unless fx >= -1 && fx < w && fy >= -1 && fy < h (tested in float, before any integer conversion: a NaN or infinite velocity gives
+ *        the empty list) the list is empty; else x0 = floor(fx); y0 = floor(fy); tx = fx - x0; ty = fy - y0; the taps are (x0 + i, y0 + j),
+ *        j outer, i inner, each in {0, 1}, with b = (i ? tx : 1 - tx) * (j ? ty : 1 - ty).
+ *   2. A tap is VALID when q lies inside the image, b > 0, H_q.N > 0, m'_q == m_p (the whole word) and, when m_p is a hit (not 0xffffffff),
+ *        (nprev_p.x * n'_q.x + nprev_p.y * n'_q.y) + nprev_p.z * n'_q.z >= normal_min   and, with d = X'_q.xyz - xprev_p per component,
+ *        |(nprev_p.x * d.x + nprev_p.y * d.y) + nprev_p.z * d.z| <= plane_max * t_p.      Two misses need only the model test.
+ *   3. Over the valid taps in list order: sw += b; sc += b * H_q.rgb (per channel); s1 += b * M_q.mu1; s2 += b * M_q.mu2; Nmin = min(Nmin, H_q.N).
+ *   4. sw > 0:  hist = sc / sw; m1 = s1 / sw; m2 = s2 / sw;  N = min(Nmin + 1, 65535);  a = max(alpha, 1.0f / N); am = max(alpha_moments, 1.0f / N);
+ *               C = hist * (1 - a) + cur * a;  mu1 = m1 * (1 - am) + l(cur) * am;  mu2 = m2 * (1 - am) + (l(cur) * l(cur)) * am.
+ *      else (disoccluded, or the first frame):  N = 1;  C = cur;  mu1 = l(cur);  mu2 = l(cur) * l(cur).
+ *   5. VARIANCE handed to the levels.  N >= 4: v = mu2 - mu1 * mu1; if (!(v > 0)) v = 0; var = v * a -- the variance of the mean while a = 1 / N,
+ *      within a factor 2 - a of the moving average's afterwards.  N < 4: pt_denoise's 7 x 7 spatial variance of the image C under the CURRENT
+ *      guides, exactly as stated above, every pixel valid.
+ *   6. FILTER: pt_denoise's levels, unchanged, on (C, var) with the current guides; every pixel is valid.
+ *   7. STORE: H.rgb = C (feedback = 0) or the rgb of level 0's output (feedback = 1, SVGF's feedback); H.N = N; M = (mu1, mu2); the current
+ *      guides become X', n', m'.
+ * pt_frame_temporal renders sample frame_index and its first-hit guides exactly as pt_frame_moving does (the same input, position, id history,
+ * SNAPSHOT, MOVED test, X_PREV and velocity; calls of either kind advance the one snapshot; the same refusals under a panoramic or
+ * orthographic camera) and then, instead of State::update, runs steps 1-7.  It leaves the accumulation and the moments Q alone (pt_denoise's
+ * view of them is not changed by it) and leaves the guides valid.  data / position / id as pt_frame_moving; out_rgba (may be NULL) receives
+ * the filtered frame (c, 1), which also counts as the last denoised frame for pt_write_denoised_image.
+ * pt_read_temporal copies out H as stored (colour_n: rgb | N), M (moments2) and step 5's variance of the last step; any pointer may be NULL;
+ * PT_ERR_STATE when there is no history.  pt_reset_temporal drops the history; so do pt_set_config with a new image size, pt_set_projection
+ * and pt_set_lens with another aperture or focus than the one in force.  Camera moves and pt_set_instances + pt_build do not: they are what the pass exists for.
+ * pt_post_temporal runs steps 1-5 and the feedback = 0 form of step 7 on caller images (host pointers, row-major w * h): the previous H, M,
+ * X' | t', n' and m'; the current input rgba, position xyzt, normal xyz and model; xprev (NULL selects the position), nprev (NULL selects the
+ * normal) and the velocity (NULL selects rest); out: H (rgb | N), M and the variance.  on_device 0 evaluates on the host and touches no GPU;
+ * 1 runs the kernels over the same per-pixel function.  denoise supplies sigma_normal and sigma_plane of step 5's spatial variance.
+ * Errors, before any device call and changing nothing: PT_ERR_ARG for NULL params or images, alpha or alpha_moments outside [0, 1] or NaN,
+ * normal_min outside [-1, 1] or NaN, plane_max negative or not finite, feedback > 1, a non-zero reserved word, and whatever pt_denoise
+ * refuses; PT_ERR_STATE as for pt_frame_moving (world_size > 1 included).
+ * The interactive recipe: pt_frame_temporal(k, last_inv_projection), then present its result.
+ * Out of scope: followed guides as the history's guides; albedo demodulation of the history; a 3 x 3 rescue search for disoccluded pixels;
+ * pt_multi_* variants. */
+typedef struct pt_temporal_params
+{
+    float alpha;          /* floor of the colour blend weight, in [0, 1]; 0 => 0.2 */
+    float alpha_moments;  /* floor of the moments blend weight, in [0, 1]; 0 => 0.2 */
+    float normal_min;     /* least nprev . n' a tap may have, in [-1, 1]; 0 => 0.9 */
+    float plane_max;      /* greatest plane distance of a tap, as a fraction of t_p, finite and >= 0; 0 => 0.02 */
+    uint32_t feedback;    /* 0: the history keeps C; 1: it keeps level 0's output */
+    uint32_t reserved[3]; /* must be 0 */
+} pt_temporal_params;
+int pt_frame_temporal(pt_ctx* ctx, uint32_t frame_index, const float* last_inv_projection, const pt_temporal_params* params,
+                      const pt_denoise_params* denoise, float* data_rgba, float* position_xyzt, uint32_t* id, float* out_rgba);
+int pt_read_temporal(pt_ctx* ctx, float* colour_n, float* moments2, float* variance);
+int pt_reset_temporal(pt_ctx* ctx);
+int pt_post_temporal(pt_ctx* ctx, int on_device, uint32_t w, uint32_t h, const pt_temporal_params* params, const pt_denoise_params* denoise,
+                     const float* prev_colour_n, const float* prev_moments2, const float* prev_position_xyzt, const float* prev_normal_xyz,
+                     const uint32_t* prev_model, const float* input_rgba, const float* position_xyzt, const float* normal_xyz, const uint32_t* model,
+                     const float* xprev_xyzt, const float* nprev_xyz, const float* velocity, float* out_colour_n, float* out_moments2,
+                     float* out_variance);
+
 /* ---- caller-supplied rays: "what radiance arrives along THIS ray?" ---------------------------------------------------- */
 /* Every render entry point above starts its paths at the context's camera.  pt_integrate_rays runs the same wavefront integrator over rays the
  * caller supplies: light probes and lightmaps, cameras the library does not model (stereo pairs, panoramas, fisheyes, orthographic views,

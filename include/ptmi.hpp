@@ -260,6 +260,16 @@ public:
         }
         else check(pt_frame_moving(ctx_, frame_index, last_inv_projection.data(), nullptr, nullptr, nullptr));
     }
+    // frame_moving's render, guides and velocity, then the temporal stage of the denoiser instead of State::update (pt_frame_temporal): the
+    // history is reprojected through geometry tests, blended by its length and filtered with the variance the pixels observed over time.  The
+    // result stays on the device for write_denoised_image; filtered (W*H*4 floats) receives it too
+    void frame_temporal(uint32_t frame_index, const Mat4& last_inv_projection, const pt_temporal_params& t = pt_temporal_params{},
+                        const pt_denoise_params& d = pt_denoise_params{}, std::vector<float>* filtered = nullptr)
+    {
+        if (filtered) filtered->resize((size_t)width_ * height_ * 4);
+        check(pt_frame_temporal(ctx_, frame_index, last_inv_projection.data(), &t, &d, nullptr, nullptr, nullptr, filtered ? filtered->data() : nullptr));
+    }
+    void reset_temporal() { check(pt_reset_temporal(ctx_)); }
     // replaces the instance matrices of model `model` (index in Scene::models) and rebuilds: BLASes are kept, the TLASes are built again and,
     // when the instance count is unchanged, the next render patches the resident scene in place
     void set_instances(int model, const std::vector<Affine3A>& matrices)

@@ -47,6 +47,7 @@ EXPORTS = [
     "pt_set_projection", "pt_get_projection",
     "pt_bake_lightmap", "pt_lightmap_texels", "pt_lightmap_ray", "pt_lightmap_dilate",
     "pt_render_guides_followed", "pt_read_guide_hops", "pt_accumulate_albedo_followed", "pt_guide_follow_dir",
+    "pt_frame_temporal", "pt_read_temporal", "pt_reset_temporal", "pt_post_temporal",
 ]
 
 
@@ -97,6 +98,12 @@ class Adaptive(C.Structure):
 class DenoiseParams(C.Structure):
     """pt_denoise_params: the a-trous filter's levels and edge-stopping widths (include/pt_api.h); 0 selects each default"""
     _fields_ = [("iterations", C.c_uint32), ("sigma_luminance", C.c_float), ("sigma_normal", C.c_uint32), ("sigma_plane", C.c_float)]
+
+
+class TemporalParams(C.Structure):
+    """pt_temporal_params: the temporal stage's blend floors, tap tests and feedback switch (include/pt_api.h); 0 selects each default"""
+    _fields_ = [("alpha", C.c_float), ("alpha_moments", C.c_float), ("normal_min", C.c_float), ("plane_max", C.c_float), ("feedback", C.c_uint32),
+                ("reserved", C.c_uint32 * 3)]
 
 
 class GuideParams(C.Structure):
@@ -273,6 +280,10 @@ def lib():
         L.pt_read_guide_hops.argtypes = [vp, vp]
         L.pt_accumulate_albedo_followed.argtypes = [vp, u32, u32, C.POINTER(GuideParams)]
         L.pt_guide_follow_dir.argtypes = [vp, C.c_int, C.c_int, u32, vp, vp, vp, vp]
+        L.pt_frame_temporal.argtypes = [vp, u32, vp, C.POINTER(TemporalParams), C.POINTER(DenoiseParams), vp, vp, vp, vp]
+        L.pt_read_temporal.argtypes = [vp, vp, vp, vp]
+        L.pt_reset_temporal.argtypes = [vp]
+        L.pt_post_temporal.argtypes = [vp, C.c_int, u32, u32, C.POINTER(TemporalParams), C.POINTER(DenoiseParams)] + [vp] * 15
         _lib = L
     return _lib
 
@@ -796,6 +807,54 @@ class Renderer:
         prm = DenoiseParams(iterations, sigma_luminance, sigma_normal, sigma_plane)
         self._chk(self.L.pt_post_denoise(self.ctx, w, h, C.byref(prm), _p(accum), _p(position), _p(normal), _p(model), _p(q), _p(out)))
         return out
+
+    # ---- the temporal stage: reprojected history, history length and luminance moments (pt_frame_temporal)
+    def frame_temporal(self, frame_index, last_inv_projection=None, ident=None, download=True, alpha=0.0, alpha_moments=0.0, normal_min=0.0,
+                       plane_max=0.0, feedback=0, iterations=0, sigma_luminance=0.0, sigma_normal=0, sigma_plane=0.0):
+        """frame_moving's render, guides and velocity, then the temporal stage instead of State::update: the history is reprojected through
+        geometry tests, blended by its length, and the a-trous levels run on it with the variance the pixels observed over time.  Returns
+        data, position, id, result (download=False: None; the result stays on the device for write_denoised_image)"""
+        m = None if last_inv_projection is None else np.ascontiguousarray(last_inv_projection, np.float32)
+        tp = TemporalParams(alpha, alpha_moments, normal_min, plane_max, feedback)
+        dp = DenoiseParams(iterations, sigma_luminance, sigma_normal, sigma_plane)
+        if not download:
+            self._chk(self.L.pt_frame_temporal(self.ctx, frame_index, _p(m), C.byref(tp), C.byref(dp), None, None, None, None))
+            return None
+        h, w = self.cfg.height, self.cfg.width
+        data = np.zeros((h, w, 4), np.float32); pos = np.zeros((h, w, 4), np.float32); out = np.zeros((h, w, 4), np.float32)
+        idb = np.zeros((h, w), np.uint32) if ident is None else ident
+        self._chk(self.L.pt_frame_temporal(self.ctx, frame_index, _p(m), C.byref(tp), C.byref(dp), _p(data), _p(pos), _p(idb), _p(out)))
+        return data, pos, idb, out
+
+    def read_temporal(self):
+        """the temporal stage's state after the last frame_temporal: history (rgb | N), moments (mu1, mu2), the variance handed to the levels"""
+        h, w = self.cfg.height, self.cfg.width
+        cn = np.zeros((h, w, 4), np.float32); mom = np.zeros((h, w, 2), np.float32); var = np.zeros((h, w), np.float32)
+        self._chk(self.L.pt_read_temporal(self.ctx, _p(cn), _p(mom), _p(var)))
+        return cn, mom, var
+
+    def reset_temporal(self):
+        self._chk(self.L.pt_reset_temporal(self.ctx))
+
+    def post_temporal(self, prev, cur, xprev=None, nprev=None, velocity=None, on_device=False, alpha=0.0, alpha_moments=0.0, normal_min=0.0,
+                      plane_max=0.0, sigma_normal=0, sigma_plane=0.0):
+        """one temporal step (without the levels) on caller images.  prev = (history h x w x 4, moments h x w x 2, position h x w x 4, normal
+        h x w x 3, model h x w) of the previous call, cur = (input h x w x 4, position, normal, model) of this frame; xprev / nprev None: the
+        position / the normal; velocity None: at rest.  on_device False evaluates on the host and touches no GPU.  Returns history, moments,
+        variance"""
+        ph, pm, px, pn, pmod = (np.ascontiguousarray(a, t) for a, t in zip(prev, (np.float32,) * 4 + (np.uint32,)))
+        ci, cx, cn, cmod = (np.ascontiguousarray(a, t) for a, t in zip(cur, (np.float32,) * 3 + (np.uint32,)))
+        h, w = ci.shape[:2]
+        opt = [None if a is None else np.ascontiguousarray(a, np.float32) for a in (xprev, nprev, velocity)]
+        sizes = [(ph, 4), (pm, 2), (px, 4), (pn, 3), (pmod, 1), (ci, 4), (cx, 4), (cn, 3), (cmod, 1), (opt[0], 4), (opt[1], 3), (opt[2], 2)]
+        if any(a is not None and a.size != h * w * k for a, k in sizes):
+            raise PtError(-1, f"post_temporal: images are not those of a {w}x{h} frame")
+        out_h = np.zeros((h, w, 4), np.float32); out_m = np.zeros((h, w, 2), np.float32); out_v = np.zeros((h, w), np.float32)
+        tp = TemporalParams(alpha, alpha_moments, normal_min, plane_max, 0)
+        dp = DenoiseParams(0, 0.0, sigma_normal, sigma_plane)
+        self._chk(self.L.pt_post_temporal(self.ctx, int(bool(on_device)), w, h, C.byref(tp), C.byref(dp), _p(ph), _p(pm), _p(px), _p(pn), _p(pmod), _p(ci),
+                                          _p(cx), _p(cn), _p(cmod), _p(opt[0]), _p(opt[1]), _p(opt[2]), _p(out_h), _p(out_m), _p(out_v)))
+        return out_h, out_m, out_v
 
     # ---- mean albedo and the demodulated filter (pt_denoise_albedo)
     def accumulate_albedo(self, first_sample: int, n_samples: int, follow: int = 0):

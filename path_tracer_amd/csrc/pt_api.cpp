@@ -199,6 +199,13 @@ struct pt_ctx
     DevBuf d_motion, d_xprev;
     bool denoised_valid = false;
 
+    // temporal stage (pt_frame_temporal): the history C | N and the moments, each a pair (a pixel gathers its neighbours' records, so a step
+    // reads one and writes the other; tp_cur holds the history), the previous call's guides X' | t' and n' | m', the variance handed to the
+    // levels and the carried-back normals.  temporal_valid: there is a history.  Nothing is allocated until the first call.
+    DevBuf d_tp_hist[2], d_tp_mom[2], d_tp_x, d_tp_g, d_tp_var, d_tp_nprev;
+    int tp_cur = 0;
+    bool temporal_valid = false;
+
     // pt_integrate_rays_device: the callers' stream keys side by side, 8 bytes per ray of the longest list so far (kept: allocating and freeing
     // it per call would synchronise the device twice per call).  Nothing is allocated until the first call.
     DevBuf d_ray_keys;
@@ -1663,6 +1670,7 @@ int pt_set_config(pt_ctx* c, const pt_config* cfg)
     if (c->local_pixels != old_px)
     {
         c->denoised_valid = false;
+        c->temporal_valid = false; // the history belongs to the old image size
         c->d_accum.reset();
         c->d_position.reset();
         c->d_id.reset();
@@ -1958,6 +1966,8 @@ int pt_set_lens(pt_ctx* c, float aperture, float focus)                         
     if (!(aperture >= 0.0f) || !std::isfinite(aperture)) return fail(c, PT_ERR_ARG, "aperture must be finite and >= 0");
     if (aperture > 0.0f && (!(focus > 0.0f) || !std::isfinite(focus))) return fail(c, PT_ERR_ARG, "focus must be finite and > 0 when aperture > 0");
     if (aperture > 0.0f && c->scene.camera.proj_kind != PROJ_PERSPECTIVE) return fail(c, PT_ERR_STATE, "a lens needs the perspective projection (pt_set_projection)");
+    // the temporal history belongs to the old lens (setting the lens in force again, as a binding's set_camera does, keeps it)
+    if (bits(c->scene.camera.aperture) != bits(aperture) || bits(c->scene.camera.focus) != bits(focus)) c->temporal_valid = false;
     c->scene.camera.aperture = aperture;
     c->scene.camera.focus = focus;
     c->scene_version++; // the guides belong to the old camera; pt_multi replicates the lens with it
@@ -1987,6 +1997,7 @@ int pt_set_projection(pt_ctx* c, const pt_projection* p)
     cam.span_y_deg = p->span_y_deg;
     cam.ortho_height = p->ortho_height;
     c->scene_version++; // the guides and the mean-albedo sums belong to the old camera; pt_multi replicates the projection with it
+    c->temporal_valid = false;
     return PT_OK;
 }
 
@@ -2324,8 +2335,9 @@ int prepare_motion(pt_ctx* c, bool* world_moved)
 
 int render_guides_locked(pt_ctx* c, uint32_t sample, uint32_t max_hops = 0u);
 
-// pt_frame (moving = false) and pt_frame_moving under the context's lock
-int frame_locked(pt_ctx* c, uint32_t frame_index, const float* last_inv_projection, float* data, float* position, uint32_t* id, bool moving)
+// What pt_frame, pt_frame_moving and pt_frame_temporal share, in two parts.  frame_render: the refusals, then sample frame_index of every pixel
+// into d_input with the position and the id history beside it.
+int frame_render(pt_ctx* c, uint32_t frame_index, const float* last_inv_projection, const uint32_t* id)
 {
     int r;
     if ((r = precheck(c))) return r;
@@ -2350,7 +2362,20 @@ int frame_locked(pt_ctx* c, uint32_t frame_index, const float* last_inv_projecti
     if ((r = batch_begin(br, c, BatchSpec{0, frame_index, 1u, render_rect(c), true, (f4*)c->d_input.p, true})) || (r = run_group(c, &br, 1, after)) ||
         (r = harvest_batch(c, 0)))
         return r;
-    c->moments_valid = false; // State::update adds (or reprojects) the sample without Q: the moments no longer describe the accumulation
+    return PT_OK;
+}
+
+// frame_velocity: the MOVED test and, where it holds, the velocity in d_velocity.  world: an instance moved, so d_xprev holds X_PREV and
+// d_motion the table that made it.
+struct FrameMoved
+{
+    bool moved = false, world = false;
+};
+int frame_velocity(pt_ctx* c, uint32_t frame_index, const float* last_inv_projection, bool moving, FrameMoved& fm)
+{
+    int r;
+    const bool projected = c->scene.camera.proj_kind != PROJ_PERSPECTIVE;
+    const size_t px = c->local_pixels;
     hipStream_t s = c->stream;
     const int w = (int)c->cfg.width, h = (int)c->cfg.height;
     bool moved = false;                                                                                                    // state.rs:549 `inv_projection == last_inv_projection`
@@ -2372,10 +2397,37 @@ int frame_locked(pt_ctx* c, uint32_t frame_index, const float* last_inv_projecti
         vel_from = (const f4*)c->d_xprev.p;
         moved = true;
     }
-    if (!moved) launch_post_accumulate(s, (uint32_t)px, (const f4*)c->d_input.p, (f4*)c->d_accum.p);           // state.rs:561-566
+    if (moved) launch_post_velocity(s, w, h, vel_from, last_inv_projection ? last_inv_projection : cur, (float*)c->d_velocity.p);  // state.rs:569-572
+    fm.moved = moved;
+    fm.world = world_moved;
+    return PT_OK;
+}
+
+// the snapshot the next pt_frame_moving / pt_frame_temporal compares with: this build's matrices (a render needs a built scene, so the
+// models hold exactly them)
+void frame_snapshot(pt_ctx* c)
+{
+    if (c->snap_valid && c->snap_build == c->scene.tlas_builds) return;
+    c->snap.resize(c->scene.models.size());
+    for (size_t m = 0; m < c->scene.models.size(); ++m) c->snap[m] = c->scene.models[m].matrices;
+    c->snap_valid = true;
+    c->snap_build = c->scene.tlas_builds;
+}
+
+// pt_frame (moving = false) and pt_frame_moving under the context's lock
+int frame_locked(pt_ctx* c, uint32_t frame_index, const float* last_inv_projection, float* data, float* position, uint32_t* id, bool moving)
+{
+    int r;
+    if ((r = frame_render(c, frame_index, last_inv_projection, id))) return r;
+    c->moments_valid = false; // State::update adds (or reprojects) the sample without Q: the moments no longer describe the accumulation
+    FrameMoved fm;
+    if ((r = frame_velocity(c, frame_index, last_inv_projection, moving, fm))) return r;
+    const size_t px = c->local_pixels;
+    hipStream_t s = c->stream;
+    const int w = (int)c->cfg.width, h = (int)c->cfg.height;
+    if (!fm.moved) launch_post_accumulate(s, (uint32_t)px, (const f4*)c->d_input.p, (f4*)c->d_accum.p);        // state.rs:561-566
     else
     {
-        launch_post_velocity(s, w, h, vel_from, last_inv_projection ? last_inv_projection : cur, (float*)c->d_velocity.p);  // state.rs:569-572
         launch_post_reproject(s, w, h, (const f4*)c->d_input.p, (const f4*)c->d_accum.p, (const float*)c->d_velocity.p,
                               (const uint32_t*)c->d_id.p, (f4*)c->d_output.p);                                              // state.rs:574-578
         HIPCHK(c, hipMemcpyAsync(c->d_accum.p, c->d_output.p, px * 16, hipMemcpyDeviceToDevice, s));                        // state.rs:583
@@ -2385,14 +2437,83 @@ int frame_locked(pt_ctx* c, uint32_t frame_index, const float* last_inv_projecti
     if (id) HIPCHK(c, hipMemcpyAsync(id, c->d_id.p, px * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     HIPCHK(c, hipGetLastError());
-    if (moving && !(c->snap_valid && c->snap_build == c->scene.tlas_builds))
+    if (moving) frame_snapshot(c);
+    return PT_OK;
+}
+
+// the temporal parameters with their defaults filled in; everything that can be refused without touching the device
+int temporal_params(pt_ctx* c, const pt_temporal_params* p, TemporalK& k)
+{
+    if (!p) return fail(c, PT_ERR_ARG, "null pt_temporal_params");
+    if (!(p->alpha >= 0.0f && p->alpha <= 1.0f)) return fail(c, PT_ERR_ARG, "pt_temporal_params.alpha must lie in [0, 1]");
+    if (!(p->alpha_moments >= 0.0f && p->alpha_moments <= 1.0f)) return fail(c, PT_ERR_ARG, "pt_temporal_params.alpha_moments must lie in [0, 1]");
+    if (!(p->normal_min >= -1.0f && p->normal_min <= 1.0f)) return fail(c, PT_ERR_ARG, "pt_temporal_params.normal_min must lie in [-1, 1]");
+    if (!(p->plane_max >= 0.0f) || !std::isfinite(p->plane_max)) return fail(c, PT_ERR_ARG, "pt_temporal_params.plane_max must be finite and >= 0");
+    if (p->feedback > 1u) return fail(c, PT_ERR_ARG, "pt_temporal_params.feedback must be 0 or 1");
+    for (uint32_t w : p->reserved)
+        if (w != 0u) return fail(c, PT_ERR_ARG, "pt_temporal_params::reserved must be 0");
+    k.alpha = p->alpha != 0.0f ? p->alpha : 0.2f;
+    k.alpha_moments = p->alpha_moments != 0.0f ? p->alpha_moments : 0.2f;
+    k.normal_min = p->normal_min != 0.0f ? p->normal_min : 0.9f;
+    k.plane_max = p->plane_max != 0.0f ? p->plane_max : 0.02f;
+    return PT_OK;
+}
+
+// pt_frame_temporal under the context's lock
+int frame_temporal_locked(pt_ctx* c, uint32_t frame_index, const float* last_inv_projection, const pt_temporal_params* tp, const pt_denoise_params* dp, float* data,
+                          float* position, uint32_t* id, float* out)
+{
+    int r;
+    TemporalK tk{};
+    DenoiseK k{};
+    if ((r = temporal_params(c, tp, tk)) || (r = denoise_params(c, dp, k))) return r;
+    if ((r = frame_render(c, frame_index, last_inv_projection, id))) return r;
+    FrameMoved fm;
+    if ((r = frame_velocity(c, frame_index, last_inv_projection, true, fm))) return r;
+    const size_t px = c->local_pixels;
+    hipStream_t s = c->stream;
+    const int w = (int)c->cfg.width, h = (int)c->cfg.height;
+    for (int i = 0; i < 2; ++i)
+        if ((r = dev_alloc(c, c->d_tp_hist[i], px * 16)) || (r = dev_alloc(c, c->d_tp_mom[i], px * 8))) return r;
+    if ((r = dev_alloc(c, c->d_tp_x, px * 16)) || (r = dev_alloc(c, c->d_tp_g, px * 16)) || (r = dev_alloc(c, c->d_tp_var, px * 4)) ||
+        (r = denoise_scratch(c, px)) || (r = dev_alloc(c, c->d_dn_out, px * 16)))
+        return r;
+    const int from = c->tp_cur, to = 1 - c->tp_cur;
+    if (!c->temporal_valid)
     {
-        // the snapshot the next call compares with: this build's matrices (a render needs a built scene, so the models hold exactly them)
-        c->snap.resize(c->scene.models.size());
-        for (size_t m = 0; m < c->scene.models.size(); ++m) c->snap[m] = c->scene.models[m].matrices;
-        c->snap_valid = true;
-        c->snap_build = c->scene.tlas_builds;
+        // no history: N = 0 everywhere fails every tap (the guides are cleared with it so that no word of them is read unwritten)
+        HIPCHK(c, hipMemsetAsync(c->d_tp_hist[from].p, 0, px * 16, s));
+        HIPCHK(c, hipMemsetAsync(c->d_tp_g.p, 0, px * 16, s));
     }
+    const f4* xprev = (const f4*)c->d_gpos.p;
+    const f4* nprev = (const f4*)c->d_gnrm.p;
+    if (fm.world)
+    {
+        if ((r = dev_alloc(c, c->d_tp_nprev, px * 16))) return r;
+        launch_temporal_motion_normal(s, (uint32_t)px, (const f4*)c->d_gnrm.p, (const uint32_t*)c->d_ginst.p, (uint32_t)c->scene.world.instances.size(),
+                                      (const MotionRow*)c->d_motion.p, (f4*)c->d_tp_nprev.p);
+        xprev = (const f4*)c->d_xprev.p;
+        nprev = (const f4*)c->d_tp_nprev.p;
+    }
+    const TemporalImages im{w, h, (const f4*)c->d_tp_hist[from].p, (const f2*)c->d_tp_mom[from].p, (const f4*)c->d_tp_x.p, (const f4*)c->d_tp_g.p,
+                            (const f4*)c->d_input.p, (const f4*)c->d_gpos.p, (const f4*)c->d_gnrm.p, (const uint32_t*)c->d_gmodel.p, xprev, nprev,
+                            fm.moved ? (const f2*)c->d_velocity.p : nullptr};
+    launch_temporal_reproject(s, im, tk, (f4*)c->d_tp_hist[to].p, (f2*)c->d_tp_mom[to].p);
+    launch_temporal_variance(s, w, h, k, tk.alpha, (const f4*)c->d_tp_hist[to].p, (const f2*)c->d_tp_mom[to].p, (const f4*)c->d_gpos.p, (const f4*)c->d_gnrm.p,
+                             (const uint32_t*)c->d_gmodel.p, (f4*)c->d_dn_a.p, (f4*)c->d_dn_nv.p, (float*)c->d_tp_var.p);
+    launch_temporal_filter(s, w, h, k, tp->feedback != 0u, (const f4*)c->d_gpos.p, (const f4*)c->d_gnrm.p, (const uint32_t*)c->d_gmodel.p, (f4*)c->d_dn_a.p,
+                           (f4*)c->d_dn_b.p, (f4*)c->d_dn_nv.p, (f4*)c->d_dn_out.p, (f4*)c->d_tp_hist[to].p, (f4*)c->d_tp_x.p, (f4*)c->d_tp_g.p);
+    c->temporal_valid = false; // until the step is known to have run
+    if (data) HIPCHK(c, hipMemcpyAsync(data, c->d_input.p, px * 16, hipMemcpyDeviceToHost, s));
+    if (position) HIPCHK(c, hipMemcpyAsync(position, c->d_position.p, px * 16, hipMemcpyDeviceToHost, s));
+    if (id) HIPCHK(c, hipMemcpyAsync(id, c->d_id.p, px * 4, hipMemcpyDeviceToHost, s));
+    if (out) HIPCHK(c, hipMemcpyAsync(out, c->d_dn_out.p, px * 16, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    HIPCHK(c, hipGetLastError());
+    c->tp_cur = to;
+    c->temporal_valid = true;
+    c->denoised_valid = true;
+    frame_snapshot(c);
     return PT_OK;
 }
 } // namespace
@@ -2411,6 +2532,112 @@ int pt_frame_moving(pt_ctx* c, uint32_t frame_index, const float* last_inv_proje
     if (!c) return PT_ERR_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
     return frame_locked(c, frame_index, last_inv_projection, data, position, id, true);
+}
+
+int pt_frame_temporal(pt_ctx* c, uint32_t frame_index, const float* last_inv_projection, const pt_temporal_params* tp, const pt_denoise_params* dp, float* data,
+                      float* position, uint32_t* id, float* out)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    return frame_temporal_locked(c, frame_index, last_inv_projection, tp, dp, data, position, id, out);
+}
+
+int pt_read_temporal(pt_ctx* c, float* colour_n, float* moments2, float* variance)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->temporal_valid) return fail(c, PT_ERR_STATE, "no temporal history: pt_frame_temporal first");
+    const size_t px = c->local_pixels;
+    if (colour_n) HIPCHK(c, hipMemcpyAsync(colour_n, c->d_tp_hist[c->tp_cur].p, px * 16, hipMemcpyDeviceToHost, c->stream));
+    if (moments2) HIPCHK(c, hipMemcpyAsync(moments2, c->d_tp_mom[c->tp_cur].p, px * 8, hipMemcpyDeviceToHost, c->stream));
+    if (variance) HIPCHK(c, hipMemcpyAsync(variance, c->d_tp_var.p, px * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PT_OK;
+}
+
+int pt_reset_temporal(pt_ctx* c)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    c->temporal_valid = false;
+    return PT_OK;
+}
+
+int pt_post_temporal(pt_ctx* c, int on_device, uint32_t w, uint32_t h, const pt_temporal_params* tp, const pt_denoise_params* dp, const float* prev_colour_n,
+                     const float* prev_moments2, const float* prev_position_xyzt, const float* prev_normal_xyz, const uint32_t* prev_model, const float* input_rgba,
+                     const float* position_xyzt, const float* normal_xyz, const uint32_t* model, const float* xprev_xyzt, const float* nprev_xyz,
+                     const float* velocity, float* out_colour_n, float* out_moments2, float* out_variance)
+{
+    if (!c) return PT_ERR_ARG;
+    if (!prev_colour_n || !prev_moments2 || !prev_position_xyzt || !prev_normal_xyz || !prev_model || !input_rgba || !position_xyzt || !normal_xyz || !model ||
+        !out_colour_n || !out_moments2 || !out_variance || !w || !h)
+        return fail(c, PT_ERR_ARG, "pt_post_temporal: null image or empty size");
+    if ((uint64_t)w * h > 0x7fffffffull) return fail(c, PT_ERR_ARG, "pt_post_temporal: image too large");
+    std::lock_guard<std::mutex> lk(c->mu);
+    TemporalK tk{};
+    DenoiseK k{};
+    int r;
+    if ((r = temporal_params(c, tp, tk)) || (r = denoise_params(c, dp, k))) return r;
+    const size_t px = (size_t)w * h;
+    // the records as the kernels read them: normals widened to 16 bytes, the previous model word beside its normal
+    std::vector<f4> gq(px), nr(px), np;
+    for (size_t i = 0; i < px; ++i)
+    {
+        gq[i] = f4{prev_normal_xyz[3 * i], prev_normal_xyz[3 * i + 1], prev_normal_xyz[3 * i + 2], from_bits(prev_model[i])};
+        nr[i] = f4{normal_xyz[3 * i], normal_xyz[3 * i + 1], normal_xyz[3 * i + 2], 0.0f};
+    }
+    if (nprev_xyz)
+    {
+        np.resize(px);
+        for (size_t i = 0; i < px; ++i) np[i] = f4{nprev_xyz[3 * i], nprev_xyz[3 * i + 1], nprev_xyz[3 * i + 2], 0.0f};
+    }
+    if (!on_device)
+    {
+        const TemporalImages im{(int)w, (int)h, (const f4*)prev_colour_n, (const f2*)prev_moments2, (const f4*)prev_position_xyzt, gq.data(), (const f4*)input_rgba,
+                                (const f4*)position_xyzt, nr.data(), model, (const f4*)(xprev_xyzt ? xprev_xyzt : position_xyzt), nprev_xyz ? np.data() : nr.data(),
+                                (const f2*)velocity};
+        std::vector<f4> cn(px);
+        std::vector<f2> mm(px);
+        for (uint32_t y = 0; y < h; ++y)
+            for (uint32_t x = 0; x < w; ++x)
+            {
+                const TemporalOut o = temporal_pixel(im, tk, (int)x, (int)y);
+                cn[(size_t)y * w + x] = o.h;
+                mm[(size_t)y * w + x] = o.m;
+            }
+        for (uint32_t y = 0; y < h; ++y)
+            for (uint32_t x = 0; x < w; ++x)
+                out_variance[(size_t)y * w + x] =
+                    temporal_variance((int)w, (int)h, cn.data(), mm.data(), im.pos, im.nrm, model, tk.alpha, k.log2_sigma_n, k.sigma_x, (int)x, (int)y);
+        std::memcpy(out_colour_n, cn.data(), px * 16);
+        std::memcpy(out_moments2, mm.data(), px * 8);
+        return PT_OK;
+    }
+    if ((r = ensure_device(c))) return r;
+    Staging t(c);
+    TemporalImages im{};
+    im.w = (int)w;
+    im.h = (int)h;
+    im.hist = (const f4*)t.in(prev_colour_n, px * 16);
+    im.mom = (const f2*)t.in(prev_moments2, px * 8);
+    im.xq = (const f4*)t.in(prev_position_xyzt, px * 16);
+    im.gq = (const f4*)t.in(gq.data(), px * 16);
+    im.cur = (const f4*)t.in(input_rgba, px * 16);
+    im.pos = (const f4*)t.in(position_xyzt, px * 16);
+    im.nrm = (const f4*)t.in(nr.data(), px * 16);
+    im.model = (const uint32_t*)t.in(model, px * 4);
+    im.xprev = xprev_xyzt ? (const f4*)t.in(xprev_xyzt, px * 16) : im.pos;
+    im.nprev = nprev_xyz ? (const f4*)t.in(np.data(), px * 16) : im.nrm;
+    im.vel = velocity ? (const f2*)t.in(velocity, px * 8) : nullptr;
+    f4* dh = (f4*)t.out(px * 16);
+    f2* dm = (f2*)t.out(px * 8);
+    float* dv = (float*)t.out(px * 4);
+    if (t.err) return t.err;
+    launch_temporal_reproject(c->stream, im, tk, dh, dm);
+    launch_temporal_variance(c->stream, (int)w, (int)h, k, tk.alpha, dh, dm, im.pos, im.nrm, im.model, nullptr, nullptr, dv);
+    HIPCHK(c, hipGetLastError());
+    if ((r = t.download(out_colour_n, dh, px * 16)) || (r = t.download(out_moments2, dm, px * 8))) return r;
+    return t.download(out_variance, dv, px * 4);
 }
 
 int pt_present(pt_ctx* c, float* rgba)

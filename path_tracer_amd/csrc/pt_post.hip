@@ -500,7 +500,102 @@ void denoise_levels(hipStream_t s, int w, int h, const DenoiseK& p, bool moments
         }
     }
 }
+
+// ---- temporal stage (pt_frame_temporal / pt_post_temporal): the per-pixel steps are pt_temporal.h's, shared with the host path.  One thread
+// per pixel in 16 x 16 workgroups.  k_tp_reproject is gather-bound: per tap two 16-byte loads (C | N, n' | m') decide whether the other two
+// (X' | t', the moments) are made at all, and the four taps' loads stand before the first use.
+__global__ void __launch_bounds__(256) k_tp_motion_normal(uint32_t n, const f4* __restrict__ normal, const uint32_t* __restrict__ instance, uint32_t n_instances,
+                                                          const MotionRow* __restrict__ rows, f4* __restrict__ n_prev)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    f4 N = normal[i];
+    const uint32_t inst = instance[i];
+    if (inst < n_instances && rows[inst].moved) N = motion_normal(rows[inst].inv, rows[inst].prv, N);
+    n_prev[i] = N;
+}
+
+__global__ void __launch_bounds__(256) k_tp_reproject(const TemporalImages im, const TemporalK k, f4* __restrict__ hist_out, f2* __restrict__ mom_out)
+{
+    const int x = blockIdx.x * 16 + threadIdx.x, y = blockIdx.y * 16 + threadIdx.y;
+    if (x >= im.w || y >= im.h) return;
+    const TemporalOut o = temporal_pixel(im, k, x, y);
+    const size_t i = (size_t)y * im.w + x;
+    hist_out[i] = o.h;
+    mom_out[i] = o.m;
+}
+
+// the variance of every pixel and the filter's input images; a pixel whose history is long enough returns before the 49-tap loop
+__global__ void __launch_bounds__(256) k_tp_variance(int w, int h, const DenoiseK p, float alpha, const f4* __restrict__ cn, const f2* __restrict__ mom,
+                                                     const f4* __restrict__ pos, const f4* __restrict__ nrm, const uint32_t* __restrict__ model,
+                                                     f4* __restrict__ cv, f4* __restrict__ nv, float* __restrict__ var)
+{
+    const int x = blockIdx.x * 16 + threadIdx.x, y = blockIdx.y * 16 + threadIdx.y;
+    if (x >= w || y >= h) return;
+    const size_t i = (size_t)y * w + x;
+    const float v = temporal_variance(w, h, cn, mom, pos, nrm, model, alpha, p.log2_sigma_n, p.sigma_x, x, y);
+    var[i] = v;
+    if (cv)
+    {
+        const f4 c = cn[i];
+        cv[i] = f4{c.x, c.y, c.z, v};
+    }
+    if (nv)
+    {
+        const f4 n = nrm[i];
+        nv[i] = f4{n.x, n.y, n.z, 1.0f};
+    }
+}
+
+// step 7: the current guides become the history's; lvl0 (feedback) replaces the history's colour, null leaves C
+__global__ void __launch_bounds__(256) k_tp_store(uint32_t n, const f4* __restrict__ pos, const f4* __restrict__ nrm, const uint32_t* __restrict__ model,
+                                                  const f4* __restrict__ lvl0, f4* __restrict__ hist, f4* __restrict__ xq, f4* __restrict__ gq)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const f4 nr = nrm[i];
+    xq[i] = pos[i];
+    gq[i] = f4{nr.x, nr.y, nr.z, from_bits(model[i])};
+    if (lvl0)
+    {
+        const f4 c = lvl0[i];
+        hist[i] = f4{c.x, c.y, c.z, hist[i].w};
+    }
+}
 } // namespace
+
+void launch_temporal_motion_normal(hipStream_t s, uint32_t n, const f4* normal, const uint32_t* instance, uint32_t n_instances, const MotionRow* rows, f4* n_prev)
+{
+    hipLaunchKernelGGL(k_tp_motion_normal, dim3((n + 255u) / 256u), dim3(256), 0, s, n, normal, instance, n_instances, rows, n_prev);
+}
+void launch_temporal_reproject(hipStream_t s, const TemporalImages& im, const TemporalK& k, f4* hist_out, f2* mom_out)
+{
+    hipLaunchKernelGGL(k_tp_reproject, dim3((im.w + 15) / 16, (im.h + 15) / 16), dim3(16, 16), 0, s, im, k, hist_out, mom_out);
+}
+void launch_temporal_variance(hipStream_t s, int w, int h, const DenoiseK& p, float alpha, const f4* cn, const f2* mom, const f4* position, const f4* normal,
+                              const uint32_t* model, f4* cv, f4* nv, float* var)
+{
+    hipLaunchKernelGGL(k_tp_variance, dim3((w + 15) / 16, (h + 15) / 16), dim3(16, 16), 0, s, w, h, p, alpha, cn, mom, position, normal, model, cv, nv, var);
+}
+void launch_temporal_filter(hipStream_t s, int w, int h, const DenoiseK& p, bool feedback, const f4* position, const f4* normal, const uint32_t* model, f4* cv_a,
+                            f4* cv_b, f4* nv, f4* out, f4* hist, f4* xq, f4* gq)
+{
+    const dim3 tile(16, 16), grid((w + 15) / 16, (h + 15) / 16);
+    const uint32_t n = (uint32_t)w * (uint32_t)h;
+    f4* cur = cv_a;
+    f4* other = cv_b;
+    for (uint32_t it = 0; it < p.iterations; ++it)
+    {
+        const int step = 1 << it;
+        const bool last = it + 1u == p.iterations;
+        f4* dst = last ? out : other;
+        if (last) hipLaunchKernelGGL(k_dn_level<true>, grid, tile, 0, s, w, h, step, p, (const f4*)cur, position, (const f4*)nv, model, dst, (const f4*)nullptr);
+        else hipLaunchKernelGGL(k_dn_level<false>, grid, tile, 0, s, w, h, step, p, (const f4*)cur, position, (const f4*)nv, model, dst, (const f4*)nullptr);
+        if (it == 0u)
+            hipLaunchKernelGGL(k_tp_store, dim3((n + 255u) / 256u), dim3(256), 0, s, n, position, normal, model, feedback ? (const f4*)dst : (const f4*)nullptr, hist, xq, gq);
+        if (!last) std::swap(cur, other);
+    }
+}
 
 void launch_denoise(hipStream_t s, int w, int h, const DenoiseK& p, const f4* accum, const float* moments, const f4* position, const f4* normal,
                     const uint32_t* model, f4* cv_a, f4* cv_b, f4* nv, f4* out)

@@ -1,0 +1,208 @@
+// The temporal stage of the denoiser (pt_frame_temporal / pt_post_temporal): the per-pixel steps of include/pt_api.h, written once for the
+// host path and the gfx950 kernels (pt_post.hip), as pt_materials.h is.  Every operation is an explicit binary32 operation in the order the
+// header states; build with -ffp-contract=off.
+//
+// Records of the previous call, one per pixel, each read with one 16-byte (M: 8-byte) load:
+//   hist : C.rgb | N          mom : mu1, mu2          xq : X'.xyz | t'          gq : n'.xyz | the bits of m'
+// A tap is tested on m' and N (gq, hist) before xq and mom are touched.
+#pragma once
+#include "pt_math.h"
+#include "pt_types.h"
+
+namespace pt {
+
+struct f2 { float x, y; };
+
+struct TemporalK
+{
+    float alpha, alpha_moments, normal_min, plane_max; // defaults filled in
+};
+constexpr float kTemporalMaxN = 65535.0f;
+constexpr float kTemporalMomentsN = 4.0f; // history length from which the moments carry the variance
+
+struct TemporalImages
+{
+    int w, h;
+    const f4* hist;  // previous call
+    const f2* mom;
+    const f4* xq;
+    const f4* gq;
+    const f4* cur;   // this frame: sample, position | t, normal, model
+    const f4* pos;
+    const f4* nrm;
+    const uint32_t* model;
+    const f4* xprev; // carried back (the position / the normal where nothing moved)
+    const f4* nprev;
+    const f2* vel;   // null: at rest
+};
+struct TemporalOut
+{
+    f4 h; // C.rgb | N
+    f2 m; // mu1, mu2
+};
+
+PT_HD float tp_lum(f4 c) { return (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z; }
+
+// n carried back by the linear parts of the instance's inverse and previous forward matrix (rows of the 3x4s), as X_PREV carries the point
+PT_HD f4 motion_normal(const float inv[12], const float prv[12], f4 n)
+{
+    float o[3], q[3];
+    for (int k = 0; k < 3; ++k) o[k] = (inv[4 * k] * n.x + inv[4 * k + 1] * n.y) + inv[4 * k + 2] * n.z;
+    for (int k = 0; k < 3; ++k) q[k] = (prv[4 * k] * o[0] + prv[4 * k + 1] * o[1]) + prv[4 * k + 2] * o[2];
+    return f4{q[0], q[1], q[2], n.w};
+}
+
+// steps 1-4 for pixel (x, y): the taps, their tests, the fold and the blend
+PT_HD TemporalOut temporal_pixel(const TemporalImages& im, const TemporalK& k, int x, int y)
+{
+    const int w = im.w, h = im.h;
+    const size_t i = (size_t)y * w + x;
+    // the list as four slots in list order; a slot that is not in the list has b = 0 and fails the b > 0 test
+    int qx[4] = {x, x, x, x}, qy[4] = {y, y, y, y};
+    float b[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (!im.vel) b[0] = 1.0f;
+    else
+    {
+        const f2 v = im.vel[i];
+        const float cu = ((float)x + 0.5f) / (float)w, cv = ((float)y + 0.5f) / (float)h;
+        const float pu = cu - v.x, pv = cv - v.y;
+        const float fx = pu * (float)w - 0.5f, fy = pv * (float)h - 0.5f;
+        if (fx >= -1.0f && fx < (float)w && fy >= -1.0f && fy < (float)h) // in float: a NaN or infinite velocity fails here
+        {
+            const float bx = floorf(fx), by = floorf(fy);
+            const float tx = fx - bx, ty = fy - by;
+            const int x0 = (int)bx, y0 = (int)by; // -1 .. w - 1, -1 .. h - 1
+            for (int j = 0; j < 2; ++j)
+                for (int ii = 0; ii < 2; ++ii)
+                {
+                    qx[2 * j + ii] = x0 + ii;
+                    qy[2 * j + ii] = y0 + j;
+                    b[2 * j + ii] = (ii ? tx : 1.0f - tx) * (j ? ty : 1.0f - ty);
+                }
+        }
+    }
+    const uint32_t mp = im.model[i];
+    const bool hit = mp != MISS_ID;
+    size_t q[4];
+    bool ok[4];
+    f4 hq[4], gq[4];
+    for (int t = 0; t < 4; ++t)
+    {
+        const bool inside = qx[t] >= 0 && qx[t] < w && qy[t] >= 0 && qy[t] < h;
+        q[t] = inside ? (size_t)qy[t] * w + qx[t] : i; // an outside tap reads p's record and is not valid
+        ok[t] = inside && b[t] > 0.0f;
+        hq[t] = im.hist[q[t]];
+        gq[t] = im.gq[q[t]];
+    }
+    for (int t = 0; t < 4; ++t) ok[t] = ok[t] && hq[t].w > 0.0f && bits(gq[t].w) == mp;
+    if (hit)
+    {
+        const f4 np = im.nprev[i], xp = im.xprev[i];
+        const float bound = k.plane_max * im.pos[i].w;
+        f4 xq[4];
+        for (int t = 0; t < 4; ++t) xq[t] = ok[t] ? im.xq[q[t]] : f4{0.0f, 0.0f, 0.0f, 0.0f};
+        for (int t = 0; t < 4; ++t)
+        {
+            const float nd = (np.x * gq[t].x + np.y * gq[t].y) + np.z * gq[t].z;
+            const float dx = xq[t].x - xp.x, dy = xq[t].y - xp.y, dz = xq[t].z - xp.z;
+            const float pd = fabsf((np.x * dx + np.y * dy) + np.z * dz);
+            ok[t] = ok[t] && nd >= k.normal_min && pd <= bound;
+        }
+    }
+    f2 mq[4];
+    for (int t = 0; t < 4; ++t) mq[t] = ok[t] ? im.mom[q[t]] : f2{0.0f, 0.0f};
+    float sw = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f, s1 = 0.0f, s2 = 0.0f, nmin = INFINITY;
+    for (int t = 0; t < 4; ++t)
+    {
+        if (!ok[t]) continue;
+        sw = sw + b[t];
+        sr = sr + b[t] * hq[t].x;
+        sg = sg + b[t] * hq[t].y;
+        sb = sb + b[t] * hq[t].z;
+        s1 = s1 + b[t] * mq[t].x;
+        s2 = s2 + b[t] * mq[t].y;
+        nmin = nmin < hq[t].w ? nmin : hq[t].w;
+    }
+    const f4 cur = im.cur[i];
+    const float l = tp_lum(cur);
+    TemporalOut o;
+    if (sw > 0.0f)
+    {
+        const float hr = sr / sw, hg = sg / sw, hb = sb / sw, m1 = s1 / sw, m2 = s2 / sw;
+        const float n1 = nmin + 1.0f;
+        const float n = n1 < kTemporalMaxN ? n1 : kTemporalMaxN;
+        const float rn = 1.0f / n;
+        const float a = k.alpha > rn ? k.alpha : rn, am = k.alpha_moments > rn ? k.alpha_moments : rn;
+        o.h = f4{hr * (1.0f - a) + cur.x * a, hg * (1.0f - a) + cur.y * a, hb * (1.0f - a) + cur.z * a, n};
+        o.m = f2{m1 * (1.0f - am) + l * am, m2 * (1.0f - am) + (l * l) * am};
+    }
+    else
+    {
+        o.h = f4{cur.x, cur.y, cur.z, 1.0f};
+        o.m = f2{l, l * l};
+    }
+    return o;
+}
+
+// geometry terms of two hits, in pt_denoise's order
+PT_HD float tp_normal_w(f4 np, f4 nq, uint32_t log2_sn)
+{
+    const float nd = (np.x * nq.x + np.y * nq.y) + np.z * nq.z;
+    float wn = nd > 0.0f ? nd : 0.0f;
+    for (uint32_t k = 0; k < log2_sn; ++k) wn = wn * wn;
+    return wn;
+}
+PT_HD float tp_plane(f4 np, f4 xp, f4 xq, float sigma_x)
+{
+    const float dx = xq.x - xp.x, dy = xq.y - xp.y, dz = xq.z - xp.z;
+    const float d2 = (dx * dx + dy * dy) + dz * dz;
+    return d2 > 0.0f ? fabsf((np.x * dx + np.y * dy) + np.z * dz) / (sigma_x * sqrtf(d2)) : 0.0f;
+}
+
+// step 5 for pixel (x, y): the variance handed to the levels.  cn = this call's C | N, mom its moments.  From kTemporalMomentsN on the
+// moments answer at once; only younger pixels walk pt_denoise's 7 x 7 spatial variance of C under the current guides (every pixel valid).
+PT_HD float temporal_variance(int w, int h, const f4* cn, const f2* mom, const f4* pos, const f4* nrm, const uint32_t* model, float alpha, uint32_t log2_sn,
+                              float sigma_x, int x, int y)
+{
+    const size_t i = (size_t)y * w + x;
+    const f4 cp = cn[i];
+    if (cp.w >= kTemporalMomentsN)
+    {
+        const f2 m = mom[i];
+        float v = m.y - m.x * m.x;
+        if (!(v > 0.0f)) v = 0.0f;
+        const float rn = 1.0f / cp.w;
+        return v * (alpha > rn ? alpha : rn);
+    }
+    const uint32_t mp = model[i];
+    const bool hit = mp != MISS_ID;
+    const f4 np = nrm[i], xp = pos[i];
+    float sw = 0.0f, sl = 0.0f, sll = 0.0f;
+    for (int dy = -3; dy <= 3; ++dy)
+    {
+        const int yy = y + dy;
+        if (yy < 0 || yy >= h) continue;
+        for (int dx = -3; dx <= 3; ++dx)
+        {
+            const int xx = x + dx;
+            if (xx < 0 || xx >= w) continue;
+            const size_t q = (size_t)yy * w + xx;
+            float wt = 1.0f;
+            if (dx != 0 || dy != 0)
+            {
+                if (model[q] != mp) continue;
+                if (hit) wt = tp_normal_w(np, nrm[q], log2_sn) * exp_det(-tp_plane(np, xp, pos[q], sigma_x));
+            }
+            const float l = tp_lum(cn[q]);
+            sw = sw + wt;
+            sl = sl + wt * l;
+            sll = sll + wt * (l * l);
+        }
+    }
+    const float mu = sl / sw;
+    float v = sll / sw - mu * mu;
+    if (!(v > 0.0f)) v = 0.0f;
+    return v;
+}
+
+} // namespace pt

@@ -12,7 +12,13 @@ albedo beside pt_denoise's, its cost beside pt_denoise's, and the cost of one sa
 profiles/r16_followed_guides.md), and adds the cost of the guides on the mixed Cornell box at the timing size: the plain call and max_hops
 1, 2 and 8 measured in turn, --reps rounds (median, min and max of each).
 
-    python tools/denoise_bench.py [--albedo] [--follow K] [--size 256] [--ref-spp 4096] [--spp 1,4,16,64] [--width 1920 --height 1080 --reps 20] [--out file.json]
+--temporal adds the temporal stage (pt_frame_temporal, profiles/r20_temporal.md): the display-space RMSE of the last of --temporal-frames
+1-spp frames of a slow camera pan against a many-sample render of the last pose, for the raw frame, for pt_frame_moving + pt_denoise over
+the same sequence and for pt_frame_temporal; and at the timing size the whole calls in turn, round by round: pt_frame_moving + pt_denoise,
+pt_frame_temporal in steady state, and pt_frame_temporal on the frames right after a cut (pt_reset_temporal), where every pixel still walks
+the 7 x 7 spatial variance.
+
+    python tools/denoise_bench.py [--albedo] [--follow K] [--temporal] [--size 256] [--ref-spp 4096] [--spp 1,4,16,64] [--width 1920 --height 1080 --reps 20] [--out file.json]
 """
 import argparse
 import json
@@ -107,6 +113,63 @@ def follow_timing(api, scenes, w, h, reps, depth):
     return row
 
 
+PAN = (1.0, 0.0, 4.0e-7)   # EV_MOUSE_MOTION per frame: 0.004 rad, half a pixel of a 128-pixel, 60-degree frame
+
+
+def temporal_quality(api, scenes, size, frames, ref_spp, depth, feedback=0, pan=True, **params):
+    sc = scenes.cornell_box(size, size)
+    t = api.Renderer(sc, size, size, max_bounces=depth); m = api.Renderer(sc, size, size, max_bounces=depth)
+    ref = api.Renderer(sc, size, size, max_bounces=depth)
+    last_t, last_m = t.inv_projection(), m.inv_projection()
+    for k in range(frames):
+        if k and pan:
+            for r in (t, m, ref):
+                r.camera_input(api.EV_MOUSE_MOTION, *PAN)
+        data, _, _, out = t.frame_temporal(k, last_t, feedback=feedback, **params)
+        m.frame_moving(k, last_m, download=False)
+        last_t, last_m = t.inv_projection(), m.inv_projection()
+    den = m.denoise()
+    hist = t.read_temporal()[0]
+    n = hist[..., 3]
+    hist = np.concatenate([hist[..., :3], np.ones_like(hist[..., 3:])], -1)     # (with feedback: level 0's output)
+    racc, _, _ = ref.render(1 << 20, ref_spp, want_position=False)
+    ref_disp = ref.post_tonemap(racc)
+    row = dict(size=size, frames=frames, ref_spp=ref_spp, feedback=feedback, pan=pan, params=params, display_rmse_history=rmse(t.post_tonemap(hist), ref_disp), display_rmse_raw=rmse(t.post_tonemap(data), ref_disp),
+               display_rmse_moving_denoise=rmse(m.post_tonemap(den), ref_disp), display_rmse_temporal=rmse(t.post_tonemap(out), ref_disp),
+               mean_history=float(n.mean()), disoccluded=int((n == 1).sum()))
+    for r in (t, m, ref):
+        r.close()
+    print(json.dumps(row), flush=True)
+    return row
+
+
+def temporal_timing(api, scenes, w, h, reps, depth):
+    sc = scenes.cornell_box(w, h)
+    m = api.Renderer(sc, w, h, max_bounces=depth); t = api.Renderer(sc, w, h, max_bounces=depth); c = api.Renderer(sc, w, h, max_bounces=depth)
+    last = {id(r): r.inv_projection() for r in (m, t, c)}
+    tm, td, ts, tc = [], [], [], []
+    for k in range(reps + 4):
+        for r in (m, t, c):
+            r.camera_input(api.EV_MOUSE_MOTION, *PAN)
+        t0 = time.perf_counter(); m.frame_moving(k, last[id(m)], download=False); t1 = time.perf_counter()
+        m.denoise(download=False); t2 = time.perf_counter()
+        t.frame_temporal(k, last[id(t)], download=False); t3 = time.perf_counter()
+        c.reset_temporal()
+        c.frame_temporal(k, last[id(c)], download=False); t4 = time.perf_counter()
+        for r in (m, t, c):
+            last[id(r)] = r.inv_projection()
+        if k >= 4:
+            tm.append(t1 - t0); td.append(t2 - t1); ts.append(t3 - t2); tc.append(t4 - t3)
+    young = float((t.read_temporal()[0][..., 3] < 4).mean())
+    for r in (m, t, c):
+        r.close()
+    med = lambda v: dict(median=1e3 * float(np.median(v)), min=1e3 * float(np.min(v)), max=1e3 * float(np.max(v)))
+    row = dict(width=w, height=h, reps=reps, ms_frame_moving=med(tm), ms_denoise=med(td), ms_frame_temporal_steady=med(ts), ms_frame_temporal_after_cut=med(tc),
+               steady_fraction_below_4=young)
+    print(json.dumps(row), flush=True)
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=256)
@@ -120,6 +183,10 @@ def main():
     ap.add_argument("--no-quality", action="store_true")
     ap.add_argument("--albedo", action="store_true", help="also measure pt_accumulate_albedo and pt_denoise_albedo")
     ap.add_argument("--follow", type=int, default=0, help="follow up to K mirror / glass surfaces per pixel in the guides (0..8)")
+    ap.add_argument("--temporal", action="store_true", help="also measure pt_frame_temporal against pt_frame_moving + pt_denoise")
+    ap.add_argument("--temporal-size", type=int, default=128)
+    ap.add_argument("--temporal-frames", type=int, default=16)
+    ap.add_argument("--temporal-ref-spp", type=int, default=1024)
     ap.add_argument("--out")
     a = ap.parse_args()
     from path_tracer_amd import api, scenes
@@ -131,6 +198,11 @@ def main():
         res["timing"] = timing(api, scenes, a.width, a.height, a.reps, a.bounces, a.albedo)
         if a.follow:
             res["follow_timing"] = follow_timing(api, scenes, a.width, a.height, a.reps, a.bounces)
+    if a.temporal:
+        if not a.no_quality:
+            res["temporal_quality"] = [temporal_quality(api, scenes, a.temporal_size, a.temporal_frames, a.temporal_ref_spp, a.bounces, feedback=f) for f in (0, 1)]
+        if a.reps > 0:
+            res["temporal_timing"] = temporal_timing(api, scenes, a.width, a.height, a.reps, a.bounces)
     if a.out:
         with open(a.out, "w") as f:
             json.dump(res, f, indent=1)
