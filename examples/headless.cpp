@@ -14,7 +14,8 @@
 //                                          the BLASes are kept, the resident scene is patched) and the loop drives frame_moving instead of frame
 //   examples/headless ... --temporal out.png   the loop drives frame_temporal instead: the scripted frames (--move, --slide) go through the temporal
 //                                          stage of the denoiser (reprojected history, history length, luminance moments, then the a-trous levels) and the
-//                                          last frame's result is written
+//                                          last frame's result is written; --temporal-rescue, --temporal-mean-length and --temporal-demodulate (only
+//                                          with --temporal) switch on pt_temporal_options' rescue, length_rule and demodulate
 //   examples/headless ... --denoise den.png   also writes the final frame through the edge-aware denoiser (guides of the last frame's sample)
 //   examples/headless ... --denoise-albedo den.png   the same through the demodulated filter (pt_denoise_albedo): the mean albedo of every pixel
 //                                        is accumulated over the samples that were rendered, the frame divided by it, filtered and multiplied back,
@@ -59,6 +60,8 @@ int main(int argc, char** argv)
     std::vector<int32_t> devices;
     std::string models_dir = "models/cornell", out = "", load_state = "", save_state = "", denoise_out = "", denoise_albedo_out = "", temporal_out = "";
     bool render_mode = false;
+    pt_temporal_options temporal{};
+    bool temporal_option = false;
     uint32_t render_first = 0, render_count = 0;
     float aperture = 0.0f, focus = 950.0f; // main.rs:127's values: a pinhole
     uint32_t probes[3] = {0, 0, 0}, probe_spp = 0, checker = 0, emission_checker = 0, normal_ripples = 0, follow = 0;
@@ -81,6 +84,9 @@ int main(int argc, char** argv)
         else if (a == "--out") out = next("--out");
         else if (a == "--denoise") denoise_out = next("--denoise");
         else if (a == "--temporal") temporal_out = next("--temporal");
+        else if (a == "--temporal-rescue") { temporal.rescue = 1; temporal_option = true; }
+        else if (a == "--temporal-mean-length") { temporal.length_rule = PT_TEMPORAL_LENGTH_MEAN; temporal_option = true; }
+        else if (a == "--temporal-demodulate") { temporal.demodulate = 1; temporal_option = true; }
         else if (a == "--denoise-albedo") denoise_albedo_out = next("--denoise-albedo");
         else if (a == "--follow") follow = (uint32_t)std::atoi(next("--follow"));
         else if (a == "--mirror-glass") mirror_glass = true;
@@ -124,7 +130,7 @@ int main(int argc, char** argv)
         }
         else if (a == "--help" || a == "-h")
         {
-            std::printf("usage: %s [--width W] [--height H] [--frames N] [--bounces B] [--move] [--slide DX DZ] [--models DIR] [--out file.png] [--temporal file.png] [--denoise file.png] [--denoise-albedo file.png] [--follow K] [--mirror-glass] [--aperture A --focus F] [--projection panorama[:SX:SY]|ortho:HEIGHT] [--bake-probes NX NY NZ SPP file.txt] [--bake-lightmap W H SPP PASSES file.txt] [--checker N] [--emission-checker N] [--normal-ripples N]\n", argv[0]);
+            std::printf("usage: %s [--width W] [--height H] [--frames N] [--bounces B] [--move] [--slide DX DZ] [--models DIR] [--out file.png] [--temporal file.png [--temporal-rescue] [--temporal-mean-length] [--temporal-demodulate]] [--denoise file.png] [--denoise-albedo file.png] [--follow K] [--mirror-glass] [--aperture A --focus F] [--projection panorama[:SX:SY]|ortho:HEIGHT] [--bake-probes NX NY NZ SPP file.txt] [--bake-lightmap W H SPP PASSES file.txt] [--checker N] [--emission-checker N] [--normal-ripples N]\n", argv[0]);
             return 0;
         }
         else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
@@ -139,6 +145,11 @@ int main(int argc, char** argv)
     {
         // frame_temporal leaves the accumulation alone: there is nothing in it for these to write
         std::fprintf(stderr, "--temporal cannot be combined with --out, --denoise, --denoise-albedo, --render or --gpus: its frames do not accumulate\n");
+        return 2;
+    }
+    if (temporal_option && temporal_out.empty())
+    {
+        std::fprintf(stderr, "--temporal-rescue, --temporal-mean-length and --temporal-demodulate are options of --temporal\n");
         return 2;
     }
     try
@@ -332,7 +343,8 @@ int main(int argc, char** argv)
                 const float f = (float)frame;
                 renderer.set_instances(5, {Affine3A{{1, 0, 0, f * slide_dx, 0, 1, 0, 0.0f, 0, 0, 1, f * slide_dz}}});
             }
-            if (!temporal_out.empty()) renderer.frame_temporal(frame, last_inv_proj);
+            if (!temporal_out.empty() && temporal_option) renderer.frame_temporal(frame, last_inv_proj, temporal);
+            else if (!temporal_out.empty()) renderer.frame_temporal(frame, last_inv_proj);
             else if (slide) renderer.frame_moving(frame, last_inv_proj);
             else renderer.frame(frame, last_inv_proj);       // the pixel loop + state.update   main.rs:181-215
             last_inv_proj = renderer.inv_projection();       // main.rs:216

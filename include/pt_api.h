@@ -703,8 +703,40 @@ int pt_post_denoise_albedo(pt_ctx* ctx, uint32_t w, uint32_t h, const pt_denoise
  * normal_min outside [-1, 1] or NaN, plane_max negative or not finite, feedback > 1, a non-zero reserved word, and whatever pt_denoise
  * refuses; PT_ERR_STATE as for pt_frame_moving (world_size > 1 included).
  * The interactive recipe: pt_frame_temporal(k, last_inv_projection), then present its result.
- * Out of scope: followed guides as the history's guides; albedo demodulation of the history; a 3 x 3 rescue search for disoccluded pixels;
+ *
+ * THREE OPTIONS, each a word of pt_temporal_options that is 0 or 1, handed to pt_frame_temporal_options / pt_post_temporal_options, which are
+ * pt_frame_temporal / pt_post_temporal with one more argument.  (pt_temporal_params' reserved words stay reserved and refused: a caller that
+ * was refused yesterday is refused today.)  With all three 0 the steps above are the whole definition, bit for bit, and the call is the plain one.
+ * They answer what the plain stage loses on a pan: the guides are one jittered sample's first hit, so a silhouette pixel sees another model
+ * every other frame, restarts at N = 1 and, through Nmin, drags its neighbours' history length down along the motion; and a textured wall
+ * is smeared across texels by the levels and across frames by the history.
+ *   length_rule = PT_TEMPORAL_LENGTH_MEAN.  Step 3's fold over the valid taps also forms sN += b * H_q.N.  Step 4 takes
+ *        N = min(floorf(sN / sw + 0.5f) + 1, 65535)
+ *      in place of min(Nmin + 1, 65535): still an integer held in f32.  (The + 0.5f is needed: four taps of equal N can give sN / sw one ulp
+ *      below N, and a bare floor would freeze the history length under motion.)  Nmin is still formed and not used.
+ *   rescue = 1, the 3 x 3 rescue search, is step 3b.  It runs only when the list of step 1 was not empty and step 3 ended with sw == 0.
+ *      Centre c: at rest c = p; moved, c = (x0 + (tx >= 0.5f ? 1 : 0), y0 + (ty >= 0.5f ? 1 : 0)).  The rescue list is the nine pixels
+ *      c + (dx, dy), dy outer and dx inner, each in -1 .. 1, every one with b = 1.  A rescue tap is VALID by step 2's tests, unchanged (inside
+ *      the image, H_q.N > 0, the whole model word, and for hits the normal and plane tests against nprev_p and xprev_p).  Step 3's fold, sN
+ *      included, runs over the valid ones in that order; then step 4 as written: sw > 0 blends, otherwise the pixel restarts at N = 1.  An
+ *      out-of-frame reprojection (the empty list) is not rescued; a centre outside the image is no special case, its outside taps fail.
+ *   demodulate = 1 (pt_frame_temporal only), albedo demodulation of the history.  A = the pixel's albedo guide of this frame (what
+ *      pt_read_guide_albedo returns); k = (1, 1, 1) when m_p is a miss, otherwise per channel k.ch = A.ch > 0x1p-10f ? A.ch : 0x1p-10f
+ *      (pt_denoise_albedo's k).  cur'.ch = cur.ch / k.ch, and steps 1-5 and 7 use cur' wherever they say cur, l(cur') included: H.rgb and M
+ *      hold demodulated values.  Step 6 runs the unchanged levels on (C, var) to c''; the output is (c''.r * k.r, c''.g * k.g, c''.b * k.b, 1).
+ *      Step 7 stores C (feedback = 0) or level 0's output BEFORE that multiplication (feedback = 1), for every iterations, 1 included, where
+ *      level 0 is also the last.  data_rgba, position and id are what they were; pt_read_temporal returns the demodulated state;
+ *      pt_write_denoised_image writes the multiplied result.  A call whose demodulate differs from that of the call which wrote the
+ *      history starts as after pt_reset_temporal: one history never mixes the two kinds.  The frame's sample and its albedo guide are the same
+ *      jittered ray, so cur / A has none of the texel-edge mismatch PT_ALBEDO_MEAN exists for.
+ *   So: under an albedo of exactly 1 everywhere, or a frame of misses, demodulate = 1 gives demodulate = 0's bits in state and output; at
+ *   rest, with every pixel's own tap valid, rescue = 1 gives rescue = 0's bits.
+ *   pt_post_temporal_options honours rescue and length_rule on both paths and refuses demodulate != 0: it runs on caller images, and a caller
+ *   who wants demodulation divides its input image itself.  Errors of the two calls, before any device call and changing nothing: those of the
+ *   plain calls, then PT_ERR_ARG for NULL options, for any of the three words above 1, for a non-zero reserved word and for that demodulate.
+ * Out of scope: followed guides as the history's guides; unjittered or sample-averaged guides; PT_ALBEDO_MEAN in the temporal stage;
  * pt_multi_* variants. */
+enum { PT_TEMPORAL_LENGTH_MIN = 0, PT_TEMPORAL_LENGTH_MEAN = 1 };
 typedef struct pt_temporal_params
 {
     float alpha;          /* floor of the colour blend weight, in [0, 1]; 0 => 0.2 */
@@ -714,6 +746,13 @@ typedef struct pt_temporal_params
     uint32_t feedback;    /* 0: the history keeps C; 1: it keeps level 0's output */
     uint32_t reserved[3]; /* must be 0 */
 } pt_temporal_params;
+typedef struct pt_temporal_options
+{
+    uint32_t rescue;      /* 0: off; 1: a pixel with no valid tap searches the 3 x 3 around its reprojected position */
+    uint32_t length_rule; /* 0: PT_TEMPORAL_LENGTH_MIN (Nmin); 1: PT_TEMPORAL_LENGTH_MEAN */
+    uint32_t demodulate;  /* 0: off; 1: history, moments and levels work on cur / albedo guide; the output is multiplied back */
+    uint32_t reserved;    /* must be 0 */
+} pt_temporal_options;
 int pt_frame_temporal(pt_ctx* ctx, uint32_t frame_index, const float* last_inv_projection, const pt_temporal_params* params,
                       const pt_denoise_params* denoise, float* data_rgba, float* position_xyzt, uint32_t* id, float* out_rgba);
 int pt_read_temporal(pt_ctx* ctx, float* colour_n, float* moments2, float* variance);
@@ -723,6 +762,14 @@ int pt_post_temporal(pt_ctx* ctx, int on_device, uint32_t w, uint32_t h, const p
                      const uint32_t* prev_model, const float* input_rgba, const float* position_xyzt, const float* normal_xyz, const uint32_t* model,
                      const float* xprev_xyzt, const float* nprev_xyz, const float* velocity, float* out_colour_n, float* out_moments2,
                      float* out_variance);
+int pt_frame_temporal_options(pt_ctx* ctx, uint32_t frame_index, const float* last_inv_projection, const pt_temporal_params* params,
+                              const pt_temporal_options* options, const pt_denoise_params* denoise, float* data_rgba, float* position_xyzt, uint32_t* id,
+                              float* out_rgba);
+int pt_post_temporal_options(pt_ctx* ctx, int on_device, uint32_t w, uint32_t h, const pt_temporal_params* params, const pt_temporal_options* options,
+                             const pt_denoise_params* denoise, const float* prev_colour_n, const float* prev_moments2, const float* prev_position_xyzt,
+                             const float* prev_normal_xyz, const uint32_t* prev_model, const float* input_rgba, const float* position_xyzt,
+                             const float* normal_xyz, const uint32_t* model, const float* xprev_xyzt, const float* nprev_xyz, const float* velocity,
+                             float* out_colour_n, float* out_moments2, float* out_variance);
 
 /* ---- caller-supplied rays: "what radiance arrives along THIS ray?" ---------------------------------------------------- */
 /* Every render entry point above starts its paths at the context's camera.  pt_integrate_rays runs the same wavefront integrator over rays the

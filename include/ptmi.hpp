@@ -269,6 +269,14 @@ public:
         if (filtered) filtered->resize((size_t)width_ * height_ * 4);
         check(pt_frame_temporal(ctx_, frame_index, last_inv_projection.data(), &t, &d, nullptr, nullptr, nullptr, filtered ? filtered->data() : nullptr));
     }
+    // the same under the stage's options (pt_frame_temporal_options): o.rescue, a 3 x 3 rescue search for pixels that lost every tap;
+    // o.length_rule, PT_TEMPORAL_LENGTH_MEAN; o.demodulate, the stage on the sample divided by its albedo guide
+    void frame_temporal(uint32_t frame_index, const Mat4& last_inv_projection, const pt_temporal_options& o, const pt_temporal_params& t = pt_temporal_params{},
+                        const pt_denoise_params& d = pt_denoise_params{}, std::vector<float>* filtered = nullptr)
+    {
+        if (filtered) filtered->resize((size_t)width_ * height_ * 4);
+        check(pt_frame_temporal_options(ctx_, frame_index, last_inv_projection.data(), &t, &o, &d, nullptr, nullptr, nullptr, filtered ? filtered->data() : nullptr));
+    }
     void reset_temporal() { check(pt_reset_temporal(ctx_)); }
     // replaces the instance matrices of model `model` (index in Scene::models) and rebuilds: BLASes are kept, the TLASes are built again and,
     // when the instance count is unchanged, the next render patches the resident scene in place

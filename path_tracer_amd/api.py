@@ -47,7 +47,7 @@ EXPORTS = [
     "pt_set_projection", "pt_get_projection",
     "pt_bake_lightmap", "pt_lightmap_texels", "pt_lightmap_ray", "pt_lightmap_dilate",
     "pt_render_guides_followed", "pt_read_guide_hops", "pt_accumulate_albedo_followed", "pt_guide_follow_dir",
-    "pt_frame_temporal", "pt_read_temporal", "pt_reset_temporal", "pt_post_temporal",
+    "pt_frame_temporal", "pt_read_temporal", "pt_reset_temporal", "pt_post_temporal", "pt_frame_temporal_options", "pt_post_temporal_options",
 ]
 
 
@@ -104,6 +104,14 @@ class TemporalParams(C.Structure):
     """pt_temporal_params: the temporal stage's blend floors, tap tests and feedback switch (include/pt_api.h); 0 selects each default"""
     _fields_ = [("alpha", C.c_float), ("alpha_moments", C.c_float), ("normal_min", C.c_float), ("plane_max", C.c_float), ("feedback", C.c_uint32),
                 ("reserved", C.c_uint32 * 3)]
+
+
+class TemporalOptions(C.Structure):
+    """pt_temporal_options: the temporal stage's options, each 0 or 1 (include/pt_api.h): the 3 x 3 rescue search, the length rule, demodulation"""
+    _fields_ = [("rescue", C.c_uint32), ("length_rule", C.c_uint32), ("demodulate", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+TEMPORAL_LENGTH_MIN, TEMPORAL_LENGTH_MEAN = 0, 1
 
 
 class GuideParams(C.Structure):
@@ -284,6 +292,8 @@ def lib():
         L.pt_read_temporal.argtypes = [vp, vp, vp, vp]
         L.pt_reset_temporal.argtypes = [vp]
         L.pt_post_temporal.argtypes = [vp, C.c_int, u32, u32, C.POINTER(TemporalParams), C.POINTER(DenoiseParams)] + [vp] * 15
+        L.pt_frame_temporal_options.argtypes = [vp, u32, vp, C.POINTER(TemporalParams), C.POINTER(TemporalOptions), C.POINTER(DenoiseParams), vp, vp, vp, vp]
+        L.pt_post_temporal_options.argtypes = [vp, C.c_int, u32, u32, C.POINTER(TemporalParams), C.POINTER(TemporalOptions), C.POINTER(DenoiseParams)] + [vp] * 15
         _lib = L
     return _lib
 
@@ -810,20 +820,28 @@ class Renderer:
 
     # ---- the temporal stage: reprojected history, history length and luminance moments (pt_frame_temporal)
     def frame_temporal(self, frame_index, last_inv_projection=None, ident=None, download=True, alpha=0.0, alpha_moments=0.0, normal_min=0.0,
-                       plane_max=0.0, feedback=0, iterations=0, sigma_luminance=0.0, sigma_normal=0, sigma_plane=0.0):
+                       plane_max=0.0, feedback=0, iterations=0, sigma_luminance=0.0, sigma_normal=0, sigma_plane=0.0, rescue=0, length_rule=0, demodulate=0):
         """frame_moving's render, guides and velocity, then the temporal stage instead of State::update: the history is reprojected through
-        geometry tests, blended by its length, and the a-trous levels run on it with the variance the pixels observed over time.  Returns
+        geometry tests, blended by its length, and the a-trous levels run on it with the variance the pixels observed over time.  rescue=1: a
+        pixel that lost every tap searches the 3 x 3 around its reprojected position; length_rule=1 (TEMPORAL_LENGTH_MEAN): the taps' mean
+        history length, not their least; demodulate=1: the stage works on the sample divided by its albedo guide (any of the three set: the
+        call goes through pt_frame_temporal_options, otherwise through pt_frame_temporal).  Returns
         data, position, id, result (download=False: None; the result stays on the device for write_denoised_image)"""
         m = None if last_inv_projection is None else np.ascontiguousarray(last_inv_projection, np.float32)
         tp = TemporalParams(alpha, alpha_moments, normal_min, plane_max, feedback)
         dp = DenoiseParams(iterations, sigma_luminance, sigma_normal, sigma_plane)
+        if rescue or length_rule or demodulate:
+            to = TemporalOptions(rescue, length_rule, demodulate)
+            call = lambda *bufs: self.L.pt_frame_temporal_options(self.ctx, frame_index, _p(m), C.byref(tp), C.byref(to), C.byref(dp), *bufs)
+        else:
+            call = lambda *bufs: self.L.pt_frame_temporal(self.ctx, frame_index, _p(m), C.byref(tp), C.byref(dp), *bufs)
         if not download:
-            self._chk(self.L.pt_frame_temporal(self.ctx, frame_index, _p(m), C.byref(tp), C.byref(dp), None, None, None, None))
+            self._chk(call(None, None, None, None))
             return None
         h, w = self.cfg.height, self.cfg.width
         data = np.zeros((h, w, 4), np.float32); pos = np.zeros((h, w, 4), np.float32); out = np.zeros((h, w, 4), np.float32)
         idb = np.zeros((h, w), np.uint32) if ident is None else ident
-        self._chk(self.L.pt_frame_temporal(self.ctx, frame_index, _p(m), C.byref(tp), C.byref(dp), _p(data), _p(pos), _p(idb), _p(out)))
+        self._chk(call(_p(data), _p(pos), _p(idb), _p(out)))
         return data, pos, idb, out
 
     def read_temporal(self):
@@ -837,11 +855,11 @@ class Renderer:
         self._chk(self.L.pt_reset_temporal(self.ctx))
 
     def post_temporal(self, prev, cur, xprev=None, nprev=None, velocity=None, on_device=False, alpha=0.0, alpha_moments=0.0, normal_min=0.0,
-                      plane_max=0.0, sigma_normal=0, sigma_plane=0.0):
+                      plane_max=0.0, sigma_normal=0, sigma_plane=0.0, rescue=0, length_rule=0, demodulate=0):
         """one temporal step (without the levels) on caller images.  prev = (history h x w x 4, moments h x w x 2, position h x w x 4, normal
         h x w x 3, model h x w) of the previous call, cur = (input h x w x 4, position, normal, model) of this frame; xprev / nprev None: the
-        position / the normal; velocity None: at rest.  on_device False evaluates on the host and touches no GPU.  Returns history, moments,
-        variance"""
+        position / the normal; velocity None: at rest.  on_device False evaluates on the host and touches no GPU.  rescue and length_rule as
+        frame_temporal's; the library refuses demodulate here (divide the input image yourself).  Returns history, moments, variance"""
         ph, pm, px, pn, pmod = (np.ascontiguousarray(a, t) for a, t in zip(prev, (np.float32,) * 4 + (np.uint32,)))
         ci, cx, cn, cmod = (np.ascontiguousarray(a, t) for a, t in zip(cur, (np.float32,) * 3 + (np.uint32,)))
         h, w = ci.shape[:2]
@@ -852,8 +870,12 @@ class Renderer:
         out_h = np.zeros((h, w, 4), np.float32); out_m = np.zeros((h, w, 2), np.float32); out_v = np.zeros((h, w), np.float32)
         tp = TemporalParams(alpha, alpha_moments, normal_min, plane_max, 0)
         dp = DenoiseParams(0, 0.0, sigma_normal, sigma_plane)
-        self._chk(self.L.pt_post_temporal(self.ctx, int(bool(on_device)), w, h, C.byref(tp), C.byref(dp), _p(ph), _p(pm), _p(px), _p(pn), _p(pmod), _p(ci),
-                                          _p(cx), _p(cn), _p(cmod), _p(opt[0]), _p(opt[1]), _p(opt[2]), _p(out_h), _p(out_m), _p(out_v)))
+        images = [_p(a) for a in (ph, pm, px, pn, pmod, ci, cx, cn, cmod, opt[0], opt[1], opt[2], out_h, out_m, out_v)]
+        if rescue or length_rule or demodulate:
+            to = TemporalOptions(rescue, length_rule, demodulate)
+            self._chk(self.L.pt_post_temporal_options(self.ctx, int(bool(on_device)), w, h, C.byref(tp), C.byref(to), C.byref(dp), *images))
+        else:
+            self._chk(self.L.pt_post_temporal(self.ctx, int(bool(on_device)), w, h, C.byref(tp), C.byref(dp), *images))
         return out_h, out_m, out_v
 
     # ---- mean albedo and the demodulated filter (pt_denoise_albedo)

@@ -205,6 +205,7 @@ struct pt_ctx
     DevBuf d_tp_hist[2], d_tp_mom[2], d_tp_x, d_tp_g, d_tp_var, d_tp_nprev;
     int tp_cur = 0;
     bool temporal_valid = false;
+    bool temporal_demodulated = false; // the kind of history held: one written under demodulate = 1 holds cur / albedo
 
     // pt_integrate_rays_device: the callers' stream keys side by side, 8 bytes per ray of the longest list so far (kept: allocating and freeing
     // it per call would synchronise the device twice per call).  Nothing is allocated until the first call.
@@ -2459,14 +2460,28 @@ int temporal_params(pt_ctx* c, const pt_temporal_params* p, TemporalK& k)
     return PT_OK;
 }
 
-// pt_frame_temporal under the context's lock
-int frame_temporal_locked(pt_ctx* c, uint32_t frame_index, const float* last_inv_projection, const pt_temporal_params* tp, const pt_denoise_params* dp, float* data,
-                          float* position, uint32_t* id, float* out)
+// the stage's options (pt_temporal_options); post: pt_post_temporal_options, which does not demodulate
+constexpr pt_temporal_options kNoTemporalOptions{0u, 0u, 0u, 0u};
+int temporal_options(pt_ctx* c, const pt_temporal_options* o, bool post)
+{
+    if (!o) return fail(c, PT_ERR_ARG, "null pt_temporal_options");
+    if (o->rescue > 1u) return fail(c, PT_ERR_ARG, "pt_temporal_options.rescue must be 0 or 1");
+    if (o->length_rule > PT_TEMPORAL_LENGTH_MEAN) return fail(c, PT_ERR_ARG, "pt_temporal_options.length_rule must be PT_TEMPORAL_LENGTH_MIN or PT_TEMPORAL_LENGTH_MEAN");
+    if (o->demodulate > 1u) return fail(c, PT_ERR_ARG, "pt_temporal_options.demodulate must be 0 or 1");
+    if (o->reserved != 0u) return fail(c, PT_ERR_ARG, "pt_temporal_options::reserved must be 0");
+    if (post && o->demodulate != 0u)
+        return fail(c, PT_ERR_ARG, "pt_temporal_options.demodulate: pt_post_temporal_options does not demodulate; divide the input image by the albedo instead");
+    return PT_OK;
+}
+
+// pt_frame_temporal / pt_frame_temporal_options under the context's lock
+int frame_temporal_locked(pt_ctx* c, uint32_t frame_index, const float* last_inv_projection, const pt_temporal_params* tp, const pt_temporal_options* opts,
+                          const pt_denoise_params* dp, float* data, float* position, uint32_t* id, float* out)
 {
     int r;
     TemporalK tk{};
     DenoiseK k{};
-    if ((r = temporal_params(c, tp, tk)) || (r = denoise_params(c, dp, k))) return r;
+    if ((r = temporal_params(c, tp, tk)) || (r = temporal_options(c, opts, false)) || (r = denoise_params(c, dp, k))) return r;
     if ((r = frame_render(c, frame_index, last_inv_projection, id))) return r;
     FrameMoved fm;
     if ((r = frame_velocity(c, frame_index, last_inv_projection, true, fm))) return r;
@@ -2478,9 +2493,15 @@ int frame_temporal_locked(pt_ctx* c, uint32_t frame_index, const float* last_inv
     if ((r = dev_alloc(c, c->d_tp_x, px * 16)) || (r = dev_alloc(c, c->d_tp_g, px * 16)) || (r = dev_alloc(c, c->d_tp_var, px * 4)) ||
         (r = denoise_scratch(c, px)) || (r = dev_alloc(c, c->d_dn_out, px * 16)))
         return r;
+    const bool demod = opts->demodulate != 0u;
+    if (demod && (r = dev_alloc(c, c->d_dn_k, px * 16))) return r;
+    const f4* albedo = demod ? (const f4*)c->d_galbedo.p : nullptr;
+    f4* kd = demod ? (f4*)c->d_dn_k.p : nullptr;
     const int from = c->tp_cur, to = 1 - c->tp_cur;
-    if (!c->temporal_valid)
+    if (!c->temporal_valid || c->temporal_demodulated != demod)
     {
+        // a history of the other kind is no history: the call starts as after pt_reset_temporal
+        c->temporal_valid = false;
         // no history: N = 0 everywhere fails every tap (the guides are cleared with it so that no word of them is read unwritten)
         HIPCHK(c, hipMemsetAsync(c->d_tp_hist[from].p, 0, px * 16, s));
         HIPCHK(c, hipMemsetAsync(c->d_tp_g.p, 0, px * 16, s));
@@ -2498,11 +2519,11 @@ int frame_temporal_locked(pt_ctx* c, uint32_t frame_index, const float* last_inv
     const TemporalImages im{w, h, (const f4*)c->d_tp_hist[from].p, (const f2*)c->d_tp_mom[from].p, (const f4*)c->d_tp_x.p, (const f4*)c->d_tp_g.p,
                             (const f4*)c->d_input.p, (const f4*)c->d_gpos.p, (const f4*)c->d_gnrm.p, (const uint32_t*)c->d_gmodel.p, xprev, nprev,
                             fm.moved ? (const f2*)c->d_velocity.p : nullptr};
-    launch_temporal_reproject(s, im, tk, (f4*)c->d_tp_hist[to].p, (f2*)c->d_tp_mom[to].p);
+    launch_temporal_reproject(s, im, tk, opts->rescue != 0u, opts->length_rule == PT_TEMPORAL_LENGTH_MEAN, albedo, kd, (f4*)c->d_tp_hist[to].p, (f2*)c->d_tp_mom[to].p);
     launch_temporal_variance(s, w, h, k, tk.alpha, (const f4*)c->d_tp_hist[to].p, (const f2*)c->d_tp_mom[to].p, (const f4*)c->d_gpos.p, (const f4*)c->d_gnrm.p,
                              (const uint32_t*)c->d_gmodel.p, (f4*)c->d_dn_a.p, (f4*)c->d_dn_nv.p, (float*)c->d_tp_var.p);
     launch_temporal_filter(s, w, h, k, tp->feedback != 0u, (const f4*)c->d_gpos.p, (const f4*)c->d_gnrm.p, (const uint32_t*)c->d_gmodel.p, (f4*)c->d_dn_a.p,
-                           (f4*)c->d_dn_b.p, (f4*)c->d_dn_nv.p, (f4*)c->d_dn_out.p, (f4*)c->d_tp_hist[to].p, (f4*)c->d_tp_x.p, (f4*)c->d_tp_g.p);
+                           (f4*)c->d_dn_b.p, (f4*)c->d_dn_nv.p, kd, (f4*)c->d_dn_out.p, (f4*)c->d_tp_hist[to].p, (f4*)c->d_tp_x.p, (f4*)c->d_tp_g.p);
     c->temporal_valid = false; // until the step is known to have run
     if (data) HIPCHK(c, hipMemcpyAsync(data, c->d_input.p, px * 16, hipMemcpyDeviceToHost, s));
     if (position) HIPCHK(c, hipMemcpyAsync(position, c->d_position.p, px * 16, hipMemcpyDeviceToHost, s));
@@ -2512,6 +2533,7 @@ int frame_temporal_locked(pt_ctx* c, uint32_t frame_index, const float* last_inv
     HIPCHK(c, hipGetLastError());
     c->tp_cur = to;
     c->temporal_valid = true;
+    c->temporal_demodulated = demod;
     c->denoised_valid = true;
     frame_snapshot(c);
     return PT_OK;
@@ -2539,7 +2561,15 @@ int pt_frame_temporal(pt_ctx* c, uint32_t frame_index, const float* last_inv_pro
 {
     if (!c) return PT_ERR_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
-    return frame_temporal_locked(c, frame_index, last_inv_projection, tp, dp, data, position, id, out);
+    return frame_temporal_locked(c, frame_index, last_inv_projection, tp, &kNoTemporalOptions, dp, data, position, id, out);
+}
+
+int pt_frame_temporal_options(pt_ctx* c, uint32_t frame_index, const float* last_inv_projection, const pt_temporal_params* tp, const pt_temporal_options* to,
+                              const pt_denoise_params* dp, float* data, float* position, uint32_t* id, float* out)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    return frame_temporal_locked(c, frame_index, last_inv_projection, tp, to, dp, data, position, id, out);
 }
 
 int pt_read_temporal(pt_ctx* c, float* colour_n, float* moments2, float* variance)
@@ -2568,6 +2598,16 @@ int pt_post_temporal(pt_ctx* c, int on_device, uint32_t w, uint32_t h, const pt_
                      const float* position_xyzt, const float* normal_xyz, const uint32_t* model, const float* xprev_xyzt, const float* nprev_xyz,
                      const float* velocity, float* out_colour_n, float* out_moments2, float* out_variance)
 {
+    return pt_post_temporal_options(c, on_device, w, h, tp, &kNoTemporalOptions, dp, prev_colour_n, prev_moments2, prev_position_xyzt, prev_normal_xyz, prev_model,
+                                    input_rgba, position_xyzt, normal_xyz, model, xprev_xyzt, nprev_xyz, velocity, out_colour_n, out_moments2, out_variance);
+}
+
+int pt_post_temporal_options(pt_ctx* c, int on_device, uint32_t w, uint32_t h, const pt_temporal_params* tp, const pt_temporal_options* to,
+                             const pt_denoise_params* dp, const float* prev_colour_n, const float* prev_moments2, const float* prev_position_xyzt,
+                             const float* prev_normal_xyz, const uint32_t* prev_model, const float* input_rgba, const float* position_xyzt,
+                             const float* normal_xyz, const uint32_t* model, const float* xprev_xyzt, const float* nprev_xyz, const float* velocity,
+                             float* out_colour_n, float* out_moments2, float* out_variance)
+{
     if (!c) return PT_ERR_ARG;
     if (!prev_colour_n || !prev_moments2 || !prev_position_xyzt || !prev_normal_xyz || !prev_model || !input_rgba || !position_xyzt || !normal_xyz || !model ||
         !out_colour_n || !out_moments2 || !out_variance || !w || !h)
@@ -2577,7 +2617,8 @@ int pt_post_temporal(pt_ctx* c, int on_device, uint32_t w, uint32_t h, const pt_
     TemporalK tk{};
     DenoiseK k{};
     int r;
-    if ((r = temporal_params(c, tp, tk)) || (r = denoise_params(c, dp, k))) return r;
+    if ((r = temporal_params(c, tp, tk)) || (r = temporal_options(c, to, true)) || (r = denoise_params(c, dp, k))) return r;
+    const bool rescue = to->rescue != 0u, mean_length = to->length_rule == PT_TEMPORAL_LENGTH_MEAN;
     const size_t px = (size_t)w * h;
     // the records as the kernels read them: normals widened to 16 bytes, the previous model word beside its normal
     std::vector<f4> gq(px), nr(px), np;
@@ -2601,7 +2642,8 @@ int pt_post_temporal(pt_ctx* c, int on_device, uint32_t w, uint32_t h, const pt_
         for (uint32_t y = 0; y < h; ++y)
             for (uint32_t x = 0; x < w; ++x)
             {
-                const TemporalOut o = temporal_pixel(im, tk, (int)x, (int)y);
+                const TemporalOut o = rescue ? (mean_length ? temporal_pixel<true, true>(im, tk, (int)x, (int)y) : temporal_pixel<true, false>(im, tk, (int)x, (int)y))
+                                             : (mean_length ? temporal_pixel<false, true>(im, tk, (int)x, (int)y) : temporal_pixel<false, false>(im, tk, (int)x, (int)y));
                 cn[(size_t)y * w + x] = o.h;
                 mm[(size_t)y * w + x] = o.m;
             }
@@ -2633,7 +2675,7 @@ int pt_post_temporal(pt_ctx* c, int on_device, uint32_t w, uint32_t h, const pt_
     f2* dm = (f2*)t.out(px * 8);
     float* dv = (float*)t.out(px * 4);
     if (t.err) return t.err;
-    launch_temporal_reproject(c->stream, im, tk, dh, dm);
+    launch_temporal_reproject(c->stream, im, tk, rescue, mean_length, nullptr, nullptr, dh, dm);
     launch_temporal_variance(c->stream, (int)w, (int)h, k, tk.alpha, dh, dm, im.pos, im.nrm, im.model, nullptr, nullptr, dv);
     HIPCHK(c, hipGetLastError());
     if ((r = t.download(out_colour_n, dh, px * 16)) || (r = t.download(out_moments2, dm, px * 8))) return r;

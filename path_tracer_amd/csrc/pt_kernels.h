@@ -245,16 +245,18 @@ void launch_denoise(hipStream_t s, int w, int h, const DenoiseK& p, const f4* ac
 void launch_denoise_albedo(hipStream_t s, int w, int h, const DenoiseK& p, const f4* accum, const float* moments, const f4* position, const f4* normal,
                            const uint32_t* model, const f4* albedo, bool albedo_is_sum, f4* cv_a, f4* cv_b, f4* nv, f4* kd, f4* out);
 // the temporal stage (pt_frame_temporal, pt_post_temporal; the per-pixel steps are pt_temporal.h's).  n_prev <- the normal guide carried back
-// like launch_post_motion carries the position; hist_out, mom_out <- steps 1-4 of every pixel of im
+// like launch_post_motion carries the position; hist_out, mom_out <- steps 1-4 of every pixel of im under the options rescue and mean_length;
+// albedo (null: no demodulation): cur is divided by the divisor made of it, which goes to kd
 void launch_temporal_motion_normal(hipStream_t s, uint32_t n, const f4* normal, const uint32_t* instance, uint32_t n_instances, const MotionRow* rows, f4* n_prev);
-void launch_temporal_reproject(hipStream_t s, const TemporalImages& im, const TemporalK& k, f4* hist_out, f2* mom_out);
+void launch_temporal_reproject(hipStream_t s, const TemporalImages& im, const TemporalK& k, bool rescue, bool mean_length, const f4* albedo, f4* kd, f4* hist_out,
+                               f2* mom_out);
 // step 5: var <- the variance of every pixel of (cn, mom); cv, nv (either may be null) <- the filter's (C | var) and (normal | 1) images
 void launch_temporal_variance(hipStream_t s, int w, int h, const DenoiseK& p, float alpha, const f4* cn, const f2* mom, const f4* position, const f4* normal,
                               const uint32_t* model, f4* cv, f4* nv, float* var);
 // steps 6 and 7: pt_denoise's levels on cv_a (every pixel valid) to out, and after level 0 the store: xq, gq <- the current guides, with
-// feedback hist.rgb <- level 0's output
+// feedback hist.rgb <- level 0's output; kmul (null: none): the result, and only the result, is multiplied by it
 void launch_temporal_filter(hipStream_t s, int w, int h, const DenoiseK& p, bool feedback, const f4* position, const f4* normal, const uint32_t* model, f4* cv_a,
-                            f4* cv_b, f4* nv, f4* out, f4* hist, f4* xq, f4* gq);
+                            f4* cv_b, f4* nv, const f4* kmul, f4* out, f4* hist, f4* xq, f4* gq);
 // the camera rays of sample rp.first_sample of every local pixel into a hook queue (ray index = local pixel), n_and_heads[0] <- local pixels
 void launch_guide_rays(hipStream_t s, const RenderParams& rp, const CameraView& cam, const CameraOptics& opt, RayQueue rq, uint32_t* n_and_heads);
 // unit hook (pt_surface_colour): rgb[i] <- surface colour of world instance[i], leaf-order triangle tri[i] at barycentrics u[i], v[i]

@@ -515,12 +515,23 @@ __global__ void __launch_bounds__(256) k_tp_motion_normal(uint32_t n, const f4* 
     n_prev[i] = N;
 }
 
-__global__ void __launch_bounds__(256) k_tp_reproject(const TemporalImages im, const TemporalK k, f4* __restrict__ hist_out, f2* __restrict__ mom_out)
+// RESCUE, MEAN: pt_temporal.h's options.  DEMOD (pt_frame_temporal's demodulate): the pixel's divisor k from its albedo guide goes to kd for
+// the last level's multiplication, and cur is divided by it where temporal_pixel loads it; albedo and kd are not touched otherwise
+template <bool RESCUE, bool MEAN, bool DEMOD>
+__global__ void __launch_bounds__(256) k_tp_reproject(const TemporalImages im, const TemporalK k, f4* __restrict__ hist_out, f2* __restrict__ mom_out,
+                                                      const f4* __restrict__ albedo, f4* __restrict__ kd)
 {
     const int x = blockIdx.x * 16 + threadIdx.x, y = blockIdx.y * 16 + threadIdx.y;
     if (x >= im.w || y >= im.h) return;
-    const TemporalOut o = temporal_pixel(im, k, x, y);
     const size_t i = (size_t)y * im.w + x;
+    TemporalOut o;
+    if (DEMOD)
+    {
+        const f4 kdiv = tp_divisor(im.model[i], albedo[i]);
+        kd[i] = kdiv;
+        o = temporal_pixel<RESCUE, MEAN, true>(im, k, x, y, kdiv);
+    }
+    else o = temporal_pixel<RESCUE, MEAN>(im, k, x, y);
     hist_out[i] = o.h;
     mom_out[i] = o.m;
 }
@@ -562,15 +573,37 @@ __global__ void __launch_bounds__(256) k_tp_store(uint32_t n, const f4* __restri
         hist[i] = f4{c.x, c.y, c.z, hist[i].w};
     }
 }
+
+// pt_frame_temporal's demodulate with one level and feedback: the store above took level 0's output, which is the result; now the multiplication
+// k_dn_level<true, true> would have done (the same single operation per channel)
+__global__ void __launch_bounds__(256) k_tp_remodulate(uint32_t n, const f4* __restrict__ kmul, f4* __restrict__ out)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const f4 c = out[i], k = kmul[i];
+    out[i] = f4{c.x * k.x, c.y * k.y, c.z * k.z, 1.0f};
+}
+
+template <bool RESCUE, bool MEAN>
+void tp_reproject(hipStream_t s, const TemporalImages& im, const TemporalK& k, f4* hist_out, f2* mom_out, const f4* albedo, f4* kd)
+{
+    const dim3 grid((im.w + 15) / 16, (im.h + 15) / 16), tile(16, 16);
+    if (albedo) hipLaunchKernelGGL((k_tp_reproject<RESCUE, MEAN, true>), grid, tile, 0, s, im, k, hist_out, mom_out, albedo, kd);
+    else hipLaunchKernelGGL((k_tp_reproject<RESCUE, MEAN, false>), grid, tile, 0, s, im, k, hist_out, mom_out, albedo, kd);
+}
 } // namespace
 
 void launch_temporal_motion_normal(hipStream_t s, uint32_t n, const f4* normal, const uint32_t* instance, uint32_t n_instances, const MotionRow* rows, f4* n_prev)
 {
     hipLaunchKernelGGL(k_tp_motion_normal, dim3((n + 255u) / 256u), dim3(256), 0, s, n, normal, instance, n_instances, rows, n_prev);
 }
-void launch_temporal_reproject(hipStream_t s, const TemporalImages& im, const TemporalK& k, f4* hist_out, f2* mom_out)
+void launch_temporal_reproject(hipStream_t s, const TemporalImages& im, const TemporalK& k, bool rescue, bool mean_length, const f4* albedo, f4* kd, f4* hist_out,
+                               f2* mom_out)
 {
-    hipLaunchKernelGGL(k_tp_reproject, dim3((im.w + 15) / 16, (im.h + 15) / 16), dim3(16, 16), 0, s, im, k, hist_out, mom_out);
+    if (rescue && mean_length) tp_reproject<true, true>(s, im, k, hist_out, mom_out, albedo, kd);
+    else if (rescue) tp_reproject<true, false>(s, im, k, hist_out, mom_out, albedo, kd);
+    else if (mean_length) tp_reproject<false, true>(s, im, k, hist_out, mom_out, albedo, kd);
+    else tp_reproject<false, false>(s, im, k, hist_out, mom_out, albedo, kd);
 }
 void launch_temporal_variance(hipStream_t s, int w, int h, const DenoiseK& p, float alpha, const f4* cn, const f2* mom, const f4* position, const f4* normal,
                               const uint32_t* model, f4* cv, f4* nv, float* var)
@@ -578,23 +611,28 @@ void launch_temporal_variance(hipStream_t s, int w, int h, const DenoiseK& p, fl
     hipLaunchKernelGGL(k_tp_variance, dim3((w + 15) / 16, (h + 15) / 16), dim3(16, 16), 0, s, w, h, p, alpha, cn, mom, position, normal, model, cv, nv, var);
 }
 void launch_temporal_filter(hipStream_t s, int w, int h, const DenoiseK& p, bool feedback, const f4* position, const f4* normal, const uint32_t* model, f4* cv_a,
-                            f4* cv_b, f4* nv, f4* out, f4* hist, f4* xq, f4* gq)
+                            f4* cv_b, f4* nv, const f4* kmul, f4* out, f4* hist, f4* xq, f4* gq)
 {
     const dim3 tile(16, 16), grid((w + 15) / 16, (h + 15) / 16);
     const uint32_t n = (uint32_t)w * (uint32_t)h;
     f4* cur = cv_a;
     f4* other = cv_b;
+    // the history keeps level 0's output BEFORE the multiplication: where level 0 is also the last, the multiplication follows the store
+    const bool remod_after = kmul && feedback && p.iterations == 1u;
     for (uint32_t it = 0; it < p.iterations; ++it)
     {
         const int step = 1 << it;
         const bool last = it + 1u == p.iterations;
         f4* dst = last ? out : other;
-        if (last) hipLaunchKernelGGL(k_dn_level<true>, grid, tile, 0, s, w, h, step, p, (const f4*)cur, position, (const f4*)nv, model, dst, (const f4*)nullptr);
+        if (last && kmul && !remod_after)
+            hipLaunchKernelGGL((k_dn_level<true, true>), grid, tile, 0, s, w, h, step, p, (const f4*)cur, position, (const f4*)nv, model, dst, kmul);
+        else if (last) hipLaunchKernelGGL(k_dn_level<true>, grid, tile, 0, s, w, h, step, p, (const f4*)cur, position, (const f4*)nv, model, dst, (const f4*)nullptr);
         else hipLaunchKernelGGL(k_dn_level<false>, grid, tile, 0, s, w, h, step, p, (const f4*)cur, position, (const f4*)nv, model, dst, (const f4*)nullptr);
         if (it == 0u)
             hipLaunchKernelGGL(k_tp_store, dim3((n + 255u) / 256u), dim3(256), 0, s, n, position, normal, model, feedback ? (const f4*)dst : (const f4*)nullptr, hist, xq, gq);
         if (!last) std::swap(cur, other);
     }
+    if (remod_after) hipLaunchKernelGGL(k_tp_remodulate, dim3((n + 255u) / 256u), dim3(256), 0, s, n, kmul, out);
 }
 
 void launch_denoise(hipStream_t s, int w, int h, const DenoiseK& p, const f4* accum, const float* moments, const f4* position, const f4* normal,

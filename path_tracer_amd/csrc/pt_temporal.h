@@ -5,6 +5,10 @@
 // Records of the previous call, one per pixel, each read with one 16-byte (M: 8-byte) load:
 //   hist : C.rgb | N          mom : mu1, mu2          xq : X'.xyz | t'          gq : n'.xyz | the bits of m'
 // A tap is tested on m' and N (gq, hist) before xq and mom are touched.
+//
+// The options of pt_temporal_params are template parameters, so that the plain stage compiles to what it was: RESCUE (step 3b: a pixel whose
+// listed taps all failed searches the 3 x 3 around its reprojected position), MEAN (PT_TEMPORAL_LENGTH_MEAN: the history length is the taps'
+// weighted mean, not their least) and DEMOD (cur is divided by the pixel's divisor kdiv, see tp_divisor, where it is loaded).
 #pragma once
 #include "pt_math.h"
 #include "pt_types.h"
@@ -52,14 +56,26 @@ PT_HD f4 motion_normal(const float inv[12], const float prv[12], f4 n)
     return f4{q[0], q[1], q[2], n.w};
 }
 
-// steps 1-4 for pixel (x, y): the taps, their tests, the fold and the blend
-PT_HD TemporalOut temporal_pixel(const TemporalImages& im, const TemporalK& k, int x, int y)
+// pt_denoise_albedo's divisor: (1, 1, 1) for a miss, else the albedo floored at 2^-10 per channel
+constexpr float kTemporalAlbedoFloor = 0x1p-10f;
+PT_HD f4 tp_divisor(uint32_t model, f4 A)
+{
+    if (model == MISS_ID) return f4{1.0f, 1.0f, 1.0f, 0.0f};
+    return f4{A.x > kTemporalAlbedoFloor ? A.x : kTemporalAlbedoFloor, A.y > kTemporalAlbedoFloor ? A.y : kTemporalAlbedoFloor,
+              A.z > kTemporalAlbedoFloor ? A.z : kTemporalAlbedoFloor, 0.0f};
+}
+
+// steps 1-4 for pixel (x, y): the taps, their tests, the fold (3b: the rescue walk) and the blend
+template <bool RESCUE = false, bool MEAN = false, bool DEMOD = false>
+PT_HD TemporalOut temporal_pixel(const TemporalImages& im, const TemporalK& k, int x, int y, f4 kdiv = f4{1.0f, 1.0f, 1.0f, 0.0f})
 {
     const int w = im.w, h = im.h;
     const size_t i = (size_t)y * w + x;
     // the list as four slots in list order; a slot that is not in the list has b = 0 and fails the b > 0 test
     int qx[4] = {x, x, x, x}, qy[4] = {y, y, y, y};
     float b[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    [[maybe_unused]] int cx = x, cy = y; // RESCUE: the centre of the 3 x 3, and whether step 1's list has any entry
+    [[maybe_unused]] bool listed = true;
     if (!im.vel) b[0] = 1.0f;
     else
     {
@@ -79,7 +95,13 @@ PT_HD TemporalOut temporal_pixel(const TemporalImages& im, const TemporalK& k, i
                     qy[2 * j + ii] = y0 + j;
                     b[2 * j + ii] = (ii ? tx : 1.0f - tx) * (j ? ty : 1.0f - ty);
                 }
+            if (RESCUE)
+            {
+                cx = x0 + (tx >= 0.5f ? 1 : 0);
+                cy = y0 + (ty >= 0.5f ? 1 : 0);
+            }
         }
+        else listed = false;
     }
     const uint32_t mp = im.model[i];
     const bool hit = mp != MISS_ID;
@@ -112,6 +134,7 @@ PT_HD TemporalOut temporal_pixel(const TemporalImages& im, const TemporalK& k, i
     f2 mq[4];
     for (int t = 0; t < 4; ++t) mq[t] = ok[t] ? im.mom[q[t]] : f2{0.0f, 0.0f};
     float sw = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f, s1 = 0.0f, s2 = 0.0f, nmin = INFINITY;
+    [[maybe_unused]] float sn = 0.0f;
     for (int t = 0; t < 4; ++t)
     {
         if (!ok[t]) continue;
@@ -122,14 +145,67 @@ PT_HD TemporalOut temporal_pixel(const TemporalImages& im, const TemporalK& k, i
         s1 = s1 + b[t] * mq[t].x;
         s2 = s2 + b[t] * mq[t].y;
         nmin = nmin < hq[t].w ? nmin : hq[t].w;
+        if (MEAN) sn = sn + b[t] * hq[t].w;
     }
-    const f4 cur = im.cur[i];
+    if (RESCUE)
+    {
+        // step 3b, a row of the 3 x 3 at a time under the loads' discipline above; every tap has b = 1, and 1 * v is v
+        if (listed && sw == 0.0f)
+        {
+            const f4 np = hit ? im.nprev[i] : f4{0.0f, 0.0f, 0.0f, 0.0f}, xp = hit ? im.xprev[i] : f4{0.0f, 0.0f, 0.0f, 0.0f};
+            const float bound = hit ? k.plane_max * im.pos[i].w : 0.0f;
+            for (int dy = -1; dy <= 1; ++dy)
+            {
+                size_t rq[3];
+                bool rok[3];
+                f4 rh[3], rg[3];
+                for (int t = 0; t < 3; ++t)
+                {
+                    const int rx = cx + (t - 1), ry = cy + dy;
+                    const bool inside = rx >= 0 && rx < w && ry >= 0 && ry < h;
+                    rq[t] = inside ? (size_t)ry * w + rx : i;
+                    rh[t] = im.hist[rq[t]];
+                    rg[t] = im.gq[rq[t]];
+                    rok[t] = inside;
+                }
+                for (int t = 0; t < 3; ++t) rok[t] = rok[t] && rh[t].w > 0.0f && bits(rg[t].w) == mp;
+                if (hit)
+                {
+                    f4 rx4[3];
+                    for (int t = 0; t < 3; ++t) rx4[t] = rok[t] ? im.xq[rq[t]] : f4{0.0f, 0.0f, 0.0f, 0.0f};
+                    for (int t = 0; t < 3; ++t)
+                    {
+                        const float nd = (np.x * rg[t].x + np.y * rg[t].y) + np.z * rg[t].z;
+                        const float ex = rx4[t].x - xp.x, ey = rx4[t].y - xp.y, ez = rx4[t].z - xp.z;
+                        const float pd = fabsf((np.x * ex + np.y * ey) + np.z * ez);
+                        rok[t] = rok[t] && nd >= k.normal_min && pd <= bound;
+                    }
+                }
+                f2 rm[3];
+                for (int t = 0; t < 3; ++t) rm[t] = rok[t] ? im.mom[rq[t]] : f2{0.0f, 0.0f};
+                for (int t = 0; t < 3; ++t)
+                {
+                    if (!rok[t]) continue;
+                    sw = sw + 1.0f;
+                    sr = sr + rh[t].x;
+                    sg = sg + rh[t].y;
+                    sb = sb + rh[t].z;
+                    s1 = s1 + rm[t].x;
+                    s2 = s2 + rm[t].y;
+                    nmin = nmin < rh[t].w ? nmin : rh[t].w;
+                    if (MEAN) sn = sn + rh[t].w;
+                }
+            }
+        }
+    }
+    f4 cur = im.cur[i];
+    if (DEMOD) cur = f4{cur.x / kdiv.x, cur.y / kdiv.y, cur.z / kdiv.z, cur.w};
     const float l = tp_lum(cur);
     TemporalOut o;
     if (sw > 0.0f)
     {
         const float hr = sr / sw, hg = sg / sw, hb = sb / sw, m1 = s1 / sw, m2 = s2 / sw;
-        const float n1 = nmin + 1.0f;
+        const float n1 = (MEAN ? floorf(sn / sw + 0.5f) : nmin) + 1.0f;
         const float n = n1 < kTemporalMaxN ? n1 : kTemporalMaxN;
         const float rn = 1.0f / n;
         const float a = k.alpha > rn ? k.alpha : rn, am = k.alpha_moments > rn ? k.alpha_moments : rn;

@@ -99,6 +99,24 @@ def cornell_box(width=256, height=256) -> SceneDesc:
     return SceneDesc.new(cornell_models(), reference_camera(width / height), "cornell")
 
 
+def checker_textured(desc: SceneDesc, names=("cb_main", "cb_left", "cb_right"), n=8, repeat=4.0, dark=0.2) -> SceneDesc:
+    """`desc` with an n x n checker (texels 1 and `dark`) on the models in `names`: UVs planar over the two longest axes of each model's
+    extent, `repeat` periods across it, computed in float64 and rounded once.  The textured-wall scene of the denoiser's measurements."""
+    from .scene_desc import Texture
+    i, j = np.meshgrid(np.arange(n), np.arange(n))
+    tex = Texture.new(np.repeat(np.where((i + j) & 1, np.float32(dark), np.float32(1.0))[..., None], 3, axis=2))
+    models = []
+    for m in desc.models:
+        if m.name in names:
+            p = np.asarray(m.positions, np.float64)
+            lo, hi = p.min(axis=(0, 1)), p.max(axis=(0, 1))
+            ax = np.sort(np.argsort(hi - lo, kind="stable")[1:])
+            uvs = ((p[:, :, ax] - lo[ax]) / (hi - lo)[ax] * float(repeat)).astype(np.float32)
+            m = Model.new(m.positions, m.normals, m.material.textured(tex), m.matrices, m.name, uvs=uvs)
+        models.append(m)
+    return SceneDesc.new(models, desc.camera, desc.name + " checker")
+
+
 def cornell_mixed(width=256, height=256) -> SceneDesc:
     """Material-variety Cornell: tall box = GGX metal (main.rs:86), short box = smooth dielectric (main.rs:89)."""
     models = cornell_models(GGX.new_metal((0.1, 0.1, 0.45), 0.4), Dielectric.new((0.95, 0.95, 0.95), 1.5, None))

@@ -16,7 +16,9 @@ profiles/r16_followed_guides.md), and adds the cost of the guides on the mixed C
 1-spp frames of a slow camera pan against a many-sample render of the last pose, for the raw frame, for pt_frame_moving + pt_denoise over
 the same sequence and for pt_frame_temporal; and at the timing size the whole calls in turn, round by round: pt_frame_moving + pt_denoise,
 pt_frame_temporal in steady state, and pt_frame_temporal on the frames right after a cut (pt_reset_temporal), where every pixel still walks
-the 7 x 7 spatial variance.
+the 7 x 7 spatial variance.  It then measures the stage's options (rescue, length_rule, demodulate; profiles/r21_temporal_options.md): the same
+pan under each option set on the Cornell box and on the checker-textured one (scenes.checker_textured), and at the timing size
+pt_frame_temporal in steady state and after a cut with no option, each option and all three, one after the other in every round.
 
     python tools/denoise_bench.py [--albedo] [--follow K] [--temporal] [--size 256] [--ref-spp 4096] [--spp 1,4,16,64] [--width 1920 --height 1080 --reps 20] [--out file.json]
 """
@@ -116,8 +118,14 @@ def follow_timing(api, scenes, w, h, reps, depth):
 PAN = (1.0, 0.0, 4.0e-7)   # EV_MOUSE_MOTION per frame: 0.004 rad, half a pixel of a 128-pixel, 60-degree frame
 
 
-def temporal_quality(api, scenes, size, frames, ref_spp, depth, feedback=0, pan=True, **params):
+OPTION_SETS = [("plain", {}), ("rescue", dict(rescue=1)), ("mean", dict(length_rule=1)), ("rescue+mean", dict(rescue=1, length_rule=1)),
+               ("demodulate", dict(demodulate=1)), ("all", dict(rescue=1, length_rule=1, demodulate=1))]
+
+
+def temporal_quality(api, scenes, size, frames, ref_spp, depth, feedback=0, pan=True, scene="cornell", **params):
     sc = scenes.cornell_box(size, size)
+    if scene == "checker":
+        sc = scenes.checker_textured(sc)
     t = api.Renderer(sc, size, size, max_bounces=depth); m = api.Renderer(sc, size, size, max_bounces=depth)
     ref = api.Renderer(sc, size, size, max_bounces=depth)
     last_t, last_m = t.inv_projection(), m.inv_projection()
@@ -134,7 +142,7 @@ def temporal_quality(api, scenes, size, frames, ref_spp, depth, feedback=0, pan=
     hist = np.concatenate([hist[..., :3], np.ones_like(hist[..., 3:])], -1)     # (with feedback: level 0's output)
     racc, _, _ = ref.render(1 << 20, ref_spp, want_position=False)
     ref_disp = ref.post_tonemap(racc)
-    row = dict(size=size, frames=frames, ref_spp=ref_spp, feedback=feedback, pan=pan, params=params, display_rmse_history=rmse(t.post_tonemap(hist), ref_disp), display_rmse_raw=rmse(t.post_tonemap(data), ref_disp),
+    row = dict(scene=scene, size=size, frames=frames, ref_spp=ref_spp, feedback=feedback, pan=pan, params=params, display_rmse_history=rmse(t.post_tonemap(hist), ref_disp), display_rmse_raw=rmse(t.post_tonemap(data), ref_disp),
                display_rmse_moving_denoise=rmse(m.post_tonemap(den), ref_disp), display_rmse_temporal=rmse(t.post_tonemap(out), ref_disp),
                mean_history=float(n.mean()), disoccluded=int((n == 1).sum()))
     for r in (t, m, ref):
@@ -170,6 +178,34 @@ def temporal_timing(api, scenes, w, h, reps, depth):
     return row
 
 
+def temporal_option_timing(api, scenes, w, h, reps, depth):
+    """pt_frame_temporal under every option set, steady and right after a cut, in turn in every round (the plain stage is one of the sets)"""
+    sc = scenes.cornell_box(w, h)
+    steady = {n: api.Renderer(sc, w, h, max_bounces=depth) for n, _ in OPTION_SETS}
+    cut = {n: api.Renderer(sc, w, h, max_bounces=depth) for n, _ in OPTION_SETS}
+    everyone = list(steady.values()) + list(cut.values())
+    last = {id(r): r.inv_projection() for r in everyone}
+    ts = {n: [] for n, _ in OPTION_SETS}; tc = {n: [] for n, _ in OPTION_SETS}
+    for k in range(reps + 4):
+        for r in everyone:
+            r.camera_input(api.EV_MOUSE_MOTION, *PAN)
+        for n, opt in OPTION_SETS:
+            t0 = time.perf_counter(); steady[n].frame_temporal(k, last[id(steady[n])], download=False, **opt); t1 = time.perf_counter()
+            cut[n].reset_temporal()
+            cut[n].frame_temporal(k, last[id(cut[n])], download=False, **opt); t2 = time.perf_counter()
+            if k >= 4:
+                ts[n].append(t1 - t0); tc[n].append(t2 - t1)
+        for r in everyone:
+            last[id(r)] = r.inv_projection()
+    lost = float((steady["plain"].read_temporal()[0][..., 3] == 1).mean())
+    for r in everyone:
+        r.close()
+    med = lambda v: dict(median=1e3 * float(np.median(v)), min=1e3 * float(np.min(v)), max=1e3 * float(np.max(v)))
+    row = dict(width=w, height=h, reps=reps, plain_fraction_restarted=lost, steady={n: med(v) for n, v in ts.items()}, after_cut={n: med(v) for n, v in tc.items()})
+    print(json.dumps(row), flush=True)
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=256)
@@ -201,8 +237,11 @@ def main():
     if a.temporal:
         if not a.no_quality:
             res["temporal_quality"] = [temporal_quality(api, scenes, a.temporal_size, a.temporal_frames, a.temporal_ref_spp, a.bounces, feedback=f) for f in (0, 1)]
+            res["temporal_option_quality"] = [temporal_quality(api, scenes, a.temporal_size, a.temporal_frames, a.temporal_ref_spp, a.bounces, scene=sc, **opt)
+                                              for sc in ("cornell", "checker") for _, opt in OPTION_SETS]
         if a.reps > 0:
             res["temporal_timing"] = temporal_timing(api, scenes, a.width, a.height, a.reps, a.bounces)
+            res["temporal_option_timing"] = temporal_option_timing(api, scenes, a.width, a.height, a.reps, a.bounces)
     if a.out:
         with open(a.out, "w") as f:
             json.dump(res, f, indent=1)
