@@ -1617,6 +1617,14 @@ bool albedo_current(const pt_ctx* c)
     return c->albedo_valid && c->albedo_scene_version == c->scene_version && c->albedo_config_version == c->config_version;
 }
 
+// xyz per pixel as the 16-byte records the kernels read: w = 0, or model's word beside the normal (the temporal stage's gq)
+std::vector<f4> widen_xyz(const float* xyz, size_t px, const uint32_t* w = nullptr)
+{
+    std::vector<f4> v(px);
+    for (size_t i = 0; i < px; ++i) v[i] = f4{xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], w ? from_bits(w[i]) : 0.0f};
+    return v;
+}
+
 // the filter's scratch images for px pixels
 int denoise_scratch(pt_ctx* c, size_t px)
 {
@@ -2621,17 +2629,7 @@ int pt_post_temporal_options(pt_ctx* c, int on_device, uint32_t w, uint32_t h, c
     const bool rescue = to->rescue != 0u, mean_length = to->length_rule == PT_TEMPORAL_LENGTH_MEAN;
     const size_t px = (size_t)w * h;
     // the records as the kernels read them: normals widened to 16 bytes, the previous model word beside its normal
-    std::vector<f4> gq(px), nr(px), np;
-    for (size_t i = 0; i < px; ++i)
-    {
-        gq[i] = f4{prev_normal_xyz[3 * i], prev_normal_xyz[3 * i + 1], prev_normal_xyz[3 * i + 2], from_bits(prev_model[i])};
-        nr[i] = f4{normal_xyz[3 * i], normal_xyz[3 * i + 1], normal_xyz[3 * i + 2], 0.0f};
-    }
-    if (nprev_xyz)
-    {
-        np.resize(px);
-        for (size_t i = 0; i < px; ++i) np[i] = f4{nprev_xyz[3 * i], nprev_xyz[3 * i + 1], nprev_xyz[3 * i + 2], 0.0f};
-    }
+    const std::vector<f4> gq = widen_xyz(prev_normal_xyz, px, prev_model), nr = widen_xyz(normal_xyz, px), np = widen_xyz(nprev_xyz, nprev_xyz ? px : 0);
     if (!on_device)
     {
         const TemporalImages im{(int)w, (int)h, (const f4*)prev_colour_n, (const f2*)prev_moments2, (const f4*)prev_position_xyzt, gq.data(), (const f4*)input_rgba,
@@ -2639,14 +2637,15 @@ int pt_post_temporal_options(pt_ctx* c, int on_device, uint32_t w, uint32_t h, c
                                 (const f2*)velocity};
         std::vector<f4> cn(px);
         std::vector<f2> mm(px);
-        for (uint32_t y = 0; y < h; ++y)
-            for (uint32_t x = 0; x < w; ++x)
-            {
-                const TemporalOut o = rescue ? (mean_length ? temporal_pixel<true, true>(im, tk, (int)x, (int)y) : temporal_pixel<true, false>(im, tk, (int)x, (int)y))
-                                             : (mean_length ? temporal_pixel<false, true>(im, tk, (int)x, (int)y) : temporal_pixel<false, false>(im, tk, (int)x, (int)y));
-                cn[(size_t)y * w + x] = o.h;
-                mm[(size_t)y * w + x] = o.m;
-            }
+        with_temporal_options(rescue, mean_length, [&](auto R, auto M) {
+            for (uint32_t y = 0; y < h; ++y)
+                for (uint32_t x = 0; x < w; ++x)
+                {
+                    const TemporalOut o = temporal_pixel<R.value, M.value>(im, tk, (int)x, (int)y);
+                    cn[(size_t)y * w + x] = o.h;
+                    mm[(size_t)y * w + x] = o.m;
+                }
+        });
         for (uint32_t y = 0; y < h; ++y)
             for (uint32_t x = 0; x < w; ++x)
                 out_variance[(size_t)y * w + x] =
@@ -2989,6 +2988,55 @@ int denoise_ready(pt_ctx* c, const pt_denoise_params* p, const char* who, const 
     return PT_OK;
 }
 
+// pt_denoise and pt_denoise_albedo (albedo_source: the latter's, else null) under the context's lock
+int denoise_locked(pt_ctx* c, const pt_denoise_params* p, const char* who, const uint32_t* albedo_source, float* rgba)
+{
+    DenoiseK k{};
+    const float* moments;
+    int r;
+    if ((r = denoise_ready(c, p, who, albedo_source, k, &moments))) return r;
+    const bool mean = albedo_source && *albedo_source == PT_ALBEDO_MEAN;
+    const size_t px = c->local_pixels;
+    if (albedo_source && (r = dev_alloc(c, c->d_dn_k, px * 16))) return r;
+    const void* albedo = !albedo_source ? nullptr : mean ? c->d_albedo_sum.p : c->d_galbedo.p;
+    launch_denoise(c->stream, (int)c->cfg.width, (int)c->cfg.height, k,
+                   DenoiseImages{(const f4*)c->d_accum.p, moments, (const f4*)c->d_gpos.p, (const f4*)c->d_gnrm.p, (const uint32_t*)c->d_gmodel.p, (const f4*)albedo, mean,
+                                 (f4*)c->d_dn_a.p, (f4*)c->d_dn_b.p, (f4*)c->d_dn_nv.p, (f4*)c->d_dn_k.p, (f4*)c->d_dn_out.p});
+    HIPCHK(c, hipGetLastError());
+    if (rgba) HIPCHK(c, hipMemcpyAsync(rgba, c->d_dn_out.p, px * 16, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->denoised_valid = true;
+    return PT_OK;
+}
+
+// pt_post_denoise and pt_post_denoise_albedo (albedo: the latter's xyz image, else null) from the first device call on, under the lock
+int post_denoise_locked(pt_ctx* c, uint32_t w, uint32_t h, const DenoiseK& k, const float* accum, const float* position, const float* normal, const uint32_t* model,
+                        const float* albedo, const float* sumsq, float* out)
+{
+    int r;
+    if ((r = ensure_device(c))) return r;
+    Staging t(c);
+    const size_t px = (size_t)w * h;
+    const std::vector<f4> nr = widen_xyz(normal, px), al = widen_xyz(albedo, albedo ? px : 0);
+    DenoiseImages im{};
+    im.accum = (const f4*)t.in(accum, px * 16);
+    im.position = (const f4*)t.in(position, px * 16);
+    im.normal = (const f4*)t.in(nr.data(), px * 16);
+    if (albedo) im.albedo = (const f4*)t.in(al.data(), px * 16);
+    im.model = (const uint32_t*)t.in(model, px * 4);
+    im.moments = sumsq ? (const float*)t.in(sumsq, px * 4) : nullptr;
+    im.out = (f4*)t.out(px * 16);
+    if (t.err) return t.err;
+    if ((r = denoise_scratch(c, px)) || (albedo && (r = dev_alloc(c, c->d_dn_k, px * 16)))) return r;
+    im.cv_a = (f4*)c->d_dn_a.p;
+    im.cv_b = (f4*)c->d_dn_b.p;
+    im.nv = (f4*)c->d_dn_nv.p;
+    im.kd = (f4*)c->d_dn_k.p;
+    launch_denoise(c->stream, (int)w, (int)h, k, im);
+    HIPCHK(c, hipGetLastError());
+    return t.download(out, im.out, px * 16);
+}
+
 int accumulate_albedo_locked(pt_ctx* c, uint32_t first_sample, uint32_t n_samples, uint32_t max_hops, const char* who);
 } // namespace
 
@@ -3060,18 +3108,7 @@ int pt_denoise(pt_ctx* c, const pt_denoise_params* p, float* rgba)
 {
     if (!c) return PT_ERR_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
-    DenoiseK k{};
-    const float* moments;
-    int r;
-    if ((r = denoise_ready(c, p, "pt_denoise", nullptr, k, &moments))) return r;
-    const size_t px = c->local_pixels;
-    launch_denoise(c->stream, (int)c->cfg.width, (int)c->cfg.height, k, (const f4*)c->d_accum.p, moments, (const f4*)c->d_gpos.p, (const f4*)c->d_gnrm.p,
-                   (const uint32_t*)c->d_gmodel.p, (f4*)c->d_dn_a.p, (f4*)c->d_dn_b.p, (f4*)c->d_dn_nv.p, (f4*)c->d_dn_out.p);
-    HIPCHK(c, hipGetLastError());
-    if (rgba) HIPCHK(c, hipMemcpyAsync(rgba, c->d_dn_out.p, px * 16, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->denoised_valid = true;
-    return PT_OK;
+    return denoise_locked(c, p, "pt_denoise", nullptr, rgba);
 }
 
 int pt_write_denoised_image(pt_ctx* c, const char* path)
@@ -3097,22 +3134,7 @@ int pt_post_denoise(pt_ctx* c, uint32_t w, uint32_t h, const pt_denoise_params* 
     DenoiseK k{};
     int r;
     if ((r = denoise_params(c, p, k))) return r;
-    if ((r = ensure_device(c))) return r;
-    Staging t(c);
-    const size_t px = (size_t)w * h;
-    std::vector<f4> nr(px);
-    for (size_t i = 0; i < px; ++i) nr[i] = f4{normal[3 * i], normal[3 * i + 1], normal[3 * i + 2], 0.0f};
-    const f4* da = (const f4*)t.in(accum, px * 16);
-    const f4* dp = (const f4*)t.in(position, px * 16);
-    const f4* dn = (const f4*)t.in(nr.data(), px * 16);
-    const uint32_t* dm = (const uint32_t*)t.in(model, px * 4);
-    const float* dq = sumsq ? (const float*)t.in(sumsq, px * 4) : nullptr;
-    f4* dout = (f4*)t.out(px * 16);
-    if (t.err) return t.err;
-    if ((r = denoise_scratch(c, px))) return r;
-    launch_denoise(c->stream, (int)w, (int)h, k, da, dq, dp, dn, dm, (f4*)c->d_dn_a.p, (f4*)c->d_dn_b.p, (f4*)c->d_dn_nv.p, dout);
-    HIPCHK(c, hipGetLastError());
-    return t.download(out, dout, px * 16);
+    return post_denoise_locked(c, w, h, k, accum, position, normal, model, nullptr, sumsq, out);
 }
 
 // ---- mean albedo and the demodulated filter
@@ -3189,21 +3211,7 @@ int pt_denoise_albedo(pt_ctx* c, const pt_denoise_params* p, uint32_t albedo_sou
 {
     if (!c) return PT_ERR_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
-    DenoiseK k{};
-    const float* moments;
-    int r;
-    if ((r = denoise_ready(c, p, "pt_denoise_albedo", &albedo_source, k, &moments))) return r;
-    const bool mean = albedo_source == PT_ALBEDO_MEAN;
-    const size_t px = c->local_pixels;
-    if ((r = dev_alloc(c, c->d_dn_k, px * 16))) return r;
-    launch_denoise_albedo(c->stream, (int)c->cfg.width, (int)c->cfg.height, k, (const f4*)c->d_accum.p, moments, (const f4*)c->d_gpos.p,
-                          (const f4*)c->d_gnrm.p, (const uint32_t*)c->d_gmodel.p, (const f4*)(mean ? c->d_albedo_sum.p : c->d_galbedo.p), mean, (f4*)c->d_dn_a.p, (f4*)c->d_dn_b.p, (f4*)c->d_dn_nv.p,
-                          (f4*)c->d_dn_k.p, (f4*)c->d_dn_out.p);
-    HIPCHK(c, hipGetLastError());
-    if (rgba) HIPCHK(c, hipMemcpyAsync(rgba, c->d_dn_out.p, px * 16, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->denoised_valid = true;
-    return PT_OK;
+    return denoise_locked(c, p, "pt_denoise_albedo", &albedo_source, rgba);
 }
 
 int pt_post_denoise_albedo(pt_ctx* c, uint32_t w, uint32_t h, const pt_denoise_params* p, const float* accum, const float* position, const float* normal,
@@ -3220,24 +3228,7 @@ int pt_post_denoise_albedo(pt_ctx* c, uint32_t w, uint32_t h, const pt_denoise_p
     for (size_t i = 0; i < 3 * px; ++i)
         if (!(albedo[i] >= 0.0f) || !std::isfinite(albedo[i]))
             return fail(c, PT_ERR_ARG, "pt_post_denoise_albedo: pixel " + std::to_string(i / 3) + " has an albedo component that is negative or not finite");
-    if ((r = ensure_device(c))) return r;
-    Staging t(c);
-    std::vector<f4> nr(px), al(px);
-    for (size_t i = 0; i < px; ++i) nr[i] = f4{normal[3 * i], normal[3 * i + 1], normal[3 * i + 2], 0.0f};
-    for (size_t i = 0; i < px; ++i) al[i] = f4{albedo[3 * i], albedo[3 * i + 1], albedo[3 * i + 2], 0.0f};
-    const f4* da = (const f4*)t.in(accum, px * 16);
-    const f4* dp = (const f4*)t.in(position, px * 16);
-    const f4* dn = (const f4*)t.in(nr.data(), px * 16);
-    const f4* dal = (const f4*)t.in(al.data(), px * 16);
-    const uint32_t* dm = (const uint32_t*)t.in(model, px * 4);
-    const float* dq = sumsq ? (const float*)t.in(sumsq, px * 4) : nullptr;
-    f4* dout = (f4*)t.out(px * 16);
-    if (t.err) return t.err;
-    if ((r = denoise_scratch(c, px)) || (r = dev_alloc(c, c->d_dn_k, px * 16))) return r;
-    launch_denoise_albedo(c->stream, (int)w, (int)h, k, da, dq, dp, dn, dm, dal, false, (f4*)c->d_dn_a.p, (f4*)c->d_dn_b.p, (f4*)c->d_dn_nv.p,
-                          (f4*)c->d_dn_k.p, dout);
-    HIPCHK(c, hipGetLastError());
-    return t.download(out, dout, px * 16);
+    return post_denoise_locked(c, w, h, k, accum, position, normal, model, albedo, sumsq, out);
 }
 
 // ---- caller-supplied rays and irradiance probes

@@ -236,14 +236,24 @@ struct DenoiseK
     uint32_t log2_sigma_n; // max(0, n_p . n_q) is squared this many times
     uint32_t iterations;   // 1..8
 };
-// guides of a w x h image: position xyz | t, normal xyz | -, model (MISS_ID = miss); moments null = spatial variance.  Works in the three
-// scratch images cv_a, cv_b (colour | variance) and nv (normal | valid) and writes the result (c, 1) or (0, 0, 0, 0) to out
-void launch_denoise(hipStream_t s, int w, int h, const DenoiseK& p, const f4* accum, const float* moments, const f4* position, const f4* normal,
-                    const uint32_t* model, f4* cv_a, f4* cv_b, f4* nv, f4* out);
-// pt_denoise_albedo / pt_post_denoise_albedo: the same filter on the accumulation divided by the albedo (xyz per pixel; albedo_is_sum: the
-// mean-albedo sums, xyz / w), the last level multiplying it back.  kd: one more scratch image, the per-pixel divisor
-void launch_denoise_albedo(hipStream_t s, int w, int h, const DenoiseK& p, const f4* accum, const float* moments, const f4* position, const f4* normal,
-                           const uint32_t* model, const f4* albedo, bool albedo_is_sum, f4* cv_a, f4* cv_b, f4* nv, f4* kd, f4* out);
+// the filter's images (w x h).  Guides: position xyz | t, normal xyz | -, model (MISS_ID = miss); moments null = spatial variance.  albedo null:
+// pt_denoise / pt_post_denoise.  Else pt_denoise_albedo / pt_post_denoise_albedo: the same filter on the accumulation divided by the albedo
+// (xyz per pixel; albedo_is_sum: the mean-albedo sums, xyz / w), the last level multiplying it back
+struct DenoiseImages
+{
+    const f4* accum;
+    const float* moments;
+    const f4* position;
+    const f4* normal;
+    const uint32_t* model;
+    const f4* albedo;
+    bool albedo_is_sum;
+    f4 *cv_a, *cv_b; // scratch: colour | variance
+    f4* nv;          // scratch: normal | valid
+    f4* kd;          // scratch, with an albedo only: the per-pixel divisor
+    f4* out;         // the result (c, 1) or (0, 0, 0, 0)
+};
+void launch_denoise(hipStream_t s, int w, int h, const DenoiseK& p, const DenoiseImages& im);
 // the temporal stage (pt_frame_temporal, pt_post_temporal; the per-pixel steps are pt_temporal.h's).  n_prev <- the normal guide carried back
 // like launch_post_motion carries the position; hist_out, mom_out <- steps 1-4 of every pixel of im under the options rescue and mean_length;
 // albedo (null: no demodulation): cur is divided by the divisor made of it, which goes to kd
@@ -253,7 +263,7 @@ void launch_temporal_reproject(hipStream_t s, const TemporalImages& im, const Te
 // step 5: var <- the variance of every pixel of (cn, mom); cv, nv (either may be null) <- the filter's (C | var) and (normal | 1) images
 void launch_temporal_variance(hipStream_t s, int w, int h, const DenoiseK& p, float alpha, const f4* cn, const f2* mom, const f4* position, const f4* normal,
                               const uint32_t* model, f4* cv, f4* nv, float* var);
-// steps 6 and 7: pt_denoise's levels on cv_a (every pixel valid) to out, and after level 0 the store: xq, gq <- the current guides, with
+// steps 6 and 7: launch_denoise's level loop on cv_a (every pixel valid) to out, and after level 0 the store: xq, gq <- the current guides, with
 // feedback hist.rgb <- level 0's output; kmul (null: none): the result, and only the result, is multiplied by it
 void launch_temporal_filter(hipStream_t s, int w, int h, const DenoiseK& p, bool feedback, const f4* position, const f4* normal, const uint32_t* model, f4* cv_a,
                             f4* cv_b, f4* nv, const f4* kmul, f4* out, f4* hist, f4* xq, f4* gq);

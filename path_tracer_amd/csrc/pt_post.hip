@@ -14,6 +14,7 @@
 // casts, out-of-bounds textureLoad = 0 — the same definitions the oracle uses, so the two agree bit for bit.
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
 #include <utility>
 
 #include "pt_kernels.h"
@@ -270,26 +271,27 @@ __global__ void __launch_bounds__(256) k_post_deinterleave(uint32_t w, uint32_t 
 // states.  One thread per pixel in 16 x 16 workgroups; what a tap reads is three 16-byte loads (colour | variance, position | t,
 // normal | valid) and the model word.  Per-pixel divisors are hoisted out of the tap loops; one exp_det per tap.
 constexpr float kDenoiseEps = 1e-6f;
-__device__ __forceinline__ float dn_lum(f4 c) { return (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z; }
-// max(0, n_p . n_q)^(2^log2_sn) and the plane term a_x = |n_p . (x_q - x_p)| / (sigma_x * |x_q - x_p|) (0 where x_q == x_p) of two hits
-__device__ __forceinline__ float dn_normal_w(f4 np, f4 nq, uint32_t log2_sn)
-{
-    const float nd = (np.x * nq.x + np.y * nq.y) + np.z * nq.z;
-    float wn = nd > 0.0f ? nd : 0.0f;
-    for (uint32_t k = 0; k < log2_sn; ++k) wn = wn * wn;
-    return wn;
-}
-__device__ __forceinline__ float dn_plane(f4 np, f4 xp, f4 xq, float sigma_x)
-{
-    const float dx = xq.x - xp.x, dy = xq.y - xp.y, dz = xq.z - xp.z;
-    const float d2 = (dx * dx + dy * dy) + dz * dz;
-    return d2 > 0.0f ? fabsf((np.x * dx + np.y * dy) + np.z * dz) / (sigma_x * sqrtf(d2)) : 0.0f;
-}
 
-// colour = acc.rgb / acc.w, variance = the adaptive criterion's e2 (moments) or 0 (the spatial pass fills it in), valid = acc.w != 0
-__global__ void __launch_bounds__(256) k_dn_prep(uint32_t n, const f4* __restrict__ accum, const float* __restrict__ moments, const f4* __restrict__ normal,
-                                                 f4* __restrict__ cv, f4* __restrict__ nv)
+// the prep kernel's albedo: none (pt_denoise), the albedo image (pt_denoise_albedo's guide, a caller's image) or the mean-albedo sums S (A = S.rgb / S.w)
+enum class AlbedoFrom { None, Image, Sums };
+struct NoAlbedo {};
+struct AlbedoImages
 {
+    const uint32_t* model;
+    const f4* albedo;
+    f4* kd;
+};
+
+// colour = acc.rgb / acc.w, variance = the adaptive criterion's e2 (moments) or 0 (the spatial pass fills it in), valid = acc.w != 0.
+// With an albedo A (pt_denoise_albedo): k = pt_filter.h's divisor of A; colour c' = (acc / k) / acc.w; with moments the variance e2 of the
+// modulated colour scaled by r * r, r = l(c') / l(c) (1 where l(c) is not positive), which keeps the relative error.  k goes to kd for the
+// last level.
+template <AlbedoFrom SRC>
+__global__ void __launch_bounds__(256) k_dn_prep(uint32_t n, const f4* __restrict__ accum, const float* __restrict__ moments, const f4* __restrict__ normal,
+                                                 f4* __restrict__ cv, f4* __restrict__ nv,
+                                                 const std::conditional_t<SRC == AlbedoFrom::None, NoAlbedo, AlbedoImages> al)
+{
+    constexpr bool ALBEDO = SRC != AlbedoFrom::None;
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const f4 a = accum[i];
@@ -297,66 +299,44 @@ __global__ void __launch_bounds__(256) k_dn_prep(uint32_t n, const f4* __restric
     {
         cv[i] = f4{0.0f, 0.0f, 0.0f, 0.0f};
         nv[i] = f4{0.0f, 0.0f, 0.0f, 0.0f};
+        if constexpr (ALBEDO) al.kd[i] = f4{0.0f, 0.0f, 0.0f, 0.0f};
         return;
+    }
+    f4 c{a.x / a.w, a.y / a.w, a.z / a.w, 0.0f};
+    [[maybe_unused]] f4 k;
+    if constexpr (ALBEDO)
+    {
+        const uint32_t mp = al.model[i];
+        k = divisor(MISS_ID, f4{0.0f, 0.0f, 0.0f, 0.0f}); // a miss does not read the albedo
+        if (mp != MISS_ID)
+        {
+            f4 A = al.albedo[i];
+            if (SRC == AlbedoFrom::Sums) A = f4{A.x / A.w, A.y / A.w, A.z / A.w, 0.0f};
+            k = divisor(mp, A);
+        }
+        c = f4{(a.x / k.x) / a.w, (a.y / k.y) / a.w, (a.z / k.z) / a.w, 0.0f};
     }
     float var = 0.0f;
     if (moments)
     {
-        const float m = dn_lum(a) / a.w;
+        const float m = lum(a) / a.w;
         float v = moments[i] / a.w - m * m;
         if (!(v > 0.0f)) v = 0.0f;
         var = v / a.w;
+        if constexpr (ALBEDO)
+        {
+            const float lc = lum(f4{a.x / a.w, a.y / a.w, a.z / a.w, 0.0f});
+            const float r = lc > 0.0f ? lum(c) / lc : 1.0f;
+            var = (var * r) * r;
+        }
     }
     const f4 nr = normal[i];
-    cv[i] = f4{a.x / a.w, a.y / a.w, a.z / a.w, var};
+    cv[i] = f4{c.x, c.y, c.z, var};
     nv[i] = f4{nr.x, nr.y, nr.z, 1.0f};
+    if constexpr (ALBEDO) al.kd[i] = k;
 }
 
-// pt_denoise_albedo's prep: the same with the colour divided by the albedo first.  A = the albedo image (MEAN: the sums' S.rgb / S.w);
-// k = (1, 1, 1) for a miss, else A floored at 2^-10 per channel; colour c' = (acc / k) / acc.w; with moments the variance e2 of the modulated
-// colour scaled by r * r, r = l(c') / l(c) (1 where l(c) is not positive), which keeps the relative error.  k goes to kd for the last level.
-constexpr float kAlbedoFloor = 0x1p-10f;
-template <bool MEAN>
-__global__ void __launch_bounds__(256) k_dn_prep_albedo(uint32_t n, const f4* __restrict__ accum, const float* __restrict__ moments, const f4* __restrict__ normal,
-                                                        const uint32_t* __restrict__ model, const f4* __restrict__ albedo, f4* __restrict__ cv,
-                                                        f4* __restrict__ nv, f4* __restrict__ kd)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const f4 a = accum[i];
-    if (a.w == 0.0f)
-    {
-        cv[i] = f4{0.0f, 0.0f, 0.0f, 0.0f};
-        nv[i] = f4{0.0f, 0.0f, 0.0f, 0.0f};
-        kd[i] = f4{0.0f, 0.0f, 0.0f, 0.0f};
-        return;
-    }
-    f4 k{1.0f, 1.0f, 1.0f, 0.0f};
-    if (model[i] != MISS_ID)
-    {
-        f4 A = albedo[i];
-        if (MEAN) A = f4{A.x / A.w, A.y / A.w, A.z / A.w, 0.0f};
-        k = f4{A.x > kAlbedoFloor ? A.x : kAlbedoFloor, A.y > kAlbedoFloor ? A.y : kAlbedoFloor, A.z > kAlbedoFloor ? A.z : kAlbedoFloor, 0.0f};
-    }
-    const f4 cd{(a.x / k.x) / a.w, (a.y / k.y) / a.w, (a.z / k.z) / a.w, 0.0f};
-    float var = 0.0f;
-    if (moments)
-    {
-        const float m = dn_lum(a) / a.w;
-        float v = moments[i] / a.w - m * m;
-        if (!(v > 0.0f)) v = 0.0f;
-        const float e2 = v / a.w;
-        const float lc = dn_lum(f4{a.x / a.w, a.y / a.w, a.z / a.w, 0.0f});
-        const float r = lc > 0.0f ? dn_lum(cd) / lc : 1.0f;
-        var = (e2 * r) * r;
-    }
-    const f4 nr = normal[i];
-    cv[i] = f4{cd.x, cd.y, cd.z, var};
-    nv[i] = f4{nr.x, nr.y, nr.z, 1.0f};
-    kd[i] = k;
-}
-
-// variance of l over the 7 x 7 neighbourhood, taps weighted by the model, normal and plane terms (no luminance term)
+// variance of l over the 7 x 7 neighbourhood (pt_filter.h's walk, a neighbour valid where nv.w says so)
 __global__ void __launch_bounds__(256) k_dn_spatial_var(int w, int h, const DenoiseK p, const f4* __restrict__ cv_in, const f4* __restrict__ pos,
                                                         const f4* __restrict__ nv, const uint32_t* __restrict__ model, f4* __restrict__ cv_out)
 {
@@ -365,36 +345,7 @@ __global__ void __launch_bounds__(256) k_dn_spatial_var(int w, int h, const Deno
     const size_t i = (size_t)y * w + x;
     const f4 cp = cv_in[i], np = nv[i];
     if (np.w == 0.0f) { cv_out[i] = f4{0.0f, 0.0f, 0.0f, 0.0f}; return; }
-    const uint32_t mp = model[i];
-    const bool hit = mp != MISS_ID;
-    const f4 xp = pos[i];
-    float sw = 0.0f, sl = 0.0f, sll = 0.0f;
-    for (int dy = -3; dy <= 3; ++dy)
-    {
-        const int yy = y + dy;
-        if (yy < 0 || yy >= h) continue;
-        for (int dx = -3; dx <= 3; ++dx)
-        {
-            const int xx = x + dx;
-            if (xx < 0 || xx >= w) continue;
-            const size_t q = (size_t)yy * w + xx;
-            float wt = 1.0f;
-            if (dx != 0 || dy != 0)
-            {
-                const f4 nq = nv[q];
-                if (nq.w == 0.0f || model[q] != mp) continue;
-                if (hit) wt = dn_normal_w(np, nq, p.log2_sigma_n) * exp_det(-dn_plane(np, xp, pos[q], p.sigma_x));
-            }
-            const float l = dn_lum(cv_in[q]);
-            sw = sw + wt;
-            sl = sl + wt * l;
-            sll = sll + wt * (l * l);
-        }
-    }
-    const float mu = sl / sw;
-    float v = sll / sw - mu * mu;
-    if (!(v > 0.0f)) v = 0.0f;
-    cv_out[i] = f4{cp.x, cp.y, cp.z, v};
+    cv_out[i] = f4{cp.x, cp.y, cp.z, spatial_variance<true>(w, h, cv_in, pos, nv, model, p.log2_sigma_n, p.sigma_x, x, y, np)};
 }
 
 // one a-trous level, step s: g = 3 x 3 binomial blur of the variance, then the 5 x 5 B3-spline taps p + s (dx, dy) with edge-stopping weights.
@@ -432,7 +383,7 @@ __global__ void __launch_bounds__(256) k_dn_level(int w, int h, int s, const Den
     }
     const float g = sg / sk;
     const float inv = 1.0f / (p.sigma_l * sqrtf(g) + kDenoiseEps);
-    const float lp = dn_lum(cp);
+    const float lp = lum(cp);
     const float hk[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
     float sw = 0.0f, sr = 0.0f, sgc = 0.0f, sb = 0.0f, sv = 0.0f;
     for (int dy = -2; dy <= 2; ++dy)
@@ -450,8 +401,8 @@ __global__ void __launch_bounds__(256) k_dn_level(int w, int h, int s, const Den
             {
                 const f4 nq = nv[q];
                 if (nq.w == 0.0f || model[q] != mp) continue;
-                const float al = fabsf(lp - dn_lum(cq)) * inv;
-                if (hit) e = dn_normal_w(np, nq, p.log2_sigma_n) * exp_det(-(dn_plane(np, xp, pos[q], p.sigma_x) + al));
+                const float al = fabsf(lp - lum(cq)) * inv;
+                if (hit) e = normal_w(np, nq, p.log2_sigma_n) * exp_det(-(plane(np, xp, pos[q], p.sigma_x) + al));
                 else e = exp_det(-al);
             }
             const float wt = (hk[dx + 2] * hk[dy + 2]) * e;
@@ -470,35 +421,6 @@ __global__ void __launch_bounds__(256) k_dn_level(int w, int h, int s, const Den
         cv_out[i] = f4{c.x * k.x, c.y * k.y, c.z * k.z, 1.0f};
     }
     else cv_out[i] = FINAL ? f4{c.x, c.y, c.z, 1.0f} : f4{c.x, c.y, c.z, sv / (sw * sw)};
-}
-
-// the spatial variance where there are no moments, then the levels, on the prepared (colour | variance) in cv_a; kmul: the last level
-// multiplies its result by it (pt_denoise_albedo), null: it does not
-void denoise_levels(hipStream_t s, int w, int h, const DenoiseK& p, bool moments, const f4* position, const uint32_t* model, f4* cv_a, f4* cv_b, f4* nv,
-                    const f4* kmul, f4* out)
-{
-    const dim3 tile(16, 16), grid((w + 15) / 16, (h + 15) / 16);
-    f4* cur = cv_a;
-    f4* other = cv_b;
-    if (!moments)
-    {
-        hipLaunchKernelGGL(k_dn_spatial_var, grid, tile, 0, s, w, h, p, (const f4*)cv_a, position, (const f4*)nv, model, cv_b);
-        std::swap(cur, other);
-    }
-    for (uint32_t it = 0; it < p.iterations; ++it)
-    {
-        const int step = 1 << it;
-        if (it + 1u == p.iterations)
-        {
-            if (kmul) hipLaunchKernelGGL((k_dn_level<true, true>), grid, tile, 0, s, w, h, step, p, (const f4*)cur, position, (const f4*)nv, model, out, kmul);
-            else hipLaunchKernelGGL(k_dn_level<true>, grid, tile, 0, s, w, h, step, p, (const f4*)cur, position, (const f4*)nv, model, out, kmul);
-        }
-        else
-        {
-            hipLaunchKernelGGL(k_dn_level<false>, grid, tile, 0, s, w, h, step, p, (const f4*)cur, position, (const f4*)nv, model, other, (const f4*)nullptr);
-            std::swap(cur, other);
-        }
-    }
 }
 
 // ---- temporal stage (pt_frame_temporal / pt_post_temporal): the per-pixel steps are pt_temporal.h's, shared with the host path.  One thread
@@ -527,7 +449,7 @@ __global__ void __launch_bounds__(256) k_tp_reproject(const TemporalImages im, c
     TemporalOut o;
     if (DEMOD)
     {
-        const f4 kdiv = tp_divisor(im.model[i], albedo[i]);
+        const f4 kdiv = divisor(im.model[i], albedo[i]);
         kd[i] = kdiv;
         o = temporal_pixel<RESCUE, MEAN, true>(im, k, x, y, kdiv);
     }
@@ -584,12 +506,42 @@ __global__ void __launch_bounds__(256) k_tp_remodulate(uint32_t n, const f4* __r
     out[i] = f4{c.x * k.x, c.y * k.y, c.z * k.z, 1.0f};
 }
 
-template <bool RESCUE, bool MEAN>
-void tp_reproject(hipStream_t s, const TemporalImages& im, const TemporalK& k, f4* hist_out, f2* mom_out, const f4* albedo, f4* kd)
+// the temporal stage's step 7 between the levels: after level 0, k_tp_store of the current guides, with feedback also of level 0's output
+struct Level0Store
 {
-    const dim3 grid((im.w + 15) / 16, (im.h + 15) / 16), tile(16, 16);
-    if (albedo) hipLaunchKernelGGL((k_tp_reproject<RESCUE, MEAN, true>), grid, tile, 0, s, im, k, hist_out, mom_out, albedo, kd);
-    else hipLaunchKernelGGL((k_tp_reproject<RESCUE, MEAN, false>), grid, tile, 0, s, im, k, hist_out, mom_out, albedo, kd);
+    const f4* normal;
+    bool feedback;
+    f4 *hist, *xq, *gq;
+};
+
+// the spatial variance where there are no moments, then the levels, on the prepared (colour | variance) in cv_a; kmul: the result, and only
+// the result, is multiplied by it (pt_denoise_albedo, demodulate), null: it is not; store: null for the spatial filter
+void denoise_levels(hipStream_t s, int w, int h, const DenoiseK& p, bool moments, const f4* position, const uint32_t* model, f4* cv_a, f4* cv_b, f4* nv,
+                    const f4* kmul, f4* out, const Level0Store* store = nullptr)
+{
+    const dim3 tile(16, 16), grid((w + 15) / 16, (h + 15) / 16);
+    const uint32_t n = (uint32_t)w * (uint32_t)h;
+    f4* cur = cv_a;
+    f4* other = cv_b;
+    if (!moments)
+    {
+        hipLaunchKernelGGL(k_dn_spatial_var, grid, tile, 0, s, w, h, p, (const f4*)cv_a, position, (const f4*)nv, model, cv_b);
+        std::swap(cur, other);
+    }
+    // the history keeps level 0's output BEFORE the multiplication: where level 0 is also the last, the multiplication follows the store
+    const bool remod_after = kmul && store && store->feedback && p.iterations == 1u;
+    for (uint32_t it = 0; it < p.iterations; ++it)
+    {
+        const bool last = it + 1u == p.iterations, remod = last && kmul && !remod_after;
+        f4* dst = last ? out : other;
+        const auto level = !last ? k_dn_level<false> : remod ? k_dn_level<true, true> : k_dn_level<true>;
+        hipLaunchKernelGGL(level, grid, tile, 0, s, w, h, 1 << it, p, (const f4*)cur, position, (const f4*)nv, model, dst, remod ? kmul : (const f4*)nullptr);
+        if (it == 0u && store)
+            hipLaunchKernelGGL(k_tp_store, dim3((n + 255u) / 256u), dim3(256), 0, s, n, position, store->normal, model,
+                               store->feedback ? (const f4*)dst : (const f4*)nullptr, store->hist, store->xq, store->gq);
+        if (!last) std::swap(cur, other);
+    }
+    if (remod_after) hipLaunchKernelGGL(k_tp_remodulate, dim3((n + 255u) / 256u), dim3(256), 0, s, n, kmul, out);
 }
 } // namespace
 
@@ -600,10 +552,11 @@ void launch_temporal_motion_normal(hipStream_t s, uint32_t n, const f4* normal, 
 void launch_temporal_reproject(hipStream_t s, const TemporalImages& im, const TemporalK& k, bool rescue, bool mean_length, const f4* albedo, f4* kd, f4* hist_out,
                                f2* mom_out)
 {
-    if (rescue && mean_length) tp_reproject<true, true>(s, im, k, hist_out, mom_out, albedo, kd);
-    else if (rescue) tp_reproject<true, false>(s, im, k, hist_out, mom_out, albedo, kd);
-    else if (mean_length) tp_reproject<false, true>(s, im, k, hist_out, mom_out, albedo, kd);
-    else tp_reproject<false, false>(s, im, k, hist_out, mom_out, albedo, kd);
+    const dim3 grid((im.w + 15) / 16, (im.h + 15) / 16), tile(16, 16);
+    with_temporal_options(rescue, mean_length, [&](auto R, auto M) {
+        if (albedo) hipLaunchKernelGGL((k_tp_reproject<R.value, M.value, true>), grid, tile, 0, s, im, k, hist_out, mom_out, albedo, kd);
+        else hipLaunchKernelGGL((k_tp_reproject<R.value, M.value, false>), grid, tile, 0, s, im, k, hist_out, mom_out, albedo, kd);
+    });
 }
 void launch_temporal_variance(hipStream_t s, int w, int h, const DenoiseK& p, float alpha, const f4* cn, const f2* mom, const f4* position, const f4* normal,
                               const uint32_t* model, f4* cv, f4* nv, float* var)
@@ -613,43 +566,19 @@ void launch_temporal_variance(hipStream_t s, int w, int h, const DenoiseK& p, fl
 void launch_temporal_filter(hipStream_t s, int w, int h, const DenoiseK& p, bool feedback, const f4* position, const f4* normal, const uint32_t* model, f4* cv_a,
                             f4* cv_b, f4* nv, const f4* kmul, f4* out, f4* hist, f4* xq, f4* gq)
 {
-    const dim3 tile(16, 16), grid((w + 15) / 16, (h + 15) / 16);
-    const uint32_t n = (uint32_t)w * (uint32_t)h;
-    f4* cur = cv_a;
-    f4* other = cv_b;
-    // the history keeps level 0's output BEFORE the multiplication: where level 0 is also the last, the multiplication follows the store
-    const bool remod_after = kmul && feedback && p.iterations == 1u;
-    for (uint32_t it = 0; it < p.iterations; ++it)
-    {
-        const int step = 1 << it;
-        const bool last = it + 1u == p.iterations;
-        f4* dst = last ? out : other;
-        if (last && kmul && !remod_after)
-            hipLaunchKernelGGL((k_dn_level<true, true>), grid, tile, 0, s, w, h, step, p, (const f4*)cur, position, (const f4*)nv, model, dst, kmul);
-        else if (last) hipLaunchKernelGGL(k_dn_level<true>, grid, tile, 0, s, w, h, step, p, (const f4*)cur, position, (const f4*)nv, model, dst, (const f4*)nullptr);
-        else hipLaunchKernelGGL(k_dn_level<false>, grid, tile, 0, s, w, h, step, p, (const f4*)cur, position, (const f4*)nv, model, dst, (const f4*)nullptr);
-        if (it == 0u)
-            hipLaunchKernelGGL(k_tp_store, dim3((n + 255u) / 256u), dim3(256), 0, s, n, position, normal, model, feedback ? (const f4*)dst : (const f4*)nullptr, hist, xq, gq);
-        if (!last) std::swap(cur, other);
-    }
-    if (remod_after) hipLaunchKernelGGL(k_tp_remodulate, dim3((n + 255u) / 256u), dim3(256), 0, s, n, kmul, out);
+    const Level0Store store{normal, feedback, hist, xq, gq};
+    denoise_levels(s, w, h, p, true, position, model, cv_a, cv_b, nv, kmul, out, &store);
 }
 
-void launch_denoise(hipStream_t s, int w, int h, const DenoiseK& p, const f4* accum, const float* moments, const f4* position, const f4* normal,
-                    const uint32_t* model, f4* cv_a, f4* cv_b, f4* nv, f4* out)
+void launch_denoise(hipStream_t s, int w, int h, const DenoiseK& p, const DenoiseImages& im)
 {
     const uint32_t n = (uint32_t)w * (uint32_t)h;
-    hipLaunchKernelGGL(k_dn_prep, dim3((n + 255u) / 256u), dim3(256), 0, s, n, accum, moments, normal, cv_a, nv);
-    denoise_levels(s, w, h, p, moments != nullptr, position, model, cv_a, cv_b, nv, nullptr, out);
-}
-
-void launch_denoise_albedo(hipStream_t s, int w, int h, const DenoiseK& p, const f4* accum, const float* moments, const f4* position, const f4* normal,
-                           const uint32_t* model, const f4* albedo, bool albedo_is_sum, f4* cv_a, f4* cv_b, f4* nv, f4* kd, f4* out)
-{
-    const uint32_t n = (uint32_t)w * (uint32_t)h;
-    if (albedo_is_sum) hipLaunchKernelGGL(k_dn_prep_albedo<true>, dim3((n + 255u) / 256u), dim3(256), 0, s, n, accum, moments, normal, model, albedo, cv_a, nv, kd);
-    else hipLaunchKernelGGL(k_dn_prep_albedo<false>, dim3((n + 255u) / 256u), dim3(256), 0, s, n, accum, moments, normal, model, albedo, cv_a, nv, kd);
-    denoise_levels(s, w, h, p, moments != nullptr, position, model, cv_a, cv_b, nv, (const f4*)kd, out);
+    const dim3 grid((n + 255u) / 256u), block(256);
+    const AlbedoImages al{im.model, im.albedo, im.kd};
+    if (!im.albedo) hipLaunchKernelGGL(k_dn_prep<AlbedoFrom::None>, grid, block, 0, s, n, im.accum, im.moments, im.normal, im.cv_a, im.nv, NoAlbedo{});
+    else if (im.albedo_is_sum) hipLaunchKernelGGL(k_dn_prep<AlbedoFrom::Sums>, grid, block, 0, s, n, im.accum, im.moments, im.normal, im.cv_a, im.nv, al);
+    else hipLaunchKernelGGL(k_dn_prep<AlbedoFrom::Image>, grid, block, 0, s, n, im.accum, im.moments, im.normal, im.cv_a, im.nv, al);
+    denoise_levels(s, w, h, p, im.moments != nullptr, im.position, im.model, im.cv_a, im.cv_b, im.nv, im.albedo ? (const f4*)im.kd : nullptr, im.out);
 }
 
 void launch_post_deinterleave(hipStream_t s, uint32_t w, uint32_t h, uint32_t world, uint32_t strip, uint32_t pad_rows, const f4* parts, f4* full)

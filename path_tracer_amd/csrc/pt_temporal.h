@@ -8,10 +8,11 @@
 //
 // The options of pt_temporal_params are template parameters, so that the plain stage compiles to what it was: RESCUE (step 3b: a pixel whose
 // listed taps all failed searches the 3 x 3 around its reprojected position), MEAN (PT_TEMPORAL_LENGTH_MEAN: the history length is the taps'
-// weighted mean, not their least) and DEMOD (cur is divided by the pixel's divisor kdiv, see tp_divisor, where it is loaded).
+// weighted mean, not their least) and DEMOD (cur is divided by the pixel's divisor kdiv, pt_filter.h's, where it is loaded).
 #pragma once
-#include "pt_math.h"
-#include "pt_types.h"
+#include <type_traits>
+
+#include "pt_filter.h"
 
 namespace pt {
 
@@ -45,8 +46,6 @@ struct TemporalOut
     f2 m; // mu1, mu2
 };
 
-PT_HD float tp_lum(f4 c) { return (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z; }
-
 // n carried back by the linear parts of the instance's inverse and previous forward matrix (rows of the 3x4s), as X_PREV carries the point
 PT_HD f4 motion_normal(const float inv[12], const float prv[12], f4 n)
 {
@@ -56,13 +55,14 @@ PT_HD f4 motion_normal(const float inv[12], const float prv[12], f4 n)
     return f4{q[0], q[1], q[2], n.w};
 }
 
-// pt_denoise_albedo's divisor: (1, 1, 1) for a miss, else the albedo floored at 2^-10 per channel
-constexpr float kTemporalAlbedoFloor = 0x1p-10f;
-PT_HD f4 tp_divisor(uint32_t model, f4 A)
+// a tap's geometry test on a hit (ok: what it passed so far): its normal n' against the carried-back normal np, and its point X' within `bound` = plane_max * t of the
+// plane through the carried-back point xp
+PT_HD bool tap_geometry_ok(bool ok, f4 np, f4 xp, f4 ng, f4 xq, float normal_min, float bound)
 {
-    if (model == MISS_ID) return f4{1.0f, 1.0f, 1.0f, 0.0f};
-    return f4{A.x > kTemporalAlbedoFloor ? A.x : kTemporalAlbedoFloor, A.y > kTemporalAlbedoFloor ? A.y : kTemporalAlbedoFloor,
-              A.z > kTemporalAlbedoFloor ? A.z : kTemporalAlbedoFloor, 0.0f};
+    const float nd = (np.x * ng.x + np.y * ng.y) + np.z * ng.z;
+    const float dx = xq.x - xp.x, dy = xq.y - xp.y, dz = xq.z - xp.z;
+    const float pd = fabsf((np.x * dx + np.y * dy) + np.z * dz);
+    return ok && nd >= normal_min && pd <= bound;
 }
 
 // steps 1-4 for pixel (x, y): the taps, their tests, the fold (3b: the rescue walk) and the blend
@@ -123,13 +123,7 @@ PT_HD TemporalOut temporal_pixel(const TemporalImages& im, const TemporalK& k, i
         const float bound = k.plane_max * im.pos[i].w;
         f4 xq[4];
         for (int t = 0; t < 4; ++t) xq[t] = ok[t] ? im.xq[q[t]] : f4{0.0f, 0.0f, 0.0f, 0.0f};
-        for (int t = 0; t < 4; ++t)
-        {
-            const float nd = (np.x * gq[t].x + np.y * gq[t].y) + np.z * gq[t].z;
-            const float dx = xq[t].x - xp.x, dy = xq[t].y - xp.y, dz = xq[t].z - xp.z;
-            const float pd = fabsf((np.x * dx + np.y * dy) + np.z * dz);
-            ok[t] = ok[t] && nd >= k.normal_min && pd <= bound;
-        }
+        for (int t = 0; t < 4; ++t) ok[t] = tap_geometry_ok(ok[t], np, xp, gq[t], xq[t], k.normal_min, bound);
     }
     f2 mq[4];
     for (int t = 0; t < 4; ++t) mq[t] = ok[t] ? im.mom[q[t]] : f2{0.0f, 0.0f};
@@ -173,13 +167,7 @@ PT_HD TemporalOut temporal_pixel(const TemporalImages& im, const TemporalK& k, i
                 {
                     f4 rx4[3];
                     for (int t = 0; t < 3; ++t) rx4[t] = rok[t] ? im.xq[rq[t]] : f4{0.0f, 0.0f, 0.0f, 0.0f};
-                    for (int t = 0; t < 3; ++t)
-                    {
-                        const float nd = (np.x * rg[t].x + np.y * rg[t].y) + np.z * rg[t].z;
-                        const float ex = rx4[t].x - xp.x, ey = rx4[t].y - xp.y, ez = rx4[t].z - xp.z;
-                        const float pd = fabsf((np.x * ex + np.y * ey) + np.z * ez);
-                        rok[t] = rok[t] && nd >= k.normal_min && pd <= bound;
-                    }
+                    for (int t = 0; t < 3; ++t) rok[t] = tap_geometry_ok(rok[t], np, xp, rg[t], rx4[t], k.normal_min, bound);
                 }
                 f2 rm[3];
                 for (int t = 0; t < 3; ++t) rm[t] = rok[t] ? im.mom[rq[t]] : f2{0.0f, 0.0f};
@@ -200,7 +188,7 @@ PT_HD TemporalOut temporal_pixel(const TemporalImages& im, const TemporalK& k, i
     }
     f4 cur = im.cur[i];
     if (DEMOD) cur = f4{cur.x / kdiv.x, cur.y / kdiv.y, cur.z / kdiv.z, cur.w};
-    const float l = tp_lum(cur);
+    const float l = lum(cur);
     TemporalOut o;
     if (sw > 0.0f)
     {
@@ -220,19 +208,12 @@ PT_HD TemporalOut temporal_pixel(const TemporalImages& im, const TemporalK& k, i
     return o;
 }
 
-// geometry terms of two hits, in pt_denoise's order
-PT_HD float tp_normal_w(f4 np, f4 nq, uint32_t log2_sn)
+// the instantiation of the options: f(std::bool_constant<RESCUE>, std::bool_constant<MEAN>) for the runtime (rescue, mean_length)
+template <class Fn>
+auto with_temporal_options(bool rescue, bool mean_length, Fn&& f)
 {
-    const float nd = (np.x * nq.x + np.y * nq.y) + np.z * nq.z;
-    float wn = nd > 0.0f ? nd : 0.0f;
-    for (uint32_t k = 0; k < log2_sn; ++k) wn = wn * wn;
-    return wn;
-}
-PT_HD float tp_plane(f4 np, f4 xp, f4 xq, float sigma_x)
-{
-    const float dx = xq.x - xp.x, dy = xq.y - xp.y, dz = xq.z - xp.z;
-    const float d2 = (dx * dx + dy * dy) + dz * dz;
-    return d2 > 0.0f ? fabsf((np.x * dx + np.y * dy) + np.z * dz) / (sigma_x * sqrtf(d2)) : 0.0f;
+    if (rescue) return mean_length ? f(std::true_type{}, std::true_type{}) : f(std::true_type{}, std::false_type{});
+    return mean_length ? f(std::false_type{}, std::true_type{}) : f(std::false_type{}, std::false_type{});
 }
 
 // step 5 for pixel (x, y): the variance handed to the levels.  cn = this call's C | N, mom its moments.  From kTemporalMomentsN on the
@@ -250,35 +231,7 @@ PT_HD float temporal_variance(int w, int h, const f4* cn, const f2* mom, const f
         const float rn = 1.0f / cp.w;
         return v * (alpha > rn ? alpha : rn);
     }
-    const uint32_t mp = model[i];
-    const bool hit = mp != MISS_ID;
-    const f4 np = nrm[i], xp = pos[i];
-    float sw = 0.0f, sl = 0.0f, sll = 0.0f;
-    for (int dy = -3; dy <= 3; ++dy)
-    {
-        const int yy = y + dy;
-        if (yy < 0 || yy >= h) continue;
-        for (int dx = -3; dx <= 3; ++dx)
-        {
-            const int xx = x + dx;
-            if (xx < 0 || xx >= w) continue;
-            const size_t q = (size_t)yy * w + xx;
-            float wt = 1.0f;
-            if (dx != 0 || dy != 0)
-            {
-                if (model[q] != mp) continue;
-                if (hit) wt = tp_normal_w(np, nrm[q], log2_sn) * exp_det(-tp_plane(np, xp, pos[q], sigma_x));
-            }
-            const float l = tp_lum(cn[q]);
-            sw = sw + wt;
-            sl = sl + wt * l;
-            sll = sll + wt * (l * l);
-        }
-    }
-    const float mu = sl / sw;
-    float v = sll / sw - mu * mu;
-    if (!(v > 0.0f)) v = 0.0f;
-    return v;
+    return spatial_variance<false>(w, h, cn, pos, nrm, model, log2_sn, sigma_x, x, y, nrm[i]);
 }
 
 } // namespace pt

@@ -3,8 +3,7 @@ numpy float32 from include/pt_api.h, operation for operation, on top of the exis
 the random cases the two suites use.  Nothing here calls the library."""
 import numpy as np
 
-from denoise_albedo_common import levels, spatial_variance
-from test_denoise_host import MISS, F, _shift, lum, params  # noqa: F401  (_shift: the levels' and the variance's neighbourhoods)
+from denoise_common import MISS, F, _shift, levels, lum, params, spatial_variance  # noqa: F401  (_shift: the levels' and the variance's neighbourhoods)
 
 MAXN = F(65535)
 MOMENTS_N = F(4)

@@ -3,10 +3,9 @@ rescue, length_rule and demodulate) restated in numpy float32 from include/pt_ap
 variance and levels; and the cases the two suites use.  Nothing here calls the library."""
 import numpy as np
 
-from denoise_albedo_common import levels
+import denoise_common
+from denoise_common import levels
 from temporal_common import MAXN, MISS, F, _dot, lum, params, random_case, taps, tparams, variance
-
-ALBEDO_FLOOR = F(2.0 ** -10)
 
 
 def _fold(acc, tap_list, gate, prev, cur, xp, npv, nmin_, pmax):
@@ -110,10 +109,7 @@ def post_temporal(prev, cur, xprev=None, nprev=None, velocity=None, alpha=0.0, a
 
 def divisor(model, albedo):
     """pt_denoise_albedo's k: (1, 1, 1) for a miss, else the albedo floored at 2^-10 per channel"""
-    A = np.asarray(albedo, F)[..., :3]
-    k = np.where(A > ALBEDO_FLOOR, A, ALBEDO_FLOOR).astype(F)
-    k[np.asarray(model, np.uint32) == MISS] = F(1)
-    return k
+    return denoise_common.divisor(np.asarray(albedo, F)[..., :3], model)
 
 
 def frame_temporal(prev, cur, xprev=None, nprev=None, velocity=None, feedback=0, alpha=0.0, alpha_moments=0.0, normal_min=0.0, plane_max=0.0,

@@ -7,8 +7,9 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from denoise_albedo_common import FLOOR, checker_image, denoise_albedo, prepare, random_albedo, rmse
-from test_denoise_host import MISS, F, denoise, random_case
+from denoise_albedo_common import checker_image, denoise_albedo, random_albedo, rmse
+from denoise_common import FLOOR, MISS, F, prepare
+from test_denoise_host import denoise, random_case
 
 
 def _u32(a):

@@ -2,7 +2,8 @@
 A kernel template that gained trailing parameters renames its old instantiations (k<a, b> becomes k<a, b, false>; a kernel that became a
 template, k becomes k<false>; one that gained a trailing parameter PACK keeps k<a, b> with the empty pack, under another symbol): such a
 kernel is compared with the one it was and marked `+param`.  r20_name holds the one renaming that is no such growth: the surface pass's
-eleven positional parameters became six named axes and the camera kernels one template over the camera kind.
+eleven positional parameters became six named axes and the camera kernels one template over the camera kind.  r22_name: the denoiser's two
+prep kernels became one template over the albedo source.
 usage: python tools/asm_diff.py old.s new.s"""
 import re, subprocess, sys
 
@@ -51,9 +52,14 @@ def r20_name(d):
         return f'{k}<{", ".join([view] + t[:3])}>'
     return d
 
+def r22_name(d):
+    """the merged prep kernel's name for k_dn_prep and k_dn_prep_albedo<MEAN> (AlbedoFrom: None 0, Image 1, Sums 2), or d itself"""
+    src = {'k_dn_prep': 0, 'k_dn_prep_albedo<false>': 1, 'k_dn_prep_albedo<true>': 2}
+    return f'k_dn_prep<(pt::(anonymous namespace)::AlbedoFrom){src[d]}>' if d in src else d
+
 a, b = funcs(sys.argv[1]), funcs(sys.argv[2])
 print(len(a), 'kernels before,', len(b), 'after')
-old_names = {r20_name(dem(n)): n for n in a if n not in b}
+old_names = {r22_name(r20_name(dem(n))): n for n in a if n not in b}
 renamed = set()
 for n in b:
     o = n if n in a else was(n, old_names)
