@@ -30,6 +30,9 @@
 //       ceiling and back wall (cb_main.obj, model 1) under --checker's planar UVs, in which floor and ceiling overlap and the lower triangle index
 //       wins (rays start 0.25 off the surface, stream keys = texel indices), dilates it PASSES times and writes one line per texel:
 //       its coverage byte (1 baked, 2 dilated, 0 neither) and the three raw sums as hexadecimal floats (%a)
+//   examples/headless ... --bake-lightmap ... --baked-view SPP out.png   sets the dilated map it just baked, sum / its SPP, on the shell
+//       (pt_set_lightmap) and writes the baked view (pt_render_baked: SPP samples per pixel, chains followed --follow K hops, unmapped
+//       surfaces black)
 //   examples/headless ... --checker N   an N x N checker (texels 1 and 0.2, bilinear, repeating) on the floor, ceiling and back wall (cb_main.obj) with
 //                                        planar UVs: a vertex's (x, z) over the model's own extent in x and z
 //   examples/headless ... --emission-checker N   the same N x N checker as the EMISSION texture of the light (cb_light.obj) under the same planar UVs:
@@ -68,6 +71,8 @@ int main(int argc, char** argv)
     std::string probes_out = "";
     uint32_t lightmap[4] = {0, 0, 0, 0}; // W H SPP PASSES
     std::string lightmap_out = "";
+    uint32_t baked_spp = 0;
+    std::string baked_out = "";
     pt_projection projection{}; // PT_PROJ_PERSPECTIVE
     for (int i = 1; i < argc; ++i)
     {
@@ -121,6 +126,11 @@ int main(int argc, char** argv)
             for (uint32_t& n : lightmap) n = (uint32_t)std::atoi(next("--bake-lightmap"));
             lightmap_out = next("--bake-lightmap");
         }
+        else if (a == "--baked-view")
+        {
+            baked_spp = (uint32_t)std::atoi(next("--baked-view"));
+            baked_out = next("--baked-view");
+        }
         else if (a == "--load-state") load_state = next("--load-state");
         else if (a == "--save-state") save_state = next("--save-state");
         else if (a == "--devices")
@@ -130,10 +140,15 @@ int main(int argc, char** argv)
         }
         else if (a == "--help" || a == "-h")
         {
-            std::printf("usage: %s [--width W] [--height H] [--frames N] [--bounces B] [--move] [--slide DX DZ] [--models DIR] [--out file.png] [--temporal file.png [--temporal-rescue] [--temporal-mean-length] [--temporal-demodulate]] [--denoise file.png] [--denoise-albedo file.png] [--follow K] [--mirror-glass] [--aperture A --focus F] [--projection panorama[:SX:SY]|ortho:HEIGHT] [--bake-probes NX NY NZ SPP file.txt] [--bake-lightmap W H SPP PASSES file.txt] [--checker N] [--emission-checker N] [--normal-ripples N]\n", argv[0]);
+            std::printf("usage: %s [--width W] [--height H] [--frames N] [--bounces B] [--move] [--slide DX DZ] [--models DIR] [--out file.png] [--temporal file.png [--temporal-rescue] [--temporal-mean-length] [--temporal-demodulate]] [--denoise file.png] [--denoise-albedo file.png] [--follow K] [--mirror-glass] [--aperture A --focus F] [--projection panorama[:SX:SY]|ortho:HEIGHT] [--bake-probes NX NY NZ SPP file.txt] [--bake-lightmap W H SPP PASSES file.txt [--baked-view SPP file.png]] [--checker N] [--emission-checker N] [--normal-ripples N]\n", argv[0]);
             return 0;
         }
         else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
+    }
+    if (!baked_out.empty() && (lightmap_out.empty() || !lightmap[2] || !baked_spp))
+    {
+        std::fprintf(stderr, "--baked-view shows the map --bake-lightmap bakes: it needs that option, and samples for both\n");
+        return 2;
     }
     if (normal_ripples && (checker || !lightmap_out.empty()))
     {
@@ -283,6 +298,12 @@ int main(int argc, char** argv)
             if (!f) { std::fprintf(stderr, "cannot write %s\n", lightmap_out.c_str()); return false; }
             for (size_t k = 0; k < cov.size(); ++k) std::fprintf(f, "%u %a %a %a\n", (unsigned)cov[k], (double)sums[3 * k], (double)sums[3 * k + 1], (double)sums[3 * k + 2]);
             std::fclose(f);
+            if (baked_out.empty()) return true;
+            // ... and its consumer: the map's texel means on the shell, the followed first hits shaded from it
+            for (float& s : sums) s = s / (float)lightmap[2];
+            renderer.set_lightmap(1, 0, lightmap[0], lightmap[1], sums);
+            renderer.render_baked(0, baked_spp, follow);
+            renderer.write_baked_image(baked_out);
             return true;
         };
         // the demodulated denoiser on samples [first, first + count) of the frame: guides of the last sample, the mean albedo of all of them

@@ -884,7 +884,7 @@ int pt_probe_ray(pt_ctx* ctx, uint32_t key, uint32_t sample, float d[3], float y
  * reserved word, key_base + w * h or first_sample + n_samples beyond 2^32; PT_ERR_LIMIT for a side above 16384 or more than 2^26 texels.
  * A map with no covered texel is PT_OK and integrates nothing.
  * Out of scope: unwrapping and atlas packing, conservative or supersampled coverage, direct light sampled at the texel, directional maps,
- * denoising, feeding a baked map back into a render, pt_multi_* variants. */
+ * denoising, pt_multi_* variants.  (Showing a map: pt_set_lightmap and pt_render_baked, below.) */
 typedef struct pt_lightmap_params
 {
     int32_t model;                    /* model index */
@@ -911,6 +911,71 @@ int pt_lightmap_ray(pt_ctx* ctx, uint32_t key, uint32_t sample, const float norm
  * floats: sums or finished irradiance alike) and coverage (w * h bytes) are IN/OUT host pointers.  PT_ERR_ARG for a NULL pointer or a side of
  * 0, PT_ERR_LIMIT as pt_bake_lightmap, both before any device call; passes == 0 does nothing. */
 int pt_lightmap_dilate(pt_ctx* ctx, uint32_t w, uint32_t h, uint32_t passes, float* rgb, uint8_t* coverage);
+
+/* ---- lightmaps kept by the context, and the baked view: followed first hits shaded from them ------------------------------------------- */
+/* pt_set_lightmap gives the context the finished map of ONE placement, (model, instance) as pt_bake_lightmap keys it: rgb is w * h * 3 floats,
+ * texel (i, j) at index j * w + i.  A texel is the MEAN of the bake's radiance samples of that texel, rgb_sum / n_samples after dilation: with
+ * cosine-distributed directions that mean is the Lambertian surface's outgoing radiance per unit albedo, so no pi appears anywhere.  Dividing
+ * by n is the caller's.  rgb NULL with w == h == 0 clears the map; pt_get_lightmap_info reports 0 x 0 where there is none.
+ * The call neither un-builds the scene nor touches the flattened scene: pt_scene_info does not move, a pt_render launches what it launched
+ * before, and a scene with lightmaps is not a textured scene.  The maps live on the device in tables of their own (16-byte texels; offset, w, h
+ * and the way to its model's UVs per world-TLAS leaf, 0 x 0 for a leaf without a map; the leaf-order UVs of the models that carry a map unless
+ * the texture tables hold them already), uploaded by the next baked call.
+ * Errors, all before any device call (a refused call changes nothing): PT_ERR_ARG for a bad model or instance index, w or h of 0 with rgb, a
+ * non-zero w or h without, a texel that is negative or not finite; PT_ERR_STATE for a model without UVs; PT_ERR_LIMIT for a side above 16384 or
+ * more than 2^28 texels in all maps together.  Where several apply, the first in this order is reported: the indices and the sizes against
+ * the pointer (ARG), the limits, the model's UVs (STATE: pt_bake_lightmap's order), then the texels (ARG), which are read last.
+ * Lifetime: pt_set_instances keeps the maps of the ordinals that still exist and drops the others (a moved instance keeps its now stale
+ * lighting: the caller's business); pt_set_model_uvs on a model drops that model's maps; pt_build keeps them. */
+int pt_set_lightmap(pt_ctx* ctx, int model, uint32_t instance, uint32_t w, uint32_t h, const float* rgb);
+int pt_get_lightmap_info(pt_ctx* ctx, int model, uint32_t instance, uint32_t* w, uint32_t* h);
+/* THE LOOKUP of a hit at barycentrics (u, v) of a triangle with UVs a, b, c (load-order vertices 0, 1, 2) in a w x h map.  Binary32, one
+ * rounding per operation, no contraction, in this order:
+ *     s = (a.s + u * (b.s - a.s)) + v * (c.s - a.s);  t likewise          -- the surface colour's s, t, WITHOUT repeat addressing
+ *     x = (float)w * s - 0.5f;  y = (float)h * t - 0.5f                   -- texel (i, j) has its centre at ((i + .5) / w, (j + .5) / h): the bake's p
+ *     x = !(x > 0) ? 0 : (x > (float)(w - 1) ? (float)(w - 1) : x);  y alike with h          -- clamp to edge; a NaN gives 0
+ *     x0 = (uint32_t)x;  xf = x - truncf(x);  x1 = x0 + 1 < w ? x0 + 1 : x0;                 y0, yf, y1 alike
+ *     c00 = texel(x0, y0); c01 = texel(x0, y1); c10 = texel(x1, y0); c11 = texel(x1, y1)
+ *     I = ((((1-xf)*(1-yf)) * c00 + ((1-xf)*yf) * c01) + (xf*(1-yf)) * c10) + (xf*yf) * c11       -- the textures' blend
+ *   At s = (i + 0.5) / w, t = (j + 0.5) / h of a map whose sides are powers of two I is texel (i, j) bit for bit, and a triangle whose three
+ *   UVs are equal has that UV everywhere.
+ * pt_lightmap_lookup is its unit hook: n queries {world-TLAS leaf, load-order primitive, u, v} (host pointers); mapped[k] = 0 and rgb[k] =
+ * (0, 0, 0) where the leaf's (model, ordinal) has no map.  on_device = 0 evaluates on the host and touches no GPU, 1 runs a kernel over the
+ * same function.  PT_ERR_STATE without a built scene, PT_ERR_ARG for a bad leaf or primitive. */
+int pt_lightmap_lookup(pt_ctx* ctx, int on_device, uint32_t n, const uint32_t* instance, const uint32_t* prim, const float* u, const float* v,
+                       float* rgb, uint8_t* mapped);
+/* THE BAKED VIEW.  For every local pixel and every sample s of [first_sample, first_sample + n_samples), ascending, the chain is exactly the
+ * chain pt_render_guides_followed(s, max_hops) defines, on any rank and without the primary-cull rectangle: the same camera ray under every
+ * camera kind, the same hops, the same c_i (surface colour, or an emissive hit's emitted colour), the same running product
+ * R_h = ((c_0 * c_1) * ...) * c_h, media ignored.  The baked sample B of a chain that ends at hop H:
+ *     on a PT_EMISSIVE surface, either face                                         B = R_H
+ *     on any other kind, the leaf mapped and the hit a front face (the flag of the
+ *       unperturbed normal)                                                         B = R_H * I, per component (I: the lookup above)
+ *     on any other kind, with no map or on a back face                              B = R_H * unlit    (the bake lit the front side only)
+ *     as a miss: E = env_lookup of the last ray's direction under an environment
+ *       map, else (0.006, 0.006, 0.006)                                             B = E at H = 0, with no arithmetic; else R_{H-1} * E
+ *     S.r += B.r;  S.g += B.g;  S.b += B.b;  S.w += 1       -- one binary32 add each, into a per-pixel baked sum the context owns
+ * There is no finite check and no clamp: every input was checked at its setter.  Calls continue the sums ((0, a) then (a, b) is (0, a + b)
+ * bit for bit); rgbn (may be NULL; local_rows * width entries of 4 floats) receives them, as pt_read_baked does.  Adding onto stale or reset
+ * sums starts from zero; they go stale on what makes the guides stale, on pt_set_lightmap, and on a call whose max_hops or unlit bits differ
+ * from those of the call that made them.  pt_write_baked_image writes pt_write_image's transform of S.rgb / S.w (one rank).
+ * The call never touches the accumulation, the position, the id history, the moments or the guides (they stay valid; the hook queues, the hits
+ * and the chain state are shared as scratch), and a context that never calls these functions allocates and launches nothing for them.
+ * Errors, all before any device call: PT_ERR_ARG for what pt_guide_params refuses, an unlit that is negative or not finite, n_samples == 0 or
+ * a range beyond 2^32; PT_ERR_STATE as pt_render_guides; pt_read_baked and pt_write_baked_image PT_ERR_STATE without current sums.  A scene
+ * with no map at all is legal.
+ * Out of scope: pt_multi_* variants, coverage-aware filtering (the caller dilates), directional maps, probes as the fallback of unmapped
+ * surfaces, a specular response on GGX surfaces, perturbed normals, ending the path tracer's own paths in the maps, denoising the view. */
+typedef struct pt_baked_params
+{
+    uint32_t max_hops;    /* 0..8, as pt_guide_params */
+    float unlit[3];       /* the factor of a final surface that has no usable map; finite, >= 0; all zeros: black */
+    uint32_t reserved[4]; /* must be 0 */
+} pt_baked_params;
+int pt_render_baked(pt_ctx* ctx, uint32_t first_sample, uint32_t n_samples, const pt_baked_params* params, float* rgbn);
+int pt_read_baked(pt_ctx* ctx, float* rgbn);
+int pt_reset_baked(pt_ctx* ctx);
+int pt_write_baked_image(pt_ctx* ctx, const char* path);
 
 /* ---- unit hooks: TLAS::intersect / any_intersect  src/tlas.rs:66, 111 ------------------------------------------ */
 /* which: 0 world TLAS, 1 lights TLAS.  Host SoA in, host SoA out.  miss => inst = prim = 0xffffffff, t = +inf.

@@ -428,6 +428,44 @@ public:
         if (rgb.size() != px * 3 || coverage.size() != px) throw Error(PT_ERR_ARG, "dilate_lightmap: rgb holds 3 values and coverage one byte per texel");
         check(pt_lightmap_dilate(ctx_, w, h, passes, rgb.data(), coverage.data()));
     }
+    // the finished map of one placement (pt_set_lightmap): rgb holds w * h * 3 texel means (sum / n_samples after dilation); empty with
+    // w == h == 0 clears it.  lightmap_info: {w, h}, 0 x 0 where there is none
+    void set_lightmap(int model, uint32_t instance, uint32_t w, uint32_t h, const std::vector<float>& rgb)
+    {
+        if (rgb.size() != (size_t)w * h * 3) throw Error(PT_ERR_ARG, "set_lightmap: rgb does not hold 3 values per texel");
+        check(pt_set_lightmap(ctx_, model, instance, w, h, rgb.empty() ? nullptr : rgb.data()));
+    }
+    std::array<uint32_t, 2> lightmap_info(int model, uint32_t instance) const
+    {
+        std::array<uint32_t, 2> wh{};
+        check(pt_get_lightmap_info(ctx_, model, instance, &wh[0], &wh[1]));
+        return wh;
+    }
+    // the lightmap at n hits {world-TLAS leaf, load-order primitive, u, v} (pt_lightmap_lookup): rgb (n * 3) and the mapped bytes
+    std::vector<float> lightmap_lookup(const std::vector<uint32_t>& instance, const std::vector<uint32_t>& prim, const std::vector<float>& u,
+                                       const std::vector<float>& v, std::vector<uint8_t>& mapped, bool on_device = false) const
+    {
+        const size_t n = instance.size();
+        if (prim.size() != n || u.size() != n || v.size() != n) throw Error(PT_ERR_ARG, "lightmap_lookup: the four arrays differ in length");
+        std::vector<float> rgb(n * 3);
+        mapped.assign(n, 0);
+        check(pt_lightmap_lookup(ctx_, on_device ? 1 : 0, (uint32_t)n, instance.data(), prim.data(), u.data(), v.data(), rgb.data(), mapped.data()));
+        return rgb;
+    }
+    // the baked view (pt_render_baked): adds samples [first_sample, first_sample + n_samples) of every pixel's followed first hit, shaded
+    // from the lightmaps, to the baked sums and returns them (sum r, sum g, sum b, n per pixel)
+    std::vector<float> render_baked(uint32_t first_sample, uint32_t n_samples, uint32_t max_hops = 0, std::array<float, 3> unlit = {0.0f, 0.0f, 0.0f})
+    {
+        pt_baked_params p{};
+        p.max_hops = max_hops;
+        p.unlit[0] = unlit[0]; p.unlit[1] = unlit[1]; p.unlit[2] = unlit[2];
+        std::vector<float> v((size_t)width_ * height_ * 4);
+        check(pt_render_baked(ctx_, first_sample, n_samples, &p, v.data()));
+        return v;
+    }
+    std::vector<float> read_baked() const { std::vector<float> v((size_t)width_ * height_ * 4); check(pt_read_baked(ctx_, v.data())); return v; }
+    void reset_baked() { check(pt_reset_baked(ctx_)); }
+    void write_baked_image(const std::string& path) const { check(pt_write_baked_image(ctx_, path.c_str())); }
     // the world TLAS's root box: min xyz, max xyz
     std::array<float, 6> root_box() const { uint32_t rect[4]; std::array<float, 6> b{}; check(pt_active_pixels(ctx_, rect, b.data())); return b; }
     pt_stats stats() const { pt_stats s{}; check(pt_get_stats(ctx_, &s)); return s; }

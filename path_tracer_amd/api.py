@@ -48,6 +48,7 @@ EXPORTS = [
     "pt_bake_lightmap", "pt_lightmap_texels", "pt_lightmap_ray", "pt_lightmap_dilate",
     "pt_render_guides_followed", "pt_read_guide_hops", "pt_accumulate_albedo_followed", "pt_guide_follow_dir",
     "pt_frame_temporal", "pt_read_temporal", "pt_reset_temporal", "pt_post_temporal", "pt_frame_temporal_options", "pt_post_temporal_options",
+    "pt_set_lightmap", "pt_get_lightmap_info", "pt_lightmap_lookup", "pt_render_baked", "pt_read_baked", "pt_reset_baked", "pt_write_baked_image",
 ]
 
 
@@ -117,6 +118,11 @@ TEMPORAL_LENGTH_MIN, TEMPORAL_LENGTH_MEAN = 0, 1
 class GuideParams(C.Structure):
     """pt_guide_params: how many mirror / glass surfaces the guide chains follow per pixel (include/pt_api.h)"""
     _fields_ = [("max_hops", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class BakedParams(C.Structure):
+    """pt_baked_params: the hops the baked view's chains follow and the factor of a final surface without a usable map (include/pt_api.h)"""
+    _fields_ = [("max_hops", C.c_uint32), ("unlit", C.c_float * 3), ("reserved", C.c_uint32 * 4)]
 
 
 class RaysParams(C.Structure):
@@ -284,6 +290,13 @@ def lib():
         L.pt_lightmap_texels.argtypes = [vp, C.c_int, u32, u32, u32, C.c_int, vp, vp, vp, vp]
         L.pt_lightmap_ray.argtypes = [vp, u32, u32, vp, vp]
         L.pt_lightmap_dilate.argtypes = [vp, u32, u32, u32, vp, vp]
+        L.pt_set_lightmap.argtypes = [vp, C.c_int, u32, u32, u32, vp]
+        L.pt_get_lightmap_info.argtypes = [vp, C.c_int, u32, vp, vp]
+        L.pt_lightmap_lookup.argtypes = [vp, C.c_int, u32, vp, vp, vp, vp, vp, vp]
+        L.pt_render_baked.argtypes = [vp, u32, u32, C.POINTER(BakedParams), vp]
+        L.pt_read_baked.argtypes = [vp, vp]
+        L.pt_reset_baked.argtypes = [vp]
+        L.pt_write_baked_image.argtypes = [vp, C.c_char_p]
         L.pt_render_guides_followed.argtypes = [vp, u32, C.POINTER(GuideParams)]
         L.pt_read_guide_hops.argtypes = [vp, vp]
         L.pt_accumulate_albedo_followed.argtypes = [vp, u32, u32, C.POINTER(GuideParams)]
@@ -1014,6 +1027,61 @@ class Renderer:
             raise PtError(-1, "dilate_lightmap: rgb is (h, w, 3) and coverage (h, w)")
         self._chk(self.L.pt_lightmap_dilate(self.ctx, a.shape[1], a.shape[0], passes, _p(a), _p(cv)))
         return a, cv
+
+    # ---- lightmaps kept by the context, and the baked view
+    def set_lightmap(self, model, instance, rgb):
+        """the finished map of placement (model, instance) (pt_set_lightmap): rgb (h, w, 3), every texel the MEAN of the bake's radiance
+        samples (sums / n_samples after dilation); None clears the map"""
+        if rgb is None:
+            self._chk(self.L.pt_set_lightmap(self.ctx, model, instance, 0, 0, None))
+            return
+        a = np.ascontiguousarray(rgb, np.float32)
+        if a.ndim != 3 or a.shape[2] != 3:
+            raise PtError(-1, "set_lightmap: rgb is (h, w, 3)")
+        self._chk(self.L.pt_set_lightmap(self.ctx, model, instance, a.shape[1], a.shape[0], _p(a)))
+
+    def set_lightmap_sums(self, model, instance, sums, n_samples):
+        """set_lightmap of a bake's raw sums (bake_lightmap, dilate_lightmap) over n_samples samples: the division is done here"""
+        if not n_samples > 0:
+            raise PtError(-1, "set_lightmap_sums: n_samples must be positive")
+        self.set_lightmap(model, instance, np.asarray(sums, np.float32) / np.float32(n_samples))
+
+    def lightmap_info(self, model, instance):
+        """(w, h) of the map of placement (model, instance); (0, 0): none"""
+        w = C.c_uint32(); h = C.c_uint32()
+        self._chk(self.L.pt_get_lightmap_info(self.ctx, model, instance, C.byref(w), C.byref(h)))
+        return w.value, h.value
+
+    def lightmap_lookup(self, instance, prim, u, v, on_device=False):
+        """unit hook: (rgb [n, 3], mapped [n] uint8) of the lightmap at hits (world-TLAS instance, load-order primitive, barycentrics) of the
+        built scene, zeros where the leaf has no map; on the host (no GPU) unless on_device"""
+        i = np.ascontiguousarray(instance, dtype=np.uint32); p = np.ascontiguousarray(prim, dtype=np.uint32)
+        uu = np.ascontiguousarray(u, dtype=np.float32); vv = np.ascontiguousarray(v, dtype=np.float32)
+        assert i.shape == p.shape == uu.shape == vv.shape and i.ndim == 1
+        out = np.zeros((i.shape[0], 3), np.float32); mapped = np.zeros(i.shape[0], np.uint8)
+        self._chk(self.L.pt_lightmap_lookup(self.ctx, int(bool(on_device)), i.shape[0], _p(i), _p(p), _p(uu), _p(vv), _p(out), _p(mapped)))
+        return out, mapped
+
+    def render_baked(self, first_sample: int, n_samples: int, follow: int = 0, unlit=(0.0, 0.0, 0.0), download=True):
+        """the baked view (pt_render_baked): adds samples [first_sample, first_sample + n_samples) of every local pixel to the baked sums:
+        the chain of render_guides(.., follow=K), its final surface's colour times the lightmap at the hit (`unlit` where the surface has no
+        usable map).  Returns the sums (sum r, sum g, sum b, n), local rows x width x 4"""
+        prm = BakedParams(follow, (C.c_float * 3)(*[float(x) for x in unlit]))
+        out = np.zeros((len(self.local_rows()), self.cfg.width, 4), np.float32) if download else None
+        self._chk(self.L.pt_render_baked(self.ctx, first_sample, n_samples, C.byref(prm), _p(out) if download else None))
+        return out
+
+    def read_baked(self):
+        """the baked sums (sum r, sum g, sum b, n), local rows x width x 4"""
+        out = np.zeros((len(self.local_rows()), self.cfg.width, 4), np.float32)
+        self._chk(self.L.pt_read_baked(self.ctx, _p(out)))
+        return out
+
+    def reset_baked(self):
+        self._chk(self.L.pt_reset_baked(self.ctx))
+
+    def write_baked_image(self, path):
+        self._chk(self.L.pt_write_baked_image(self.ctx, str(path).encode()))
 
     # ---- unit hooks
     def trace_closest(self, o, d, tmax=None, which=0):

@@ -16,6 +16,9 @@
 //   host_sanitize normals <n> <seed>   normal maps' host side: n random triangles with random UVs (degenerate, huge and mirrored ones among them) under a
 //                                      normal texture, Scene::new, then shading_normal (pt_materials.h) at random hits over the flattened tables;
 //                                      prints how many triangles got a tangent and a checksum of the normals
+//   host_sanitize lightmaps <n> <seed> lightmaps' host side: n random triangles with random UVs (far outside [0, 1], huge, mirrored and overflowing ones
+//                                      among them) under three placements, random maps of several sizes on two of them, then lightmap_lookup
+//                                      (pt_materials.h) at random hits; prints how many lookups met a map and a checksum of the results
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -230,6 +233,71 @@ int main(int argc, char** argv)
         // clearing takes the tangents out again
         if (sc.set_material_normal_texture(mat, -1) != 0 || sc.build(&err) != 0 || !sc.flat.tri_tan.empty() || sc.flat.has_textures) return 7;
         std::printf("{\"triangles\": %u, \"with_tangent\": %u, \"checksum\": %.6f}\n", n, with_tangent, acc);
+        return 0;
+    }
+    if (cmd == "lightmaps" && argc >= 4)
+    {
+        const uint32_t n = (uint32_t)std::atoi(argv[2]);
+        uint64_t s = 0x9E3779B97F4A7C15ull ^ (uint64_t)std::atoll(argv[3]);
+        auto rnd = [&]() { s ^= s << 13; s ^= s >> 7; s ^= s << 17; return (float)((s >> 40) & 0xffff) / 65535.0f; };
+        HostScene sc;
+        const int mat = light_scene(sc);
+        if (mat < 0 || n == 0) return 3;
+        std::vector<float> p, nr, uv;
+        for (uint32_t t = 0; t < n; ++t)
+        {
+            const float c[3] = {200.0f * rnd() - 100.0f, 200.0f * rnd() - 100.0f, 200.0f * rnd() - 100.0f};
+            for (int v = 0; v < 3; ++v)
+                for (int k = 0; k < 3; ++k) { p.push_back(c[k] + 10.0f * rnd() - 5.0f); nr.push_back(k == 1 ? 1.0f : 0.2f * rnd() - 0.1f); }
+            const uint32_t shape = t % 6u; // inside, far outside, all equal, around 1e6, mirrored, the largest finite values (their differences overflow)
+            const float a[2] = {rnd(), rnd()};
+            for (int v = 0; v < 3; ++v)
+                for (int k = 0; k < 2; ++k)
+                    uv.push_back(shape == 0u ? rnd() : shape == 1u ? 40.0f * rnd() - 20.0f : shape == 2u ? a[k] : shape == 3u ? 1.0e6f + 3.0f * rnd()
+                                 : shape == 4u ? (v ? -1.0f : 1.0f) * (a[k] + rnd()) : (rnd() < 0.5f ? -3.0e38f : 3.0e38f));
+        }
+        // three placements of the soup; a map of its own on the first two, sizes from one texel to a few hundred
+        const float turn[12] = {0, 0, 1, 30, 0, 1, 0, -20, -1, 0, 0, 10};
+        std::vector<float> mats(kIdentity, kIdentity + 12);
+        mats.insert(mats.end(), turn, turn + 12);
+        mats.insert(mats.end(), kIdentity, kIdentity + 12);
+        mats[2 * 12 + 3] = 500.0f;
+        const int model = sc.add_model(p.data(), nr.data(), n, mat, mats.data(), 3);
+        if (model < 0 || sc.set_model_uvs(model, uv.data(), n) != 0) return 4;
+        std::string err;
+        if (sc.build(&err) != 0) { std::printf("{\"error\": \"%s\"}\n", err.c_str()); return 0; }
+        if (sc.flat.has_textures || !sc.flat.tri_uv.empty()) return 5; // a scene with lightmaps is no textured scene
+        struct Map { uint32_t w, h; std::vector<f4> texels; };
+        std::vector<Map> maps(2);
+        const uint32_t sizes[4][2] = {{1, 1}, {5, 3}, {16, 16}, {2, 37}};
+        for (Map& m : maps)
+        {
+            const uint32_t* wh = sizes[(uint32_t)(rnd() * 3.999f) % 4u];
+            m.w = wh[0];
+            m.h = wh[1];
+            for (uint32_t k = 0; k < m.w * m.h; ++k) m.texels.push_back(f4{rnd(), rnd(), rnd(), 0.0f});
+        }
+        double acc = 0.0;
+        uint32_t mapped = 0;
+        for (uint32_t q = 0; q < 8u * n; ++q)
+        {
+            const uint32_t inst = (uint32_t)(rnd() * 3.999f) % (uint32_t)sc.world.instances.size();
+            const uint32_t mi = sc.world.instances[inst].model;
+            if ((int)mi != model) continue;                                      // the light: no UVs, no map
+            uint32_t ordinal = 0;
+            for (uint32_t k = 0; k < inst; ++k) ordinal += sc.world.instances[k].model == mi ? 1u : 0u;
+            if (ordinal >= maps.size()) continue;                                // the third placement: no map
+            const uint32_t prim = (uint32_t)(rnd() * (float)n) % n;
+            const float u = rnd(), v = rnd() * (1.0f - u);
+            const float* t = &sc.models[mi].uvs[(size_t)prim * 6];
+            const Map& m = maps[ordinal];
+            const f3 c = lightmap_lookup(m.texels.data(), m.w, m.h, DTriUV{{t[0], t[1]}, {t[2], t[3]}, {t[4], t[5]}}, u, v);
+            const float top = 1.0001f;                                           // a blend of texels in [0, 1]: the weights sum to 1 within rounding
+            if (!(c.x >= 0.0f && c.x <= top && c.y >= 0.0f && c.y <= top && c.z >= 0.0f && c.z <= top)) return 6;
+            acc += c.x + 2.0 * c.y + 3.0 * c.z;
+            ++mapped;
+        }
+        std::printf("{\"triangles\": %u, \"lookups\": %u, \"checksum\": %.6f}\n", n, mapped, acc);
         return 0;
     }
     if (cmd == "plan")

@@ -191,6 +191,23 @@ struct pt_ctx
     DevBuf d_gray2_a, d_gray2_b, d_ghead2, d_gstate, d_ghops;
     uint32_t guides_max_hops = 0, albedo_max_hops = 0;
 
+    // lightmaps (pt_set_lightmap): lightmaps[model][ordinal], w == 0: none (rows may be shorter than the model's matrices); lightmap_version
+    // counts their changes.  On the device in tables of their own (LmView), uploaded by the next baked call when the maps or the resident
+    // scene changed since (lm_version, lm_upload: uploads_full + uploads_patched then).
+    struct Lightmap { uint32_t w = 0, h = 0; std::vector<f4> texels; };
+    std::vector<std::vector<Lightmap>> lightmaps;
+    uint64_t lightmap_texels = 0, lightmap_version = 0;
+    DevBuf d_lm_texels, d_lm_leaf, d_lm_uv;
+    LmView lm{};
+    bool lm_valid = false;
+    uint64_t lm_version = 0, lm_upload = 0;
+    // the baked view (pt_render_baked): sum r, g, b | n per local pixel, traced through the guides' hook queues, and what the sums belong
+    // to: what keeps the guides current, the lightmaps, max_hops and the bits of unlit.  Nothing is allocated until the first call.
+    DevBuf d_baked_sum;
+    bool baked_valid = false;
+    uint64_t baked_scene_version = 0, baked_config_version = 0, baked_lm_version = 0;
+    uint32_t baked_max_hops = 0, baked_unlit[3] = {0, 0, 0};
+
     // pt_frame_moving: the forward instance matrices, per model, of the build in force when the previous call returned PT_OK (the snapshot)
     // and the build it was taken from (a call on that very build has nothing to compare); the motion table and x_prev on the device.
     std::vector<std::vector<xf34>> snap;
@@ -1490,6 +1507,84 @@ int lightmap_check(pt_ctx* c, int model, uint32_t instance, uint32_t w, uint32_t
     return PT_OK;
 }
 
+// ---- lightmaps kept by the context (pt_set_lightmap; the lookup is pt_materials.h's)
+// the map of (model, ordinal), null where there is none
+const pt_ctx::Lightmap* lightmap_of(const pt_ctx* c, uint32_t model, uint32_t ordinal)
+{
+    if (model >= c->lightmaps.size() || ordinal >= c->lightmaps[model].size() || !c->lightmaps[model][ordinal].w) return nullptr;
+    return &c->lightmaps[model][ordinal];
+}
+// drops the maps of `model` from ordinal `keep` on (pt_set_instances, pt_set_model_uvs)
+void drop_lightmaps(pt_ctx* c, int model, size_t keep)
+{
+    if ((size_t)model >= c->lightmaps.size() || c->lightmaps[model].size() <= keep) return;
+    bool any = false;
+    for (size_t j = keep; j < c->lightmaps[model].size(); ++j)
+    {
+        const pt_ctx::Lightmap& l = c->lightmaps[model][j];
+        c->lightmap_texels -= (uint64_t)l.w * l.h;
+        any = any || l.w;
+    }
+    c->lightmaps[model].resize(keep);
+    if (any) c->lightmap_version++;
+}
+// the ordinal of every world-TLAS leaf among the instances of its model: leaf i is (world.instances[i].model, ordinal[i])
+std::vector<uint32_t> leaf_ordinals(const HostScene& sc)
+{
+    std::vector<uint32_t> next(sc.models.size(), 0u), ordinal(sc.world.instances.size());
+    for (size_t i = 0; i < ordinal.size(); ++i) ordinal[i] = next[sc.world.instances[i].model]++;
+    return ordinal;
+}
+// The lightmap tables of the resident scene (after upload_scene), uploaded when the maps or the resident scene changed since: a record per
+// world-TLAS leaf, the texels of the maps in use one after the other, and the leaf-order UVs of the models that carry a map, unless the
+// scene is textured: then TexView's table holds every model's UVs already.
+int ensure_lightmaps(pt_ctx* c)
+{
+    const uint64_t upload = c->uploads_full + c->uploads_patched;
+    if (c->lm_valid && c->lm_version == c->lightmap_version && c->lm_upload == upload) return PT_OK;
+    c->lm_valid = false;
+    const HostScene& sc = c->scene;
+    const FlatScene& f = sc.flat;
+    const std::vector<uint32_t> ordinal = leaf_ordinals(sc);
+    std::vector<DLightmap> leaf(std::max<size_t>(ordinal.size(), 1), DLightmap{0u, 0u, 0u, 0u});
+    std::vector<f4> texels;
+    std::vector<DTriUV> uvs;
+    std::vector<uint32_t> uv_add(sc.models.size(), 0u); // what takes a model's triangles into uvs (mod 2^32: any value, 0 included)
+    std::vector<bool> placed(sc.models.size(), false);  // ... and whether the model's UVs are there yet
+    for (size_t i = 0; i < ordinal.size(); ++i)
+    {
+        const uint32_t mi = sc.world.instances[i].model;
+        const pt_ctx::Lightmap* l = lightmap_of(c, mi, ordinal[i]);
+        if (!l || sc.models[mi].uvs.empty()) continue;
+        if (!c->tex.tri_uv && !placed[mi])
+        {
+            const HostBlas& bl = sc.blas[mi];
+            uv_add[mi] = (uint32_t)uvs.size() - f.tri_base[mi];
+            placed[mi] = true;
+            for (const uint32_t id : bl.prim_ids)
+            {
+                const float* p = &sc.models[mi].uvs[(size_t)id * 6];
+                uvs.push_back(DTriUV{{p[0], p[1]}, {p[2], p[3]}, {p[4], p[5]}});
+            }
+        }
+        leaf[i] = DLightmap{(uint32_t)texels.size(), l->w, l->h, uv_add[mi]};
+        texels.insert(texels.end(), l->texels.begin(), l->texels.end());
+    }
+    int r;
+    if ((r = dev_alloc(c, c->d_lm_leaf, leaf.size() * sizeof(DLightmap))) || (r = dev_alloc(c, c->d_lm_texels, texels.size() * sizeof(f4))) ||
+        (r = dev_alloc(c, c->d_lm_uv, uvs.size() * sizeof(DTriUV))))
+        return r;
+    HIPCHK(c, hipStreamSynchronize(c->stream)); // an earlier baked call may still be reading the tables
+    HIPCHK(c, hipMemcpy(c->d_lm_leaf.p, leaf.data(), leaf.size() * sizeof(DLightmap), hipMemcpyHostToDevice));
+    if (!texels.empty()) HIPCHK(c, hipMemcpy(c->d_lm_texels.p, texels.data(), texels.size() * sizeof(f4), hipMemcpyHostToDevice));
+    if (!uvs.empty()) HIPCHK(c, hipMemcpy(c->d_lm_uv.p, uvs.data(), uvs.size() * sizeof(DTriUV), hipMemcpyHostToDevice));
+    c->lm = LmView{(const f4*)c->d_lm_texels.p, (const DLightmap*)c->d_lm_leaf.p, c->tex.tri_uv ? c->tex.tri_uv : (const DTriUV*)c->d_lm_uv.p};
+    c->lm_valid = true;
+    c->lm_version = c->lightmap_version;
+    c->lm_upload = upload;
+    return PT_OK;
+}
+
 // owner[k] = the lowest triangle index whose UVs contain the centre of texel k, MISS_ID where none does: the walk k_lm_cover does, triangle by
 // triangle over its texel rectangle, with a running minimum in the atomic's place
 void lightmap_owner_host(const HostModel& m, uint32_t w, uint32_t h, std::vector<uint32_t>& owner)
@@ -1767,6 +1862,7 @@ int pt_set_instances(pt_ctx* c, int model, const float* affines, uint32_t n_inst
     catch (const std::exception& e) { return fail(c, PT_ERR_LIMIT, std::string("instance matrices do not fit in host memory: ") + e.what()); }
     if (r == -4) return fail(c, PT_ERR_NONRIGID, "Model matrix can only contain translation and rotation");
     if (r < 0) return fail(c, PT_ERR_ARG, "bad model index or matrices");
+    drop_lightmaps(c, model, n_inst); // the maps of ordinals that still exist stay (pt_set_lightmap)
     c->scene_uploaded = false;
     return PT_OK;
 }
@@ -1832,6 +1928,7 @@ int pt_set_model_uvs(pt_ctx* c, int model, const float* uv, uint32_t n_tris)
     try { r = c->scene.set_model_uvs(model, uv, n_tris); }
     catch (const std::exception& e) { return fail(c, PT_ERR_LIMIT, std::string("UVs do not fit in host memory: ") + e.what()); }
     if (r < 0) return fail(c, PT_ERR_ARG, "bad model index, a triangle count that is not the model's, or a UV that is not finite");
+    drop_lightmaps(c, model, 0); // they were baked over the old layout (pt_set_lightmap)
     c->scene_uploaded = false;
     return PT_OK;
 }
@@ -2885,7 +2982,9 @@ int follow_params(pt_ctx* c, const pt_guide_params* gp, const char* who)
 // chains into the guides (sum null) or into the mean-albedo sums and queues the others' next rays into the other hook queue.  That
 // queue's count stays on the device, in the head word the next trace reads; a hop nobody reached is two empty launches.  No chain goes
 // on from the last hop, so that launch gets no next queue (max_hops 0, the first-hit guides, never has one).
-int follow_chains(pt_ctx* c, uint32_t sample, uint32_t max_hops, f4* sum)
+// (ending(q, h): the launch that ends or continues the chains of hop h; q holds the hop's queues, hits, count words and state)
+template <class Ending>
+int walk_chains(pt_ctx* c, uint32_t sample, uint32_t max_hops, Ending&& ending)
 {
     int r;
     c->hook_log.clear();
@@ -2899,7 +2998,7 @@ int follow_chains(pt_ctx* c, uint32_t sample, uint32_t max_hops, f4* sum)
     {
         const uint32_t cur = h & 1u, nxt = cur ^ 1u;
         if (h) launch_trace_rays_closest(c->stream, trace_launch(c), c->sv.world_root, q[cur], c->local_pixels, head[cur], (f4*)c->d_ghits.p);
-        FollowArgs a{};
+        ChainHop a{};
         a.in = q[cur];
         a.hits = (const f4*)c->d_ghits.p;
         a.n_in = head[cur];
@@ -2910,6 +3009,15 @@ int follow_chains(pt_ctx* c, uint32_t sample, uint32_t max_hops, f4* sum)
             a.n_next = head[nxt];
         }
         a.state = max_hops ? (f4*)c->d_gstate.p : nullptr;
+        ending(a, h);
+    }
+    return PT_OK;
+}
+int follow_chains(pt_ctx* c, uint32_t sample, uint32_t max_hops, f4* sum)
+{
+    return walk_chains(c, sample, max_hops, [&](const ChainHop& q, uint32_t h) {
+        FollowArgs a{};
+        static_cast<ChainHop&>(a) = q;
         a.position = (f4*)c->d_gpos.p;
         a.normal = (f4*)c->d_gnrm.p;
         a.albedo = (f4*)c->d_galbedo.p;
@@ -2921,8 +3029,24 @@ int follow_chains(pt_ctx* c, uint32_t sample, uint32_t max_hops, f4* sum)
         a.hop = h;
         a.max_hops = max_hops;
         launch_guide_follow(c->stream, c->sv, c->tex, a);
-    }
-    return PT_OK;
+    });
+}
+// ... and the baked view's chains (pt_render_baked): the same walk, ended by launch_baked_follow into the baked sums
+int baked_chains(pt_ctx* c, uint32_t sample, const pt_baked_params& p)
+{
+    EnvView env{};
+    if (c->env_w) env = EnvView{(const f4*)c->d_env.p, c->env_w, c->env_h, 0u, 0u};
+    return walk_chains(c, sample, p.max_hops, [&](const ChainHop& q, uint32_t h) {
+        BakedArgs b{};
+        static_cast<ChainHop&>(b) = q;
+        b.sum = (f4*)c->d_baked_sum.p;
+        b.env = env;
+        std::memcpy(b.unlit, p.unlit, sizeof(b.unlit));
+        b.cap = c->local_pixels;
+        b.hop = h;
+        b.max_hops = p.max_hops;
+        launch_baked_follow(c->stream, c->sv, c->tex, c->lm, b);
+    });
 }
 
 // The guides of `sample` of every local pixel: the chains of at most max_hops hops, 0 being the first hits (pt_render_guides,
@@ -3430,6 +3554,183 @@ int pt_lightmap_dilate(pt_ctx* c, uint32_t w, uint32_t h, uint32_t passes, float
     HIPCHK(c, hipGetLastError());
     if ((r = st.download(rgb, d_rgb[passes & 1u], px * 12))) return r;
     return st.download(coverage, d_cov[passes & 1u], px);
+}
+
+// ---- lightmaps kept by the context and the baked view (the definitions are include/pt_api.h's)
+int pt_set_lightmap(pt_ctx* c, int model, uint32_t instance, uint32_t w, uint32_t h, const float* rgb)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (model < 0 || model >= (int)c->scene.models.size()) return fail(c, PT_ERR_ARG, "pt_set_lightmap: model index");
+    const HostModel& m = c->scene.models[model];
+    if (instance >= m.matrices.size()) return fail(c, PT_ERR_ARG, "pt_set_lightmap: instance index");
+    const bool clear = !rgb && w == 0 && h == 0;
+    if (!clear && (!rgb || w == 0 || h == 0)) return fail(c, PT_ERR_ARG, "pt_set_lightmap: rgb with a non-zero w and h sets a map, NULL with w == h == 0 clears it");
+    const pt_ctx::Lightmap* old = lightmap_of(c, (uint32_t)model, instance);
+    const uint64_t old_texels = old ? (uint64_t)old->w * old->h : 0;
+    if (clear)
+    {
+        if (!old) return PT_OK;
+        c->lightmaps[model][instance] = pt_ctx::Lightmap{};
+        c->lightmap_texels -= old_texels;
+        c->lightmap_version++;
+        return PT_OK;
+    }
+    if (w > 16384u || h > 16384u || c->lightmap_texels - old_texels + (uint64_t)w * h > (1ull << 28))
+        return fail(c, PT_ERR_LIMIT, "pt_set_lightmap: a side is at most 16384 texels and all maps together hold at most 2^28");
+    if (m.uvs.empty()) return fail(c, PT_ERR_STATE, "pt_set_lightmap: the model has no UVs (pt_set_model_uvs)");
+    const size_t n = (size_t)w * h;
+    for (size_t i = 0; i < 3 * n; ++i)
+        if (!(rgb[i] >= 0.0f) || !std::isfinite(rgb[i])) return fail(c, PT_ERR_ARG, "pt_set_lightmap: a texel that is negative or not finite");
+    pt_ctx::Lightmap l;
+    try
+    {
+        l.texels.resize(n);
+        if (c->lightmaps.size() <= (size_t)model) c->lightmaps.resize((size_t)model + 1);
+        if (c->lightmaps[model].size() <= instance) c->lightmaps[model].resize((size_t)instance + 1);
+    }
+    catch (const std::exception& e) { return fail(c, PT_ERR_LIMIT, std::string("lightmap does not fit in host memory: ") + e.what()); }
+    for (size_t i = 0; i < n; ++i) l.texels[i] = f4{rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2], 0.0f};
+    l.w = w;
+    l.h = h;
+    c->lightmaps[model][instance] = std::move(l);
+    c->lightmap_texels = c->lightmap_texels - old_texels + n;
+    c->lightmap_version++;
+    return PT_OK;
+}
+
+int pt_get_lightmap_info(pt_ctx* c, int model, uint32_t instance, uint32_t* w, uint32_t* h)
+{
+    if (!c || !w || !h) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (model < 0 || model >= (int)c->scene.models.size()) return fail(c, PT_ERR_ARG, "pt_get_lightmap_info: model index");
+    if (instance >= c->scene.models[model].matrices.size()) return fail(c, PT_ERR_ARG, "pt_get_lightmap_info: instance index");
+    const pt_ctx::Lightmap* l = lightmap_of(c, (uint32_t)model, instance);
+    *w = l ? l->w : 0u;
+    *h = l ? l->h : 0u;
+    return PT_OK;
+}
+
+int pt_lightmap_lookup(pt_ctx* c, int on_device, uint32_t n, const uint32_t* instance, const uint32_t* prim, const float* u, const float* v, float* rgb,
+                       uint8_t* mapped)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->scene.built) return fail(c, PT_ERR_STATE, "pt_build has not been called");
+    if (n == 0) return PT_OK;
+    if (!instance || !prim || !u || !v || !rgb || !mapped) return fail(c, PT_ERR_ARG, "null pointer");
+    std::vector<uint32_t> tri;
+    int r;
+    if ((r = leaf_order_tris(c, n, instance, prim, tri))) return r;
+    if (!on_device)
+    {
+        const std::vector<uint32_t> ordinal = leaf_ordinals(c->scene);
+        for (uint32_t i = 0; i < n; ++i)
+        {
+            const uint32_t mi = c->scene.world.instances[instance[i]].model;
+            const pt_ctx::Lightmap* l = lightmap_of(c, mi, ordinal[instance[i]]);
+            f3 col{0.0f, 0.0f, 0.0f};
+            if (l)
+            {
+                const float* p = &c->scene.models[mi].uvs[(size_t)prim[i] * 6];
+                col = lightmap_lookup(l->texels.data(), l->w, l->h, DTriUV{{p[0], p[1]}, {p[2], p[3]}, {p[4], p[5]}}, u[i], v[i]);
+            }
+            rgb[3 * (size_t)i] = col.x; rgb[3 * (size_t)i + 1] = col.y; rgb[3 * (size_t)i + 2] = col.z;
+            mapped[i] = l ? 1u : 0u;
+        }
+        return PT_OK;
+    }
+    if ((r = upload_scene(c)) || (r = ensure_lightmaps(c))) return r;
+    Staging st(c);
+    const SurfaceQueries q = upload_queries(st, n, instance, tri, u, v);
+    float* d_rgb = (float*)st.out((size_t)n * 12);
+    uint8_t* d_mapped = (uint8_t*)st.out(n);
+    if (st.err) return st.err;
+    launch_lightmap_lookup(c->stream, c->lm, n, q.instance, q.tri, q.u, q.v, d_rgb, d_mapped);
+    HIPCHK(c, hipGetLastError());
+    if ((r = st.download(rgb, d_rgb, (size_t)n * 12))) return r;
+    return st.download(mapped, d_mapped, n);
+}
+
+// the baked sums exist and belong to what is in force: what keeps the guides current, and the lightmaps
+static bool baked_current(const pt_ctx* c)
+{
+    return c->baked_valid && c->baked_scene_version == c->scene_version && c->baked_config_version == c->config_version &&
+           c->baked_lm_version == c->lightmap_version;
+}
+
+int pt_render_baked(pt_ctx* c, uint32_t first_sample, uint32_t n_samples, const pt_baked_params* p, float* rgbn)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!p) return fail(c, PT_ERR_ARG, "pt_render_baked: params must not be NULL");
+    if (p->max_hops > 8u) return fail(c, PT_ERR_ARG, "pt_render_baked: max_hops is at most 8");
+    if (p->reserved[0] || p->reserved[1] || p->reserved[2] || p->reserved[3]) return fail(c, PT_ERR_ARG, "pt_render_baked: the reserved words must be 0");
+    for (int k = 0; k < 3; ++k)
+        if (!(p->unlit[k] >= 0.0f) || !std::isfinite(p->unlit[k])) return fail(c, PT_ERR_ARG, "pt_render_baked: unlit must be finite and not negative");
+    if (n_samples == 0u) return fail(c, PT_ERR_ARG, "pt_render_baked: n_samples must be at least 1");
+    if ((uint64_t)first_sample + n_samples > 0x100000000ull) return fail(c, PT_ERR_ARG, "pt_render_baked: first_sample + n_samples exceeds 2^32");
+    if (!c->scene.built) return fail(c, PT_ERR_STATE, "pt_build has not been called");
+    if (!c->scene.camera.set) return fail(c, PT_ERR_STATE, "pt_set_camera has not been called");
+    int r;
+    if ((r = upload_scene(c)) || (r = ensure_environment(c)) || (r = ensure_lightmaps(c))) return r;
+    const uint32_t px = c->local_pixels;
+    const size_t n = std::max<uint32_t>(px, 1);
+    if ((r = guide_scratch(c, p->max_hops)) || (r = dev_alloc(c, c->d_baked_sum, n * 16))) return r;
+    uint32_t unlit[3];
+    std::memcpy(unlit, p->unlit, sizeof(unlit));
+    const bool fresh = !baked_current(c) || c->baked_max_hops != p->max_hops || std::memcmp(unlit, c->baked_unlit, sizeof(unlit)) != 0;
+    c->baked_valid = false; // a failure below leaves no sum
+    if (fresh) HIPCHK(c, hipMemsetAsync(c->d_baked_sum.p, 0, n * 16, c->stream));
+    if (px)
+    {
+        for (uint32_t k = 0; k < n_samples; ++k)
+            if ((r = baked_chains(c, first_sample + k, *p))) return r;
+        HIPCHK(c, hipGetLastError());
+        if (rgbn) HIPCHK(c, hipMemcpyAsync(rgbn, c->d_baked_sum.p, (size_t)px * 16, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->baked_valid = true;
+    c->baked_scene_version = c->scene_version;
+    c->baked_config_version = c->config_version;
+    c->baked_lm_version = c->lightmap_version;
+    c->baked_max_hops = p->max_hops;
+    std::memcpy(c->baked_unlit, unlit, sizeof(unlit));
+    return PT_OK;
+}
+
+int pt_read_baked(pt_ctx* c, float* rgbn)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!baked_current(c)) return fail(c, PT_ERR_STATE, "no baked view (none rendered, reset, or stale): pt_render_baked first");
+    const size_t px = c->local_pixels;
+    if (!px || !rgbn) return PT_OK;
+    HIPCHK(c, hipMemcpyAsync(rgbn, c->d_baked_sum.p, px * 16, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PT_OK;
+}
+
+int pt_reset_baked(pt_ctx* c)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    c->baked_valid = false;
+    return PT_OK;
+}
+
+int pt_write_baked_image(pt_ctx* c, const char* path)
+{
+    if (!c || !path) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (c->cfg.world_size != 1) return fail(c, PT_ERR_STATE, "pt_write_baked_image needs the whole frame on one rank");
+    if (!baked_current(c)) return fail(c, PT_ERR_STATE, "no baked view (none rendered, reset, or stale): pt_render_baked first");
+    std::vector<uint8_t> host;
+    int r = present_rgb8_locked(c, host, (const f4*)c->d_baked_sum.p);
+    if (r) return r;
+    std::string err;
+    if (!write_png_rgb8(path, host.data(), c->cfg.width, c->cfg.height, &err)) return fail(c, PT_ERR_IO, err.c_str());
+    return PT_OK;
 }
 
 // ---- unit hooks

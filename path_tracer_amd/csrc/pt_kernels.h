@@ -278,17 +278,21 @@ void launch_shading_normal(hipStream_t s, const SceneView& sv, const TexNView& t
                            const float* v, const float* dir, float* out4);
 
 // unit hooks
-// pt_render_guides[_followed] / pt_accumulate_albedo[_followed]: hop `hop` of the guide chains (first-hit guides: max_hops 0).  `in`: the hook queue
-// launch_trace_rays_closest just traced into hits (n_in: its count word); chains that go on are appended to `next` (n_next: its count word, zero
-// before the launch; both queues hold cap slots; all null at the last hop, where no chain goes on).  sum null: a chain that ends writes the six
-// guides of its pixel; else it adds its albedo product to sum[pixel]
-struct FollowArgs
+// One hop of the guide chains, what every ending is handed (pt_api.cpp, walk_chains).  `in`: the hook queue launch_trace_rays_closest just traced
+// into hits (n_in: its count word); chains that go on are appended to `next` (n_next: its count word, zero before the launch; both queues hold cap
+// slots; both null at the last hop, where no chain goes on)
+struct ChainHop
 {
     RayQueue in, next;
     const f4* hits;
     const uint32_t* n_in;
     uint32_t* n_next;
-    f4* state;             // per pixel: running albedo product | t sum of a chain that goes on (may be null at max_hops 0)
+    f4* state;             // per pixel: running colour product | t sum of a chain that goes on (may be null at max_hops 0)
+};
+// pt_render_guides[_followed] / pt_accumulate_albedo[_followed]: hop `hop` of the guide chains (first-hit guides: max_hops 0).  sum null: a chain
+// that ends writes the six guides of its pixel; else it adds its albedo product to sum[pixel]
+struct FollowArgs : ChainHop
+{
     f4 *position, *normal, *albedo;
     uint32_t *model, *instance;
     uint8_t* hops;
@@ -296,6 +300,19 @@ struct FollowArgs
     uint32_t cap, hop, max_hops;
 };
 void launch_guide_follow(hipStream_t s, const SceneView& sv, const TexView& tex, const FollowArgs& a);
+// pt_render_baked: hop `hop` of the same chains with the baked view's ending (include/pt_api.h states it): a chain that ends adds its baked
+// sample and 1 to sum[pixel]; state[].w is not used.  env.w == 0: the constant ambient
+struct BakedArgs : ChainHop
+{
+    f4* sum;
+    EnvView env;
+    float unlit[3];
+    uint32_t cap, hop, max_hops;
+};
+void launch_baked_follow(hipStream_t s, const SceneView& sv, const TexView& tex, const LmView& lm, const BakedArgs& a);
+// unit hook (pt_lightmap_lookup): lightmap_at (pt_materials.h) of world instance[i], leaf-order triangle tri[i] at barycentrics u[i], v[i]
+void launch_lightmap_lookup(hipStream_t s, const LmView& lm, uint32_t n, const uint32_t* instance, const uint32_t* tri, const float* u, const float* v,
+                            float* rgb, uint8_t* mapped);
 // pt_guide_follow_dir(on_device = 1): guide_follow_dir (pt_materials.h) of n hits of `material`, out4 = wo | followed
 void launch_guide_follow_dir(hipStream_t s, const SceneView& sv, int material, uint32_t n, const float* incoming, const float* normal, const uint8_t* front,
                              float* out4);

@@ -2987,6 +2987,97 @@ __global__ void __launch_bounds__(256, 8) k_guide_follow(const SceneView sv, con
         a.next.b[pos] = next_b;
     }
 }
+// ---- the baked view (pt_render_baked; include/pt_api.h states the sample).  k_guide_follow's chains, hop by hop through the same queues, with
+// another ending: a chain that ends adds its baked sample B and 1 to sum[pixel], one binary32 add per component, no finite check and no
+// clamp.  B = the running colour product R on a light; R * the lightmap at the hit on a front face of a leaf that has a map; R * unlit on any
+// other surface; the environment (or the constant ambient) of a miss, times R of the hop before unless the camera ray itself missed.  One
+// thread per ray slot, every output addressed by pixel, the next hop reserved with one ballot and one atomic per wave: as k_guide_follow,
+// whose remarks on the queues, the count words and what hop 0 and the last hop never touch hold here.  state[pixel].w is not used.
+template <bool FIRST>
+__global__ void __launch_bounds__(256, 8) k_baked_follow(const SceneView sv, const TexView tex, const LmView lm, const BakedArgs a)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t n = min(*a.n_in, a.cap);
+    bool go_on = false;
+    f4 next_a{}, next_b{};
+    if (i < n)
+    {
+        const f4 hit = a.hits[i];
+        const f4 rb = a.in.b[i];
+        const uint32_t px = asu(rb.w);
+        const f3 d = xyz(rb);
+        f3 b{0.0f, 0.0f, 0.0f};
+        const uint32_t hid = asu(hit.w);
+        if (hid == MISS_ID)
+        {
+            b = a.env.w ? env_lookup(a.env, d) : f3{0.006f, 0.006f, 0.006f};
+            if (!FIRST) b = xyz(a.state[px]) * b;
+        }
+        else
+        {
+            // (one gather after the other, each behind a compiler barrier, the map's four texels last: see k_guide_follow)
+            const uint32_t inst = hid >> sv.prim_bits, tri = hid & ((1u << sv.prim_bits) - 1u);
+            const DMaterial& dm = sv.materials[sv.instances[inst].material];
+            f3 c = surface_colour(tex, dm.texture, f3{dm.colour[0], dm.colour[1], dm.colour[2]}, tri, hit.y, hit.z);
+            if (!FIRST) c = xyz(a.state[px]) * c;
+            const uint32_t kind = dm.kind;
+            __asm__ volatile("" ::: "memory");
+            bool front;
+            const f3 nrm = hit_normal(sv, inst, tri, hit.y, hit.z, d, front);
+            const FollowDir f = guide_follow_dir(kind, dm.ior, d, nrm, front);
+            go_on = f.followed && a.hop < a.max_hops;
+            __asm__ volatile("" ::: "memory");
+            if (go_on)
+            {
+                const f3 p = fma3(d, bc3(hit.x), xyz(a.in.a[i]));
+                a.state[px] = f4{c.x, c.y, c.z, 0.0f};
+                next_a = f4{p.x, p.y, p.z, __builtin_inff()};
+                next_b = f4{f.wo.x, f.wo.y, f.wo.z, asf(px)};
+            }
+            else if (kind == MAT_EMISSIVE) b = c;
+            else
+            {
+                f3 l{a.unlit[0], a.unlit[1], a.unlit[2]};
+                if (front) // the bake lit the front side only
+                {
+                    bool mapped;
+                    const f3 m = lightmap_at(lm, inst, tri, hit.y, hit.z, &mapped);
+                    if (mapped) l = m;
+                }
+                b = c * l;
+            }
+        }
+        if (!go_on)
+        {
+            const f4 s = a.sum[px];
+            a.sum[px] = f4{s.x + b.x, s.y + b.y, s.z + b.z, s.w + 1.0f};
+        }
+    }
+    // every lane of the block is here (no early exit above), so lane 0 of each wave can reserve for it
+    const uint64_t m = __ballot(go_on);
+    if (m == 0ull) return;
+    uint32_t base = 0u;
+    if (lane_id() == 0u) base = atomicAdd(a.n_next, (uint32_t)__popcll(m));
+    base = __builtin_amdgcn_readfirstlane(base);
+    if (go_on)
+    {
+        const uint32_t pos = base + mbcnt64(m); // < the chains that go on <= n <= a.cap, the queues' slots
+        a.next.a[pos] = next_a;
+        a.next.b[pos] = next_b;
+    }
+}
+// unit hook of the lightmap lookup: rgb, mapped = lightmap_at
+__global__ void __launch_bounds__(256) k_lightmap_lookup(const LmView lm, const uint32_t n, const uint32_t* __restrict__ instance, const uint32_t* __restrict__ tri,
+                                                         const float* __restrict__ u, const float* __restrict__ v, float* __restrict__ rgb,
+                                                         uint8_t* __restrict__ mapped)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    bool has;
+    const f3 c = lightmap_at(lm, instance[i], tri[i], u[i], v[i], &has);
+    rgb[3u * (size_t)i] = c.x; rgb[3u * (size_t)i + 1u] = c.y; rgb[3u * (size_t)i + 2u] = c.z;
+    mapped[i] = has ? 1u : 0u;
+}
 // unit hook of guide_follow_dir: out4 = wo | followed
 __global__ void __launch_bounds__(256) k_guide_follow_dir(const SceneView sv, const int material, const uint32_t n, const float* __restrict__ incoming,
                                                           const float* __restrict__ normal, const uint8_t* __restrict__ front, float* __restrict__ out4)
@@ -3531,6 +3622,19 @@ void launch_guide_follow(hipStream_t s, const SceneView& sv, const TexView& tex,
     auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, sv, tex, a); };
     if (a.sum) a.hop == 0u ? go(k_guide_follow<true, true>) : go(k_guide_follow<true, false>);
     else a.hop == 0u ? go(k_guide_follow<false, true>) : go(k_guide_follow<false, false>);
+}
+void launch_baked_follow(hipStream_t s, const SceneView& sv, const TexView& tex, const LmView& lm, const BakedArgs& a)
+{
+    if (a.cap == 0u) return;
+    const dim3 grid((a.cap + 255u) / 256u);
+    if (a.hop == 0u) hipLaunchKernelGGL(k_baked_follow<true>, grid, dim3(256), 0, s, sv, tex, lm, a);
+    else hipLaunchKernelGGL(k_baked_follow<false>, grid, dim3(256), 0, s, sv, tex, lm, a);
+}
+void launch_lightmap_lookup(hipStream_t s, const LmView& lm, uint32_t n, const uint32_t* instance, const uint32_t* tri, const float* u, const float* v,
+                            float* rgb, uint8_t* mapped)
+{
+    if (n == 0u) return;
+    hipLaunchKernelGGL(k_lightmap_lookup, dim3((n + 255u) / 256u), dim3(256), 0, s, lm, n, instance, tri, u, v, rgb, mapped);
 }
 void launch_guide_follow_dir(hipStream_t s, const SceneView& sv, int material, uint32_t n, const float* incoming, const float* normal, const uint8_t* front,
                              float* out4)

@@ -177,6 +177,35 @@ PT_HD f3 surface_colour(const TexView& tv, uint32_t texture, f3 colour, uint32_t
     return colour * bilinear_rgb(tv.texels + t.offset, t.w, t.h, s, w);
 }
 
+// The lightmap lookup (pt_set_lightmap; the definition is include/pt_api.h's): the w x h map `texels` at the hit's interpolated UV, which is
+// surface_colour's s, t WITHOUT the repeat addressing.  Texel (i, j) has its centre at ((i + .5) / w, (j + .5) / h), the bake's p (lm_centre,
+// pt_lightmap.h), so the texel coordinate is w * s - 0.5, clamped to the edge (a NaN gives 0: no index leaves the map whatever the UVs are);
+// the blend is bilinear_blend's.  uv: the triangle's UVs at load-order vertices 0, 1, 2.  Every operation rounded once, in the order written.
+// Shared by the baked view's kernel, the unit hook's kernel and the hook's host evaluation.
+PT_HD f3 lightmap_lookup(const f4* texels, uint32_t w, uint32_t h, const DTriUV& uv, float u, float v)
+{
+    const float s = (uv.a[0] + u * (uv.b[0] - uv.a[0])) + v * (uv.c[0] - uv.a[0]);
+    const float t = (uv.a[1] + u * (uv.b[1] - uv.a[1])) + v * (uv.c[1] - uv.a[1]);
+    float x = (float)w * s - 0.5f, y = (float)h * t - 0.5f;
+    const float xm = (float)(w - 1u), ym = (float)(h - 1u);
+    x = !(x > 0.0f) ? 0.0f : (x > xm ? xm : x);
+    y = !(y > 0.0f) ? 0.0f : (y > ym ? ym : y);
+    const uint32_t x0 = (uint32_t)x, y0 = (uint32_t)y;
+    const float xf = x - truncf(x), yf = y - truncf(y);
+    const uint32_t x1 = x0 + 1u < w ? x0 + 1u : x0, y1 = y0 + 1u < h ? y0 + 1u : y0;
+    const f4 c00 = texels[(size_t)y0 * w + x0], c01 = texels[(size_t)y1 * w + x0];
+    const f4 c10 = texels[(size_t)y0 * w + x1], c11 = texels[(size_t)y1 * w + x1];
+    return bilinear_blend(BilinearTap{f3{c00.x, c00.y, c00.z}, f3{c01.x, c01.y, c01.z}, f3{c10.x, c10.y, c10.z}, f3{c11.x, c11.y, c11.z}, xf, yf});
+}
+// ... of a hit on world-TLAS leaf `inst`, leaf-order triangle `tri`; *mapped <- the leaf has a map (else the result is 0)
+PT_HD f3 lightmap_at(const LmView& lm, uint32_t inst, uint32_t tri, float u, float v, bool* mapped)
+{
+    const DLightmap r = lm.leaf[inst];
+    *mapped = r.w != 0u;
+    if (!*mapped) return f3{0.0f, 0.0f, 0.0f};
+    return lightmap_lookup(lm.texels + r.offset, r.w, r.h, lm.tri_uv[tri + r.uv_add], u, v);
+}
+
 // The normal map's lookup: bilinear_rgb, except that four EQUAL texels (rgb) are that texel, with no arithmetic.  The four bilinear weights do
 // not always sum to exactly 1 in binary32, so a constant region of a map would otherwise come back an ulp off at some UVs, and a flat map
 // would not be the plain normal bit for bit there.

@@ -112,6 +112,22 @@ struct TexNView : TexView
 {
     const f4* tri_tan;
 };
+// Lightmaps (pt_set_lightmap): one record per world-TLAS leaf in allocation order, the texels of every map in ONE f4 buffer like the textures'.
+struct alignas(16) DLightmap
+{
+    uint32_t offset;    // first texel of the leaf's map in the texel buffer
+    uint32_t w, h;      // 0 x 0: the leaf's (model, ordinal) has no map (a map has no side of 0), and nothing else of the record is read
+    uint32_t uv_add;    // what is added (mod 2^32, any value) to a hit's leaf-order triangle to index tri_uv
+};
+static_assert(sizeof(DLightmap) == 16, "");
+// What a lightmap lookup (lightmap_lookup, pt_materials.h) reads: tables of their own, outside SceneView and TexView, handed only to the baked
+// view's kernels.  tri_uv: the UVs of the models that carry a map, in leaf order; a textured scene's TexView::tri_uv itself (uv_add = 0).
+struct LmView
+{
+    const f4* texels;
+    const DLightmap* leaf;
+    const DTriUV* tri_uv;
+};
 
 // the barycentrics (u = v) of the light sampler's one-point quadrature (pt_api.h, LIGHT WEIGHT): a light triangle's weight is its area times
 // the length of its emitted colour there.  One constant for the host's weights (HostScene::build_lights) and the kernels' pdf (resolve_nee)

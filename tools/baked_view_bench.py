@@ -1,0 +1,104 @@
+#!/usr/bin/env python3
+"""What a baked view costs (profiles/r22_baked_view.md): on the 1080p Cornell frame with a 256 x 256 map on every placement, milliseconds per
+pt_render_baked(1 sample) at K = 0 and K = 2, beside pt_render_guides_followed at the same K (the same rays and traces, another ending) and
+the 1-spp pt_frame.  Every figure is the median of --calls blocking calls, taken --reps times with the routes alternating, so that a drift
+of the shared machine touches all of them; the report keeps every repeat, the spread is theirs.
+
+    python tools/baked_view_bench.py [--calls 20] [--reps 3] [--what all|guides] [--out report.json]
+
+--what guides times the guides call alone and runs on a tree that has no baked view: run it from the parent commit's tree and from this one,
+turn about, for the comparison across the two (the guide kernels themselves must not have moved)."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+W, H, DEPTH, SIZE = 1920, 1080, 8, 256
+HOPS = (0, 2)
+
+
+def planar_uvs(positions):
+    """UVs [n, 3, 2] over the two axes a model extends furthest along, each over the model's own extent: a layout for timing, not for baking"""
+    p = np.asarray(positions, np.float64).reshape(-1, 3, 3)
+    lo, hi = p.reshape(-1, 3).min(0), p.reshape(-1, 3).max(0)
+    ax = sorted(np.argsort(hi - lo)[1:])
+    return ((p[:, :, ax] - lo[ax]) / np.maximum(hi[ax] - lo[ax], 1e-9)).astype(np.float32)
+
+
+def timed(fn, calls):
+    ms = []
+    for _ in range(calls):
+        t0 = time.perf_counter()
+        fn()                                  # blocking: the call has synchronised its stream when it returns
+        ms.append(1e3 * (time.perf_counter() - t0))
+    return statistics.median(ms)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--calls", type=int, default=20)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--what", choices=["all", "guides"], default="all")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("baked_view_bench needs the GPU: there is nothing to time without one")
+    from path_tracer_amd import api, scenes
+    sc = scenes.cornell_box(W, H)
+    baked = args.what == "all"
+    if baked:
+        for m in sc.models:
+            m.uvs = planar_uvs(m.positions)
+    r = api.Renderer(sc, W, H, max_bounces=DEPTH)
+    report = {"width": W, "height": H, "map": SIZE, "calls": args.calls, "what": args.what, "guides_ms": {str(k): [] for k in HOPS}}
+    if baked:
+        rng = np.random.default_rng(22)
+        for mi, m in enumerate(sc.models):
+            for j in range(m.matrices.shape[0]):
+                r.set_lightmap(mi, j, rng.uniform(0.0, 1.0, (SIZE, SIZE, 3)).astype(np.float32))
+        report.update(baked_ms={str(k): [] for k in HOPS}, frame_ms=[])
+    routes = []
+    sample = [0]
+
+    def guides(k):
+        sample[0] += 1
+        r.render_guides(sample[0], follow=k)
+
+    def view(k):
+        sample[0] += 1
+        r.render_baked(sample[0], 1, follow=k, download=False)
+    last = [r.inv_projection()]
+
+    def frame():
+        sample[0] += 1
+        r.frame(sample[0], last[0], download=False)
+        last[0] = r.inv_projection()
+    for k in HOPS:
+        routes.append((report["guides_ms"][str(k)], lambda k=k: guides(k)))
+        if baked:
+            routes.append((report["baked_ms"][str(k)], lambda k=k: view(k)))
+    if baked:
+        routes.append((report["frame_ms"], frame))
+    for _, fn in routes:                      # warm-up: scene and map upload, code objects, the scratch at the size the timed calls use
+        fn()
+    for _ in range(args.reps):
+        for into, fn in routes:
+            into.append(round(timed(fn, args.calls), 4))
+    line = json.dumps(report)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
