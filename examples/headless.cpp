@@ -33,6 +33,9 @@
 //   examples/headless ... --bake-lightmap ... --baked-view SPP out.png   sets the dilated map it just baked, sum / its SPP, on the shell
 //       (pt_set_lightmap) and writes the baked view (pt_render_baked: SPP samples per pixel, chains followed --follow K hops, unmapped
 //       surfaces black)
+//   examples/headless ... --bake-lightmap ... --lightmap-denoise [--baked-view ...]   bakes with second moments (pt_bake_lightmap_moments), runs the
+//       texel-space filter on the sums (pt_lightmap_denoise, default parameters) and dilates its texel MEANS: map.txt then holds means, not sums,
+//       and --baked-view sets them as they are
 //   examples/headless ... --checker N   an N x N checker (texels 1 and 0.2, bilinear, repeating) on the floor, ceiling and back wall (cb_main.obj) with
 //                                        planar UVs: a vertex's (x, z) over the model's own extent in x and z
 //   examples/headless ... --emission-checker N   the same N x N checker as the EMISSION texture of the light (cb_light.obj) under the same planar UVs:
@@ -72,6 +75,7 @@ int main(int argc, char** argv)
     uint32_t lightmap[4] = {0, 0, 0, 0}; // W H SPP PASSES
     std::string lightmap_out = "";
     uint32_t baked_spp = 0;
+    bool lightmap_denoise = false;
     std::string baked_out = "";
     pt_projection projection{}; // PT_PROJ_PERSPECTIVE
     for (int i = 1; i < argc; ++i)
@@ -131,6 +135,7 @@ int main(int argc, char** argv)
             baked_spp = (uint32_t)std::atoi(next("--baked-view"));
             baked_out = next("--baked-view");
         }
+        else if (a == "--lightmap-denoise") lightmap_denoise = true;
         else if (a == "--load-state") load_state = next("--load-state");
         else if (a == "--save-state") save_state = next("--save-state");
         else if (a == "--devices")
@@ -140,7 +145,7 @@ int main(int argc, char** argv)
         }
         else if (a == "--help" || a == "-h")
         {
-            std::printf("usage: %s [--width W] [--height H] [--frames N] [--bounces B] [--move] [--slide DX DZ] [--models DIR] [--out file.png] [--temporal file.png [--temporal-rescue] [--temporal-mean-length] [--temporal-demodulate]] [--denoise file.png] [--denoise-albedo file.png] [--follow K] [--mirror-glass] [--aperture A --focus F] [--projection panorama[:SX:SY]|ortho:HEIGHT] [--bake-probes NX NY NZ SPP file.txt] [--bake-lightmap W H SPP PASSES file.txt [--baked-view SPP file.png]] [--checker N] [--emission-checker N] [--normal-ripples N]\n", argv[0]);
+            std::printf("usage: %s [--width W] [--height H] [--frames N] [--bounces B] [--move] [--slide DX DZ] [--models DIR] [--out file.png] [--temporal file.png [--temporal-rescue] [--temporal-mean-length] [--temporal-demodulate]] [--denoise file.png] [--denoise-albedo file.png] [--follow K] [--mirror-glass] [--aperture A --focus F] [--projection panorama[:SX:SY]|ortho:HEIGHT] [--bake-probes NX NY NZ SPP file.txt] [--bake-lightmap W H SPP PASSES file.txt [--lightmap-denoise] [--baked-view SPP file.png]] [--checker N] [--emission-checker N] [--normal-ripples N]\n", argv[0]);
             return 0;
         }
         else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
@@ -148,6 +153,11 @@ int main(int argc, char** argv)
     if (!baked_out.empty() && (lightmap_out.empty() || !lightmap[2] || !baked_spp))
     {
         std::fprintf(stderr, "--baked-view shows the map --bake-lightmap bakes: it needs that option, and samples for both\n");
+        return 2;
+    }
+    if (lightmap_denoise && (lightmap_out.empty() || !lightmap[2]))
+    {
+        std::fprintf(stderr, "--lightmap-denoise filters the map --bake-lightmap bakes: it needs that option, and samples\n");
         return 2;
     }
     if (normal_ripples && (checker || !lightmap_out.empty()))
@@ -292,7 +302,15 @@ int main(int argc, char** argv)
         auto bake_lightmap = [&]() -> bool {
             if (lightmap_out.empty()) return true;
             std::vector<float> sums;
-            std::vector<uint8_t> cov = renderer.bake_lightmap(1, 0, lightmap[0], lightmap[1], lightmap[2], sums, 0, 0, 0.25f);
+            std::vector<uint8_t> cov;
+            if (lightmap_denoise)
+            {
+                // the moments steer the filter's luminance term; what it returns are texel means, and those are what is dilated, written and set
+                std::vector<float> sumsq;
+                cov = renderer.bake_lightmap_moments(1, 0, lightmap[0], lightmap[1], lightmap[2], sums, sumsq, 0, 0, 0.25f);
+                sums = renderer.denoise_lightmap(1, 0, lightmap[0], lightmap[1], lightmap[2], sums, sumsq);
+            }
+            else cov = renderer.bake_lightmap(1, 0, lightmap[0], lightmap[1], lightmap[2], sums, 0, 0, 0.25f);
             renderer.dilate_lightmap(lightmap[0], lightmap[1], lightmap[3], sums, cov);
             std::FILE* f = std::fopen(lightmap_out.c_str(), "w");
             if (!f) { std::fprintf(stderr, "cannot write %s\n", lightmap_out.c_str()); return false; }
@@ -300,7 +318,8 @@ int main(int argc, char** argv)
             std::fclose(f);
             if (baked_out.empty()) return true;
             // ... and its consumer: the map's texel means on the shell, the followed first hits shaded from it
-            for (float& s : sums) s = s / (float)lightmap[2];
+            if (!lightmap_denoise)
+                for (float& s : sums) s = s / (float)lightmap[2];
             renderer.set_lightmap(1, 0, lightmap[0], lightmap[1], sums);
             renderer.render_baked(0, baked_spp, follow);
             renderer.write_baked_image(baked_out);

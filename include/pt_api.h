@@ -884,7 +884,8 @@ int pt_probe_ray(pt_ctx* ctx, uint32_t key, uint32_t sample, float d[3], float y
  * reserved word, key_base + w * h or first_sample + n_samples beyond 2^32; PT_ERR_LIMIT for a side above 16384 or more than 2^26 texels.
  * A map with no covered texel is PT_OK and integrates nothing.
  * Out of scope: unwrapping and atlas packing, conservative or supersampled coverage, direct light sampled at the texel, directional maps,
- * denoising, pt_multi_* variants.  (Showing a map: pt_set_lightmap and pt_render_baked, below.) */
+ * pt_multi_* variants.  (Denoising a map: pt_bake_lightmap_moments and pt_lightmap_denoise; showing one: pt_set_lightmap and pt_render_baked;
+ * all below.) */
 typedef struct pt_lightmap_params
 {
     int32_t model;                    /* model index */
@@ -911,6 +912,55 @@ int pt_lightmap_ray(pt_ctx* ctx, uint32_t key, uint32_t sample, const float norm
  * floats: sums or finished irradiance alike) and coverage (w * h bytes) are IN/OUT host pointers.  PT_ERR_ARG for a NULL pointer or a side of
  * 0, PT_ERR_LIMIT as pt_bake_lightmap, both before any device call; passes == 0 does nothing. */
 int pt_lightmap_dilate(pt_ctx* ctx, uint32_t w, uint32_t h, uint32_t passes, float* rgb, uint8_t* coverage);
+
+/* ---- denoising a lightmap in texel space: a second moment from the bake, pt_denoise's filter with a chart-aware tap term --------------- */
+/* pt_bake_lightmap_moments is pt_bake_lightmap, and it also folds a second moment: for every covered texel k and every sample s ascending,
+ * with L the radiance of that sample's ray,
+ *     Q[k] = Q[k] + l(L) * l(L),   l(c) = (0.2126f * c.r + 0.7152f * c.g) + 0.0722f * c.b        -- binary32, one rounding per operation
+ * which is the adaptive mode's Q of a texel.  sumsq (host, w * h floats) is IN/OUT like rgb_sum: (0, a) then (a, b) is (0, a + b) bit for bit in
+ * both arrays; rgb_sum and coverage come out as pt_bake_lightmap's, bit for bit.  Errors: pt_bake_lightmap's, and PT_ERR_ARG for a NULL sumsq.
+ *
+ * pt_lightmap_denoise is pt_denoise's filter (above: the terms, the taps, the order of the sums, c' = sc / sw; binary32, every operation rounded
+ * once, no contraction, in the order written, exp = exp_det) run on a texel grid, with ONE added term.  Two things make a texel grid differ
+ * from a frame: charts that lie side by side in UV space can be metres apart in the world, and the plane term is an angle, so two coplanar
+ * charts pass it at any distance and an a-trous step of 16 texels jumps the atlas padding.  REACH, below, is the term that stops that leak.
+ *   THE IMAGE the filter runs on: the texel table of (model, instance, w, h), as pt_lightmap_texels gives it.  A texel is VALID iff it is covered
+ *   (prim != 0xffffffff); acc = (sum.r, sum.g, sum.b, (float)n_samples) for a covered texel; position and normal are the table's P and n; every
+ *   covered texel is a hit of one model.  VARIANCE before level 0: with sumsq, pt_denoise's e2 from (acc, Q); without, its 7 x 7 spatial estimate.
+ *   TEXEL AREA of a covered texel whose triangle has object-space positions Pa, Pb, Pc and UVs a, b, c (a rigid instance keeps areas):
+ *       X = cross(Pb - Pa, Pc - Pa);  A3 = sqrt((X.x * X.x + X.y * X.y) + X.z * X.z)      -- cross: (a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, ..)
+ *       A2 = (float)fabs(E(a, b, c))                                                      -- the coverage rule's binary64 E, rounded once
+ *       area = A3 / ((A2 * (float)w) * (float)h)                                          -- the world area one texel covers
+ *     texel_area (w * h floats, may be NULL) receives it, and 0 for an uncovered texel.
+ *   REACH.  A tap q of p at texel offset (ox, oy) is, in addition to everything pt_denoise asks of a neighbour, accepted only if
+ *       d2 <= ((reach * reach) * area_p) * (float)(ox * ox + oy * oy)
+ *     d2 being the plane term's squared world distance of the two texels.  (ox, oy) are the real offsets: (s * dx, s * dy) in a level, (dx, dy) in
+ *     the 3 x 3 variance blur and in the 7 x 7 spatial variance, where the test applies as well; the integer is exact in binary32 up to step 128.
+ *     The comparison is written this way round so that a NaN on its right (A3 and A2 both 0) REJECTS the tap and an infinite area (A2 rounds to
+ *     0) ACCEPTS it.  reach * reach may overflow to infinity: that is the documented way to switch the term off, and then, wherever area_p is
+ *     neither 0 nor NaN, the result equals pt_post_denoise's bit for bit on accum = (sum, n) with w = 0 where the texel is uncovered,
+ *     position = (P, 0), normal = n, model = 0 and the same sumsq.  The default of 2 tolerates a 4 : 1 anisotropic UV stretch.
+ *   OUTPUT.  rgb_mean (w * h * 3) receives the last level's c' of a covered texel and (0, 0, 0) for an uncovered one, which is never a neighbour;
+ *   the caller dilates afterwards (pt_lightmap_dilate takes sums or finished irradiance alike).
+ * on_device = 0 walks the map on the host and touches no GPU; on_device = 1 runs kernels over the same per-texel functions.
+ * Errors, all before any device call (a refused call changes nothing): what pt_lightmap_texels refuses for model, instance, w and h; what
+ * pt_denoise refuses for the filter parameters; PT_ERR_ARG for a NULL p, rgb_sum or rgb_mean, a non-zero reserved word, n_samples of 0 or above
+ * 2^24, a reach that is negative, NaN or infinite, a value of rgb_sum or sumsq that is negative or not finite.
+ * Out of scope: per-texel sample counts, adaptive baking from the moments, chart ids from UV connectivity, filling uncovered texels inside the
+ * filter, demodulation, pt_multi_* variants. */
+int pt_bake_lightmap_moments(pt_ctx* ctx, const pt_lightmap_params* p, float* rgb_sum, float* sumsq, uint8_t* coverage);
+typedef struct pt_lightmap_denoise_params
+{
+    int32_t model;            /* the placement and the map, as pt_lightmap_texels */
+    uint32_t instance;
+    uint32_t w, h;
+    uint32_t n_samples;       /* samples in the sums: 1 .. 2^24 */
+    pt_denoise_params filter; /* defaults and ranges exactly pt_denoise's */
+    float reach;              /* 0 => 2; otherwise finite and > 0 */
+    uint32_t reserved[4];     /* must be 0 */
+} pt_lightmap_denoise_params;
+int pt_lightmap_denoise(pt_ctx* ctx, int on_device, const pt_lightmap_denoise_params* p, const float* rgb_sum, const float* sumsq, float* rgb_mean,
+                        float* texel_area);
 
 /* ---- lightmaps kept by the context, and the baked view: followed first hits shaded from them ------------------------------------------- */
 /* pt_set_lightmap gives the context the finished map of ONE placement, (model, instance) as pt_bake_lightmap keys it: rgb is w * h * 3 floats,
@@ -964,8 +1014,9 @@ int pt_lightmap_lookup(pt_ctx* ctx, int on_device, uint32_t n, const uint32_t* i
  * Errors, all before any device call: PT_ERR_ARG for what pt_guide_params refuses, an unlit that is negative or not finite, n_samples == 0 or
  * a range beyond 2^32; PT_ERR_STATE as pt_render_guides; pt_read_baked and pt_write_baked_image PT_ERR_STATE without current sums.  A scene
  * with no map at all is legal.
- * Out of scope: pt_multi_* variants, coverage-aware filtering (the caller dilates), directional maps, probes as the fallback of unmapped
- * surfaces, a specular response on GGX surfaces, perturbed normals, ending the path tracer's own paths in the maps, denoising the view. */
+ * Out of scope: pt_multi_* variants, directional maps, probes as the fallback of unmapped surfaces, a specular response on GGX surfaces,
+ * perturbed normals, ending the path tracer's own paths in the maps.  (The maps themselves are filtered before they are set:
+ * pt_lightmap_denoise, which knows the coverage, then pt_lightmap_dilate.) */
 typedef struct pt_baked_params
 {
     uint32_t max_hops;    /* 0..8, as pt_guide_params */

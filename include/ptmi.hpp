@@ -421,6 +421,38 @@ public:
         check(pt_bake_lightmap(ctx_, &p, rgb_sum.data(), coverage.data()));
         return coverage;
     }
+    // bake_lightmap that also folds the second moment of every sample's luminance into sumsq (w * h; empty: from zero), for denoise_lightmap
+    // (pt_bake_lightmap_moments)
+    std::vector<uint8_t> bake_lightmap_moments(int model, uint32_t instance, uint32_t w, uint32_t h, uint32_t n_samples, std::vector<float>& rgb_sum,
+                                               std::vector<float>& sumsq, uint32_t first_sample = 0, uint32_t key_base = 0, float bias = 0.0f)
+    {
+        const size_t px = (size_t)w * h;
+        if (rgb_sum.empty()) rgb_sum.assign(px * 3, 0.0f);
+        if (sumsq.empty()) sumsq.assign(px, 0.0f);
+        if (rgb_sum.size() != px * 3 || sumsq.size() != px) throw Error(PT_ERR_ARG, "bake_lightmap_moments: rgb_sum holds 3 values per texel and sumsq one");
+        std::vector<uint8_t> coverage(px);
+        pt_lightmap_params p{};
+        p.model = model; p.instance = instance; p.w = w; p.h = h;
+        p.first_sample = first_sample; p.n_samples = n_samples; p.key_base = key_base; p.bias = bias;
+        check(pt_bake_lightmap_moments(ctx_, &p, rgb_sum.data(), sumsq.data(), coverage.data()));
+        return coverage;
+    }
+    // the texel-space filter (pt_lightmap_denoise) on a bake's raw sums over n_samples samples: the texel means (w * h * 3, zeros where
+    // uncovered: dilate afterwards).  sumsq empty: the spatial variance; filter and reach 0: the defaults
+    std::vector<float> denoise_lightmap(int model, uint32_t instance, uint32_t w, uint32_t h, uint32_t n_samples, const std::vector<float>& rgb_sum,
+                                        const std::vector<float>& sumsq = {}, pt_denoise_params filter = {}, float reach = 0.0f, bool on_device = true,
+                                        std::vector<float>* texel_area = nullptr) const
+    {
+        const size_t px = (size_t)w * h;
+        if (rgb_sum.size() != px * 3 || (!sumsq.empty() && sumsq.size() != px)) throw Error(PT_ERR_ARG, "denoise_lightmap: rgb_sum holds 3 values per texel and sumsq one");
+        pt_lightmap_denoise_params p{};
+        p.model = model; p.instance = instance; p.w = w; p.h = h;
+        p.n_samples = n_samples; p.filter = filter; p.reach = reach;
+        std::vector<float> mean(px * 3);
+        if (texel_area) texel_area->assign(px, 0.0f);
+        check(pt_lightmap_denoise(ctx_, on_device ? 1 : 0, &p, rgb_sum.data(), sumsq.empty() ? nullptr : sumsq.data(), mean.data(), texel_area ? texel_area->data() : nullptr));
+        return mean;
+    }
     // `passes` dilation passes over a w x h map and its coverage bytes (pt_lightmap_dilate); filled texels carry the byte 2
     void dilate_lightmap(uint32_t w, uint32_t h, uint32_t passes, std::vector<float>& rgb, std::vector<uint8_t>& coverage)
     {

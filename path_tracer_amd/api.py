@@ -49,6 +49,7 @@ EXPORTS = [
     "pt_render_guides_followed", "pt_read_guide_hops", "pt_accumulate_albedo_followed", "pt_guide_follow_dir",
     "pt_frame_temporal", "pt_read_temporal", "pt_reset_temporal", "pt_post_temporal", "pt_frame_temporal_options", "pt_post_temporal_options",
     "pt_set_lightmap", "pt_get_lightmap_info", "pt_lightmap_lookup", "pt_render_baked", "pt_read_baked", "pt_reset_baked", "pt_write_baked_image",
+    "pt_bake_lightmap_moments", "pt_lightmap_denoise",
 ]
 
 
@@ -139,6 +140,12 @@ class LightmapParams(C.Structure):
     """pt_lightmap_params: the placement, size, sample range, stream keys and ray bias of a lightmap bake (include/pt_api.h)"""
     _fields_ = [("model", C.c_int32), ("instance", C.c_uint32), ("w", C.c_uint32), ("h", C.c_uint32), ("first_sample", C.c_uint32),
                 ("n_samples", C.c_uint32), ("key_base", C.c_uint32), ("bias", C.c_float), ("reserved", C.c_uint32 * 4)]
+
+
+class LightmapDenoiseParams(C.Structure):
+    """pt_lightmap_denoise_params: the placement and map, the samples in the sums, pt_denoise's filter parameters and the reach (include/pt_api.h)"""
+    _fields_ = [("model", C.c_int32), ("instance", C.c_uint32), ("w", C.c_uint32), ("h", C.c_uint32), ("n_samples", C.c_uint32),
+                ("filter", DenoiseParams), ("reach", C.c_float), ("reserved", C.c_uint32 * 4)]
 
 
 class SceneInfo(C.Structure):
@@ -290,6 +297,8 @@ def lib():
         L.pt_lightmap_texels.argtypes = [vp, C.c_int, u32, u32, u32, C.c_int, vp, vp, vp, vp]
         L.pt_lightmap_ray.argtypes = [vp, u32, u32, vp, vp]
         L.pt_lightmap_dilate.argtypes = [vp, u32, u32, u32, vp, vp]
+        L.pt_bake_lightmap_moments.argtypes = [vp, C.POINTER(LightmapParams), vp, vp, vp]
+        L.pt_lightmap_denoise.argtypes = [vp, C.c_int, C.POINTER(LightmapDenoiseParams), vp, vp, vp, vp]
         L.pt_set_lightmap.argtypes = [vp, C.c_int, u32, u32, u32, vp]
         L.pt_get_lightmap_info.argtypes = [vp, C.c_int, u32, vp, vp]
         L.pt_lightmap_lookup.argtypes = [vp, C.c_int, u32, vp, vp, vp, vp, vp, vp]
@@ -1027,6 +1036,36 @@ class Renderer:
             raise PtError(-1, "dilate_lightmap: rgb is (h, w, 3) and coverage (h, w)")
         self._chk(self.L.pt_lightmap_dilate(self.ctx, a.shape[1], a.shape[0], passes, _p(a), _p(cv)))
         return a, cv
+
+    def bake_lightmap_moments(self, model, instance, w, h, n_samples, first_sample=0, key_base=0, bias=0.0, sums=None, sumsq=None):
+        """bake_lightmap that also folds the second moment of every sample's luminance (pt_bake_lightmap_moments): returns (sums (h, w, 3),
+        sumsq (h, w), coverage (h, w) uint8); sums and sumsq continue from what is passed in (None: zero)"""
+        out = np.zeros((h, w, 3), np.float32) if sums is None else np.ascontiguousarray(sums, np.float32)
+        sq = np.zeros((h, w), np.float32) if sumsq is None else np.ascontiguousarray(sumsq, np.float32)
+        if out.size != w * h * 3 or sq.size != w * h:
+            raise PtError(-1, "bake_lightmap_moments: sums holds 3 values per texel and sumsq one")
+        cov = np.zeros((h, w), np.uint8)
+        prm = LightmapParams(model, instance, w, h, first_sample, n_samples, key_base, bias)
+        self._chk(self.L.pt_bake_lightmap_moments(self.ctx, C.byref(prm), _p(out), _p(sq), _p(cov)))
+        return out.reshape(h, w, 3), sq.reshape(h, w), cov
+
+    def denoise_lightmap(self, model, instance, sums, n_samples, sumsq=None, iterations=0, sigma_luminance=0.0, sigma_normal=0, sigma_plane=0.0, reach=0.0,
+                         on_device=True, want_area=False):
+        """the texel-space filter (pt_lightmap_denoise) on a bake's raw sums (h, w, 3) over n_samples samples, with its second moments sumsq
+        (h, w) or, None, the spatial variance: the texel means (h, w, 3), zeros where uncovered (dilate afterwards); with want_area
+        (means, texel areas (h, w)).  0 selects each default; on the host (no GPU) unless on_device"""
+        a = np.ascontiguousarray(sums, np.float32)
+        if a.ndim != 3 or a.shape[2] != 3:
+            raise PtError(-1, "denoise_lightmap: sums is (h, w, 3)")
+        h, w = a.shape[:2]
+        sq = None if sumsq is None else np.ascontiguousarray(sumsq, np.float32)
+        if sq is not None and sq.shape != (h, w):
+            raise PtError(-1, "denoise_lightmap: sumsq is (h, w)")
+        prm = LightmapDenoiseParams(model, instance, w, h, n_samples, DenoiseParams(iterations, sigma_luminance, sigma_normal, sigma_plane), reach)
+        out = np.zeros((h, w, 3), np.float32)
+        area = np.zeros((h, w), np.float32) if want_area else None
+        self._chk(self.L.pt_lightmap_denoise(self.ctx, int(bool(on_device)), C.byref(prm), _p(a), _p(sq), _p(out), _p(area)))
+        return (out, area) if want_area else out
 
     # ---- lightmaps kept by the context, and the baked view
     def set_lightmap(self, model, instance, rgb):

@@ -19,6 +19,10 @@
 //   host_sanitize lightmaps <n> <seed> lightmaps' host side: n random triangles with random UVs (far outside [0, 1], huge, mirrored and overflowing ones
 //                                      among them) under three placements, random maps of several sizes on two of them, then lightmap_lookup
 //                                      (pt_materials.h) at random hits; prints how many lookups met a map and a checksum of the results
+//   host_sanitize texelfilter <n> <seed> the texel filter's host side (pt_lightmap_filter.h, the functions the kernels run): n random triangles with the
+//                                      same hostile UVs, their texel tables on maps from 1 x 1 up, sides that are no multiple of 16 among them, random
+//                                      positive sums, then the whole filter with 8 levels (step 128 exceeds every map), with and without second
+//                                      moments, under the default reach, a tiny one and one whose square overflows; prints a checksum of the means
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -28,6 +32,7 @@
 #include <vector>
 
 #include "pt_batch_plan.h"
+#include "pt_lightmap_filter.h"
 #include "pt_materials.h"
 #include "pt_png.h"
 #include "pt_scene.h"
@@ -298,6 +303,64 @@ int main(int argc, char** argv)
             ++mapped;
         }
         std::printf("{\"triangles\": %u, \"lookups\": %u, \"checksum\": %.6f}\n", n, mapped, acc);
+        return 0;
+    }
+    if (cmd == "texelfilter" && argc >= 4)
+    {
+        const uint32_t n = (uint32_t)std::atoi(argv[2]);
+        uint64_t s = 0x9E3779B97F4A7C15ull ^ (uint64_t)std::atoll(argv[3]);
+        auto rnd = [&]() { s ^= s << 13; s ^= s >> 7; s ^= s << 17; return (float)((s >> 40) & 0xffff) / 65535.0f; };
+        if (n == 0) return 3;
+        std::vector<float> p, nr, uv;
+        for (uint32_t t = 0; t < n; ++t)
+        {
+            const float c[3] = {200.0f * rnd() - 100.0f, 200.0f * rnd() - 100.0f, 200.0f * rnd() - 100.0f};
+            const uint32_t shape = t % 7u; // lightmaps' six, and a triangle whose three positions are equal (A3 = 0) under UVs inside the map
+            for (int v = 0; v < 3; ++v)
+                for (int k = 0; k < 3; ++k) { p.push_back(shape == 6u ? c[k] : c[k] + 10.0f * rnd() - 5.0f); nr.push_back(k == 1 ? 1.0f : 0.2f * rnd() - 0.1f); }
+            const float a[2] = {rnd(), rnd()};
+            for (int v = 0; v < 3; ++v)
+                for (int k = 0; k < 2; ++k)
+                    uv.push_back(shape == 0u || shape == 6u ? rnd() : shape == 1u ? 40.0f * rnd() - 20.0f : shape == 2u ? a[k] : shape == 3u ? 1.0e6f + 3.0f * rnd()
+                                 : shape == 4u ? (v ? -1.0f : 1.0f) * (a[k] + rnd()) : (rnd() < 0.5f ? -3.0e38f : 3.0e38f));
+        }
+        const xf34 turn{m33{f3{0, 0, -1}, f3{0, 1, 0}, f3{1, 0, 0}}, f3{30, -20, 10}};
+        const uint32_t sizes[6][2] = {{1, 1}, {5, 3}, {16, 16}, {37, 19}, {2, 37}, {48, 32}};
+        const float reaches[3] = {2.0f, 1.0e-3f, 1.0e30f};
+        double acc = 0.0;
+        uint32_t covered = 0, finite = 0;
+        for (const uint32_t* wh : sizes)
+        {
+            const uint32_t w = wh[0], h = wh[1];
+            const size_t px = (size_t)w * h;
+            std::vector<uint32_t> owner;
+            lm_owner_host(uv.data(), n, w, h, owner);
+            std::vector<float> P(px * 3), N(px * 3), sum(px * 3), sq(px), mean(px * 3), area(px);
+            for (size_t k = 0; k < px; ++k)
+            {
+                float u32, v32;
+                f3 x, nn;
+                lm_resolve_host(uv.data(), p.data(), nr.data(), turn, w, h, k, owner[k], &u32, &v32, &x, &nn);
+                P[3 * k] = x.x; P[3 * k + 1] = x.y; P[3 * k + 2] = x.z;
+                N[3 * k] = nn.x; N[3 * k + 1] = nn.y; N[3 * k + 2] = nn.z;
+                for (int ch = 0; ch < 3; ++ch) sum[3 * k + ch] = 40.0f * rnd();
+                sq[k] = 200.0f * rnd();
+                covered += owner[k] != MISS_ID ? 1u : 0u;
+            }
+            for (int pass = 0; pass < 6; ++pass)
+            {
+                const float reach = reaches[pass % 3];
+                const LmFilterK k{4.0f, 1.0f, 7u, 8u, reach * reach};
+                lmf_filter_host(w, h, k, owner.data(), P.data(), N.data(), p.data(), uv.data(), sum.data(), pass < 3 ? sq.data() : nullptr, 16u, mean.data(), area.data());
+                for (size_t k2 = 0; k2 < px; ++k2)
+                {
+                    if (owner[k2] == MISS_ID && (mean[3 * k2] != 0.0f || mean[3 * k2 + 1] != 0.0f || mean[3 * k2 + 2] != 0.0f || area[k2] != 0.0f)) return 6;
+                    for (int ch = 0; ch < 3; ++ch)
+                        if (std::isfinite(mean[3 * k2 + ch])) { acc += (ch + 1.0) * mean[3 * k2 + ch]; ++finite; }
+                }
+            }
+        }
+        std::printf("{\"triangles\": %u, \"covered\": %u, \"finite\": %u, \"checksum\": %.6f}\n", n, covered, finite, acc);
         return 0;
     }
     if (cmd == "plan")

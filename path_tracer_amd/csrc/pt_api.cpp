@@ -20,6 +20,7 @@
 #include "pt_kernels.h"
 #include "pt_png.h"
 #include "pt_lightmap.h"
+#include "pt_lightmap_filter.h"
 #include "pt_probe.h"
 #include "pt_scene.h"
 
@@ -1585,25 +1586,8 @@ int ensure_lightmaps(pt_ctx* c)
     return PT_OK;
 }
 
-// owner[k] = the lowest triangle index whose UVs contain the centre of texel k, MISS_ID where none does: the walk k_lm_cover does, triangle by
-// triangle over its texel rectangle, with a running minimum in the atomic's place
-void lightmap_owner_host(const HostModel& m, uint32_t w, uint32_t h, std::vector<uint32_t>& owner)
-{
-    owner.assign((size_t)w * h, MISS_ID);
-    for (uint32_t t = 0; t < m.n_tris; ++t)
-    {
-        const float* uv = m.uvs.data() + 6u * (size_t)t;
-        LmBox box;
-        if (!lm_box(uv, w, h, &box)) continue;
-        for (uint32_t j = box.j0; j < box.j0 + box.bh; ++j)
-            for (uint32_t i = box.i0; i < box.i0 + box.bw; ++i)
-            {
-                double u, v;
-                uint32_t& o = owner[(size_t)j * w + i];
-                if (t < o && lm_contains(uv, lm_centre(i, w), lm_centre(j, h), &u, &v)) o = t;
-            }
-    }
-}
+// the owner of every texel of a map of model m (pt_lightmap.h's host walk)
+void lightmap_owner_host(const HostModel& m, uint32_t w, uint32_t h, std::vector<uint32_t>& owner) { lm_owner_host(m.uvs.data(), m.n_tris, w, h, owner); }
 
 // the coverage launch's work items: every triangle's texel rectangle in slices of kLightmapSlice texels
 std::vector<uint2> lightmap_items(const HostModel& m, uint32_t w, uint32_t h)
@@ -1626,6 +1610,7 @@ struct LightmapDev
     uint32_t* prim;
     float *uv2, *position, *normal;
     uint8_t* coverage;
+    LightmapView view; // the model's uploaded arrays and the matrix, for the kernels that run on the table afterwards
 };
 int lightmap_texels_device(pt_ctx* c, Staging& st, const HostModel& m, uint32_t instance, uint32_t w, uint32_t h, LightmapDev& out)
 {
@@ -1647,6 +1632,7 @@ int lightmap_texels_device(pt_ctx* c, Staging& st, const HostModel& m, uint32_t 
     launch_lightmap_cover(c->stream, lm, d_items, (uint32_t)items.size(), out.prim);
     launch_lightmap_resolve(c->stream, lm, out.prim, out.uv2, out.position, out.normal, out.coverage);
     HIPCHK(c, hipGetLastError());
+    out.view = lm;
     return PT_OK;
 }
 
@@ -3466,15 +3452,9 @@ int pt_lightmap_texels(pt_ctx* c, int model, uint32_t instance, uint32_t w, uint
         for (size_t k = 0; k < px; ++k)
         {
             const uint32_t t = owner[k];
-            float u32 = 0.0f, v32 = 0.0f;
-            f3 P{0.0f, 0.0f, 0.0f}, n{0.0f, 0.0f, 0.0f};
-            if (t != MISS_ID)
-            {
-                double u = 0.0, v = 0.0;
-                (void)lm_contains(m.uvs.data() + 6u * (size_t)t, lm_centre((uint32_t)(k % w), w), lm_centre((uint32_t)(k / w), h), &u, &v);
-                u32 = (float)u; v32 = (float)v;
-                lm_surface(m.positions.data() + 9u * (size_t)t, m.normals.data() + 9u * (size_t)t, m.matrices[instance], u32, v32, &P, &n);
-            }
+            float u32, v32;
+            f3 P, n;
+            lm_resolve_host(m.uvs.data(), m.positions.data(), m.normals.data(), m.matrices[instance], w, h, k, t, &u32, &v32, &P, &n);
             if (prim) prim[k] = t;
             if (uv2) { uv2[2 * k] = u32; uv2[2 * k + 1] = v32; }
             if (position) { position[3 * k] = P.x; position[3 * k + 1] = P.y; position[3 * k + 2] = P.z; }
@@ -3494,13 +3474,15 @@ int pt_lightmap_texels(pt_ctx* c, int model, uint32_t instance, uint32_t w, uint
     return PT_OK;
 }
 
-int pt_bake_lightmap(pt_ctx* c, const pt_lightmap_params* p, float* rgb_sum, uint8_t* coverage)
+} // extern "C"
+namespace {
+// pt_bake_lightmap (sumsq null, moments false) and pt_bake_lightmap_moments under the context's lock
+int bake_lightmap_locked(pt_ctx* c, const pt_lightmap_params* p, float* rgb_sum, float* sumsq, bool moments, uint8_t* coverage)
 {
-    if (!c) return PT_ERR_ARG;
-    std::lock_guard<std::mutex> lk(c->mu);
     int r;
     if ((r = rays_precheck(c))) return r;
     if (!p || !rgb_sum) return fail(c, PT_ERR_ARG, "pt_bake_lightmap: p and rgb_sum must not be NULL");
+    if (moments && !sumsq) return fail(c, PT_ERR_ARG, "pt_bake_lightmap_moments: sumsq must not be NULL");
     if (p->reserved[0] || p->reserved[1] || p->reserved[2] || p->reserved[3]) return fail(c, PT_ERR_ARG, "pt_lightmap_params.reserved must be 0");
     if ((r = lightmap_check(c, p->model, p->instance, p->w, p->h))) return r;
     if (p->n_samples == 0) return fail(c, PT_ERR_ARG, "pt_lightmap_params.n_samples must be non-zero");
@@ -3524,14 +3506,91 @@ int pt_bake_lightmap(pt_ctx* c, const pt_lightmap_params* p, float* rgb_sum, uin
     {
         const uint32_t* d_texels = (const uint32_t*)st.in(texels.data(), (size_t)n_cov * 4);
         float* d_sum = (float*)st.in(rgb_sum, px * 12);
+        float* d_sq = moments ? (float*)st.in(sumsq, px * 4) : nullptr;
         const LightmapBake lb{d_texels, t.position, t.normal, n_cov, p->first_sample, p->n_samples, p->key_base, c->cfg.n_sobol, p->bias, c->cfg.seed};
         if ((r = bake_rays(c, st, n_cov, p->n_samples,
                            [&](uint64_t first, uint32_t cnt, float* o, float* d, uint2* key) { launch_lightmap_rays(c->stream, lb, first, cnt, o, d, key); },
-                           [&](uint64_t first, uint32_t cnt, const float*, const f4* rad) { launch_lightmap_fold(c->stream, lb, first, cnt, rad, d_sum); })))
+                           [&](uint64_t first, uint32_t cnt, const float*, const f4* rad) { launch_lightmap_fold(c->stream, lb, first, cnt, rad, d_sum, d_sq); })))
             return r;
         if ((r = st.download(rgb_sum, d_sum, px * 12))) return r;
+        if (moments && (r = st.download(sumsq, d_sq, px * 4))) return r;
     }
     if (coverage) std::memcpy(coverage, cov.data(), px);
+    return PT_OK;
+}
+} // namespace
+extern "C" {
+
+int pt_bake_lightmap(pt_ctx* c, const pt_lightmap_params* p, float* rgb_sum, uint8_t* coverage)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    return bake_lightmap_locked(c, p, rgb_sum, nullptr, false, coverage);
+}
+
+int pt_bake_lightmap_moments(pt_ctx* c, const pt_lightmap_params* p, float* rgb_sum, float* sumsq, uint8_t* coverage)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    return bake_lightmap_locked(c, p, rgb_sum, sumsq, true, coverage);
+}
+
+int pt_lightmap_denoise(pt_ctx* c, int on_device, const pt_lightmap_denoise_params* p, const float* rgb_sum, const float* sumsq, float* rgb_mean, float* texel_area)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    int r;
+    if (!p || !rgb_sum || !rgb_mean) return fail(c, PT_ERR_ARG, "pt_lightmap_denoise: p, rgb_sum and rgb_mean must not be NULL");
+    if (p->reserved[0] || p->reserved[1] || p->reserved[2] || p->reserved[3]) return fail(c, PT_ERR_ARG, "pt_lightmap_denoise_params.reserved must be 0");
+    if ((r = lightmap_check(c, p->model, p->instance, p->w, p->h))) return r;
+    DenoiseK dk{};
+    if ((r = denoise_params(c, &p->filter, dk))) return r;
+    if (p->n_samples == 0 || p->n_samples > (1u << 24)) return fail(c, PT_ERR_ARG, "pt_lightmap_denoise_params.n_samples must be from 1 to 2^24");
+    if (!(p->reach >= 0.0f) || !std::isfinite(p->reach)) return fail(c, PT_ERR_ARG, "pt_lightmap_denoise_params.reach must be finite and >= 0");
+    const size_t px = (size_t)p->w * p->h;
+    for (size_t i = 0; i < px * 3; ++i)
+        if (!(rgb_sum[i] >= 0.0f) || !std::isfinite(rgb_sum[i])) return fail(c, PT_ERR_ARG, "pt_lightmap_denoise: a value of rgb_sum that is negative or not finite");
+    for (size_t i = 0; sumsq && i < px; ++i)
+        if (!(sumsq[i] >= 0.0f) || !std::isfinite(sumsq[i])) return fail(c, PT_ERR_ARG, "pt_lightmap_denoise: a value of sumsq that is negative or not finite");
+    const float reach = p->reach != 0.0f ? p->reach : 2.0f;
+    const LmFilterK k{dk.sigma_l, dk.sigma_x, dk.log2_sigma_n, dk.iterations, reach * reach};
+    const HostModel& m = c->scene.models[p->model];
+    if (!on_device)
+    {
+        try
+        {
+            std::vector<uint32_t> owner;
+            lightmap_owner_host(m, p->w, p->h, owner);
+            std::vector<float> P(px * 3), N(px * 3);
+            for (size_t t = 0; t < px; ++t)
+            {
+                float u32, v32;
+                f3 x, n;
+                lm_resolve_host(m.uvs.data(), m.positions.data(), m.normals.data(), m.matrices[p->instance], p->w, p->h, t, owner[t], &u32, &v32, &x, &n);
+                P[3 * t] = x.x; P[3 * t + 1] = x.y; P[3 * t + 2] = x.z;
+                N[3 * t] = n.x; N[3 * t + 1] = n.y; N[3 * t + 2] = n.z;
+            }
+            lmf_filter_host(p->w, p->h, k, owner.data(), P.data(), N.data(), m.positions.data(), m.uvs.data(), rgb_sum, sumsq, p->n_samples, rgb_mean, texel_area);
+        }
+        catch (const std::exception& e) { return fail(c, PT_ERR_LIMIT, std::string("the texel filter's images do not fit in host memory: ") + e.what()); }
+        return PT_OK;
+    }
+    if ((r = ensure_device(c))) return r;
+    Staging st(c);
+    LightmapDev t{};
+    if ((r = lightmap_texels_device(c, st, m, p->instance, p->w, p->h, t))) return r;
+    LmFilterImages im{};
+    im.prim = t.prim; im.position = t.position; im.normal = t.normal;
+    im.sum = (const float*)st.in(rgb_sum, px * 12);
+    im.sumsq = sumsq ? (const float*)st.in(sumsq, px * 4) : nullptr;
+    im.cv_a = (f4*)st.out(px * 16); im.cv_b = (f4*)st.out(px * 16); im.pa = (f4*)st.out(px * 16); im.nv = (f4*)st.out(px * 16);
+    im.rgb = (float*)st.out(px * 12);
+    im.area = texel_area ? (float*)st.out(px * 4) : nullptr;
+    if (st.err) return st.err;
+    launch_lightmap_denoise(c->stream, t.view, k, p->n_samples, sumsq != nullptr, im);
+    HIPCHK(c, hipGetLastError());
+    if ((r = st.download(rgb_mean, im.rgb, px * 12))) return r;
+    if (texel_area && (r = st.download(texel_area, im.area, px * 4))) return r;
     return PT_OK;
 }
 

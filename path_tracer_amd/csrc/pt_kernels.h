@@ -129,9 +129,23 @@ struct LightmapBake
     uint64_t seed;
 };
 void launch_lightmap_rays(hipStream_t s, const LightmapBake& lb, uint64_t first, uint32_t count, float* o, float* d, uint2* key);
-void launch_lightmap_fold(hipStream_t s, const LightmapBake& lb, uint64_t first, uint32_t count, const f4* radiance, float* sum);
+// sumsq (pt_bake_lightmap_moments; null: pt_bake_lightmap's launch as it was): the map's w * h second moments, Q[texel] += l(L) * l(L) in the same order
+void launch_lightmap_fold(hipStream_t s, const LightmapBake& lb, uint64_t first, uint32_t count, const f4* radiance, float* sum, float* sumsq = nullptr);
 // one dilation pass (lm_dilate) of a w x h map from (rgb, cov) to (rgb_out, cov_out)
 void launch_lightmap_dilate(hipStream_t s, uint32_t w, uint32_t h, const float* rgb, const uint8_t* cov, float* rgb_out, uint8_t* cov_out);
+// the texel filter (pt_lightmap_denoise; the per-texel steps are pt_lightmap_filter.h's) of the map of lm: prim, position, normal are
+// launch_lightmap_resolve's table, sum (w * h * 3) and sumsq (w * h; read with `moments` only, else the spatial variance) the bake's; cv_a, cv_b,
+// pa, nv: scratch of w * h 16-byte entries each; rgb <- the means (w * h * 3, zeros where uncovered); area (may be null) <- the texel areas
+struct LmFilterK;
+struct LmFilterImages
+{
+    const uint32_t* prim;
+    const float *position, *normal, *sum, *sumsq;
+    f4 *cv_a, *cv_b, *pa, *nv;
+    float* rgb;
+    float* area;
+};
+void launch_lightmap_denoise(hipStream_t s, const LightmapView& lm, const LmFilterK& p, uint32_t n_samples, bool moments, const LmFilterImages& im);
 
 // ---- the keyed launchers' variants, for tests (pt_variant_axes, pt_variant_compiled, pt_last_launches; include/pt_api.h has the axes' values).
 // A keyed launcher turns integers into template arguments (pick_axes, pt_kernels.hip); the axes' bounds and the predicate that says which of

@@ -3,6 +3,8 @@
 // and for the host evaluations (pt_lightmap_texels with on_device = 0, pt_lightmap_ray).  include/pt_api.h, pt_bake_lightmap, states it
 // operation for operation; every operation is rounded once, in this order (the library is built without contraction).
 #pragma once
+#include <vector>
+
 #include "pt_types.h"
 
 namespace pt {
@@ -56,6 +58,39 @@ PT_HD void lm_surface(const float p9[9], const float n9[9], const xf34& m, float
     const f3 n_obj = unit3((na * wgt + nb * u) + nc * v);
     *P = xf_point(m, p_obj);
     *n = xf_vector(m, n_obj);
+}
+
+// The texel table on the host (pt_lightmap_texels with on_device = 0, pt_lightmap_denoise's host walk), over a model's load-order arrays.
+// owner[k] = the lowest triangle index whose UVs contain the centre of texel k, MISS_ID where none does: the walk k_lm_cover does, triangle by
+// triangle over its texel rectangle, with a running minimum in the atomic's place
+inline void lm_owner_host(const float* uvs, uint32_t n_tris, uint32_t w, uint32_t h, std::vector<uint32_t>& owner)
+{
+    owner.assign((size_t)w * h, MISS_ID);
+    for (uint32_t t = 0; t < n_tris; ++t)
+    {
+        const float* uv = uvs + 6u * (size_t)t;
+        LmBox box;
+        if (!lm_box(uv, w, h, &box)) continue;
+        for (uint32_t j = box.j0; j < box.j0 + box.bh; ++j)
+            for (uint32_t i = box.i0; i < box.i0 + box.bw; ++i)
+            {
+                double u, v;
+                uint32_t& o = owner[(size_t)j * w + i];
+                if (t < o && lm_contains(uv, lm_centre(i, w), lm_centre(j, h), &u, &v)) o = t;
+            }
+    }
+}
+// what k_lm_resolve writes for texel k owned by triangle t (MISS_ID: zeros)
+inline void lm_resolve_host(const float* uvs, const float* positions, const float* normals, const xf34& m, uint32_t w, uint32_t h, size_t k, uint32_t t,
+                            float* u32, float* v32, f3* P, f3* n)
+{
+    *u32 = 0.0f; *v32 = 0.0f;
+    *P = f3{0.0f, 0.0f, 0.0f}; *n = f3{0.0f, 0.0f, 0.0f};
+    if (t == MISS_ID) return;
+    double u = 0.0, v = 0.0;
+    (void)lm_contains(uvs + 6u * (size_t)t, lm_centre((uint32_t)(k % w), w), lm_centre((uint32_t)(k / w), h), &u, &v);
+    *u32 = (float)u; *v32 = (float)v;
+    lm_surface(positions + 9u * (size_t)t, normals + 9u * (size_t)t, m, *u32, *v32, P, n);
 }
 
 // origin of a texel's rays

@@ -4,12 +4,17 @@
 //   k_lm_cover     a workgroup per (triangle, slice of its texel rectangle): the coverage predicate, atomicMin of the triangle index
 //   k_lm_resolve   a thread per texel: (u, v) of the owner, surface point and normal under the instance matrix, coverage byte
 //   k_lm_rays      a thread per ray: origin P + bias * n, a cosine-distributed direction over n, the stream key
-//   k_lm_fold      a thread per (covered texel, channel): the window's radiance added to the texel's sum in sample order
+//   k_lm_fold      a thread per (covered texel, channel): the window's radiance added to the texel's sum in sample order; with MOMENTS a
+//                  fourth thread per texel adds l(L) * l(L) to its second moment (pt_bake_lightmap_moments)
 //   k_lm_dilate    a thread per texel: one dilation pass from one buffer pair to the other
+//   k_lmf_*        pt_lightmap_denoise: the per-texel steps of pt_lightmap_filter.h.  One thread per texel; the spatial variance and the levels
+//                  in 16 x 16 workgroups, ping-pong.  Gather-bound like k_dn_level: a tap is three 16-byte loads (colour | variance, P | area,
+//                  n | valid), and the valid word decides whether the other two are made
 #include <hip/hip_runtime.h>
 
 #include "pt_kernels.h"
 #include "pt_lightmap.h"
+#include "pt_lightmap_filter.h"
 
 namespace pt {
 namespace {
@@ -93,15 +98,31 @@ __global__ void __launch_bounds__(256) k_lm_rays(const LightmapBake lb, const ui
 // sum[texel][c] += L[c] over the window's rays of that texel, in sample order: one thread per (covered texel, channel), a serial fold by
 // definition (float addition does not associate) and no atomics.  The adds form one dependent chain; the loads do not depend on it, so eight
 // samples are fetched before their adds, and the next eight can be in flight while those adds run.
+// MOMENTS: four threads per texel; the fourth folds Q[texel] += l(L) * l(L) over the same rays in the same order, and the other three run
+// the code they run without it
+template <bool MOMENTS>
 __global__ void __launch_bounds__(256) k_lm_fold(const LightmapBake lb, const uint64_t first, const uint32_t count, const f4* __restrict__ radiance,
-                                                  float* __restrict__ sum)
+                                                  float* __restrict__ sum, float* __restrict__ sumsq)
 {
+    constexpr uint32_t CH = MOMENTS ? 4u : 3u;
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t p0 = (uint32_t)(first / lb.n_samples), p1 = (uint32_t)((first + count - 1u) / lb.n_samples);
-    if (t / 3u > p1 - p0) return;
-    const uint32_t rank = p0 + t / 3u, c = t % 3u;
+    if (t / CH > p1 - p0) return;
+    const uint32_t rank = p0 + t / CH, c = t % CH;
     const uint64_t lo = (uint64_t)rank * lb.n_samples, hi = lo + lb.n_samples;
     const uint32_t i0 = (uint32_t)((lo > first ? lo : first) - first), i1 = (uint32_t)((hi < first + count ? hi : first + count) - first);
+    if (MOMENTS && c == 3u)
+    {
+        float* q = sumsq + lb.texels[rank];
+        float acc = *q;
+        for (uint32_t i = i0; i < i1; ++i)
+        {
+            const float l = lum(radiance[i]);
+            acc = acc + l * l;
+        }
+        *q = acc;
+        return;
+    }
     float* dst = sum + 3u * (size_t)lb.texels[rank] + c;
     const float* src = (const float*)radiance + c;
     float acc = *dst;
@@ -131,6 +152,42 @@ __global__ void __launch_bounds__(256) k_lm_dilate(const uint32_t w, const uint3
     cov_out[k] = filled ? (uint8_t)2u : cov[k];
 }
 
+// ---- the texel filter (pt_lightmap_denoise)
+__global__ void __launch_bounds__(256) k_lmf_prep(const LightmapView lm, const uint32_t* __restrict__ prim, const float* __restrict__ position,
+                                                   const float* __restrict__ normal, const float* __restrict__ sum, const float* __restrict__ sumsq, const float n,
+                                                   f4* __restrict__ cv, f4* __restrict__ pa, f4* __restrict__ nv, float* __restrict__ area)
+{
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= lm.w * lm.h) return;
+    lmf_prep(k, lm.w, lm.h, prim, position, normal, lm.positions, lm.uv, sum, sumsq, n, cv, pa, nv);
+    if (area) area[k] = pa[k].w;
+}
+
+__global__ void __launch_bounds__(256) k_lmf_spatial_var(const int w, const int h, const LmFilterK p, const f4* __restrict__ cv_in, const f4* __restrict__ pa,
+                                                          const f4* __restrict__ nv, f4* __restrict__ cv_out)
+{
+    const int x = blockIdx.x * 16 + threadIdx.x, y = blockIdx.y * 16 + threadIdx.y;
+    if (x >= w || y >= h) return;
+    const size_t i = (size_t)y * w + x;
+    if (nv[i].w == 0.0f) { cv_out[i] = f4{0.0f, 0.0f, 0.0f, 0.0f}; return; }
+    const f4 c = cv_in[i];
+    cv_out[i] = f4{c.x, c.y, c.z, lmf_spatial_variance(w, h, p, cv_in, pa, nv, x, y)};
+}
+
+// FINAL: the last level writes the map's rgb (zeros for an uncovered texel) instead of (c', var')
+template <bool FINAL>
+__global__ void __launch_bounds__(256) k_lmf_level(const int w, const int h, const int s, const LmFilterK p, const f4* __restrict__ cv_in, const f4* __restrict__ pa,
+                                                    const f4* __restrict__ nv, f4* __restrict__ cv_out, float* __restrict__ rgb)
+{
+    const int x = blockIdx.x * 16 + threadIdx.x, y = blockIdx.y * 16 + threadIdx.y;
+    if (x >= w || y >= h) return;
+    const size_t i = (size_t)y * w + x;
+    f4 c{0.0f, 0.0f, 0.0f, 0.0f};
+    if (nv[i].w != 0.0f) c = lmf_level(w, h, s, p, cv_in, pa, nv, x, y);
+    if (FINAL) { rgb[3u * i] = c.x; rgb[3u * i + 1u] = c.y; rgb[3u * i + 2u] = c.z; }
+    else cv_out[i] = c;
+}
+
 inline dim3 blocks_for(uint64_t n) { return dim3((uint32_t)((n + 255u) / 256u)); }
 
 } // namespace
@@ -149,15 +206,37 @@ void launch_lightmap_rays(hipStream_t s, const LightmapBake& lb, uint64_t first,
     if (count == 0) return;
     hipLaunchKernelGGL(k_lm_rays, blocks_for(count), dim3(256), 0, s, lb, first, count, o, d, key);
 }
-void launch_lightmap_fold(hipStream_t s, const LightmapBake& lb, uint64_t first, uint32_t count, const f4* radiance, float* sum)
+void launch_lightmap_fold(hipStream_t s, const LightmapBake& lb, uint64_t first, uint32_t count, const f4* radiance, float* sum, float* sumsq)
 {
     if (count == 0) return;
     const uint64_t texels = (first + count - 1u) / lb.n_samples - first / lb.n_samples + 1u;
-    hipLaunchKernelGGL(k_lm_fold, blocks_for(texels * 3u), dim3(256), 0, s, lb, first, count, radiance, sum);
+    if (sumsq) hipLaunchKernelGGL(k_lm_fold<true>, blocks_for(texels * 4u), dim3(256), 0, s, lb, first, count, radiance, sum, sumsq);
+    else hipLaunchKernelGGL(k_lm_fold<false>, blocks_for(texels * 3u), dim3(256), 0, s, lb, first, count, radiance, sum, sumsq);
 }
 void launch_lightmap_dilate(hipStream_t s, uint32_t w, uint32_t h, const float* rgb, const uint8_t* cov, float* rgb_out, uint8_t* cov_out)
 {
     hipLaunchKernelGGL(k_lm_dilate, blocks_for((uint64_t)w * h), dim3(256), 0, s, w, h, rgb, cov, rgb_out, cov_out);
+}
+
+void launch_lightmap_denoise(hipStream_t s, const LightmapView& lm, const LmFilterK& p, uint32_t n_samples, bool moments, const LmFilterImages& im)
+{
+    const int w = (int)lm.w, h = (int)lm.h;
+    const dim3 tile(16, 16), grid((lm.w + 15u) / 16u, (lm.h + 15u) / 16u);
+    f4* cur = im.cv_a;
+    f4* other = im.cv_b;
+    hipLaunchKernelGGL(k_lmf_prep, blocks_for((uint64_t)lm.w * lm.h), dim3(256), 0, s, lm, im.prim, im.position, im.normal, im.sum, moments ? im.sumsq : (const float*)nullptr,
+                       (float)n_samples, cur, im.pa, im.nv, im.area);
+    if (!moments)
+    {
+        hipLaunchKernelGGL(k_lmf_spatial_var, grid, tile, 0, s, w, h, p, (const f4*)cur, (const f4*)im.pa, (const f4*)im.nv, other);
+        std::swap(cur, other);
+    }
+    for (uint32_t it = 0; it < p.iterations; ++it)
+    {
+        if (it + 1u == p.iterations) hipLaunchKernelGGL(k_lmf_level<true>, grid, tile, 0, s, w, h, 1 << it, p, (const f4*)cur, (const f4*)im.pa, (const f4*)im.nv, other, im.rgb);
+        else hipLaunchKernelGGL(k_lmf_level<false>, grid, tile, 0, s, w, h, 1 << it, p, (const f4*)cur, (const f4*)im.pa, (const f4*)im.nv, other, im.rgb);
+        std::swap(cur, other);
+    }
 }
 
 } // namespace pt

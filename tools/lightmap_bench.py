@@ -7,7 +7,14 @@ The difference is coverage, resolve, ray generation, fold and the map's copies; 
 
     python tools/lightmap_bench.py [--size 1024] [--spp 64] [--reps 3] [--model cb_box_short] [--only bake|rays] [--out report.json]
 
---only bake with --reps 1 is the run to put under rocprofv3 --kernel-trace --stats for the per-kernel table (tools/kernel_times.py)."""
+--only bake with --reps 1 is the run to put under rocprofv3 --kernel-trace --stats for the per-kernel table (tools/kernel_times.py).
+
+    python tools/lightmap_bench.py --denoise [--size 1024] [--reps 3] [--out report.json]
+
+times the texel filter (pt_lightmap_denoise, profiles/r23_lightmap_denoise.md) beside the bake it follows: the moments bake against the plain
+bake at 16 samples, the blocking filter call at 1 and at 5 levels (their difference / 4 is a level; what is left of the 1-level call is the
+texel table, the prep and the staging of the map's copies), and the filter's purpose on the tests' 48 x 32 map: RMSE over covered texels of
+the raw and of the denoised mean at 4, 16 and 64 samples against a 4096-sample bake of disjoint samples."""
 import argparse
 import json
 import os
@@ -48,8 +55,48 @@ def torch_rays(torch, table, spp):
     return o, d, key, sample
 
 
+def rmse(a, b, covered):
+    d = (a.astype(np.float64) - b.astype(np.float64))[covered]
+    return float(np.sqrt((d * d).mean()))
+
+
+def denoise_report(r, model, size, reps):
+    spp = 16
+    report = {"size": size, "spp": spp, "bake_ms": [], "bake_moments_ms": [], "filter_1_level_ms": [], "filter_5_levels_ms": [], "filter_5_levels_spatial_ms": []}
+    r.bake_lightmap(model, 0, size, size, 1, bias=BIAS)                          # warm-up, as below
+    sums, sumsq, cov = r.bake_lightmap_moments(model, 0, size, size, 1, bias=BIAS)
+    r.denoise_lightmap(model, 0, sums, 1, sumsq=sumsq, iterations=1)
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        r.bake_lightmap(model, 0, size, size, spp, bias=BIAS)
+        report["bake_ms"].append(1e3 * (time.perf_counter() - t0))
+        t0 = time.perf_counter()
+        sums, sumsq, cov = r.bake_lightmap_moments(model, 0, size, size, spp, bias=BIAS)
+        report["bake_moments_ms"].append(1e3 * (time.perf_counter() - t0))
+        for name, kw in (("filter_1_level_ms", dict(sumsq=sumsq, iterations=1)), ("filter_5_levels_ms", dict(sumsq=sumsq, iterations=5)),
+                         ("filter_5_levels_spatial_ms", dict(iterations=5))):
+            t0 = time.perf_counter()
+            r.denoise_lightmap(model, 0, sums, spp, **kw)                        # blocking
+            report[name].append(1e3 * (time.perf_counter() - t0))
+    report["covered"] = int(cov.sum())
+    report["level_ms"] = (min(report["filter_5_levels_ms"]) - min(report["filter_1_level_ms"])) / 4.0
+    report["table_prep_staging_ms"] = min(report["filter_1_level_ms"]) - report["level_ms"]
+    # the error figures, on the map of tests/test_gpu_lightmap_denoise.py; the reference takes samples 16 .. 4111, the 64-sample bake the 64 after
+    w, h = 48, 32
+    ref, cov = r.bake_lightmap(model, 0, w, h, 4096, first_sample=16, bias=BIAS)
+    ref = ref / np.float32(4096)
+    report["rmse"] = {}
+    for n, first in ((4, 0), (16, 0), (64, 16 + 4096)):
+        sums, sumsq, _ = r.bake_lightmap_moments(model, 0, w, h, n, first_sample=first, bias=BIAS)
+        den = r.denoise_lightmap(model, 0, sums, n, sumsq=sumsq)
+        spatial = r.denoise_lightmap(model, 0, sums, n)
+        report["rmse"][str(n)] = {"raw": rmse(sums / np.float32(n), ref, cov == 1), "denoised": rmse(den, ref, cov == 1), "denoised_spatial_variance": rmse(spatial, ref, cov == 1)}
+    return report
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--denoise", action="store_true")
     ap.add_argument("--size", type=int, default=1024)
     ap.add_argument("--spp", type=int, default=64)
     ap.add_argument("--reps", type=int, default=3)
@@ -65,6 +112,14 @@ def main():
     sc, model = LC.cornell_atlas_scene(args.model, W, H)
     r = api.Renderer(sc, W, H, max_bounces=DEPTH)
     size, spp = args.size, args.spp
+    if args.denoise:
+        line = json.dumps(denoise_report(r, model, size, args.reps))
+        print(line)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                f.write(line + "\n")
+        return
     # warm-up: scene upload, code objects, the wavefront pool at the size the timed calls use
     r.bake_lightmap(model, 0, size, size, 1, bias=BIAS)
     table = r.lightmap_texels(model, 0, size, size, on_device=True)
