@@ -23,6 +23,11 @@
 //                                      same hostile UVs, their texel tables on maps from 1 x 1 up, sides that are no multiple of 16 among them, random
 //                                      positive sums, then the whole filter with 8 levels (step 128 exceeds every map), with and without second
 //                                      moments, under the default reach, a tiny one and one whose square overflows; prints a checksum of the means
+//   host_sanitize screenfilter <seed>  the a-trous core (pt_filter.h: spatial_variance, atrous_level) under the screen rule: random images of 1 x 1,
+//                                      5 x 3, 16 x 16 and 37 x 19 pixels with miss pixels, invalid pixels and two models, the 7 x 7 variance and
+//                                      8 levels (step 128 leaves every map); then the rules' defining property: with one model, every pixel a valid
+//                                      hit and reach2 = +inf the texel rule gives the screen rule's bits (nonzero exit if not); prints a checksum
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -50,6 +55,27 @@ static int light_scene(HostScene& sc)
     const float nrm[18] = {0, -1, 0, 0, -1, 0, 0, -1, 0, 0, -1, 0, 0, -1, 0, 0, -1, 0};
     if (sc.add_model(quad, nrm, 2, m1, kIdentity, 1) < 0) return -1;
     return m0;
+}
+
+// screenfilter's walk: the 7 x 7 variance (pass 0), then k.iterations levels, of prepared images under the rule make(i) builds for centre i
+template <class MakeRule>
+static std::vector<f4> core_filter_host(int w, int h, const DenoiseK& k, std::vector<f4> cv, const f4* pos, const f4* nv, MakeRule make)
+{
+    std::vector<f4> other(cv.size());
+    for (uint32_t pass = 0; pass <= k.iterations; ++pass)
+    {
+        for (int y = 0; y < h; ++y)
+            for (int x = 0; x < w; ++x)
+            {
+                const size_t i = (size_t)y * w + x;
+                const f4 c = cv[i];
+                if (nv[i].w == 0.0f) other[i] = f4{0.0f, 0.0f, 0.0f, 0.0f};
+                else if (pass == 0) other[i] = f4{c.x, c.y, c.z, spatial_variance(make(i), w, h, k, cv.data(), pos, nv, x, y)};
+                else other[i] = atrous_level(make(i), w, h, 1 << (pass - 1), k, cv.data(), pos, nv, x, y);
+            }
+        std::swap(cv, other);
+    }
+    return cv;
 }
 
 int main(int argc, char** argv)
@@ -350,7 +376,7 @@ int main(int argc, char** argv)
             for (int pass = 0; pass < 6; ++pass)
             {
                 const float reach = reaches[pass % 3];
-                const LmFilterK k{4.0f, 1.0f, 7u, 8u, reach * reach};
+                const LmFilterK k{{4.0f, 1.0f, 7u, 8u}, reach * reach};
                 lmf_filter_host(w, h, k, owner.data(), P.data(), N.data(), p.data(), uv.data(), sum.data(), pass < 3 ? sq.data() : nullptr, 16u, mean.data(), area.data());
                 for (size_t k2 = 0; k2 < px; ++k2)
                 {
@@ -361,6 +387,54 @@ int main(int argc, char** argv)
             }
         }
         std::printf("{\"triangles\": %u, \"covered\": %u, \"finite\": %u, \"checksum\": %.6f}\n", n, covered, finite, acc);
+        return 0;
+    }
+    if (cmd == "screenfilter" && argc >= 3)
+    {
+        uint64_t s = 0x9E3779B97F4A7C15ull ^ (uint64_t)std::atoll(argv[2]);
+        auto rnd = [&]() { s ^= s << 13; s ^= s >> 7; s ^= s << 17; return (float)((s >> 40) & 0xffff) / 65535.0f; };
+        const LmFilterK k{{4.0f, 1.0f, 7u, 8u}, INFINITY};
+        const uint32_t sizes[4][2] = {{1, 1}, {5, 3}, {16, 16}, {37, 19}};
+        double acc = 0.0;
+        uint32_t pixels = 0, finite = 0;
+        auto tally = [&](const std::vector<f4>& out) {
+            for (const f4& c : out)
+                for (float v : {c.x, c.y, c.z, c.w})
+                    if (std::isfinite(v)) { acc += v; ++finite; }
+        };
+        for (const uint32_t* wh : sizes)
+        {
+            const int w = (int)wh[0], h = (int)wh[1];
+            const size_t px = (size_t)w * h;
+            pixels += (uint32_t)px;
+            // a floor and a wall under noisy colour; pos.w is the texel rule's area (positive: +inf * area is +inf)
+            std::vector<f4> cv(px), pos(px), nv(px);
+            std::vector<uint32_t> model(px);
+            for (size_t i = 0; i < px; ++i)
+            {
+                const bool wall = rnd() < 0.4f;
+                cv[i] = f4{4.0f * rnd(), 4.0f * rnd(), 4.0f * rnd(), 0.0f};
+                pos[i] = f4{10.0f * rnd(), wall ? 10.0f * rnd() : 0.0f, wall ? 0.0f : 10.0f * rnd(), 0.5f + rnd()};
+                nv[i] = f4{0.2f * rnd() - 0.1f, wall ? 0.0f : 1.0f, wall ? 1.0f : 0.0f, 1.0f};
+                model[i] = rnd() < 0.15f ? (uint32_t)MISS_ID : rnd() < 0.5f ? 0u : 1u;
+            }
+            // the screen rule on what the prep kernel would leave: zeros at an invalid pixel
+            std::vector<f4> cvi = cv, nvi = nv;
+            for (size_t i = 0; i < px; ++i)
+                if (rnd() < 0.1f) cvi[i] = nvi[i] = f4{0.0f, 0.0f, 0.0f, 0.0f};
+            tally(core_filter_host(w, h, k, cvi, pos.data(), nvi.data(), [&](size_t i) { return ScreenRule(nvi.data(), model.data(), i); }));
+            // one model, every pixel a valid hit, no reach: the two rules are one filter
+            std::fill(model.begin(), model.end(), 0u);
+            const std::vector<f4> screen = core_filter_host(w, h, k, cv, pos.data(), nv.data(), [&](size_t i) { return ScreenRule(nv.data(), model.data(), i); });
+            const std::vector<f4> texel = core_filter_host(w, h, k, cv, pos.data(), nv.data(), [&](size_t i) { return TexelRule(k, pos.data(), nv.data(), i); });
+            if (std::memcmp(screen.data(), texel.data(), px * sizeof(f4)) != 0)
+            {
+                std::printf("{\"error\": \"%d x %d: the texel rule without reach differs from the screen rule\"}\n", w, h);
+                return 7;
+            }
+            tally(screen);
+        }
+        std::printf("{\"pixels\": %u, \"finite\": %u, \"checksum\": %.6f}\n", pixels, finite, acc);
         return 0;
     }
     if (cmd == "plan")

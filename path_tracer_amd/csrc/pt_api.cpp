@@ -2732,7 +2732,7 @@ int pt_post_temporal_options(pt_ctx* c, int on_device, uint32_t w, uint32_t h, c
         for (uint32_t y = 0; y < h; ++y)
             for (uint32_t x = 0; x < w; ++x)
                 out_variance[(size_t)y * w + x] =
-                    temporal_variance((int)w, (int)h, cn.data(), mm.data(), im.pos, im.nrm, model, tk.alpha, k.log2_sigma_n, k.sigma_x, (int)x, (int)y);
+                    temporal_variance((int)w, (int)h, k, tk.alpha, cn.data(), mm.data(), im.pos, im.nrm, model, (int)x, (int)y);
         std::memcpy(out_colour_n, cn.data(), px * 16);
         std::memcpy(out_moments2, mm.data(), px * 8);
         return PT_OK;
@@ -3553,7 +3553,7 @@ int pt_lightmap_denoise(pt_ctx* c, int on_device, const pt_lightmap_denoise_para
     for (size_t i = 0; sumsq && i < px; ++i)
         if (!(sumsq[i] >= 0.0f) || !std::isfinite(sumsq[i])) return fail(c, PT_ERR_ARG, "pt_lightmap_denoise: a value of sumsq that is negative or not finite");
     const float reach = p->reach != 0.0f ? p->reach : 2.0f;
-    const LmFilterK k{dk.sigma_l, dk.sigma_x, dk.log2_sigma_n, dk.iterations, reach * reach};
+    const LmFilterK k{dk, reach * reach};
     const HostModel& m = c->scene.models[p->model];
     if (!on_device)
     {

@@ -133,7 +133,7 @@ void launch_lightmap_rays(hipStream_t s, const LightmapBake& lb, uint64_t first,
 void launch_lightmap_fold(hipStream_t s, const LightmapBake& lb, uint64_t first, uint32_t count, const f4* radiance, float* sum, float* sumsq = nullptr);
 // one dilation pass (lm_dilate) of a w x h map from (rgb, cov) to (rgb_out, cov_out)
 void launch_lightmap_dilate(hipStream_t s, uint32_t w, uint32_t h, const float* rgb, const uint8_t* cov, float* rgb_out, uint8_t* cov_out);
-// the texel filter (pt_lightmap_denoise; the per-texel steps are pt_lightmap_filter.h's) of the map of lm: prim, position, normal are
+// the texel filter (pt_lightmap_denoise: pt_filter.h's a-trous core under pt_lightmap_filter.h's texel rule) of the map of lm: prim, position, normal are
 // launch_lightmap_resolve's table, sum (w * h * 3) and sumsq (w * h; read with `moments` only, else the spatial variance) the bake's; cv_a, cv_b,
 // pa, nv: scratch of w * h 16-byte entries each; rgb <- the means (w * h * 3, zeros where uncovered); area (may be null) <- the texel areas
 struct LmFilterK;
@@ -243,13 +243,8 @@ void launch_post_tonemap(hipStream_t s, uint32_t n, const f4* accum, f4* out);
 void launch_post_rgb8(hipStream_t s, uint32_t n, const f4* accum, uint8_t* out);
 void launch_post_deinterleave(hipStream_t s, uint32_t w, uint32_t h, uint32_t world, uint32_t strip, uint32_t pad_rows, const f4* parts, f4* full);
 
-// edge-aware a-trous denoiser (pt_denoise, pt_post_denoise; the definition is include/pt_api.h's), validated by the host
-struct DenoiseK
-{
-    float sigma_l, sigma_x;
-    uint32_t log2_sigma_n; // max(0, n_p . n_q) is squared this many times
-    uint32_t iterations;   // 1..8
-};
+// edge-aware a-trous denoiser (pt_denoise, pt_post_denoise; the definition is include/pt_api.h's, the per-pixel arithmetic and the
+// parameters DenoiseK pt_filter.h's).
 // the filter's images (w x h).  Guides: position xyz | t, normal xyz | -, model (MISS_ID = miss); moments null = spatial variance.  albedo null:
 // pt_denoise / pt_post_denoise.  Else pt_denoise_albedo / pt_post_denoise_albedo: the same filter on the accumulation divided by the albedo
 // (xyz per pixel; albedo_is_sum: the mean-albedo sums, xyz / w), the last level multiplying it back

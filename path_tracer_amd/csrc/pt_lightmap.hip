@@ -7,7 +7,7 @@
 //   k_lm_fold      a thread per (covered texel, channel): the window's radiance added to the texel's sum in sample order; with MOMENTS a
 //                  fourth thread per texel adds l(L) * l(L) to its second moment (pt_bake_lightmap_moments)
 //   k_lm_dilate    a thread per texel: one dilation pass from one buffer pair to the other
-//   k_lmf_*        pt_lightmap_denoise: the per-texel steps of pt_lightmap_filter.h.  One thread per texel; the spatial variance and the levels
+//   k_lmf_*        pt_lightmap_denoise: pt_filter.h's a-trous core under pt_lightmap_filter.h's texel rule.  One thread per texel; the spatial variance and the levels
 //                  in 16 x 16 workgroups, ping-pong.  Gather-bound like k_dn_level: a tap is three 16-byte loads (colour | variance, P | area,
 //                  n | valid), and the valid word decides whether the other two are made
 #include <hip/hip_runtime.h>
@@ -171,7 +171,7 @@ __global__ void __launch_bounds__(256) k_lmf_spatial_var(const int w, const int 
     const size_t i = (size_t)y * w + x;
     if (nv[i].w == 0.0f) { cv_out[i] = f4{0.0f, 0.0f, 0.0f, 0.0f}; return; }
     const f4 c = cv_in[i];
-    cv_out[i] = f4{c.x, c.y, c.z, lmf_spatial_variance(w, h, p, cv_in, pa, nv, x, y)};
+    cv_out[i] = f4{c.x, c.y, c.z, spatial_variance(TexelRule(p, pa, nv, i), w, h, p, cv_in, pa, nv, x, y)};
 }
 
 // FINAL: the last level writes the map's rgb (zeros for an uncovered texel) instead of (c', var')
@@ -183,7 +183,7 @@ __global__ void __launch_bounds__(256) k_lmf_level(const int w, const int h, con
     if (x >= w || y >= h) return;
     const size_t i = (size_t)y * w + x;
     f4 c{0.0f, 0.0f, 0.0f, 0.0f};
-    if (nv[i].w != 0.0f) c = lmf_level(w, h, s, p, cv_in, pa, nv, x, y);
+    if (nv[i].w != 0.0f) c = atrous_level(TexelRule(p, pa, nv, i), w, h, s, p, cv_in, pa, nv, x, y);
     if (FINAL) { rgb[3u * i] = c.x; rgb[3u * i + 1u] = c.y; rgb[3u * i + 2u] = c.z; }
     else cv_out[i] = c;
 }

@@ -1,8 +1,8 @@
 // The texel-space denoiser (pt_lightmap_denoise): pt_denoise's a-trous filter on a lightmap's texel table, with one added tap term, REACH,
-// which keeps charts that are neighbours in UV space and far apart in the world from exchanging light.  The per-texel steps (prep, spatial
-// variance, one level) are written once here for the gfx950 kernels (pt_lightmap.hip) and for the host walk (on_device = 0, the sanitizer
-// driver); the tap terms are pt_filter.h's.  include/pt_api.h states the definition; every operation is rounded once, in this order (the
-// library is built without contraction).
+// which keeps charts that are neighbours in UV space and far apart in the world from exchanging light.  The spatial variance and the level
+// are pt_filter.h's core under the texel rule below; what is the texel filter's own stands here, once for the gfx950 kernels
+// (pt_lightmap.hip) and for the host walk (on_device = 0, the sanitizer driver): the texel area, the reach, the prep.  include/pt_api.h
+// states the definition; every operation is rounded once, in this order (the library is built without contraction).
 //
 // The three images a tap reads, 16 bytes each: cv = colour | variance, pa = P | texel area, nv = n | valid (1 / 0).  Every covered texel is a
 // hit of one model, so pt_denoise's model test has nothing to do here.
@@ -15,15 +15,10 @@
 
 namespace pt {
 
-struct LmFilterK
+struct LmFilterK : DenoiseK
 {
-    float sigma_l, sigma_x;
-    uint32_t log2_sigma_n;
-    uint32_t iterations; // 1..8
-    float reach2;        // reach * reach; may be +inf (the term is off)
+    float reach2; // reach * reach; may be +inf (the term is off)
 };
-
-constexpr float kLmFilterEps = 1e-6f; // pt_denoise's
 
 // TEXEL AREA: the world area one texel of a w x h map covers on the triangle with object-space positions p9 and UVs uv
 PT_HD float lm_texel_area(const float p9[9], const float uv[6], uint32_t w, uint32_t h)
@@ -35,15 +30,23 @@ PT_HD float lm_texel_area(const float p9[9], const float uv[6], uint32_t w, uint
     return A3 / ((A2 * (float)w) * (float)h);
 }
 
-// squared world distance of two texels: the plane term's d2
-PT_HD float lmf_d2(f4 xp, f4 xq)
+// REACH of the tap at texel offset (ox, oy) != (0, 0): the squared world distance of the two texels (the plane term's d2) against
+// lim = (reach * reach) * area_p.  Written this way round: a NaN on the right rejects the tap, +inf accepts it
+PT_HD bool lmf_reach(float lim, f4 xp, f4 xq, int ox, int oy)
 {
     const float dx = xq.x - xp.x, dy = xq.y - xp.y, dz = xq.z - xp.z;
-    return (dx * dx + dy * dy) + dz * dz;
+    return (dx * dx + dy * dy) + dz * dz <= lim * (float)(ox * ox + oy * oy);
 }
-// REACH of the tap at texel offset (ox, oy) != (0, 0); lim = (reach * reach) * area_p.  Written this way round: a NaN on the right rejects
-// the tap, +inf accepts it
-PT_HD bool lmf_reach(float lim, f4 xp, f4 xq, int ox, int oy) { return lmf_d2(xp, xq) <= lim * (float)(ox * ox + oy * oy); }
+// the texel filter's neighbour rule (pt_filter.h): a covered texel (nv.w != 0) within reach of the centre p; every centre is a hit
+struct TexelRule
+{
+    const f4 *nv, *pa;
+    f4 xp;
+    float lim;
+    PT_HD TexelRule(const LmFilterK& k, const f4* pa_, const f4* nv_, size_t p) : nv(nv_), pa(pa_), xp(pa_[p]), lim(k.reach2 * pa_[p].w) {}
+    PT_HD bool neighbour(size_t q, int ox, int oy, f4& nq) const { nq = nv[q]; return nq.w != 0.0f && lmf_reach(lim, xp, pa[q], ox, oy); }
+    PT_HD bool geometry() const { return true; }
+};
 
 // the three images' entries of texel k from the texel table (prim, P, n: pt_lightmap_texels'), the model's load-order positions and UVs and
 // the sums; n = (float)n_samples; sumsq null: variance 0, the spatial pass fills it in
@@ -59,117 +62,13 @@ PT_HD void lmf_prep(uint32_t k, uint32_t w, uint32_t h, const uint32_t* prim, co
         return;
     }
     const f4 a{sum[3u * (size_t)k], sum[3u * (size_t)k + 1u], sum[3u * (size_t)k + 2u], n};
-    float var = 0.0f;
-    if (sumsq)
-    {
-        const float m = lum(a) / a.w;
-        float v = sumsq[k] / a.w - m * m;
-        if (!(v > 0.0f)) v = 0.0f;
-        var = v / a.w;
-    }
+    const float var = sumsq ? mean_variance(a, sumsq[k]) : 0.0f;
     float p9[9], uv[6];
     for (int q = 0; q < 9; ++q) p9[q] = positions9[9u * (size_t)t + q];
     for (int q = 0; q < 6; ++q) uv[q] = uvs6[6u * (size_t)t + q];
     cv[k] = f4{a.x / a.w, a.y / a.w, a.z / a.w, var};
     pa[k] = f4{position[3u * (size_t)k], position[3u * (size_t)k + 1u], position[3u * (size_t)k + 2u], lm_texel_area(p9, uv, w, h)};
     nv[k] = f4{normal[3u * (size_t)k], normal[3u * (size_t)k + 1u], normal[3u * (size_t)k + 2u], 1.0f};
-}
-
-// pt_filter.h's spatial_variance of a covered texel (x, y) with the reach test on every neighbour
-PT_HD float lmf_spatial_variance(int w, int h, const LmFilterK& p, const f4* cv, const f4* pa, const f4* nv, int x, int y)
-{
-    const size_t i = (size_t)y * w + x;
-    const f4 np = nv[i], xp = pa[i];
-    const float lim = p.reach2 * xp.w;
-    float sw = 0.0f, sl = 0.0f, sll = 0.0f;
-    for (int dy = -3; dy <= 3; ++dy)
-    {
-        const int yy = y + dy;
-        if (yy < 0 || yy >= h) continue;
-        for (int dx = -3; dx <= 3; ++dx)
-        {
-            const int xx = x + dx;
-            if (xx < 0 || xx >= w) continue;
-            const size_t q = (size_t)yy * w + xx;
-            float wt = 1.0f;
-            if (dx != 0 || dy != 0)
-            {
-                const f4 nq = nv[q];
-                if (nq.w == 0.0f) continue;
-                const f4 xq = pa[q];
-                if (!lmf_reach(lim, xp, xq, dx, dy)) continue;
-                wt = normal_w(np, nq, p.log2_sigma_n) * exp_det(-plane(np, xp, xq, p.sigma_x));
-            }
-            const float l = lum(cv[q]);
-            sw = sw + wt;
-            sl = sl + wt * l;
-            sll = sll + wt * (l * l);
-        }
-    }
-    const float mu = sl / sw;
-    float v = sll / sw - mu * mu;
-    if (!(v > 0.0f)) v = 0.0f;
-    return v;
-}
-
-// one a-trous level, step s, of a covered texel (x, y): (c', var') as pt_denoise's level, a neighbour being a covered texel inside the map
-// that passes the reach test
-PT_HD f4 lmf_level(int w, int h, int s, const LmFilterK& p, const f4* cv, const f4* pa, const f4* nv, int x, int y)
-{
-    const size_t i = (size_t)y * w + x;
-    const f4 cp = cv[i], np = nv[i], xp = pa[i];
-    const float lim = p.reach2 * xp.w;
-    const float kb[3] = {0.25f, 0.5f, 0.25f};
-    float sg = 0.0f, sk = 0.0f;
-    for (int dy = -1; dy <= 1; ++dy)
-    {
-        const int yy = y + dy;
-        if (yy < 0 || yy >= h) continue;
-        for (int dx = -1; dx <= 1; ++dx)
-        {
-            const int xx = x + dx;
-            if (xx < 0 || xx >= w) continue;
-            const size_t q = (size_t)yy * w + xx;
-            if ((dx != 0 || dy != 0) && (nv[q].w == 0.0f || !lmf_reach(lim, xp, pa[q], dx, dy))) continue;
-            const float k = kb[dx + 1] * kb[dy + 1];
-            sg = sg + k * cv[q].w;
-            sk = sk + k;
-        }
-    }
-    const float g = sg / sk;
-    const float inv = 1.0f / (p.sigma_l * sqrtf(g) + kLmFilterEps);
-    const float lp = lum(cp);
-    const float hk[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
-    float sw = 0.0f, sr = 0.0f, sgc = 0.0f, sb = 0.0f, sv = 0.0f;
-    for (int dy = -2; dy <= 2; ++dy)
-    {
-        const int yy = y + s * dy;
-        if (yy < 0 || yy >= h) continue;
-        for (int dx = -2; dx <= 2; ++dx)
-        {
-            const int xx = x + s * dx;
-            if (xx < 0 || xx >= w) continue;
-            const size_t q = (size_t)yy * w + xx;
-            float e = 1.0f;
-            if (dx != 0 || dy != 0)
-            {
-                const f4 nq = nv[q];
-                if (nq.w == 0.0f) continue;
-                const f4 xq = pa[q];
-                if (!lmf_reach(lim, xp, xq, s * dx, s * dy)) continue;
-                const float al = fabsf(lp - lum(cv[q])) * inv;
-                e = normal_w(np, nq, p.log2_sigma_n) * exp_det(-(plane(np, xp, xq, p.sigma_x) + al));
-            }
-            const f4 cq = cv[q];
-            const float wt = (hk[dx + 2] * hk[dy + 2]) * e;
-            sw = sw + wt;
-            sr = sr + wt * cq.x;
-            sgc = sgc + wt * cq.y;
-            sb = sb + wt * cq.z;
-            sv = sv + (wt * wt) * cq.w;
-        }
-    }
-    return f4{sr / sw, sgc / sw, sb / sw, sv / (sw * sw)};
 }
 
 // The whole filter on the host: the walk on_device = 0 does.  prim, position, normal: the texel table; positions9, uvs6: the model's
@@ -191,7 +90,7 @@ inline void lmf_filter_host(uint32_t w, uint32_t h, const LmFilterK& p, const ui
             {
                 const size_t i = (size_t)y * w + x;
                 const f4 c = cv[i];
-                other[i] = nv[i].w == 0.0f ? f4{0.0f, 0.0f, 0.0f, 0.0f} : f4{c.x, c.y, c.z, lmf_spatial_variance(iw, ih, p, cv.data(), pa.data(), nv.data(), x, y)};
+                other[i] = nv[i].w == 0.0f ? f4{0.0f, 0.0f, 0.0f, 0.0f} : f4{c.x, c.y, c.z, spatial_variance(TexelRule(p, pa.data(), nv.data(), i), iw, ih, p, cv.data(), pa.data(), nv.data(), x, y)};
             }
         std::swap(cv, other);
     }
@@ -201,7 +100,7 @@ inline void lmf_filter_host(uint32_t w, uint32_t h, const LmFilterK& p, const ui
             for (int x = 0; x < iw; ++x)
             {
                 const size_t i = (size_t)y * w + x;
-                other[i] = nv[i].w == 0.0f ? f4{0.0f, 0.0f, 0.0f, 0.0f} : lmf_level(iw, ih, 1 << it, p, cv.data(), pa.data(), nv.data(), x, y);
+                other[i] = nv[i].w == 0.0f ? f4{0.0f, 0.0f, 0.0f, 0.0f} : atrous_level(TexelRule(p, pa.data(), nv.data(), i), iw, ih, 1 << it, p, cv.data(), pa.data(), nv.data(), x, y);
             }
         std::swap(cv, other);
     }

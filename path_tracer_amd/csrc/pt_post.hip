@@ -268,9 +268,8 @@ __global__ void __launch_bounds__(256) k_post_deinterleave(uint32_t w, uint32_t 
 }
 
 // ---- edge-aware a-trous denoiser (pt_denoise / pt_post_denoise): SVGF's spatial filter, every operation in the order include/pt_api.h
-// states.  One thread per pixel in 16 x 16 workgroups; what a tap reads is three 16-byte loads (colour | variance, position | t,
-// normal | valid) and the model word.  Per-pixel divisors are hoisted out of the tap loops; one exp_det per tap.
-constexpr float kDenoiseEps = 1e-6f;
+// states.  The per-pixel arithmetic is pt_filter.h's core under the screen rule; the kernels are its shells.  One thread per pixel in
+// 16 x 16 workgroups; what a tap reads is three 16-byte loads (colour | variance, position | t, normal | valid) and the model word.
 
 // the prep kernel's albedo: none (pt_denoise), the albedo image (pt_denoise_albedo's guide, a caller's image) or the mean-albedo sums S (A = S.rgb / S.w)
 enum class AlbedoFrom { None, Image, Sums };
@@ -319,10 +318,7 @@ __global__ void __launch_bounds__(256) k_dn_prep(uint32_t n, const f4* __restric
     float var = 0.0f;
     if (moments)
     {
-        const float m = lum(a) / a.w;
-        float v = moments[i] / a.w - m * m;
-        if (!(v > 0.0f)) v = 0.0f;
-        var = v / a.w;
+        var = mean_variance(a, moments[i]);
         if constexpr (ALBEDO)
         {
             const float lc = lum(f4{a.x / a.w, a.y / a.w, a.z / a.w, 0.0f});
@@ -345,12 +341,12 @@ __global__ void __launch_bounds__(256) k_dn_spatial_var(int w, int h, const Deno
     const size_t i = (size_t)y * w + x;
     const f4 cp = cv_in[i], np = nv[i];
     if (np.w == 0.0f) { cv_out[i] = f4{0.0f, 0.0f, 0.0f, 0.0f}; return; }
-    cv_out[i] = f4{cp.x, cp.y, cp.z, spatial_variance<true>(w, h, cv_in, pos, nv, model, p.log2_sigma_n, p.sigma_x, x, y, np)};
+    cv_out[i] = f4{cp.x, cp.y, cp.z, spatial_variance(ScreenRule(nv, model, i), w, h, p, cv_in, pos, nv, x, y)};
 }
 
-// one a-trous level, step s: g = 3 x 3 binomial blur of the variance, then the 5 x 5 B3-spline taps p + s (dx, dy) with edge-stopping weights.
-// FINAL writes the result (c', 1) / (0, 0, 0, 0) instead of (c', var'); REMOD (pt_denoise_albedo's last level, FINAL) multiplies that result
-// by the divisor k the prep kernel kept in kmul, per channel (kmul is not read otherwise)
+// one a-trous level, step s (pt_filter.h's atrous_level).  FINAL writes the result (c', 1) / (0, 0, 0, 0) instead of (c', var'); REMOD
+// (pt_denoise_albedo's last level, FINAL) multiplies that result by the divisor k the prep kernel kept in kmul, per channel (kmul is not
+// read otherwise)
 template <bool FINAL, bool REMOD = false>
 __global__ void __launch_bounds__(256) k_dn_level(int w, int h, int s, const DenoiseK p, const f4* __restrict__ cv_in, const f4* __restrict__ pos,
                                                   const f4* __restrict__ nv, const uint32_t* __restrict__ model, f4* __restrict__ cv_out,
@@ -359,68 +355,15 @@ __global__ void __launch_bounds__(256) k_dn_level(int w, int h, int s, const Den
     const int x = blockIdx.x * 16 + threadIdx.x, y = blockIdx.y * 16 + threadIdx.y;
     if (x >= w || y >= h) return;
     const size_t i = (size_t)y * w + x;
-    const f4 cp = cv_in[i], np = nv[i];
-    if (np.w == 0.0f) { cv_out[i] = f4{0.0f, 0.0f, 0.0f, 0.0f}; return; }
-    const uint32_t mp = model[i];
-    const bool hit = mp != MISS_ID;
-    const f4 xp = pos[i];
-    const float kb[3] = {0.25f, 0.5f, 0.25f};
-    float sg = 0.0f, sk = 0.0f;
-    for (int dy = -1; dy <= 1; ++dy)
-    {
-        const int yy = y + dy;
-        if (yy < 0 || yy >= h) continue;
-        for (int dx = -1; dx <= 1; ++dx)
-        {
-            const int xx = x + dx;
-            if (xx < 0 || xx >= w) continue;
-            const size_t q = (size_t)yy * w + xx;
-            if ((dx != 0 || dy != 0) && (nv[q].w == 0.0f || model[q] != mp)) continue;
-            const float k = kb[dx + 1] * kb[dy + 1];
-            sg = sg + k * cv_in[q].w;
-            sk = sk + k;
-        }
-    }
-    const float g = sg / sk;
-    const float inv = 1.0f / (p.sigma_l * sqrtf(g) + kDenoiseEps);
-    const float lp = lum(cp);
-    const float hk[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
-    float sw = 0.0f, sr = 0.0f, sgc = 0.0f, sb = 0.0f, sv = 0.0f;
-    for (int dy = -2; dy <= 2; ++dy)
-    {
-        const int yy = y + s * dy;
-        if (yy < 0 || yy >= h) continue;
-        for (int dx = -2; dx <= 2; ++dx)
-        {
-            const int xx = x + s * dx;
-            if (xx < 0 || xx >= w) continue;
-            const size_t q = (size_t)yy * w + xx;
-            const f4 cq = cv_in[q];
-            float e = 1.0f;
-            if (dx != 0 || dy != 0)
-            {
-                const f4 nq = nv[q];
-                if (nq.w == 0.0f || model[q] != mp) continue;
-                const float al = fabsf(lp - lum(cq)) * inv;
-                if (hit) e = normal_w(np, nq, p.log2_sigma_n) * exp_det(-(plane(np, xp, pos[q], p.sigma_x) + al));
-                else e = exp_det(-al);
-            }
-            const float wt = (hk[dx + 2] * hk[dy + 2]) * e;
-            sw = sw + wt;
-            sr = sr + wt * cq.x;
-            sgc = sgc + wt * cq.y;
-            sb = sb + wt * cq.z;
-            sv = sv + (wt * wt) * cq.w;
-        }
-    }
-    const f4 c{sr / sw, sgc / sw, sb / sw, 0.0f};
+    if (nv[i].w == 0.0f) { cv_out[i] = f4{0.0f, 0.0f, 0.0f, 0.0f}; return; }
+    const f4 c = atrous_level(ScreenRule(nv, model, i), w, h, s, p, cv_in, pos, nv, x, y);
     static_assert(FINAL || !REMOD, "");
     if (REMOD)
     {
         const f4 k = kmul[i];
         cv_out[i] = f4{c.x * k.x, c.y * k.y, c.z * k.z, 1.0f};
     }
-    else cv_out[i] = FINAL ? f4{c.x, c.y, c.z, 1.0f} : f4{c.x, c.y, c.z, sv / (sw * sw)};
+    else cv_out[i] = FINAL ? f4{c.x, c.y, c.z, 1.0f} : c;
 }
 
 // ---- temporal stage (pt_frame_temporal / pt_post_temporal): the per-pixel steps are pt_temporal.h's, shared with the host path.  One thread
@@ -466,7 +409,7 @@ __global__ void __launch_bounds__(256) k_tp_variance(int w, int h, const Denoise
     const int x = blockIdx.x * 16 + threadIdx.x, y = blockIdx.y * 16 + threadIdx.y;
     if (x >= w || y >= h) return;
     const size_t i = (size_t)y * w + x;
-    const float v = temporal_variance(w, h, cn, mom, pos, nrm, model, alpha, p.log2_sigma_n, p.sigma_x, x, y);
+    const float v = temporal_variance(w, h, p, alpha, cn, mom, pos, nrm, model, x, y);
     var[i] = v;
     if (cv)
     {

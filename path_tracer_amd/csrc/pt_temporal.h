@@ -218,8 +218,8 @@ auto with_temporal_options(bool rescue, bool mean_length, Fn&& f)
 
 // step 5 for pixel (x, y): the variance handed to the levels.  cn = this call's C | N, mom its moments.  From kTemporalMomentsN on the
 // moments answer at once; only younger pixels walk pt_denoise's 7 x 7 spatial variance of C under the current guides (every pixel valid).
-PT_HD float temporal_variance(int w, int h, const f4* cn, const f2* mom, const f4* pos, const f4* nrm, const uint32_t* model, float alpha, uint32_t log2_sn,
-                              float sigma_x, int x, int y)
+PT_HD float temporal_variance(int w, int h, const DenoiseK& p, float alpha, const f4* cn, const f2* mom, const f4* pos, const f4* nrm, const uint32_t* model,
+                              int x, int y)
 {
     const size_t i = (size_t)y * w + x;
     const f4 cp = cn[i];
@@ -231,7 +231,7 @@ PT_HD float temporal_variance(int w, int h, const f4* cn, const f2* mom, const f
         const float rn = 1.0f / cp.w;
         return v * (alpha > rn ? alpha : rn);
     }
-    return spatial_variance<false>(w, h, cn, pos, nrm, model, log2_sn, sigma_x, x, y, nrm[i]);
+    return spatial_variance(ScreenAllValidRule(nrm, model, i), w, h, p, cn, pos, nrm, x, y);
 }
 
 } // namespace pt
