@@ -33,6 +33,10 @@
 //   examples/headless ... --bake-lightmap ... --baked-view SPP out.png   sets the dilated map it just baked, sum / its SPP, on the shell
 //       (pt_set_lightmap) and writes the baked view (pt_render_baked: SPP samples per pixel, chains followed --follow K hops, unmapped
 //       surfaces black)
+//   examples/headless ... --probe-grid NX NY NZ SPP --baked-view SPP out.png   alone or beside --bake-lightmap: bakes an NX x NY x NZ irradiance volume
+//       spanning the scene's bounds inset by half a cell (SPP samples per probe; probes that see back faces in more than a quarter of their rays
+//       are left out: pt_probe_backfaces), sets it (pt_set_probe_grid) and writes the baked view, in which the grid lights every final surface
+//       that no map lights
 //   examples/headless ... --bake-lightmap ... --lightmap-denoise [--baked-view ...]   bakes with second moments (pt_bake_lightmap_moments), runs the
 //       texel-space filter on the sums (pt_lightmap_denoise, default parameters) and dilates its texel MEANS: map.txt then holds means, not sums,
 //       and --baked-view sets them as they are
@@ -75,6 +79,7 @@ int main(int argc, char** argv)
     uint32_t lightmap[4] = {0, 0, 0, 0}; // W H SPP PASSES
     std::string lightmap_out = "";
     uint32_t baked_spp = 0;
+    uint32_t probe_grid[4] = {0, 0, 0, 0}; // --probe-grid NX NY NZ SPP
     bool lightmap_denoise = false;
     std::string baked_out = "";
     pt_projection projection{}; // PT_PROJ_PERSPECTIVE
@@ -130,6 +135,10 @@ int main(int argc, char** argv)
             for (uint32_t& n : lightmap) n = (uint32_t)std::atoi(next("--bake-lightmap"));
             lightmap_out = next("--bake-lightmap");
         }
+        else if (a == "--probe-grid")
+        {
+            for (uint32_t& n : probe_grid) n = (uint32_t)std::atoi(next("--probe-grid"));
+        }
         else if (a == "--baked-view")
         {
             baked_spp = (uint32_t)std::atoi(next("--baked-view"));
@@ -145,14 +154,20 @@ int main(int argc, char** argv)
         }
         else if (a == "--help" || a == "-h")
         {
-            std::printf("usage: %s [--width W] [--height H] [--frames N] [--bounces B] [--move] [--slide DX DZ] [--models DIR] [--out file.png] [--temporal file.png [--temporal-rescue] [--temporal-mean-length] [--temporal-demodulate]] [--denoise file.png] [--denoise-albedo file.png] [--follow K] [--mirror-glass] [--aperture A --focus F] [--projection panorama[:SX:SY]|ortho:HEIGHT] [--bake-probes NX NY NZ SPP file.txt] [--bake-lightmap W H SPP PASSES file.txt [--lightmap-denoise] [--baked-view SPP file.png]] [--checker N] [--emission-checker N] [--normal-ripples N]\n", argv[0]);
+            std::printf("usage: %s [--width W] [--height H] [--frames N] [--bounces B] [--move] [--slide DX DZ] [--models DIR] [--out file.png] [--temporal file.png [--temporal-rescue] [--temporal-mean-length] [--temporal-demodulate]] [--denoise file.png] [--denoise-albedo file.png] [--follow K] [--mirror-glass] [--aperture A --focus F] [--projection panorama[:SX:SY]|ortho:HEIGHT] [--bake-probes NX NY NZ SPP file.txt] [--bake-lightmap W H SPP PASSES file.txt [--lightmap-denoise] [--baked-view SPP file.png]] [--probe-grid NX NY NZ SPP --baked-view SPP file.png] [--checker N] [--emission-checker N] [--normal-ripples N]\n", argv[0]);
             return 0;
         }
         else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
     }
-    if (!baked_out.empty() && (lightmap_out.empty() || !lightmap[2] || !baked_spp))
+    const bool with_grid = probe_grid[0] && probe_grid[1] && probe_grid[2] && probe_grid[3];
+    if (!baked_out.empty() && (((lightmap_out.empty() || !lightmap[2]) && !with_grid) || !baked_spp))
     {
-        std::fprintf(stderr, "--baked-view shows the map --bake-lightmap bakes: it needs that option, and samples for both\n");
+        std::fprintf(stderr, "--baked-view shows the map --bake-lightmap bakes or the volume --probe-grid bakes: it needs one of them, and samples for both\n");
+        return 2;
+    }
+    if ((probe_grid[0] || probe_grid[1] || probe_grid[2] || probe_grid[3]) && (!with_grid || baked_out.empty()))
+    {
+        std::fprintf(stderr, "--probe-grid NX NY NZ SPP takes four non-zero numbers and lights --baked-view\n");
         return 2;
     }
     if (lightmap_denoise && (lightmap_out.empty() || !lightmap[2]))
@@ -317,13 +332,30 @@ int main(int argc, char** argv)
             for (size_t k = 0; k < cov.size(); ++k) std::fprintf(f, "%u %a %a %a\n", (unsigned)cov[k], (double)sums[3 * k], (double)sums[3 * k + 1], (double)sums[3 * k + 2]);
             std::fclose(f);
             if (baked_out.empty()) return true;
-            // ... and its consumer: the map's texel means on the shell, the followed first hits shaded from it
+            // ... and its consumer: the map's texel means on the shell (baked_view shades the followed first hits from it)
             if (!lightmap_denoise)
                 for (float& s : sums) s = s / (float)lightmap[2];
             renderer.set_lightmap(1, 0, lightmap[0], lightmap[1], sums);
+            return true;
+        };
+        // the baked view, after bake_lightmap: under --probe-grid an irradiance volume over the scene's bounds inset by half a cell lights
+        // what the map (if any) does not
+        auto baked_view = [&]() {
+            if (baked_out.empty()) return;
+            if (with_grid)
+            {
+                const std::array<float, 6> box = renderer.root_box();
+                pt_probe_grid g{};
+                for (int k = 0; k < 3; ++k)
+                {
+                    g.count[k] = probe_grid[k];
+                    g.cell[k] = (box[3 + k] - box[k]) / (float)probe_grid[k];
+                    g.origin[k] = box[k] + 0.5f * g.cell[k];
+                }
+                renderer.bake_probe_grid(g, probe_grid[3]);
+            }
             renderer.render_baked(0, baked_spp, follow);
             renderer.write_baked_image(baked_out);
-            return true;
         };
         // the demodulated denoiser on samples [first, first + count) of the frame: guides of the last sample, the mean albedo of all of them
         auto denoise_albedo = [&](uint32_t first, uint32_t count) {
@@ -363,7 +395,9 @@ int main(int argc, char** argv)
             std::printf("{\"first_sample\": %u, \"samples\": %u, \"width\": %u, \"height\": %u}\n", render_first, render_count, width, height);
             if (!out.empty()) renderer.write_image(out);
             if (!denoise_albedo_out.empty() && render_count) denoise_albedo(render_first, render_count);
-            return bake_probes() && bake_lightmap() ? 0 : 1;
+            if (!bake_probes() || !bake_lightmap()) return 1;
+            baked_view();
+            return 0;
         }
         Mat4 last_inv_proj = renderer.inv_projection();
 
@@ -405,6 +439,7 @@ int main(int argc, char** argv)
         }
         if (!denoise_albedo_out.empty() && frames) denoise_albedo(0, frames);
         if (!bake_probes() || !bake_lightmap()) return 1;
+        baked_view();
     }
     catch (const Error& e)
     {

@@ -830,7 +830,8 @@ int pt_integrate_rays_device(pt_ctx* ctx, uint64_t n, const float* o_xyz, const 
  * pt_config.batch_spp, a render's test knob, cuts here too: wavefront batches of batch_spp * n_probes rays.  The frame is not touched.
  * Errors, before any device call: PT_ERR_STATE as pt_integrate_rays; PT_ERR_ARG for a NULL position_xyz, p or sh27 with n_probes > 0,
  * n_samples == 0, a non-zero reserved word, a position that is not finite, key_base + n_probes or first_sample + n_samples beyond 2^32.
- * Out of scope: higher bands, cosine-convolved output, visibility or depth moments, probe placement. */
+ * Out of scope: higher bands, cosine-convolved output, visibility or depth moments, probe placement.  (pt_set_probe_grid keeps a grid of
+ * such probes, scaled by the caller, and applies the cosine lobe in its lookup; pt_probe_backfaces tells which probes sit inside geometry.) */
 typedef struct pt_probe_params
 {
     uint32_t first_sample, n_samples; /* samples [first_sample, first_sample + n_samples) of every probe */
@@ -1014,7 +1015,8 @@ int pt_lightmap_lookup(pt_ctx* ctx, int on_device, uint32_t n, const uint32_t* i
  * Errors, all before any device call: PT_ERR_ARG for what pt_guide_params refuses, an unlit that is negative or not finite, n_samples == 0 or
  * a range beyond 2^32; PT_ERR_STATE as pt_render_guides; pt_read_baked and pt_write_baked_image PT_ERR_STATE without current sums.  A scene
  * with no map at all is legal.
- * Out of scope: pt_multi_* variants, directional maps, probes as the fallback of unmapped surfaces, a specular response on GGX surfaces,
+ * With a probe grid set (pt_set_probe_grid, below) the third ending reads the grid instead of unlit wherever the grid lights the point.
+ * Out of scope: pt_multi_* variants, directional maps, a specular response on GGX surfaces,
  * perturbed normals, ending the path tracer's own paths in the maps.  (The maps themselves are filtered before they are set:
  * pt_lightmap_denoise, which knows the coverage, then pt_lightmap_dilate.) */
 typedef struct pt_baked_params
@@ -1027,6 +1029,68 @@ int pt_render_baked(pt_ctx* ctx, uint32_t first_sample, uint32_t n_samples, cons
 int pt_read_baked(pt_ctx* ctx, float* rgbn);
 int pt_reset_baked(pt_ctx* ctx);
 int pt_write_baked_image(pt_ctx* ctx, const char* path);
+
+/* ---- the irradiance volume: a regular grid of SH9 probes that lights what no lightmap lights --------------------------------------------- */
+/* pt_set_probe_grid gives the context a grid of nx * ny * nz probes in WORLD space: node (ix, iy, iz) stands at origin + (ix, iy, iz) * cell
+ * and has index (iz * ny + iy) * nx + ix.  sh27 holds 9 x 3 floats per node, coefficient-major and channel-minor as pt_bake_probes writes
+ * them; the values are the RADIANCE SH coefficients L_m, i.e. the bake's raw sums times 4 pi / n_samples (the multiplication is the caller's,
+ * as the division is for pt_set_lightmap).  Negative coefficients are legal.  valid (may be NULL: all valid) holds a byte per node, non-zero:
+ * usable; an invalid node's coefficients are checked and then not kept.  sh27 NULL with all three counts 0 clears the grid (valid and the
+ * other fields of g are then not read, except reserved); pt_get_probe_grid_info reports counts of 0 where there is none and the number of
+ * valid nodes in n_valid (either output may be NULL).
+ * The call neither un-builds the scene nor touches the flattened scene: pt_scene_info does not move and a pt_render launches what it launched
+ * before.  The grid is world-space data: it survives pt_build, pt_set_instances, pt_set_model_uvs and pt_set_lightmap.  It lives on the device
+ * as seven 16-byte words per node (27 coefficients and the valid word), uploaded by the next call that needs it; a context that never sets a
+ * grid allocates and launches nothing for it.  Clearing the grid launches nothing more for it either, but the device table's memory is kept
+ * for the next grid and released with the context.
+ * Errors, all before any device call (a refused call changes nothing).  Where several apply, the first in this order is reported: a NULL g
+ * (ARG); a non-zero reserved word (ARG); sh27 NULL with a non-zero count, or sh27 with a count of 0 (ARG); a count above 256 (PT_ERR_LIMIT);
+ * an origin, cell or normal_bias that is not finite, a cell that is not > 0, a negative normal_bias (ARG); then the coefficients, which are
+ * read last: one that is not finite (ARG).  A grid that does not fit in host memory is PT_ERR_LIMIT.
+ * THE LOOKUP at world position P with unit normal n.  Binary32, one rounding per operation, no contraction, in this order:
+ *     P'_a = P_a + normal_bias * n_a                                                                  a = x, y, z
+ *     g_a  = (P'_a - origin_a) / cell_a
+ *     g_a  = !(g_a > 0) ? 0 : (g_a > (float)(n_a - 1) ? (float)(n_a - 1) : g_a)                       -- clamp to the grid; a NaN gives 0
+ *     i0_a = (uint32_t)g_a;  f_a = g_a - truncf(g_a);  i1_a = i0_a + 1 < n_a ? i0_a + 1 : i0_a
+ *     y = y0..y8 of n as pt_bake_probes states them;  yc_m = a_m * y_m,  a = 1 (m = 0), 0.6666667f (m = 1..3), 0.25f (m = 4..8)
+ *                                             -- the cosine lobe over pi: the result is in the lightmap's unit and no pi appears
+ *     corner k = 0..7 (bit 0: x1, bit 1: y1, bit 2: z1; a clear bit: the 0 index):
+ *         w_k   = ((wx * wy) * wz) * (valid ? 1.0f : 0.0f),   wx = bit 0 ? f_x : 1 - f_x, wy and wz alike
+ *         e_k,c = (((yc_0 * L_0,c + yc_1 * L_1,c) + yc_2 * L_2,c) + ... ) + yc_8 * L_8,c               -- the corner EVALUATED, then blended
+ *     W   = ((w_0 + w_1) + ...) + w_7
+ *     E_c = ((w_0 * e_0,c + w_1 * e_1,c) + ...) + w_7 * e_7,c
+ *     lit = W > 0;   I_c = E_c / W;   I_c = !(I_c > 0) ? 0 : I_c                                     -- SH ringing may go negative: clamp
+ *   At a valid node's own position with normal_bias 0 the result is max(e_node, 0) bit for bit (f = 0 on every axis, W = 1 and every other
+ *   product is a zero), and a 1 x 1 x 1 grid returns its one probe's evaluation everywhere.  Where lit is false I is (0, 0, 0).
+ * pt_probe_grid_lookup is its unit hook: n queries (host pointers; position_xyz and normal_xyz 3 floats each, any values), rgb 3 floats and
+ * lit a byte per query.  on_device = 0 evaluates on the host and touches no GPU, 1 runs a kernel over the same function.  PT_ERR_STATE
+ * without a grid, PT_ERR_ARG for a NULL pointer with n > 0.
+ * THE BAKED VIEW WITH A GRID.  While a grid is set, the third ending of pt_render_baked's table (any kind but PT_EMISSIVE, with no map or on
+ * a back face) becomes
+ *     l = lit ? I : unlit;   B = R_H * l,   the lookup at P = the position and n = the normal that pt_render_guides_followed writes for that
+ *     chain's end (the unperturbed normal on the side the ray came from)
+ * and every other ending is what it was: a mapped front face is lit by its map.  The ending is a kernel of its own, chosen on the host, so
+ * without a grid every call returns the bits it returned before.  The baked sums go stale on pt_set_probe_grid as on pt_set_lightmap.
+ * Out of scope: visibility or depth moments, cell-skipping and probe relocation, probes in the path tracer's own paths, a specular response,
+ * pt_multi_* variants, SH above band 2. */
+typedef struct pt_probe_grid
+{
+    float origin[3];      /* position of node (0, 0, 0); finite */
+    float cell[3];        /* node spacing per axis; finite, > 0 */
+    uint32_t count[3];    /* nx, ny, nz: each 1..256 */
+    float normal_bias;    /* the lookup moves P by this much along n first; finite, >= 0 */
+    uint32_t reserved[4]; /* must be 0 */
+} pt_probe_grid;
+int pt_set_probe_grid(pt_ctx* ctx, const pt_probe_grid* g, const float* sh27, const uint8_t* valid);
+int pt_get_probe_grid_info(pt_ctx* ctx, pt_probe_grid* out, uint32_t* n_valid);
+int pt_probe_grid_lookup(pt_ctx* ctx, int on_device, uint32_t n, const float* position_xyz, const float* normal_xyz, float* rgb, uint8_t* lit);
+/* WHICH PROBES SIT INSIDE GEOMETRY.  For probe j and every sample s of [first_sample, first_sample + n_samples) the ray from position_xyz[j]
+ * in the direction of pt_probe_ray(key_base + j, s), the ray pt_bake_probes casts, is traced ONCE for its closest hit in the world TLAS:
+ * hits[j] counts the rays that hit anything, back[j] those whose hit is a back face (the front flag of the unperturbed interpolated normal,
+ * the one the guides use, is false).  The counts are integers and do not depend on how the rays are cut into launches: one wave per probe,
+ * a wave reduction, no atomics (pt_config.batch_spp, a render's test knob, cuts the ray table here as in the bake).  What fraction of back faces makes a probe unusable is the caller's policy.  The frame is not touched.
+ * Errors, before any device call: those of pt_bake_probes, with hits and back in sh27's place. */
+int pt_probe_backfaces(pt_ctx* ctx, uint32_t n_probes, const float* position_xyz, const pt_probe_params* p, uint32_t* hits, uint32_t* back);
 
 /* ---- unit hooks: TLAS::intersect / any_intersect  src/tlas.rs:66, 111 ------------------------------------------ */
 /* which: 0 world TLAS, 1 lights TLAS.  Host SoA in, host SoA out.  miss => inst = prim = 0xffffffff, t = +inf.

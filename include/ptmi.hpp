@@ -498,6 +498,69 @@ public:
     std::vector<float> read_baked() const { std::vector<float> v((size_t)width_ * height_ * 4); check(pt_read_baked(ctx_, v.data())); return v; }
     void reset_baked() { check(pt_reset_baked(ctx_)); }
     void write_baked_image(const std::string& path) const { check(pt_write_baked_image(ctx_, path.c_str())); }
+    // the irradiance volume (pt_set_probe_grid): g places the nodes, sh27 holds 27 RADIANCE coefficients per node (node (ix, iy, iz) at
+    // (iz * ny + iy) * nx + ix), valid a byte per node (empty: all valid).  An empty sh27 with counts of 0 clears the grid.
+    void set_probe_grid(const pt_probe_grid& g, const std::vector<float>& sh27, const std::vector<uint8_t>& valid = {})
+    {
+        const size_t n = (size_t)g.count[0] * g.count[1] * g.count[2];
+        if (sh27.size() != n * 27 || (!valid.empty() && valid.size() != n)) throw Error(PT_ERR_ARG, "set_probe_grid: sh27 holds 27 values per node and valid one byte");
+        check(pt_set_probe_grid(ctx_, &g, sh27.empty() ? nullptr : sh27.data(), valid.empty() ? nullptr : valid.data()));
+    }
+    // ... of bake_probes' raw sums over n_samples samples: the factor 4 pi / n_samples is applied here
+    void set_probe_grid_sums(const pt_probe_grid& g, const std::vector<float>& sums, uint32_t n_samples, const std::vector<uint8_t>& valid = {})
+    {
+        if (n_samples == 0) throw Error(PT_ERR_ARG, "set_probe_grid_sums: n_samples must be positive");
+        const float scale = 12.566371f / (float)n_samples;
+        std::vector<float> sh(sums);
+        for (float& v : sh) v *= scale;
+        set_probe_grid(g, sh, valid);
+    }
+    // the grid in force (counts of 0: none); n_valid: its valid nodes
+    pt_probe_grid probe_grid_info(uint32_t* n_valid = nullptr) const { pt_probe_grid g{}; check(pt_get_probe_grid_info(ctx_, &g, n_valid)); return g; }
+    // the grid's lookup at n world positions and normals (3 floats each; pt_probe_grid_lookup): rgb (n * 3) and the lit bytes
+    std::vector<float> probe_grid_lookup(const std::vector<float>& position, const std::vector<float>& normal, std::vector<uint8_t>& lit, bool on_device = false) const
+    {
+        if (position.size() % 3 != 0 || normal.size() != position.size()) throw Error(PT_ERR_ARG, "probe_grid_lookup: positions and normals are 3 floats per query");
+        const size_t n = position.size() / 3;
+        std::vector<float> rgb(n * 3);
+        lit.assign(n, 0);
+        check(pt_probe_grid_lookup(ctx_, on_device ? 1 : 0, (uint32_t)n, position.data(), normal.data(), rgb.data(), lit.data()));
+        return rgb;
+    }
+    // the census of probes inside geometry (pt_probe_backfaces): per probe, bake_probes' rays that hit anything and those that hit a back face
+    void probe_backfaces(const std::vector<float>& positions, uint32_t n_samples, std::vector<uint32_t>& hits, std::vector<uint32_t>& back,
+                         uint32_t first_sample = 0, uint32_t key_base = 0)
+    {
+        if (positions.size() % 3 != 0 || positions.size() / 3 > 0xffffffffull) throw Error(PT_ERR_ARG, "probe_backfaces: positions are 3 floats per probe");
+        const size_t n = positions.size() / 3;
+        hits.assign(n, 0u); back.assign(n, 0u);
+        pt_probe_params p{};
+        p.first_sample = first_sample; p.n_samples = n_samples; p.key_base = key_base;
+        check(pt_probe_backfaces(ctx_, (uint32_t)n, positions.data(), &p, hits.data(), back.data()));
+    }
+    // the usual policy over probe_backfaces: a probe is usable while at most max_back_fraction of its rays see a back face
+    std::vector<uint8_t> probe_validity(const std::vector<float>& positions, uint32_t n_samples, float max_back_fraction = 0.25f)
+    {
+        std::vector<uint32_t> hits, back;
+        probe_backfaces(positions, n_samples, hits, back);
+        std::vector<uint8_t> valid(back.size());
+        for (size_t i = 0; i < back.size(); ++i) valid[i] = (float)back[i] <= max_back_fraction * (float)n_samples ? 1 : 0;
+        return valid;
+    }
+    // bakes and sets a grid: the node positions, bake_probes, probe_validity and set_probe_grid_sums; returns the valid bytes
+    std::vector<uint8_t> bake_probe_grid(const pt_probe_grid& g, uint32_t n_samples, float max_back_fraction = 0.25f)
+    {
+        std::vector<float> pos;
+        for (uint32_t z = 0; z < g.count[2]; ++z)
+            for (uint32_t y = 0; y < g.count[1]; ++y)
+                for (uint32_t x = 0; x < g.count[0]; ++x)
+                    for (float v : {g.origin[0] + (float)x * g.cell[0], g.origin[1] + (float)y * g.cell[1], g.origin[2] + (float)z * g.cell[2]}) pos.push_back(v);
+        std::vector<float> sums;
+        bake_probes(pos, n_samples, sums);
+        const std::vector<uint8_t> valid = probe_validity(pos, n_samples, max_back_fraction);
+        set_probe_grid_sums(g, sums, n_samples, valid);
+        return valid;
+    }
     // the world TLAS's root box: min xyz, max xyz
     std::array<float, 6> root_box() const { uint32_t rect[4]; std::array<float, 6> b{}; check(pt_active_pixels(ctx_, rect, b.data())); return b; }
     pt_stats stats() const { pt_stats s{}; check(pt_get_stats(ctx_, &s)); return s; }

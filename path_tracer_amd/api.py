@@ -49,6 +49,7 @@ EXPORTS = [
     "pt_render_guides_followed", "pt_read_guide_hops", "pt_accumulate_albedo_followed", "pt_guide_follow_dir",
     "pt_frame_temporal", "pt_read_temporal", "pt_reset_temporal", "pt_post_temporal", "pt_frame_temporal_options", "pt_post_temporal_options",
     "pt_set_lightmap", "pt_get_lightmap_info", "pt_lightmap_lookup", "pt_render_baked", "pt_read_baked", "pt_reset_baked", "pt_write_baked_image",
+    "pt_set_probe_grid", "pt_get_probe_grid_info", "pt_probe_grid_lookup", "pt_probe_backfaces",
     "pt_bake_lightmap_moments", "pt_lightmap_denoise",
 ]
 
@@ -134,6 +135,12 @@ class RaysParams(C.Structure):
 class ProbeParams(C.Structure):
     """pt_probe_params: the sample range and stream keys of a probe bake (include/pt_api.h)"""
     _fields_ = [("first_sample", C.c_uint32), ("n_samples", C.c_uint32), ("key_base", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class ProbeGrid(C.Structure):
+    """pt_probe_grid: where the nodes of the irradiance volume stand and the lookup's offset along the normal (include/pt_api.h)"""
+    _fields_ = [("origin", C.c_float * 3), ("cell", C.c_float * 3), ("count", C.c_uint32 * 3), ("normal_bias", C.c_float),
+                ("reserved", C.c_uint32 * 4)]
 
 
 class LightmapParams(C.Structure):
@@ -306,6 +313,10 @@ def lib():
         L.pt_read_baked.argtypes = [vp, vp]
         L.pt_reset_baked.argtypes = [vp]
         L.pt_write_baked_image.argtypes = [vp, C.c_char_p]
+        L.pt_set_probe_grid.argtypes = [vp, C.POINTER(ProbeGrid), vp, vp]
+        L.pt_get_probe_grid_info.argtypes = [vp, C.POINTER(ProbeGrid), C.POINTER(u32)]
+        L.pt_probe_grid_lookup.argtypes = [vp, C.c_int, u32, vp, vp, vp, vp]
+        L.pt_probe_backfaces.argtypes = [vp, u32, vp, C.POINTER(ProbeParams), vp, vp]
         L.pt_render_guides_followed.argtypes = [vp, u32, C.POINTER(GuideParams)]
         L.pt_read_guide_hops.argtypes = [vp, vp]
         L.pt_accumulate_albedo_followed.argtypes = [vp, u32, u32, C.POINTER(GuideParams)]
@@ -1121,6 +1132,79 @@ class Renderer:
 
     def write_baked_image(self, path):
         self._chk(self.L.pt_write_baked_image(self.ctx, str(path).encode()))
+
+    # ---- the irradiance volume: a grid of SH9 probes that lights what no lightmap lights
+    def set_probe_grid(self, origin, cell, sh, valid=None, normal_bias=0.0):
+        """the probe grid (pt_set_probe_grid): node (ix, iy, iz) at origin + (ix, iy, iz) * cell; sh (nz, ny, nx, 9, 3) float32 the RADIANCE SH
+        coefficients of every node (a bake's raw sums times 4 pi / n_samples: set_probe_grid_sums does that); valid (nz, ny, nx), None: all
+        valid.  sh None clears the grid."""
+        if sh is None:
+            self._chk(self.L.pt_set_probe_grid(self.ctx, C.byref(ProbeGrid()), None, None))
+            return
+        a = np.ascontiguousarray(sh, np.float32)
+        if a.ndim != 5 or a.shape[3:] != (9, 3):
+            raise PtError(-1, "set_probe_grid: sh is (nz, ny, nx, 9, 3)")
+        nz, ny, nx = a.shape[:3]
+        v = None if valid is None else np.ascontiguousarray(np.asarray(valid) != 0, np.uint8)
+        if v is not None and v.shape != (nz, ny, nx):
+            raise PtError(-1, "set_probe_grid: valid is (nz, ny, nx)")
+        g = ProbeGrid(_f3(origin), _f3(cell), (C.c_uint32 * 3)(nx, ny, nz), float(normal_bias))
+        self._chk(self.L.pt_set_probe_grid(self.ctx, C.byref(g), _p(a), _p(v)))
+
+    def set_probe_grid_sums(self, origin, cell, sums, n_samples, valid=None, normal_bias=0.0):
+        """set_probe_grid of bake_probes' raw sums (nz, ny, nx, 9, 3) over n_samples samples: the factor 4 pi / n_samples is applied here"""
+        if not n_samples > 0:
+            raise PtError(-1, "set_probe_grid_sums: n_samples must be positive")
+        scale = np.float32(4.0 * np.pi) / np.float32(n_samples)
+        self.set_probe_grid(origin, cell, np.asarray(sums, np.float32) * scale, valid, normal_bias)
+
+    def probe_grid_info(self):
+        """(origin, cell, (nx, ny, nz), normal_bias, valid nodes) of the grid; counts of 0: none"""
+        g = ProbeGrid(); n = C.c_uint32()
+        self._chk(self.L.pt_get_probe_grid_info(self.ctx, C.byref(g), C.byref(n)))
+        return np.array(g.origin, np.float32), np.array(g.cell, np.float32), tuple(g.count), float(g.normal_bias), n.value
+
+    def probe_grid_lookup(self, position, normal, on_device=False):
+        """unit hook: (rgb [n, 3], lit [n] uint8) of the grid's lookup at world positions and normals [n, 3]; on the host (no GPU) unless
+        on_device"""
+        p = np.ascontiguousarray(position, np.float32).reshape(-1, 3); nn = np.ascontiguousarray(normal, np.float32).reshape(-1, 3)
+        assert p.shape == nn.shape
+        out = np.zeros((p.shape[0], 3), np.float32); lit = np.zeros(p.shape[0], np.uint8)
+        self._chk(self.L.pt_probe_grid_lookup(self.ctx, int(bool(on_device)), p.shape[0], _p(p), _p(nn), _p(out), _p(lit)))
+        return out, lit
+
+    def probe_backfaces(self, positions, n_samples, first_sample=0, key_base=0):
+        """the census of probes inside geometry (pt_probe_backfaces): (hits [n], back [n]) uint32 over bake_probes' rays of samples
+        [first_sample, first_sample + n_samples), each traced once: the rays that hit, and those that hit a back face"""
+        pos = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
+        n = pos.shape[0]
+        hits = np.zeros(n, np.uint32); back = np.zeros(n, np.uint32)
+        prm = ProbeParams(first_sample, n_samples, key_base, 0)
+        self._chk(self.L.pt_probe_backfaces(self.ctx, n, _p(pos), C.byref(prm), _p(hits), _p(back)))
+        return hits, back
+
+    def probe_validity(self, positions, n_samples, max_back_fraction=0.25):
+        """the usual policy over probe_backfaces: a probe is usable while at most max_back_fraction of its rays see a back face"""
+        _, back = self.probe_backfaces(positions, n_samples)
+        return back <= max_back_fraction * n_samples
+
+    @staticmethod
+    def probe_grid_positions(origin, cell, count):
+        """the node positions (nz, ny, nx, 3) float32 of a grid: origin + index * cell, one binary32 product and sum per component"""
+        nx, ny, nz = (int(k) for k in count)
+        o = np.asarray(origin, np.float32); c = np.asarray(cell, np.float32)
+        idx = np.stack(np.meshgrid(np.arange(nz), np.arange(ny), np.arange(nx), indexing="ij")[::-1], axis=-1).astype(np.float32)
+        return (o + idx * c).astype(np.float32)
+
+    def bake_probe_grid(self, origin, cell, count, n_samples, max_back_fraction=0.25, normal_bias=0.0):
+        """bakes and sets a grid of count = (nx, ny, nz) probes: the node positions, bake_probes, probe_validity and set_probe_grid_sums.
+        Returns (sums (nz, ny, nx, 9, 3), valid (nz, ny, nx))"""
+        nx, ny, nz = (int(k) for k in count)
+        pos = self.probe_grid_positions(origin, cell, count).reshape(-1, 3)
+        sums = self.bake_probes(pos, n_samples).reshape(nz, ny, nx, 9, 3)
+        valid = self.probe_validity(pos, n_samples, max_back_fraction).reshape(nz, ny, nx)
+        self.set_probe_grid_sums(origin, cell, sums, n_samples, valid, normal_bias)
+        return sums, valid
 
     # ---- unit hooks
     def trace_closest(self, o, d, tmax=None, which=0):

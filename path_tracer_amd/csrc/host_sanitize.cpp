@@ -27,6 +27,10 @@
 //                                      5 x 3, 16 x 16 and 37 x 19 pixels with miss pixels, invalid pixels and two models, the 7 x 7 variance and
 //                                      8 levels (step 128 leaves every map); then the rules' defining property: with one model, every pixel a valid
 //                                      hit and reach2 = +inf the texel rule gives the screen rule's bits (nonzero exit if not); prints a checksum
+//   host_sanitize probegrid <n> <seed> the probe grid's host side: random grids of 1 x 1 x 1, 2 x 2 x 2, 3 x 2 x 4, 5 x 1 x 3 and two with a single line of
+//                                      nodes, a fifth of the nodes invalid, then probe_grid_lookup (pt_probe.h, the function the kernels run) at n
+//                                      points each: inside, far outside, huge, infinite and NaN positions, NaN normals; prints how many were lit and
+//                                      a checksum of the results
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -40,6 +44,7 @@
 #include "pt_lightmap_filter.h"
 #include "pt_materials.h"
 #include "pt_png.h"
+#include "pt_probe.h"
 #include "pt_scene.h"
 
 using namespace pt;
@@ -435,6 +440,50 @@ int main(int argc, char** argv)
             tally(screen);
         }
         std::printf("{\"pixels\": %u, \"finite\": %u, \"checksum\": %.6f}\n", pixels, finite, acc);
+        return 0;
+    }
+    if (cmd == "probegrid" && argc >= 4)
+    {
+        const uint32_t n = (uint32_t)std::atoi(argv[2]);
+        uint64_t s = 0x9E3779B97F4A7C15ull ^ (uint64_t)std::atoll(argv[3]);
+        auto rnd = [&]() { s ^= s << 13; s ^= s >> 7; s ^= s << 17; return (float)((s >> 40) & 0xffff) / 65535.0f; };
+        const uint32_t counts[6][3] = {{1, 1, 1}, {2, 2, 2}, {3, 2, 4}, {5, 1, 3}, {1, 7, 1}, {1, 1, 6}};
+        double acc = 0.0;
+        uint32_t lookups = 0, lit = 0;
+        for (const uint32_t* cnt : counts)
+        {
+            const size_t nodes = (size_t)cnt[0] * cnt[1] * cnt[2];
+            std::vector<DProbe> rec(nodes); // exactly the grid: a node index past it is a heap overflow
+            for (DProbe& r : rec)
+            {
+                r.valid = rnd() < 0.8f ? 1.0f : 0.0f;
+                for (float& v : r.sh) v = r.valid != 0.0f ? 4.0f * rnd() - 1.0f : 0.0f;
+            }
+            const ProbeGridView g{rec.data(), {4.0f * rnd() - 2.0f, 4.0f * rnd() - 2.0f, 4.0f * rnd() - 2.0f},
+                                  {0.25f + rnd(), 0.25f + rnd(), 0.25f + rnd()}, {cnt[0], cnt[1], cnt[2]}, rnd() < 0.5f ? 0.0f : 0.125f};
+            for (uint32_t i = 0; i < n; ++i)
+            {
+                // inside, a little outside, far outside, huge, infinite and NaN positions; unit, zero and NaN normals
+                const uint32_t kind = i % 8u;
+                const float reach = kind == 0u ? 1.0f : kind == 1u ? 3.0f : kind == 2u ? 1e4f : kind == 3u ? 1e30f : 1.0f;
+                float p[3], nn[3];
+                for (int a = 0; a < 3; ++a)
+                {
+                    p[a] = g.origin[a] + reach * (2.0f * rnd() - 0.5f) * g.cell[a] * (float)cnt[a];
+                    nn[a] = 2.0f * rnd() - 1.0f;
+                }
+                if (kind == 4u) p[i % 3u] = NAN;
+                if (kind == 5u) p[i % 3u] = i & 8u ? INFINITY : -INFINITY;
+                if (kind == 6u) nn[i % 3u] = NAN;
+                if (kind == 7u) p[0] = p[1] = p[2] = 3.0e38f;
+                f3 c;
+                if (probe_grid_lookup(g, f3{p[0], p[1], p[2]}, f3{nn[0], nn[1], nn[2]}, &c)) ++lit;
+                for (float v : {c.x, c.y, c.z})
+                    if (std::isfinite(v)) acc += v;
+                ++lookups;
+            }
+        }
+        std::printf("{\"lookups\": %u, \"lit\": %u, \"checksum\": %.6f}\n", lookups, lit, acc);
         return 0;
     }
     if (cmd == "plan")

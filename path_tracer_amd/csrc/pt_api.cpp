@@ -208,6 +208,14 @@ struct pt_ctx
     bool baked_valid = false;
     uint64_t baked_scene_version = 0, baked_config_version = 0, baked_lm_version = 0;
     uint32_t baked_max_hops = 0, baked_unlit[3] = {0, 0, 0};
+    // the probe grid (pt_set_probe_grid): world-space data that no scene call touches.  probes: the records as the device gets them (empty: no
+    // grid); probe_version counts the grid's changes (the baked sums keep the one they were made under); pg_version: the one on the device.
+    pt_probe_grid probe_grid{};
+    std::vector<DProbe> probes;
+    uint32_t probes_valid = 0;
+    uint64_t probe_version = 0, baked_probe_version = 0, pg_version = 0;
+    DevBuf d_probes;
+    bool pg_valid = false;
 
     // pt_frame_moving: the forward instance matrices, per model, of the build in force when the previous call returned PT_OK (the snapshot)
     // and the build it was taken from (a call on that very build has nothing to compare); the motion table and x_prev on the device.
@@ -1583,6 +1591,27 @@ int ensure_lightmaps(pt_ctx* c)
     c->lm_valid = true;
     c->lm_version = c->lightmap_version;
     c->lm_upload = upload;
+    return PT_OK;
+}
+
+// ---- the probe grid kept by the context (pt_set_probe_grid; the lookup is pt_probe.h's)
+// what the lookup reads, over the records at `nodes`: the host's copy or the device table
+ProbeGridView probe_grid_view(const pt_ctx* c, const DProbe* nodes)
+{
+    const pt_probe_grid& g = c->probe_grid;
+    return ProbeGridView{nodes, {g.origin[0], g.origin[1], g.origin[2]}, {g.cell[0], g.cell[1], g.cell[2]}, {g.count[0], g.count[1], g.count[2]}, g.normal_bias};
+}
+// The grid's device table (after ensure_device), uploaded when the grid changed since; only called with a grid set.
+int ensure_probe_grid(pt_ctx* c)
+{
+    if (c->pg_valid && c->pg_version == c->probe_version) return PT_OK;
+    c->pg_valid = false;
+    int r;
+    HIPCHK(c, hipStreamSynchronize(c->stream)); // an earlier call may still be reading the table
+    if ((r = dev_alloc(c, c->d_probes, c->probes.size() * sizeof(DProbe)))) return r;
+    HIPCHK(c, hipMemcpy(c->d_probes.p, c->probes.data(), c->probes.size() * sizeof(DProbe), hipMemcpyHostToDevice));
+    c->pg_valid = true;
+    c->pg_version = c->probe_version;
     return PT_OK;
 }
 
@@ -3017,9 +3046,11 @@ int follow_chains(pt_ctx* c, uint32_t sample, uint32_t max_hops, f4* sum)
         launch_guide_follow(c->stream, c->sv, c->tex, a);
     });
 }
-// ... and the baked view's chains (pt_render_baked): the same walk, ended by launch_baked_follow into the baked sums
+// ... and the baked view's chains (pt_render_baked): the same walk, ended by launch_baked_follow into the baked sums, or by the probe ending
+// while a grid is set (pt_set_probe_grid)
 int baked_chains(pt_ctx* c, uint32_t sample, const pt_baked_params& p)
 {
+    const bool grid = !c->probes.empty();
     EnvView env{};
     if (c->env_w) env = EnvView{(const f4*)c->d_env.p, c->env_w, c->env_h, 0u, 0u};
     return walk_chains(c, sample, p.max_hops, [&](const ChainHop& q, uint32_t h) {
@@ -3031,7 +3062,8 @@ int baked_chains(pt_ctx* c, uint32_t sample, const pt_baked_params& p)
         b.cap = c->local_pixels;
         b.hop = h;
         b.max_hops = p.max_hops;
-        launch_baked_follow(c->stream, c->sv, c->tex, c->lm, b);
+        if (grid) launch_baked_follow_probes(c->stream, c->sv, c->tex, c->lm, b, probe_grid_view(c, (const DProbe*)c->d_probes.p));
+        else launch_baked_follow(c->stream, c->sv, c->tex, c->lm, b);
     });
 }
 
@@ -3396,13 +3428,13 @@ int pt_probe_ray(pt_ctx* c, uint32_t key, uint32_t sample, float d[3], float y9[
     return PT_OK;
 }
 
-int pt_bake_probes(pt_ctx* c, uint32_t n_probes, const float* position, const pt_probe_params* p, float* sh27)
+// what pt_bake_probes and pt_probe_backfaces refuse before any device call (`outputs`: the call's output arrays by name, any_null: one is NULL)
+static int probe_call_check(pt_ctx* c, const std::string& who, const char* outputs, uint32_t n_probes, const float* position, const pt_probe_params* p,
+                            bool any_null)
 {
-    if (!c) return PT_ERR_ARG;
-    std::lock_guard<std::mutex> lk(c->mu);
     int r;
     if ((r = rays_precheck(c))) return r;
-    if (n_probes > 0 && (!position || !p || !sh27)) return fail(c, PT_ERR_ARG, "pt_bake_probes: position_xyz, p and sh27 must not be NULL");
+    if (n_probes > 0 && (!position || !p || any_null)) return fail(c, PT_ERR_ARG, who + ": position_xyz, p and " + outputs + " must not be NULL");
     if (p)
     {
         if (p->reserved) return fail(c, PT_ERR_ARG, "pt_probe_params.reserved must be 0");
@@ -3411,7 +3443,16 @@ int pt_bake_probes(pt_ctx* c, uint32_t n_probes, const float* position, const pt
         if ((uint64_t)p->first_sample + p->n_samples > 0x100000000ull) return fail(c, PT_ERR_ARG, "pt_probe_params.first_sample + n_samples wraps 32 bits");
     }
     for (uint64_t i = 0; i < (uint64_t)n_probes * 3; ++i)
-        if (!std::isfinite(position[i])) return fail(c, PT_ERR_ARG, "pt_bake_probes: probe " + std::to_string(i / 3) + " has a position that is not finite");
+        if (!std::isfinite(position[i])) return fail(c, PT_ERR_ARG, who + ": probe " + std::to_string(i / 3) + " has a position that is not finite");
+    return PT_OK;
+}
+
+int pt_bake_probes(pt_ctx* c, uint32_t n_probes, const float* position, const pt_probe_params* p, float* sh27)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    int r;
+    if ((r = probe_call_check(c, "pt_bake_probes", "sh27", n_probes, position, p, !sh27))) return r;
     if (n_probes == 0) return PT_OK;
     if ((r = upload_scene(c))) return r;
     Staging st(c);
@@ -3711,11 +3752,11 @@ int pt_lightmap_lookup(pt_ctx* c, int on_device, uint32_t n, const uint32_t* ins
     return st.download(mapped, d_mapped, n);
 }
 
-// the baked sums exist and belong to what is in force: what keeps the guides current, and the lightmaps
+// the baked sums exist and belong to what is in force: what keeps the guides current, the lightmaps and the probe grid
 static bool baked_current(const pt_ctx* c)
 {
     return c->baked_valid && c->baked_scene_version == c->scene_version && c->baked_config_version == c->config_version &&
-           c->baked_lm_version == c->lightmap_version;
+           c->baked_lm_version == c->lightmap_version && c->baked_probe_version == c->probe_version;
 }
 
 int pt_render_baked(pt_ctx* c, uint32_t first_sample, uint32_t n_samples, const pt_baked_params* p, float* rgbn)
@@ -3733,6 +3774,7 @@ int pt_render_baked(pt_ctx* c, uint32_t first_sample, uint32_t n_samples, const 
     if (!c->scene.camera.set) return fail(c, PT_ERR_STATE, "pt_set_camera has not been called");
     int r;
     if ((r = upload_scene(c)) || (r = ensure_environment(c)) || (r = ensure_lightmaps(c))) return r;
+    if (!c->probes.empty() && (r = ensure_probe_grid(c))) return r;
     const uint32_t px = c->local_pixels;
     const size_t n = std::max<uint32_t>(px, 1);
     if ((r = guide_scratch(c, p->max_hops)) || (r = dev_alloc(c, c->d_baked_sum, n * 16))) return r;
@@ -3753,6 +3795,7 @@ int pt_render_baked(pt_ctx* c, uint32_t first_sample, uint32_t n_samples, const 
     c->baked_scene_version = c->scene_version;
     c->baked_config_version = c->config_version;
     c->baked_lm_version = c->lightmap_version;
+    c->baked_probe_version = c->probe_version;
     c->baked_max_hops = p->max_hops;
     std::memcpy(c->baked_unlit, unlit, sizeof(unlit));
     return PT_OK;
@@ -3790,6 +3833,140 @@ int pt_write_baked_image(pt_ctx* c, const char* path)
     std::string err;
     if (!write_png_rgb8(path, host.data(), c->cfg.width, c->cfg.height, &err)) return fail(c, PT_ERR_IO, err.c_str());
     return PT_OK;
+}
+
+// ---- the probe grid and the census of probes inside geometry (the definitions are include/pt_api.h's)
+int pt_set_probe_grid(pt_ctx* c, const pt_probe_grid* g, const float* sh27, const uint8_t* valid)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!g) return fail(c, PT_ERR_ARG, "pt_set_probe_grid: g must not be NULL");
+    if (g->reserved[0] || g->reserved[1] || g->reserved[2] || g->reserved[3]) return fail(c, PT_ERR_ARG, "pt_probe_grid.reserved must be 0");
+    const bool none = !g->count[0] && !g->count[1] && !g->count[2];
+    if (!sh27 && none)
+    {
+        if (!c->probes.empty()) c->probe_version++;
+        std::vector<DProbe>().swap(c->probes);
+        c->probe_grid = pt_probe_grid{};
+        c->probes_valid = 0;
+        return PT_OK;
+    }
+    if (!sh27 || !g->count[0] || !g->count[1] || !g->count[2])
+        return fail(c, PT_ERR_ARG, "pt_set_probe_grid: sh27 with three non-zero counts sets a grid, NULL with all counts 0 clears it");
+    for (int a = 0; a < 3; ++a)
+        if (g->count[a] > 256u) return fail(c, PT_ERR_LIMIT, "pt_probe_grid.count: an axis holds at most 256 nodes");
+    for (int a = 0; a < 3; ++a)
+    {
+        if (!std::isfinite(g->origin[a])) return fail(c, PT_ERR_ARG, "pt_probe_grid.origin must be finite");
+        if (!(g->cell[a] > 0.0f) || !std::isfinite(g->cell[a])) return fail(c, PT_ERR_ARG, "pt_probe_grid.cell must be finite and > 0");
+    }
+    if (!(g->normal_bias >= 0.0f) || !std::isfinite(g->normal_bias)) return fail(c, PT_ERR_ARG, "pt_probe_grid.normal_bias must be finite and >= 0");
+    const size_t n = (size_t)g->count[0] * g->count[1] * g->count[2];
+    for (size_t i = 0; i < n * 27; ++i)
+        if (!std::isfinite(sh27[i])) return fail(c, PT_ERR_ARG, "pt_set_probe_grid: node " + std::to_string(i / 27) + " has a coefficient that is not finite");
+    std::vector<DProbe> rec;
+    try { rec.assign(n, DProbe{}); }
+    catch (const std::exception& e) { return fail(c, PT_ERR_LIMIT, std::string("probe grid does not fit in host memory: ") + e.what()); }
+    uint32_t n_valid = 0;
+    for (size_t i = 0; i < n; ++i)
+    {
+        if (valid && !valid[i]) continue; // (its coefficients are not kept: zeros, and the valid word 0)
+        std::memcpy(rec[i].sh, sh27 + i * 27, sizeof(rec[i].sh));
+        rec[i].valid = 1.0f;
+        ++n_valid;
+    }
+    c->probes.swap(rec);
+    c->probe_grid = *g;
+    c->probes_valid = n_valid;
+    c->probe_version++;
+    return PT_OK;
+}
+
+int pt_get_probe_grid_info(pt_ctx* c, pt_probe_grid* out, uint32_t* n_valid)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (out) *out = c->probe_grid;
+    if (n_valid) *n_valid = c->probes_valid;
+    return PT_OK;
+}
+
+int pt_probe_grid_lookup(pt_ctx* c, int on_device, uint32_t n, const float* position, const float* normal, float* rgb, uint8_t* lit)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (c->probes.empty()) return fail(c, PT_ERR_STATE, "no probe grid: pt_set_probe_grid first");
+    if (n == 0) return PT_OK;
+    if (!position || !normal || !rgb || !lit) return fail(c, PT_ERR_ARG, "pt_probe_grid_lookup: null pointer");
+    if (!on_device)
+    {
+        const ProbeGridView g = probe_grid_view(c, c->probes.data());
+        for (uint32_t i = 0; i < n; ++i)
+        {
+            const float *pp = position + 3 * (size_t)i, *pn = normal + 3 * (size_t)i;
+            f3 col;
+            lit[i] = probe_grid_lookup(g, f3{pp[0], pp[1], pp[2]}, f3{pn[0], pn[1], pn[2]}, &col) ? 1u : 0u;
+            rgb[3 * (size_t)i] = col.x; rgb[3 * (size_t)i + 1] = col.y; rgb[3 * (size_t)i + 2] = col.z;
+        }
+        return PT_OK;
+    }
+    int r;
+    if ((r = ensure_device(c)) || (r = ensure_probe_grid(c))) return r;
+    Staging st(c);
+    const float* d_pos = (const float*)st.in(position, (size_t)n * 12);
+    const float* d_nrm = (const float*)st.in(normal, (size_t)n * 12);
+    float* d_rgb = (float*)st.out((size_t)n * 12);
+    uint8_t* d_lit = (uint8_t*)st.out(n);
+    if (st.err) return st.err;
+    launch_probe_grid_lookup(c->stream, probe_grid_view(c, (const DProbe*)c->d_probes.p), n, d_pos, d_nrm, d_rgb, d_lit);
+    HIPCHK(c, hipGetLastError());
+    if ((r = st.download(rgb, d_rgb, (size_t)n * 12))) return r;
+    return st.download(lit, d_lit, n);
+}
+
+int pt_probe_backfaces(pt_ctx* c, uint32_t n_probes, const float* position, const pt_probe_params* p, uint32_t* hits, uint32_t* back)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    int r;
+    if ((r = probe_call_check(c, "pt_probe_backfaces", "hits and back", n_probes, position, p, !hits || !back))) return r;
+    if (n_probes == 0) return PT_OK;
+    if ((r = upload_scene(c))) return r;
+    std::memset(hits, 0, (size_t)n_probes * 4);
+    std::memset(back, 0, (size_t)n_probes * 4);
+    if (c->sv.world_root == MISS_ID) return PT_OK; // an empty world: every ray misses
+    // the bake's rays through a ray table of at most 2^21 at a time: filled (k_probe_rays), queued, traced once, counted per probe.
+    // pt_config.batch_spp cuts here as it cuts the bake (tables of 3 * batch_spp * n_probes rays): the counts do not depend on the cut
+    const uint64_t total = (uint64_t)n_probes * p->n_samples;
+    const uint64_t cut = c->cfg.batch_spp ? 3ull * c->cfg.batch_spp * n_probes : total;
+    const uint32_t chunk = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(total, cut), 1ull << 21);
+    Staging st(c);
+    const float* d_position = (const float*)st.in(position, (size_t)n_probes * 12);
+    uint32_t* d_hits = (uint32_t*)st.in(hits, (size_t)n_probes * 4);
+    uint32_t* d_back = (uint32_t*)st.in(back, (size_t)n_probes * 4);
+    float* d_o = (float*)st.out((size_t)chunk * 12);
+    float* d_d = (float*)st.out((size_t)chunk * 12);
+    uint2* d_key = (uint2*)st.out((size_t)chunk * 8);
+    const RayQueue q{(f4*)st.out((size_t)chunk * 16), (f4*)st.out((size_t)chunk * 16)};
+    f4* d_hit = (f4*)st.out((size_t)chunk * 16);
+    const size_t head_bytes = ((size_t)32 + kHeadWordsPerQueue) * 4;
+    uint32_t* d_head = (uint32_t*)st.out(head_bytes);
+    if (st.err) return st.err;
+    const ProbeBake pb{d_position, n_probes, p->first_sample, p->n_samples, p->key_base, c->cfg.n_sobol, c->cfg.seed};
+    c->hook_log.clear();
+    const LaunchLogScope logging(&c->hook_log);
+    for (uint64_t first = 0; first < total; first += chunk)
+    {
+        const uint32_t cnt = (uint32_t)std::min<uint64_t>(chunk, total - first);
+        launch_probe_rays(c->stream, pb, first, cnt, d_o, d_d, d_key);
+        HIPCHK(c, hipMemsetAsync(d_head, 0, head_bytes, c->stream));
+        launch_rays_to_queue(c->stream, cnt, d_o, d_d, q, d_head);
+        launch_trace_rays_closest(c->stream, trace_launch(c), c->sv.world_root, q, cnt, d_head, d_hit);
+        launch_probe_backfaces(c->stream, c->sv, pb, first, cnt, d_d, d_hit, d_hits, d_back);
+        HIPCHK(c, hipGetLastError());
+    }
+    if ((r = st.download(hits, d_hits, (size_t)n_probes * 4))) return r;
+    return st.download(back, d_back, (size_t)n_probes * 4);
 }
 
 // ---- unit hooks

@@ -319,6 +319,17 @@ struct BakedArgs : ChainHop
     uint32_t cap, hop, max_hops;
 };
 void launch_baked_follow(hipStream_t s, const SceneView& sv, const TexView& tex, const LmView& lm, const BakedArgs& a);
+// ... with a probe grid set (pt_set_probe_grid): the same hop with the probe ending, kernels of their own (launch_baked_follow's keep their
+// arguments and their code)
+void launch_baked_follow_probes(hipStream_t s, const SceneView& sv, const TexView& tex, const LmView& lm, const BakedArgs& a, const ProbeGridView& grid);
+// unit hook (pt_probe_grid_lookup): probe_grid_lookup (pt_probe.h) at n positions and normals (3 floats each)
+void launch_probe_grid_lookup(hipStream_t s, const ProbeGridView& grid, uint32_t n, const float* position, const float* normal, float* rgb, uint8_t* lit);
+// pt_probe_backfaces: a ray table's entries [0, n) (o, d: 3 floats per ray) as a hook queue (t_max +inf, ray index = entry), its count word set;
+// then the closest hits of rays [first, first + count) of the bake `pb` (d, hits: the window) counted per probe into hits_out and back_out,
+// which continue from what they hold: one wave per probe, no atomics
+void launch_rays_to_queue(hipStream_t s, uint32_t n, const float* o, const float* d, RayQueue rq, uint32_t* n_and_heads);
+void launch_probe_backfaces(hipStream_t s, const SceneView& sv, const ProbeBake& pb, uint64_t first, uint32_t count, const float* d, const f4* hits,
+                            uint32_t* hits_out, uint32_t* back_out);
 // unit hook (pt_lightmap_lookup): lightmap_at (pt_materials.h) of world instance[i], leaf-order triangle tri[i] at barycentrics u[i], v[i]
 void launch_lightmap_lookup(hipStream_t s, const LmView& lm, uint32_t n, const uint32_t* instance, const uint32_t* tri, const float* u, const float* v,
                             float* rgb, uint8_t* mapped);

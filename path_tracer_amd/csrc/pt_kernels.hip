@@ -2686,6 +2686,43 @@ __global__ void __launch_bounds__(256) k_probe_project(const ProbeBake pb, const
     }
     sh27[(size_t)j * 27u + kc] = acc;
 }
+// pt_probe_backfaces: the closest hits of rays [first, first + count) of a bake (hits[i] of ray first + i, its direction d[i]) counted into
+// hits_out[probe] and back_out[probe]: one wave per probe the window touches, its lanes striding the probe's rays of the window, a wave
+// reduction, and lane 0 adds the two integers to what the counts hold.  A wave owns its probe for the launch and the launches of a call
+// follow each other on one stream: no atomics, and integers do not care how the rays were cut.  The front flag is hit_normal's.
+__global__ void __launch_bounds__(256) k_probe_backfaces(const SceneView sv, const ProbeBake pb, const uint64_t first, const uint32_t count,
+                                                         const float* __restrict__ d, const f4* __restrict__ hits, uint32_t* __restrict__ hits_out,
+                                                         uint32_t* __restrict__ back_out)
+{
+    const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const uint32_t p0 = (uint32_t)(first / pb.n_samples), p1 = (uint32_t)((first + count - 1u) / pb.n_samples);
+    if (wave > p1 - p0) return; // (wave-uniform)
+    const uint32_t j = p0 + wave;
+    const uint64_t lo = (uint64_t)j * pb.n_samples, hi = lo + pb.n_samples;
+    const uint32_t i0 = (uint32_t)((lo > first ? lo : first) - first), i1 = (uint32_t)((hi < first + count ? hi : first + count) - first);
+    uint32_t n_hit = 0u, n_back = 0u;
+    for (uint32_t i = i0 + lane_id(); i < i1; i += 64u)
+    {
+        const f4 hit = hits[i];
+        const uint32_t hid = asu(hit.w);
+        if (hid == MISS_ID) continue;
+        const float* pd = d + 3u * (size_t)i;
+        bool front;
+        hit_normal(sv, hid >> sv.prim_bits, hid & ((1u << sv.prim_bits) - 1u), hit.y, hit.z, f3{pd[0], pd[1], pd[2]}, front);
+        n_hit += 1u;
+        n_back += front ? 0u : 1u;
+    }
+    for (int off = 32; off > 0; off >>= 1)
+    {
+        n_hit += (uint32_t)__shfl_down((int)n_hit, off, 64);
+        n_back += (uint32_t)__shfl_down((int)n_back, off, 64);
+    }
+    if (lane_id() == 0u)
+    {
+        hits_out[j] = hits_out[j] + n_hit;
+        back_out[j] = back_out[j] + n_back;
+    }
+}
 
 // ------------------------------------------------------------------------------------------------ adaptive selection (PT_FLAG_ADAPTIVE)
 // The criterion of pt_api.h's pt_adaptive, in f32 with every operation correctly rounded and in this order (the tests restate it in
@@ -3065,6 +3102,102 @@ __global__ void __launch_bounds__(256, 8) k_baked_follow(const SceneView sv, con
         a.next.a[pos] = next_a;
         a.next.b[pos] = next_b;
     }
+}
+// ... with a probe grid set (pt_set_probe_grid): k_baked_follow with another third ending, as a kernel of its own so that the one above keeps its
+// arguments and its code.  A final surface that no map lights is lit by the grid where the grid is lit, by unlit where not; P and n are the
+// guides' (the hit position, the face-forwarded unperturbed normal).  The corner being evaluated and the one in flight are 56 registers and
+// the ending must not spill, so its bounds leave it 128; it takes 66 (seven waves per SIMD) and no scratch (profiles/r24_probe_grid.md).
+template <bool FIRST>
+__global__ void __launch_bounds__(256, 4) k_baked_follow_probes(const SceneView sv, const TexView tex, const LmView lm, const BakedArgs a, const ProbeGridView grid)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t n = min(*a.n_in, a.cap);
+    bool go_on = false;
+    f4 next_a{}, next_b{};
+    if (i < n)
+    {
+        const f4 hit = a.hits[i];
+        const f4 rb = a.in.b[i];
+        const uint32_t px = asu(rb.w);
+        const f3 d = xyz(rb);
+        f3 b{0.0f, 0.0f, 0.0f};
+        const uint32_t hid = asu(hit.w);
+        if (hid == MISS_ID)
+        {
+            b = a.env.w ? env_lookup(a.env, d) : f3{0.006f, 0.006f, 0.006f};
+            if (!FIRST) b = xyz(a.state[px]) * b;
+        }
+        else
+        {
+            // (one gather after the other, each behind a compiler barrier, the grid's corners last: see k_guide_follow)
+            const uint32_t inst = hid >> sv.prim_bits, tri = hid & ((1u << sv.prim_bits) - 1u);
+            const DMaterial& dm = sv.materials[sv.instances[inst].material];
+            f3 c = surface_colour(tex, dm.texture, f3{dm.colour[0], dm.colour[1], dm.colour[2]}, tri, hit.y, hit.z);
+            if (!FIRST) c = xyz(a.state[px]) * c;
+            const uint32_t kind = dm.kind;
+            __asm__ volatile("" ::: "memory");
+            bool front;
+            const f3 nrm = hit_normal(sv, inst, tri, hit.y, hit.z, d, front);
+            const FollowDir f = guide_follow_dir(kind, dm.ior, d, nrm, front);
+            go_on = f.followed && a.hop < a.max_hops;
+            __asm__ volatile("" ::: "memory");
+            if (go_on)
+            {
+                const f3 p = fma3(d, bc3(hit.x), xyz(a.in.a[i]));
+                a.state[px] = f4{c.x, c.y, c.z, 0.0f};
+                next_a = f4{p.x, p.y, p.z, __builtin_inff()};
+                next_b = f4{f.wo.x, f.wo.y, f.wo.z, asf(px)};
+            }
+            else if (kind == MAT_EMISSIVE) b = c;
+            else
+            {
+                f3 l{a.unlit[0], a.unlit[1], a.unlit[2]};
+                bool mapped = false;
+                if (front) // the bake lit the front side only
+                {
+                    const f3 m = lightmap_at(lm, inst, tri, hit.y, hit.z, &mapped);
+                    if (mapped) l = m;
+                }
+                if (!mapped) // the grid lights what no map lights, where it is lit itself
+                {
+                    __asm__ volatile("" ::: "memory");
+                    f3 irr;
+                    if (probe_grid_lookup(grid, fma3(d, bc3(hit.x), xyz(a.in.a[i])), nrm, &irr)) l = irr;
+                }
+                b = c * l;
+            }
+        }
+        if (!go_on)
+        {
+            const f4 s = a.sum[px];
+            a.sum[px] = f4{s.x + b.x, s.y + b.y, s.z + b.z, s.w + 1.0f};
+        }
+    }
+    // every lane of the block is here (no early exit above), so lane 0 of each wave can reserve for it
+    const uint64_t m = __ballot(go_on);
+    if (m == 0ull) return;
+    uint32_t base = 0u;
+    if (lane_id() == 0u) base = atomicAdd(a.n_next, (uint32_t)__popcll(m));
+    base = __builtin_amdgcn_readfirstlane(base);
+    if (go_on)
+    {
+        const uint32_t pos = base + mbcnt64(m); // < the chains that go on <= n <= a.cap, the queues' slots
+        a.next.a[pos] = next_a;
+        a.next.b[pos] = next_b;
+    }
+}
+// unit hook of the probe grid's lookup: rgb, lit = probe_grid_lookup
+__global__ void __launch_bounds__(256, 4) k_probe_grid_lookup(const ProbeGridView grid, const uint32_t n, const float* __restrict__ position,
+                                                              const float* __restrict__ normal, float* __restrict__ rgb, uint8_t* __restrict__ lit)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float* pp = position + 3u * (size_t)i;
+    const float* pn = normal + 3u * (size_t)i;
+    f3 c;
+    const bool has = probe_grid_lookup(grid, f3{pp[0], pp[1], pp[2]}, f3{pn[0], pn[1], pn[2]}, &c);
+    rgb[3u * (size_t)i] = c.x; rgb[3u * (size_t)i + 1u] = c.y; rgb[3u * (size_t)i + 2u] = c.z;
+    lit[i] = has ? 1u : 0u;
 }
 // unit hook of the lightmap lookup: rgb, mapped = lightmap_at
 __global__ void __launch_bounds__(256) k_lightmap_lookup(const LmView lm, const uint32_t n, const uint32_t* __restrict__ instance, const uint32_t* __restrict__ tri,
@@ -3629,6 +3762,32 @@ void launch_baked_follow(hipStream_t s, const SceneView& sv, const TexView& tex,
     const dim3 grid((a.cap + 255u) / 256u);
     if (a.hop == 0u) hipLaunchKernelGGL(k_baked_follow<true>, grid, dim3(256), 0, s, sv, tex, lm, a);
     else hipLaunchKernelGGL(k_baked_follow<false>, grid, dim3(256), 0, s, sv, tex, lm, a);
+}
+void launch_baked_follow_probes(hipStream_t s, const SceneView& sv, const TexView& tex, const LmView& lm, const BakedArgs& a, const ProbeGridView& grid)
+{
+    if (a.cap == 0u) return;
+    const dim3 grid_dim((a.cap + 255u) / 256u);
+    if (a.hop == 0u) hipLaunchKernelGGL(k_baked_follow_probes<true>, grid_dim, dim3(256), 0, s, sv, tex, lm, a, grid);
+    else hipLaunchKernelGGL(k_baked_follow_probes<false>, grid_dim, dim3(256), 0, s, sv, tex, lm, a, grid);
+}
+void launch_probe_grid_lookup(hipStream_t s, const ProbeGridView& grid, uint32_t n, const float* position, const float* normal, float* rgb, uint8_t* lit)
+{
+    if (n == 0u) return;
+    hipLaunchKernelGGL(k_probe_grid_lookup, dim3((n + 255u) / 256u), dim3(256), 0, s, grid, n, position, normal, rgb, lit);
+}
+void launch_rays_to_queue(hipStream_t s, uint32_t n, const float* o, const float* d, RayQueue rq, uint32_t* n_and_heads)
+{
+    if (n == 0u) return;
+    // (k_generate_rays writes the count into word 0 of what it is handed: a batch's first counter row there, a hook queue's count word here)
+    static_assert(__builtin_offsetof(Counters, n_closest) == 0, "a hook queue's count word is read as Counters::n_closest");
+    hipLaunchKernelGGL(k_generate_rays, dim3((n + 255u) / 256u), dim3(256), 0, s, n, o, d, rq, (Counters*)n_and_heads);
+}
+void launch_probe_backfaces(hipStream_t s, const SceneView& sv, const ProbeBake& pb, uint64_t first, uint32_t count, const float* d, const f4* hits,
+                            uint32_t* hits_out, uint32_t* back_out)
+{
+    if (count == 0u) return;
+    const uint64_t probes = (first + count - 1u) / pb.n_samples - first / pb.n_samples + 1u;
+    hipLaunchKernelGGL(k_probe_backfaces, dim3((uint32_t)((probes * 64u + 255u) / 256u)), dim3(256), 0, s, sv, pb, first, count, d, hits, hits_out, back_out);
 }
 void launch_lightmap_lookup(hipStream_t s, const LmView& lm, uint32_t n, const uint32_t* instance, const uint32_t* tri, const float* u, const float* v,
                             float* rgb, uint8_t* mapped)

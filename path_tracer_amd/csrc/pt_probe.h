@@ -41,4 +41,71 @@ PT_HD void probe_ray(uint64_t seed, uint32_t n_sobol, uint32_t key, uint32_t sam
     probe_sh9(d, y);
 }
 
+// The probe grid's lookup (pt_set_probe_grid; the definition is include/pt_api.h's, operation for operation): the irradiance over pi that the
+// grid's SH9 radiance probes give a surface at p with normal n, trilinear over the cell's eight corners with the invalid ones left out and
+// the rest renormalised.  Each corner is EVALUATED before it is blended: three running sums instead of 27 blended coefficients, and a corner
+// is seven 16-byte loads that are issued one corner ahead of the arithmetic.  Returns lit (some valid corner has weight); *out is the clamped
+// I where lit and 0 where not.  No index leaves the grid whatever p is (a NaN coordinate lands on node 0 of its axis).
+// Shared by the baked view's probe ending, the unit hook's kernel and the hook's host evaluation.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define PT_PROBE_PIN(a, b, c, d) __asm__ volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : : "memory")
+#else
+#define PT_PROBE_PIN(a, b, c, d) ((void)0)
+#endif
+PT_HD bool probe_grid_lookup(const ProbeGridView& g, f3 p, f3 n, f3* out)
+{
+    const float pp[3] = {p.x + g.bias * n.x, p.y + g.bias * n.y, p.z + g.bias * n.z};
+    uint32_t i0[3], i1[3];
+    float f[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+    {
+        float x = (pp[a] - g.origin[a]) / g.cell[a];
+        const float top = (float)(g.count[a] - 1u);
+        x = !(x > 0.0f) ? 0.0f : (x > top ? top : x);
+        i0[a] = (uint32_t)x;
+        f[a] = x - truncf(x);
+        i1[a] = i0[a] + 1u < g.count[a] ? i0[a] + 1u : i0[a];
+    }
+    const float d[3] = {n.x, n.y, n.z};
+    float yc[9];
+    probe_sh9(d, yc);
+#pragma unroll
+    for (int m = 1; m < 4; ++m) yc[m] = 0.6666667f * yc[m];
+#pragma unroll
+    for (int m = 4; m < 9; ++m) yc[m] = 0.25f * yc[m];
+    const uint32_t row[2] = {i0[2] * g.count[1], i1[2] * g.count[1]};
+    const uint32_t line[4] = {(row[0] + i0[1]) * g.count[0], (row[0] + i1[1]) * g.count[0], (row[1] + i0[1]) * g.count[0], (row[1] + i1[1]) * g.count[0]};
+    float W = 0.0f, E[3] = {0.0f, 0.0f, 0.0f};
+    DProbe r = g.nodes[line[0] + i0[0]];
+#pragma unroll
+    for (uint32_t k = 0; k < 8u; ++k)
+    {
+        const DProbe cur = r;
+        if (k < 7u) r = g.nodes[line[(k + 1u) >> 1] + (((k + 1u) & 1u) ? i1[0] : i0[0])];
+        const float wx = (k & 1u) ? f[0] : 1.0f - f[0], wy = (k & 2u) ? f[1] : 1.0f - f[1], wz = (k & 4u) ? f[2] : 1.0f - f[2];
+        const float w = ((wx * wy) * wz) * (cur.valid != 0.0f ? 1.0f : 0.0f);
+        W = k ? W + w : w;
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+        {
+            float e = yc[0] * cur.sh[c] + yc[1] * cur.sh[3 + c];
+#pragma unroll
+            for (int m = 2; m < 9; ++m) e = e + yc[m] * cur.sh[3 * m + c];
+            E[c] = k ? E[c] + w * e : w * e;
+        }
+        PT_PROBE_PIN(W, E[0], E[1], E[2]);
+    }
+    const bool lit = W > 0.0f;
+    float I[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+    {
+        const float v = E[c] / W;
+        I[c] = lit && v > 0.0f ? v : 0.0f;
+    }
+    *out = f3{I[0], I[1], I[2]};
+    return lit;
+}
+
 } // namespace pt

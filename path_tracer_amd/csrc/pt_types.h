@@ -128,6 +128,23 @@ struct LmView
     const DLightmap* leaf;
     const DTriUV* tri_uv;
 };
+// The probe grid (pt_set_probe_grid): one record per node, node (ix, iy, iz) at (iz * ny + iy) * nx + ix: the 27 radiance SH coefficients
+// (coefficient-major, channel-minor) and the valid word (1.0f or 0.0f; an invalid node's coefficients are kept as zeros), seven 16-byte words.
+struct alignas(16) DProbe
+{
+    float sh[27];
+    float valid;
+};
+static_assert(sizeof(DProbe) == 112, "seven 16-byte words");
+// What a probe-grid lookup (probe_grid_lookup, pt_probe.h) reads: a view of its own, handed only to the baked view's probe ending and to the
+// unit hook's kernel; the same struct points at the host's copy for the host evaluation.
+struct ProbeGridView
+{
+    const DProbe* nodes;
+    float origin[3], cell[3];
+    uint32_t count[3];
+    float bias;
+};
 
 // the barycentrics (u = v) of the light sampler's one-point quadrature (pt_api.h, LIGHT WEIGHT): a light triangle's weight is its area times
 // the length of its emitted colour there.  One constant for the host's weights (HostScene::build_lights) and the kernels' pdf (resolve_nee)

@@ -4,10 +4,14 @@ pt_render_baked(1 sample) at K = 0 and K = 2, beside pt_render_guides_followed a
 the 1-spp pt_frame.  Every figure is the median of --calls blocking calls, taken --reps times with the routes alternating, so that a drift
 of the shared machine touches all of them; the report keeps every repeat, the spread is theirs.
 
-    python tools/baked_view_bench.py [--calls 20] [--reps 3] [--what all|guides] [--out report.json]
+    python tools/baked_view_bench.py [--calls 20] [--reps 3] [--what all|guides] [--probes] [--out report.json]
 
 --what guides times the guides call alone and runs on a tree that has no baked view: run it from the parent commit's tree and from this one,
-turn about, for the comparison across the two (the guide kernels themselves must not have moved)."""
+turn about, for the comparison across the two (the guide kernels themselves must not have moved).
+
+--probes (profiles/r24_probe_grid.md) times the probe ending instead: no map anywhere, so that a 16 x 16 x 16 probe grid over the scene's
+bounds is the only light source of every final surface, ms per pt_render_baked(1 sample) at K = 0 and K = 2 with the grid beside the same
+calls on a context without one; and pt_probe_backfaces for 4 096 probes x 256 samples beside pt_bake_probes of the same shape."""
 import argparse
 import json
 import os
@@ -46,12 +50,15 @@ def main():
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--what", choices=["all", "guides"], default="all")
+    ap.add_argument("--probes", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("baked_view_bench needs the GPU: there is nothing to time without one")
     from path_tracer_amd import api, scenes
+    if args.probes:
+        return probes(args, api, scenes)
     sc = scenes.cornell_box(W, H)
     baked = args.what == "all"
     if baked:
@@ -92,12 +99,51 @@ def main():
     for _ in range(args.reps):
         for into, fn in routes:
             into.append(round(timed(fn, args.calls), 4))
+    emit(report, args.out)
+
+
+def emit(report, out):
     line = json.dumps(report)
     print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
             f.write(line + "\n")
+
+
+GRID, CENSUS_PROBES, CENSUS_SAMPLES = 16, 4096, 256
+
+
+def probes(args, api, scenes):
+    sc = scenes.cornell_box(W, H)
+    bare, lit = api.Renderer(sc, W, H, max_bounces=DEPTH), api.Renderer(sc, W, H, max_bounces=DEPTH)
+    pts = np.concatenate([(m.positions.reshape(-1, 3) @ mat[:, :3].T + mat[:, 3]) for m in sc.models for mat in m.matrices.astype(np.float64)])
+    lo, hi = pts.min(0), pts.max(0)
+    cell = (hi - lo) / GRID
+    rng = np.random.default_rng(24)
+    sh = rng.uniform(-0.2, 0.2, (GRID, GRID, GRID, 9, 3)).astype(np.float32)
+    sh[..., 0, :] = rng.uniform(1.0, 3.0, (GRID, GRID, GRID, 3)).astype(np.float32)
+    lit.set_probe_grid(lo + 0.5 * cell, cell, sh, normal_bias=0.01 * float(cell.min()))
+    pos = (lo + rng.uniform(0.0, 1.0, (CENSUS_PROBES, 3)) * (hi - lo)).astype(np.float32)
+    report = {"width": W, "height": H, "grid": GRID, "calls": args.calls, "what": "probes", "baked_ms": {str(k): [] for k in HOPS},
+              "baked_probes_ms": {str(k): [] for k in HOPS}, "census": [CENSUS_PROBES, CENSUS_SAMPLES], "backfaces_ms": [], "bake_probes_ms": []}
+    sample = [0]
+
+    def view(r, k):
+        sample[0] += 1
+        r.render_baked(sample[0], 1, follow=k, unlit=(0.5, 0.5, 0.5), download=False)
+    routes = []
+    for k in HOPS:
+        routes.append((report["baked_ms"][str(k)], lambda k=k: view(bare, k), args.calls))
+        routes.append((report["baked_probes_ms"][str(k)], lambda k=k: view(lit, k), args.calls))
+    routes.append((report["backfaces_ms"], lambda: bare.probe_backfaces(pos, CENSUS_SAMPLES), 3))
+    routes.append((report["bake_probes_ms"], lambda: bare.bake_probes(pos, CENSUS_SAMPLES), 3))
+    for _, fn, _ in routes:
+        fn()
+    for _ in range(args.reps):
+        for into, fn, calls in routes:
+            into.append(round(timed(fn, calls), 4))
+    emit(report, args.out)
 
 
 if __name__ == "__main__":
