@@ -2997,7 +2997,7 @@ int follow_params(pt_ctx* c, const pt_guide_params* gp, const char* who)
 // chains into the guides (sum null) or into the mean-albedo sums and queues the others' next rays into the other hook queue.  That
 // queue's count stays on the device, in the head word the next trace reads; a hop nobody reached is two empty launches.  No chain goes
 // on from the last hop, so that launch gets no next queue (max_hops 0, the first-hit guides, never has one).
-// (ending(q, h): the launch that ends or continues the chains of hop h; q holds the hop's queues, hits, count words and state)
+// (ending(q): the launch that ends or continues the chains of hop q.hop; q holds the hop's queues, hits, count words, state and hop numbers)
 template <class Ending>
 int walk_chains(pt_ctx* c, uint32_t sample, uint32_t max_hops, Ending&& ending)
 {
@@ -3024,13 +3024,16 @@ int walk_chains(pt_ctx* c, uint32_t sample, uint32_t max_hops, Ending&& ending)
             a.n_next = head[nxt];
         }
         a.state = max_hops ? (f4*)c->d_gstate.p : nullptr;
-        ending(a, h);
+        a.cap = c->local_pixels;
+        a.hop = h;
+        a.max_hops = max_hops;
+        ending(a);
     }
     return PT_OK;
 }
 int follow_chains(pt_ctx* c, uint32_t sample, uint32_t max_hops, f4* sum)
 {
-    return walk_chains(c, sample, max_hops, [&](const ChainHop& q, uint32_t h) {
+    return walk_chains(c, sample, max_hops, [&](const ChainHop& q) {
         FollowArgs a{};
         static_cast<ChainHop&>(a) = q;
         a.position = (f4*)c->d_gpos.p;
@@ -3040,9 +3043,6 @@ int follow_chains(pt_ctx* c, uint32_t sample, uint32_t max_hops, f4* sum)
         a.instance = (uint32_t*)c->d_ginst.p;
         a.hops = (uint8_t*)c->d_ghops.p;
         a.sum = sum;
-        a.cap = c->local_pixels;
-        a.hop = h;
-        a.max_hops = max_hops;
         launch_guide_follow(c->stream, c->sv, c->tex, a);
     });
 }
@@ -3053,15 +3053,12 @@ int baked_chains(pt_ctx* c, uint32_t sample, const pt_baked_params& p)
     const bool grid = !c->probes.empty();
     EnvView env{};
     if (c->env_w) env = EnvView{(const f4*)c->d_env.p, c->env_w, c->env_h, 0u, 0u};
-    return walk_chains(c, sample, p.max_hops, [&](const ChainHop& q, uint32_t h) {
+    return walk_chains(c, sample, p.max_hops, [&](const ChainHop& q) {
         BakedArgs b{};
         static_cast<ChainHop&>(b) = q;
         b.sum = (f4*)c->d_baked_sum.p;
         b.env = env;
         std::memcpy(b.unlit, p.unlit, sizeof(b.unlit));
-        b.cap = c->local_pixels;
-        b.hop = h;
-        b.max_hops = p.max_hops;
         if (grid) launch_baked_follow_probes(c->stream, c->sv, c->tex, c->lm, b, probe_grid_view(c, (const DProbe*)c->d_probes.p));
         else launch_baked_follow(c->stream, c->sv, c->tex, c->lm, b);
     });

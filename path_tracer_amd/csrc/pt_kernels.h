@@ -289,16 +289,18 @@ void launch_shading_normal(hipStream_t s, const SceneView& sv, const TexNView& t
 // unit hooks
 // One hop of the guide chains, what every ending is handed (pt_api.cpp, walk_chains).  `in`: the hook queue launch_trace_rays_closest just traced
 // into hits (n_in: its count word); chains that go on are appended to `next` (n_next: its count word, zero before the launch; both queues hold cap
-// slots; both null at the last hop, where no chain goes on)
+// slots; both null at the last hop, where no chain goes on).  Hop `hop` of at most max_hops; the kernels of every ending are shells over one
+// chain_hop (pt_kernels.hip) that reads all of this
 struct ChainHop
 {
     RayQueue in, next;
     const f4* hits;
     const uint32_t* n_in;
     uint32_t* n_next;
-    f4* state;             // per pixel: running colour product | t sum of a chain that goes on (may be null at max_hops 0)
+    f4* state;             // per pixel: running colour product | t of a chain that goes on, summed by the guides (may be null at max_hops 0)
+    uint32_t cap, hop, max_hops;
 };
-// pt_render_guides[_followed] / pt_accumulate_albedo[_followed]: hop `hop` of the guide chains (first-hit guides: max_hops 0).  sum null: a chain
+// pt_render_guides[_followed] / pt_accumulate_albedo[_followed]: the guides' ending (first-hit guides: max_hops 0).  sum null: a chain
 // that ends writes the six guides of its pixel; else it adds its albedo product to sum[pixel]
 struct FollowArgs : ChainHop
 {
@@ -306,21 +308,19 @@ struct FollowArgs : ChainHop
     uint32_t *model, *instance;
     uint8_t* hops;
     f4* sum;
-    uint32_t cap, hop, max_hops;
 };
 void launch_guide_follow(hipStream_t s, const SceneView& sv, const TexView& tex, const FollowArgs& a);
-// pt_render_baked: hop `hop` of the same chains with the baked view's ending (include/pt_api.h states it): a chain that ends adds its baked
-// sample and 1 to sum[pixel]; state[].w is not used.  env.w == 0: the constant ambient
+// pt_render_baked: the same chains with the baked view's ending (include/pt_api.h states it): a chain that ends adds its baked sample and 1 to
+// sum[pixel]; state[].w is not read.  env.w == 0: the constant ambient
 struct BakedArgs : ChainHop
 {
     f4* sum;
     EnvView env;
     float unlit[3];
-    uint32_t cap, hop, max_hops;
 };
 void launch_baked_follow(hipStream_t s, const SceneView& sv, const TexView& tex, const LmView& lm, const BakedArgs& a);
-// ... with a probe grid set (pt_set_probe_grid): the same hop with the probe ending, kernels of their own (launch_baked_follow's keep their
-// arguments and their code)
+// ... with a probe grid set (pt_set_probe_grid): the baked ending with its probe lookup compiled in, which lights a final surface that no map
+// lights
 void launch_baked_follow_probes(hipStream_t s, const SceneView& sv, const TexView& tex, const LmView& lm, const BakedArgs& a, const ProbeGridView& grid);
 // unit hook (pt_probe_grid_lookup): probe_grid_lookup (pt_probe.h) at n positions and normals (3 floats each)
 void launch_probe_grid_lookup(hipStream_t s, const ProbeGridView& grid, uint32_t n, const float* position, const float* normal, float* rgb, uint8_t* lit);

@@ -2921,6 +2921,86 @@ __device__ __forceinline__ f3 surface_colour_at(const SceneView& sv, const TexVi
     const DMaterial& dm = sv.materials[sv.instances[inst].material];
     return surface_colour(tex, dm.texture, f3{dm.colour[0], dm.colour[1], dm.colour[2]}, tri, u, v);
 }
+// ---- one hop of the followed chains (pt_api.cpp, walk_chains), stated once for the guides and the baked view.  chain_hop<FIRST> is what
+// their kernels share: the slot's hit, ray and pixel, the colour product and t sum out of state[pixel], whether the chain goes on, its
+// parked state, its next ray and the append to `next`.  The Ending says what a chain that stops here leaves: miss(first, slot, pixel, d)
+// for a ray that left the scene, surface(ChainEnd) for a surface the chain is not followed through (or the hop cap); both return a value
+// and store(pixel, value) puts it away at the hop's one tail.  (Endings that stored in miss() and in surface() themselves cost the probe
+// ending 28 registers and two waves per SIMD: profiles/r25_chain_hop.md.)
+struct ChainEnd // the surface a chain ends on
+{
+    uint32_t slot, px, inst, tri, kind;
+    f4 hit;          // the slot's: this hop's t | u | v | id
+    float t;         // summed over the hops where the ending asks (kSumT)
+    f3 d, c, p, nrm; // the ray's direction, the colour product with this surface in it, the hit position, the face-forwarded world normal
+    bool front;
+};
+// the lanes of a wave that go on append their next rays: one ballot and one atomic on the queue's count word per wave, the lane's rank by
+// mbcnt.  Every lane of the block must call it (no early exit before it), so that lane 0 of each wave can reserve for the others
+__device__ __forceinline__ void chain_append(const ChainHop& a, bool go_on, const f4& next_a, const f4& next_b)
+{
+    const uint64_t m = __ballot(go_on);
+    if (m == 0ull) return;
+    uint32_t base = 0u;
+    if (lane_id() == 0u) base = atomicAdd(a.n_next, (uint32_t)__popcll(m));
+    base = __builtin_amdgcn_readfirstlane(base);
+    if (go_on)
+    {
+        const uint32_t pos = base + mbcnt64(m); // < the chains that go on <= n <= a.cap, the queues' slots
+        a.next.a[pos] = next_a;
+        a.next.b[pos] = next_b;
+    }
+}
+template <bool FIRST, class Ending>
+__device__ __forceinline__ void chain_hop(const SceneView& sv, const TexView& tex, const ChainHop& a, const Ending& e)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t n = min(*a.n_in, a.cap);
+    bool go_on = false;
+    f4 next_a{}, next_b{};
+    if (i < n)
+    {
+        const f4 hit = a.hits[i];
+        const f4 rb = a.in.b[i];
+        const uint32_t px = asu(rb.w);
+        const f3 d = xyz(rb);
+        f3 out{};
+        const uint32_t hid = asu(hit.w);
+        if (hid == MISS_ID) out = e.miss(FIRST, i, px, d);
+        else
+        {
+            // (one gather after the other, each behind a compiler barrier, an ending's own gathers last: hoisting all their loads to the top
+            // costs scratch at 64 VGPRs)
+            const uint32_t inst = hid >> sv.prim_bits, tri = hid & ((1u << sv.prim_bits) - 1u);
+            const DMaterial& dm = sv.materials[sv.instances[inst].material];
+            f3 c = surface_colour(tex, dm.texture, f3{dm.colour[0], dm.colour[1], dm.colour[2]}, tri, hit.y, hit.z);
+            float t = hit.x;
+            if (!FIRST)
+            {
+                const f4 s = a.state[px];
+                c = xyz(s) * c;
+                if (Ending::kSumT) t = s.w + t;
+            }
+            const uint32_t kind = dm.kind;
+            __asm__ volatile("" ::: "memory");
+            bool front;
+            const f3 nrm = hit_normal(sv, inst, tri, hit.y, hit.z, d, front);
+            const FollowDir f = guide_follow_dir(kind, dm.ior, d, nrm, front);
+            go_on = f.followed && a.hop < a.max_hops;
+            __asm__ volatile("" ::: "memory");
+            const f3 p = fma3(d, bc3(hit.x), xyz(a.in.a[i]));
+            if (go_on)
+            {
+                a.state[px] = f4{c.x, c.y, c.z, t};
+                next_a = f4{p.x, p.y, p.z, __builtin_inff()};
+                next_b = f4{f.wo.x, f.wo.y, f.wo.z, asf(px)};
+            }
+            else out = e.surface(ChainEnd{i, px, inst, tri, kind, hit, t, d, c, p, nrm, front});
+        }
+        if (!go_on) e.store(px, out);
+    }
+    chain_append(a, go_on, next_a, next_b);
+}
 // ---- the guides (pt_render_guides, pt_render_guides_followed, pt_accumulate_albedo[_followed]; include/pt_api.h states the chain)
 // Hop a.hop of every live chain: one thread per ray slot of the `in` hook queue (slot = local pixel at hop 0, compacted afterwards; the
 // ray's pixel rides in rq.b[].w, its origin in rq.a[]), its closest hit in hits[slot].  A chain that ends here (a miss, a rough surface,
@@ -2937,254 +3017,111 @@ __device__ __forceinline__ f3 surface_colour_at(const SceneView& sv, const TexVi
 // between hops.  Where a chain lands in `next` shows in nothing it writes: every output is addressed by pixel.
 // First-hit guides are the chains of max_hops = 0.  At the last hop (a.hop == a.max_hops) no lane goes on, so `next` and n_next are never
 // dereferenced, and hop 0 never reads `state`: the host passes null for what a launch cannot touch (all three at max_hops = 0).
+template <bool ACCUM>
+struct GuideEnding
+{
+    const SceneView& sv;
+    const FollowArgs& a;
+    static constexpr bool kSumT = true; // position.w is the t of the whole chain
+    __device__ __forceinline__ f3 miss(bool first, uint32_t i, uint32_t px, const f3& d) const
+    {
+        if (!ACCUM)
+        {
+            const f3 far = fma3(d, bc3(1e5f), xyz(a.in.a[i]));
+            a.position[px] = f4{far.x, far.y, far.z, 1e5f};
+            a.normal[px] = f4{0.0f, 0.0f, 0.0f, 0.0f};
+            a.model[px] = MISS_ID;
+            a.instance[px] = MISS_ID;
+        }
+        return bc3(ACCUM ? 1.0f : 0.0f);
+    }
+    __device__ __forceinline__ f3 surface(const ChainEnd& h) const
+    {
+        if (!ACCUM)
+        {
+            a.position[h.px] = f4{h.p.x, h.p.y, h.p.z, h.t};
+            a.normal[h.px] = f4{h.nrm.x, h.nrm.y, h.nrm.z, 0.0f};
+            a.model[h.px] = sv.instances[h.inst].blas | (a.hop << 28);
+            a.instance[h.px] = h.inst;
+        }
+        return h.c;
+    }
+    __device__ __forceinline__ void store(uint32_t px, const f3& c) const
+    {
+        if (ACCUM)
+        {
+            const f4 s = a.sum[px];
+            a.sum[px] = f4{s.x + c.x, s.y + c.y, s.z + c.z, s.w + 1.0f};
+        }
+        else
+        {
+            a.albedo[px] = f4{c.x, c.y, c.z, 0.0f};
+            a.hops[px] = (uint8_t)a.hop;
+        }
+    }
+};
 template <bool ACCUM, bool FIRST>
 __global__ void __launch_bounds__(256, 8) k_guide_follow(const SceneView sv, const TexView tex, const FollowArgs a)
 {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t n = min(*a.n_in, a.cap);
-    bool go_on = false;
-    f4 next_a{}, next_b{};
-    if (i < n)
-    {
-        const f4 hit = a.hits[i];
-        const f4 rb = a.in.b[i];
-        const uint32_t px = asu(rb.w);
-        const f3 d = xyz(rb);
-        f3 c{ACCUM ? 1.0f : 0.0f, ACCUM ? 1.0f : 0.0f, ACCUM ? 1.0f : 0.0f}; // what a chain that ended as a miss leaves
-        const uint32_t hid = asu(hit.w);
-        if (hid == MISS_ID)
-        {
-            if (!ACCUM)
-            {
-                const f3 far = fma3(d, bc3(1e5f), xyz(a.in.a[i]));
-                a.position[px] = f4{far.x, far.y, far.z, 1e5f};
-                a.normal[px] = f4{0.0f, 0.0f, 0.0f, 0.0f};
-                a.model[px] = MISS_ID;
-                a.instance[px] = MISS_ID;
-            }
-        }
-        else
-        {
-            // (one gather after the other, each behind a compiler barrier: hoisting all their loads to the top costs scratch at 64 VGPRs)
-            const uint32_t inst = hid >> sv.prim_bits, tri = hid & ((1u << sv.prim_bits) - 1u);
-            const DMaterial& dm = sv.materials[sv.instances[inst].material];
-            c = surface_colour(tex, dm.texture, f3{dm.colour[0], dm.colour[1], dm.colour[2]}, tri, hit.y, hit.z);
-            float t = hit.x;
-            if (!FIRST)
-            {
-                const f4 s = a.state[px];
-                c = xyz(s) * c;
-                t = s.w + t;
-            }
-            __asm__ volatile("" ::: "memory");
-            bool front;
-            const f3 nrm = hit_normal(sv, inst, tri, hit.y, hit.z, d, front);
-            const FollowDir f = guide_follow_dir(dm.kind, dm.ior, d, nrm, front);
-            go_on = f.followed && a.hop < a.max_hops;
-            __asm__ volatile("" ::: "memory");
-            const f3 p = fma3(d, bc3(hit.x), xyz(a.in.a[i]));
-            if (go_on)
-            {
-                a.state[px] = f4{c.x, c.y, c.z, t};
-                next_a = f4{p.x, p.y, p.z, __builtin_inff()};
-                next_b = f4{f.wo.x, f.wo.y, f.wo.z, asf(px)};
-            }
-            else if (!ACCUM)
-            {
-                a.position[px] = f4{p.x, p.y, p.z, t};
-                a.normal[px] = f4{nrm.x, nrm.y, nrm.z, 0.0f};
-                a.model[px] = sv.instances[inst].blas | (a.hop << 28);
-                a.instance[px] = inst;
-            }
-        }
-        if (!go_on)
-        {
-            if (ACCUM)
-            {
-                const f4 s = a.sum[px];
-                a.sum[px] = f4{s.x + c.x, s.y + c.y, s.z + c.z, s.w + 1.0f};
-            }
-            else
-            {
-                a.albedo[px] = f4{c.x, c.y, c.z, 0.0f};
-                a.hops[px] = (uint8_t)a.hop;
-            }
-        }
-    }
-    // every lane of the block is here (no early exit above), so lane 0 of each wave can reserve for it
-    const uint64_t m = __ballot(go_on);
-    if (m == 0ull) return;
-    uint32_t base = 0u;
-    if (lane_id() == 0u) base = atomicAdd(a.n_next, (uint32_t)__popcll(m));
-    base = __builtin_amdgcn_readfirstlane(base);
-    if (go_on)
-    {
-        const uint32_t pos = base + mbcnt64(m); // < the chains that go on <= n <= a.cap, the queues' slots
-        a.next.a[pos] = next_a;
-        a.next.b[pos] = next_b;
-    }
+    chain_hop<FIRST>(sv, tex, a, GuideEnding<ACCUM>{sv, a});
 }
-// ---- the baked view (pt_render_baked; include/pt_api.h states the sample).  k_guide_follow's chains, hop by hop through the same queues, with
-// another ending: a chain that ends adds its baked sample B and 1 to sum[pixel], one binary32 add per component, no finite check and no
-// clamp.  B = the running colour product R on a light; R * the lightmap at the hit on a front face of a leaf that has a map; R * unlit on any
-// other surface; the environment (or the constant ambient) of a miss, times R of the hop before unless the camera ray itself missed.  One
-// thread per ray slot, every output addressed by pixel, the next hop reserved with one ballot and one atomic per wave: as k_guide_follow,
-// whose remarks on the queues, the count words and what hop 0 and the last hop never touch hold here.  state[pixel].w is not used.
+// ---- the baked view (pt_render_baked; include/pt_api.h states the sample).  The same chains with another ending: a chain that ends adds its
+// baked sample B and 1 to sum[pixel], one binary32 add per component, no finite check and no clamp.  B = the running colour product R on a
+// light; R * the lightmap at the hit on a front face of a leaf that has a map; R * unlit on any other surface; the environment (or the
+// constant ambient) of a miss, times R of the hop before unless the camera ray itself missed.  PROBES, with a probe grid set
+// (pt_set_probe_grid): a final surface that no map lights is lit by the grid where the grid is lit, by unlit where not; P and n are the
+// guides' (the hit position, the face-forwarded unperturbed normal).
+template <bool PROBES>
+struct BakedEnding
+{
+    const LmView& lm;
+    const BakedArgs& a;
+    const ProbeGridView* grid; // null without PROBES
+    // nothing here reads t, and carrying its sum through both barriers costs the probe ending's later hops a 67th register (the parent's 66 are
+    // the bound: profiles/r25_chain_hop.md), so state[pixel].w holds one hop's t here
+    static constexpr bool kSumT = false;
+    __device__ __forceinline__ f3 miss(bool first, uint32_t i, uint32_t px, const f3& d) const
+    {
+        const f3 b = a.env.w ? env_lookup(a.env, d) : f3{0.006f, 0.006f, 0.006f};
+        return first ? b : xyz(a.state[px]) * b;
+    }
+    __device__ __forceinline__ f3 surface(const ChainEnd& h) const
+    {
+        if (h.kind == MAT_EMISSIVE) return h.c;
+        f3 l{a.unlit[0], a.unlit[1], a.unlit[2]};
+        bool mapped = false;
+        if (h.front) // the bake lit the front side only
+        {
+            const f3 m = lightmap_at(lm, h.inst, h.tri, h.hit.y, h.hit.z, &mapped);
+            if (mapped) l = m;
+        }
+        if (PROBES && !mapped) // the grid lights what no map lights, where it is lit itself
+        {
+            // the grid's corners after the map's four texels, and P made again behind the barrier: h.p kept across the map's gather is five
+            // registers more
+            __asm__ volatile("" ::: "memory");
+            f3 irr;
+            if (probe_grid_lookup(*grid, fma3(h.d, bc3(h.hit.x), xyz(a.in.a[h.slot])), h.nrm, &irr)) l = irr;
+        }
+        return h.c * l;
+    }
+    __device__ __forceinline__ void store(uint32_t px, const f3& b) const
+    {
+        const f4 s = a.sum[px];
+        a.sum[px] = f4{s.x + b.x, s.y + b.y, s.z + b.z, s.w + 1.0f};
+    }
+};
 template <bool FIRST>
 __global__ void __launch_bounds__(256, 8) k_baked_follow(const SceneView sv, const TexView tex, const LmView lm, const BakedArgs a)
 {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t n = min(*a.n_in, a.cap);
-    bool go_on = false;
-    f4 next_a{}, next_b{};
-    if (i < n)
-    {
-        const f4 hit = a.hits[i];
-        const f4 rb = a.in.b[i];
-        const uint32_t px = asu(rb.w);
-        const f3 d = xyz(rb);
-        f3 b{0.0f, 0.0f, 0.0f};
-        const uint32_t hid = asu(hit.w);
-        if (hid == MISS_ID)
-        {
-            b = a.env.w ? env_lookup(a.env, d) : f3{0.006f, 0.006f, 0.006f};
-            if (!FIRST) b = xyz(a.state[px]) * b;
-        }
-        else
-        {
-            // (one gather after the other, each behind a compiler barrier, the map's four texels last: see k_guide_follow)
-            const uint32_t inst = hid >> sv.prim_bits, tri = hid & ((1u << sv.prim_bits) - 1u);
-            const DMaterial& dm = sv.materials[sv.instances[inst].material];
-            f3 c = surface_colour(tex, dm.texture, f3{dm.colour[0], dm.colour[1], dm.colour[2]}, tri, hit.y, hit.z);
-            if (!FIRST) c = xyz(a.state[px]) * c;
-            const uint32_t kind = dm.kind;
-            __asm__ volatile("" ::: "memory");
-            bool front;
-            const f3 nrm = hit_normal(sv, inst, tri, hit.y, hit.z, d, front);
-            const FollowDir f = guide_follow_dir(kind, dm.ior, d, nrm, front);
-            go_on = f.followed && a.hop < a.max_hops;
-            __asm__ volatile("" ::: "memory");
-            if (go_on)
-            {
-                const f3 p = fma3(d, bc3(hit.x), xyz(a.in.a[i]));
-                a.state[px] = f4{c.x, c.y, c.z, 0.0f};
-                next_a = f4{p.x, p.y, p.z, __builtin_inff()};
-                next_b = f4{f.wo.x, f.wo.y, f.wo.z, asf(px)};
-            }
-            else if (kind == MAT_EMISSIVE) b = c;
-            else
-            {
-                f3 l{a.unlit[0], a.unlit[1], a.unlit[2]};
-                if (front) // the bake lit the front side only
-                {
-                    bool mapped;
-                    const f3 m = lightmap_at(lm, inst, tri, hit.y, hit.z, &mapped);
-                    if (mapped) l = m;
-                }
-                b = c * l;
-            }
-        }
-        if (!go_on)
-        {
-            const f4 s = a.sum[px];
-            a.sum[px] = f4{s.x + b.x, s.y + b.y, s.z + b.z, s.w + 1.0f};
-        }
-    }
-    // every lane of the block is here (no early exit above), so lane 0 of each wave can reserve for it
-    const uint64_t m = __ballot(go_on);
-    if (m == 0ull) return;
-    uint32_t base = 0u;
-    if (lane_id() == 0u) base = atomicAdd(a.n_next, (uint32_t)__popcll(m));
-    base = __builtin_amdgcn_readfirstlane(base);
-    if (go_on)
-    {
-        const uint32_t pos = base + mbcnt64(m); // < the chains that go on <= n <= a.cap, the queues' slots
-        a.next.a[pos] = next_a;
-        a.next.b[pos] = next_b;
-    }
+    chain_hop<FIRST>(sv, tex, a, BakedEnding<false>{lm, a, nullptr});
 }
-// ... with a probe grid set (pt_set_probe_grid): k_baked_follow with another third ending, as a kernel of its own so that the one above keeps its
-// arguments and its code.  A final surface that no map lights is lit by the grid where the grid is lit, by unlit where not; P and n are the
-// guides' (the hit position, the face-forwarded unperturbed normal).  The corner being evaluated and the one in flight are 56 registers and
-// the ending must not spill, so its bounds leave it 128; it takes 66 (seven waves per SIMD) and no scratch (profiles/r24_probe_grid.md).
+// The corner being evaluated and the one in flight are 56 registers and the probe ending must not spill, so its bounds leave it 128; it takes
+// 66 (seven waves per SIMD) and no scratch (profiles/r24_probe_grid.md).
 template <bool FIRST>
 __global__ void __launch_bounds__(256, 4) k_baked_follow_probes(const SceneView sv, const TexView tex, const LmView lm, const BakedArgs a, const ProbeGridView grid)
 {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t n = min(*a.n_in, a.cap);
-    bool go_on = false;
-    f4 next_a{}, next_b{};
-    if (i < n)
-    {
-        const f4 hit = a.hits[i];
-        const f4 rb = a.in.b[i];
-        const uint32_t px = asu(rb.w);
-        const f3 d = xyz(rb);
-        f3 b{0.0f, 0.0f, 0.0f};
-        const uint32_t hid = asu(hit.w);
-        if (hid == MISS_ID)
-        {
-            b = a.env.w ? env_lookup(a.env, d) : f3{0.006f, 0.006f, 0.006f};
-            if (!FIRST) b = xyz(a.state[px]) * b;
-        }
-        else
-        {
-            // (one gather after the other, each behind a compiler barrier, the grid's corners last: see k_guide_follow)
-            const uint32_t inst = hid >> sv.prim_bits, tri = hid & ((1u << sv.prim_bits) - 1u);
-            const DMaterial& dm = sv.materials[sv.instances[inst].material];
-            f3 c = surface_colour(tex, dm.texture, f3{dm.colour[0], dm.colour[1], dm.colour[2]}, tri, hit.y, hit.z);
-            if (!FIRST) c = xyz(a.state[px]) * c;
-            const uint32_t kind = dm.kind;
-            __asm__ volatile("" ::: "memory");
-            bool front;
-            const f3 nrm = hit_normal(sv, inst, tri, hit.y, hit.z, d, front);
-            const FollowDir f = guide_follow_dir(kind, dm.ior, d, nrm, front);
-            go_on = f.followed && a.hop < a.max_hops;
-            __asm__ volatile("" ::: "memory");
-            if (go_on)
-            {
-                const f3 p = fma3(d, bc3(hit.x), xyz(a.in.a[i]));
-                a.state[px] = f4{c.x, c.y, c.z, 0.0f};
-                next_a = f4{p.x, p.y, p.z, __builtin_inff()};
-                next_b = f4{f.wo.x, f.wo.y, f.wo.z, asf(px)};
-            }
-            else if (kind == MAT_EMISSIVE) b = c;
-            else
-            {
-                f3 l{a.unlit[0], a.unlit[1], a.unlit[2]};
-                bool mapped = false;
-                if (front) // the bake lit the front side only
-                {
-                    const f3 m = lightmap_at(lm, inst, tri, hit.y, hit.z, &mapped);
-                    if (mapped) l = m;
-                }
-                if (!mapped) // the grid lights what no map lights, where it is lit itself
-                {
-                    __asm__ volatile("" ::: "memory");
-                    f3 irr;
-                    if (probe_grid_lookup(grid, fma3(d, bc3(hit.x), xyz(a.in.a[i])), nrm, &irr)) l = irr;
-                }
-                b = c * l;
-            }
-        }
-        if (!go_on)
-        {
-            const f4 s = a.sum[px];
-            a.sum[px] = f4{s.x + b.x, s.y + b.y, s.z + b.z, s.w + 1.0f};
-        }
-    }
-    // every lane of the block is here (no early exit above), so lane 0 of each wave can reserve for it
-    const uint64_t m = __ballot(go_on);
-    if (m == 0ull) return;
-    uint32_t base = 0u;
-    if (lane_id() == 0u) base = atomicAdd(a.n_next, (uint32_t)__popcll(m));
-    base = __builtin_amdgcn_readfirstlane(base);
-    if (go_on)
-    {
-        const uint32_t pos = base + mbcnt64(m); // < the chains that go on <= n <= a.cap, the queues' slots
-        a.next.a[pos] = next_a;
-        a.next.b[pos] = next_b;
-    }
+    chain_hop<FIRST>(sv, tex, a, BakedEnding<true>{lm, a, &grid});
 }
 // unit hook of the probe grid's lookup: rgb, lit = probe_grid_lookup
 __global__ void __launch_bounds__(256, 4) k_probe_grid_lookup(const ProbeGridView grid, const uint32_t n, const float* __restrict__ position,
@@ -3748,27 +3685,25 @@ void launch_guide_rays(hipStream_t s, const RenderParams& rp, const CameraView& 
         hipLaunchKernelGGL(k_guide_rays<kind>, dim3((rp.local_pixels + 255u) / 256u), dim3(256), 0, s, rp, camera_arg<kind>(cam, opt), rq, n_and_heads);
     });
 }
-void launch_guide_follow(hipStream_t s, const SceneView& sv, const TexView& tex, const FollowArgs& a)
+// a hop's launch: none without slots, one thread per slot, the FIRST instantiation at hop 0 (it never reads `state`)
+template <class Kernel, class... Args>
+void launch_chain_hop(hipStream_t s, const ChainHop& a, Kernel first, Kernel later, const Args&... args)
 {
     if (a.cap == 0u) return;
-    const dim3 grid((a.cap + 255u) / 256u);
-    auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, sv, tex, a); };
-    if (a.sum) a.hop == 0u ? go(k_guide_follow<true, true>) : go(k_guide_follow<true, false>);
-    else a.hop == 0u ? go(k_guide_follow<false, true>) : go(k_guide_follow<false, false>);
+    hipLaunchKernelGGL(a.hop == 0u ? first : later, dim3((a.cap + 255u) / 256u), dim3(256), 0, s, args...);
+}
+void launch_guide_follow(hipStream_t s, const SceneView& sv, const TexView& tex, const FollowArgs& a)
+{
+    if (a.sum) launch_chain_hop(s, a, k_guide_follow<true, true>, k_guide_follow<true, false>, sv, tex, a);
+    else launch_chain_hop(s, a, k_guide_follow<false, true>, k_guide_follow<false, false>, sv, tex, a);
 }
 void launch_baked_follow(hipStream_t s, const SceneView& sv, const TexView& tex, const LmView& lm, const BakedArgs& a)
 {
-    if (a.cap == 0u) return;
-    const dim3 grid((a.cap + 255u) / 256u);
-    if (a.hop == 0u) hipLaunchKernelGGL(k_baked_follow<true>, grid, dim3(256), 0, s, sv, tex, lm, a);
-    else hipLaunchKernelGGL(k_baked_follow<false>, grid, dim3(256), 0, s, sv, tex, lm, a);
+    launch_chain_hop(s, a, k_baked_follow<true>, k_baked_follow<false>, sv, tex, lm, a);
 }
 void launch_baked_follow_probes(hipStream_t s, const SceneView& sv, const TexView& tex, const LmView& lm, const BakedArgs& a, const ProbeGridView& grid)
 {
-    if (a.cap == 0u) return;
-    const dim3 grid_dim((a.cap + 255u) / 256u);
-    if (a.hop == 0u) hipLaunchKernelGGL(k_baked_follow_probes<true>, grid_dim, dim3(256), 0, s, sv, tex, lm, a, grid);
-    else hipLaunchKernelGGL(k_baked_follow_probes<false>, grid_dim, dim3(256), 0, s, sv, tex, lm, a, grid);
+    launch_chain_hop(s, a, k_baked_follow_probes<true>, k_baked_follow_probes<false>, sv, tex, lm, a, grid);
 }
 void launch_probe_grid_lookup(hipStream_t s, const ProbeGridView& grid, uint32_t n, const float* position, const float* normal, float* rgb, uint8_t* lit)
 {

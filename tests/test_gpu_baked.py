@@ -144,15 +144,22 @@ def test_device_lookup_in_a_textured_scene_uses_its_uv_table(api):
 
 
 # ---- 2. without maps and with unlit = 1 the view is the albedo guide
+@pytest.mark.parametrize("grid", ["none", "invalid"])
 @pytest.mark.parametrize("follow", [0, 2])
-def test_unlit_one_without_maps_is_the_albedo_guide(api, follow):
+def test_unlit_one_without_maps_is_the_albedo_guide(api, follow, grid):
+    """... and with a probe grid none of whose nodes is valid: the lookup's weights sum to 0 everywhere, it lights nothing, and the probe ending
+    falls to unlit on every surface.  So the guides' ending, the baked one and the probe one leave the same bits"""
     r = api.Renderer(G.follow_room(), G.W, G.H, max_bounces=DEPTH)
+    if grid == "invalid":
+        sh = np.random.default_rng(25).uniform(1.0, 3.0, (2, 2, 2, 9, 3)).astype(F)      # bright wherever a node counted
+        r.set_probe_grid((-10.0, -10.0, -10.0), (20.0, 20.0, 20.0), sh, valid=np.zeros((2, 2, 2), bool))
+        assert r.probe_grid_info()[2] == (2, 2, 2) and r.probe_grid_info()[4] == 0
     for sample in (0, 5):
         got = _one(r, sample, follow, (1.0, 1.0, 1.0))
         r.render_guides(sample, follow=follow)
         surface = r.read_guides()[2] != MISS
         assert surface.sum() > 500 and (~surface).any()
-        assert_bit_equal(got[surface], r.read_guide_albedo()[surface], f"sample {sample}, follow {follow}")
+        assert_bit_equal(got[surface], r.read_guide_albedo()[surface], f"sample {sample}, follow {follow}, grid {grid}")
         if follow:
             assert (r.read_guide_hops()[surface] > 0).any()
 
