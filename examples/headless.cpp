@@ -37,6 +37,9 @@
 //       spanning the scene's bounds inset by half a cell (SPP samples per probe; probes that see back faces in more than a quarter of their rays
 //       are left out: pt_probe_backfaces), sets it (pt_set_probe_grid) and writes the baked view, in which the grid lights every final surface
 //       that no map lights
+//   examples/headless ... --probe-grid NX NY NZ SPP --probe-depth R --baked-view SPP out.png   also bakes the nodes' R x R octahedral depth moments
+//       from the same rays (pt_bake_probe_depth, distances clamped to 1.5 cell diagonals) and sets them (pt_set_probe_grid_depth), so that the
+//       grid's lookup weighs every node by its visibility and light stops leaking through walls
 //   examples/headless ... --bake-lightmap ... --lightmap-denoise [--baked-view ...]   bakes with second moments (pt_bake_lightmap_moments), runs the
 //       texel-space filter on the sums (pt_lightmap_denoise, default parameters) and dilates its texel MEANS: map.txt then holds means, not sums,
 //       and --baked-view sets them as they are
@@ -80,6 +83,8 @@ int main(int argc, char** argv)
     std::string lightmap_out = "";
     uint32_t baked_spp = 0;
     uint32_t probe_grid[4] = {0, 0, 0, 0}; // --probe-grid NX NY NZ SPP
+    uint32_t probe_depth = 0;              // --probe-depth R
+    bool probe_depth_given = false;
     bool lightmap_denoise = false;
     std::string baked_out = "";
     pt_projection projection{}; // PT_PROJ_PERSPECTIVE
@@ -139,6 +144,11 @@ int main(int argc, char** argv)
         {
             for (uint32_t& n : probe_grid) n = (uint32_t)std::atoi(next("--probe-grid"));
         }
+        else if (a == "--probe-depth")
+        {
+            probe_depth = (uint32_t)std::atoi(next("--probe-depth"));
+            probe_depth_given = true;
+        }
         else if (a == "--baked-view")
         {
             baked_spp = (uint32_t)std::atoi(next("--baked-view"));
@@ -168,6 +178,11 @@ int main(int argc, char** argv)
     if ((probe_grid[0] || probe_grid[1] || probe_grid[2] || probe_grid[3]) && (!with_grid || baked_out.empty()))
     {
         std::fprintf(stderr, "--probe-grid NX NY NZ SPP takes four non-zero numbers and lights --baked-view\n");
+        return 2;
+    }
+    if (probe_depth_given && (!with_grid || probe_depth < 2 || probe_depth > 16))
+    {
+        std::fprintf(stderr, "--probe-depth R takes a map side of 2..16 and goes with --probe-grid\n");
         return 2;
     }
     if (lightmap_denoise && (lightmap_out.empty() || !lightmap[2]))
@@ -352,7 +367,7 @@ int main(int argc, char** argv)
                     g.cell[k] = (box[3 + k] - box[k]) / (float)probe_grid[k];
                     g.origin[k] = box[k] + 0.5f * g.cell[k];
                 }
-                renderer.bake_probe_grid(g, probe_grid[3]);
+                renderer.bake_probe_grid(g, probe_grid[3], 0.25f, probe_depth);
             }
             renderer.render_baked(0, baked_spp, follow);
             renderer.write_baked_image(baked_out);

@@ -830,7 +830,8 @@ int pt_integrate_rays_device(pt_ctx* ctx, uint64_t n, const float* o_xyz, const 
  * pt_config.batch_spp, a render's test knob, cuts here too: wavefront batches of batch_spp * n_probes rays.  The frame is not touched.
  * Errors, before any device call: PT_ERR_STATE as pt_integrate_rays; PT_ERR_ARG for a NULL position_xyz, p or sh27 with n_probes > 0,
  * n_samples == 0, a non-zero reserved word, a position that is not finite, key_base + n_probes or first_sample + n_samples beyond 2^32.
- * Out of scope: higher bands, cosine-convolved output, visibility or depth moments, probe placement.  (pt_set_probe_grid keeps a grid of
+ * Out of scope: higher bands, cosine-convolved output, probe placement.  (pt_bake_probe_depth bakes depth moments from the same rays;
+ * pt_set_probe_grid keeps a grid of
  * such probes, scaled by the caller, and applies the cosine lobe in its lookup; pt_probe_backfaces tells which probes sit inside geometry.) */
 typedef struct pt_probe_params
 {
@@ -1071,7 +1072,8 @@ int pt_write_baked_image(pt_ctx* ctx, const char* path);
  *     chain's end (the unperturbed normal on the side the ray came from)
  * and every other ending is what it was: a mapped front face is lit by its map.  The ending is a kernel of its own, chosen on the host, so
  * without a grid every call returns the bits it returned before.  The baked sums go stale on pt_set_probe_grid as on pt_set_lightmap.
- * Out of scope: visibility or depth moments, cell-skipping and probe relocation, probes in the path tracer's own paths, a specular response,
+ * Visibility is pt_set_probe_grid_depth's, below.
+ * Out of scope: cell-skipping and probe relocation, probes in the path tracer's own paths, a specular response,
  * pt_multi_* variants, SH above band 2. */
 typedef struct pt_probe_grid
 {
@@ -1091,6 +1093,77 @@ int pt_probe_grid_lookup(pt_ctx* ctx, int on_device, uint32_t n, const float* po
  * a wave reduction, no atomics (pt_config.batch_spp, a render's test knob, cuts the ray table here as in the bake).  What fraction of back faces makes a probe unusable is the caller's policy.  The frame is not touched.
  * Errors, before any device call: those of pt_bake_probes, with hits and back in sh27's place. */
 int pt_probe_backfaces(pt_ctx* ctx, uint32_t n_probes, const float* position_xyz, const pt_probe_params* p, uint32_t* hits, uint32_t* back);
+
+/* ---- probe visibility: depth moments on an octahedral map stop the grid's light leaking through walls ------------------------------------ */
+/* The trilinear blend of pt_set_probe_grid takes a node on the far side of a wall at full weight.  With depth set, every node also holds an
+ * R x R octahedral map of the first two moments of the distance it sees, and the lookup weighs a corner by the Chebyshev bound on the chance
+ * that the node sees as far as the shaded point.  Depth is opt-in: a context that never sets it launches what it launched before.
+ * THE TEXEL of direction v in a map of side R (probe_oct_texel).  Binary32, one rounding per operation, no contraction; v is used as given
+ * and not normalised (the map is scale-free):
+ *     s  = (|vx| + |vy|) + |vz|
+ *     px = vx / s;  py = vy / s
+ *     if (vz < 0):  (px, py) = ((1 - |py|) * (px >= 0 ? 1 : -1),  (1 - |px|) * (py >= 0 ? 1 : -1))         -- both from the OLD px, py
+ *     u  = px * 0.5f + 0.5f  (two roundings);  v likewise
+ *     ix = !(u * R > 0) ? 0 : min((uint32_t)(u * R), R - 1);  iy alike                                     -- a NaN (v = 0) lands on texel 0
+ *     texel = iy * R + ix
+ * pt_probe_depth_texel is its host hook: n directions (3 floats each, any values) to n texels; it needs no context and no GPU.  PT_ERR_LIMIT
+ * for a res outside 2..16, PT_ERR_ARG for a NULL pointer with n > 0.
+ * THE BAKE.  pt_bake_probe_depth casts pt_bake_probes' rays (pt_probe_ray(key_base + j, s) from position_xyz[j]) and traces each ONCE for its
+ * closest hit, as pt_probe_backfaces does.  For each ray
+ *     d = hit ? (t < max_distance ? t : max_distance) : max_distance          t: the closest hit's parameter, what pt_trace_closest returns
+ *     texel = THE TEXEL of the ray's direction
+ *     counts[j][texel] += 1;   sums[j][texel][0] = sums[j][texel][0] + d;   sums[j][texel][1] = sums[j][texel][1] + d * d
+ * Per (probe, texel) the adds happen in ascending sample order, starting from what the arrays hold, however the ray table is cut (2^21 rays
+ * at a time, and pt_config.batch_spp as in the census): bake(0, a) then bake(a, b) equals bake(0, a + b) bit for bit.  One wave owns a probe
+ * for a launch, the launches of a call are serial on one stream, and there are no atomics.  In an empty world every ray counts max_distance.
+ * sums (n_probes * R*R * 2 floats) and counts (n_probes * R*R) are host arrays, IN/OUT.  The frame is not touched.
+ * Errors, before any device call: those of pt_probe_backfaces (with sums and counts in the outputs' place); then a res outside 2..16
+ * (PT_ERR_LIMIT), a max_distance that is not finite and > 0 (ARG), a non-zero reserved word (ARG). */
+typedef struct pt_probe_depth_params
+{
+    uint32_t first_sample, n_samples, key_base; /* as pt_probe_params */
+    uint32_t res;                               /* R: side of the octahedral map, 2..16 */
+    float max_distance;                         /* finite, > 0: a miss and every farther hit count as this */
+    uint32_t reserved[3];                       /* must be 0 */
+} pt_probe_depth_params;
+int pt_probe_depth_texel(uint32_t res, uint32_t n, const float* dir_xyz, uint32_t* texel);
+int pt_bake_probe_depth(pt_ctx* ctx, uint32_t n_probes, const float* position_xyz, const pt_probe_depth_params* p, float* sums, uint32_t* counts);
+/* DEPTH ON THE GRID.  pt_set_probe_grid_depth gives every node of the grid in force its map: moments holds nodes * R*R * 2 floats in the
+ * nodes' order, per texel the MEAN distance and the MEAN squared distance (the division by the counts is the caller's, as the 4 pi / n is for
+ * the coefficients; a texel no ray fell into should hold (max_distance, max_distance^2): nothing was seen nearer).  moments NULL with res 0
+ * clears depth (flags, vis_floor are then not read, reserved is).  pt_get_probe_grid_depth_info reports what is set, res 0 where none is.
+ * Depth belongs to a grid: ANY pt_set_probe_grid call drops it (the node count may have changed); otherwise it survives what the grid
+ * survives.  Setting or clearing depth makes the baked sums stale, as the grid does.  On the device it is a table of its own, 8 bytes per
+ * texel per node, uploaded by the next call that needs it and handed only to the kernels that read it.
+ * Errors, all before any device call (a refused call changes nothing); the first in this order is reported: a NULL v (ARG); a non-zero
+ * reserved word (ARG); no grid set (PT_ERR_STATE); moments NULL with a non-zero res, or moments with res 0 (ARG); a res outside 2..16
+ * (PT_ERR_LIMIT); flag bits other than PT_PROBE_VIS_FACING (ARG); a vis_floor that is not finite or outside 0..1 (ARG); then the moments,
+ * read last: one that is not finite or is negative (ARG).  A table that does not fit in host memory is PT_ERR_LIMIT.
+ * THE LOOKUP WITH VISIBILITY.  With depth set, corner k of THE LOOKUP above, at node (i_x, i_y, i_z), becomes (P' the biased point):
+ *     Q_a = origin_a + (float)i_a * cell_a;   v_a = P'_a - Q_a
+ *     r   = sqrtf((vx*vx + vy*vy) + vz*vz)
+ *     (m1, m2) = moments[node][THE TEXEL of v]
+ *     var = fabsf(m2 - m1 * m1);   dl = r - m1;   c = var / (var + dl * dl);   c3 = (c * c) * c
+ *     vis = r > m1 ? (c3 > vis_floor ? c3 : vis_floor) : 1.0f                                           -- a NaN c is never selected
+ *     with PT_PROBE_VIS_FACING:  cs = ((vx*nx + vy*ny) + vz*nz) / r;  h = (1.0f - cs) * 0.5f;  fb = r > 0 ? h * h + 0.2f : 1.0f
+ *     w_k = (((wx * wy) * wz) * (valid ? 1.0f : 0.0f)) * vis  [ * fb ]
+ *   and everything after w_k is what it is without depth.  Two exact cases: with every m1 at least the grid's diagonal and FACING off, vis = 1
+ *   and the result is the plain lookup bit for bit; at a valid node's own position (r = 0) the result is still max(e_node, 0) bit for bit.
+ *   Where every corner is fully occluded and vis_floor is 0, lit is false.
+ * pt_probe_grid_lookup (both on_device values) and the baked view's probe ending apply visibility whenever depth is set: kernels of their
+ * own, chosen on the host; with a grid alone every call returns the bits it returned before.
+ * Out of scope: bilinear or cosine-power filtering of the depth map across texels and its border, probe relocation and cell-skipping, probes
+ * in the path tracer's own paths, pt_multi_* variants, SH above band 2. */
+#define PT_PROBE_VIS_FACING 1u
+typedef struct pt_probe_depth
+{
+    uint32_t res;         /* R, 2..16 */
+    uint32_t flags;       /* PT_PROBE_VIS_FACING; other bits must be 0 */
+    float vis_floor;      /* finite, 0..1: the least visibility an occluded probe keeps */
+    uint32_t reserved[5]; /* must be 0 */
+} pt_probe_depth;
+int pt_set_probe_grid_depth(pt_ctx* ctx, const pt_probe_depth* v, const float* moments);
+int pt_get_probe_grid_depth_info(pt_ctx* ctx, pt_probe_depth* out);
 
 /* ---- unit hooks: TLAS::intersect / any_intersect  src/tlas.rs:66, 111 ------------------------------------------ */
 /* which: 0 world TLAS, 1 lights TLAS.  Host SoA in, host SoA out.  miss => inst = prim = 0xffffffff, t = +inf.

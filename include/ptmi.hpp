@@ -21,6 +21,7 @@
 // Material::EmissionTextured (pt_set_material_emission_texture), Material::NormalMapped (pt_set_material_normal_texture).
 #pragma once
 #include <array>
+#include <cmath>
 #include <cstdint>
 #include <memory>
 #include <optional>
@@ -548,7 +549,10 @@ public:
         return valid;
     }
     // bakes and sets a grid: the node positions, bake_probes, probe_validity and set_probe_grid_sums; returns the valid bytes
-    std::vector<uint8_t> bake_probe_grid(const pt_probe_grid& g, uint32_t n_samples, float max_back_fraction = 0.25f)
+    // depth_res > 0 also bakes the nodes' depth moments from the same rays and sets them (bake_probe_depth, set_probe_grid_depth_sums);
+    // max_distance <= 0: the cell's diagonal times 1.5
+    std::vector<uint8_t> bake_probe_grid(const pt_probe_grid& g, uint32_t n_samples, float max_back_fraction = 0.25f, uint32_t depth_res = 0,
+                                         float max_distance = 0.0f, float vis_floor = 0.0f, bool facing = false)
     {
         std::vector<float> pos;
         for (uint32_t z = 0; z < g.count[2]; ++z)
@@ -559,8 +563,66 @@ public:
         bake_probes(pos, n_samples, sums);
         const std::vector<uint8_t> valid = probe_validity(pos, n_samples, max_back_fraction);
         set_probe_grid_sums(g, sums, n_samples, valid);
+        if (depth_res)
+        {
+            if (!(max_distance > 0.0f))
+                max_distance = (float)(1.5 * std::sqrt((double)g.cell[0] * g.cell[0] + (double)g.cell[1] * g.cell[1] + (double)g.cell[2] * g.cell[2]));
+            std::vector<float> dsums;
+            std::vector<uint32_t> dcounts;
+            bake_probe_depth(pos, n_samples, depth_res, max_distance, dsums, dcounts);
+            set_probe_grid_depth_sums(depth_res, dsums, dcounts, max_distance, vis_floor, facing);
+        }
         return valid;
     }
+    // probe visibility.  The texel of every direction (3 floats each, any values) in an octahedral map of side res (pt_probe_depth_texel)
+    static std::vector<uint32_t> probe_depth_texel(const std::vector<float>& directions, uint32_t res)
+    {
+        if (directions.size() % 3 != 0 || directions.size() / 3 > 0xffffffffull) throw Error(PT_ERR_ARG, "probe_depth_texel: directions are 3 floats each");
+        std::vector<uint32_t> texel(directions.size() / 3);
+        const int r = pt_probe_depth_texel(res, (uint32_t)texel.size(), directions.data(), texel.data());
+        if (r != PT_OK) throw Error(r, "probe_depth_texel: res is 2..16");
+        return texel;
+    }
+    // depth moments (pt_bake_probe_depth): adds the clamped distances bake_probes' rays see to the raw sums (res * res * 2 floats per probe)
+    // and counts (res * res per probe) per octahedral texel, in sample order; empty vectors start a fresh bake from zero
+    void bake_probe_depth(const std::vector<float>& positions, uint32_t n_samples, uint32_t res, float max_distance, std::vector<float>& sums,
+                          std::vector<uint32_t>& counts, uint32_t first_sample = 0, uint32_t key_base = 0)
+    {
+        if (positions.size() % 3 != 0 || positions.size() / 3 > 0xffffffffull) throw Error(PT_ERR_ARG, "bake_probe_depth: positions are 3 floats per probe");
+        const size_t n = positions.size() / 3, texels = n * res * res;
+        if (sums.empty() && counts.empty()) { sums.assign(texels * 2, 0.0f); counts.assign(texels, 0u); }
+        if (res >= 2 && res <= 16 && (sums.size() != texels * 2 || counts.size() != texels))
+            throw Error(PT_ERR_ARG, "bake_probe_depth: sums hold res * res * 2 values and counts res * res per probe");
+        pt_probe_depth_params p{};
+        p.first_sample = first_sample; p.n_samples = n_samples; p.key_base = key_base; p.res = res; p.max_distance = max_distance;
+        check(pt_bake_probe_depth(ctx_, (uint32_t)n, positions.data(), &p, sums.data(), counts.data()));
+    }
+    // depth on the grid in force (pt_set_probe_grid_depth): per node and texel the mean distance and the mean squared distance; empty
+    // moments with res 0 clear it
+    void set_probe_grid_depth(uint32_t res, const std::vector<float>& moments, float vis_floor = 0.0f, bool facing = false)
+    {
+        pt_probe_depth v{};
+        v.res = res; v.flags = facing ? PT_PROBE_VIS_FACING : 0u; v.vis_floor = vis_floor;
+        uint32_t n_valid = 0;
+        const pt_probe_grid g = probe_grid_info(&n_valid);
+        const size_t nodes = (size_t)g.count[0] * g.count[1] * g.count[2];
+        if (res >= 2 && res <= 16 && moments.size() != nodes * res * res * 2) throw Error(PT_ERR_ARG, "set_probe_grid_depth: moments hold res * res * 2 values per node");
+        check(pt_set_probe_grid_depth(ctx_, &v, moments.empty() ? nullptr : moments.data()));
+    }
+    // ... of bake_probe_depth's raw sums and counts: the means are taken here, and a texel without a sample gets (max_distance, its square)
+    void set_probe_grid_depth_sums(uint32_t res, const std::vector<float>& sums, const std::vector<uint32_t>& counts, float max_distance, float vis_floor = 0.0f,
+                                   bool facing = false)
+    {
+        if (sums.size() != counts.size() * 2) throw Error(PT_ERR_ARG, "set_probe_grid_depth_sums: two sums per count");
+        std::vector<float> m(sums.size());
+        for (size_t i = 0; i < counts.size(); ++i)
+        {
+            m[2 * i] = counts[i] ? sums[2 * i] / (float)counts[i] : max_distance;
+            m[2 * i + 1] = counts[i] ? sums[2 * i + 1] / (float)counts[i] : max_distance * max_distance;
+        }
+        set_probe_grid_depth(res, m, vis_floor, facing);
+    }
+    pt_probe_depth probe_grid_depth_info() const { pt_probe_depth v{}; check(pt_get_probe_grid_depth_info(ctx_, &v)); return v; }
     // the world TLAS's root box: min xyz, max xyz
     std::array<float, 6> root_box() const { uint32_t rect[4]; std::array<float, 6> b{}; check(pt_active_pixels(ctx_, rect, b.data())); return b; }
     pt_stats stats() const { pt_stats s{}; check(pt_get_stats(ctx_, &s)); return s; }

@@ -51,11 +51,13 @@ EXPORTS = [
     "pt_set_lightmap", "pt_get_lightmap_info", "pt_lightmap_lookup", "pt_render_baked", "pt_read_baked", "pt_reset_baked", "pt_write_baked_image",
     "pt_set_probe_grid", "pt_get_probe_grid_info", "pt_probe_grid_lookup", "pt_probe_backfaces",
     "pt_bake_lightmap_moments", "pt_lightmap_denoise",
+    "pt_probe_depth_texel", "pt_bake_probe_depth", "pt_set_probe_grid_depth", "pt_get_probe_grid_depth_info",
 ]
 
 
 LAUNCHERS = ("shade", "terminal", "closest", "any", "fused", "generate", "guide_rays", "accumulate")   # pt_launcher
 LAUNCHES_BATCH, LAUNCHES_HOOK = 0, 1   # pt_last_launches' which
+PROBE_VIS_FACING = 1   # pt_probe_depth's flags
 ALBEDO_GUIDE, ALBEDO_MEAN = 1, 2   # pt_denoise_albedo's albedo_source
 PROJ_PERSPECTIVE, PROJ_PANORAMA, PROJ_ORTHOGRAPHIC = range(3)   # pt_projection_kind
 EV_MOUSE_MOTION, EV_KEY_W, EV_KEY_S, EV_KEY_A, EV_KEY_D = range(5)
@@ -141,6 +143,17 @@ class ProbeGrid(C.Structure):
     """pt_probe_grid: where the nodes of the irradiance volume stand and the lookup's offset along the normal (include/pt_api.h)"""
     _fields_ = [("origin", C.c_float * 3), ("cell", C.c_float * 3), ("count", C.c_uint32 * 3), ("normal_bias", C.c_float),
                 ("reserved", C.c_uint32 * 4)]
+
+
+class ProbeDepthParams(C.Structure):
+    """pt_probe_depth_params: the sample range and stream keys of a depth bake, the octahedral map's side and the distance clamp (include/pt_api.h)"""
+    _fields_ = [("first_sample", C.c_uint32), ("n_samples", C.c_uint32), ("key_base", C.c_uint32), ("res", C.c_uint32), ("max_distance", C.c_float),
+                ("reserved", C.c_uint32 * 3)]
+
+
+class ProbeDepth(C.Structure):
+    """pt_probe_depth: the side of the nodes' octahedral depth maps, PROBE_VIS_FACING and the visibility floor (include/pt_api.h)"""
+    _fields_ = [("res", C.c_uint32), ("flags", C.c_uint32), ("vis_floor", C.c_float), ("reserved", C.c_uint32 * 5)]
 
 
 class LightmapParams(C.Structure):
@@ -317,6 +330,10 @@ def lib():
         L.pt_get_probe_grid_info.argtypes = [vp, C.POINTER(ProbeGrid), C.POINTER(u32)]
         L.pt_probe_grid_lookup.argtypes = [vp, C.c_int, u32, vp, vp, vp, vp]
         L.pt_probe_backfaces.argtypes = [vp, u32, vp, C.POINTER(ProbeParams), vp, vp]
+        L.pt_probe_depth_texel.argtypes = [u32, u32, vp, vp]
+        L.pt_bake_probe_depth.argtypes = [vp, u32, vp, C.POINTER(ProbeDepthParams), vp, vp]
+        L.pt_set_probe_grid_depth.argtypes = [vp, C.POINTER(ProbeDepth), vp]
+        L.pt_get_probe_grid_depth_info.argtypes = [vp, C.POINTER(ProbeDepth)]
         L.pt_render_guides_followed.argtypes = [vp, u32, C.POINTER(GuideParams)]
         L.pt_read_guide_hops.argtypes = [vp, vp]
         L.pt_accumulate_albedo_followed.argtypes = [vp, u32, u32, C.POINTER(GuideParams)]
@@ -1196,15 +1213,78 @@ class Renderer:
         idx = np.stack(np.meshgrid(np.arange(nz), np.arange(ny), np.arange(nx), indexing="ij")[::-1], axis=-1).astype(np.float32)
         return (o + idx * c).astype(np.float32)
 
-    def bake_probe_grid(self, origin, cell, count, n_samples, max_back_fraction=0.25, normal_bias=0.0):
+    def bake_probe_grid(self, origin, cell, count, n_samples, max_back_fraction=0.25, normal_bias=0.0, depth_res=0, max_distance=None, vis_floor=0.0,
+                        facing=False):
         """bakes and sets a grid of count = (nx, ny, nz) probes: the node positions, bake_probes, probe_validity and set_probe_grid_sums.
-        Returns (sums (nz, ny, nx, 9, 3), valid (nz, ny, nx))"""
+        Returns (sums (nz, ny, nx, 9, 3), valid (nz, ny, nx)).  depth_res > 0 also bakes the nodes' depth moments from the same rays
+        (bake_probe_depth) and sets them (set_probe_grid_depth_sums); max_distance None: the cell's diagonal times 1.5."""
         nx, ny, nz = (int(k) for k in count)
         pos = self.probe_grid_positions(origin, cell, count).reshape(-1, 3)
         sums = self.bake_probes(pos, n_samples).reshape(nz, ny, nx, 9, 3)
         valid = self.probe_validity(pos, n_samples, max_back_fraction).reshape(nz, ny, nx)
         self.set_probe_grid_sums(origin, cell, sums, n_samples, valid, normal_bias)
+        if depth_res:
+            if max_distance is None:
+                max_distance = 1.5 * float(np.linalg.norm(np.asarray(cell, np.float64)))
+            dsums, dcounts = self.bake_probe_depth(pos, n_samples, depth_res, max_distance)
+            self.set_probe_grid_depth_sums(dsums, dcounts, max_distance, vis_floor, facing)
         return sums, valid
+
+    # ---- probe visibility: depth moments on the nodes' octahedral maps
+    def probe_depth_texel(self, directions, res):
+        """the texel of every direction [n, 3] (any values, not normalised) in an octahedral map of side res (pt_probe_depth_texel; no GPU)"""
+        d = np.ascontiguousarray(directions, np.float32).reshape(-1, 3)
+        out = np.zeros(d.shape[0], np.uint32)
+        self._chk(self.L.pt_probe_depth_texel(int(res), d.shape[0], _p(d), _p(out)))
+        return out
+
+    def bake_probe_depth(self, positions, n_samples, res, max_distance, first_sample=0, key_base=0, sums=None, counts=None):
+        """depth moments (pt_bake_probe_depth): adds the distances seen by bake_probes' rays of samples [first_sample, first_sample + n_samples),
+        clamped to max_distance, to the raw sums (n, res * res, 2) float32 and counts (n, res * res) uint32 per octahedral texel (None: zeros),
+        in sample order per texel.  Returns (sums, counts)."""
+        pos = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
+        n, rr = pos.shape[0], int(res) * int(res)
+        s = np.zeros((n, rr, 2), np.float32) if sums is None else np.ascontiguousarray(sums, np.float32).copy()
+        k = np.zeros((n, rr), np.uint32) if counts is None else np.ascontiguousarray(counts, np.uint32).copy()
+        if 2 <= int(res) <= 16 and (s.size != n * rr * 2 or k.size != n * rr):
+            raise PtError(-1, "bake_probe_depth: sums hold res * res * 2 values and counts res * res per probe")
+        prm = ProbeDepthParams(first_sample, n_samples, key_base, int(res), float(max_distance))
+        self._chk(self.L.pt_bake_probe_depth(self.ctx, n, _p(pos), C.byref(prm), _p(s), _p(k)))
+        return s, k
+
+    def set_probe_grid_depth(self, moments, vis_floor=0.0, facing=False):
+        """depth on the grid in force (pt_set_probe_grid_depth): moments (nodes, res * res, 2) float32, per texel the mean distance and the
+        mean squared distance.  moments None clears depth."""
+        if moments is None:
+            self._chk(self.L.pt_set_probe_grid_depth(self.ctx, C.byref(ProbeDepth()), None))
+            return
+        m = np.ascontiguousarray(moments, np.float32)
+        res = int(round(np.sqrt(m.shape[-2]))) if m.ndim >= 2 else 0
+        nodes = int(np.prod(self.probe_grid_info()[2]))
+        if m.ndim < 2 or m.shape[-1] != 2 or res * res != m.shape[-2] or m.size != nodes * res * res * 2:
+            raise PtError(-1, "set_probe_grid_depth: moments is (nodes, res * res, 2)")
+        v = ProbeDepth(res, PROBE_VIS_FACING if facing else 0, float(vis_floor))
+        self._chk(self.L.pt_set_probe_grid_depth(self.ctx, C.byref(v), _p(m)))
+
+    def set_probe_grid_depth_sums(self, sums, counts, max_distance, vis_floor=0.0, facing=False):
+        """set_probe_grid_depth of bake_probe_depth's raw sums and counts: the means are taken here, one binary32 division each, and a texel
+        without a sample gets (max_distance, max_distance * max_distance): nothing was seen nearer"""
+        self.set_probe_grid_depth(self.probe_depth_means(sums, counts, max_distance), vis_floor, facing)
+
+    @staticmethod
+    def probe_depth_means(sums, counts, max_distance):
+        """the moments (.., res * res, 2) float32 of raw depth sums and counts, as set_probe_grid_depth_sums sets them"""
+        s = np.asarray(sums, np.float32); k = np.asarray(counts, np.uint32)
+        far = np.float32(max_distance)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            mean = (s / k.astype(np.float32)[..., None]).astype(np.float32)
+        return np.where((k > 0)[..., None], mean, np.array([far, far * far], np.float32)).astype(np.float32)
+
+    def probe_grid_depth_info(self):
+        """(res, flags, vis_floor) of the grid's depth; res 0: none"""
+        v = ProbeDepth()
+        self._chk(self.L.pt_get_probe_grid_depth_info(self.ctx, C.byref(v)))
+        return int(v.res), int(v.flags), float(v.vis_floor)
 
     # ---- unit hooks
     def trace_closest(self, o, d, tmax=None, which=0):

@@ -31,6 +31,10 @@
 //                                      nodes, a fifth of the nodes invalid, then probe_grid_lookup (pt_probe.h, the function the kernels run) at n
 //                                      points each: inside, far outside, huge, infinite and NaN positions, NaN normals; prints how many were lit and
 //                                      a checksum of the results
+//   host_sanitize probedepth <n> <seed> probe visibility's host side: the same grids, each with a random depth table of side 2..16 that fills its
+//                                      allocation exactly, random flags and floor, then probe_grid_lookup<true> at the same kinds of points, and
+//                                      probe_oct_texel alone over zero, huge, infinite and NaN directions; prints how many were lit, a checksum
+//                                      and the largest texel seen against the map's size
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -484,6 +488,61 @@ int main(int argc, char** argv)
             }
         }
         std::printf("{\"lookups\": %u, \"lit\": %u, \"checksum\": %.6f}\n", lookups, lit, acc);
+        return 0;
+    }
+    if (cmd == "probedepth" && argc >= 4)
+    {
+        const uint32_t n = (uint32_t)std::atoi(argv[2]);
+        uint64_t s = 0x9E3779B97F4A7C15ull ^ (uint64_t)std::atoll(argv[3]);
+        auto rnd = [&]() { s ^= s << 13; s ^= s >> 7; s ^= s << 17; return (float)((s >> 40) & 0xffff) / 65535.0f; };
+        const uint32_t counts[6][3] = {{1, 1, 1}, {2, 2, 2}, {3, 2, 4}, {5, 1, 3}, {1, 7, 1}, {1, 1, 6}};
+        double acc = 0.0;
+        uint32_t lookups = 0, lit = 0, texels_ok = 1;
+        for (const uint32_t* cnt : counts)
+        {
+            const size_t nodes = (size_t)cnt[0] * cnt[1] * cnt[2];
+            std::vector<DProbe> rec(nodes);
+            for (DProbe& r : rec)
+            {
+                r.valid = rnd() < 0.8f ? 1.0f : 0.0f;
+                for (float& v : r.sh) v = r.valid != 0.0f ? 4.0f * rnd() - 1.0f : 0.0f;
+            }
+            const ProbeGridView g{rec.data(), {4.0f * rnd() - 2.0f, 4.0f * rnd() - 2.0f, 4.0f * rnd() - 2.0f},
+                                  {0.25f + rnd(), 0.25f + rnd(), 0.25f + rnd()}, {cnt[0], cnt[1], cnt[2]}, rnd() < 0.5f ? 0.0f : 0.125f};
+            const uint32_t res = 2u + (uint32_t)(rnd() * 14.99f);
+            std::vector<DProbeDepth> table(nodes * res * res); // exactly the table: a texel past a node's map, or a node past the grid, is a heap overflow
+            for (DProbeDepth& m : table)
+            {
+                m.m1 = 3.0f * rnd();
+                m.m2 = rnd() < 0.8f ? m.m1 * m.m1 + rnd() : m.m1 * m.m1 * rnd(); // (both signs of m2 - m1^2; zero variance where rnd() is 0)
+            }
+            const ProbeDepthView dv{table.data(), res, rnd() < 0.5f ? 1u : 0u, rnd() < 0.5f ? 0.0f : 0.05f};
+            for (uint32_t i = 0; i < n; ++i)
+            {
+                const uint32_t kind = i % 8u;
+                const float reach = kind == 0u ? 1.0f : kind == 1u ? 3.0f : kind == 2u ? 1e4f : kind == 3u ? 1e30f : 1.0f;
+                float p[3], nn[3];
+                for (int a = 0; a < 3; ++a)
+                {
+                    p[a] = g.origin[a] + reach * (2.0f * rnd() - 0.5f) * g.cell[a] * (float)cnt[a];
+                    nn[a] = 2.0f * rnd() - 1.0f;
+                }
+                if (kind == 4u) p[i % 3u] = NAN;
+                if (kind == 5u) p[i % 3u] = i & 8u ? INFINITY : -INFINITY;
+                if (kind == 6u) nn[i % 3u] = NAN;
+                if (kind == 7u) p[0] = p[1] = p[2] = 3.0e38f;
+                f3 c;
+                if (probe_grid_lookup<true>(g, f3{p[0], p[1], p[2]}, f3{nn[0], nn[1], nn[2]}, &c, &dv)) ++lit;
+                for (float v : {c.x, c.y, c.z})
+                    if (std::isfinite(v)) acc += v;
+                ++lookups;
+                // the texel alone, of what a lookup can form and more
+                const float odd[6] = {0.0f, -0.0f, 3.0e38f, INFINITY, -INFINITY, NAN};
+                const float dir[3] = {kind < 6u ? odd[kind] : p[0], i & 16u ? p[1] : odd[(i >> 5) % 6u], p[2]};
+                if (probe_oct_texel(dir, res) >= res * res) texels_ok = 0;
+            }
+        }
+        std::printf("{\"lookups\": %u, \"lit\": %u, \"checksum\": %.6f, \"texels_inside\": %u}\n", lookups, lit, acc, texels_ok);
         return 0;
     }
     if (cmd == "plan")

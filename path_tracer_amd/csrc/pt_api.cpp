@@ -216,6 +216,13 @@ struct pt_ctx
     uint64_t probe_version = 0, baked_probe_version = 0, pg_version = 0;
     DevBuf d_probes;
     bool pg_valid = false;
+    // probe visibility (pt_set_probe_grid_depth): the nodes' depth moments as the device gets them (empty: none), which belong to the grid in
+    // force: any pt_set_probe_grid drops them, and a change of theirs counts in probe_version too.  pd_version: the one on the device.
+    pt_probe_depth probe_depth{};
+    std::vector<DProbeDepth> probe_moments;
+    uint64_t pd_version = 0;
+    DevBuf d_probe_moments;
+    bool pd_valid = false;
 
     // pt_frame_moving: the forward instance matrices, per model, of the build in force when the previous call returned PT_OK (the snapshot)
     // and the build it was taken from (a call on that very build has nothing to compare); the motion table and x_prev on the device.
@@ -1612,6 +1619,23 @@ int ensure_probe_grid(pt_ctx* c)
     HIPCHK(c, hipMemcpy(c->d_probes.p, c->probes.data(), c->probes.size() * sizeof(DProbe), hipMemcpyHostToDevice));
     c->pg_valid = true;
     c->pg_version = c->probe_version;
+    return PT_OK;
+}
+// ... and the depth moments' table beside it (pt_set_probe_grid_depth), by the same pattern; only called with depth set
+ProbeDepthView probe_depth_view(const pt_ctx* c, const DProbeDepth* moments)
+{
+    return ProbeDepthView{moments, c->probe_depth.res, c->probe_depth.flags & PT_PROBE_VIS_FACING, c->probe_depth.vis_floor};
+}
+int ensure_probe_depth(pt_ctx* c)
+{
+    if (c->pd_valid && c->pd_version == c->probe_version) return PT_OK;
+    c->pd_valid = false;
+    int r;
+    HIPCHK(c, hipStreamSynchronize(c->stream)); // an earlier call may still be reading the table
+    if ((r = dev_alloc(c, c->d_probe_moments, c->probe_moments.size() * sizeof(DProbeDepth)))) return r;
+    HIPCHK(c, hipMemcpy(c->d_probe_moments.p, c->probe_moments.data(), c->probe_moments.size() * sizeof(DProbeDepth), hipMemcpyHostToDevice));
+    c->pd_valid = true;
+    c->pd_version = c->probe_version;
     return PT_OK;
 }
 
@@ -3047,10 +3071,10 @@ int follow_chains(pt_ctx* c, uint32_t sample, uint32_t max_hops, f4* sum)
     });
 }
 // ... and the baked view's chains (pt_render_baked): the same walk, ended by launch_baked_follow into the baked sums, or by the probe ending
-// while a grid is set (pt_set_probe_grid)
+// while a grid is set (pt_set_probe_grid), over the lookup with visibility while the grid has depth (pt_set_probe_grid_depth)
 int baked_chains(pt_ctx* c, uint32_t sample, const pt_baked_params& p)
 {
-    const bool grid = !c->probes.empty();
+    const bool grid = !c->probes.empty(), depth = grid && !c->probe_moments.empty();
     EnvView env{};
     if (c->env_w) env = EnvView{(const f4*)c->d_env.p, c->env_w, c->env_h, 0u, 0u};
     return walk_chains(c, sample, p.max_hops, [&](const ChainHop& q) {
@@ -3059,7 +3083,10 @@ int baked_chains(pt_ctx* c, uint32_t sample, const pt_baked_params& p)
         b.sum = (f4*)c->d_baked_sum.p;
         b.env = env;
         std::memcpy(b.unlit, p.unlit, sizeof(b.unlit));
-        if (grid) launch_baked_follow_probes(c->stream, c->sv, c->tex, c->lm, b, probe_grid_view(c, (const DProbe*)c->d_probes.p));
+        if (depth)
+            launch_baked_follow_probes_vis(c->stream, c->sv, c->tex, c->lm, b, probe_grid_view(c, (const DProbe*)c->d_probes.p),
+                                           probe_depth_view(c, (const DProbeDepth*)c->d_probe_moments.p));
+        else if (grid) launch_baked_follow_probes(c->stream, c->sv, c->tex, c->lm, b, probe_grid_view(c, (const DProbe*)c->d_probes.p));
         else launch_baked_follow(c->stream, c->sv, c->tex, c->lm, b);
     });
 }
@@ -3772,6 +3799,7 @@ int pt_render_baked(pt_ctx* c, uint32_t first_sample, uint32_t n_samples, const 
     int r;
     if ((r = upload_scene(c)) || (r = ensure_environment(c)) || (r = ensure_lightmaps(c))) return r;
     if (!c->probes.empty() && (r = ensure_probe_grid(c))) return r;
+    if (!c->probe_moments.empty() && (r = ensure_probe_depth(c))) return r;
     const uint32_t px = c->local_pixels;
     const size_t n = std::max<uint32_t>(px, 1);
     if ((r = guide_scratch(c, p->max_hops)) || (r = dev_alloc(c, c->d_baked_sum, n * 16))) return r;
@@ -3833,6 +3861,11 @@ int pt_write_baked_image(pt_ctx* c, const char* path)
 }
 
 // ---- the probe grid and the census of probes inside geometry (the definitions are include/pt_api.h's)
+static void drop_probe_depth(pt_ctx* c)
+{
+    std::vector<DProbeDepth>().swap(c->probe_moments);
+    c->probe_depth = pt_probe_depth{};
+}
 int pt_set_probe_grid(pt_ctx* c, const pt_probe_grid* g, const float* sh27, const uint8_t* valid)
 {
     if (!c) return PT_ERR_ARG;
@@ -3844,6 +3877,7 @@ int pt_set_probe_grid(pt_ctx* c, const pt_probe_grid* g, const float* sh27, cons
     {
         if (!c->probes.empty()) c->probe_version++;
         std::vector<DProbe>().swap(c->probes);
+        drop_probe_depth(c);
         c->probe_grid = pt_probe_grid{};
         c->probes_valid = 0;
         return PT_OK;
@@ -3873,6 +3907,7 @@ int pt_set_probe_grid(pt_ctx* c, const pt_probe_grid* g, const float* sh27, cons
         ++n_valid;
     }
     c->probes.swap(rec);
+    drop_probe_depth(c); // (the node count may have changed)
     c->probe_grid = *g;
     c->probes_valid = n_valid;
     c->probe_version++;
@@ -3898,24 +3933,32 @@ int pt_probe_grid_lookup(pt_ctx* c, int on_device, uint32_t n, const float* posi
     if (!on_device)
     {
         const ProbeGridView g = probe_grid_view(c, c->probes.data());
+        const bool vis = !c->probe_moments.empty();
+        const ProbeDepthView dv = probe_depth_view(c, c->probe_moments.data());
         for (uint32_t i = 0; i < n; ++i)
         {
             const float *pp = position + 3 * (size_t)i, *pn = normal + 3 * (size_t)i;
+            const f3 P{pp[0], pp[1], pp[2]}, N{pn[0], pn[1], pn[2]};
             f3 col;
-            lit[i] = probe_grid_lookup(g, f3{pp[0], pp[1], pp[2]}, f3{pn[0], pn[1], pn[2]}, &col) ? 1u : 0u;
+            lit[i] = (vis ? probe_grid_lookup<true>(g, P, N, &col, &dv) : probe_grid_lookup(g, P, N, &col)) ? 1u : 0u;
             rgb[3 * (size_t)i] = col.x; rgb[3 * (size_t)i + 1] = col.y; rgb[3 * (size_t)i + 2] = col.z;
         }
         return PT_OK;
     }
     int r;
     if ((r = ensure_device(c)) || (r = ensure_probe_grid(c))) return r;
+    const bool vis = !c->probe_moments.empty();
+    if (vis && (r = ensure_probe_depth(c))) return r;
     Staging st(c);
     const float* d_pos = (const float*)st.in(position, (size_t)n * 12);
     const float* d_nrm = (const float*)st.in(normal, (size_t)n * 12);
     float* d_rgb = (float*)st.out((size_t)n * 12);
     uint8_t* d_lit = (uint8_t*)st.out(n);
     if (st.err) return st.err;
-    launch_probe_grid_lookup(c->stream, probe_grid_view(c, (const DProbe*)c->d_probes.p), n, d_pos, d_nrm, d_rgb, d_lit);
+    if (vis)
+        launch_probe_grid_lookup_vis(c->stream, probe_grid_view(c, (const DProbe*)c->d_probes.p), probe_depth_view(c, (const DProbeDepth*)c->d_probe_moments.p), n,
+                                     d_pos, d_nrm, d_rgb, d_lit);
+    else launch_probe_grid_lookup(c->stream, probe_grid_view(c, (const DProbe*)c->d_probes.p), n, d_pos, d_nrm, d_rgb, d_lit);
     HIPCHK(c, hipGetLastError());
     if ((r = st.download(rgb, d_rgb, (size_t)n * 12))) return r;
     return st.download(lit, d_lit, n);
@@ -3964,6 +4007,111 @@ int pt_probe_backfaces(pt_ctx* c, uint32_t n_probes, const float* position, cons
     }
     if ((r = st.download(hits, d_hits, (size_t)n_probes * 4))) return r;
     return st.download(back, d_back, (size_t)n_probes * 4);
+}
+
+// ---- probe visibility: the depth moments' bake, the table on the grid (the definitions are include/pt_api.h's)
+int pt_probe_depth_texel(uint32_t res, uint32_t n, const float* dir, uint32_t* texel)
+{
+    if (res < 2u || res > 16u) return PT_ERR_LIMIT;
+    if (n > 0 && (!dir || !texel)) return PT_ERR_ARG;
+    for (uint32_t i = 0; i < n; ++i) texel[i] = probe_oct_texel(dir + 3 * (size_t)i, res);
+    return PT_OK;
+}
+
+int pt_bake_probe_depth(pt_ctx* c, uint32_t n_probes, const float* position, const pt_probe_depth_params* p, float* sums, uint32_t* counts)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    int r;
+    pt_probe_params range{};
+    if (p) range = pt_probe_params{p->first_sample, p->n_samples, p->key_base, 0u};
+    if ((r = probe_call_check(c, "pt_bake_probe_depth", "sums and counts", n_probes, position, p ? &range : nullptr, !sums || !counts))) return r;
+    if (p)
+    {
+        if (p->res < 2u || p->res > 16u) return fail(c, PT_ERR_LIMIT, "pt_probe_depth_params.res: the octahedral map's side is 2..16");
+        if (!(p->max_distance > 0.0f) || !std::isfinite(p->max_distance)) return fail(c, PT_ERR_ARG, "pt_probe_depth_params.max_distance must be finite and > 0");
+        if (p->reserved[0] || p->reserved[1] || p->reserved[2]) return fail(c, PT_ERR_ARG, "pt_probe_depth_params.reserved must be 0");
+    }
+    if (n_probes == 0) return PT_OK;
+    if ((r = upload_scene(c))) return r;
+    // the census' ray table and cuts (pt_probe_backfaces): filled, queued, traced once, folded per probe in sample order.  An empty world
+    // traces nothing: every hit record is a miss
+    const bool empty = c->sv.world_root == MISS_ID;
+    const size_t texels = (size_t)n_probes * p->res * p->res;
+    const uint64_t total = (uint64_t)n_probes * p->n_samples;
+    const uint64_t cut = c->cfg.batch_spp ? 3ull * c->cfg.batch_spp * n_probes : total;
+    const uint32_t chunk = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(total, cut), 1ull << 21);
+    Staging st(c);
+    const float* d_position = (const float*)st.in(position, (size_t)n_probes * 12);
+    DProbeDepth* d_sums = (DProbeDepth*)st.in(sums, texels * 8);
+    uint32_t* d_counts = (uint32_t*)st.in(counts, texels * 4);
+    float* d_o = (float*)st.out((size_t)chunk * 12);
+    float* d_d = (float*)st.out((size_t)chunk * 12);
+    uint2* d_key = (uint2*)st.out((size_t)chunk * 8);
+    const RayQueue q{(f4*)st.out((size_t)chunk * 16), (f4*)st.out((size_t)chunk * 16)};
+    f4* d_hit = (f4*)st.out((size_t)chunk * 16);
+    const size_t head_bytes = ((size_t)32 + kHeadWordsPerQueue) * 4;
+    uint32_t* d_head = (uint32_t*)st.out(head_bytes);
+    if (st.err) return st.err;
+    const ProbeBake pb{d_position, n_probes, p->first_sample, p->n_samples, p->key_base, c->cfg.n_sobol, c->cfg.seed};
+    c->hook_log.clear();
+    const LaunchLogScope logging(&c->hook_log);
+    for (uint64_t first = 0; first < total; first += chunk)
+    {
+        const uint32_t cnt = (uint32_t)std::min<uint64_t>(chunk, total - first);
+        launch_probe_rays(c->stream, pb, first, cnt, d_o, d_d, d_key);
+        if (empty) HIPCHK(c, hipMemsetAsync(d_hit, 0xff, (size_t)cnt * 16, c->stream)); // id = MISS_ID
+        else
+        {
+            HIPCHK(c, hipMemsetAsync(d_head, 0, head_bytes, c->stream));
+            launch_rays_to_queue(c->stream, cnt, d_o, d_d, q, d_head);
+            launch_trace_rays_closest(c->stream, trace_launch(c), c->sv.world_root, q, cnt, d_head, d_hit);
+        }
+        launch_probe_depth_fold(c->stream, pb, first, cnt, d_d, d_hit, p->res, p->max_distance, d_sums, d_counts);
+        HIPCHK(c, hipGetLastError());
+    }
+    if ((r = st.download(sums, d_sums, texels * 8))) return r;
+    return st.download(counts, d_counts, texels * 4);
+}
+
+int pt_set_probe_grid_depth(pt_ctx* c, const pt_probe_depth* v, const float* moments)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!v) return fail(c, PT_ERR_ARG, "pt_set_probe_grid_depth: v must not be NULL");
+    for (uint32_t w : v->reserved)
+        if (w) return fail(c, PT_ERR_ARG, "pt_probe_depth.reserved must be 0");
+    if (c->probes.empty()) return fail(c, PT_ERR_STATE, "no probe grid: pt_set_probe_grid first");
+    if (!moments && v->res == 0u)
+    {
+        if (!c->probe_moments.empty()) c->probe_version++;
+        drop_probe_depth(c);
+        return PT_OK;
+    }
+    if (!moments || v->res == 0u) return fail(c, PT_ERR_ARG, "pt_set_probe_grid_depth: moments with a non-zero res sets depth, NULL with res 0 clears it");
+    if (v->res < 2u || v->res > 16u) return fail(c, PT_ERR_LIMIT, "pt_probe_depth.res: the octahedral map's side is 2..16");
+    if (v->flags & ~PT_PROBE_VIS_FACING) return fail(c, PT_ERR_ARG, "pt_probe_depth.flags: unknown bits");
+    if (!(v->vis_floor >= 0.0f && v->vis_floor <= 1.0f)) return fail(c, PT_ERR_ARG, "pt_probe_depth.vis_floor must be in 0..1");
+    const size_t n = c->probes.size() * v->res * v->res;
+    for (size_t i = 0; i < n * 2; ++i)
+        if (!std::isfinite(moments[i]) || moments[i] < 0.0f)
+            return fail(c, PT_ERR_ARG, "pt_set_probe_grid_depth: node " + std::to_string(i / (2 * (size_t)v->res * v->res)) + " has a moment that is not finite and >= 0");
+    std::vector<DProbeDepth> rec;
+    try { rec.resize(n); }
+    catch (const std::exception& e) { return fail(c, PT_ERR_LIMIT, std::string("probe depth does not fit in host memory: ") + e.what()); }
+    std::memcpy(rec.data(), moments, n * sizeof(DProbeDepth));
+    c->probe_moments.swap(rec);
+    c->probe_depth = *v;
+    c->probe_version++;
+    return PT_OK;
+}
+
+int pt_get_probe_grid_depth_info(pt_ctx* c, pt_probe_depth* out)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (out) *out = c->probe_depth;
+    return PT_OK;
 }
 
 // ---- unit hooks

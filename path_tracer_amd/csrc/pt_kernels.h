@@ -330,6 +330,15 @@ void launch_probe_grid_lookup(hipStream_t s, const ProbeGridView& grid, uint32_t
 void launch_rays_to_queue(hipStream_t s, uint32_t n, const float* o, const float* d, RayQueue rq, uint32_t* n_and_heads);
 void launch_probe_backfaces(hipStream_t s, const SceneView& sv, const ProbeBake& pb, uint64_t first, uint32_t count, const float* d, const f4* hits,
                             uint32_t* hits_out, uint32_t* back_out);
+// pt_bake_probe_depth: the same window's hits folded into the probes' R x R octahedral depth maps (sums: the two moments' sums per texel,
+// counts: the rays per texel; both continue from what they hold), in sample order per texel: one wave per probe, no atomics
+void launch_probe_depth_fold(hipStream_t s, const ProbeBake& pb, uint64_t first, uint32_t count, const float* d, const f4* hits, uint32_t res,
+                             float max_distance, DProbeDepth* sums, uint32_t* counts);
+// with depth set on the grid (pt_set_probe_grid_depth): the probe ending and the unit hook over the lookup with visibility
+void launch_baked_follow_probes_vis(hipStream_t s, const SceneView& sv, const TexView& tex, const LmView& lm, const BakedArgs& a, const ProbeGridView& grid,
+                                    const ProbeDepthView& depth);
+void launch_probe_grid_lookup_vis(hipStream_t s, const ProbeGridView& grid, const ProbeDepthView& depth, uint32_t n, const float* position, const float* normal,
+                                  float* rgb, uint8_t* lit);
 // unit hook (pt_lightmap_lookup): lightmap_at (pt_materials.h) of world instance[i], leaf-order triangle tri[i] at barycentrics u[i], v[i]
 void launch_lightmap_lookup(hipStream_t s, const LmView& lm, uint32_t n, const uint32_t* instance, const uint32_t* tri, const float* u, const float* v,
                             float* rgb, uint8_t* mapped);

@@ -2723,6 +2723,70 @@ __global__ void __launch_bounds__(256) k_probe_backfaces(const SceneView sv, con
         back_out[j] = back_out[j] + n_back;
     }
 }
+// pt_bake_probe_depth: the closest hits of the same window folded into the probes' octahedral depth maps: counts[probe][texel] += 1,
+// sums[probe][texel] += (d, d * d), d = the hit's t clamped to max_distance (a miss: max_distance), texel = probe_oct_texel of the ray's
+// direction.  Float addition does not associate, so a texel's adds happen in sample order: k_probe_backfaces' ownership (one wave per probe
+// the window touches, launches of a call serial on one stream, no atomics), the wave walking its probe's rays of the window 64 at a time in
+// sample order.  Each lane computes its ray's (texel, d); the wave then steps through the 64 entries with a wave-uniform lane read, and
+// lane texel & 63 adds into its accumulator texel >> 6 (R * R <= 256: at most four a lane, chosen by a uniform branch and not by a dynamic
+// register index).  The accumulators are loaded from and stored to the arrays once per launch.
+__device__ __forceinline__ void depth_add(float& s0, float& s1, uint32_t& n, float dd)
+{
+    s0 = s0 + dd;
+    s1 = s1 + dd * dd;
+    n += 1u;
+}
+__global__ void __launch_bounds__(256) k_probe_depth_fold(const ProbeBake pb, const uint64_t first, const uint32_t count, const float* __restrict__ d,
+                                                          const f4* __restrict__ hits, const uint32_t res, const float max_distance,
+                                                          DProbeDepth* __restrict__ sums, uint32_t* __restrict__ counts)
+{
+    const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const uint32_t p0 = (uint32_t)(first / pb.n_samples), p1 = (uint32_t)((first + count - 1u) / pb.n_samples);
+    if (wave > p1 - p0) return; // (wave-uniform)
+    const uint32_t j = p0 + wave;
+    const uint64_t lo = (uint64_t)j * pb.n_samples, hi = lo + pb.n_samples;
+    const uint32_t i0 = (uint32_t)((lo > first ? lo : first) - first), i1 = (uint32_t)((hi < first + count ? hi : first + count) - first);
+    const uint32_t rr = res * res, lane = lane_id();
+    const size_t base = (size_t)j * rr;
+    float a0 = 0.0f, b0 = 0.0f, a1 = 0.0f, b1 = 0.0f, a2 = 0.0f, b2 = 0.0f, a3 = 0.0f, b3 = 0.0f;
+    uint32_t n0 = 0u, n1 = 0u, n2 = 0u, n3 = 0u;
+    if (lane < rr) { const DProbeDepth s = sums[base + lane]; a0 = s.m1; b0 = s.m2; n0 = counts[base + lane]; }
+    if (lane + 64u < rr) { const DProbeDepth s = sums[base + lane + 64u]; a1 = s.m1; b1 = s.m2; n1 = counts[base + lane + 64u]; }
+    if (lane + 128u < rr) { const DProbeDepth s = sums[base + lane + 128u]; a2 = s.m1; b2 = s.m2; n2 = counts[base + lane + 128u]; }
+    if (lane + 192u < rr) { const DProbeDepth s = sums[base + lane + 192u]; a3 = s.m1; b3 = s.m2; n3 = counts[base + lane + 192u]; }
+    for (uint32_t at = i0; at < i1; at += 64u)
+    {
+        const uint32_t i = at + lane;
+        uint32_t texel = 0u;
+        float dd = max_distance;
+        if (i < i1)
+        {
+            const f4 hit = hits[i];
+            if (asu(hit.w) != MISS_ID) dd = hit.x < max_distance ? hit.x : max_distance;
+            const float* pd = d + 3u * (size_t)i;
+            const float dir[3] = {pd[0], pd[1], pd[2]};
+            texel = probe_oct_texel(dir, res); // < res * res <= 256
+        }
+        const uint32_t m = i1 - at < 64u ? i1 - at : 64u; // (wave-uniform)
+        for (uint32_t e = 0; e < m; ++e)
+        {
+            const uint32_t te = (uint32_t)__builtin_amdgcn_readlane((int)texel, (int)e);
+            const float de = asf((uint32_t)__builtin_amdgcn_readlane((int)asu(dd), (int)e));
+            const uint32_t q = te >> 6; // (wave-uniform)
+            if ((te & 63u) == lane)
+            {
+                if (q == 0u) depth_add(a0, b0, n0, de);
+                else if (q == 1u) depth_add(a1, b1, n1, de);
+                else if (q == 2u) depth_add(a2, b2, n2, de);
+                else depth_add(a3, b3, n3, de);
+            }
+        }
+    }
+    if (lane < rr) { sums[base + lane] = DProbeDepth{a0, b0}; counts[base + lane] = n0; }
+    if (lane + 64u < rr) { sums[base + lane + 64u] = DProbeDepth{a1, b1}; counts[base + lane + 64u] = n1; }
+    if (lane + 128u < rr) { sums[base + lane + 128u] = DProbeDepth{a2, b2}; counts[base + lane + 128u] = n2; }
+    if (lane + 192u < rr) { sums[base + lane + 192u] = DProbeDepth{a3, b3}; counts[base + lane + 192u] = n3; }
+}
 
 // ------------------------------------------------------------------------------------------------ adaptive selection (PT_FLAG_ADAPTIVE)
 // The criterion of pt_api.h's pt_adaptive, in f32 with every operation correctly rounded and in this order (the tests restate it in
@@ -3071,12 +3135,13 @@ __global__ void __launch_bounds__(256, 8) k_guide_follow(const SceneView sv, con
 // constant ambient) of a miss, times R of the hop before unless the camera ray itself missed.  PROBES, with a probe grid set
 // (pt_set_probe_grid): a final surface that no map lights is lit by the grid where the grid is lit, by unlit where not; P and n are the
 // guides' (the hit position, the face-forwarded unperturbed normal).
-template <bool PROBES>
+template <bool PROBES, bool VIS = false>
 struct BakedEnding
 {
     const LmView& lm;
     const BakedArgs& a;
     const ProbeGridView* grid; // null without PROBES
+    const ProbeDepthView* depth = nullptr; // null without VIS (pt_set_probe_grid_depth: the lookup with visibility)
     // nothing here reads t, and carrying its sum through both barriers costs the probe ending's later hops a 67th register (the parent's 66 are
     // the bound: profiles/r25_chain_hop.md), so state[pixel].w holds one hop's t here
     static constexpr bool kSumT = false;
@@ -3101,7 +3166,7 @@ struct BakedEnding
             // registers more
             __asm__ volatile("" ::: "memory");
             f3 irr;
-            if (probe_grid_lookup(*grid, fma3(h.d, bc3(h.hit.x), xyz(a.in.a[h.slot])), h.nrm, &irr)) l = irr;
+            if (probe_grid_lookup<VIS>(*grid, fma3(h.d, bc3(h.hit.x), xyz(a.in.a[h.slot])), h.nrm, &irr, depth)) l = irr;
         }
         return h.c * l;
     }
@@ -3123,6 +3188,14 @@ __global__ void __launch_bounds__(256, 4) k_baked_follow_probes(const SceneView 
 {
     chain_hop<FIRST>(sv, tex, a, BakedEnding<true>{lm, a, &grid});
 }
+// ... and with depth set on the grid (pt_set_probe_grid_depth): the same ending over the lookup with visibility, chosen on the host as the
+// probe ending is (profiles/r25_probe_depth.md has its registers)
+template <bool FIRST>
+__global__ void __launch_bounds__(256, 4) k_baked_follow_probes_vis(const SceneView sv, const TexView tex, const LmView lm, const BakedArgs a, const ProbeGridView grid,
+                                                                    const ProbeDepthView depth)
+{
+    chain_hop<FIRST>(sv, tex, a, BakedEnding<true, true>{lm, a, &grid, &depth});
+}
 // unit hook of the probe grid's lookup: rgb, lit = probe_grid_lookup
 __global__ void __launch_bounds__(256, 4) k_probe_grid_lookup(const ProbeGridView grid, const uint32_t n, const float* __restrict__ position,
                                                               const float* __restrict__ normal, float* __restrict__ rgb, uint8_t* __restrict__ lit)
@@ -3133,6 +3206,18 @@ __global__ void __launch_bounds__(256, 4) k_probe_grid_lookup(const ProbeGridVie
     const float* pn = normal + 3u * (size_t)i;
     f3 c;
     const bool has = probe_grid_lookup(grid, f3{pp[0], pp[1], pp[2]}, f3{pn[0], pn[1], pn[2]}, &c);
+    rgb[3u * (size_t)i] = c.x; rgb[3u * (size_t)i + 1u] = c.y; rgb[3u * (size_t)i + 2u] = c.z;
+    lit[i] = has ? 1u : 0u;
+}
+__global__ void __launch_bounds__(256, 4) k_probe_grid_lookup_vis(const ProbeGridView grid, const ProbeDepthView depth, const uint32_t n, const float* __restrict__ position,
+                                                                  const float* __restrict__ normal, float* __restrict__ rgb, uint8_t* __restrict__ lit)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float* pp = position + 3u * (size_t)i;
+    const float* pn = normal + 3u * (size_t)i;
+    f3 c;
+    const bool has = probe_grid_lookup<true>(grid, f3{pp[0], pp[1], pp[2]}, f3{pn[0], pn[1], pn[2]}, &c, &depth);
     rgb[3u * (size_t)i] = c.x; rgb[3u * (size_t)i + 1u] = c.y; rgb[3u * (size_t)i + 2u] = c.z;
     lit[i] = has ? 1u : 0u;
 }
@@ -3723,6 +3808,25 @@ void launch_probe_backfaces(hipStream_t s, const SceneView& sv, const ProbeBake&
     if (count == 0u) return;
     const uint64_t probes = (first + count - 1u) / pb.n_samples - first / pb.n_samples + 1u;
     hipLaunchKernelGGL(k_probe_backfaces, dim3((uint32_t)((probes * 64u + 255u) / 256u)), dim3(256), 0, s, sv, pb, first, count, d, hits, hits_out, back_out);
+}
+void launch_probe_depth_fold(hipStream_t s, const ProbeBake& pb, uint64_t first, uint32_t count, const float* d, const f4* hits, uint32_t res,
+                             float max_distance, DProbeDepth* sums, uint32_t* counts)
+{
+    if (count == 0u) return;
+    const uint64_t probes = (first + count - 1u) / pb.n_samples - first / pb.n_samples + 1u;
+    hipLaunchKernelGGL(k_probe_depth_fold, dim3((uint32_t)((probes * 64u + 255u) / 256u)), dim3(256), 0, s, pb, first, count, d, hits, res, max_distance, sums,
+                       counts);
+}
+void launch_baked_follow_probes_vis(hipStream_t s, const SceneView& sv, const TexView& tex, const LmView& lm, const BakedArgs& a, const ProbeGridView& grid,
+                                    const ProbeDepthView& depth)
+{
+    launch_chain_hop(s, a, k_baked_follow_probes_vis<true>, k_baked_follow_probes_vis<false>, sv, tex, lm, a, grid, depth);
+}
+void launch_probe_grid_lookup_vis(hipStream_t s, const ProbeGridView& grid, const ProbeDepthView& depth, uint32_t n, const float* position, const float* normal,
+                                  float* rgb, uint8_t* lit)
+{
+    if (n == 0u) return;
+    hipLaunchKernelGGL(k_probe_grid_lookup_vis, dim3((n + 255u) / 256u), dim3(256), 0, s, grid, depth, n, position, normal, rgb, lit);
 }
 void launch_lightmap_lookup(hipStream_t s, const LmView& lm, uint32_t n, const uint32_t* instance, const uint32_t* tri, const float* u, const float* v,
                             float* rgb, uint8_t* mapped)

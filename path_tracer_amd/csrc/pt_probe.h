@@ -41,6 +41,39 @@ PT_HD void probe_ray(uint64_t seed, uint32_t n_sobol, uint32_t key, uint32_t sam
     probe_sh9(d, y);
 }
 
+// ---- probe visibility (pt_set_probe_grid_depth; include/pt_api.h states all of it operation for operation)
+// The texel of direction v (used as given, not normalised: the map is scale-free) in an R x R octahedral map.  A NaN lands on texel 0.
+PT_HD uint32_t probe_oct_texel(const float v[3], uint32_t R)
+{
+    const float s = (fabsf(v[0]) + fabsf(v[1])) + fabsf(v[2]);
+    float px = v[0] / s, py = v[1] / s;
+    if (v[2] < 0.0f)
+    {
+        const float qx = (1.0f - fabsf(py)) * (px >= 0.0f ? 1.0f : -1.0f), qy = (1.0f - fabsf(px)) * (py >= 0.0f ? 1.0f : -1.0f);
+        px = qx;
+        py = qy;
+    }
+    const float u = px * 0.5f + 0.5f, w = py * 0.5f + 0.5f, fr = (float)R;
+    const float ur = u * fr, wr = w * fr; // in [0, R] or NaN
+    const uint32_t ix = !(ur > 0.0f) ? 0u : ((uint32_t)ur < R - 1u ? (uint32_t)ur : R - 1u);
+    const uint32_t iy = !(wr > 0.0f) ? 0u : ((uint32_t)wr < R - 1u ? (uint32_t)wr : R - 1u);
+    return iy * R + ix;
+}
+// v = P' - Q of the node (ix, iy, iz), Q_a = origin_a + (float)i_a * cell_a
+PT_HD void probe_corner_vector(const ProbeGridView& g, const float pp[3], uint32_t ix, uint32_t iy, uint32_t iz, float v[3])
+{
+    v[0] = pp[0] - (g.origin[0] + (float)ix * g.cell[0]);
+    v[1] = pp[1] - (g.origin[1] + (float)iy * g.cell[1]);
+    v[2] = pp[2] - (g.origin[2] + (float)iz * g.cell[2]);
+}
+// the moments node `node` = (ix, iy, iz) holds in the direction of P' (the index stays inside the node's R * R texels whatever P' is)
+PT_HD DProbeDepth probe_corner_moments(const ProbeGridView& g, const ProbeDepthView& dv, const float pp[3], uint32_t ix, uint32_t iy, uint32_t iz, uint32_t node)
+{
+    float v[3];
+    probe_corner_vector(g, pp, ix, iy, iz, v);
+    return dv.moments[(size_t)node * (dv.res * dv.res) + probe_oct_texel(v, dv.res)];
+}
+
 // The probe grid's lookup (pt_set_probe_grid; the definition is include/pt_api.h's, operation for operation): the irradiance over pi that the
 // grid's SH9 radiance probes give a surface at p with normal n, trilinear over the cell's eight corners with the invalid ones left out and
 // the rest renormalised.  Each corner is EVALUATED before it is blended: three running sums instead of 27 blended coefficients, and a corner
@@ -52,7 +85,12 @@ PT_HD void probe_ray(uint64_t seed, uint32_t n_sobol, uint32_t key, uint32_t sam
 #else
 #define PT_PROBE_PIN(a, b, c, d) ((void)0)
 #endif
-PT_HD bool probe_grid_lookup(const ProbeGridView& g, f3 p, f3 n, f3* out)
+// VIS (pt_set_probe_grid_depth): every corner's weight is multiplied by the Chebyshev visibility of P' from the node, read from the node's
+// depth moments in the texel of the direction node -> P', and with PT_PROBE_VIS_FACING by a factor that prefers nodes the surface faces.
+// The moments of a corner are one 8-byte load whose address depends on P' alone: it is issued one corner ahead with the corner's record.
+// Without VIS the function is what it was, operation for operation (dv is not read).
+template <bool VIS = false>
+PT_HD bool probe_grid_lookup(const ProbeGridView& g, f3 p, f3 n, f3* out, const ProbeDepthView* dv = nullptr)
 {
     const float pp[3] = {p.x + g.bias * n.x, p.y + g.bias * n.y, p.z + g.bias * n.z};
     uint32_t i0[3], i1[3];
@@ -78,13 +116,36 @@ PT_HD bool probe_grid_lookup(const ProbeGridView& g, f3 p, f3 n, f3* out)
     const uint32_t line[4] = {(row[0] + i0[1]) * g.count[0], (row[0] + i1[1]) * g.count[0], (row[1] + i0[1]) * g.count[0], (row[1] + i1[1]) * g.count[0]};
     float W = 0.0f, E[3] = {0.0f, 0.0f, 0.0f};
     DProbe r = g.nodes[line[0] + i0[0]];
+    DProbeDepth mr{};
+    if (VIS) mr = probe_corner_moments(g, *dv, pp, i0[0], i0[1], i0[2], line[0] + i0[0]);
 #pragma unroll
     for (uint32_t k = 0; k < 8u; ++k)
     {
         const DProbe cur = r;
-        if (k < 7u) r = g.nodes[line[(k + 1u) >> 1] + (((k + 1u) & 1u) ? i1[0] : i0[0])];
+        const DProbeDepth mcur = mr;
+        if (k < 7u)
+        {
+            const uint32_t node = line[(k + 1u) >> 1] + (((k + 1u) & 1u) ? i1[0] : i0[0]);
+            r = g.nodes[node];
+            if (VIS) mr = probe_corner_moments(g, *dv, pp, ((k + 1u) & 1u) ? i1[0] : i0[0], ((k + 1u) & 2u) ? i1[1] : i0[1], ((k + 1u) & 4u) ? i1[2] : i0[2], node);
+        }
         const float wx = (k & 1u) ? f[0] : 1.0f - f[0], wy = (k & 2u) ? f[1] : 1.0f - f[1], wz = (k & 4u) ? f[2] : 1.0f - f[2];
-        const float w = ((wx * wy) * wz) * (cur.valid != 0.0f ? 1.0f : 0.0f);
+        float w = ((wx * wy) * wz) * (cur.valid != 0.0f ? 1.0f : 0.0f);
+        if (VIS)
+        {
+            float v[3];
+            probe_corner_vector(g, pp, (k & 1u) ? i1[0] : i0[0], (k & 2u) ? i1[1] : i0[1], (k & 4u) ? i1[2] : i0[2], v);
+            const float rr = sqrtf((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
+            const float var = fabsf(mcur.m2 - mcur.m1 * mcur.m1), dl = rr - mcur.m1;
+            const float ch = var / (var + dl * dl), c3 = (ch * ch) * ch;
+            const float vis = rr > mcur.m1 ? (c3 > dv->vis_floor ? c3 : dv->vis_floor) : 1.0f; // (a NaN c3 is never selected)
+            w = w * vis;
+            if (dv->facing)
+            {
+                const float cs = ((v[0] * n.x + v[1] * n.y) + v[2] * n.z) / rr, h = (1.0f - cs) * 0.5f;
+                w = w * (rr > 0.0f ? h * h + 0.2f : 1.0f);
+            }
+        }
         W = k ? W + w : w;
 #pragma unroll
         for (int c = 0; c < 3; ++c)

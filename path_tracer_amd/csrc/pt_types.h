@@ -145,6 +145,21 @@ struct ProbeGridView
     uint32_t count[3];
     float bias;
 };
+// Probe visibility (pt_set_probe_grid_depth): the depth moments of a node's octahedral map, R * R texels per node in the nodes' order, texel
+// probe_oct_texel (pt_probe.h) of the direction from the node: the mean distance seen through the texel and the mean of its square.
+struct alignas(8) DProbeDepth
+{
+    float m1, m2;
+};
+static_assert(sizeof(DProbeDepth) == 8, "one 8-byte word");
+// What the lookup with visibility reads on top of the grid: a table and a view of their own, handed only to the VIS instantiations.
+struct ProbeDepthView
+{
+    const DProbeDepth* moments;
+    uint32_t res;    // R, 2..16
+    uint32_t facing; // PT_PROBE_VIS_FACING set
+    float vis_floor;
+};
 
 // the barycentrics (u = v) of the light sampler's one-point quadrature (pt_api.h, LIGHT WEIGHT): a light triangle's weight is its area times
 // the length of its emitted colour there.  One constant for the host's weights (HostScene::build_lights) and the kernels' pdf (resolve_nee)

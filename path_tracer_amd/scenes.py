@@ -255,6 +255,33 @@ def cornell_media(width=256, height=256, level=3) -> SceneDesc:
     return SceneDesc.new(models, reference_camera(width / height), "cornell_media")
 
 
+def _room(x0, x1, y0, y1, z0, z1):
+    """the six quads of a sealed room, normals towards its inside"""
+    t = np.concatenate([
+        _quad((x0, y0, z1), (x1, y0, z1), (x1, y0, z0), (x0, y0, z0)), _quad((x0, y1, z0), (x1, y1, z0), (x1, y1, z1), (x0, y1, z1)),
+        _quad((x0, y0, z0), (x1, y0, z0), (x1, y1, z0), (x0, y1, z0)), _quad((x0, y0, z1), (x0, y1, z1), (x1, y1, z1), (x1, y0, z1)),
+        _quad((x0, y0, z1), (x0, y0, z0), (x0, y1, z0), (x0, y1, z1)), _quad((x1, y0, z0), (x1, y0, z1), (x1, y1, z1), (x1, y1, z0))])
+    return t, _flat_normals(t, ((x0 + x1) / 2, (y0 + y1) / 2, (z0 + z1) / 2))
+
+
+def two_rooms(width=48, height=32) -> SceneDesc:
+    """The light leak of an irradiance volume, isolated: a lit room (x < 0, a lamp under its ceiling) and a sealed lightless room (x > 0) share
+    a partition at x = 0, a thin slab whose two faces (x = -0.125 and 0.125) each close their own room, so that both rooms see front faces.
+    Everything is Lambertian; no light reaches the dark room, whose true radiance is 0.  The rooms span x -8..8, y 0..4, z 0..4: a 4 x 2 x 2
+    grid over the scene's bounds inset by half a cell (cell 4 x 2 x 2) has node columns at x = -6, -2, 2, 6 with the slab between columns 1
+    and 2.  The camera stands in the dark room and looks at the partition."""
+    gray = Lambertian.new((0.73, 0.73, 0.73))
+    lit_t, lit_n = _room(-8.0, -0.125, 0.0, 4.0, 0.0, 4.0)
+    dark_t, dark_n = _room(0.125, 8.0, 0.0, 4.0, 0.0, 4.0)
+    lamp_t = _quad((-5.0, 3.96875, 1.0), (-3.0, 3.96875, 1.0), (-3.0, 3.96875, 3.0), (-5.0, 3.96875, 3.0))
+    models = [
+        _model(lamp_t, _flat_normals(lamp_t, (-4.0, 2.0, 2.0)), Emissive.new((15.0, 15.0, 15.0)), "tr_lamp"),
+        _model(lit_t, lit_n, gray, "tr_lit"),
+        _model(dark_t, dark_n, gray, "tr_dark"),
+    ]
+    return SceneDesc.new(models, Camera.new((7.5, 2.0, 2.0), (0.125, 1.0, 2.0), 60.0, width / height), "two_rooms")
+
+
 def general_turn(rng, spread=60) -> np.ndarray:
     """A rigid instance matrix as the reference's host would build it — unit quaternion -> Mat3A::from_quat in binary32 (scene_desc) — that
     passes Model::new's own `scale == ONE` assert (model.rs:40-44; about a third of random quaternions do: the three column lengths must

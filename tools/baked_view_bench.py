@@ -4,14 +4,19 @@ pt_render_baked(1 sample) at K = 0 and K = 2, beside pt_render_guides_followed a
 the 1-spp pt_frame.  Every figure is the median of --calls blocking calls, taken --reps times with the routes alternating, so that a drift
 of the shared machine touches all of them; the report keeps every repeat, the spread is theirs.
 
-    python tools/baked_view_bench.py [--calls 20] [--reps 3] [--what all|guides] [--probes] [--out report.json]
+    python tools/baked_view_bench.py [--calls 20] [--reps 3] [--what all|guides] [--probes [--depth R]] [--out report.json]
 
 --what guides times the guides call alone and runs on a tree that has no baked view: run it from the parent commit's tree and from this one,
 turn about, for the comparison across the two (the guide kernels themselves must not have moved).
 
 --probes (profiles/r24_probe_grid.md) times the probe ending instead: no map anywhere, so that a 16 x 16 x 16 probe grid over the scene's
 bounds is the only light source of every final surface, ms per pt_render_baked(1 sample) at K = 0 and K = 2 with the grid beside the same
-calls on a context without one; and pt_probe_backfaces for 4 096 probes x 256 samples beside pt_bake_probes of the same shape."""
+calls on a context without one; and pt_probe_backfaces for 4 096 probes x 256 samples beside pt_bake_probes of the same shape.
+
+--probes --depth R (profiles/r25_probe_depth.md) adds probe visibility: a third context whose grid carries a seeded R x R depth table (FACING
+on), its pt_render_baked beside the two others; pt_bake_probe_depth beside pt_probe_backfaces on 4 096 probes x 1 024 rays (the same trace
+plus one fold each); and pt_probe_grid_lookup(on_device) with and without depth on 2^20 points (blocking calls: both include the same
+staging copies of 28 MiB)."""
 import argparse
 import json
 import os
@@ -51,6 +56,7 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--what", choices=["all", "guides"], default="all")
     ap.add_argument("--probes", action="store_true")
+    ap.add_argument("--depth", type=int, default=0)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import torch
@@ -112,6 +118,7 @@ def emit(report, out):
 
 
 GRID, CENSUS_PROBES, CENSUS_SAMPLES = 16, 4096, 256
+DEPTH_SAMPLES, LOOKUPS = 1024, 1 << 20
 
 
 def probes(args, api, scenes):
@@ -138,6 +145,26 @@ def probes(args, api, scenes):
         routes.append((report["baked_probes_ms"][str(k)], lambda k=k: view(lit, k), args.calls))
     routes.append((report["backfaces_ms"], lambda: bare.probe_backfaces(pos, CENSUS_SAMPLES), 3))
     routes.append((report["bake_probes_ms"], lambda: bare.bake_probes(pos, CENSUS_SAMPLES), 3))
+    if args.depth:
+        R = args.depth
+        vis = api.Renderer(sc, W, H, max_bounces=DEPTH)
+        vis.set_probe_grid(lo + 0.5 * cell, cell, sh, normal_bias=0.01 * float(cell.min()))
+        reach = float(np.linalg.norm(cell))
+        m1 = rng.uniform(0.3, 1.5, (GRID ** 3, R * R)).astype(np.float32) * np.float32(reach)
+        m2 = m1 * m1 + (rng.uniform(0.0, 0.3, m1.shape).astype(np.float32) * np.float32(reach)) ** 2
+        vis.set_probe_grid_depth(np.stack([m1, m2], axis=-1), 0.0, True)
+        far = 1.5 * reach
+        q = (lo + rng.uniform(0.0, 1.0, (LOOKUPS, 3)) * (hi - lo)).astype(np.float32)
+        qn = rng.normal(size=(LOOKUPS, 3))
+        qn = (qn / np.linalg.norm(qn, axis=1, keepdims=True)).astype(np.float32)
+        report.update(depth=R, baked_probes_depth_ms={str(k): [] for k in HOPS}, depth_census=[CENSUS_PROBES, DEPTH_SAMPLES], backfaces_1024_ms=[],
+                      bake_probe_depth_ms=[], lookups=LOOKUPS, lookup_ms=[], lookup_depth_ms=[])
+        for k in HOPS:
+            routes.append((report["baked_probes_depth_ms"][str(k)], lambda k=k: view(vis, k), args.calls))
+        routes.append((report["backfaces_1024_ms"], lambda: bare.probe_backfaces(pos, DEPTH_SAMPLES), 3))
+        routes.append((report["bake_probe_depth_ms"], lambda: bare.bake_probe_depth(pos, DEPTH_SAMPLES, R, far), 3))
+        routes.append((report["lookup_ms"], lambda: lit.probe_grid_lookup(q, qn, on_device=True), 5))
+        routes.append((report["lookup_depth_ms"], lambda: vis.probe_grid_lookup(q, qn, on_device=True), 5))
     for _, fn, _ in routes:
         fn()
     for _ in range(args.reps):
