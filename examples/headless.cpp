@@ -40,6 +40,9 @@
 //   examples/headless ... --probe-grid NX NY NZ SPP --probe-depth R --baked-view SPP out.png   also bakes the nodes' R x R octahedral depth moments
 //       from the same rays (pt_bake_probe_depth, distances clamped to 1.5 cell diagonals) and sets them (pt_set_probe_grid_depth), so that the
 //       grid's lookup weighs every node by its visibility and light stops leaking through walls
+//   examples/headless ... --probe-grid NX NY NZ SPP --probe-radiance R --baked-view SPP out.png   also bakes the nodes' R x R octahedral radiance maps
+//       from the same rays (pt_bake_probe_radiance), prefilters them on the device at the GGX alphas 0.1, 0.2, 0.4, 0.7 and 1 and sets them
+//       (pt_set_probe_grid_radiance), so that GGX metal in the baked view reflects its surroundings; --metal-box makes the tall box such a metal
 //   examples/headless ... --bake-lightmap ... --lightmap-denoise [--baked-view ...]   bakes with second moments (pt_bake_lightmap_moments), runs the
 //       texel-space filter on the sums (pt_lightmap_denoise, default parameters) and dilates its texel MEANS: map.txt then holds means, not sums,
 //       and --baked-view sets them as they are
@@ -85,6 +88,8 @@ int main(int argc, char** argv)
     uint32_t probe_grid[4] = {0, 0, 0, 0}; // --probe-grid NX NY NZ SPP
     uint32_t probe_depth = 0;              // --probe-depth R
     bool probe_depth_given = false;
+    uint32_t probe_radiance = 0;           // --probe-radiance R
+    bool probe_radiance_given = false, metal_box = false;
     bool lightmap_denoise = false;
     std::string baked_out = "";
     pt_projection projection{}; // PT_PROJ_PERSPECTIVE
@@ -149,6 +154,12 @@ int main(int argc, char** argv)
             probe_depth = (uint32_t)std::atoi(next("--probe-depth"));
             probe_depth_given = true;
         }
+        else if (a == "--probe-radiance")
+        {
+            probe_radiance = (uint32_t)std::atoi(next("--probe-radiance"));
+            probe_radiance_given = true;
+        }
+        else if (a == "--metal-box") metal_box = true;
         else if (a == "--baked-view")
         {
             baked_spp = (uint32_t)std::atoi(next("--baked-view"));
@@ -164,7 +175,7 @@ int main(int argc, char** argv)
         }
         else if (a == "--help" || a == "-h")
         {
-            std::printf("usage: %s [--width W] [--height H] [--frames N] [--bounces B] [--move] [--slide DX DZ] [--models DIR] [--out file.png] [--temporal file.png [--temporal-rescue] [--temporal-mean-length] [--temporal-demodulate]] [--denoise file.png] [--denoise-albedo file.png] [--follow K] [--mirror-glass] [--aperture A --focus F] [--projection panorama[:SX:SY]|ortho:HEIGHT] [--bake-probes NX NY NZ SPP file.txt] [--bake-lightmap W H SPP PASSES file.txt [--lightmap-denoise] [--baked-view SPP file.png]] [--probe-grid NX NY NZ SPP --baked-view SPP file.png] [--checker N] [--emission-checker N] [--normal-ripples N]\n", argv[0]);
+            std::printf("usage: %s [--width W] [--height H] [--frames N] [--bounces B] [--move] [--slide DX DZ] [--models DIR] [--out file.png] [--temporal file.png [--temporal-rescue] [--temporal-mean-length] [--temporal-demodulate]] [--denoise file.png] [--denoise-albedo file.png] [--follow K] [--mirror-glass] [--aperture A --focus F] [--projection panorama[:SX:SY]|ortho:HEIGHT] [--bake-probes NX NY NZ SPP file.txt] [--bake-lightmap W H SPP PASSES file.txt [--lightmap-denoise] [--baked-view SPP file.png]] [--probe-grid NX NY NZ SPP [--probe-depth R] [--probe-radiance R] --baked-view SPP file.png] [--metal-box] [--checker N] [--emission-checker N] [--normal-ripples N]\n", argv[0]);
             return 0;
         }
         else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
@@ -183,6 +194,11 @@ int main(int argc, char** argv)
     if (probe_depth_given && (!with_grid || probe_depth < 2 || probe_depth > 16))
     {
         std::fprintf(stderr, "--probe-depth R takes a map side of 2..16 and goes with --probe-grid\n");
+        return 2;
+    }
+    if (probe_radiance_given && (!with_grid || probe_radiance < 2 || probe_radiance > 16))
+    {
+        std::fprintf(stderr, "--probe-radiance R takes a map side of 2..16 and goes with --probe-grid\n");
         return 2;
     }
     if (lightmap_denoise && (lightmap_out.empty() || !lightmap[2]))
@@ -246,7 +262,7 @@ int main(int argc, char** argv)
             Model::New(models_dir + "/cb_main.obj", main_gray, one),
             Model::New(models_dir + "/cb_right.obj", diffuse_red, one),
             Model::New(models_dir + "/cb_left.obj", diffuse_green, one),
-            Model::New(models_dir + "/cb_box_tall.obj", mirror_glass ? Specular::New(Vec3A::splat(1.0f)) : diffuse_gray, one),
+            Model::New(models_dir + "/cb_box_tall.obj", mirror_glass ? Specular::New(Vec3A::splat(1.0f)) : metal_box ? GGX::NewMetal(Vec3A{0.9f, 0.8f, 0.6f}, 0.4f) : diffuse_gray, one),
             Model::New(models_dir + "/cb_box_short.obj", mirror_glass ? Dielectric::New(Vec3A::splat(0.95f), 1.5f, std::nullopt) : diffuse_gray, one),
         });
 
@@ -367,7 +383,7 @@ int main(int argc, char** argv)
                     g.cell[k] = (box[3 + k] - box[k]) / (float)probe_grid[k];
                     g.origin[k] = box[k] + 0.5f * g.cell[k];
                 }
-                renderer.bake_probe_grid(g, probe_grid[3], 0.25f, probe_depth);
+                renderer.bake_probe_grid(g, probe_grid[3], 0.25f, probe_depth, 0.0f, 0.0f, false, probe_radiance);
             }
             renderer.render_baked(0, baked_spp, follow);
             renderer.write_baked_image(baked_out);

@@ -1017,8 +1017,7 @@ int pt_lightmap_lookup(pt_ctx* ctx, int on_device, uint32_t n, const uint32_t* i
  * a range beyond 2^32; PT_ERR_STATE as pt_render_guides; pt_read_baked and pt_write_baked_image PT_ERR_STATE without current sums.  A scene
  * with no map at all is legal.
  * With a probe grid set (pt_set_probe_grid, below) the third ending reads the grid instead of unlit wherever the grid lights the point.
- * Out of scope: pt_multi_* variants, directional maps, a specular response on GGX surfaces,
- * perturbed normals, ending the path tracer's own paths in the maps.  (The maps themselves are filtered before they are set:
+ * Out of scope: pt_multi_* variants, directional maps, perturbed normals, ending the path tracer's own paths in the maps.  (The maps themselves are filtered before they are set:
  * pt_lightmap_denoise, which knows the coverage, then pt_lightmap_dilate.) */
 typedef struct pt_baked_params
 {
@@ -1073,8 +1072,8 @@ int pt_write_baked_image(pt_ctx* ctx, const char* path);
  * and every other ending is what it was: a mapped front face is lit by its map.  The ending is a kernel of its own, chosen on the host, so
  * without a grid every call returns the bits it returned before.  The baked sums go stale on pt_set_probe_grid as on pt_set_lightmap.
  * Visibility is pt_set_probe_grid_depth's, below.
- * Out of scope: cell-skipping and probe relocation, probes in the path tracer's own paths, a specular response,
- * pt_multi_* variants, SH above band 2. */
+ * A specular response on GGX metal is pt_set_probe_grid_radiance's, below.
+ * Out of scope: cell-skipping and probe relocation, probes in the path tracer's own paths, pt_multi_* variants, SH above band 2. */
 typedef struct pt_probe_grid
 {
     float origin[3];      /* position of node (0, 0, 0); finite */
@@ -1164,6 +1163,112 @@ typedef struct pt_probe_depth
 } pt_probe_depth;
 int pt_set_probe_grid_depth(pt_ctx* ctx, const pt_probe_depth* v, const float* moments);
 int pt_get_probe_grid_depth_info(pt_ctx* ctx, pt_probe_depth* out);
+
+/* ---- reflection probes: GGX-prefiltered radiance on the nodes' octahedral maps ------------------------------------------------------------- */
+/* The SH9 probes of pt_set_probe_grid hold irradiance; a rough metal reflects a lobe of RADIANCE around the mirror direction.  With radiance
+ * set, every node also holds, per roughness level, an R x R octahedral map of the radiance it sees, prefiltered by that level's GGX lobe, and
+ * pt_probe_grid_specular reads it in the reflected direction.  Radiance is opt-in: a context that never sets it launches what it launched
+ * before.  Everything below is binary32, one rounding per operation, no contraction, sums in the stated order.
+ * THE DIRECTION of texel i = iy * R + ix (probe_oct_dir), the inverse of THE TEXEL at texel centres:
+ *     px = 2 * (((float)ix + 0.5f) / (float)R) - 1;  py likewise from iy
+ *     z  = (1 - |px|) - |py|
+ *     if (z < 0):  (px, py) = ((1 - |py|) * (px >= 0 ? 1 : -1),  (1 - |px|) * (py >= 0 ? 1 : -1))         -- both from the OLD px, py
+ *     len = sqrtf((px*px + py*py) + z*z);   dir = (px / len, py / len, z / len);   omega = 1 / ((len * len) * len)
+ *   omega is the texel's solid angle up to the constant 4 / R^2 (the octahedral map's area element is dA / len^3 and the fold is an isometry);
+ *   the constant cancels in the prefilter.  THE TEXEL of dir(i) in a map of side R is i, for every R in 2..16.
+ * pt_probe_radiance_dir is its host hook: n texels to n directions (3 floats each) and n omegas; no context, no GPU.  PT_ERR_LIMIT for a res
+ * outside 2..16, PT_ERR_ARG for a NULL pointer with n > 0 or a texel >= res * res (nothing is written then).
+ * THE BAKE.  pt_bake_probe_radiance casts pt_bake_probes' rays (pt_probe_ray(key_base + j, s) from position_xyz[j], stream (key_base + j, s),
+ * draws_consumed = 1) and integrates them as pt_bake_probes does, the full path.  For each ray, L its radiance:
+ *     texel = THE TEXEL of the ray's direction;   counts[j][texel] += 1;   rgb_sums[j][texel][c] = rgb_sums[j][texel][c] + L[c]
+ * Per (probe, texel) the adds happen in ascending sample order, starting from what the arrays hold, however the ray table is cut (its chunks,
+ * and pt_config.batch_spp): bake(0, a) then bake(a, b) equals bake(0, a + b) bit for bit.  One wave owns a probe for a launch, the launches of
+ * a call are serial on one stream, and there are no atomics.  rgb_sums (n_probes * R*R * 3 floats) and counts (n_probes * R*R) are host
+ * arrays, IN/OUT.  The frame is not touched.
+ * Errors, before any device call: those of pt_bake_probes (with rgb_sums and counts in sh27's place); then a res outside 2..16 (PT_ERR_LIMIT),
+ * a non-zero reserved word (ARG). */
+typedef struct pt_probe_radiance_params
+{
+    uint32_t first_sample, n_samples, key_base; /* as pt_probe_params */
+    uint32_t res;                               /* R: side of the octahedral map, 2..16 */
+    uint32_t reserved[4];                       /* must be 0 */
+} pt_probe_radiance_params;
+int pt_probe_radiance_dir(uint32_t res, uint32_t n, const uint32_t* texel, float* dir_xyz, float* omega);
+int pt_bake_probe_radiance(pt_ctx* ctx, uint32_t n_probes, const float* position_xyz, const pt_probe_radiance_params* p, float* rgb_sums, uint32_t* counts);
+/* THE PREFILTER.  pt_probe_radiance_prefilter turns n_probes raw maps into table[probe][level][texel] (4 floats each, the fourth 0), the layout
+ * pt_set_probe_grid_radiance takes.  For probe q, level l and output texel i, with n = dir(i) and (l_j, omega_j) = THE DIRECTION of texel j:
+ *     A = (0, 0, 0);  Wt = 0
+ *     for j = 0 .. R*R - 1, ascending:
+ *         skip j if counts[q][j] == 0
+ *         nl = (n.x * l_j.x + n.y * l_j.y) + n.z * l_j.z;                 skip j if !(nl > 0)
+ *         h  = n + l_j;  h = h / sqrtf((h.x*h.x + h.y*h.y) + h.z*h.z);    nh = (n.x * h.x + n.y * h.y) + n.z * h.z
+ *         nh = nh > 1 ? 1 : nh                                            -- rounding takes the cosine of j = i past 1, where D is a NaN
+ *         w  = (D(alpha[l], nh) * nl) * omega_j             D: the material's own GGX distribution (ggx_d, which reads the cosine only):
+ *                  nh <= 0 ? 0 :  c2 = nh * nh;  x = alpha * alpha + sqrtf(1 - c2) / c2;  (alpha * alpha) / ((((PI * c2) * c2) * x) * x)
+ *         mean_c = rgb_sums[q][j][c] / (float)counts[q][j]
+ *         A_c = A_c + w * mean_c;   Wt = Wt + w
+ *     table[q][l][i] = Wt > 0 ? (A_0 / Wt, A_1 / Wt, A_2 / Wt, 0) : (0, 0, 0, 0)
+ *   the split-sum radiance integral with V = N = R, as a quadrature over the map.  A constant map comes back as that constant up to rounding.
+ * on_device = 0 evaluates on the host and touches no GPU; 1 runs k_probe_radiance_prefilter over the same per-texel function: one workgroup
+ * per (probe, level), one lane per output texel, the probe's means and the direction table staged in LDS once, the j loop serial in a lane.
+ * Errors, before any device call, the first in this order: a NULL f (ARG); a non-zero reserved word (ARG); a res outside 2..16 (PT_ERR_LIMIT);
+ * n_levels outside 1..8 (PT_ERR_LIMIT); an alpha that is not finite, not in (0, 1] or not above the one before (ARG); a NULL array with
+ * n_probes > 0 (ARG); a table above 2^31 bytes (PT_ERR_LIMIT).  The sums' values are not checked. */
+typedef struct pt_probe_radiance_filter
+{
+    uint32_t res;         /* R, 2..16 */
+    uint32_t n_probes;
+    uint32_t n_levels;    /* 1..8 */
+    float alpha[8];       /* the levels' GGX alphas: finite, in (0, 1], strictly ascending; those from n_levels on are not read */
+    uint32_t reserved[5]; /* must be 0 */
+} pt_probe_radiance_filter;
+int pt_probe_radiance_prefilter(pt_ctx* ctx, int on_device, const pt_probe_radiance_filter* f, const float* rgb_sums, const uint32_t* counts, float* table);
+/* RADIANCE ON THE GRID.  pt_set_probe_grid_radiance gives every node of the grid in force its prefiltered maps: table holds
+ * nodes * n_levels * R*R * 4 floats, [node][level][texel], as THE PREFILTER writes them.  r NULL (with table NULL) clears radiance.
+ * pt_get_probe_grid_radiance_info reports what is set, res 0 where none is.  Radiance belongs to a grid: ANY pt_set_probe_grid call drops it;
+ * otherwise it survives what the grid survives.  Setting or clearing it counts as a change of the grid: the baked sums go stale.  On the
+ * device it is a table of its own, 16 bytes per texel per level per node, uploaded by the next call that needs it and handed only to the
+ * kernels that read it.  An invalid node's values are checked and then kept as zeros.
+ * Errors, all before any device call (a refused call changes nothing); the first in this order is reported: r NULL with a table (ARG); a
+ * non-zero reserved word (ARG); no grid set (PT_ERR_STATE); r with a NULL table (ARG); a res outside 2..16 (PT_ERR_LIMIT); n_levels outside
+ * 1..8 (PT_ERR_LIMIT); an alpha as THE PREFILTER refuses it (ARG); a table above 2^31 bytes (PT_ERR_LIMIT); then the values, read last: one
+ * that is not finite or is negative (ARG).  A table that does not fit in host memory is PT_ERR_LIMIT.
+ * THE SPECULAR LOOKUP at world position P with unit normal n, incoming ray direction d and roughness a (probe_grid_specular):
+ *     r = d - (2 * ((n.x * d.x + n.y * d.y) + n.z * d.z)) * n                    -- reflect_rs, the mirror's own
+ *     texel = THE TEXEL of r: the nearest texel, computed once, the same for all eight corners (a NaN lands on texel 0)
+ *     a = !(a > alpha[0]) ? alpha[0] : a;   l = the last level with alpha[l] <= a
+ *     l + 1 < n_levels:  t = (a - alpha[l]) / (alpha[l+1] - alpha[l]), l' = l + 1;   otherwise (one level, or at or above the top): t = 0, l' = l
+ *     corner k = 0..7: w_k is THE LOOKUP's, with P' = P + normal_bias * n, its clamp and NaN rule and invalid corners 0, and with depth set THE
+ *         LOOKUP WITH VISIBILITY's (vis and, with PT_PROBE_VIS_FACING, fb)
+ *         L_k,c = (1 - t) * T[node_k][l][texel][c] + t * T[node_k][l'][texel][c]
+ *         S_c = S_c + w_k * L_k,c;   W = W + w_k                                                            -- both from 0, k ascending
+ *     lit = W > 0;   result = lit ? S / W : 0
+ *   Two exact cases without depth: a 1 x 1 x 1 grid with one level returns its table entry of the texel bit for bit, everywhere; at a valid
+ *   node's own position with normal_bias 0 and t = 0 the result is that node's entry T[node][l][texel] (with depth set as well: vis = fb = 1).
+ * pt_probe_grid_specular is its unit hook: n queries (host pointers; position_xyz, normal_xyz and incoming_xyz 3 floats each, alpha one float
+ * each, any values), rgb 3 floats and lit a byte per query.  on_device = 0 evaluates on the host and touches no GPU, 1 runs a kernel over the
+ * same function (one with visibility when depth is set).  PT_ERR_STATE without a grid or without radiance, PT_ERR_ARG for a NULL pointer with
+ * n > 0.
+ * THE BAKED VIEW WITH RADIANCE.  While radiance is set, a chain of pt_render_baked that ends on a PT_GGX_METAL surface, on either face, becomes
+ *     B = R_H * S   where THE SPECULAR LOOKUP is lit at P = the position and n = the normal that pt_render_guides_followed writes for that
+ *     chain's end, d = the direction of the chain's last ray and a = the material's GGX alpha (roughness squared, clamped to 0.0001..0.9999)
+ * before any map is asked: a map holds irradiance, which a metal does not reflect diffusely.  Where the lookup is not lit the ending is what it
+ * is without radiance, and every other kind is untouched.  The endings are kernels of their own (k_baked_follow_probes_spec[_vis]), chosen on
+ * the host: without radiance every call launches what it launched and returns the bits it returned before.
+ * Out of scope: bilinear filtering across texels and fold lines, a Fresnel or environment-BRDF term, PT_GGX_DIELECTRIC, lobes that depend on
+ * the view angle, maps above 16 x 16, per-texel stratified rays, parallax correction, pt_multi_* variants, probes in the path tracer's own
+ * paths. */
+typedef struct pt_probe_radiance
+{
+    uint32_t res;         /* R, 2..16 */
+    uint32_t n_levels;    /* 1..8 */
+    float alpha[8];       /* as pt_probe_radiance_filter's */
+    uint32_t reserved[6]; /* must be 0 */
+} pt_probe_radiance;
+int pt_set_probe_grid_radiance(pt_ctx* ctx, const pt_probe_radiance* r, const float* table);
+int pt_get_probe_grid_radiance_info(pt_ctx* ctx, pt_probe_radiance* out);
+int pt_probe_grid_specular(pt_ctx* ctx, int on_device, uint32_t n, const float* position_xyz, const float* normal_xyz, const float* incoming_xyz,
+                           const float* alpha, float* rgb, uint8_t* lit);
 
 /* ---- unit hooks: TLAS::intersect / any_intersect  src/tlas.rs:66, 111 ------------------------------------------ */
 /* which: 0 world TLAS, 1 lights TLAS.  Host SoA in, host SoA out.  miss => inst = prim = 0xffffffff, t = +inf.

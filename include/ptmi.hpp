@@ -550,9 +550,11 @@ public:
     }
     // bakes and sets a grid: the node positions, bake_probes, probe_validity and set_probe_grid_sums; returns the valid bytes
     // depth_res > 0 also bakes the nodes' depth moments from the same rays and sets them (bake_probe_depth, set_probe_grid_depth_sums);
-    // max_distance <= 0: the cell's diagonal times 1.5
+    // max_distance <= 0: the cell's diagonal times 1.5.  radiance_res > 0 also bakes the nodes' radiance maps from the same rays, prefilters
+    // them at radiance_alphas on the device and sets them (bake_probe_radiance, set_probe_grid_radiance_sums)
     std::vector<uint8_t> bake_probe_grid(const pt_probe_grid& g, uint32_t n_samples, float max_back_fraction = 0.25f, uint32_t depth_res = 0,
-                                         float max_distance = 0.0f, float vis_floor = 0.0f, bool facing = false)
+                                         float max_distance = 0.0f, float vis_floor = 0.0f, bool facing = false, uint32_t radiance_res = 0,
+                                         const std::vector<float>& radiance_alphas = {0.1f, 0.2f, 0.4f, 0.7f, 1.0f})
     {
         std::vector<float> pos;
         for (uint32_t z = 0; z < g.count[2]; ++z)
@@ -571,6 +573,13 @@ public:
             std::vector<uint32_t> dcounts;
             bake_probe_depth(pos, n_samples, depth_res, max_distance, dsums, dcounts);
             set_probe_grid_depth_sums(depth_res, dsums, dcounts, max_distance, vis_floor, facing);
+        }
+        if (radiance_res)
+        {
+            std::vector<float> rsums;
+            std::vector<uint32_t> rcounts;
+            bake_probe_radiance(pos, n_samples, radiance_res, rsums, rcounts);
+            set_probe_grid_radiance_sums(radiance_res, rsums, rcounts, radiance_alphas);
         }
         return valid;
     }
@@ -623,6 +632,80 @@ public:
         set_probe_grid_depth(res, m, vis_floor, facing);
     }
     pt_probe_depth probe_grid_depth_info() const { pt_probe_depth v{}; check(pt_get_probe_grid_depth_info(ctx_, &v)); return v; }
+    // reflection probes.  The unit direction (3 floats each) and relative solid angle of every texel centre of an octahedral map of side res,
+    // in the texels' order (pt_probe_radiance_dir)
+    static std::vector<float> probe_radiance_dir(uint32_t res, std::vector<float>& omega)
+    {
+        if (res < 2 || res > 16) throw Error(PT_ERR_LIMIT, "probe_radiance_dir: res is 2..16");
+        std::vector<uint32_t> texel(res * res);
+        for (uint32_t i = 0; i < res * res; ++i) texel[i] = i;
+        std::vector<float> dir(texel.size() * 3);
+        omega.assign(texel.size(), 0.0f);
+        const int r = pt_probe_radiance_dir(res, (uint32_t)texel.size(), texel.data(), dir.data(), omega.data());
+        if (r != PT_OK) throw Error(r, "probe_radiance_dir");
+        return dir;
+    }
+    // radiance maps (pt_bake_probe_radiance): adds the radiance of bake_probes' rays, the full path each, to the raw sums (res * res * 3 floats
+    // per probe) and counts (res * res per probe) per octahedral texel, in sample order; empty vectors start a fresh bake from zero
+    void bake_probe_radiance(const std::vector<float>& positions, uint32_t n_samples, uint32_t res, std::vector<float>& sums, std::vector<uint32_t>& counts,
+                             uint32_t first_sample = 0, uint32_t key_base = 0)
+    {
+        if (positions.size() % 3 != 0 || positions.size() / 3 > 0xffffffffull) throw Error(PT_ERR_ARG, "bake_probe_radiance: positions are 3 floats per probe");
+        const size_t n = positions.size() / 3, texels = n * res * res;
+        if (sums.empty() && counts.empty()) { sums.assign(texels * 3, 0.0f); counts.assign(texels, 0u); }
+        if (res >= 2 && res <= 16 && (sums.size() != texels * 3 || counts.size() != texels))
+            throw Error(PT_ERR_ARG, "bake_probe_radiance: sums hold res * res * 3 values and counts res * res per probe");
+        pt_probe_radiance_params p{};
+        p.first_sample = first_sample; p.n_samples = n_samples; p.key_base = key_base; p.res = res;
+        check(pt_bake_probe_radiance(ctx_, (uint32_t)n, positions.data(), &p, sums.data(), counts.data()));
+    }
+    // the GGX prefilter of raw radiance maps (pt_probe_radiance_prefilter): the table [probe][level][texel] of 4 floats each, one level per alpha
+    std::vector<float> probe_radiance_prefilter(uint32_t res, const std::vector<float>& sums, const std::vector<uint32_t>& counts, const std::vector<float>& alphas,
+                                                bool on_device = true)
+    {
+        if (res < 2 || res > 16 || alphas.empty() || alphas.size() > 8 || counts.size() % (res * res) != 0 || sums.size() != counts.size() * 3)
+            throw Error(PT_ERR_ARG, "probe_radiance_prefilter: res 2..16, 1..8 alphas, res * res counts and three sums per count per probe");
+        pt_probe_radiance_filter f{};
+        f.res = res; f.n_probes = (uint32_t)(counts.size() / (res * res)); f.n_levels = (uint32_t)alphas.size();
+        for (size_t l = 0; l < alphas.size(); ++l) f.alpha[l] = alphas[l];
+        std::vector<float> table(counts.size() * alphas.size() * 4);
+        check(pt_probe_radiance_prefilter(ctx_, on_device ? 1 : 0, &f, sums.data(), counts.data(), table.data()));
+        return table;
+    }
+    // radiance on the grid in force (pt_set_probe_grid_radiance): probe_radiance_prefilter's table over the grid's nodes; an empty table clears it
+    void set_probe_grid_radiance(uint32_t res, const std::vector<float>& table, const std::vector<float>& alphas)
+    {
+        if (table.empty()) { check(pt_set_probe_grid_radiance(ctx_, nullptr, nullptr)); return; }
+        if (alphas.empty() || alphas.size() > 8) throw Error(PT_ERR_ARG, "set_probe_grid_radiance: 1..8 alphas");
+        pt_probe_radiance v{};
+        v.res = res; v.n_levels = (uint32_t)alphas.size();
+        for (size_t l = 0; l < alphas.size(); ++l) v.alpha[l] = alphas[l];
+        const pt_probe_grid g = probe_grid_info();
+        const size_t nodes = (size_t)g.count[0] * g.count[1] * g.count[2];
+        if (res >= 2 && res <= 16 && table.size() != nodes * alphas.size() * res * res * 4)
+            throw Error(PT_ERR_ARG, "set_probe_grid_radiance: the table holds levels * res * res * 4 values per node");
+        check(pt_set_probe_grid_radiance(ctx_, &v, table.data()));
+    }
+    // ... of bake_probe_radiance's raw sums and counts: the prefilter, then the setter
+    void set_probe_grid_radiance_sums(uint32_t res, const std::vector<float>& sums, const std::vector<uint32_t>& counts, const std::vector<float>& alphas,
+                                      bool on_device = true)
+    {
+        set_probe_grid_radiance(res, probe_radiance_prefilter(res, sums, counts, alphas, on_device), alphas);
+    }
+    pt_probe_radiance probe_grid_radiance_info() const { pt_probe_radiance v{}; check(pt_get_probe_grid_radiance_info(ctx_, &v)); return v; }
+    // the reflection probes' lookup at n world positions, normals and incoming directions (3 floats each) and GGX alphas (one each;
+    // pt_probe_grid_specular): rgb (n * 3) and the lit bytes
+    std::vector<float> probe_grid_specular(const std::vector<float>& position, const std::vector<float>& normal, const std::vector<float>& incoming,
+                                           const std::vector<float>& alpha, std::vector<uint8_t>& lit, bool on_device = false) const
+    {
+        if (position.size() % 3 != 0 || normal.size() != position.size() || incoming.size() != position.size() || alpha.size() * 3 != position.size())
+            throw Error(PT_ERR_ARG, "probe_grid_specular: positions, normals and incoming directions are 3 floats and alpha one per query");
+        const size_t n = alpha.size();
+        std::vector<float> rgb(n * 3);
+        lit.assign(n, 0);
+        check(pt_probe_grid_specular(ctx_, on_device ? 1 : 0, (uint32_t)n, position.data(), normal.data(), incoming.data(), alpha.data(), rgb.data(), lit.data()));
+        return rgb;
+    }
     // the world TLAS's root box: min xyz, max xyz
     std::array<float, 6> root_box() const { uint32_t rect[4]; std::array<float, 6> b{}; check(pt_active_pixels(ctx_, rect, b.data())); return b; }
     pt_stats stats() const { pt_stats s{}; check(pt_get_stats(ctx_, &s)); return s; }

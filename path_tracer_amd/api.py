@@ -52,6 +52,8 @@ EXPORTS = [
     "pt_set_probe_grid", "pt_get_probe_grid_info", "pt_probe_grid_lookup", "pt_probe_backfaces",
     "pt_bake_lightmap_moments", "pt_lightmap_denoise",
     "pt_probe_depth_texel", "pt_bake_probe_depth", "pt_set_probe_grid_depth", "pt_get_probe_grid_depth_info",
+    "pt_probe_radiance_dir", "pt_bake_probe_radiance", "pt_probe_radiance_prefilter", "pt_set_probe_grid_radiance", "pt_get_probe_grid_radiance_info",
+    "pt_probe_grid_specular",
 ]
 
 
@@ -154,6 +156,21 @@ class ProbeDepthParams(C.Structure):
 class ProbeDepth(C.Structure):
     """pt_probe_depth: the side of the nodes' octahedral depth maps, PROBE_VIS_FACING and the visibility floor (include/pt_api.h)"""
     _fields_ = [("res", C.c_uint32), ("flags", C.c_uint32), ("vis_floor", C.c_float), ("reserved", C.c_uint32 * 5)]
+
+
+class ProbeRadianceParams(C.Structure):
+    """pt_probe_radiance_params: the sample range and stream keys of a radiance bake and the octahedral map's side (include/pt_api.h)"""
+    _fields_ = [("first_sample", C.c_uint32), ("n_samples", C.c_uint32), ("key_base", C.c_uint32), ("res", C.c_uint32), ("reserved", C.c_uint32 * 4)]
+
+
+class ProbeRadianceFilter(C.Structure):
+    """pt_probe_radiance_filter: the maps' side, how many probes, and the GGX alphas of the levels the prefilter writes (include/pt_api.h)"""
+    _fields_ = [("res", C.c_uint32), ("n_probes", C.c_uint32), ("n_levels", C.c_uint32), ("alpha", C.c_float * 8), ("reserved", C.c_uint32 * 5)]
+
+
+class ProbeRadiance(C.Structure):
+    """pt_probe_radiance: the side of the nodes' prefiltered radiance maps and their levels' GGX alphas (include/pt_api.h)"""
+    _fields_ = [("res", C.c_uint32), ("n_levels", C.c_uint32), ("alpha", C.c_float * 8), ("reserved", C.c_uint32 * 6)]
 
 
 class LightmapParams(C.Structure):
@@ -334,6 +351,12 @@ def lib():
         L.pt_bake_probe_depth.argtypes = [vp, u32, vp, C.POINTER(ProbeDepthParams), vp, vp]
         L.pt_set_probe_grid_depth.argtypes = [vp, C.POINTER(ProbeDepth), vp]
         L.pt_get_probe_grid_depth_info.argtypes = [vp, C.POINTER(ProbeDepth)]
+        L.pt_probe_radiance_dir.argtypes = [u32, u32, vp, vp, vp]
+        L.pt_bake_probe_radiance.argtypes = [vp, u32, vp, C.POINTER(ProbeRadianceParams), vp, vp]
+        L.pt_probe_radiance_prefilter.argtypes = [vp, C.c_int, C.POINTER(ProbeRadianceFilter), vp, vp, vp]
+        L.pt_set_probe_grid_radiance.argtypes = [vp, C.POINTER(ProbeRadiance), vp]
+        L.pt_get_probe_grid_radiance_info.argtypes = [vp, C.POINTER(ProbeRadiance)]
+        L.pt_probe_grid_specular.argtypes = [vp, C.c_int, u32, vp, vp, vp, vp, vp, vp]
         L.pt_render_guides_followed.argtypes = [vp, u32, C.POINTER(GuideParams)]
         L.pt_read_guide_hops.argtypes = [vp, vp]
         L.pt_accumulate_albedo_followed.argtypes = [vp, u32, u32, C.POINTER(GuideParams)]
@@ -1214,10 +1237,12 @@ class Renderer:
         return (o + idx * c).astype(np.float32)
 
     def bake_probe_grid(self, origin, cell, count, n_samples, max_back_fraction=0.25, normal_bias=0.0, depth_res=0, max_distance=None, vis_floor=0.0,
-                        facing=False):
+                        facing=False, radiance_res=0, radiance_alphas=(0.1, 0.2, 0.4, 0.7, 1.0)):
         """bakes and sets a grid of count = (nx, ny, nz) probes: the node positions, bake_probes, probe_validity and set_probe_grid_sums.
         Returns (sums (nz, ny, nx, 9, 3), valid (nz, ny, nx)).  depth_res > 0 also bakes the nodes' depth moments from the same rays
-        (bake_probe_depth) and sets them (set_probe_grid_depth_sums); max_distance None: the cell's diagonal times 1.5."""
+        (bake_probe_depth) and sets them (set_probe_grid_depth_sums); max_distance None: the cell's diagonal times 1.5.  radiance_res > 0
+        also bakes the nodes' radiance maps from the same rays (bake_probe_radiance), prefilters them at radiance_alphas on the device and sets
+        them (set_probe_grid_radiance_sums)."""
         nx, ny, nz = (int(k) for k in count)
         pos = self.probe_grid_positions(origin, cell, count).reshape(-1, 3)
         sums = self.bake_probes(pos, n_samples).reshape(nz, ny, nx, 9, 3)
@@ -1228,6 +1253,9 @@ class Renderer:
                 max_distance = 1.5 * float(np.linalg.norm(np.asarray(cell, np.float64)))
             dsums, dcounts = self.bake_probe_depth(pos, n_samples, depth_res, max_distance)
             self.set_probe_grid_depth_sums(dsums, dcounts, max_distance, vis_floor, facing)
+        if radiance_res:
+            rsums, rcounts = self.bake_probe_radiance(pos, n_samples, radiance_res)
+            self.set_probe_grid_radiance_sums(rsums, rcounts, radiance_alphas)
         return sums, valid
 
     # ---- probe visibility: depth moments on the nodes' octahedral maps
@@ -1285,6 +1313,85 @@ class Renderer:
         v = ProbeDepth()
         self._chk(self.L.pt_get_probe_grid_depth_info(self.ctx, C.byref(v)))
         return int(v.res), int(v.flags), float(v.vis_floor)
+
+    # ---- reflection probes: GGX-prefiltered radiance on the nodes' octahedral maps
+    def probe_radiance_dir(self, res, texels=None):
+        """(dir [n, 3], omega [n]) float32 of texel centres in an octahedral map of side res (pt_probe_radiance_dir; no GPU); texels None:
+        every texel in order"""
+        t = np.arange(int(res) * int(res), dtype=np.uint32) if texels is None else np.ascontiguousarray(texels, np.uint32).reshape(-1)
+        d = np.zeros((t.shape[0], 3), np.float32); om = np.zeros(t.shape[0], np.float32)
+        self._chk(self.L.pt_probe_radiance_dir(int(res), t.shape[0], _p(t), _p(d), _p(om)))
+        return d, om
+
+    def bake_probe_radiance(self, positions, n_samples, res, first_sample=0, key_base=0, sums=None, counts=None):
+        """radiance maps (pt_bake_probe_radiance): adds the radiance of bake_probes' rays of samples [first_sample, first_sample + n_samples),
+        the full path each, to the raw sums (n, res * res, 3) float32 and counts (n, res * res) uint32 per octahedral texel (None: zeros), in
+        sample order per texel.  Returns (sums, counts)."""
+        pos = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
+        n, rr = pos.shape[0], int(res) * int(res)
+        s = np.zeros((n, rr, 3), np.float32) if sums is None else np.ascontiguousarray(sums, np.float32).copy()
+        k = np.zeros((n, rr), np.uint32) if counts is None else np.ascontiguousarray(counts, np.uint32).copy()
+        if 2 <= int(res) <= 16 and (s.size != n * rr * 3 or k.size != n * rr):
+            raise PtError(-1, "bake_probe_radiance: sums hold res * res * 3 values and counts res * res per probe")
+        prm = ProbeRadianceParams(first_sample, n_samples, key_base, int(res))
+        self._chk(self.L.pt_bake_probe_radiance(self.ctx, n, _p(pos), C.byref(prm), _p(s), _p(k)))
+        return s, k
+
+    def probe_radiance_prefilter(self, sums, counts, alphas, on_device=True):
+        """the GGX prefilter of raw radiance maps (pt_probe_radiance_prefilter): sums (n, res * res, 3) and counts (n, res * res) to the table
+        (n, levels, res * res, 4) float32 that set_probe_grid_radiance takes, one level per alpha; on the host (no GPU) unless on_device"""
+        s = np.ascontiguousarray(sums, np.float32); k = np.ascontiguousarray(counts, np.uint32)
+        if s.ndim != 3 or s.shape[2] != 3 or k.shape != s.shape[:2]:
+            raise PtError(-1, "probe_radiance_prefilter: sums is (n, res * res, 3) and counts (n, res * res)")
+        n, rr = k.shape
+        res = int(round(np.sqrt(rr)))
+        al = [float(a) for a in alphas]
+        if res * res != rr or not 1 <= len(al) <= 8:
+            raise PtError(-1, "probe_radiance_prefilter: res * res texels per probe and 1..8 alphas")
+        f = ProbeRadianceFilter(res, n, len(al), (C.c_float * 8)(*al))
+        table = np.zeros((n, len(al), rr, 4), np.float32)
+        self._chk(self.L.pt_probe_radiance_prefilter(self.ctx, int(bool(on_device)), C.byref(f), _p(s), _p(k), _p(table)))
+        return table
+
+    def set_probe_grid_radiance(self, table, alphas=None):
+        """radiance on the grid in force (pt_set_probe_grid_radiance): table (nodes, levels, res * res, 4) float32 as probe_radiance_prefilter
+        returns it, alphas the levels' GGX alphas.  table None clears radiance."""
+        if table is None:
+            self._chk(self.L.pt_set_probe_grid_radiance(self.ctx, None, None))
+            return
+        if alphas is None:
+            raise PtError(-1, "set_probe_grid_radiance: a table needs its levels' alphas")
+        t = np.ascontiguousarray(table, np.float32)
+        al = [float(a) for a in alphas]
+        nodes = int(np.prod(self.probe_grid_info()[2]))
+        res = int(round(np.sqrt(t.shape[2]))) if t.ndim == 4 else 0
+        if t.ndim != 4 or t.shape[3] != 4 or t.shape[0] != nodes or t.shape[1] != len(al) or res * res != t.shape[2] or not 1 <= len(al) <= 8:
+            raise PtError(-1, "set_probe_grid_radiance: table is (nodes, levels, res * res, 4) with one alpha per level")
+        v = ProbeRadiance(res, len(al), (C.c_float * 8)(*al))
+        self._chk(self.L.pt_set_probe_grid_radiance(self.ctx, C.byref(v), _p(t)))
+
+    def set_probe_grid_radiance_sums(self, sums, counts, alphas, on_device=True):
+        """set_probe_grid_radiance of bake_probe_radiance's raw sums and counts: the prefilter, then the setter.  Returns the table."""
+        table = self.probe_radiance_prefilter(sums, counts, alphas, on_device)
+        self.set_probe_grid_radiance(table, alphas)
+        return table
+
+    def probe_grid_radiance_info(self):
+        """(res, alphas) of the grid's radiance; res 0: none"""
+        v = ProbeRadiance()
+        self._chk(self.L.pt_get_probe_grid_radiance_info(self.ctx, C.byref(v)))
+        return int(v.res), tuple(float(v.alpha[l]) for l in range(int(v.n_levels)))
+
+    def probe_grid_specular(self, position, normal, incoming, alpha, on_device=False):
+        """unit hook: (rgb [n, 3], lit [n] uint8) of the reflection probes' lookup at world positions, normals and incoming directions [n, 3]
+        and GGX alphas [n] (a scalar: the same for all); on the host (no GPU) unless on_device"""
+        p = np.ascontiguousarray(position, np.float32).reshape(-1, 3); nn = np.ascontiguousarray(normal, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(incoming, np.float32).reshape(-1, 3)
+        a = np.ascontiguousarray(np.broadcast_to(np.asarray(alpha, np.float32), (p.shape[0],)))
+        assert p.shape == nn.shape == d.shape
+        out = np.zeros((p.shape[0], 3), np.float32); lit = np.zeros(p.shape[0], np.uint8)
+        self._chk(self.L.pt_probe_grid_specular(self.ctx, int(bool(on_device)), p.shape[0], _p(p), _p(nn), _p(d), _p(a), _p(out), _p(lit)))
+        return out, lit
 
     # ---- unit hooks
     def trace_closest(self, o, d, tmax=None, which=0):

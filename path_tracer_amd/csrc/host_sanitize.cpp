@@ -35,6 +35,11 @@
 //                                      allocation exactly, random flags and floor, then probe_grid_lookup<true> at the same kinds of points, and
 //                                      probe_oct_texel alone over zero, huge, infinite and NaN directions; prints how many were lit, a checksum
 //                                      and the largest texel seen against the map's size
+//   host_sanitize proberadiance <n> <seed> reflection probes' host side: the same grids, each with raw radiance maps of side 2..16 with empty texels
+//                                      (every third probe empty altogether) run through probe_prefilter_texel at 1..8 levels into a table that
+//                                      fills its allocation exactly, then probe_grid_specular with and without a random depth table at the same
+//                                      kinds of points, with zero, huge, infinite and NaN directions and alphas; probe_oct_dir's round trip
+//                                      through probe_oct_texel; prints how many were lit, checksums, and whether every filtered value was finite
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -543,6 +548,103 @@ int main(int argc, char** argv)
             }
         }
         std::printf("{\"lookups\": %u, \"lit\": %u, \"checksum\": %.6f, \"texels_inside\": %u}\n", lookups, lit, acc, texels_ok);
+        return 0;
+    }
+    if (cmd == "proberadiance" && argc >= 4)
+    {
+        const uint32_t n = (uint32_t)std::atoi(argv[2]);
+        uint64_t s = 0x9E3779B97F4A7C15ull ^ (uint64_t)std::atoll(argv[3]);
+        auto rnd = [&]() { s ^= s << 13; s ^= s >> 7; s ^= s << 17; return (float)((s >> 40) & 0xffff) / 65535.0f; };
+        const uint32_t counts[6][3] = {{1, 1, 1}, {2, 2, 2}, {3, 2, 4}, {5, 1, 3}, {1, 7, 1}, {1, 1, 6}};
+        double acc = 0.0, filtered = 0.0;
+        uint32_t lookups = 0, lit = 0, round_trip = 1, finite = 1;
+        for (const uint32_t* cnt : counts)
+        {
+            const size_t nodes = (size_t)cnt[0] * cnt[1] * cnt[2];
+            std::vector<DProbe> rec(nodes);
+            for (DProbe& r : rec)
+            {
+                r.valid = rnd() < 0.8f ? 1.0f : 0.0f;
+                for (float& v : r.sh) v = r.valid != 0.0f ? 4.0f * rnd() - 1.0f : 0.0f;
+            }
+            const ProbeGridView g{rec.data(), {4.0f * rnd() - 2.0f, 4.0f * rnd() - 2.0f, 4.0f * rnd() - 2.0f},
+                                  {0.25f + rnd(), 0.25f + rnd(), 0.25f + rnd()}, {cnt[0], cnt[1], cnt[2]}, rnd() < 0.5f ? 0.0f : 0.125f};
+            const uint32_t res = 2u + (uint32_t)(rnd() * 14.99f), rr = res * res, levels = 1u + (uint32_t)(rnd() * 7.99f);
+            // the prefilter over raw maps with empty texels, one probe's worth of exactly rr entries at a time, into a table that is exactly
+            // nodes * levels * rr texels: a texel past a map, a level past the levels or a node past the grid is a heap overflow
+            ProbeRadianceView rv{nullptr, res, levels, {}};
+            for (uint32_t l = 0; l < levels; ++l) rv.alpha[l] = (float)(l + 1u) / (float)levels;
+            std::vector<f4> table(nodes * levels * rr), dirw(rr), mean(rr);
+            for (uint32_t j = 0; j < rr; ++j)
+            {
+                float d[3], om;
+                probe_oct_dir(j, res, d, &om);
+                dirw[j] = f4{d[0], d[1], d[2], om};
+                if (probe_oct_texel(d, res) != j) round_trip = 0;
+            }
+            for (size_t node = 0; node < nodes; ++node)
+            {
+                const float empty = node % 3u == 0u ? 1.0f : 0.3f; // (every third probe saw nothing at all)
+                for (uint32_t j = 0; j < rr; ++j)
+                {
+                    const uint32_t k = rnd() < empty ? 0u : 1u + (uint32_t)(rnd() * 30.0f);
+                    const float sums[3] = {5.0f * rnd() * (float)k, 5.0f * rnd() * (float)k, 5.0f * rnd() * (float)k};
+                    mean[j] = probe_radiance_mean(sums, k);
+                }
+                for (uint32_t l = 0; l < levels; ++l)
+                    for (uint32_t i = 0; i < rr; ++i)
+                    {
+                        const f4 o = probe_prefilter_texel(dirw.data(), mean.data(), rr, rv.alpha[l], i);
+                        table[(node * levels + l) * rr + i] = o;
+                        for (float v : {o.x, o.y, o.z})
+                        {
+                            if (!std::isfinite(v) || v < 0.0f) finite = 0;
+                            filtered += v;
+                        }
+                    }
+            }
+            rv.table = table.data();
+            const uint32_t dres = 2u + (uint32_t)(rnd() * 14.99f);
+            std::vector<DProbeDepth> moments(nodes * dres * dres);
+            for (DProbeDepth& m : moments)
+            {
+                m.m1 = 3.0f * rnd();
+                m.m2 = rnd() < 0.8f ? m.m1 * m.m1 + rnd() : m.m1 * m.m1 * rnd();
+            }
+            const ProbeDepthView dv{moments.data(), dres, rnd() < 0.5f ? 1u : 0u, rnd() < 0.5f ? 0.0f : 0.05f};
+            for (uint32_t i = 0; i < n; ++i)
+            {
+                // inside, a little outside, far outside, huge, infinite and NaN positions; unit, zero, huge, infinite and NaN normals and
+                // directions; alphas below, inside and above the levels, infinite and NaN
+                const uint32_t kind = i % 8u;
+                const float reach = kind == 0u ? 1.0f : kind == 1u ? 3.0f : kind == 2u ? 1e4f : kind == 3u ? 1e30f : 1.0f;
+                float p[3], nn[3], dd[3];
+                for (int a = 0; a < 3; ++a)
+                {
+                    p[a] = g.origin[a] + reach * (2.0f * rnd() - 0.5f) * g.cell[a] * (float)cnt[a];
+                    nn[a] = 2.0f * rnd() - 1.0f;
+                    dd[a] = 2.0f * rnd() - 1.0f;
+                }
+                if (kind == 4u) p[i % 3u] = NAN;
+                if (kind == 5u) p[i % 3u] = i & 8u ? INFINITY : -INFINITY;
+                if (kind == 6u) nn[i % 3u] = NAN;
+                if (kind == 7u) p[0] = p[1] = p[2] = 3.0e38f;
+                const float odd[6] = {0.0f, -0.0f, 3.0e38f, INFINITY, -INFINITY, NAN};
+                if ((i >> 3) % 4u == 1u) dd[i % 3u] = odd[(i >> 5) % 6u];
+                if ((i >> 3) % 4u == 2u) dd[0] = dd[1] = dd[2] = 0.0f;
+                const float alphas[6] = {-1.0f, 0.0f, 1.5f * rnd(), 2.0f, INFINITY, NAN};
+                const float a = alphas[(i >> 4) % 6u];
+                f3 c;
+                const bool has = i & 1u ? probe_grid_specular<true>(g, rv, f3{p[0], p[1], p[2]}, f3{nn[0], nn[1], nn[2]}, f3{dd[0], dd[1], dd[2]}, a, &c, &dv)
+                                        : probe_grid_specular(g, rv, f3{p[0], p[1], p[2]}, f3{nn[0], nn[1], nn[2]}, f3{dd[0], dd[1], dd[2]}, a, &c);
+                if (has) ++lit;
+                for (float v : {c.x, c.y, c.z})
+                    if (std::isfinite(v)) acc += v;
+                ++lookups;
+            }
+        }
+        std::printf("{\"lookups\": %u, \"lit\": %u, \"checksum\": %.6f, \"filtered\": %.6f, \"round_trip\": %u, \"finite\": %u}\n", lookups, lit, acc, filtered,
+                    round_trip, finite);
         return 0;
     }
     if (cmd == "plan")

@@ -223,6 +223,13 @@ struct pt_ctx
     uint64_t pd_version = 0;
     DevBuf d_probe_moments;
     bool pd_valid = false;
+    // reflection probes (pt_set_probe_grid_radiance): the nodes' prefiltered radiance maps as the device gets them (empty: none), which belong
+    // to the grid in force exactly as the depth moments do.  pr_version: the one on the device.
+    pt_probe_radiance probe_radiance{};
+    std::vector<f4> probe_radiance_table;
+    uint64_t pr_version = 0;
+    DevBuf d_probe_radiance;
+    bool pr_valid = false;
 
     // pt_frame_moving: the forward instance matrices, per model, of the build in force when the previous call returned PT_OK (the snapshot)
     // and the build it was taken from (a call on that very build has nothing to compare); the motion table and x_prev on the device.
@@ -1636,6 +1643,25 @@ int ensure_probe_depth(pt_ctx* c)
     HIPCHK(c, hipMemcpy(c->d_probe_moments.p, c->probe_moments.data(), c->probe_moments.size() * sizeof(DProbeDepth), hipMemcpyHostToDevice));
     c->pd_valid = true;
     c->pd_version = c->probe_version;
+    return PT_OK;
+}
+// ... and the prefiltered radiance maps (pt_set_probe_grid_radiance), by the same pattern; only called with radiance set
+ProbeRadianceView probe_radiance_view(const pt_ctx* c, const f4* table)
+{
+    ProbeRadianceView v{table, c->probe_radiance.res, c->probe_radiance.n_levels, {}};
+    for (int l = 0; l < 8; ++l) v.alpha[l] = c->probe_radiance.alpha[l];
+    return v;
+}
+int ensure_probe_radiance(pt_ctx* c)
+{
+    if (c->pr_valid && c->pr_version == c->probe_version) return PT_OK;
+    c->pr_valid = false;
+    int r;
+    HIPCHK(c, hipStreamSynchronize(c->stream)); // an earlier call may still be reading the table
+    if ((r = dev_alloc(c, c->d_probe_radiance, c->probe_radiance_table.size() * sizeof(f4)))) return r;
+    HIPCHK(c, hipMemcpy(c->d_probe_radiance.p, c->probe_radiance_table.data(), c->probe_radiance_table.size() * sizeof(f4), hipMemcpyHostToDevice));
+    c->pr_valid = true;
+    c->pr_version = c->probe_version;
     return PT_OK;
 }
 
@@ -3071,10 +3097,11 @@ int follow_chains(pt_ctx* c, uint32_t sample, uint32_t max_hops, f4* sum)
     });
 }
 // ... and the baked view's chains (pt_render_baked): the same walk, ended by launch_baked_follow into the baked sums, or by the probe ending
-// while a grid is set (pt_set_probe_grid), over the lookup with visibility while the grid has depth (pt_set_probe_grid_depth)
+// while a grid is set (pt_set_probe_grid), over the lookup with visibility while the grid has depth (pt_set_probe_grid_depth), and by the
+// ending whose GGX metal reflects the grid's prefiltered radiance while it has some (pt_set_probe_grid_radiance)
 int baked_chains(pt_ctx* c, uint32_t sample, const pt_baked_params& p)
 {
-    const bool grid = !c->probes.empty(), depth = grid && !c->probe_moments.empty();
+    const bool grid = !c->probes.empty(), depth = grid && !c->probe_moments.empty(), radiance = grid && !c->probe_radiance_table.empty();
     EnvView env{};
     if (c->env_w) env = EnvView{(const f4*)c->d_env.p, c->env_w, c->env_h, 0u, 0u};
     return walk_chains(c, sample, p.max_hops, [&](const ChainHop& q) {
@@ -3083,7 +3110,13 @@ int baked_chains(pt_ctx* c, uint32_t sample, const pt_baked_params& p)
         b.sum = (f4*)c->d_baked_sum.p;
         b.env = env;
         std::memcpy(b.unlit, p.unlit, sizeof(b.unlit));
-        if (depth)
+        if (radiance)
+        {
+            const ProbeDepthView dv = probe_depth_view(c, (const DProbeDepth*)c->d_probe_moments.p);
+            launch_baked_follow_probes_spec(c->stream, c->sv, c->tex, c->lm, b, probe_grid_view(c, (const DProbe*)c->d_probes.p), depth ? &dv : nullptr,
+                                            probe_radiance_view(c, (const f4*)c->d_probe_radiance.p));
+        }
+        else if (depth)
             launch_baked_follow_probes_vis(c->stream, c->sv, c->tex, c->lm, b, probe_grid_view(c, (const DProbe*)c->d_probes.p),
                                            probe_depth_view(c, (const DProbeDepth*)c->d_probe_moments.p));
         else if (grid) launch_baked_follow_probes(c->stream, c->sv, c->tex, c->lm, b, probe_grid_view(c, (const DProbe*)c->d_probes.p));
@@ -3800,6 +3833,7 @@ int pt_render_baked(pt_ctx* c, uint32_t first_sample, uint32_t n_samples, const 
     if ((r = upload_scene(c)) || (r = ensure_environment(c)) || (r = ensure_lightmaps(c))) return r;
     if (!c->probes.empty() && (r = ensure_probe_grid(c))) return r;
     if (!c->probe_moments.empty() && (r = ensure_probe_depth(c))) return r;
+    if (!c->probe_radiance_table.empty() && (r = ensure_probe_radiance(c))) return r;
     const uint32_t px = c->local_pixels;
     const size_t n = std::max<uint32_t>(px, 1);
     if ((r = guide_scratch(c, p->max_hops)) || (r = dev_alloc(c, c->d_baked_sum, n * 16))) return r;
@@ -3866,6 +3900,11 @@ static void drop_probe_depth(pt_ctx* c)
     std::vector<DProbeDepth>().swap(c->probe_moments);
     c->probe_depth = pt_probe_depth{};
 }
+static void drop_probe_radiance(pt_ctx* c)
+{
+    std::vector<f4>().swap(c->probe_radiance_table);
+    c->probe_radiance = pt_probe_radiance{};
+}
 int pt_set_probe_grid(pt_ctx* c, const pt_probe_grid* g, const float* sh27, const uint8_t* valid)
 {
     if (!c) return PT_ERR_ARG;
@@ -3878,6 +3917,7 @@ int pt_set_probe_grid(pt_ctx* c, const pt_probe_grid* g, const float* sh27, cons
         if (!c->probes.empty()) c->probe_version++;
         std::vector<DProbe>().swap(c->probes);
         drop_probe_depth(c);
+        drop_probe_radiance(c);
         c->probe_grid = pt_probe_grid{};
         c->probes_valid = 0;
         return PT_OK;
@@ -3908,6 +3948,7 @@ int pt_set_probe_grid(pt_ctx* c, const pt_probe_grid* g, const float* sh27, cons
     }
     c->probes.swap(rec);
     drop_probe_depth(c); // (the node count may have changed)
+    drop_probe_radiance(c);
     c->probe_grid = *g;
     c->probes_valid = n_valid;
     c->probe_version++;
@@ -4112,6 +4153,194 @@ int pt_get_probe_grid_depth_info(pt_ctx* c, pt_probe_depth* out)
     std::lock_guard<std::mutex> lk(c->mu);
     if (out) *out = c->probe_depth;
     return PT_OK;
+}
+
+// ---- reflection probes: the radiance maps' bake, their prefilter, the table on the grid and its lookup (the definitions are include/pt_api.h's)
+int pt_probe_radiance_dir(uint32_t res, uint32_t n, const uint32_t* texel, float* dir, float* omega)
+{
+    if (res < 2u || res > 16u) return PT_ERR_LIMIT;
+    if (n > 0 && (!texel || !dir || !omega)) return PT_ERR_ARG;
+    for (uint32_t i = 0; i < n; ++i)
+        if (texel[i] >= res * res) return PT_ERR_ARG;
+    for (uint32_t i = 0; i < n; ++i) probe_oct_dir(texel[i], res, dir + 3 * (size_t)i, omega + i);
+    return PT_OK;
+}
+
+int pt_bake_probe_radiance(pt_ctx* c, uint32_t n_probes, const float* position, const pt_probe_radiance_params* p, float* rgb_sums, uint32_t* counts)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    int r;
+    pt_probe_params range{};
+    if (p) range = pt_probe_params{p->first_sample, p->n_samples, p->key_base, 0u};
+    if ((r = probe_call_check(c, "pt_bake_probe_radiance", "rgb_sums and counts", n_probes, position, p ? &range : nullptr, !rgb_sums || !counts))) return r;
+    if (p)
+    {
+        if (p->res < 2u || p->res > 16u) return fail(c, PT_ERR_LIMIT, "pt_probe_radiance_params.res: the octahedral map's side is 2..16");
+        for (uint32_t w : p->reserved)
+            if (w) return fail(c, PT_ERR_ARG, "pt_probe_radiance_params.reserved must be 0");
+    }
+    if (n_probes == 0) return PT_OK;
+    if ((r = upload_scene(c))) return r;
+    const size_t texels = (size_t)n_probes * p->res * p->res;
+    Staging st(c);
+    const float* d_position = (const float*)st.in(position, (size_t)n_probes * 12);
+    float* d_sums = (float*)st.in(rgb_sums, texels * 12);
+    uint32_t* d_counts = (uint32_t*)st.in(counts, texels * 4);
+    const ProbeBake pb{d_position, n_probes, p->first_sample, p->n_samples, p->key_base, c->cfg.n_sobol, c->cfg.seed};
+    const uint32_t res = p->res;
+    if ((r = bake_rays(c, st, n_probes, p->n_samples,
+                       [&](uint64_t first, uint32_t cnt, float* o, float* d, uint2* key) { launch_probe_rays(c->stream, pb, first, cnt, o, d, key); },
+                       [&](uint64_t first, uint32_t cnt, const float* d, const f4* rad) { launch_probe_radiance_fold(c->stream, pb, first, cnt, d, rad, res, d_sums, d_counts); })))
+        return r;
+    if ((r = st.download(rgb_sums, d_sums, texels * 12))) return r;
+    return st.download(counts, d_counts, texels * 4);
+}
+
+// what the prefilter and the setter refuse of their levels
+static int probe_levels_check(pt_ctx* c, const char* who, uint32_t res, uint32_t n_levels, const float alpha[8])
+{
+    if (res < 2u || res > 16u) return fail(c, PT_ERR_LIMIT, std::string(who) + ".res: the octahedral map's side is 2..16");
+    if (n_levels < 1u || n_levels > 8u) return fail(c, PT_ERR_LIMIT, std::string(who) + ".n_levels is 1..8");
+    for (uint32_t l = 0; l < n_levels; ++l)
+        if (!std::isfinite(alpha[l]) || !(alpha[l] > 0.0f) || !(alpha[l] <= 1.0f) || (l && !(alpha[l] > alpha[l - 1])))
+            return fail(c, PT_ERR_ARG, std::string(who) + ".alpha must be finite, in (0, 1] and strictly ascending");
+    return PT_OK;
+}
+
+int pt_probe_radiance_prefilter(pt_ctx* c, int on_device, const pt_probe_radiance_filter* f, const float* rgb_sums, const uint32_t* counts, float* table)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!f) return fail(c, PT_ERR_ARG, "pt_probe_radiance_prefilter: f must not be NULL");
+    for (uint32_t w : f->reserved)
+        if (w) return fail(c, PT_ERR_ARG, "pt_probe_radiance_filter.reserved must be 0");
+    int r;
+    if ((r = probe_levels_check(c, "pt_probe_radiance_filter", f->res, f->n_levels, f->alpha))) return r;
+    if (f->n_probes > 0 && (!rgb_sums || !counts || !table)) return fail(c, PT_ERR_ARG, "pt_probe_radiance_prefilter: rgb_sums, counts and table must not be NULL");
+    const uint32_t rr = f->res * f->res;
+    const uint64_t out_texels = (uint64_t)f->n_probes * f->n_levels * rr;
+    if (out_texels * 16 > (1ull << 31)) return fail(c, PT_ERR_LIMIT, "pt_probe_radiance_prefilter: the table is above 2^31 bytes");
+    if (f->n_probes == 0) return PT_OK;
+    if (!on_device)
+    {
+        f4 dirw[256], mean[256];
+        for (uint32_t j = 0; j < rr; ++j)
+        {
+            float d[3], om;
+            probe_oct_dir(j, f->res, d, &om);
+            dirw[j] = f4{d[0], d[1], d[2], om};
+        }
+        for (uint32_t q = 0; q < f->n_probes; ++q)
+        {
+            for (uint32_t j = 0; j < rr; ++j) mean[j] = probe_radiance_mean(rgb_sums + 3 * ((size_t)q * rr + j), counts[(size_t)q * rr + j]);
+            for (uint32_t l = 0; l < f->n_levels; ++l)
+                for (uint32_t i = 0; i < rr; ++i)
+                {
+                    const f4 o = probe_prefilter_texel(dirw, mean, rr, f->alpha[l], i);
+                    float* po = table + 4 * (((size_t)q * f->n_levels + l) * rr + i);
+                    po[0] = o.x; po[1] = o.y; po[2] = o.z; po[3] = o.w;
+                }
+        }
+        return PT_OK;
+    }
+    if ((r = ensure_device(c))) return r;
+    Staging st(c);
+    const float* d_sums = (const float*)st.in(rgb_sums, (size_t)f->n_probes * rr * 12);
+    const uint32_t* d_counts = (const uint32_t*)st.in(counts, (size_t)f->n_probes * rr * 4);
+    f4* d_table = (f4*)st.out((size_t)out_texels * 16);
+    if (st.err) return st.err;
+    launch_probe_radiance_prefilter(c->stream, f->res, f->n_probes, f->n_levels, f->alpha, d_sums, d_counts, d_table);
+    HIPCHK(c, hipGetLastError());
+    return st.download(table, d_table, (size_t)out_texels * 16);
+}
+
+int pt_set_probe_grid_radiance(pt_ctx* c, const pt_probe_radiance* v, const float* table)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!v && table) return fail(c, PT_ERR_ARG, "pt_set_probe_grid_radiance: r NULL clears radiance and takes no table");
+    if (v)
+        for (uint32_t w : v->reserved)
+            if (w) return fail(c, PT_ERR_ARG, "pt_probe_radiance.reserved must be 0");
+    if (c->probes.empty()) return fail(c, PT_ERR_STATE, "no probe grid: pt_set_probe_grid first");
+    if (!v)
+    {
+        if (!c->probe_radiance_table.empty()) c->probe_version++;
+        drop_probe_radiance(c);
+        return PT_OK;
+    }
+    if (!table) return fail(c, PT_ERR_ARG, "pt_set_probe_grid_radiance: table must not be NULL");
+    int r;
+    if ((r = probe_levels_check(c, "pt_probe_radiance", v->res, v->n_levels, v->alpha))) return r;
+    const size_t per_node = (size_t)v->n_levels * v->res * v->res;
+    const uint64_t n = (uint64_t)c->probes.size() * per_node;
+    if (n * 16 > (1ull << 31)) return fail(c, PT_ERR_LIMIT, "pt_set_probe_grid_radiance: the table is above 2^31 bytes");
+    for (uint64_t i = 0; i < n * 4; ++i)
+        if (!std::isfinite(table[i]) || table[i] < 0.0f)
+            return fail(c, PT_ERR_ARG, "pt_set_probe_grid_radiance: node " + std::to_string(i / (4 * per_node)) + " has a value that is not finite and >= 0");
+    std::vector<f4> rec;
+    try { rec.assign((size_t)n, f4{0.0f, 0.0f, 0.0f, 0.0f}); }
+    catch (const std::exception& e) { return fail(c, PT_ERR_LIMIT, std::string("probe radiance does not fit in host memory: ") + e.what()); }
+    for (size_t node = 0; node < c->probes.size(); ++node)
+        if (c->probes[node].valid != 0.0f) std::memcpy(&rec[node * per_node], table + 4 * node * per_node, per_node * sizeof(f4));
+    c->probe_radiance_table.swap(rec);
+    c->probe_radiance = *v;
+    for (uint32_t l = v->n_levels; l < 8u; ++l) c->probe_radiance.alpha[l] = 0.0f; // (not read: reported as zeros)
+    c->probe_version++;
+    return PT_OK;
+}
+
+int pt_get_probe_grid_radiance_info(pt_ctx* c, pt_probe_radiance* out)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (out) *out = c->probe_radiance;
+    return PT_OK;
+}
+
+int pt_probe_grid_specular(pt_ctx* c, int on_device, uint32_t n, const float* position, const float* normal, const float* incoming, const float* alpha,
+                           float* rgb, uint8_t* lit)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (c->probes.empty()) return fail(c, PT_ERR_STATE, "no probe grid: pt_set_probe_grid first");
+    if (c->probe_radiance_table.empty()) return fail(c, PT_ERR_STATE, "no probe radiance: pt_set_probe_grid_radiance first");
+    if (n == 0) return PT_OK;
+    if (!position || !normal || !incoming || !alpha || !rgb || !lit) return fail(c, PT_ERR_ARG, "pt_probe_grid_specular: null pointer");
+    const bool vis = !c->probe_moments.empty();
+    if (!on_device)
+    {
+        const ProbeGridView g = probe_grid_view(c, c->probes.data());
+        const ProbeRadianceView rv = probe_radiance_view(c, c->probe_radiance_table.data());
+        const ProbeDepthView dv = probe_depth_view(c, c->probe_moments.data());
+        for (uint32_t i = 0; i < n; ++i)
+        {
+            const float *pp = position + 3 * (size_t)i, *pn = normal + 3 * (size_t)i, *pi = incoming + 3 * (size_t)i;
+            const f3 P{pp[0], pp[1], pp[2]}, N{pn[0], pn[1], pn[2]}, D{pi[0], pi[1], pi[2]};
+            f3 col;
+            lit[i] = (vis ? probe_grid_specular<true>(g, rv, P, N, D, alpha[i], &col, &dv) : probe_grid_specular(g, rv, P, N, D, alpha[i], &col)) ? 1u : 0u;
+            rgb[3 * (size_t)i] = col.x; rgb[3 * (size_t)i + 1] = col.y; rgb[3 * (size_t)i + 2] = col.z;
+        }
+        return PT_OK;
+    }
+    int r;
+    if ((r = ensure_device(c)) || (r = ensure_probe_grid(c)) || (r = ensure_probe_radiance(c))) return r;
+    if (vis && (r = ensure_probe_depth(c))) return r;
+    Staging st(c);
+    const float* d_pos = (const float*)st.in(position, (size_t)n * 12);
+    const float* d_nrm = (const float*)st.in(normal, (size_t)n * 12);
+    const float* d_inc = (const float*)st.in(incoming, (size_t)n * 12);
+    const float* d_alpha = (const float*)st.in(alpha, (size_t)n * 4);
+    float* d_rgb = (float*)st.out((size_t)n * 12);
+    uint8_t* d_lit = (uint8_t*)st.out(n);
+    if (st.err) return st.err;
+    const ProbeDepthView dv = probe_depth_view(c, (const DProbeDepth*)c->d_probe_moments.p);
+    launch_probe_grid_specular(c->stream, probe_grid_view(c, (const DProbe*)c->d_probes.p), probe_radiance_view(c, (const f4*)c->d_probe_radiance.p), vis ? &dv : nullptr,
+                               n, d_pos, d_nrm, d_inc, d_alpha, d_rgb, d_lit);
+    HIPCHK(c, hipGetLastError());
+    if ((r = st.download(rgb, d_rgb, (size_t)n * 12))) return r;
+    return st.download(lit, d_lit, n);
 }
 
 // ---- unit hooks

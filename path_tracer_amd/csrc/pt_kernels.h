@@ -339,6 +339,19 @@ void launch_baked_follow_probes_vis(hipStream_t s, const SceneView& sv, const Te
                                     const ProbeDepthView& depth);
 void launch_probe_grid_lookup_vis(hipStream_t s, const ProbeGridView& grid, const ProbeDepthView& depth, uint32_t n, const float* position, const float* normal,
                                   float* rgb, uint8_t* lit);
+// reflection probes.  pt_bake_probe_radiance: the same window's integrated radiance folded into the probes' R x R octahedral radiance maps
+// (sums: r, g, b per texel, counts: the rays per texel; both continue from what they hold), in sample order per texel: one wave per probe,
+// no atomics.  pt_probe_radiance_prefilter: table[probe][level][texel] = the GGX prefilter of the means, one workgroup per (probe, level).
+// pt_probe_grid_specular's unit hook: probe_grid_specular (pt_probe.h) of n queries, with visibility where depth is not null
+// with radiance set on the grid (pt_set_probe_grid_radiance): the probe ending whose GGX metal reflects the prefiltered radiance (depth: null without)
+void launch_baked_follow_probes_spec(hipStream_t s, const SceneView& sv, const TexView& tex, const LmView& lm, const BakedArgs& a, const ProbeGridView& grid,
+                                     const ProbeDepthView* depth, const ProbeRadianceView& rad);
+void launch_probe_radiance_fold(hipStream_t s, const ProbeBake& pb, uint64_t first, uint32_t count, const float* d, const f4* radiance, uint32_t res,
+                                float* sums, uint32_t* counts);
+void launch_probe_radiance_prefilter(hipStream_t s, uint32_t res, uint32_t n_probes, uint32_t n_levels, const float* alpha, const float* sums,
+                                     const uint32_t* counts, f4* table);
+void launch_probe_grid_specular(hipStream_t s, const ProbeGridView& grid, const ProbeRadianceView& rad, const ProbeDepthView* depth, uint32_t n,
+                                const float* position, const float* normal, const float* incoming, const float* alpha, float* rgb, uint8_t* lit);
 // unit hook (pt_lightmap_lookup): lightmap_at (pt_materials.h) of world instance[i], leaf-order triangle tri[i] at barycentrics u[i], v[i]
 void launch_lightmap_lookup(hipStream_t s, const LmView& lm, uint32_t n, const uint32_t* instance, const uint32_t* tri, const float* u, const float* v,
                             float* rgb, uint8_t* mapped);

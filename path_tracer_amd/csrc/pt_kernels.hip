@@ -2787,6 +2787,113 @@ __global__ void __launch_bounds__(256) k_probe_depth_fold(const ProbeBake pb, co
     if (lane + 128u < rr) { sums[base + lane + 128u] = DProbeDepth{a2, b2}; counts[base + lane + 128u] = n2; }
     if (lane + 192u < rr) { sums[base + lane + 192u] = DProbeDepth{a3, b3}; counts[base + lane + 192u] = n3; }
 }
+// pt_bake_probe_radiance: the integrated radiance of the same window's rays folded into the probes' octahedral radiance maps:
+// counts[probe][texel] += 1, sums[probe][texel][c] += L[c].  k_probe_depth_fold's ownership and walk: one wave per probe the window touches,
+// a texel's adds in sample order, lane texel & 63 adding into its accumulator set texel >> 6 (four sets of three channels and a count,
+// chosen by a uniform branch), loaded from and stored to the arrays once per launch.
+struct RadAcc
+{
+    float r, g, b;
+    uint32_t n;
+};
+__device__ __forceinline__ void radiance_add(RadAcc& a, float lr, float lg, float lb)
+{
+    a.r = a.r + lr;
+    a.g = a.g + lg;
+    a.b = a.b + lb;
+    a.n += 1u;
+}
+__device__ __forceinline__ RadAcc radiance_load(const float* __restrict__ sums, const uint32_t* __restrict__ counts, size_t texel)
+{
+    return RadAcc{sums[3u * texel], sums[3u * texel + 1u], sums[3u * texel + 2u], counts[texel]};
+}
+__device__ __forceinline__ void radiance_store(float* __restrict__ sums, uint32_t* __restrict__ counts, size_t texel, const RadAcc& a)
+{
+    sums[3u * texel] = a.r; sums[3u * texel + 1u] = a.g; sums[3u * texel + 2u] = a.b;
+    counts[texel] = a.n;
+}
+__global__ void __launch_bounds__(256) k_probe_radiance_fold(const ProbeBake pb, const uint64_t first, const uint32_t count, const float* __restrict__ d,
+                                                             const f4* __restrict__ radiance, const uint32_t res, float* __restrict__ sums,
+                                                             uint32_t* __restrict__ counts)
+{
+    const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const uint32_t p0 = (uint32_t)(first / pb.n_samples), p1 = (uint32_t)((first + count - 1u) / pb.n_samples);
+    if (wave > p1 - p0) return; // (wave-uniform)
+    const uint32_t j = p0 + wave;
+    const uint64_t lo = (uint64_t)j * pb.n_samples, hi = lo + pb.n_samples;
+    const uint32_t i0 = (uint32_t)((lo > first ? lo : first) - first), i1 = (uint32_t)((hi < first + count ? hi : first + count) - first);
+    const uint32_t rr = res * res, lane = lane_id();
+    const size_t base = (size_t)j * rr;
+    RadAcc a0{0.0f, 0.0f, 0.0f, 0u}, a1 = a0, a2 = a0, a3 = a0;
+    if (lane < rr) a0 = radiance_load(sums, counts, base + lane);
+    if (lane + 64u < rr) a1 = radiance_load(sums, counts, base + lane + 64u);
+    if (lane + 128u < rr) a2 = radiance_load(sums, counts, base + lane + 128u);
+    if (lane + 192u < rr) a3 = radiance_load(sums, counts, base + lane + 192u);
+    for (uint32_t at = i0; at < i1; at += 64u)
+    {
+        const uint32_t i = at + lane;
+        uint32_t texel = 0u;
+        f4 l4{0.0f, 0.0f, 0.0f, 0.0f};
+        if (i < i1)
+        {
+            l4 = radiance[i];
+            const float* pd = d + 3u * (size_t)i;
+            const float dir[3] = {pd[0], pd[1], pd[2]};
+            texel = probe_oct_texel(dir, res); // < res * res <= 256
+        }
+        const uint32_t m = i1 - at < 64u ? i1 - at : 64u; // (wave-uniform)
+        for (uint32_t e = 0; e < m; ++e)
+        {
+            const uint32_t te = (uint32_t)__builtin_amdgcn_readlane((int)texel, (int)e);
+            const float lr = asf((uint32_t)__builtin_amdgcn_readlane((int)asu(l4.x), (int)e));
+            const float lg = asf((uint32_t)__builtin_amdgcn_readlane((int)asu(l4.y), (int)e));
+            const float lb = asf((uint32_t)__builtin_amdgcn_readlane((int)asu(l4.z), (int)e));
+            const uint32_t q = te >> 6; // (wave-uniform)
+            if ((te & 63u) == lane)
+            {
+                if (q == 0u) radiance_add(a0, lr, lg, lb);
+                else if (q == 1u) radiance_add(a1, lr, lg, lb);
+                else if (q == 2u) radiance_add(a2, lr, lg, lb);
+                else radiance_add(a3, lr, lg, lb);
+            }
+        }
+    }
+    if (lane < rr) radiance_store(sums, counts, base + lane, a0);
+    if (lane + 64u < rr) radiance_store(sums, counts, base + lane + 64u, a1);
+    if (lane + 128u < rr) radiance_store(sums, counts, base + lane + 128u, a2);
+    if (lane + 192u < rr) radiance_store(sums, counts, base + lane + 192u, a3);
+}
+// pt_probe_radiance_prefilter: one workgroup per (probe, level) of R * R lanes rounded up to whole waves, one lane per output texel.  The
+// probe's means and the map's direction / solid-angle table are staged in LDS once (32 bytes a texel, sized at the launch: 8 KiB at R = 16,
+// 2 KiB at R = 8, so that LDS never holds the single-wave workgroups of small maps below eight waves per SIMD); the quadrature of a lane then
+// walks the input texels serially, in the order that defines the sum, and every lane reads the same LDS address at a time: a broadcast.  No
+// atomics.
+struct PrefilterArgs
+{
+    uint32_t res, n_levels;
+    float alpha[8];
+};
+__global__ void __launch_bounds__(256) k_probe_radiance_prefilter(const PrefilterArgs a, const float* __restrict__ sums, const uint32_t* __restrict__ counts,
+                                                                  f4* __restrict__ table)
+{
+    extern __shared__ __attribute__((aligned(16))) f4 s_prefilter[]; // rr entries of {dir, omega}, then rr of {mean, filled}
+    const uint32_t rr = a.res * a.res;
+    f4* const s_dirw = s_prefilter;
+    f4* const s_mean = s_prefilter + rr;
+    const uint32_t probe = blockIdx.x / a.n_levels, level = blockIdx.x - probe * a.n_levels, t = threadIdx.x;
+    if (t < rr) // (blockDim.x >= rr)
+    {
+        float dir[3], omega;
+        probe_oct_dir(t, a.res, dir, &omega);
+        s_dirw[t] = f4{dir[0], dir[1], dir[2], omega};
+        const size_t at = (size_t)probe * rr + t;
+        const float s3[3] = {sums[3u * at], sums[3u * at + 1u], sums[3u * at + 2u]};
+        s_mean[t] = probe_radiance_mean(s3, counts[at]);
+    }
+    __syncthreads();
+    if (t >= rr) return;
+    table[(size_t)blockIdx.x * rr + t] = probe_prefilter_texel(s_dirw, s_mean, rr, a.alpha[level], t);
+}
 
 // ------------------------------------------------------------------------------------------------ adaptive selection (PT_FLAG_ADAPTIVE)
 // The criterion of pt_api.h's pt_adaptive, in f32 with every operation correctly rounded and in this order (the tests restate it in
@@ -3196,6 +3303,43 @@ __global__ void __launch_bounds__(256, 4) k_baked_follow_probes_vis(const SceneV
 {
     chain_hop<FIRST>(sv, tex, a, BakedEnding<true, true>{lm, a, &grid, &depth});
 }
+// ... and with radiance set on the grid (pt_set_probe_grid_radiance): a chain that ends on GGX metal, on either face, reflects the grid's
+// prefiltered radiance, B = R * S, where probe_grid_specular is lit, whether or not a map lights the surface (a map holds irradiance, which a
+// metal does not reflect diffusely); where it is not lit, and on every other kind, the ending is the probe ending's.  The metal branch comes
+// first and returns, so a lane holds one lookup's registers at a time.  P, n and d are ChainEnd's; the alpha is the material's own.
+template <bool VIS>
+struct BakedSpecEnding
+{
+    BakedEnding<true, VIS> base;
+    const SceneView& sv;
+    const ProbeRadianceView& rad;
+    static constexpr bool kSumT = false;
+    __device__ __forceinline__ f3 miss(bool first, uint32_t i, uint32_t px, const f3& d) const { return base.miss(first, i, px, d); }
+    __device__ __forceinline__ f3 surface(const ChainEnd& h) const
+    {
+        if (h.kind == MAT_GGX_METAL)
+        {
+            const float alpha = sv.materials[sv.instances[h.inst].material].alpha;
+            __asm__ volatile("" ::: "memory");
+            f3 s;
+            if (probe_grid_specular<VIS>(*base.grid, rad, fma3(h.d, bc3(h.hit.x), xyz(base.a.in.a[h.slot])), h.nrm, h.d, alpha, &s, base.depth)) return h.c * s;
+        }
+        return base.surface(h);
+    }
+    __device__ __forceinline__ void store(uint32_t px, const f3& b) const { base.store(px, b); }
+};
+template <bool FIRST>
+__global__ void __launch_bounds__(256, 4) k_baked_follow_probes_spec(const SceneView sv, const TexView tex, const LmView lm, const BakedArgs a, const ProbeGridView grid,
+                                                                     const ProbeRadianceView rad)
+{
+    chain_hop<FIRST>(sv, tex, a, BakedSpecEnding<false>{BakedEnding<true>{lm, a, &grid}, sv, rad});
+}
+template <bool FIRST>
+__global__ void __launch_bounds__(256, 4) k_baked_follow_probes_spec_vis(const SceneView sv, const TexView tex, const LmView lm, const BakedArgs a,
+                                                                         const ProbeGridView grid, const ProbeDepthView depth, const ProbeRadianceView rad)
+{
+    chain_hop<FIRST>(sv, tex, a, BakedSpecEnding<true>{BakedEnding<true, true>{lm, a, &grid, &depth}, sv, rad});
+}
 // unit hook of the probe grid's lookup: rgb, lit = probe_grid_lookup
 __global__ void __launch_bounds__(256, 4) k_probe_grid_lookup(const ProbeGridView grid, const uint32_t n, const float* __restrict__ position,
                                                               const float* __restrict__ normal, float* __restrict__ rgb, uint8_t* __restrict__ lit)
@@ -3218,6 +3362,23 @@ __global__ void __launch_bounds__(256, 4) k_probe_grid_lookup_vis(const ProbeGri
     const float* pn = normal + 3u * (size_t)i;
     f3 c;
     const bool has = probe_grid_lookup<true>(grid, f3{pp[0], pp[1], pp[2]}, f3{pn[0], pn[1], pn[2]}, &c, &depth);
+    rgb[3u * (size_t)i] = c.x; rgb[3u * (size_t)i + 1u] = c.y; rgb[3u * (size_t)i + 2u] = c.z;
+    lit[i] = has ? 1u : 0u;
+}
+// unit hook of the reflection probes' lookup (pt_probe_grid_specular): rgb, lit = probe_grid_specular<VIS>, VIS with depth set on the grid
+template <bool VIS>
+__global__ void __launch_bounds__(256, 4) k_probe_grid_specular(const ProbeGridView grid, const ProbeRadianceView rad, const ProbeDepthView depth, const uint32_t n,
+                                                                const float* __restrict__ position, const float* __restrict__ normal,
+                                                                const float* __restrict__ incoming, const float* __restrict__ alpha, float* __restrict__ rgb,
+                                                                uint8_t* __restrict__ lit)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float* pp = position + 3u * (size_t)i;
+    const float* pn = normal + 3u * (size_t)i;
+    const float* pi = incoming + 3u * (size_t)i;
+    f3 c;
+    const bool has = probe_grid_specular<VIS>(grid, rad, f3{pp[0], pp[1], pp[2]}, f3{pn[0], pn[1], pn[2]}, f3{pi[0], pi[1], pi[2]}, alpha[i], &c, &depth);
     rgb[3u * (size_t)i] = c.x; rgb[3u * (size_t)i + 1u] = c.y; rgb[3u * (size_t)i + 2u] = c.z;
     lit[i] = has ? 1u : 0u;
 }
@@ -3822,11 +3983,41 @@ void launch_baked_follow_probes_vis(hipStream_t s, const SceneView& sv, const Te
 {
     launch_chain_hop(s, a, k_baked_follow_probes_vis<true>, k_baked_follow_probes_vis<false>, sv, tex, lm, a, grid, depth);
 }
+void launch_baked_follow_probes_spec(hipStream_t s, const SceneView& sv, const TexView& tex, const LmView& lm, const BakedArgs& a, const ProbeGridView& grid,
+                                     const ProbeDepthView* depth, const ProbeRadianceView& rad)
+{
+    if (depth) launch_chain_hop(s, a, k_baked_follow_probes_spec_vis<true>, k_baked_follow_probes_spec_vis<false>, sv, tex, lm, a, grid, *depth, rad);
+    else launch_chain_hop(s, a, k_baked_follow_probes_spec<true>, k_baked_follow_probes_spec<false>, sv, tex, lm, a, grid, rad);
+}
 void launch_probe_grid_lookup_vis(hipStream_t s, const ProbeGridView& grid, const ProbeDepthView& depth, uint32_t n, const float* position, const float* normal,
                                   float* rgb, uint8_t* lit)
 {
     if (n == 0u) return;
     hipLaunchKernelGGL(k_probe_grid_lookup_vis, dim3((n + 255u) / 256u), dim3(256), 0, s, grid, depth, n, position, normal, rgb, lit);
+}
+void launch_probe_radiance_fold(hipStream_t s, const ProbeBake& pb, uint64_t first, uint32_t count, const float* d, const f4* radiance, uint32_t res,
+                                float* sums, uint32_t* counts)
+{
+    if (count == 0u) return;
+    const uint64_t probes = (first + count - 1u) / pb.n_samples - first / pb.n_samples + 1u;
+    hipLaunchKernelGGL(k_probe_radiance_fold, dim3((uint32_t)((probes * 64u + 255u) / 256u)), dim3(256), 0, s, pb, first, count, d, radiance, res, sums, counts);
+}
+void launch_probe_radiance_prefilter(hipStream_t s, uint32_t res, uint32_t n_probes, uint32_t n_levels, const float* alpha, const float* sums,
+                                     const uint32_t* counts, f4* table)
+{
+    if (n_probes == 0u) return;
+    PrefilterArgs a{res, n_levels, {}};
+    for (uint32_t l = 0; l < n_levels && l < 8u; ++l) a.alpha[l] = alpha[l];
+    hipLaunchKernelGGL(k_probe_radiance_prefilter, dim3(n_probes * n_levels), dim3((res * res + 63u) / 64u * 64u), res * res * 2u * sizeof(f4), s, a, sums, counts, table);
+}
+void launch_probe_grid_specular(hipStream_t s, const ProbeGridView& grid, const ProbeRadianceView& rad, const ProbeDepthView* depth, uint32_t n,
+                                const float* position, const float* normal, const float* incoming, const float* alpha, float* rgb, uint8_t* lit)
+{
+    if (n == 0u) return;
+    if (depth) hipLaunchKernelGGL(k_probe_grid_specular<true>, dim3((n + 255u) / 256u), dim3(256), 0, s, grid, rad, *depth, n, position, normal, incoming, alpha, rgb, lit);
+    else
+        hipLaunchKernelGGL(k_probe_grid_specular<false>, dim3((n + 255u) / 256u), dim3(256), 0, s, grid, rad, ProbeDepthView{}, n, position, normal, incoming, alpha,
+                           rgb, lit);
 }
 void launch_lightmap_lookup(hipStream_t s, const LmView& lm, uint32_t n, const uint32_t* instance, const uint32_t* tri, const float* u, const float* v,
                             float* rgb, uint8_t* mapped)

@@ -3,6 +3,7 @@
 // operation; every operation is rounded once, in this order (the library is built without contraction).
 #pragma once
 #include "pt_types.h"
+#include "pt_materials.h"
 
 namespace pt {
 
@@ -166,6 +167,136 @@ PT_HD bool probe_grid_lookup(const ProbeGridView& g, f3 p, f3 n, f3* out, const 
         I[c] = lit && v > 0.0f ? v : 0.0f;
     }
     *out = f3{I[0], I[1], I[2]};
+    return lit;
+}
+
+// ---- reflection probes (pt_set_probe_grid_radiance; include/pt_api.h states all of it operation for operation)
+// The unit direction of the centre of texel `texel` of an R x R octahedral map, the inverse of probe_oct_texel there, and the texel's relative
+// solid angle omega = 1 / |v|^3, v the centre's point on the unit octahedron (the map's area element is dA / |v|^3; the fold is an isometry).
+PT_HD void probe_oct_dir(uint32_t texel, uint32_t R, float dir[3], float* omega)
+{
+    const uint32_t iy = texel / R, ix = texel - iy * R;
+    const float fr = (float)R;
+    float px = 2.0f * (((float)ix + 0.5f) / fr) - 1.0f, py = 2.0f * (((float)iy + 0.5f) / fr) - 1.0f;
+    const float z = (1.0f - fabsf(px)) - fabsf(py);
+    if (z < 0.0f)
+    {
+        const float qx = (1.0f - fabsf(py)) * (px >= 0.0f ? 1.0f : -1.0f), qy = (1.0f - fabsf(px)) * (py >= 0.0f ? 1.0f : -1.0f);
+        px = qx;
+        py = qy;
+    }
+    const float len = sqrtf((px * px + py * py) + z * z);
+    dir[0] = px / len;
+    dir[1] = py / len;
+    dir[2] = z / len;
+    *omega = 1.0f / ((len * len) * len);
+}
+// what the prefilter reads of input texel j: {mean r, g, b, filled}: sums / (float)count, one division per channel; an empty texel is zeros
+PT_HD f4 probe_radiance_mean(const float sums[3], uint32_t count)
+{
+    if (count == 0u) return f4{0.0f, 0.0f, 0.0f, 0.0f};
+    const float n = (float)count;
+    return f4{sums[0] / n, sums[1] / n, sums[2] / n, 1.0f};
+}
+// Output texel i of one probe's map prefiltered by the GGX lobe of `alpha` around the texel's own direction (V = N = R): a quadrature over the
+// rr input texels in ascending order.  dirw[j] = {probe_oct_dir(j), omega_j}, mean[j] = probe_radiance_mean of texel j.  One function for the
+// host evaluation and k_probe_radiance_prefilter, whose lanes read dirw and mean from LDS, every lane the same j at a time.
+PT_HD f4 probe_prefilter_texel(const f4* dirw, const f4* mean, uint32_t rr, float alpha, uint32_t i)
+{
+    const f4 ni = dirw[i];
+    const f3 n{ni.x, ni.y, ni.z};
+    float A[3] = {0.0f, 0.0f, 0.0f}, Wt = 0.0f;
+    for (uint32_t j = 0; j < rr; ++j)
+    {
+        const f4 m = mean[j];
+        if (m.w == 0.0f) continue;
+        const f4 lj = dirw[j];
+        const f3 l{lj.x, lj.y, lj.z};
+        const float nl = dot3(n, l);
+        if (!(nl > 0.0f)) continue;
+        const f3 h = unit3(n + l);
+        float nh = dot3(n, h);
+        nh = nh > 1.0f ? 1.0f : nh; // (rounding takes the cosine of j = i past 1, where ggx_d's sqrtf(1 - c2) is a NaN)
+        const float w = (ggx_d(alpha, f3{h.x, h.y, nh}) * nl) * lj.w;
+        A[0] = A[0] + w * m.x;
+        A[1] = A[1] + w * m.y;
+        A[2] = A[2] + w * m.z;
+        Wt = Wt + w;
+    }
+    if (!(Wt > 0.0f)) return f4{0.0f, 0.0f, 0.0f, 0.0f};
+    return f4{A[0] / Wt, A[1] / Wt, A[2] / Wt, 0.0f};
+}
+
+// The specular lookup (pt_probe_grid_specular): the prefiltered radiance the grid's reflection probes hold in the direction of the mirror
+// reflection of `incoming` about n, at roughness a.  The texel is the nearest one, computed once; the level pair and its blend t come from a;
+// the corner weights are probe_grid_lookup<VIS>'s, restated here so that the existing instantiations stay what they are.  Returns lit; *out is
+// S / W where lit and 0 where not.  No index leaves the tables whatever p, n, incoming and a are.
+template <bool VIS = false>
+PT_HD bool probe_grid_specular(const ProbeGridView& g, const ProbeRadianceView& rv, f3 p, f3 n, f3 incoming, float a, f3* out, const ProbeDepthView* dv = nullptr)
+{
+    const float pp[3] = {p.x + g.bias * n.x, p.y + g.bias * n.y, p.z + g.bias * n.z};
+    uint32_t i0[3], i1[3];
+    float f[3];
+#pragma unroll
+    for (int ax = 0; ax < 3; ++ax)
+    {
+        float x = (pp[ax] - g.origin[ax]) / g.cell[ax];
+        const float top = (float)(g.count[ax] - 1u);
+        x = !(x > 0.0f) ? 0.0f : (x > top ? top : x);
+        i0[ax] = (uint32_t)x;
+        f[ax] = x - truncf(x);
+        i1[ax] = i0[ax] + 1u < g.count[ax] ? i0[ax] + 1u : i0[ax];
+    }
+    const f3 r = reflect_rs(incoming, n);
+    const float rd[3] = {r.x, r.y, r.z};
+    const uint32_t rr = rv.res * rv.res, texel = probe_oct_texel(rd, rv.res);
+    // the level: l the last one with alpha[l] <= a (a clamped into the levels' range, a NaN to the lowest), hi the next one's alpha
+    uint32_t l = 0u;
+    float lo = rv.alpha[0], hi = rv.alpha[0];
+    bool at_top = true;
+    if (!(a > lo)) a = lo;
+#pragma unroll
+    for (uint32_t k = 1u; k < 8u; ++k)
+        if (k < rv.n_levels)
+        {
+            if (rv.alpha[k] <= a) { l = k; lo = rv.alpha[k]; }
+            else if (at_top) { hi = rv.alpha[k]; at_top = false; }
+        }
+    const float t = at_top ? 0.0f : (a - lo) / (hi - lo), t1 = 1.0f - t;
+    const uint32_t l1 = at_top ? l : l + 1u;
+    float W = 0.0f, S[3] = {0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (uint32_t k = 0; k < 8u; ++k)
+    {
+        const uint32_t cx = (k & 1u) ? i1[0] : i0[0], cy = (k & 2u) ? i1[1] : i0[1], cz = (k & 4u) ? i1[2] : i0[2];
+        const uint32_t node = (cz * g.count[1] + cy) * g.count[0] + cx;
+        const float wx = (k & 1u) ? f[0] : 1.0f - f[0], wy = (k & 2u) ? f[1] : 1.0f - f[1], wz = (k & 4u) ? f[2] : 1.0f - f[2];
+        float w = ((wx * wy) * wz) * (g.nodes[node].valid != 0.0f ? 1.0f : 0.0f);
+        if (VIS)
+        {
+            const DProbeDepth mcur = probe_corner_moments(g, *dv, pp, cx, cy, cz, node);
+            float v[3];
+            probe_corner_vector(g, pp, cx, cy, cz, v);
+            const float dist = sqrtf((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
+            const float var = fabsf(mcur.m2 - mcur.m1 * mcur.m1), dl = dist - mcur.m1;
+            const float ch = var / (var + dl * dl), c3 = (ch * ch) * ch;
+            const float vis = dist > mcur.m1 ? (c3 > dv->vis_floor ? c3 : dv->vis_floor) : 1.0f;
+            w = w * vis;
+            if (dv->facing)
+            {
+                const float cs = ((v[0] * n.x + v[1] * n.y) + v[2] * n.z) / dist, hh = (1.0f - cs) * 0.5f;
+                w = w * (dist > 0.0f ? hh * hh + 0.2f : 1.0f);
+            }
+        }
+        const size_t base = (size_t)node * rv.n_levels;
+        const f4 T0 = rv.table[(base + l) * rr + texel], T1 = rv.table[(base + l1) * rr + texel];
+        S[0] = S[0] + w * (t1 * T0.x + t * T1.x);
+        S[1] = S[1] + w * (t1 * T0.y + t * T1.y);
+        S[2] = S[2] + w * (t1 * T0.z + t * T1.z);
+        W = W + w;
+    }
+    const bool lit = W > 0.0f;
+    *out = lit ? f3{S[0] / W, S[1] / W, S[2] / W} : f3{0.0f, 0.0f, 0.0f};
     return lit;
 }
 

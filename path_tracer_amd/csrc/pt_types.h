@@ -160,6 +160,16 @@ struct ProbeDepthView
     uint32_t facing; // PT_PROBE_VIS_FACING set
     float vis_floor;
 };
+// Reflection probes (pt_set_probe_grid_radiance): every node's GGX-prefiltered radiance on an R x R octahedral map per roughness level,
+// table[(node * n_levels + level) * R * R + texel] = {r, g, b, 0}, texel probe_oct_texel of the reflected direction.  A table and a view of
+// their own, handed only to the kernels that read them (probe_grid_specular, pt_probe.h).
+struct ProbeRadianceView
+{
+    const f4* table;
+    uint32_t res;      // R, 2..16
+    uint32_t n_levels; // 1..8
+    float alpha[8];    // the levels' GGX alphas, strictly ascending; those from n_levels on are not read
+};
 
 // the barycentrics (u = v) of the light sampler's one-point quadrature (pt_api.h, LIGHT WEIGHT): a light triangle's weight is its area times
 // the length of its emitted colour there.  One constant for the host's weights (HostScene::build_lights) and the kernels' pdf (resolve_nee)

@@ -4,7 +4,7 @@ pt_render_baked(1 sample) at K = 0 and K = 2, beside pt_render_guides_followed a
 the 1-spp pt_frame.  Every figure is the median of --calls blocking calls, taken --reps times with the routes alternating, so that a drift
 of the shared machine touches all of them; the report keeps every repeat, the spread is theirs.
 
-    python tools/baked_view_bench.py [--calls 20] [--reps 3] [--what all|guides] [--probes [--depth R]] [--out report.json]
+    python tools/baked_view_bench.py [--calls 20] [--reps 3] [--what all|guides] [--probes [--depth R] [--radiance R]] [--out report.json]
 
 --what guides times the guides call alone and runs on a tree that has no baked view: run it from the parent commit's tree and from this one,
 turn about, for the comparison across the two (the guide kernels themselves must not have moved).
@@ -16,7 +16,13 @@ calls on a context without one; and pt_probe_backfaces for 4 096 probes x 256 sa
 --probes --depth R (profiles/r25_probe_depth.md) adds probe visibility: a third context whose grid carries a seeded R x R depth table (FACING
 on), its pt_render_baked beside the two others; pt_bake_probe_depth beside pt_probe_backfaces on 4 096 probes x 1 024 rays (the same trace
 plus one fold each); and pt_probe_grid_lookup(on_device) with and without depth on 2^20 points (blocking calls: both include the same
-staging copies of 28 MiB)."""
+staging copies of 28 MiB).
+
+--probes --radiance R (profiles/r27_probe_radiance.md) adds reflection probes: both boxes of the scene become GGX metal (roughness 0.4) in
+every context of the run, a further context's grid carries a seeded R x R radiance table of five levels, its pt_render_baked beside the
+grid's alone; pt_bake_probe_radiance beside pt_bake_probes on 4 096 probes x 1 024 rays (the same integration, another fold);
+pt_probe_radiance_prefilter(on_device) of 4 096 probes x 5 levels at R = 8 and R = 16 (blocking calls: staging copies included; the
+profile quotes the kernel alone from a kernel trace beside them); and pt_probe_grid_specular(on_device) beside pt_probe_grid_lookup on 2^20 points."""
 import argparse
 import json
 import os
@@ -57,6 +63,7 @@ def main():
     ap.add_argument("--what", choices=["all", "guides"], default="all")
     ap.add_argument("--probes", action="store_true")
     ap.add_argument("--depth", type=int, default=0)
+    ap.add_argument("--radiance", type=int, default=0)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import torch
@@ -123,6 +130,10 @@ DEPTH_SAMPLES, LOOKUPS = 1024, 1 << 20
 
 def probes(args, api, scenes):
     sc = scenes.cornell_box(W, H)
+    if args.radiance:
+        from path_tracer_amd.scene_desc import GGX, SceneDesc
+        metal = GGX.new_metal((0.9, 0.8, 0.6), 0.4)
+        sc = SceneDesc.new(scenes.cornell_models(tall_material=metal, short_material=metal), sc.camera, "cornell, metal boxes")
     bare, lit = api.Renderer(sc, W, H, max_bounces=DEPTH), api.Renderer(sc, W, H, max_bounces=DEPTH)
     pts = np.concatenate([(m.positions.reshape(-1, 3) @ mat[:, :3].T + mat[:, 3]) for m in sc.models for mat in m.matrices.astype(np.float64)])
     lo, hi = pts.min(0), pts.max(0)
@@ -165,6 +176,35 @@ def probes(args, api, scenes):
         routes.append((report["bake_probe_depth_ms"], lambda: bare.bake_probe_depth(pos, DEPTH_SAMPLES, R, far), 3))
         routes.append((report["lookup_ms"], lambda: lit.probe_grid_lookup(q, qn, on_device=True), 5))
         routes.append((report["lookup_depth_ms"], lambda: vis.probe_grid_lookup(q, qn, on_device=True), 5))
+    if args.radiance:
+        R = args.radiance
+        alphas = (0.1, 0.2, 0.4, 0.7, 1.0)
+        spec = api.Renderer(sc, W, H, max_bounces=DEPTH)
+        spec.set_probe_grid(lo + 0.5 * cell, cell, sh, normal_bias=0.01 * float(cell.min()))
+        table = rng.uniform(0.0, 2.0, (GRID ** 3, len(alphas), R * R, 4)).astype(np.float32)
+        table[..., 3] = 0.0
+        spec.set_probe_grid_radiance(table, alphas)
+        q = (lo + rng.uniform(0.0, 1.0, (LOOKUPS, 3)) * (hi - lo)).astype(np.float32)
+        qn = rng.normal(size=(LOOKUPS, 3)); qd = rng.normal(size=(LOOKUPS, 3))
+        qn = (qn / np.linalg.norm(qn, axis=1, keepdims=True)).astype(np.float32)
+        qd = (qd / np.linalg.norm(qd, axis=1, keepdims=True)).astype(np.float32)
+        qa = rng.uniform(0.0, 1.0, LOOKUPS).astype(np.float32)
+        raw = {}
+        for side in (8, 16):
+            counts = rng.integers(0, 12, (CENSUS_PROBES, side * side)).astype(np.uint32)
+            raw[side] = ((rng.uniform(0.0, 3.0, (CENSUS_PROBES, side * side, 3)) * counts[..., None]).astype(np.float32), counts)
+        report.update(radiance=R, baked_probes_radiance_ms={str(k): [] for k in HOPS}, radiance_census=[CENSUS_PROBES, DEPTH_SAMPLES], bake_probes_1024_ms=[],
+                      bake_probe_radiance_ms=[], prefilter_ms={"8": [], "16": []}, lookups=LOOKUPS, lookup_specular_ms=[])
+        report.setdefault("lookup_ms", [])
+        for k in HOPS:
+            routes.append((report["baked_probes_radiance_ms"][str(k)], lambda k=k: view(spec, k), args.calls))
+        routes.append((report["bake_probes_1024_ms"], lambda: bare.bake_probes(pos, DEPTH_SAMPLES), 3))
+        routes.append((report["bake_probe_radiance_ms"], lambda: bare.bake_probe_radiance(pos, DEPTH_SAMPLES, R), 3))
+        for side in (8, 16):
+            routes.append((report["prefilter_ms"][str(side)], lambda side=side: bare.probe_radiance_prefilter(*raw[side], alphas, on_device=True), 5))
+        if not args.depth:
+            routes.append((report["lookup_ms"], lambda: lit.probe_grid_lookup(q, qn, on_device=True), 5))
+        routes.append((report["lookup_specular_ms"], lambda: spec.probe_grid_specular(q, qn, qd, qa, on_device=True), 5))
     for _, fn, _ in routes:
         fn()
     for _ in range(args.reps):
