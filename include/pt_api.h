@@ -92,7 +92,26 @@ enum
 pt_ctx* pt_create(const pt_config* cfg);
 void pt_destroy(pt_ctx* ctx);
 const char* pt_last_error(pt_ctx* ctx);
-int pt_set_config(pt_ctx* ctx, const pt_config* cfg); /* change image size / bounces / seed / sharding between renders */
+/* Change image size / bounces / seed / sharding / flags / tuning knobs of a live context between renders.  The contract
+ * (tests/test_reconfig_host.py, tests/test_gpu_reconfig.py):
+ *  - A REFUSED call (any negative return: PT_ERR_ARG for a zero width or height, rank >= world_size, more than 2^31 - 1 pixels or more than
+ *    2^30 - 1 of them on this rank; PT_ERR_STATE for another device ordinal once the context has used its device) changes nothing: the
+ *    configuration in force, the local rows, every product, every validity flag and the resident scene are what they were.
+ *  - An ACCEPTED call that changes the SET of local pixels, i.e. after the defaults are applied (width, the list of local rows) differs,
+ *    whether through width, height, rank, world_size or strip_rows, leaves the frame state as pt_create leaves it: accumulation, position,
+ *    id history and moments read back zero, and there is no temporal history, no denoised frame, no adaptive list and no guides, mean
+ *    albedo or baked sums at all (pt_read_guides and friends answer PT_ERR_STATE: their buffers held another frame's pixels).  The test is
+ *    on the set, not on its size: 32 x 24 -> 24 x 32, rank 0 -> 1 of 2 and strip_rows 4 -> 2 drop everything although the count stays.
+ *  - An accepted call that keeps the set of local pixels keeps accumulation, position, id history, moments and temporal history (a
+ *    change of max_bounces, seed, ... accumulates onto them: pt_reset_accumulation is the caller's).  Turning PT_FLAG_ADAPTIVE on over an
+ *    accumulation that may hold samples leaves the moments invalid until pt_reset_accumulation or pt_write_moments.
+ *  - ANY accepted call makes the guides, the mean-albedo sums and the baked sums stale: the calls that need them answer PT_ERR_STATE until
+ *    they are made again (where the set of local pixels was kept, pt_read_guides, pt_read_guide_instances, pt_read_guide_albedo and
+ *    pt_read_guide_hops still copy out the stale guides, as after a camera move).  A change of stack_lds_levels or PT_FLAG_NO_LDS_SCENE uploads the scene again by the patch path (pt_scene_info);
+ *    no other change uploads anything.
+ *  - After any accepted call (and pt_reset_accumulation / pt_reset_temporal where the state was kept) every product is bit for bit what a
+ *    context created with that configuration produces. */
+int pt_set_config(pt_ctx* ctx, const pt_config* cfg);
 
 /* ---- Scene::new(Vec<Model>)  src/scene.rs:21 ------------------------------------------------------------------ */
 /* returns the material index (>= 0) or a negative pt_status */
@@ -693,7 +712,8 @@ int pt_post_denoise_albedo(pt_ctx* ctx, uint32_t w, uint32_t h, const pt_denoise
  * view of them is not changed by it) and leaves the guides valid.  data / position / id as pt_frame_moving; out_rgba (may be NULL) receives
  * the filtered frame (c, 1), which also counts as the last denoised frame for pt_write_denoised_image.
  * pt_read_temporal copies out H as stored (colour_n: rgb | N), M (moments2) and step 5's variance of the last step; any pointer may be NULL;
- * PT_ERR_STATE when there is no history.  pt_reset_temporal drops the history; so do pt_set_config with a new image size, pt_set_projection
+ * PT_ERR_STATE when there is no history.  pt_reset_temporal drops the history; so do an accepted pt_set_config that changes the set of local pixels (a new image size of the same
+ * pixel count included; see pt_set_config), pt_set_projection
  * and pt_set_lens with another aperture or focus than the one in force.  Camera moves and pt_set_instances + pt_build do not: they are what the pass exists for.
  * pt_post_temporal runs steps 1-5 and the feedback = 0 form of step 7 on caller images (host pointers, row-major w * h): the previous H, M,
  * X' | t', n' and m'; the current input rgba, position xyzt, normal xyz and model; xprev (NULL selects the position), nprev (NULL selects the

@@ -571,9 +571,14 @@ class Renderer:
             pass
 
     def set_config(self, **kw):
+        """pt_set_config with the given fields changed.  A refused call leaves the context AND self.cfg (which sizes every host buffer) as they were."""
+        new = Config.from_buffer_copy(self.cfg)
         for k, v in kw.items():
-            setattr(self.cfg, k, v)
-        self._chk(self.L.pt_set_config(self.ctx, C.byref(self.cfg)))
+            if not hasattr(Config, k):
+                raise AttributeError(f"pt_config has no field {k!r}")
+            setattr(new, k, v)
+        self._chk(self.L.pt_set_config(self.ctx, C.byref(new)))
+        self.cfg = new
 
     def set_camera(self, cam: CameraDesc):
         """Camera::new: the view and, with it, the description's thin lens (aperture 0 = pinhole)"""

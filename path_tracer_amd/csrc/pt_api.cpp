@@ -1826,20 +1826,31 @@ int pt_set_config(pt_ctx* c, const pt_config* cfg)
 {
     if (!c || !cfg) return PT_ERR_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
-    const uint32_t old_px = c->local_pixels;
-    const int old_dev = c->cfg.device;
     const pt_config old = c->cfg;
-    int r = normalise_config(c, cfg);
+    const std::vector<uint32_t> old_rows = c->rows;
+    int r = normalise_config(c, cfg); // (commits nothing when it refuses)
     if (r) return r;
+    if (c->dev_ready && cfg->device != old.device && cfg->device >= 0)
+    {
+        // a refused call changes nothing: the configuration and the row table are the old ones again before anything else is touched
+        c->cfg = old;
+        compute_rows(c);
+        return fail(c, PT_ERR_STATE, "device cannot change after first use");
+    }
     if (c->cfg.stack_lds_levels != old.stack_lds_levels || ((c->cfg.flags ^ old.flags) & PT_FLAG_NO_LDS_SCENE)) c->scene_uploaded = false;
-    if (c->dev_ready && cfg->device != old_dev && cfg->device >= 0) return fail(c, PT_ERR_STATE, "device cannot change after first use");
     // moments that were not kept while the flag was off do not describe an accumulation that may hold samples
     if ((c->cfg.flags & ~old.flags & PT_FLAG_ADAPTIVE) && c->d_accum.p) c->moments_valid = false;
     c->config_version++; // the guides belong to the old configuration
-    if (c->local_pixels != old_px)
+    // the frame state belongs to a SET of local pixels (width, local rows), not to their number: 32 x 24 -> 24 x 32, rank 0 -> 1 of 2 and
+    // strip_rows 4 -> 2 can all keep the count and none keeps a pixel where it was
+    if (c->cfg.width != old.width || c->rows != old_rows)
     {
         c->denoised_valid = false;
         c->temporal_valid = false; // the history belongs to the old image size
+        // stale guides stay readable (pt_read_guides): not these, whose buffers hold another frame's pixels and may be too small for this one
+        c->guides_valid = false;
+        c->albedo_valid = false;
+        c->baked_valid = false;
         c->d_accum.reset();
         c->d_position.reset();
         c->d_id.reset();
