@@ -46,6 +46,10 @@
 //   examples/headless ... --bake-lightmap ... --lightmap-denoise [--baked-view ...]   bakes with second moments (pt_bake_lightmap_moments), runs the
 //       texel-space filter on the sums (pt_lightmap_denoise, default parameters) and dilates its texel MEANS: map.txt then holds means, not sums,
 //       and --baked-view sets them as they are
+//   examples/headless ... --bake-lightmap ... --directional [--normal-ripples N] [--baked-view ...]   bakes the first moments beside the sums
+//       (pt_bake_lightmap_directional), takes their tangential gradient (pt_lightmap_gradient), dilates it plane by plane and, under --baked-view,
+//       sets it beside the map (pt_set_lightmap_directional): with --normal-ripples, which then lie under the bake's planar UVs (the floor and the
+//       ceiling have a tangent frame in them, the back wall has none and stays flat), the baked view shades the ripples.  map.txt is unchanged
 //   examples/headless ... --checker N   an N x N checker (texels 1 and 0.2, bilinear, repeating) on the floor, ceiling and back wall (cb_main.obj) with
 //                                        planar UVs: a vertex's (x, z) over the model's own extent in x and z
 //   examples/headless ... --emission-checker N   the same N x N checker as the EMISSION texture of the light (cb_light.obj) under the same planar UVs:
@@ -90,7 +94,7 @@ int main(int argc, char** argv)
     bool probe_depth_given = false;
     uint32_t probe_radiance = 0;           // --probe-radiance R
     bool probe_radiance_given = false, metal_box = false;
-    bool lightmap_denoise = false;
+    bool lightmap_denoise = false, directional = false;
     std::string baked_out = "";
     pt_projection projection{}; // PT_PROJ_PERSPECTIVE
     for (int i = 1; i < argc; ++i)
@@ -166,6 +170,7 @@ int main(int argc, char** argv)
             baked_out = next("--baked-view");
         }
         else if (a == "--lightmap-denoise") lightmap_denoise = true;
+        else if (a == "--directional") directional = true;
         else if (a == "--load-state") load_state = next("--load-state");
         else if (a == "--save-state") save_state = next("--save-state");
         else if (a == "--devices")
@@ -175,7 +180,7 @@ int main(int argc, char** argv)
         }
         else if (a == "--help" || a == "-h")
         {
-            std::printf("usage: %s [--width W] [--height H] [--frames N] [--bounces B] [--move] [--slide DX DZ] [--models DIR] [--out file.png] [--temporal file.png [--temporal-rescue] [--temporal-mean-length] [--temporal-demodulate]] [--denoise file.png] [--denoise-albedo file.png] [--follow K] [--mirror-glass] [--aperture A --focus F] [--projection panorama[:SX:SY]|ortho:HEIGHT] [--bake-probes NX NY NZ SPP file.txt] [--bake-lightmap W H SPP PASSES file.txt [--lightmap-denoise] [--baked-view SPP file.png]] [--probe-grid NX NY NZ SPP [--probe-depth R] [--probe-radiance R] --baked-view SPP file.png] [--metal-box] [--checker N] [--emission-checker N] [--normal-ripples N]\n", argv[0]);
+            std::printf("usage: %s [--width W] [--height H] [--frames N] [--bounces B] [--move] [--slide DX DZ] [--models DIR] [--out file.png] [--temporal file.png [--temporal-rescue] [--temporal-mean-length] [--temporal-demodulate]] [--denoise file.png] [--denoise-albedo file.png] [--follow K] [--mirror-glass] [--aperture A --focus F] [--projection panorama[:SX:SY]|ortho:HEIGHT] [--bake-probes NX NY NZ SPP file.txt] [--bake-lightmap W H SPP PASSES file.txt [--lightmap-denoise | --directional] [--baked-view SPP file.png]] [--probe-grid NX NY NZ SPP [--probe-depth R] [--probe-radiance R] --baked-view SPP file.png] [--metal-box] [--checker N] [--emission-checker N] [--normal-ripples N]\n", argv[0]);
             return 0;
         }
         else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
@@ -206,10 +211,16 @@ int main(int argc, char** argv)
         std::fprintf(stderr, "--lightmap-denoise filters the map --bake-lightmap bakes: it needs that option, and samples\n");
         return 2;
     }
-    if (normal_ripples && (checker || !lightmap_out.empty()))
+    if (directional && (lightmap_out.empty() || !lightmap[2] || lightmap_denoise))
     {
-        // both want the UVs of cb_main.obj: the checker and the lightmap the planar (x, z) ones, the ripples (x, y + z)
-        std::fprintf(stderr, "--normal-ripples cannot be combined with --checker or --bake-lightmap: each sets the UVs of cb_main.obj\n");
+        std::fprintf(stderr, "--directional bakes a direction beside the map --bake-lightmap bakes: it needs that option, and samples, and does not go with --lightmap-denoise\n");
+        return 2;
+    }
+    if (normal_ripples && (checker || (!lightmap_out.empty() && !directional)))
+    {
+        // both want the UVs of cb_main.obj: the checker and the lightmap the planar (x, z) ones, the ripples (x, y + z).  Under --directional
+        // the ripples take the bake's planar UVs
+        std::fprintf(stderr, "--normal-ripples cannot be combined with --checker, or with --bake-lightmap unless --directional: each sets the UVs of cb_main.obj\n");
         return 2;
     }
     if (!temporal_out.empty() && (!out.empty() || !denoise_out.empty() || !denoise_albedo_out.empty() || render_mode || gpus > 0 || !devices.empty()))
@@ -302,7 +313,7 @@ int main(int argc, char** argv)
         };
         if (checker || !lightmap_out.empty()) planar_uvs(1);
         if (emission_checker) planar_uvs(0);
-        if (normal_ripples)
+        if (normal_ripples && lightmap_out.empty())
         {
             // s = x, t = y + z, each over the model's own extent: no face of the room is degenerate in them
             const std::vector<float> p = renderer.model_positions(1);
@@ -347,9 +358,18 @@ int main(int argc, char** argv)
         // a lightmap for a run-time consumer: the room's shell under the planar UVs above, baked by the path tracer and dilated
         auto bake_lightmap = [&]() -> bool {
             if (lightmap_out.empty()) return true;
-            std::vector<float> sums;
+            std::vector<float> sums, grad;
             std::vector<uint8_t> cov;
-            if (lightmap_denoise)
+            if (directional)
+            {
+                // the first moments beside the sums, their gradient, and its dilation with a coverage of its own (the map's is dilated below)
+                std::vector<float> dirs;
+                cov = renderer.bake_lightmap_directional(1, 0, lightmap[0], lightmap[1], lightmap[2], sums, dirs, 0, 0, 0.25f);
+                grad = renderer.lightmap_gradient(1, 0, lightmap[0], lightmap[1], lightmap[2], dirs, true);
+                std::vector<uint8_t> grad_cov = cov;
+                renderer.dilate_lightmap_directional(lightmap[0], lightmap[1], lightmap[3], grad, grad_cov);
+            }
+            else if (lightmap_denoise)
             {
                 // the moments steer the filter's luminance term; what it returns are texel means, and those are what is dilated, written and set
                 std::vector<float> sumsq;
@@ -367,6 +387,7 @@ int main(int argc, char** argv)
             if (!lightmap_denoise)
                 for (float& s : sums) s = s / (float)lightmap[2];
             renderer.set_lightmap(1, 0, lightmap[0], lightmap[1], sums);
+            if (directional) renderer.set_lightmap_directional(1, 0, lightmap[0], lightmap[1], grad);
             return true;
         };
         // the baked view, after bake_lightmap: under --probe-grid an irradiance volume over the scene's bounds inset by half a cell lights

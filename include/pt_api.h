@@ -905,9 +905,9 @@ int pt_probe_ray(pt_ctx* ctx, uint32_t key, uint32_t sample, float d[3], float y
  * PT_ERR_ARG for a bad model or instance index, w or h of 0, n_samples == 0, a bias that is not finite, a NULL p or rgb_sum, a non-zero
  * reserved word, key_base + w * h or first_sample + n_samples beyond 2^32; PT_ERR_LIMIT for a side above 16384 or more than 2^26 texels.
  * A map with no covered texel is PT_OK and integrates nothing.
- * Out of scope: unwrapping and atlas packing, conservative or supersampled coverage, direct light sampled at the texel, directional maps,
- * pt_multi_* variants.  (Denoising a map: pt_bake_lightmap_moments and pt_lightmap_denoise; showing one: pt_set_lightmap and pt_render_baked;
- * all below.) */
+ * Out of scope: unwrapping and atlas packing, conservative or supersampled coverage, direct light sampled at the texel, pt_multi_* variants.
+ * (Denoising a map: pt_bake_lightmap_moments and pt_lightmap_denoise; showing one: pt_set_lightmap and pt_render_baked; a direction beside
+ * the irradiance, for normal-mapped surfaces: pt_bake_lightmap_directional; all below.) */
 typedef struct pt_lightmap_params
 {
     int32_t model;                    /* model index */
@@ -1037,7 +1037,8 @@ int pt_lightmap_lookup(pt_ctx* ctx, int on_device, uint32_t n, const uint32_t* i
  * a range beyond 2^32; PT_ERR_STATE as pt_render_guides; pt_read_baked and pt_write_baked_image PT_ERR_STATE without current sums.  A scene
  * with no map at all is legal.
  * With a probe grid set (pt_set_probe_grid, below) the third ending reads the grid instead of unlit wherever the grid lights the point.
- * Out of scope: pt_multi_* variants, directional maps, perturbed normals, ending the path tracer's own paths in the maps.  (The maps themselves are filtered before they are set:
+ * With a gradient set on a map (pt_set_lightmap_directional, below) the second ending reads the directional lookup under the hit's perturbed normal.
+ * Out of scope: pt_multi_* variants, ending the path tracer's own paths in the maps.  (The maps themselves are filtered before they are set:
  * pt_lightmap_denoise, which knows the coverage, then pt_lightmap_dilate.) */
 typedef struct pt_baked_params
 {
@@ -1049,6 +1050,64 @@ int pt_render_baked(pt_ctx* ctx, uint32_t first_sample, uint32_t n_samples, cons
 int pt_read_baked(pt_ctx* ctx, float* rgbn);
 int pt_reset_baked(pt_ctx* ctx);
 int pt_write_baked_image(pt_ctx* ctx, const char* path);
+
+/* ---- directional lightmaps: a direction baked beside the irradiance, so that the baked view shades normal-mapped surfaces ------------------- */
+/* A lightmap texel is the mean M0 = (1/N) sum L_s of the radiance over N cosine-distributed directions d_s about the texel normal n: what a
+ * Lambertian surface with shading normal n returns.  Under a perturbed normal n' the exact response is (1/N) sum L_s max(0, n'.d_s) / (n.d_s);
+ * without the clamp that is (n'.n) M0 + n'_t . E[L d_t / cos], whose second term has logarithmically infinite variance under cosine sampling and
+ * is not folded.  What is folded is the bounded first moment M1 = (1/N) sum L_s d_s, per channel a world-space vector, and the tangential
+ * gradient is taken from it under a linear model of radiance over the hemisphere, L = a + b.d: under the measure cos dw / pi,
+ * E[d d^T] = I/4 + n n^T/4, so the tangential part of M1 is b_t / 4, and (1/pi) int L d_t dw = (2/3) b_t: G = (8/3) (M1 - (M1.n) n).
+ *
+ * pt_bake_lightmap_directional is pt_bake_lightmap, and it also folds the first moment: for every covered texel k, every sample s ascending,
+ * every axis a = x, y, z and channel c, with L the radiance of that sample's ray and d its direction (pt_lightmap_ray's for that sample),
+ *     dir_sum[(k * 3 + a) * 3 + c] = dir_sum[(k * 3 + a) * 3 + c] + L[c] * d[a]        -- binary32: the product rounded, then the add
+ * dir_sum (host, w * h * 9 floats) is IN/OUT like rgb_sum: (0, a) then (a, b) is (0, a + b) bit for bit in both arrays; rgb_sum and coverage come
+ * out as pt_bake_lightmap's, bit for bit.  Errors, limits and their order: pt_bake_lightmap's, and PT_ERR_ARG for a NULL dir_sum.
+ *
+ * pt_lightmap_gradient turns the sums of n_samples samples into the gradient of every texel of the table of (model, instance, w, h), as
+ * pt_lightmap_texels gives it, n being the table's normal used as given (not renormalised).  Per covered texel and channel c, binary32, one
+ * rounding per operation, no contraction, in this order:
+ *     m.a = dir_sum[(k * 3 + a) * 3 + c] / (float)n_samples                       a = x, y, z
+ *     q = (m.x * n.x + m.y * n.y) + m.z * n.z
+ *     grad[(k * 3 + a) * 3 + c] = 2.6666667f * (m.a - q * n.a)
+ * An uncovered texel gets zeros.  on_device = 0 evaluates on the host and touches no GPU; 1 runs a kernel over the same function on the table
+ * the bake's own kernels make.  Errors: what pt_lightmap_texels refuses, PT_ERR_ARG for a NULL pointer or n_samples == 0.  Dilation is
+ * pt_lightmap_dilate on each of the three axis planes grad[.][a][.] (w * h * 3 floats each), each with a fresh copy of the coverage.
+ *
+ * pt_set_lightmap_directional attaches a gradient (w * h * 9 floats, the layout above) to a placement that already has a map of the same size;
+ * grad NULL with w == h == 0 clears it; pt_get_lightmap_directional_info reports 1 where a placement has one.  Refusals come before any device
+ * call and change nothing, the first that applies in this order: PT_ERR_ARG for a bad model or instance index, a grad without a size or a size
+ * without a grad; PT_ERR_STATE where the placement has no map; PT_ERR_ARG for a size that is not the map's, then for a value that is not finite
+ * (negative values are legal).  The gradient follows its map through pt_set_instances, pt_set_model_uvs and pt_build; pt_set_lightmap on the
+ * placement drops it; setting or clearing one makes the baked sums stale exactly as pt_set_lightmap does.  On the device: a second 16-byte
+ * buffer, three entries per texel (G_x, G_y, G_z, each rgb | unused) at three times the map's offset, built only while a gradient is set.
+ *
+ * THE DIRECTIONAL LOOKUP of a hit, with n the face-forwarded world normal of the hit's UNPERTURBED normal (the guides' normal) and n' the
+ * shading normal pt_shading_normal defines for the hit: the lookup above up to its weights (the same s, t, clamp, x0, x1, y0, y1, xf, yf), then
+ *     M0, G_x, G_y, G_z = the textures' blend of the four texels of the map and of each gradient plane
+ *     delta = n' - n        per component; (0, 0, 0) with no subtraction where the hit's material has no normal texture
+ *     dd = (delta.x * delta.x + delta.y * delta.y) + delta.z * delta.z
+ *     J = (M0 - (0.5f * dd) * M0) + ((G_x * delta.x + G_y * delta.y) + G_z * delta.z)        per channel
+ *     I = !(J > 0) ? 0 : J                                                                   -- never negative, a NaN gives 0
+ * For unit vectors n'.n = 1 - dd / 2 and G.n = 0; delta = 0 returns the lookup above bit for bit.  pt_lightmap_lookup_directional is its unit
+ * hook: pt_lightmap_lookup's queries with the ray's world direction dir_xyz (3 floats each), which decides the face: n and n' are both the
+ * face-forwarded ones, and the hook reads the map on either face.  A mapped leaf without a gradient gives pt_lightmap_lookup's result.
+ *
+ * THE BAKED VIEW WITH A GRADIENT.  While at least one map in use has a gradient and the built scene has a normal-mapped material, the second
+ * ending of pt_render_baked's table reads I of the directional lookup on a leaf whose map has a gradient (the scalar lookup on one whose map has
+ * none), and with a probe grid the third ending hands n' to the grid's lookup instead of n.  GGX metal under reflection probes keeps its
+ * unperturbed normal.  With no gradient, or no normal-mapped material, every call launches the kernels it launched and returns the bits it
+ * returned before.
+ * Out of scope: a second moment or the texel-space filter for dir_sum, pt_multi_* variants, a perturbed normal in the reflection probes'
+ * lookup, ending the path tracer's own paths in the maps. */
+int pt_bake_lightmap_directional(pt_ctx* ctx, const pt_lightmap_params* p, float* rgb_sum, float* dir_sum, uint8_t* coverage);
+int pt_lightmap_gradient(pt_ctx* ctx, int on_device, int model, uint32_t instance, uint32_t w, uint32_t h, uint32_t n_samples, const float* dir_sum,
+                         float* grad);
+int pt_set_lightmap_directional(pt_ctx* ctx, int model, uint32_t instance, uint32_t w, uint32_t h, const float* grad);
+int pt_get_lightmap_directional_info(pt_ctx* ctx, int model, uint32_t instance, uint32_t* has);
+int pt_lightmap_lookup_directional(pt_ctx* ctx, int on_device, uint32_t n, const uint32_t* instance, const uint32_t* prim, const float* u, const float* v,
+                                   const float* dir_xyz, float* rgb, uint8_t* mapped);
 
 /* ---- the irradiance volume: a regular grid of SH9 probes that lights what no lightmap lights --------------------------------------------- */
 /* pt_set_probe_grid gives the context a grid of nx * ny * nz probes in WORLD space: node (ix, iy, iz) stands at origin + (ix, iy, iz) * cell

@@ -485,6 +485,75 @@ public:
         check(pt_lightmap_lookup(ctx_, on_device ? 1 : 0, (uint32_t)n, instance.data(), prim.data(), u.data(), v.data(), rgb.data(), mapped.data()));
         return rgb;
     }
+    // directional lightmaps: bake_lightmap that also folds every sample's radiance times its direction into dir_sum (w * h * 9 as
+    // [texel][axis][channel]; empty: from zero) (pt_bake_lightmap_directional) ...
+    std::vector<uint8_t> bake_lightmap_directional(int model, uint32_t instance, uint32_t w, uint32_t h, uint32_t n_samples, std::vector<float>& rgb_sum,
+                                                   std::vector<float>& dir_sum, uint32_t first_sample = 0, uint32_t key_base = 0, float bias = 0.0f)
+    {
+        const size_t px = (size_t)w * h;
+        if (rgb_sum.empty()) rgb_sum.assign(px * 3, 0.0f);
+        if (dir_sum.empty()) dir_sum.assign(px * 9, 0.0f);
+        if (rgb_sum.size() != px * 3 || dir_sum.size() != px * 9) throw Error(PT_ERR_ARG, "bake_lightmap_directional: rgb_sum holds 3 values per texel and dir_sum 9");
+        std::vector<uint8_t> coverage(px);
+        pt_lightmap_params p{};
+        p.model = model; p.instance = instance; p.w = w; p.h = h;
+        p.first_sample = first_sample; p.n_samples = n_samples; p.key_base = key_base; p.bias = bias;
+        check(pt_bake_lightmap_directional(ctx_, &p, rgb_sum.data(), dir_sum.data(), coverage.data()));
+        return coverage;
+    }
+    // ... the tangential gradient of those sums over n_samples samples (pt_lightmap_gradient; w * h * 9, zeros where uncovered) ...
+    std::vector<float> lightmap_gradient(int model, uint32_t instance, uint32_t w, uint32_t h, uint32_t n_samples, const std::vector<float>& dir_sum,
+                                         bool on_device = false) const
+    {
+        if (dir_sum.size() != (size_t)w * h * 9) throw Error(PT_ERR_ARG, "lightmap_gradient: dir_sum does not hold 9 values per texel");
+        std::vector<float> grad(dir_sum.size());
+        check(pt_lightmap_gradient(ctx_, on_device ? 1 : 0, model, instance, w, h, n_samples, dir_sum.data(), grad.data()));
+        return grad;
+    }
+    // ... its dilation: dilate_lightmap on each of the three axis planes, each with a fresh copy of the coverage, which comes back dilated ...
+    void dilate_lightmap_directional(uint32_t w, uint32_t h, uint32_t passes, std::vector<float>& grad, std::vector<uint8_t>& coverage)
+    {
+        const size_t px = (size_t)w * h;
+        if (grad.size() != px * 9 || coverage.size() != px) throw Error(PT_ERR_ARG, "dilate_lightmap_directional: grad holds 9 values and coverage one byte per texel");
+        std::vector<uint8_t> out = coverage;
+        for (size_t a = 0; a < 3; ++a)
+        {
+            std::vector<float> plane(px * 3);
+            for (size_t k = 0; k < px; ++k)
+                for (size_t c = 0; c < 3; ++c) plane[3 * k + c] = grad[(3 * k + a) * 3 + c];
+            out = coverage;
+            dilate_lightmap(w, h, passes, plane, out);
+            for (size_t k = 0; k < px; ++k)
+                for (size_t c = 0; c < 3; ++c) grad[(3 * k + a) * 3 + c] = plane[3 * k + c];
+        }
+        coverage = out;
+    }
+    // ... and the gradient of one placement beside its map (pt_set_lightmap_directional): w * h * 9 values of the map's size; empty with
+    // w == h == 0 clears it.  lightmap_directional_info: whether the placement has one
+    void set_lightmap_directional(int model, uint32_t instance, uint32_t w, uint32_t h, const std::vector<float>& grad)
+    {
+        if (grad.size() != (size_t)w * h * 9) throw Error(PT_ERR_ARG, "set_lightmap_directional: grad does not hold 9 values per texel");
+        check(pt_set_lightmap_directional(ctx_, model, instance, w, h, grad.empty() ? nullptr : grad.data()));
+    }
+    bool lightmap_directional_info(int model, uint32_t instance) const
+    {
+        uint32_t has = 0;
+        check(pt_get_lightmap_directional_info(ctx_, model, instance, &has));
+        return has != 0;
+    }
+    // the lightmap under the perturbed normal at n hits made by rays of world direction dir (n * 3) (pt_lightmap_lookup_directional)
+    std::vector<float> lightmap_lookup_directional(const std::vector<uint32_t>& instance, const std::vector<uint32_t>& prim, const std::vector<float>& u,
+                                                   const std::vector<float>& v, const std::vector<float>& dir, std::vector<uint8_t>& mapped,
+                                                   bool on_device = false) const
+    {
+        const size_t n = instance.size();
+        if (prim.size() != n || u.size() != n || v.size() != n || dir.size() != n * 3) throw Error(PT_ERR_ARG, "lightmap_lookup_directional: the arrays differ in length");
+        std::vector<float> rgb(n * 3);
+        mapped.assign(n, 0);
+        check(pt_lightmap_lookup_directional(ctx_, on_device ? 1 : 0, (uint32_t)n, instance.data(), prim.data(), u.data(), v.data(), dir.data(), rgb.data(),
+                                             mapped.data()));
+        return rgb;
+    }
     // the baked view (pt_render_baked): adds samples [first_sample, first_sample + n_samples) of every pixel's followed first hit, shaded
     // from the lightmaps, to the baked sums and returns them (sum r, sum g, sum b, n per pixel)
     std::vector<float> render_baked(uint32_t first_sample, uint32_t n_samples, uint32_t max_hops = 0, std::array<float, 3> unlit = {0.0f, 0.0f, 0.0f})

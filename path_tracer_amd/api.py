@@ -54,6 +54,7 @@ EXPORTS = [
     "pt_probe_depth_texel", "pt_bake_probe_depth", "pt_set_probe_grid_depth", "pt_get_probe_grid_depth_info",
     "pt_probe_radiance_dir", "pt_bake_probe_radiance", "pt_probe_radiance_prefilter", "pt_set_probe_grid_radiance", "pt_get_probe_grid_radiance_info",
     "pt_probe_grid_specular",
+    "pt_bake_lightmap_directional", "pt_lightmap_gradient", "pt_set_lightmap_directional", "pt_get_lightmap_directional_info", "pt_lightmap_lookup_directional",
 ]
 
 
@@ -340,6 +341,11 @@ def lib():
         L.pt_get_lightmap_info.argtypes = [vp, C.c_int, u32, vp, vp]
         L.pt_lightmap_lookup.argtypes = [vp, C.c_int, u32, vp, vp, vp, vp, vp, vp]
         L.pt_render_baked.argtypes = [vp, u32, u32, C.POINTER(BakedParams), vp]
+        L.pt_bake_lightmap_directional.argtypes = [vp, C.POINTER(LightmapParams), vp, vp, vp]
+        L.pt_lightmap_gradient.argtypes = [vp, C.c_int, C.c_int, u32, u32, u32, u32, vp, vp]
+        L.pt_set_lightmap_directional.argtypes = [vp, C.c_int, u32, u32, u32, vp]
+        L.pt_get_lightmap_directional_info.argtypes = [vp, C.c_int, u32, vp]
+        L.pt_lightmap_lookup_directional.argtypes = [vp, C.c_int, u32, vp, vp, vp, vp, vp, vp, vp]
         L.pt_read_baked.argtypes = [vp, vp]
         L.pt_reset_baked.argtypes = [vp]
         L.pt_write_baked_image.argtypes = [vp, C.c_char_p]
@@ -1155,6 +1161,66 @@ class Renderer:
         assert i.shape == p.shape == uu.shape == vv.shape and i.ndim == 1
         out = np.zeros((i.shape[0], 3), np.float32); mapped = np.zeros(i.shape[0], np.uint8)
         self._chk(self.L.pt_lightmap_lookup(self.ctx, int(bool(on_device)), i.shape[0], _p(i), _p(p), _p(uu), _p(vv), _p(out), _p(mapped)))
+        return out, mapped
+
+    # ---- directional lightmaps: a direction baked beside the irradiance, for normal-mapped surfaces in the baked view
+    def bake_lightmap_directional(self, model, instance, w, h, n_samples, first_sample=0, key_base=0, bias=0.0, sums=None, dir_sums=None):
+        """bake_lightmap that also folds every sample's radiance times its direction (pt_bake_lightmap_directional): returns (sums (h, w, 3),
+        dir_sums (h, w, 3, 3) as [axis][channel], coverage (h, w) uint8); both sums continue from what is passed in (None: zero)"""
+        out = np.zeros((h, w, 3), np.float32) if sums is None else np.ascontiguousarray(sums, np.float32)
+        dirs = np.zeros((h, w, 3, 3), np.float32) if dir_sums is None else np.ascontiguousarray(dir_sums, np.float32)
+        if out.size != w * h * 3 or dirs.size != w * h * 9:
+            raise PtError(-1, "bake_lightmap_directional: sums holds 3 values per texel and dir_sums 9")
+        cov = np.zeros((h, w), np.uint8)
+        prm = LightmapParams(model, instance, w, h, first_sample, n_samples, key_base, bias)
+        self._chk(self.L.pt_bake_lightmap_directional(self.ctx, C.byref(prm), _p(out), _p(dirs), _p(cov)))
+        return out.reshape(h, w, 3), dirs.reshape(h, w, 3, 3), cov
+
+    def lightmap_gradient(self, model, instance, dir_sums, n_samples, on_device=False):
+        """the tangential gradient (pt_lightmap_gradient) of a directional bake's raw first moments (h, w, 3, 3) over n_samples samples:
+        (h, w, 3, 3) as [axis][channel], zeros where uncovered; on the host (no GPU) unless on_device"""
+        a = np.ascontiguousarray(dir_sums, np.float32)
+        if a.ndim != 4 or a.shape[2:] != (3, 3):
+            raise PtError(-1, "lightmap_gradient: dir_sums is (h, w, 3, 3)")
+        out = np.zeros_like(a)
+        self._chk(self.L.pt_lightmap_gradient(self.ctx, int(bool(on_device)), model, instance, a.shape[1], a.shape[0], n_samples, _p(a), _p(out)))
+        return out
+
+    def dilate_lightmap_directional(self, grad, coverage, passes=1):
+        """dilate_lightmap on the three axis planes of a gradient (h, w, 3, 3), each with a fresh copy of the coverage; returns (grad, coverage)"""
+        g = np.array(grad, np.float32, order="C")
+        if g.ndim != 4 or g.shape[2:] != (3, 3):
+            raise PtError(-1, "dilate_lightmap_directional: grad is (h, w, 3, 3)")
+        cov = np.asarray(coverage, np.uint8)
+        for a in range(3):
+            g[:, :, a, :], cov_out = self.dilate_lightmap(g[:, :, a, :], cov, passes)
+        return g, cov_out
+
+    def set_lightmap_directional(self, model, instance, grad):
+        """the gradient of placement (model, instance) (pt_set_lightmap_directional): grad (h, w, 3, 3) of the size of the placement's map; None
+        clears it"""
+        if grad is None:
+            self._chk(self.L.pt_set_lightmap_directional(self.ctx, model, instance, 0, 0, None))
+            return
+        a = np.ascontiguousarray(grad, np.float32)
+        if a.ndim != 4 or a.shape[2:] != (3, 3):
+            raise PtError(-1, "set_lightmap_directional: grad is (h, w, 3, 3)")
+        self._chk(self.L.pt_set_lightmap_directional(self.ctx, model, instance, a.shape[1], a.shape[0], _p(a)))
+
+    def lightmap_directional_info(self, model, instance):
+        """whether placement (model, instance) has a gradient"""
+        has = C.c_uint32()
+        self._chk(self.L.pt_get_lightmap_directional_info(self.ctx, model, instance, C.byref(has)))
+        return bool(has.value)
+
+    def lightmap_lookup_directional(self, instance, prim, u, v, direction, on_device=False):
+        """unit hook: lightmap_lookup under the perturbed normal of hits made by rays of world direction `direction` [n, 3]"""
+        i = np.ascontiguousarray(instance, dtype=np.uint32); p = np.ascontiguousarray(prim, dtype=np.uint32)
+        uu = np.ascontiguousarray(u, dtype=np.float32); vv = np.ascontiguousarray(v, dtype=np.float32)
+        d = np.ascontiguousarray(direction, dtype=np.float32)
+        assert i.shape == p.shape == uu.shape == vv.shape and i.ndim == 1 and d.shape == (i.shape[0], 3)
+        out = np.zeros((i.shape[0], 3), np.float32); mapped = np.zeros(i.shape[0], np.uint8)
+        self._chk(self.L.pt_lightmap_lookup_directional(self.ctx, int(bool(on_device)), i.shape[0], _p(i), _p(p), _p(uu), _p(vv), _p(d), _p(out), _p(mapped)))
         return out, mapped
 
     def render_baked(self, first_sample: int, n_samples: int, follow: int = 0, unlit=(0.0, 0.0, 0.0), download=True):

@@ -19,6 +19,10 @@
 //   host_sanitize lightmaps <n> <seed> lightmaps' host side: n random triangles with random UVs (far outside [0, 1], huge, mirrored and overflowing ones
 //                                      among them) under three placements, random maps of several sizes on two of them, then lightmap_lookup
 //                                      (pt_materials.h) at random hits; prints how many lookups met a map and a checksum of the results
+//   host_sanitize lightmaps_dir <n> <seed> directional lightmaps' host side: the same hostile UVs under a normal texture and three placements; gradients by
+//                                      lm_gradient (pt_lightmap.h) from random first-moment sums, denormal ones and zero normals among them, in tables
+//                                      that fill their allocation exactly; then lightmap_lookup_directional (pt_materials.h) under shading_normal_delta
+//                                      at random hits; prints the lookups and a checksum (nonzero exit for a negative or NaN result)
 //   host_sanitize texelfilter <n> <seed> the texel filter's host side (pt_lightmap_filter.h, the functions the kernels run): n random triangles with the
 //                                      same hostile UVs, their texel tables on maps from 1 x 1 up, sides that are no multiple of 16 among them, random
 //                                      positive sums, then the whole filter with 8 levels (step 128 exceeds every map), with and without second
@@ -343,6 +347,93 @@ int main(int argc, char** argv)
             ++mapped;
         }
         std::printf("{\"triangles\": %u, \"lookups\": %u, \"checksum\": %.6f}\n", n, mapped, acc);
+        return 0;
+    }
+    if (cmd == "lightmaps_dir" && argc >= 4)
+    {
+        const uint32_t n = (uint32_t)std::atoi(argv[2]);
+        uint64_t s = 0x9E3779B97F4A7C15ull ^ (uint64_t)std::atoll(argv[3]);
+        auto rnd = [&]() { s ^= s << 13; s ^= s >> 7; s ^= s << 17; return (float)((s >> 40) & 0xffff) / 65535.0f; };
+        HostScene sc;
+        const int mat = light_scene(sc);
+        if (mat < 0 || n == 0) return 3;
+        std::vector<float> p, nr, uv, ntex;
+        for (uint32_t t = 0; t < n; ++t)
+        {
+            const float c[3] = {200.0f * rnd() - 100.0f, 200.0f * rnd() - 100.0f, 200.0f * rnd() - 100.0f};
+            for (int v = 0; v < 3; ++v)
+                for (int k = 0; k < 3; ++k) { p.push_back(c[k] + 10.0f * rnd() - 5.0f); nr.push_back(k == 1 ? 1.0f : 0.2f * rnd() - 0.1f); }
+            const uint32_t shape = t % 6u; // lightmaps' six: inside, far outside, all equal, around 1e6, mirrored, the largest finite values
+            const float a[2] = {rnd(), rnd()};
+            for (int v = 0; v < 3; ++v)
+                for (int k = 0; k < 2; ++k)
+                    uv.push_back(shape == 0u ? rnd() : shape == 1u ? 40.0f * rnd() - 20.0f : shape == 2u ? a[k] : shape == 3u ? 1.0e6f + 3.0f * rnd()
+                                 : shape == 4u ? (v ? -1.0f : 1.0f) * (a[k] + rnd()) : (rnd() < 0.5f ? -3.0e38f : 3.0e38f));
+        }
+        for (int k = 0; k < 5 * 3; ++k) { ntex.push_back(rnd()); ntex.push_back(rnd()); ntex.push_back(0.5f + 0.5f * rnd()); }
+        const float turn[12] = {0, 0, 1, 30, 0, 1, 0, -20, -1, 0, 0, 10};
+        std::vector<float> mats(kIdentity, kIdentity + 12);
+        mats.insert(mats.end(), turn, turn + 12);
+        mats.insert(mats.end(), kIdentity, kIdentity + 12);
+        mats[2 * 12 + 3] = 500.0f;
+        const int model = sc.add_model(p.data(), nr.data(), n, mat, mats.data(), 3);
+        const int tex = sc.add_texture(5, 3, ntex.data());
+        if (model < 0 || tex < 0 || sc.set_model_uvs(model, uv.data(), n) != 0 || sc.set_material_normal_texture(mat, tex) != 0) return 4;
+        std::string err;
+        if (sc.build(&err) != 0) { std::printf("{\"error\": \"%s\"}\n", err.c_str()); return 0; }
+        const FlatScene& f = sc.flat;
+        if (!f.has_normal_maps) return 5;
+        // a map and a gradient on the first two placements: the gradient of random sums under random normals, a tenth of the normals zero
+        // and a tenth of the sums denormal
+        struct Map { uint32_t w, h; std::vector<f4> texels, grad; };
+        std::vector<Map> maps(2);
+        const uint32_t sizes[4][2] = {{1, 1}, {5, 3}, {16, 16}, {2, 37}};
+        for (Map& m : maps)
+        {
+            const uint32_t* wh = sizes[(uint32_t)(rnd() * 3.999f) % 4u];
+            m.w = wh[0];
+            m.h = wh[1];
+            for (uint32_t k = 0; k < m.w * m.h; ++k)
+            {
+                m.texels.push_back(f4{rnd(), rnd(), rnd(), 0.0f});
+                float dir9[9], g9[9];
+                const bool tiny = rnd() < 0.1f;
+                for (float& d : dir9) d = tiny ? 1.0e-42f * (rnd() - 0.5f) : 64.0f * (rnd() - 0.5f);
+                const f3 nn = rnd() < 0.1f ? f3{0.0f, 0.0f, 0.0f} : unit3(f3{rnd() - 0.5f, rnd() - 0.5f, rnd() + 0.1f});
+                lm_gradient(dir9, nn, 64.0f, g9);
+                for (int a = 0; a < 3; ++a) m.grad.push_back(f4{g9[3 * a], g9[3 * a + 1], g9[3 * a + 2], 0.0f});
+            }
+            m.texels.shrink_to_fit();
+            m.grad.shrink_to_fit();
+        }
+        const TexNView tv = f.texn_view();
+        double acc = 0.0;
+        uint32_t mapped = 0, moved = 0;
+        for (uint32_t q = 0; q < 8u * n; ++q)
+        {
+            const uint32_t inst = (uint32_t)(rnd() * 3.999f) % (uint32_t)sc.world.instances.size();
+            const uint32_t mi = sc.world.instances[inst].model;
+            if ((int)mi != model) continue;
+            uint32_t ordinal = 0;
+            for (uint32_t k = 0; k < inst; ++k) ordinal += sc.world.instances[k].model == mi ? 1u : 0u;
+            if (ordinal >= maps.size()) continue;
+            const uint32_t leaf_tri = (uint32_t)(rnd() * (float)n) % n, tri = f.tri_base[mi] + leaf_tri;
+            const uint32_t prim = sc.blas[mi].prim_ids[leaf_tri];
+            const float u = rnd(), v = rnd() * (1.0f - u);
+            const f3 d{rnd() - 0.5f, rnd() - 0.5f, rnd() - 0.5f};
+            bool front;
+            const f3 nrm = unperturbed_normal(f.tri_shade.data(), f.instances.data(), inst, tri, u, v, d, front);
+            f3 delta;
+            (void)shading_normal_delta(f.tri_shade.data(), f.instances.data(), f.materials.data(), tv, inst, tri, u, v, d, nrm, &delta);
+            const float* t = &sc.models[mi].uvs[(size_t)prim * 6];
+            const Map& m = maps[ordinal];
+            const f3 c = lightmap_lookup_directional(m.texels.data(), m.grad.data(), m.w, m.h, DTriUV{{t[0], t[1]}, {t[2], t[3]}, {t[4], t[5]}}, u, v, delta);
+            if (!(c.x >= 0.0f && c.y >= 0.0f && c.z >= 0.0f)) return 6;                // never negative, never a NaN
+            if (std::isfinite(c.x) && std::isfinite(c.y) && std::isfinite(c.z)) acc += c.x + 2.0 * c.y + 3.0 * c.z;
+            moved += (delta.x != 0.0f || delta.y != 0.0f || delta.z != 0.0f) ? 1u : 0u;
+            ++mapped;
+        }
+        std::printf("{\"triangles\": %u, \"lookups\": %u, \"moved\": %u, \"checksum\": %.6f}\n", n, mapped, moved, acc);
         return 0;
     }
     if (cmd == "texelfilter" && argc >= 4)

@@ -195,10 +195,14 @@ struct pt_ctx
     // lightmaps (pt_set_lightmap): lightmaps[model][ordinal], w == 0: none (rows may be shorter than the model's matrices); lightmap_version
     // counts their changes.  On the device in tables of their own (LmView), uploaded by the next baked call when the maps or the resident
     // scene changed since (lm_version, lm_upload: uploads_full + uploads_patched then).
-    struct Lightmap { uint32_t w = 0, h = 0; std::vector<f4> texels; };
+    // grad (pt_set_lightmap_directional): three f4 per texel (G_x, G_y, G_z, each rgb | 0), empty: the map has no gradient.  It lives and dies
+    // with its map; lm_dir: whether any map in use has one, as of the last ensure_lightmaps (the DIR endings' first condition)
+    struct Lightmap { uint32_t w = 0, h = 0; std::vector<f4> texels; std::vector<f4> grad; };
     std::vector<std::vector<Lightmap>> lightmaps;
     uint64_t lightmap_texels = 0, lightmap_version = 0;
-    DevBuf d_lm_texels, d_lm_leaf, d_lm_uv;
+    DevBuf d_lm_texels, d_lm_leaf, d_lm_uv, d_lm_grad, d_lm_leaf_dir;
+    LmDirView ld{};
+    bool lm_dir = false;
     LmView lm{};
     bool lm_valid = false;
     uint64_t lm_version = 0, lm_upload = 0;
@@ -1532,7 +1536,7 @@ int lightmap_check(pt_ctx* c, int model, uint32_t instance, uint32_t w, uint32_t
 
 // ---- lightmaps kept by the context (pt_set_lightmap; the lookup is pt_materials.h's)
 // the map of (model, ordinal), null where there is none
-const pt_ctx::Lightmap* lightmap_of(const pt_ctx* c, uint32_t model, uint32_t ordinal)
+pt_ctx::Lightmap* lightmap_of(pt_ctx* c, uint32_t model, uint32_t ordinal)
 {
     if (model >= c->lightmaps.size() || ordinal >= c->lightmaps[model].size() || !c->lightmaps[model][ordinal].w) return nullptr;
     return &c->lightmaps[model][ordinal];
@@ -1571,6 +1575,8 @@ int ensure_lightmaps(pt_ctx* c)
     const std::vector<uint32_t> ordinal = leaf_ordinals(sc);
     std::vector<DLightmap> leaf(std::max<size_t>(ordinal.size(), 1), DLightmap{0u, 0u, 0u, 0u});
     std::vector<f4> texels;
+    std::vector<std::pair<size_t, const pt_ctx::Lightmap*>> dirs; // the maps in use that have a gradient, with their first texel
+    std::vector<uint32_t> leaf_dir(leaf.size(), 0u);
     std::vector<DTriUV> uvs;
     std::vector<uint32_t> uv_add(sc.models.size(), 0u); // what takes a model's triangles into uvs (mod 2^32: any value, 0 included)
     std::vector<bool> placed(sc.models.size(), false);  // ... and whether the model's UVs are there yet
@@ -1591,9 +1597,31 @@ int ensure_lightmaps(pt_ctx* c)
             }
         }
         leaf[i] = DLightmap{(uint32_t)texels.size(), l->w, l->h, uv_add[mi]};
+        if (!l->grad.empty())
+        {
+            dirs.emplace_back(texels.size(), l);
+            leaf_dir[i] = 1u;
+        }
         texels.insert(texels.end(), l->texels.begin(), l->texels.end());
     }
     int r;
+    // the gradients beside the texels, at three times a map's offset, only while one is set (a map without one keeps zeros nothing reads)
+    std::vector<f4> grad;
+    if (dirs.empty())
+    {
+        // the last gradient is gone: so are its tables (an earlier baked call may still be reading them)
+        if (c->d_lm_grad.p || c->d_lm_leaf_dir.p) HIPCHK(c, hipStreamSynchronize(c->stream));
+        c->d_lm_grad.reset();
+        c->d_lm_leaf_dir.reset();
+    }
+    else
+    {
+        // (three f4 per texel of EVERY map in use, the maps without a gradient included: the table is addressed by the scalar map's offset)
+        try { grad.assign(texels.size() * 3, f4{0.0f, 0.0f, 0.0f, 0.0f}); }
+        catch (const std::exception& e) { return fail(c, PT_ERR_LIMIT, std::string("the gradient table does not fit in host memory: ") + e.what()); }
+        for (const auto& d : dirs) std::copy(d.second->grad.begin(), d.second->grad.end(), grad.begin() + 3 * d.first);
+        if ((r = dev_alloc(c, c->d_lm_grad, grad.size() * sizeof(f4))) || (r = dev_alloc(c, c->d_lm_leaf_dir, leaf_dir.size() * sizeof(uint32_t)))) return r;
+    }
     if ((r = dev_alloc(c, c->d_lm_leaf, leaf.size() * sizeof(DLightmap))) || (r = dev_alloc(c, c->d_lm_texels, texels.size() * sizeof(f4))) ||
         (r = dev_alloc(c, c->d_lm_uv, uvs.size() * sizeof(DTriUV))))
         return r;
@@ -1602,6 +1630,14 @@ int ensure_lightmaps(pt_ctx* c)
     if (!texels.empty()) HIPCHK(c, hipMemcpy(c->d_lm_texels.p, texels.data(), texels.size() * sizeof(f4), hipMemcpyHostToDevice));
     if (!uvs.empty()) HIPCHK(c, hipMemcpy(c->d_lm_uv.p, uvs.data(), uvs.size() * sizeof(DTriUV), hipMemcpyHostToDevice));
     c->lm = LmView{(const f4*)c->d_lm_texels.p, (const DLightmap*)c->d_lm_leaf.p, c->tex.tri_uv ? c->tex.tri_uv : (const DTriUV*)c->d_lm_uv.p};
+    c->ld = LmDirView{};
+    c->lm_dir = !dirs.empty();
+    if (c->lm_dir)
+    {
+        HIPCHK(c, hipMemcpy(c->d_lm_grad.p, grad.data(), grad.size() * sizeof(f4), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(c->d_lm_leaf_dir.p, leaf_dir.data(), leaf_dir.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        c->ld = LmDirView{(const f4*)c->d_lm_grad.p, (const uint32_t*)c->d_lm_leaf_dir.p};
+    }
     c->lm_valid = true;
     c->lm_version = c->lightmap_version;
     c->lm_upload = upload;
@@ -3115,13 +3151,22 @@ int baked_chains(pt_ctx* c, uint32_t sample, const pt_baked_params& p)
     const bool grid = !c->probes.empty(), depth = grid && !c->probe_moments.empty(), radiance = grid && !c->probe_radiance_table.empty();
     EnvView env{};
     if (c->env_w) env = EnvView{(const f4*)c->d_env.p, c->env_w, c->env_h, 0u, 0u};
+    // the DIR endings only where they can differ: a gradient in use and a normal-mapped material in the built scene
+    const bool dir = c->lm_dir && c->scene.flat.has_normal_maps;
     return walk_chains(c, sample, p.max_hops, [&](const ChainHop& q) {
         BakedArgs b{};
         static_cast<ChainHop&>(b) = q;
         b.sum = (f4*)c->d_baked_sum.p;
         b.env = env;
         std::memcpy(b.unlit, p.unlit, sizeof(b.unlit));
-        if (radiance)
+        if (dir)
+        {
+            const ProbeGridView gv = grid ? probe_grid_view(c, (const DProbe*)c->d_probes.p) : ProbeGridView{};
+            const ProbeDepthView dv = depth ? probe_depth_view(c, (const DProbeDepth*)c->d_probe_moments.p) : ProbeDepthView{};
+            const ProbeRadianceView rv = radiance ? probe_radiance_view(c, (const f4*)c->d_probe_radiance.p) : ProbeRadianceView{};
+            launch_baked_follow_directional(c->stream, c->sv, c->tex, c->lm, c->ld, b, grid ? &gv : nullptr, depth ? &dv : nullptr, radiance ? &rv : nullptr);
+        }
+        else if (radiance)
         {
             const ProbeDepthView dv = probe_depth_view(c, (const DProbeDepth*)c->d_probe_moments.p);
             launch_baked_follow_probes_spec(c->stream, c->sv, c->tex, c->lm, b, probe_grid_view(c, (const DProbe*)c->d_probes.p), depth ? &dv : nullptr,
@@ -3585,13 +3630,16 @@ int pt_lightmap_texels(pt_ctx* c, int model, uint32_t instance, uint32_t w, uint
 
 } // extern "C"
 namespace {
-// pt_bake_lightmap (sumsq null, moments false) and pt_bake_lightmap_moments under the context's lock
-int bake_lightmap_locked(pt_ctx* c, const pt_lightmap_params* p, float* rgb_sum, float* sumsq, bool moments, uint8_t* coverage)
+// pt_bake_lightmap (sumsq null, moments false), pt_bake_lightmap_moments and pt_bake_lightmap_directional (directional, dir_sum) under the
+// context's lock
+int bake_lightmap_locked(pt_ctx* c, const pt_lightmap_params* p, float* rgb_sum, float* sumsq, bool moments, uint8_t* coverage, float* dir_sum = nullptr,
+                         bool directional = false)
 {
     int r;
     if ((r = rays_precheck(c))) return r;
     if (!p || !rgb_sum) return fail(c, PT_ERR_ARG, "pt_bake_lightmap: p and rgb_sum must not be NULL");
     if (moments && !sumsq) return fail(c, PT_ERR_ARG, "pt_bake_lightmap_moments: sumsq must not be NULL");
+    if (directional && !dir_sum) return fail(c, PT_ERR_ARG, "pt_bake_lightmap_directional: dir_sum must not be NULL");
     if (p->reserved[0] || p->reserved[1] || p->reserved[2] || p->reserved[3]) return fail(c, PT_ERR_ARG, "pt_lightmap_params.reserved must be 0");
     if ((r = lightmap_check(c, p->model, p->instance, p->w, p->h))) return r;
     if (p->n_samples == 0) return fail(c, PT_ERR_ARG, "pt_lightmap_params.n_samples must be non-zero");
@@ -3616,12 +3664,17 @@ int bake_lightmap_locked(pt_ctx* c, const pt_lightmap_params* p, float* rgb_sum,
         const uint32_t* d_texels = (const uint32_t*)st.in(texels.data(), (size_t)n_cov * 4);
         float* d_sum = (float*)st.in(rgb_sum, px * 12);
         float* d_sq = moments ? (float*)st.in(sumsq, px * 4) : nullptr;
+        float* d_dir = directional ? (float*)st.in(dir_sum, px * 36) : nullptr;
         const LightmapBake lb{d_texels, t.position, t.normal, n_cov, p->first_sample, p->n_samples, p->key_base, c->cfg.n_sobol, p->bias, c->cfg.seed};
         if ((r = bake_rays(c, st, n_cov, p->n_samples,
                            [&](uint64_t first, uint32_t cnt, float* o, float* d, uint2* key) { launch_lightmap_rays(c->stream, lb, first, cnt, o, d, key); },
-                           [&](uint64_t first, uint32_t cnt, const float*, const f4* rad) { launch_lightmap_fold(c->stream, lb, first, cnt, rad, d_sum, d_sq); })))
+                           [&](uint64_t first, uint32_t cnt, const float* d, const f4* rad) {
+                               if (directional) launch_lightmap_fold_directional(c->stream, lb, first, cnt, rad, d, d_sum, d_dir);
+                               else launch_lightmap_fold(c->stream, lb, first, cnt, rad, d_sum, d_sq);
+                           })))
             return r;
         if ((r = st.download(rgb_sum, d_sum, px * 12))) return r;
+        if (directional && (r = st.download(dir_sum, d_dir, px * 36))) return r;
         if (moments && (r = st.download(sumsq, d_sq, px * 4))) return r;
     }
     if (coverage) std::memcpy(coverage, cov.data(), px);
@@ -3642,6 +3695,54 @@ int pt_bake_lightmap_moments(pt_ctx* c, const pt_lightmap_params* p, float* rgb_
     if (!c) return PT_ERR_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
     return bake_lightmap_locked(c, p, rgb_sum, sumsq, true, coverage);
+}
+
+int pt_bake_lightmap_directional(pt_ctx* c, const pt_lightmap_params* p, float* rgb_sum, float* dir_sum, uint8_t* coverage)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    return bake_lightmap_locked(c, p, rgb_sum, nullptr, false, coverage, dir_sum, true);
+}
+
+int pt_lightmap_gradient(pt_ctx* c, int on_device, int model, uint32_t instance, uint32_t w, uint32_t h, uint32_t n_samples, const float* dir_sum, float* grad)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    int r;
+    if (!dir_sum || !grad) return fail(c, PT_ERR_ARG, "pt_lightmap_gradient: dir_sum and grad must not be NULL");
+    if ((r = lightmap_check(c, model, instance, w, h))) return r;
+    if (n_samples == 0) return fail(c, PT_ERR_ARG, "pt_lightmap_gradient: n_samples must be non-zero");
+    const HostModel& m = c->scene.models[model];
+    const size_t px = (size_t)w * h;
+    if (!on_device)
+    {
+        std::vector<uint32_t> owner;
+        try { lightmap_owner_host(m, w, h, owner); }
+        catch (const std::exception& e) { return fail(c, PT_ERR_LIMIT, std::string("the texel table does not fit in host memory: ") + e.what()); }
+        for (size_t k = 0; k < px; ++k)
+        {
+            float out[9] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+            if (owner[k] != MISS_ID)
+            {
+                float u32, v32;
+                f3 P, n;
+                lm_resolve_host(m.uvs.data(), m.positions.data(), m.normals.data(), m.matrices[instance], w, h, k, owner[k], &u32, &v32, &P, &n);
+                lm_gradient(dir_sum + 9 * k, n, (float)n_samples, out);
+            }
+            std::memcpy(grad + 9 * k, out, sizeof(out));
+        }
+        return PT_OK;
+    }
+    if ((r = ensure_device(c))) return r;
+    Staging st(c);
+    LightmapDev t{};
+    if ((r = lightmap_texels_device(c, st, m, instance, w, h, t))) return r;
+    const float* d_dir = (const float*)st.in(dir_sum, px * 36);
+    float* d_grad = (float*)st.out(px * 36);
+    if (st.err) return st.err;
+    launch_lightmap_gradient(c->stream, (uint32_t)px, t.coverage, t.normal, n_samples, d_dir, d_grad);
+    HIPCHK(c, hipGetLastError());
+    return st.download(grad, d_grad, px * 36);
 }
 
 int pt_lightmap_denoise(pt_ctx* c, int on_device, const pt_lightmap_denoise_params* p, const float* rgb_sum, const float* sumsq, float* rgb_mean, float* texel_area)
@@ -3777,6 +3878,102 @@ int pt_get_lightmap_info(pt_ctx* c, int model, uint32_t instance, uint32_t* w, u
     *w = l ? l->w : 0u;
     *h = l ? l->h : 0u;
     return PT_OK;
+}
+
+int pt_set_lightmap_directional(pt_ctx* c, int model, uint32_t instance, uint32_t w, uint32_t h, const float* grad)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (model < 0 || model >= (int)c->scene.models.size()) return fail(c, PT_ERR_ARG, "pt_set_lightmap_directional: model index");
+    if (instance >= c->scene.models[model].matrices.size()) return fail(c, PT_ERR_ARG, "pt_set_lightmap_directional: instance index");
+    const bool clear = !grad && w == 0 && h == 0;
+    if (!clear && (!grad || w == 0 || h == 0))
+        return fail(c, PT_ERR_ARG, "pt_set_lightmap_directional: grad with a non-zero w and h sets a gradient, NULL with w == h == 0 clears it");
+    pt_ctx::Lightmap* l = lightmap_of(c, (uint32_t)model, instance);
+    if (clear)
+    {
+        if (!l || l->grad.empty()) return PT_OK;
+        l->grad = std::vector<f4>();
+        c->lightmap_version++;
+        return PT_OK;
+    }
+    if (!l) return fail(c, PT_ERR_STATE, "pt_set_lightmap_directional: the placement has no map (pt_set_lightmap)");
+    if (w != l->w || h != l->h) return fail(c, PT_ERR_ARG, "pt_set_lightmap_directional: w and h must be those of the placement's map");
+    const size_t n = (size_t)w * h;
+    for (size_t i = 0; i < 9 * n; ++i)
+        if (!std::isfinite(grad[i])) return fail(c, PT_ERR_ARG, "pt_set_lightmap_directional: a value that is not finite");
+    std::vector<f4> g;
+    try { g.resize(3 * n); }
+    catch (const std::exception& e) { return fail(c, PT_ERR_LIMIT, std::string("the gradient does not fit in host memory: ") + e.what()); }
+    for (size_t i = 0; i < 3 * n; ++i) g[i] = f4{grad[3 * i], grad[3 * i + 1], grad[3 * i + 2], 0.0f};
+    l->grad = std::move(g);
+    c->lightmap_version++;
+    return PT_OK;
+}
+
+int pt_get_lightmap_directional_info(pt_ctx* c, int model, uint32_t instance, uint32_t* has)
+{
+    if (!c || !has) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (model < 0 || model >= (int)c->scene.models.size()) return fail(c, PT_ERR_ARG, "pt_get_lightmap_directional_info: model index");
+    if (instance >= c->scene.models[model].matrices.size()) return fail(c, PT_ERR_ARG, "pt_get_lightmap_directional_info: instance index");
+    const pt_ctx::Lightmap* l = lightmap_of(c, (uint32_t)model, instance);
+    *has = l && !l->grad.empty() ? 1u : 0u;
+    return PT_OK;
+}
+
+int pt_lightmap_lookup_directional(pt_ctx* c, int on_device, uint32_t n, const uint32_t* instance, const uint32_t* prim, const float* u, const float* v,
+                                   const float* dir_xyz, float* rgb, uint8_t* mapped)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->scene.built) return fail(c, PT_ERR_STATE, "pt_build has not been called");
+    if (n == 0) return PT_OK;
+    if (!instance || !prim || !u || !v || !dir_xyz || !rgb || !mapped) return fail(c, PT_ERR_ARG, "null pointer");
+    std::vector<uint32_t> tri;
+    int r;
+    if ((r = leaf_order_tris(c, n, instance, prim, tri))) return r;
+    if (!on_device)
+    {
+        const FlatScene& f = c->scene.flat;
+        const TexNView tv = f.texn_view();
+        const std::vector<uint32_t> ordinal = leaf_ordinals(c->scene);
+        for (uint32_t i = 0; i < n; ++i)
+        {
+            const uint32_t mi = c->scene.world.instances[instance[i]].model;
+            const pt_ctx::Lightmap* l = lightmap_of(c, mi, ordinal[instance[i]]);
+            f3 col{0.0f, 0.0f, 0.0f};
+            if (l)
+            {
+                const float* p = &c->scene.models[mi].uvs[(size_t)prim[i] * 6];
+                const DTriUV uv{{p[0], p[1]}, {p[2], p[3]}, {p[4], p[5]}};
+                if (l->grad.empty()) col = lightmap_lookup(l->texels.data(), l->w, l->h, uv, u[i], v[i]);
+                else
+                {
+                    const f3 d{dir_xyz[3 * (size_t)i], dir_xyz[3 * (size_t)i + 1], dir_xyz[3 * (size_t)i + 2]};
+                    bool front;
+                    const f3 nrm = unperturbed_normal(f.tri_shade.data(), f.instances.data(), instance[i], tri[i], u[i], v[i], d, front);
+                    f3 delta;
+                    (void)shading_normal_delta(f.tri_shade.data(), f.instances.data(), f.materials.data(), tv, instance[i], tri[i], u[i], v[i], d, nrm, &delta);
+                    col = lightmap_lookup_directional(l->texels.data(), l->grad.data(), l->w, l->h, uv, u[i], v[i], delta);
+                }
+            }
+            rgb[3 * (size_t)i] = col.x; rgb[3 * (size_t)i + 1] = col.y; rgb[3 * (size_t)i + 2] = col.z;
+            mapped[i] = l ? 1u : 0u;
+        }
+        return PT_OK;
+    }
+    if ((r = upload_scene(c)) || (r = ensure_lightmaps(c))) return r;
+    Staging st(c);
+    const SurfaceQueries q = upload_queries(st, n, instance, tri, u, v);
+    const float* d_dir = (const float*)st.in(dir_xyz, (size_t)n * 12);
+    float* d_rgb = (float*)st.out((size_t)n * 12);
+    uint8_t* d_mapped = (uint8_t*)st.out(n);
+    if (st.err) return st.err;
+    launch_lightmap_lookup_directional(c->stream, c->sv, c->tex, c->lm, c->ld, n, q.instance, q.tri, q.u, q.v, d_dir, d_rgb, d_mapped);
+    HIPCHK(c, hipGetLastError());
+    if ((r = st.download(rgb, d_rgb, (size_t)n * 12))) return r;
+    return st.download(mapped, d_mapped, n);
 }
 
 int pt_lightmap_lookup(pt_ctx* c, int on_device, uint32_t n, const uint32_t* instance, const uint32_t* prim, const float* u, const float* v, float* rgb,

@@ -131,6 +131,11 @@ struct LightmapBake
 void launch_lightmap_rays(hipStream_t s, const LightmapBake& lb, uint64_t first, uint32_t count, float* o, float* d, uint2* key);
 // sumsq (pt_bake_lightmap_moments; null: pt_bake_lightmap's launch as it was): the map's w * h second moments, Q[texel] += l(L) * l(L) in the same order
 void launch_lightmap_fold(hipStream_t s, const LightmapBake& lb, uint64_t first, uint32_t count, const f4* radiance, float* sum, float* sumsq = nullptr);
+// pt_bake_lightmap_directional: the same window folded by twelve threads per covered texel, the three sums as above and the nine first moments
+// dir[texel][axis][channel] += L[channel] * d[axis] (d: the window's ray table, launch_lightmap_rays' directions) in the same order
+void launch_lightmap_fold_directional(hipStream_t s, const LightmapBake& lb, uint64_t first, uint32_t count, const f4* radiance, const float* d, float* sum, float* dir);
+// pt_lightmap_gradient: grad <- lm_gradient (pt_lightmap.h) of every texel of launch_lightmap_resolve's table (coverage, normal), zeros where uncovered
+void launch_lightmap_gradient(hipStream_t s, uint32_t n_texels, const uint8_t* coverage, const float* normal, uint32_t n_samples, const float* dir, float* grad);
 // one dilation pass (lm_dilate) of a w x h map from (rgb, cov) to (rgb_out, cov_out)
 void launch_lightmap_dilate(hipStream_t s, uint32_t w, uint32_t h, const float* rgb, const uint8_t* cov, float* rgb_out, uint8_t* cov_out);
 // the texel filter (pt_lightmap_denoise: pt_filter.h's a-trous core under pt_lightmap_filter.h's texel rule) of the map of lm: prim, position, normal are
@@ -355,6 +360,15 @@ void launch_probe_grid_specular(hipStream_t s, const ProbeGridView& grid, const 
 // unit hook (pt_lightmap_lookup): lightmap_at (pt_materials.h) of world instance[i], leaf-order triangle tri[i] at barycentrics u[i], v[i]
 void launch_lightmap_lookup(hipStream_t s, const LmView& lm, uint32_t n, const uint32_t* instance, const uint32_t* tri, const float* u, const float* v,
                             float* rgb, uint8_t* mapped);
+// directional lightmaps (pt_set_lightmap_directional).  The baked endings' DIR variants: a front-face hit on a mapped leaf reads the map through
+// lightmap_at_directional with delta = n' - n, and with a grid the probe lookup of an unmapped surface takes n' (shading_normal_delta,
+// pt_materials.h).  grid null: no grid; depth, rad null: without.  The host launches them only while a gradient is set and the built scene has a
+// normal-mapped material; every other call launches the kernels above
+void launch_baked_follow_directional(hipStream_t s, const SceneView& sv, const TexNView& tex, const LmView& lm, const LmDirView& ld, const BakedArgs& a,
+                                     const ProbeGridView* grid, const ProbeDepthView* depth, const ProbeRadianceView* rad);
+// unit hook (pt_lightmap_lookup_directional): lightmap_at_directional of n hits with ray directions dir (3 floats each)
+void launch_lightmap_lookup_directional(hipStream_t s, const SceneView& sv, const TexNView& tex, const LmView& lm, const LmDirView& ld, uint32_t n,
+                                        const uint32_t* instance, const uint32_t* tri, const float* u, const float* v, const float* dir, float* rgb, uint8_t* mapped);
 // pt_guide_follow_dir(on_device = 1): guide_follow_dir (pt_materials.h) of n hits of `material`, out4 = wo | followed
 void launch_guide_follow_dir(hipStream_t s, const SceneView& sv, int material, uint32_t n, const float* incoming, const float* normal, const uint8_t* front,
                              float* out4);

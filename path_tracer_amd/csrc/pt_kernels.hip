@@ -3242,13 +3242,19 @@ __global__ void __launch_bounds__(256, 8) k_guide_follow(const SceneView sv, con
 // constant ambient) of a miss, times R of the hop before unless the camera ray itself missed.  PROBES, with a probe grid set
 // (pt_set_probe_grid): a final surface that no map lights is lit by the grid where the grid is lit, by unlit where not; P and n are the
 // guides' (the hit position, the face-forwarded unperturbed normal).
-template <bool PROBES, bool VIS = false>
+// DIR, with a gradient set and a normal-mapped material in the scene (pt_set_lightmap_directional): n' = shading_normal of the hit, delta =
+// n' - n (zero by construction without a normal texture); a front face of a mapped leaf reads lightmap_at_directional, and the grid takes n'.
+// n' is gathered behind a barrier of its own, after the hop's gathers and before the map's, so one lookup's registers are live at a time.
+template <bool PROBES, bool VIS = false, bool DIR = false>
 struct BakedEnding
 {
     const LmView& lm;
     const BakedArgs& a;
     const ProbeGridView* grid; // null without PROBES
     const ProbeDepthView* depth = nullptr; // null without VIS (pt_set_probe_grid_depth: the lookup with visibility)
+    const LmDirView* ld = nullptr;  // these three: null without DIR
+    const SceneView* sv = nullptr;
+    const TexNView* texn = nullptr;
     // nothing here reads t, and carrying its sum through both barriers costs the probe ending's later hops a 67th register (the parent's 66 are
     // the bound: profiles/r25_chain_hop.md), so state[pixel].w holds one hop's t here
     static constexpr bool kSumT = false;
@@ -3262,7 +3268,23 @@ struct BakedEnding
         if (h.kind == MAT_EMISSIVE) return h.c;
         f3 l{a.unlit[0], a.unlit[1], a.unlit[2]};
         bool mapped = false;
-        if (h.front) // the bake lit the front side only
+        f3 np = h.nrm;
+        if constexpr (DIR)
+        {
+            if (PROBES || h.front)
+            {
+                __asm__ volatile("" ::: "memory");
+                f3 delta;
+                np = shading_normal_delta(sv->tri_shade, sv->instances, sv->materials, *texn, h.inst, h.tri, h.hit.y, h.hit.z, h.d, h.nrm, &delta);
+                if (h.front)
+                {
+                    __asm__ volatile("" ::: "memory");
+                    const f3 m = lightmap_at_directional(lm, *ld, h.inst, h.tri, h.hit.y, h.hit.z, delta, &mapped);
+                    if (mapped) l = m;
+                }
+            }
+        }
+        else if (h.front) // the bake lit the front side only
         {
             const f3 m = lightmap_at(lm, h.inst, h.tri, h.hit.y, h.hit.z, &mapped);
             if (mapped) l = m;
@@ -3273,7 +3295,7 @@ struct BakedEnding
             // registers more
             __asm__ volatile("" ::: "memory");
             f3 irr;
-            if (probe_grid_lookup<VIS>(*grid, fma3(h.d, bc3(h.hit.x), xyz(a.in.a[h.slot])), h.nrm, &irr, depth)) l = irr;
+            if (probe_grid_lookup<VIS>(*grid, fma3(h.d, bc3(h.hit.x), xyz(a.in.a[h.slot])), np, &irr, depth)) l = irr;
         }
         return h.c * l;
     }
@@ -3307,10 +3329,10 @@ __global__ void __launch_bounds__(256, 4) k_baked_follow_probes_vis(const SceneV
 // prefiltered radiance, B = R * S, where probe_grid_specular is lit, whether or not a map lights the surface (a map holds irradiance, which a
 // metal does not reflect diffusely); where it is not lit, and on every other kind, the ending is the probe ending's.  The metal branch comes
 // first and returns, so a lane holds one lookup's registers at a time.  P, n and d are ChainEnd's; the alpha is the material's own.
-template <bool VIS>
+template <bool VIS, bool DIR = false>
 struct BakedSpecEnding
 {
-    BakedEnding<true, VIS> base;
+    BakedEnding<true, VIS, DIR> base;
     const SceneView& sv;
     const ProbeRadianceView& rad;
     static constexpr bool kSumT = false;
@@ -3339,6 +3361,43 @@ __global__ void __launch_bounds__(256, 4) k_baked_follow_probes_spec_vis(const S
                                                                          const ProbeGridView grid, const ProbeDepthView depth, const ProbeRadianceView rad)
 {
     chain_hop<FIRST>(sv, tex, a, BakedSpecEnding<true>{BakedEnding<true, true>{lm, a, &grid, &depth}, sv, rad});
+}
+// ... and the DIR variants of the five endings above (BakedEnding's DIR axis), chosen on the host while a gradient is set and the scene has a
+// normal-mapped material.  All of them under the probe ending's bounds, which leave 128 registers: none spills
+// (profiles/r29_directional_lightmaps.md has their registers)
+template <bool FIRST>
+__global__ void __launch_bounds__(256, 4) k_baked_follow_dir(const SceneView sv, const TexNView tex, const LmView lm, const LmDirView ld, const BakedArgs a)
+{
+    chain_hop<FIRST>(sv, tex, a, BakedEnding<false, false, true>{lm, a, nullptr, nullptr, &ld, &sv, &tex});
+}
+template <bool FIRST, bool VIS>
+__global__ void __launch_bounds__(256, 4) k_baked_follow_probes_dir(const SceneView sv, const TexNView tex, const LmView lm, const LmDirView ld, const BakedArgs a,
+                                                                    const ProbeGridView grid, const ProbeDepthView depth)
+{
+    chain_hop<FIRST>(sv, tex, a, BakedEnding<true, VIS, true>{lm, a, &grid, VIS ? &depth : nullptr, &ld, &sv, &tex});
+}
+template <bool FIRST, bool VIS>
+__global__ void __launch_bounds__(256, 4) k_baked_follow_probes_spec_dir(const SceneView sv, const TexNView tex, const LmView lm, const LmDirView ld, const BakedArgs a,
+                                                                         const ProbeGridView grid, const ProbeDepthView depth, const ProbeRadianceView rad)
+{
+    chain_hop<FIRST>(sv, tex, a, BakedSpecEnding<VIS, true>{BakedEnding<true, VIS, true>{lm, a, &grid, VIS ? &depth : nullptr, &ld, &sv, &tex}, sv, rad});
+}
+// unit hook of the directional lookup: rgb, mapped = lightmap_at_directional with delta = n' - n of the hit under the ray direction dir
+__global__ void __launch_bounds__(256) k_lightmap_lookup_directional(const SceneView sv, const TexNView tex, const LmView lm, const LmDirView ld, const uint32_t n,
+                                                                     const uint32_t* __restrict__ instance, const uint32_t* __restrict__ tri,
+                                                                     const float* __restrict__ u, const float* __restrict__ v, const float* __restrict__ dir,
+                                                                     float* __restrict__ rgb, uint8_t* __restrict__ mapped)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const f3 d{dir[3u * (size_t)i], dir[3u * (size_t)i + 1u], dir[3u * (size_t)i + 2u]};
+    bool front, has;
+    const f3 nrm = unperturbed_normal(sv.tri_shade, sv.instances, instance[i], tri[i], u[i], v[i], d, front);
+    f3 delta;
+    (void)shading_normal_delta(sv.tri_shade, sv.instances, sv.materials, tex, instance[i], tri[i], u[i], v[i], d, nrm, &delta);
+    const f3 c = lightmap_at_directional(lm, ld, instance[i], tri[i], u[i], v[i], delta, &has);
+    rgb[3u * (size_t)i] = c.x; rgb[3u * (size_t)i + 1u] = c.y; rgb[3u * (size_t)i + 2u] = c.z;
+    mapped[i] = has ? 1u : 0u;
 }
 // unit hook of the probe grid's lookup: rgb, lit = probe_grid_lookup
 __global__ void __launch_bounds__(256, 4) k_probe_grid_lookup(const ProbeGridView grid, const uint32_t n, const float* __restrict__ position,
@@ -3988,6 +4047,22 @@ void launch_baked_follow_probes_spec(hipStream_t s, const SceneView& sv, const T
 {
     if (depth) launch_chain_hop(s, a, k_baked_follow_probes_spec_vis<true>, k_baked_follow_probes_spec_vis<false>, sv, tex, lm, a, grid, *depth, rad);
     else launch_chain_hop(s, a, k_baked_follow_probes_spec<true>, k_baked_follow_probes_spec<false>, sv, tex, lm, a, grid, rad);
+}
+void launch_baked_follow_directional(hipStream_t s, const SceneView& sv, const TexNView& tex, const LmView& lm, const LmDirView& ld, const BakedArgs& a,
+                                     const ProbeGridView* grid, const ProbeDepthView* depth, const ProbeRadianceView* rad)
+{
+    const ProbeDepthView dv = depth ? *depth : ProbeDepthView{};
+    if (!grid) launch_chain_hop(s, a, k_baked_follow_dir<true>, k_baked_follow_dir<false>, sv, tex, lm, ld, a);
+    else if (rad && depth) launch_chain_hop(s, a, k_baked_follow_probes_spec_dir<true, true>, k_baked_follow_probes_spec_dir<false, true>, sv, tex, lm, ld, a, *grid, dv, *rad);
+    else if (rad) launch_chain_hop(s, a, k_baked_follow_probes_spec_dir<true, false>, k_baked_follow_probes_spec_dir<false, false>, sv, tex, lm, ld, a, *grid, dv, *rad);
+    else if (depth) launch_chain_hop(s, a, k_baked_follow_probes_dir<true, true>, k_baked_follow_probes_dir<false, true>, sv, tex, lm, ld, a, *grid, dv);
+    else launch_chain_hop(s, a, k_baked_follow_probes_dir<true, false>, k_baked_follow_probes_dir<false, false>, sv, tex, lm, ld, a, *grid, dv);
+}
+void launch_lightmap_lookup_directional(hipStream_t s, const SceneView& sv, const TexNView& tex, const LmView& lm, const LmDirView& ld, uint32_t n,
+                                        const uint32_t* instance, const uint32_t* tri, const float* u, const float* v, const float* dir, float* rgb, uint8_t* mapped)
+{
+    if (n == 0u) return;
+    hipLaunchKernelGGL(k_lightmap_lookup_directional, dim3((n + 255u) / 256u), dim3(256), 0, s, sv, tex, lm, ld, n, instance, tri, u, v, dir, rgb, mapped);
 }
 void launch_probe_grid_lookup_vis(hipStream_t s, const ProbeGridView& grid, const ProbeDepthView& depth, uint32_t n, const float* position, const float* normal,
                                   float* rgb, uint8_t* lit)

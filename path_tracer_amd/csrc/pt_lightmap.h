@@ -112,6 +112,21 @@ PT_HD f3 lightmap_ray(uint64_t seed, uint32_t n_sobol, uint32_t key, uint32_t sa
     return mul(onb_from_normal(n), f3{cs * r, sn * r, z});
 }
 
+// The tangential gradient of a covered texel (pt_lightmap_gradient; include/pt_api.h states it): dir9 the texel's first-moment sums
+// [axis][channel] over n_samples cosine-distributed samples, n the texel table's normal, used as given.  Per channel m = dir / n_samples,
+// q = m . n, G = (8/3) * (m - q * n); grad9 in the same layout.  Shared by k_lm_gradient and the host evaluation.
+PT_HD void lm_gradient(const float dir9[9], f3 n, float n_samples, float grad9[9])
+{
+    for (uint32_t c = 0; c < 3u; ++c)
+    {
+        const f3 m{dir9[c] / n_samples, dir9[3u + c] / n_samples, dir9[6u + c] / n_samples};
+        const float q = (m.x * n.x + m.y * n.y) + m.z * n.z;
+        grad9[c] = 2.6666667f * (m.x - q * n.x);
+        grad9[3u + c] = 2.6666667f * (m.y - q * n.y);
+        grad9[6u + c] = 2.6666667f * (m.z - q * n.z);
+    }
+}
+
 // One dilation step of texel (i, j): false when the texel keeps its value (it is covered, or none of its eight neighbours is); otherwise the
 // mean of the neighbours with a non-zero coverage byte, added dy = -1..1 outer, dx = -1..1 inner
 PT_HD bool lm_dilate(const float* rgb, const uint8_t* cov, uint32_t w, uint32_t h, uint32_t i, uint32_t j, float out[3])

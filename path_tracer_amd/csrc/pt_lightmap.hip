@@ -6,6 +6,8 @@
 //   k_lm_rays      a thread per ray: origin P + bias * n, a cosine-distributed direction over n, the stream key
 //   k_lm_fold      a thread per (covered texel, channel): the window's radiance added to the texel's sum in sample order; with MOMENTS a
 //                  fourth thread per texel adds l(L) * l(L) to its second moment (pt_bake_lightmap_moments)
+//   k_lm_fold_dir  pt_bake_lightmap_directional: twelve threads per covered texel, the three sums as k_lm_fold and nine first moments L[c] * d[a]
+//   k_lm_gradient  a thread per texel: the tangential gradient of the first moments (lm_gradient)
 //   k_lm_dilate    a thread per texel: one dilation pass from one buffer pair to the other
 //   k_lmf_*        pt_lightmap_denoise: pt_filter.h's a-trous core under pt_lightmap_filter.h's texel rule.  One thread per texel; the spatial variance and the levels
 //                  in 16 x 16 workgroups, ping-pong.  Gather-bound like k_dn_level: a tap is three 16-byte loads (colour | variance, P | area,
@@ -95,9 +97,26 @@ __global__ void __launch_bounds__(256) k_lm_rays(const LightmapBake lb, const ui
     key[i] = make_uint2(lb.key_base + k, s);
 }
 
+// one channel's chain of k_lm_fold: *dst += src[4 * i] for i in [i0, i1), in order.  The adds form one dependent chain; the loads do not depend on
+// it, so eight samples are fetched before their adds, and the next eight can be in flight while those adds run
+__device__ __forceinline__ void fold_channel(float* __restrict__ dst, const float* __restrict__ src, uint32_t i0, uint32_t i1)
+{
+    float acc = *dst;
+    uint32_t i = i0;
+    for (; i + 8u <= i1; i += 8u)
+    {
+        float l[8];
+#pragma unroll
+        for (uint32_t q = 0; q < 8u; ++q) l[q] = src[4u * (size_t)(i + q)];
+#pragma unroll
+        for (uint32_t q = 0; q < 8u; ++q) acc = acc + l[q];
+    }
+    for (; i < i1; ++i) acc = acc + src[4u * (size_t)i];
+    *dst = acc;
+}
+
 // sum[texel][c] += L[c] over the window's rays of that texel, in sample order: one thread per (covered texel, channel), a serial fold by
-// definition (float addition does not associate) and no atomics.  The adds form one dependent chain; the loads do not depend on it, so eight
-// samples are fetched before their adds, and the next eight can be in flight while those adds run.
+// definition (float addition does not associate) and no atomics: fold_channel.
 // MOMENTS: four threads per texel; the fourth folds Q[texel] += l(L) * l(L) over the same rays in the same order, and the other three run
 // the code they run without it
 template <bool MOMENTS>
@@ -123,20 +142,61 @@ __global__ void __launch_bounds__(256) k_lm_fold(const LightmapBake lb, const ui
         *q = acc;
         return;
     }
-    float* dst = sum + 3u * (size_t)lb.texels[rank] + c;
-    const float* src = (const float*)radiance + c;
+    fold_channel(sum + 3u * (size_t)lb.texels[rank] + c, (const float*)radiance + c, i0, i1);
+}
+
+// pt_bake_lightmap_directional: twelve threads per covered texel.  The first three fold the sums with the code they run in k_lm_fold; thread
+// 3 + 3 * a + c folds the first moment M[texel][a][c] += L[c] * d[a] over the same rays in the same order, d being the window's ray table
+// (k_lm_rays' directions, still live after the integration: lightmap_ray's bits).  The product is rounded, then the add; each chain is one
+// dependent add chain like the sums', so it keeps their shape: eight samples' loads ahead of their adds
+__global__ void __launch_bounds__(256) k_lm_fold_dir(const LightmapBake lb, const uint64_t first, const uint32_t count, const f4* __restrict__ radiance,
+                                                      const float* __restrict__ d, float* __restrict__ sum, float* __restrict__ dir)
+{
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t p0 = (uint32_t)(first / lb.n_samples), p1 = (uint32_t)((first + count - 1u) / lb.n_samples);
+    if (t / 12u > p1 - p0) return;
+    const uint32_t rank = p0 + t / 12u, c = t % 12u;
+    const uint64_t lo = (uint64_t)rank * lb.n_samples, hi = lo + lb.n_samples;
+    const uint32_t i0 = (uint32_t)((lo > first ? lo : first) - first), i1 = (uint32_t)((hi < first + count ? hi : first + count) - first);
+    if (c < 3u)
+    {
+        fold_channel(sum + 3u * (size_t)lb.texels[rank] + c, (const float*)radiance + c, i0, i1);
+        return;
+    }
+    const uint32_t m = c - 3u, axis = m / 3u;
+    float* dst = dir + 9u * (size_t)lb.texels[rank] + m;
+    const float* src = (const float*)radiance + (m - 3u * axis);
+    const float* dsrc = d + axis;
     float acc = *dst;
     uint32_t i = i0;
     for (; i + 8u <= i1; i += 8u)
     {
-        float l[8];
+        float l[8], w[8];
 #pragma unroll
-        for (uint32_t q = 0; q < 8u; ++q) l[q] = src[4u * (size_t)(i + q)];
+        for (uint32_t q = 0; q < 8u; ++q) { l[q] = src[4u * (size_t)(i + q)]; w[q] = dsrc[3u * (size_t)(i + q)]; }
 #pragma unroll
-        for (uint32_t q = 0; q < 8u; ++q) acc = acc + l[q];
+        for (uint32_t q = 0; q < 8u; ++q) acc = acc + l[q] * w[q];
     }
-    for (; i < i1; ++i) acc = acc + src[4u * (size_t)i];
+    for (; i < i1; ++i) acc = acc + src[4u * (size_t)i] * dsrc[3u * (size_t)i];
     *dst = acc;
+}
+
+// pt_lightmap_gradient on the device: lm_gradient (pt_lightmap.h) of every texel of the table k_lm_cover / k_lm_resolve made; zeros where uncovered
+__global__ void __launch_bounds__(256) k_lm_gradient(const uint32_t n, const uint8_t* __restrict__ coverage, const float* __restrict__ normal, const float n_samples,
+                                                      const float* __restrict__ dir, float* __restrict__ grad)
+{
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    float in[9], out[9] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    if (coverage[k])
+    {
+#pragma unroll
+        for (uint32_t q = 0; q < 9u; ++q) in[q] = dir[9u * (size_t)k + q];
+        const float* pn = normal + 3u * (size_t)k;
+        lm_gradient(in, f3{pn[0], pn[1], pn[2]}, n_samples, out);
+    }
+#pragma unroll
+    for (uint32_t q = 0; q < 9u; ++q) grad[9u * (size_t)k + q] = out[q];
 }
 
 __global__ void __launch_bounds__(256) k_lm_dilate(const uint32_t w, const uint32_t h, const float* __restrict__ rgb, const uint8_t* __restrict__ cov,
@@ -212,6 +272,16 @@ void launch_lightmap_fold(hipStream_t s, const LightmapBake& lb, uint64_t first,
     const uint64_t texels = (first + count - 1u) / lb.n_samples - first / lb.n_samples + 1u;
     if (sumsq) hipLaunchKernelGGL(k_lm_fold<true>, blocks_for(texels * 4u), dim3(256), 0, s, lb, first, count, radiance, sum, sumsq);
     else hipLaunchKernelGGL(k_lm_fold<false>, blocks_for(texels * 3u), dim3(256), 0, s, lb, first, count, radiance, sum, sumsq);
+}
+void launch_lightmap_fold_directional(hipStream_t s, const LightmapBake& lb, uint64_t first, uint32_t count, const f4* radiance, const float* d, float* sum, float* dir)
+{
+    if (count == 0) return;
+    const uint64_t texels = (first + count - 1u) / lb.n_samples - first / lb.n_samples + 1u;
+    hipLaunchKernelGGL(k_lm_fold_dir, blocks_for(texels * 12u), dim3(256), 0, s, lb, first, count, radiance, d, sum, dir);
+}
+void launch_lightmap_gradient(hipStream_t s, uint32_t n_texels, const uint8_t* coverage, const float* normal, uint32_t n_samples, const float* dir, float* grad)
+{
+    hipLaunchKernelGGL(k_lm_gradient, blocks_for(n_texels), dim3(256), 0, s, n_texels, coverage, normal, (float)n_samples, dir, grad);
 }
 void launch_lightmap_dilate(hipStream_t s, uint32_t w, uint32_t h, const float* rgb, const uint8_t* cov, float* rgb_out, uint8_t* cov_out)
 {

@@ -261,6 +261,81 @@ PT_HD f3 shading_normal(const DTriVerts* tri_shade, const DInstance* instances, 
               (in.fwd[8] * m.x + in.fwd[9] * m.y) + in.fwd[10] * m.z};
 }
 
+// The directional lightmap lookup (pt_set_lightmap_directional; the definition is include/pt_api.h's): lightmap_lookup's s, t, clamp and
+// bilinear weights on the map's texel M0 and on its three gradient texels G_x, G_y, G_z (grad: three f4 per texel), each blended with
+// bilinear_blend's expression, one after the other so that one blend's texels are live at a time; then, with delta = n' - n,
+//     I = max(0, (M0 - (0.5 * (delta . delta)) * M0) + ((G_x * delta.x + G_y * delta.y) + G_z * delta.z))        per channel
+// the max written so that a NaN gives 0.  delta = 0 returns lightmap_lookup's bits: M0 - 0 * M0 and + (+-0) change nothing of a finite M0 >= 0.
+// Shared by the baked view's DIR kernels, the unit hook's kernel and the hook's host evaluation.
+// (The addressing lines are lightmap_lookup's, and unperturbed_normal below is shading_normal's first half, restated and not factored out
+// of them on purpose: lightmap_lookup, shading_normal and every kernel over them stay instruction for instruction what they were.)
+PT_HD f3 lightmap_lookup_directional(const f4* texels, const f4* grad, uint32_t w, uint32_t h, const DTriUV& uv, float u, float v, f3 delta)
+{
+    const float s = (uv.a[0] + u * (uv.b[0] - uv.a[0])) + v * (uv.c[0] - uv.a[0]);
+    const float t = (uv.a[1] + u * (uv.b[1] - uv.a[1])) + v * (uv.c[1] - uv.a[1]);
+    float x = (float)w * s - 0.5f, y = (float)h * t - 0.5f;
+    const float xm = (float)(w - 1u), ym = (float)(h - 1u);
+    x = !(x > 0.0f) ? 0.0f : (x > xm ? xm : x);
+    y = !(y > 0.0f) ? 0.0f : (y > ym ? ym : y);
+    const uint32_t x0 = (uint32_t)x, y0 = (uint32_t)y;
+    const float xf = x - truncf(x), yf = y - truncf(y);
+    const uint32_t x1 = x0 + 1u < w ? x0 + 1u : x0, y1 = y0 + 1u < h ? y0 + 1u : y0;
+    const size_t i00 = (size_t)y0 * w + x0, i01 = (size_t)y1 * w + x0, i10 = (size_t)y0 * w + x1, i11 = (size_t)y1 * w + x1;
+    f3 out;
+    {
+        const f4 c00 = texels[i00], c01 = texels[i01], c10 = texels[i10], c11 = texels[i11];
+        const f3 m0 = bilinear_blend(BilinearTap{f3{c00.x, c00.y, c00.z}, f3{c01.x, c01.y, c01.z}, f3{c10.x, c10.y, c10.z}, f3{c11.x, c11.y, c11.z}, xf, yf});
+        out = m0 - (0.5f * dot3(delta, delta)) * m0;
+    }
+    f3 g[3];
+#pragma unroll
+    for (uint32_t a = 0; a < 3u; ++a)
+    {
+        const f4 c00 = grad[3u * i00 + a], c01 = grad[3u * i01 + a], c10 = grad[3u * i10 + a], c11 = grad[3u * i11 + a];
+        g[a] = bilinear_blend(BilinearTap{f3{c00.x, c00.y, c00.z}, f3{c01.x, c01.y, c01.z}, f3{c10.x, c10.y, c10.z}, f3{c11.x, c11.y, c11.z}, xf, yf});
+    }
+    out = out + ((g[0] * delta.x + g[1] * delta.y) + g[2] * delta.z);
+    return f3{!(out.x > 0.0f) ? 0.0f : out.x, !(out.y > 0.0f) ? 0.0f : out.y, !(out.z > 0.0f) ? 0.0f : out.z};
+}
+// The face-forwarded world normal of the UNPERTURBED N of a hit: hit_normal's arithmetic (pt_kernels.hip), stated here for the host; it is
+// shading_normal's result on a material without a normal texture, bit for bit.
+PT_HD f3 unperturbed_normal(const DTriVerts* tri_shade, const DInstance* instances, uint32_t inst, uint32_t tri, float u, float v, f3 dir_world, bool& front)
+{
+    const DTriVerts tv3 = tri_shade[tri];
+    const float wgt = 1.0f - u - v;
+    const m33 nm{f3{tv3.a.x, tv3.a.y, tv3.a.z}, f3{tv3.b.x, tv3.b.y, tv3.b.z}, f3{tv3.c.x, tv3.c.y, tv3.c.z}};
+    f3 n = unit3(mul(nm, f3{wgt, u, v}));
+    const DInstance& in = instances[inst];
+    const f3 d_obj{(in.inv[0] * dir_world.x + in.inv[1] * dir_world.y) + in.inv[2] * dir_world.z,
+                   (in.inv[4] * dir_world.x + in.inv[5] * dir_world.y) + in.inv[6] * dir_world.z,
+                   (in.inv[8] * dir_world.x + in.inv[9] * dir_world.y) + in.inv[10] * dir_world.z};
+    front = dot3(d_obj, n) < 0.0f;
+    if (!front) n = -n;
+    return f3{(in.fwd[0] * n.x + in.fwd[1] * n.y) + in.fwd[2] * n.z, (in.fwd[4] * n.x + in.fwd[5] * n.y) + in.fwd[6] * n.z,
+              (in.fwd[8] * n.x + in.fwd[9] * n.y) + in.fwd[10] * n.z};
+}
+// n' of a hit whose unperturbed world normal is n (ChainEnd::nrm): shading_normal's result; n itself, with no arithmetic, where the hit's
+// material has no normal texture, so that delta = n' - n is zero there by construction and not by subtraction.  *delta <- n' - n.
+PT_HD f3 shading_normal_delta(const DTriVerts* tri_shade, const DInstance* instances, const DMaterial* materials, const TexNView& tv, uint32_t inst,
+                              uint32_t tri, float u, float v, f3 dir_world, f3 n, f3* delta)
+{
+    *delta = f3{0.0f, 0.0f, 0.0f};
+    if (materials[instances[inst].material].normal_texture == 0u) return n;
+    bool front;
+    const f3 np = shading_normal(tri_shade, instances, materials, tv, inst, tri, u, v, dir_world, front);
+    *delta = np - n;
+    return np;
+}
+// ... of a hit on world-TLAS leaf `inst`: lightmap_at where the leaf's map has no gradient (or there is no gradient at all)
+PT_HD f3 lightmap_at_directional(const LmView& lm, const LmDirView& ld, uint32_t inst, uint32_t tri, float u, float v, f3 delta, bool* mapped)
+{
+    const DLightmap r = lm.leaf[inst];
+    *mapped = r.w != 0u;
+    if (!*mapped) return f3{0.0f, 0.0f, 0.0f};
+    if (!ld.grad || !ld.leaf_dir[inst]) return lightmap_lookup(lm.texels + r.offset, r.w, r.h, lm.tri_uv[tri + r.uv_add], u, v);
+    return lightmap_lookup_directional(lm.texels + r.offset, ld.grad + 3u * (size_t)r.offset, r.w, r.h, lm.tri_uv[tri + r.uv_add], u, v, delta);
+}
+
 // MaterialTrait::scatter_direction
 PT_HD f3 mat_scatter(const MatView& m, Stream& rng, f3 incoming, f3 normal, bool front)
 {

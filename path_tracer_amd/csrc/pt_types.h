@@ -128,6 +128,16 @@ struct LmView
     const DLightmap* leaf;
     const DTriUV* tri_uv;
 };
+// ... and what a directional lookup (lightmap_lookup_directional, pt_materials.h; pt_set_lightmap_directional) reads beside it: the gradients
+// of every map in ONE f4 buffer, three f4 per texel (G_x, G_y, G_z, each rgb | unused), a map's first at three times DLightmap::offset, and a
+// word per world-TLAS leaf, non-zero where the leaf's map has a gradient (a map without one keeps zeros in the buffer, which nothing reads).
+// A view of its own, as TexNView is on top of TexView: LmView and the argument layout of every kernel that takes it stay what they are.  Only
+// built while a gradient is set; both null without.
+struct LmDirView
+{
+    const f4* grad;
+    const uint32_t* leaf_dir;
+};
 // The probe grid (pt_set_probe_grid): one record per node, node (ix, iy, iz) at (iz * ny + iy) * nx + ix: the 27 radiance SH coefficients
 // (coefficient-major, channel-minor) and the valid word (1.0f or 0.0f; an invalid node's coefficients are kept as zeros), seven 16-byte words.
 struct alignas(16) DProbe

@@ -4,7 +4,7 @@ pt_render_baked(1 sample) at K = 0 and K = 2, beside pt_render_guides_followed a
 the 1-spp pt_frame.  Every figure is the median of --calls blocking calls, taken --reps times with the routes alternating, so that a drift
 of the shared machine touches all of them; the report keeps every repeat, the spread is theirs.
 
-    python tools/baked_view_bench.py [--calls 20] [--reps 3] [--what all|guides] [--probes [--depth R] [--radiance R]] [--out report.json]
+    python tools/baked_view_bench.py [--calls 20] [--reps 3] [--what all|guides] [--probes [--depth R] [--radiance R]] [--directional] [--out report.json]
 
 --what guides times the guides call alone and runs on a tree that has no baked view: run it from the parent commit's tree and from this one,
 turn about, for the comparison across the two (the guide kernels themselves must not have moved).
@@ -22,7 +22,12 @@ staging copies of 28 MiB).
 every context of the run, a further context's grid carries a seeded R x R radiance table of five levels, its pt_render_baked beside the
 grid's alone; pt_bake_probe_radiance beside pt_bake_probes on 4 096 probes x 1 024 rays (the same integration, another fold);
 pt_probe_radiance_prefilter(on_device) of 4 096 probes x 5 levels at R = 8 and R = 16 (blocking calls: staging copies included; the
-profile quotes the kernel alone from a kernel trace beside them); and pt_probe_grid_specular(on_device) beside pt_probe_grid_lookup on 2^20 points."""
+profile quotes the kernel alone from a kernel trace beside them); and pt_probe_grid_specular(on_device) beside pt_probe_grid_lookup on 2^20 points.
+
+--directional (profiles/r29_directional_lightmaps.md) times the DIR endings: every Lambertian material of the scene carries an 8 x 8 ripple
+normal map, every placement a 256 x 256 map; one context stops there (the scalar kernels), a second also sets a seeded gradient on every
+placement (the DIR kernels): ms per pt_render_baked(1 sample) at K = 0 and K = 2 on both, turn about; and pt_bake_lightmap_directional beside
+pt_bake_lightmap on the shell's 256 x 256 map at 16 samples (the same integration, another fold, 36 more bytes per texel each way)."""
 import argparse
 import json
 import os
@@ -64,6 +69,7 @@ def main():
     ap.add_argument("--probes", action="store_true")
     ap.add_argument("--depth", type=int, default=0)
     ap.add_argument("--radiance", type=int, default=0)
+    ap.add_argument("--directional", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import torch
@@ -72,6 +78,8 @@ def main():
     from path_tracer_amd import api, scenes
     if args.probes:
         return probes(args, api, scenes)
+    if args.directional:
+        return directional(args, api, scenes)
     sc = scenes.cornell_box(W, H)
     baked = args.what == "all"
     if baked:
@@ -205,6 +213,51 @@ def probes(args, api, scenes):
         if not args.depth:
             routes.append((report["lookup_ms"], lambda: lit.probe_grid_lookup(q, qn, on_device=True), 5))
         routes.append((report["lookup_specular_ms"], lambda: spec.probe_grid_specular(q, qn, qd, qa, on_device=True), 5))
+    for _, fn, _ in routes:
+        fn()
+    for _ in range(args.reps):
+        for into, fn, calls in routes:
+            into.append(round(timed(fn, calls), 4))
+    emit(report, args.out)
+
+
+BAKE_SAMPLES = 16
+
+
+def directional(args, api, scenes):
+    import dataclasses
+    from path_tracer_amd.scene_desc import LAMBERTIAN, SceneDesc, Texture
+    n = 8
+    a = (np.arange(n, dtype=np.float32) + 0.5) / n
+    tri = 0.3 * (4.0 * np.abs(a - 0.5) - 1.0)
+    x, y = np.meshgrid(tri, tri)
+    ripples = Texture.new((0.5 * np.stack([x, y, np.sqrt(1.0 - x * x - y * y)], axis=2) + 0.5).astype(np.float32))
+    base = scenes.cornell_box(W, H)
+    models = [dataclasses.replace(m, material=m.material.normal_mapped(ripples) if m.material.kind == LAMBERTIAN else m.material, uvs=planar_uvs(m.positions))
+              for m in base.models]
+    sc = SceneDesc.new(models, base.camera, "cornell, rippled")
+    plain, dirn = api.Renderer(sc, W, H, max_bounces=DEPTH), api.Renderer(sc, W, H, max_bounces=DEPTH)
+    rng = np.random.default_rng(29)
+    for mi, m in enumerate(sc.models):
+        for j in range(m.matrices.shape[0]):
+            tex = rng.uniform(0.0, 1.0, (SIZE, SIZE, 3)).astype(np.float32)
+            plain.set_lightmap(mi, j, tex)
+            dirn.set_lightmap(mi, j, tex)
+            dirn.set_lightmap_directional(mi, j, rng.uniform(-0.5, 0.5, (SIZE, SIZE, 3, 3)).astype(np.float32))
+    shell = [m.name for m in sc.models].index("cb_main")
+    report = {"width": W, "height": H, "map": SIZE, "calls": args.calls, "what": "directional", "baked_ms": {str(k): [] for k in HOPS},
+              "baked_directional_ms": {str(k): [] for k in HOPS}, "bake": [SIZE, SIZE, BAKE_SAMPLES], "bake_lightmap_ms": [], "bake_lightmap_directional_ms": []}
+    sample = [0]
+
+    def view(r, k):
+        sample[0] += 1
+        r.render_baked(sample[0], 1, follow=k, download=False)
+    routes = []
+    for k in HOPS:
+        routes.append((report["baked_ms"][str(k)], lambda k=k: view(plain, k), args.calls))
+        routes.append((report["baked_directional_ms"][str(k)], lambda k=k: view(dirn, k), args.calls))
+    routes.append((report["bake_lightmap_ms"], lambda: plain.bake_lightmap(shell, 0, SIZE, SIZE, BAKE_SAMPLES, bias=0.25), 3))
+    routes.append((report["bake_lightmap_directional_ms"], lambda: plain.bake_lightmap_directional(shell, 0, SIZE, SIZE, BAKE_SAMPLES, bias=0.25), 3))
     for _, fn, _ in routes:
         fn()
     for _ in range(args.reps):
