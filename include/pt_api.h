@@ -1478,6 +1478,11 @@ int pt_variant_compiled(uint32_t launcher, const uint32_t axes6[6]);
  * row b - 1.  At most cap_rows rows are written; *n_rows <- how many there are. */
 enum { PT_LAUNCHES_BATCH = 0, PT_LAUNCHES_HOOK = 1 };
 int pt_last_launches(pt_ctx* ctx, uint32_t which, uint32_t* rows8, uint32_t cap_rows, uint32_t* n_rows);
+/* The launch geometry of the traversal kernels as the last scene upload derived it (host only, no device work): out[0] threads per traversal
+ * workgroup (256, 128 or 64: the most whose BVH and stacks fit 64 KiB of LDS), out[1] workgroups a traversal launch asks for at most, out[2]
+ * closest-hit stack levels kept in LDS (deeper ones spill to global memory), out[3] 1 when the Lambertian shading pass walks its shadow
+ * rays itself instead of queueing them.  PT_ERR_STATE before the first upload (any render or trace call uploads). */
+int pt_trace_geometry(pt_ctx* ctx, uint32_t out[4]);
 /* diagnostic (tools/shade_access_bench.py): path ids of slots [first, first + count) of a surface class's shade queue as the LAST batch's
  * last bounce left it (the order its shading pass read them in); 0xffffffff marks a slot no ray took.  qclass: 1 lambert .. 4 ggx */
 int pt_last_batch_shade_pids(pt_ctx* ctx, uint32_t qclass, uint32_t first, uint32_t count, uint32_t* pids);

@@ -69,6 +69,7 @@ def lib():
         L.pto_render_samples.argtypes = [C.c_void_p, C.POINTER(RenderCfg), C.c_void_p]
         L.pto_integrate.argtypes = [C.c_void_p, C.POINTER(RenderCfg), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
                                     C.c_void_p, C.c_void_p, C.c_void_p]
+        L.pto_integrate_counted.argtypes = [C.c_void_p, C.POINTER(RenderCfg), C.c_uint32] + [C.c_void_p] * 4 + [C.c_uint32] + [C.c_void_p] * 4
         L.pto_trace_closest.argtypes = [C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 10
         L.pto_trace_any.argtypes = [C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 4
         L.pto_blas_count.argtypes = [C.c_void_p]
@@ -251,6 +252,18 @@ class Oracle:
         o = np.ascontiguousarray(o, np.float32); d = np.ascontiguousarray(d, np.float32)
         self.L.pto_integrate(self.ctx, C.byref(cfg), _p(o), _p(d), pixel, sample, draws_consumed, _p(col), _p(pos), _p(idv))
         return col, pos, int(idv[0])
+
+    def integrate_counted(self, o, d, pixel, sample, draws_consumed=1, **kw):
+        """integrate over n rays at once: (radiance (n, 4), position (n, 4), id (n,), casts (n, 3) = each path's world closest-hit, any-hit and
+        lights closest-hit casts)"""
+        cfg = self.cfg(1, 1, **kw)
+        o = np.ascontiguousarray(o, np.float32); d = np.ascontiguousarray(d, np.float32)
+        pixel = np.ascontiguousarray(pixel, np.uint32); sample = np.ascontiguousarray(sample, np.uint32)
+        n = o.shape[0]
+        col = np.zeros((n, 4), np.float32); pos = np.zeros((n, 4), np.float32); idv = np.zeros(n, np.uint8); casts = np.zeros((n, 3), np.uint64)
+        r = self.L.pto_integrate_counted(self.ctx, C.byref(cfg), n, _p(o), _p(d), _p(pixel), _p(sample), draws_consumed, _p(col), _p(pos), _p(idv), _p(casts))
+        assert r == 0
+        return col, pos, idv, casts
 
     def blas_count(self):
         return self.L.pto_blas_count(self.ctx)

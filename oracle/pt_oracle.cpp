@@ -1613,6 +1613,24 @@ int pto_integrate(pto_ctx* c, const pto_render_cfg* cfg, const float o[3], const
     return 0;
 }
 
+int pto_integrate_counted(pto_ctx* c, const pto_render_cfg* cfg, uint32_t n, const float* o, const float* d, const uint32_t* pixel,
+                          const uint32_t* sample, uint32_t draws_consumed, float* colour, float* position, uint8_t* id, uint64_t* casts)
+{
+    if (!c->scene) return -3;
+    for (uint32_t i = 0; i < n; ++i)
+    {
+        Tracer tr(c->scene.get()); // a tracer of its own per ray: its counters are this ray's
+        Rng rng{stream_state0(cfg->seed, pixel[i], sample[i]), draws_consumed};
+        Ray r = Ray::make(V3{o[i * 3], o[i * 3 + 1], o[i * 3 + 2]}, V3{d[i * 3], d[i * 3 + 1], d[i * 3 + 2]});
+        Sample s = integrate(tr, r, rng, cfg->max_bounces, cfg->enable_nee != 0, &c->env);
+        std::memcpy(colour + 4 * i, &s.colour, 16);
+        std::memcpy(position + 4 * i, &s.position, 16);
+        id[i] = s.id;
+        for (int k = 0; k < 3; ++k) casts[3 * i + k] = tr.ctr.c[k];
+    }
+    return 0;
+}
+
 int pto_trace_closest(pto_ctx* c, int which, uint32_t n, const float* o, const float* d, const float* tmax, float* t, float* u, float* v,
                       uint32_t* inst, uint32_t* prim, float* normal, uint8_t* front)
 {

@@ -66,6 +66,9 @@ int pto_render(pto_ctx*, const pto_render_cfg*, float* accum_rgba, float* positi
 int pto_render_samples(pto_ctx*, const pto_render_cfg*, float* samples_rgba);
 int pto_integrate(pto_ctx*, const pto_render_cfg*, const float o[3], const float d[3], uint32_t pixel, uint32_t sample,
                   uint32_t draws_consumed, float colour[4], float position[4], uint8_t* id);
+/* pto_integrate over n rays (o, d: n * xyz; pixel, sample: the stream keys), and what each ray's path cast: casts[3 * i + k] = counters 0..2 */
+int pto_integrate_counted(pto_ctx*, const pto_render_cfg*, uint32_t n, const float* o, const float* d, const uint32_t* pixel,
+                          const uint32_t* sample, uint32_t draws_consumed, float* colour, float* position, uint8_t* id, uint64_t* casts);
 
 /* which: 0 = world TLAS, 1 = lights TLAS.  hit_*: t,u,v ; inst = TLAS leaf index (allocation order), prim = triangle
  * index inside its BLAS (original order); miss => inst = prim = 0xffffffff */

@@ -35,7 +35,7 @@ EXPORTS = [
     "pt_read_accumulation", "pt_read_frame", "pt_write_accumulation", "pt_render_samples", "pt_render_adaptive", "pt_adaptive_mask", "pt_read_moments", "pt_write_moments", "pt_active_pixels", "pt_local_rows", "pt_set_stream", "pt_synchronize", "pt_camera_input", "pt_camera_angles", "pt_frame", "pt_inv_projection", "pt_present", "pt_post_velocity", "pt_post_reproject", "pt_post_tonemap", "pt_post_rgb8", "pt_present_rgb8", "pt_write_image", "pt_trace_closest", "pt_trace_any",
     "pt_ss_sobol", "pt_math_batch", "pt_material_eval", "pt_volume_eval", "pt_bsdf_eval", "pt_blas_count", "pt_blas_dump", "pt_tlas_dump", "pt_tlas_instances", "pt_instance_materials", "pt_light_cdf",
     "pt_triangle_dump", "pt_get_stats", "pt_reset_stats", "pt_last_batch_counters", "pt_last_batch_shade_pids", "pt_last_batch_step_stats",
-    "pt_variant_axes", "pt_variant_compiled", "pt_last_launches",
+    "pt_variant_axes", "pt_variant_compiled", "pt_last_launches", "pt_trace_geometry",
     "pt_multi_create", "pt_multi_destroy", "pt_multi_last_error", "pt_multi_ctx", "pt_multi_render", "pt_multi_framebuffer_device_ptr",
     "pt_multi_reset_accumulation", "pt_multi_get_stats", "pt_multi_used_rccl", "pt_multi_write_image",
     "pt_render_guides", "pt_read_guides", "pt_denoise", "pt_write_denoised_image", "pt_post_denoise",
@@ -300,6 +300,7 @@ def lib():
         L.pt_reset_stats.argtypes = [vp]
         L.pt_last_batch_counters.argtypes = [vp, vp, u32, C.POINTER(u32)]
         L.pt_last_launches.argtypes = [vp, u32, vp, u32, C.POINTER(u32)]
+        L.pt_trace_geometry.argtypes = [vp, vp]
         L.pt_variant_axes.argtypes = [u32, vp]
         L.pt_variant_compiled.argtypes = [u32, vp]
         L.pt_last_batch_shade_pids.argtypes = [vp, u32, u32, u32, vp]
@@ -1601,6 +1602,14 @@ class Renderer:
         rows = np.zeros((max(n.value, 1), 8), np.uint32)
         self._chk(self.L.pt_last_launches(self.ctx, which, _p(rows), rows.shape[0], C.byref(n)))
         return [(LAUNCHERS[int(r[0])], int(r[1]), tuple(int(v) for v in r[2:2 + len(variant_axes(LAUNCHERS[int(r[0])]))])) for r in rows[: n.value]]
+
+    def trace_geometry(self):
+        """pt_trace_geometry: {block_threads, trace_blocks, stack_lds, shade_traces_shadow} of the uploaded scene (uploads it if need be)"""
+        z = np.zeros((0, 3), np.float32)
+        self.trace_closest(z, z)   # no rays: uploads the scene and launches nothing
+        out = np.zeros(4, np.uint32)
+        self._chk(self.L.pt_trace_geometry(self.ctx, _p(out)))
+        return {"block_threads": int(out[0]), "trace_blocks": int(out[1]), "stack_lds": int(out[2]), "shade_traces_shadow": bool(out[3])}
 
     def last_batch_shade_pids(self, qclass, first, count):
         out = np.zeros(count, np.uint32)

@@ -44,6 +44,12 @@
 //                                      fills its allocation exactly, then probe_grid_specular with and without a random depth table at the same
 //                                      kinds of points, with zero, huge, infinite and NaN directions and alphas; probe_oct_dir's round trip
 //                                      through probe_oct_texel; prints how many were lit, checksums, and whether every filtered value was finite
+//   host_sanitize queues <seed>        pt_queue_plan.h, the integer arithmetic under the hot kernels, swept over ray counts 1..4200, every 2^k - 1, 2^k, 2^k + 1
+//                                      below 2^29 and log-uniform ones: (P1) the static ranges and the accepted claims of fetch_plan / chunk_of / claim_range
+//                                      cover [0, n) exactly once for every grid, waves per workgroup, chunk divisor and taper; (P2) the striped regions of
+//                                      stripes_for are disjoint, stripe_valid and stripe_extent agree with what producers reserved, a region past the capacity
+//                                      is refused; (P3) region_size's bounds; (P4) fastdiv against `/`; (P5) pid_split / pid_join are inverse bijections
+//                                      under pid_block_layout.  Prints one JSON line of counts; nonzero exit on the first few failures (stderr names them)
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -58,6 +64,7 @@
 #include "pt_materials.h"
 #include "pt_png.h"
 #include "pt_probe.h"
+#include "pt_queue_plan.h"
 #include "pt_scene.h"
 
 using namespace pt;
@@ -95,6 +102,8 @@ static std::vector<f4> core_filter_host(int w, int h, const DenoiseK& k, std::ve
     }
     return cv;
 }
+
+#include "host_sanitize_queues.h"
 
 int main(int argc, char** argv)
 {
@@ -738,6 +747,7 @@ int main(int argc, char** argv)
                     round_trip, finite);
         return 0;
     }
+    if (cmd == "queues" && argc >= 3) return qsweep::queues_sweep((uint64_t)std::strtoull(argv[2], nullptr, 10));
     if (cmd == "plan")
     {
         std::printf("[");

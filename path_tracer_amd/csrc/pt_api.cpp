@@ -22,6 +22,7 @@
 #include "pt_lightmap.h"
 #include "pt_lightmap_filter.h"
 #include "pt_probe.h"
+#include "pt_queue_plan.h"
 #include "pt_scene.h"
 
 using namespace pt;
@@ -43,12 +44,6 @@ using namespace pt;
 #endif
 #ifndef PT_SIDE_PRIORITY
 #define PT_SIDE_PRIORITY 0
-#endif
-// samples per block of path ids (power of two; 1 = sample-major path ids as in rounds 1-3): RenderParams::blk_log.  Same-box A/B of 1 / 4 / 8 / 16 / 64, ms per
-// frame: Cornell 256 spp 67.6 / 67.4 / 66.7 / 67.3 / 67.6, atrium 64 spp 288.4 / 283.8 / 283.1 / 281.4 / 281.4, three spheres 49.95 / 49.2 / 49.0 / 48.7 / 48.7, mixed
-// materials 79.05 / 78.3 / 77.1 / 77.2 / 77.3, 82 k / 328 k meshes +-0: the camera-ray launch gains 7-10 % (Cornell 4.61 -> 4.30 ms, atrium 33.2 -> 30.0 ms), the rest ~1 %.
-#ifndef PT_PID_BLOCK
-#define PT_PID_BLOCK 16
 #endif
 #ifndef PT_FUSED_TRACE
 #define PT_FUSED_TRACE 1
@@ -965,13 +960,7 @@ int batch_begin(BatchRun& br, pt_ctx* c, const BatchSpec& spec)
     rp.keep_s_id = count >= 2 ? count - 2 : 0u;
     rp.keep_s_pos = count - 1;
     rp.seed = g.seed;
-    // path ids in blocks of PT_PID_BLOCK samples (RenderParams::blk_log); a batch shorter than a block is one short block
-    rp.blk_log = 0;
-    while ((2u << rp.blk_log) <= (uint32_t)PT_PID_BLOCK && (2u << rp.blk_log) <= count) ++rp.blk_log;
-    rp.n_blk = (count + (1u << rp.blk_log) - 1u) >> rp.blk_log;
-    rp.blk_last = count - ((rp.n_blk - 1u) << rp.blk_log);
-    rp.div_blk_paths = fastdiv_make(rp.act_pixels << rp.blk_log);
-    rp.div_blk_last = fastdiv_make(rp.blk_last);
+    pid_block_layout(rp); // path ids in blocks of PT_PID_BLOCK samples (RenderParams::blk_log)
     rp.div_act_w = fastdiv_make(rp.act_w);
     rp.div_width = fastdiv_make(rp.width);
     rp.div_strip_rows = fastdiv_make(rp.strip_rows);
@@ -5145,6 +5134,17 @@ int pt_last_launches(pt_ctx* c, uint32_t which, uint32_t* rows8, uint32_t cap_ro
     static_assert(sizeof(LaunchRow) == 32, "pt_last_launches hands the rows out as they are");
     if (cap_rows && !log.empty()) std::memcpy(rows8, log.data(), std::min<size_t>(cap_rows, log.size()) * sizeof(LaunchRow));
     *n_rows = (uint32_t)log.size();
+    return PT_OK;
+}
+int pt_trace_geometry(pt_ctx* c, uint32_t out[4])
+{
+    if (!c || !out) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->scene_uploaded) return fail(c, PT_ERR_STATE, "the scene has not been uploaded");
+    out[0] = c->block_threads;
+    out[1] = c->trace_blocks;
+    out[2] = c->sv.stack_lds;
+    out[3] = shade_traces_shadow(trace_launch(c)) ? 1u : 0u;
     return PT_OK;
 }
 int pt_variant_axes(uint32_t launcher, uint32_t bounds6[6])

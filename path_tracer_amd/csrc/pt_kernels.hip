@@ -19,6 +19,7 @@
 #include "pt_camera.h"
 #include "pt_probe.h"
 #include "pt_materials.h"
+#include "pt_queue_plan.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -107,20 +108,6 @@ constexpr uint32_t trace_waves_cap(bool lds, bool ident) { return lds && ident ?
 #ifndef PT_WAVE_TIMES
 #define PT_WAVE_TIMES 0
 #endif
-// a wave takes part in a launch only if the queue holds this many 64-ray generations for it (fetch_plan)
-#ifndef PT_MIN_GENERATIONS
-#define PT_MIN_GENERATIONS 1
-#endif
-// striped shade-queue tails: see stripes_for
-#ifndef PT_STRIPE_DIV
-#define PT_STRIPE_DIV 64
-#endif
-#ifndef PT_REGIONS_PER_STRIPE
-#define PT_REGIONS_PER_STRIPE 256
-#endif
-#ifndef PT_REGION_DIV
-#define PT_REGION_DIV 16
-#endif
 // tapered chunks: 64-ray chunks per wave in a queue's last level (0 = chunks of one size; chunk_of)
 #ifndef PT_TAPER
 #define PT_TAPER 2
@@ -172,9 +159,6 @@ constexpr int shade_waves(uint32_t qclass, bool volumes)
 #ifndef PT_SHADE_THREADS
 #define PT_SHADE_THREADS 256
 #endif
-#ifndef PT_CHUNK_MAX
-#define PT_CHUNK_MAX 1024
-#endif
 #ifndef PT_CHUNK_DIV
 #define PT_CHUNK_DIV 4
 #endif
@@ -193,79 +177,18 @@ template <bool LDS_SCENE> struct Refill
     static constexpr int kBelowAny = LDS_SCENE ? PT_REFILL_BELOW_ANY : PT_REFILL_BELOW_GLOBAL_BVH;
 };
 
-__device__ __forceinline__ uint32_t fastdiv(uint32_t n, const FastDiv& f)
-{
-    const uint32_t q = __umulhi(f.magic, n);
-    const uint32_t t = ((n - q) >> 1) + q;
-    return f.one ? n : (t >> f.shift);
-}
 __device__ __forceinline__ uint32_t lane_id() { return threadIdx.x & 63u; }
 __device__ __forceinline__ uint32_t mbcnt64(uint64_t m)
 {
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
 }
-// Persistent-thread work fetch.  A single queue-head word sustains only ~88 dequeues/us on MI355X — 16 k claims take 186 us, which
-// used to be most of a 1 M-ray launch — so:
-//  * the first chunk of every wave is static (wave w owns rays [w*chunk, (w+1)*chunk)): a launch with few rays costs no atomics
-//    at all, and only as many workgroups as the queue has 64-ray chunks take part (the others leave before staging anything);
-//  * the rest of the queue is cut into kQueueHeads partitions with one claim cursor each, every cursor in a cache line of its own
-//    (QueueHeads, pt_types.h).  A wave that runs dry looks at all cursors with ONE 64-lane load, claims a chunk with one atomic
-//    from the first partition at or after its home partition that has one left, and so drifts on to other partitions (steals)
-//    when its own is empty.  "Nothing left anywhere" is seen by that load: no wave ends with an atomic that finds the queue empty;
-//  * with claims this cheap the chunks can be small (n / 4 per wave, 64..1024 rays; same-box sweep: 512/8 the same, 256/16 and
-//    2048/2 worse): the launch ends about one small chunk after the last claim instead of after the slowest wave's two big ones.
-struct FetchPlan
-{
-    uint32_t n;        // rays (queue slots) in the launch
-    uint32_t chunk;    // rays per static chunk, and the most a dynamic claim takes; multiple of 64
-    uint32_t n_static; // slots [0, n_static) are owned statically, chunk by chunk, by the participating waves
-    uint32_t psize;    // slots per dynamic partition, multiple of 64
-    uint32_t lvl;      // the last `lvl` slots of a partition are handed out 64 at a time, the 2 lvl before them 128 at a time, ... (chunk_of)
-    uint32_t blocks;   // workgroups that take part
-};
-// The chunks of a partition, in the order they are handed out: big ones first, small ones last, so that what the waves still hold
-// when the queue runs dry — each its current chunk and the one it claimed ahead — is little.  (Per-wave time records of a 17 M-ray
-// launch, tools/wave_times.py: with 1024-ray chunks throughout the waves end anywhere in the last 590 us of 1510, an average wave
-// idles for the last 18 % of the launch; with 128-ray chunks throughout they end within 90 us of each other, but every chunk
-// boundary costs ~5 us of a wave's time — a refill cut short — and the launch is no shorter.)  The cursor of a partition counts
-// chunks, not slots.  false: the partition has no chunk i.
-__device__ __forceinline__ bool chunk_of(const FetchPlan& pl, uint32_t i, uint32_t& start, uint32_t& len)
-{
-    uint32_t rem = pl.psize, base = 0u;
-    const uint32_t e64 = min(rem, pl.lvl); rem -= e64;
-    const uint32_t e128 = min(rem, 2u * pl.lvl); rem -= e128;
-    const uint32_t e256 = min(rem, 4u * pl.lvl); rem -= e256;
-    const uint32_t e512 = min(rem, 8u * pl.lvl); rem -= e512;
-    const uint32_t e1024 = rem;
-#define PT_LEVEL(E, C)                                                                                     \
-    {                                                                                                      \
-        const uint32_t c = min((uint32_t)(C), pl.chunk), cnt = ((E) + c - 1u) / c;                          \
-        if (i < cnt) { start = base + i * c; len = min(c, (E) - i * c); return true; }                      \
-        i -= cnt;                                                                                          \
-        base += (E);                                                                                       \
-    }
-    PT_LEVEL(e1024, 1024u) PT_LEVEL(e512, 512u) PT_LEVEL(e256, 256u) PT_LEVEL(e128, 128u) PT_LEVEL(e64, 64u)
-#undef PT_LEVEL
-    return false;
-}
+// Persistent-thread work fetch: FetchPlan, chunk_of and fetch_plan (pt_queue_plan.h) say which rays are whose; the claims themselves follow.
+// the plan of the launch this thread runs in.  (The launch's shape is read HERE, the block size first: read at the call sites the compiler
+// merged the kernels' two plans differently, and the move of this arithmetic into the header was to leave the generated code as it was.)
 __device__ __forceinline__ FetchPlan fetch_plan(uint32_t n, uint32_t chunk_div, uint32_t taper)
 {
-    FetchPlan pl;
     const uint32_t wpb = blockDim.x >> 6;
-    const uint32_t need_waves = (n + 63u) >> 6;
-    pl.blocks = min(gridDim.x, (need_waves + wpb * (uint32_t)PT_MIN_GENERATIONS - 1u) / (wpb * (uint32_t)PT_MIN_GENERATIONS));
-    const uint32_t waves = max(pl.blocks, 1u) * wpb;
-    uint32_t c = n / (waves * chunk_div);
-    c = c < 64u ? 64u : (c > (uint32_t)PT_CHUNK_MAX ? (uint32_t)PT_CHUNK_MAX : c);
-    pl.chunk = (c + 63u) & ~63u;
-    pl.n = n;
-    const uint64_t st = (uint64_t)waves * pl.chunk;
-    pl.n_static = st >= n ? n : (uint32_t)st;
-    const uint32_t units = (n - pl.n_static + 63u) >> 6;
-    pl.psize = ((units + kQueueHeads - 1u) / kQueueHeads) << 6;
-    // over all partitions the 64-ray level holds PT_TAPER chunks per wave (`taper`; 2 = the current one and the one claimed ahead)
-    pl.lvl = taper ? ((taper * waves * 64u / kQueueHeads + 63u) & ~63u) : 0u;
-    return pl;
+    return pt::fetch_plan(n, chunk_div, taper, gridDim.x, wpb);
 }
 struct WaveRange
 {
@@ -289,23 +212,13 @@ __device__ __forceinline__ void prefetch_claim(WaveRange& wr, uint32_t* heads, c
 // chunk `idx` of partition p, clipped to the queue; false if nothing of it exists
 __device__ __forceinline__ bool take_claim(WaveRange& wr, const FetchPlan& pl, uint32_t p, uint32_t idx)
 {
-    const uint32_t dyn = pl.n - pl.n_static;
-    uint32_t start, len;
-    if (!chunk_of(pl, idx, start, len)) return false;
-    const uint64_t off = (uint64_t)p * pl.psize + start;
-    if (off >= dyn) return false;
-    const uint64_t stop = min(off + len, (uint64_t)dyn);
-    wr.cur = pl.n_static + (uint32_t)off;
-    wr.end = pl.n_static + (uint32_t)stop;
-    return true;
+    return claim_range(pl, p, idx, wr.cur, wr.end);
 }
 __device__ __forceinline__ WaveRange first_range(const FetchPlan& pl, uint32_t* heads)
 {
     const uint32_t wave = blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); // wave-uniform: keep the range in SGPRs
-    const uint64_t lo = (uint64_t)wave * pl.chunk;
     WaveRange wr;
-    wr.cur = lo >= pl.n_static ? pl.n : (uint32_t)lo;
-    wr.end = lo >= pl.n_static ? pl.n : (uint32_t)min((uint64_t)pl.n_static, lo + pl.chunk);
+    static_range(pl, wave, wr.cur, wr.end);
     wr.home = (wave * 7u) & (kQueueHeads - 1u); // neighbouring waves start on different cursors
     wr.drained = pl.n_static >= pl.n;            // nothing is handed out dynamically
     wr.nx_valid = false;
@@ -382,13 +295,6 @@ __device__ __forceinline__ void add_tally(uint32_t* heads, uint32_t per_lane, ui
 enum : uint32_t { PRIMARY_MISS = 0xffu /* PathState::occl: the camera ray left the scene at once (radiance = ambient) */ };
 enum : uint32_t { HOLE = 0xffffffffu, PATH_ENDS = 0x80000000u /* shadow-ray path ids: see k_any */ };
 struct Region { uint32_t cur, end; };
-// `least`: the most one reservation has to take in one go (64 for a wave, 256 for a workgroup)
-__device__ __forceinline__ uint32_t region_size(uint32_t n_in, uint32_t producers, uint32_t least)
-{
-    uint32_t r = n_in / (max(producers, 1u) * (uint32_t)PT_REGION_DIV);
-    r = r < least ? least : (r > kQueueDumpSlots ? (uint32_t)kQueueDumpSlots : r);
-    return (r + 63u) & ~63u;
-}
 // one thread: next region of `rsize` slots, or the dump area when the queue is full
 __device__ __forceinline__ uint32_t next_region(const Region& rg, uint32_t* counter, uint32_t rsize, uint32_t cap, uint32_t* overflow)
 {
@@ -420,29 +326,15 @@ __device__ __forceinline__ Placement wave_reserve(Region& rg, uint32_t* counter,
     return p;
 }
 
-// ---- striped tails (pt_types.h): the same region scheme with the reservations spread over up to 64 tail words
-struct Stripes { uint32_t log_r, log_k; }; // region = 1 << log_r slots, 1 << log_k stripes
-// `n_key` = slots of the bounce's closest-hit input queue: what the producers (k_closest) and the consumers (k_shade_surface) of the
-// bounce's shade queues both know.  Regions of n_key / (4096 * PT_STRIPE_DIV) slots rounded down to a power of two in [64, 8192]
-// (4096 = the traversal waves of a full launch); about PT_REGIONS_PER_STRIPE regions per stripe, so a short queue has one tail
-// and no gaps at all, a long one 64.
-__device__ __forceinline__ Stripes stripes_for(uint32_t n_key)
-{
-    const uint32_t want = n_key / (4096u * (uint32_t)PT_STRIPE_DIV);
-    Stripes st;
-    st.log_r = want < 64u ? 6u : min(13u, 31u - (uint32_t)__clz(want));
-    const uint32_t per = (n_key >> st.log_r) / (uint32_t)PT_REGIONS_PER_STRIPE;
-    st.log_k = per == 0u ? 0u : min(6u, 31u - (uint32_t)__clz(per));
-    return st;
-}
+// ---- striped tails (pt_types.h): the same region scheme with the reservations spread over up to 64 tail words (Stripes, stripes_for: pt_queue_plan.h)
 // one thread: the next region of stripe `rot & (K - 1)`, or the dump area when the queue is full
 __device__ __forceinline__ uint32_t next_region_striped(const Region& rg, uint32_t* tails, const Stripes st, uint32_t rot, uint32_t cap, uint32_t* overflow)
 {
     if (rg.end > cap) return cap; // already diverted: stay in the dump area
     const uint32_t k = rot & ((1u << st.log_k) - 1u);
     const uint32_t r = atomicAdd(tails + k * kTailStrideWords, 1u);
-    const uint64_t base = (((uint64_t)r << st.log_k) | k) << st.log_r;
-    if (base + (1ull << st.log_r) > (uint64_t)cap)
+    const uint64_t base = stripe_region_base(st, r, k);
+    if (!stripe_region_fits(st, base, cap))
     {
         __hip_atomic_store(overflow, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         return cap;
@@ -471,19 +363,10 @@ __device__ __forceinline__ uint32_t stripe_load(const uint32_t* tails, const Str
 {
     const uint32_t l = lane_id();
     my_tail = l < (1u << st.log_k) ? tails[l * kTailStrideWords] : 0u;
-    uint64_t e = my_tail != 0u ? (((((uint64_t)(my_tail - 1u)) << st.log_k) | l) + 1ull) << st.log_r : 0ull;
-    e = e > (uint64_t)cap ? (uint64_t)cap : e;
-    uint32_t ext = (uint32_t)e;
+    uint32_t ext = stripe_extent(st, l, my_tail, cap);
     for (int off = 32; off > 0; off >>= 1) ext = max(ext, (uint32_t)__shfl_xor((int)ext, off));
     return ext;
 }
-// does slot `idx` lie in a region that some producer reserved?  `tail_of` = the 64 tails (LDS)
-__device__ __forceinline__ bool stripe_valid(const uint32_t* tail_of, const Stripes st, uint32_t idx)
-{
-    const uint32_t g = idx >> st.log_r;
-    return (g >> st.log_k) < tail_of[g & ((1u << st.log_k) - 1u)];
-}
-
 // Block-wide queue append for up to four queues at once: the workgroup reserves EXACTLY what it appends, one atomic per queue and
 // call (two barriers).  Regions per workgroup, as the traversal waves use them, were tried first (region = slots_in / (workgroups * 16),
 // at least 256): fewer atomics, but whatever 3072 workgroups leave of their last regions are holes in the next launch's queue — for
@@ -1636,20 +1519,7 @@ __device__ __forceinline__ uint32_t global_row(const RenderParams& rp, uint32_t 
     const uint32_t strip = fastdiv(ly, rp.div_strip_rows);
     return (strip * rp.world_size + rp.rank) * rp.strip_rows + (ly - strip * rp.strip_rows);
 }
-// path id <-> (batch-local sample, index of the pixel in the active rectangle): RenderParams::blk_log
-struct PidParts { uint32_t s, k; };
-__device__ __forceinline__ PidParts pid_split(const RenderParams& rp, uint32_t pid)
-{
-    const uint32_t b = fastdiv(pid, rp.div_blk_paths), rem = pid - b * (rp.act_pixels << rp.blk_log);
-    const bool short_blk = b + 1u == rp.n_blk;   // (the last block; blk_last == 1 << blk_log when it is a full one: both branches then agree)
-    const uint32_t k = short_blk ? fastdiv(rem, rp.div_blk_last) : (rem >> rp.blk_log);
-    return PidParts{(b << rp.blk_log) + (rem - k * (short_blk ? rp.blk_last : (1u << rp.blk_log))), k};
-}
-__device__ __forceinline__ uint32_t pid_join(const RenderParams& rp, uint32_t s, uint32_t k)
-{
-    const uint32_t b = s >> rp.blk_log;
-    return b * (rp.act_pixels << rp.blk_log) + k * (b + 1u == rp.n_blk ? rp.blk_last : (1u << rp.blk_log)) + (s - (b << rp.blk_log));
-}
+// path id <-> (batch-local sample, index of the pixel in the active rectangle): pid_split, pid_join (pt_queue_plan.h)
 __device__ __forceinline__ PixelId path_pixel(const RenderParams& rp, uint32_t pid, uint32_t* s_local = nullptr, uint32_t* k_out = nullptr)
 {
     const PidParts pp = pid_split(rp, pid);

@@ -270,14 +270,19 @@ def test_checkpoint_restores_into_a_fresh_context(api, oracle_mod):
     assert_bit_equal(c.read_frame()[0], oa, "accumulation alone")
 
 
-def test_empty_and_edge_inputs(api, cornell64):
+def test_empty_and_edge_inputs(api, oracle_mod, cornell64):
     r = api.Renderer(cornell64, 64, 64)
     z = np.zeros((0, 3), np.float32)
     assert r.trace_closest(z, z)["t"].shape == (0,)
     acc, _, _ = r.render(0, 0)
     assert (acc == 0).all()
     one = api.Renderer(cornell64, 1, 1, max_bounces=2)
-    assert one.render(0, 3)[0][0, 0, 3] == 3
+    acc, pos, idb = one.render(0, 3)
+    assert acc[0, 0, 3] == 3
+    oacc, opos, oid, octr = oracle_mod.Oracle(cornell64).render(1, 1, 3, max_bounces=2)   # one pixel: one path id per sample, a single short block
+    assert_bit_equal(acc, oacc, "1 x 1 accumulation"); assert_bit_equal(pos, opos, "1 x 1 position"); assert np.array_equal(idb, oid)
+    st = one.stats()
+    assert (st.rays_closest, st.rays_any, st.rays_light_closest) == (int(octr[0]), int(octr[1]), int(octr[2]))
     empty_rank = api.Renderer(cornell64, 8, 4, rank=1, world_size=2, strip_rows=4)   # a rank that owns no row
     assert empty_rank.render(0, 2)[0].shape == (0, 8, 4)
 
