@@ -1332,8 +1332,8 @@ int pt_probe_radiance_prefilter(pt_ctx* ctx, int on_device, const pt_probe_radia
  *     B = R_H * S   where THE SPECULAR LOOKUP is lit at P = the position and n = the normal that pt_render_guides_followed writes for that
  *     chain's end, d = the direction of the chain's last ray and a = the material's GGX alpha (roughness squared, clamped to 0.0001..0.9999)
  * before any map is asked: a map holds irradiance, which a metal does not reflect diffusely.  Where the lookup is not lit the ending is what it
- * is without radiance, and every other kind is untouched.  The endings are kernels of their own (k_baked_follow_probes_spec[_vis]), chosen on
- * the host: without radiance every call launches what it launched and returns the bits it returned before.
+ * is without radiance, and every other kind is untouched.  The endings are instantiations of their own (the SPEC axis of k_baked_follow), chosen
+ * on the host: without radiance every call launches what it launched and returns the bits it returned before.
  * Out of scope: bilinear filtering across texels and fold lines, a Fresnel or environment-BRDF term, PT_GGX_DIELECTRIC, lobes that depend on
  * the view angle, maps above 16 x 16, per-texel stratified rays, parallax correction, pt_multi_* variants, probes in the path tracer's own
  * paths. */

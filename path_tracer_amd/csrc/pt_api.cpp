@@ -81,6 +81,16 @@ struct DevBuf : Owned<void*, hipFree>
     DevBuf(DevBuf&& o) noexcept : Owned(std::move(o)), bytes(std::exchange(o.bytes, 0)) {}
     void reset() { Owned::reset(); bytes = 0; }
 };
+// A table the context keeps on the host as the device gets it (empty: not set) and its copy on the device: `valid` says that `dev` holds the
+// table as it was at `version` of whatever counts the table's changes (ensure_mirror uploads it when that has moved on)
+template <class T>
+struct Mirror
+{
+    std::vector<T> host;
+    DevBuf dev;
+    bool valid = false;
+    uint64_t version = 0;
+};
 
 } // namespace
 
@@ -196,9 +206,7 @@ struct pt_ctx
     std::vector<std::vector<Lightmap>> lightmaps;
     uint64_t lightmap_texels = 0, lightmap_version = 0;
     DevBuf d_lm_texels, d_lm_leaf, d_lm_uv, d_lm_grad, d_lm_leaf_dir;
-    LmDirView ld{};
     bool lm_dir = false;
-    LmView lm{};
     bool lm_valid = false;
     uint64_t lm_version = 0, lm_upload = 0;
     // the baked view (pt_render_baked): sum r, g, b | n per local pixel, traced through the guides' hook queues, and what the sums belong
@@ -208,27 +216,19 @@ struct pt_ctx
     uint64_t baked_scene_version = 0, baked_config_version = 0, baked_lm_version = 0;
     uint32_t baked_max_hops = 0, baked_unlit[3] = {0, 0, 0};
     // the probe grid (pt_set_probe_grid): world-space data that no scene call touches.  probes: the records as the device gets them (empty: no
-    // grid); probe_version counts the grid's changes (the baked sums keep the one they were made under); pg_version: the one on the device.
+    // grid); probe_version counts the grid's changes (the baked sums keep the one they were made under, each table's Mirror the one on the device).
     pt_probe_grid probe_grid{};
-    std::vector<DProbe> probes;
+    Mirror<DProbe> probes;
     uint32_t probes_valid = 0;
-    uint64_t probe_version = 0, baked_probe_version = 0, pg_version = 0;
-    DevBuf d_probes;
-    bool pg_valid = false;
+    uint64_t probe_version = 0, baked_probe_version = 0;
     // probe visibility (pt_set_probe_grid_depth): the nodes' depth moments as the device gets them (empty: none), which belong to the grid in
-    // force: any pt_set_probe_grid drops them, and a change of theirs counts in probe_version too.  pd_version: the one on the device.
+    // force: any pt_set_probe_grid drops them, and a change of theirs counts in probe_version too.
     pt_probe_depth probe_depth{};
-    std::vector<DProbeDepth> probe_moments;
-    uint64_t pd_version = 0;
-    DevBuf d_probe_moments;
-    bool pd_valid = false;
+    Mirror<DProbeDepth> probe_moments;
     // reflection probes (pt_set_probe_grid_radiance): the nodes' prefiltered radiance maps as the device gets them (empty: none), which belong
-    // to the grid in force exactly as the depth moments do.  pr_version: the one on the device.
+    // to the grid in force exactly as the depth moments do.
     pt_probe_radiance probe_radiance{};
-    std::vector<f4> probe_radiance_table;
-    uint64_t pr_version = 0;
-    DevBuf d_probe_radiance;
-    bool pr_valid = false;
+    Mirror<f4> probe_radiance_table;
 
     // pt_frame_moving: the forward instance matrices, per model, of the build in force when the previous call returned PT_OK (the snapshot)
     // and the build it was taken from (a call on that very build has nothing to compare); the motion table and x_prev on the device.
@@ -1554,10 +1554,8 @@ std::vector<uint32_t> leaf_ordinals(const HostScene& sc)
 // The lightmap tables of the resident scene (after upload_scene), uploaded when the maps or the resident scene changed since: a record per
 // world-TLAS leaf, the texels of the maps in use one after the other, and the leaf-order UVs of the models that carry a map, unless the
 // scene is textured: then TexView's table holds every model's UVs already.
-int ensure_lightmaps(pt_ctx* c)
+int upload_lightmaps(pt_ctx* c, uint64_t upload)
 {
-    const uint64_t upload = c->uploads_full + c->uploads_patched;
-    if (c->lm_valid && c->lm_version == c->lightmap_version && c->lm_upload == upload) return PT_OK;
     c->lm_valid = false;
     const HostScene& sc = c->scene;
     const FlatScene& f = sc.flat;
@@ -1618,75 +1616,85 @@ int ensure_lightmaps(pt_ctx* c)
     HIPCHK(c, hipMemcpy(c->d_lm_leaf.p, leaf.data(), leaf.size() * sizeof(DLightmap), hipMemcpyHostToDevice));
     if (!texels.empty()) HIPCHK(c, hipMemcpy(c->d_lm_texels.p, texels.data(), texels.size() * sizeof(f4), hipMemcpyHostToDevice));
     if (!uvs.empty()) HIPCHK(c, hipMemcpy(c->d_lm_uv.p, uvs.data(), uvs.size() * sizeof(DTriUV), hipMemcpyHostToDevice));
-    c->lm = LmView{(const f4*)c->d_lm_texels.p, (const DLightmap*)c->d_lm_leaf.p, c->tex.tri_uv ? c->tex.tri_uv : (const DTriUV*)c->d_lm_uv.p};
-    c->ld = LmDirView{};
     c->lm_dir = !dirs.empty();
     if (c->lm_dir)
     {
         HIPCHK(c, hipMemcpy(c->d_lm_grad.p, grad.data(), grad.size() * sizeof(f4), hipMemcpyHostToDevice));
         HIPCHK(c, hipMemcpy(c->d_lm_leaf_dir.p, leaf_dir.data(), leaf_dir.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        c->ld = LmDirView{(const f4*)c->d_lm_grad.p, (const uint32_t*)c->d_lm_leaf_dir.p};
     }
     c->lm_valid = true;
     c->lm_version = c->lightmap_version;
     c->lm_upload = upload;
     return PT_OK;
 }
+// ... and the views over them, the tables uploaded first where they are stale (ld: null without a gradient in use)
+int ensure_lightmaps(pt_ctx* c, LmView& lm, LmDirView& ld)
+{
+    const uint64_t upload = c->uploads_full + c->uploads_patched;
+    int r;
+    if (!(c->lm_valid && c->lm_version == c->lightmap_version && c->lm_upload == upload) && (r = upload_lightmaps(c, upload))) return r;
+    lm = LmView{(const f4*)c->d_lm_texels.p, (const DLightmap*)c->d_lm_leaf.p, c->tex.tri_uv ? c->tex.tri_uv : (const DTriUV*)c->d_lm_uv.p};
+    ld = c->lm_dir ? LmDirView{(const f4*)c->d_lm_grad.p, (const uint32_t*)c->d_lm_leaf_dir.p} : LmDirView{};
+    return PT_OK;
+}
 
-// ---- the probe grid kept by the context (pt_set_probe_grid; the lookup is pt_probe.h's)
-// what the lookup reads, over the records at `nodes`: the host's copy or the device table
+// ---- the probe grid kept by the context (pt_set_probe_grid; the lookups are pt_probe.h's)
+// what the lookups read, over the host's tables or the device's: the grid, its depth moments (pt_set_probe_grid_depth) and its prefiltered
+// radiance maps (pt_set_probe_grid_radiance)
 ProbeGridView probe_grid_view(const pt_ctx* c, const DProbe* nodes)
 {
     const pt_probe_grid& g = c->probe_grid;
     return ProbeGridView{nodes, {g.origin[0], g.origin[1], g.origin[2]}, {g.cell[0], g.cell[1], g.cell[2]}, {g.count[0], g.count[1], g.count[2]}, g.normal_bias};
 }
-// The grid's device table (after ensure_device), uploaded when the grid changed since; only called with a grid set.
-int ensure_probe_grid(pt_ctx* c)
-{
-    if (c->pg_valid && c->pg_version == c->probe_version) return PT_OK;
-    c->pg_valid = false;
-    int r;
-    HIPCHK(c, hipStreamSynchronize(c->stream)); // an earlier call may still be reading the table
-    if ((r = dev_alloc(c, c->d_probes, c->probes.size() * sizeof(DProbe)))) return r;
-    HIPCHK(c, hipMemcpy(c->d_probes.p, c->probes.data(), c->probes.size() * sizeof(DProbe), hipMemcpyHostToDevice));
-    c->pg_valid = true;
-    c->pg_version = c->probe_version;
-    return PT_OK;
-}
-// ... and the depth moments' table beside it (pt_set_probe_grid_depth), by the same pattern; only called with depth set
 ProbeDepthView probe_depth_view(const pt_ctx* c, const DProbeDepth* moments)
 {
     return ProbeDepthView{moments, c->probe_depth.res, c->probe_depth.flags & PT_PROBE_VIS_FACING, c->probe_depth.vis_floor};
 }
-int ensure_probe_depth(pt_ctx* c)
-{
-    if (c->pd_valid && c->pd_version == c->probe_version) return PT_OK;
-    c->pd_valid = false;
-    int r;
-    HIPCHK(c, hipStreamSynchronize(c->stream)); // an earlier call may still be reading the table
-    if ((r = dev_alloc(c, c->d_probe_moments, c->probe_moments.size() * sizeof(DProbeDepth)))) return r;
-    HIPCHK(c, hipMemcpy(c->d_probe_moments.p, c->probe_moments.data(), c->probe_moments.size() * sizeof(DProbeDepth), hipMemcpyHostToDevice));
-    c->pd_valid = true;
-    c->pd_version = c->probe_version;
-    return PT_OK;
-}
-// ... and the prefiltered radiance maps (pt_set_probe_grid_radiance), by the same pattern; only called with radiance set
 ProbeRadianceView probe_radiance_view(const pt_ctx* c, const f4* table)
 {
     ProbeRadianceView v{table, c->probe_radiance.res, c->probe_radiance.n_levels, {}};
     for (int l = 0; l < 8; ++l) v.alpha[l] = c->probe_radiance.alpha[l];
     return v;
 }
-int ensure_probe_radiance(pt_ctx* c)
+// One of the three tables on the device (after ensure_device), uploaded when the grid changed since; only called with the table set.
+template <class T>
+int ensure_mirror(pt_ctx* c, Mirror<T>& m)
 {
-    if (c->pr_valid && c->pr_version == c->probe_version) return PT_OK;
-    c->pr_valid = false;
+    if (m.valid && m.version == c->probe_version) return PT_OK;
+    m.valid = false;
     int r;
     HIPCHK(c, hipStreamSynchronize(c->stream)); // an earlier call may still be reading the table
-    if ((r = dev_alloc(c, c->d_probe_radiance, c->probe_radiance_table.size() * sizeof(f4)))) return r;
-    HIPCHK(c, hipMemcpy(c->d_probe_radiance.p, c->probe_radiance_table.data(), c->probe_radiance_table.size() * sizeof(f4), hipMemcpyHostToDevice));
-    c->pr_valid = true;
-    c->pr_version = c->probe_version;
+    if ((r = dev_alloc(c, m.dev, m.host.size() * sizeof(T)))) return r;
+    HIPCHK(c, hipMemcpy(m.dev.p, m.host.data(), m.host.size() * sizeof(T), hipMemcpyHostToDevice));
+    m.valid = true;
+    m.version = c->probe_version;
+    return PT_OK;
+}
+// The one place that says what lights a final surface of the baked view: light <- the views, key <- the ending's axes (pt_kernels.h).  The
+// grid's unit hooks take their views from it too.  LIGHT_GRID_HOST: the grid's three over the host's tables, nothing uploaded; LIGHT_GRID: over
+// the device's (after ensure_device), uploaded where stale; LIGHT_ALL: with the lightmaps' tables as well (after upload_scene) and the DIR axis
+enum LightOf { LIGHT_GRID_HOST, LIGHT_GRID, LIGHT_ALL };
+int baked_light(pt_ctx* c, LightOf what, BakedLight& light, BakedKey& key)
+{
+    light = BakedLight{};
+    key = BakedKey{};
+    int r;
+    if (what == LIGHT_ALL)
+    {
+        if ((r = ensure_lightmaps(c, light.lm, light.ld))) return r;
+        // the DIR endings only where they can differ: a gradient in use and a normal-mapped material in the built scene
+        key.dir = c->lm_dir && c->scene.flat.has_normal_maps;
+    }
+    key.grid = !c->probes.host.empty();
+    key.vis = key.grid && !c->probe_moments.host.empty();
+    key.spec = key.grid && !c->probe_radiance_table.host.empty();
+    const bool dev = what != LIGHT_GRID_HOST;
+    if (dev && ((key.grid && (r = ensure_mirror(c, c->probes))) || (key.vis && (r = ensure_mirror(c, c->probe_moments))) ||
+                (key.spec && (r = ensure_mirror(c, c->probe_radiance_table)))))
+        return r;
+    if (key.grid) light.grid = probe_grid_view(c, dev ? (const DProbe*)c->probes.dev.p : c->probes.host.data());
+    if (key.vis) light.depth = probe_depth_view(c, dev ? (const DProbeDepth*)c->probe_moments.dev.p : c->probe_moments.host.data());
+    if (key.spec) light.rad = probe_radiance_view(c, dev ? (const f4*)c->probe_radiance_table.dev.p : c->probe_radiance_table.host.data());
     return PT_OK;
 }
 
@@ -3132,40 +3140,19 @@ int follow_chains(pt_ctx* c, uint32_t sample, uint32_t max_hops, f4* sum)
         launch_guide_follow(c->stream, c->sv, c->tex, a);
     });
 }
-// ... and the baked view's chains (pt_render_baked): the same walk, ended by launch_baked_follow into the baked sums, or by the probe ending
-// while a grid is set (pt_set_probe_grid), over the lookup with visibility while the grid has depth (pt_set_probe_grid_depth), and by the
-// ending whose GGX metal reflects the grid's prefiltered radiance while it has some (pt_set_probe_grid_radiance)
-int baked_chains(pt_ctx* c, uint32_t sample, const pt_baked_params& p)
+// ... and the baked view's chains (pt_render_baked): the same walk, ended by launch_baked_follow into the baked sums under the ending that
+// baked_light decided for the call
+int baked_chains(pt_ctx* c, uint32_t sample, const pt_baked_params& p, const BakedLight& light, const BakedKey& key)
 {
-    const bool grid = !c->probes.empty(), depth = grid && !c->probe_moments.empty(), radiance = grid && !c->probe_radiance_table.empty();
     EnvView env{};
     if (c->env_w) env = EnvView{(const f4*)c->d_env.p, c->env_w, c->env_h, 0u, 0u};
-    // the DIR endings only where they can differ: a gradient in use and a normal-mapped material in the built scene
-    const bool dir = c->lm_dir && c->scene.flat.has_normal_maps;
     return walk_chains(c, sample, p.max_hops, [&](const ChainHop& q) {
         BakedArgs b{};
         static_cast<ChainHop&>(b) = q;
         b.sum = (f4*)c->d_baked_sum.p;
         b.env = env;
         std::memcpy(b.unlit, p.unlit, sizeof(b.unlit));
-        if (dir)
-        {
-            const ProbeGridView gv = grid ? probe_grid_view(c, (const DProbe*)c->d_probes.p) : ProbeGridView{};
-            const ProbeDepthView dv = depth ? probe_depth_view(c, (const DProbeDepth*)c->d_probe_moments.p) : ProbeDepthView{};
-            const ProbeRadianceView rv = radiance ? probe_radiance_view(c, (const f4*)c->d_probe_radiance.p) : ProbeRadianceView{};
-            launch_baked_follow_directional(c->stream, c->sv, c->tex, c->lm, c->ld, b, grid ? &gv : nullptr, depth ? &dv : nullptr, radiance ? &rv : nullptr);
-        }
-        else if (radiance)
-        {
-            const ProbeDepthView dv = probe_depth_view(c, (const DProbeDepth*)c->d_probe_moments.p);
-            launch_baked_follow_probes_spec(c->stream, c->sv, c->tex, c->lm, b, probe_grid_view(c, (const DProbe*)c->d_probes.p), depth ? &dv : nullptr,
-                                            probe_radiance_view(c, (const f4*)c->d_probe_radiance.p));
-        }
-        else if (depth)
-            launch_baked_follow_probes_vis(c->stream, c->sv, c->tex, c->lm, b, probe_grid_view(c, (const DProbe*)c->d_probes.p),
-                                           probe_depth_view(c, (const DProbeDepth*)c->d_probe_moments.p));
-        else if (grid) launch_baked_follow_probes(c->stream, c->sv, c->tex, c->lm, b, probe_grid_view(c, (const DProbe*)c->d_probes.p));
-        else launch_baked_follow(c->stream, c->sv, c->tex, c->lm, b);
+        launch_baked_follow(c->stream, c->sv, c->tex, light, key, b);
     });
 }
 
@@ -3911,14 +3898,14 @@ int pt_get_lightmap_directional_info(pt_ctx* c, int model, uint32_t instance, ui
     return PT_OK;
 }
 
-int pt_lightmap_lookup_directional(pt_ctx* c, int on_device, uint32_t n, const uint32_t* instance, const uint32_t* prim, const float* u, const float* v,
-                                   const float* dir_xyz, float* rgb, uint8_t* mapped)
+// pt_lightmap_lookup and pt_lightmap_lookup_directional under the context's lock.  directional: dir_xyz must be there and a map with a gradient
+// is read through it; else dir_xyz is null and every map is read as the scalar map it is
+static int lightmap_lookup_locked(pt_ctx* c, int on_device, bool directional, uint32_t n, const uint32_t* instance, const uint32_t* prim, const float* u, const float* v,
+                                  const float* dir_xyz, float* rgb, uint8_t* mapped)
 {
-    if (!c) return PT_ERR_ARG;
-    std::lock_guard<std::mutex> lk(c->mu);
     if (!c->scene.built) return fail(c, PT_ERR_STATE, "pt_build has not been called");
     if (n == 0) return PT_OK;
-    if (!instance || !prim || !u || !v || !dir_xyz || !rgb || !mapped) return fail(c, PT_ERR_ARG, "null pointer");
+    if (!instance || !prim || !u || !v || (directional && !dir_xyz) || !rgb || !mapped) return fail(c, PT_ERR_ARG, "null pointer");
     std::vector<uint32_t> tri;
     int r;
     if ((r = leaf_order_tris(c, n, instance, prim, tri))) return r;
@@ -3936,7 +3923,7 @@ int pt_lightmap_lookup_directional(pt_ctx* c, int on_device, uint32_t n, const u
             {
                 const float* p = &c->scene.models[mi].uvs[(size_t)prim[i] * 6];
                 const DTriUV uv{{p[0], p[1]}, {p[2], p[3]}, {p[4], p[5]}};
-                if (l->grad.empty()) col = lightmap_lookup(l->texels.data(), l->w, l->h, uv, u[i], v[i]);
+                if (!directional || l->grad.empty()) col = lightmap_lookup(l->texels.data(), l->w, l->h, uv, u[i], v[i]);
                 else
                 {
                     const f3 d{dir_xyz[3 * (size_t)i], dir_xyz[3 * (size_t)i + 1], dir_xyz[3 * (size_t)i + 2]};
@@ -3952,58 +3939,34 @@ int pt_lightmap_lookup_directional(pt_ctx* c, int on_device, uint32_t n, const u
         }
         return PT_OK;
     }
-    if ((r = upload_scene(c)) || (r = ensure_lightmaps(c))) return r;
+    LmView lm;
+    LmDirView ld;
+    if ((r = upload_scene(c)) || (r = ensure_lightmaps(c, lm, ld))) return r;
     Staging st(c);
     const SurfaceQueries q = upload_queries(st, n, instance, tri, u, v);
-    const float* d_dir = (const float*)st.in(dir_xyz, (size_t)n * 12);
+    const float* d_dir = directional ? (const float*)st.in(dir_xyz, (size_t)n * 12) : nullptr;
     float* d_rgb = (float*)st.out((size_t)n * 12);
     uint8_t* d_mapped = (uint8_t*)st.out(n);
     if (st.err) return st.err;
-    launch_lightmap_lookup_directional(c->stream, c->sv, c->tex, c->lm, c->ld, n, q.instance, q.tri, q.u, q.v, d_dir, d_rgb, d_mapped);
+    if (directional) launch_lightmap_lookup_directional(c->stream, c->sv, c->tex, lm, ld, n, q.instance, q.tri, q.u, q.v, d_dir, d_rgb, d_mapped);
+    else launch_lightmap_lookup(c->stream, lm, n, q.instance, q.tri, q.u, q.v, d_rgb, d_mapped);
     HIPCHK(c, hipGetLastError());
     if ((r = st.download(rgb, d_rgb, (size_t)n * 12))) return r;
     return st.download(mapped, d_mapped, n);
 }
-
+int pt_lightmap_lookup_directional(pt_ctx* c, int on_device, uint32_t n, const uint32_t* instance, const uint32_t* prim, const float* u, const float* v,
+                                   const float* dir_xyz, float* rgb, uint8_t* mapped)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    return lightmap_lookup_locked(c, on_device, true, n, instance, prim, u, v, dir_xyz, rgb, mapped);
+}
 int pt_lightmap_lookup(pt_ctx* c, int on_device, uint32_t n, const uint32_t* instance, const uint32_t* prim, const float* u, const float* v, float* rgb,
                        uint8_t* mapped)
 {
     if (!c) return PT_ERR_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
-    if (!c->scene.built) return fail(c, PT_ERR_STATE, "pt_build has not been called");
-    if (n == 0) return PT_OK;
-    if (!instance || !prim || !u || !v || !rgb || !mapped) return fail(c, PT_ERR_ARG, "null pointer");
-    std::vector<uint32_t> tri;
-    int r;
-    if ((r = leaf_order_tris(c, n, instance, prim, tri))) return r;
-    if (!on_device)
-    {
-        const std::vector<uint32_t> ordinal = leaf_ordinals(c->scene);
-        for (uint32_t i = 0; i < n; ++i)
-        {
-            const uint32_t mi = c->scene.world.instances[instance[i]].model;
-            const pt_ctx::Lightmap* l = lightmap_of(c, mi, ordinal[instance[i]]);
-            f3 col{0.0f, 0.0f, 0.0f};
-            if (l)
-            {
-                const float* p = &c->scene.models[mi].uvs[(size_t)prim[i] * 6];
-                col = lightmap_lookup(l->texels.data(), l->w, l->h, DTriUV{{p[0], p[1]}, {p[2], p[3]}, {p[4], p[5]}}, u[i], v[i]);
-            }
-            rgb[3 * (size_t)i] = col.x; rgb[3 * (size_t)i + 1] = col.y; rgb[3 * (size_t)i + 2] = col.z;
-            mapped[i] = l ? 1u : 0u;
-        }
-        return PT_OK;
-    }
-    if ((r = upload_scene(c)) || (r = ensure_lightmaps(c))) return r;
-    Staging st(c);
-    const SurfaceQueries q = upload_queries(st, n, instance, tri, u, v);
-    float* d_rgb = (float*)st.out((size_t)n * 12);
-    uint8_t* d_mapped = (uint8_t*)st.out(n);
-    if (st.err) return st.err;
-    launch_lightmap_lookup(c->stream, c->lm, n, q.instance, q.tri, q.u, q.v, d_rgb, d_mapped);
-    HIPCHK(c, hipGetLastError());
-    if ((r = st.download(rgb, d_rgb, (size_t)n * 12))) return r;
-    return st.download(mapped, d_mapped, n);
+    return lightmap_lookup_locked(c, on_device, false, n, instance, prim, u, v, nullptr, rgb, mapped);
 }
 
 // the baked sums exist and belong to what is in force: what keeps the guides current, the lightmaps and the probe grid
@@ -4027,10 +3990,9 @@ int pt_render_baked(pt_ctx* c, uint32_t first_sample, uint32_t n_samples, const 
     if (!c->scene.built) return fail(c, PT_ERR_STATE, "pt_build has not been called");
     if (!c->scene.camera.set) return fail(c, PT_ERR_STATE, "pt_set_camera has not been called");
     int r;
-    if ((r = upload_scene(c)) || (r = ensure_environment(c)) || (r = ensure_lightmaps(c))) return r;
-    if (!c->probes.empty() && (r = ensure_probe_grid(c))) return r;
-    if (!c->probe_moments.empty() && (r = ensure_probe_depth(c))) return r;
-    if (!c->probe_radiance_table.empty() && (r = ensure_probe_radiance(c))) return r;
+    BakedLight light;
+    BakedKey key;
+    if ((r = upload_scene(c)) || (r = ensure_environment(c)) || (r = baked_light(c, LIGHT_ALL, light, key))) return r;
     const uint32_t px = c->local_pixels;
     const size_t n = std::max<uint32_t>(px, 1);
     if ((r = guide_scratch(c, p->max_hops)) || (r = dev_alloc(c, c->d_baked_sum, n * 16))) return r;
@@ -4042,7 +4004,7 @@ int pt_render_baked(pt_ctx* c, uint32_t first_sample, uint32_t n_samples, const 
     if (px)
     {
         for (uint32_t k = 0; k < n_samples; ++k)
-            if ((r = baked_chains(c, first_sample + k, *p))) return r;
+            if ((r = baked_chains(c, first_sample + k, *p, light, key))) return r;
         HIPCHK(c, hipGetLastError());
         if (rgbn) HIPCHK(c, hipMemcpyAsync(rgbn, c->d_baked_sum.p, (size_t)px * 16, hipMemcpyDeviceToHost, c->stream));
     }
@@ -4094,12 +4056,12 @@ int pt_write_baked_image(pt_ctx* c, const char* path)
 // ---- the probe grid and the census of probes inside geometry (the definitions are include/pt_api.h's)
 static void drop_probe_depth(pt_ctx* c)
 {
-    std::vector<DProbeDepth>().swap(c->probe_moments);
+    std::vector<DProbeDepth>().swap(c->probe_moments.host);
     c->probe_depth = pt_probe_depth{};
 }
 static void drop_probe_radiance(pt_ctx* c)
 {
-    std::vector<f4>().swap(c->probe_radiance_table);
+    std::vector<f4>().swap(c->probe_radiance_table.host);
     c->probe_radiance = pt_probe_radiance{};
 }
 int pt_set_probe_grid(pt_ctx* c, const pt_probe_grid* g, const float* sh27, const uint8_t* valid)
@@ -4111,8 +4073,8 @@ int pt_set_probe_grid(pt_ctx* c, const pt_probe_grid* g, const float* sh27, cons
     const bool none = !g->count[0] && !g->count[1] && !g->count[2];
     if (!sh27 && none)
     {
-        if (!c->probes.empty()) c->probe_version++;
-        std::vector<DProbe>().swap(c->probes);
+        if (!c->probes.host.empty()) c->probe_version++;
+        std::vector<DProbe>().swap(c->probes.host);
         drop_probe_depth(c);
         drop_probe_radiance(c);
         c->probe_grid = pt_probe_grid{};
@@ -4143,7 +4105,7 @@ int pt_set_probe_grid(pt_ctx* c, const pt_probe_grid* g, const float* sh27, cons
         rec[i].valid = 1.0f;
         ++n_valid;
     }
-    c->probes.swap(rec);
+    c->probes.host.swap(rec);
     drop_probe_depth(c); // (the node count may have changed)
     drop_probe_radiance(c);
     c->probe_grid = *g;
@@ -4165,38 +4127,33 @@ int pt_probe_grid_lookup(pt_ctx* c, int on_device, uint32_t n, const float* posi
 {
     if (!c) return PT_ERR_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
-    if (c->probes.empty()) return fail(c, PT_ERR_STATE, "no probe grid: pt_set_probe_grid first");
+    if (c->probes.host.empty()) return fail(c, PT_ERR_STATE, "no probe grid: pt_set_probe_grid first");
     if (n == 0) return PT_OK;
     if (!position || !normal || !rgb || !lit) return fail(c, PT_ERR_ARG, "pt_probe_grid_lookup: null pointer");
+    BakedLight l;
+    BakedKey k;
+    int r;
     if (!on_device)
     {
-        const ProbeGridView g = probe_grid_view(c, c->probes.data());
-        const bool vis = !c->probe_moments.empty();
-        const ProbeDepthView dv = probe_depth_view(c, c->probe_moments.data());
+        (void)baked_light(c, LIGHT_GRID_HOST, l, k);
         for (uint32_t i = 0; i < n; ++i)
         {
             const float *pp = position + 3 * (size_t)i, *pn = normal + 3 * (size_t)i;
             const f3 P{pp[0], pp[1], pp[2]}, N{pn[0], pn[1], pn[2]};
             f3 col;
-            lit[i] = (vis ? probe_grid_lookup<true>(g, P, N, &col, &dv) : probe_grid_lookup(g, P, N, &col)) ? 1u : 0u;
+            lit[i] = (k.vis ? probe_grid_lookup<true>(l.grid, P, N, &col, &l.depth) : probe_grid_lookup(l.grid, P, N, &col)) ? 1u : 0u;
             rgb[3 * (size_t)i] = col.x; rgb[3 * (size_t)i + 1] = col.y; rgb[3 * (size_t)i + 2] = col.z;
         }
         return PT_OK;
     }
-    int r;
-    if ((r = ensure_device(c)) || (r = ensure_probe_grid(c))) return r;
-    const bool vis = !c->probe_moments.empty();
-    if (vis && (r = ensure_probe_depth(c))) return r;
+    if ((r = ensure_device(c)) || (r = baked_light(c, LIGHT_GRID, l, k))) return r;
     Staging st(c);
     const float* d_pos = (const float*)st.in(position, (size_t)n * 12);
     const float* d_nrm = (const float*)st.in(normal, (size_t)n * 12);
     float* d_rgb = (float*)st.out((size_t)n * 12);
     uint8_t* d_lit = (uint8_t*)st.out(n);
     if (st.err) return st.err;
-    if (vis)
-        launch_probe_grid_lookup_vis(c->stream, probe_grid_view(c, (const DProbe*)c->d_probes.p), probe_depth_view(c, (const DProbeDepth*)c->d_probe_moments.p), n,
-                                     d_pos, d_nrm, d_rgb, d_lit);
-    else launch_probe_grid_lookup(c->stream, probe_grid_view(c, (const DProbe*)c->d_probes.p), n, d_pos, d_nrm, d_rgb, d_lit);
+    launch_probe_grid_lookup(c->stream, l.grid, k.vis ? &l.depth : nullptr, n, d_pos, d_nrm, d_rgb, d_lit);
     HIPCHK(c, hipGetLastError());
     if ((r = st.download(rgb, d_rgb, (size_t)n * 12))) return r;
     return st.download(lit, d_lit, n);
@@ -4319,10 +4276,10 @@ int pt_set_probe_grid_depth(pt_ctx* c, const pt_probe_depth* v, const float* mom
     if (!v) return fail(c, PT_ERR_ARG, "pt_set_probe_grid_depth: v must not be NULL");
     for (uint32_t w : v->reserved)
         if (w) return fail(c, PT_ERR_ARG, "pt_probe_depth.reserved must be 0");
-    if (c->probes.empty()) return fail(c, PT_ERR_STATE, "no probe grid: pt_set_probe_grid first");
+    if (c->probes.host.empty()) return fail(c, PT_ERR_STATE, "no probe grid: pt_set_probe_grid first");
     if (!moments && v->res == 0u)
     {
-        if (!c->probe_moments.empty()) c->probe_version++;
+        if (!c->probe_moments.host.empty()) c->probe_version++;
         drop_probe_depth(c);
         return PT_OK;
     }
@@ -4330,7 +4287,7 @@ int pt_set_probe_grid_depth(pt_ctx* c, const pt_probe_depth* v, const float* mom
     if (v->res < 2u || v->res > 16u) return fail(c, PT_ERR_LIMIT, "pt_probe_depth.res: the octahedral map's side is 2..16");
     if (v->flags & ~PT_PROBE_VIS_FACING) return fail(c, PT_ERR_ARG, "pt_probe_depth.flags: unknown bits");
     if (!(v->vis_floor >= 0.0f && v->vis_floor <= 1.0f)) return fail(c, PT_ERR_ARG, "pt_probe_depth.vis_floor must be in 0..1");
-    const size_t n = c->probes.size() * v->res * v->res;
+    const size_t n = c->probes.host.size() * v->res * v->res;
     for (size_t i = 0; i < n * 2; ++i)
         if (!std::isfinite(moments[i]) || moments[i] < 0.0f)
             return fail(c, PT_ERR_ARG, "pt_set_probe_grid_depth: node " + std::to_string(i / (2 * (size_t)v->res * v->res)) + " has a moment that is not finite and >= 0");
@@ -4338,7 +4295,7 @@ int pt_set_probe_grid_depth(pt_ctx* c, const pt_probe_depth* v, const float* mom
     try { rec.resize(n); }
     catch (const std::exception& e) { return fail(c, PT_ERR_LIMIT, std::string("probe depth does not fit in host memory: ") + e.what()); }
     std::memcpy(rec.data(), moments, n * sizeof(DProbeDepth));
-    c->probe_moments.swap(rec);
+    c->probe_moments.host.swap(rec);
     c->probe_depth = *v;
     c->probe_version++;
     return PT_OK;
@@ -4460,10 +4417,10 @@ int pt_set_probe_grid_radiance(pt_ctx* c, const pt_probe_radiance* v, const floa
     if (v)
         for (uint32_t w : v->reserved)
             if (w) return fail(c, PT_ERR_ARG, "pt_probe_radiance.reserved must be 0");
-    if (c->probes.empty()) return fail(c, PT_ERR_STATE, "no probe grid: pt_set_probe_grid first");
+    if (c->probes.host.empty()) return fail(c, PT_ERR_STATE, "no probe grid: pt_set_probe_grid first");
     if (!v)
     {
-        if (!c->probe_radiance_table.empty()) c->probe_version++;
+        if (!c->probe_radiance_table.host.empty()) c->probe_version++;
         drop_probe_radiance(c);
         return PT_OK;
     }
@@ -4471,7 +4428,7 @@ int pt_set_probe_grid_radiance(pt_ctx* c, const pt_probe_radiance* v, const floa
     int r;
     if ((r = probe_levels_check(c, "pt_probe_radiance", v->res, v->n_levels, v->alpha))) return r;
     const size_t per_node = (size_t)v->n_levels * v->res * v->res;
-    const uint64_t n = (uint64_t)c->probes.size() * per_node;
+    const uint64_t n = (uint64_t)c->probes.host.size() * per_node;
     if (n * 16 > (1ull << 31)) return fail(c, PT_ERR_LIMIT, "pt_set_probe_grid_radiance: the table is above 2^31 bytes");
     for (uint64_t i = 0; i < n * 4; ++i)
         if (!std::isfinite(table[i]) || table[i] < 0.0f)
@@ -4479,9 +4436,9 @@ int pt_set_probe_grid_radiance(pt_ctx* c, const pt_probe_radiance* v, const floa
     std::vector<f4> rec;
     try { rec.assign((size_t)n, f4{0.0f, 0.0f, 0.0f, 0.0f}); }
     catch (const std::exception& e) { return fail(c, PT_ERR_LIMIT, std::string("probe radiance does not fit in host memory: ") + e.what()); }
-    for (size_t node = 0; node < c->probes.size(); ++node)
-        if (c->probes[node].valid != 0.0f) std::memcpy(&rec[node * per_node], table + 4 * node * per_node, per_node * sizeof(f4));
-    c->probe_radiance_table.swap(rec);
+    for (size_t node = 0; node < c->probes.host.size(); ++node)
+        if (c->probes.host[node].valid != 0.0f) std::memcpy(&rec[node * per_node], table + 4 * node * per_node, per_node * sizeof(f4));
+    c->probe_radiance_table.host.swap(rec);
     c->probe_radiance = *v;
     for (uint32_t l = v->n_levels; l < 8u; ++l) c->probe_radiance.alpha[l] = 0.0f; // (not read: reported as zeros)
     c->probe_version++;
@@ -4501,29 +4458,27 @@ int pt_probe_grid_specular(pt_ctx* c, int on_device, uint32_t n, const float* po
 {
     if (!c) return PT_ERR_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
-    if (c->probes.empty()) return fail(c, PT_ERR_STATE, "no probe grid: pt_set_probe_grid first");
-    if (c->probe_radiance_table.empty()) return fail(c, PT_ERR_STATE, "no probe radiance: pt_set_probe_grid_radiance first");
+    if (c->probes.host.empty()) return fail(c, PT_ERR_STATE, "no probe grid: pt_set_probe_grid first");
+    if (c->probe_radiance_table.host.empty()) return fail(c, PT_ERR_STATE, "no probe radiance: pt_set_probe_grid_radiance first");
     if (n == 0) return PT_OK;
     if (!position || !normal || !incoming || !alpha || !rgb || !lit) return fail(c, PT_ERR_ARG, "pt_probe_grid_specular: null pointer");
-    const bool vis = !c->probe_moments.empty();
+    BakedLight l;
+    BakedKey k;
+    int r;
     if (!on_device)
     {
-        const ProbeGridView g = probe_grid_view(c, c->probes.data());
-        const ProbeRadianceView rv = probe_radiance_view(c, c->probe_radiance_table.data());
-        const ProbeDepthView dv = probe_depth_view(c, c->probe_moments.data());
+        (void)baked_light(c, LIGHT_GRID_HOST, l, k);
         for (uint32_t i = 0; i < n; ++i)
         {
             const float *pp = position + 3 * (size_t)i, *pn = normal + 3 * (size_t)i, *pi = incoming + 3 * (size_t)i;
             const f3 P{pp[0], pp[1], pp[2]}, N{pn[0], pn[1], pn[2]}, D{pi[0], pi[1], pi[2]};
             f3 col;
-            lit[i] = (vis ? probe_grid_specular<true>(g, rv, P, N, D, alpha[i], &col, &dv) : probe_grid_specular(g, rv, P, N, D, alpha[i], &col)) ? 1u : 0u;
+            lit[i] = (k.vis ? probe_grid_specular<true>(l.grid, l.rad, P, N, D, alpha[i], &col, &l.depth) : probe_grid_specular(l.grid, l.rad, P, N, D, alpha[i], &col)) ? 1u : 0u;
             rgb[3 * (size_t)i] = col.x; rgb[3 * (size_t)i + 1] = col.y; rgb[3 * (size_t)i + 2] = col.z;
         }
         return PT_OK;
     }
-    int r;
-    if ((r = ensure_device(c)) || (r = ensure_probe_grid(c)) || (r = ensure_probe_radiance(c))) return r;
-    if (vis && (r = ensure_probe_depth(c))) return r;
+    if ((r = ensure_device(c)) || (r = baked_light(c, LIGHT_GRID, l, k))) return r;
     Staging st(c);
     const float* d_pos = (const float*)st.in(position, (size_t)n * 12);
     const float* d_nrm = (const float*)st.in(normal, (size_t)n * 12);
@@ -4532,9 +4487,7 @@ int pt_probe_grid_specular(pt_ctx* c, int on_device, uint32_t n, const float* po
     float* d_rgb = (float*)st.out((size_t)n * 12);
     uint8_t* d_lit = (uint8_t*)st.out(n);
     if (st.err) return st.err;
-    const ProbeDepthView dv = probe_depth_view(c, (const DProbeDepth*)c->d_probe_moments.p);
-    launch_probe_grid_specular(c->stream, probe_grid_view(c, (const DProbe*)c->d_probes.p), probe_radiance_view(c, (const f4*)c->d_probe_radiance.p), vis ? &dv : nullptr,
-                               n, d_pos, d_nrm, d_inc, d_alpha, d_rgb, d_lit);
+    launch_probe_grid_specular(c->stream, l.grid, l.rad, k.vis ? &l.depth : nullptr, n, d_pos, d_nrm, d_inc, d_alpha, d_rgb, d_lit);
     HIPCHK(c, hipGetLastError());
     if ((r = st.download(rgb, d_rgb, (size_t)n * 12))) return r;
     return st.download(lit, d_lit, n);

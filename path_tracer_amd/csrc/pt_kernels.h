@@ -323,12 +323,28 @@ struct BakedArgs : ChainHop
     EnvView env;
     float unlit[3];
 };
-void launch_baked_follow(hipStream_t s, const SceneView& sv, const TexView& tex, const LmView& lm, const BakedArgs& a);
-// ... with a probe grid set (pt_set_probe_grid): the baked ending with its probe lookup compiled in, which lights a final surface that no map
-// lights
-void launch_baked_follow_probes(hipStream_t s, const SceneView& sv, const TexView& tex, const LmView& lm, const BakedArgs& a, const ProbeGridView& grid);
-// unit hook (pt_probe_grid_lookup): probe_grid_lookup (pt_probe.h) at n positions and normals (3 floats each)
-void launch_probe_grid_lookup(hipStream_t s, const ProbeGridView& grid, uint32_t n, const float* position, const float* normal, float* rgb, uint8_t* lit);
+// What lights a final surface of the baked view, every variant's one argument: the lightmap tables, their gradients (null without one), the
+// probe grid, its depth moments and its prefiltered radiance (zeroed where not set).  A variant reads the views of its axes and no other.
+struct BakedLight
+{
+    LmView lm;
+    LmDirView ld;
+    ProbeGridView grid;
+    ProbeDepthView depth;
+    ProbeRadianceView rad;
+};
+// ... and the ending's four axes, 0 or 1 each: a probe grid set (it lights a final surface that no map lights); depth set on it (its lookups
+// are the ones with visibility); radiance set on it (GGX metal reflects it); a gradient in use and a normal-mapped material in the scene (maps
+// and grid are read under the perturbed normal).  vis and spec are the grid's: a key with either and no grid names no kernel and aborts
+struct BakedKey
+{
+    uint32_t grid, vis, spec, dir;
+};
+void launch_baked_follow(hipStream_t s, const SceneView& sv, const TexNView& tex, const BakedLight& light, const BakedKey& key, const BakedArgs& a);
+// unit hook (pt_probe_grid_lookup): probe_grid_lookup (pt_probe.h) at n positions and normals (3 floats each), with visibility where depth is
+// not null
+void launch_probe_grid_lookup(hipStream_t s, const ProbeGridView& grid, const ProbeDepthView* depth, uint32_t n, const float* position, const float* normal, float* rgb,
+                              uint8_t* lit);
 // pt_probe_backfaces: a ray table's entries [0, n) (o, d: 3 floats per ray) as a hook queue (t_max +inf, ray index = entry), its count word set;
 // then the closest hits of rays [first, first + count) of the bake `pb` (d, hits: the window) counted per probe into hits_out and back_out,
 // which continue from what they hold: one wave per probe, no atomics
@@ -339,18 +355,10 @@ void launch_probe_backfaces(hipStream_t s, const SceneView& sv, const ProbeBake&
 // counts: the rays per texel; both continue from what they hold), in sample order per texel: one wave per probe, no atomics
 void launch_probe_depth_fold(hipStream_t s, const ProbeBake& pb, uint64_t first, uint32_t count, const float* d, const f4* hits, uint32_t res,
                              float max_distance, DProbeDepth* sums, uint32_t* counts);
-// with depth set on the grid (pt_set_probe_grid_depth): the probe ending and the unit hook over the lookup with visibility
-void launch_baked_follow_probes_vis(hipStream_t s, const SceneView& sv, const TexView& tex, const LmView& lm, const BakedArgs& a, const ProbeGridView& grid,
-                                    const ProbeDepthView& depth);
-void launch_probe_grid_lookup_vis(hipStream_t s, const ProbeGridView& grid, const ProbeDepthView& depth, uint32_t n, const float* position, const float* normal,
-                                  float* rgb, uint8_t* lit);
 // reflection probes.  pt_bake_probe_radiance: the same window's integrated radiance folded into the probes' R x R octahedral radiance maps
 // (sums: r, g, b per texel, counts: the rays per texel; both continue from what they hold), in sample order per texel: one wave per probe,
 // no atomics.  pt_probe_radiance_prefilter: table[probe][level][texel] = the GGX prefilter of the means, one workgroup per (probe, level).
 // pt_probe_grid_specular's unit hook: probe_grid_specular (pt_probe.h) of n queries, with visibility where depth is not null
-// with radiance set on the grid (pt_set_probe_grid_radiance): the probe ending whose GGX metal reflects the prefiltered radiance (depth: null without)
-void launch_baked_follow_probes_spec(hipStream_t s, const SceneView& sv, const TexView& tex, const LmView& lm, const BakedArgs& a, const ProbeGridView& grid,
-                                     const ProbeDepthView* depth, const ProbeRadianceView& rad);
 void launch_probe_radiance_fold(hipStream_t s, const ProbeBake& pb, uint64_t first, uint32_t count, const float* d, const f4* radiance, uint32_t res,
                                 float* sums, uint32_t* counts);
 void launch_probe_radiance_prefilter(hipStream_t s, uint32_t res, uint32_t n_probes, uint32_t n_levels, const float* alpha, const float* sums,
@@ -360,12 +368,6 @@ void launch_probe_grid_specular(hipStream_t s, const ProbeGridView& grid, const 
 // unit hook (pt_lightmap_lookup): lightmap_at (pt_materials.h) of world instance[i], leaf-order triangle tri[i] at barycentrics u[i], v[i]
 void launch_lightmap_lookup(hipStream_t s, const LmView& lm, uint32_t n, const uint32_t* instance, const uint32_t* tri, const float* u, const float* v,
                             float* rgb, uint8_t* mapped);
-// directional lightmaps (pt_set_lightmap_directional).  The baked endings' DIR variants: a front-face hit on a mapped leaf reads the map through
-// lightmap_at_directional with delta = n' - n, and with a grid the probe lookup of an unmapped surface takes n' (shading_normal_delta,
-// pt_materials.h).  grid null: no grid; depth, rad null: without.  The host launches them only while a gradient is set and the built scene has a
-// normal-mapped material; every other call launches the kernels above
-void launch_baked_follow_directional(hipStream_t s, const SceneView& sv, const TexNView& tex, const LmView& lm, const LmDirView& ld, const BakedArgs& a,
-                                     const ProbeGridView* grid, const ProbeDepthView* depth, const ProbeRadianceView* rad);
 // unit hook (pt_lightmap_lookup_directional): lightmap_at_directional of n hits with ray directions dir (3 floats each)
 void launch_lightmap_lookup_directional(hipStream_t s, const SceneView& sv, const TexNView& tex, const LmView& lm, const LmDirView& ld, uint32_t n,
                                         const uint32_t* instance, const uint32_t* tri, const float* u, const float* v, const float* dir, float* rgb, uint8_t* mapped);

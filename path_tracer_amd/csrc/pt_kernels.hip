@@ -3109,22 +3109,31 @@ __global__ void __launch_bounds__(256, 8) k_guide_follow(const SceneView sv, con
 // ---- the baked view (pt_render_baked; include/pt_api.h states the sample).  The same chains with another ending: a chain that ends adds its
 // baked sample B and 1 to sum[pixel], one binary32 add per component, no finite check and no clamp.  B = the running colour product R on a
 // light; R * the lightmap at the hit on a front face of a leaf that has a map; R * unlit on any other surface; the environment (or the
-// constant ambient) of a miss, times R of the hop before unless the camera ray itself missed.  PROBES, with a probe grid set
-// (pt_set_probe_grid): a final surface that no map lights is lit by the grid where the grid is lit, by unlit where not; P and n are the
-// guides' (the hit position, the face-forwarded unperturbed normal).
+// constant ambient) of a miss, times R of the hop before unless the camera ray itself missed.  What lights a final surface beside that is the
+// ending's four axes, decided on the host (pt_api.cpp, baked_light) and handed over as a BakedKey:
+// GRID, with a probe grid set (pt_set_probe_grid): a final surface that no map lights is lit by the grid where the grid is lit, by unlit where
+// not; P and n are the guides' (the hit position, the face-forwarded unperturbed normal).
+// VIS, with depth set on the grid (pt_set_probe_grid_depth): the grid's lookups are the ones with visibility.
+// SPEC, with radiance set on the grid (pt_set_probe_grid_radiance): a chain that ends on GGX metal, on either face, reflects the grid's
+// prefiltered radiance, B = R * S, where probe_grid_specular is lit, whether or not a map lights the surface (a map holds irradiance, which a
+// metal does not reflect diffusely); where it is not lit, and on every other kind, the ending is what it is without SPEC.  The metal branch
+// comes first and returns, so a lane holds one lookup's registers at a time.  P, n and d are ChainEnd's; the alpha is the material's own.
 // DIR, with a gradient set and a normal-mapped material in the scene (pt_set_lightmap_directional): n' = shading_normal of the hit, delta =
 // n' - n (zero by construction without a normal texture); a front face of a mapped leaf reads lightmap_at_directional, and the grid takes n'.
 // n' is gathered behind a barrier of its own, after the hop's gathers and before the map's, so one lookup's registers are live at a time.
-template <bool PROBES, bool VIS = false, bool DIR = false>
+// VIS and SPEC are the grid's, so the points of the axes that are kernels are the ten of baked_variant_ok.
+constexpr bool baked_variant_ok(uint32_t grid, uint32_t vis, uint32_t spec, uint32_t dir) { return grid || (!vis && !spec); }
+// The plain ending runs at eight waves per SIMD.  The corner of a grid being evaluated and the one in flight are 56 registers and the probe
+// ending must not spill, so with a grid the bounds leave 128; it takes 66 (seven waves per SIMD) and no scratch, and every DIR ending fits
+// under the same bounds (profiles/r30_baked_axes.md has the registers of all ten)
+constexpr int baked_min_blocks(bool grid, bool dir) { return grid || dir ? 4 : 8; }
+template <bool GRID, bool VIS, bool SPEC, bool DIR>
 struct BakedEnding
 {
-    const LmView& lm;
+    const SceneView& sv;
+    const TexNView& texn;
+    const BakedLight& light; // a variant reads the views of its axes and no other
     const BakedArgs& a;
-    const ProbeGridView* grid; // null without PROBES
-    const ProbeDepthView* depth = nullptr; // null without VIS (pt_set_probe_grid_depth: the lookup with visibility)
-    const LmDirView* ld = nullptr;  // these three: null without DIR
-    const SceneView* sv = nullptr;
-    const TexNView* texn = nullptr;
     // nothing here reads t, and carrying its sum through both barriers costs the probe ending's later hops a 67th register (the parent's 66 are
     // the bound: profiles/r25_chain_hop.md), so state[pixel].w holds one hop's t here
     static constexpr bool kSumT = false;
@@ -3135,37 +3144,48 @@ struct BakedEnding
     }
     __device__ __forceinline__ f3 surface(const ChainEnd& h) const
     {
+        if constexpr (SPEC)
+        {
+            if (h.kind == MAT_GGX_METAL)
+            {
+                const float alpha = sv.materials[sv.instances[h.inst].material].alpha;
+                __asm__ volatile("" ::: "memory");
+                f3 s;
+                if (probe_grid_specular<VIS>(light.grid, light.rad, fma3(h.d, bc3(h.hit.x), xyz(a.in.a[h.slot])), h.nrm, h.d, alpha, &s, VIS ? &light.depth : nullptr))
+                    return h.c * s;
+            }
+        }
         if (h.kind == MAT_EMISSIVE) return h.c;
         f3 l{a.unlit[0], a.unlit[1], a.unlit[2]};
         bool mapped = false;
         f3 np = h.nrm;
         if constexpr (DIR)
         {
-            if (PROBES || h.front)
+            if (GRID || h.front)
             {
                 __asm__ volatile("" ::: "memory");
                 f3 delta;
-                np = shading_normal_delta(sv->tri_shade, sv->instances, sv->materials, *texn, h.inst, h.tri, h.hit.y, h.hit.z, h.d, h.nrm, &delta);
+                np = shading_normal_delta(sv.tri_shade, sv.instances, sv.materials, texn, h.inst, h.tri, h.hit.y, h.hit.z, h.d, h.nrm, &delta);
                 if (h.front)
                 {
                     __asm__ volatile("" ::: "memory");
-                    const f3 m = lightmap_at_directional(lm, *ld, h.inst, h.tri, h.hit.y, h.hit.z, delta, &mapped);
+                    const f3 m = lightmap_at_directional(light.lm, light.ld, h.inst, h.tri, h.hit.y, h.hit.z, delta, &mapped);
                     if (mapped) l = m;
                 }
             }
         }
         else if (h.front) // the bake lit the front side only
         {
-            const f3 m = lightmap_at(lm, h.inst, h.tri, h.hit.y, h.hit.z, &mapped);
+            const f3 m = lightmap_at(light.lm, h.inst, h.tri, h.hit.y, h.hit.z, &mapped);
             if (mapped) l = m;
         }
-        if (PROBES && !mapped) // the grid lights what no map lights, where it is lit itself
+        if (GRID && !mapped) // the grid lights what no map lights, where it is lit itself
         {
             // the grid's corners after the map's four texels, and P made again behind the barrier: h.p kept across the map's gather is five
             // registers more
             __asm__ volatile("" ::: "memory");
             f3 irr;
-            if (probe_grid_lookup<VIS>(*grid, fma3(h.d, bc3(h.hit.x), xyz(a.in.a[h.slot])), np, &irr, depth)) l = irr;
+            if (probe_grid_lookup<VIS>(light.grid, fma3(h.d, bc3(h.hit.x), xyz(a.in.a[h.slot])), np, &irr, VIS ? &light.depth : nullptr)) l = irr;
         }
         return h.c * l;
     }
@@ -3175,82 +3195,11 @@ struct BakedEnding
         a.sum[px] = f4{s.x + b.x, s.y + b.y, s.z + b.z, s.w + 1.0f};
     }
 };
-template <bool FIRST>
-__global__ void __launch_bounds__(256, 8) k_baked_follow(const SceneView sv, const TexView tex, const LmView lm, const BakedArgs a)
+template <bool FIRST, bool GRID, bool VIS, bool SPEC, bool DIR>
+__global__ void __launch_bounds__(256, baked_min_blocks(GRID, DIR)) k_baked_follow(const SceneView sv, const TexNView tex, const BakedLight light, const BakedArgs a)
 {
-    chain_hop<FIRST>(sv, tex, a, BakedEnding<false>{lm, a, nullptr});
-}
-// The corner being evaluated and the one in flight are 56 registers and the probe ending must not spill, so its bounds leave it 128; it takes
-// 66 (seven waves per SIMD) and no scratch (profiles/r24_probe_grid.md).
-template <bool FIRST>
-__global__ void __launch_bounds__(256, 4) k_baked_follow_probes(const SceneView sv, const TexView tex, const LmView lm, const BakedArgs a, const ProbeGridView grid)
-{
-    chain_hop<FIRST>(sv, tex, a, BakedEnding<true>{lm, a, &grid});
-}
-// ... and with depth set on the grid (pt_set_probe_grid_depth): the same ending over the lookup with visibility, chosen on the host as the
-// probe ending is (profiles/r25_probe_depth.md has its registers)
-template <bool FIRST>
-__global__ void __launch_bounds__(256, 4) k_baked_follow_probes_vis(const SceneView sv, const TexView tex, const LmView lm, const BakedArgs a, const ProbeGridView grid,
-                                                                    const ProbeDepthView depth)
-{
-    chain_hop<FIRST>(sv, tex, a, BakedEnding<true, true>{lm, a, &grid, &depth});
-}
-// ... and with radiance set on the grid (pt_set_probe_grid_radiance): a chain that ends on GGX metal, on either face, reflects the grid's
-// prefiltered radiance, B = R * S, where probe_grid_specular is lit, whether or not a map lights the surface (a map holds irradiance, which a
-// metal does not reflect diffusely); where it is not lit, and on every other kind, the ending is the probe ending's.  The metal branch comes
-// first and returns, so a lane holds one lookup's registers at a time.  P, n and d are ChainEnd's; the alpha is the material's own.
-template <bool VIS, bool DIR = false>
-struct BakedSpecEnding
-{
-    BakedEnding<true, VIS, DIR> base;
-    const SceneView& sv;
-    const ProbeRadianceView& rad;
-    static constexpr bool kSumT = false;
-    __device__ __forceinline__ f3 miss(bool first, uint32_t i, uint32_t px, const f3& d) const { return base.miss(first, i, px, d); }
-    __device__ __forceinline__ f3 surface(const ChainEnd& h) const
-    {
-        if (h.kind == MAT_GGX_METAL)
-        {
-            const float alpha = sv.materials[sv.instances[h.inst].material].alpha;
-            __asm__ volatile("" ::: "memory");
-            f3 s;
-            if (probe_grid_specular<VIS>(*base.grid, rad, fma3(h.d, bc3(h.hit.x), xyz(base.a.in.a[h.slot])), h.nrm, h.d, alpha, &s, base.depth)) return h.c * s;
-        }
-        return base.surface(h);
-    }
-    __device__ __forceinline__ void store(uint32_t px, const f3& b) const { base.store(px, b); }
-};
-template <bool FIRST>
-__global__ void __launch_bounds__(256, 4) k_baked_follow_probes_spec(const SceneView sv, const TexView tex, const LmView lm, const BakedArgs a, const ProbeGridView grid,
-                                                                     const ProbeRadianceView rad)
-{
-    chain_hop<FIRST>(sv, tex, a, BakedSpecEnding<false>{BakedEnding<true>{lm, a, &grid}, sv, rad});
-}
-template <bool FIRST>
-__global__ void __launch_bounds__(256, 4) k_baked_follow_probes_spec_vis(const SceneView sv, const TexView tex, const LmView lm, const BakedArgs a,
-                                                                         const ProbeGridView grid, const ProbeDepthView depth, const ProbeRadianceView rad)
-{
-    chain_hop<FIRST>(sv, tex, a, BakedSpecEnding<true>{BakedEnding<true, true>{lm, a, &grid, &depth}, sv, rad});
-}
-// ... and the DIR variants of the five endings above (BakedEnding's DIR axis), chosen on the host while a gradient is set and the scene has a
-// normal-mapped material.  All of them under the probe ending's bounds, which leave 128 registers: none spills
-// (profiles/r29_directional_lightmaps.md has their registers)
-template <bool FIRST>
-__global__ void __launch_bounds__(256, 4) k_baked_follow_dir(const SceneView sv, const TexNView tex, const LmView lm, const LmDirView ld, const BakedArgs a)
-{
-    chain_hop<FIRST>(sv, tex, a, BakedEnding<false, false, true>{lm, a, nullptr, nullptr, &ld, &sv, &tex});
-}
-template <bool FIRST, bool VIS>
-__global__ void __launch_bounds__(256, 4) k_baked_follow_probes_dir(const SceneView sv, const TexNView tex, const LmView lm, const LmDirView ld, const BakedArgs a,
-                                                                    const ProbeGridView grid, const ProbeDepthView depth)
-{
-    chain_hop<FIRST>(sv, tex, a, BakedEnding<true, VIS, true>{lm, a, &grid, VIS ? &depth : nullptr, &ld, &sv, &tex});
-}
-template <bool FIRST, bool VIS>
-__global__ void __launch_bounds__(256, 4) k_baked_follow_probes_spec_dir(const SceneView sv, const TexNView tex, const LmView lm, const LmDirView ld, const BakedArgs a,
-                                                                         const ProbeGridView grid, const ProbeDepthView depth, const ProbeRadianceView rad)
-{
-    chain_hop<FIRST>(sv, tex, a, BakedSpecEnding<VIS, true>{BakedEnding<true, VIS, true>{lm, a, &grid, VIS ? &depth : nullptr, &ld, &sv, &tex}, sv, rad});
+    static_assert(baked_variant_ok(GRID, VIS, SPEC, DIR), "no such ending");
+    chain_hop<FIRST>(sv, tex, a, BakedEnding<GRID, VIS, SPEC, DIR>{sv, tex, light, a});
 }
 // unit hook of the directional lookup: rgb, mapped = lightmap_at_directional with delta = n' - n of the hit under the ray direction dir
 __global__ void __launch_bounds__(256) k_lightmap_lookup_directional(const SceneView sv, const TexNView tex, const LmView lm, const LmDirView ld, const uint32_t n,
@@ -3269,8 +3218,9 @@ __global__ void __launch_bounds__(256) k_lightmap_lookup_directional(const Scene
     rgb[3u * (size_t)i] = c.x; rgb[3u * (size_t)i + 1u] = c.y; rgb[3u * (size_t)i + 2u] = c.z;
     mapped[i] = has ? 1u : 0u;
 }
-// unit hook of the probe grid's lookup: rgb, lit = probe_grid_lookup
-__global__ void __launch_bounds__(256, 4) k_probe_grid_lookup(const ProbeGridView grid, const uint32_t n, const float* __restrict__ position,
+// unit hook of the probe grid's lookup (pt_probe_grid_lookup): rgb, lit = probe_grid_lookup<VIS>, VIS with depth set on the grid
+template <bool VIS>
+__global__ void __launch_bounds__(256, 4) k_probe_grid_lookup(const ProbeGridView grid, const ProbeDepthView depth, const uint32_t n, const float* __restrict__ position,
                                                               const float* __restrict__ normal, float* __restrict__ rgb, uint8_t* __restrict__ lit)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -3278,19 +3228,7 @@ __global__ void __launch_bounds__(256, 4) k_probe_grid_lookup(const ProbeGridVie
     const float* pp = position + 3u * (size_t)i;
     const float* pn = normal + 3u * (size_t)i;
     f3 c;
-    const bool has = probe_grid_lookup(grid, f3{pp[0], pp[1], pp[2]}, f3{pn[0], pn[1], pn[2]}, &c);
-    rgb[3u * (size_t)i] = c.x; rgb[3u * (size_t)i + 1u] = c.y; rgb[3u * (size_t)i + 2u] = c.z;
-    lit[i] = has ? 1u : 0u;
-}
-__global__ void __launch_bounds__(256, 4) k_probe_grid_lookup_vis(const ProbeGridView grid, const ProbeDepthView depth, const uint32_t n, const float* __restrict__ position,
-                                                                  const float* __restrict__ normal, float* __restrict__ rgb, uint8_t* __restrict__ lit)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float* pp = position + 3u * (size_t)i;
-    const float* pn = normal + 3u * (size_t)i;
-    f3 c;
-    const bool has = probe_grid_lookup<true>(grid, f3{pp[0], pp[1], pp[2]}, f3{pn[0], pn[1], pn[2]}, &c, &depth);
+    const bool has = probe_grid_lookup<VIS>(grid, f3{pp[0], pp[1], pp[2]}, f3{pn[0], pn[1], pn[2]}, &c, &depth);
     rgb[3u * (size_t)i] = c.x; rgb[3u * (size_t)i + 1u] = c.y; rgb[3u * (size_t)i + 2u] = c.z;
     lit[i] = has ? 1u : 0u;
 }
@@ -3872,18 +3810,31 @@ void launch_guide_follow(hipStream_t s, const SceneView& sv, const TexView& tex,
     if (a.sum) launch_chain_hop(s, a, k_guide_follow<true, true>, k_guide_follow<true, false>, sv, tex, a);
     else launch_chain_hop(s, a, k_guide_follow<false, true>, k_guide_follow<false, false>, sv, tex, a);
 }
-void launch_baked_follow(hipStream_t s, const SceneView& sv, const TexView& tex, const LmView& lm, const BakedArgs& a)
+// the baked view's ending by its axes: key says what lights a final surface (BakedKey), light holds the views that go with it
+typedef std::integer_sequence<uint32_t, 2, 2, 2, 2> baked_axes; // grid, vis, spec, dir
+void launch_baked_follow(hipStream_t s, const SceneView& sv, const TexNView& tex, const BakedLight& light, const BakedKey& key, const BakedArgs& a)
 {
-    launch_chain_hop(s, a, k_baked_follow<true>, k_baked_follow<false>, sv, tex, lm, a);
+    bool launched = false;
+    pick_axes_of(baked_axes{}, {key.grid, key.vis, key.spec, key.dir}, [&](auto grid, auto vis, auto spec, auto dir) {
+        if constexpr (baked_variant_ok(grid, vis, spec, dir)) // (depth and radiance are a grid's: the other six points are no kernels)
+        {
+            launched = true;
+            launch_chain_hop(s, a, k_baked_follow<true, grid != 0u, vis != 0u, spec != 0u, dir != 0u>, k_baked_follow<false, grid != 0u, vis != 0u, spec != 0u, dir != 0u>, sv,
+                             tex, light, a);
+        }
+    });
+    if (!launched) // a missing kernel is an error, never a skipped pass
+    {
+        fprintf(stderr, "launch_baked_follow: no ending for grid %u, vis %u, spec %u, dir %u\n", key.grid, key.vis, key.spec, key.dir);
+        abort();
+    }
 }
-void launch_baked_follow_probes(hipStream_t s, const SceneView& sv, const TexView& tex, const LmView& lm, const BakedArgs& a, const ProbeGridView& grid)
-{
-    launch_chain_hop(s, a, k_baked_follow_probes<true>, k_baked_follow_probes<false>, sv, tex, lm, a, grid);
-}
-void launch_probe_grid_lookup(hipStream_t s, const ProbeGridView& grid, uint32_t n, const float* position, const float* normal, float* rgb, uint8_t* lit)
+void launch_probe_grid_lookup(hipStream_t s, const ProbeGridView& grid, const ProbeDepthView* depth, uint32_t n, const float* position, const float* normal, float* rgb,
+                              uint8_t* lit)
 {
     if (n == 0u) return;
-    hipLaunchKernelGGL(k_probe_grid_lookup, dim3((n + 255u) / 256u), dim3(256), 0, s, grid, n, position, normal, rgb, lit);
+    if (depth) hipLaunchKernelGGL(k_probe_grid_lookup<true>, dim3((n + 255u) / 256u), dim3(256), 0, s, grid, *depth, n, position, normal, rgb, lit);
+    else hipLaunchKernelGGL(k_probe_grid_lookup<false>, dim3((n + 255u) / 256u), dim3(256), 0, s, grid, ProbeDepthView{}, n, position, normal, rgb, lit);
 }
 void launch_rays_to_queue(hipStream_t s, uint32_t n, const float* o, const float* d, RayQueue rq, uint32_t* n_and_heads)
 {
@@ -3907,38 +3858,11 @@ void launch_probe_depth_fold(hipStream_t s, const ProbeBake& pb, uint64_t first,
     hipLaunchKernelGGL(k_probe_depth_fold, dim3((uint32_t)((probes * 64u + 255u) / 256u)), dim3(256), 0, s, pb, first, count, d, hits, res, max_distance, sums,
                        counts);
 }
-void launch_baked_follow_probes_vis(hipStream_t s, const SceneView& sv, const TexView& tex, const LmView& lm, const BakedArgs& a, const ProbeGridView& grid,
-                                    const ProbeDepthView& depth)
-{
-    launch_chain_hop(s, a, k_baked_follow_probes_vis<true>, k_baked_follow_probes_vis<false>, sv, tex, lm, a, grid, depth);
-}
-void launch_baked_follow_probes_spec(hipStream_t s, const SceneView& sv, const TexView& tex, const LmView& lm, const BakedArgs& a, const ProbeGridView& grid,
-                                     const ProbeDepthView* depth, const ProbeRadianceView& rad)
-{
-    if (depth) launch_chain_hop(s, a, k_baked_follow_probes_spec_vis<true>, k_baked_follow_probes_spec_vis<false>, sv, tex, lm, a, grid, *depth, rad);
-    else launch_chain_hop(s, a, k_baked_follow_probes_spec<true>, k_baked_follow_probes_spec<false>, sv, tex, lm, a, grid, rad);
-}
-void launch_baked_follow_directional(hipStream_t s, const SceneView& sv, const TexNView& tex, const LmView& lm, const LmDirView& ld, const BakedArgs& a,
-                                     const ProbeGridView* grid, const ProbeDepthView* depth, const ProbeRadianceView* rad)
-{
-    const ProbeDepthView dv = depth ? *depth : ProbeDepthView{};
-    if (!grid) launch_chain_hop(s, a, k_baked_follow_dir<true>, k_baked_follow_dir<false>, sv, tex, lm, ld, a);
-    else if (rad && depth) launch_chain_hop(s, a, k_baked_follow_probes_spec_dir<true, true>, k_baked_follow_probes_spec_dir<false, true>, sv, tex, lm, ld, a, *grid, dv, *rad);
-    else if (rad) launch_chain_hop(s, a, k_baked_follow_probes_spec_dir<true, false>, k_baked_follow_probes_spec_dir<false, false>, sv, tex, lm, ld, a, *grid, dv, *rad);
-    else if (depth) launch_chain_hop(s, a, k_baked_follow_probes_dir<true, true>, k_baked_follow_probes_dir<false, true>, sv, tex, lm, ld, a, *grid, dv);
-    else launch_chain_hop(s, a, k_baked_follow_probes_dir<true, false>, k_baked_follow_probes_dir<false, false>, sv, tex, lm, ld, a, *grid, dv);
-}
 void launch_lightmap_lookup_directional(hipStream_t s, const SceneView& sv, const TexNView& tex, const LmView& lm, const LmDirView& ld, uint32_t n,
                                         const uint32_t* instance, const uint32_t* tri, const float* u, const float* v, const float* dir, float* rgb, uint8_t* mapped)
 {
     if (n == 0u) return;
     hipLaunchKernelGGL(k_lightmap_lookup_directional, dim3((n + 255u) / 256u), dim3(256), 0, s, sv, tex, lm, ld, n, instance, tri, u, v, dir, rgb, mapped);
-}
-void launch_probe_grid_lookup_vis(hipStream_t s, const ProbeGridView& grid, const ProbeDepthView& depth, uint32_t n, const float* position, const float* normal,
-                                  float* rgb, uint8_t* lit)
-{
-    if (n == 0u) return;
-    hipLaunchKernelGGL(k_probe_grid_lookup_vis, dim3((n + 255u) / 256u), dim3(256), 0, s, grid, depth, n, position, normal, rgb, lit);
 }
 void launch_probe_radiance_fold(hipStream_t s, const ProbeBake& pb, uint64_t first, uint32_t count, const float* d, const f4* radiance, uint32_t res,
                                 float* sums, uint32_t* counts)

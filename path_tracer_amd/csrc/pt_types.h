@@ -172,7 +172,7 @@ struct ProbeDepthView
 };
 // Reflection probes (pt_set_probe_grid_radiance): every node's GGX-prefiltered radiance on an R x R octahedral map per roughness level,
 // table[(node * n_levels + level) * R * R + texel] = {r, g, b, 0}, texel probe_oct_texel of the reflected direction.  A table and a view of
-// their own, handed only to the kernels that read them (probe_grid_specular, pt_probe.h).
+// their own, read only by the kernels that call probe_grid_specular (pt_probe.h).
 struct ProbeRadianceView
 {
     const f4* table;

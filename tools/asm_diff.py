@@ -3,7 +3,8 @@ A kernel template that gained trailing parameters renames its old instantiations
 template, k becomes k<false>; one that gained a trailing parameter PACK keeps k<a, b> with the empty pack, under another symbol): such a
 kernel is compared with the one it was and marked `+param`.  r20_name holds the one renaming that is no such growth: the surface pass's
 eleven positional parameters became six named axes and the camera kernels one template over the camera kind.  r22_name: the denoiser's two
-prep kernels became one template over the albedo source.
+prep kernels became one template over the albedo source.  r30_name: the baked view's eight shells became one template over the ending's
+axes (FIRST, GRID, VIS, SPEC, DIR), the grid lookup's two hooks one over VIS.
 usage: python tools/asm_diff.py old.s new.s"""
 import re, subprocess, sys
 
@@ -57,9 +58,18 @@ def r22_name(d):
     src = {'k_dn_prep': 0, 'k_dn_prep_albedo<false>': 1, 'k_dn_prep_albedo<true>': 2}
     return f'k_dn_prep<(pt::(anonymous namespace)::AlbedoFrom){src[d]}>' if d in src else d
 
+def r30_name(d):
+    """the one baked kernel's instantiation for a shell of the baked view as named before the ending's axes, or d itself"""
+    if d == 'k_probe_grid_lookup_vis': return 'k_probe_grid_lookup<true>'
+    m = re.fullmatch(r'k_baked_follow_(probes|probes_vis|probes_spec|probes_spec_vis|dir|probes_dir|probes_spec_dir)<(\w+)(?:, (\w+))?>', d)
+    if not m: return d
+    shell, first, vis = m.groups()
+    axes = ['true' if 'probes' in shell else 'false', vis or ('true' if 'vis' in shell else 'false'), 'true' if 'spec' in shell else 'false', 'true' if 'dir' in shell else 'false']
+    return f'k_baked_follow<{", ".join([first] + axes)}>'
+
 a, b = funcs(sys.argv[1]), funcs(sys.argv[2])
 print(len(a), 'kernels before,', len(b), 'after')
-old_names = {r22_name(r20_name(dem(n))): n for n in a if n not in b}
+old_names = {r30_name(r22_name(r20_name(dem(n)))): n for n in a if n not in b}
 renamed = set()
 for n in b:
     o = n if n in a else was(n, old_names)

@@ -4,7 +4,7 @@ pt_render_baked(1 sample) at K = 0 and K = 2, beside pt_render_guides_followed a
 the 1-spp pt_frame.  Every figure is the median of --calls blocking calls, taken --reps times with the routes alternating, so that a drift
 of the shared machine touches all of them; the report keeps every repeat, the spread is theirs.
 
-    python tools/baked_view_bench.py [--calls 20] [--reps 3] [--what all|guides] [--probes [--depth R] [--radiance R]] [--directional] [--out report.json]
+    python tools/baked_view_bench.py [--calls 20] [--reps 3] [--what all|guides] [--probes [--depth R] [--radiance R]] [--directional] [--endings] [--out report.json]
 
 --what guides times the guides call alone and runs on a tree that has no baked view: run it from the parent commit's tree and from this one,
 turn about, for the comparison across the two (the guide kernels themselves must not have moved).
@@ -27,8 +27,15 @@ profile quotes the kernel alone from a kernel trace beside them); and pt_probe_g
 --directional (profiles/r29_directional_lightmaps.md) times the DIR endings: every Lambertian material of the scene carries an 8 x 8 ripple
 normal map, every placement a 256 x 256 map; one context stops there (the scalar kernels), a second also sets a seeded gradient on every
 placement (the DIR kernels): ms per pt_render_baked(1 sample) at K = 0 and K = 2 on both, turn about; and pt_bake_lightmap_directional beside
-pt_bake_lightmap on the shell's 256 x 256 map at 16 samples (the same integration, another fold, 36 more bytes per texel each way)."""
+pt_bake_lightmap on the shell's 256 x 256 map at 16 samples (the same integration, another fold, 36 more bytes per texel each way).
+
+--endings (profiles/r30_baked_axes.md) times every ending of the baked view, one context after the other: the rippled scene of --directional
+with both boxes GGX metal, a 256 x 256 map on the shell's placement only (the grid lights the other walls), and the axes switched on one by
+one: the 16 x 16 x 16 grid, its R = 8 depth table, its R = 8 radiance table, the gradient: ms per pt_render_baked(1 sample) at K = 0 and K = 2
+for the ten points of (grid, vis, spec, dir) that are kernels, and the SHA-1 of the sums the timed calls of each left (two builds that compute
+the same bits report the same digests)."""
 import argparse
+import hashlib
 import json
 import os
 import statistics
@@ -70,6 +77,7 @@ def main():
     ap.add_argument("--depth", type=int, default=0)
     ap.add_argument("--radiance", type=int, default=0)
     ap.add_argument("--directional", action="store_true")
+    ap.add_argument("--endings", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import torch
@@ -80,6 +88,8 @@ def main():
         return probes(args, api, scenes)
     if args.directional:
         return directional(args, api, scenes)
+    if args.endings:
+        return endings(args, api, scenes)
     sc = scenes.cornell_box(W, H)
     baked = args.what == "all"
     if baked:
@@ -224,7 +234,8 @@ def probes(args, api, scenes):
 BAKE_SAMPLES = 16
 
 
-def directional(args, api, scenes):
+def rippled(scenes, **materials):
+    """the Cornell box with every Lambertian material under an 8 x 8 ripple normal map and planar UVs on every model"""
     import dataclasses
     from path_tracer_amd.scene_desc import LAMBERTIAN, SceneDesc, Texture
     n = 8
@@ -232,10 +243,13 @@ def directional(args, api, scenes):
     tri = 0.3 * (4.0 * np.abs(a - 0.5) - 1.0)
     x, y = np.meshgrid(tri, tri)
     ripples = Texture.new((0.5 * np.stack([x, y, np.sqrt(1.0 - x * x - y * y)], axis=2) + 0.5).astype(np.float32))
-    base = scenes.cornell_box(W, H)
     models = [dataclasses.replace(m, material=m.material.normal_mapped(ripples) if m.material.kind == LAMBERTIAN else m.material, uvs=planar_uvs(m.positions))
-              for m in base.models]
-    sc = SceneDesc.new(models, base.camera, "cornell, rippled")
+              for m in scenes.cornell_models(**materials)]
+    return SceneDesc.new(models, scenes.cornell_box(W, H).camera, "cornell, rippled")
+
+
+def directional(args, api, scenes):
+    sc = rippled(scenes)
     plain, dirn = api.Renderer(sc, W, H, max_bounces=DEPTH), api.Renderer(sc, W, H, max_bounces=DEPTH)
     rng = np.random.default_rng(29)
     for mi, m in enumerate(sc.models):
@@ -263,6 +277,46 @@ def directional(args, api, scenes):
     for _ in range(args.reps):
         for into, fn, calls in routes:
             into.append(round(timed(fn, calls), 4))
+    emit(report, args.out)
+
+
+def endings(args, api, scenes):
+    from path_tracer_amd.scene_desc import GGX
+    metal = GGX.new_metal((0.9, 0.8, 0.6), 0.4)
+    sc = rippled(scenes, tall_material=metal, short_material=metal)
+    pts = np.concatenate([(m.positions.reshape(-1, 3) @ mat[:, :3].T + mat[:, 3]) for m in sc.models for mat in m.matrices.astype(np.float64)])
+    lo, hi = pts.min(0), pts.max(0)
+    cell = (hi - lo) / GRID
+    rng = np.random.default_rng(30)
+    sh = rng.uniform(-0.2, 0.2, (GRID, GRID, GRID, 9, 3)).astype(np.float32)
+    sh[..., 0, :] = rng.uniform(1.0, 3.0, (GRID, GRID, GRID, 3)).astype(np.float32)
+    reach, R, alphas = float(np.linalg.norm(cell)), 8, (0.1, 0.2, 0.4, 0.7, 1.0)
+    m1 = rng.uniform(0.3, 1.5, (GRID ** 3, R * R)).astype(np.float32) * np.float32(reach)
+    m2 = m1 * m1 + (rng.uniform(0.0, 0.3, m1.shape).astype(np.float32) * np.float32(reach)) ** 2
+    table = rng.uniform(0.0, 2.0, (GRID ** 3, len(alphas), R * R, 4)).astype(np.float32)
+    table[..., 3] = 0.0
+    shell = [m.name for m in sc.models].index("cb_main")
+    tex, grad = rng.uniform(0.0, 1.0, (SIZE, SIZE, 3)).astype(np.float32), rng.uniform(-0.5, 0.5, (SIZE, SIZE, 3, 3)).astype(np.float32)
+    report = {"width": W, "height": H, "map": SIZE, "grid": GRID, "calls": args.calls, "what": "endings", "baked_ms": {}, "baked_sha1": {}}
+    for grid, vis, spec, dirn in [(g, v, s, d) for d in (0, 1) for g in (0, 1) for v in (0, 1) for s in (0, 1) if g or not (v or s)]:
+        r = api.Renderer(sc, W, H, max_bounces=DEPTH)
+        r.set_lightmap(shell, 0, tex)
+        if dirn:
+            r.set_lightmap_directional(shell, 0, grad)
+        if grid:
+            r.set_probe_grid(lo + 0.5 * cell, cell, sh, normal_bias=0.01 * float(cell.min()))
+        if vis:
+            r.set_probe_grid_depth(np.stack([m1, m2], axis=-1), 0.0, True)
+        if spec:
+            r.set_probe_grid_radiance(table, alphas)
+        for k in HOPS:
+            view = lambda n, k=k: r.render_baked(n, 1, follow=k, unlit=(0.5, 0.5, 0.5), download=False)
+            view(0)
+            ms = report["baked_ms"][f"grid {grid} vis {vis} spec {spec} dir {dirn}, K = {k}"] = []
+            for rep in range(args.reps):
+                ms.append(round(timed(lambda: view(1 + rep), args.calls), 4))
+            report["baked_sha1"][f"grid {grid} vis {vis} spec {spec} dir {dirn}, K = {k}"] = hashlib.sha1(r.read_baked().tobytes()).hexdigest()
+        del r
     emit(report, args.out)
 
 
