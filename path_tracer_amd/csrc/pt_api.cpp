@@ -280,32 +280,58 @@ int dev_alloc(pt_ctx* c, DevBuf& b, size_t bytes)
     return PT_OK;
 }
 
-// Device buffers of one call, freed when it returns.  in() uploads an input (src null: allocates only) and the copy has finished when it
-// returns, before any launch that reads it; out() allocates an output; download() synchronises the context's stream, then copies back.
-// After a failure in() and out() return null and `err` holds the code.
+// Device buffers of one call, one hipMalloc each, freed when it returns.  Every member counts elements of the device type T; the host's S is T
+// itself or the float / uint32_t words that f4, f2 and uint2 records are handed over as.  in() uploads an input (host null: allocates only)
+// and the copy has finished when it returns, before any launch that reads it; out(count) is scratch; out(host, count) and inout() are
+// results, copied back by fetch() in the order they were named (host null: an output the caller declined, allocated and left behind);
+// expect() names a result whose buffer is picked after the launches.  After a failure in() and out() return null and `err` holds the code.
 struct Staging
 {
     pt_ctx* c;
     int err = PT_OK;
     std::vector<DevBuf> bufs;
+    struct Result { void* host; const void* dev; size_t bytes; };
+    std::vector<Result> results;
     explicit Staging(pt_ctx* c_) : c(c_) {}
-    void* in(const void* src, size_t bytes)
+    template <class T, class S> const T* in(const S* host, size_t count) { return in_rw<T>(host, count); }
+    template <class T, class S> T* in_rw(const S* host, size_t count) { return (T*)alloc(host, bytes<T, S>(count)); } // an input the kernels go on to write
+    template <class T> T* out(size_t count) { return (T*)alloc(nullptr, count * sizeof(T)); }
+    template <class T, class S> T* out(S* host, size_t count) { T* d = out<T>(count); expect(host, d, count); return d; }
+    template <class T, class S> T* inout(S* host, size_t count) { T* d = in_rw<T>(host, count); expect(host, d, count); return d; }
+    template <class T, class S> void expect(S* host, const T* dev, size_t count) { if (host && dev) results.push_back({host, dev, bytes<T, S>(count)}); }
+    // the launches' error, one wait for the context's stream, then every result
+    int fetch()
+    {
+        if (err) return err;
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        for (const Result& o : results) HIPCHK(c, hipMemcpy(o.host, o.dev, o.bytes, hipMemcpyDeviceToHost));
+        results.clear();
+        return PT_OK;
+    }
+    // one buffer (or a part of one) at once, for a call that brings results back as it goes
+    template <class T, class S> int fetch(S* host, const T* dev, size_t count) { expect(host, dev, count); return fetch(); }
+
+private:
+    template <class T, class S> static size_t bytes(size_t count)
+    {
+        static_assert(sizeof(T) % sizeof(S) == 0, "a device record is whole host words");
+        return count * sizeof(T);
+    }
+    void* alloc(const void* host, size_t n_bytes)
     {
         DevBuf b;
-        if (err || (err = dev_alloc(c, b, bytes))) return nullptr;
-        const hipError_t e = src ? hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice) : hipSuccess;
+        if (err || (err = dev_alloc(c, b, n_bytes))) return nullptr;
+        const hipError_t e = host ? hipMemcpy(b.p, host, n_bytes, hipMemcpyHostToDevice) : hipSuccess;
         if (e != hipSuccess) { err = fail(c, PT_ERR_HIP, hipGetErrorString(e)); return nullptr; }
         bufs.push_back(std::move(b));
         return bufs.back().p;
     }
-    void* out(size_t bytes) { return in(nullptr, bytes); }
-    int download(void* dst, const void* src, size_t bytes)
-    {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
-        return PT_OK;
-    }
 };
+
+// the i-th of an array of 3-float records, as the C-ABI hands positions, directions and colours over
+inline f3 load3(const float* p, size_t i) { return f3{p[3 * i], p[3 * i + 1], p[3 * i + 2]}; }
+inline void store3(float* p, size_t i, f3 v) { p[3 * i] = v.x; p[3 * i + 1] = v.y; p[3 * i + 2] = v.z; }
 
 void compute_rows(pt_ctx* c)
 {
@@ -1365,7 +1391,7 @@ struct RenderBatches
     std::chrono::steady_clock::time_point t0{};
     int planned(uint32_t batch, uint32_t)
     {
-        if (samples_out) d_samples = (f4*)st.out((size_t)batch * c->local_pixels * 16);
+        if (samples_out) d_samples = st.out<f4>((size_t)batch * c->local_pixels);
         t0 = std::chrono::steady_clock::now();
         return st.err;
     }
@@ -1375,7 +1401,7 @@ struct RenderBatches
         int r;
         if (!samples_out) return PT_OK;
         if ((r = harvest_batch(c, first.spec.pipe))) return r;
-        return st.download(samples_out + (size_t)(first.spec.first_sample - first_sample) * c->local_pixels * 4, d_samples, (size_t)first.spec.count * c->local_pixels * 16);
+        return st.fetch(samples_out + (size_t)(first.spec.first_sample - first_sample) * c->local_pixels * 4, d_samples, (size_t)first.spec.count * c->local_pixels);
     }
     // On PT_ERR_LIMIT some batches have added incomplete samples to the frame: drop the partial sums so that nothing stale can be read back
     // as a result (pt_api.h: the accumulation is reset by a failed render).
@@ -1484,10 +1510,10 @@ int bake_rays(pt_ctx* c, Staging& st, uint32_t n_items, uint32_t n_samples, Fill
     const uint64_t cut = (uint64_t)c->cfg.batch_spp * n_items;
     const uint32_t batch_rays = (uint32_t)std::min<uint64_t>(cut, (1ull << 29) - 1);
     const uint32_t chunk = (uint32_t)std::min<uint64_t>(total, batch_rays ? std::min<uint64_t>(3ull * batch_rays, 1ull << 26) : (1ull << 26));
-    float* d_o = (float*)st.out((size_t)chunk * 12);
-    float* d_d = (float*)st.out((size_t)chunk * 12);
-    uint2* d_key = (uint2*)st.out((size_t)chunk * 8);
-    f4* d_rad = (f4*)st.out((size_t)chunk * 16);
+    float* d_o = st.out<float>(3 * (size_t)chunk);
+    float* d_d = st.out<float>(3 * (size_t)chunk);
+    uint2* d_key = st.out<uint2>(chunk);
+    f4* d_rad = st.out<f4>(chunk);
     if (st.err) return st.err;
     int r;
     for (uint64_t first = 0; first < total; first += chunk)
@@ -1497,6 +1523,42 @@ int bake_rays(pt_ctx* c, Staging& st, uint32_t n_items, uint32_t n_samples, Fill
         if ((r = integrate_rays_device(c, cnt, d_o, d_d, d_key, 1u, batch_rays, d_rad, nullptr, nullptr))) return r;
         fold(first, cnt, d_d, d_rad);
         HIPCHK(c, hipGetLastError());
+    }
+    return PT_OK;
+}
+
+// The rays of a census (pt_probe_backfaces, pt_bake_probe_depth): bake_probes' rays through a ray table of at most 2^21 at a time, in buffers
+// of `st`: filled (k_probe_rays), queued, traced once (an empty world traces nothing: every hit record is a miss), folded per probe in sample
+// order (fold).  pt_config.batch_spp cuts here as it cuts the bake (tables of 3 * batch_spp * n_probes rays): results do not depend on the cut.
+template <class Fold>
+int probe_trace_rays(pt_ctx* c, Staging& st, const ProbeBake& pb, Fold&& fold)
+{
+    const uint64_t total = (uint64_t)pb.n_probes * pb.n_samples;
+    const uint64_t cut = c->cfg.batch_spp ? 3ull * c->cfg.batch_spp * pb.n_probes : total;
+    const uint32_t chunk = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(total, cut), 1ull << 21);
+    float* d_o = st.out<float>(3 * (size_t)chunk);
+    float* d_d = st.out<float>(3 * (size_t)chunk);
+    uint2* d_key = st.out<uint2>(chunk);
+    const RayQueue q{st.out<f4>(chunk), st.out<f4>(chunk)};
+    f4* d_hit = st.out<f4>(chunk);
+    const size_t head_words = (size_t)32 + kHeadWordsPerQueue;
+    uint32_t* d_head = st.out<uint32_t>(head_words);
+    if (st.err) return st.err;
+    c->hook_log.clear();
+    const LaunchLogScope logging(&c->hook_log);
+    for (uint64_t first = 0; first < total; first += chunk)
+    {
+        const uint32_t cnt = (uint32_t)std::min<uint64_t>(chunk, total - first);
+        launch_probe_rays(c->stream, pb, first, cnt, d_o, d_d, d_key);
+        if (c->sv.world_root == MISS_ID) HIPCHK(c, hipMemsetAsync(d_hit, 0xff, (size_t)cnt * sizeof(f4), c->stream)); // id = MISS_ID
+        else
+        {
+            HIPCHK(c, hipMemsetAsync(d_head, 0, head_words * sizeof(uint32_t), c->stream));
+            launch_rays_to_queue(c->stream, cnt, d_o, d_d, q, d_head);
+            launch_trace_rays_closest(c->stream, trace_launch(c), c->sv.world_root, q, cnt, d_head, d_hit);
+        }
+        fold(first, cnt, d_d, d_hit);
+        HIPCHK(c, hipGetLastError()); // (a refused launch ends the loop)
     }
     return PT_OK;
 }
@@ -1729,22 +1791,21 @@ int lightmap_texels_device(pt_ctx* c, Staging& st, const HostModel& m, uint32_t 
     const size_t px = (size_t)w * h;
     const std::vector<uint2> items = lightmap_items(m, w, h);
     LightmapView lm{};
-    lm.uv = (const float*)st.in(m.uvs.data(), (size_t)m.n_tris * 24);
-    lm.positions = (const float*)st.in(m.positions.data(), (size_t)m.n_tris * 36);
-    lm.normals = (const float*)st.in(m.normals.data(), (size_t)m.n_tris * 36);
+    lm.uv = st.in<float>(m.uvs.data(), 6 * (size_t)m.n_tris);
+    lm.positions = st.in<float>(m.positions.data(), 9 * (size_t)m.n_tris);
+    lm.normals = st.in<float>(m.normals.data(), 9 * (size_t)m.n_tris);
     lm.n_tris = m.n_tris; lm.w = w; lm.h = h;
     lm.m = m.matrices[instance];
-    const uint2* d_items = items.empty() ? nullptr : (const uint2*)st.in(items.data(), items.size() * 8);
-    out.prim = (uint32_t*)st.out(px * 4);
-    out.uv2 = (float*)st.out(px * 8);
-    out.position = (float*)st.out(px * 12);
-    out.normal = (float*)st.out(px * 12);
-    out.coverage = (uint8_t*)st.out(px);
+    const uint2* d_items = items.empty() ? nullptr : st.in<uint2>(items.data(), items.size());
+    out.prim = st.out<uint32_t>(px);
+    out.uv2 = st.out<float>(2 * px);
+    out.position = st.out<float>(3 * px);
+    out.normal = st.out<float>(3 * px);
+    out.coverage = st.out<uint8_t>(px);
     if (st.err) return st.err;
     launch_lightmap_cover(c->stream, lm, d_items, (uint32_t)items.size(), out.prim);
     launch_lightmap_resolve(c->stream, lm, out.prim, out.uv2, out.position, out.normal, out.coverage);
-    HIPCHK(c, hipGetLastError());
-    out.view = lm;
+    out.view = lm; // (the caller's fetch() reports a refused launch)
     return PT_OK;
 }
 
@@ -2083,10 +2144,10 @@ struct SurfaceQueries { const uint32_t *instance, *tri; const float *u, *v; };
 static SurfaceQueries upload_queries(Staging& st, uint32_t n, const uint32_t* instance, const std::vector<uint32_t>& tri, const float* u, const float* v)
 {
     SurfaceQueries q;
-    q.instance = (const uint32_t*)st.in(instance, (size_t)n * 4);
-    q.tri = (const uint32_t*)st.in(tri.data(), (size_t)n * 4);
-    q.u = (const float*)st.in(u, (size_t)n * 4);
-    q.v = (const float*)st.in(v, (size_t)n * 4);
+    q.instance = st.in<uint32_t>(instance, n);
+    q.tri = st.in<uint32_t>(tri.data(), n);
+    q.u = st.in<float>(u, n);
+    q.v = st.in<float>(v, n);
     return q;
 }
 
@@ -2108,18 +2169,17 @@ int pt_surface_colour(pt_ctx* c, int on_device, uint32_t n, const uint32_t* inst
         {
             const DMaterial& dm = f.materials[f.instances[instance[i]].material];
             const f3 col = surface_colour(tv, dm.texture, f3{dm.colour[0], dm.colour[1], dm.colour[2]}, tri[i], u[i], v[i]);
-            rgb[3 * (size_t)i] = col.x; rgb[3 * (size_t)i + 1] = col.y; rgb[3 * (size_t)i + 2] = col.z;
+            store3(rgb, i, col);
         }
         return PT_OK;
     }
     if ((r = upload_scene(c))) return r;
     Staging st(c);
     const SurfaceQueries q = upload_queries(st, n, instance, tri, u, v);
-    float* d_rgb = (float*)st.out((size_t)n * 12);
+    float* d_rgb = st.out<float>(rgb, 3 * (size_t)n);
     if (st.err) return st.err;
     launch_surface_colour(c->stream, c->sv, c->tex, n, q.instance, q.tri, q.u, q.v, d_rgb);
-    HIPCHK(c, hipGetLastError());
-    return st.download(rgb, d_rgb, (size_t)n * 12);
+    return st.fetch();
 }
 
 int pt_shading_normal(pt_ctx* c, int on_device, uint32_t n, const uint32_t* instance, const uint32_t* prim, const float* u, const float* v, const float* dir_xyz,
@@ -2141,8 +2201,8 @@ int pt_shading_normal(pt_ctx* c, int on_device, uint32_t n, const uint32_t* inst
         {
             bool front;
             const f3 nn = shading_normal(f.tri_shade.data(), f.instances.data(), f.materials.data(), tv, instance[i], tri[i], u[i], v[i],
-                                         f3{dir_xyz[3 * (size_t)i], dir_xyz[3 * (size_t)i + 1], dir_xyz[3 * (size_t)i + 2]}, front);
-            out_normal_xyz[3 * (size_t)i] = nn.x; out_normal_xyz[3 * (size_t)i + 1] = nn.y; out_normal_xyz[3 * (size_t)i + 2] = nn.z;
+                                         load3(dir_xyz, i), front);
+            store3(out_normal_xyz, i, nn);
             out_front[i] = front ? 1 : 0;
         }
         return PT_OK;
@@ -2150,13 +2210,12 @@ int pt_shading_normal(pt_ctx* c, int on_device, uint32_t n, const uint32_t* inst
     if ((r = upload_scene(c))) return r;
     Staging st(c);
     const SurfaceQueries q = upload_queries(st, n, instance, tri, u, v);
-    const float* d_dir = (const float*)st.in(dir_xyz, (size_t)n * 12);
-    float* d_out = (float*)st.out((size_t)n * 16);
+    const float* d_dir = st.in<float>(dir_xyz, 3 * (size_t)n);
+    std::vector<float> out4((size_t)n * 4); // normal | front, as the kernel writes them
+    float* d_out = st.out<float>(out4.data(), out4.size());
     if (st.err) return st.err;
     launch_shading_normal(c->stream, c->sv, c->tex, n, q.instance, q.tri, q.u, q.v, d_dir, d_out);
-    HIPCHK(c, hipGetLastError());
-    std::vector<float> out4((size_t)n * 4);
-    if ((r = st.download(out4.data(), d_out, (size_t)n * 16))) return r;
+    if ((r = st.fetch())) return r;
     for (uint32_t i = 0; i < n; ++i)
     {
         for (int k = 0; k < 3; ++k) out_normal_xyz[3 * (size_t)i + k] = out4[4 * (size_t)i + k];
@@ -2823,11 +2882,11 @@ int pt_post_temporal_options(pt_ctx* c, int on_device, uint32_t w, uint32_t h, c
                              float* out_colour_n, float* out_moments2, float* out_variance)
 {
     if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
     if (!prev_colour_n || !prev_moments2 || !prev_position_xyzt || !prev_normal_xyz || !prev_model || !input_rgba || !position_xyzt || !normal_xyz || !model ||
         !out_colour_n || !out_moments2 || !out_variance || !w || !h)
         return fail(c, PT_ERR_ARG, "pt_post_temporal: null image or empty size");
     if ((uint64_t)w * h > 0x7fffffffull) return fail(c, PT_ERR_ARG, "pt_post_temporal: image too large");
-    std::lock_guard<std::mutex> lk(c->mu);
     TemporalK tk{};
     DenoiseK k{};
     int r;
@@ -2865,26 +2924,24 @@ int pt_post_temporal_options(pt_ctx* c, int on_device, uint32_t w, uint32_t h, c
     TemporalImages im{};
     im.w = (int)w;
     im.h = (int)h;
-    im.hist = (const f4*)t.in(prev_colour_n, px * 16);
-    im.mom = (const f2*)t.in(prev_moments2, px * 8);
-    im.xq = (const f4*)t.in(prev_position_xyzt, px * 16);
-    im.gq = (const f4*)t.in(gq.data(), px * 16);
-    im.cur = (const f4*)t.in(input_rgba, px * 16);
-    im.pos = (const f4*)t.in(position_xyzt, px * 16);
-    im.nrm = (const f4*)t.in(nr.data(), px * 16);
-    im.model = (const uint32_t*)t.in(model, px * 4);
-    im.xprev = xprev_xyzt ? (const f4*)t.in(xprev_xyzt, px * 16) : im.pos;
-    im.nprev = nprev_xyz ? (const f4*)t.in(np.data(), px * 16) : im.nrm;
-    im.vel = velocity ? (const f2*)t.in(velocity, px * 8) : nullptr;
-    f4* dh = (f4*)t.out(px * 16);
-    f2* dm = (f2*)t.out(px * 8);
-    float* dv = (float*)t.out(px * 4);
+    im.hist = t.in<f4>(prev_colour_n, px);
+    im.mom = t.in<f2>(prev_moments2, px);
+    im.xq = t.in<f4>(prev_position_xyzt, px);
+    im.gq = t.in<f4>(gq.data(), px);
+    im.cur = t.in<f4>(input_rgba, px);
+    im.pos = t.in<f4>(position_xyzt, px);
+    im.nrm = t.in<f4>(nr.data(), px);
+    im.model = t.in<uint32_t>(model, px);
+    im.xprev = xprev_xyzt ? t.in<f4>(xprev_xyzt, px) : im.pos;
+    im.nprev = nprev_xyz ? t.in<f4>(np.data(), px) : im.nrm;
+    im.vel = velocity ? t.in<f2>(velocity, px) : nullptr;
+    f4* dh = t.out<f4>(out_colour_n, px);
+    f2* dm = t.out<f2>(out_moments2, px);
+    float* dv = t.out<float>(out_variance, px);
     if (t.err) return t.err;
     launch_temporal_reproject(c->stream, im, tk, rescue, mean_length, nullptr, nullptr, dh, dm);
     launch_temporal_variance(c->stream, (int)w, (int)h, k, tk.alpha, dh, dm, im.pos, im.nrm, im.model, nullptr, nullptr, dv);
-    HIPCHK(c, hipGetLastError());
-    if ((r = t.download(out_colour_n, dh, px * 16)) || (r = t.download(out_moments2, dm, px * 8))) return r;
-    return t.download(out_variance, dv, px * 4);
+    return t.fetch();
 }
 
 int pt_present(pt_ctx* c, float* rgba)
@@ -2943,15 +3000,14 @@ int pt_post_velocity(pt_ctx* c, uint32_t w, uint32_t h, const float* position, c
 {
     if (!c || !position || !last_inv_projection || !velocity || !w || !h) return PT_ERR_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
-    int r;
-    if ((r = ensure_device(c))) return r;
+    if (int r = ensure_device(c)) return r;
     Staging t(c);
     const size_t px = (size_t)w * h;
-    const f4* dp = (const f4*)t.in(position, px * 16);
-    float* dv = (float*)t.out(px * 8);
+    const f4* dp = t.in<f4>(position, px);
+    float* dv = t.out<float>(velocity, 2 * px);
     if (t.err) return t.err;
     launch_post_velocity(c->stream, (int)w, (int)h, dp, last_inv_projection, dv);
-    return t.download(velocity, dv, px * 8);
+    return t.fetch();
 }
 
 int pt_post_motion(pt_ctx* c, uint32_t w, uint32_t h, const float* position, const uint32_t* instance, uint32_t n_instances, const float* matrix12,
@@ -2975,61 +3031,58 @@ int pt_post_motion(pt_ctx* c, uint32_t w, uint32_t h, const float* position, con
         rows[i].moved = std::memcmp(matrix12 + 12 * (size_t)i, rows[i].prv, 48) != 0 ? 1u : 0u;
     }
     Staging t(c);
-    const f4* dp = (const f4*)t.in(position, px * 16);
-    const uint32_t* di = (const uint32_t*)t.in(instance, px * 4);
-    const MotionRow* dr = (const MotionRow*)t.in(rows.data(), rows.size() * sizeof(MotionRow));
-    f4* dx = (f4*)t.out(px * 16);
+    const f4* dp = t.in<f4>(position, px);
+    const uint32_t* di = t.in<uint32_t>(instance, px);
+    const MotionRow* dr = t.in<MotionRow>(rows.data(), rows.size());
+    f4* dx = t.out<f4>(x_prev, px);
     if (t.err) return t.err;
     launch_post_motion(c->stream, (uint32_t)px, dp, di, n_instances, dr, dx);
-    return t.download(x_prev, dx, px * 16);
+    return t.fetch();
 }
 
 int pt_post_reproject(pt_ctx* c, uint32_t w, uint32_t h, const float* input, const float* accum, const float* velocity, const uint32_t* id, float* output)
 {
     if (!c || !input || !accum || !velocity || !id || !output || !w || !h) return PT_ERR_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
-    int r;
-    if ((r = ensure_device(c))) return r;
+    if (int r = ensure_device(c)) return r;
     Staging t(c);
     const size_t px = (size_t)w * h;
-    const f4* di = (const f4*)t.in(input, px * 16);
-    const f4* da = (const f4*)t.in(accum, px * 16);
-    const float* dv = (const float*)t.in(velocity, px * 8);
-    const uint32_t* did = (const uint32_t*)t.in(id, px * 4);
-    f4* dout = (f4*)t.out(px * 16);
+    const f4* di = t.in<f4>(input, px);
+    const f4* da = t.in<f4>(accum, px);
+    const float* dv = t.in<float>(velocity, 2 * px);
+    const uint32_t* did = t.in<uint32_t>(id, px);
+    f4* dout = t.out<f4>(output, px);
     if (t.err) return t.err;
     launch_post_reproject(c->stream, (int)w, (int)h, di, da, dv, did, dout);
-    return t.download(output, dout, px * 16);
+    return t.fetch();
 }
 
 int pt_post_tonemap(pt_ctx* c, uint32_t w, uint32_t h, const float* accum, float* out)
 {
     if (!c || !accum || !out || !w || !h) return PT_ERR_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
-    int r;
-    if ((r = ensure_device(c))) return r;
+    if (int r = ensure_device(c)) return r;
     Staging t(c);
     const size_t px = (size_t)w * h;
-    const f4* da = (const f4*)t.in(accum, px * 16);
-    f4* dout = (f4*)t.out(px * 16);
+    const f4* da = t.in<f4>(accum, px);
+    f4* dout = t.out<f4>(out, px);
     if (t.err) return t.err;
     launch_post_tonemap(c->stream, (uint32_t)px, da, dout);
-    return t.download(out, dout, px * 16);
+    return t.fetch();
 }
 
 int pt_post_rgb8(pt_ctx* c, uint32_t w, uint32_t h, const float* accum, uint8_t* rgb)
 {
     if (!c || !accum || !rgb || !w || !h) return PT_ERR_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
-    int r;
-    if ((r = ensure_device(c))) return r;
+    if (int r = ensure_device(c)) return r;
     Staging t(c);
     const size_t px = (size_t)w * h;
-    const f4* da = (const f4*)t.in(accum, px * 16);
-    uint8_t* dout = (uint8_t*)t.out(px * 3);
+    const f4* da = t.in<f4>(accum, px);
+    uint8_t* dout = t.out<uint8_t>(rgb, 3 * px);
     if (t.err) return t.err;
     launch_post_rgb8(c->stream, (uint32_t)px, da, dout);
-    return t.download(rgb, dout, px * 3);
+    return t.fetch();
 }
 
 // ---- denoiser: first-hit guides + edge-aware a-trous filter
@@ -3250,13 +3303,13 @@ int post_denoise_locked(pt_ctx* c, uint32_t w, uint32_t h, const DenoiseK& k, co
     const size_t px = (size_t)w * h;
     const std::vector<f4> nr = widen_xyz(normal, px), al = widen_xyz(albedo, albedo ? px : 0);
     DenoiseImages im{};
-    im.accum = (const f4*)t.in(accum, px * 16);
-    im.position = (const f4*)t.in(position, px * 16);
-    im.normal = (const f4*)t.in(nr.data(), px * 16);
-    if (albedo) im.albedo = (const f4*)t.in(al.data(), px * 16);
-    im.model = (const uint32_t*)t.in(model, px * 4);
-    im.moments = sumsq ? (const float*)t.in(sumsq, px * 4) : nullptr;
-    im.out = (f4*)t.out(px * 16);
+    im.accum = t.in<f4>(accum, px);
+    im.position = t.in<f4>(position, px);
+    im.normal = t.in<f4>(nr.data(), px);
+    if (albedo) im.albedo = t.in<f4>(al.data(), px);
+    im.model = t.in<uint32_t>(model, px);
+    im.moments = sumsq ? t.in<float>(sumsq, px) : nullptr;
+    im.out = t.out<f4>(out, px);
     if (t.err) return t.err;
     if ((r = denoise_scratch(c, px)) || (albedo && (r = dev_alloc(c, c->d_dn_k, px * 16)))) return r;
     im.cv_a = (f4*)c->d_dn_a.p;
@@ -3264,8 +3317,7 @@ int post_denoise_locked(pt_ctx* c, uint32_t w, uint32_t h, const DenoiseK& k, co
     im.nv = (f4*)c->d_dn_nv.p;
     im.kd = (f4*)c->d_dn_k.p;
     launch_denoise(c->stream, (int)w, (int)h, k, im);
-    HIPCHK(c, hipGetLastError());
-    return t.download(out, im.out, px * 16);
+    return t.fetch();
 }
 
 int accumulate_albedo_locked(pt_ctx* c, uint32_t first_sample, uint32_t n_samples, uint32_t max_hops, const char* who);
@@ -3359,9 +3411,9 @@ int pt_post_denoise(pt_ctx* c, uint32_t w, uint32_t h, const pt_denoise_params* 
                     const uint32_t* model, const float* sumsq, float* out)
 {
     if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
     if (!accum || !position || !normal || !model || !out || !w || !h) return fail(c, PT_ERR_ARG, "pt_post_denoise: null image or empty size");
     if ((uint64_t)w * h > 0x7fffffffull) return fail(c, PT_ERR_ARG, "pt_post_denoise: image too large");
-    std::lock_guard<std::mutex> lk(c->mu);
     DenoiseK k{};
     int r;
     if ((r = denoise_params(c, p, k))) return r;
@@ -3449,9 +3501,9 @@ int pt_post_denoise_albedo(pt_ctx* c, uint32_t w, uint32_t h, const pt_denoise_p
                            const uint32_t* model, const float* albedo, const float* sumsq, float* out)
 {
     if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
     if (!accum || !position || !normal || !model || !albedo || !out || !w || !h) return fail(c, PT_ERR_ARG, "pt_post_denoise_albedo: null image or empty size");
     if ((uint64_t)w * h > 0x7fffffffull) return fail(c, PT_ERR_ARG, "pt_post_denoise_albedo: image too large");
-    std::lock_guard<std::mutex> lk(c->mu);
     DenoiseK k{};
     int r;
     if ((r = denoise_params(c, p, k))) return r;
@@ -3479,18 +3531,16 @@ int pt_integrate_rays(pt_ctx* c, uint64_t n, const float* o, const float* d, con
     std::vector<uint2> keys(n);
     for (uint64_t i = 0; i < n; ++i) keys[i] = make_uint2(key[i], sample[i]);
     Staging st(c);
-    const float* d_o = (const float*)st.in(o, n * 12);
-    const float* d_d = (const float*)st.in(d, n * 12);
-    const uint2* d_key = (const uint2*)st.in(keys.data(), n * 8);
-    f4* d_rad = radiance ? (f4*)st.out(n * 16) : nullptr;
-    f4* d_pos = position ? (f4*)st.out(n * 16) : nullptr;
-    uint8_t* d_id = id ? (uint8_t*)st.out(n) : nullptr;
+    const float* d_o = st.in<float>(o, 3 * n);
+    const float* d_d = st.in<float>(d, 3 * n);
+    const uint2* d_key = st.in<uint2>(keys.data(), n);
+    // (a declined output is not allocated: the batches skip its writes)
+    f4* d_rad = radiance ? st.out<f4>(radiance, n) : nullptr;
+    f4* d_pos = position ? st.out<f4>(position, n) : nullptr;
+    uint8_t* d_id = id ? st.out<uint8_t>(id, n) : nullptr;
     if (st.err) return st.err;
     if ((r = integrate_rays_device(c, n, d_o, d_d, d_key, p->draws_consumed, p->batch_rays, d_rad, d_pos, d_id))) return r;
-    if (radiance && (r = st.download(radiance, d_rad, n * 16))) return r;
-    if (position && (r = st.download(position, d_pos, n * 16))) return r;
-    if (id && (r = st.download(id, d_id, n))) return r;
-    return PT_OK;
+    return st.fetch();
 }
 
 int pt_integrate_rays_device(pt_ctx* c, uint64_t n, const float* o, const float* d, const uint32_t* key, const uint32_t* sample, const pt_rays_params* p,
@@ -3545,14 +3595,14 @@ int pt_bake_probes(pt_ctx* c, uint32_t n_probes, const float* position, const pt
     if (n_probes == 0) return PT_OK;
     if ((r = upload_scene(c))) return r;
     Staging st(c);
-    const float* d_position = (const float*)st.in(position, (size_t)n_probes * 12);
-    float* d_sh = (float*)st.in(sh27, (size_t)n_probes * 27 * 4);
+    const float* d_position = st.in<float>(position, 3 * (size_t)n_probes);
+    float* d_sh = st.inout<float>(sh27, 27 * (size_t)n_probes);
     const ProbeBake pb{d_position, n_probes, p->first_sample, p->n_samples, p->key_base, c->cfg.n_sobol, c->cfg.seed};
     if ((r = bake_rays(c, st, n_probes, p->n_samples,
                        [&](uint64_t first, uint32_t cnt, float* o, float* d, uint2* key) { launch_probe_rays(c->stream, pb, first, cnt, o, d, key); },
                        [&](uint64_t first, uint32_t cnt, const float* d, const f4* rad) { launch_probe_project(c->stream, pb, first, cnt, d, rad, d_sh); })))
         return r;
-    return st.download(sh27, d_sh, (size_t)n_probes * 27 * 4);
+    return st.fetch();
 }
 
 // ---- lightmaps
@@ -3587,8 +3637,8 @@ int pt_lightmap_texels(pt_ctx* c, int model, uint32_t instance, uint32_t w, uint
             lm_resolve_host(m.uvs.data(), m.positions.data(), m.normals.data(), m.matrices[instance], w, h, k, t, &u32, &v32, &P, &n);
             if (prim) prim[k] = t;
             if (uv2) { uv2[2 * k] = u32; uv2[2 * k + 1] = v32; }
-            if (position) { position[3 * k] = P.x; position[3 * k + 1] = P.y; position[3 * k + 2] = P.z; }
-            if (normal) { normal[3 * k] = n.x; normal[3 * k + 1] = n.y; normal[3 * k + 2] = n.z; }
+            if (position) store3(position, k, P);
+            if (normal) store3(normal, k, n);
         }
         return PT_OK;
     }
@@ -3596,12 +3646,11 @@ int pt_lightmap_texels(pt_ctx* c, int model, uint32_t instance, uint32_t w, uint
     Staging st(c);
     LightmapDev t{};
     if ((r = lightmap_texels_device(c, st, m, instance, w, h, t))) return r;
-    if (prim && (r = st.download(prim, t.prim, px * 4))) return r;
-    if (uv2 && (r = st.download(uv2, t.uv2, px * 8))) return r;
-    if (position && (r = st.download(position, t.position, px * 12))) return r;
-    if (normal && (r = st.download(normal, t.normal, px * 12))) return r;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return PT_OK;
+    st.expect(prim, t.prim, px);
+    st.expect(uv2, t.uv2, 2 * px);
+    st.expect(position, t.position, 3 * px);
+    st.expect(normal, t.normal, 3 * px);
+    return st.fetch();
 }
 
 } // extern "C"
@@ -3630,17 +3679,17 @@ int bake_lightmap_locked(pt_ctx* c, const pt_lightmap_params* p, float* rgb_sum,
     if ((r = lightmap_texels_device(c, st, m, p->instance, p->w, p->h, t))) return r;
     // the covered texels in ascending order, so that neighbouring texels share a wave: the coverage bytes come back and are scanned here
     std::vector<uint8_t> cov(px);
-    if ((r = st.download(cov.data(), t.coverage, px))) return r;
+    if ((r = st.fetch(cov.data(), t.coverage, px))) return r;
     std::vector<uint32_t> texels;
     for (size_t k = 0; k < px; ++k)
         if (cov[k]) texels.push_back((uint32_t)k);
     const uint32_t n_cov = (uint32_t)texels.size();
     if (n_cov > 0)
     {
-        const uint32_t* d_texels = (const uint32_t*)st.in(texels.data(), (size_t)n_cov * 4);
-        float* d_sum = (float*)st.in(rgb_sum, px * 12);
-        float* d_sq = moments ? (float*)st.in(sumsq, px * 4) : nullptr;
-        float* d_dir = directional ? (float*)st.in(dir_sum, px * 36) : nullptr;
+        const uint32_t* d_texels = st.in<uint32_t>(texels.data(), n_cov);
+        float* d_sum = st.inout<float>(rgb_sum, 3 * px);
+        float* d_dir = directional ? st.inout<float>(dir_sum, 9 * px) : nullptr;
+        float* d_sq = moments ? st.inout<float>(sumsq, px) : nullptr;
         const LightmapBake lb{d_texels, t.position, t.normal, n_cov, p->first_sample, p->n_samples, p->key_base, c->cfg.n_sobol, p->bias, c->cfg.seed};
         if ((r = bake_rays(c, st, n_cov, p->n_samples,
                            [&](uint64_t first, uint32_t cnt, float* o, float* d, uint2* key) { launch_lightmap_rays(c->stream, lb, first, cnt, o, d, key); },
@@ -3649,9 +3698,7 @@ int bake_lightmap_locked(pt_ctx* c, const pt_lightmap_params* p, float* rgb_sum,
                                else launch_lightmap_fold(c->stream, lb, first, cnt, rad, d_sum, d_sq);
                            })))
             return r;
-        if ((r = st.download(rgb_sum, d_sum, px * 12))) return r;
-        if (directional && (r = st.download(dir_sum, d_dir, px * 36))) return r;
-        if (moments && (r = st.download(sumsq, d_sq, px * 4))) return r;
+        if ((r = st.fetch())) return r;
     }
     if (coverage) std::memcpy(coverage, cov.data(), px);
     return PT_OK;
@@ -3713,12 +3760,11 @@ int pt_lightmap_gradient(pt_ctx* c, int on_device, int model, uint32_t instance,
     Staging st(c);
     LightmapDev t{};
     if ((r = lightmap_texels_device(c, st, m, instance, w, h, t))) return r;
-    const float* d_dir = (const float*)st.in(dir_sum, px * 36);
-    float* d_grad = (float*)st.out(px * 36);
+    const float* d_dir = st.in<float>(dir_sum, 9 * px);
+    float* d_grad = st.out<float>(grad, 9 * px);
     if (st.err) return st.err;
     launch_lightmap_gradient(c->stream, (uint32_t)px, t.coverage, t.normal, n_samples, d_dir, d_grad);
-    HIPCHK(c, hipGetLastError());
-    return st.download(grad, d_grad, px * 36);
+    return st.fetch();
 }
 
 int pt_lightmap_denoise(pt_ctx* c, int on_device, const pt_lightmap_denoise_params* p, const float* rgb_sum, const float* sumsq, float* rgb_mean, float* texel_area)
@@ -3753,8 +3799,8 @@ int pt_lightmap_denoise(pt_ctx* c, int on_device, const pt_lightmap_denoise_para
                 float u32, v32;
                 f3 x, n;
                 lm_resolve_host(m.uvs.data(), m.positions.data(), m.normals.data(), m.matrices[p->instance], p->w, p->h, t, owner[t], &u32, &v32, &x, &n);
-                P[3 * t] = x.x; P[3 * t + 1] = x.y; P[3 * t + 2] = x.z;
-                N[3 * t] = n.x; N[3 * t + 1] = n.y; N[3 * t + 2] = n.z;
+                store3(P.data(), t, x);
+                store3(N.data(), t, n);
             }
             lmf_filter_host(p->w, p->h, k, owner.data(), P.data(), N.data(), m.positions.data(), m.uvs.data(), rgb_sum, sumsq, p->n_samples, rgb_mean, texel_area);
         }
@@ -3767,17 +3813,14 @@ int pt_lightmap_denoise(pt_ctx* c, int on_device, const pt_lightmap_denoise_para
     if ((r = lightmap_texels_device(c, st, m, p->instance, p->w, p->h, t))) return r;
     LmFilterImages im{};
     im.prim = t.prim; im.position = t.position; im.normal = t.normal;
-    im.sum = (const float*)st.in(rgb_sum, px * 12);
-    im.sumsq = sumsq ? (const float*)st.in(sumsq, px * 4) : nullptr;
-    im.cv_a = (f4*)st.out(px * 16); im.cv_b = (f4*)st.out(px * 16); im.pa = (f4*)st.out(px * 16); im.nv = (f4*)st.out(px * 16);
-    im.rgb = (float*)st.out(px * 12);
-    im.area = texel_area ? (float*)st.out(px * 4) : nullptr;
+    im.sum = st.in<float>(rgb_sum, 3 * px);
+    im.sumsq = sumsq ? st.in<float>(sumsq, px) : nullptr;
+    im.cv_a = st.out<f4>(px); im.cv_b = st.out<f4>(px); im.pa = st.out<f4>(px); im.nv = st.out<f4>(px);
+    im.rgb = st.out<float>(rgb_mean, 3 * px);
+    im.area = texel_area ? st.out<float>(texel_area, px) : nullptr; // (the kernel skips a null area)
     if (st.err) return st.err;
     launch_lightmap_denoise(c->stream, t.view, k, p->n_samples, sumsq != nullptr, im);
-    HIPCHK(c, hipGetLastError());
-    if ((r = st.download(rgb_mean, im.rgb, px * 12))) return r;
-    if (texel_area && (r = st.download(texel_area, im.area, px * 4))) return r;
-    return PT_OK;
+    return st.fetch();
 }
 
 int pt_lightmap_dilate(pt_ctx* c, uint32_t w, uint32_t h, uint32_t passes, float* rgb, uint8_t* coverage)
@@ -3788,17 +3831,17 @@ int pt_lightmap_dilate(pt_ctx* c, uint32_t w, uint32_t h, uint32_t passes, float
     if (w == 0 || h == 0) return fail(c, PT_ERR_ARG, "lightmap: w and h must be non-zero");
     if (w > 16384u || h > 16384u || (uint64_t)w * h > (1ull << 26)) return fail(c, PT_ERR_LIMIT, "lightmap: a side is at most 16384 texels and a map holds at most 2^26");
     if (passes == 0) return PT_OK;
-    int r;
-    if ((r = ensure_device(c))) return r;
+    if (int r = ensure_device(c)) return r;
     const size_t px = (size_t)w * h;
     Staging st(c);
-    float* d_rgb[2] = {(float*)st.in(rgb, px * 12), (float*)st.out(px * 12)};
-    uint8_t* d_cov[2] = {(uint8_t*)st.in(coverage, px), (uint8_t*)st.out(px)};
+    // (each pass reads one of the pair and writes the other: the result is where the last pass left it)
+    float* d_rgb[2] = {st.in_rw<float>(rgb, 3 * px), st.out<float>(3 * px)};
+    uint8_t* d_cov[2] = {st.in_rw<uint8_t>(coverage, px), st.out<uint8_t>(px)};
     if (st.err) return st.err;
     for (uint32_t i = 0; i < passes; ++i) launch_lightmap_dilate(c->stream, w, h, d_rgb[i & 1u], d_cov[i & 1u], d_rgb[(i + 1u) & 1u], d_cov[(i + 1u) & 1u]);
-    HIPCHK(c, hipGetLastError());
-    if ((r = st.download(rgb, d_rgb[passes & 1u], px * 12))) return r;
-    return st.download(coverage, d_cov[passes & 1u], px);
+    st.expect(rgb, d_rgb[passes & 1u], 3 * px);
+    st.expect(coverage, d_cov[passes & 1u], px);
+    return st.fetch();
 }
 
 // ---- lightmaps kept by the context and the baked view (the definitions are include/pt_api.h's)
@@ -3926,7 +3969,7 @@ static int lightmap_lookup_locked(pt_ctx* c, int on_device, bool directional, ui
                 if (!directional || l->grad.empty()) col = lightmap_lookup(l->texels.data(), l->w, l->h, uv, u[i], v[i]);
                 else
                 {
-                    const f3 d{dir_xyz[3 * (size_t)i], dir_xyz[3 * (size_t)i + 1], dir_xyz[3 * (size_t)i + 2]};
+                    const f3 d = load3(dir_xyz, i);
                     bool front;
                     const f3 nrm = unperturbed_normal(f.tri_shade.data(), f.instances.data(), instance[i], tri[i], u[i], v[i], d, front);
                     f3 delta;
@@ -3934,7 +3977,7 @@ static int lightmap_lookup_locked(pt_ctx* c, int on_device, bool directional, ui
                     col = lightmap_lookup_directional(l->texels.data(), l->grad.data(), l->w, l->h, uv, u[i], v[i], delta);
                 }
             }
-            rgb[3 * (size_t)i] = col.x; rgb[3 * (size_t)i + 1] = col.y; rgb[3 * (size_t)i + 2] = col.z;
+            store3(rgb, i, col);
             mapped[i] = l ? 1u : 0u;
         }
         return PT_OK;
@@ -3944,15 +3987,13 @@ static int lightmap_lookup_locked(pt_ctx* c, int on_device, bool directional, ui
     if ((r = upload_scene(c)) || (r = ensure_lightmaps(c, lm, ld))) return r;
     Staging st(c);
     const SurfaceQueries q = upload_queries(st, n, instance, tri, u, v);
-    const float* d_dir = directional ? (const float*)st.in(dir_xyz, (size_t)n * 12) : nullptr;
-    float* d_rgb = (float*)st.out((size_t)n * 12);
-    uint8_t* d_mapped = (uint8_t*)st.out(n);
+    const float* d_dir = directional ? st.in<float>(dir_xyz, 3 * (size_t)n) : nullptr;
+    float* d_rgb = st.out<float>(rgb, 3 * (size_t)n);
+    uint8_t* d_mapped = st.out<uint8_t>(mapped, n);
     if (st.err) return st.err;
     if (directional) launch_lightmap_lookup_directional(c->stream, c->sv, c->tex, lm, ld, n, q.instance, q.tri, q.u, q.v, d_dir, d_rgb, d_mapped);
     else launch_lightmap_lookup(c->stream, lm, n, q.instance, q.tri, q.u, q.v, d_rgb, d_mapped);
-    HIPCHK(c, hipGetLastError());
-    if ((r = st.download(rgb, d_rgb, (size_t)n * 12))) return r;
-    return st.download(mapped, d_mapped, n);
+    return st.fetch();
 }
 int pt_lightmap_lookup_directional(pt_ctx* c, int on_device, uint32_t n, const uint32_t* instance, const uint32_t* prim, const float* u, const float* v,
                                    const float* dir_xyz, float* rgb, uint8_t* mapped)
@@ -4138,25 +4179,22 @@ int pt_probe_grid_lookup(pt_ctx* c, int on_device, uint32_t n, const float* posi
         (void)baked_light(c, LIGHT_GRID_HOST, l, k);
         for (uint32_t i = 0; i < n; ++i)
         {
-            const float *pp = position + 3 * (size_t)i, *pn = normal + 3 * (size_t)i;
-            const f3 P{pp[0], pp[1], pp[2]}, N{pn[0], pn[1], pn[2]};
+            const f3 P = load3(position, i), N = load3(normal, i);
             f3 col;
             lit[i] = (k.vis ? probe_grid_lookup<true>(l.grid, P, N, &col, &l.depth) : probe_grid_lookup(l.grid, P, N, &col)) ? 1u : 0u;
-            rgb[3 * (size_t)i] = col.x; rgb[3 * (size_t)i + 1] = col.y; rgb[3 * (size_t)i + 2] = col.z;
+            store3(rgb, i, col);
         }
         return PT_OK;
     }
     if ((r = ensure_device(c)) || (r = baked_light(c, LIGHT_GRID, l, k))) return r;
     Staging st(c);
-    const float* d_pos = (const float*)st.in(position, (size_t)n * 12);
-    const float* d_nrm = (const float*)st.in(normal, (size_t)n * 12);
-    float* d_rgb = (float*)st.out((size_t)n * 12);
-    uint8_t* d_lit = (uint8_t*)st.out(n);
+    const float* d_pos = st.in<float>(position, 3 * (size_t)n);
+    const float* d_nrm = st.in<float>(normal, 3 * (size_t)n);
+    float* d_rgb = st.out<float>(rgb, 3 * (size_t)n);
+    uint8_t* d_lit = st.out<uint8_t>(lit, n);
     if (st.err) return st.err;
     launch_probe_grid_lookup(c->stream, l.grid, k.vis ? &l.depth : nullptr, n, d_pos, d_nrm, d_rgb, d_lit);
-    HIPCHK(c, hipGetLastError());
-    if ((r = st.download(rgb, d_rgb, (size_t)n * 12))) return r;
-    return st.download(lit, d_lit, n);
+    return st.fetch();
 }
 
 int pt_probe_backfaces(pt_ctx* c, uint32_t n_probes, const float* position, const pt_probe_params* p, uint32_t* hits, uint32_t* back)
@@ -4170,38 +4208,16 @@ int pt_probe_backfaces(pt_ctx* c, uint32_t n_probes, const float* position, cons
     std::memset(hits, 0, (size_t)n_probes * 4);
     std::memset(back, 0, (size_t)n_probes * 4);
     if (c->sv.world_root == MISS_ID) return PT_OK; // an empty world: every ray misses
-    // the bake's rays through a ray table of at most 2^21 at a time: filled (k_probe_rays), queued, traced once, counted per probe.
-    // pt_config.batch_spp cuts here as it cuts the bake (tables of 3 * batch_spp * n_probes rays): the counts do not depend on the cut
-    const uint64_t total = (uint64_t)n_probes * p->n_samples;
-    const uint64_t cut = c->cfg.batch_spp ? 3ull * c->cfg.batch_spp * n_probes : total;
-    const uint32_t chunk = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(total, cut), 1ull << 21);
     Staging st(c);
-    const float* d_position = (const float*)st.in(position, (size_t)n_probes * 12);
-    uint32_t* d_hits = (uint32_t*)st.in(hits, (size_t)n_probes * 4);
-    uint32_t* d_back = (uint32_t*)st.in(back, (size_t)n_probes * 4);
-    float* d_o = (float*)st.out((size_t)chunk * 12);
-    float* d_d = (float*)st.out((size_t)chunk * 12);
-    uint2* d_key = (uint2*)st.out((size_t)chunk * 8);
-    const RayQueue q{(f4*)st.out((size_t)chunk * 16), (f4*)st.out((size_t)chunk * 16)};
-    f4* d_hit = (f4*)st.out((size_t)chunk * 16);
-    const size_t head_bytes = ((size_t)32 + kHeadWordsPerQueue) * 4;
-    uint32_t* d_head = (uint32_t*)st.out(head_bytes);
-    if (st.err) return st.err;
+    const float* d_position = st.in<float>(position, 3 * (size_t)n_probes);
+    uint32_t* d_hits = st.inout<uint32_t>(hits, n_probes);
+    uint32_t* d_back = st.inout<uint32_t>(back, n_probes);
     const ProbeBake pb{d_position, n_probes, p->first_sample, p->n_samples, p->key_base, c->cfg.n_sobol, c->cfg.seed};
-    c->hook_log.clear();
-    const LaunchLogScope logging(&c->hook_log);
-    for (uint64_t first = 0; first < total; first += chunk)
-    {
-        const uint32_t cnt = (uint32_t)std::min<uint64_t>(chunk, total - first);
-        launch_probe_rays(c->stream, pb, first, cnt, d_o, d_d, d_key);
-        HIPCHK(c, hipMemsetAsync(d_head, 0, head_bytes, c->stream));
-        launch_rays_to_queue(c->stream, cnt, d_o, d_d, q, d_head);
-        launch_trace_rays_closest(c->stream, trace_launch(c), c->sv.world_root, q, cnt, d_head, d_hit);
-        launch_probe_backfaces(c->stream, c->sv, pb, first, cnt, d_d, d_hit, d_hits, d_back);
-        HIPCHK(c, hipGetLastError());
-    }
-    if ((r = st.download(hits, d_hits, (size_t)n_probes * 4))) return r;
-    return st.download(back, d_back, (size_t)n_probes * 4);
+    if ((r = probe_trace_rays(c, st, pb, [&](uint64_t first, uint32_t cnt, const float* d, const f4* hit) {
+            launch_probe_backfaces(c->stream, c->sv, pb, first, cnt, d, hit, d_hits, d_back);
+        })))
+        return r;
+    return st.fetch();
 }
 
 // ---- probe visibility: the depth moments' bake, the table on the grid (the definitions are include/pt_api.h's)
@@ -4229,44 +4245,17 @@ int pt_bake_probe_depth(pt_ctx* c, uint32_t n_probes, const float* position, con
     }
     if (n_probes == 0) return PT_OK;
     if ((r = upload_scene(c))) return r;
-    // the census' ray table and cuts (pt_probe_backfaces): filled, queued, traced once, folded per probe in sample order.  An empty world
-    // traces nothing: every hit record is a miss
-    const bool empty = c->sv.world_root == MISS_ID;
     const size_t texels = (size_t)n_probes * p->res * p->res;
-    const uint64_t total = (uint64_t)n_probes * p->n_samples;
-    const uint64_t cut = c->cfg.batch_spp ? 3ull * c->cfg.batch_spp * n_probes : total;
-    const uint32_t chunk = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(total, cut), 1ull << 21);
     Staging st(c);
-    const float* d_position = (const float*)st.in(position, (size_t)n_probes * 12);
-    DProbeDepth* d_sums = (DProbeDepth*)st.in(sums, texels * 8);
-    uint32_t* d_counts = (uint32_t*)st.in(counts, texels * 4);
-    float* d_o = (float*)st.out((size_t)chunk * 12);
-    float* d_d = (float*)st.out((size_t)chunk * 12);
-    uint2* d_key = (uint2*)st.out((size_t)chunk * 8);
-    const RayQueue q{(f4*)st.out((size_t)chunk * 16), (f4*)st.out((size_t)chunk * 16)};
-    f4* d_hit = (f4*)st.out((size_t)chunk * 16);
-    const size_t head_bytes = ((size_t)32 + kHeadWordsPerQueue) * 4;
-    uint32_t* d_head = (uint32_t*)st.out(head_bytes);
-    if (st.err) return st.err;
+    const float* d_position = st.in<float>(position, 3 * (size_t)n_probes);
+    DProbeDepth* d_sums = st.inout<DProbeDepth>(sums, texels);
+    uint32_t* d_counts = st.inout<uint32_t>(counts, texels);
     const ProbeBake pb{d_position, n_probes, p->first_sample, p->n_samples, p->key_base, c->cfg.n_sobol, c->cfg.seed};
-    c->hook_log.clear();
-    const LaunchLogScope logging(&c->hook_log);
-    for (uint64_t first = 0; first < total; first += chunk)
-    {
-        const uint32_t cnt = (uint32_t)std::min<uint64_t>(chunk, total - first);
-        launch_probe_rays(c->stream, pb, first, cnt, d_o, d_d, d_key);
-        if (empty) HIPCHK(c, hipMemsetAsync(d_hit, 0xff, (size_t)cnt * 16, c->stream)); // id = MISS_ID
-        else
-        {
-            HIPCHK(c, hipMemsetAsync(d_head, 0, head_bytes, c->stream));
-            launch_rays_to_queue(c->stream, cnt, d_o, d_d, q, d_head);
-            launch_trace_rays_closest(c->stream, trace_launch(c), c->sv.world_root, q, cnt, d_head, d_hit);
-        }
-        launch_probe_depth_fold(c->stream, pb, first, cnt, d_d, d_hit, p->res, p->max_distance, d_sums, d_counts);
-        HIPCHK(c, hipGetLastError());
-    }
-    if ((r = st.download(sums, d_sums, texels * 8))) return r;
-    return st.download(counts, d_counts, texels * 4);
+    if ((r = probe_trace_rays(c, st, pb, [&](uint64_t first, uint32_t cnt, const float* d, const f4* hit) {
+            launch_probe_depth_fold(c->stream, pb, first, cnt, d, hit, p->res, p->max_distance, d_sums, d_counts);
+        })))
+        return r;
+    return st.fetch();
 }
 
 int pt_set_probe_grid_depth(pt_ctx* c, const pt_probe_depth* v, const float* moments)
@@ -4338,17 +4327,16 @@ int pt_bake_probe_radiance(pt_ctx* c, uint32_t n_probes, const float* position, 
     if ((r = upload_scene(c))) return r;
     const size_t texels = (size_t)n_probes * p->res * p->res;
     Staging st(c);
-    const float* d_position = (const float*)st.in(position, (size_t)n_probes * 12);
-    float* d_sums = (float*)st.in(rgb_sums, texels * 12);
-    uint32_t* d_counts = (uint32_t*)st.in(counts, texels * 4);
+    const float* d_position = st.in<float>(position, 3 * (size_t)n_probes);
+    float* d_sums = st.inout<float>(rgb_sums, 3 * texels);
+    uint32_t* d_counts = st.inout<uint32_t>(counts, texels);
     const ProbeBake pb{d_position, n_probes, p->first_sample, p->n_samples, p->key_base, c->cfg.n_sobol, c->cfg.seed};
     const uint32_t res = p->res;
     if ((r = bake_rays(c, st, n_probes, p->n_samples,
                        [&](uint64_t first, uint32_t cnt, float* o, float* d, uint2* key) { launch_probe_rays(c->stream, pb, first, cnt, o, d, key); },
                        [&](uint64_t first, uint32_t cnt, const float* d, const f4* rad) { launch_probe_radiance_fold(c->stream, pb, first, cnt, d, rad, res, d_sums, d_counts); })))
         return r;
-    if ((r = st.download(rgb_sums, d_sums, texels * 12))) return r;
-    return st.download(counts, d_counts, texels * 4);
+    return st.fetch();
 }
 
 // what the prefilter and the setter refuse of their levels
@@ -4400,13 +4388,12 @@ int pt_probe_radiance_prefilter(pt_ctx* c, int on_device, const pt_probe_radianc
     }
     if ((r = ensure_device(c))) return r;
     Staging st(c);
-    const float* d_sums = (const float*)st.in(rgb_sums, (size_t)f->n_probes * rr * 12);
-    const uint32_t* d_counts = (const uint32_t*)st.in(counts, (size_t)f->n_probes * rr * 4);
-    f4* d_table = (f4*)st.out((size_t)out_texels * 16);
+    const float* d_sums = st.in<float>(rgb_sums, 3 * (size_t)f->n_probes * rr);
+    const uint32_t* d_counts = st.in<uint32_t>(counts, (size_t)f->n_probes * rr);
+    f4* d_table = st.out<f4>(table, (size_t)out_texels);
     if (st.err) return st.err;
     launch_probe_radiance_prefilter(c->stream, f->res, f->n_probes, f->n_levels, f->alpha, d_sums, d_counts, d_table);
-    HIPCHK(c, hipGetLastError());
-    return st.download(table, d_table, (size_t)out_texels * 16);
+    return st.fetch();
 }
 
 int pt_set_probe_grid_radiance(pt_ctx* c, const pt_probe_radiance* v, const float* table)
@@ -4470,27 +4457,24 @@ int pt_probe_grid_specular(pt_ctx* c, int on_device, uint32_t n, const float* po
         (void)baked_light(c, LIGHT_GRID_HOST, l, k);
         for (uint32_t i = 0; i < n; ++i)
         {
-            const float *pp = position + 3 * (size_t)i, *pn = normal + 3 * (size_t)i, *pi = incoming + 3 * (size_t)i;
-            const f3 P{pp[0], pp[1], pp[2]}, N{pn[0], pn[1], pn[2]}, D{pi[0], pi[1], pi[2]};
+            const f3 P = load3(position, i), N = load3(normal, i), D = load3(incoming, i);
             f3 col;
             lit[i] = (k.vis ? probe_grid_specular<true>(l.grid, l.rad, P, N, D, alpha[i], &col, &l.depth) : probe_grid_specular(l.grid, l.rad, P, N, D, alpha[i], &col)) ? 1u : 0u;
-            rgb[3 * (size_t)i] = col.x; rgb[3 * (size_t)i + 1] = col.y; rgb[3 * (size_t)i + 2] = col.z;
+            store3(rgb, i, col);
         }
         return PT_OK;
     }
     if ((r = ensure_device(c)) || (r = baked_light(c, LIGHT_GRID, l, k))) return r;
     Staging st(c);
-    const float* d_pos = (const float*)st.in(position, (size_t)n * 12);
-    const float* d_nrm = (const float*)st.in(normal, (size_t)n * 12);
-    const float* d_inc = (const float*)st.in(incoming, (size_t)n * 12);
-    const float* d_alpha = (const float*)st.in(alpha, (size_t)n * 4);
-    float* d_rgb = (float*)st.out((size_t)n * 12);
-    uint8_t* d_lit = (uint8_t*)st.out(n);
+    const float* d_pos = st.in<float>(position, 3 * (size_t)n);
+    const float* d_nrm = st.in<float>(normal, 3 * (size_t)n);
+    const float* d_inc = st.in<float>(incoming, 3 * (size_t)n);
+    const float* d_alpha = st.in<float>(alpha, n);
+    float* d_rgb = st.out<float>(rgb, 3 * (size_t)n);
+    uint8_t* d_lit = st.out<uint8_t>(lit, n);
     if (st.err) return st.err;
     launch_probe_grid_specular(c->stream, l.grid, l.rad, k.vis ? &l.depth : nullptr, n, d_pos, d_nrm, d_inc, d_alpha, d_rgb, d_lit);
-    HIPCHK(c, hipGetLastError());
-    if ((r = st.download(rgb, d_rgb, (size_t)n * 12))) return r;
-    return st.download(lit, d_lit, n);
+    return st.fetch();
 }
 
 // ---- unit hooks
@@ -4501,23 +4485,25 @@ static uint32_t* upload_rays(Staging& t, uint32_t n, const float* o, const float
     std::vector<f4> a(n), b(n);
     for (uint32_t i = 0; i < n; ++i)
     {
-        a[i] = f4{o[3 * i], o[3 * i + 1], o[3 * i + 2], tmax ? tmax[i] : __builtin_inff()};
-        b[i] = f4{d[3 * i], d[3 * i + 1], d[3 * i + 2], from_bits(i)};
+        const f3 oi = load3(o, i), di = load3(d, i);
+        a[i] = f4{oi.x, oi.y, oi.z, tmax ? tmax[i] : __builtin_inff()};
+        b[i] = f4{di.x, di.y, di.z, from_bits(i)};
     }
     std::vector<uint32_t> head(32 + kHeadWordsPerQueue, 0u);
     head[0] = n;
-    q = RayQueue{(f4*)t.in(a.data(), (size_t)n * 16), (f4*)t.in(b.data(), (size_t)n * 16)};
-    return (uint32_t*)t.in(head.data(), head.size() * 4);
+    q = RayQueue{t.in_rw<f4>(a.data(), n), t.in_rw<f4>(b.data(), n)};
+    return t.in_rw<uint32_t>(head.data(), head.size());
 }
 
 int pt_trace_closest(pt_ctx* c, int which, uint32_t n, const float* o, const float* d, const float* tmax, float* t, float* u, float* v,
                      uint32_t* inst, uint32_t* prim)
 {
-    if (!c || !o || !d || !t || !u || !v || !inst || !prim) return PT_ERR_ARG;
+    if (!c) return PT_ERR_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
     int r;
-    if ((r = upload_scene(c))) return r;
+    if ((r = upload_scene(c))) return r; // (ahead of n == 0: a call without rays is how Renderer.trace_geometry makes the scene resident)
     if (n == 0) return PT_OK;
+    if (!o || !d || !t || !u || !v || !inst || !prim) return PT_ERR_ARG;
     const uint32_t root = which ? c->sv.lights_root : c->sv.world_root;
     if (root == MISS_ID)
     {
@@ -4527,15 +4513,15 @@ int pt_trace_closest(pt_ctx* c, int which, uint32_t n, const float* o, const flo
     Staging st(c);
     RayQueue q;
     uint32_t* dh = upload_rays(st, n, o, d, tmax, q);
-    f4* dhit = (f4*)st.out((size_t)n * 16);
+    std::vector<f4> h(n);
+    f4* dhit = st.out<f4>(h.data(), n);
     if (st.err) return st.err;
     {
         c->hook_log.clear();
         const LaunchLogScope logging(&c->hook_log);
         launch_trace_rays_closest(c->stream, trace_launch(c), root, q, n, dh, dhit);
     }
-    std::vector<f4> h(n);
-    if ((r = st.download(h.data(), dhit, (size_t)n * 16))) return r;
+    if ((r = st.fetch())) return r;
     const FlatScene& f = c->scene.flat;
     const uint32_t mask = (1u << f.prim_bits) - 1u;
     for (uint32_t i = 0; i < n; ++i)
@@ -4554,155 +4540,157 @@ int pt_trace_closest(pt_ctx* c, int which, uint32_t n, const float* o, const flo
 
 int pt_trace_any(pt_ctx* c, int which, uint32_t n, const float* o, const float* d, const float* tmax, uint8_t* hit)
 {
-    if (!c || !o || !d || !tmax || !hit) return PT_ERR_ARG;
+    if (!c) return PT_ERR_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
     int r;
-    if ((r = upload_scene(c))) return r;
+    if ((r = upload_scene(c))) return r; // (ahead of n == 0, as in pt_trace_closest)
     if (n == 0) return PT_OK;
+    if (!o || !d || !tmax || !hit) return PT_ERR_ARG;
     const uint32_t root = which ? c->sv.lights_root : c->sv.world_root;
     if (root == MISS_ID) { std::memset(hit, 0, n); return PT_OK; }
     Staging st(c);
     RayQueue q;
     uint32_t* dh = upload_rays(st, n, o, d, tmax, q);
-    uint32_t* docc = (uint32_t*)st.out((size_t)n * 4);
+    std::vector<uint32_t> h(n);
+    uint32_t* docc = st.out<uint32_t>(h.data(), n);
     if (st.err) return st.err;
     {
         c->hook_log.clear();
         const LaunchLogScope logging(&c->hook_log);
         launch_trace_rays_any(c->stream, trace_launch(c), root, q, n, dh, docc);
     }
-    std::vector<uint32_t> h(n);
-    if ((r = st.download(h.data(), docc, (size_t)n * 4))) return r;
+    if ((r = st.fetch())) return r;
     for (uint32_t i = 0; i < n; ++i) hit[i] = h[i] ? 1 : 0;
     return PT_OK;
 }
 
 int pt_ss_sobol(pt_ctx* c, uint32_t n_points, uint32_t n, const uint32_t* index, const uint32_t* seed, float* out)
 {
-    if (!c || !index || !seed || !out || n_points == 0) return PT_ERR_ARG;
+    if (!c || n_points == 0) return PT_ERR_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
-    int r;
-    if ((r = ensure_device(c))) return r;
+    if (n == 0) return PT_OK;
+    if (!index || !seed || !out) return PT_ERR_ARG;
+    if (int r = ensure_device(c)) return r;
     Staging t(c);
-    const uint32_t* di = (const uint32_t*)t.in(index, (size_t)n * 4);
-    const uint32_t* ds = (const uint32_t*)t.in(seed, (size_t)n * 4);
-    float* dout = (float*)t.out((size_t)n * 8);
+    const uint32_t* di = t.in<uint32_t>(index, n);
+    const uint32_t* ds = t.in<uint32_t>(seed, n);
+    float* dout = t.out<float>(out, 2 * (size_t)n);
     if (t.err) return t.err;
     launch_sobol_probe(c->stream, n_points, n, di, ds, dout);
-    return t.download(out, dout, (size_t)n * 8);
+    return t.fetch();
 }
 
 int pt_math_batch(pt_ctx* c, int fn, uint32_t n, const float* a, const float* b, float* o0, float* o1)
 {
-    if (!c || !a || !o0) return PT_ERR_ARG;
+    if (!c) return PT_ERR_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
-    int r;
-    if ((r = ensure_device(c))) return r;
+    if (n == 0) return PT_OK;
+    if (!a || !o0) return PT_ERR_ARG;
+    if (int r = ensure_device(c)) return r;
     Staging t(c);
-    const float* da = (const float*)t.in(a, (size_t)n * 4);
-    float* db = (float*)t.in(b, (size_t)n * 4);
-    float* d0 = (float*)t.out((size_t)n * 4);
-    float* d1 = (float*)t.out((size_t)n * 4);
+    const float* da = t.in<float>(a, n);
+    float* db = t.in_rw<float>(b, n); // (b null: zeros, below)
+    float* d0 = t.out<float>(o0, n);
+    float* d1 = t.out<float>(o1, n); // (the kernel writes both whatever the caller takes)
     if (t.err) return t.err;
     // on the probe's own stream: c->stream is non-blocking, so a hipMemset (null stream, asynchronous to the host for device memory)
     // is not ordered before the kernel and could clear what the kernel wrote
-    if (!b) HIPCHK(c, hipMemsetAsync(db, 0, (size_t)n * 4, c->stream));
-    HIPCHK(c, hipMemsetAsync(d1, 0, (size_t)n * 4, c->stream));
+    if (!b) HIPCHK(c, hipMemsetAsync(db, 0, (size_t)n * sizeof(float), c->stream));
+    HIPCHK(c, hipMemsetAsync(d1, 0, (size_t)n * sizeof(float), c->stream));
     launch_math_probe(c->stream, fn, n, da, db, d0, d1, c->cfg.seed);
-    if ((r = t.download(o0, d0, (size_t)n * 4))) return r;
-    return o1 ? t.download(o1, d1, (size_t)n * 4) : PT_OK;
+    return t.fetch();
 }
 
 int pt_material_eval(pt_ctx* c, int material, uint32_t n, const float* incoming, const float* normal, const uint8_t* front, const uint32_t* pixel,
                      const uint32_t* sample, uint32_t draws, float* out9)
 {
-    if (!c || !incoming || !normal || !front || !pixel || !sample || !out9) return PT_ERR_ARG;
+    if (!c) return PT_ERR_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
     if (material < 0 || material >= (int)c->scene.materials.size()) return fail(c, PT_ERR_ARG, "material index");
-    int r;
-    if ((r = upload_scene(c))) return r;
+    if (n == 0) return PT_OK;
+    if (!incoming || !normal || !front || !pixel || !sample || !out9) return PT_ERR_ARG;
+    if (int r = upload_scene(c)) return r;
     Staging t(c);
-    const float* di = (const float*)t.in(incoming, (size_t)n * 12);
-    const float* dn = (const float*)t.in(normal, (size_t)n * 12);
-    const uint8_t* df = (const uint8_t*)t.in(front, n);
-    const uint32_t* dp = (const uint32_t*)t.in(pixel, (size_t)n * 4);
-    const uint32_t* ds = (const uint32_t*)t.in(sample, (size_t)n * 4);
-    float* dout = (float*)t.out((size_t)n * 36);
+    const float* di = t.in<float>(incoming, 3 * (size_t)n);
+    const float* dn = t.in<float>(normal, 3 * (size_t)n);
+    const uint8_t* df = t.in<uint8_t>(front, n);
+    const uint32_t* dp = t.in<uint32_t>(pixel, n);
+    const uint32_t* ds = t.in<uint32_t>(sample, n);
+    float* dout = t.out<float>(out9, 9 * (size_t)n);
     if (t.err) return t.err;
     launch_material_probe(c->stream, c->sv, material, n, di, dn, df, dp, ds, draws, c->cfg.seed, dout);
-    return t.download(out9, dout, (size_t)n * 36);
+    return t.fetch();
 }
 
 int pt_volume_eval(pt_ctx* c, int material, uint32_t n, const float* incoming, const float* t_max, const float* dist, const uint32_t* pixel,
                    const uint32_t* sample, uint32_t draws, float* out9)
 {
-    if (!c || !incoming || !t_max || !dist || !pixel || !sample || !out9) return PT_ERR_ARG;
+    if (!c) return PT_ERR_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
     if (material < 0 || material >= (int)c->scene.materials.size()) return fail(c, PT_ERR_ARG, "material index");
     if (n == 0) return PT_OK;
-    int r;
-    if ((r = upload_scene(c))) return r;
+    if (!incoming || !t_max || !dist || !pixel || !sample || !out9) return PT_ERR_ARG;
+    if (int r = upload_scene(c)) return r;
     Staging t(c);
-    const float* di = (const float*)t.in(incoming, (size_t)n * 12);
-    const float* dt = (const float*)t.in(t_max, (size_t)n * 4);
-    const float* dd = (const float*)t.in(dist, (size_t)n * 4);
-    const uint32_t* dp = (const uint32_t*)t.in(pixel, (size_t)n * 4);
-    const uint32_t* ds = (const uint32_t*)t.in(sample, (size_t)n * 4);
-    float* dout = (float*)t.out((size_t)n * 36);
+    const float* di = t.in<float>(incoming, 3 * (size_t)n);
+    const float* dt = t.in<float>(t_max, n);
+    const float* dd = t.in<float>(dist, n);
+    const uint32_t* dp = t.in<uint32_t>(pixel, n);
+    const uint32_t* ds = t.in<uint32_t>(sample, n);
+    float* dout = t.out<float>(out9, 9 * (size_t)n);
     if (t.err) return t.err;
     launch_volume_probe(c->stream, c->sv, material, n, di, dt, dd, dp, ds, draws, c->cfg.seed, dout);
-    return t.download(out9, dout, (size_t)n * 36);
+    return t.fetch();
 }
 
 int pt_bsdf_eval(pt_ctx* c, int material, uint32_t n, const float* incoming, const float* outgoing, const float* normal, const uint8_t* front,
                  float* out4)
 {
-    if (!c || !incoming || !outgoing || !normal || !front || !out4) return PT_ERR_ARG;
+    if (!c) return PT_ERR_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
     if (material < 0 || material >= (int)c->scene.materials.size()) return fail(c, PT_ERR_ARG, "material index");
     if (n == 0) return PT_OK;
-    int r;
-    if ((r = upload_scene(c))) return r;
+    if (!incoming || !outgoing || !normal || !front || !out4) return PT_ERR_ARG;
+    if (int r = upload_scene(c)) return r;
     Staging t(c);
-    const float* di = (const float*)t.in(incoming, (size_t)n * 12);
-    const float* dw = (const float*)t.in(outgoing, (size_t)n * 12);
-    const float* dn = (const float*)t.in(normal, (size_t)n * 12);
-    const uint8_t* df = (const uint8_t*)t.in(front, n);
-    float* dout = (float*)t.out((size_t)n * 16);
+    const float* di = t.in<float>(incoming, 3 * (size_t)n);
+    const float* dw = t.in<float>(outgoing, 3 * (size_t)n);
+    const float* dn = t.in<float>(normal, 3 * (size_t)n);
+    const uint8_t* df = t.in<uint8_t>(front, n);
+    float* dout = t.out<float>(out4, 4 * (size_t)n);
     if (t.err) return t.err;
     launch_bsdf_probe(c->stream, c->sv, material, n, di, dw, dn, df, dout);
-    return t.download(out4, dout, (size_t)n * 16);
+    return t.fetch();
 }
 
 int pt_guide_follow_dir(pt_ctx* c, int on_device, int material, uint32_t n, const float* incoming, const float* normal, const uint8_t* front, float* out4)
 {
-    if (!c || !incoming || !normal || !front || !out4) return PT_ERR_ARG;
+    if (!c) return PT_ERR_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
     if (material < 0 || material >= (int)c->scene.materials.size()) return fail(c, PT_ERR_ARG, "material index");
     if (n == 0) return PT_OK;
+    if (!incoming || !normal || !front || !out4) return PT_ERR_ARG;
     if (!on_device)
     {
         const DMaterial& dm = c->scene.materials[material];
         for (uint32_t i = 0; i < n; ++i)
         {
-            const FollowDir f = guide_follow_dir(dm.kind, dm.ior, f3{incoming[3 * i], incoming[3 * i + 1], incoming[3 * i + 2]},
-                                                 f3{normal[3 * i], normal[3 * i + 1], normal[3 * i + 2]}, front[i] != 0);
+            const FollowDir f = guide_follow_dir(dm.kind, dm.ior, load3(incoming, i), load3(normal, i), front[i] != 0);
             float* o = out4 + 4 * (size_t)i;
-            o[0] = f.wo.x; o[1] = f.wo.y; o[2] = f.wo.z;
+            store3(o, 0, f.wo);
             o[3] = f.followed ? 1.0f : 0.0f;
         }
         return PT_OK;
     }
-    int r;
-    if ((r = upload_scene(c))) return r;
+    if (int r = upload_scene(c)) return r;
     Staging t(c);
-    const float* di = (const float*)t.in(incoming, (size_t)n * 12);
-    const float* dn = (const float*)t.in(normal, (size_t)n * 12);
-    const uint8_t* df = (const uint8_t*)t.in(front, n);
-    float* dout = (float*)t.out((size_t)n * 16);
+    const float* di = t.in<float>(incoming, 3 * (size_t)n);
+    const float* dn = t.in<float>(normal, 3 * (size_t)n);
+    const uint8_t* df = t.in<uint8_t>(front, n);
+    float* dout = t.out<float>(out4, 4 * (size_t)n);
     if (t.err) return t.err;
     launch_guide_follow_dir(c->stream, c->sv, material, n, di, dn, df, dout);
-    return t.download(out4, dout, (size_t)n * 16);
+    return t.fetch();
 }
 
 // ---- host-builder introspection
@@ -5013,11 +5001,11 @@ int pt_multi_write_image(pt_multi* m, const char* path)
     const size_t px = (size_t)c0->cfg.width * c0->cfg.height;
     MHIPCHK(m, hipSetDevice(c0->device));
     Staging t(c0);
-    uint8_t* d_rgb = (uint8_t*)t.out(px * 3);
+    std::vector<uint8_t> host(px * 3);
+    uint8_t* d_rgb = t.out<uint8_t>(host.data(), host.size());
     if (t.err) return mfail(m, t.err, pt_last_error(c0));
     launch_post_rgb8(c0->stream, (uint32_t)px, (const f4*)m->d_full.p, d_rgb);   // ImageHelper::write_image  image_helper.rs:37-58
-    std::vector<uint8_t> host(px * 3);
-    if (int r = t.download(host.data(), d_rgb, px * 3)) return mfail(m, r, pt_last_error(c0));
+    if (int r = t.fetch()) return mfail(m, r, pt_last_error(c0));
     std::string err;
     if (!write_png_rgb8(path, host.data(), c0->cfg.width, c0->cfg.height, &err)) return mfail(m, PT_ERR_IO, err);
     return PT_OK;
@@ -5113,13 +5101,19 @@ int pt_variant_compiled(uint32_t launcher, const uint32_t axes6[6]) { return axe
 // array `a` of the class's shade queue, which nothing overwrites after the batch's last traversal launch.  HOLE (0xffffffff) = a slot no ray took.
 int pt_last_batch_shade_pids(pt_ctx* c, uint32_t qclass, uint32_t first, uint32_t count, uint32_t* pids)
 {
-    if (!c || !pids || qclass == Q_TERMINAL || qclass >= Q_COUNT) return PT_ERR_ARG;
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (qclass == Q_TERMINAL || qclass >= Q_COUNT) return PT_ERR_ARG;
     const pt_ctx::Pipe& pp = c->pipe[c->last_pipe];
     if (!pp.wb.q_shade_base || !((pp.wb.class_mask >> qclass) & 1u)) return PT_ERR_STATE;
     if ((uint64_t)first + count > pp.wb.q_stride) return PT_ERR_ARG;
+    if (count == 0) return PT_OK;
+    if (!pids) return PT_ERR_ARG;
     HIPCHK(c, hipSetDevice(c->device));
-    const ShadeQueue q = shade_queue(pp.wb, qclass);
-    HIPCHK(c, hipMemcpy2D(pids, 4, reinterpret_cast<const uint8_t*>(q.a + first) + 12, 16, 4, count, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipStreamSynchronize(c->pipe_stream(c->last_pipe))); // the batch that filled the queue may still be running
+    // one word of every record: rows of sizeof(uint32_t) bytes at a pitch of sizeof(f4)
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(shade_queue(pp.wb, qclass).a + first) + kShadePidWord;
+    HIPCHK(c, hipMemcpy2D(pids, sizeof(uint32_t), src, sizeof(f4), sizeof(uint32_t), count, hipMemcpyDeviceToHost));
     return PT_OK;
 }
 

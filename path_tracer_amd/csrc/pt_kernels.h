@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <vector>
 
 #include "pt_materials.h"
@@ -60,6 +61,9 @@ struct WavefrontBuffers
     uint32_t class_mask;  // bit q: the scene has instances of shade class q
 };
 
+// the word of a ShadeQueue::a record (direction.xyz | path id) that holds the path id: what reads the ids back from the host goes by it
+enum : uint32_t { kShadePidWord = 3u };
+static_assert(sizeof(f4) == 4 * sizeof(uint32_t) && kShadePidWord == offsetof(f4, w) / sizeof(uint32_t), "ShadeQueue::a keeps the path id in .w of a 16-byte record");
 inline ShadeQueue shade_queue(const WavefrontBuffers& wb, uint32_t q)
 {
     const size_t slot = (wb.q_class_slot >> (4u * q)) & 0xfu;
