@@ -46,6 +46,11 @@
 //   examples/headless ... --bake-lightmap ... --lightmap-denoise [--baked-view ...]   bakes with second moments (pt_bake_lightmap_moments), runs the
 //       texel-space filter on the sums (pt_lightmap_denoise, default parameters) and dilates its texel MEANS: map.txt then holds means, not sums,
 //       and --baked-view sets them as they are
+//   examples/headless ... --bake-lightmap W H SPP PASSES map.txt --adaptive REL MAX [--lightmap-denoise] [--baked-view ...]   bakes adaptively
+//       (pt_bake_lightmap_adaptive): rounds of SPP samples for the texels whose mean luminance is not yet known to the relative error REL, at
+//       most MAX samples per texel (0: no cap), until a round selects no texel; prints the rays spent and the mean count.  Every texel is
+//       divided by its own count before the means are dilated (or filtered with the counts, pt_lightmap_denoise_counts, then dilated), so
+//       map.txt holds means, and --baked-view sets them as they are
 //   examples/headless ... --bake-lightmap ... --directional [--normal-ripples N] [--baked-view ...]   bakes the first moments beside the sums
 //       (pt_bake_lightmap_directional), takes their tangential gradient (pt_lightmap_gradient), dilates it plane by plane and, under --baked-view,
 //       sets it beside the map (pt_set_lightmap_directional): with --normal-ripples, which then lie under the bake's planar UVs (the floor and the
@@ -94,7 +99,9 @@ int main(int argc, char** argv)
     bool probe_depth_given = false;
     uint32_t probe_radiance = 0;           // --probe-radiance R
     bool probe_radiance_given = false, metal_box = false;
-    bool lightmap_denoise = false, directional = false;
+    bool lightmap_denoise = false, directional = false, adaptive = false;
+    float adaptive_rel = 0.0f;
+    uint32_t adaptive_max = 0;
     std::string baked_out = "";
     pt_projection projection{}; // PT_PROJ_PERSPECTIVE
     for (int i = 1; i < argc; ++i)
@@ -171,6 +178,12 @@ int main(int argc, char** argv)
         }
         else if (a == "--lightmap-denoise") lightmap_denoise = true;
         else if (a == "--directional") directional = true;
+        else if (a == "--adaptive")
+        {
+            adaptive = true;
+            adaptive_rel = (float)std::atof(next("--adaptive"));
+            adaptive_max = (uint32_t)std::atoi(next("--adaptive"));
+        }
         else if (a == "--load-state") load_state = next("--load-state");
         else if (a == "--save-state") save_state = next("--save-state");
         else if (a == "--devices")
@@ -180,7 +193,7 @@ int main(int argc, char** argv)
         }
         else if (a == "--help" || a == "-h")
         {
-            std::printf("usage: %s [--width W] [--height H] [--frames N] [--bounces B] [--move] [--slide DX DZ] [--models DIR] [--out file.png] [--temporal file.png [--temporal-rescue] [--temporal-mean-length] [--temporal-demodulate]] [--denoise file.png] [--denoise-albedo file.png] [--follow K] [--mirror-glass] [--aperture A --focus F] [--projection panorama[:SX:SY]|ortho:HEIGHT] [--bake-probes NX NY NZ SPP file.txt] [--bake-lightmap W H SPP PASSES file.txt [--lightmap-denoise | --directional] [--baked-view SPP file.png]] [--probe-grid NX NY NZ SPP [--probe-depth R] [--probe-radiance R] --baked-view SPP file.png] [--metal-box] [--checker N] [--emission-checker N] [--normal-ripples N]\n", argv[0]);
+            std::printf("usage: %s [--width W] [--height H] [--frames N] [--bounces B] [--move] [--slide DX DZ] [--models DIR] [--out file.png] [--temporal file.png [--temporal-rescue] [--temporal-mean-length] [--temporal-demodulate]] [--denoise file.png] [--denoise-albedo file.png] [--follow K] [--mirror-glass] [--aperture A --focus F] [--projection panorama[:SX:SY]|ortho:HEIGHT] [--bake-probes NX NY NZ SPP file.txt] [--bake-lightmap W H SPP PASSES file.txt [--adaptive REL MAX] [--lightmap-denoise | --directional] [--baked-view SPP file.png]] [--probe-grid NX NY NZ SPP [--probe-depth R] [--probe-radiance R] --baked-view SPP file.png] [--metal-box] [--checker N] [--emission-checker N] [--normal-ripples N]\n", argv[0]);
             return 0;
         }
         else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
@@ -214,6 +227,12 @@ int main(int argc, char** argv)
     if (directional && (lightmap_out.empty() || !lightmap[2] || lightmap_denoise))
     {
         std::fprintf(stderr, "--directional bakes a direction beside the map --bake-lightmap bakes: it needs that option, and samples, and does not go with --lightmap-denoise\n");
+        return 2;
+    }
+    if (adaptive && (lightmap_out.empty() || !lightmap[2] || directional || !(adaptive_rel >= 0.0f) || (adaptive_max != 0 && adaptive_max < 2) ||
+                     (adaptive_rel == 0.0f && adaptive_max == 0)))
+    {
+        std::fprintf(stderr, "--adaptive REL MAX bakes the map --bake-lightmap bakes in rounds of its SPP: it needs that option, and samples, REL >= 0 and MAX of 0 or at least 2 (not both 0: the rounds would not end), and does not go with --directional\n");
         return 2;
     }
     if (normal_ripples && (checker || (!lightmap_out.empty() && !directional)))
@@ -369,6 +388,25 @@ int main(int argc, char** argv)
                 std::vector<uint8_t> grad_cov = cov;
                 renderer.dilate_lightmap_directional(lightmap[0], lightmap[1], lightmap[3], grad, grad_cov);
             }
+            else if (adaptive)
+            {
+                // rounds of SPP samples for the texels the criterion still selects; the means are each texel's sums over ITS OWN count, taken
+                // before anything is dilated (a dilated raw sum would mix neighbours with different denominators)
+                std::vector<float> sumsq;
+                std::vector<uint32_t> counts;
+                const pt_adaptive crit{adaptive_rel, 0.0f, 2u, adaptive_max};
+                uint64_t rays = 0, rounds = 0;
+                for (uint32_t n = 1; n != 0; ++rounds)
+                {
+                    n = renderer.bake_lightmap_adaptive(1, 0, lightmap[0], lightmap[1], lightmap[2], crit, sums, sumsq, counts, &cov, 0, 0.25f);
+                    rays += (uint64_t)n * lightmap[2];
+                }
+                uint64_t covered = 0, total = 0;
+                for (size_t k = 0; k < cov.size(); ++k) { covered += cov[k] ? 1u : 0u; total += cov[k] ? counts[k] : 0u; }
+                std::printf("{\"adaptive_rounds\": %llu, \"rays\": %llu, \"covered\": %llu, \"mean_count\": %.3f}\n", (unsigned long long)(rounds - 1),
+                            (unsigned long long)rays, (unsigned long long)covered, covered ? (double)total / (double)covered : 0.0);
+                sums = lightmap_denoise ? renderer.denoise_lightmap_counts(1, 0, lightmap[0], lightmap[1], sums, sumsq, counts) : ptmi::Renderer::lightmap_means(sums, counts);
+            }
             else if (lightmap_denoise)
             {
                 // the moments steer the filter's luminance term; what it returns are texel means, and those are what is dilated, written and set
@@ -384,7 +422,7 @@ int main(int argc, char** argv)
             std::fclose(f);
             if (baked_out.empty()) return true;
             // ... and its consumer: the map's texel means on the shell (baked_view shades the followed first hits from it)
-            if (!lightmap_denoise)
+            if (!lightmap_denoise && !adaptive)
                 for (float& s : sums) s = s / (float)lightmap[2];
             renderer.set_lightmap(1, 0, lightmap[0], lightmap[1], sums);
             if (directional) renderer.set_lightmap_directional(1, 0, lightmap[0], lightmap[1], grad);

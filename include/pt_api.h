@@ -968,8 +968,8 @@ int pt_lightmap_dilate(pt_ctx* ctx, uint32_t w, uint32_t h, uint32_t passes, flo
  * Errors, all before any device call (a refused call changes nothing): what pt_lightmap_texels refuses for model, instance, w and h; what
  * pt_denoise refuses for the filter parameters; PT_ERR_ARG for a NULL p, rgb_sum or rgb_mean, a non-zero reserved word, n_samples of 0 or above
  * 2^24, a reach that is negative, NaN or infinite, a value of rgb_sum or sumsq that is negative or not finite.
- * Out of scope: per-texel sample counts, adaptive baking from the moments, chart ids from UV connectivity, filling uncovered texels inside the
- * filter, demodulation, pt_multi_* variants. */
+ * Out of scope: chart ids from UV connectivity, filling uncovered texels inside the filter, demodulation, pt_multi_* variants.  (Per-texel
+ * sample counts: pt_lightmap_denoise_counts; baking adaptively from the moments: pt_bake_lightmap_adaptive; both below.) */
 int pt_bake_lightmap_moments(pt_ctx* ctx, const pt_lightmap_params* p, float* rgb_sum, float* sumsq, uint8_t* coverage);
 typedef struct pt_lightmap_denoise_params
 {
@@ -983,6 +983,47 @@ typedef struct pt_lightmap_denoise_params
 } pt_lightmap_denoise_params;
 int pt_lightmap_denoise(pt_ctx* ctx, int on_device, const pt_lightmap_denoise_params* p, const float* rgb_sum, const float* sumsq, float* rgb_mean,
                         float* texel_area);
+
+/* ---- adaptive lightmap baking: spend a bake's samples on the texels that are still noisy ------------------------------------------------ */
+/* pt_bake_lightmap_adaptive is pt_render_adaptive for a lightmap.  The caller keeps three host arrays per map, all IN/OUT: rgb_sum (w * h * 3
+ * floats) and sumsq (w * h floats) as pt_bake_lightmap_moments folds them, and counts (w * h uint32 words), the samples each texel has had.  A
+ * fresh bake starts from three arrays of zeros.  A covered texel k is ACTIVE when, in binary32 with every operation rounded once, in this
+ * order, no contraction,
+ *     n = (float)counts[k];  S = (0.2126f * sum.r + 0.7152f * sum.g) + 0.0722f * sum.b;  m = S / n;  v = Q[k] / n - m * m;  if (!(v > 0)) v = 0;
+ *     e2 = v / n;  t = rel_error * (m > abs_floor ? m : abs_floor);
+ *     active = counts[k] < min_samples || ((max_samples == 0 || counts[k] < max_samples) && e2 > t * t)
+ * which is pt_adaptive's rule word for word with the count taken from counts[k] (exact in binary32 up to 2^24); with a count of 0 the 0 / 0 is
+ * computed and ignored, since 0 < min_samples.  An UNCOVERED texel is never active, never read for its values and never written.
+ * The call selects the active texels from the arrays as they come in, on the device (two passes over the texel table, no atomics: the list is
+ * in ascending texel order whatever the scheduling).  Each active texel k then gets samples [counts[k], counts[k] + p->n_samples), folded into
+ * rgb_sum[k] and sumsq[k] in sample order exactly as pt_bake_lightmap_moments folds them - the same ray, the same key key_base + k, the same
+ * draws_consumed - and afterwards counts[k] += p->n_samples.  Inactive and uncovered texels are bit-unchanged in all three arrays.
+ * THE CONTRACT: after ANY sequence of adaptive calls, (rgb_sum[k], sumsq[k]) of a covered texel are bit for bit what
+ * pt_bake_lightmap_moments(first_sample = 0, n_samples = counts[k]) gives that texel, whatever the other texels, the list, the batch cut
+ * (pt_config.batch_spp), the ray-table cut and the place of the BVH were.  So the three arrays are a checkpoint: any context of the same scene
+ * and config continues them to the same bits.
+ * p->first_sample must be 0: a texel's first sample is its own count.  *n_active (may be NULL) receives the number of active texels;
+ * pt_stats.paths grows by n_active * n_samples.  With no active texel the call is PT_OK, integrates nothing and changes nothing.  coverage
+ * (may be NULL) as pt_bake_lightmap's.  Blocking.  The context does not need PT_FLAG_ADAPTIVE: the moments are the caller's arrays.
+ * Errors, all before any device call (a refused call changes nothing), in this order: what pt_bake_lightmap_moments refuses; PT_ERR_ARG for
+ * a NULL crit, sumsq or counts and for first_sample != 0; PT_ERR_ARG for an invalid pt_adaptive by pt_render_adaptive's rules; PT_ERR_LIMIT when
+ * some covered texel has counts[k] + n_samples > 2^24 (f32 counts stop being exact there, and the filter's range ends there too).
+ * Out of scope: adaptive directional bakes (pt_bake_lightmap_directional), pt_multi_* variants, criteria other than luminance. */
+int pt_bake_lightmap_adaptive(pt_ctx* ctx, const pt_lightmap_params* p, const pt_adaptive* crit, float* rgb_sum, float* sumsq, uint32_t* counts,
+                              uint8_t* coverage /* may be NULL */, uint32_t* n_active /* may be NULL */);
+/* the selection alone, the unit hook of the above: mask[k] = 1 (active) or 0, w * h bytes (may be NULL), *n_active their number.  on_device = 0
+ * evaluates coverage and criterion on the host and touches no GPU; on_device = 1 runs the bake's own selection kernels, reads the list back and
+ * builds the mask from it (a list that is not ascending texels with their counts is PT_ERR_HIP).  Errors: pt_lightmap_texels' for model,
+ * instance, w and h; PT_ERR_ARG for a NULL crit, rgb_sum, sumsq, counts or n_active and for an invalid pt_adaptive; PT_ERR_LIMIT when a covered
+ * texel's count is above 2^24. */
+int pt_lightmap_adaptive_mask(pt_ctx* ctx, int on_device, int model, uint32_t instance, uint32_t w, uint32_t h, const pt_adaptive* crit,
+                              const float* rgb_sum, const float* sumsq, const uint32_t* counts, uint8_t* mask /* may be NULL */, uint32_t* n_active);
+/* pt_lightmap_denoise with a sample count per texel: acc = (sum.r, sum.g, sum.b, (float)counts[k]) for a covered texel, everything else as
+ * above (the filter carries a count per pixel in acc.w anyway).  p->n_samples must be 0 here.  With the same count n in every covered texel
+ * the result is pt_lightmap_denoise's with n_samples = n, bit for bit.  Errors: pt_lightmap_denoise's, PT_ERR_ARG for a NULL counts, for
+ * p->n_samples != 0 and for a covered texel whose count is 0 (the filter would silently treat it as invalid) or above 2^24. */
+int pt_lightmap_denoise_counts(pt_ctx* ctx, int on_device, const pt_lightmap_denoise_params* p, const float* rgb_sum, const float* sumsq,
+                               const uint32_t* counts, float* rgb_mean, float* texel_area);
 
 /* ---- lightmaps kept by the context, and the baked view: followed first hits shaded from them ------------------------------------------- */
 /* pt_set_lightmap gives the context the finished map of ONE placement, (model, instance) as pt_bake_lightmap keys it: rgb is w * h * 3 floats,

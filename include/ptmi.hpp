@@ -454,6 +454,63 @@ public:
         check(pt_lightmap_denoise(ctx_, on_device ? 1 : 0, &p, rgb_sum.data(), sumsq.empty() ? nullptr : sumsq.data(), mean.data(), texel_area ? texel_area->data() : nullptr));
         return mean;
     }
+    // one round of an adaptive bake (pt_bake_lightmap_adaptive): the texels of the map that crit selects from (rgb_sum, sumsq, counts) get
+    // n_samples more samples each, continuing from their own counts.  The three are IN/OUT (empty: a fresh bake from zeros); returns the
+    // number of texels selected, and the coverage bytes if asked.  Call until it returns 0.
+    uint32_t bake_lightmap_adaptive(int model, uint32_t instance, uint32_t w, uint32_t h, uint32_t n_samples, const pt_adaptive& crit, std::vector<float>& rgb_sum,
+                                    std::vector<float>& sumsq, std::vector<uint32_t>& counts, std::vector<uint8_t>* coverage = nullptr, uint32_t key_base = 0,
+                                    float bias = 0.0f)
+    {
+        const size_t px = (size_t)w * h;
+        if (rgb_sum.empty()) rgb_sum.assign(px * 3, 0.0f);
+        if (sumsq.empty()) sumsq.assign(px, 0.0f);
+        if (counts.empty()) counts.assign(px, 0u);
+        if (rgb_sum.size() != px * 3 || sumsq.size() != px || counts.size() != px)
+            throw Error(PT_ERR_ARG, "bake_lightmap_adaptive: rgb_sum holds 3 values per texel, sumsq and counts one");
+        if (coverage) coverage->assign(px, 0);
+        pt_lightmap_params p{};
+        p.model = model; p.instance = instance; p.w = w; p.h = h;
+        p.n_samples = n_samples; p.key_base = key_base; p.bias = bias;
+        uint32_t n = 0;
+        check(pt_bake_lightmap_adaptive(ctx_, &p, &crit, rgb_sum.data(), sumsq.data(), counts.data(), coverage ? coverage->data() : nullptr, &n));
+        return n;
+    }
+    // the selection alone (pt_lightmap_adaptive_mask): 1 per texel that bake_lightmap_adaptive would give samples
+    std::vector<uint8_t> lightmap_adaptive_mask(int model, uint32_t instance, uint32_t w, uint32_t h, const pt_adaptive& crit, const std::vector<float>& rgb_sum,
+                                                const std::vector<float>& sumsq, const std::vector<uint32_t>& counts, bool on_device = false) const
+    {
+        const size_t px = (size_t)w * h;
+        if (rgb_sum.size() != px * 3 || sumsq.size() != px || counts.size() != px)
+            throw Error(PT_ERR_ARG, "lightmap_adaptive_mask: rgb_sum holds 3 values per texel, sumsq and counts one");
+        std::vector<uint8_t> mask(px);
+        uint32_t n = 0;
+        check(pt_lightmap_adaptive_mask(ctx_, on_device ? 1 : 0, model, instance, w, h, &crit, rgb_sum.data(), sumsq.data(), counts.data(), mask.data(), &n));
+        return mask;
+    }
+    // denoise_lightmap with a sample count per texel (pt_lightmap_denoise_counts): an adaptive bake's sums, moments and counts
+    std::vector<float> denoise_lightmap_counts(int model, uint32_t instance, uint32_t w, uint32_t h, const std::vector<float>& rgb_sum, const std::vector<float>& sumsq,
+                                               const std::vector<uint32_t>& counts, pt_denoise_params filter = {}, float reach = 0.0f, bool on_device = true) const
+    {
+        const size_t px = (size_t)w * h;
+        if (rgb_sum.size() != px * 3 || (!sumsq.empty() && sumsq.size() != px) || counts.size() != px)
+            throw Error(PT_ERR_ARG, "denoise_lightmap_counts: rgb_sum holds 3 values per texel, sumsq and counts one");
+        pt_lightmap_denoise_params p{};
+        p.model = model; p.instance = instance; p.w = w; p.h = h;
+        p.filter = filter; p.reach = reach;
+        std::vector<float> mean(px * 3);
+        check(pt_lightmap_denoise_counts(ctx_, on_device ? 1 : 0, &p, rgb_sum.data(), sumsq.empty() ? nullptr : sumsq.data(), counts.data(), mean.data(), nullptr));
+        return mean;
+    }
+    // the texel means of an adaptive bake: every texel's sums over ITS OWN count, zero where the count is 0.  Divide first, dilate the means
+    // afterwards: a dilated raw sum would mix neighbours with different denominators
+    static std::vector<float> lightmap_means(const std::vector<float>& rgb_sum, const std::vector<uint32_t>& counts)
+    {
+        if (rgb_sum.size() != counts.size() * 3) throw Error(PT_ERR_ARG, "lightmap_means: rgb_sum holds 3 values per texel and counts one");
+        std::vector<float> mean(rgb_sum.size(), 0.0f);
+        for (size_t k = 0; k < counts.size(); ++k)
+            for (size_t ch = 0; counts[k] && ch < 3; ++ch) mean[3 * k + ch] = rgb_sum[3 * k + ch] / (float)counts[k];
+        return mean;
+    }
     // `passes` dilation passes over a w x h map and its coverage bytes (pt_lightmap_dilate); filled texels carry the byte 2
     void dilate_lightmap(uint32_t w, uint32_t h, uint32_t passes, std::vector<float>& rgb, std::vector<uint8_t>& coverage)
     {

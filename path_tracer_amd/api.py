@@ -55,6 +55,7 @@ EXPORTS = [
     "pt_probe_radiance_dir", "pt_bake_probe_radiance", "pt_probe_radiance_prefilter", "pt_set_probe_grid_radiance", "pt_get_probe_grid_radiance_info",
     "pt_probe_grid_specular",
     "pt_bake_lightmap_directional", "pt_lightmap_gradient", "pt_set_lightmap_directional", "pt_get_lightmap_directional_info", "pt_lightmap_lookup_directional",
+    "pt_bake_lightmap_adaptive", "pt_lightmap_adaptive_mask", "pt_lightmap_denoise_counts",
 ]
 
 
@@ -338,6 +339,9 @@ def lib():
         L.pt_lightmap_dilate.argtypes = [vp, u32, u32, u32, vp, vp]
         L.pt_bake_lightmap_moments.argtypes = [vp, C.POINTER(LightmapParams), vp, vp, vp]
         L.pt_lightmap_denoise.argtypes = [vp, C.c_int, C.POINTER(LightmapDenoiseParams), vp, vp, vp, vp]
+        L.pt_bake_lightmap_adaptive.argtypes = [vp, C.POINTER(LightmapParams), C.POINTER(Adaptive), vp, vp, vp, vp, C.POINTER(u32)]
+        L.pt_lightmap_adaptive_mask.argtypes = [vp, C.c_int, C.c_int, u32, u32, u32, C.POINTER(Adaptive), vp, vp, vp, vp, C.POINTER(u32)]
+        L.pt_lightmap_denoise_counts.argtypes = [vp, C.c_int, C.POINTER(LightmapDenoiseParams), vp, vp, vp, vp, vp]
         L.pt_set_lightmap.argtypes = [vp, C.c_int, u32, u32, u32, vp]
         L.pt_get_lightmap_info.argtypes = [vp, C.c_int, u32, vp, vp]
         L.pt_lightmap_lookup.argtypes = [vp, C.c_int, u32, vp, vp, vp, vp, vp, vp]
@@ -1113,10 +1117,11 @@ class Renderer:
         return out.reshape(h, w, 3), sq.reshape(h, w), cov
 
     def denoise_lightmap(self, model, instance, sums, n_samples, sumsq=None, iterations=0, sigma_luminance=0.0, sigma_normal=0, sigma_plane=0.0, reach=0.0,
-                         on_device=True, want_area=False):
+                         on_device=True, want_area=False, counts=None):
         """the texel-space filter (pt_lightmap_denoise) on a bake's raw sums (h, w, 3) over n_samples samples, with its second moments sumsq
         (h, w) or, None, the spatial variance: the texel means (h, w, 3), zeros where uncovered (dilate afterwards); with want_area
-        (means, texel areas (h, w)).  0 selects each default; on the host (no GPU) unless on_device"""
+        (means, texel areas (h, w)).  0 selects each default; on the host (no GPU) unless on_device.  counts (h, w) uint32, an adaptive
+        bake's samples per texel, routes to pt_lightmap_denoise_counts; n_samples must then be 0 (or None)"""
         a = np.ascontiguousarray(sums, np.float32)
         if a.ndim != 3 or a.shape[2] != 3:
             raise PtError(-1, "denoise_lightmap: sums is (h, w, 3)")
@@ -1124,11 +1129,62 @@ class Renderer:
         sq = None if sumsq is None else np.ascontiguousarray(sumsq, np.float32)
         if sq is not None and sq.shape != (h, w):
             raise PtError(-1, "denoise_lightmap: sumsq is (h, w)")
-        prm = LightmapDenoiseParams(model, instance, w, h, n_samples, DenoiseParams(iterations, sigma_luminance, sigma_normal, sigma_plane), reach)
+        cn = None if counts is None else np.ascontiguousarray(counts, np.uint32)
+        if cn is not None and cn.shape != (h, w):
+            raise PtError(-1, "denoise_lightmap: counts is (h, w)")
+        prm = LightmapDenoiseParams(model, instance, w, h, n_samples or 0, DenoiseParams(iterations, sigma_luminance, sigma_normal, sigma_plane), reach)
         out = np.zeros((h, w, 3), np.float32)
         area = np.zeros((h, w), np.float32) if want_area else None
-        self._chk(self.L.pt_lightmap_denoise(self.ctx, int(bool(on_device)), C.byref(prm), _p(a), _p(sq), _p(out), _p(area)))
+        if cn is not None:
+            self._chk(self.L.pt_lightmap_denoise_counts(self.ctx, int(bool(on_device)), C.byref(prm), _p(a), _p(sq), _p(cn), _p(out), _p(area)))
+        else:
+            self._chk(self.L.pt_lightmap_denoise(self.ctx, int(bool(on_device)), C.byref(prm), _p(a), _p(sq), _p(out), _p(area)))
         return (out, area) if want_area else out
+
+    # ---- adaptive bakes
+    @staticmethod
+    def _lightmap_state(what, w, h, sums, sumsq, counts, copy):
+        """the three arrays of an adaptive bake as C-contiguous (h, w, 3) float32, (h, w) float32, (h, w) uint32; None: zeros"""
+        def one(a, shape, dt):
+            if a is None:
+                return np.zeros(shape, dt)
+            a = np.array(a, dt, order="C") if copy else np.ascontiguousarray(a, dt)
+            if a.shape != shape:
+                raise PtError(-1, f"{what}: sums is (h, w, 3) float32, sumsq (h, w) float32 and counts (h, w) uint32 for a {w} x {h} map")
+            return a
+        return one(sums, (h, w, 3), np.float32), one(sumsq, (h, w), np.float32), one(counts, (h, w), np.uint32)
+
+    def bake_lightmap_adaptive(self, model, instance, w, h, n_samples, rel_error, abs_floor=0.0, min_samples=2, max_samples=0, key_base=0, bias=0.0,
+                               sums=None, sumsq=None, counts=None):
+        """One round of an adaptive bake (pt_bake_lightmap_adaptive): selects the covered texels whose mean luminance is not yet known to
+        rel_error (pt_adaptive's rule on sums, sumsq and counts as they come in) and gives each of them n_samples more samples, continuing from
+        its own count.  Returns (sums (h, w, 3), sumsq (h, w), counts (h, w) uint32, coverage (h, w) uint8, n_active): new arrays, the ones
+        passed in are not written (None: a fresh bake from zeros, where every covered texel is active).  Every texel's sums are bit for bit
+        bake_lightmap_moments(0, counts[texel]) at that texel.  Call until n_active == 0."""
+        out, sq, cn = self._lightmap_state("bake_lightmap_adaptive", w, h, sums, sumsq, counts, copy=True)
+        cov = np.zeros((h, w), np.uint8)
+        n = C.c_uint32(0)
+        prm = LightmapParams(model, instance, w, h, 0, n_samples, key_base, bias)
+        crit = self._adaptive(rel_error, abs_floor, min_samples, max_samples)
+        self._chk(self.L.pt_bake_lightmap_adaptive(self.ctx, C.byref(prm), C.byref(crit), _p(out), _p(sq), _p(cn), _p(cov), C.byref(n)))
+        return out, sq, cn, cov, n.value
+
+    def lightmap_adaptive_mask(self, model, instance, sums, sumsq, counts, rel_error, abs_floor=0.0, min_samples=2, max_samples=0, on_device=False):
+        """unit hook: the selection of bake_lightmap_adaptive alone, bool (h, w), True = the texel would get samples; on the host (no GPU)
+        unless on_device, which runs the bake's selection kernels and builds the mask from their list"""
+        a = np.ascontiguousarray(sums, np.float32)
+        if a.ndim != 3 or a.shape[2] != 3:
+            raise PtError(-1, "lightmap_adaptive_mask: sums is (h, w, 3)")
+        h, w = a.shape[:2]
+        a, sq, cn = self._lightmap_state("lightmap_adaptive_mask", w, h, a, sumsq, counts, copy=False)
+        if sumsq is None or counts is None:
+            raise PtError(-1, "lightmap_adaptive_mask: sumsq and counts are needed")
+        mask = np.zeros((h, w), np.uint8)
+        n = C.c_uint32(0)
+        crit = self._adaptive(rel_error, abs_floor, min_samples, max_samples)
+        self._chk(self.L.pt_lightmap_adaptive_mask(self.ctx, int(bool(on_device)), model, instance, w, h, C.byref(crit), _p(a), _p(sq), _p(cn), _p(mask), C.byref(n)))
+        assert int(mask.sum()) == n.value
+        return mask.astype(bool)
 
     # ---- lightmaps kept by the context, and the baked view
     def set_lightmap(self, model, instance, rgb):
@@ -1147,6 +1203,24 @@ class Renderer:
         if not n_samples > 0:
             raise PtError(-1, "set_lightmap_sums: n_samples must be positive")
         self.set_lightmap(model, instance, np.asarray(sums, np.float32) / np.float32(n_samples))
+
+    def set_lightmap_counts(self, model, instance, sums, counts, coverage, passes=0):
+        """set_lightmap of an adaptive bake: sums (h, w, 3), counts (h, w), coverage (h, w) as bake_lightmap_adaptive returns them.  Every
+        texel is divided by ITS OWN count FIRST (zero where the count is 0), THEN the means are dilated `passes` times, then set.  The order
+        matters: with per-texel counts a dilated raw sum is a mix of neighbours with different denominators, and there is no count left to
+        divide it by; a mean of means is what dilation is meant to produce.  Returns the (means, coverage) that were set."""
+        a = np.ascontiguousarray(sums, np.float32)
+        cn = np.ascontiguousarray(counts, np.uint32)
+        cv = np.ascontiguousarray(coverage, np.uint8)
+        if a.ndim != 3 or a.shape[2] != 3 or cn.shape != a.shape[:2] or cv.shape != a.shape[:2]:
+            raise PtError(-1, "set_lightmap_counts: sums is (h, w, 3), counts and coverage (h, w)")
+        mean = np.zeros_like(a)
+        have = cn > 0
+        mean[have] = a[have] / cn[have].astype(np.float32)[:, None]
+        if passes:
+            mean, cv = self.dilate_lightmap(mean, cv, passes)
+        self.set_lightmap(model, instance, mean)
+        return mean, cv
 
     def lightmap_info(self, model, instance):
         """(w, h) of the map of placement (model, instance); (0, 0): none"""

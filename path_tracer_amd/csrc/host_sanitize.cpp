@@ -491,7 +491,7 @@ int main(int argc, char** argv)
             {
                 const float reach = reaches[pass % 3];
                 const LmFilterK k{{4.0f, 1.0f, 7u, 8u}, reach * reach};
-                lmf_filter_host(w, h, k, owner.data(), P.data(), N.data(), p.data(), uv.data(), sum.data(), pass < 3 ? sq.data() : nullptr, 16u, mean.data(), area.data());
+                lmf_filter_host(w, h, k, owner.data(), P.data(), N.data(), p.data(), uv.data(), sum.data(), pass < 3 ? sq.data() : nullptr, 16u, nullptr, mean.data(), area.data());
                 for (size_t k2 = 0; k2 < px; ++k2)
                 {
                     if (owner[k2] == MISS_ID && (mean[3 * k2] != 0.0f || mean[3 * k2 + 1] != 0.0f || mean[3 * k2 + 2] != 0.0f || area[k2] != 0.0f)) return 6;

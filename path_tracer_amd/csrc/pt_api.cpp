@@ -1811,14 +1811,20 @@ int lightmap_texels_device(pt_ctx* c, Staging& st, const HostModel& m, uint32_t 
 
 // ---- adaptive sampling (PT_FLAG_ADAPTIVE)
 // everything that can be refused without touching the device
-int adaptive_check(pt_ctx* c, const pt_adaptive* a)
+// the criterion's own values (the lightmap calls stop here: their moments are the caller's arrays, so the context needs no flag)
+int adaptive_crit_check(pt_ctx* c, const pt_adaptive* a)
 {
-    if (!(c->cfg.flags & PT_FLAG_ADAPTIVE)) return fail(c, PT_ERR_STATE, "adaptive sampling needs PT_FLAG_ADAPTIVE in pt_config.flags");
     if (!a) return fail(c, PT_ERR_ARG, "null pt_adaptive");
     if (!(a->rel_error >= 0.0f) || !std::isfinite(a->rel_error)) return fail(c, PT_ERR_ARG, "pt_adaptive.rel_error must be finite and >= 0");
     if (!(a->abs_floor >= 0.0f) || !std::isfinite(a->abs_floor)) return fail(c, PT_ERR_ARG, "pt_adaptive.abs_floor must be finite and >= 0");
     if (a->min_samples < 2u) return fail(c, PT_ERR_ARG, "pt_adaptive.min_samples must be >= 2");
     if (a->max_samples != 0u && a->max_samples < a->min_samples) return fail(c, PT_ERR_ARG, "pt_adaptive.max_samples must be 0 or >= min_samples");
+    return PT_OK;
+}
+int adaptive_check(pt_ctx* c, const pt_adaptive* a)
+{
+    if (!(c->cfg.flags & PT_FLAG_ADAPTIVE)) return fail(c, PT_ERR_STATE, "adaptive sampling needs PT_FLAG_ADAPTIVE in pt_config.flags");
+    if (int r = adaptive_crit_check(c, a)) return r;
     if (!c->moments_valid)
         return fail(c, PT_ERR_STATE, "the moments do not describe the accumulation (pt_write_accumulation without pt_write_moments, pt_frame, or "
                                      "PT_FLAG_ADAPTIVE set after samples were accumulated): pt_write_moments or pt_reset_accumulation first");
@@ -3657,8 +3663,8 @@ int pt_lightmap_texels(pt_ctx* c, int model, uint32_t instance, uint32_t w, uint
 namespace {
 // pt_bake_lightmap (sumsq null, moments false), pt_bake_lightmap_moments and pt_bake_lightmap_directional (directional, dir_sum) under the
 // context's lock
-int bake_lightmap_locked(pt_ctx* c, const pt_lightmap_params* p, float* rgb_sum, float* sumsq, bool moments, uint8_t* coverage, float* dir_sum = nullptr,
-                         bool directional = false)
+// what the three refuse, all before any device call
+int bake_lightmap_check(pt_ctx* c, const pt_lightmap_params* p, const float* rgb_sum, const float* sumsq, bool moments, const float* dir_sum, bool directional)
 {
     int r;
     if ((r = rays_precheck(c))) return r;
@@ -3672,6 +3678,14 @@ int bake_lightmap_locked(pt_ctx* c, const pt_lightmap_params* p, float* rgb_sum,
     const size_t px = (size_t)p->w * p->h;
     if ((uint64_t)p->key_base + px > 0x100000000ull) return fail(c, PT_ERR_ARG, "pt_lightmap_params.key_base + w * h wraps 32 bits");
     if ((uint64_t)p->first_sample + p->n_samples > 0x100000000ull) return fail(c, PT_ERR_ARG, "pt_lightmap_params.first_sample + n_samples wraps 32 bits");
+    return PT_OK;
+}
+int bake_lightmap_locked(pt_ctx* c, const pt_lightmap_params* p, float* rgb_sum, float* sumsq, bool moments, uint8_t* coverage, float* dir_sum = nullptr,
+                         bool directional = false)
+{
+    int r;
+    if ((r = bake_lightmap_check(c, p, rgb_sum, sumsq, moments, dir_sum, directional))) return r;
+    const size_t px = (size_t)p->w * p->h;
     if ((r = upload_scene(c))) return r;
     const HostModel& m = c->scene.models[p->model];
     Staging st(c);
@@ -3703,8 +3717,239 @@ int bake_lightmap_locked(pt_ctx* c, const pt_lightmap_params* p, float* rgb_sum,
     if (coverage) std::memcpy(coverage, cov.data(), px);
     return PT_OK;
 }
+
+// ---- adaptive bakes (pt_bake_lightmap_adaptive; the criterion is pt_types.h's adaptive_active)
+constexpr uint64_t kMaxTexelCount = 1ull << 24; // f32 counts are exact up to here, and the texel filter's range ends here
+
+// *over: does some COVERED texel have counts[k] + add > 2^24?  Host only.  The coverage is worked out only when some texel at all has such a
+// count, so the usual call pays one pass over the counts.
+int lightmap_counts_over(pt_ctx* c, const HostModel& m, uint32_t w, uint32_t h, const uint32_t* counts, uint32_t add, bool* over)
+{
+    const size_t px = (size_t)w * h;
+    *over = false;
+    size_t k = 0;
+    while (k < px && (uint64_t)counts[k] + add <= kMaxTexelCount) ++k;
+    if (k == px) return PT_OK;
+    std::vector<uint32_t> owner;
+    try { lightmap_owner_host(m, w, h, owner); }
+    catch (const std::exception& e) { return fail(c, PT_ERR_LIMIT, std::string("the texel table does not fit in host memory: ") + e.what()); }
+    for (; k < px && !*over; ++k) *over = owner[k] != MISS_ID && (uint64_t)counts[k] + add > kMaxTexelCount;
+    return PT_OK;
+}
+
+// the selection on the device: k_lm_select_count + k_lm_select_write over the table `t` and the three device arrays, then ONE small read-back:
+// the list's length and the limit flag.  d_list: px entries, in a buffer of `st`.  The stream is idle when this returns.
+int lightmap_select_device(pt_ctx* c, Staging& st, const LightmapDev& t, size_t px, const pt_adaptive* a, uint32_t n_samples, const float* d_sum,
+                           const float* d_sq, const uint32_t* d_counts, uint2** d_list, uint32_t* n_active)
+{
+    const uint32_t blocks = lightmap_select_blocks((uint32_t)px);
+    *d_list = st.out<uint2>(px);
+    uint32_t* header = st.out<uint32_t>((size_t)blocks + 4);
+    if (st.err) return st.err;
+    const LightmapSelect sel{t.coverage, d_sum, d_sq, d_counts, (uint32_t)px, n_samples, AdaptiveCrit{a->rel_error, a->abs_floor, a->min_samples, a->max_samples}};
+    HIPCHK(c, hipMemsetAsync(header, 0, 16, c->stream));
+    launch_lightmap_select(c->stream, sel, header + 4, *d_list, header);
+    HIPCHK(c, hipGetLastError());
+    uint32_t h[2] = {0u, 0u};
+    HIPCHK(c, hipMemcpyAsync(h, header, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    // (the host has looked already, with its own coverage walk: the two agree bit for bit, so this does not fire)
+    if (h[1]) return fail(c, PT_ERR_LIMIT, "lightmap: a covered texel's sample count would pass 2^24: f32 counts are not exact beyond");
+    if (h[0] > px) return fail(c, PT_ERR_HIP, "lightmap: the selection's list is longer than the map");
+    *n_active = h[0];
+    return PT_OK;
+}
+
+int bake_lightmap_adaptive_locked(pt_ctx* c, const pt_lightmap_params* p, const pt_adaptive* crit, float* rgb_sum, float* sumsq, uint32_t* counts,
+                                  uint8_t* coverage, uint32_t* n_active)
+{
+    int r;
+    if ((r = bake_lightmap_check(c, p, rgb_sum, sumsq, true, nullptr, false))) return r;
+    if (!crit || !counts) return fail(c, PT_ERR_ARG, "pt_bake_lightmap_adaptive: crit, sumsq and counts must not be NULL");
+    if (p->first_sample != 0) return fail(c, PT_ERR_ARG, "pt_bake_lightmap_adaptive: first_sample must be 0 (a texel's first sample is its own count)");
+    if ((r = adaptive_crit_check(c, crit))) return r;
+    const HostModel& m = c->scene.models[p->model];
+    bool over = false;
+    if ((r = lightmap_counts_over(c, m, p->w, p->h, counts, p->n_samples, &over))) return r;
+    if (over) return fail(c, PT_ERR_LIMIT, "pt_bake_lightmap_adaptive: a covered texel's count + n_samples is above 2^24: f32 counts are not exact beyond");
+    const size_t px = (size_t)p->w * p->h;
+    if ((r = upload_scene(c))) return r;
+    Staging st(c);
+    LightmapDev t{};
+    if ((r = lightmap_texels_device(c, st, m, p->instance, p->w, p->h, t))) return r;
+    // the three arrays go up once; they come back only when something was added to them
+    float* d_sum = st.in_rw<float>(rgb_sum, 3 * px);
+    float* d_sq = st.in_rw<float>(sumsq, px);
+    uint32_t* d_counts = st.in_rw<uint32_t>(counts, px);
+    uint2* d_list = nullptr;
+    uint32_t n = 0;
+    if ((r = lightmap_select_device(c, st, t, px, crit, p->n_samples, d_sum, d_sq, d_counts, &d_list, &n))) return r;
+    if (n > 0)
+    {
+        const LightmapAdaptiveBake lb{d_list, t.position, t.normal, n, p->n_samples, p->key_base, c->cfg.n_sobol, p->bias, c->cfg.seed};
+        if ((r = bake_rays(c, st, n, p->n_samples,
+                           [&](uint64_t first, uint32_t cnt, float* o, float* d, uint2* key) { launch_lightmap_rays(c->stream, lb, first, cnt, o, d, key); },
+                           [&](uint64_t first, uint32_t cnt, const float*, const f4* rad) { launch_lightmap_fold(c->stream, lb, first, cnt, rad, d_sum, d_sq); })))
+            return r;
+        launch_lightmap_advance(c->stream, d_list, n, p->n_samples, d_counts);
+        st.expect(rgb_sum, d_sum, 3 * px);
+        st.expect(sumsq, d_sq, px);
+        st.expect(counts, d_counts, px);
+    }
+    st.expect(coverage, t.coverage, px);
+    if ((r = st.fetch())) return r;
+    if (n_active) *n_active = n;
+    return PT_OK;
+}
+
+// pt_lightmap_denoise and pt_lightmap_denoise_counts (counts: the per-texel sample counts, null for the former) under the context's lock
+int lightmap_denoise_locked(pt_ctx* c, int on_device, const pt_lightmap_denoise_params* p, const float* rgb_sum, const float* sumsq, const uint32_t* counts,
+                            bool per_texel, float* rgb_mean, float* texel_area)
+{
+    int r;
+    if (!p || !rgb_sum || !rgb_mean) return fail(c, PT_ERR_ARG, "pt_lightmap_denoise: p, rgb_sum and rgb_mean must not be NULL");
+    if (per_texel && !counts) return fail(c, PT_ERR_ARG, "pt_lightmap_denoise_counts: counts must not be NULL");
+    if (p->reserved[0] || p->reserved[1] || p->reserved[2] || p->reserved[3]) return fail(c, PT_ERR_ARG, "pt_lightmap_denoise_params.reserved must be 0");
+    if ((r = lightmap_check(c, p->model, p->instance, p->w, p->h))) return r;
+    DenoiseK dk{};
+    if ((r = denoise_params(c, &p->filter, dk))) return r;
+    if (per_texel && p->n_samples != 0) return fail(c, PT_ERR_ARG, "pt_lightmap_denoise_counts: pt_lightmap_denoise_params.n_samples must be 0 (the counts are per texel)");
+    if (!per_texel && (p->n_samples == 0 || p->n_samples > (1u << 24))) return fail(c, PT_ERR_ARG, "pt_lightmap_denoise_params.n_samples must be from 1 to 2^24");
+    if (!(p->reach >= 0.0f) || !std::isfinite(p->reach)) return fail(c, PT_ERR_ARG, "pt_lightmap_denoise_params.reach must be finite and >= 0");
+    const size_t px = (size_t)p->w * p->h;
+    for (size_t i = 0; i < px * 3; ++i)
+        if (!(rgb_sum[i] >= 0.0f) || !std::isfinite(rgb_sum[i])) return fail(c, PT_ERR_ARG, "pt_lightmap_denoise: a value of rgb_sum that is negative or not finite");
+    for (size_t i = 0; sumsq && i < px; ++i)
+        if (!(sumsq[i] >= 0.0f) || !std::isfinite(sumsq[i])) return fail(c, PT_ERR_ARG, "pt_lightmap_denoise: a value of sumsq that is negative or not finite");
+    const float reach = p->reach != 0.0f ? p->reach : 2.0f;
+    const LmFilterK k{dk, reach * reach};
+    const HostModel& m = c->scene.models[p->model];
+    std::vector<uint32_t> owner;
+    if (per_texel)
+    {
+        // a covered texel's count is from 1 to 2^24 (the filter would take a count of 0 for an invalid texel, silently); the coverage is
+        // worked out for this only when some texel at all is outside
+        size_t k0 = 0;
+        while (k0 < px && counts[k0] >= 1u && counts[k0] <= kMaxTexelCount) ++k0;
+        if (k0 < px)
+        {
+            try { lightmap_owner_host(m, p->w, p->h, owner); }
+            catch (const std::exception& e) { return fail(c, PT_ERR_LIMIT, std::string("the texel table does not fit in host memory: ") + e.what()); }
+            for (; k0 < px; ++k0)
+                if (owner[k0] != MISS_ID && (counts[k0] < 1u || counts[k0] > kMaxTexelCount))
+                    return fail(c, PT_ERR_ARG, "pt_lightmap_denoise_counts: a covered texel's count must be from 1 to 2^24");
+        }
+    }
+    if (!on_device)
+    {
+        try
+        {
+            if (owner.empty()) lightmap_owner_host(m, p->w, p->h, owner);
+            std::vector<float> P(px * 3), N(px * 3);
+            for (size_t t = 0; t < px; ++t)
+            {
+                float u32, v32;
+                f3 x, n;
+                lm_resolve_host(m.uvs.data(), m.positions.data(), m.normals.data(), m.matrices[p->instance], p->w, p->h, t, owner[t], &u32, &v32, &x, &n);
+                store3(P.data(), t, x);
+                store3(N.data(), t, n);
+            }
+            lmf_filter_host(p->w, p->h, k, owner.data(), P.data(), N.data(), m.positions.data(), m.uvs.data(), rgb_sum, sumsq, p->n_samples, counts, rgb_mean, texel_area);
+        }
+        catch (const std::exception& e) { return fail(c, PT_ERR_LIMIT, std::string("the texel filter's images do not fit in host memory: ") + e.what()); }
+        return PT_OK;
+    }
+    if ((r = ensure_device(c))) return r;
+    Staging st(c);
+    LightmapDev t{};
+    if ((r = lightmap_texels_device(c, st, m, p->instance, p->w, p->h, t))) return r;
+    LmFilterImages im{};
+    im.prim = t.prim; im.position = t.position; im.normal = t.normal;
+    im.sum = st.in<float>(rgb_sum, 3 * px);
+    im.sumsq = sumsq ? st.in<float>(sumsq, px) : nullptr;
+    im.counts = counts ? st.in<uint32_t>(counts, px) : nullptr;
+    im.cv_a = st.out<f4>(px); im.cv_b = st.out<f4>(px); im.pa = st.out<f4>(px); im.nv = st.out<f4>(px);
+    im.rgb = st.out<float>(rgb_mean, 3 * px);
+    im.area = texel_area ? st.out<float>(texel_area, px) : nullptr; // (the kernel skips a null area)
+    if (st.err) return st.err;
+    launch_lightmap_denoise(c->stream, t.view, k, p->n_samples, sumsq != nullptr, im);
+    return st.fetch();
+}
 } // namespace
 extern "C" {
+
+int pt_bake_lightmap_adaptive(pt_ctx* c, const pt_lightmap_params* p, const pt_adaptive* crit, float* rgb_sum, float* sumsq, uint32_t* counts, uint8_t* coverage,
+                              uint32_t* n_active)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    return bake_lightmap_adaptive_locked(c, p, crit, rgb_sum, sumsq, counts, coverage, n_active);
+}
+
+int pt_lightmap_adaptive_mask(pt_ctx* c, int on_device, int model, uint32_t instance, uint32_t w, uint32_t h, const pt_adaptive* crit, const float* rgb_sum,
+                              const float* sumsq, const uint32_t* counts, uint8_t* mask, uint32_t* n_active)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    int r;
+    if ((r = lightmap_check(c, model, instance, w, h))) return r;
+    if (!crit || !rgb_sum || !sumsq || !counts || !n_active) return fail(c, PT_ERR_ARG, "pt_lightmap_adaptive_mask: crit, rgb_sum, sumsq, counts and n_active must not be NULL");
+    if ((r = adaptive_crit_check(c, crit))) return r;
+    const HostModel& m = c->scene.models[model];
+    bool over = false;
+    if ((r = lightmap_counts_over(c, m, w, h, counts, 0u, &over))) return r;
+    if (over) return fail(c, PT_ERR_LIMIT, "pt_lightmap_adaptive_mask: a covered texel's count is above 2^24: f32 counts are not exact beyond");
+    const size_t px = (size_t)w * h;
+    if (!on_device)
+    {
+        std::vector<uint32_t> owner;
+        try { lightmap_owner_host(m, w, h, owner); }
+        catch (const std::exception& e) { return fail(c, PT_ERR_LIMIT, std::string("the texel table does not fit in host memory: ") + e.what()); }
+        const AdaptiveCrit cr{crit->rel_error, crit->abs_floor, crit->min_samples, crit->max_samples};
+        uint32_t n = 0;
+        for (size_t k = 0; k < px; ++k)
+        {
+            // (an uncovered texel is not read for its values)
+            uint32_t n_p;
+            bool bad;
+            const bool act = owner[k] != MISS_ID && adaptive_active(f4{rgb_sum[3 * k], rgb_sum[3 * k + 1], rgb_sum[3 * k + 2], (float)counts[k]}, sumsq[k], cr, n_p, bad);
+            if (mask) mask[k] = act ? 1u : 0u;
+            n += act ? 1u : 0u;
+        }
+        *n_active = n;
+        return PT_OK;
+    }
+    if ((r = ensure_device(c))) return r;
+    Staging st(c);
+    LightmapDev t{};
+    if ((r = lightmap_texels_device(c, st, m, instance, w, h, t))) return r;
+    const float* d_sum = st.in<float>(rgb_sum, 3 * px);
+    const float* d_sq = st.in<float>(sumsq, px);
+    const uint32_t* d_counts = st.in<uint32_t>(counts, px);
+    uint2* d_list = nullptr;
+    uint32_t n = 0;
+    if ((r = lightmap_select_device(c, st, t, px, crit, 0u, d_sum, d_sq, d_counts, &d_list, &n))) return r;
+    // the mask is made from the LIST, which has to be the bake's: ascending texels, each with its count
+    std::vector<uint2> list(n);
+    if (n > 0 && (r = st.fetch(list.data(), d_list, n))) return r;
+    if (mask) std::memset(mask, 0, px);
+    for (uint32_t i = 0; i < n; ++i)
+    {
+        if (list[i].x >= px || (i > 0 && list[i].x <= list[i - 1].x) || list[i].y != counts[list[i].x])
+            return fail(c, PT_ERR_HIP, "pt_lightmap_adaptive_mask: the selection's list is not ascending texels with their counts");
+        if (mask) mask[list[i].x] = 1u;
+    }
+    *n_active = n;
+    return PT_OK;
+}
+
+int pt_lightmap_denoise_counts(pt_ctx* c, int on_device, const pt_lightmap_denoise_params* p, const float* rgb_sum, const float* sumsq, const uint32_t* counts,
+                               float* rgb_mean, float* texel_area)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    return lightmap_denoise_locked(c, on_device, p, rgb_sum, sumsq, counts, true, rgb_mean, texel_area);
+}
 
 int pt_bake_lightmap(pt_ctx* c, const pt_lightmap_params* p, float* rgb_sum, uint8_t* coverage)
 {
@@ -3771,56 +4016,7 @@ int pt_lightmap_denoise(pt_ctx* c, int on_device, const pt_lightmap_denoise_para
 {
     if (!c) return PT_ERR_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
-    int r;
-    if (!p || !rgb_sum || !rgb_mean) return fail(c, PT_ERR_ARG, "pt_lightmap_denoise: p, rgb_sum and rgb_mean must not be NULL");
-    if (p->reserved[0] || p->reserved[1] || p->reserved[2] || p->reserved[3]) return fail(c, PT_ERR_ARG, "pt_lightmap_denoise_params.reserved must be 0");
-    if ((r = lightmap_check(c, p->model, p->instance, p->w, p->h))) return r;
-    DenoiseK dk{};
-    if ((r = denoise_params(c, &p->filter, dk))) return r;
-    if (p->n_samples == 0 || p->n_samples > (1u << 24)) return fail(c, PT_ERR_ARG, "pt_lightmap_denoise_params.n_samples must be from 1 to 2^24");
-    if (!(p->reach >= 0.0f) || !std::isfinite(p->reach)) return fail(c, PT_ERR_ARG, "pt_lightmap_denoise_params.reach must be finite and >= 0");
-    const size_t px = (size_t)p->w * p->h;
-    for (size_t i = 0; i < px * 3; ++i)
-        if (!(rgb_sum[i] >= 0.0f) || !std::isfinite(rgb_sum[i])) return fail(c, PT_ERR_ARG, "pt_lightmap_denoise: a value of rgb_sum that is negative or not finite");
-    for (size_t i = 0; sumsq && i < px; ++i)
-        if (!(sumsq[i] >= 0.0f) || !std::isfinite(sumsq[i])) return fail(c, PT_ERR_ARG, "pt_lightmap_denoise: a value of sumsq that is negative or not finite");
-    const float reach = p->reach != 0.0f ? p->reach : 2.0f;
-    const LmFilterK k{dk, reach * reach};
-    const HostModel& m = c->scene.models[p->model];
-    if (!on_device)
-    {
-        try
-        {
-            std::vector<uint32_t> owner;
-            lightmap_owner_host(m, p->w, p->h, owner);
-            std::vector<float> P(px * 3), N(px * 3);
-            for (size_t t = 0; t < px; ++t)
-            {
-                float u32, v32;
-                f3 x, n;
-                lm_resolve_host(m.uvs.data(), m.positions.data(), m.normals.data(), m.matrices[p->instance], p->w, p->h, t, owner[t], &u32, &v32, &x, &n);
-                store3(P.data(), t, x);
-                store3(N.data(), t, n);
-            }
-            lmf_filter_host(p->w, p->h, k, owner.data(), P.data(), N.data(), m.positions.data(), m.uvs.data(), rgb_sum, sumsq, p->n_samples, rgb_mean, texel_area);
-        }
-        catch (const std::exception& e) { return fail(c, PT_ERR_LIMIT, std::string("the texel filter's images do not fit in host memory: ") + e.what()); }
-        return PT_OK;
-    }
-    if ((r = ensure_device(c))) return r;
-    Staging st(c);
-    LightmapDev t{};
-    if ((r = lightmap_texels_device(c, st, m, p->instance, p->w, p->h, t))) return r;
-    LmFilterImages im{};
-    im.prim = t.prim; im.position = t.position; im.normal = t.normal;
-    im.sum = st.in<float>(rgb_sum, 3 * px);
-    im.sumsq = sumsq ? st.in<float>(sumsq, px) : nullptr;
-    im.cv_a = st.out<f4>(px); im.cv_b = st.out<f4>(px); im.pa = st.out<f4>(px); im.nv = st.out<f4>(px);
-    im.rgb = st.out<float>(rgb_mean, 3 * px);
-    im.area = texel_area ? st.out<float>(texel_area, px) : nullptr; // (the kernel skips a null area)
-    if (st.err) return st.err;
-    launch_lightmap_denoise(c->stream, t.view, k, p->n_samples, sumsq != nullptr, im);
-    return st.fetch();
+    return lightmap_denoise_locked(c, on_device, p, rgb_sum, sumsq, nullptr, false, rgb_mean, texel_area);
 }
 
 int pt_lightmap_dilate(pt_ctx* c, uint32_t w, uint32_t h, uint32_t passes, float* rgb, uint8_t* coverage)

@@ -138,18 +138,50 @@ void launch_lightmap_fold(hipStream_t s, const LightmapBake& lb, uint64_t first,
 // pt_bake_lightmap_directional: the same window folded by twelve threads per covered texel, the three sums as above and the nine first moments
 // dir[texel][axis][channel] += L[channel] * d[axis] (d: the window's ray table, launch_lightmap_rays' directions) in the same order
 void launch_lightmap_fold_directional(hipStream_t s, const LightmapBake& lb, uint64_t first, uint32_t count, const f4* radiance, const float* d, float* sum, float* dir);
+// Adaptive bakes (pt_bake_lightmap_adaptive): the items are the entries {texel, its sample count} of launch_lightmap_select's list instead of
+// every covered texel, and ray r is sample list[r / n_samples].y + r % n_samples of texel list[r / n_samples].x; otherwise LightmapBake, and
+// the same rays and fold kernels, instantiated over this record.
+struct LightmapAdaptiveBake
+{
+    const uint2* list;
+    const float* position;
+    const float* normal;
+    uint32_t n_active, n_samples, key_base, n_sobol;
+    float bias;
+    uint64_t seed;
+};
+void launch_lightmap_rays(hipStream_t s, const LightmapAdaptiveBake& lb, uint64_t first, uint32_t count, float* o, float* d, uint2* key);
+void launch_lightmap_fold(hipStream_t s, const LightmapAdaptiveBake& lb, uint64_t first, uint32_t count, const f4* radiance, float* sum, float* sumsq);
+// The texel selection: texel k is ACTIVE iff coverage[k] (launch_lightmap_resolve's byte) and adaptive_active (pt_types.h) of (sum[k],
+// sumsq[k], counts[k]).  Two passes over the table, no atomic append: list <- {k, counts[k]} of the active texels in ascending k (room for
+// n_texels entries), header[0] <- their number, header[1] |= 1 when an ACTIVE OR INACTIVE covered texel has counts[k] + n_samples > 2^24.
+// header: 4 zeroed words; block_counts: lightmap_select_blocks(n_texels) words of scratch.  Uncovered texels are read for their byte only.
+struct LightmapSelect
+{
+    const uint8_t* coverage;
+    const float *sum, *sumsq;
+    const uint32_t* counts;
+    uint32_t n_texels, n_samples;
+    AdaptiveCrit cr;
+};
+uint32_t lightmap_select_blocks(uint32_t n_texels);
+void launch_lightmap_select(hipStream_t s, const LightmapSelect& sel, uint32_t* block_counts, uint2* list, uint32_t* header);
+// counts[list[i].x] += n_samples for i < n_active: once per call, after its last window was folded
+void launch_lightmap_advance(hipStream_t s, const uint2* list, uint32_t n_active, uint32_t n_samples, uint32_t* counts);
 // pt_lightmap_gradient: grad <- lm_gradient (pt_lightmap.h) of every texel of launch_lightmap_resolve's table (coverage, normal), zeros where uncovered
 void launch_lightmap_gradient(hipStream_t s, uint32_t n_texels, const uint8_t* coverage, const float* normal, uint32_t n_samples, const float* dir, float* grad);
 // one dilation pass (lm_dilate) of a w x h map from (rgb, cov) to (rgb_out, cov_out)
 void launch_lightmap_dilate(hipStream_t s, uint32_t w, uint32_t h, const float* rgb, const uint8_t* cov, float* rgb_out, uint8_t* cov_out);
 // the texel filter (pt_lightmap_denoise: pt_filter.h's a-trous core under pt_lightmap_filter.h's texel rule) of the map of lm: prim, position, normal are
 // launch_lightmap_resolve's table, sum (w * h * 3) and sumsq (w * h; read with `moments` only, else the spatial variance) the bake's; cv_a, cv_b,
-// pa, nv: scratch of w * h 16-byte entries each; rgb <- the means (w * h * 3, zeros where uncovered); area (may be null) <- the texel areas
+// pa, nv: scratch of w * h 16-byte entries each; rgb <- the means (w * h * 3, zeros where uncovered); area (may be null) <- the texel areas;
+// counts (pt_lightmap_denoise_counts; null: every texel has n_samples): the sample count of each texel, w * h words, n_samples then unread
 struct LmFilterK;
 struct LmFilterImages
 {
     const uint32_t* prim;
     const float *position, *normal, *sum, *sumsq;
+    const uint32_t* counts;
     f4 *cv_a, *cv_b, *pa, *nv;
     float* rgb;
     float* area;

@@ -2766,21 +2766,7 @@ __global__ void __launch_bounds__(256) k_probe_radiance_prefilter(const Prefilte
 }
 
 // ------------------------------------------------------------------------------------------------ adaptive selection (PT_FLAG_ADAPTIVE)
-// The criterion of pt_api.h's pt_adaptive, in f32 with every operation correctly rounded and in this order (the tests restate it in
-// numpy bit for bit).  The count is an exact integer in [0, 2^24] or the pixel is bad (the call fails with PT_ERR_LIMIT).
-__device__ __forceinline__ bool adaptive_active(const f4 a, const float qsum, const AdaptiveCrit& cr, uint32_t& n_p, bool& bad)
-{
-    const float n = a.w;
-    bad = !(n >= 0.0f && n <= 16777216.0f && n == truncf(n));
-    n_p = bad ? 0u : (uint32_t)n;
-    const float m = luminance(a.x, a.y, a.z) / n;
-    float v = qsum / n - m * m;
-    if (!(v > 0.0f)) v = 0.0f;
-    const float e2 = v / n;
-    const float t = cr.rel_error * (m > cr.abs_floor ? m : cr.abs_floor);
-    return !bad && (n_p < cr.min_samples || ((cr.max_samples == 0u || n_p < cr.max_samples) && e2 > t * t));
-}
-
+// (the criterion itself, adaptive_active, is pt_types.h's: the texel selection of pt_lightmap.hip and the host share it)
 // Two passes, no atomic append: the list comes out in ascending pixel order whatever the scheduling.  Block b owns local pixels
 // [b * kSelectPerBlock, (b + 1) * kSelectPerBlock), thread i of it pixels b * kSelectPerBlock + j * 256 + i (j = 0..3).
 // k_adaptive_count: active pixels per block -> counts[b]; a bad count anywhere sets header[1].

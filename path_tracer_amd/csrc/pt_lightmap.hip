@@ -6,6 +6,8 @@
 //   k_lm_rays      a thread per ray: origin P + bias * n, a cosine-distributed direction over n, the stream key
 //   k_lm_fold      a thread per (covered texel, channel): the window's radiance added to the texel's sum in sample order; with MOMENTS a
 //                  fourth thread per texel adds l(L) * l(L) to its second moment (pt_bake_lightmap_moments)
+//   k_lm_select_*  pt_bake_lightmap_adaptive: the active texels {texel, its sample count} compacted in ascending order, two passes, no atomics;
+//                  k_lm_rays and k_lm_fold run over that list (LightmapAdaptiveBake) as they run over the covered texels; k_lm_advance
 //   k_lm_fold_dir  pt_bake_lightmap_directional: twelve threads per covered texel, the three sums as k_lm_fold and nine first moments L[c] * d[a]
 //   k_lm_gradient  a thread per texel: the tangential gradient of the first moments (lm_gradient)
 //   k_lm_dilate    a thread per texel: one dilation pass from one buffer pair to the other
@@ -76,15 +78,24 @@ __global__ void __launch_bounds__(256) k_lm_resolve(const LightmapView lm, const
     coverage[k] = tri < lm.n_tris ? (uint8_t)1u : (uint8_t)0u;
 }
 
-// rays [first, first + count) of a bake into entries [0, count) of a ray table: sample first_sample + r % n_samples of covered texel r / n_samples
-__global__ void __launch_bounds__(256) k_lm_rays(const LightmapBake lb, const uint64_t first, const uint32_t count, float* __restrict__ o,
+// item `rank` of a bake, {texel, the texel's first sample of the call}: the rank-th covered texel from the call's first_sample, or (adaptive)
+// the rank-th entry of the selection's list, whose texel continues from its own count
+__device__ __forceinline__ uint2 bake_item(const LightmapBake& lb, uint32_t rank) { return make_uint2(lb.texels[rank], lb.first_sample); }
+__device__ __forceinline__ uint2 bake_item(const LightmapAdaptiveBake& lb, uint32_t rank) { return lb.list[rank]; }
+
+// rays [first, first + count) of a bake into entries [0, count) of a ray table: sample first_sample + r % n_samples of covered texel r / n_samples,
+// or, over a LightmapAdaptiveBake, sample list[r / n_samples].y + r % n_samples of texel list[r / n_samples].x
+template <class Bake>
+__global__ void __launch_bounds__(256) k_lm_rays(const Bake lb, const uint64_t first, const uint32_t count, float* __restrict__ o,
                                                   float* __restrict__ d, uint2* __restrict__ key)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= count) return;
     const uint64_t r = first + i;
-    const uint32_t rank = (uint32_t)(r / lb.n_samples), s = lb.first_sample + (uint32_t)(r - (uint64_t)rank * lb.n_samples);
-    const uint32_t k = lb.texels[rank];
+    const uint32_t rank = (uint32_t)(r / lb.n_samples);
+    const uint2 item = bake_item(lb, rank);
+    const uint32_t s = item.y + (uint32_t)(r - (uint64_t)rank * lb.n_samples);
+    const uint32_t k = item.x;
     const float* pp = lb.position + 3u * (size_t)k;
     const float* pn = lb.normal + 3u * (size_t)k;
     const f3 n{pn[0], pn[1], pn[2]};
@@ -119,8 +130,8 @@ __device__ __forceinline__ void fold_channel(float* __restrict__ dst, const floa
 // definition (float addition does not associate) and no atomics: fold_channel.
 // MOMENTS: four threads per texel; the fourth folds Q[texel] += l(L) * l(L) over the same rays in the same order, and the other three run
 // the code they run without it
-template <bool MOMENTS>
-__global__ void __launch_bounds__(256) k_lm_fold(const LightmapBake lb, const uint64_t first, const uint32_t count, const f4* __restrict__ radiance,
+template <bool MOMENTS, class Bake>
+__global__ void __launch_bounds__(256) k_lm_fold(const Bake lb, const uint64_t first, const uint32_t count, const f4* __restrict__ radiance,
                                                   float* __restrict__ sum, float* __restrict__ sumsq)
 {
     constexpr uint32_t CH = MOMENTS ? 4u : 3u;
@@ -132,7 +143,7 @@ __global__ void __launch_bounds__(256) k_lm_fold(const LightmapBake lb, const ui
     const uint32_t i0 = (uint32_t)((lo > first ? lo : first) - first), i1 = (uint32_t)((hi < first + count ? hi : first + count) - first);
     if (MOMENTS && c == 3u)
     {
-        float* q = sumsq + lb.texels[rank];
+        float* q = sumsq + bake_item(lb, rank).x;
         float acc = *q;
         for (uint32_t i = i0; i < i1; ++i)
         {
@@ -142,7 +153,101 @@ __global__ void __launch_bounds__(256) k_lm_fold(const LightmapBake lb, const ui
         *q = acc;
         return;
     }
-    fold_channel(sum + 3u * (size_t)lb.texels[rank] + c, (const float*)radiance + c, i0, i1);
+    fold_channel(sum + 3u * (size_t)bake_item(lb, rank).x + c, (const float*)radiance + c, i0, i1);
+}
+
+// ---- the texel selection of an adaptive bake (pt_bake_lightmap_adaptive, pt_lightmap_adaptive_mask)
+__device__ __forceinline__ uint32_t lane_id() { return threadIdx.x & 63u; }
+__device__ __forceinline__ uint32_t mbcnt64(uint64_t m)
+{
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+}
+// is texel k < n_texels active?  n_k: its count; over: a covered texel whose count the call would take beyond 2^24, where f32 stops counting.
+// An uncovered texel is read for its coverage byte and nothing else.
+__device__ __forceinline__ bool texel_active(const LightmapSelect& sel, const uint32_t k, uint32_t& n_k, bool& over)
+{
+    n_k = 0u;
+    over = false;
+    if (!sel.coverage[k]) return false;
+    n_k = sel.counts[k];
+    over = (uint64_t)n_k + sel.n_samples > (1ull << 24);
+    const float* s = sel.sum + 3u * (size_t)k;
+    uint32_t n_p;
+    bool bad; // (not below the limit: the float is then the count)
+    return adaptive_active(f4{s[0], s[1], s[2], (float)n_k}, sel.sumsq[k], sel.cr, n_p, bad);
+}
+
+// k_adaptive_count / k_adaptive_write's two passes (pt_kernels.hip) over the texel table: block b owns texels [b * kSelectPerBlock,
+// (b + 1) * kSelectPerBlock), thread i of it texels b * kSelectPerBlock + j * 256 + i (j = 0..3), so the list comes out in ascending texel order
+// whatever the scheduling.  k_lm_select_count: active texels per block -> block_counts[b]; a count over the limit anywhere sets header[1].
+__global__ void __launch_bounds__(256) k_lm_select_count(const LightmapSelect sel, uint32_t* __restrict__ block_counts, uint32_t* __restrict__ header)
+{
+    __shared__ uint32_t sh_cnt[4];
+    const uint32_t base = blockIdx.x * kSelectPerBlock;
+    uint32_t mine = 0u;
+    bool any_over = false;
+#pragma unroll
+    for (uint32_t j = 0; j < kSelectPerBlock / 256u; ++j)
+    {
+        const uint32_t k = base + j * 256u + threadIdx.x;
+        if (k >= sel.n_texels) break;
+        uint32_t n_k;
+        bool over;
+        mine += texel_active(sel, k, n_k, over) ? 1u : 0u;
+        any_over |= over;
+    }
+    if (any_over) atomicOr(header + 1, 1u);
+    uint32_t w = mine;
+    for (int off = 32; off > 0; off >>= 1) w += (uint32_t)__shfl_xor((int)w, off);
+    if (lane_id() == 0u) sh_cnt[threadIdx.x >> 6] = w;
+    __syncthreads();
+    if (threadIdx.x == 0u) block_counts[blockIdx.x] = sh_cnt[0] + sh_cnt[1] + sh_cnt[2] + sh_cnt[3];
+}
+// k_lm_select_write: the block's offset is the sum of the counts of the blocks before it; each group of 256 texels is compacted with one
+// ballot per wave, mbcnt for a lane's rank in its wave and the waves' counts in LDS.  The last block writes the total to header[0].
+__global__ void __launch_bounds__(256) k_lm_select_write(const LightmapSelect sel, const uint32_t* __restrict__ block_counts, uint2* __restrict__ list,
+                                                          uint32_t* __restrict__ header)
+{
+    __shared__ uint32_t sh_sum[4];
+    __shared__ uint32_t sh_wave[kSelectPerBlock / 256u][4];
+    const uint32_t wid = threadIdx.x >> 6;
+    uint32_t before = 0u;
+    for (uint32_t b = threadIdx.x; b < blockIdx.x; b += 256u) before += block_counts[b];
+    for (int off = 32; off > 0; off >>= 1) before += (uint32_t)__shfl_xor((int)before, off);
+    if (lane_id() == 0u) sh_sum[wid] = before;
+    const uint32_t base = blockIdx.x * kSelectPerBlock;
+    bool act[kSelectPerBlock / 256u];
+    uint32_t nk[kSelectPerBlock / 256u];
+    uint64_t m[kSelectPerBlock / 256u];
+#pragma unroll
+    for (uint32_t j = 0; j < kSelectPerBlock / 256u; ++j)
+    {
+        const uint32_t k = base + j * 256u + threadIdx.x;
+        bool over;
+        nk[j] = 0u;
+        act[j] = k < sel.n_texels && texel_active(sel, k, nk[j], over);
+        m[j] = __ballot(act[j]);
+        if (lane_id() == 0u) sh_wave[j][wid] = (uint32_t)__popcll(m[j]);
+    }
+    __syncthreads();
+    uint32_t off = sh_sum[0] + sh_sum[1] + sh_sum[2] + sh_sum[3];
+#pragma unroll
+    for (uint32_t j = 0; j < kSelectPerBlock / 256u; ++j)
+    {
+        uint32_t pos = off;
+        for (uint32_t w2 = 0; w2 < wid; ++w2) pos += sh_wave[j][w2];
+        if (act[j]) list[pos + mbcnt64(m[j])] = make_uint2(base + j * 256u + threadIdx.x, nk[j]);
+        off += sh_wave[j][0] + sh_wave[j][1] + sh_wave[j][2] + sh_wave[j][3];
+    }
+    if (blockIdx.x + 1u == gridDim.x && threadIdx.x == 0u) header[0] = off;
+}
+// the call's samples are in the sums: every listed texel's count moves on, once, after the last window's fold
+__global__ void __launch_bounds__(256) k_lm_advance(const uint2* __restrict__ list, const uint32_t n_active, const uint32_t n_samples, uint32_t* __restrict__ counts)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_active) return;
+    const uint2 e = list[i];
+    counts[e.x] = e.y + n_samples;
 }
 
 // pt_bake_lightmap_directional: twelve threads per covered texel.  The first three fold the sums with the code they run in k_lm_fold; thread
@@ -213,13 +318,16 @@ __global__ void __launch_bounds__(256) k_lm_dilate(const uint32_t w, const uint3
 }
 
 // ---- the texel filter (pt_lightmap_denoise)
+// COUNTS (pt_lightmap_denoise_counts): a texel's sample count is counts[k] instead of the map's n
+template <bool COUNTS>
 __global__ void __launch_bounds__(256) k_lmf_prep(const LightmapView lm, const uint32_t* __restrict__ prim, const float* __restrict__ position,
                                                    const float* __restrict__ normal, const float* __restrict__ sum, const float* __restrict__ sumsq, const float n,
-                                                   f4* __restrict__ cv, f4* __restrict__ pa, f4* __restrict__ nv, float* __restrict__ area)
+                                                   const uint32_t* __restrict__ counts, f4* __restrict__ cv, f4* __restrict__ pa, f4* __restrict__ nv,
+                                                   float* __restrict__ area)
 {
     const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= lm.w * lm.h) return;
-    lmf_prep(k, lm.w, lm.h, prim, position, normal, lm.positions, lm.uv, sum, sumsq, n, cv, pa, nv);
+    lmf_prep(k, lm.w, lm.h, prim, position, normal, lm.positions, lm.uv, sum, sumsq, COUNTS ? (float)counts[k] : n, cv, pa, nv);
     if (area) area[k] = pa[k].w;
 }
 
@@ -264,14 +372,38 @@ void launch_lightmap_resolve(hipStream_t s, const LightmapView& lm, const uint32
 void launch_lightmap_rays(hipStream_t s, const LightmapBake& lb, uint64_t first, uint32_t count, float* o, float* d, uint2* key)
 {
     if (count == 0) return;
-    hipLaunchKernelGGL(k_lm_rays, blocks_for(count), dim3(256), 0, s, lb, first, count, o, d, key);
+    hipLaunchKernelGGL(k_lm_rays<LightmapBake>, blocks_for(count), dim3(256), 0, s, lb, first, count, o, d, key);
+}
+void launch_lightmap_rays(hipStream_t s, const LightmapAdaptiveBake& lb, uint64_t first, uint32_t count, float* o, float* d, uint2* key)
+{
+    if (count == 0) return;
+    hipLaunchKernelGGL(k_lm_rays<LightmapAdaptiveBake>, blocks_for(count), dim3(256), 0, s, lb, first, count, o, d, key);
 }
 void launch_lightmap_fold(hipStream_t s, const LightmapBake& lb, uint64_t first, uint32_t count, const f4* radiance, float* sum, float* sumsq)
 {
     if (count == 0) return;
     const uint64_t texels = (first + count - 1u) / lb.n_samples - first / lb.n_samples + 1u;
-    if (sumsq) hipLaunchKernelGGL(k_lm_fold<true>, blocks_for(texels * 4u), dim3(256), 0, s, lb, first, count, radiance, sum, sumsq);
-    else hipLaunchKernelGGL(k_lm_fold<false>, blocks_for(texels * 3u), dim3(256), 0, s, lb, first, count, radiance, sum, sumsq);
+    if (sumsq) hipLaunchKernelGGL((k_lm_fold<true, LightmapBake>), blocks_for(texels * 4u), dim3(256), 0, s, lb, first, count, radiance, sum, sumsq);
+    else hipLaunchKernelGGL((k_lm_fold<false, LightmapBake>), blocks_for(texels * 3u), dim3(256), 0, s, lb, first, count, radiance, sum, sumsq);
+}
+void launch_lightmap_fold(hipStream_t s, const LightmapAdaptiveBake& lb, uint64_t first, uint32_t count, const f4* radiance, float* sum, float* sumsq)
+{
+    if (count == 0) return;
+    const uint64_t texels = (first + count - 1u) / lb.n_samples - first / lb.n_samples + 1u;
+    hipLaunchKernelGGL((k_lm_fold<true, LightmapAdaptiveBake>), blocks_for(texels * 4u), dim3(256), 0, s, lb, first, count, radiance, sum, sumsq);
+}
+uint32_t lightmap_select_blocks(uint32_t n_texels) { return (n_texels + kSelectPerBlock - 1u) / kSelectPerBlock; }
+void launch_lightmap_select(hipStream_t s, const LightmapSelect& sel, uint32_t* block_counts, uint2* list, uint32_t* header)
+{
+    const uint32_t blocks = lightmap_select_blocks(sel.n_texels);
+    if (blocks == 0) return;
+    hipLaunchKernelGGL(k_lm_select_count, dim3(blocks), dim3(256), 0, s, sel, block_counts, header);
+    hipLaunchKernelGGL(k_lm_select_write, dim3(blocks), dim3(256), 0, s, sel, (const uint32_t*)block_counts, list, header);
+}
+void launch_lightmap_advance(hipStream_t s, const uint2* list, uint32_t n_active, uint32_t n_samples, uint32_t* counts)
+{
+    if (n_active == 0) return;
+    hipLaunchKernelGGL(k_lm_advance, blocks_for(n_active), dim3(256), 0, s, list, n_active, n_samples, counts);
 }
 void launch_lightmap_fold_directional(hipStream_t s, const LightmapBake& lb, uint64_t first, uint32_t count, const f4* radiance, const float* d, float* sum, float* dir)
 {
@@ -294,8 +426,9 @@ void launch_lightmap_denoise(hipStream_t s, const LightmapView& lm, const LmFilt
     const dim3 tile(16, 16), grid((lm.w + 15u) / 16u, (lm.h + 15u) / 16u);
     f4* cur = im.cv_a;
     f4* other = im.cv_b;
-    hipLaunchKernelGGL(k_lmf_prep, blocks_for((uint64_t)lm.w * lm.h), dim3(256), 0, s, lm, im.prim, im.position, im.normal, im.sum, moments ? im.sumsq : (const float*)nullptr,
-                       (float)n_samples, cur, im.pa, im.nv, im.area);
+    const float* q = moments ? im.sumsq : (const float*)nullptr;
+    if (im.counts) hipLaunchKernelGGL(k_lmf_prep<true>, blocks_for((uint64_t)lm.w * lm.h), dim3(256), 0, s, lm, im.prim, im.position, im.normal, im.sum, q, 0.0f, im.counts, cur, im.pa, im.nv, im.area);
+    else hipLaunchKernelGGL(k_lmf_prep<false>, blocks_for((uint64_t)lm.w * lm.h), dim3(256), 0, s, lm, im.prim, im.position, im.normal, im.sum, q, (float)n_samples, im.counts, cur, im.pa, im.nv, im.area);
     if (!moments)
     {
         hipLaunchKernelGGL(k_lmf_spatial_var, grid, tile, 0, s, w, h, p, (const f4*)cur, (const f4*)im.pa, (const f4*)im.nv, other);

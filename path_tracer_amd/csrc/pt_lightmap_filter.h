@@ -49,7 +49,7 @@ struct TexelRule
 };
 
 // the three images' entries of texel k from the texel table (prim, P, n: pt_lightmap_texels'), the model's load-order positions and UVs and
-// the sums; n = (float)n_samples; sumsq null: variance 0, the spatial pass fills it in
+// the sums; n = the texel's sample count as f32 (the map's n_samples, or its own: pt_lightmap_denoise_counts); sumsq null: variance 0, the spatial pass fills it in
 PT_HD void lmf_prep(uint32_t k, uint32_t w, uint32_t h, const uint32_t* prim, const float* position, const float* normal, const float* positions9,
                     const float* uvs6, const float* sum, const float* sumsq, float n, f4* cv, f4* pa, f4* nv)
 {
@@ -72,14 +72,15 @@ PT_HD void lmf_prep(uint32_t k, uint32_t w, uint32_t h, const uint32_t* prim, co
 }
 
 // The whole filter on the host: the walk on_device = 0 does.  prim, position, normal: the texel table; positions9, uvs6: the model's
-// load-order arrays; rgb_mean w * h * 3; texel_area w * h or null
+// load-order arrays; rgb_mean w * h * 3; texel_area w * h or null; counts (pt_lightmap_denoise_counts) w * h sample counts, or null: n_samples everywhere
 inline void lmf_filter_host(uint32_t w, uint32_t h, const LmFilterK& p, const uint32_t* prim, const float* position, const float* normal,
-                            const float* positions9, const float* uvs6, const float* sum, const float* sumsq, uint32_t n_samples, float* rgb_mean,
-                            float* texel_area)
+                            const float* positions9, const float* uvs6, const float* sum, const float* sumsq, uint32_t n_samples, const uint32_t* counts,
+                            float* rgb_mean, float* texel_area)
 {
     const size_t px = (size_t)w * h;
     std::vector<f4> cv(px), other(px), pa(px), nv(px);
-    for (size_t k = 0; k < px; ++k) lmf_prep((uint32_t)k, w, h, prim, position, normal, positions9, uvs6, sum, sumsq, (float)n_samples, cv.data(), pa.data(), nv.data());
+    for (size_t k = 0; k < px; ++k)
+        lmf_prep((uint32_t)k, w, h, prim, position, normal, positions9, uvs6, sum, sumsq, (float)(counts ? counts[k] : n_samples), cv.data(), pa.data(), nv.data());
     if (texel_area)
         for (size_t k = 0; k < px; ++k) texel_area[k] = pa[k].w;
     const int iw = (int)w, ih = (int)h;

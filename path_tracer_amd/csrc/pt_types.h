@@ -330,7 +330,24 @@ struct AdaptiveCrit
     float rel_error, abs_floor;
     uint32_t min_samples, max_samples; // max_samples 0: no cap
 };
-enum : uint32_t { kSelectPerBlock = 1024u }; // local pixels per workgroup of the selection kernels (k_adaptive_count / k_adaptive_write)
+enum : uint32_t { kSelectPerBlock = 1024u }; // local pixels (texels) per workgroup of the selection kernels (k_adaptive_count / k_adaptive_write, k_lm_select_*)
+// The criterion of pt_api.h's pt_adaptive, in f32 with every operation correctly rounded and in this order (the tests restate it in numpy bit
+// for bit), on a = the colour sums | the sample count and qsum = Q.  The count is an exact integer in [0, 2^24] or the pixel is bad (the call
+// fails with PT_ERR_LIMIT); n = 0 computes 0 / 0 and the answer does not depend on it.  One definition for the pixel selection
+// (pt_kernels.hip), for the texel selection (pt_lightmap.hip), whose a.w is (float)counts[k] of a count the host has held to 2^24, and for
+// the host evaluation (pt_lightmap_adaptive_mask)
+PT_HD bool adaptive_active(const f4 a, const float qsum, const AdaptiveCrit& cr, uint32_t& n_p, bool& bad)
+{
+    const float n = a.w;
+    bad = !(n >= 0.0f && n <= 16777216.0f && n == truncf(n));
+    n_p = bad ? 0u : (uint32_t)n;
+    const float m = ((0.2126f * a.x + 0.7152f * a.y) + 0.0722f * a.z) / n;
+    float v = qsum / n - m * m;
+    if (!(v > 0.0f)) v = 0.0f;
+    const float e2 = v / n;
+    const float t = cr.rel_error * (m > cr.abs_floor ? m : cr.abs_floor);
+    return !bad && (n_p < cr.min_samples || ((cr.max_samples == 0u || n_p < cr.max_samples) && e2 > t * t));
+}
 
 // wavefront state, one slot per path (pid = s_local * local_pixels + local_pixel).  What a shading pass reads and writes together is
 // ONE 64-byte record: in later bounces only a sparse subset of paths is alive, and a record costs one memory sector per live path

@@ -14,7 +14,16 @@ The difference is coverage, resolve, ray generation, fold and the map's copies; 
 times the texel filter (pt_lightmap_denoise, profiles/r23_lightmap_denoise.md) beside the bake it follows: the moments bake against the plain
 bake at 16 samples, the blocking filter call at 1 and at 5 levels (their difference / 4 is a level; what is left of the 1-level call is the
 texel table, the prep and the staging of the map's copies), and the filter's purpose on the tests' 48 x 32 map: RMSE over covered texels of
-the raw and of the denoised mean at 4, 16 and 64 samples against a 4096-sample bake of disjoint samples."""
+the raw and of the denoised mean at 4, 16 and 64 samples against a 4096-sample bake of disjoint samples.
+
+    python tools/lightmap_bench.py --adaptive [--size 1024] [--spp 16] [--reps 5] [--rel 0.05] [--cap 64] [--out report.json]
+
+measures adaptive baking (pt_bake_lightmap_adaptive, profiles/r32_adaptive_lightmap.md).  OVERHEAD: one all-active adaptive call from zero
+arrays (min_samples = max_samples = SPP) beside pt_bake_lightmap_moments of the same SPP at SIZE x SIZE, alternating; the rays and the fold
+are the same, so the difference is the selection and the three arrays' transfers less the coverage round trip saved.  GAIN: on the tests'
+48 x 32 map and on a 256 x 256 one, rounds of 4 samples under (REL, floor 0.01, at least 4, at most CAP) until no texel is selected, beside
+uniform bakes of the same ray budget (the mean count rounded down and up): RMSE over covered texels, raw and through the texel filter,
+against a 4096-sample bake of OTHER samples (key_base shifted by 2^24), and the distribution of the counts."""
 import argparse
 import json
 import os
@@ -94,9 +103,59 @@ def denoise_report(r, model, size, reps):
     return report
 
 
+def adaptive_report(r, model, size, spp, reps, rel, cap):
+    report = {"size": size, "spp": spp, "rel_error": rel, "cap": cap, "bake_moments_ms": [], "adaptive_all_active_ms": []}
+    for _ in range(2):                  # warm-up at the timed shape: scene upload, code objects, the wavefront pool, the staging sizes
+        r.bake_lightmap_moments(model, 0, size, size, spp, bias=BIAS)
+        r.bake_lightmap_adaptive(model, 0, size, size, spp, 0.0, min_samples=spp, max_samples=spp, bias=BIAS)
+    for _ in range(reps):               # the two routes alternate, so that a drift of the shared machine touches both
+        t0 = time.perf_counter()
+        plain = r.bake_lightmap_moments(model, 0, size, size, spp, bias=BIAS)
+        report["bake_moments_ms"].append(1e3 * (time.perf_counter() - t0))
+        t0 = time.perf_counter()
+        ad = r.bake_lightmap_adaptive(model, 0, size, size, spp, 0.0, min_samples=spp, max_samples=spp, bias=BIAS)
+        report["adaptive_all_active_ms"].append(1e3 * (time.perf_counter() - t0))
+    report["covered"] = int(plain[2].sum())
+    report["all_active_equals_plain"] = bool(np.array_equal(plain[0].view(np.uint32), ad[0].view(np.uint32)) and np.array_equal(plain[1].view(np.uint32), ad[1].view(np.uint32))
+                                             and ad[4] == report["covered"])
+    report["overhead_ms"] = float(np.median(report["adaptive_all_active_ms"]) - np.median(report["bake_moments_ms"]))
+    report["gain"] = {}
+    f32 = np.float32
+    for w, h in ((48, 32), (256, 256)):
+        ref, cov = r.bake_lightmap(model, 0, w, h, 4096, key_base=1 << 24, bias=BIAS)
+        ref = ref / f32(4096)
+        covered = cov == 1
+        state, rays, rounds, spent = (None, None, None), 0, 0, 0.0
+        while True:
+            t0 = time.perf_counter()
+            *state, _, n_active = r.bake_lightmap_adaptive(model, 0, w, h, 4, rel, abs_floor=0.01, min_samples=4, max_samples=cap, bias=BIAS, sums=state[0], sumsq=state[1], counts=state[2])
+            spent += time.perf_counter() - t0
+            if n_active == 0:
+                break
+            rays += n_active * 4
+            rounds += 1
+        sums, sumsq, counts = state
+        mean = np.zeros_like(sums)
+        mean[covered] = sums[covered] / counts[covered].astype(f32)[:, None]
+        values, freq = np.unique(counts[covered], return_counts=True)
+        g = {"covered": int(covered.sum()), "rays": int(rays), "rounds": rounds, "adaptive_ms": 1e3 * spent, "mean_count": float(counts[covered].mean()),
+             "counts": {str(int(v)): int(f) for v, f in zip(values, freq)},
+             "adaptive": {"raw": rmse(mean, ref, covered), "denoised": rmse(r.denoise_lightmap(model, 0, sums, 0, sumsq=sumsq, counts=counts), ref, covered)}}
+        for name, n in (("uniform_floor", rays // g["covered"]), ("uniform_ceil", -(-rays // g["covered"]))):
+            t0 = time.perf_counter()
+            u = r.bake_lightmap_moments(model, 0, w, h, n, bias=BIAS)
+            g[name] = {"samples": int(n), "rays": int(n) * g["covered"], "ms": 1e3 * (time.perf_counter() - t0), "raw": rmse(u[0] / f32(n), ref, covered),
+                       "denoised": rmse(r.denoise_lightmap(model, 0, u[0], n, sumsq=u[1]), ref, covered)}
+        report["gain"][f"{w}x{h}"] = g
+    return report
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--denoise", action="store_true")
+    ap.add_argument("--adaptive", action="store_true")
+    ap.add_argument("--rel", type=float, default=0.05)
+    ap.add_argument("--cap", type=int, default=64)
     ap.add_argument("--size", type=int, default=1024)
     ap.add_argument("--spp", type=int, default=64)
     ap.add_argument("--reps", type=int, default=3)
@@ -112,8 +171,8 @@ def main():
     sc, model = LC.cornell_atlas_scene(args.model, W, H)
     r = api.Renderer(sc, W, H, max_bounces=DEPTH)
     size, spp = args.size, args.spp
-    if args.denoise:
-        line = json.dumps(denoise_report(r, model, size, args.reps))
+    if args.denoise or args.adaptive:
+        line = json.dumps(adaptive_report(r, model, size, spp, args.reps, args.rel, args.cap) if args.adaptive else denoise_report(r, model, size, args.reps))
         print(line)
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
