@@ -63,6 +63,10 @@
 //                                        tangent-space vector (0.3 * tri((i + 0.5) / N), 0.3 * tri((j + 0.5) / N), z), tri(a) = 4 * |a - 0.5| - 1, z making it
 //                                        a unit vector, encoded 0.5 * v + 0.5 (every step one binary32 operation).  UVs: s = x, t = y + z over the model's own
 //                                        extents, so that the floor, the ceiling and the back wall all have a tangent frame
+//   examples/headless ... --metal-box --roughness-checker N   an N x N checker of linear roughness 0.1 / 0.6 (texel (i, j): 0.6 where i + j is odd) as
+//                                        the ROUGHNESS map (pt_set_material_roughness_texture) of the tall box --metal-box turns to GGX metal, under
+//                                        planar UVs set the way --checker sets cb_main.obj's: the GGX alpha of a hit is its bilinear texel's first
+//                                        component squared, and the material's own roughness 0.4 is not read
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -89,7 +93,7 @@ int main(int argc, char** argv)
     bool temporal_option = false;
     uint32_t render_first = 0, render_count = 0;
     float aperture = 0.0f, focus = 950.0f; // main.rs:127's values: a pinhole
-    uint32_t probes[3] = {0, 0, 0}, probe_spp = 0, checker = 0, emission_checker = 0, normal_ripples = 0, follow = 0;
+    uint32_t probes[3] = {0, 0, 0}, probe_spp = 0, checker = 0, emission_checker = 0, normal_ripples = 0, roughness_checker = 0, follow = 0;
     std::string probes_out = "";
     uint32_t lightmap[4] = {0, 0, 0, 0}; // W H SPP PASSES
     std::string lightmap_out = "";
@@ -142,6 +146,7 @@ int main(int argc, char** argv)
         else if (a == "--gpus") gpus = (uint32_t)std::atoi(next("--gpus"));
         else if (a == "--checker") checker = (uint32_t)std::atoi(next("--checker"));
         else if (a == "--normal-ripples") normal_ripples = (uint32_t)std::atoi(next("--normal-ripples"));
+        else if (a == "--roughness-checker") roughness_checker = (uint32_t)std::atoi(next("--roughness-checker"));
         else if (a == "--emission-checker") emission_checker = (uint32_t)std::atoi(next("--emission-checker"));
         else if (a == "--spp") spp = (uint32_t)std::atoi(next("--spp"));
         else if (a == "--render") { render_mode = true; render_first = (uint32_t)std::atoi(next("--render")); render_count = (uint32_t)std::atoi(next("--render")); }
@@ -193,7 +198,7 @@ int main(int argc, char** argv)
         }
         else if (a == "--help" || a == "-h")
         {
-            std::printf("usage: %s [--width W] [--height H] [--frames N] [--bounces B] [--move] [--slide DX DZ] [--models DIR] [--out file.png] [--temporal file.png [--temporal-rescue] [--temporal-mean-length] [--temporal-demodulate]] [--denoise file.png] [--denoise-albedo file.png] [--follow K] [--mirror-glass] [--aperture A --focus F] [--projection panorama[:SX:SY]|ortho:HEIGHT] [--bake-probes NX NY NZ SPP file.txt] [--bake-lightmap W H SPP PASSES file.txt [--adaptive REL MAX] [--lightmap-denoise | --directional] [--baked-view SPP file.png]] [--probe-grid NX NY NZ SPP [--probe-depth R] [--probe-radiance R] --baked-view SPP file.png] [--metal-box] [--checker N] [--emission-checker N] [--normal-ripples N]\n", argv[0]);
+            std::printf("usage: %s [--width W] [--height H] [--frames N] [--bounces B] [--move] [--slide DX DZ] [--models DIR] [--out file.png] [--temporal file.png [--temporal-rescue] [--temporal-mean-length] [--temporal-demodulate]] [--denoise file.png] [--denoise-albedo file.png] [--follow K] [--mirror-glass] [--aperture A --focus F] [--projection panorama[:SX:SY]|ortho:HEIGHT] [--bake-probes NX NY NZ SPP file.txt] [--bake-lightmap W H SPP PASSES file.txt [--adaptive REL MAX] [--lightmap-denoise | --directional] [--baked-view SPP file.png]] [--probe-grid NX NY NZ SPP [--probe-depth R] [--probe-radiance R] --baked-view SPP file.png] [--metal-box] [--checker N] [--emission-checker N] [--normal-ripples N] [--metal-box --roughness-checker N]\n", argv[0]);
             return 0;
         }
         else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
@@ -242,6 +247,12 @@ int main(int argc, char** argv)
         std::fprintf(stderr, "--normal-ripples cannot be combined with --checker, or with --bake-lightmap unless --directional: each sets the UVs of cb_main.obj\n");
         return 2;
     }
+    if (roughness_checker && (!metal_box || mirror_glass))
+    {
+        // the map goes on the GGX metal --metal-box makes of the tall box (a mirror has no roughness), whose UVs no other option sets
+        std::fprintf(stderr, "--roughness-checker N puts a roughness map on the box --metal-box turns to metal: it needs that option, and does not go with --mirror-glass\n");
+        return 2;
+    }
     if (!temporal_out.empty() && (!out.empty() || !denoise_out.empty() || !denoise_albedo_out.empty() || render_mode || gpus > 0 || !devices.empty()))
     {
         // frame_temporal leaves the accumulation alone: there is nothing in it for these to write
@@ -285,6 +296,16 @@ int main(int argc, char** argv)
             main_gray = main_gray.NormalMapped(Texture::New(n, n, std::move(texels)));
         }
 
+        Material box_metal = GGX::NewMetal(Vec3A{0.9f, 0.8f, 0.6f}, 0.4f);
+        if (roughness_checker)
+        {
+            const uint32_t n = roughness_checker;
+            std::vector<float> texels;
+            for (uint32_t j = 0; j < n; ++j)
+                for (uint32_t i = 0; i < n; ++i) texels.insert(texels.end(), 3, ((i + j) & 1u) ? 0.6f : 0.1f);
+            box_metal = box_metal.RoughnessMapped(Texture::New(n, n, std::move(texels)));
+        }
+
         // Models and BVHs  main.rs:94-117 (the two blocks the reference has commented out stand in for its dragon, whose file it does not ship)
         const std::vector<Affine3A> one{Affine3A::IDENTITY()};
         const Scene scene = Scene::New({
@@ -292,7 +313,7 @@ int main(int argc, char** argv)
             Model::New(models_dir + "/cb_main.obj", main_gray, one),
             Model::New(models_dir + "/cb_right.obj", diffuse_red, one),
             Model::New(models_dir + "/cb_left.obj", diffuse_green, one),
-            Model::New(models_dir + "/cb_box_tall.obj", mirror_glass ? Specular::New(Vec3A::splat(1.0f)) : metal_box ? GGX::NewMetal(Vec3A{0.9f, 0.8f, 0.6f}, 0.4f) : diffuse_gray, one),
+            Model::New(models_dir + "/cb_box_tall.obj", mirror_glass ? Specular::New(Vec3A::splat(1.0f)) : metal_box ? box_metal : diffuse_gray, one),
             Model::New(models_dir + "/cb_box_short.obj", mirror_glass ? Dielectric::New(Vec3A::splat(0.95f), 1.5f, std::nullopt) : diffuse_gray, one),
         });
 
@@ -332,6 +353,7 @@ int main(int argc, char** argv)
         };
         if (checker || !lightmap_out.empty()) planar_uvs(1);
         if (emission_checker) planar_uvs(0);
+        if (roughness_checker) planar_uvs(4);
         if (normal_ripples && lightmap_out.empty())
         {
             // s = x, t = y + z, each over the model's own extent: no face of the room is degenerate in them

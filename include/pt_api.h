@@ -194,7 +194,7 @@ int pt_get_scene_info(pt_ctx* ctx, pt_scene_info* out);
  * negative or not finite, a UV that is not finite, a bad index, n_tris different from the model's, or an emissive material; PT_ERR_LIMIT
  * for a texture side above 16384 texels or more than 2^28 texels in all textures together (texels are addressed by 32-bit offsets into one
  * 16-byte-per-texel buffer).  A refused call changes nothing.
- * Out of scope: mip maps and filter footprints, nearest filtering, roughness maps (normal maps: pt_set_material_normal_texture, below), changing texel data after upload,
+ * Out of scope: mip maps and filter footprints, nearest filtering (normal maps: pt_set_material_normal_texture, roughness maps: pt_set_material_roughness_texture, both below), changing texel data after upload,
  * PNG decoding.  (Demodulating the denoiser's input by the albedo is pt_denoise_albedo, below.) */
 int pt_add_texture(pt_ctx* ctx, uint32_t w, uint32_t h, const float* rgb_linear);        /* returns the texture index */
 int pt_set_material_texture(pt_ctx* ctx, int material, int texture);                     /* texture -1 clears */
@@ -298,7 +298,7 @@ int pt_set_material_emission_texture(pt_ctx* ctx, int material, int texture);   
  * with a normal-mapped material is a textured scene (UVs, texel tables, TEX variants, queued shadow rays) that also carries one 16-byte
  * tangent per triangle and runs the normal-map variants of the surface passes; a scene without one flattens to the bytes and launches the
  * kernels it does without this entry point.
- * Out of scope: a strength / scale factor, object-space normal maps, roughness / height / parallax maps, mip maps, per-vertex tangents (the
+ * Out of scope: a strength / scale factor, object-space normal maps, height / parallax maps (roughness maps: below), mip maps, per-vertex tangents (the
  * tangent is per triangle, so it is discontinuous across the edges of a curved mesh), the guides (pt_render_guides' normal guide and
  * pt_guide_follow_dir keep the unperturbed normal: a followed reflection in a rippled mirror is the smooth mirror's), the lightmap baker's
  * hemisphere, and microfacet-style fixes for perturbed normals below the horizon. */
@@ -308,6 +308,45 @@ int pt_set_material_normal_texture(pt_ctx* ctx, int material, int texture);     
  * on_device 0 evaluates on the host and touches no GPU; 1 runs a kernel over the same function.  PT_ERR_STATE: not built */
 int pt_shading_normal(pt_ctx* ctx, int on_device, uint32_t n, const uint32_t* instance, const uint32_t* prim, const float* u, const float* v,
                       const float* dir_xyz, float* out_normal_xyz, uint8_t* out_front);
+
+/* ---- roughness maps: per-hit GGX roughness from a texture --------------------------------------------------------------- */
+/* The reference's GGX materials have one roughness each; this is the library's own addition, defined here and checked bit for bit.
+ * A PT_GGX_METAL or PT_GGX_DIELECTRIC material may reference one texture of pt_add_texture as its ROUGHNESS TEXTURE, independently of its
+ * colour and normal textures.
+ *
+ * All arithmetic is binary32, one rounding per operation, no contraction.  The GGX ALPHA at a hit (instance, load-order triangle,
+ * barycentrics u, v) of such a material is
+ *     s, t  = the hit's interpolated, repeat-addressed UV          -- exactly the surface colour's s, t
+ *     c     = get_pixel_bilinear(roughness texture, s, t)          -- with the normal map's exception: four equal texels (r, g and b) are
+ *                                                                     that texel, with no arithmetic
+ *     rho   = c.r                                                  -- the texel's first component IS the linear roughness; g and b are not read
+ *     x     = rho * rho
+ *     alpha = x < 1e-4f ? 1e-4f : (x > 0.9999f ? 0.9999f : x)     -- the expression pt_add_material applies (material.rs:294,309)
+ * The material's own `roughness` is not read where a map is set; clearing the map restores it.  Without a roughness texture the alpha is the
+ * material's stored alpha, with no arithmetic.  A constant map of value rho, at any UVs, is the material GGX::new_*(.., rho, ..) bit for bit;
+ * at s = i/w, t = j/h (w and h powers of two) the alpha is texel (i, j)'s; a model without UVs reads (0, 0) everywhere.
+ *
+ * The alpha replaces the material's everywhere the surface shading pass uses it for the hit being shaded: the half-vector sample,
+ * get_bsdf_pdf and both direct-light estimates; and in the baked view's ending on GGX metal (pt_set_probe_grid_radiance: the level pair and
+ * blend of THE SPECULAR LOOKUP are those of the alpha at the hit).  Nothing else changes: the material kind and with it the shade class, RNG
+ * draws and ray tallies, media, the light sampler, the guides (GGX still ends a chain), and hooks keyed by a material index, which keep the
+ * material's own alpha.
+ *
+ * pt_set_material_roughness_texture makes the scene un-built like the other texture setters; the next pt_build rebuilds no BLAS and no TLAS
+ * (pt_scene_info's counters do not move) and the next render uploads in full; pt_set_instances + pt_build afterwards keeps the patch path,
+ * and pt_multi_render replicates it with the scene.  PT_ERR_ARG, before any device call, for a bad material or texture index or a kind other
+ * than the two GGX kinds; a refused call changes nothing.  A scene with a roughness-mapped material is a textured scene (UVs, texel tables,
+ * TEX variants, queued shadow rays), also when the roughness map is its only texture; it launches the variants its other textures call for
+ * (there is no roughness variant: the GGX instantiations of the TEX surface passes test the material's word at run time).  A scene without
+ * one flattens to the bytes and renders the bits it does without this entry point.
+ * Out of scope: a roughness factor on top of the map, reading another channel, anisotropy, metalness or specular maps, mip maps, a roughness
+ * guide for the denoisers, roughness-dependent following of GGX in the guides. */
+int pt_set_material_roughness_texture(pt_ctx* ctx, int material, int texture);           /* texture -1 clears */
+/* unit hook: the GGX alpha (as defined above) of n hits of a BUILT scene; instance = world-TLAS leaf in allocation order, prim in load order.
+ * The stored alpha for an unmapped GGX material, 0.0f for a kind that is not GGX.  on_device 0 evaluates on the host and touches no GPU; 1
+ * runs a kernel over the same function.  PT_ERR_STATE: not built; PT_ERR_ARG: a bad leaf or primitive, or a NULL pointer */
+int pt_surface_roughness(pt_ctx* ctx, int on_device, uint32_t n, const uint32_t* instance, const uint32_t* prim, const float* u, const float* v,
+                         float* alpha);
 
 /* ---- Camera::new / create_ray  src/camera.rs:17-31, 94-105 ---------------------------------------------------- */
 int pt_set_camera(pt_ctx* ctx, const float eye[3], const float target[3], float fov_y_deg, float aspect);
@@ -1371,7 +1410,8 @@ int pt_probe_radiance_prefilter(pt_ctx* ctx, int on_device, const pt_probe_radia
  * n > 0.
  * THE BAKED VIEW WITH RADIANCE.  While radiance is set, a chain of pt_render_baked that ends on a PT_GGX_METAL surface, on either face, becomes
  *     B = R_H * S   where THE SPECULAR LOOKUP is lit at P = the position and n = the normal that pt_render_guides_followed writes for that
- *     chain's end, d = the direction of the chain's last ray and a = the material's GGX alpha (roughness squared, clamped to 0.0001..0.9999)
+ *     chain's end, d = the direction of the chain's last ray and a = the GGX ALPHA AT THE HIT (roughness maps, above: the material's own
+ *     alpha, roughness squared and clamped to 0.0001..0.9999, without a roughness texture)
  * before any map is asked: a map holds irradiance, which a metal does not reflect diffusely.  Where the lookup is not lit the ending is what it
  * is without radiance, and every other kind is untouched.  The endings are instantiations of their own (the SPEC axis of k_baked_follow), chosen
  * on the host: without radiance every call launches what it launched and returns the bits it returned before.

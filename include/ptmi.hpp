@@ -18,7 +18,8 @@
 //   state.render()                        state.rs:629       ptmi::Renderer::present
 //   ImageHelper::write_image              image_helper.rs:37 ptmi::Renderer::write_image
 // The library's own additions have no line of the reference: ptmi::Texture with Material::Textured and Model::WithUVs (pt_add_texture),
-// Material::EmissionTextured (pt_set_material_emission_texture), Material::NormalMapped (pt_set_material_normal_texture).
+// Material::EmissionTextured (pt_set_material_emission_texture), Material::NormalMapped (pt_set_material_normal_texture),
+// Material::RoughnessMapped (pt_set_material_roughness_texture).
 #pragma once
 #include <array>
 #include <cmath>
@@ -79,10 +80,13 @@ struct Material
     Material EmissionTextured(const Texture& t) const { Material m = *this; m.emission_texture = t; return m; }
     std::optional<Texture> normal_texture; // tangent-space normal map: the shading normal is perturbed by its bilinear texel; any kind but Emissive
     Material NormalMapped(const Texture& t) const { Material m = *this; m.normal_texture = t; return m; }
+    std::optional<Texture> roughness_texture; // the hit's linear roughness = its bilinear texel's first component, `roughness` is not read; the two GGX kinds only
+    Material RoughnessMapped(const Texture& t) const { Material m = *this; m.roughness_texture = t; return m; }
     bool operator==(const Material& o) const
     {
         return (texture ? texture->rgb : nullptr) == (o.texture ? o.texture->rgb : nullptr) &&
                (normal_texture ? normal_texture->rgb : nullptr) == (o.normal_texture ? o.normal_texture->rgb : nullptr) &&
+               (roughness_texture ? roughness_texture->rgb : nullptr) == (o.roughness_texture ? o.roughness_texture->rgb : nullptr) &&
                (emission_texture ? emission_texture->rgb : nullptr) == (o.emission_texture ? o.emission_texture->rgb : nullptr) && d.kind == o.d.kind && d.colour[0] == o.d.colour[0] && d.colour[1] == o.d.colour[1] && d.colour[2] == o.d.colour[2] &&
                d.roughness == o.d.roughness && d.ior == o.d.ior && d.has_volume == o.d.has_volume &&
                (!d.has_volume || (d.vol_absorption[0] == o.d.vol_absorption[0] && d.vol_absorption[1] == o.d.vol_absorption[1] &&
@@ -192,6 +196,7 @@ inline void upload(pt_ctx* ctx_, const Scene& scene)
                 if (m.material.texture) check(pt_set_material_texture(ctx_, (int)idx, texture_index(*m.material.texture)));
                 if (m.material.emission_texture) check(pt_set_material_emission_texture(ctx_, (int)idx, texture_index(*m.material.emission_texture)));
                 if (m.material.normal_texture) check(pt_set_material_normal_texture(ctx_, (int)idx, texture_index(*m.material.normal_texture)));
+                if (m.material.roughness_texture) check(pt_set_material_roughness_texture(ctx_, (int)idx, texture_index(*m.material.roughness_texture)));
             }
             const float* mat = m.matrices.empty() ? nullptr : m.matrices[0].m.data();
             const uint32_t n_inst = (uint32_t)m.matrices.size();

@@ -43,6 +43,7 @@ EXPORTS = [
     "pt_set_instances", "pt_get_scene_info", "pt_read_guide_instances", "pt_frame_moving", "pt_post_motion",
     "pt_add_texture", "pt_set_material_texture", "pt_set_model_uvs", "pt_model_uvs", "pt_surface_colour", "pt_read_guide_albedo",
     "pt_set_material_emission_texture", "pt_set_material_normal_texture", "pt_shading_normal",
+    "pt_set_material_roughness_texture", "pt_surface_roughness",
     "pt_accumulate_albedo", "pt_reset_albedo", "pt_read_albedo", "pt_denoise_albedo", "pt_post_denoise_albedo",
     "pt_set_projection", "pt_get_projection",
     "pt_bake_lightmap", "pt_lightmap_texels", "pt_lightmap_ray", "pt_lightmap_dilate",
@@ -324,6 +325,8 @@ def lib():
         L.pt_set_material_emission_texture.argtypes = [vp, C.c_int, C.c_int]
         L.pt_set_material_normal_texture.argtypes = [vp, C.c_int, C.c_int]
         L.pt_shading_normal.argtypes = [vp, C.c_int, u32, vp, vp, vp, vp, vp, vp, vp]
+        L.pt_set_material_roughness_texture.argtypes = [vp, C.c_int, C.c_int]
+        L.pt_surface_roughness.argtypes = [vp, C.c_int, u32, vp, vp, vp, vp, vp]
         L.pt_set_model_uvs.argtypes = [vp, C.c_int, vp, u32]
         L.pt_model_uvs.argtypes = [vp, C.c_int, vp, u32, C.POINTER(u32)]
         L.pt_surface_colour.argtypes = [vp, C.c_int, u32, vp, vp, vp, vp, vp]
@@ -452,6 +455,8 @@ class Renderer:
                 self.set_material_emission_texture(mi, self._texture_index(m.emission_texture))
             if getattr(m, "normal_texture", None) is not None:
                 self.set_material_normal_texture(mi, self._texture_index(m.normal_texture))
+            if getattr(m, "roughness_texture", None) is not None:
+                self.set_material_roughness_texture(mi, self._texture_index(m.roughness_texture))
         return self._materials.index(m)
 
     def _texture_index(self, t) -> int:
@@ -475,7 +480,7 @@ class Renderer:
             self.set_model_uvs(r, mod.uvs)
         return r
 
-    # ---- textured surface colour (include/pt_api.h); the three setters un-build the scene: rebuild() before the next render
+    # ---- textured surface colour (include/pt_api.h); the texture setters un-build the scene: rebuild() before the next render
     def add_texture(self, rgb) -> int:
         """[h, w, 3] linear RGB, finite and non-negative; returns the texture index"""
         a = np.ascontiguousarray(rgb, dtype=np.float32)
@@ -495,6 +500,10 @@ class Renderer:
     def set_material_normal_texture(self, material: int, texture: int):
         """the tangent-space normal map of a material of any kind but EMISSIVE (include/pt_api.h); texture -1 clears"""
         self._chk(self.L.pt_set_material_normal_texture(self.ctx, material, texture))
+
+    def set_material_roughness_texture(self, material: int, texture: int):
+        """the roughness map of a GGX material: the texel's first component is the hit's linear roughness (include/pt_api.h); texture -1 clears"""
+        self._chk(self.L.pt_set_material_roughness_texture(self.ctx, material, texture))
 
     def set_model_uvs(self, model: int, uvs):
         """[n_tris, 3, 2] in load order; None clears"""
@@ -522,6 +531,16 @@ class Renderer:
         assert i.shape == p.shape == uu.shape == vv.shape and i.ndim == 1
         out = np.zeros((i.shape[0], 3), np.float32)
         self._chk(self.L.pt_surface_colour(self.ctx, int(bool(on_device)), i.shape[0], _p(i), _p(p), _p(uu), _p(vv), _p(out)))
+        return out
+
+    def surface_roughness(self, instance, prim, u, v, on_device=False):
+        """unit hook: the GGX alpha [n] of hits (world-TLAS instance, load-order primitive, barycentrics) of the built scene, roughness maps
+        applied; the stored alpha of an unmapped GGX material, 0 for a kind that is not GGX; on the host (no GPU) unless on_device"""
+        i = np.ascontiguousarray(instance, dtype=np.uint32); p = np.ascontiguousarray(prim, dtype=np.uint32)
+        uu = np.ascontiguousarray(u, dtype=np.float32); vv = np.ascontiguousarray(v, dtype=np.float32)
+        assert i.shape == p.shape == uu.shape == vv.shape and i.ndim == 1
+        out = np.zeros(i.shape[0], np.float32)
+        self._chk(self.L.pt_surface_roughness(self.ctx, int(bool(on_device)), i.shape[0], _p(i), _p(p), _p(uu), _p(vv), _p(out)))
         return out
 
     def shading_normal(self, instance, prim, u, v, direction, on_device=False):

@@ -16,6 +16,10 @@
 //   host_sanitize normals <n> <seed>   normal maps' host side: n random triangles with random UVs (degenerate, huge and mirrored ones among them) under a
 //                                      normal texture, Scene::new, then shading_normal (pt_materials.h) at random hits over the flattened tables;
 //                                      prints how many triangles got a tangent and a checksum of the normals
+//   host_sanitize roughness <n> <seed> roughness maps' host side: the setter's refusals (kinds that are not GGX, bad indices: nothing changes), then n
+//                                      random triangles with mirrored, negative, exactly-1 and 1e6 UVs under a 5 x 3 map, a model without UVs under a
+//                                      1 x 1 map and one under an 8 x 4 map, and surface_alpha (pt_materials.h) at random hits: every map's values lie in
+//                                      a range of its own and no alpha may leave its map's; clearing the maps gives the never-mapped scene's bytes
 //   host_sanitize lightmaps <n> <seed> lightmaps' host side: n random triangles with random UVs (far outside [0, 1], huge, mirrored and overflowing ones
 //                                      among them) under three placements, random maps of several sizes on two of them, then lightmap_lookup
 //                                      (pt_materials.h) at random hits; prints how many lookups met a map and a checksum of the results
@@ -291,6 +295,100 @@ int main(int argc, char** argv)
         // clearing takes the tangents out again
         if (sc.set_material_normal_texture(mat, -1) != 0 || sc.build(&err) != 0 || !sc.flat.tri_tan.empty() || sc.flat.has_textures) return 7;
         std::printf("{\"triangles\": %u, \"with_tangent\": %u, \"checksum\": %.6f}\n", n, with_tangent, acc);
+        return 0;
+    }
+    if (cmd == "roughness" && argc >= 4)
+    {
+        const uint32_t n = (uint32_t)std::atoi(argv[2]);
+        uint64_t s = 0x9E3779B97F4A7C15ull ^ (uint64_t)std::atoll(argv[3]);
+        auto rnd = [&]() { s ^= s << 13; s ^= s >> 7; s ^= s << 17; return (float)((s >> 40) & 0xffff) / 65535.0f; };
+        HostScene sc;
+        const int lam = light_scene(sc), light = 1;
+        if (lam < 0 || n == 0) return 3;
+        const float tint[3] = {0.9f, 0.8f, 0.7f}, zero[3] = {0, 0, 0};
+        const int metal = sc.add_material(MAT_GGX_METAL, tint, 0.3f, 1.0f, false, zero, 0, 0, 0);
+        const int glass = sc.add_material(MAT_GGX_DIELECTRIC, tint, 0.4f, 1.5f, false, zero, 0, 0, 0);
+        const int mirror = sc.add_material(MAT_SPECULAR, tint, 0.0f, 1.0f, false, zero, 0, 0, 0);
+        const int smooth = sc.add_material(MAT_DIELECTRIC, tint, 0.0f, 1.5f, false, zero, 0, 0, 0);
+        const int metal2 = sc.add_material(MAT_GGX_METAL, tint, 0.2f, 1.0f, false, zero, 0, 0, 0);
+        // three models: n triangles under a 5 x 3 map with hostile UVs (general, mirrored, negative, exactly 1, around 1e6), a few WITHOUT UVs
+        // under a 1 x 1 map, a few under an 8 x 4 map.  Every map's r values lie in a range of its own (g and b are loud), so a texel that left
+        // its texture shows in the alpha even where the sanitizer sees one allocation
+        auto soup = [&](uint32_t tris, std::vector<float>& p, std::vector<float>& nr) {
+            for (uint32_t t = 0; t < tris; ++t)
+            {
+                const float c[3] = {200.0f * rnd() - 100.0f, 200.0f * rnd() - 100.0f, 200.0f * rnd() - 100.0f};
+                for (int v = 0; v < 3; ++v)
+                    for (int k = 0; k < 3; ++k) { p.push_back(c[k] + 10.0f * rnd() - 5.0f); nr.push_back(k == 1 ? 1.0f : 0.2f * rnd() - 0.1f); }
+            }
+        };
+        std::vector<float> p0, n0, p1, n1, p2, n2, uv0, uv2;
+        soup(n, p0, n0); soup(7, p1, n1); soup(9, p2, n2);
+        for (uint32_t t = 0; t < n; ++t)
+        {
+            const uint32_t shape = t % 5u;
+            const float a[2] = {4.0f * rnd() - 2.0f, 4.0f * rnd() - 2.0f};
+            for (int v = 0; v < 3; ++v)
+                for (int k = 0; k < 2; ++k)
+                    uv0.push_back(shape == 1u ? (v ? -1.0f : 1.0f) * (a[k] + rnd()) : shape == 2u ? -3.0f * rnd() : shape == 3u ? (float)((v + k) & 1) : shape == 4u ? 1.0e6f + 3.0f * rnd() : a[k] + rnd());
+        }
+        for (uint32_t t = 0; t < 9u * 6u; ++t) uv2.push_back(t % 3u == 0u ? 1.0f : 5.0f * rnd() - 2.5f);
+        const float range[3][2] = {{0.1f, 0.2f}, {0.5f, 0.5f}, {0.8f, 0.9f}};
+        auto map = [&](uint32_t w, uint32_t h, const float* r) {
+            std::vector<float> texels;
+            for (uint32_t k = 0; k < w * h; ++k) { texels.push_back(r[0] + (r[1] - r[0]) * rnd()); texels.push_back(50.0f); texels.push_back(1.0e6f); }
+            return sc.add_texture(w, h, texels.data());
+        };
+        const int models[3] = {sc.add_model(p0.data(), n0.data(), n, metal, kIdentity, 1), sc.add_model(p1.data(), n1.data(), 7, glass, kIdentity, 1),
+                               sc.add_model(p2.data(), n2.data(), 9, metal2, kIdentity, 1)};
+        const int tex[3] = {map(5, 3, range[0]), map(1, 1, range[1]), map(8, 4, range[2])};
+        if (models[0] < 0 || models[1] < 0 || models[2] < 0 || tex[0] < 0 || tex[1] < 0 || tex[2] < 0) return 4;
+        if (sc.set_model_uvs(models[0], uv0.data(), n) != 0 || sc.set_model_uvs(models[2], uv2.data(), 9) != 0) return 4;
+        std::string err;
+        if (sc.build(&err) != 0) { std::printf("{\"error\": \"%s\"}\n", err.c_str()); return 0; }
+        if (sc.flat.has_textures || !sc.flat.tri_uv.empty()) return 5; // textures nobody references: no textured scene
+        const std::vector<DMaterial> never = sc.flat.materials, before = sc.materials;
+        // the refusals: a kind that is not GGX, a bad material, a bad texture; each changes nothing and leaves the scene built
+        const int refused[][2] = {{lam, tex[0]}, {light, tex[0]}, {mirror, tex[0]}, {smooth, tex[0]}, {lam, -1}, {light, -1}, {-1, tex[0]}, {99, tex[0]}, {metal, 3}, {metal, -2}, {glass, 99}};
+        for (const auto& rf : refused)
+            if (sc.set_material_roughness_texture(rf[0], rf[1]) != -1 || !sc.built || std::memcmp(sc.materials.data(), before.data(), before.size() * sizeof(DMaterial)) != 0) return 6;
+        const int mats[3] = {metal, glass, metal2};
+        for (int k = 0; k < 3; ++k)
+            if (sc.set_material_roughness_texture(mats[k], tex[k]) != 0 || sc.built) return 7;
+        const uint64_t blas_builds = sc.blas_builds;
+        if (sc.build(&err) != 0 || sc.blas_builds != blas_builds) return 8;
+        const FlatScene& f = sc.flat;
+        if (!f.has_textures || f.has_normal_maps || f.tri_uv.size() != f.tri_orig.size() || !f.tri_tan.empty()) return 9;
+        const TexView tv = f.tex_view();
+        double acc = 0.0;
+        uint32_t outside = 0, per_model[3] = {0, 0, 0};
+        for (uint32_t q = 0; q < 4u * n + 64u; ++q)
+        {
+            const uint32_t inst = (uint32_t)(rnd() * 3.999f) % (uint32_t)sc.world.instances.size();
+            const uint32_t mi = sc.world.instances[inst].model;
+            const uint32_t tri = f.tri_base[mi] + (uint32_t)(rnd() * (float)sc.blas[mi].tris.size()) % (uint32_t)sc.blas[mi].tris.size();
+            const uint32_t corner = q % 7u; // the vertices and an edge among the hits
+            const float u = corner == 0u ? 1.0f : corner == 1u ? 0.0f : rnd(), v = corner < 2u ? 0.0f : corner == 2u ? 1.0f - u : rnd() * (1.0f - u);
+            const float a = surface_roughness_at(f.instances.data(), f.materials.data(), tv, inst, tri, u, v);
+            int k = -1;
+            for (int j = 0; j < 3; ++j) if ((int)mi == models[j]) k = j;
+            if (k < 0) { if (a != 0.0f) ++outside; continue; } // the light: not GGX
+            ++per_model[k];
+            const float lo = range[k][0] * range[k][0], hi = range[k][1] * range[k][1];
+            if (!(a >= lo * 0.9999f && a <= hi * 1.0001f)) ++outside;
+            acc += a;
+        }
+        if (outside) { std::printf("{\"error\": \"%u alphas outside their texture's range\"}\n", outside); return 10; }
+        // clearing every map gives the bytes of the scene that never had one
+        for (int k = 0; k < 3; ++k)
+            if (sc.set_material_roughness_texture(mats[k], -1) != 0) return 11;
+        if (sc.build(&err) != 0 || sc.flat.has_textures || !sc.flat.tri_uv.empty() || sc.flat.materials.size() != never.size() ||
+            std::memcmp(sc.flat.materials.data(), never.data(), never.size() * sizeof(DMaterial)) != 0)
+            return 12;
+        const float own = surface_roughness_at(sc.flat.instances.data(), sc.flat.materials.data(), sc.flat.tex_view(), 1u, sc.flat.tri_base[models[0]], 0.25f, 0.25f);
+        if (own != clamp_rs(sq(0.3f), 0.0001f, 0.9999f)) return 13;
+        std::printf("{\"triangles\": %u, \"hits\": [%u, %u, %u], \"refused\": %zu, \"checksum\": %.6f}\n", n, per_model[0], per_model[1], per_model[2],
+                    sizeof(refused) / sizeof(refused[0]), acc);
         return 0;
     }
     if (cmd == "lightmaps" && argc >= 4)

@@ -2071,7 +2071,7 @@ int pt_add_texture(pt_ctx* c, uint32_t w, uint32_t h, const float* rgb_linear)
     return r;
 }
 
-// the three pt_set_material_*texture calls: HostScene's setter, `what` when it refuses
+// the four pt_set_material_*texture calls: HostScene's setter, `what` when it refuses
 static int set_material_texture(pt_ctx* c, int (HostScene::*set)(int, int), int material, int texture, const char* what)
 {
     if (!c) return PT_ERR_ARG;
@@ -2094,6 +2094,11 @@ int pt_set_material_emission_texture(pt_ctx* c, int material, int texture)
 int pt_set_material_normal_texture(pt_ctx* c, int material, int texture)
 {
     return set_material_texture(c, &HostScene::set_material_normal_texture, material, texture, "bad material or texture index, or an emissive material");
+}
+
+int pt_set_material_roughness_texture(pt_ctx* c, int material, int texture)
+{
+    return set_material_texture(c, &HostScene::set_material_roughness_texture, material, texture, "bad material or texture index, or a material that is not GGX");
 }
 
 int pt_set_model_uvs(pt_ctx* c, int model, const float* uv, uint32_t n_tris)
@@ -2122,7 +2127,7 @@ int pt_model_uvs(pt_ctx* c, int model, float* uv, uint32_t cap_tris, uint32_t* n
     return PT_OK;
 }
 
-// ---- the unit hooks pt_surface_colour and pt_shading_normal: n queries {world instance, load-order primitive, u, v}
+// ---- the unit hooks pt_surface_colour, pt_surface_roughness and pt_shading_normal: n queries {world instance, load-order primitive, u, v}
 // tri[i] <- the leaf-order triangle of query i: tri_orig inverted for the models asked about
 static int leaf_order_tris(pt_ctx* c, uint32_t n, const uint32_t* instance, const uint32_t* prim, std::vector<uint32_t>& tri)
 {
@@ -2185,6 +2190,32 @@ int pt_surface_colour(pt_ctx* c, int on_device, uint32_t n, const uint32_t* inst
     float* d_rgb = st.out<float>(rgb, 3 * (size_t)n);
     if (st.err) return st.err;
     launch_surface_colour(c->stream, c->sv, c->tex, n, q.instance, q.tri, q.u, q.v, d_rgb);
+    return st.fetch();
+}
+
+int pt_surface_roughness(pt_ctx* c, int on_device, uint32_t n, const uint32_t* instance, const uint32_t* prim, const float* u, const float* v, float* alpha)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->scene.built) return fail(c, PT_ERR_STATE, "pt_build has not been called");
+    if (n == 0) return PT_OK;
+    if (!instance || !prim || !u || !v || !alpha) return fail(c, PT_ERR_ARG, "null pointer");
+    const FlatScene& f = c->scene.flat;
+    std::vector<uint32_t> tri;
+    int r;
+    if ((r = leaf_order_tris(c, n, instance, prim, tri))) return r;
+    if (!on_device)
+    {
+        const TexView tv = f.tex_view();
+        for (uint32_t i = 0; i < n; ++i) alpha[i] = surface_roughness_at(f.instances.data(), f.materials.data(), tv, instance[i], tri[i], u[i], v[i]);
+        return PT_OK;
+    }
+    if ((r = upload_scene(c))) return r;
+    Staging st(c);
+    const SurfaceQueries q = upload_queries(st, n, instance, tri, u, v);
+    float* d_alpha = st.out<float>(alpha, n);
+    if (st.err) return st.err;
+    launch_surface_roughness(c->stream, c->sv, c->tex, n, q.instance, q.tri, q.u, q.v, d_alpha);
     return st.fetch();
 }
 

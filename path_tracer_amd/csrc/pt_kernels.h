@@ -322,6 +322,10 @@ void launch_guide_rays(hipStream_t s, const RenderParams& rp, const CameraView& 
 // unit hook (pt_surface_colour): rgb[i] <- surface colour of world instance[i], leaf-order triangle tri[i] at barycentrics u[i], v[i]
 void launch_surface_colour(hipStream_t s, const SceneView& sv, const TexView& tex, uint32_t n, const uint32_t* instance, const uint32_t* tri, const float* u,
                            const float* v, float* rgb);
+// unit hook (pt_surface_roughness): alpha[i] <- surface_roughness_at (pt_materials.h) of the same queries; tex is all null in a scene without textures
+// (no material then asks for it)
+void launch_surface_roughness(hipStream_t s, const SceneView& sv, const TexView& tex, uint32_t n, const uint32_t* instance, const uint32_t* tri, const float* u,
+                              const float* v, float* alpha);
 // unit hook (pt_shading_normal): out4[i] <- shading_normal (pt_materials.h) of world instance[i], leaf-order triangle tri[i] at barycentrics u[i], v[i]
 // for the world direction dir[i] | front.  tex.tri_tan is null in a scene without a normal map (no material then asks for it)
 void launch_shading_normal(hipStream_t s, const SceneView& sv, const TexNView& tex, uint32_t n, const uint32_t* instance, const uint32_t* tri, const float* u,

@@ -2011,7 +2011,12 @@ k_shade_surface(const ShadeArg<SURFACE> kargs)
             const uint32_t inst = hid >> sv.prim_bits, tri = hid & ((1u << sv.prim_bits) - 1u);
             const DInstance& in = sv.instances[inst];
             MatView mat = load_material(sv.materials, in.material);
+            // a roughness map (pt_set_material_roughness_texture): the GGX alpha of this hit, a run-time test inside the TEX variants of the
+            // GGX class, as `texture == 0u` is inside surface_colour; no other kernel reads the word.  Behind the colour's lookup: started before
+            // it behind a barrier, the plain SURF_TEX kernels gain 8 bytes of scratch, which here they do not (profiles/r33_roughness_maps.md)
             if (TEX) mat.colour = PT_TEX_EARLY ? surf : textured();
+            if constexpr (TEX && QCLASS == Q_GGX)
+                mat.alpha = surface_alpha(shade_args_tex(), sv.materials[in.material].roughness_texture, mat.alpha, tri, hit.y, hit.z);
             // the queue class fixes the material kind: let the compiler drop the other materials' code from this kernel
             if (QCLASS == Q_LAMBERT) mat.kind = (VOLUMES && mat.kind == MAT_EMISSIVE) ? (uint32_t)MAT_EMISSIVE : (uint32_t)MAT_LAMBERTIAN;
             else if (QCLASS == Q_SPECULAR) mat.kind = MAT_SPECULAR;
@@ -3103,7 +3108,7 @@ __global__ void __launch_bounds__(256, 8) k_guide_follow(const SceneView sv, con
 // SPEC, with radiance set on the grid (pt_set_probe_grid_radiance): a chain that ends on GGX metal, on either face, reflects the grid's
 // prefiltered radiance, B = R * S, where probe_grid_specular is lit, whether or not a map lights the surface (a map holds irradiance, which a
 // metal does not reflect diffusely); where it is not lit, and on every other kind, the ending is what it is without SPEC.  The metal branch
-// comes first and returns, so a lane holds one lookup's registers at a time.  P, n and d are ChainEnd's; the alpha is the material's own.
+// comes first and returns, so a lane holds one lookup's registers at a time.  P, n and d are ChainEnd's; the alpha is the hit's (surface_alpha).
 // DIR, with a gradient set and a normal-mapped material in the scene (pt_set_lightmap_directional): n' = shading_normal of the hit, delta =
 // n' - n (zero by construction without a normal texture); a front face of a mapped leaf reads lightmap_at_directional, and the grid takes n'.
 // n' is gathered behind a barrier of its own, after the hop's gathers and before the map's, so one lookup's registers are live at a time.
@@ -3134,7 +3139,10 @@ struct BakedEnding
         {
             if (h.kind == MAT_GGX_METAL)
             {
-                const float alpha = sv.materials[sv.instances[h.inst].material].alpha;
+                // the alpha AT THE HIT: the material's own without a roughness map (pt_set_material_roughness_texture), surface_alpha's with
+                // one; its four texels are gathered and blended before the barrier, so one lookup's registers are live at a time
+                const DMaterial& dm = sv.materials[sv.instances[h.inst].material];
+                const float alpha = surface_alpha(texn, dm.roughness_texture, dm.alpha, h.tri, h.hit.y, h.hit.z);
                 __asm__ volatile("" ::: "memory");
                 f3 s;
                 if (probe_grid_specular<VIS>(light.grid, light.rad, fma3(h.d, bc3(h.hit.x), xyz(a.in.a[h.slot])), h.nrm, h.d, alpha, &s, VIS ? &light.depth : nullptr))
@@ -3268,6 +3276,15 @@ __global__ void __launch_bounds__(256) k_surface_colour(const SceneView sv, cons
     if (i >= n) return;
     const f3 c = surface_colour_at(sv, tex, instance[i], tri[i], u[i], v[i]);
     rgb[3u * (size_t)i] = c.x; rgb[3u * (size_t)i + 1u] = c.y; rgb[3u * (size_t)i + 2u] = c.z;
+}
+// unit hook of surface_alpha (pt_surface_roughness): alpha[i] <- surface_roughness_at (pt_materials.h), as the host evaluation
+__global__ void __launch_bounds__(256) k_surface_roughness(const SceneView sv, const TexView tex, const uint32_t n, const uint32_t* __restrict__ instance,
+                                                           const uint32_t* __restrict__ tri, const float* __restrict__ u, const float* __restrict__ v,
+                                                           float* __restrict__ alpha)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    alpha[i] = surface_roughness_at(sv.instances, sv.materials, tex, instance[i], tri[i], u[i], v[i]);
 }
 // unit hook of shading_normal: out4 = world shading normal | front
 __global__ void __launch_bounds__(256) k_shading_normal(const SceneView sv, const TexNView tex, const uint32_t n, const uint32_t* __restrict__ instance,
@@ -3891,6 +3908,12 @@ void launch_surface_colour(hipStream_t s, const SceneView& sv, const TexView& te
 {
     if (n == 0u) return;
     hipLaunchKernelGGL(k_surface_colour, dim3((n + 255u) / 256u), dim3(256), 0, s, sv, tex, n, instance, tri, u, v, rgb);
+}
+void launch_surface_roughness(hipStream_t s, const SceneView& sv, const TexView& tex, uint32_t n, const uint32_t* instance, const uint32_t* tri, const float* u,
+                              const float* v, float* alpha)
+{
+    if (n == 0u) return;
+    hipLaunchKernelGGL(k_surface_roughness, dim3((n + 255u) / 256u), dim3(256), 0, s, sv, tex, n, instance, tri, u, v, alpha);
 }
 void launch_shading_normal(hipStream_t s, const SceneView& sv, const TexNView& tex, uint32_t n, const uint32_t* instance, const uint32_t* tri, const float* u,
                            const float* v, const float* dir, float* out4)

@@ -217,6 +217,31 @@ PT_HD f3 bilinear_rgb_const(const f4* data, uint32_t w, uint32_t h, float u, flo
     return bilinear_blend(t);
 }
 
+// Roughness maps (pt_set_material_roughness_texture; the definition is include/pt_api.h's): the GGX alpha of a hit.  `roughness_texture` =
+// DMaterial::roughness_texture (index + 1), `alpha` = DMaterial::alpha, returned with no arithmetic without a map; tri: leaf order.  With a
+// map: the first component of the bilinear texel (the normal map's lookup: a constant region is its texel) at surface_colour's s, t is the
+// linear roughness, squared and clamped as HostScene::add_material does (material.rs:294,309), so a constant map of rho is the material of
+// roughness rho bit for bit.  Shared by the GGX surface pass, the baked view's SPEC ending, the unit hook's kernel and its host evaluation.
+PT_HD float surface_alpha(const TexView& tv, uint32_t roughness_texture, float alpha, uint32_t tri, float u, float v)
+{
+    if (roughness_texture == 0u) return alpha;
+    const DTriUV uv = tv.tri_uv[tri];
+    const DTexture t = tv.table[roughness_texture - 1u];
+    float s = (uv.a[0] + u * (uv.b[0] - uv.a[0])) + v * (uv.c[0] - uv.a[0]);   // surface_colour's s, t
+    float w = (uv.a[1] + u * (uv.b[1] - uv.a[1])) + v * (uv.c[1] - uv.a[1]);
+    s = s - floorf(s);
+    w = w - floorf(w);
+    const float rho = bilinear_rgb_const(tv.texels + t.offset, t.w, t.h, s, w).x;
+    return clamp_rs(sq(rho), 0.0001f, 0.9999f);
+}
+// ... of a hit on world-TLAS leaf `inst` (pt_surface_roughness): 0 on a kind that is not GGX
+PT_HD float surface_roughness_at(const DInstance* instances, const DMaterial* materials, const TexView& tex, uint32_t inst, uint32_t tri, float u, float v)
+{
+    const DMaterial& dm = materials[instances[inst].material];
+    if (dm.kind != MAT_GGX_METAL && dm.kind != MAT_GGX_DIELECTRIC) return 0.0f;
+    return surface_alpha(tex, dm.roughness_texture, dm.alpha, tri, u, v);
+}
+
 // Normal maps (pt_set_material_normal_texture; the definition is include/pt_api.h's).  n: the object-space unit3(interpolated vertex normals)
 // of the hit, before face-forwarding; `normal_texture` = DMaterial::normal_texture (index + 1); tri: leaf order.  Returns the object-space
 // N': n itself, bit for bit, without a normal texture, at a flat texel (x == 0 and y == 0) and on a triangle without a tangent (T == 0).

@@ -464,6 +464,16 @@ int HostScene::set_material_normal_texture(int material, int texture)
     return 0;
 }
 
+int HostScene::set_material_roughness_texture(int material, int texture)
+{
+    if (material < 0 || material >= (int)materials.size() || texture < -1 || texture >= (int)textures.size()) return -1;
+    if (materials[material].kind != MAT_GGX_METAL && materials[material].kind != MAT_GGX_DIELECTRIC) return -1; // only GGX has an alpha
+    materials[material].roughness_texture = (uint32_t)(texture + 1);
+    built = false;
+    ++layout_epoch; // the UV, table and texel arrays come or go with the first / last reference: the next upload is a full one
+    return 0;
+}
+
 // The tangent of one triangle for its normal map (pt_api.h, TANGENTS): object-space positions p0 p1 p2, UVs a b c (s, t pairs) in load order;
 // T.xyz | sign.  Every operation one binary32 operation, in the header's order
 static f4 triangle_tangent(const f3 p[3], const float* uv)
@@ -804,6 +814,7 @@ int HostScene::flatten(std::string* err)
     for (const DMaterial& m : materials) f.has_emission_textures = f.has_emission_textures || (m.texture != 0 && m.kind == MAT_EMISSIVE);
     for (const DMaterial& m : materials) f.has_normal_maps = f.has_normal_maps || m.normal_texture != 0;
     f.has_textures = f.has_textures || f.has_normal_maps; // (a normal map is looked up like a colour texture: UVs, table and texels)
+    for (const DMaterial& m : materials) f.has_textures = f.has_textures || m.roughness_texture != 0; // (... and so is a roughness map)
     // One volume per model.  The reference keys its volume stack by the address of the material (volume.rs:146-162), and every BLAS
     // owns a copy of its model's material (blas.rs:167,197): two models of equal materials are two volumes, all instances of one model
     // are one.  The device keys the stack by material index, so the first model of a volume-bearing material keeps the index and

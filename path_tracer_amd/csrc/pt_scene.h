@@ -104,7 +104,7 @@ struct FlatScene
     uint32_t ident_tlas = 0;            // IDENT_TLAS_WORLD / IDENT_TLAS_LIGHTS: every instance of that TLAS carries INSTANCE_IDENTITY
     float light_weight_sum = 0;
     bool has_volumes = false;
-    bool has_textures = false;          // some material references a texture, as its surface colour or as its emission: the shading passes are the TEX variants
+    bool has_textures = false;          // some material references a texture, as its surface colour, its emission, its normal map or its roughness map: the shading passes are the TEX variants
     bool has_emission_textures = false; // ... and some EMISSIVE material does (pt_set_material_emission_texture)
     bool has_normal_maps = false;       // some material references a normal texture (pt_set_material_normal_texture): has_textures too, and tri_tan is written
     TexView tex_view() const { return TexView{tex_texels.data(), tex_table.data(), tri_uv.data()}; } // over the host copies
@@ -157,6 +157,7 @@ public:
     int set_material_texture(int material, int texture);             // -1 clears
     int set_material_emission_texture(int material, int texture);    // -1 clears; EMISSIVE materials only (the light sampler is rebuilt)
     int set_material_normal_texture(int material, int texture);      // -1 clears; any kind but EMISSIVE
+    int set_material_roughness_texture(int material, int texture);   // -1 clears; the two GGX kinds only
     int set_model_uvs(int model, const float* uv, uint32_t n_tris);  // nullptr, 0 clears
     int build(std::string* err);
     void set_camera(const float eye[3], const float target[3], float fov_deg, float aspect);

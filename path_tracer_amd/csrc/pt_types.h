@@ -82,7 +82,7 @@ struct alignas(16) DMaterial
     float vol_g;
     uint32_t texture;   // index + 1 into the texture table (TexView), 0 = none: the surface colour is `colour` itself
     uint32_t normal_texture; // index + 1 of the normal map (pt_set_material_normal_texture), 0 = none: the shading normal is the interpolated one
-    float pad;
+    uint32_t roughness_texture; // index + 1 of the roughness map (pt_set_material_roughness_texture), 0 = none: the GGX alpha is `alpha` itself
 };
 static_assert(sizeof(DMaterial) == 64, "");
 

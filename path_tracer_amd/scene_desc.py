@@ -69,21 +69,29 @@ class Material:
     texture: Optional[Texture] = None  # surface colour = colour * bilinear texel at the hit's UV (any kind but EMISSIVE); the oracle ignores it
     emission_texture: Optional[Texture] = None  # EMISSIVE only: emitted colour = colour * bilinear texel (pt_set_material_emission_texture); the oracle ignores it
     normal_texture: Optional[Texture] = None  # tangent-space normal map (pt_set_material_normal_texture; any kind but EMISSIVE); the oracle ignores it
+    roughness_texture: Optional[Texture] = None  # GGX kinds only: the hit's linear roughness = the bilinear texel's r (pt_set_material_roughness_texture); the oracle ignores it
 
     def textured(self, texture: Optional[Texture]) -> "Material":
         """this material with `texture` (None: without one)"""
         assert texture is None or self.kind != EMISSIVE
-        return Material(self.kind, self.colour, self.roughness, self.ior, self.volume, texture, self.emission_texture, self.normal_texture)
+        return Material(self.kind, self.colour, self.roughness, self.ior, self.volume, texture, self.emission_texture, self.normal_texture, self.roughness_texture)
 
     def normal_mapped(self, texture: Optional[Texture]) -> "Material":
         """this material with `texture` as its normal map (None: without one); composes with textured()"""
         assert texture is None or self.kind != EMISSIVE
-        return Material(self.kind, self.colour, self.roughness, self.ior, self.volume, self.texture, self.emission_texture, texture)
+        return Material(self.kind, self.colour, self.roughness, self.ior, self.volume, self.texture, self.emission_texture, texture, self.roughness_texture)
+
+    def roughness_mapped(self, texture: Optional[Texture]) -> "Material":
+        """this GGX material with `texture` as its roughness map (None: without one): the texel's first component is the hit's linear roughness
+        and `roughness` is not read; composes with textured() and normal_mapped()"""
+        if texture is not None and self.kind not in (GGX_METAL, GGX_DIELECTRIC):
+            raise ValueError("a roughness map needs a GGX material")
+        return Material(self.kind, self.colour, self.roughness, self.ior, self.volume, self.texture, self.emission_texture, self.normal_texture, texture)
 
     def emission_textured(self, texture: Optional[Texture]) -> "Material":
         """this EMISSIVE material with `texture` as its emission texture (None: without one)"""
         assert texture is None or self.kind == EMISSIVE
-        return Material(self.kind, self.colour, self.roughness, self.ior, self.volume, self.texture, texture, self.normal_texture)
+        return Material(self.kind, self.colour, self.roughness, self.ior, self.volume, self.texture, texture, self.normal_texture, self.roughness_texture)
 
 
 def _c3(v):

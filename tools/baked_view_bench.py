@@ -4,7 +4,7 @@ pt_render_baked(1 sample) at K = 0 and K = 2, beside pt_render_guides_followed a
 the 1-spp pt_frame.  Every figure is the median of --calls blocking calls, taken --reps times with the routes alternating, so that a drift
 of the shared machine touches all of them; the report keeps every repeat, the spread is theirs.
 
-    python tools/baked_view_bench.py [--calls 20] [--reps 3] [--what all|guides] [--probes [--depth R] [--radiance R]] [--directional] [--endings] [--out report.json]
+    python tools/baked_view_bench.py [--calls 20] [--reps 3] [--what all|guides] [--probes [--depth R] [--radiance R [--views-only] [--roughness-checker N]]] [--directional] [--endings] [--out report.json]
 
 --what guides times the guides call alone and runs on a tree that has no baked view: run it from the parent commit's tree and from this one,
 turn about, for the comparison across the two (the guide kernels themselves must not have moved).
@@ -23,6 +23,10 @@ every context of the run, a further context's grid carries a seeded R x R radian
 grid's alone; pt_bake_probe_radiance beside pt_bake_probes on 4 096 probes x 1 024 rays (the same integration, another fold);
 pt_probe_radiance_prefilter(on_device) of 4 096 probes x 5 levels at R = 8 and R = 16 (blocking calls: staging copies included; the
 profile quotes the kernel alone from a kernel trace beside them); and pt_probe_grid_specular(on_device) beside pt_probe_grid_lookup on 2^20 points.
+
+--probes --radiance R --views-only [--roughness-checker N] (profiles/r33_roughness_maps.md) keeps the pt_render_baked routes of that run alone, and
+with --roughness-checker adds a context whose two metal boxes carry an N x N roughness checker of 0.1 / 0.6 under planar UVs (a textured scene:
+pt_set_material_roughness_texture), its pt_render_baked beside the unmapped metal's: what reading the alpha at the hit costs the SPEC ending.
 
 --directional (profiles/r29_directional_lightmaps.md) times the DIR endings: every Lambertian material of the scene carries an 8 x 8 ripple
 normal map, every placement a 256 x 256 map; one context stops there (the scalar kernels), a second also sets a seeded gradient on every
@@ -76,6 +80,8 @@ def main():
     ap.add_argument("--probes", action="store_true")
     ap.add_argument("--depth", type=int, default=0)
     ap.add_argument("--radiance", type=int, default=0)
+    ap.add_argument("--views-only", action="store_true", help="with --probes: time the pt_render_baked routes alone")
+    ap.add_argument("--roughness-checker", type=int, default=0, help="with --probes --radiance: also the metal boxes under an N x N roughness checker")
     ap.add_argument("--directional", action="store_true")
     ap.add_argument("--endings", action="store_true")
     ap.add_argument("--out", default=None)
@@ -216,6 +222,20 @@ def probes(args, api, scenes):
         report.setdefault("lookup_ms", [])
         for k in HOPS:
             routes.append((report["baked_probes_radiance_ms"][str(k)], lambda k=k: view(spec, k), args.calls))
+        if args.roughness_checker:
+            import dataclasses
+            from path_tracer_amd.scene_desc import GGX_METAL, Texture
+            n = args.roughness_checker
+            ci, cj = np.meshgrid(np.arange(n), np.arange(n))
+            checker = Texture.new(np.repeat(np.where((ci + cj) & 1, np.float32(0.6), np.float32(0.1))[..., None], 3, axis=2))
+            mapped = SceneDesc.new([dataclasses.replace(m, material=m.material.roughness_mapped(checker), uvs=planar_uvs(m.positions))
+                                    if m.material.kind == GGX_METAL else m for m in sc.models], sc.camera, "cornell, roughness-mapped metal boxes")
+            rough = api.Renderer(mapped, W, H, max_bounces=DEPTH)
+            rough.set_probe_grid(lo + 0.5 * cell, cell, sh, normal_bias=0.01 * float(cell.min()))
+            rough.set_probe_grid_radiance(table, alphas)
+            report.update(roughness_checker=n, baked_probes_radiance_rough_ms={str(k): [] for k in HOPS})
+            for k in HOPS:
+                routes.append((report["baked_probes_radiance_rough_ms"][str(k)], lambda k=k: view(rough, k), args.calls))
         routes.append((report["bake_probes_1024_ms"], lambda: bare.bake_probes(pos, DEPTH_SAMPLES), 3))
         routes.append((report["bake_probe_radiance_ms"], lambda: bare.bake_probe_radiance(pos, DEPTH_SAMPLES, R), 3))
         for side in (8, 16):
@@ -223,6 +243,8 @@ def probes(args, api, scenes):
         if not args.depth:
             routes.append((report["lookup_ms"], lambda: lit.probe_grid_lookup(q, qn, on_device=True), 5))
         routes.append((report["lookup_specular_ms"], lambda: spec.probe_grid_specular(q, qn, qd, qa, on_device=True), 5))
+    if args.views_only:
+        routes = [rt for rt in routes if rt[2] == args.calls]
     for _, fn, _ in routes:
         fn()
     for _ in range(args.reps):

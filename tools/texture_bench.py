@@ -9,6 +9,12 @@ TEX shading variants (and of queueing the shadow rays the untextured frame walks
                                                                (profiles/r17_emission_textures.md): emit8_over_plain beside tex8_over_plain
     python tools/texture_bench.py --normal --reps 5            adds `nmap8`: the frame with its floor, ceiling and walls under an 8 x 8 ripple NORMAL map instead
                                                                of the checker, same UVs (profiles/r18_normal_maps.md): nmap8_over_plain, nmap8_over_tex8
+    python tools/texture_bench.py --roughness --reps 7         INSTEAD of the variants above (profiles/r33_roughness_maps.md): the texel-corner room of
+                                                               tests/textures_common.py and the `mixed` Cornell box, each without textures (`*_plain`),
+                                                               colour-textured (`*_tex`) and colour-textured with an 8 x 8 roughness checker of 0.1 / 0.6 on
+                                                               its GGX materials (`*_rough`); every frame's time is kept (`ms_all`), so that two builds'
+                                                               runs can be held against each other's spread.  A build without roughness maps measures
+                                                               the first two states
 """
 import argparse
 import json
@@ -79,6 +85,38 @@ def emission_cornell(scenes, W, H, n):
     return SceneDesc.new(models, scenes.reference_camera(W / H), f"cornell emission checker {n}")
 
 
+def roughness_checker(n):
+    i, j = np.meshgrid(np.arange(n), np.arange(n))
+    return np.repeat(np.where((i + j) & 1, np.float32(0.6), np.float32(0.1))[..., None], 3, axis=2)
+
+
+def roughness_variants(scenes, W, H, repeat):
+    """{name: make} of --roughness: the corner room and the mixed Cornell box in their two or three states"""
+    import dataclasses
+    from path_tracer_amd.scene_desc import GGX_DIELECTRIC, GGX_METAL, Material, SceneDesc, Texture
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    from textures_common import corner_scene
+    can = hasattr(Material, "roughness_mapped")
+    rough = Texture.new(roughness_checker(8))
+
+    def mapped(desc):
+        """the roughness checker on every GGX material; a model that has no UVs yet gets planar ones (the corner room's keep their one
+        corner, which the 8 x 8 map turns into one of its texels' corners: four different texels, blended)"""
+        models = []
+        for m in desc.models:
+            if m.material.kind in (GGX_METAL, GGX_DIELECTRIC):
+                m = dataclasses.replace(m, material=m.material.roughness_mapped(rough), uvs=m.uvs if m.uvs is not None else planar_uvs(m.positions, repeat))
+            models.append(m)
+        return SceneDesc.new(models, desc.camera, desc.name + " roughness")
+
+    v = {"corner_plain": lambda: corner_scene(W, H)[1], "corner_tex": lambda: corner_scene(W, H)[0],
+         "mixed_plain": lambda: scenes.cornell_mixed(W, H), "mixed_tex": lambda: scenes.checker_textured(scenes.cornell_mixed(W, H), repeat=repeat)}
+    if can:
+        v["corner_rough"] = lambda: mapped(corner_scene(W, H)[0])
+        v["mixed_rough"] = lambda: mapped(scenes.checker_textured(scenes.cornell_mixed(W, H), repeat=repeat))
+    return v
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--width", type=int, default=1920)
@@ -90,6 +128,7 @@ def main():
     ap.add_argument("--only", choices=["plain", "tex8", "tex1024", "emit8", "nmap8"])
     ap.add_argument("--normal", action="store_true", help="also measure nmap8: the walls under an 8 x 8 ripple normal map")
     ap.add_argument("--emission", action="store_true", help="also measure emit8: the light on an 8 x 8 checker emission texture")
+    ap.add_argument("--roughness", action="store_true", help="measure the corner room and the mixed box plain, textured and roughness-mapped instead")
     ap.add_argument("--out")
     a = ap.parse_args()
     from path_tracer_amd import api, scenes
@@ -102,6 +141,8 @@ def main():
         variants["nmap8"] = lambda: rippled_cornell(scenes, W, H, 8, a.repeat)
     if a.only:
         variants = {a.only: variants[a.only]}
+    if a.roughness:
+        variants = roughness_variants(scenes, W, H, a.repeat)
     rs = {}
     for name, make in variants.items():
         r = api.Renderer(make(), W, H, max_bounces=a.bounces)
@@ -121,7 +162,7 @@ def main():
     for name, r in rs.items():
         t = times[name]
         st = r.stats()
-        res["variants"][name] = dict(ms_per_frame=float(np.median(t)) if t else None, ms_min=min(t) if t else None, ms_max=max(t) if t else None,
+        res["variants"][name] = dict(ms_per_frame=float(np.median(t)) if t else None, ms_min=min(t) if t else None, ms_max=max(t) if t else None, ms_all=t,
                                      scene_bytes=int(r.scene_info().scene_bytes), rays_any=int(st.rays_any))
     if "plain" in rs and a.reps:
         for name in rs:
