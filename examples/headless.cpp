@@ -51,6 +51,9 @@
 //       most MAX samples per texel (0: no cap), until a round selects no texel; prints the rays spent and the mean count.  Every texel is
 //       divided by its own count before the means are dilated (or filtered with the counts, pt_lightmap_denoise_counts, then dilated), so
 //       map.txt holds means, and --baked-view sets them as they are
+//   examples/headless ... --bake-lightmap ... --direct [--adaptive REL MAX] [--lightmap-denoise] [--baked-view ...]   takes one light sample with a
+//       shadow ray at the texel beside every gather sample (pt_bake_lightmap_direct, pt_bake_lightmap_adaptive_direct; the light samples'
+//       streams follow the gather samples': light_key_base = W * H); everything after the bake is what it is without the option
 //   examples/headless ... --bake-lightmap ... --directional [--normal-ripples N] [--baked-view ...]   bakes the first moments beside the sums
 //       (pt_bake_lightmap_directional), takes their tangential gradient (pt_lightmap_gradient), dilates it plane by plane and, under --baked-view,
 //       sets it beside the map (pt_set_lightmap_directional): with --normal-ripples, which then lie under the bake's planar UVs (the floor and the
@@ -103,7 +106,7 @@ int main(int argc, char** argv)
     bool probe_depth_given = false;
     uint32_t probe_radiance = 0;           // --probe-radiance R
     bool probe_radiance_given = false, metal_box = false;
-    bool lightmap_denoise = false, directional = false, adaptive = false;
+    bool lightmap_denoise = false, directional = false, adaptive = false, direct = false;
     float adaptive_rel = 0.0f;
     uint32_t adaptive_max = 0;
     std::string baked_out = "";
@@ -182,6 +185,7 @@ int main(int argc, char** argv)
             baked_out = next("--baked-view");
         }
         else if (a == "--lightmap-denoise") lightmap_denoise = true;
+        else if (a == "--direct") direct = true;
         else if (a == "--directional") directional = true;
         else if (a == "--adaptive")
         {
@@ -198,7 +202,7 @@ int main(int argc, char** argv)
         }
         else if (a == "--help" || a == "-h")
         {
-            std::printf("usage: %s [--width W] [--height H] [--frames N] [--bounces B] [--move] [--slide DX DZ] [--models DIR] [--out file.png] [--temporal file.png [--temporal-rescue] [--temporal-mean-length] [--temporal-demodulate]] [--denoise file.png] [--denoise-albedo file.png] [--follow K] [--mirror-glass] [--aperture A --focus F] [--projection panorama[:SX:SY]|ortho:HEIGHT] [--bake-probes NX NY NZ SPP file.txt] [--bake-lightmap W H SPP PASSES file.txt [--adaptive REL MAX] [--lightmap-denoise | --directional] [--baked-view SPP file.png]] [--probe-grid NX NY NZ SPP [--probe-depth R] [--probe-radiance R] --baked-view SPP file.png] [--metal-box] [--checker N] [--emission-checker N] [--normal-ripples N] [--metal-box --roughness-checker N]\n", argv[0]);
+            std::printf("usage: %s [--width W] [--height H] [--frames N] [--bounces B] [--move] [--slide DX DZ] [--models DIR] [--out file.png] [--temporal file.png [--temporal-rescue] [--temporal-mean-length] [--temporal-demodulate]] [--denoise file.png] [--denoise-albedo file.png] [--follow K] [--mirror-glass] [--aperture A --focus F] [--projection panorama[:SX:SY]|ortho:HEIGHT] [--bake-probes NX NY NZ SPP file.txt] [--bake-lightmap W H SPP PASSES file.txt [--direct] [--adaptive REL MAX] [--lightmap-denoise | --directional] [--baked-view SPP file.png]] [--probe-grid NX NY NZ SPP [--probe-depth R] [--probe-radiance R] --baked-view SPP file.png] [--metal-box] [--checker N] [--emission-checker N] [--normal-ripples N] [--metal-box --roughness-checker N]\n", argv[0]);
             return 0;
         }
         else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
@@ -232,6 +236,11 @@ int main(int argc, char** argv)
     if (directional && (lightmap_out.empty() || !lightmap[2] || lightmap_denoise))
     {
         std::fprintf(stderr, "--directional bakes a direction beside the map --bake-lightmap bakes: it needs that option, and samples, and does not go with --lightmap-denoise\n");
+        return 2;
+    }
+    if (direct && (lightmap_out.empty() || !lightmap[2] || directional))
+    {
+        std::fprintf(stderr, "--direct samples the lights at the texels of the map --bake-lightmap bakes: it needs that option, and samples, and does not go with --directional\n");
         return 2;
     }
     if (adaptive && (lightmap_out.empty() || !lightmap[2] || directional || !(adaptive_rel >= 0.0f) || (adaptive_max != 0 && adaptive_max < 2) ||
@@ -401,6 +410,7 @@ int main(int argc, char** argv)
             if (lightmap_out.empty()) return true;
             std::vector<float> sums, grad;
             std::vector<uint8_t> cov;
+            const uint32_t light_keys = lightmap[0] * lightmap[1]; // --direct: the light samples' streams, behind the gather samples' [0, W * H)
             if (directional)
             {
                 // the first moments beside the sums, their gradient, and its dilation with a coverage of its own (the map's is dilated below)
@@ -420,7 +430,8 @@ int main(int argc, char** argv)
                 uint64_t rays = 0, rounds = 0;
                 for (uint32_t n = 1; n != 0; ++rounds)
                 {
-                    n = renderer.bake_lightmap_adaptive(1, 0, lightmap[0], lightmap[1], lightmap[2], crit, sums, sumsq, counts, &cov, 0, 0.25f);
+                    n = direct ? renderer.bake_lightmap_adaptive_direct(1, 0, lightmap[0], lightmap[1], lightmap[2], crit, sums, sumsq, counts, light_keys, &cov, 0, 0.25f)
+                               : renderer.bake_lightmap_adaptive(1, 0, lightmap[0], lightmap[1], lightmap[2], crit, sums, sumsq, counts, &cov, 0, 0.25f);
                     rays += (uint64_t)n * lightmap[2];
                 }
                 uint64_t covered = 0, total = 0;
@@ -433,9 +444,11 @@ int main(int argc, char** argv)
             {
                 // the moments steer the filter's luminance term; what it returns are texel means, and those are what is dilated, written and set
                 std::vector<float> sumsq;
-                cov = renderer.bake_lightmap_moments(1, 0, lightmap[0], lightmap[1], lightmap[2], sums, sumsq, 0, 0, 0.25f);
+                cov = direct ? renderer.bake_lightmap_direct(1, 0, lightmap[0], lightmap[1], lightmap[2], sums, &sumsq, light_keys, 0, 0, 0.25f)
+                             : renderer.bake_lightmap_moments(1, 0, lightmap[0], lightmap[1], lightmap[2], sums, sumsq, 0, 0, 0.25f);
                 sums = renderer.denoise_lightmap(1, 0, lightmap[0], lightmap[1], lightmap[2], sums, sumsq);
             }
+            else if (direct) cov = renderer.bake_lightmap_direct(1, 0, lightmap[0], lightmap[1], lightmap[2], sums, nullptr, light_keys, 0, 0, 0.25f);
             else cov = renderer.bake_lightmap(1, 0, lightmap[0], lightmap[1], lightmap[2], sums, 0, 0, 0.25f);
             renderer.dilate_lightmap(lightmap[0], lightmap[1], lightmap[3], sums, cov);
             std::FILE* f = std::fopen(lightmap_out.c_str(), "w");

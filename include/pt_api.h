@@ -944,8 +944,8 @@ int pt_probe_ray(pt_ctx* ctx, uint32_t key, uint32_t sample, float d[3], float y
  * PT_ERR_ARG for a bad model or instance index, w or h of 0, n_samples == 0, a bias that is not finite, a NULL p or rgb_sum, a non-zero
  * reserved word, key_base + w * h or first_sample + n_samples beyond 2^32; PT_ERR_LIMIT for a side above 16384 or more than 2^26 texels.
  * A map with no covered texel is PT_OK and integrates nothing.
- * Out of scope: unwrapping and atlas packing, conservative or supersampled coverage, direct light sampled at the texel, pt_multi_* variants.
- * (Denoising a map: pt_bake_lightmap_moments and pt_lightmap_denoise; showing one: pt_set_lightmap and pt_render_baked; a direction beside
+ * Out of scope: unwrapping and atlas packing, conservative or supersampled coverage, pt_multi_* variants.
+ * (Direct light sampled at the texel: pt_bake_lightmap_direct.  Denoising a map: pt_bake_lightmap_moments and pt_lightmap_denoise; showing one: pt_set_lightmap and pt_render_baked; a direction beside
  * the irradiance, for normal-mapped surfaces: pt_bake_lightmap_directional; all below.) */
 typedef struct pt_lightmap_params
 {
@@ -1063,6 +1063,67 @@ int pt_lightmap_adaptive_mask(pt_ctx* ctx, int on_device, int model, uint32_t in
  * p->n_samples != 0 and for a covered texel whose count is 0 (the filter would silently treat it as invalid) or above 2^24. */
 int pt_lightmap_denoise_counts(pt_ctx* ctx, int on_device, const pt_lightmap_denoise_params* p, const float* rgb_sum, const float* sumsq,
                                const uint32_t* counts, float* rgb_mean, float* texel_area);
+
+/* ---- lightmap bakes with direct light sampled at the texel ----------------------------------------------------------------------------- */
+/* pt_bake_lightmap estimates the direct term the expensive way: a texel sees a lamp only when a gather ray happens to hit it (a gather ray is
+ * a camera ray to the integrator, so it takes the lamp's full emission with no next-event estimate).  pt_bake_lightmap_direct is the bake
+ * whose sample is X = G + D: G the gather radiance, set to zero when the gather ray's FIRST HIT is a lamp (that case is exactly the direct
+ * term), and D one light sample taken at the texel, with a shadow ray.  Coverage, the texel table, o = P + bias * n and the gather ray of
+ * (key_base + k, s) - pt_lightmap_ray, draws_consumed = 1 - are pt_bake_lightmap's.  All arithmetic is binary32, one rounding per operation,
+ * no contraction.
+ * THE LIGHT SAMPLE of sample s of texel k, with o and n from the texel table (n not renormalised), is estimate_direct_explicit
+ * (integrator.rs:25-74) for a Lambertian surface of colour 1 with the MIS weight replaced by 1, in the same operation order:
+ *     x, lu, lv = draws 0, 1, 2 of the stream (light_key_base + k, s) under the context's seed (none consumed before)
+ *     i  = number of entries of pt_light_cdf's cdf whose total-order key is below x's, clamped to n_lights - 1
+ *     if (lu + lv > 1) { lu = 1 - lu; lv = 1 - lv; }   lw = 1 - lu - lv
+ *     A, B, C / NA, NB, NC = the light triangle's positions and shading normals exactly as the shading pass reads them (pt_triangle_dump) -
+ *                            object space, the reference's own convention for lights
+ *     point = (A * lw + B * lu) + C * lv;   ln = unit3((NA * lw + NB * lu) + NC * lv)
+ *     w = point - o;  dist2 = len_sq(w);  dist = sqrt(dist2);  dir = unit3(w)
+ *     c = dot3(dir, n);   if !(c > 0): D = 0, no shadow ray, light = i still reported
+ *     sample_pdf = pdf_i / (0.5f * len3(n0))            -- n0: the triangle's unnormalised geometric normal (out36[0..2] of pt_triangle_dump)
+ *     cosl = fabsf(dot3(dir, ln));   light_pdf = sample_pdf * (dist2 / cosl)
+ *     emitted = the light material's colour; under an emission texture the surface colour of the triangle at (lu, lv)
+ *     ce = finalise(((emitted * fabsf(c)) * 0.31830987f) / light_pdf)      -- finite check, length clamp 100, as every sample
+ *     shadow ray (o, dir, t_max = (1 - 5e-4f) * dist): TLAS::any_intersect over the world, i.e. pt_trace_any(which = 0)
+ *     D = blocked ? 0 : ce
+ * THE FOLD, per channel, s ascending:
+ *     G = the gather ray's radiance, as pt_bake_lightmap takes it;  G = 0 when that ray's first hit is on an emissive model
+ *     X = G + D;   sum[k][c] = sum[k][c] + X[c];   with sumsq: Q[k] = Q[k] + l(X) * l(X)
+ * "First hit on an emissive model" is what the integrator already returns: the id byte of pt_integrate_rays, the model index's low byte, 255
+ * for a miss.  One byte per ray is all the path state keeps, hence PT_ERR_LIMIT when an emissive model shares its low byte with a
+ * non-emissive one, or has low byte 255.
+ *   - pi * sum / n is still the irradiance: pt_set_lightmap, pt_lightmap_denoise*, pt_lightmap_dilate and the baked view take these maps unchanged.
+ *   - bake(0, a) followed by bake(a, b) is bake(0, a + b), bit for bit, in both arrays.
+ *   - A texel's result depends only on the scene, the config, its triangle and (key_base, light_key_base, s, bias): not on the batch cut, the
+ *     table cut, the texel order or where the BVH lives.
+ *   - pt_bake_lightmap_adaptive_direct is pt_bake_lightmap_adaptive over these samples, its contract word for word: after any sequence of
+ *     rounds a covered texel holds what pt_bake_lightmap_direct with sumsq gives it at first_sample = 0, n_samples = counts[k].  The
+ *     selection is the same.
+ *   - The caller keeps [light_key_base, light_key_base + w * h) disjoint from [key_base, key_base + w * h): otherwise the texel's light point
+ *     repeats the choice its gather path makes at its first hit (unbiased still, but correlated).
+ * The existing entry points, their launches and their bits do not change; a context that never calls these allocates and launches nothing new.
+ * The shadow rays go through pt_trace_any's launch, a window at a time; pt_stats.paths grows by covered * n_samples as pt_bake_lightmap's.
+ * Errors, all before any device call (a refused call changes nothing), in this order: everything pt_bake_lightmap_moments refuses
+ * (pt_bake_lightmap with a NULL sumsq; pt_bake_lightmap_adaptive for the adaptive call); PT_ERR_ARG for a NULL dp, a non-zero dp->reserved,
+ * light_key_base + w * h beyond 2^32; PT_ERR_STATE for a scene without an emissive model, whatever enable_nee is; PT_ERR_STATE for a scene
+ * with participating media (G = 0 is exact only on an empty volume stack); the PT_ERR_LIMIT above.
+ * Out of scope: MIS between the texel's light sample and its gather ray, more than one light sample per gather sample, directional bakes,
+ * pt_multi_* variants, sampling the environment map at the texel. */
+typedef struct pt_lightmap_direct
+{
+    uint32_t light_key_base;   /* texel k's light samples draw from the stream of pixel light_key_base + k */
+    uint32_t reserved[3];      /* must be 0 */
+} pt_lightmap_direct;
+int pt_bake_lightmap_direct(pt_ctx* ctx, const pt_lightmap_params* p, const pt_lightmap_direct* dp, float* rgb_sum,
+                            float* sumsq /* may be NULL: no moments */, uint8_t* coverage /* may be NULL */);
+int pt_bake_lightmap_adaptive_direct(pt_ctx* ctx, const pt_lightmap_params* p, const pt_lightmap_direct* dp, const pt_adaptive* crit, float* rgb_sum,
+                                     float* sumsq, uint32_t* counts, uint8_t* coverage /* may be NULL */, uint32_t* n_active /* may be NULL */);
+/* the light sample alone, the unit hook of the above, for n caller-given (key = light_key_base + k, sample, o, n); outputs (any may be NULL):
+ * light = i, dir_xyz, t_max, and ce_rgb BEFORE the shadow ray (zeros where none is cast).  on_device = 0 evaluates on the host and touches no
+ * GPU; on_device = 1 runs the bake's own per-sample function in a kernel.  PT_ERR_STATE for a scene without an emissive model. */
+int pt_lightmap_light_sample(pt_ctx* ctx, int on_device, uint32_t n, const uint32_t* key, const uint32_t* sample, const float* origin_xyz,
+                             const float* normal_xyz, uint32_t* light, float* dir_xyz, float* t_max, float* ce_rgb);
 
 /* ---- lightmaps kept by the context, and the baked view: followed first hits shaded from them ------------------------------------------- */
 /* pt_set_lightmap gives the context the finished map of ONE placement, (model, instance) as pt_bake_lightmap keys it: rgb is w * h * 3 floats,

@@ -480,6 +480,46 @@ public:
         check(pt_bake_lightmap_adaptive(ctx_, &p, &crit, rgb_sum.data(), sumsq.data(), counts.data(), coverage ? coverage->data() : nullptr, &n));
         return n;
     }
+    // bake_lightmap with direct light sampled at the texel (pt_bake_lightmap_direct): a sample is the gather radiance, zero when the gather
+    // ray's first hit is a lamp, plus one light sample with a shadow ray.  sumsq null: no moments; otherwise as bake_lightmap_moments'.  The
+    // light samples draw from the streams of pixels light_key_base + texel: keep them apart from [key_base, key_base + w * h)
+    std::vector<uint8_t> bake_lightmap_direct(int model, uint32_t instance, uint32_t w, uint32_t h, uint32_t n_samples, std::vector<float>& rgb_sum,
+                                              std::vector<float>* sumsq, uint32_t light_key_base, uint32_t first_sample = 0, uint32_t key_base = 0, float bias = 0.0f)
+    {
+        const size_t px = (size_t)w * h;
+        if (rgb_sum.empty()) rgb_sum.assign(px * 3, 0.0f);
+        if (sumsq && sumsq->empty()) sumsq->assign(px, 0.0f);
+        if (rgb_sum.size() != px * 3 || (sumsq && sumsq->size() != px)) throw Error(PT_ERR_ARG, "bake_lightmap_direct: rgb_sum holds 3 values per texel and sumsq one");
+        std::vector<uint8_t> coverage(px);
+        pt_lightmap_params p{};
+        p.model = model; p.instance = instance; p.w = w; p.h = h;
+        p.first_sample = first_sample; p.n_samples = n_samples; p.key_base = key_base; p.bias = bias;
+        pt_lightmap_direct dp{};
+        dp.light_key_base = light_key_base;
+        check(pt_bake_lightmap_direct(ctx_, &p, &dp, rgb_sum.data(), sumsq ? sumsq->data() : nullptr, coverage.data()));
+        return coverage;
+    }
+    // one round of bake_lightmap_adaptive over bake_lightmap_direct's samples (pt_bake_lightmap_adaptive_direct)
+    uint32_t bake_lightmap_adaptive_direct(int model, uint32_t instance, uint32_t w, uint32_t h, uint32_t n_samples, const pt_adaptive& crit, std::vector<float>& rgb_sum,
+                                           std::vector<float>& sumsq, std::vector<uint32_t>& counts, uint32_t light_key_base, std::vector<uint8_t>* coverage = nullptr,
+                                           uint32_t key_base = 0, float bias = 0.0f)
+    {
+        const size_t px = (size_t)w * h;
+        if (rgb_sum.empty()) rgb_sum.assign(px * 3, 0.0f);
+        if (sumsq.empty()) sumsq.assign(px, 0.0f);
+        if (counts.empty()) counts.assign(px, 0u);
+        if (rgb_sum.size() != px * 3 || sumsq.size() != px || counts.size() != px)
+            throw Error(PT_ERR_ARG, "bake_lightmap_adaptive_direct: rgb_sum holds 3 values per texel, sumsq and counts one");
+        if (coverage) coverage->assign(px, 0);
+        pt_lightmap_params p{};
+        p.model = model; p.instance = instance; p.w = w; p.h = h;
+        p.n_samples = n_samples; p.key_base = key_base; p.bias = bias;
+        pt_lightmap_direct dp{};
+        dp.light_key_base = light_key_base;
+        uint32_t n = 0;
+        check(pt_bake_lightmap_adaptive_direct(ctx_, &p, &dp, &crit, rgb_sum.data(), sumsq.data(), counts.data(), coverage ? coverage->data() : nullptr, &n));
+        return n;
+    }
     // the selection alone (pt_lightmap_adaptive_mask): 1 per texel that bake_lightmap_adaptive would give samples
     std::vector<uint8_t> lightmap_adaptive_mask(int model, uint32_t instance, uint32_t w, uint32_t h, const pt_adaptive& crit, const std::vector<float>& rgb_sum,
                                                 const std::vector<float>& sumsq, const std::vector<uint32_t>& counts, bool on_device = false) const

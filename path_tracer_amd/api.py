@@ -57,6 +57,7 @@ EXPORTS = [
     "pt_probe_grid_specular",
     "pt_bake_lightmap_directional", "pt_lightmap_gradient", "pt_set_lightmap_directional", "pt_get_lightmap_directional_info", "pt_lightmap_lookup_directional",
     "pt_bake_lightmap_adaptive", "pt_lightmap_adaptive_mask", "pt_lightmap_denoise_counts",
+    "pt_bake_lightmap_direct", "pt_bake_lightmap_adaptive_direct", "pt_lightmap_light_sample",
 ]
 
 
@@ -180,6 +181,11 @@ class LightmapParams(C.Structure):
     """pt_lightmap_params: the placement, size, sample range, stream keys and ray bias of a lightmap bake (include/pt_api.h)"""
     _fields_ = [("model", C.c_int32), ("instance", C.c_uint32), ("w", C.c_uint32), ("h", C.c_uint32), ("first_sample", C.c_uint32),
                 ("n_samples", C.c_uint32), ("key_base", C.c_uint32), ("bias", C.c_float), ("reserved", C.c_uint32 * 4)]
+
+
+class LightmapDirect(C.Structure):
+    """pt_lightmap_direct: the stream keys of a direct bake's light samples (include/pt_api.h)"""
+    _fields_ = [("light_key_base", C.c_uint32), ("reserved", C.c_uint32 * 3)]
 
 
 class LightmapDenoiseParams(C.Structure):
@@ -345,6 +351,9 @@ def lib():
         L.pt_bake_lightmap_adaptive.argtypes = [vp, C.POINTER(LightmapParams), C.POINTER(Adaptive), vp, vp, vp, vp, C.POINTER(u32)]
         L.pt_lightmap_adaptive_mask.argtypes = [vp, C.c_int, C.c_int, u32, u32, u32, C.POINTER(Adaptive), vp, vp, vp, vp, C.POINTER(u32)]
         L.pt_lightmap_denoise_counts.argtypes = [vp, C.c_int, C.POINTER(LightmapDenoiseParams), vp, vp, vp, vp, vp]
+        L.pt_bake_lightmap_direct.argtypes = [vp, C.POINTER(LightmapParams), C.POINTER(LightmapDirect), vp, vp, vp]
+        L.pt_bake_lightmap_adaptive_direct.argtypes = [vp, C.POINTER(LightmapParams), C.POINTER(LightmapDirect), C.POINTER(Adaptive), vp, vp, vp, vp, C.POINTER(u32)]
+        L.pt_lightmap_light_sample.argtypes = [vp, C.c_int, u32, vp, vp, vp, vp, vp, vp, vp, vp]
         L.pt_set_lightmap.argtypes = [vp, C.c_int, u32, u32, u32, vp]
         L.pt_get_lightmap_info.argtypes = [vp, C.c_int, u32, vp, vp]
         L.pt_lightmap_lookup.argtypes = [vp, C.c_int, u32, vp, vp, vp, vp, vp, vp]
@@ -1204,6 +1213,50 @@ class Renderer:
         self._chk(self.L.pt_lightmap_adaptive_mask(self.ctx, int(bool(on_device)), model, instance, w, h, C.byref(crit), _p(a), _p(sq), _p(cn), _p(mask), C.byref(n)))
         assert int(mask.sum()) == n.value
         return mask.astype(bool)
+
+    # ---- direct light sampled at the texel
+    def bake_lightmap_direct(self, model, instance, w, h, n_samples, first_sample=0, key_base=0, bias=0.0, sums=None, sumsq=None, light_key_base=None,
+                             moments=False):
+        """bake_lightmap whose sample is X = G + D (pt_bake_lightmap_direct): the gather radiance, zero when the gather ray's first hit is a
+        lamp, plus one light sample taken at the texel with a shadow ray.  light_key_base (None: key_base + w * h) keys the light samples'
+        streams.  Returns (sums (h, w, 3), coverage (h, w) uint8) as bake_lightmap does; with sumsq given (or moments=True, from zero) the
+        second moments are folded too and (sums, sumsq (h, w), coverage) come back, as bake_lightmap_moments"""
+        out = np.zeros((h, w, 3), np.float32) if sums is None else np.ascontiguousarray(sums, np.float32)
+        with_sq = moments or sumsq is not None
+        sq = None if not with_sq else np.zeros((h, w), np.float32) if sumsq is None else np.ascontiguousarray(sumsq, np.float32)
+        if out.size != w * h * 3 or (sq is not None and sq.size != w * h):
+            raise PtError(-1, "bake_lightmap_direct: sums holds 3 values per texel and sumsq one")
+        cov = np.zeros((h, w), np.uint8)
+        prm = LightmapParams(model, instance, w, h, first_sample, n_samples, key_base, bias)
+        dp = LightmapDirect(key_base + w * h if light_key_base is None else light_key_base)
+        self._chk(self.L.pt_bake_lightmap_direct(self.ctx, C.byref(prm), C.byref(dp), _p(out), _p(sq), _p(cov)))
+        return (out.reshape(h, w, 3), sq.reshape(h, w), cov) if with_sq else (out.reshape(h, w, 3), cov)
+
+    def bake_lightmap_adaptive_direct(self, model, instance, w, h, n_samples, rel_error, abs_floor=0.0, min_samples=2, max_samples=0, key_base=0, bias=0.0,
+                                      sums=None, sumsq=None, counts=None, light_key_base=None):
+        """One round of bake_lightmap_adaptive over bake_lightmap_direct's samples (pt_bake_lightmap_adaptive_direct); arguments and the five
+        return values as bake_lightmap_adaptive, light_key_base as bake_lightmap_direct"""
+        out, sq, cn = self._lightmap_state("bake_lightmap_adaptive_direct", w, h, sums, sumsq, counts, copy=True)
+        cov = np.zeros((h, w), np.uint8)
+        n = C.c_uint32(0)
+        prm = LightmapParams(model, instance, w, h, 0, n_samples, key_base, bias)
+        dp = LightmapDirect(key_base + w * h if light_key_base is None else light_key_base)
+        crit = self._adaptive(rel_error, abs_floor, min_samples, max_samples)
+        self._chk(self.L.pt_bake_lightmap_adaptive_direct(self.ctx, C.byref(prm), C.byref(dp), C.byref(crit), _p(out), _p(sq), _p(cn), _p(cov), C.byref(n)))
+        return out, sq, cn, cov, n.value
+
+    def lightmap_light_sample(self, key, sample, origin, normal, on_device=False):
+        """unit hook: the light sample bake_lightmap_direct takes for (key = light_key_base + texel, sample) at `origin` under `normal`
+        (pt_lightmap_light_sample): (light (n,) uint32, dir (n, 3), t_max (n,), ce (n, 3) before the shadow ray); on the host (no GPU)
+        unless on_device"""
+        key = np.ascontiguousarray(key, np.uint32).reshape(-1); smp = np.ascontiguousarray(sample, np.uint32).reshape(-1)
+        n = key.size
+        o = np.ascontiguousarray(origin, np.float32).reshape(n, 3); nr = np.ascontiguousarray(normal, np.float32).reshape(n, 3)
+        if smp.size != n:
+            raise PtError(-1, "lightmap_light_sample: key and sample have one entry per sample")
+        light = np.zeros(n, np.uint32); d = np.zeros((n, 3), np.float32); t = np.zeros(n, np.float32); ce = np.zeros((n, 3), np.float32)
+        self._chk(self.L.pt_lightmap_light_sample(self.ctx, int(bool(on_device)), n, _p(key), _p(smp), _p(o), _p(nr), _p(light), _p(d), _p(t), _p(ce)))
+        return light, d, t, ce
 
     # ---- lightmaps kept by the context, and the baked view
     def set_lightmap(self, model, instance, rgb):

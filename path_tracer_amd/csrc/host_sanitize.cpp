@@ -27,6 +27,11 @@
 //                                      lm_gradient (pt_lightmap.h) from random first-moment sums, denormal ones and zero normals among them, in tables
 //                                      that fill their allocation exactly; then lightmap_lookup_directional (pt_materials.h) under shading_normal_delta
 //                                      at random hits; prints the lookups and a checksum (nonzero exit for a negative or NaN result)
+//   host_sanitize lightmap_direct <n> <seed> direct light sampled at the texel: lm_light_sample (pt_lightmap.h, the function the kernels run) and the host
+//                                      fold of X = G + D over n random texels and four designed ones, against light tables that fill their
+//                                      allocations exactly: a light point exactly at o, cosl == 0, a zero-area light triangle (weight 0 when n is
+//                                      odd), a cdf that ends below 1 so that a draw lands past the last entry, and x == 1.0; no index leaves its
+//                                      table and no D is negative, a NaN or longer than 100 (nonzero exit otherwise); prints counts and a checksum
 //   host_sanitize texelfilter <n> <seed> the texel filter's host side (pt_lightmap_filter.h, the functions the kernels run): n random triangles with the
 //                                      same hostile UVs, their texel tables on maps from 1 x 1 up, sides that are no multiple of 16 among them, random
 //                                      positive sums, then the whole filter with 8 levels (step 128 exceeds every map), with and without second
@@ -541,6 +546,109 @@ int main(int argc, char** argv)
             ++mapped;
         }
         std::printf("{\"triangles\": %u, \"lookups\": %u, \"moved\": %u, \"checksum\": %.6f}\n", n, mapped, moved, acc);
+        return 0;
+    }
+    if (cmd == "lightmap_direct" && argc >= 4)
+    {
+        const uint32_t n = (uint32_t)std::atoi(argv[2]);
+        uint64_t s = 0x9E3779B97F4A7C15ull ^ (uint64_t)std::atoll(argv[3]);
+        auto rnd = [&]() { s ^= s << 13; s ^= s >> 7; s ^= s << 17; return (float)((s >> 40) & 0xffff) / 65535.0f; };
+        if (n == 0) return 3;
+        // the light tables written out by hand, each filling its allocation exactly: random triangles, then three designed ones.  Z: zero
+        // area with all vertices at one point (a light point exactly at o when o is that point); P: in the plane z = 0 with normals along
+        // z (cosl == 0 exactly for an origin in that plane); the cdf stops at 0.75, so a draw above it runs off the table's end and is
+        // clamped to the last entry, which is the ordinary triangle T
+        const uint32_t n_random = 1u + n % 7u, n_lights = n_random + 3u, Z = n_random, P = n_random + 1u;
+        std::vector<DLight> lights(n_lights);
+        std::vector<DTriVerts> pos(n_lights), shade(n_lights);
+        std::vector<DTriIsect> isect(n_lights);
+        std::vector<DTriUV> uvs(n_lights);
+        std::vector<DMaterial> mats(2);
+        std::memset(mats.data(), 0, 2 * sizeof(DMaterial));
+        for (uint32_t m = 0; m < 2u; ++m)
+        {
+            mats[m].kind = MAT_EMISSIVE;
+            mats[m].colour[0] = 5.0f + m; mats[m].colour[1] = 4.0f; mats[m].colour[2] = 3.0f;
+        }
+        mats[1].texture = 1u;
+        std::vector<DTexture> table{DTexture{0u, 5u, 3u, 0u}};
+        std::vector<f4> texels(15);
+        for (f4& t : texels) t = f4{4.0f * rnd(), 4.0f * rnd(), 4.0f * rnd(), 0.0f};
+        const f3 zp{3.0f, -2.0f, 1.5f};
+        float run = 0.0f;
+        for (uint32_t i = 0; i < n_lights; ++i)
+        {
+            f3 a{20.0f * rnd() - 10.0f, 20.0f * rnd() - 10.0f, 5.0f + 5.0f * rnd()};
+            f3 b = a + f3{2.0f * rnd() + 0.1f, rnd() - 0.5f, rnd() - 0.5f}, c = a + f3{rnd() - 0.5f, 2.0f * rnd() + 0.1f, rnd() - 0.5f};
+            f3 nn = unit3(cross3(b - a, c - a));
+            if (i == Z) { a = b = c = zp; nn = f3{0.0f, 0.0f, 1.0f}; }
+            if (i == P) { a = f3{1.0f, 0.0f, 0.0f}; b = f3{2.0f, 0.0f, 0.0f}; c = f3{1.0f, 1.0f, 0.0f}; nn = f3{0.0f, 0.0f, 1.0f}; }
+            pos[i] = DTriVerts{f4{a.x, a.y, a.z, 0.0f}, f4{b.x, b.y, b.z, 0.0f}, f4{c.x, c.y, c.z, 0.0f}};
+            shade[i] = DTriVerts{f4{nn.x, nn.y, nn.z, 0.0f}, f4{nn.x, nn.y, nn.z, 0.0f}, f4{nn.x, nn.y, nn.z, 0.0f}};
+            const f3 n0 = cross3(b - a, c - a);
+            isect[i] = DTriIsect{f4{n0.x, n0.y, n0.z, 0.0f}, f4{0.0f, 0.0f, 0.0f, 0.0f}, f4{0.0f, 0.0f, 0.0f, 0.0f}};
+            uvs[i] = DTriUV{{40.0f * rnd() - 20.0f, rnd()}, {rnd(), 1.0e6f * rnd()}, {-rnd(), rnd()}};
+            const float pdf = i == Z && (n & 1u) ? 0.0f : 0.75f / (float)n_lights; // (a zero-area triangle's weight is 0: 0 / 0 as well as x / 0)
+            run += pdf;
+            lights[i] = DLight{i, i & 1u, pdf, run};
+        }
+        const LmLightView lv{lights.data(), pos.data(), shade.data(), isect.data(), mats.data(), n_lights, TexView{texels.data(), table.data(), uvs.data()}};
+        const uint64_t seed = 0x5EED5EEDull;
+        // the samples: random texels, then the designed ones.  Key 480975 is a stream whose draw 0 is exactly 1.0 under this seed
+        const uint32_t n_texels = n + 4u, total = 4u * n + 4u * 64u; // four samples of a random texel, 64 of a designed one
+        std::vector<uint32_t> key(n_texels);
+        std::vector<f3> org(n_texels), nrm(n_texels);
+        for (uint32_t k = 0; k < n_texels; ++k)
+        {
+            key[k] = (uint32_t)(rnd() * 65535.0f) * 65536u + (uint32_t)(rnd() * 65535.0f);
+            org[k] = f3{10.0f * rnd() - 5.0f, 10.0f * rnd() - 5.0f, rnd()};
+            nrm[k] = f3{0.4f * rnd() - 0.2f, 0.4f * rnd() - 0.2f, 1.0f};
+        }
+        org[n] = zp;                                   // every sample that picks Z has its light point exactly at o
+        org[n + 1u] = f3{0.0f, 0.25f, 0.0f}; nrm[n + 1u] = f3{1.0f, 0.0f, 0.0f};  // in P's plane, facing it: cosl == 0, light_pdf = +inf
+        key[n + 2u] = 480975u;                         // x == 1.0 at sample 0
+        nrm[n + 3u] = f3{0.0f, 0.0f, 0.0f};            // c == 0: nothing is cast
+        {
+            Stream probe{stream_key(seed, 480975u, 0u), 0u};
+            if (probe.f32() != 1.0f) return 7;
+        }
+        std::vector<uint8_t> emissive(256, 0);
+        emissive[1] = 1;
+        std::vector<float> sum(3 * (size_t)n_texels, 0.0f), sumsq(n_texels, 0.0f);
+        uint32_t picked[4] = {0, 0, 0, 0}, cast = 0, at_o = 0, grazing = 0, last = 0;
+        double acc = 0.0;
+        for (uint32_t k = 0; k < n_texels; ++k)
+            for (uint32_t sm = 0; sm < (k < n ? 4u : 64u); ++sm)
+            {
+                const LmLightSample ls = lm_light_sample(lv, seed, key[k], sm, org[k], nrm[k]);
+                if (ls.light >= n_lights) return 8;
+                if (!(ls.ce.x >= 0.0f && ls.ce.y >= 0.0f && ls.ce.z >= 0.0f)) return 6;                 // never negative, never a NaN
+                if (!(std::sqrt((double)ls.ce.x * ls.ce.x + (double)ls.ce.y * ls.ce.y + (double)ls.ce.z * ls.ce.z) <= 100.0 * (1.0 + 1e-6))) return 9;
+                if (!ls.cast && (ls.ce.x != 0.0f || ls.ce.y != 0.0f || ls.ce.z != 0.0f)) return 10;
+                picked[ls.light == Z ? 0 : ls.light == P ? 1 : ls.light == n_lights - 1u ? 2 : 3] += 1u;
+                cast += ls.cast ? 1u : 0u;
+                at_o += (k == n && ls.light == Z) ? 1u : 0u;
+                grazing += (k == n + 1u && ls.light == P && ls.cast) ? 1u : 0u;
+                last += (k == n + 2u && sm == 0u && ls.light == n_lights - 1u) ? 1u : 0u;
+                // the host fold: X = G + D under a random gather radiance, id byte and shadow-ray result
+                const uint8_t id = (uint8_t)(rnd() * 2.999f);
+                const bool blocked = rnd() < 0.3f;
+                const float g[3] = {rnd(), rnd(), rnd()}, ce[3] = {ls.ce.x, ls.ce.y, ls.ce.z};
+                f4 x{0.0f, 0.0f, 0.0f, 0.0f};
+                float* xs = &x.x;
+                for (int c = 0; c < 3; ++c)
+                {
+                    xs[c] = lm_direct_x(g[c], emissive[id] != 0, ce[c], blocked);
+                    sum[3 * (size_t)k + c] = sum[3 * (size_t)k + c] + xs[c];
+                }
+                const float l = lum(x);
+                sumsq[k] = sumsq[k] + l * l;
+                if (!(l >= 0.0f) || !std::isfinite(l)) return 11;
+            }
+        for (uint32_t k = 0; k < n_texels; ++k) acc += sum[3 * (size_t)k] + 2.0 * sum[3 * (size_t)k + 1] + 3.0 * sum[3 * (size_t)k + 2] + sumsq[k];
+        if (last != 1u) return 12;
+        std::printf("{\"texels\": %u, \"lights\": %u, \"samples\": %u, \"cast\": %u, \"zero_area\": %u, \"at_origin\": %u, \"grazing\": %u, \"last_entry\": %u, \"checksum\": %.6f}\n",
+                    n_texels, n_lights, total, cast, picked[0], at_o, grazing, picked[2], acc);
         return 0;
     }
     if (cmd == "texelfilter" && argc >= 4)

@@ -13,6 +13,7 @@
 #include <cstring>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -1503,25 +1504,39 @@ int integrate_rays_device(pt_ctx* c, uint64_t n, const float* o, const float* d,
 // `chunk` rays at a time, in buffers of `st`: filled on the device (fill), integrated (in wavefront batches of their own), folded in sample
 // order (fold).  pt_config.batch_spp, a render's test knob, cuts here as well: wavefront batches of batch_spp * n_items rays, and three of
 // them per table (2^26 rays at the most), so that an item's samples straddle both.  Results do not depend on either cut.
-template <class Fill, class Fold>
-int bake_rays(pt_ctx* c, Staging& st, uint32_t n_items, uint32_t n_samples, Fill&& fill, Fold&& fold)
+// bake_chunk: the rays the table holds at a time, and the wavefront batch's cut (0: the planner's)
+uint32_t bake_chunk(const pt_ctx* c, uint32_t n_items, uint32_t n_samples, uint32_t* batch_rays)
 {
     const uint64_t total = (uint64_t)n_items * n_samples;
     const uint64_t cut = (uint64_t)c->cfg.batch_spp * n_items;
-    const uint32_t batch_rays = (uint32_t)std::min<uint64_t>(cut, (1ull << 29) - 1);
-    const uint32_t chunk = (uint32_t)std::min<uint64_t>(total, batch_rays ? std::min<uint64_t>(3ull * batch_rays, 1ull << 26) : (1ull << 26));
+    *batch_rays = (uint32_t)std::min<uint64_t>(cut, (1ull << 29) - 1);
+    return (uint32_t)std::min<uint64_t>(total, *batch_rays ? std::min<uint64_t>(3ull * *batch_rays, 1ull << 26) : (1ull << 26));
+}
+// with_id (pt_bake_lightmap_direct): the window's first-hit id bytes are kept as well, and fold takes them as a fifth argument; it is then the
+// place for whatever else the window needs between its integration and its fold
+template <class Fill, class Fold>
+int bake_rays(pt_ctx* c, Staging& st, uint32_t n_items, uint32_t n_samples, Fill&& fill, Fold&& fold, bool with_id = false)
+{
+    const uint64_t total = (uint64_t)n_items * n_samples;
+    uint32_t batch_rays;
+    const uint32_t chunk = bake_chunk(c, n_items, n_samples, &batch_rays);
     float* d_o = st.out<float>(3 * (size_t)chunk);
     float* d_d = st.out<float>(3 * (size_t)chunk);
     uint2* d_key = st.out<uint2>(chunk);
     f4* d_rad = st.out<f4>(chunk);
+    uint8_t* d_id = with_id ? st.out<uint8_t>(chunk) : nullptr;
     if (st.err) return st.err;
     int r;
     for (uint64_t first = 0; first < total; first += chunk)
     {
         const uint32_t cnt = (uint32_t)std::min<uint64_t>(chunk, total - first);
         fill(first, cnt, d_o, d_d, d_key);
-        if ((r = integrate_rays_device(c, cnt, d_o, d_d, d_key, 1u, batch_rays, d_rad, nullptr, nullptr))) return r;
-        fold(first, cnt, d_d, d_rad);
+        if ((r = integrate_rays_device(c, cnt, d_o, d_d, d_key, 1u, batch_rays, d_rad, nullptr, d_id))) return r;
+        if constexpr (std::is_invocable_v<Fold&, uint64_t, uint32_t, const float*, const f4*, const uint8_t*>)
+        {
+            if ((r = fold(first, cnt, d_d, d_rad, d_id))) return r;
+        }
+        else fold(first, cnt, d_d, d_rad);
         HIPCHK(c, hipGetLastError());
     }
     return PT_OK;
@@ -3711,11 +3726,80 @@ int bake_lightmap_check(pt_ctx* c, const pt_lightmap_params* p, const float* rgb
     if ((uint64_t)p->first_sample + p->n_samples > 0x100000000ull) return fail(c, PT_ERR_ARG, "pt_lightmap_params.first_sample + n_samples wraps 32 bits");
     return PT_OK;
 }
+// ---- direct light sampled at the texel (pt_bake_lightmap_direct; the light sample is pt_lightmap.h's lm_light_sample)
+// what a direct bake refuses on top of the plain one's checks, before any device call; emissive: the 256-entry table of the first-hit id bytes
+// (a model index's low byte) that mean an emissive model
+int lightmap_direct_check(pt_ctx* c, const pt_lightmap_params* p, const pt_lightmap_direct* dp, uint8_t emissive[256])
+{
+    if (!dp) return fail(c, PT_ERR_ARG, "pt_bake_lightmap_direct: dp must not be NULL");
+    if (dp->reserved[0] || dp->reserved[1] || dp->reserved[2]) return fail(c, PT_ERR_ARG, "pt_lightmap_direct.reserved must be 0");
+    if ((uint64_t)dp->light_key_base + (uint64_t)p->w * p->h > 0x100000000ull) return fail(c, PT_ERR_ARG, "pt_lightmap_direct.light_key_base + w * h wraps 32 bits");
+    if (no_light_to_sample(c)) return fail(c, PT_ERR_STATE, "pt_bake_lightmap_direct: the scene has no emissive model");
+    if (c->scene.flat.has_volumes) return fail(c, PT_ERR_STATE, "pt_bake_lightmap_direct: scenes with participating media are out of scope");
+    uint8_t seen[256] = {}; // 1: an emissive model has this byte, 2: a non-emissive one
+    for (size_t i = 0; i < c->scene.models.size(); ++i)
+    {
+        const bool em = c->scene.materials[c->scene.models[i].material].kind == MAT_EMISSIVE;
+        seen[i & 0xffu] |= em ? 1u : 2u;
+        if (em && (i & 0xffu) == 255u) return fail(c, PT_ERR_LIMIT, "pt_bake_lightmap_direct: an emissive model's index has the low byte 255, the first-hit id of a miss");
+    }
+    for (uint32_t b = 0; b < 256u; ++b)
+    {
+        if (seen[b] == 3u) return fail(c, PT_ERR_LIMIT, "pt_bake_lightmap_direct: an emissive model shares the low byte of its index with a non-emissive one");
+        emissive[b] = seen[b] == 1u ? 1u : 0u;
+    }
+    return PT_OK;
+}
+// the light table over the resident scene (after upload_scene) ...
+LmLightView light_view_device(const pt_ctx* c)
+{
+    return LmLightView{c->sv.lights, c->sv.tri_pos, c->sv.tri_shade, c->sv.tri_isect, c->sv.materials, c->sv.n_lights, c->tex};
+}
+// ... and over the host's copies
+LmLightView light_view_host(const FlatScene& f)
+{
+    return LmLightView{f.lights.data(), f.tri_pos.data(), f.tri_shade.data(), f.tri_isect.data(), f.materials.data(), (uint32_t)f.lights.size(), f.tex_view()};
+}
+// A direct bake's buffers beside the ray table's, for windows of at most `chunk` rays: the shadow-ray queue (32 B per ray), ce (16), the any-hit
+// results (4) and the queue's count word and claim cursors; the id bytes are bake_rays'
+struct DirectWindow
+{
+    RayQueue q{};
+    f4* ce = nullptr;
+    uint32_t* occluded = nullptr;
+    uint32_t* head = nullptr;
+    const uint8_t* emissive = nullptr;
+    uint32_t light_key_base = 0;
+};
+int direct_window_alloc(Staging& st, uint32_t chunk, const uint8_t emissive[256], uint32_t light_key_base, DirectWindow& w)
+{
+    w.q = RayQueue{st.out<f4>(chunk), st.out<f4>(chunk)};
+    w.ce = st.out<f4>(chunk);
+    w.occluded = st.out<uint32_t>(chunk);
+    w.head = st.out<uint32_t>((size_t)32 + kHeadWordsPerQueue);
+    w.emissive = st.in<uint8_t>(emissive, 256);
+    w.light_key_base = light_key_base;
+    return st.err;
+}
+// a window between its integration and its fold: the light samples, their shadow rays through pt_trace_any's launch, then the fold of X = G + D
+template <class Bake>
+int direct_window_fold(pt_ctx* c, const Bake& lb, const DirectWindow& w, uint64_t first, uint32_t cnt, const f4* rad, const uint8_t* id, float* d_sum, float* d_sq)
+{
+    HIPCHK(c, hipMemsetAsync(w.head, 0, ((size_t)32 + kHeadWordsPerQueue) * sizeof(uint32_t), c->stream));
+    launch_lightmap_light_samples(c->stream, lb, light_view_device(c), w.light_key_base, first, cnt, w.q, w.ce, w.head);
+    if (c->sv.world_root == MISS_ID) HIPCHK(c, hipMemsetAsync(w.occluded, 0, (size_t)cnt * sizeof(uint32_t), c->stream));
+    else launch_trace_rays_any(c->stream, trace_launch(c), c->sv.world_root, w.q, cnt, w.head, w.occluded);
+    launch_lightmap_fold_direct(c->stream, lb, first, cnt, LightmapDirectWindow{rad, id, w.emissive, w.ce, w.occluded}, d_sum, d_sq);
+    return PT_OK;
+}
+
 int bake_lightmap_locked(pt_ctx* c, const pt_lightmap_params* p, float* rgb_sum, float* sumsq, bool moments, uint8_t* coverage, float* dir_sum = nullptr,
-                         bool directional = false)
+                         bool directional = false, const pt_lightmap_direct* dp = nullptr, bool direct = false)
 {
     int r;
     if ((r = bake_lightmap_check(c, p, rgb_sum, sumsq, moments, dir_sum, directional))) return r;
+    uint8_t emissive[256];
+    if (direct && (r = lightmap_direct_check(c, p, dp, emissive))) return r;
     const size_t px = (size_t)p->w * p->h;
     if ((r = upload_scene(c))) return r;
     const HostModel& m = c->scene.models[p->model];
@@ -3736,7 +3820,20 @@ int bake_lightmap_locked(pt_ctx* c, const pt_lightmap_params* p, float* rgb_sum,
         float* d_dir = directional ? st.inout<float>(dir_sum, 9 * px) : nullptr;
         float* d_sq = moments ? st.inout<float>(sumsq, px) : nullptr;
         const LightmapBake lb{d_texels, t.position, t.normal, n_cov, p->first_sample, p->n_samples, p->key_base, c->cfg.n_sobol, p->bias, c->cfg.seed};
-        if ((r = bake_rays(c, st, n_cov, p->n_samples,
+        if (direct)
+        {
+            uint32_t batch_rays;
+            DirectWindow dw;
+            if ((r = direct_window_alloc(st, bake_chunk(c, n_cov, p->n_samples, &batch_rays), emissive, dp->light_key_base, dw))) return r;
+            if ((r = bake_rays(c, st, n_cov, p->n_samples,
+                               [&](uint64_t first, uint32_t cnt, float* o, float* d, uint2* key) { launch_lightmap_rays(c->stream, lb, first, cnt, o, d, key); },
+                               [&](uint64_t first, uint32_t cnt, const float*, const f4* rad, const uint8_t* id) {
+                                   return direct_window_fold(c, lb, dw, first, cnt, rad, id, d_sum, d_sq);
+                               },
+                               true)))
+                return r;
+        }
+        else if ((r = bake_rays(c, st, n_cov, p->n_samples,
                            [&](uint64_t first, uint32_t cnt, float* o, float* d, uint2* key) { launch_lightmap_rays(c->stream, lb, first, cnt, o, d, key); },
                            [&](uint64_t first, uint32_t cnt, const float* d, const f4* rad) {
                                if (directional) launch_lightmap_fold_directional(c->stream, lb, first, cnt, rad, d, d_sum, d_dir);
@@ -3792,7 +3889,7 @@ int lightmap_select_device(pt_ctx* c, Staging& st, const LightmapDev& t, size_t 
 }
 
 int bake_lightmap_adaptive_locked(pt_ctx* c, const pt_lightmap_params* p, const pt_adaptive* crit, float* rgb_sum, float* sumsq, uint32_t* counts,
-                                  uint8_t* coverage, uint32_t* n_active)
+                                  uint8_t* coverage, uint32_t* n_active, const pt_lightmap_direct* dp = nullptr, bool direct = false)
 {
     int r;
     if ((r = bake_lightmap_check(c, p, rgb_sum, sumsq, true, nullptr, false))) return r;
@@ -3803,6 +3900,8 @@ int bake_lightmap_adaptive_locked(pt_ctx* c, const pt_lightmap_params* p, const 
     bool over = false;
     if ((r = lightmap_counts_over(c, m, p->w, p->h, counts, p->n_samples, &over))) return r;
     if (over) return fail(c, PT_ERR_LIMIT, "pt_bake_lightmap_adaptive: a covered texel's count + n_samples is above 2^24: f32 counts are not exact beyond");
+    uint8_t emissive[256];
+    if (direct && (r = lightmap_direct_check(c, p, dp, emissive))) return r;
     const size_t px = (size_t)p->w * p->h;
     if ((r = upload_scene(c))) return r;
     Staging st(c);
@@ -3818,7 +3917,20 @@ int bake_lightmap_adaptive_locked(pt_ctx* c, const pt_lightmap_params* p, const 
     if (n > 0)
     {
         const LightmapAdaptiveBake lb{d_list, t.position, t.normal, n, p->n_samples, p->key_base, c->cfg.n_sobol, p->bias, c->cfg.seed};
-        if ((r = bake_rays(c, st, n, p->n_samples,
+        if (direct)
+        {
+            uint32_t batch_rays;
+            DirectWindow dw;
+            if ((r = direct_window_alloc(st, bake_chunk(c, n, p->n_samples, &batch_rays), emissive, dp->light_key_base, dw))) return r;
+            if ((r = bake_rays(c, st, n, p->n_samples,
+                               [&](uint64_t first, uint32_t cnt, float* o, float* d, uint2* key) { launch_lightmap_rays(c->stream, lb, first, cnt, o, d, key); },
+                               [&](uint64_t first, uint32_t cnt, const float*, const f4* rad, const uint8_t* id) {
+                                   return direct_window_fold(c, lb, dw, first, cnt, rad, id, d_sum, d_sq);
+                               },
+                               true)))
+                return r;
+        }
+        else if ((r = bake_rays(c, st, n, p->n_samples,
                            [&](uint64_t first, uint32_t cnt, float* o, float* d, uint2* key) { launch_lightmap_rays(c->stream, lb, first, cnt, o, d, key); },
                            [&](uint64_t first, uint32_t cnt, const float*, const f4* rad) { launch_lightmap_fold(c->stream, lb, first, cnt, rad, d_sum, d_sq); })))
             return r;
@@ -4001,6 +4113,66 @@ int pt_bake_lightmap_directional(pt_ctx* c, const pt_lightmap_params* p, float* 
     if (!c) return PT_ERR_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
     return bake_lightmap_locked(c, p, rgb_sum, nullptr, false, coverage, dir_sum, true);
+}
+
+int pt_bake_lightmap_direct(pt_ctx* c, const pt_lightmap_params* p, const pt_lightmap_direct* dp, float* rgb_sum, float* sumsq, uint8_t* coverage)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    return bake_lightmap_locked(c, p, rgb_sum, sumsq, sumsq != nullptr, coverage, nullptr, false, dp, true);
+}
+
+int pt_bake_lightmap_adaptive_direct(pt_ctx* c, const pt_lightmap_params* p, const pt_lightmap_direct* dp, const pt_adaptive* crit, float* rgb_sum, float* sumsq,
+                                     uint32_t* counts, uint8_t* coverage, uint32_t* n_active)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    return bake_lightmap_adaptive_locked(c, p, crit, rgb_sum, sumsq, counts, coverage, n_active, dp, true);
+}
+
+int pt_lightmap_light_sample(pt_ctx* c, int on_device, uint32_t n, const uint32_t* key, const uint32_t* sample, const float* origin, const float* normal,
+                             uint32_t* light, float* dir, float* t_max, float* ce)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->scene.built) return fail(c, PT_ERR_STATE, "pt_build has not been called");
+    if (no_light_to_sample(c)) return fail(c, PT_ERR_STATE, "pt_lightmap_light_sample: the scene has no emissive model");
+    if (n == 0) return PT_OK;
+    if (!key || !sample || !origin || !normal) return fail(c, PT_ERR_ARG, "pt_lightmap_light_sample: key, sample, origin_xyz and normal_xyz must not be NULL");
+    if (!on_device)
+    {
+        const LmLightView lv = light_view_host(c->scene.flat);
+        for (uint32_t i = 0; i < n; ++i)
+        {
+            const LmLightSample ls = lm_light_sample(lv, c->cfg.seed, key[i], sample[i], load3(origin, i), load3(normal, i));
+            if (light) light[i] = ls.light;
+            if (dir) store3(dir, i, ls.dir);
+            if (t_max) t_max[i] = ls.t_max;
+            if (ce) store3(ce, i, ls.ce);
+        }
+        return PT_OK;
+    }
+    int r;
+    if ((r = upload_scene(c))) return r;
+    Staging st(c);
+    const uint32_t* d_key = st.in<uint32_t>(key, n);
+    const uint32_t* d_sample = st.in<uint32_t>(sample, n);
+    const float* d_o = st.in<float>(origin, 3 * (size_t)n);
+    const float* d_n = st.in<float>(normal, 3 * (size_t)n);
+    uint32_t* d_light = st.out<uint32_t>(light, n);
+    std::vector<f4> h_dir(n), h_ce(n);
+    f4* d_dir = st.out<f4>((float*)h_dir.data(), n);
+    f4* d_ce = st.out<f4>((float*)h_ce.data(), n);
+    if (st.err) return st.err;
+    launch_lightmap_light_sample_hook(c->stream, light_view_device(c), c->cfg.seed, n, d_key, d_sample, d_o, d_n, d_light, d_dir, d_ce);
+    if ((r = st.fetch())) return r;
+    for (uint32_t i = 0; i < n; ++i)
+    {
+        if (dir) store3(dir, i, f3{h_dir[i].x, h_dir[i].y, h_dir[i].z});
+        if (t_max) t_max[i] = h_dir[i].w;
+        if (ce) store3(ce, i, f3{h_ce[i].x, h_ce[i].y, h_ce[i].z});
+    }
+    return PT_OK;
 }
 
 int pt_lightmap_gradient(pt_ctx* c, int on_device, int model, uint32_t instance, uint32_t w, uint32_t h, uint32_t n_samples, const float* dir_sum, float* grad)

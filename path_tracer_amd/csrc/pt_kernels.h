@@ -152,6 +152,28 @@ struct LightmapAdaptiveBake
 };
 void launch_lightmap_rays(hipStream_t s, const LightmapAdaptiveBake& lb, uint64_t first, uint32_t count, float* o, float* d, uint2* key);
 void launch_lightmap_fold(hipStream_t s, const LightmapAdaptiveBake& lb, uint64_t first, uint32_t count, const f4* radiance, float* sum, float* sumsq);
+// Direct light sampled at the texel (pt_bake_lightmap_direct, pt_bake_lightmap_adaptive_direct; lm_light_sample, pt_lightmap.h).
+// launch_lightmap_light_samples writes the light samples of rays [first, first + count) of a bake into entries [0, count) of a ray queue, as
+// shadow rays (o | t_max, dir | entry; a hole where none is cast), and of a ce table, and the count into n_and_heads[0]: the queue is
+// launch_trace_rays_any's.  launch_lightmap_fold_direct is launch_lightmap_fold over X = G + D of the same window.
+struct LmLightView;
+struct LightmapDirectWindow
+{
+    const f4* radiance;       // the gather rays' radiance, as launch_lightmap_fold takes it
+    const uint8_t* id;        // ... and their first-hit id bytes (launch_store_rays)
+    const uint8_t* emissive;  // 256 bytes: non-zero where the id byte means an emissive model
+    const f4* ce;             // the light samples
+    const uint32_t* occluded; // ... and their shadow rays' results (holes unwritten)
+};
+void launch_lightmap_light_samples(hipStream_t s, const LightmapBake& lb, const LmLightView& lv, uint32_t light_key_base, uint64_t first, uint32_t count, RayQueue q,
+                                   f4* ce, uint32_t* n_and_heads);
+void launch_lightmap_light_samples(hipStream_t s, const LightmapAdaptiveBake& lb, const LmLightView& lv, uint32_t light_key_base, uint64_t first, uint32_t count,
+                                   RayQueue q, f4* ce, uint32_t* n_and_heads);
+void launch_lightmap_fold_direct(hipStream_t s, const LightmapBake& lb, uint64_t first, uint32_t count, const LightmapDirectWindow& w, float* sum, float* sumsq);
+void launch_lightmap_fold_direct(hipStream_t s, const LightmapAdaptiveBake& lb, uint64_t first, uint32_t count, const LightmapDirectWindow& w, float* sum, float* sumsq);
+// unit hook (pt_lightmap_light_sample): lm_light_sample of n caller-given (key, sample, origin, normal); dir_t = dir | t_max, ce = ce | 1.0f where a ray is cast
+void launch_lightmap_light_sample_hook(hipStream_t s, const LmLightView& lv, uint64_t seed, uint32_t n, const uint32_t* key, const uint32_t* sample,
+                                       const float* origin, const float* normal, uint32_t* light, f4* dir_t, f4* ce);
 // The texel selection: texel k is ACTIVE iff coverage[k] (launch_lightmap_resolve's byte) and adaptive_active (pt_types.h) of (sum[k],
 // sumsq[k], counts[k]).  Two passes over the table, no atomic append: list <- {k, counts[k]} of the active texels in ascending k (room for
 // n_texels entries), header[0] <- their number, header[1] |= 1 when an ACTIVE OR INACTIVE covered texel has counts[k] + n_samples > 2^24.

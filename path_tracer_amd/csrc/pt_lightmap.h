@@ -5,6 +5,7 @@
 #pragma once
 #include <vector>
 
+#include "pt_materials.h"
 #include "pt_types.h"
 
 namespace pt {
@@ -110,6 +111,87 @@ PT_HD f3 lightmap_ray(uint64_t seed, uint32_t n_sobol, uint32_t key, uint32_t sa
     float sn, cs;
     sincos_det(phi, &sn, &cs);
     return mul(onb_from_normal(n), f3{cs * r, sn * r, z});
+}
+
+// ---- direct light sampled at the texel (pt_bake_lightmap_direct; include/pt_api.h states it)
+// what a texel's light sample reads: the light table and the per-triangle and material tables the shading pass samples lights from, over the
+// device's copies (the kernel) or the host's (FlatScene: the hook's host evaluation)
+struct LmLightView
+{
+    const DLight* lights;
+    const DTriVerts* tri_pos;
+    const DTriVerts* tri_shade;
+    const DTriIsect* tri_isect;
+    const DMaterial* materials;
+    uint32_t n_lights;
+    TexView tex;
+};
+// light: the chosen entry of the light table; (dir, t_max): the shadow ray from the texel's origin, cast only when `cast`; ce: what the
+// sample adds when that ray is not blocked (zeros without a ray)
+struct LmLightSample
+{
+    f3 dir, ce;
+    float t_max;
+    uint32_t light;
+    bool cast;
+};
+PT_HD f3 lm_xyz(f4 v) { return f3{v.x, v.y, v.z}; }
+// the finite check and length clamp every sample ends with (finalise, pt_kernels.hip)
+PT_HD f3 lm_finalise(f3 v)
+{
+    if (!finite3(v)) return f3{0.0f, 0.0f, 0.0f};
+    return clamp_len_max(v, 100.0f);
+}
+// Light sample `sample` of the texel whose light stream is pixel `key`, at origin o under normal n (used as given): k_shade_surface's
+// estimate_direct_explicit for a Lambertian surface of colour 1 with the MIS weight replaced by 1, in its operation order.  THREE draws of
+// the stream are consumed.  Requires n_lights > 0.
+PT_HD LmLightSample lm_light_sample(const LmLightView& lv, uint64_t seed, uint32_t key, uint32_t sample, f3 o, f3 n)
+{
+    Stream rng{stream_key(seed, key, sample), 0u};
+    const float x = rng.f32();
+    uint32_t li = 0, hi = lv.n_lights;
+    const int32_t xk = total_order_key(x);
+    while (li < hi)
+    {
+        const uint32_t mid = (li + hi) >> 1;
+        if (total_order_key(lv.lights[mid].cdf) < xk) li = mid + 1u; else hi = mid;
+    }
+    if (li >= lv.n_lights) li = lv.n_lights - 1u;
+    const DLight L = lv.lights[li];
+    float lu = rng.f32();
+    float lv_ = rng.f32();
+    if (lu + lv_ > 1.0f) { lu = 1.0f - lu; lv_ = 1.0f - lv_; }
+    const float lw = 1.0f - lu - lv_;
+    const DTriVerts lp = lv.tri_pos[L.tri], ln = lv.tri_shade[L.tri];
+    const f3 point = mul(m33{lm_xyz(lp.a), lm_xyz(lp.b), lm_xyz(lp.c)}, f3{lw, lu, lv_});
+    const f3 lnormal = unit3(mul(m33{lm_xyz(ln.a), lm_xyz(ln.b), lm_xyz(ln.c)}, f3{lw, lu, lv_}));
+    const f3 d = point - o;
+    const float dist2 = len_sq(d);
+    const float dist = sqrtf(dist2);
+    LmLightSample out;
+    out.dir = unit3(d);
+    out.t_max = (1.0f - PT_EPSILON) * dist;
+    out.light = li;
+    out.ce = f3{0.0f, 0.0f, 0.0f};
+    const float c = dot3(out.dir, n);
+    out.cast = c > 0.0f;
+    if (!out.cast) return out;
+    const DTriIsect ti = lv.tri_isect[L.tri];
+    const float sample_pdf = L.pdf / (0.5f * len3(lm_xyz(ti.n0)));
+    const float cosl = fabsf(dot3(out.dir, lnormal));
+    const float light_pdf = sample_pdf * (dist2 / cosl);
+    const DMaterial& lm = lv.materials[L.material];
+    const f3 emitted = surface_colour(lv.tex, lm.texture, f3{lm.colour[0], lm.colour[1], lm.colour[2]}, L.tri, lu, lv_);
+    out.ce = lm_finalise(((emitted * fabsf(c)) * 0.31830987f) / light_pdf);
+    return out;
+}
+// one sample of a direct bake: X = G + D per channel, G the gather ray's radiance unless its first hit is on an emissive model (then the
+// light sample stands for it), D the light sample unless its shadow ray was blocked
+PT_HD float lm_direct_x(float radiance, bool first_hit_emissive, float ce, bool blocked)
+{
+    const float g = first_hit_emissive ? 0.0f : radiance;
+    const float dl = blocked ? 0.0f : ce;
+    return g + dl;
 }
 
 // The tangential gradient of a covered texel (pt_lightmap_gradient; include/pt_api.h states it): dir9 the texel's first-moment sums

@@ -156,6 +156,103 @@ __global__ void __launch_bounds__(256) k_lm_fold(const Bake lb, const uint64_t f
     fold_channel(sum + 3u * (size_t)bake_item(lb, rank).x + c, (const float*)radiance + c, i0, i1);
 }
 
+// ---- direct light sampled at the texel (pt_bake_lightmap_direct, pt_bake_lightmap_adaptive_direct)
+constexpr uint32_t kQueueHole = 0xffffffffu; // the ray queues' tag of a slot no ray took: the any-hit walk skips the entry and writes no result
+
+// one light sample into entry i of a ray queue and of the ce table: (o | t_max, dir | i), or a hole where no shadow ray is cast
+__device__ __forceinline__ void put_light_sample(const LmLightSample& ls, const f3 o, const uint32_t i, f4* __restrict__ qa, f4* __restrict__ qb, f4* __restrict__ ce)
+{
+    qa[i] = ls.cast ? f4{o.x, o.y, o.z, ls.t_max} : f4{0.0f, 0.0f, 0.0f, 0.0f};
+    qb[i] = ls.cast ? f4{ls.dir.x, ls.dir.y, ls.dir.z, __uint_as_float(i)} : f4{0.0f, 0.0f, 0.0f, __uint_as_float(kQueueHole)};
+    ce[i] = f4{ls.ce.x, ls.ce.y, ls.ce.z, 0.0f};
+}
+
+// the light samples of rays [first, first + count) of a bake, k_lm_rays' (rank, s) decomposition: lm_light_sample of the texel's origin and
+// normal under the stream of pixel light_key_base + texel.  Three contiguous 16-byte stores per lane, no atomics; thread 0 writes the
+// queue's count word (n_and_heads[0], what launch_trace_rays_any reads)
+template <class Bake>
+__global__ void __launch_bounds__(256) k_lm_light_samples(const Bake lb, const LmLightView lv, const uint32_t light_key_base, const uint64_t first, const uint32_t count,
+                                                           f4* __restrict__ qa, f4* __restrict__ qb, f4* __restrict__ ce, uint32_t* __restrict__ n_and_heads)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    if (i == 0u) n_and_heads[0] = count;
+    const uint64_t r = first + i;
+    const uint32_t rank = (uint32_t)(r / lb.n_samples);
+    const uint2 item = bake_item(lb, rank);
+    const uint32_t s = item.y + (uint32_t)(r - (uint64_t)rank * lb.n_samples);
+    const uint32_t k = item.x;
+    const float* pp = lb.position + 3u * (size_t)k;
+    const float* pn = lb.normal + 3u * (size_t)k;
+    const f3 n{pn[0], pn[1], pn[2]};
+    const f3 org = lm_origin(f3{pp[0], pp[1], pp[2]}, n, lb.bias);
+    put_light_sample(lm_light_sample(lv, lb.seed, light_key_base + k, s, org, n), org, i, qa, qb, ce);
+}
+
+// pt_lightmap_light_sample on the device: the same body over caller-given keys, samples, origins and normals; the outputs are the hook's
+__global__ void __launch_bounds__(256) k_lm_light_sample_hook(const LmLightView lv, const uint64_t seed, const uint32_t n, const uint32_t* __restrict__ key,
+                                                               const uint32_t* __restrict__ sample, const float* __restrict__ origin, const float* __restrict__ normal,
+                                                               uint32_t* __restrict__ light, f4* __restrict__ dir_t, f4* __restrict__ ce)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float* po = origin + 3u * (size_t)i;
+    const float* pn = normal + 3u * (size_t)i;
+    const LmLightSample ls = lm_light_sample(lv, seed, key[i], sample[i], f3{po[0], po[1], po[2]}, f3{pn[0], pn[1], pn[2]});
+    light[i] = ls.light;
+    dir_t[i] = f4{ls.dir.x, ls.dir.y, ls.dir.z, ls.t_max};
+    ce[i] = f4{ls.ce.x, ls.ce.y, ls.ce.z, ls.cast ? 1.0f : 0.0f};
+}
+
+// k_lm_fold over X = G + D (lm_direct_x): per sample from the gather ray's radiance and first-hit id byte, the 256-entry table of the bytes
+// that mean an emissive model, the light sample's ce and its shadow ray's result.  Threads per texel and the chain as k_lm_fold has them:
+// eight samples' loads ahead of their adds.  A hole's `occluded` word was never written, and its ce is 0 either way
+__device__ __forceinline__ float direct_x(const f4* __restrict__ radiance, const uint8_t* __restrict__ id, const uint8_t* __restrict__ emissive,
+                                          const f4* __restrict__ ce, const uint32_t* __restrict__ occluded, const uint32_t i, const uint32_t c)
+{
+    return lm_direct_x(((const float*)(radiance + i))[c], emissive[id[i]] != 0u, ((const float*)(ce + i))[c], occluded[i] != 0u);
+}
+template <bool MOMENTS, class Bake>
+__global__ void __launch_bounds__(256) k_lm_fold_direct(const Bake lb, const uint64_t first, const uint32_t count, const f4* __restrict__ radiance,
+                                                         const uint8_t* __restrict__ id, const uint8_t* __restrict__ emissive, const f4* __restrict__ ce,
+                                                         const uint32_t* __restrict__ occluded, float* __restrict__ sum, float* __restrict__ sumsq)
+{
+    constexpr uint32_t CH = MOMENTS ? 4u : 3u;
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t p0 = (uint32_t)(first / lb.n_samples), p1 = (uint32_t)((first + count - 1u) / lb.n_samples);
+    if (t / CH > p1 - p0) return;
+    const uint32_t rank = p0 + t / CH, c = t % CH;
+    const uint64_t lo = (uint64_t)rank * lb.n_samples, hi = lo + lb.n_samples;
+    const uint32_t i0 = (uint32_t)((lo > first ? lo : first) - first), i1 = (uint32_t)((hi < first + count ? hi : first + count) - first);
+    if (MOMENTS && c == 3u)
+    {
+        float* q = sumsq + bake_item(lb, rank).x;
+        float acc = *q;
+        for (uint32_t i = i0; i < i1; ++i)
+        {
+            const f4 x{direct_x(radiance, id, emissive, ce, occluded, i, 0u), direct_x(radiance, id, emissive, ce, occluded, i, 1u),
+                       direct_x(radiance, id, emissive, ce, occluded, i, 2u), 0.0f};
+            const float l = lum(x);
+            acc = acc + l * l;
+        }
+        *q = acc;
+        return;
+    }
+    float* dst = sum + 3u * (size_t)bake_item(lb, rank).x + c;
+    float acc = *dst;
+    uint32_t i = i0;
+    for (; i + 8u <= i1; i += 8u)
+    {
+        float x[8];
+#pragma unroll
+        for (uint32_t q = 0; q < 8u; ++q) x[q] = direct_x(radiance, id, emissive, ce, occluded, i + q, c);
+#pragma unroll
+        for (uint32_t q = 0; q < 8u; ++q) acc = acc + x[q];
+    }
+    for (; i < i1; ++i) acc = acc + direct_x(radiance, id, emissive, ce, occluded, i, c);
+    *dst = acc;
+}
+
 // ---- the texel selection of an adaptive bake (pt_bake_lightmap_adaptive, pt_lightmap_adaptive_mask)
 __device__ __forceinline__ uint32_t lane_id() { return threadIdx.x & 63u; }
 __device__ __forceinline__ uint32_t mbcnt64(uint64_t m)
@@ -391,6 +488,42 @@ void launch_lightmap_fold(hipStream_t s, const LightmapAdaptiveBake& lb, uint64_
     if (count == 0) return;
     const uint64_t texels = (first + count - 1u) / lb.n_samples - first / lb.n_samples + 1u;
     hipLaunchKernelGGL((k_lm_fold<true, LightmapAdaptiveBake>), blocks_for(texels * 4u), dim3(256), 0, s, lb, first, count, radiance, sum, sumsq);
+}
+template <class Bake>
+static void light_samples(hipStream_t s, const Bake& lb, const LmLightView& lv, uint32_t light_key_base, uint64_t first, uint32_t count, RayQueue q, f4* ce,
+                          uint32_t* n_and_heads)
+{
+    if (count == 0) return;
+    hipLaunchKernelGGL(k_lm_light_samples<Bake>, blocks_for(count), dim3(256), 0, s, lb, lv, light_key_base, first, count, q.a, q.b, ce, n_and_heads);
+}
+void launch_lightmap_light_samples(hipStream_t s, const LightmapBake& lb, const LmLightView& lv, uint32_t light_key_base, uint64_t first, uint32_t count, RayQueue q,
+                                   f4* ce, uint32_t* n_and_heads)
+{
+    light_samples(s, lb, lv, light_key_base, first, count, q, ce, n_and_heads);
+}
+void launch_lightmap_light_samples(hipStream_t s, const LightmapAdaptiveBake& lb, const LmLightView& lv, uint32_t light_key_base, uint64_t first, uint32_t count,
+                                   RayQueue q, f4* ce, uint32_t* n_and_heads)
+{
+    light_samples(s, lb, lv, light_key_base, first, count, q, ce, n_and_heads);
+}
+void launch_lightmap_light_sample_hook(hipStream_t s, const LmLightView& lv, uint64_t seed, uint32_t n, const uint32_t* key, const uint32_t* sample,
+                                       const float* origin, const float* normal, uint32_t* light, f4* dir_t, f4* ce)
+{
+    if (n == 0) return;
+    hipLaunchKernelGGL(k_lm_light_sample_hook, blocks_for(n), dim3(256), 0, s, lv, seed, n, key, sample, origin, normal, light, dir_t, ce);
+}
+void launch_lightmap_fold_direct(hipStream_t s, const LightmapBake& lb, uint64_t first, uint32_t count, const LightmapDirectWindow& w, float* sum, float* sumsq)
+{
+    if (count == 0) return;
+    const uint64_t texels = (first + count - 1u) / lb.n_samples - first / lb.n_samples + 1u;
+    if (sumsq) hipLaunchKernelGGL((k_lm_fold_direct<true, LightmapBake>), blocks_for(texels * 4u), dim3(256), 0, s, lb, first, count, w.radiance, w.id, w.emissive, w.ce, w.occluded, sum, sumsq);
+    else hipLaunchKernelGGL((k_lm_fold_direct<false, LightmapBake>), blocks_for(texels * 3u), dim3(256), 0, s, lb, first, count, w.radiance, w.id, w.emissive, w.ce, w.occluded, sum, sumsq);
+}
+void launch_lightmap_fold_direct(hipStream_t s, const LightmapAdaptiveBake& lb, uint64_t first, uint32_t count, const LightmapDirectWindow& w, float* sum, float* sumsq)
+{
+    if (count == 0) return;
+    const uint64_t texels = (first + count - 1u) / lb.n_samples - first / lb.n_samples + 1u;
+    hipLaunchKernelGGL((k_lm_fold_direct<true, LightmapAdaptiveBake>), blocks_for(texels * 4u), dim3(256), 0, s, lb, first, count, w.radiance, w.id, w.emissive, w.ce, w.occluded, sum, sumsq);
 }
 uint32_t lightmap_select_blocks(uint32_t n_texels) { return (n_texels + kSelectPerBlock - 1u) / kSelectPerBlock; }
 void launch_lightmap_select(hipStream_t s, const LightmapSelect& sel, uint32_t* block_counts, uint2* list, uint32_t* header)

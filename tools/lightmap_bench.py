@@ -23,7 +23,17 @@ arrays (min_samples = max_samples = SPP) beside pt_bake_lightmap_moments of the 
 are the same, so the difference is the selection and the three arrays' transfers less the coverage round trip saved.  GAIN: on the tests'
 48 x 32 map and on a 256 x 256 one, rounds of 4 samples under (REL, floor 0.01, at least 4, at most CAP) until no texel is selected, beside
 uniform bakes of the same ray budget (the mean count rounded down and up): RMSE over covered texels, raw and through the texel filter,
-against a 4096-sample bake of OTHER samples (key_base shifted by 2^24), and the distribution of the counts."""
+against a 4096-sample bake of OTHER samples (key_base shifted by 2^24), and the distribution of the counts.
+
+    python tools/lightmap_bench.py --direct [--size 1024] [--spp 64] [--reps 5] [--only-cost] [--out report.json]
+
+measures direct light sampled at the texel (pt_bake_lightmap_direct, profiles/r34_lightmap_direct.md).  QUALITY, on the tests' 48 x 32 map: RMSE
+over covered texels against a 4096-sample PLAIN bake of other samples (key_base shifted by 2^24) of the plain and the direct bake at 4, 16 and
+64 samples, raw and through the texel filter; of both adaptive bakes (rounds of 4 under REL, floor 0.01, at least 4, at most 64) at REL 0.05,
+0.1 and 0.2 with the rays each spent, beside a uniform direct bake of the plain adaptive bake's budget; and the residual of a 4096-sample
+direct bake of yet other samples, which is clamp and estimator differences.  COST: the direct and the plain bake at SIZE x SIZE x SPP,
+alternating, every time kept (--only-cost with --reps 1 is the run for rocprofv3 --kernel-trace --stats: the light-sample kernel, the any-hit
+launch and the fold are kernels of their own)."""
 import argparse
 import json
 import os
@@ -150,8 +160,71 @@ def adaptive_report(r, model, size, spp, reps, rel, cap):
     return report
 
 
+def direct_report(r, model, size, spp, reps, only_cost):
+    f32 = np.float32
+    report = {"size": size, "spp": spp, "plain_ms": [], "direct_ms": []}
+    for _ in range(2):                  # warm-up at the timed shape
+        r.bake_lightmap(model, 0, size, size, spp, bias=BIAS)
+        r.bake_lightmap_direct(model, 0, size, size, spp, bias=BIAS)
+    for _ in range(reps):               # the two routes alternate, so that a drift of the shared machine touches both
+        t0 = time.perf_counter()
+        plain = r.bake_lightmap(model, 0, size, size, spp, bias=BIAS)
+        report["plain_ms"].append(1e3 * (time.perf_counter() - t0))
+        t0 = time.perf_counter()
+        direct = r.bake_lightmap_direct(model, 0, size, size, spp, bias=BIAS)
+        report["direct_ms"].append(1e3 * (time.perf_counter() - t0))
+    covered = plain[1] == 1
+    report["covered"] = int(covered.sum())
+    report["rays"] = report["covered"] * spp
+    for name in ("plain", "direct"):
+        t = report[name + "_ms"]
+        report[name + "_median_ms"], report[name + "_spread_ms"] = float(np.median(t)), [float(min(t)), float(max(t))]
+    report["mean_irradiance"] = {"plain": float(np.pi * plain[0][covered].mean() / spp), "direct": float(np.pi * direct[0][covered].mean() / spp)}
+    if only_cost:
+        return report
+    w, h = 48, 32
+    ref, cov = r.bake_lightmap(model, 0, w, h, 4096, key_base=1 << 24, bias=BIAS)
+    ref = ref / f32(4096)
+    covered = cov == 1
+    report["quality"] = {"covered": int(covered.sum()), "uniform": {}, "adaptive": {}}
+    q = report["quality"]
+    for n in (4, 16, 64):
+        row = {}
+        for name, bake in (("plain", lambda: r.bake_lightmap_moments(model, 0, w, h, n, bias=BIAS)), ("direct", lambda: r.bake_lightmap_direct(model, 0, w, h, n, bias=BIAS, moments=True))):
+            sums, sumsq, _ = bake()
+            row[name] = {"raw": rmse(sums / f32(n), ref, covered), "denoised": rmse(r.denoise_lightmap(model, 0, sums, n, sumsq=sumsq), ref, covered)}
+        q["uniform"][str(n)] = row
+    big, _ = r.bake_lightmap_direct(model, 0, w, h, 4096, key_base=1 << 25, bias=BIAS)
+    again, _ = r.bake_lightmap(model, 0, w, h, 4096, key_base=1 << 25, bias=BIAS)
+    q["residual_4096"] = {"direct": rmse(big / f32(4096), ref, covered), "plain_of_the_same_samples": rmse(again / f32(4096), ref, covered)}
+    err = np.abs((big / f32(4096)).astype(np.float64) - ref.astype(np.float64)).mean(2)
+    q["residual_4096"]["largest_texel"] = {"error": float(err[covered].max()), "texel": [int(v) for v in np.unravel_index(np.argmax(np.where(covered, err, -1)), err.shape)]}
+    for rel in (0.05, 0.1, 0.2):
+        row = {}
+        for name, bake in (("plain", r.bake_lightmap_adaptive), ("direct", r.bake_lightmap_adaptive_direct)):
+            state, rays = (None, None, None), 0
+            while True:
+                *state, _, n_active = bake(model, 0, w, h, 4, rel, abs_floor=0.01, min_samples=4, max_samples=64, bias=BIAS, sums=state[0], sumsq=state[1], counts=state[2])
+                if n_active == 0:
+                    break
+                rays += n_active * 4
+            sums, sumsq, counts = state
+            mean = np.zeros_like(sums)
+            mean[covered] = sums[covered] / counts[covered].astype(f32)[:, None]
+            row[name] = {"rays": int(rays), "mean_count": float(counts[covered].mean()), "raw": rmse(mean, ref, covered),
+                         "denoised": rmse(r.denoise_lightmap(model, 0, sums, 0, sumsq=sumsq, counts=counts), ref, covered)}
+        n = -(-row["plain"]["rays"] // q["covered"])
+        sums, sumsq, _ = r.bake_lightmap_direct(model, 0, w, h, n, bias=BIAS, moments=True)
+        row["direct_uniform_at_the_plain_budget"] = {"samples": int(n), "rays": int(n) * q["covered"], "raw": rmse(sums / f32(n), ref, covered),
+                                                      "denoised": rmse(r.denoise_lightmap(model, 0, sums, n, sumsq=sumsq), ref, covered)}
+        q["adaptive"][str(rel)] = row
+    return report
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--direct", action="store_true")
+    ap.add_argument("--only-cost", action="store_true")
     ap.add_argument("--denoise", action="store_true")
     ap.add_argument("--adaptive", action="store_true")
     ap.add_argument("--rel", type=float, default=0.05)
@@ -171,8 +244,9 @@ def main():
     sc, model = LC.cornell_atlas_scene(args.model, W, H)
     r = api.Renderer(sc, W, H, max_bounces=DEPTH)
     size, spp = args.size, args.spp
-    if args.denoise or args.adaptive:
-        line = json.dumps(adaptive_report(r, model, size, spp, args.reps, args.rel, args.cap) if args.adaptive else denoise_report(r, model, size, args.reps))
+    if args.denoise or args.adaptive or args.direct:
+        line = json.dumps(direct_report(r, model, size, spp, args.reps, args.only_cost) if args.direct
+                          else adaptive_report(r, model, size, spp, args.reps, args.rel, args.cap) if args.adaptive else denoise_report(r, model, size, args.reps))
         print(line)
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
