@@ -54,6 +54,9 @@
 //   examples/headless ... --bake-lightmap ... --direct [--adaptive REL MAX] [--lightmap-denoise] [--baked-view ...]   takes one light sample with a
 //       shadow ray at the texel beside every gather sample (pt_bake_lightmap_direct, pt_bake_lightmap_adaptive_direct; the light samples'
 //       streams follow the gather samples': light_key_base = W * H); everything after the bake is what it is without the option
+//   examples/headless ... --bake-lightmap ... --gather ITERATIONS [--direct] [--baked-view ...]   bakes by final gather (pt_bake_lightmap_gather):
+//       ITERATIONS passes, each from the map the pass before set on the shell, the gather rays ending in it; with --direct pass k holds the
+//       direct light and k bounces between the shell's own surfaces
 //   examples/headless ... --bake-lightmap ... --directional [--normal-ripples N] [--baked-view ...]   bakes the first moments beside the sums
 //       (pt_bake_lightmap_directional), takes their tangential gradient (pt_lightmap_gradient), dilates it plane by plane and, under --baked-view,
 //       sets it beside the map (pt_set_lightmap_directional): with --normal-ripples, which then lie under the bake's planar UVs (the floor and the
@@ -107,6 +110,8 @@ int main(int argc, char** argv)
     uint32_t probe_radiance = 0;           // --probe-radiance R
     bool probe_radiance_given = false, metal_box = false;
     bool lightmap_denoise = false, directional = false, adaptive = false, direct = false;
+    uint32_t gather = 0;
+    bool gather_given = false;
     float adaptive_rel = 0.0f;
     uint32_t adaptive_max = 0;
     std::string baked_out = "";
@@ -186,6 +191,7 @@ int main(int argc, char** argv)
         }
         else if (a == "--lightmap-denoise") lightmap_denoise = true;
         else if (a == "--direct") direct = true;
+        else if (a == "--gather") { gather = (uint32_t)std::atoi(next("--gather")); gather_given = true; }
         else if (a == "--directional") directional = true;
         else if (a == "--adaptive")
         {
@@ -241,6 +247,11 @@ int main(int argc, char** argv)
     if (direct && (lightmap_out.empty() || !lightmap[2] || directional))
     {
         std::fprintf(stderr, "--direct samples the lights at the texels of the map --bake-lightmap bakes: it needs that option, and samples, and does not go with --directional\n");
+        return 2;
+    }
+    if (gather_given && (!gather || lightmap_out.empty() || !lightmap[2] || directional || adaptive || lightmap_denoise))
+    {
+        std::fprintf(stderr, "--gather ITERATIONS bakes the map --bake-lightmap bakes by final gather, ITERATIONS >= 1 passes: it needs that option, and samples, and goes with --direct and --baked-view only\n");
         return 2;
     }
     if (adaptive && (lightmap_out.empty() || !lightmap[2] || directional || !(adaptive_rel >= 0.0f) || (adaptive_max != 0 && adaptive_max < 2) ||
@@ -447,6 +458,24 @@ int main(int argc, char** argv)
                 cov = direct ? renderer.bake_lightmap_direct(1, 0, lightmap[0], lightmap[1], lightmap[2], sums, &sumsq, light_keys, 0, 0, 0.25f)
                              : renderer.bake_lightmap_moments(1, 0, lightmap[0], lightmap[1], lightmap[2], sums, sumsq, 0, 0, 0.25f);
                 sums = renderer.denoise_lightmap(1, 0, lightmap[0], lightmap[1], lightmap[2], sums, sumsq);
+            }
+            else if (gather)
+            {
+                // the final-gather loop on the one placement: every pass bakes the shell from the map set by the pass before (the first from
+                // whatever is set: nothing), its gather rays ending in that map after at most two mirror or glass hops, black where no map
+                // is; all but the last pass are divided, dilated and set here, the last below like every other bake
+                for (uint32_t pass = 0; pass < gather; ++pass)
+                {
+                    sums.clear();
+                    cov = renderer.bake_lightmap_gather(1, 0, lightmap[0], lightmap[1], lightmap[2], sums, nullptr, direct, direct ? light_keys : 0u, 2u, {0.0f, 0.0f, 0.0f}, 0,
+                                                        0, 0.25f);
+                    if (pass + 1 == gather) break;
+                    std::vector<float> means = sums;
+                    std::vector<uint8_t> filled = cov;
+                    for (float& m : means) m = m / (float)lightmap[2];
+                    renderer.dilate_lightmap(lightmap[0], lightmap[1], lightmap[3], means, filled);
+                    renderer.set_lightmap(1, 0, lightmap[0], lightmap[1], means);
+                }
             }
             else if (direct) cov = renderer.bake_lightmap_direct(1, 0, lightmap[0], lightmap[1], lightmap[2], sums, nullptr, light_keys, 0, 0, 0.25f);
             else cov = renderer.bake_lightmap(1, 0, lightmap[0], lightmap[1], lightmap[2], sums, 0, 0, 0.25f);

@@ -1192,6 +1192,72 @@ int pt_read_baked(pt_ctx* ctx, float* rgbn);
 int pt_reset_baked(pt_ctx* ctx);
 int pt_write_baked_image(pt_ctx* ctx, const char* path);
 
+/* ---- baked rays and the final-gather bake: chains of caller rays, and gather rays, ended in the maps the context holds ------------------- */
+/* BAKED RAYS.  pt_baked_rays evaluates the baked view's ending for n rays the caller supplies (o_xyz, d_xyz: 3 floats per ray).  Ray i is
+ * Ray::new(o[i], d[i]), the direction used as given (not normalised).  Its chain is word for word the chain pt_render_baked defines with "the
+ * camera ray" replaced by this ray: the same hops, the same c_i and running product R_h, the same endings (a light, a mapped front face, unlit,
+ * a miss under the environment map or the constant ambient) and the same axes selected by the context's state (probe grid, depth, radiance,
+ * directional gradient: the sections below).  Media are ignored, as the view ignores them.  All arithmetic is binary32, one rounding per
+ * operation, no contraction.
+ *     rgbh[i] = (B.r, B.g, B.b, (float)H)      -- H: the hop the chain ended at; STORED, not added
+ *     id[i]   = the id byte pt_integrate_rays would report for this ray's FIRST hit: the model index's low byte, 255 for a miss
+ * Either output may be NULL.  A ray's result depends only on the scene, the maps and grid set, `baked` and the ray: not on n, its index, its
+ * neighbours, window_rays, where the BVH lives, the walk variant or the rank.  No stream draw is consumed.  The call touches and stales none
+ * of the accumulation, the position and id history, the moments, the guides, the baked sums and the temporal history: the rays go through
+ * scratch of the call's own, a window at a time (two hook queues, hits, chain state and head words for window_rays rays), one closest-hit
+ * trace and one ending launch per hop, nothing coming back to the host between hops; the traces are logged under PT_LAUNCHES_HOOK.
+ * pt_baked_rays_device is the same call with every array a device pointer (rgbh: 16 bytes per ray) and p a host pointer; the results are
+ * complete when it returns.
+ * Errors, all before any device call, in this order: PT_ERR_ARG for a NULL p and for what pt_render_baked refuses in `baked` (max_hops above
+ * 8, its reserved words, an unlit that is negative or not finite); PT_ERR_ARG for a non-zero p->reserved; PT_ERR_STATE without a built scene
+ * (no camera is needed); PT_ERR_ARG for a NULL o_xyz or d_xyz with n > 0; in the host variant PT_ERR_ARG for a ray component that is not
+ * finite.  n = 0 is PT_OK. */
+typedef struct pt_baked_rays_params
+{
+    pt_baked_params baked;   /* max_hops, unlit: exactly pt_render_baked's meaning and checks */
+    uint32_t window_rays;    /* 0 = the implementation's window; otherwise rays per window (a test knob, like pt_rays_params.batch_rays) */
+    uint32_t reserved[3];    /* must be 0 */
+} pt_baked_rays_params;
+int pt_baked_rays(pt_ctx* ctx, uint64_t n, const float* o_xyz, const float* d_xyz, const pt_baked_rays_params* p, float* rgbh /* may be NULL */,
+                  uint8_t* id /* may be NULL */);
+int pt_baked_rays_device(pt_ctx* ctx, uint64_t n, const float* o_xyz, const float* d_xyz, const pt_baked_rays_params* p, float* rgbh, uint8_t* id);
+/* THE FINAL-GATHER BAKE.  pt_bake_lightmap_gather is a lightmap bake whose gather ray is one baked chain instead of a path: one closest-hit
+ * trace per hop, no shading pass, no RNG beyond the ray's own draw.  Coverage, the texel table, o = P + bias * n and the gather ray of
+ * (key_base + k, s) - pt_lightmap_ray; draw 0 of that stream is the only draw used - are pt_bake_lightmap's.  The sample X of texel k, sample s:
+ *     G = B of pt_baked_rays for that ray under g->baked
+ *     direct == 0:  X = G
+ *     direct == 1:  G = 0 when the ray's id byte says its first hit is on an emissive model (pt_bake_lightmap_direct's rule and PT_ERR_LIMIT);
+ *                   D = pt_lightmap_light_sample's ce of (light_key_base + k, s), or 0 when its shadow ray is blocked;   X = G + D
+ * The fold is pt_bake_lightmap_direct's, operation for operation, sumsq from l(X).  A lamp reached through a mirror or glass (H > 0) stays in
+ * G: D does not sample that path.  There is no finite check and no clamp on G.  The maps, grid and probes read are the ones set on the
+ * context (pt_set_lightmap* ...), the baked placement's own previous map possibly among them; the call sets nothing.  Baking every placement
+ * from the maps of the previous pass, then setting them all, is the radiosity / final-gather iteration: pass 0 with no maps and unlit = 0 is
+ * direct light only, pass k adds bounce k.
+ *   - bake(0, a) followed by bake(a, b) is bake(0, a + b), bit for bit, in both arrays.
+ *   - A texel's result does not depend on the batch cut (pt_config.batch_spp cuts the windows here as well), the window cut or the texel order.
+ *   - pt_bake_lightmap_adaptive_gather is pt_bake_lightmap_adaptive over these samples, its contract word for word: after any rounds a
+ *     covered texel holds what pt_bake_lightmap_gather with sumsq gives it at first_sample = 0, n_samples = counts[k].
+ *   - pi * sum / n is still the irradiance: pt_set_lightmap, pt_lightmap_denoise*, pt_lightmap_dilate and the baked view take these maps unchanged.
+ *   - pt_stats.paths grows by covered * n_samples (by active * n_samples in the adaptive call).
+ * The existing bakes, their launches and their bits do not change; a context that never calls these allocates and launches nothing new.
+ * Errors, all before any device call, in this order: everything pt_bake_lightmap_moments refuses (pt_bake_lightmap with a NULL sumsq;
+ * pt_bake_lightmap_adaptive for the adaptive call); PT_ERR_ARG for a NULL g and for what pt_render_baked refuses in g->baked; PT_ERR_ARG for
+ * a non-zero g->reserved, a direct above 1, light_key_base != 0 with direct == 0; with direct == 1 everything pt_bake_lightmap_direct
+ * refuses of (p, light_key_base); with direct == 0 PT_ERR_STATE for a scene with participating media (direct == 1 refuses it as the direct
+ * bake does).
+ * Out of scope: directional gather, pt_multi_* variants, continuing a path where a chain ends unlit. */
+typedef struct pt_lightmap_gather
+{
+    pt_baked_params baked;     /* how the gather chain ends */
+    uint32_t direct;           /* 1: add the light sample at the texel and zero a gather ray whose first hit is a lamp; 0: gather only */
+    uint32_t light_key_base;   /* as pt_lightmap_direct's; ignored (must be 0) when direct == 0 */
+    uint32_t reserved[2];      /* must be 0 */
+} pt_lightmap_gather;
+int pt_bake_lightmap_gather(pt_ctx* ctx, const pt_lightmap_params* p, const pt_lightmap_gather* g, float* rgb_sum, float* sumsq /* may be NULL */,
+                            uint8_t* coverage /* may be NULL */);
+int pt_bake_lightmap_adaptive_gather(pt_ctx* ctx, const pt_lightmap_params* p, const pt_lightmap_gather* g, const pt_adaptive* crit, float* rgb_sum,
+                                     float* sumsq, uint32_t* counts, uint8_t* coverage /* may be NULL */, uint32_t* n_active /* may be NULL */);
+
 /* ---- directional lightmaps: a direction baked beside the irradiance, so that the baked view shades normal-mapped surfaces ------------------- */
 /* A lightmap texel is the mean M0 = (1/N) sum L_s of the radiance over N cosine-distributed directions d_s about the texel normal n: what a
  * Lambertian surface with shading normal n returns.  Under a perturbed normal n' the exact response is (1/N) sum L_s max(0, n'.d_s) / (n.d_s);

@@ -168,6 +168,20 @@ struct RayResults
     std::vector<uint8_t> id;               // n
 };
 
+// what Renderer::baked_rays returns, per ray: the baked sample and the hop its chain ended at (r, g, b, hop), and the first hit's id byte
+struct BakedRays
+{
+    std::vector<float> rgbh; // n * 4
+    std::vector<uint8_t> id; // n
+};
+inline pt_baked_params baked_params(uint32_t max_hops, const std::array<float, 3>& unlit)
+{
+    pt_baked_params p{};
+    p.max_hops = max_hops;
+    p.unlit[0] = unlit[0]; p.unlit[1] = unlit[1]; p.unlit[2] = unlit[2];
+    return p;
+}
+
 // Scene::new on a context: materials in first-use order, models, pt_build
 inline void upload(pt_ctx* ctx_, const Scene& scene)
 {
@@ -670,6 +684,65 @@ public:
     std::vector<float> read_baked() const { std::vector<float> v((size_t)width_ * height_ * 4); check(pt_read_baked(ctx_, v.data())); return v; }
     void reset_baked() { check(pt_reset_baked(ctx_)); }
     void write_baked_image(const std::string& path) const { check(pt_write_baked_image(ctx_, path.c_str())); }
+    // the baked view's chain for caller-supplied rays (pt_baked_rays): o, d 3 floats per ray (d is used as given); rgbh gets (B.r, B.g, B.b,
+    // the hop the chain ended at) per ray and id the first hit's id byte (255 = miss).  window_rays 0: the library's window
+    BakedRays baked_rays(const std::vector<float>& o, const std::vector<float>& d, uint32_t max_hops = 0, std::array<float, 3> unlit = {0.0f, 0.0f, 0.0f},
+                         uint32_t window_rays = 0)
+    {
+        if (o.size() != d.size() || o.size() % 3 != 0) throw Error(PT_ERR_ARG, "baked_rays: o and d are 3 floats per ray for the same rays");
+        const size_t n = o.size() / 3;
+        BakedRays out;
+        out.rgbh.resize(n * 4); out.id.resize(n);
+        pt_baked_rays_params p{};
+        p.baked = baked_params(max_hops, unlit);
+        p.window_rays = window_rays;
+        check(pt_baked_rays(ctx_, n, o.data(), d.data(), &p, out.rgbh.data(), out.id.data()));
+        return out;
+    }
+    // the final-gather bake (pt_bake_lightmap_gather): bake_lightmap whose gather ray is one baked chain (max_hops, unlit as render_baked)
+    // ended in the maps, grid and probes set on this renderer; with direct the texel's light sample is added and a gather ray whose first hit
+    // is a lamp counts zero, as bake_lightmap_direct (light_key_base likewise; 0 without direct).  sumsq null: no moments.  Sets nothing.
+    std::vector<uint8_t> bake_lightmap_gather(int model, uint32_t instance, uint32_t w, uint32_t h, uint32_t n_samples, std::vector<float>& rgb_sum,
+                                              std::vector<float>* sumsq, bool direct, uint32_t light_key_base, uint32_t max_hops = 0,
+                                              std::array<float, 3> unlit = {0.0f, 0.0f, 0.0f}, uint32_t first_sample = 0, uint32_t key_base = 0, float bias = 0.0f)
+    {
+        const size_t px = (size_t)w * h;
+        if (rgb_sum.empty()) rgb_sum.assign(px * 3, 0.0f);
+        if (sumsq && sumsq->empty()) sumsq->assign(px, 0.0f);
+        if (rgb_sum.size() != px * 3 || (sumsq && sumsq->size() != px)) throw Error(PT_ERR_ARG, "bake_lightmap_gather: rgb_sum holds 3 values per texel and sumsq one");
+        std::vector<uint8_t> coverage(px);
+        pt_lightmap_params p{};
+        p.model = model; p.instance = instance; p.w = w; p.h = h;
+        p.first_sample = first_sample; p.n_samples = n_samples; p.key_base = key_base; p.bias = bias;
+        pt_lightmap_gather g{};
+        g.baked = baked_params(max_hops, unlit);
+        g.direct = direct ? 1u : 0u; g.light_key_base = light_key_base;
+        check(pt_bake_lightmap_gather(ctx_, &p, &g, rgb_sum.data(), sumsq ? sumsq->data() : nullptr, coverage.data()));
+        return coverage;
+    }
+    // one round of bake_lightmap_adaptive over bake_lightmap_gather's samples (pt_bake_lightmap_adaptive_gather)
+    uint32_t bake_lightmap_adaptive_gather(int model, uint32_t instance, uint32_t w, uint32_t h, uint32_t n_samples, const pt_adaptive& crit, std::vector<float>& rgb_sum,
+                                           std::vector<float>& sumsq, std::vector<uint32_t>& counts, bool direct, uint32_t light_key_base, uint32_t max_hops = 0,
+                                           std::array<float, 3> unlit = {0.0f, 0.0f, 0.0f}, std::vector<uint8_t>* coverage = nullptr, uint32_t key_base = 0,
+                                           float bias = 0.0f)
+    {
+        const size_t px = (size_t)w * h;
+        if (rgb_sum.empty()) rgb_sum.assign(px * 3, 0.0f);
+        if (sumsq.empty()) sumsq.assign(px, 0.0f);
+        if (counts.empty()) counts.assign(px, 0u);
+        if (rgb_sum.size() != px * 3 || sumsq.size() != px || counts.size() != px)
+            throw Error(PT_ERR_ARG, "bake_lightmap_adaptive_gather: rgb_sum holds 3 values per texel, sumsq and counts one");
+        if (coverage) coverage->assign(px, 0);
+        pt_lightmap_params p{};
+        p.model = model; p.instance = instance; p.w = w; p.h = h;
+        p.n_samples = n_samples; p.key_base = key_base; p.bias = bias;
+        pt_lightmap_gather g{};
+        g.baked = baked_params(max_hops, unlit);
+        g.direct = direct ? 1u : 0u; g.light_key_base = light_key_base;
+        uint32_t n = 0;
+        check(pt_bake_lightmap_adaptive_gather(ctx_, &p, &g, &crit, rgb_sum.data(), sumsq.data(), counts.data(), coverage ? coverage->data() : nullptr, &n));
+        return n;
+    }
     // the irradiance volume (pt_set_probe_grid): g places the nodes, sh27 holds 27 RADIANCE coefficients per node (node (ix, iy, iz) at
     // (iz * ny + iy) * nx + ix), valid a byte per node (empty: all valid).  An empty sh27 with counts of 0 clears the grid.
     void set_probe_grid(const pt_probe_grid& g, const std::vector<float>& sh27, const std::vector<uint8_t>& valid = {})

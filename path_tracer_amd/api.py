@@ -58,6 +58,7 @@ EXPORTS = [
     "pt_bake_lightmap_directional", "pt_lightmap_gradient", "pt_set_lightmap_directional", "pt_get_lightmap_directional_info", "pt_lightmap_lookup_directional",
     "pt_bake_lightmap_adaptive", "pt_lightmap_adaptive_mask", "pt_lightmap_denoise_counts",
     "pt_bake_lightmap_direct", "pt_bake_lightmap_adaptive_direct", "pt_lightmap_light_sample",
+    "pt_baked_rays", "pt_baked_rays_device", "pt_bake_lightmap_gather", "pt_bake_lightmap_adaptive_gather",
 ]
 
 
@@ -186,6 +187,16 @@ class LightmapParams(C.Structure):
 class LightmapDirect(C.Structure):
     """pt_lightmap_direct: the stream keys of a direct bake's light samples (include/pt_api.h)"""
     _fields_ = [("light_key_base", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class BakedRaysParams(C.Structure):
+    """pt_baked_rays_params"""
+    _fields_ = [("baked", BakedParams), ("window_rays", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class LightmapGather(C.Structure):
+    """pt_lightmap_gather"""
+    _fields_ = [("baked", BakedParams), ("direct", C.c_uint32), ("light_key_base", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
 class LightmapDenoiseParams(C.Structure):
@@ -354,6 +365,10 @@ def lib():
         L.pt_bake_lightmap_direct.argtypes = [vp, C.POINTER(LightmapParams), C.POINTER(LightmapDirect), vp, vp, vp]
         L.pt_bake_lightmap_adaptive_direct.argtypes = [vp, C.POINTER(LightmapParams), C.POINTER(LightmapDirect), C.POINTER(Adaptive), vp, vp, vp, vp, C.POINTER(u32)]
         L.pt_lightmap_light_sample.argtypes = [vp, C.c_int, u32, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.pt_baked_rays.argtypes = [vp, C.c_uint64, vp, vp, C.POINTER(BakedRaysParams), vp, vp]
+        L.pt_baked_rays_device.argtypes = [vp, C.c_uint64, vp, vp, C.POINTER(BakedRaysParams), vp, vp]
+        L.pt_bake_lightmap_gather.argtypes = [vp, C.POINTER(LightmapParams), C.POINTER(LightmapGather), vp, vp, vp]
+        L.pt_bake_lightmap_adaptive_gather.argtypes = [vp, C.POINTER(LightmapParams), C.POINTER(LightmapGather), C.POINTER(Adaptive), vp, vp, vp, vp, C.POINTER(u32)]
         L.pt_set_lightmap.argtypes = [vp, C.c_int, u32, u32, u32, vp]
         L.pt_get_lightmap_info.argtypes = [vp, C.c_int, u32, vp, vp]
         L.pt_lightmap_lookup.argtypes = [vp, C.c_int, u32, vp, vp, vp, vp, vp, vp]
@@ -1378,6 +1393,94 @@ class Renderer:
         out = np.zeros((len(self.local_rows()), self.cfg.width, 4), np.float32) if download else None
         self._chk(self.L.pt_render_baked(self.ctx, first_sample, n_samples, C.byref(prm), _p(out) if download else None))
         return out
+
+    # ---- baked rays and the final-gather bake
+    @staticmethod
+    def _baked_params(follow, unlit):
+        return BakedParams(follow, (C.c_float * 3)(*[float(x) for x in unlit]))
+
+    def baked_rays(self, o, d, follow: int = 0, unlit=(0.0, 0.0, 0.0), window_rays: int = 0):
+        """The baked view's chain for caller-supplied rays (pt_baked_rays): o, d (n, 3) float32 (d is used as given).  Returns (rgb (n, 3) the
+        baked sample B of every ray, hops (n,) uint32 the hop its chain ended at, id (n,) uint8 the first hit's id byte as integrate_rays
+        reports it).  With torch tensors on the GPU for o and d the rays are read in place and the results are GPU tensors: (rgbh (n, 4)
+        float32 with the hop in .w, id) (pt_baked_rays_device)."""
+        prm = BakedRaysParams(self._baked_params(follow, unlit), window_rays)
+        if type(o).__module__.startswith("torch"):
+            import torch
+            n = o.shape[0]
+            if not (o.is_cuda and d.is_cuda and o.is_contiguous() and d.is_contiguous()) or o.dtype != torch.float32 or d.dtype != torch.float32 or \
+                    o.numel() != 3 * n or d.numel() != 3 * n:
+                raise PtError(-1, "baked_rays: device rays are contiguous float32 GPU tensors of 3 values per ray")
+            rgbh = torch.zeros((n, 4), dtype=torch.float32, device=o.device); idb = torch.zeros(n, dtype=torch.uint8, device=o.device)
+            torch.cuda.synchronize(o.device)  # the library launches on its own stream
+            ptr = lambda t: C.c_void_p(t.data_ptr())
+            self._chk(self.L.pt_baked_rays_device(self.ctx, n, ptr(o), ptr(d), C.byref(prm), ptr(rgbh), ptr(idb)))
+            return rgbh, idb
+        o = np.ascontiguousarray(o, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(d, np.float32).reshape(-1, 3)
+        n = o.shape[0]
+        if d.shape[0] != n:
+            raise PtError(-1, "baked_rays: o and d do not describe the same number of rays")
+        rgbh = np.zeros((n, 4), np.float32); idb = np.zeros(n, np.uint8)
+        self._chk(self.L.pt_baked_rays(self.ctx, n, _p(o), _p(d), C.byref(prm), _p(rgbh), _p(idb)))
+        return np.ascontiguousarray(rgbh[:, :3]), rgbh[:, 3].astype(np.uint32), idb
+
+    def _gather(self, w, h, key_base, follow, unlit, direct, light_key_base):
+        lkb = 0 if not direct else key_base + w * h if light_key_base is None else light_key_base
+        return LightmapGather(self._baked_params(follow, unlit), int(bool(direct)), lkb)
+
+    def bake_lightmap_gather(self, model, instance, w, h, n_samples, first_sample=0, key_base=0, bias=0.0, sums=None, sumsq=None, follow=0,
+                             unlit=(0.0, 0.0, 0.0), direct=True, light_key_base=None, moments=False):
+        """The final-gather bake (pt_bake_lightmap_gather): bake_lightmap whose gather ray is one baked chain, baked_rays(.., follow, unlit) of
+        the texel's ray, ended in the maps, grid and probes set on this renderer; with direct the texel's light sample is added and a gather
+        ray whose first hit is a lamp counts zero, as bake_lightmap_direct (light_key_base likewise).  Sets nothing.  Returns (sums, coverage),
+        or with sumsq given (or moments=True) (sums, sumsq, coverage)."""
+        out = np.zeros((h, w, 3), np.float32) if sums is None else np.ascontiguousarray(sums, np.float32)
+        with_sq = moments or sumsq is not None
+        sq = None if not with_sq else np.zeros((h, w), np.float32) if sumsq is None else np.ascontiguousarray(sumsq, np.float32)
+        if out.size != w * h * 3 or (sq is not None and sq.size != w * h):
+            raise PtError(-1, "bake_lightmap_gather: sums holds 3 values per texel and sumsq one")
+        cov = np.zeros((h, w), np.uint8)
+        prm = LightmapParams(model, instance, w, h, first_sample, n_samples, key_base, bias)
+        g = self._gather(w, h, key_base, follow, unlit, direct, light_key_base)
+        self._chk(self.L.pt_bake_lightmap_gather(self.ctx, C.byref(prm), C.byref(g), _p(out), _p(sq), _p(cov)))
+        return (out.reshape(h, w, 3), sq.reshape(h, w), cov) if with_sq else (out.reshape(h, w, 3), cov)
+
+    def bake_lightmap_adaptive_gather(self, model, instance, w, h, n_samples, rel_error, abs_floor=0.0, min_samples=2, max_samples=0, key_base=0, bias=0.0,
+                                      sums=None, sumsq=None, counts=None, follow=0, unlit=(0.0, 0.0, 0.0), direct=True, light_key_base=None):
+        """One round of bake_lightmap_adaptive over bake_lightmap_gather's samples (pt_bake_lightmap_adaptive_gather); arguments and the five
+        return values as bake_lightmap_adaptive, the gather's as bake_lightmap_gather"""
+        out, sq, cn = self._lightmap_state("bake_lightmap_adaptive_gather", w, h, sums, sumsq, counts, copy=True)
+        cov = np.zeros((h, w), np.uint8)
+        n = C.c_uint32(0)
+        prm = LightmapParams(model, instance, w, h, 0, n_samples, key_base, bias)
+        g = self._gather(w, h, key_base, follow, unlit, direct, light_key_base)
+        crit = self._adaptive(rel_error, abs_floor, min_samples, max_samples)
+        self._chk(self.L.pt_bake_lightmap_adaptive_gather(self.ctx, C.byref(prm), C.byref(g), C.byref(crit), _p(out), _p(sq), _p(cn), _p(cov), C.byref(n)))
+        return out, sq, cn, cov, n.value
+
+    def bake_lightmaps_gather(self, placements, sizes, n_samples, iterations, key_bases=None, bias=0.0, follow=0, unlit=(0.0, 0.0, 0.0), direct=True,
+                              dilate=1):
+        """The Jacobi loop of the final gather over several placements: placements [(model, instance), ..], sizes [(w, h), ..], key_bases one
+        per placement (None: disjoint ranges of 2 * w * h keys from 0 on, the second half the light samples').  Each of `iterations` passes
+        bakes EVERY placement with bake_lightmap_gather from the maps currently set (pass 0: whatever is set), then divides by n_samples,
+        dilates `dilate` times and sets all of them.  The same keys every pass.  Returns one list per pass of (sums, coverage) per placement."""
+        if len(placements) != len(sizes):
+            raise PtError(-1, "bake_lightmaps_gather: one size per placement")
+        if key_bases is None:
+            key_bases, k = [], 0
+            for (w, h) in sizes:
+                key_bases.append(k)
+                k += 2 * w * h
+        passes = []
+        for _ in range(iterations):
+            baked = [self.bake_lightmap_gather(m, i, w, h, n_samples, key_base=kb, bias=bias, follow=follow, unlit=unlit, direct=direct)
+                     for (m, i), (w, h), kb in zip(placements, sizes, key_bases)]
+            for (m, i), (sums, cov) in zip(placements, baked):
+                mean = sums / np.float32(n_samples)
+                self.set_lightmap(m, i, self.dilate_lightmap(mean, cov, dilate)[0] if dilate else mean)
+            passes.append(baked)
+        return passes
 
     def read_baked(self):
         """the baked sums (sum r, sum g, sum b, n), local rows x width x 4"""

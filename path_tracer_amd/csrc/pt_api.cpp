@@ -1514,8 +1514,16 @@ uint32_t bake_chunk(const pt_ctx* c, uint32_t n_items, uint32_t n_samples, uint3
 }
 // with_id (pt_bake_lightmap_direct): the window's first-hit id bytes are kept as well, and fold takes them as a fifth argument; it is then the
 // place for whatever else the window needs between its integration and its fold
-template <class Fill, class Fold>
-int bake_rays(pt_ctx* c, Staging& st, uint32_t n_items, uint32_t n_samples, Fill&& fill, Fold&& fold, bool with_id = false)
+// integrate(cnt, o, d, key, batch_rays, rad, id) is what turns a table's rays into their radiance (and id bytes): the path tracer
+// (path_integrator) for every bake but the gather bakes, whose rays are baked chains (pt_bake_lightmap_gather)
+inline auto path_integrator(pt_ctx* c)
+{
+    return [c](uint32_t cnt, const float* o, const float* d, const uint2* key, uint32_t batch_rays, f4* rad, uint8_t* id) {
+        return integrate_rays_device(c, cnt, o, d, key, 1u, batch_rays, rad, nullptr, id);
+    };
+}
+template <class Integrate, class Fill, class Fold>
+int bake_rays(pt_ctx* c, Staging& st, uint32_t n_items, uint32_t n_samples, Integrate&& integrate, Fill&& fill, Fold&& fold, bool with_id = false)
 {
     const uint64_t total = (uint64_t)n_items * n_samples;
     uint32_t batch_rays;
@@ -1531,7 +1539,7 @@ int bake_rays(pt_ctx* c, Staging& st, uint32_t n_items, uint32_t n_samples, Fill
     {
         const uint32_t cnt = (uint32_t)std::min<uint64_t>(chunk, total - first);
         fill(first, cnt, d_o, d_d, d_key);
-        if ((r = integrate_rays_device(c, cnt, d_o, d_d, d_key, 1u, batch_rays, d_rad, nullptr, d_id))) return r;
+        if ((r = integrate(cnt, d_o, d_d, d_key, batch_rays, d_rad, d_id))) return r;
         if constexpr (std::is_invocable_v<Fold&, uint64_t, uint32_t, const float*, const f4*, const uint8_t*>)
         {
             if ((r = fold(first, cnt, d_d, d_rad, d_id))) return r;
@@ -3192,11 +3200,60 @@ int follow_params(pt_ctx* c, const pt_guide_params* gp, const char* who)
     if (gp->reserved[0] || gp->reserved[1] || gp->reserved[2]) return fail(c, PT_ERR_ARG, std::string(who) + ": the reserved words must be 0");
     return PT_OK;
 }
-// the chains of `sample` of every local pixel, hop by hop (enqueued, not waited for): trace the queue, then k_guide_follow, which ends
-// chains into the guides (sum null) or into the mean-albedo sums and queues the others' next rays into the other hook queue.  That
-// queue's count stays on the device, in the head word the next trace reads; a hop nobody reached is two empty launches.  No chain goes
-// on from the last hop, so that launch gets no next queue (max_hops 0, the first-hit guides, never has one).
+// pt_baked_params as pt_render_baked, pt_baked_rays and the gather bakes take it
+int baked_params_check(pt_ctx* c, const pt_baked_params* p, const char* who)
+{
+    if (!p) return fail(c, PT_ERR_ARG, std::string(who) + ": params must not be NULL");
+    if (p->max_hops > 8u) return fail(c, PT_ERR_ARG, std::string(who) + ": max_hops is at most 8");
+    if (p->reserved[0] || p->reserved[1] || p->reserved[2] || p->reserved[3]) return fail(c, PT_ERR_ARG, std::string(who) + ": the reserved words must be 0");
+    for (int k = 0; k < 3; ++k)
+        if (!(p->unlit[k] >= 0.0f) || !std::isfinite(p->unlit[k])) return fail(c, PT_ERR_ARG, std::string(who) + ": unlit must be finite and not negative");
+    return PT_OK;
+}
+// What the hop loop runs on, whoever owns it: the two hook queues it alternates between with their count and claim words, the hits and the
+// per-slot-owner state, for `cap` rays at hop 0 (q[1], head[1] and state may be null at max_hops 0)
+constexpr size_t kHookHeadBytes = ((size_t)32 + kHeadWordsPerQueue) * 4;
+struct ChainScratch
+{
+    RayQueue q[2];
+    uint32_t* head[2];
+    f4 *hits, *state;
+    uint32_t cap;
+};
+// ... and the loop itself, from hop 0's hits on: q[0] holds the cap rays of hop 0, head[0] their count, hits their closest hits.  Hop by hop
+// (enqueued, not waited for): the ending's launch, which ends chains and queues the others' next rays into the other hook queue, then the trace
+// of that queue.  Its count stays on the device, in the head word the next trace reads; a hop nobody reached is two empty launches.  No chain
+// goes on from the last hop, so that launch gets no next queue (max_hops 0 never has one).
 // (ending(q): the launch that ends or continues the chains of hop q.hop; q holds the hop's queues, hits, count words, state and hop numbers)
+template <class Ending>
+int walk_hops(pt_ctx* c, const ChainScratch& s, uint32_t max_hops, Ending&& ending)
+{
+    // (an empty world: every chain ends at hop 0 as a miss)
+    const uint32_t last = c->sv.world_root == MISS_ID ? 0u : max_hops;
+    for (uint32_t h = 0; h <= last; ++h)
+    {
+        const uint32_t cur = h & 1u, nxt = cur ^ 1u;
+        if (h) launch_trace_rays_closest(c->stream, trace_launch(c), c->sv.world_root, s.q[cur], s.cap, s.head[cur], s.hits);
+        ChainHop a{};
+        a.in = s.q[cur];
+        a.hits = s.hits;
+        a.n_in = s.head[cur];
+        if (h < last)
+        {
+            HIPCHK(c, hipMemsetAsync(s.head[nxt], 0, kHookHeadBytes, c->stream));
+            a.next = s.q[nxt];
+            a.n_next = s.head[nxt];
+        }
+        a.state = max_hops ? s.state : nullptr;
+        a.cap = s.cap;
+        a.hop = h;
+        a.max_hops = max_hops;
+        ending(a);
+    }
+    return PT_OK;
+}
+// the chains of `sample` of every local pixel over the context's own scratch: the camera rays traced (guide_trace), then the hop loop with
+// k_guide_follow, which ends chains into the guides (sum null) or into the mean-albedo sums, or with the baked view's ending
 template <class Ending>
 int walk_chains(pt_ctx* c, uint32_t sample, uint32_t max_hops, Ending&& ending)
 {
@@ -3204,29 +3261,57 @@ int walk_chains(pt_ctx* c, uint32_t sample, uint32_t max_hops, Ending&& ending)
     c->hook_log.clear();
     const LaunchLogScope logging(&c->hook_log);
     if ((r = guide_trace(c, sample))) return r; // hop 0: the camera rays, slot = local pixel
-    const RayQueue q[2] = {RayQueue{(f4*)c->d_gray_a.p, (f4*)c->d_gray_b.p}, RayQueue{(f4*)c->d_gray2_a.p, (f4*)c->d_gray2_b.p}};
-    uint32_t* const head[2] = {(uint32_t*)c->d_ghead.p, (uint32_t*)c->d_ghead2.p};
-    // (an empty world: every chain ends at hop 0 as a miss)
-    const uint32_t last = c->sv.world_root == MISS_ID ? 0u : max_hops;
-    for (uint32_t h = 0; h <= last; ++h)
+    const ChainScratch s{{RayQueue{(f4*)c->d_gray_a.p, (f4*)c->d_gray_b.p}, RayQueue{(f4*)c->d_gray2_a.p, (f4*)c->d_gray2_b.p}},
+                         {(uint32_t*)c->d_ghead.p, (uint32_t*)c->d_ghead2.p},
+                         (f4*)c->d_ghits.p,
+                         (f4*)c->d_gstate.p,
+                         c->local_pixels};
+    return walk_hops(c, s, max_hops, ending);
+}
+// The window walk (pt_baked_rays, the gather bakes): the same hop loop over rays [0, n) of a device table (o, d: 3 floats per ray), `window`
+// rays at a time through scratch `w` that holds so many (in buffers of the call, never the context's: local_pixels has no say here).  The
+// queue's "pixel" word is the ray's index in its window; out and id (either may be null) are indexed like the table.  Enqueued, not waited for.
+int ray_window_alloc(Staging& st, uint32_t cap, uint32_t max_hops, ChainScratch& w)
+{
+    w = ChainScratch{};
+    w.cap = cap;
+    w.q[0] = RayQueue{st.out<f4>(cap), st.out<f4>(cap)};
+    w.hits = st.out<f4>(cap);
+    w.head[0] = st.out<uint32_t>(kHookHeadBytes / 4);
+    if (max_hops)
     {
-        const uint32_t cur = h & 1u, nxt = cur ^ 1u;
-        if (h) launch_trace_rays_closest(c->stream, trace_launch(c), c->sv.world_root, q[cur], c->local_pixels, head[cur], (f4*)c->d_ghits.p);
-        ChainHop a{};
-        a.in = q[cur];
-        a.hits = (const f4*)c->d_ghits.p;
-        a.n_in = head[cur];
-        if (h < last)
-        {
-            HIPCHK(c, hipMemsetAsync(head[nxt], 0, c->d_ghead.bytes, c->stream));
-            a.next = q[nxt];
-            a.n_next = head[nxt];
-        }
-        a.state = max_hops ? (f4*)c->d_gstate.p : nullptr;
-        a.cap = c->local_pixels;
-        a.hop = h;
-        a.max_hops = max_hops;
-        ending(a);
+        w.q[1] = RayQueue{st.out<f4>(cap), st.out<f4>(cap)};
+        w.state = st.out<f4>(cap);
+        w.head[1] = st.out<uint32_t>(kHookHeadBytes / 4);
+    }
+    return st.err;
+}
+constexpr uint32_t kBakedRayWindow = 1u << 20; // rays per window where the caller names none: four launches' worth of a full device, 96 MiB of scratch
+int baked_ray_chains(pt_ctx* c, const ChainScratch& w, uint64_t n, const float* o, const float* d, const pt_baked_params& p, const BakedLight& light,
+                     const BakedKey& key, f4* out, uint8_t* id)
+{
+    EnvView env{};
+    if (c->env_w) env = EnvView{(const f4*)c->d_env.p, c->env_w, c->env_h, 0u, 0u};
+    const LaunchLogScope logging(&c->hook_log);
+    int r;
+    for (uint64_t first = 0; first < n; first += w.cap)
+    {
+        ChainScratch s = w;
+        s.cap = (uint32_t)std::min<uint64_t>(w.cap, n - first);
+        HIPCHK(c, hipMemsetAsync(s.head[0], 0, kHookHeadBytes, c->stream));
+        launch_rays_to_queue(c->stream, s.cap, o + 3 * first, d + 3 * first, s.q[0], s.head[0]);
+        if (c->sv.world_root == MISS_ID) HIPCHK(c, hipMemsetAsync(s.hits, 0xff, (size_t)s.cap * 16, c->stream));
+        else launch_trace_rays_closest(c->stream, trace_launch(c), c->sv.world_root, s.q[0], s.cap, s.head[0], s.hits);
+        if ((r = walk_hops(c, s, p.max_hops, [&](const ChainHop& q) {
+                 BakedRayArgs b{};
+                 static_cast<ChainHop&>(b) = q;
+                 b.out = out ? out + first : nullptr;
+                 b.id = id ? id + first : nullptr;
+                 b.env = env;
+                 std::memcpy(b.unlit, p.unlit, sizeof(b.unlit));
+                 launch_baked_rays(c->stream, c->sv, c->tex, light, key, b);
+             })))
+            return r;
     }
     return PT_OK;
 }
@@ -3650,7 +3735,7 @@ int pt_bake_probes(pt_ctx* c, uint32_t n_probes, const float* position, const pt
     const float* d_position = st.in<float>(position, 3 * (size_t)n_probes);
     float* d_sh = st.inout<float>(sh27, 27 * (size_t)n_probes);
     const ProbeBake pb{d_position, n_probes, p->first_sample, p->n_samples, p->key_base, c->cfg.n_sobol, c->cfg.seed};
-    if ((r = bake_rays(c, st, n_probes, p->n_samples,
+    if ((r = bake_rays(c, st, n_probes, p->n_samples, path_integrator(c),
                        [&](uint64_t first, uint32_t cnt, float* o, float* d, uint2* key) { launch_probe_rays(c->stream, pb, first, cnt, o, d, key); },
                        [&](uint64_t first, uint32_t cnt, const float* d, const f4* rad) { launch_probe_project(c->stream, pb, first, cnt, d, rad, d_sh); })))
         return r;
@@ -3793,13 +3878,61 @@ int direct_window_fold(pt_ctx* c, const Bake& lb, const DirectWindow& w, uint64_
     return PT_OK;
 }
 
+// ---- final-gather bakes (pt_bake_lightmap_gather): the gather ray is a baked chain (baked_ray_chains), ended in what the context holds
+// what a gather bake refuses on top of the plain one's checks, before any device call; dp, emissive: the direct bake's, for direct == 1
+int lightmap_gather_check(pt_ctx* c, const pt_lightmap_params* p, const pt_lightmap_gather* g, pt_lightmap_direct& dp, uint8_t emissive[256])
+{
+    if (!g) return fail(c, PT_ERR_ARG, "pt_bake_lightmap_gather: g must not be NULL");
+    int r;
+    if ((r = baked_params_check(c, &g->baked, "pt_bake_lightmap_gather"))) return r;
+    if (g->reserved[0] || g->reserved[1]) return fail(c, PT_ERR_ARG, "pt_lightmap_gather.reserved must be 0");
+    if (g->direct > 1u) return fail(c, PT_ERR_ARG, "pt_lightmap_gather.direct must be 0 or 1");
+    if (!g->direct && g->light_key_base) return fail(c, PT_ERR_ARG, "pt_lightmap_gather.light_key_base must be 0 when direct is 0");
+    dp = pt_lightmap_direct{g->light_key_base, {0u, 0u, 0u}};
+    if (g->direct) return lightmap_direct_check(c, p, &dp, emissive);
+    if (c->scene.flat.has_volumes) return fail(c, PT_ERR_STATE, "pt_bake_lightmap_gather: scenes with participating media are out of scope");
+    return PT_OK;
+}
+// A gather bake's integrator for bake_rays: what lights the chains' endings, decided once for the call, and the window walk's scratch for
+// windows of the wavefront batch's cut (pt_config.batch_spp moves it as it moves the path tracer's; 0: kBakedRayWindow)
+struct GatherWalk
+{
+    pt_ctx* c;
+    pt_baked_params baked;
+    BakedLight light;
+    BakedKey key;
+    ChainScratch w;
+    int ready(Staging& st, uint32_t n_items, uint32_t n_samples)
+    {
+        int r;
+        if ((r = ensure_environment(c)) || (r = baked_light(c, LIGHT_ALL, light, key))) return r;
+        uint32_t batch_rays;
+        const uint32_t chunk = bake_chunk(c, n_items, n_samples, &batch_rays);
+        c->hook_log.clear();
+        return ray_window_alloc(st, std::min(chunk, batch_rays ? std::min(batch_rays, kBakedRayWindow) : kBakedRayWindow), baked.max_hops, w);
+    }
+    int operator()(uint32_t cnt, const float* o, const float* d, const uint2*, uint32_t, f4* rad, uint8_t* id) const
+    {
+        c->stats.paths += cnt; // a gather ray is a path of the bake, as the path tracer's batches count theirs
+        return baked_ray_chains(c, w, cnt, o, d, baked, light, key, rad, id);
+    }
+};
+
 int bake_lightmap_locked(pt_ctx* c, const pt_lightmap_params* p, float* rgb_sum, float* sumsq, bool moments, uint8_t* coverage, float* dir_sum = nullptr,
-                         bool directional = false, const pt_lightmap_direct* dp = nullptr, bool direct = false)
+                         bool directional = false, const pt_lightmap_direct* dp = nullptr, bool direct = false, const pt_lightmap_gather* gp = nullptr,
+                         bool gather = false)
 {
     int r;
     if ((r = bake_lightmap_check(c, p, rgb_sum, sumsq, moments, dir_sum, directional))) return r;
     uint8_t emissive[256];
-    if (direct && (r = lightmap_direct_check(c, p, dp, emissive))) return r;
+    pt_lightmap_direct gather_dp;
+    if (gather)
+    {
+        if ((r = lightmap_gather_check(c, p, gp, gather_dp, emissive))) return r;
+        dp = &gather_dp;
+        direct = gp->direct != 0u;
+    }
+    else if (direct && (r = lightmap_direct_check(c, p, dp, emissive))) return r;
     const size_t px = (size_t)p->w * p->h;
     if ((r = upload_scene(c))) return r;
     const HostModel& m = c->scene.models[p->model];
@@ -3820,25 +3953,25 @@ int bake_lightmap_locked(pt_ctx* c, const pt_lightmap_params* p, float* rgb_sum,
         float* d_dir = directional ? st.inout<float>(dir_sum, 9 * px) : nullptr;
         float* d_sq = moments ? st.inout<float>(sumsq, px) : nullptr;
         const LightmapBake lb{d_texels, t.position, t.normal, n_cov, p->first_sample, p->n_samples, p->key_base, c->cfg.n_sobol, p->bias, c->cfg.seed};
-        if (direct)
+        const auto fill = [&](uint64_t first, uint32_t cnt, float* o, float* d, uint2* key) { launch_lightmap_rays(c->stream, lb, first, cnt, o, d, key); };
+        const auto fold = [&](uint64_t first, uint32_t cnt, const float* d, const f4* rad) {
+            if (directional) launch_lightmap_fold_directional(c->stream, lb, first, cnt, rad, d, d_sum, d_dir);
+            else launch_lightmap_fold(c->stream, lb, first, cnt, rad, d_sum, d_sq);
+        };
+        DirectWindow dw;
+        const auto fold_direct = [&](uint64_t first, uint32_t cnt, const float*, const f4* rad, const uint8_t* id) {
+            return direct_window_fold(c, lb, dw, first, cnt, rad, id, d_sum, d_sq);
+        };
+        uint32_t batch_rays;
+        if (direct && (r = direct_window_alloc(st, bake_chunk(c, n_cov, p->n_samples, &batch_rays), emissive, dp->light_key_base, dw))) return r;
+        if (gather)
         {
-            uint32_t batch_rays;
-            DirectWindow dw;
-            if ((r = direct_window_alloc(st, bake_chunk(c, n_cov, p->n_samples, &batch_rays), emissive, dp->light_key_base, dw))) return r;
-            if ((r = bake_rays(c, st, n_cov, p->n_samples,
-                               [&](uint64_t first, uint32_t cnt, float* o, float* d, uint2* key) { launch_lightmap_rays(c->stream, lb, first, cnt, o, d, key); },
-                               [&](uint64_t first, uint32_t cnt, const float*, const f4* rad, const uint8_t* id) {
-                                   return direct_window_fold(c, lb, dw, first, cnt, rad, id, d_sum, d_sq);
-                               },
-                               true)))
-                return r;
+            GatherWalk walk{c, gp->baked};
+            if ((r = walk.ready(st, n_cov, p->n_samples))) return r;
+            if ((r = direct ? bake_rays(c, st, n_cov, p->n_samples, walk, fill, fold_direct, true) : bake_rays(c, st, n_cov, p->n_samples, walk, fill, fold))) return r;
         }
-        else if ((r = bake_rays(c, st, n_cov, p->n_samples,
-                           [&](uint64_t first, uint32_t cnt, float* o, float* d, uint2* key) { launch_lightmap_rays(c->stream, lb, first, cnt, o, d, key); },
-                           [&](uint64_t first, uint32_t cnt, const float* d, const f4* rad) {
-                               if (directional) launch_lightmap_fold_directional(c->stream, lb, first, cnt, rad, d, d_sum, d_dir);
-                               else launch_lightmap_fold(c->stream, lb, first, cnt, rad, d_sum, d_sq);
-                           })))
+        else if ((r = direct ? bake_rays(c, st, n_cov, p->n_samples, path_integrator(c), fill, fold_direct, true)
+                             : bake_rays(c, st, n_cov, p->n_samples, path_integrator(c), fill, fold)))
             return r;
         if ((r = st.fetch())) return r;
     }
@@ -3889,7 +4022,8 @@ int lightmap_select_device(pt_ctx* c, Staging& st, const LightmapDev& t, size_t 
 }
 
 int bake_lightmap_adaptive_locked(pt_ctx* c, const pt_lightmap_params* p, const pt_adaptive* crit, float* rgb_sum, float* sumsq, uint32_t* counts,
-                                  uint8_t* coverage, uint32_t* n_active, const pt_lightmap_direct* dp = nullptr, bool direct = false)
+                                  uint8_t* coverage, uint32_t* n_active, const pt_lightmap_direct* dp = nullptr, bool direct = false,
+                                  const pt_lightmap_gather* gp = nullptr, bool gather = false)
 {
     int r;
     if ((r = bake_lightmap_check(c, p, rgb_sum, sumsq, true, nullptr, false))) return r;
@@ -3901,7 +4035,14 @@ int bake_lightmap_adaptive_locked(pt_ctx* c, const pt_lightmap_params* p, const 
     if ((r = lightmap_counts_over(c, m, p->w, p->h, counts, p->n_samples, &over))) return r;
     if (over) return fail(c, PT_ERR_LIMIT, "pt_bake_lightmap_adaptive: a covered texel's count + n_samples is above 2^24: f32 counts are not exact beyond");
     uint8_t emissive[256];
-    if (direct && (r = lightmap_direct_check(c, p, dp, emissive))) return r;
+    pt_lightmap_direct gather_dp;
+    if (gather)
+    {
+        if ((r = lightmap_gather_check(c, p, gp, gather_dp, emissive))) return r;
+        dp = &gather_dp;
+        direct = gp->direct != 0u;
+    }
+    else if (direct && (r = lightmap_direct_check(c, p, dp, emissive))) return r;
     const size_t px = (size_t)p->w * p->h;
     if ((r = upload_scene(c))) return r;
     Staging st(c);
@@ -3917,22 +4058,22 @@ int bake_lightmap_adaptive_locked(pt_ctx* c, const pt_lightmap_params* p, const 
     if (n > 0)
     {
         const LightmapAdaptiveBake lb{d_list, t.position, t.normal, n, p->n_samples, p->key_base, c->cfg.n_sobol, p->bias, c->cfg.seed};
-        if (direct)
+        const auto fill = [&](uint64_t first, uint32_t cnt, float* o, float* d, uint2* key) { launch_lightmap_rays(c->stream, lb, first, cnt, o, d, key); };
+        const auto fold = [&](uint64_t first, uint32_t cnt, const float*, const f4* rad) { launch_lightmap_fold(c->stream, lb, first, cnt, rad, d_sum, d_sq); };
+        DirectWindow dw;
+        const auto fold_direct = [&](uint64_t first, uint32_t cnt, const float*, const f4* rad, const uint8_t* id) {
+            return direct_window_fold(c, lb, dw, first, cnt, rad, id, d_sum, d_sq);
+        };
+        uint32_t batch_rays;
+        if (direct && (r = direct_window_alloc(st, bake_chunk(c, n, p->n_samples, &batch_rays), emissive, dp->light_key_base, dw))) return r;
+        if (gather)
         {
-            uint32_t batch_rays;
-            DirectWindow dw;
-            if ((r = direct_window_alloc(st, bake_chunk(c, n, p->n_samples, &batch_rays), emissive, dp->light_key_base, dw))) return r;
-            if ((r = bake_rays(c, st, n, p->n_samples,
-                               [&](uint64_t first, uint32_t cnt, float* o, float* d, uint2* key) { launch_lightmap_rays(c->stream, lb, first, cnt, o, d, key); },
-                               [&](uint64_t first, uint32_t cnt, const float*, const f4* rad, const uint8_t* id) {
-                                   return direct_window_fold(c, lb, dw, first, cnt, rad, id, d_sum, d_sq);
-                               },
-                               true)))
-                return r;
+            GatherWalk walk{c, gp->baked};
+            if ((r = walk.ready(st, n, p->n_samples))) return r;
+            if ((r = direct ? bake_rays(c, st, n, p->n_samples, walk, fill, fold_direct, true) : bake_rays(c, st, n, p->n_samples, walk, fill, fold))) return r;
         }
-        else if ((r = bake_rays(c, st, n, p->n_samples,
-                           [&](uint64_t first, uint32_t cnt, float* o, float* d, uint2* key) { launch_lightmap_rays(c->stream, lb, first, cnt, o, d, key); },
-                           [&](uint64_t first, uint32_t cnt, const float*, const f4* rad) { launch_lightmap_fold(c->stream, lb, first, cnt, rad, d_sum, d_sq); })))
+        else if ((r = direct ? bake_rays(c, st, n, p->n_samples, path_integrator(c), fill, fold_direct, true)
+                             : bake_rays(c, st, n, p->n_samples, path_integrator(c), fill, fold)))
             return r;
         launch_lightmap_advance(c->stream, d_list, n, p->n_samples, d_counts);
         st.expect(rgb_sum, d_sum, 3 * px);
@@ -4128,6 +4269,21 @@ int pt_bake_lightmap_adaptive_direct(pt_ctx* c, const pt_lightmap_params* p, con
     if (!c) return PT_ERR_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
     return bake_lightmap_adaptive_locked(c, p, crit, rgb_sum, sumsq, counts, coverage, n_active, dp, true);
+}
+
+int pt_bake_lightmap_gather(pt_ctx* c, const pt_lightmap_params* p, const pt_lightmap_gather* g, float* rgb_sum, float* sumsq, uint8_t* coverage)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    return bake_lightmap_locked(c, p, rgb_sum, sumsq, sumsq != nullptr, coverage, nullptr, false, nullptr, false, g, true);
+}
+
+int pt_bake_lightmap_adaptive_gather(pt_ctx* c, const pt_lightmap_params* p, const pt_lightmap_gather* g, const pt_adaptive* crit, float* rgb_sum, float* sumsq,
+                                     uint32_t* counts, uint8_t* coverage, uint32_t* n_active)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    return bake_lightmap_adaptive_locked(c, p, crit, rgb_sum, sumsq, counts, coverage, n_active, nullptr, false, g, true);
 }
 
 int pt_lightmap_light_sample(pt_ctx* c, int on_device, uint32_t n, const uint32_t* key, const uint32_t* sample, const float* origin, const float* normal,
@@ -4420,16 +4576,12 @@ int pt_render_baked(pt_ctx* c, uint32_t first_sample, uint32_t n_samples, const 
 {
     if (!c) return PT_ERR_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
-    if (!p) return fail(c, PT_ERR_ARG, "pt_render_baked: params must not be NULL");
-    if (p->max_hops > 8u) return fail(c, PT_ERR_ARG, "pt_render_baked: max_hops is at most 8");
-    if (p->reserved[0] || p->reserved[1] || p->reserved[2] || p->reserved[3]) return fail(c, PT_ERR_ARG, "pt_render_baked: the reserved words must be 0");
-    for (int k = 0; k < 3; ++k)
-        if (!(p->unlit[k] >= 0.0f) || !std::isfinite(p->unlit[k])) return fail(c, PT_ERR_ARG, "pt_render_baked: unlit must be finite and not negative");
+    int r;
+    if ((r = baked_params_check(c, p, "pt_render_baked"))) return r;
     if (n_samples == 0u) return fail(c, PT_ERR_ARG, "pt_render_baked: n_samples must be at least 1");
     if ((uint64_t)first_sample + n_samples > 0x100000000ull) return fail(c, PT_ERR_ARG, "pt_render_baked: first_sample + n_samples exceeds 2^32");
     if (!c->scene.built) return fail(c, PT_ERR_STATE, "pt_build has not been called");
     if (!c->scene.camera.set) return fail(c, PT_ERR_STATE, "pt_set_camera has not been called");
-    int r;
     BakedLight light;
     BakedKey key;
     if ((r = upload_scene(c)) || (r = ensure_environment(c)) || (r = baked_light(c, LIGHT_ALL, light, key))) return r;
@@ -4457,6 +4609,67 @@ int pt_render_baked(pt_ctx* c, uint32_t first_sample, uint32_t n_samples, const 
     c->baked_max_hops = p->max_hops;
     std::memcpy(c->baked_unlit, unlit, sizeof(unlit));
     return PT_OK;
+}
+
+// ---- baked rays: the baked view's chain for rays the caller supplies (the chains are baked_ray_chains')
+// what both variants refuse before any device call, in the header's order
+static int baked_rays_check(pt_ctx* c, uint64_t n, const float* o, const float* d, const pt_baked_rays_params* p)
+{
+    if (!p) return fail(c, PT_ERR_ARG, "pt_baked_rays: params must not be NULL");
+    int r;
+    if ((r = baked_params_check(c, &p->baked, "pt_baked_rays"))) return r;
+    if (p->reserved[0] || p->reserved[1] || p->reserved[2]) return fail(c, PT_ERR_ARG, "pt_baked_rays_params.reserved must be 0");
+    if (!c->scene.built) return fail(c, PT_ERR_STATE, "pt_build has not been called");
+    if (n > 0 && (!o || !d)) return fail(c, PT_ERR_ARG, "pt_baked_rays: o_xyz and d_xyz must not be NULL");
+    return PT_OK;
+}
+// ... and the call itself over device arrays (any output may be null); enqueued, then waited for by the caller's fetch or synchronise
+static int baked_rays_device(pt_ctx* c, Staging& st, uint64_t n, const float* o, const float* d, const pt_baked_rays_params* p, f4* out, uint8_t* id)
+{
+    int r;
+    BakedLight light;
+    BakedKey key;
+    if ((r = ensure_environment(c)) || (r = baked_light(c, LIGHT_ALL, light, key))) return r;
+    ChainScratch w;
+    const uint32_t window = (uint32_t)std::min<uint64_t>(n, p->window_rays ? p->window_rays : kBakedRayWindow);
+    if ((r = ray_window_alloc(st, window, p->baked.max_hops, w))) return r;
+    c->hook_log.clear();
+    return baked_ray_chains(c, w, n, o, d, p->baked, light, key, out, id);
+}
+
+int pt_baked_rays(pt_ctx* c, uint64_t n, const float* o, const float* d, const pt_baked_rays_params* p, float* rgbh, uint8_t* id)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    int r;
+    if ((r = baked_rays_check(c, n, o, d, p))) return r;
+    for (uint64_t i = 0; i < n; ++i)
+        for (int k = 0; k < 3; ++k)
+            if (!std::isfinite(o[3 * i + k]) || !std::isfinite(d[3 * i + k]))
+                return fail(c, PT_ERR_ARG, "pt_baked_rays: ray " + std::to_string(i) + " has a component of " + (std::isfinite(o[3 * i + k]) ? "d" : "o") + " that is not finite");
+    if (n == 0) return PT_OK;
+    if ((r = upload_scene(c))) return r;
+    Staging st(c);
+    const float* d_o = st.in<float>(o, 3 * n);
+    const float* d_d = st.in<float>(d, 3 * n);
+    f4* d_out = rgbh ? st.out<f4>(rgbh, n) : nullptr;
+    uint8_t* d_id = id ? st.out<uint8_t>(id, n) : nullptr;
+    if (st.err) return st.err;
+    if ((r = baked_rays_device(c, st, n, d_o, d_d, p, d_out, d_id))) return r;
+    return st.fetch();
+}
+
+int pt_baked_rays_device(pt_ctx* c, uint64_t n, const float* o, const float* d, const pt_baked_rays_params* p, float* rgbh, uint8_t* id)
+{
+    if (!c) return PT_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    int r;
+    if ((r = baked_rays_check(c, n, o, d, p))) return r;
+    if (n == 0) return PT_OK;
+    if ((r = upload_scene(c))) return r;
+    Staging st(c);
+    if ((r = baked_rays_device(c, st, n, o, d, p, (f4*)rgbh, id))) return r;
+    return st.fetch(); // the scratch is the call's: it is waited for before it is freed
 }
 
 int pt_read_baked(pt_ctx* c, float* rgbn)
@@ -4731,7 +4944,7 @@ int pt_bake_probe_radiance(pt_ctx* c, uint32_t n_probes, const float* position, 
     uint32_t* d_counts = st.inout<uint32_t>(counts, texels);
     const ProbeBake pb{d_position, n_probes, p->first_sample, p->n_samples, p->key_base, c->cfg.n_sobol, c->cfg.seed};
     const uint32_t res = p->res;
-    if ((r = bake_rays(c, st, n_probes, p->n_samples,
+    if ((r = bake_rays(c, st, n_probes, p->n_samples, path_integrator(c),
                        [&](uint64_t first, uint32_t cnt, float* o, float* d, uint2* key) { launch_probe_rays(c->stream, pb, first, cnt, o, d, key); },
                        [&](uint64_t first, uint32_t cnt, const float* d, const f4* rad) { launch_probe_radiance_fold(c->stream, pb, first, cnt, d, rad, res, d_sums, d_counts); })))
         return r;

@@ -403,6 +403,17 @@ struct BakedKey
     uint32_t grid, vis, spec, dir;
 };
 void launch_baked_follow(hipStream_t s, const SceneView& sv, const TexNView& tex, const BakedLight& light, const BakedKey& key, const BakedArgs& a);
+// pt_baked_rays and the gather bakes: the same chains over a window of caller rays (the queue's "pixel" word is the ray's index in the window,
+// state holds an entry per ray of it).  A chain that ends stores out[ray] = B | its hop; hop 0 writes id[ray], the first hit's id byte as
+// pt_integrate_rays reports it, for every ray of the window.  Either output may be null.  The ending's axes and views are the baked view's.
+struct BakedRayArgs : ChainHop
+{
+    f4* out;
+    uint8_t* id;
+    EnvView env;
+    float unlit[3];
+};
+void launch_baked_rays(hipStream_t s, const SceneView& sv, const TexNView& tex, const BakedLight& light, const BakedKey& key, const BakedRayArgs& a);
 // unit hook (pt_probe_grid_lookup): probe_grid_lookup (pt_probe.h) at n positions and normals (3 floats each), with visibility where depth is
 // not null
 void launch_probe_grid_lookup(hipStream_t s, const ProbeGridView& grid, const ProbeDepthView* depth, uint32_t n, const float* position, const float* normal, float* rgb,

@@ -2958,7 +2958,8 @@ __device__ __forceinline__ f3 surface_colour_at(const SceneView& sv, const TexVi
 // parked state, its next ray and the append to `next`.  The Ending says what a chain that stops here leaves: miss(first, slot, pixel, d)
 // for a ray that left the scene, surface(ChainEnd) for a surface the chain is not followed through (or the hop cap); both return a value
 // and store(pixel, value) puts it away at the hop's one tail.  (Endings that stored in miss() and in surface() themselves cost the probe
-// ending 28 registers and two waves per SIMD: profiles/r25_chain_hop.md.)
+// ending 28 registers and two waves per SIMD: profiles/r25_chain_hop.md.)  An ending with kFirstHit is also told, at hop 0, the hit id of every
+// slot: first_hit(pixel, id), before anything else is decided.
 struct ChainEnd // the surface a chain ends on
 {
     uint32_t slot, px, inst, tri, kind;
@@ -2998,6 +2999,7 @@ __device__ __forceinline__ void chain_hop(const SceneView& sv, const TexView& te
         const f3 d = xyz(rb);
         f3 out{};
         const uint32_t hid = asu(hit.w);
+        if constexpr (FIRST && Ending::kFirstHit) e.first_hit(px, hid); // every ray of the window, whatever becomes of its chain
         if (hid == MISS_ID) out = e.miss(FIRST, i, px, d);
         else
         {
@@ -3055,6 +3057,7 @@ struct GuideEnding
     const SceneView& sv;
     const FollowArgs& a;
     static constexpr bool kSumT = true; // position.w is the t of the whole chain
+    static constexpr bool kFirstHit = false;
     __device__ __forceinline__ f3 miss(bool first, uint32_t i, uint32_t px, const f3& d) const
     {
         if (!ACCUM)
@@ -3118,13 +3121,15 @@ constexpr bool baked_variant_ok(uint32_t grid, uint32_t vis, uint32_t spec, uint
 // ending must not spill, so with a grid the bounds leave 128; it takes 66 (seven waves per SIMD) and no scratch, and every DIR ending fits
 // under the same bounds (profiles/r30_baked_axes.md has the registers of all ten)
 constexpr int baked_min_blocks(bool grid, bool dir) { return grid || dir ? 4 : 8; }
-template <bool GRID, bool VIS, bool SPEC, bool DIR>
-struct BakedEnding
+// The value B of a chain that ends, stated once for the endings that differ in where B goes: the baked view's (BakedEnding, Args = BakedArgs:
+// added into the pixel's sums) and the baked rays' (BakedRayEnding, Args = BakedRayArgs: stored per ray).  Args has the hop's ChainHop, env and unlit.
+template <class Args, bool GRID, bool VIS, bool SPEC, bool DIR>
+struct BakedValue
 {
     const SceneView& sv;
     const TexNView& texn;
     const BakedLight& light; // a variant reads the views of its axes and no other
-    const BakedArgs& a;
+    const Args& a;
     // nothing here reads t, and carrying its sum through both barriers costs the probe ending's later hops a 67th register (the parent's 66 are
     // the bound: profiles/r25_chain_hop.md), so state[pixel].w holds one hop's t here
     static constexpr bool kSumT = false;
@@ -3183,17 +3188,46 @@ struct BakedEnding
         }
         return h.c * l;
     }
+};
+template <bool GRID, bool VIS, bool SPEC, bool DIR>
+struct BakedEnding : BakedValue<BakedArgs, GRID, VIS, SPEC, DIR>
+{
+    static constexpr bool kFirstHit = false;
     __device__ __forceinline__ void store(uint32_t px, const f3& b) const
     {
-        const f4 s = a.sum[px];
-        a.sum[px] = f4{s.x + b.x, s.y + b.y, s.z + b.z, s.w + 1.0f};
+        const f4 s = this->a.sum[px];
+        this->a.sum[px] = f4{s.x + b.x, s.y + b.y, s.z + b.z, s.w + 1.0f};
     }
 };
 template <bool FIRST, bool GRID, bool VIS, bool SPEC, bool DIR>
 __global__ void __launch_bounds__(256, baked_min_blocks(GRID, DIR)) k_baked_follow(const SceneView sv, const TexNView tex, const BakedLight light, const BakedArgs a)
 {
     static_assert(baked_variant_ok(GRID, VIS, SPEC, DIR), "no such ending");
-    chain_hop<FIRST>(sv, tex, a, BakedEnding<GRID, VIS, SPEC, DIR>{sv, tex, light, a});
+    chain_hop<FIRST>(sv, tex, a, BakedEnding<GRID, VIS, SPEC, DIR>{{sv, tex, light, a}});
+}
+// ---- baked rays (pt_baked_rays, the gather of pt_bake_lightmap_gather): the baked view's chains over a window of caller rays, the queue's
+// "pixel" word being the ray's index in the window.  The value is BakedValue's; a chain that ends STORES out[ray] = B | its hop, with no
+// arithmetic on B, and hop 0 writes the id byte of every ray of the window: the low byte of the first hit's model (BLAS) index as the path
+// tracer's first_id keeps it, 255 for a miss.  Either output may be null.  The bounds are k_baked_follow's: the ending's registers are the
+// same functions' and the tail is a store where the view's is a load, four adds and a store (profiles/r35_lightmap_gather.md has the report).
+template <bool GRID, bool VIS, bool SPEC, bool DIR>
+struct BakedRayEnding : BakedValue<BakedRayArgs, GRID, VIS, SPEC, DIR>
+{
+    static constexpr bool kFirstHit = true;
+    __device__ __forceinline__ void first_hit(uint32_t ray, uint32_t hid) const
+    {
+        if (this->a.id) this->a.id[ray] = hid == MISS_ID ? (uint8_t)255u : (uint8_t)(this->sv.instances[hid >> this->sv.prim_bits].blas & 0xffu);
+    }
+    __device__ __forceinline__ void store(uint32_t ray, const f3& b) const
+    {
+        if (this->a.out) this->a.out[ray] = f4{b.x, b.y, b.z, (float)this->a.hop};
+    }
+};
+template <bool FIRST, bool GRID, bool VIS, bool SPEC, bool DIR>
+__global__ void __launch_bounds__(256, baked_min_blocks(GRID, DIR)) k_baked_rays(const SceneView sv, const TexNView tex, const BakedLight light, const BakedRayArgs a)
+{
+    static_assert(baked_variant_ok(GRID, VIS, SPEC, DIR), "no such ending");
+    chain_hop<FIRST>(sv, tex, a, BakedRayEnding<GRID, VIS, SPEC, DIR>{{sv, tex, light, a}});
 }
 // unit hook of the directional lookup: rgb, mapped = lightmap_at_directional with delta = n' - n of the hit under the ray direction dir
 __global__ void __launch_bounds__(256) k_lightmap_lookup_directional(const SceneView sv, const TexNView tex, const LmView lm, const LmDirView ld, const uint32_t n,
@@ -3829,6 +3863,24 @@ void launch_baked_follow(hipStream_t s, const SceneView& sv, const TexNView& tex
     if (!launched) // a missing kernel is an error, never a skipped pass
     {
         fprintf(stderr, "launch_baked_follow: no ending for grid %u, vis %u, spec %u, dir %u\n", key.grid, key.vis, key.spec, key.dir);
+        abort();
+    }
+}
+// ... and the same ten points with the rays' ending
+void launch_baked_rays(hipStream_t s, const SceneView& sv, const TexNView& tex, const BakedLight& light, const BakedKey& key, const BakedRayArgs& a)
+{
+    bool launched = false;
+    pick_axes_of(baked_axes{}, {key.grid, key.vis, key.spec, key.dir}, [&](auto grid, auto vis, auto spec, auto dir) {
+        if constexpr (baked_variant_ok(grid, vis, spec, dir))
+        {
+            launched = true;
+            launch_chain_hop(s, a, k_baked_rays<true, grid != 0u, vis != 0u, spec != 0u, dir != 0u>, k_baked_rays<false, grid != 0u, vis != 0u, spec != 0u, dir != 0u>, sv, tex,
+                             light, a);
+        }
+    });
+    if (!launched)
+    {
+        fprintf(stderr, "launch_baked_rays: no ending for grid %u, vis %u, spec %u, dir %u\n", key.grid, key.vis, key.spec, key.dir);
         abort();
     }
 }

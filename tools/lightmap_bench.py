@@ -33,7 +33,16 @@ over covered texels against a 4096-sample PLAIN bake of other samples (key_base 
 0.1 and 0.2 with the rays each spent, beside a uniform direct bake of the plain adaptive bake's budget; and the residual of a 4096-sample
 direct bake of yet other samples, which is clamp and estimator differences.  COST: the direct and the plain bake at SIZE x SIZE x SPP,
 alternating, every time kept (--only-cost with --reps 1 is the run for rocprofv3 --kernel-trace --stats: the light-sample kernel, the any-hit
-launch and the fold are kernels of their own)."""
+launch and the fold are kernels of their own).
+
+    python tools/lightmap_bench.py --gather [--size 1024] [--spp 64] [--reps 5] [--passes 8] [--only-cost] [--out report.json]
+
+measures the final-gather bake (pt_bake_lightmap_gather, profiles/r35_lightmap_gather.md).  COST: one gather pass with direct = 1 beside the
+direct bake at SIZE x SIZE x SPP, alternating, every time kept; the box's own map (a direct bake's dilated means) is set, so the gather
+chains that reach it end in a lookup (--only-cost with --reps 1 is the run for rocprofv3 --kernel-trace --stats).  NOISE, in the tests' lit
+room, where every surface but the lamp is mapped, on 48 x 32 maps: RMSE over the room map's covered texels against a 4096-sample direct bake
+of other samples, of every pass of the Jacobi loop (bake_lightmaps_gather from no maps, PASSES passes) at 4, 16 and 64 samples, beside the
+direct bake's at the same counts: early passes lack their later bounces, late ones show the estimator's noise and the maps' own bias."""
 import argparse
 import json
 import os
@@ -221,8 +230,51 @@ def direct_report(r, model, size, spp, reps, only_cost):
     return report
 
 
+def gather_report(r, api, model, size, spp, reps, passes, only_cost):
+    f32 = np.float32
+    report = {"size": size, "spp": spp, "direct_ms": [], "gather_ms": []}
+    sums, cov = r.bake_lightmap_direct(model, 0, size, size, 4, bias=BIAS)
+    r.set_lightmap(model, 0, r.dilate_lightmap(sums / f32(4), cov, 1)[0])
+    for _ in range(2):                  # warm-up at the timed shape
+        r.bake_lightmap_direct(model, 0, size, size, spp, bias=BIAS)
+        r.bake_lightmap_gather(model, 0, size, size, spp, bias=BIAS, follow=2)
+    for _ in range(reps):               # the two routes alternate, so that a drift of the shared machine touches both
+        t0 = time.perf_counter()
+        direct = r.bake_lightmap_direct(model, 0, size, size, spp, bias=BIAS)
+        report["direct_ms"].append(1e3 * (time.perf_counter() - t0))
+        t0 = time.perf_counter()
+        gather = r.bake_lightmap_gather(model, 0, size, size, spp, bias=BIAS, follow=2)
+        report["gather_ms"].append(1e3 * (time.perf_counter() - t0))
+    covered = direct[1] == 1
+    report["covered"] = int(covered.sum())
+    report["rays"] = report["covered"] * spp
+    for name in ("direct", "gather"):
+        t = report[name + "_ms"]
+        report[name + "_median_ms"], report[name + "_spread_ms"] = float(np.median(t)), [float(min(t)), float(max(t))]
+    report["mean_irradiance"] = {"direct": float(np.pi * direct[0][covered].mean() / spp), "gather_one_pass": float(np.pi * gather[0][covered].mean() / spp)}
+    if only_cost:
+        return report
+    import baked_common as BC
+    sc, placements = BC.lit_room()
+    lit = api.Renderer(sc, 48, 32, max_bounces=DEPTH)
+    w, h = 48, 32
+    ref, cov = lit.bake_lightmap_direct(0, 0, w, h, 4096, key_base=1 << 24, bias=BIAS)
+    ref = ref / f32(4096)
+    covered = cov == 1
+    report["noise"] = {"covered": int(covered.sum()), "passes": passes, "rmse": {}}
+    for n in (4, 16, 64):
+        d, _ = lit.bake_lightmap_direct(0, 0, w, h, n, bias=BIAS)
+        for p in placements:
+            lit.set_lightmap(*p, None)
+        per_pass = lit.bake_lightmaps_gather(placements, [(w, h)] * len(placements), n, passes, bias=BIAS)
+        report["noise"]["rmse"][str(n)] = {"direct": rmse(d / f32(n), ref, covered), "gather_per_pass": [rmse(q[0][0] / f32(n), ref, covered) for q in per_pass]}
+    return report
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--gather", action="store_true")
+    ap.add_argument("--passes", type=int, default=8)
     ap.add_argument("--direct", action="store_true")
     ap.add_argument("--only-cost", action="store_true")
     ap.add_argument("--denoise", action="store_true")
@@ -244,8 +296,9 @@ def main():
     sc, model = LC.cornell_atlas_scene(args.model, W, H)
     r = api.Renderer(sc, W, H, max_bounces=DEPTH)
     size, spp = args.size, args.spp
-    if args.denoise or args.adaptive or args.direct:
-        line = json.dumps(direct_report(r, model, size, spp, args.reps, args.only_cost) if args.direct
+    if args.denoise or args.adaptive or args.direct or args.gather:
+        line = json.dumps(gather_report(r, api, model, size, spp, args.reps, args.passes, args.only_cost) if args.gather
+                          else direct_report(r, model, size, spp, args.reps, args.only_cost) if args.direct
                           else adaptive_report(r, model, size, spp, args.reps, args.rel, args.cap) if args.adaptive else denoise_report(r, model, size, args.reps))
         print(line)
         if args.out:
